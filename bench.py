@@ -20,12 +20,17 @@ N > 1 (one process per GPU, RCCL via torch.distributed):
       processes its slab, all-gathers a 10-double record (scatter partials + counts)
       over RCCL and solves the merged 3x3.  scaling = strong.
 
-Prints ONE JSON line on rank 0.  Besides the contract's keys it carries
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline keys
+(metric, value, unit, ms_per_step, ... and config).  With --dump-outputs DIR it first writes the last timed step's
+outputs (frame result, valid cloud with its input rows, normals, voxel centroids) as DIR/<name>.npy.
+With --full the line also carries
+  roofline          the dominant kernel's exclusive duration (frames one at a time, a run of its own) against HBM
   per_frame         SURVEY par. 8(d) / BASELINE.md par. 3 protocol: ONE blocking gm_process_frame per frame, rows handed
                     over as a HOST buffer (H2D inside), median / p10 / p90 of >= 20 frames after 3 warm-ups; pageable and
                     page-locked input, with and without the /choppedCloud D2H, and device-resident rows (kernels only)
   stress_launch_literal   the reference's own launch value neighborRadius = 0.5 on the same 1 M frame (k ~ 5 100)
   cpu_config1       BASELINE configs[0]: 50 k points, r = 0.5, oracle f32_faithful on 1 thread and on all usable cores
+  (and cpu_baseline, whole_path_hbm and the other secondary rows: stage times, host input, lidar-shaped, sharded frame)
 `value` itself stays the whole-job rate with the rows resident in HBM (the round contract: a PCIe-inclusive rate
 is never `value`); `roofline.frac` uses the kernel's EXCLUSIVE duration (frames one at a time), the figure rocprofv3's
 kernel stats show, and the PMC numbers are read from profiles/r<tag>_* of the newest round that holds them.
@@ -75,6 +80,11 @@ def parse():
     ap.add_argument("--profile-tag", default=None, help="rNN prefix of the profiles/ files to quote (default: newest)")
     ap.add_argument("--group-points", type=int, default=10_000_000,
                     help="points of the sharded-frame row (gm_group, 4 ranks sharing this GPU: BASELINE configs[3] shape); 0: skip")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything besides the headline: roofline (with its exclusive-kernel frames), the secondary rows "
+                         "(--no-secondary) and the CPU baselines (--no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64)")
     return ap.parse_args()
 
 
@@ -162,6 +172,95 @@ def cpu_config1(threads):
             ts.append(time.perf_counter() - t0)
         out[name] = {"threads": int(nt), "median_ms": float(np.median(ts)) * 1e3, "points_per_s": 50000 / float(np.median(ts))}
     return out
+
+
+DUMP_MAX_ROWS = 1 << 20   # per-point arrays take 36 B a row (44 with a sample's index): at most 46 MB of the 64 MB a dump
+                          # may hold; a larger valid cloud is dumped as a fixed, seeded sample of this many rows
+
+
+def dump_outputs(out_dir, c, slot, res, ransac_on):
+    """What the timed path computed in its last step, as a caller of it receives it: the gm_wait_frame record and the
+    slot's bulky outputs (valid cloud with its input rows, normals, voxel centroids), one float32 / float64 .npy each."""
+    os.makedirs(out_dir, exist_ok=True)
+    xyz, rows = c.cropped_cloud(slot)
+    nrm = c.normals(slot)
+    vox, vcount = c.voxel_centroids(slot)
+    arrays = {"counts": np.array([res[k] for k in ("n_in", "n_cropped", "n_valid", "n_voxels")], dtype=np.float64),
+              "status_flags": np.array([res["status_flags"]], dtype=np.float64),
+              "eigenvalues": res["eigenvalues"], "eigenvectors": res["eigenvectors"], "center_axis": res["center_axis"],
+              "scatter6": res["scatter6"], "voxel_centroids": vox, "voxel_counts": vcount.astype(np.float64)}
+    if ransac_on:   # (the context fits the cylinder model only)
+        arrays.update(cylinder=res["cylinder"], cylinder_inliers=np.array([res["cylinder_inliers"]], dtype=np.float64),
+                      cylinder_axis_refit=res["cylinder_axis_refit"])
+    if len(xyz) > DUMP_MAX_ROWS:
+        pick = np.sort(np.random.default_rng(0).choice(len(xyz), DUMP_MAX_ROWS, replace=False))
+        xyz, rows, nrm = xyz[pick], rows[pick], nrm[pick]
+        arrays["sample_index"] = pick.astype(np.float64)
+    arrays.update(valid_xyz=xyz, valid_input_rows=rows.astype(np.float64), normals=nrm)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+
+
+def roofline_rows(args, n, radius, mode, value, results, k_ms_excl):
+    """--full: the dominant kernel against HBM (`roofline`) and the whole path's algorithmic bytes (`whole_path_hbm`)."""
+    # dominant kernel: the neighbourhood-normals kernel, HIP-event bracketed on the stream it runs on
+    # (gm_frame_result.normals_kernel_ms): in the timed region it shares the chip with the other frames in flight,
+    # the roofline uses its exclusive duration (what rocprofv3's kernel stats of this command show)
+    k_ms = float(np.mean([r["normals_kernel_ms"] for r in results])) if results else 0.0
+    n_crop = float(np.mean([r["n_cropped"] for r in results])) if results else 0.0
+    algo_bytes = 28.0 * n_crop                      # SURVEY par. 8d: normals = 12 N' read + 16 N' written
+    k_roof = k_ms_excl if k_ms_excl else k_ms
+    achieved = algo_bytes / (k_roof * 1e-3) / 1e9 if k_roof > 0 else 0.0
+    traffic, traffic_src = None, None
+    prof = profile_path("normals_pmc.json", args.profile_tag)
+    if prof and mode == "frames":
+        try:
+            with open(prof) as f:
+                pj = json.load(f)
+            if pj.get("points") == n and abs(pj.get("radius", 0) - radius) < 1e-9:
+                traffic, traffic_src = pj.get("hbm_bytes_per_launch"), os.path.relpath(prof, ROOT)
+        except Exception:
+            traffic = None
+    # the kernel's real bound is instruction issue (VALU + MFMA), not HBM: busy fractions from the committed PMC pass
+    # of the same workload; the live part is the instruction rate implied by that count and THIS run's duration
+    valu = None
+    vprof = profile_path("normals_valu_pmc.json", args.profile_tag)
+    if vprof and mode == "frames":
+        try:
+            with open(vprof) as f:
+                vj = json.load(f)
+            insts = float(vj["counters"]["SQ_INSTS_VALU"])
+            valu = {"valu_busy_frac_pmc": vj["derived"]["valu_busy_frac"], "SQ_INSTS_VALU_per_launch": insts,
+                    "wave_instr_per_s": insts / (k_roof * 1e-3) if k_roof else None,
+                    "peak_wave_instr_per_s_packed": 1024 * 2.4e9 / 4.0,
+                    "mfma_busy_frac_pmc": vj["derived"].get("mfma_busy_frac"),
+                    "source": os.path.relpath(vprof, ROOT)}
+            # the matrix-core side of the same kernel: v_mfma_f32_32x32x16_bf16 = 2 * 32 * 32 * 16 flops per wave instruction
+            mf = vj["counters"].get("SQ_INSTS_MFMA")
+            if mf and k_roof:
+                tf = float(mf) * 32768.0 / (k_roof * 1e-3) / 1e12
+                valu["mfma"] = {"SQ_INSTS_MFMA_per_launch": float(mf), "achieved_TFLOPs_bf16": tf, "peak_TFLOPs_bf16_dense": 2500.0,
+                                "frac": tf / 2500.0,
+                                "note": "exact bf16 splits (3 terms per fp32 value) and 0/1 weights: flops of the formulation, "
+                                        "not of an fp32 GEMM; the kernel is bound by the VALU work that feeds the products"}
+        except Exception:
+            valu = None
+    return {
+        "roofline": {"kernel": "k_normals",
+                     "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                     "avg_launch_ms": k_roof, "avg_launch_ms_in_pipeline": k_ms,
+                     "algorithmic_bytes_per_launch": algo_bytes, "issue": valu,
+                     "note": "compute-bound neighbour loop (k~256; distances and moments on the matrix cores, near-threshold pairs re-evaluated exactly on the VALU): the HBM "
+                             "fraction is reported as the contract asks, DESIGN.md par. 4 holds its issue-rate roofline. "
+                             "avg_launch_ms = hipEvent bracket with frames one at a time (= rocprofv3 kernel stats of this "
+                             "command); avg_launch_ms_in_pipeline = the same bracket inside the timed region, where the "
+                             "kernel shares the chip with the other frames in flight"},
+        "whole_path_hbm": {"algorithmic_bytes_per_point": ALGO_BYTES_PER_POINT,
+                           "achieved_GBs": value * ALGO_BYTES_PER_POINT / 1e9,
+                           "frac_of_spec": value * ALGO_BYTES_PER_POINT / 1e9 / HBM_PEAK_GBS},
+    }
 
 
 def main():
@@ -342,14 +441,17 @@ def main():
     dt, results = timed(ctx, clouds, n_slots)
     total_points = (n * args.steps * world) if mode == "frames" else (n * args.steps)
     value = total_points / dt
+    if args.dump_outputs and rank == 0:
+        # the last timed step ran on slot (steps - 1) % n_slots (run() above); nothing has run on that slot since
+        dump_outputs(args.dump_outputs, ctx, (args.steps - 1) % n_slots, results[-1], ransac_on)
 
     secondary = {}
     k_ms_excl = None
-    if mode == "frames":
+    if args.full and mode == "frames":
         # the dominant kernel with the chip to itself: frames one at a time, hipEvents on the slot's own stream
         ex = [ctx.process_frame(clouds[i % len(clouds)])["normals_kernel_ms"] for i in range(max(10, min(args.steps, 30)))]
         k_ms_excl = float(np.mean(ex[2:]))
-    if not args.no_secondary and world == 1:
+    if args.full and not args.no_secondary and world == 1:
         if ransac_on:  # the reference-faithful path alone (no extension work in the step)
             # (its shorter chain overlaps differently: measured with the step's number of slots and with one less)
             rows = {}
@@ -507,49 +609,6 @@ def main():
                 "note": "cut_ms = host: x histogram over the voxel lattice, edges, rows scattered into per-rank page-locked "
                         "buffers; device_ms = H2D + the four slabs' kernels one after the other on this one GPU + gather"}
 
-    # dominant kernel: the neighbourhood-normals kernel, HIP-event bracketed on the stream it runs on
-    # (gm_frame_result.normals_kernel_ms): in the timed region it shares the chip with the other frames in flight,
-    # the roofline uses its exclusive duration (what rocprofv3's kernel stats of this command show)
-    k_ms = float(np.mean([r["normals_kernel_ms"] for r in results])) if results else 0.0
-    n_crop = float(np.mean([r["n_cropped"] for r in results])) if results else 0.0
-    algo_bytes = 28.0 * n_crop                      # SURVEY par. 8d: normals = 12 N' read + 16 N' written
-    k_roof = k_ms_excl if k_ms_excl else k_ms
-    achieved = algo_bytes / (k_roof * 1e-3) / 1e9 if k_roof > 0 else 0.0
-    traffic, traffic_src = None, None
-    prof = profile_path("normals_pmc.json", args.profile_tag)
-    if prof and mode == "frames":
-        try:
-            with open(prof) as f:
-                pj = json.load(f)
-            if pj.get("points") == n and abs(pj.get("radius", 0) - radius) < 1e-9:
-                traffic, traffic_src = pj.get("hbm_bytes_per_launch"), os.path.relpath(prof, ROOT)
-        except Exception:
-            traffic = None
-    # the kernel's real bound is instruction issue (VALU + MFMA), not HBM: busy fractions from the committed PMC pass
-    # of the same workload; the live part is the instruction rate implied by that count and THIS run's duration
-    valu = None
-    vprof = profile_path("normals_valu_pmc.json", args.profile_tag)
-    if vprof and mode == "frames":
-        try:
-            with open(vprof) as f:
-                vj = json.load(f)
-            insts = float(vj["counters"]["SQ_INSTS_VALU"])
-            valu = {"valu_busy_frac_pmc": vj["derived"]["valu_busy_frac"], "SQ_INSTS_VALU_per_launch": insts,
-                    "wave_instr_per_s": insts / (k_roof * 1e-3) if k_roof else None,
-                    "peak_wave_instr_per_s_packed": 1024 * 2.4e9 / 4.0,
-                    "mfma_busy_frac_pmc": vj["derived"].get("mfma_busy_frac"),
-                    "source": os.path.relpath(vprof, ROOT)}
-            # the matrix-core side of the same kernel: v_mfma_f32_32x32x16_bf16 = 2 * 32 * 32 * 16 flops per wave instruction
-            mf = vj["counters"].get("SQ_INSTS_MFMA")
-            if mf and k_roof:
-                tf = float(mf) * 32768.0 / (k_roof * 1e-3) / 1e12
-                valu["mfma"] = {"SQ_INSTS_MFMA_per_launch": float(mf), "achieved_TFLOPs_bf16": tf, "peak_TFLOPs_bf16_dense": 2500.0,
-                                "frac": tf / 2500.0,
-                                "note": "exact bf16 splits (3 terms per fp32 value) and 0/1 weights: flops of the formulation, "
-                                        "not of an fp32 GEMM; the kernel is bound by the VALU work that feeds the products"}
-        except Exception:
-            valu = None
-
     if rank == 0:
         out = {
             "metric": "points/sec full segment+fit, 1M-pt synthetic tunnel frame",
@@ -564,24 +623,13 @@ def main():
                        "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES"),
                        "ransac_model": "cylinder, H=1024, tau=0.03 (extension)" if ransac_on else "none (reference-faithful path)",
                        "parallelism": f"{mode}x{world}", "collective_backend": args.dist_backend if world > 1 else None},
-            "roofline": {"kernel": "k_normals",
-                         "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "avg_launch_ms": k_roof, "avg_launch_ms_in_pipeline": k_ms,
-                         "algorithmic_bytes_per_launch": algo_bytes, "issue": valu,
-                         "note": "compute-bound neighbour loop (k~256; distances and moments on the matrix cores, near-threshold pairs re-evaluated exactly on the VALU): the HBM "
-                                 "fraction is reported as the contract asks, DESIGN.md par. 4 holds its issue-rate roofline. "
-                                 "avg_launch_ms = hipEvent bracket with frames one at a time (= rocprofv3 kernel stats of this "
-                                 "command); avg_launch_ms_in_pipeline = the same bracket inside the timed region, where the "
-                                 "kernel shares the chip with the other frames in flight"},
-            "whole_path_hbm": {"algorithmic_bytes_per_point": ALGO_BYTES_PER_POINT,
-                               "achieved_GBs": value * ALGO_BYTES_PER_POINT / 1e9,
-                               "frac_of_spec": value * ALGO_BYTES_PER_POINT / 1e9 / HBM_PEAK_GBS},
         }
-        out.update(secondary)
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(n, radius, args.cpu_threads)
-            out["cpu_config1"] = cpu_config1(args.cpu_threads)
+        if args.full:
+            out.update(roofline_rows(args, n, radius, mode, value, results, k_ms_excl))
+            out.update(secondary)
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(n, radius, args.cpu_threads)
+                out["cpu_config1"] = cpu_config1(args.cpu_threads)
         print(json.dumps(out))
     ctx.close()
     if world > 1:

@@ -124,7 +124,7 @@ def test_config3_10m_frame_over_four_ranks(gm):
 
 
 def test_bench_line_keeps_its_contract():
-    """`python bench.py` as the driver runs it at N = 1 (a child process; fewer steps and a smaller frame so that the test
+    """`python bench.py --full` as the driver runs it at N = 1 (a child process; fewer steps and a smaller frame so that the test
     takes seconds): ONE JSON line on stdout whose keys, types and cross-checks are the round contract's -- BASELINE.json's
     metric and unit, steps / warmup echoed, whole-job value = points x steps / time, `roofline` with achieved / peak / frac
     consistent, `cpu_baseline` from the oracle, no model keys in `config`."""
@@ -132,7 +132,7 @@ def test_bench_line_keeps_its_contract():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     n, steps, warmup = 200_000, 6, 2
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--points", str(n),
-                          "--no-secondary", "--group-points", "0"], capture_output=True, text=True, timeout=600, cwd=root)
+                          "--full", "--no-secondary", "--group-points", "0"], capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines                                   # ONE line
@@ -152,3 +152,37 @@ def test_bench_line_keeps_its_contract():
     cb = d["cpu_baseline"]
     assert cb["kind"] in ("port", "reference") and cb["value"] > 0 and cb["cores"] >= 1 and cb["unit"] == d["unit"] and cb["sample"]
     assert d["value"] > cb["value"]                                  # (a GPU that loses to the CPU oracle is a broken build)
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `python bench.py` (no --full) prints the headline line only -- no roofline, secondary rows or CPU
+    baselines -- and --dump-outputs writes the last timed step's outputs as float32 / float64 .npy files that agree
+    with the frame record and with each other."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, steps, warmup = 200_000, 7, 2
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--points", str(n),
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == steps and d["warmup"] == warmup and d["unit"] == "points/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and abs(d["value"] - n / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    for k in ("roofline", "whole_path_hbm", "cpu_baseline", "cpu_config1", "per_frame", "stage_ms_one_frame_alone"):
+        assert k not in d, k
+    a = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert sum((tmp_path / f).stat().st_size for f in os.listdir(tmp_path)) <= 64 << 20
+    n_in, n_cropped, n_valid, n_voxels = a["counts"].astype(np.int64)
+    assert n_in == n and 0 < n_valid <= n_cropped <= n and n_voxels == len(a["voxel_centroids"]) > 0
+    assert a["valid_xyz"].shape == (n_valid, 3) and a["normals"].shape == (n_valid, 4)
+    rows = a["valid_input_rows"].astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and rows[-1] < n
+    # the step's frame is the input the timed loop fed last: (steps - 1) % distinct frames (5) of the synthetic stream
+    xyz = synth.tunnel_frame(n, seed=(steps - 1) % 5)
+    assert np.array_equal(a["valid_xyz"], xyz[rows])
+    assert a["voxel_counts"].sum() == n_valid
+    nrm = np.linalg.norm(a["normals"][:, :3].astype(np.float64), axis=1)
+    assert np.all(np.abs(nrm - 1) < 1e-3)
+    assert ang(a["center_axis"], a["eigenvectors"][:, 0]) < 1e-6

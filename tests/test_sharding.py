@@ -248,7 +248,7 @@ def test_bench_two_rank_rehearsal_on_one_gpu(mode):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-           "--points", "100000", "--mode", mode, "--dist-backend", "gloo", "--force-device", "0", "--no-cpu-baseline"]
+           "--points", "100000", "--mode", mode, "--dist-backend", "gloo", "--force-device", "0", "--full", "--no-cpu-baseline"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]

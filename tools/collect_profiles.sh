@@ -12,7 +12,7 @@ cd /tmp && export TMPDIR=/tmp
 # (bench.py asks for 8 hardware queues from inside Python, but rocprofv3's preloaded library has initialised the runtime by
 # then: the profiled runs get the same 8 queues only if the variable is in the environment before rocprofv3 starts)
 export GPU_MAX_HW_QUEUES=8
-ARGS="--steps 50 --warmup 5 --no-cpu-baseline $@"
+ARGS="--steps 50 --warmup 5 --full --no-cpu-baseline $@"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py $ARGS > $OUT/bench_trace.log 2>&1 || exit 1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -- python3 $ROOT/bench.py $ARGS > $OUT/bench_fetch.log 2>&1 || exit 2
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write -- python3 $ROOT/bench.py $ARGS > $OUT/bench_write.log 2>&1 || exit 3
