@@ -36,6 +36,7 @@ GM_CFG_RANSAC_CYLINDER = 1 << 3
 GM_CFG_STAGE_TIMING = 1 << 4
 GM_CFG_KEEP_COUNTS = 1 << 5
 GM_CFG_GRAPH = 1 << 6
+GM_CFG_CYLINDER_FIT = 1 << 7
 GM_CFG_DEFAULT = GM_CFG_VOXEL_GRID
 
 GM_CLOUD_DEVICE = 1 << 0
@@ -43,6 +44,14 @@ GM_CLOUD_BIGENDIAN = 1 << 1
 GM_CLOUD_PINNED = 1 << 2
 
 GM_RES_VOXEL_PASSTHROUGH = 1 << 0
+
+GM_FIT_OK = 0
+GM_FIT_NO_MODEL = 1
+GM_FIT_DEGENERATE = 2
+GM_FIT_SINGULAR = 3
+GM_FIT_FAILED_MASK = 0xFF
+GM_FIT_NOT_CONVERGED = 1 << 8
+GM_FIT_STEP_BOUND = 1e-2
 
 GM_N_STAGES = 9
 STAGE_NAMES = ("upload", "crop", "grid", "normals", "compact", "frame", "voxel", "ransac", "total")
@@ -70,6 +79,12 @@ class FrameResult(C.Structure):
                 ("plane", C.c_float * 4), ("cylinder", C.c_float * 7),
                 ("plane_refit", C.c_double * 4), ("cylinder_axis_refit", C.c_double * 3),
                 ("stage_ms", C.c_float * GM_N_STAGES), ("normals_kernel_ms", C.c_float)]
+
+
+class CylinderFit(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("status", C.c_uint32), ("inliers", C.c_uint32), ("passes", C.c_uint32),
+                ("point", C.c_double * 3), ("axis", C.c_double * 3), ("radius", C.c_double), ("rms", C.c_double),
+                ("last_step", C.c_double), ("model", C.c_float * 7)]
 
 
 class GmError(RuntimeError):
@@ -129,6 +144,7 @@ def load():
     vp, u32, u32p, fp, dp, i32p, u8p = (C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float),
                                          C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8))
     cfgp, cloudp, resp = C.POINTER(Config), C.POINTER(Cloud), C.POINTER(FrameResult)
+    fitp = C.POINTER(CylinderFit)
     proto = {
         "gm_create": (C.c_int, [cfgp, C.POINTER(vp)]),
         "gm_destroy": (None, [vp]),
@@ -167,6 +183,8 @@ def load():
         "gm_cylinder_hypotheses": (C.c_int, [vp, fp, fp, u32, u8p, u32, C.c_uint64, u32, fp]),
         "gm_segment_moments": (C.c_int, [vp, fp, fp, u8p, u32, u32, dp]),
         "gm_get_compressed_map": (C.c_int, [vp, u32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+        "gm_get_cylinder_fit": (C.c_int, [vp, u32, fitp]),
+        "gm_fit_cylinder": (C.c_int, [vp, fp, u32, u8p, u32, fp, C.c_double, fitp, u8p]),
         "gm_group_create": (C.c_int, [cfgp, i32p, u32, u32, C.POINTER(vp)]),
         "gm_group_destroy": (None, [vp]),
         "gm_group_size": (u32, [vp]),

@@ -16,10 +16,12 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (GM_CFG_DEFAULT, GM_CFG_KEEP_COUNTS, GM_CFG_STAGE_TIMING, GM_CFG_VOXEL_GRID, GM_CLOUD_BIGENDIAN,
-                   GM_CLOUD_DEVICE, GM_CLOUD_PINNED, GM_ERR_CAPACITY, GM_ERR_NOT_READY, GM_OK, Cloud, Config, FrameResult, GmError, STAGE_NAMES)
+from ._lib import (GM_CFG_CYLINDER_FIT, GM_CFG_DEFAULT, GM_CFG_KEEP_COUNTS, GM_CFG_STAGE_TIMING, GM_CFG_VOXEL_GRID,
+                   GM_CLOUD_BIGENDIAN, GM_CLOUD_DEVICE, GM_CLOUD_PINNED, GM_ERR_CAPACITY, GM_ERR_NOT_READY, GM_OK, Cloud, Config,
+                   CylinderFit, FrameResult, GmError, STAGE_NAMES)
 
-__all__ = ["GeometricMapping", "GeometricMappingGroup", "GmError", "solve_local_frame", "decode_compressed_map"]
+__all__ = ["GeometricMapping", "GeometricMappingGroup", "GmError", "solve_local_frame", "decode_compressed_map",
+           "GM_CFG_CYLINDER_FIT"]
 
 
 def _f32(a):
@@ -374,6 +376,36 @@ class GeometricMapping:
         return mom
 
 
+    # ---- cylinder regression (GM_CFG_CYLINDER_FIT; getCylinder, tunnel_processing.hpp:56-59) ----
+    @staticmethod
+    def _fit(f):
+        return dict(status=int(f.status), inliers=int(f.inliers), passes=int(f.passes),
+                    point=np.array(f.point[:]), axis=np.array(f.axis[:]), radius=float(f.radius), rms=float(f.rms),
+                    last_step=float(f.last_step), model=np.array(f.model[:], dtype=np.float32),
+                    ok=(int(f.status) & _lib.GM_FIT_FAILED_MASK) == 0,
+                    converged=(int(f.status) & _lib.GM_FIT_NOT_CONVERGED) == 0)
+
+    def cylinder_fit(self, slot=0):
+        """The least-squares cylinder of the slot's last frame (gm_get_cylinder_fit): dict with status, inliers, passes,
+        point, axis, radius, rms, last_step, model (the fp32 row the labels were decided with), ok, converged."""
+        f = CylinderFit()
+        self._check(self._L.gm_get_cylinder_fit(self._ctx, slot, C.byref(f)))
+        return self._fit(f)
+
+    def getCylinder(self, cloud, init7, tau, labels=None, want=0):
+        """tunnel_processing.hpp:56-59 (the reference's empty regression stub) as one stage call (gm_fit_cylinder):
+        points with labels == want (all when labels is None), starting row init7 (point, direction, radius).
+        Returns (fit dict as cylinder_fit, boolean inlier mask [n])."""
+        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+        init = np.ascontiguousarray(np.asarray(init7, dtype=np.float32).reshape(7))
+        lab, lp = self._u8(labels)
+        mask = np.zeros(max(len(xyz), 1), dtype=np.uint8)
+        f = CylinderFit()
+        self._check(self._L.gm_fit_cylinder(self._ctx, _f32(xyz), len(xyz), lp, int(want), _f32(init), float(tau),
+                                            C.byref(f), mask.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return self._fit(f), mask[:len(xyz)].astype(bool)
+
+
 def decode_compressed_map(buf):
     """Parse gm_get_compressed_map bytes (gm_map_header / gm_map_primitive in include/gm_hip.h)."""
     buf = np.ascontiguousarray(buf, dtype=np.uint8)
@@ -517,6 +549,15 @@ class GeometricMappingGroup:
         if st == GM_ERR_NOT_READY:
             return False
         self._check(st)
+
+    def cylinder_fit(self, rank, slot):
+        """The cylinder regression of a streamed frame (GM_CFG_CYLINDER_FIT): gm_get_cylinder_fit on the rank's context."""
+        ctx = self._L.gm_group_ctx(self._grp, rank)
+        f = CylinderFit()
+        st = self._L.gm_get_cylinder_fit(ctx, slot, C.byref(f))
+        if st != GM_OK:
+            raise GmError(st, self._L.gm_last_error(ctx).decode())
+        return GeometricMapping._fit(f)
 
     def rank_fetch(self, rank, slot, what):
         """Bulky output of a streamed frame: what in {"cropped_xyz", "normals", "voxel_centroids"} -> float32 [n,4]."""

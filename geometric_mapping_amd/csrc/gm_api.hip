@@ -562,6 +562,10 @@ void fill_result(gm_ctx *ctx, Slot &sl, gm_frame_result *r)
         for (int k = 0; k < 7; ++k) r->cylinder[k] = o.ext.cylinder[k];
         for (int k = 0; k < 3; ++k) r->cylinder_axis_refit[k] = o.ext.cyl_axis_refit[k];
     }
+    if (ctx->cfg.flags & GM_CFG_CYLINDER_FIT) {
+        sl.last_fit = o.fit;
+        sl.last_fit.struct_size = (uint32_t)sizeof(gm_cylinder_fit);
+    }
     float ms = 0;
     if (sl.n_in && sl.kernel_timed && hipEventElapsedTime(&ms, sl.ev_k0, sl.ev_k1) == hipSuccess) r->normals_kernel_ms = ms;
     if (ctx->cfg.flags & GM_CFG_STAGE_TIMING) {
@@ -652,9 +656,11 @@ gm_status gm_ensure_ext(gm_ctx *ctx, Slot &sl, uint32_t H)
     hipFree(sl.hyp_plane); hipFree(sl.hyp_cyl); hipFree(sl.band); hipFree(sl.score_partial); hipFree(sl.cnt_plane);
     hipFree(sl.cnt_cyl); hipFree(sl.best_plane); hipFree(sl.best_cyl); hipFree(sl.mom_partial); hipFree(sl.mom_plane);
     hipFree(sl.mom_cyl); hipFree(sl.nn_best); hipFree(sl.vox_nrm4);
+    hipFree(sl.fit_partial); hipFree(sl.fit_ticket); hipFree(sl.fit_work); hipFree(sl.fit_init); hipFree(sl.fit_stage);
     // (a failed allocation below must not leave dangling pointers for gm_destroy to free again)
     sl.hyp_plane = sl.hyp_cyl = nullptr; sl.band = nullptr; sl.score_partial = nullptr; sl.cnt_plane = sl.cnt_cyl = nullptr;
     sl.best_plane = sl.best_cyl = nullptr; sl.mom_partial = sl.mom_plane = sl.mom_cyl = nullptr; sl.nn_best = nullptr; sl.vox_nrm4 = nullptr;
+    sl.fit_partial = nullptr; sl.fit_ticket = nullptr; sl.fit_work = nullptr; sl.fit_init = nullptr; sl.fit_stage = nullptr;
     const uint32_t HH = H > sl.ext_H ? H : sl.ext_H;
     sl.ext_H = 0; sl.ext_cap = 0;
     GM_HIP(ctx, dmalloc(sl.hyp_plane, (size_t)HH * 8)); GM_HIP(ctx, dmalloc(sl.hyp_cyl, (size_t)HH * 8));
@@ -666,6 +672,9 @@ gm_status gm_ensure_ext(gm_ctx *ctx, Slot &sl, uint32_t H)
     GM_HIP(ctx, dmalloc(sl.mom_plane, 16)); GM_HIP(ctx, dmalloc(sl.mom_cyl, 16));
     GM_HIP(ctx, dmalloc(sl.nn_best, sl.cap));
     GM_HIP(ctx, dmalloc(sl.vox_nrm4, sl.cap));
+    GM_HIP(ctx, dmalloc(sl.fit_partial, (size_t)kFitBlocks * 24)); GM_HIP(ctx, dmalloc(sl.fit_ticket, 1));
+    GM_HIP(ctx, dmalloc(sl.fit_work, 1)); GM_HIP(ctx, dmalloc(sl.fit_init, 8)); GM_HIP(ctx, dmalloc(sl.fit_stage, 1));
+    GM_HIP(ctx, hipMemset(sl.fit_ticket, 0, sizeof(uint32_t)));   // the passes' last block resets it after every launch
     GM_HIP(ctx, hipMemset(sl.score_partial, 0, sizeof(uint32_t) * 4096));  // (holds the scoring launches' done-counter)
     GM_HIP(ctx, hipMemset(sl.best_plane, 0xFF, 8));
     GM_HIP(ctx, hipMemset(sl.best_cyl, 0xFF, 8));
@@ -708,6 +717,16 @@ gm_status gm_enqueue_ransac(gm_ctx *ctx, Slot &sl, uint32_t n_cap, uint32_t scat
         mom_rows = launch_label(1, sl.valid4, sl.labels, 0, 2, n_ptr, n_cap, sl.hyp_cyl, sl.band, sl.best_cyl,
                                 cf.ransac_threshold, first ? 1 : 0, fsel, fcnt, fk, s, sl.vnorm4, sl.mom_partial, fmask ? sl.inl_mask : nullptr, frep);
         first = false;
+        if (cf.flags & GM_CFG_CYLINDER_FIT) {   // regression of the winner; relabels the cylinder before the frame closes
+            CylFitArgs a;
+            a.pts = sl.valid4; a.labels = sl.labels; a.out = sl.labels;
+            a.want = 0; a.want2 = 2; a.mask_mode = 0;   // eligible: what the plane left (labels 0 and 2)
+            a.n_ptr = n_ptr; a.n_host = n_cap;
+            a.init = sl.hyp_cyl; a.best = sl.best_cyl;
+            a.work = sl.fit_work; a.fit = &sl.d_out->fit; a.partial = sl.fit_partial; a.ticket = sl.fit_ticket;
+            a.tau = cf.ransac_threshold;
+            launch_cylinder_fit(a, s);
+        }
     }
     // the label passes left the moments of their segments in sl.mom_partial (one row per block, the same grid for both
     // models); the finalizer reduces them
@@ -819,6 +838,8 @@ gm_status gm_create(const gm_config *cfg, gm_ctx **out)
         (cfg->ransac_hypotheses == 0 || cfg->ransac_hypotheses > kMaxHypotheses || !(cfg->ransac_threshold > 0.0) ||
          !std::isfinite(cfg->ransac_threshold)))
         return fail(nullptr, GM_ERR_INVALID_ARG, "gm_config: ransac_hypotheses must be in [1, 8192] and ransac_threshold > 0");
+    if ((cfg->flags & GM_CFG_CYLINDER_FIT) && !(cfg->flags & GM_CFG_RANSAC_CYLINDER))
+        return fail(nullptr, GM_ERR_INVALID_ARG, "gm_config: GM_CFG_CYLINDER_FIT needs GM_CFG_RANSAC_CYLINDER (the fit starts from the cylinder RANSAC)");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, GM_ERR_DEVICE, "no HIP device visible (libgm_hip has no CPU fallback)");
@@ -901,6 +922,7 @@ void gm_destroy(gm_ctx *ctx)
             hipFree(sl.hyp_plane); hipFree(sl.hyp_cyl); hipFree(sl.band); hipFree(sl.score_partial);
             hipFree(sl.cnt_plane); hipFree(sl.cnt_cyl); hipFree(sl.best_plane); hipFree(sl.best_cyl);
             hipFree(sl.mom_partial); hipFree(sl.mom_plane); hipFree(sl.mom_cyl); hipFree(sl.nn_best); hipFree(sl.vox_nrm4);
+            hipFree(sl.fit_partial); hipFree(sl.fit_ticket); hipFree(sl.fit_work); hipFree(sl.fit_init); hipFree(sl.fit_stage);
             if (sl.h_out) hipHostFree(sl.h_out);
             for (int k = 0; k <= GM_N_STAGES; ++k) if (sl.ev[k]) hipEventDestroy(sl.ev[k]);
             if (sl.ev_k0) hipEventDestroy(sl.ev_k0);

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/gm_hip.h"
+
 namespace gm {
 
 constexpr int kWave = 64;
@@ -121,6 +123,15 @@ struct FrameExt {
     double cyl_axis_refit[3];
 };
 
+// working model of the cylinder regression between its launches (k_cylfit.hip): the current (c, d, r), the hypothesis
+// direction (axis sign), status and the size of the last Gauss-Newton step
+struct CylFitWork {
+    double c[3], d[3], r;
+    double d_hyp[3];
+    double last_step;
+    uint32_t status, passes;
+};
+
 struct FrameOut {        // device -> host result record (one small D2H per frame)
     DevCounters ctr;
     float evals[3];
@@ -128,6 +139,7 @@ struct FrameOut {        // device -> host result record (one small D2H per fram
     double scatter[6];
     VoxelParams vox;
     FrameExt ext;
+    gm_cylinder_fit fit; // GM_CFG_CYLINDER_FIT (k_cylfit.hip); untouched otherwise
 };
 
 // ---- wave-level primitives ---------------------------------------------------
@@ -385,6 +397,25 @@ __host__ __device__ inline void eig3_sym_eigen_signs(const double a6[6], double 
         if (d < 0.0)
             for (int r = 0; r < 3; ++r) V[3 * c + r] = -V[3 * c + r];
     }
+}
+
+// inlier band of a cylinder hypothesis: (r-tau)^2 < dist_axis^2 < (r+tau)^2, both ends in fp32
+__host__ __device__ inline void cyl_band(float r, double tau, float &lo2, float &hi2)
+{
+    const double lo = (double)r - tau, hi = (double)r + tau;
+    lo2 = lo > 0 ? (float)(lo * lo) : -1.0f;
+    hi2 = (float)(hi * hi);
+}
+
+// cylinder inlier predicate of the RANSAC scorers and label passes: lo2 < |v|^2 - (v.d)^2 < hi2, v = p - point on axis
+__device__ __forceinline__ bool cyl_inlier(float x, float y, float z, float px, float py, float pz, float dx, float dy,
+                                           float dz, float lo2, float hi2)
+{
+    const float vx = __fsub_rn(x, px), vy = __fsub_rn(y, py), vz = __fsub_rn(z, pz);
+    const float t = __fmaf_rn(vx, dx, __fmaf_rn(vy, dy, __fmul_rn(vz, dz)));
+    const float vv = __fmaf_rn(vx, vx, __fmaf_rn(vy, vy, __fmul_rn(vz, vz)));
+    const float q = __fmaf_rn(-t, t, vv);
+    return q > lo2 && q < hi2;
 }
 
 // ---- the frame's closing step: fixed-order reduction of the scatter partials + 3x3 eigen + result record -------------

@@ -268,6 +268,56 @@ gm_status gm_get_labels(gm_ctx *ctx, uint32_t slot, uint8_t *labels, uint32_t ca
     return fetch_bytes(ctx, sl, sl.labels, sl.last.n_valid, 1, labels, capacity, n_out);
 }
 
+gm_status gm_get_cylinder_fit(gm_ctx *ctx, uint32_t slot, gm_cylinder_fit *out)
+{
+    if (!ctx) return GM_ERR_INVALID_ARG;
+    if (!(ctx->cfg.flags & GM_CFG_CYLINDER_FIT))
+        return gm_fail(ctx, GM_ERR_UNSUPPORTED, "gm_get_cylinder_fit: context created without GM_CFG_CYLINDER_FIT");
+    gm_status st = gm_check_slot(ctx, slot);
+    if (st != GM_OK) return st;
+    if (!out) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_get_cylinder_fit: NULL argument");
+    *out = ctx->slots[slot].last_fit;
+    return GM_OK;
+}
+
+// getCylinder (tunnel_processing.hpp:56-59, the empty stub of src/tunnel_processing.cpp:149-154) as one stage call: the
+// frame's four launches (k_cylfit.hip) on caller buffers
+gm_status gm_fit_cylinder(gm_ctx *ctx, const float *xyz, uint32_t n, const uint8_t *labels, uint32_t want,
+                          const float init7[7], double tau, gm_cylinder_fit *out, uint8_t *inlier_out)
+{
+    Slot *slp;
+    if (!ctx) return GM_ERR_INVALID_ARG;
+    if ((n && !xyz) || !init7 || !out) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_fit_cylinder: NULL argument");
+    if (!(tau > 0.0) || !isfinite(tau)) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_fit_cylinder: tau must be > 0");
+    gm_status st = prepare(ctx, slp, n, 1);
+    if (st != GM_OK) return st;
+    Slot &sl = *slp;
+    st = upload_xyz(ctx, sl, xyz, n, sl.valid4);
+    if (st != GM_OK) return st;
+    st = upload_labels(ctx, sl, labels, n);
+    if (st != GM_OK) return st;
+    float row[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int k = 0; k < 7; ++k) row[k] = init7[k];
+    GMX_HIP(ctx, hipMemcpyAsync(sl.fit_init, row, sizeof(row), hipMemcpyHostToDevice, sl.stream));
+    if (n) GMX_HIP(ctx, hipMemsetAsync(sl.inl_mask, 0, n, sl.stream));
+    CylFitArgs a;
+    a.pts = sl.valid4; a.labels = labels ? sl.labels : nullptr; a.out = sl.inl_mask;
+    a.want = want; a.want2 = want; a.mask_mode = 1;
+    a.n_ptr = nullptr; a.n_host = n;
+    a.init = sl.fit_init; a.best = nullptr;
+    a.work = sl.fit_work; a.fit = sl.fit_stage; a.partial = sl.fit_partial; a.ticket = sl.fit_ticket;
+    a.tau = tau;
+    launch_cylinder_fit(a, sl.stream);
+    gm_cylinder_fit f;
+    GMX_HIP(ctx, hipMemcpyAsync(&f, sl.fit_stage, sizeof(f), hipMemcpyDeviceToHost, sl.stream));
+    if (inlier_out && n) GMX_HIP(ctx, hipMemcpyAsync(inlier_out, sl.inl_mask, n, hipMemcpyDeviceToHost, sl.stream));
+    GMX_HIP(ctx, hipStreamSynchronize(sl.stream));
+    GMX_HIP(ctx, hipGetLastError());
+    f.struct_size = (uint32_t)sizeof(gm_cylinder_fit);
+    *out = f;
+    return GM_OK;
+}
+
 gm_status gm_get_compressed_map(gm_ctx *ctx, uint32_t slot, void *buf, size_t capacity, size_t *n_bytes)
 {
     gm_status st = gm_check_slot(ctx, slot);
@@ -307,6 +357,10 @@ gm_status gm_get_compressed_map(gm_ctx *ctx, uint32_t slot, void *buf, size_t ca
         memset(&q, 0, sizeof(q));
         q.type = 2; q.inliers = r.cylinder_inliers;
         for (int k = 0; k < 7; ++k) q.params[k] = r.cylinder[k];
+        if ((ctx->cfg.flags & GM_CFG_CYLINDER_FIT) && !(sl.last_fit.status & GM_FIT_FAILED_MASK)) {   // the fitted row
+            q.inliers = sl.last_fit.inliers;
+            for (int k = 0; k < 7; ++k) q.params[k] = sl.last_fit.model[k];
+        }
         memcpy(p, &q, sizeof(q)); p += sizeof(q);
     }
     if (nvox) {

@@ -457,6 +457,8 @@ gm_status gm_group_process_frame(gm_group *grp, const gm_cloud *cloud, gm_frame_
     G.last = gm_frame_result{};
     G.vox_cen.clear(); G.vox_nrm.clear(); G.vox_near.clear(); G.vox_nrm_valid = false;
     if (cloud->flags & GM_CLOUD_DEVICE) return gfail(grp, GM_ERR_UNSUPPORTED, "gm_group_process_frame cuts the slabs on the host: pass host rows");
+    // (a sharded frame would need the slabs' fits merged into one regression: not done)
+    if (G.cfg.flags & GM_CFG_CYLINDER_FIT) return gfail(grp, GM_ERR_UNSUPPORTED, "gm_group_process_frame: GM_CFG_CYLINDER_FIT is not supported on sharded frames (stream frames instead)");
     const uint32_t n = cloud->n_points;
     const uint64_t step = cloud->point_step;
     if (n && !cloud->data) return gfail(grp, GM_ERR_INVALID_ARG, "gm_cloud.data is NULL");

@@ -100,6 +100,13 @@ struct Slot {
     double *mom_plane = nullptr, *mom_cyl = nullptr;  // [16]
     unsigned long long *nn_best = nullptr;            // [cap]
     float4 *vox_nrm4 = nullptr;                       // [cap] normal of each voxel centroid's nearest point (GM_CFG_NEAREST)
+    // cylinder regression (k_cylfit.hip)
+    double *fit_partial = nullptr;                    // [kFitBlocks][24] partial rows of a pass
+    uint32_t *fit_ticket = nullptr;                   // last-block ticket of the passes (0 between launches)
+    CylFitWork *fit_work = nullptr;                   // model between the passes
+    float *fit_init = nullptr;                        // [8] gm_fit_cylinder's starting row
+    gm_cylinder_fit *fit_stage = nullptr;             // gm_fit_cylinder's result record
+    gm_cylinder_fit last_fit = {};                    // the fit of the slot's last completed frame (GM_CFG_CYLINDER_FIT)
     // /choppedCloud output (gm_set_cloud_output): caller-owned page-locked rows, copied on a stream of their own
     float4 *cloud_out = nullptr;
     float4 *cloud_out_dev = nullptr;   // the same rows as the device sees them (mapped page-locked memory)
@@ -224,6 +231,24 @@ void launch_ext_finalize(const float *hyp_plane, const uint32_t *best_plane, con
                          const double *partial32, uint32_t mom_rows, hipStream_t s,
                          const double *scatter_partials = nullptr, uint32_t scatter_rows = 0, uint32_t row_tile = 0,
                          const DevCounters *ctr = nullptr, const VoxelParams *voxp = nullptr, FrameOut *frame_out = nullptr);
+// k_cylfit.hip (cylinder regression, GM_CFG_CYLINDER_FIT): 3 Gauss-Newton passes + 1 label pass on a fixed grid
+constexpr uint32_t kFitBlocks = 512;
+struct CylFitArgs {
+    const float4 *pts;
+    const uint8_t *labels;     // eligibility: labels == nullptr, or labels[i] == want or want2
+    uint8_t *out;              // mask_mode 0: the label array to rewrite (eligible points: 2 inlier / 0); 1: 0/1 per point
+    uint32_t want, want2, mask_mode;
+    const uint32_t *n_ptr;     // device point count (nullptr: n_host)
+    uint32_t n_host;
+    const float *init;         // starting row = init + 8 * best[0] (best == nullptr: row 0); point, direction, radius
+    const uint32_t *best;
+    CylFitWork *work;
+    gm_cylinder_fit *fit;      // result record (device)
+    double *partial;           // [kFitBlocks][24]
+    uint32_t *ticket;
+    double tau;
+};
+void launch_cylinder_fit(const CylFitArgs &a, hipStream_t s);
 gm_status gm_enqueue_ransac(gm_ctx *ctx, Slot &sl, uint32_t n_cap, uint32_t scatter_rows, uint32_t row_tile);
 // k_nearest.hip
 void launch_nearest(const float4 *pts, const uint32_t *n_ptr, uint32_t n_cap, const float4 *queries,

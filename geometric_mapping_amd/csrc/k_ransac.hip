@@ -61,13 +61,8 @@ __device__ inline void store_nan(float *o, int k)
     for (int i = 0; i < k; ++i) o[i] = __builtin_nanf("");
 }
 
-// inlier band of a cylinder hypothesis: (r-tau)^2 < dist_axis^2 < (r+tau)^2, both ends in fp32
-__host__ __device__ inline void cyl_band(float r, double tau, float &lo2, float &hi2)
-{
-    const double lo = (double)r - tau, hi = (double)r + tau;
-    lo2 = lo > 0 ? (float)(lo * lo) : -1.0f;
-    hi2 = (float)(hi * hi);
-}
+// (cyl_band / cyl_inlier, the cylinder inlier band and predicate, live in gm_device.hpp: the regression's label pass
+// in k_cylfit.hip decides with them too)
 
 // hyp8 rows: plane a,b,c,d,-,-,-,-   cylinder px,py,pz,dx,dy,dz,r,-
 // (zero_counts != nullptr: the kernel also clears the score counter of its hypothesis, so the frame pipeline needs no memset)
@@ -179,16 +174,6 @@ __device__ __forceinline__ bool plane_inlier(float x, float y, float z, float a,
 {
     const float dist = __fmaf_rn(a, x, __fmaf_rn(b, y, __fmaf_rn(c, z, d)));
     return fabsf(dist) < tau;  // NaN hypothesis or masked (NaN) point -> false
-}
-
-__device__ __forceinline__ bool cyl_inlier(float x, float y, float z, float px, float py, float pz, float dx, float dy,
-                                           float dz, float lo2, float hi2)
-{
-    const float vx = __fsub_rn(x, px), vy = __fsub_rn(y, py), vz = __fsub_rn(z, pz);
-    const float t = __fmaf_rn(vx, dx, __fmaf_rn(vy, dy, __fmul_rn(vz, dz)));
-    const float vv = __fmaf_rn(vx, vx, __fmaf_rn(vy, vy, __fmul_rn(vz, vz)));
-    const float q = __fmaf_rn(-t, t, vv);
-    return q > lo2 && q < hi2;
 }
 
 // ---- top-K selection by the last block of a scoring launch -----------------------------------------------------------

@@ -276,18 +276,13 @@ Marker Processor::rvizArrow(const Vector3f &start, const Vector3f &end, const Ve
     return m;
 }
 
-bool Processor::rvizCylinder(const gm_frame_result &r, const double &length, Marker &m, const std::string &frame)
+// one CYLINDER marker centred on `pos`, its z axis along the unit `d`, diameter 2 rad, `length` long
+static void cylinder_marker(const double pos[3], const double d[3], double rad, double length, Marker &m,
+                            const std::string &frame)
 {
-    const double p[3] = {r.cylinder[0], r.cylinder[1], r.cylinder[2]};
-    double d[3] = {r.cylinder[3], r.cylinder[4], r.cylinder[5]};
-    const double rad = r.cylinder[6];
-    const double dn = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    if (!(r.cylinder_inliers > 0) || !(dn > 0.0) || !(rad == rad)) return false;   // no cylinder this frame
-    for (int k = 0; k < 3; ++k) d[k] /= dn;
     m.frame_id = frame; m.ns = "cylinder"; m.id = 0;
     m.type = MARKER_CYLINDER; m.action = MARKER_ADD;
-    const double t = p[0] * d[0] + p[1] * d[1] + p[2] * d[2];
-    for (int k = 0; k < 3; ++k) { m.position[k] = p[k] - t * d[k]; m.points[0][k] = m.points[1][k] = 0.0; }
+    for (int k = 0; k < 3; ++k) { m.position[k] = pos[k]; m.points[0][k] = m.points[1][k] = 0.0; }
     // shortest-arc rotation taking the marker's z axis onto d: q = (z x d, 1 + z.d), normalised
     double q[4] = {-d[1], d[0], 0.0, 1.0 + d[2]};
     const double qn = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
@@ -296,7 +291,54 @@ bool Processor::rvizCylinder(const gm_frame_result &r, const double &length, Mar
     for (int k = 0; k < 4; ++k) m.orientation[k] = q[k];
     m.scale[0] = m.scale[1] = 2.0 * rad; m.scale[2] = length;
     m.color_a = 0.3f; m.color_r = 0.0f; m.color_g = 1.0f; m.color_b = 1.0f;
+}
+
+bool Processor::rvizCylinder(const gm_frame_result &r, const double &length, Marker &m, const std::string &frame)
+{
+    const double p[3] = {r.cylinder[0], r.cylinder[1], r.cylinder[2]};
+    double d[3] = {r.cylinder[3], r.cylinder[4], r.cylinder[5]};
+    const double rad = r.cylinder[6];
+    const double dn = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    if (!(r.cylinder_inliers > 0) || !(dn > 0.0) || !(rad == rad)) return false;   // no cylinder this frame
+    for (int k = 0; k < 3; ++k) d[k] /= dn;
+    const double t = p[0] * d[0] + p[1] * d[1] + p[2] * d[2];
+    const double pos[3] = {p[0] - t * d[0], p[1] - t * d[1], p[2] - t * d[2]};
+    cylinder_marker(pos, d, rad, length, m, frame);
     return true;
+}
+
+bool Processor::rvizCylinder(const gm_cylinder_fit &f, const double &length, Marker &m, const std::string &frame)
+{
+    if ((f.status & GM_FIT_FAILED_MASK) != 0) return false;   // no fitted cylinder
+    const double dn = std::sqrt(f.axis[0] * f.axis[0] + f.axis[1] * f.axis[1] + f.axis[2] * f.axis[2]);
+    if (!(dn > 0.0) || !(f.radius == f.radius)) return false;
+    const double d[3] = {f.axis[0] / dn, f.axis[1] / dn, f.axis[2] / dn};
+    cylinder_marker(f.point, d, f.radius, length, m, frame);
+    return true;
+}
+
+gm_cylinder_fit Processor::getCylinder(const PointCloud &cloud, const float init[7], const double &tau,
+                                       const std::vector<uint8_t> &labels, unsigned want, std::vector<uint8_t> *inliers)
+{
+    const size_t n = cloud.size();
+    if (!labels.empty() && labels.size() != n) throw Error(GM_ERR_INVALID_ARG, "getCylinder: labels must have one entry per point");
+    std::vector<float> xyz(3 * (n ? n : 1));
+    for (size_t i = 0; i < n; ++i) { xyz[3 * i] = cloud[i].x; xyz[3 * i + 1] = cloud[i].y; xyz[3 * i + 2] = cloud[i].z; }
+    if (inliers) inliers->assign(n ? n : 1, 0);
+    gm_cylinder_fit f;
+    std::memset(&f, 0, sizeof(f));
+    check(gm_fit_cylinder(ctx_, &xyz[0], (uint32_t)n, labels.empty() ? 0 : &labels[0], want, init, tau, &f,
+                          inliers ? &(*inliers)[0] : 0), "getCylinder");
+    if (inliers) inliers->resize(n);
+    return f;
+}
+
+gm_cylinder_fit Processor::cylinderFit()
+{
+    gm_cylinder_fit f;
+    std::memset(&f, 0, sizeof(f));
+    check(gm_get_cylinder_fit(cur_, cur_slot_, &f), "cylinderFit");
+    return f;
 }
 
 MarkerArray Processor::rvizNormals(const double &leafSize, const PointCloud &cloud, const NormalCloud &nrm)

@@ -116,6 +116,20 @@ public:
     // Returns false (marker untouched) when the frame produced no cylinder.
     static bool rvizCylinder(const gm_frame_result &result, const double &length, Marker &marker,
                              const std::string &frame = "/velodyne");
+    // The same marker from the least-squares fit (gm_cylinder_fit): centred on fit.point, z axis along fit.axis, diameter
+    // 2 * fit.radius.  Returns false (marker untouched) when the fit failed (status GM_FIT_NO_MODEL / _DEGENERATE /
+    // _SINGULAR).
+    static bool rvizCylinder(const gm_cylinder_fit &fit, const double &length, Marker &marker,
+                             const std::string &frame = "/velodyne");
+    // getCylinder (tunnel_processing.hpp:56-59, whose body is the empty "//Regression function" stub of
+    // src/tunnel_processing.cpp:149-154): least-squares cylinder (gm_fit_cylinder) from `init` = point, direction,
+    // radius over the points with labels[i] == want (every point when `labels` is empty); `inliers` (may be null)
+    // receives 1 for each final inlier.  A failed fit is reported in the status, not thrown.
+    gm_cylinder_fit getCylinder(const PointCloud &cloud, const float init[7], const double &tau,
+                                const std::vector<uint8_t> &labels = std::vector<uint8_t>(), unsigned want = 0,
+                                std::vector<uint8_t> *inliers = 0);
+    // the fit of the frame the accessors refer to (context created with GM_CFG_CYLINDER_FIT)
+    gm_cylinder_fit cylinderFit();
 
     gm_ctx *ctx() { return ctx_; }
 

@@ -56,6 +56,8 @@ typedef enum gm_status {
 #define GM_CFG_GRAPH           (1u << 6) /* capture the frame's launch chain as a hipGraph once and replay it for every
                                             frame of about the same size (launch-bound small frames; results are the
                                             same bit for bit; normals_kernel_ms / stage_ms are not measured) */
+#define GM_CFG_CYLINDER_FIT    (1u << 7) /* least-squares regression of the RANSAC cylinder (needs GM_CFG_RANSAC_CYLINDER):
+                                            gm_get_cylinder_fit, relabelled cylinder points, fitted map record */
 #define GM_CFG_DEFAULT         (GM_CFG_VOXEL_GRID)
 
 /* The four numeric parameters are the reference's, with its types:
@@ -284,6 +286,53 @@ gm_status gm_cylinder_hypotheses(gm_ctx *ctx, const float *xyz, const float *nxy
 gm_status gm_segment_moments(gm_ctx *ctx, const float *xyz, const float *nxyzc, const uint8_t *labels,
                              uint32_t n, uint32_t label, double mom16[16]);
 
+/* ---- cylinder regression (GM_CFG_CYLINDER_FIT) -------------------------------------------------------------------
+ * The reference's getCylinder is declared (include/geometric_mapping/tunnel_processing.hpp:56-59) with an empty body
+ * under "//Regression function" (src/tunnel_processing.cpp:149-154); its cylinderPub / displayCylinder exist only to
+ * publish that regression.  This is that regression, run on the device after the cylinder RANSAC:
+ *   parameters  unit axis direction d, axis point c, radius r; residual of p: |(p-c) - ((p-c).d) d| - r.
+ *   start       the frame's winning hypothesis row (gm_frame_result.cylinder), as published.
+ *   points      those the plane did not take (label 0 or 2 after the RANSAC label passes).
+ *   3 passes    Gauss-Newton, gates 4 tau, 2 tau, tau (tau = ransac_threshold): the points with |residual| < gate sum
+ *               J^T J, J^T res, sum res^2, count and sum t = (p-c).d in fp64; J is taken in a frame e1, e2 perpendicular
+ *               to d over (shift of c along e1, e2; tilt of d along e1, e2; r); c is moved to the foot of the gated
+ *               points' mean t before each update; the 5x5 system is solved by fp64 Cholesky.
+ *   label pass  at tau with the fp32 row `model` (point, unit direction, radius) and the RANSAC's own inlier predicate:
+ *               label 2 = inlier of the fitted cylinder, former label-2 points outside go back to 0, label 1 untouched.
+ *   point       the foot on the axis of the final inliers' centroid; axis sign: positive dot with the hypothesis axis.
+ * On failure (no hypothesis, fewer than 5 gated points, a singular / non-positive pivot) the parameters are NaN and the
+ * labels stay those of the RANSAC.  A last step above GM_FIT_STEP_BOUND sets GM_FIT_NOT_CONVERGED; values are kept. */
+#define GM_FIT_OK            0u         /* fitted */
+#define GM_FIT_NO_MODEL      1u         /* no cylinder hypothesis to start from */
+#define GM_FIT_DEGENERATE    2u         /* fewer than 5 points inside a pass's gate */
+#define GM_FIT_SINGULAR      3u         /* the 5x5 normal matrix has a non-positive (or non-finite) Cholesky pivot */
+#define GM_FIT_FAILED_MASK   0xFFu      /* status & mask != 0: parameters are NaN */
+#define GM_FIT_NOT_CONVERGED (1u << 8)  /* last_step > GM_FIT_STEP_BOUND (the parameters are still published) */
+#define GM_FIT_STEP_BOUND    1e-2       /* Euclidean norm of the last 5-vector step (metres and radians): a third of tau */
+
+typedef struct gm_cylinder_fit {
+    uint32_t struct_size; /* = sizeof(gm_cylinder_fit), filled by the library */
+    uint32_t status;      /* GM_FIT_* */
+    uint32_t inliers;     /* points labelled 2 by the final pass (points with inlier_out = 1 for gm_fit_cylinder) */
+    uint32_t passes;      /* Gauss-Newton passes completed (3 on success) */
+    double   point[3];    /* foot on the axis of the final inliers' centroid */
+    double   axis[3];     /* unit axis direction, positive dot with the hypothesis axis */
+    double   radius;      /* metres */
+    double   rms;         /* root mean square residual of the final inliers against `model` */
+    double   last_step;   /* Euclidean norm of the last Gauss-Newton step (c shift, d tilt, r) */
+    float    model[7];    /* fp32 row the final labels were decided with: point on axis, unit direction, radius */
+} gm_cylinder_fit;
+
+/* The fit of a completed slot (GM_ERR_UNSUPPORTED for a context created without GM_CFG_CYLINDER_FIT).  For a group's
+ * streamed frame: gm_get_cylinder_fit(gm_group_ctx(grp, rank), slot, ...).  Sharded group frames do not fit. */
+gm_status gm_get_cylinder_fit(gm_ctx *ctx, uint32_t slot, gm_cylinder_fit *out);
+/* getCylinder as one stage call (host buffers, blocking, slot 0; the frame's kernels).  xyz rows of 3 floats; the points
+ * with labels[i] == want take part (all points when labels is NULL); init7 = starting row (point, direction, radius);
+ * tau > 0.  inlier_out (may be NULL, n bytes) receives 1 for the final inliers, 0 elsewhere.  Fed a frame's valid cloud,
+ * its labels with 2 -> 0, want = 0 and init7 = gm_frame_result.cylinder, it returns that frame's fit bit for bit. */
+gm_status gm_fit_cylinder(gm_ctx *ctx, const float *xyz, uint32_t n, const uint8_t *labels, uint32_t want,
+                          const float init7[7], double tau, gm_cylinder_fit *out, uint8_t *inlier_out);
+
 /* "Compressed map" record of a completed slot.  The reference defines no such
  * output; this is a build-defined format: header, primitive records,
  * then n_voxels rows of x,y,z,count (float32).  Returns the bytes needed in
@@ -300,7 +349,8 @@ typedef struct gm_map_header {
     float    center_axis[3];
 } gm_map_header;
 typedef struct gm_map_primitive {
-    uint32_t type;           /* 1 plane (a,b,c,d refit), 2 cylinder (point, axis, radius) */
+    uint32_t type;           /* 1 plane (a,b,c,d refit), 2 cylinder (point, axis, radius): the RANSAC hypothesis, or with
+                                GM_CFG_CYLINDER_FIT and a successful fit gm_cylinder_fit.model / .inliers */
     uint32_t inliers;
     float    params[7];
     float    pad;

@@ -13,6 +13,8 @@
 //              this publisher and parameter but leaves them commented out (:41,119-121,163-165,
 //              src/paramHandler.cpp:55-58, launch/mapping.launch:15 sets displayCylinder=false); here the
 //              parameter is honoured: it switches the RANSAC cylinder fit on and publishes one CYLINDER marker
+//   param      gmCylinderFit (default false): GM_CFG_CYLINDER_FIT -- centerAxisOutput carries the least-squares cylinder
+//              (the regression of getCylinder, src/tunnel_processing.cpp:149-154) instead of the RANSAC hypothesis
 // and replaces the PCL/Eigen arithmetic of cloud_cb (:48-125) with ONE call into
 // the C ABI (gm_process_frame reads the PointCloud2 rows directly: no pcl::fromROSMsg).
 //
@@ -61,6 +63,7 @@ struct Parameters {  // mirrors class Parameters, include/geometric_mapping/para
     double boxFilterBound = 5.0, leafSize = .1, neighborRadius = .03, weightingFactor = .2;
     bool rvizCloud = true, rvizNormals = true, rvizCenterAxis = true, pclviz = false, rvizCylinder = false;
     bool graphReplay = false;          // gmGraphReplay
+    bool cylinderFit = false;          // gmCylinderFit: publish the least-squares cylinder (getCylinder) on centerAxisOutput
     std::vector<int> devices;          // gmDevices (empty: device 0, one frame at a time)
     explicit Parameters(ros::NodeHandle &node)
     {
@@ -79,6 +82,7 @@ struct Parameters {  // mirrors class Parameters, include/geometric_mapping/para
         node.getParam("usePCLViz", pclviz);
         node.getParam("displayCylinder", rvizCylinder);
         node.getParam("gmGraphReplay", graphReplay);
+        node.getParam("gmCylinderFit", cylinderFit);
         std::string dev;
         if (node.getParam("gmDevices", dev)) {
             for (size_t i = 0; i < dev.size();) {
@@ -166,7 +170,11 @@ void publish_frame(const gm_frame_result &r, const std_msgs::Header &header)
         normalsPub.publish(to_ros(proc->rvizNormalsFromFrame()));
     if (params->rvizCenterAxis)  // :114-117
         centerAxisPub.publish(to_ros(gm_host::Processor::rvizEigens(vals, vecs)));
-    if (params->rvizCylinder) {  // the reference's commented-out block :119-121
+    if (params->cylinderFit) {   // the regression the reference's cylinderPub was meant for (getCylinder, :149-154)
+        gm_host::Marker cyl;
+        if (gm_host::Processor::rvizCylinder(proc->cylinderFit(), 2.0 * params->boxFilterBound, cyl))
+            cylinderPub.publish(to_ros(cyl));
+    } else if (params->rvizCylinder) {  // the reference's commented-out block :119-121
         gm_host::Marker cyl;
         if (gm_host::Processor::rvizCylinder(r, 2.0 * params->boxFilterBound, cyl)) cylinderPub.publish(to_ros(cyl));
     }
@@ -253,6 +261,7 @@ int main(int argc, char **argv)
     if (params->pclviz) ROS_WARN("usePCLViz is ignored by the MI355X host (no PCL in this build)");
     try {
         const unsigned flags = GM_CFG_DEFAULT | (params->rvizCylinder ? GM_CFG_RANSAC_CYLINDER : 0u) |
+                               (params->cylinderFit ? GM_CFG_RANSAC_CYLINDER | GM_CFG_CYLINDER_FIT : 0u) |
                                (params->rvizNormals ? GM_CFG_NEAREST : 0u) | (params->graphReplay ? GM_CFG_GRAPH : 0u);
         if (params->devices.size() > 1)
             proc.reset(new gm_host::Processor(params->boxFilterBound, params->leafSize, params->neighborRadius,
@@ -274,7 +283,7 @@ int main(int argc, char **argv)
     if (params->rvizCloud) cloudPub = node.advertise<sensor_msgs::PointCloud2>("cloudOutput", 10);
     if (params->rvizNormals) normalsPub = node.advertise<visualization_msgs::MarkerArray>("normalsOutput", 10);
     if (params->rvizCenterAxis) centerAxisPub = node.advertise<visualization_msgs::MarkerArray>("eigenBasisOutput", 10);
-    if (params->rvizCylinder) cylinderPub = node.advertise<visualization_msgs::Marker>("centerAxisOutput", 10);  // :165
+    if (params->rvizCylinder || params->cylinderFit) cylinderPub = node.advertise<visualization_msgs::Marker>("centerAxisOutput", 10);  // :165
     ros::spin();
     publish_finished(true);   // the frames still in flight at shutdown
     proc.reset();
