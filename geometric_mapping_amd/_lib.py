@@ -201,6 +201,9 @@ def load():
         "gm_group_wait_frame": (C.c_int, [vp, resp, u32p, u32p]),
         "gm_group_poll_frame": (C.c_int, [vp]),
         "gm_group_in_flight": (u32, [vp]),
+        "gm_group_fit_cylinder": (C.c_int, [vp, fp, fitp]),
+        "gm_group_get_cylinder_fit": (C.c_int, [vp, fitp]),
+        "gm_group_get_labels": (C.c_int, [vp, u8p, u32, u32p]),
     }
     for name, (res, args) in proto.items():
         fn = getattr(L, name)  # AttributeError if the .so does not export it

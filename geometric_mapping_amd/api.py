@@ -513,6 +513,30 @@ class GeometricMappingGroup:
         """Index (into cropped_cloud()) of the nearest valid point of every voxel centroid (GM_CFG_NEAREST)."""
         return self._fetch(self._L.gm_group_get_voxel_nearest, 1, np.int32)
 
+    def labels(self):
+        """Labels of the sharded frame, one per row of cropped_cloud() (uint8: 1 plane, 2 cylinder, 0 other)."""
+        return self._fetch(self._L.gm_group_get_labels, 1, np.uint8)
+
+    def fit_cylinder(self, init7=None):
+        """Least-squares cylinder of the sharded frame over every rank's resident cloud (gm_group_fit_cylinder), started
+        from init7 (point, direction, radius) or, when None, from the frame's published cylinder.  Relabels the frame:
+        labels() afterwards are the published plane's (1) and the fit's (2).  Returns the dict of
+        GeometricMapping.cylinder_fit."""
+        init = None
+        if init7 is not None:
+            init = np.ascontiguousarray(np.asarray(init7, dtype=np.float32).reshape(7))
+        f = CylinderFit()
+        self._check(self._L.gm_group_fit_cylinder(self._grp, _f32(init) if init is not None else None, C.byref(f)))
+        return GeometricMapping._fit(f)
+
+    def last_cylinder_fit(self):
+        """The last fit_cylinder result of the current sharded frame (gm_group_get_cylinder_fit)."""
+        f = CylinderFit()
+        st = self._L.gm_group_get_cylinder_fit(self._grp, C.byref(f))
+        if st != GM_OK:
+            raise GmError(st, "gm_group_get_cylinder_fit: no fit of the current sharded frame")
+        return GeometricMapping._fit(f)
+
     def timing(self):
         """Wall-clock split of the last process_frame call, milliseconds."""
         t = (C.c_double * _lib.GM_GROUP_N_TIMINGS)()

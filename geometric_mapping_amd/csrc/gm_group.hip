@@ -25,6 +25,7 @@
 #include <dlfcn.h>
 #include <math.h>
 #include <rccl/rccl.h>
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -174,6 +175,21 @@ struct gm_group {
     std::vector<float> vox_nrm;      // ... and the normal of each centroid's nearest point (filled on demand)
     std::vector<int32_t> vox_near;   // ... and that point's index in the merged /choppedCloud
     bool vox_nrm_valid = false;
+    // cylinder regression of the sharded frame (gm_group_fit_cylinder): per-rank device buffers, allocated on first use
+    struct FitRank {
+        double *partial = nullptr;        // [kFitBlocks][24] the rank's partial rows of a pass
+        uint32_t *ticket = nullptr;       // last-block ticket (0 between launches)
+        CylFitWork *work = nullptr;       // the model between the passes (every rank writes the same bits)
+        gm_cylinder_fit *fit = nullptr;   // the rank's copy of the result record
+        float *rows8 = nullptr;           // [0..8) starting row, [8..16) published plane row
+        uint32_t *plane_best = nullptr;   // 0: the plane row labels; 0xFFFFFFFF: no plane, every label 0
+        double *row = nullptr;            // [4 passes][24] the rank's reduced row of each pass (exchange send buffer)
+        double *rows = nullptr;           // [4 passes][n][24] every rank's row of each pass (receive buffer)
+    };
+    std::vector<FitRank> fitr;
+    gm_cylinder_fit *h_fit = nullptr;     // pinned: [n] the ranks' result records
+    gm_cylinder_fit last_fit = {};
+    bool have_fit = false;                // last_fit belongs to the sharded frame in `last`
     // streaming: frames in flight in submission order
     struct Ticket { uint32_t rank, slot; };
     std::deque<Ticket> inflight;
@@ -320,6 +336,42 @@ gm_status cut_rows(gm_group &G, const gm_cloud *cloud, CutPlan &plan, std::vecto
     return GM_OK;
 }
 
+struct MergedRow { uint32_t id; float x, y, z; uint8_t label; };
+
+// every rank's valid cloud (and, with_labels, the rank's labels of it) tagged with the input row of each point, in
+// ascending input row: the single-GPU order of the sharded frame
+gm_status merged_rows(gm_group &G, bool with_labels, std::vector<MergedRow> &all)
+{
+    all.clear();
+    all.reserve(G.last.n_valid);
+    std::vector<float> buf;
+    std::vector<uint8_t> lab;
+    for (uint32_t r = 0; r < G.n; ++r) {
+        uint32_t m = 0;
+        gm_status st = gm_get_cropped_xyz(G.ctx[r], 0, nullptr, 0, &m);
+        if (st != GM_OK && st != GM_ERR_CAPACITY) return gfail(&G, st, gm_last_error(G.ctx[r]));
+        buf.resize((size_t)(m ? m : 1) * 4);
+        st = gm_get_cropped_xyz(G.ctx[r], 0, buf.data(), m ? m : 1, &m);
+        if (st != GM_OK) return gfail(&G, st, gm_last_error(G.ctx[r]));
+        lab.assign(m ? m : 1, 0);
+        if (with_labels && m) {
+            Slot &sl = G.ctx[r]->slots[0];
+            if (hipSetDevice(G.devices[r]) != hipSuccess ||
+                hipMemcpyAsync(lab.data(), sl.labels, m, hipMemcpyDeviceToHost, sl.stream) != hipSuccess ||
+                hipStreamSynchronize(sl.stream) != hipSuccess)
+                return gfail(&G, GM_ERR_DEVICE, "gm_group: D2H of a rank's labels failed");
+        }
+        for (uint32_t i = 0; i < m; ++i) {
+            uint32_t local;
+            memcpy(&local, &buf[4 * (size_t)i + 3], 4);
+            if (local >= G.row_ids[r].size()) return gfail(&G, GM_ERR_DEVICE, "gm_group: a rank's row index is out of range");
+            all.push_back(MergedRow{G.row_ids[r][local], buf[4 * (size_t)i], buf[4 * (size_t)i + 1], buf[4 * (size_t)i + 2], lab[i]});
+        }
+    }
+    std::stable_sort(all.begin(), all.end(), [](const MergedRow &a, const MergedRow &b) { return a.id < b.id; });
+    return GM_OK;
+}
+
 struct VoxRow { long long kz, ky, kx; float v[4]; };
 
 // Voxel centroids of the group in ascending pcl key order (z slowest, x fastest: the key's order for any box).  Edges on
@@ -396,8 +448,14 @@ void gm_group_destroy(gm_group *grp)
         if (r < grp->ev.size() && grp->ev[r]) hipEventDestroy(grp->ev[r]);
         if (r < grp->ctx.size() && grp->ctx[r]) gm_destroy(grp->ctx[r]);   // (drains the rank's streams first)
         if (r < grp->prow.size() && grp->prow[r]) hipHostFree(grp->prow[r]);
+        if (r < grp->fitr.size()) {
+            const gm_group::FitRank &f = grp->fitr[r];
+            hipFree(f.partial); hipFree(f.ticket); hipFree(f.work); hipFree(f.fit); hipFree(f.rows8); hipFree(f.plane_best);
+            hipFree(f.row); hipFree(f.rows);
+        }
     }
     if (grp->h_all) hipHostFree(grp->h_all);
+    if (grp->h_fit) hipHostFree(grp->h_fit);
     delete grp;
 }
 
@@ -454,11 +512,12 @@ gm_status gm_group_process_frame(gm_group *grp, const gm_cloud *cloud, gm_frame_
     if (!G.inflight.empty()) return gfail(grp, GM_ERR_NOT_READY, "gm_group_process_frame: streamed frames are still in flight (gm_group_wait_frame)");
     // whatever happens below, the accessors must not pair this frame's rows with an older frame's results
     G.have_frame = false;
+    G.have_fit = false;
     G.last = gm_frame_result{};
     G.vox_cen.clear(); G.vox_nrm.clear(); G.vox_near.clear(); G.vox_nrm_valid = false;
     if (cloud->flags & GM_CLOUD_DEVICE) return gfail(grp, GM_ERR_UNSUPPORTED, "gm_group_process_frame cuts the slabs on the host: pass host rows");
-    // (a sharded frame would need the slabs' fits merged into one regression: not done)
-    if (G.cfg.flags & GM_CFG_CYLINDER_FIT) return gfail(grp, GM_ERR_UNSUPPORTED, "gm_group_process_frame: GM_CFG_CYLINDER_FIT is not supported on sharded frames (stream frames instead)");
+    // (the fit of a sharded frame is a stage call of its own on the resident slabs: gm_group_fit_cylinder)
+    if (G.cfg.flags & GM_CFG_CYLINDER_FIT) return gfail(grp, GM_ERR_UNSUPPORTED, "gm_group_process_frame: GM_CFG_CYLINDER_FIT is not supported on sharded frames (call gm_group_fit_cylinder after the frame, or stream frames instead)");
     const uint32_t n = cloud->n_points;
     const uint64_t step = cloud->point_step;
     if (n && !cloud->data) return gfail(grp, GM_ERR_INVALID_ARG, "gm_cloud.data is NULL");
@@ -631,29 +690,35 @@ gm_status gm_group_get_cropped_xyz(gm_group *grp, float *xyzw, uint32_t capacity
     if (total > capacity) return gfail(grp, GM_ERR_CAPACITY, "output buffer too small");
     if (!total) return GM_OK;
     if (!xyzw) return gfail(grp, GM_ERR_INVALID_ARG, "output pointer is NULL");
-    struct Row { uint32_t id; float x, y, z; };
-    std::vector<Row> all;
-    all.reserve(total);
-    std::vector<float> buf;
-    for (uint32_t r = 0; r < G.n; ++r) {
-        uint32_t m = 0;
-        gm_status st = gm_get_cropped_xyz(G.ctx[r], 0, nullptr, 0, &m);
-        if (st != GM_OK && st != GM_ERR_CAPACITY) return gfail(grp, st, gm_last_error(G.ctx[r]));
-        buf.resize((size_t)(m ? m : 1) * 4);
-        st = gm_get_cropped_xyz(G.ctx[r], 0, buf.data(), m ? m : 1, &m);
-        if (st != GM_OK) return gfail(grp, st, gm_last_error(G.ctx[r]));
-        for (uint32_t i = 0; i < m; ++i) {
-            uint32_t local;
-            memcpy(&local, &buf[4 * (size_t)i + 3], 4);
-            if (local >= G.row_ids[r].size()) return gfail(grp, GM_ERR_DEVICE, "gm_group: a rank's row index is out of range");
-            all.push_back(Row{G.row_ids[r][local], buf[4 * (size_t)i], buf[4 * (size_t)i + 1], buf[4 * (size_t)i + 2]});
-        }
-    }
-    std::stable_sort(all.begin(), all.end(), [](const Row &a, const Row &b) { return a.id < b.id; });
+    std::vector<MergedRow> all;
+    const gm_status st = merged_rows(G, false, all);
+    if (st != GM_OK) return st;
     for (size_t i = 0; i < all.size() && i < capacity; ++i) {
         xyzw[4 * i] = all[i].x; xyzw[4 * i + 1] = all[i].y; xyzw[4 * i + 2] = all[i].z;
         memcpy(&xyzw[4 * i + 3], &all[i].id, 4);
     }
+    return GM_OK;
+}
+
+// labels of a sharded frame, in the order of gm_group_get_cropped_xyz
+gm_status gm_group_get_labels(gm_group *grp, uint8_t *labels, uint32_t capacity, uint32_t *n_out)
+{
+    if (!grp) return GM_ERR_INVALID_ARG;
+    gm_group &G = *grp;
+    if (!G.have_frame) { if (n_out) *n_out = 0; return gfail(grp, GM_ERR_NOT_READY, "gm_group: no completed sharded frame"); }
+    if (!(G.cfg.flags & (GM_CFG_RANSAC_PLANE | GM_CFG_RANSAC_CYLINDER)) && !G.have_fit) {
+        if (n_out) *n_out = 0;
+        return gfail(grp, GM_ERR_NOT_READY, "gm_group_get_labels: group created without a GM_CFG_RANSAC_* flag and no gm_group_fit_cylinder on this frame");
+    }
+    const uint32_t total = G.last.n_valid;
+    if (n_out) *n_out = total;
+    if (total > capacity) return gfail(grp, GM_ERR_CAPACITY, "output buffer too small");
+    if (!total) return GM_OK;
+    if (!labels) return gfail(grp, GM_ERR_INVALID_ARG, "output pointer is NULL");
+    std::vector<MergedRow> all;
+    const gm_status st = merged_rows(G, true, all);
+    if (st != GM_OK) return st;
+    for (size_t i = 0; i < all.size() && i < capacity; ++i) labels[i] = all[i].label;
     return GM_OK;
 }
 
@@ -771,6 +836,145 @@ gm_status gm_group_get_voxel_nearest(gm_group *grp, int32_t *idx, uint32_t capac
         if (st != GM_OK) return st;
     }
     memcpy(idx, G.vox_near.data(), (size_t)V * 4);
+    return GM_OK;
+}
+
+// ---- cylinder regression of the sharded frame (DESIGN.md par. 4 "Multi-device") ------------------------------------
+// The fit is a sum followed by a 5x5 solve, so it shards like the scatter matrix: every rank runs the single-device
+// launches (k_cylfit.hip) on its resident valid cloud -- owned points only, so the ranks' sums add up to the frame's --
+// and writes its reduced 24-double row instead of solving; the rows are all-gathered (RCCL, or event-ordered device
+// copies on a loopback group) and k_cylfit_merge, on every rank, sums them in rank order and runs the single-device
+// solve.  4 exchange rounds per fit (3 Gauss-Newton passes, 1 label pass), everything enqueued, one wait at the end.
+gm_status gm_group_fit_cylinder(gm_group *grp, const float init7[7], gm_cylinder_fit *out)
+{
+    if (!grp) return GM_ERR_INVALID_ARG;
+    gm_group &G = *grp;
+    if (G.dead) return gfail(grp, GM_ERR_COMM, "gm_group: an earlier collective failed; destroy the group");
+    if (!out) return gfail(grp, GM_ERR_INVALID_ARG, "gm_group_fit_cylinder: NULL argument");
+    if (!G.have_frame) return gfail(grp, GM_ERR_NOT_READY, "gm_group: no completed sharded frame");
+    G.have_fit = false;
+    const uint32_t R = G.n;
+    const double tau = G.cfg.ransac_threshold;
+    if (!(tau > 0.0) || !std::isfinite(tau)) return gfail(grp, GM_ERR_INVALID_ARG, "gm_group_fit_cylinder: ransac_threshold must be > 0");
+    // work buffers (first call; a context created without GM_CFG_CYLINDER_FIT has none of its own)
+    G.fitr.resize(R);
+    for (uint32_t r = 0; r < R; ++r) {
+        gm_group::FitRank &f = G.fitr[r];
+        if (f.rows) continue;
+        if (hipSetDevice(G.devices[r]) != hipSuccess) return gfail(grp, GM_ERR_DEVICE, "hipSetDevice failed");
+        bool ok = (f.partial || hipMalloc((void **)&f.partial, sizeof(double) * kFitBlocks * kFitRowLen) == hipSuccess) &&
+                  (f.ticket || (hipMalloc((void **)&f.ticket, sizeof(uint32_t)) == hipSuccess &&
+                                hipMemset(f.ticket, 0, sizeof(uint32_t)) == hipSuccess)) &&   // k_cylfit resets it after every launch
+                  (f.work || hipMalloc((void **)&f.work, sizeof(CylFitWork)) == hipSuccess) &&
+                  (f.fit || hipMalloc((void **)&f.fit, sizeof(gm_cylinder_fit)) == hipSuccess) &&
+                  (f.rows8 || hipMalloc((void **)&f.rows8, sizeof(float) * 16) == hipSuccess) &&
+                  (f.plane_best || hipMalloc((void **)&f.plane_best, sizeof(uint32_t)) == hipSuccess) &&
+                  (f.row || hipMalloc((void **)&f.row, sizeof(double) * 4 * kFitRowLen) == hipSuccess) &&
+                  hipMalloc((void **)&f.rows, sizeof(double) * 4 * kFitRowLen * R) == hipSuccess;
+        if (!ok) { f.rows = nullptr; return gfail(grp, GM_ERR_OOM, "gm_group_fit_cylinder: device allocation failed"); }
+    }
+    if (!G.h_fit && hipHostMalloc((void **)&G.h_fit, sizeof(gm_cylinder_fit) * R, hipHostMallocDefault) != hipSuccess) {
+        G.h_fit = nullptr;
+        return gfail(grp, GM_ERR_OOM, "gm_group_fit_cylinder: hipHostMalloc failed");
+    }
+    // the starting row (caller's, or the published cylinder: NaN when the frame has none) and the published plane
+    const float nanf_ = std::numeric_limits<float>::quiet_NaN();
+    float rows8[16];
+    for (int k = 0; k < 16; ++k) rows8[k] = 0.f;
+    const bool has_cyl = (G.cfg.flags & GM_CFG_RANSAC_CYLINDER) && G.last.cylinder_inliers > 0;
+    for (int k = 0; k < 7; ++k) rows8[k] = init7 ? init7[k] : (has_cyl ? G.last.cylinder[k] : nanf_);
+    bool has_plane = (G.cfg.flags & GM_CFG_RANSAC_PLANE) && G.last.plane_inliers > 0;
+    for (int k = 0; k < 4; ++k) { rows8[8 + k] = G.last.plane[k]; has_plane = has_plane && std::isfinite(G.last.plane[k]); }
+    const uint32_t plane_best = has_plane ? 0u : 0xFFFFFFFFu;
+    std::vector<CylFitArgs> args(R);
+    auto fail_enqueued = [&](gm_status s, const std::string &msg) { drain(G); return gfail(grp, s, msg); };
+    for (uint32_t r = 0; r < R; ++r) {
+        gm_group::FitRank &f = G.fitr[r];
+        Slot &sl = G.ctx[r]->slots[0];
+        if (hipSetDevice(G.devices[r]) != hipSuccess ||
+            hipMemcpyAsync(f.rows8, rows8, sizeof(rows8), hipMemcpyHostToDevice, sl.stream) != hipSuccess ||
+            hipMemcpyAsync(f.plane_best, &plane_best, sizeof(uint32_t), hipMemcpyHostToDevice, sl.stream) != hipSuccess)
+            return fail_enqueued(GM_ERR_DEVICE, "gm_group_fit_cylinder: upload of the starting rows failed");
+        // plane relabel: every valid point 1 if it is an inlier of the published plane (the RANSAC's fp32 predicate), else 0
+        launch_label(0, sl.valid4, sl.labels, 0, 1, &sl.ctr->n_valid, sl.last.n_valid, f.rows8 + 8, nullptr, f.plane_best,
+                     tau, 1, nullptr, nullptr, 0, sl.stream);
+        CylFitArgs &a = args[r];
+        a.pts = sl.valid4; a.labels = sl.labels; a.out = sl.labels;
+        a.want = 0; a.want2 = 0; a.mask_mode = 0;   // eligible: what the published plane left
+        a.n_ptr = &sl.ctr->n_valid; a.n_host = sl.last.n_valid;
+        a.init = f.rows8; a.best = nullptr;
+        a.work = f.work; a.fit = f.fit; a.partial = f.partial; a.ticket = f.ticket;
+        a.tau = tau;
+    }
+    for (int pass = 0; pass < 4; ++pass) {
+        for (uint32_t r = 0; r < R; ++r) {
+            hipSetDevice(G.devices[r]);
+            hipStream_t s = G.ctx[r]->slots[0].stream;
+            CylFitArgs a = args[r];
+            a.rank_row = G.fitr[r].row + (size_t)pass * kFitRowLen;
+            launch_cylinder_fit_pass(a, pass, s);
+            if (G.loopback) hipEventRecord(G.ev[r], s);
+        }
+        // the exchange of this pass: rank q's row -> rows[pass][q] on every rank (per-pass buffers: no rank overwrites a
+        // row that another rank may still be copying)
+        if (!G.loopback) {
+            ncclResult_t rc = G.rccl.GroupStart();
+            for (uint32_t r = 0; r < R && rc == ncclSuccess; ++r) {
+                hipSetDevice(G.devices[r]);
+                rc = G.rccl.AllGather(G.fitr[r].row + (size_t)pass * kFitRowLen, G.fitr[r].rows + (size_t)pass * kFitRowLen * R, kFitRowLen,
+                                      ncclDouble, G.comms[r], G.ctx[r]->slots[0].stream);
+            }
+            const ncclResult_t rc2 = G.rccl.GroupEnd();
+            if (rc == ncclSuccess) rc = rc2;
+            if (rc != ncclSuccess) {   // as in gm_group_process_frame: no drain, the group refuses further work
+                G.dead = true;
+                return gfail(grp, GM_ERR_COMM, std::string("ncclAllGather: ") + G.rccl.GetErrorString(rc));
+            }
+        } else {
+            for (uint32_t r = 0; r < R; ++r) {
+                hipSetDevice(G.devices[r]);
+                hipStream_t s = G.ctx[r]->slots[0].stream;
+                double *dst = G.fitr[r].rows + (size_t)pass * kFitRowLen * R;
+                for (uint32_t q = 0; q < R; ++q) {
+                    if (q != r) hipStreamWaitEvent(s, G.ev[q], 0);
+                    hipMemcpyAsync(dst + (size_t)q * kFitRowLen, G.fitr[q].row + (size_t)pass * kFitRowLen, sizeof(double) * kFitRowLen,
+                                   hipMemcpyDeviceToDevice, s);
+                }
+            }
+        }
+        for (uint32_t r = 0; r < R; ++r) {
+            hipSetDevice(G.devices[r]);
+            launch_cylinder_fit_merge(args[r], pass, G.fitr[r].rows + (size_t)pass * kFitRowLen * R, R, G.ctx[r]->slots[0].stream);
+        }
+    }
+    for (uint32_t r = 0; r < R; ++r) {
+        hipSetDevice(G.devices[r]);
+        if (hipMemcpyAsync(&G.h_fit[r], G.fitr[r].fit, sizeof(gm_cylinder_fit), hipMemcpyDeviceToHost, G.ctx[r]->slots[0].stream) != hipSuccess)
+            return fail_enqueued(GM_ERR_DEVICE, "gm_group_fit_cylinder: D2H of a rank's fit failed");
+    }
+    for (uint32_t r = 0; r < R; ++r) {
+        hipSetDevice(G.devices[r]);
+        if (hipStreamSynchronize(G.ctx[r]->slots[0].stream) != hipSuccess || hipGetLastError() != hipSuccess)
+            return fail_enqueued(GM_ERR_DEVICE, std::string("gm_group_fit_cylinder: rank ") + std::to_string(r) + ": the fit's launches failed");
+    }
+    // every rank solved the same sums: the records must agree bit for bit (padding excluded)
+    const size_t cmp = offsetof(gm_cylinder_fit, model) + sizeof(((gm_cylinder_fit *)nullptr)->model);
+    for (uint32_t r = 1; r < R; ++r)
+        if (memcmp(&G.h_fit[r], &G.h_fit[0], cmp) != 0)
+            return gfail(grp, GM_ERR_DEVICE, std::string("gm_group_fit_cylinder: rank ") + std::to_string(r) + "'s fit differs from rank 0's");
+    gm_cylinder_fit f = G.h_fit[0];
+    f.struct_size = (uint32_t)sizeof(gm_cylinder_fit);
+    G.last_fit = f;
+    G.have_fit = true;
+    *out = f;
+    return GM_OK;
+}
+
+gm_status gm_group_get_cylinder_fit(const gm_group *grp, gm_cylinder_fit *out)
+{
+    if (!grp || !out) return GM_ERR_INVALID_ARG;
+    if (!grp->have_frame || !grp->have_fit) return GM_ERR_NOT_READY;
+    *out = grp->last_fit;
     return GM_OK;
 }
 

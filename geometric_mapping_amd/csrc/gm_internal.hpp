@@ -233,6 +233,7 @@ void launch_ext_finalize(const float *hyp_plane, const uint32_t *best_plane, con
                          const DevCounters *ctr = nullptr, const VoxelParams *voxp = nullptr, FrameOut *frame_out = nullptr);
 // k_cylfit.hip (cylinder regression, GM_CFG_CYLINDER_FIT): 3 Gauss-Newton passes + 1 label pass on a fixed grid
 constexpr uint32_t kFitBlocks = 512;
+constexpr int kFitRowLen = 24;   // doubles in a partial row of a pass (22 Gauss-Newton sums or 3 label sums, zero padded)
 struct CylFitArgs {
     const float4 *pts;
     const uint8_t *labels;     // eligibility: labels == nullptr, or labels[i] == want or want2
@@ -244,11 +245,16 @@ struct CylFitArgs {
     const uint32_t *best;
     CylFitWork *work;
     gm_cylinder_fit *fit;      // result record (device)
-    double *partial;           // [kFitBlocks][24]
+    double *partial;           // [kFitBlocks][kFitRowLen]
     uint32_t *ticket;
     double tau;
+    double *rank_row = nullptr;   // group: the last block writes the rank's reduced 24-double row here instead of solving
 };
 void launch_cylinder_fit(const CylFitArgs &a, hipStream_t s);
+// group (gm_group_fit_cylinder): one pass (0..2 Gauss-Newton, 3 label) with a.rank_row set, then, after the rows of every
+// rank are gathered into rows[n_ranks][24] on this rank, the merge that solves / publishes
+void launch_cylinder_fit_pass(const CylFitArgs &a, int pass, hipStream_t s);
+void launch_cylinder_fit_merge(const CylFitArgs &a, int pass, const double *rows, uint32_t n_ranks, hipStream_t s);
 gm_status gm_enqueue_ransac(gm_ctx *ctx, Slot &sl, uint32_t n_cap, uint32_t scatter_rows, uint32_t row_tile);
 // k_nearest.hip
 void launch_nearest(const float4 *pts, const uint32_t *n_ptr, uint32_t n_cap, const float4 *queries,

@@ -324,7 +324,8 @@ typedef struct gm_cylinder_fit {
 } gm_cylinder_fit;
 
 /* The fit of a completed slot (GM_ERR_UNSUPPORTED for a context created without GM_CFG_CYLINDER_FIT).  For a group's
- * streamed frame: gm_get_cylinder_fit(gm_group_ctx(grp, rank), slot, ...).  Sharded group frames do not fit. */
+ * streamed frame: gm_get_cylinder_fit(gm_group_ctx(grp, rank), slot, ...).  A sharded group frame fits through the
+ * stage call gm_group_fit_cylinder (the flag itself stays refused by gm_group_process_frame). */
 gm_status gm_get_cylinder_fit(gm_ctx *ctx, uint32_t slot, gm_cylinder_fit *out);
 /* getCylinder as one stage call (host buffers, blocking, slot 0; the frame's kernels).  xyz rows of 3 floats; the points
  * with labels[i] == want take part (all points when labels is NULL); init7 = starting row (point, direction, radius);
@@ -376,6 +377,8 @@ gm_status gm_get_compressed_map(gm_ctx *ctx, uint32_t slot, void *buf, size_t ca
  * ascending pcl key order (bit for bit the unsharded frame's; a lattice too coarse to cut along is merged through the
  * ranks' exact fixed-point voxel sums instead); fitted primitives by vote -- every rank's fit is a candidate, every rank
  * counts every candidate's inliers on its own resident owned points (gm_score_frame), the largest total wins.
+ * The cylinder regression of a sharded frame is a stage call after it, gm_group_fit_cylinder: the ranks' sums of every
+ * Gauss-Newton pass are merged into one regression on the device (one ncclAllGather of a 24-double row per pass).
  *
  * STREAMING.  Frames that fit one GPU are independent: gm_group_submit_frame hands a whole frame to the next device in
  * turn (its next free slot; gm_config.n_slots frames in flight per device), gm_group_wait_frame returns the frames in
@@ -403,6 +406,20 @@ gm_status gm_group_get_voxel_centroids(gm_group *grp, float *xyzc, uint32_t capa
  * rank, the closest point of all wins.  Needs GM_CFG_NEAREST | GM_CFG_VOXEL_GRID. */
 gm_status gm_group_get_voxel_normals(gm_group *grp, float *nxyzc, uint32_t capacity, uint32_t *n_out);
 gm_status gm_group_get_voxel_nearest(gm_group *grp, int32_t *idx, uint32_t capacity, uint32_t *n_out);
+/* Least-squares cylinder over the last sharded frame (gm_group_process_frame), every rank's resident valid cloud.
+ * init7: starting row (point, direction, radius); NULL = the frame's published (voted) cylinder.  tau = the group's
+ * ransac_threshold.  Afterwards every rank's labels are those of the published plane (1) and of the fit (2), 0 elsewhere.
+ * Same algorithm, statuses and record as gm_fit_cylinder / GM_CFG_CYLINDER_FIT.  The ranks' sums of each pass are
+ * all-gathered (4 rounds) and merged in rank order on every rank; a 1-rank group gives the single-device fit bit for bit.
+ * No plane (flag off, no inliers or a NaN row): every label starts at 0.  GM_ERR_NOT_READY without a completed sharded
+ * frame; GM_ERR_COMM after a failed collective (the group then refuses further work); GM_ERR_DEVICE if the ranks'
+ * records differ.  The rank contexts need not have GM_CFG_CYLINDER_FIT. */
+gm_status gm_group_fit_cylinder(gm_group *grp, const float init7[7], gm_cylinder_fit *out);
+/* the last gm_group_fit_cylinder result of the current sharded frame (GM_ERR_NOT_READY otherwise) */
+gm_status gm_group_get_cylinder_fit(const gm_group *grp, gm_cylinder_fit *out);
+/* labels of the last sharded frame, one per row of gm_group_get_cropped_xyz and in its order (the ranks' RANSAC labels,
+ * or those of gm_group_fit_cylinder once it ran; GM_ERR_NOT_READY without a GM_CFG_RANSAC_* flag before a fit) */
+gm_status gm_group_get_labels(gm_group *grp, uint8_t *labels, uint32_t capacity, uint32_t *n_out);
 /* wall-clock split of the last gm_group_process_frame call, milliseconds */
 enum { GM_GROUP_T_CUT = 0,    /* host: histogram, edges, rows scattered into the per-rank page-locked buffers */
        GM_GROUP_T_SUBMIT = 1, /* host: the ranks' frames enqueued (H2D + launch chains) */
