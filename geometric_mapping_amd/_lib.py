@@ -37,6 +37,7 @@ GM_CFG_STAGE_TIMING = 1 << 4
 GM_CFG_KEEP_COUNTS = 1 << 5
 GM_CFG_GRAPH = 1 << 6
 GM_CFG_CYLINDER_FIT = 1 << 7
+GM_CFG_SURFACE_MAP = 1 << 8
 GM_CFG_DEFAULT = GM_CFG_VOXEL_GRID
 
 GM_CLOUD_DEVICE = 1 << 0
@@ -52,6 +53,11 @@ GM_FIT_SINGULAR = 3
 GM_FIT_FAILED_MASK = 0xFF
 GM_FIT_NOT_CONVERGED = 1 << 8
 GM_FIT_STEP_BOUND = 1e-2
+
+GM_SURF_MAX_CELLS = 4096
+GM_SURF_OK = 0
+GM_SURF_NO_MODEL = 1
+GM_SURF_UP_FALLBACK = 1 << 8
 
 GM_N_STAGES = 9
 STAGE_NAMES = ("upload", "crop", "grid", "normals", "compact", "frame", "voxel", "ransac", "total")
@@ -85,6 +91,24 @@ class CylinderFit(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("status", C.c_uint32), ("inliers", C.c_uint32), ("passes", C.c_uint32),
                 ("point", C.c_double * 3), ("axis", C.c_double * 3), ("radius", C.c_double), ("rms", C.c_double),
                 ("last_step", C.c_double), ("model", C.c_float * 7)]
+
+
+class SurfaceParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_stations", C.c_uint32), ("n_sectors", C.c_uint32), ("reserved", C.c_uint32),
+                ("station_length", C.c_double), ("t_min", C.c_double), ("gate", C.c_double),
+                ("up", C.c_double * 3), ("forward", C.c_double * 3)]
+
+
+class SurfaceCell(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("mean", C.c_float), ("min", C.c_float), ("max", C.c_float)]
+
+
+class SurfaceInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("status", C.c_uint32), ("n_stations", C.c_uint32), ("n_sectors", C.c_uint32),
+                ("mapped", C.c_uint32), ("outside", C.c_uint32), ("beyond_gate", C.c_uint32), ("plane", C.c_uint32),
+                ("cells_hit", C.c_uint32), ("reserved", C.c_uint32),
+                ("o", C.c_float * 3), ("a", C.c_float * 3), ("u", C.c_float * 3), ("v", C.c_float * 3),
+                ("R", C.c_float), ("t_min", C.c_float), ("station_length", C.c_float), ("sector_angle", C.c_float)]
 
 
 class GmError(RuntimeError):
@@ -145,6 +169,7 @@ def load():
                                          C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8))
     cfgp, cloudp, resp = C.POINTER(Config), C.POINTER(Cloud), C.POINTER(FrameResult)
     fitp = C.POINTER(CylinderFit)
+    sprmp, scellp, sinfop = C.POINTER(SurfaceParams), C.POINTER(SurfaceCell), C.POINTER(SurfaceInfo)
     proto = {
         "gm_create": (C.c_int, [cfgp, C.POINTER(vp)]),
         "gm_destroy": (None, [vp]),
@@ -185,6 +210,11 @@ def load():
         "gm_get_compressed_map": (C.c_int, [vp, u32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
         "gm_get_cylinder_fit": (C.c_int, [vp, u32, fitp]),
         "gm_fit_cylinder": (C.c_int, [vp, fp, u32, u8p, u32, fp, C.c_double, fitp, u8p]),
+        "gm_surface_default_params": (None, [sprmp]),
+        "gm_set_surface_params": (C.c_int, [vp, sprmp]),
+        "gm_get_surface_map": (C.c_int, [vp, u32, sinfop, scellp, u32, u32p]),
+        "gm_get_surface_points": (C.c_int, [vp, u32, fp, i32p, u32, u32p]),
+        "gm_surface_map": (C.c_int, [vp, fp, u32, u8p, fp, sprmp, sinfop, scellp, u32, fp, i32p]),
         "gm_group_create": (C.c_int, [cfgp, i32p, u32, u32, C.POINTER(vp)]),
         "gm_group_destroy": (None, [vp]),
         "gm_group_size": (u32, [vp]),

@@ -405,6 +405,85 @@ class GeometricMapping:
                                             C.byref(f), mask.ctypes.data_as(C.POINTER(C.c_uint8))))
         return self._fit(f), mask[:len(xyz)].astype(bool)
 
+    # ---- wall deviation map (GM_CFG_SURFACE_MAP; include/gm_hip.h states the semantics) ----
+    @staticmethod
+    def surface_params(**kw):
+        """gm_surface_params with the library's defaults, then the keywords (n_stations, n_sectors, station_length, t_min,
+        gate, up, forward)."""
+        L = _lib.load()
+        p = _lib.SurfaceParams()
+        L.gm_surface_default_params(C.byref(p))
+        for k, v in kw.items():
+            if k in ("up", "forward"):
+                getattr(p, k)[:] = [float(x) for x in v]
+            elif not hasattr(p, k) or k == "struct_size":
+                raise TypeError(f"unknown surface parameter {k!r}")
+            else:
+                setattr(p, k, v)
+        return p
+
+    def set_surface_params(self, **kw):
+        """gm_set_surface_params: the map parameters of the frames submitted after the call."""
+        p = self.surface_params(**kw)
+        self._check(self._L.gm_set_surface_params(self._ctx, C.byref(p)))
+
+    @staticmethod
+    def _surface(info, cells):
+        """(info dict, count, mean, min, max arrays shaped (n_stations, n_sectors))."""
+        d = {k: int(getattr(info, k)) for k in ("struct_size", "status", "n_stations", "n_sectors", "mapped", "outside",
+                                                  "beyond_gate", "plane", "cells_hit")}
+        for k in ("o", "a", "u", "v"):
+            d[k] = np.array(getattr(info, k)[:], dtype=np.float32)
+        for k in ("R", "t_min", "station_length", "sector_angle"):
+            d[k] = np.float32(getattr(info, k))
+        shape = (d["n_stations"], d["n_sectors"])
+        nc = shape[0] * shape[1]
+        raw = np.frombuffer(bytes(cells), dtype=np.uint8)[:16 * nc].reshape(nc, 16)
+        count = raw[:, 0:4].copy().view(np.uint32).reshape(shape)
+        mean, mn, mx = (raw[:, 4 * k:4 * k + 4].copy().view(np.float32).reshape(shape) for k in (1, 2, 3))
+        return d, count, mean, mn, mx
+
+    def surface_map(self, slot=0):
+        """The map of the slot's last frame (gm_get_surface_map): (info dict, count, mean, min, max), the arrays shaped
+        (n_stations, n_sectors)."""
+        info = _lib.SurfaceInfo()
+        n = C.c_uint32(0)
+        st = self._L.gm_get_surface_map(self._ctx, slot, C.byref(info), None, 0, C.byref(n))
+        if st not in (GM_OK, GM_ERR_CAPACITY):
+            self._check(st)
+        cells = (_lib.SurfaceCell * max(n.value, 1))()
+        self._check(self._L.gm_get_surface_map(self._ctx, slot, C.byref(info), cells, n.value, C.byref(n)))
+        return self._surface(info, cells)
+
+    def surface_points(self, slot=0):
+        """Per valid point of the slot's last frame: (residual e [n] float32, cell index [n] int32; -1 unless mapped)."""
+        n = C.c_uint32(0)
+        st = self._L.gm_get_surface_points(self._ctx, slot, None, None, 0, C.byref(n))
+        if st not in (GM_OK, GM_ERR_CAPACITY):
+            self._check(st)
+        res = np.empty(max(n.value, 1), dtype=np.float32)
+        cell = np.empty(max(n.value, 1), dtype=np.int32)
+        if n.value:
+            self._check(self._L.gm_get_surface_points(self._ctx, slot, _f32(res), cell.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                      n.value, C.byref(n)))
+        return res[:n.value].copy(), cell[:n.value].copy()
+
+    def surfaceMap(self, cloud, model7, labels=None, **params):
+        """The map as one stage call (gm_surface_map) on a host cloud [n,3] against model7 = (c, d, R) (e.g. a frame's
+        cylinder_fit()["model"]); labels None: no point is plane.  Returns (info, count, mean, min, max, residual, cell)."""
+        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+        m = np.ascontiguousarray(np.asarray(model7, dtype=np.float32).reshape(7))
+        lab, lp = self._u8(labels)
+        p = self.surface_params(**params)
+        info = _lib.SurfaceInfo()
+        nc = int(p.n_stations) * int(p.n_sectors)
+        cells = (_lib.SurfaceCell * max(nc, 1))()
+        res = np.empty(max(len(xyz), 1), dtype=np.float32)
+        cell = np.empty(max(len(xyz), 1), dtype=np.int32)
+        self._check(self._L.gm_surface_map(self._ctx, _f32(xyz), len(xyz), lp, _f32(m), C.byref(p), C.byref(info), cells,
+                                           nc, _f32(res), cell.ctypes.data_as(C.POINTER(C.c_int32))))
+        return (*self._surface(info, cells), res[:len(xyz)].copy(), cell[:len(xyz)].copy())
+
 
 def decode_compressed_map(buf):
     """Parse gm_get_compressed_map bytes (gm_map_header / gm_map_primitive in include/gm_hip.h)."""

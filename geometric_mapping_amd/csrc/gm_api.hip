@@ -429,6 +429,10 @@ gm_status enqueue_frame(gm_ctx *ctx, Slot &sl, const gm_cloud *cloud, bool block
         st = gm_ensure_ext(ctx, sl, ctx->cfg.ransac_hypotheses ? ctx->cfg.ransac_hypotheses : 1);
         if (st != GM_OK) return st;
     }
+    if (ctx->cfg.flags & GM_CFG_SURFACE_MAP) {
+        st = gm_ensure_surface(ctx, sl);
+        if (st != GM_OK) return st;
+    }
     hipStream_t s = sl.stream;
     sl.n_in = n;
     // Epochs of replayed (graph) scans are (frame counter * 32 + launch index) mod 2^29: they repeat every 2^24 frames of
@@ -683,6 +687,37 @@ gm_status gm_ensure_ext(gm_ctx *ctx, Slot &sl, uint32_t H)
     return GM_OK;
 }
 
+// surface map buffers (k_surface.hip): the fixed-size ones once, the per-point ones with the slot's capacity.  The global
+// cell table is zeroed here and kept zero between launches by the map's last block.
+gm_status gm_ensure_surface(gm_ctx *ctx, Slot &sl)
+{
+    if (!sl.surf_table) {
+        GM_HIP(ctx, hipStreamSynchronize(sl.stream));
+        hipFree(sl.surf_prm); hipFree(sl.surf_cells); hipFree(sl.surf_info); hipFree(sl.surf_fit);
+        sl.surf_prm = nullptr; sl.surf_cells = nullptr; sl.surf_info = nullptr; sl.surf_fit = nullptr;
+        GM_HIP(ctx, dmalloc(sl.surf_prm, 2)); GM_HIP(ctx, dmalloc(sl.surf_cells, GM_SURF_MAX_CELLS));
+        GM_HIP(ctx, dmalloc(sl.surf_info, 1)); GM_HIP(ctx, dmalloc(sl.surf_fit, 1));
+        GM_HIP(ctx, hipMemsetAsync(sl.surf_info, 0, sizeof(gm_surface_info), sl.stream));
+        const SurfParams prm[2] = {surface_device_params(ctx->surf), surface_device_params(ctx->surf)};
+        GM_HIP(ctx, hipMemcpyAsync(sl.surf_prm, prm, sizeof(prm), hipMemcpyHostToDevice, sl.stream));
+        uint8_t *table = nullptr;
+        GM_HIP(ctx, dmalloc(table, surface_table_bytes()));
+        sl.surf_table = table;
+        GM_HIP(ctx, hipMemsetAsync(sl.surf_table, 0, surface_table_bytes(), sl.stream));
+        GM_HIP(ctx, hipStreamSynchronize(sl.stream));
+        ++sl.alloc_gen;
+    }
+    if (sl.surf_cap < sl.cap || !sl.surf_res) {
+        GM_HIP(ctx, hipStreamSynchronize(sl.stream));
+        hipFree(sl.surf_res); hipFree(sl.surf_cell);
+        sl.surf_res = nullptr; sl.surf_cell = nullptr; sl.surf_cap = 0;
+        GM_HIP(ctx, dmalloc(sl.surf_res, sl.cap)); GM_HIP(ctx, dmalloc(sl.surf_cell, sl.cap));
+        sl.surf_cap = sl.cap;
+        ++sl.alloc_gen;
+    }
+    return GM_OK;
+}
+
 // sequential multi-model RANSAC over the valid cloud of a frame: plane first (label 1),
 // then cylinder on what is left (label 2), moments + refits per segment
 gm_status gm_enqueue_ransac(gm_ctx *ctx, Slot &sl, uint32_t n_cap, uint32_t scatter_rows, uint32_t row_tile)
@@ -726,6 +761,13 @@ gm_status gm_enqueue_ransac(gm_ctx *ctx, Slot &sl, uint32_t n_cap, uint32_t scat
             a.work = sl.fit_work; a.fit = &sl.d_out->fit; a.partial = sl.fit_partial; a.ticket = sl.fit_ticket;
             a.tau = cf.ransac_threshold;
             launch_cylinder_fit(a, s);
+            if (cf.flags & GM_CFG_SURFACE_MAP) {   // wall deviation map against the fit's device-side record
+                SurfArgs m;
+                m.pts = sl.valid4; m.labels = sl.labels; m.n_ptr = n_ptr; m.n_host = n_cap;
+                m.fit = &sl.d_out->fit; m.prm = sl.surf_prm;
+                m.table = sl.surf_table; m.cells = sl.surf_cells; m.info = sl.surf_info; m.res = sl.surf_res; m.cell = sl.surf_cell;
+                launch_surface_map(m, n_cap, s);
+            }
         }
     }
     // the label passes left the moments of their segments in sl.mom_partial (one row per block, the same grid for both
@@ -840,6 +882,8 @@ gm_status gm_create(const gm_config *cfg, gm_ctx **out)
         return fail(nullptr, GM_ERR_INVALID_ARG, "gm_config: ransac_hypotheses must be in [1, 8192] and ransac_threshold > 0");
     if ((cfg->flags & GM_CFG_CYLINDER_FIT) && !(cfg->flags & GM_CFG_RANSAC_CYLINDER))
         return fail(nullptr, GM_ERR_INVALID_ARG, "gm_config: GM_CFG_CYLINDER_FIT needs GM_CFG_RANSAC_CYLINDER (the fit starts from the cylinder RANSAC)");
+    if ((cfg->flags & GM_CFG_SURFACE_MAP) && !(cfg->flags & GM_CFG_CYLINDER_FIT))
+        return fail(nullptr, GM_ERR_INVALID_ARG, "gm_config: GM_CFG_SURFACE_MAP needs GM_CFG_CYLINDER_FIT (the map is taken against the fitted cylinder)");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, GM_ERR_DEVICE, "no HIP device visible (libgm_hip has no CPU fallback)");
@@ -853,6 +897,7 @@ gm_status gm_create(const gm_config *cfg, gm_ctx **out)
     ctx->own_lo = -std::numeric_limits<double>::infinity();
     ctx->own_hi = std::numeric_limits<double>::infinity();
     ctx->force_voxel_sort = getenv("GM_VOXEL_SORT_PATH") != nullptr;  // tests: exercise the general path
+    gm_surface_default_params(&ctx->surf);
     gm_status st = GM_OK;
     auto body = [&]() -> gm_status {
         GM_HIP(ctx, hipSetDevice(ctx->device));
@@ -923,6 +968,8 @@ void gm_destroy(gm_ctx *ctx)
             hipFree(sl.cnt_plane); hipFree(sl.cnt_cyl); hipFree(sl.best_plane); hipFree(sl.best_cyl);
             hipFree(sl.mom_partial); hipFree(sl.mom_plane); hipFree(sl.mom_cyl); hipFree(sl.nn_best); hipFree(sl.vox_nrm4);
             hipFree(sl.fit_partial); hipFree(sl.fit_ticket); hipFree(sl.fit_work); hipFree(sl.fit_init); hipFree(sl.fit_stage);
+            hipFree(sl.surf_prm); hipFree(sl.surf_table); hipFree(sl.surf_cells); hipFree(sl.surf_info); hipFree(sl.surf_fit);
+            hipFree(sl.surf_res); hipFree(sl.surf_cell);
             if (sl.h_out) hipHostFree(sl.h_out);
             for (int k = 0; k <= GM_N_STAGES; ++k) if (sl.ev[k]) hipEventDestroy(sl.ev[k]);
             if (sl.ev_k0) hipEventDestroy(sl.ev_k0);

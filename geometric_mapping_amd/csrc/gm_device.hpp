@@ -123,6 +123,28 @@ struct FrameExt {
     double cyl_axis_refit[3];
 };
 
+// e1, e2 perpendicular to the unit d (the basis synth._basis builds): e1 = (h x d) / |h x d|, e2 = d x e1.  The cylinder
+// regression's Jacobian frame (k_cylfit.hip) and the surface map's fallback sector direction (k_surface.hip).
+__host__ __device__ inline void fit_basis(const double d[3], double e1[3], double e2[3])
+{
+    const double h[3] = {0.0, fabs(d[2]) < 0.9 ? 0.0 : 1.0, fabs(d[2]) < 0.9 ? 1.0 : 0.0};
+    double u[3] = {h[1] * d[2] - h[2] * d[1], h[2] * d[0] - h[0] * d[2], h[0] * d[1] - h[1] * d[0]};
+    const double inv = 1.0 / sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+    for (int k = 0; k < 3; ++k) e1[k] = u[k] * inv;
+    e2[0] = d[1] * e1[2] - d[2] * e1[1];
+    e2[1] = d[2] * e1[0] - d[0] * e1[2];
+    e2[2] = d[0] * e1[1] - d[1] * e1[0];
+}
+
+// surface map parameters as the map kernel reads them from the device (k_surface.hip): the fp32 binning constants are
+// rounded once on the host from gm_surface_params, so a captured graph picks up gm_set_surface_params
+struct SurfParams {
+    uint32_t n_stations, n_sectors;
+    float station_length, t_min, gate, sector_angle, two_pi;
+    uint32_t pad;
+    double up[3], forward[3];
+};
+
 // working model of the cylinder regression between its launches (k_cylfit.hip): the current (c, d, r), the hypothesis
 // direction (axis sign), status and the size of the last Gauss-Newton step
 struct CylFitWork {

@@ -318,6 +318,134 @@ gm_status gm_fit_cylinder(gm_ctx *ctx, const float *xyz, uint32_t n, const uint8
     return GM_OK;
 }
 
+// ---- wall deviation map (GM_CFG_SURFACE_MAP, k_surface.hip) ----
+
+void gm_surface_default_params(gm_surface_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(gm_surface_params);
+    p->n_stations = 40;
+    p->n_sectors = 90;
+    p->station_length = 0.25;
+    p->t_min = -5.0;     // the default crop box is +-5 m
+    p->gate = 0.25;
+    p->up[2] = 1.0;
+    p->forward[0] = 1.0;   // REP-103: x forward
+}
+
+gm_status gm_set_surface_params(gm_ctx *ctx, const gm_surface_params *p)
+{
+    if (!ctx) return GM_ERR_INVALID_ARG;
+    if (gm_check_surface_params(p) != GM_OK)
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_set_surface_params: NULL, struct_size mismatch or a parameter outside its limits");
+    for (uint32_t i = 0; i < ctx->n_slots; ++i)
+        if (ctx->slots[i].submitted && !ctx->slots[i].complete)
+            return gm_fail(ctx, GM_ERR_NOT_READY, "gm_set_surface_params: a slot holds a submitted frame that has not been waited for");
+    if (hipSetDevice(ctx->device) != hipSuccess) return gm_fail(ctx, GM_ERR_DEVICE, "hipSetDevice failed");
+    ctx->surf = *p;
+    const SurfParams d = surface_device_params(*p);
+    for (uint32_t i = 0; i < ctx->n_slots; ++i) {   // (slots without map buffers upload ctx->surf when they allocate them)
+        Slot &sl = ctx->slots[i];
+        if (!sl.surf_prm) continue;
+        GMX_HIP(ctx, hipMemcpyAsync(sl.surf_prm, &d, sizeof(d), hipMemcpyHostToDevice, sl.stream));
+        GMX_HIP(ctx, hipStreamSynchronize(sl.stream));
+    }
+    return GM_OK;
+}
+
+gm_status gm_get_surface_map(gm_ctx *ctx, uint32_t slot, gm_surface_info *info, gm_surface_cell *cells, uint32_t capacity,
+                             uint32_t *n_out)
+{
+    if (!ctx) return GM_ERR_INVALID_ARG;
+    if (!(ctx->cfg.flags & GM_CFG_SURFACE_MAP))
+        return gm_fail(ctx, GM_ERR_UNSUPPORTED, "gm_get_surface_map: context created without GM_CFG_SURFACE_MAP");
+    gm_status st = gm_check_slot(ctx, slot);
+    if (st != GM_OK) return st;
+    if (!info) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_get_surface_map: NULL info");
+    Slot &sl = ctx->slots[slot];
+    gm_surface_info inf;
+    GMX_HIP(ctx, hipMemcpyAsync(&inf, sl.surf_info, sizeof(inf), hipMemcpyDeviceToHost, sl.stream));
+    GMX_HIP(ctx, hipStreamSynchronize(sl.stream));
+    *info = inf;
+    const uint32_t nc = inf.n_stations * inf.n_sectors;
+    if (n_out) *n_out = nc;
+    if (nc > capacity) return gm_fail(ctx, GM_ERR_CAPACITY, "gm_get_surface_map: cell buffer too small");
+    if (!nc) return GM_OK;
+    if (!cells) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_get_surface_map: NULL cells");
+    GMX_HIP(ctx, hipMemcpyAsync(cells, sl.surf_cells, (size_t)nc * sizeof(gm_surface_cell), hipMemcpyDeviceToHost, sl.stream));
+    GMX_HIP(ctx, hipStreamSynchronize(sl.stream));
+    return GM_OK;
+}
+
+gm_status gm_get_surface_points(gm_ctx *ctx, uint32_t slot, float *residual, int32_t *cell, uint32_t capacity, uint32_t *n_out)
+{
+    if (!ctx) return GM_ERR_INVALID_ARG;
+    if (!(ctx->cfg.flags & GM_CFG_SURFACE_MAP))
+        return gm_fail(ctx, GM_ERR_UNSUPPORTED, "gm_get_surface_points: context created without GM_CFG_SURFACE_MAP");
+    gm_status st = gm_check_slot(ctx, slot);
+    if (st != GM_OK) return st;
+    Slot &sl = ctx->slots[slot];
+    const uint32_t n = sl.last.n_valid;
+    if (n_out) *n_out = n;
+    if (n > capacity) return gm_fail(ctx, GM_ERR_CAPACITY, "gm_get_surface_points: output buffer too small");
+    if (!n) return GM_OK;
+    if (residual) GMX_HIP(ctx, hipMemcpyAsync(residual, sl.surf_res, (size_t)n * 4, hipMemcpyDeviceToHost, sl.stream));
+    if (cell) GMX_HIP(ctx, hipMemcpyAsync(cell, sl.surf_cell, (size_t)n * 4, hipMemcpyDeviceToHost, sl.stream));
+    GMX_HIP(ctx, hipStreamSynchronize(sl.stream));
+    return GM_OK;
+}
+
+// the frame's map launch (k_surface.hip) on caller buffers, with the call's own parameter block and model row
+gm_status gm_surface_map(gm_ctx *ctx, const float *xyz, uint32_t n, const uint8_t *labels, const float model7[7],
+                         const gm_surface_params *p, gm_surface_info *info, gm_surface_cell *cells, uint32_t capacity,
+                         float *residual, int32_t *cell)
+{
+    if (!ctx) return GM_ERR_INVALID_ARG;
+    if ((n && !xyz) || !model7 || !info) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_surface_map: NULL argument");
+    gm_surface_params prm;
+    if (p) prm = *p;
+    else gm_surface_default_params(&prm);
+    if (gm_check_surface_params(&prm) != GM_OK)
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_surface_map: struct_size mismatch or a parameter outside its limits");
+    const uint32_t nc = prm.n_stations * prm.n_sectors;
+    if (nc > capacity) return gm_fail(ctx, GM_ERR_CAPACITY, "gm_surface_map: cell buffer too small");
+    if (!cells) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_surface_map: NULL cells");
+    Slot *slp;
+    gm_status st = gm_begin_stage(ctx, slp);
+    if (st != GM_OK) return st;
+    Slot &sl = *slp;
+    st = gm_ensure_capacity(ctx, sl, n ? n : 1u, (size_t)(n ? n : 1u) * 16, true);
+    if (st != GM_OK) return st;
+    st = gm_ensure_surface(ctx, sl);
+    if (st != GM_OK) return st;
+    st = upload_xyz(ctx, sl, xyz, n, sl.valid4);
+    if (st != GM_OK) return st;
+    st = upload_labels(ctx, sl, labels, n);
+    if (st != GM_OK) return st;
+    gm_cylinder_fit f;
+    memset(&f, 0, sizeof(f));
+    f.status = GM_FIT_OK;
+    for (int k = 0; k < 7; ++k) f.model[k] = model7[k];
+    const SurfParams d = surface_device_params(prm);
+    GMX_HIP(ctx, hipMemcpyAsync(sl.surf_fit, &f, sizeof(f), hipMemcpyHostToDevice, sl.stream));
+    GMX_HIP(ctx, hipMemcpyAsync(sl.surf_prm + 1, &d, sizeof(d), hipMemcpyHostToDevice, sl.stream));
+    SurfArgs a;
+    a.pts = sl.valid4; a.labels = labels ? sl.labels : nullptr; a.n_ptr = nullptr; a.n_host = n;
+    a.fit = sl.surf_fit; a.prm = sl.surf_prm + 1;
+    a.table = sl.surf_table; a.cells = sl.surf_cells; a.info = sl.surf_info; a.res = sl.surf_res; a.cell = sl.surf_cell;
+    launch_surface_map(a, n, sl.stream);
+    GMX_HIP(ctx, hipGetLastError());
+    gm_surface_info inf;
+    GMX_HIP(ctx, hipMemcpyAsync(&inf, sl.surf_info, sizeof(inf), hipMemcpyDeviceToHost, sl.stream));
+    GMX_HIP(ctx, hipMemcpyAsync(cells, sl.surf_cells, (size_t)nc * sizeof(gm_surface_cell), hipMemcpyDeviceToHost, sl.stream));
+    if (residual && n) GMX_HIP(ctx, hipMemcpyAsync(residual, sl.surf_res, (size_t)n * 4, hipMemcpyDeviceToHost, sl.stream));
+    if (cell && n) GMX_HIP(ctx, hipMemcpyAsync(cell, sl.surf_cell, (size_t)n * 4, hipMemcpyDeviceToHost, sl.stream));
+    GMX_HIP(ctx, hipStreamSynchronize(sl.stream));
+    *info = inf;
+    return GM_OK;
+}
+
 gm_status gm_get_compressed_map(gm_ctx *ctx, uint32_t slot, void *buf, size_t capacity, size_t *n_bytes)
 {
     gm_status st = gm_check_slot(ctx, slot);

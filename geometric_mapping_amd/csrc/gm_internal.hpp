@@ -107,6 +107,15 @@ struct Slot {
     float *fit_init = nullptr;                        // [8] gm_fit_cylinder's starting row
     gm_cylinder_fit *fit_stage = nullptr;             // gm_fit_cylinder's result record
     gm_cylinder_fit last_fit = {};                    // the fit of the slot's last completed frame (GM_CFG_CYLINDER_FIT)
+    // wall deviation map (k_surface.hip; GM_CFG_SURFACE_MAP or gm_surface_map, allocated on first use)
+    SurfParams *surf_prm = nullptr;                   // [2]: the frames' parameters, the stage call's
+    uint8_t *surf_table = nullptr;                    // global cell table + class counters + ticket (zero between launches)
+    gm_surface_cell *surf_cells = nullptr;            // [GM_SURF_MAX_CELLS]
+    gm_surface_info *surf_info = nullptr;
+    gm_cylinder_fit *surf_fit = nullptr;              // the stage call's model row
+    float *surf_res = nullptr;                        // [surf_cap] per valid point
+    int32_t *surf_cell = nullptr;                     // [surf_cap]
+    uint32_t surf_cap = 0;
     // /choppedCloud output (gm_set_cloud_output): caller-owned page-locked rows, copied on a stream of their own
     float4 *cloud_out = nullptr;
     float4 *cloud_out_dev = nullptr;   // the same rows as the device sees them (mapped page-locked memory)
@@ -155,6 +164,7 @@ struct gm_ctx {
     gm::Slot *slots = nullptr;
     double own_lo, own_hi;
     bool force_voxel_sort = false;
+    gm_surface_params surf;   // gm_set_surface_params (the frames' map parameters)
     std::string err;
 };
 
@@ -256,6 +266,26 @@ void launch_cylinder_fit(const CylFitArgs &a, hipStream_t s);
 void launch_cylinder_fit_pass(const CylFitArgs &a, int pass, hipStream_t s);
 void launch_cylinder_fit_merge(const CylFitArgs &a, int pass, const double *rows, uint32_t n_ranks, hipStream_t s);
 gm_status gm_enqueue_ransac(gm_ctx *ctx, Slot &sl, uint32_t n_cap, uint32_t scatter_rows, uint32_t row_tile);
+// k_surface.hip (wall deviation map, GM_CFG_SURFACE_MAP): one launch per frame
+struct SurfArgs {
+    const float4 *pts;
+    const uint8_t *labels;     // nullptr: no point is plane
+    const uint32_t *n_ptr;     // device point count (nullptr: n_host)
+    uint32_t n_host;
+    const gm_cylinder_fit *fit;   // status + fp32 model row
+    const SurfParams *prm;
+    uint8_t *table;            // Slot::surf_table
+    gm_surface_cell *cells;
+    gm_surface_info *info;
+    float *res;
+    int32_t *cell;
+};
+size_t surface_table_bytes();
+// n_cap: the most points the launch can see (the grid is sized by it)
+void launch_surface_map(const SurfArgs &a, uint32_t n_cap, hipStream_t s);
+SurfParams surface_device_params(const gm_surface_params &p);
+gm_status gm_check_surface_params(const gm_surface_params *p);
+gm_status gm_ensure_surface(gm_ctx *ctx, Slot &sl);
 // k_nearest.hip
 void launch_nearest(const float4 *pts, const uint32_t *n_ptr, uint32_t n_cap, const float4 *queries,
                     const uint32_t *nq_ptr, uint32_t nq_cap, unsigned long long *best, int32_t *idx, hipStream_t s,

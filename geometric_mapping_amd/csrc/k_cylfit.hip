@@ -29,18 +29,6 @@ constexpr int kFitCols = kFitRowLen;   // partial row: 22 GN sums (or 3 label su
 constexpr int kFitAcc = 22;
 constexpr int kFitUnroll = 4;  // points per thread and trip, loads issued together
 
-// e1, e2 perpendicular to the unit d (the basis synth._basis builds): e1 = (h x d) / |h x d|, e2 = d x e1
-__device__ inline void fit_basis(const double d[3], double e1[3], double e2[3])
-{
-    const double h[3] = {0.0, fabs(d[2]) < 0.9 ? 0.0 : 1.0, fabs(d[2]) < 0.9 ? 1.0 : 0.0};
-    double u[3] = {h[1] * d[2] - h[2] * d[1], h[2] * d[0] - h[0] * d[2], h[0] * d[1] - h[1] * d[0]};
-    const double inv = 1.0 / sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-    for (int k = 0; k < 3; ++k) e1[k] = u[k] * inv;
-    e2[0] = d[1] * e1[2] - d[2] * e1[1];
-    e2[1] = d[2] * e1[0] - d[0] * e1[2];
-    e2[2] = d[0] * e1[1] - d[1] * e1[0];
-}
-
 __device__ inline bool fit_eligible(const uint8_t *__restrict__ labels, uint32_t i, uint32_t want, uint32_t want2)
 {
     if (!labels) return true;

@@ -139,6 +139,30 @@ def velodyne_tunnel(rings=16, az=1800, seed=0, radius=2.0, axis_offset=(0.3, 0.5
                 offsets=(0, 4, 8), xyz=xyz)
 
 
+SURFACE_PATCHES = ((-2.0, -1.0, 20.0, 44.0, 0.15), (1.0, 2.0, 316.0, 340.0, -0.15))
+
+
+def tunnel_patches(n, seed=0, radius=2.0, length=12.0, sigma=0.01, floor_z=-1.2, patches=SURFACE_PATCHES):
+    """A tunnel along +x (like tunnel_frame, no outliers) whose wall is pushed radially by dr inside known patches.
+    A patch is (t0, t1, phi0_deg, phi1_deg, dr) in the coordinates of the wall deviation map (GM_CFG_SURFACE_MAP) with
+    its default up = +z: t along x, phi from +z turning toward a x u = -y.  Points below floor_z are projected onto the
+    floor as in tunnel_frame.  The defaults lie on the upper half of the wall, aligned with the default map cells
+    (0.25 m x 4 degrees from t = -5): 4 stations x 6 sectors each, +0.15 m and -0.15 m.  float32 (n, 3)."""
+    rng = np.random.default_rng(seed)
+    t = rng.uniform(-length / 2, length / 2, n)
+    phi = rng.uniform(0.0, 2 * np.pi, n)
+    rr = radius + rng.normal(0.0, sigma, n)
+    deg = np.rad2deg(phi)
+    for t0, t1, p0, p1, dr in patches:
+        rr = np.where((t >= t0) & (t < t1) & (deg >= p0) & (deg < p1), rr + dr, rr)
+    # u = +z, v = a x u = -y
+    p = np.stack([t, -rr * np.sin(phi), rr * np.cos(phi)], axis=1)
+    if floor_z is not None:
+        below = p[:, 2] < floor_z
+        p[below, 2] = floor_z + rng.normal(0.0, sigma, int(below.sum()))
+    return np.ascontiguousarray(p, dtype=np.float32)
+
+
 def drop_row_padding(msg):
     """What the node does with an organised cloud whose rows are padded (ros/geometric_mapping_node.cpp): the C ABI takes
     point_step-strided rows, so the row_step padding is dropped once on the host.  Returns the packed uint8 rows."""

@@ -341,6 +341,29 @@ gm_cylinder_fit Processor::cylinderFit()
     return f;
 }
 
+void Processor::setSurfaceParams(const gm_surface_params &params)
+{
+    if (grp_) {
+        for (unsigned r = 0; r < gm_group_size(grp_); ++r) {
+            gm_ctx *c = gm_group_ctx(grp_, r);
+            const gm_status s = gm_set_surface_params(c, &params);
+            if (s != GM_OK) throw Error(s, std::string("setSurfaceParams: ") + gm_status_string(s) + ": " + gm_last_error(c));
+        }
+        return;
+    }
+    check(gm_set_surface_params(ctx_, &params), "setSurfaceParams");
+}
+
+void Processor::getSurfaceMap(gm_surface_info &info, std::vector<gm_surface_cell> &cells)
+{
+    uint32_t n = 0;
+    gm_status s = gm_get_surface_map(cur_, cur_slot_, &info, 0, 0, &n);
+    if (s != GM_OK && s != GM_ERR_CAPACITY) throw Error(s, std::string("getSurfaceMap: ") + gm_status_string(s) + ": " + gm_last_error(cur_));
+    cells.resize(n);
+    s = gm_get_surface_map(cur_, cur_slot_, &info, n ? &cells[0] : 0, n, &n);
+    if (s != GM_OK) throw Error(s, std::string("getSurfaceMap: ") + gm_status_string(s) + ": " + gm_last_error(cur_));
+}
+
 MarkerArray Processor::rvizNormals(const double &leafSize, const PointCloud &cloud, const NormalCloud &nrm)
 {
     const PointCloud vox = voxelGrid(leafSize, cloud);        // :217-220

@@ -130,6 +130,11 @@ public:
                                 std::vector<uint8_t> *inliers = 0);
     // the fit of the frame the accessors refer to (context created with GM_CFG_CYLINDER_FIT)
     gm_cylinder_fit cylinderFit();
+    // Wall deviation map (GM_CFG_SURFACE_MAP, include/gm_hip.h): the map parameters of the frames processed after the
+    // call, on every device (gm_set_surface_params; throws GM_ERR_NOT_READY while frames are in flight) ...
+    void setSurfaceParams(const gm_surface_params &params);
+    // ... and the map of the frame the accessors refer to: info and the cells, row-major [n_stations][n_sectors]
+    void getSurfaceMap(gm_surface_info &info, std::vector<gm_surface_cell> &cells);
 
     gm_ctx *ctx() { return ctx_; }
 

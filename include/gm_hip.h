@@ -58,6 +58,8 @@ typedef enum gm_status {
                                             same bit for bit; normals_kernel_ms / stage_ms are not measured) */
 #define GM_CFG_CYLINDER_FIT    (1u << 7) /* least-squares regression of the RANSAC cylinder (needs GM_CFG_RANSAC_CYLINDER):
                                             gm_get_cylinder_fit, relabelled cylinder points, fitted map record */
+#define GM_CFG_SURFACE_MAP     (1u << 8) /* wall deviation map against the fitted cylinder (needs GM_CFG_CYLINDER_FIT):
+                                            gm_get_surface_map, gm_get_surface_points */
 #define GM_CFG_DEFAULT         (GM_CFG_VOXEL_GRID)
 
 /* The four numeric parameters are the reference's, with its types:
@@ -333,6 +335,84 @@ gm_status gm_get_cylinder_fit(gm_ctx *ctx, uint32_t slot, gm_cylinder_fit *out);
  * its labels with 2 -> 0, want = 0 and init7 = gm_frame_result.cylinder, it returns that frame's fit bit for bit. */
 gm_status gm_fit_cylinder(gm_ctx *ctx, const float *xyz, uint32_t n, const uint8_t *labels, uint32_t want,
                           const float init7[7], double tau, gm_cylinder_fit *out, uint8_t *inlier_out);
+
+/* ---- wall deviation map (GM_CFG_SURFACE_MAP) ---------------------------------------------------------------------
+ * A developed ("unrolled") map of the wall against the fitted cylinder: one cell per axial station and angular sector,
+ * holding the signed radial deviation of the points that fall into it.  Run on the device right after the cylinder
+ * regression of every frame, on the valid cloud (order of gm_get_cropped_xyz), the labels after the fit's relabel and
+ * the fit's fp32 row fit.model = (c, d, R).
+ *   map frame   computed once per frame in fp64 from the fp32 row, rounded to fp32 once, reported in gm_surface_info:
+ *               a = d if d.forward >= 0, else -d;  o = c - (c.a) a (the foot of the sensor origin: t = 0 there);
+ *               u = normalize(up - (up.a) a), or, when that projection is shorter than 0.1 |up|, the e1 of the fit's
+ *               basis of a (GM_SURF_UP_FALLBACK);  v = a x u.
+ *   per point   fp32, explicit roundings: q = p - o, t = q.a, w = q - t a, e = sqrt(w.w) - R (positive: the wall lies
+ *               outside the cylinder), theta = atan2(w.v, w.u) folded to phi in [0, 2 pi) (0 toward up, increasing toward
+ *               v), j = floor((t - t_min) / ds), k = min(floor(phi / dtheta), n_sectors - 1), dtheta = 2 pi / n_sectors.
+ *   classes     every valid point is in exactly one: plane (label 1), beyond_gate (|e| > gate or e not finite), outside
+ *               (j not in [0, n_stations)), mapped (cell j * n_sectors + k).
+ *   cells       count; mean = (sum of rint(e 2^20), int64) 2^-20 / count in fp64, rounded to fp32 once; min e, max e (the
+ *               exact fp32 residuals).  An empty cell: count 0, NaN elsewhere.  Every cell is a function of the set of
+ *               (cell, e) pairs alone -- not of arrival order, grid or launch site -- so the frame, a replayed graph,
+ *               streaming slots and the stage call give the same bytes.  No floating-point atomics.
+ *   points      e (NaN for plane points) and the cell index (-1 unless mapped).
+ * A failed fit (status & GM_FIT_FAILED_MASK) or a row that is not finite gives GM_SURF_NO_MODEL: every cell empty, every
+ * residual NaN, every cell index -1, the class counts 0 and the frame vectors NaN. */
+#define GM_SURF_MAX_CELLS   4096u      /* n_stations * n_sectors limit: a map block's LDS table, 20 B per cell = 80 KiB */
+#define GM_SURF_OK          0u
+#define GM_SURF_NO_MODEL    1u         /* no fitted cylinder: nothing mapped */
+#define GM_SURF_UP_FALLBACK (1u << 8)  /* `up` is (nearly) parallel to the axis: u is the fit basis' e1 instead */
+
+typedef struct gm_surface_params {
+    uint32_t struct_size;     /* = sizeof(gm_surface_params) */
+    uint32_t n_stations;      /* axial stations, >= 1 (default 40) */
+    uint32_t n_sectors;       /* angular sectors, >= 1 (default 90: 4 degrees); n_stations * n_sectors <= GM_SURF_MAX_CELLS */
+    uint32_t reserved;        /* 0 */
+    double   station_length;  /* ds, metres, > 0 (default 0.25) */
+    double   t_min;           /* axial coordinate of station 0's start, metres, finite (default -5: the default crop box) */
+    double   gate;            /* |e| above it is beyond_gate, metres, in (0, 8] (default 0.25) */
+    double   up[3];           /* sector 0 direction before projection, finite, non-zero (default 0, 0, 1) */
+    double   forward[3];      /* station direction sign, finite, non-zero (default 1, 0, 0: REP-103 x forward) */
+} gm_surface_params;
+
+typedef struct gm_surface_cell {
+    uint32_t count;
+    float    mean, min, max;  /* metres; NaN when count == 0 */
+} gm_surface_cell;
+
+typedef struct gm_surface_info {
+    uint32_t struct_size;     /* = sizeof(gm_surface_info), filled by the library */
+    uint32_t status;          /* GM_SURF_* */
+    uint32_t n_stations, n_sectors;
+    uint32_t mapped, outside, beyond_gate, plane;   /* points per class; they add up to n_valid (0 on GM_SURF_NO_MODEL) */
+    uint32_t cells_hit;       /* cells with count > 0 */
+    uint32_t reserved;
+    float    o[3], a[3], u[3], v[3];                /* the map frame (fp32, as the points were binned with) */
+    float    R;               /* fit.model radius */
+    float    t_min, station_length, sector_angle;   /* fp32 binning constants: t_min, ds, dtheta = 2 pi / n_sectors */
+} gm_surface_info;
+
+/* Host only: the defaults of the table above. */
+void gm_surface_default_params(gm_surface_params *p);
+/* Map parameters of the frames submitted after the call (every slot; a captured graph reads them from the device).
+ * GM_ERR_NOT_READY while any slot holds a submitted frame that has not been waited for; GM_ERR_INVALID_ARG outside the
+ * limits.  Works on any context (the stage call takes its own parameters). */
+gm_status gm_set_surface_params(gm_ctx *ctx, const gm_surface_params *p);
+/* The map of a completed slot (GM_ERR_UNSUPPORTED for a context created without GM_CFG_SURFACE_MAP).  info is required;
+ * cells (row-major [n_stations][n_sectors]) may be NULL with capacity 0: *n_out = n_stations * n_sectors, and a short
+ * buffer returns GM_ERR_CAPACITY (info is filled either way).  For a group's streamed frame: the rank's context. */
+gm_status gm_get_surface_map(gm_ctx *ctx, uint32_t slot, gm_surface_info *info, gm_surface_cell *cells, uint32_t capacity,
+                             uint32_t *n_out);
+/* Per valid point of a completed slot: residual e and cell index (either pointer may be NULL); *n_out = n_valid. */
+gm_status gm_get_surface_points(gm_ctx *ctx, uint32_t slot, float *residual, int32_t *cell, uint32_t capacity,
+                                uint32_t *n_out);
+/* The map as one stage call (host buffers, blocking, slot 0; the frame's kernel).  xyz rows of 3 floats; labels (may be
+ * NULL: no point is plane); model7 = (c, d, R) as gm_cylinder_fit.model (a non-finite row gives GM_SURF_NO_MODEL);
+ * p (NULL: defaults).  cells needs n_stations * n_sectors records (GM_ERR_CAPACITY otherwise); residual / cell (may be
+ * NULL) n entries.  Works on any context.  Fed a frame's valid cloud, labels and fit.model with the frame's
+ * parameters, it returns that frame's map bit for bit. */
+gm_status gm_surface_map(gm_ctx *ctx, const float *xyz, uint32_t n, const uint8_t *labels, const float model7[7],
+                         const gm_surface_params *p, gm_surface_info *info, gm_surface_cell *cells, uint32_t capacity,
+                         float *residual, int32_t *cell);
 
 /* "Compressed map" record of a completed slot.  The reference defines no such
  * output; this is a build-defined format: header, primitive records,
