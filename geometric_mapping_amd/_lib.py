@@ -59,6 +59,9 @@ GM_SURF_OK = 0
 GM_SURF_NO_MODEL = 1
 GM_SURF_UP_FALLBACK = 1 << 8
 
+GM_WALL_MAX_CELLS = 1 << 24
+GM_WALL_MAX_SECTORS = 4096
+
 GM_N_STAGES = 9
 STAGE_NAMES = ("upload", "crop", "grid", "normals", "compact", "frame", "voxel", "ransac", "total")
 
@@ -109,6 +112,31 @@ class SurfaceInfo(C.Structure):
                 ("cells_hit", C.c_uint32), ("reserved", C.c_uint32),
                 ("o", C.c_float * 3), ("a", C.c_float * 3), ("u", C.c_float * 3), ("v", C.c_float * 3),
                 ("R", C.c_float), ("t_min", C.c_float), ("station_length", C.c_float), ("sector_angle", C.c_float)]
+
+
+class WallParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_stations", C.c_uint32), ("n_sectors", C.c_uint32), ("reserved", C.c_uint32),
+                ("station_length", C.c_double), ("t_min", C.c_double), ("gate", C.c_double),
+                ("point", C.c_double * 3), ("direction", C.c_double * 3), ("radius", C.c_double),
+                ("up", C.c_double * 3), ("forward", C.c_double * 3)]
+
+
+class WallRawCell(C.Structure):
+    _fields_ = [("sum", C.c_int64), ("count", C.c_uint32), ("min_key", C.c_uint32), ("max_key", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class WallAddInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("status", C.c_uint32), ("anchor_station", C.c_int64),
+                ("o", C.c_float * 3), ("a", C.c_float * 3), ("u", C.c_float * 3), ("v", C.c_float * 3),
+                ("R", C.c_float), ("station_length", C.c_float), ("sector_angle", C.c_float), ("gate", C.c_float)]
+
+
+class WallInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("status", C.c_uint32), ("n_stations", C.c_uint32), ("n_sectors", C.c_uint32),
+                ("frames", C.c_uint64), ("mapped", C.c_uint64), ("outside", C.c_uint64), ("beyond_gate", C.c_uint64),
+                ("plane", C.c_uint64), ("cells_hit", C.c_uint64),
+                ("o", C.c_double * 3), ("a", C.c_double * 3), ("u", C.c_double * 3), ("v", C.c_double * 3), ("R", C.c_double)]
 
 
 class GmError(RuntimeError):
@@ -170,6 +198,8 @@ def load():
     cfgp, cloudp, resp = C.POINTER(Config), C.POINTER(Cloud), C.POINTER(FrameResult)
     fitp = C.POINTER(CylinderFit)
     sprmp, scellp, sinfop = C.POINTER(SurfaceParams), C.POINTER(SurfaceCell), C.POINTER(SurfaceInfo)
+    wprmp, wrawp, waddp, winfop = C.POINTER(WallParams), C.POINTER(WallRawCell), C.POINTER(WallAddInfo), C.POINTER(WallInfo)
+    u64, u64p = C.c_uint64, C.POINTER(C.c_uint64)
     proto = {
         "gm_create": (C.c_int, [cfgp, C.POINTER(vp)]),
         "gm_destroy": (None, [vp]),
@@ -215,6 +245,17 @@ def load():
         "gm_get_surface_map": (C.c_int, [vp, u32, sinfop, scellp, u32, u32p]),
         "gm_get_surface_points": (C.c_int, [vp, u32, fp, i32p, u32, u32p]),
         "gm_surface_map": (C.c_int, [vp, fp, u32, u8p, fp, sprmp, sinfop, scellp, u32, fp, i32p]),
+        "gm_wall_default_params": (None, [wprmp]),
+        "gm_wall_map_create": (C.c_int, [vp, wprmp, C.POINTER(vp)]),
+        "gm_wall_map_destroy": (None, [vp]),
+        "gm_wall_map_add_frame": (C.c_int, [vp, vp, u32, dp, waddp]),
+        "gm_wall_map_add_points": (C.c_int, [vp, fp, u32, u8p, dp, waddp, fp, i32p]),
+        "gm_wall_map_sync": (C.c_int, [vp]),
+        "gm_wall_map_info": (C.c_int, [vp, winfop]),
+        "gm_wall_map_read": (C.c_int, [vp, u32, u32, scellp, u64, u64p]),
+        "gm_wall_map_read_raw": (C.c_int, [vp, u32, u32, wrawp, u64, u64p]),
+        "gm_wall_map_add_raw": (C.c_int, [vp, u32, u32, wrawp]),
+        "gm_wall_map_clear": (C.c_int, [vp, u32, u32]),
         "gm_group_create": (C.c_int, [cfgp, i32p, u32, u32, C.POINTER(vp)]),
         "gm_group_destroy": (None, [vp]),
         "gm_group_size": (u32, [vp]),

@@ -20,7 +20,7 @@ from ._lib import (GM_CFG_CYLINDER_FIT, GM_CFG_DEFAULT, GM_CFG_KEEP_COUNTS, GM_C
                    GM_CLOUD_BIGENDIAN, GM_CLOUD_DEVICE, GM_CLOUD_PINNED, GM_ERR_CAPACITY, GM_ERR_NOT_READY, GM_OK, Cloud, Config,
                    CylinderFit, FrameResult, GmError, STAGE_NAMES)
 
-__all__ = ["GeometricMapping", "GeometricMappingGroup", "GmError", "solve_local_frame", "decode_compressed_map",
+__all__ = ["GeometricMapping", "GeometricMappingGroup", "WallMap", "GmError", "solve_local_frame", "decode_compressed_map",
            "GM_CFG_CYLINDER_FIT"]
 
 
@@ -71,6 +71,9 @@ class GeometricMapping:
             for p in getattr(self, "_pinned", []):
                 self._L.gm_host_free(self._ctx, p)
             self._pinned = []
+            for m in list(getattr(self, "_walls", [])):   # (gm_destroy frees the maps: their handles die here)
+                m._map = None
+            self._walls = []
             self._L.gm_destroy(self._ctx)
             self._ctx = None
 
@@ -483,6 +486,175 @@ class GeometricMapping:
         self._check(self._L.gm_surface_map(self._ctx, _f32(xyz), len(xyz), lp, _f32(m), C.byref(p), C.byref(info), cells,
                                            nc, _f32(res), cell.ctypes.data_as(C.POINTER(C.c_int32))))
         return (*self._surface(info, cells), res[:len(xyz)].copy(), cell[:len(xyz)].copy())
+
+    def wall_map(self, **params):
+        """A persistent wall map owned by this context (gm_wall_map_create): WallMap.  Keywords: gm_wall_params fields
+        (n_stations, n_sectors, station_length, t_min, gate, point, direction, radius, up, forward)."""
+        return WallMap(self, **params)
+
+
+RAW_CELL = np.dtype([("sum", "<i8"), ("count", "<u4"), ("min_key", "<u4"), ("max_key", "<u4"), ("reserved", "<u4")])
+_CELL = np.dtype([("count", "<u4"), ("mean", "<f4"), ("min", "<f4"), ("max", "<f4")])
+_WALL_VEC = ("point", "direction", "up", "forward")
+
+
+class WallMap:
+    """One gm_wall_map: a device-resident developed wall map against a design cylinder, accumulated over posed frames
+    (include/gm_hip.h states the rule).  Created by GeometricMapping.wall_map(); dies with its context."""
+
+    def __init__(self, ctx, **params):
+        self._ctx, self._L = ctx, ctx._L
+        self._map = None
+        p = self.params(**params)
+        h = C.c_void_p()
+        ctx._check(self._L.gm_wall_map_create(ctx._ctx, C.byref(p), C.byref(h)))
+        self._map, self.prm = h, p
+        self.n_stations, self.n_sectors = int(p.n_stations), int(p.n_sectors)
+        if not hasattr(ctx, "_walls"):
+            ctx._walls = []
+        ctx._walls.append(self)
+
+    @staticmethod
+    def params(**kw):
+        """gm_wall_params with the library's defaults, then the keywords."""
+        p = _lib.WallParams()
+        _lib.load().gm_wall_default_params(C.byref(p))
+        for k, v in kw.items():
+            if k in _WALL_VEC:
+                getattr(p, k)[:] = [float(x) for x in v]
+            elif not hasattr(p, k) or k == "struct_size":
+                raise TypeError(f"unknown wall map parameter {k!r}")
+            else:
+                setattr(p, k, v)
+        return p
+
+    def close(self):
+        if self._map is not None:
+            self._L.gm_wall_map_destroy(self._map)
+            self._map = None
+            if self in getattr(self._ctx, "_walls", []):
+                self._ctx._walls.remove(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _h(self):
+        if self._map is None:
+            raise ValueError("the wall map is closed (or its context is)")
+        return self._map
+
+    @staticmethod
+    def _pose(pose):
+        m = np.asarray(pose, dtype=np.float64)
+        if m.shape == (4, 4):
+            m = m[:3]
+        if m.shape != (3, 4):
+            raise ValueError("pose must be a (3, 4) or (4, 4) array")
+        return np.ascontiguousarray(m)
+
+    @staticmethod
+    def _add_info(i):
+        d = dict(status=int(i.status), anchor_station=int(i.anchor_station))
+        for k in ("o", "a", "u", "v"):
+            d[k] = np.array(getattr(i, k)[:], dtype=np.float32)
+        for k in ("R", "station_length", "sector_angle", "gate"):
+            d[k] = np.float32(getattr(i, k))
+        return d
+
+    def add_frame(self, slot=0, pose=np.eye(4)[:3]):
+        """gm_wall_map_add_frame: enqueue the slot's last submitted frame under `pose` (sensor -> map).  Returns the add
+        info dict (computed on the host; the kernel may still be running)."""
+        m = self._pose(pose)
+        i = _lib.WallAddInfo()
+        self._ctx._check(self._L.gm_wall_map_add_frame(self._h(), self._ctx._ctx, slot, m.ctypes.data_as(C.POINTER(C.c_double)),
+                                                       C.byref(i)))
+        return self._add_info(i)
+
+    def add_points(self, cloud, pose=np.eye(4)[:3], labels=None, outputs=True):
+        """gm_wall_map_add_points on a host cloud [n,3]: (add info, residual [n] float32, cell [n] int32); outputs False
+        skips the per-point arrays (None, None)."""
+        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+        m = self._pose(pose)
+        lab, lp = GeometricMapping._u8(labels)
+        i = _lib.WallAddInfo()
+        n = len(xyz)
+        res = np.empty(max(n, 1), dtype=np.float32) if outputs else None
+        cell = np.empty(max(n, 1), dtype=np.int32) if outputs else None
+        self._ctx._check(self._L.gm_wall_map_add_points(
+            self._h(), _f32(xyz), n, lp, m.ctypes.data_as(C.POINTER(C.c_double)), C.byref(i),
+            _f32(res) if outputs else None, cell.ctypes.data_as(C.POINTER(C.c_int32)) if outputs else None))
+        return self._add_info(i), (res[:n].copy() if outputs else None), (cell[:n].copy() if outputs else None)
+
+    def sync(self):
+        self._ctx._check(self._L.gm_wall_map_sync(self._h()))
+
+    def info(self):
+        i = _lib.WallInfo()
+        self._ctx._check(self._L.gm_wall_map_info(self._h(), C.byref(i)))
+        d = {k: int(getattr(i, k)) for k in ("status", "n_stations", "n_sectors", "frames", "mapped", "outside", "beyond_gate",
+                                             "plane", "cells_hit")}
+        for k in ("o", "a", "u", "v"):
+            d[k] = np.array(getattr(i, k)[:], dtype=np.float64)
+        d["R"] = float(i.R)
+        return d
+
+    def _window(self, station0, n):
+        return int(station0), int(self.n_stations - station0 if n is None else n)
+
+    def read(self, station0=0, n=None):
+        """gm_wall_map_read: (count, mean, min, max) of stations [station0, station0 + n), each shaped (n, n_sectors)."""
+        s0, n = self._window(station0, n)
+        nc = n * self.n_sectors
+        buf = np.empty(max(nc, 1), dtype=_CELL)
+        got = C.c_uint64(0)
+        self._ctx._check(self._L.gm_wall_map_read(self._h(), s0, n, buf.ctypes.data_as(C.POINTER(_lib.SurfaceCell)), nc,
+                                                  C.byref(got)))
+        b = buf[:nc].reshape(n, self.n_sectors)
+        return tuple(np.ascontiguousarray(b[k]) for k in ("count", "mean", "min", "max"))
+
+    def read_raw(self, station0=0, n=None):
+        """gm_wall_map_read_raw: a structured array (RAW_CELL: sum, count, min_key, max_key, reserved) shaped (n, n_sectors)."""
+        s0, n = self._window(station0, n)
+        nc = n * self.n_sectors
+        buf = np.zeros(max(nc, 1), dtype=RAW_CELL)
+        got = C.c_uint64(0)
+        self._ctx._check(self._L.gm_wall_map_read_raw(self._h(), s0, n, buf.ctypes.data_as(C.POINTER(_lib.WallRawCell)), nc,
+                                                      C.byref(got)))
+        return buf[:nc].reshape(n, self.n_sectors).copy()
+
+    def add_raw(self, raw, station0=0):
+        """gm_wall_map_add_raw: merge a (n, n_sectors) RAW_CELL window (counts and sums add, keys take the maximum)."""
+        raw = np.ascontiguousarray(raw, dtype=RAW_CELL)
+        if raw.ndim != 2 or raw.shape[1] != self.n_sectors:
+            raise ValueError("raw must be shaped (n, n_sectors)")
+        self._ctx._check(self._L.gm_wall_map_add_raw(self._h(), int(station0), raw.shape[0],
+                                                     raw.ctypes.data_as(C.POINTER(_lib.WallRawCell))))
+
+    def clear(self, station0=0, n=None):
+        s0, n = self._window(station0, n)
+        self._ctx._check(self._L.gm_wall_map_clear(self._h(), s0, n))
+
+    def save(self, path):
+        """The parameters and the raw cells as one .npz (numpy only)."""
+        p = self.prm
+        kw = {k: np.array(getattr(p, k)[:], dtype=np.float64) for k in _WALL_VEC}
+        np.savez_compressed(path, n_stations=np.uint32(p.n_stations), n_sectors=np.uint32(p.n_sectors),
+                            station_length=np.float64(p.station_length), t_min=np.float64(p.t_min), gate=np.float64(p.gate),
+                            radius=np.float64(p.radius), raw=self.read_raw(), **kw)
+
+    @staticmethod
+    def load(ctx, path):
+        """A new map on ctx with the file's parameters and cells (the per-class totals are not part of a file)."""
+        with np.load(path) as z:
+            kw = {k: z[k].tolist() for k in _WALL_VEC}
+            m = WallMap(ctx, n_stations=int(z["n_stations"]), n_sectors=int(z["n_sectors"]),
+                        station_length=float(z["station_length"]), t_min=float(z["t_min"]), gate=float(z["gate"]),
+                        radius=float(z["radius"]), **kw)
+            m.add_raw(z["raw"].astype(RAW_CELL, copy=False))
+        return m
 
 
 def decode_compressed_map(buf):

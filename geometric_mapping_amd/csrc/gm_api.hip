@@ -955,6 +955,7 @@ void gm_destroy(gm_ctx *ctx)
 {
     if (!ctx) return;
     hipSetDevice(ctx->device);
+    gm_wall_free_all(ctx);   // (waits for the adds still running on the slots' streams)
     if (ctx->slots) {
         for (uint32_t i = 0; i < ctx->n_slots; ++i) {
             Slot &sl = ctx->slots[i];

@@ -233,6 +233,62 @@ __host__ __device__ __forceinline__ float ordered_to_float(uint32_t o)
 #endif
 }
 
+// ---- the per-point chain of the wall maps (include/gm_hip.h states it): k_surface.hip bins against the frame's fitted
+// cylinder, k_wall.hip against the design cylinder seen from the frame.  fp32 with explicit roundings, so both kernels,
+// every grid and every launch site give the same bits.
+__device__ __forceinline__ float surf_dot3(float x, float y, float z, const float (&b)[3])
+{
+    return __fmaf_rn(x, b[0], __fmaf_rn(y, b[1], __fmul_rn(z, b[2])));
+}
+// q = p - o, t = q.a, w = q - t a; returns e = |w| - R
+__device__ __forceinline__ float surf_residual(const float4 &p, const float (&o)[3], const float (&a)[3], float R, float &t,
+                                               float &wx, float &wy, float &wz)
+{
+    const float qx = __fsub_rn(p.x, o[0]), qy = __fsub_rn(p.y, o[1]), qz = __fsub_rn(p.z, o[2]);
+    t = surf_dot3(qx, qy, qz, a);
+    wx = __fmaf_rn(-t, a[0], qx); wy = __fmaf_rn(-t, a[1], qy); wz = __fmaf_rn(-t, a[2], qz);
+    return __fsub_rn(__fsqrt_rn(__fmaf_rn(wx, wx, __fmaf_rn(wy, wy, __fmul_rn(wz, wz)))), R);
+}
+// floor((t - t_min) / ds), still a float: the caller checks the range before it converts
+__device__ __forceinline__ float surf_station(float t, float t_min, float ds)
+{
+    return floorf(__fdiv_rn(__fsub_rn(t, t_min), ds));
+}
+// k = min(floor(phi / dtheta), n_sectors - 1), phi = atan2(w.v, w.u) folded to [0, 2 pi)
+__device__ __forceinline__ uint32_t surf_sector(float wx, float wy, float wz, const float (&u)[3], const float (&v)[3],
+                                                float two_pi, float sector_angle, uint32_t nsec)
+{
+    const float th = atan2f(surf_dot3(wx, wy, wz, v), surf_dot3(wx, wy, wz, u));
+    const float phi = th < 0.0f ? __fadd_rn(th, two_pi) : th;
+    const uint32_t kk = (uint32_t)floorf(__fdiv_rn(phi, sector_angle));
+    return kk < nsec - 1u ? kk : nsec - 1u;
+}
+// runs of one cell in consecutive lanes -> the run's head lane (segmented reduction; lidar rings put ~20 consecutive
+// points into one sector).  Wave-uniform call.  Returns whether this lane still has to add its (merged) contribution.
+__device__ __forceinline__ bool surf_merge_runs(int cell, uint32_t &cn, unsigned long long &sm, uint32_t &lo, uint32_t &hi)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const int prev = __shfl_up(cell, 1, kWave);
+    const bool dup = lane > 0 && cell >= 0 && prev == cell;
+    const unsigned long long dmask = __ballot(dup);
+    if (dmask) {
+        const unsigned long long above = lane < kWave - 1 ? (~dmask & (~0ull << (lane + 1))) : 0ull;
+        const int tail = above ? __ffsll((long long)above) - 2 : kWave - 1;   // last lane of this lane's run
+#pragma unroll
+        for (int o = 1; o < kWave; o <<= 1) {
+            const uint32_t ocn = __shfl_down(cn, o, kWave), olo = __shfl_down(lo, o, kWave),
+                           ohi = __shfl_down(hi, o, kWave);
+            const unsigned long long osm = __shfl_down(sm, o, kWave);
+            if (lane + o <= tail) {
+                cn += ocn; sm += osm;
+                lo = lo > olo ? lo : olo;
+                hi = hi > ohi ? hi : ohi;
+            }
+        }
+    }
+    return cell >= 0 && !dup;
+}
+
 __device__ __forceinline__ bool finite3(float x, float y, float z)
 {
     return isfinite(x) && isfinite(y) && isfinite(z);

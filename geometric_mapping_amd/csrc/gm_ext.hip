@@ -83,6 +83,10 @@ gm_status score(gm_ctx *ctx, int model, const float *xyz, uint32_t n, const uint
 
 }  // namespace
 
+namespace gm {
+gm_status gm_upload_xyz(gm_ctx *ctx, Slot &sl, const float *xyz, uint32_t n, float4 *dst) { return upload_xyz(ctx, sl, xyz, n, dst); }
+}  // namespace gm
+
 extern "C" {
 
 int gm_ext_available(void) { return 1; }

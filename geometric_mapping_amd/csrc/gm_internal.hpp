@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <vector>
 
 #include "../../include/gm_hip.h"
 #include "gm_device.hpp"
@@ -165,6 +166,7 @@ struct gm_ctx {
     double own_lo, own_hi;
     bool force_voxel_sort = false;
     gm_surface_params surf;   // gm_set_surface_params (the frames' map parameters)
+    std::vector<gm_wall_map *> walls;   // persistent wall maps created from this context (gm_wall.hip), freed with it
     std::string err;
 };
 
@@ -286,6 +288,49 @@ void launch_surface_map(const SurfArgs &a, uint32_t n_cap, hipStream_t s);
 SurfParams surface_device_params(const gm_surface_params &p);
 gm_status gm_check_surface_params(const gm_surface_params *p);
 gm_status gm_ensure_surface(gm_ctx *ctx, Slot &sl);
+// k_wall.hip (persistent wall map, gm_wall_*): one launch per add, small kernels for read / merge / clear
+constexpr int kWallTotals = 8;   // u64 words behind the cells: mapped, outside, beyond_gate, plane, cells_hit scratch, pad
+constexpr uint32_t kWallPointsPerBlock = 8192, kWallMinPointsPerBlock = 2048, kWallSmallBlocks = 48;
+struct WallTable {   // SoA over the map's cells
+    unsigned long long *sum;
+    uint32_t *cnt, *lo, *hi;       // count, ~ordered(min e), ordered(max e)
+    unsigned long long *totals;    // [kWallTotals]
+};
+struct WallArgs {
+    const float4 *pts;
+    const uint8_t *labels;     // nullptr: no point is plane
+    const uint32_t *n_ptr;     // device point count (nullptr: n_host)
+    uint32_t n_host;
+    uint32_t n_stations, n_sectors;
+    int32_t win_first;         // the LDS window: stations [anchor + win_first, anchor + win_first + win_stations)
+    uint32_t win_stations;     // win_stations * n_sectors <= GM_SURF_MAX_CELLS
+    int64_t anchor;            // j_f
+    float o[3], a[3], u[3], v[3];   // the frame-local map frame in sensor coordinates
+    float R, station_length, gate, sector_angle, two_pi;
+    WallTable table;
+    float *res;                // stage call only (nullptr in the frame path)
+    int32_t *cell;
+};
+// the arrays of a table of ncell cells at base: sum i64 | count u32 | lo u32 | hi u32 | totals u64 [kWallTotals]
+__host__ __device__ inline WallTable wall_table(uint8_t *base, uint64_t ncell)
+{
+    WallTable t;
+    t.sum = reinterpret_cast<unsigned long long *>(base);
+    t.cnt = reinterpret_cast<uint32_t *>(base + 8 * ncell);
+    t.lo = t.cnt + ncell;
+    t.hi = t.lo + ncell;
+    t.totals = reinterpret_cast<unsigned long long *>(base + ((20 * ncell + 7) & ~(uint64_t)7));
+    return t;
+}
+size_t wall_table_bytes(uint64_t ncell);
+// n_cap: the most points the launch can see (the grid is sized by it); points_per_block 0: the default rule
+void launch_wall_add(const WallArgs &a, uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
+void launch_wall_read(const WallTable &T, uint64_t first, uint64_t n, gm_surface_cell *out, hipStream_t s);
+void launch_wall_read_raw(const WallTable &T, uint64_t first, uint64_t n, gm_wall_raw_cell *out, hipStream_t s);
+void launch_wall_merge_raw(const WallTable &T, uint64_t first, uint64_t n, const gm_wall_raw_cell *in, hipStream_t s);
+void launch_wall_clear(const WallTable &T, uint64_t first, uint64_t n, bool totals_too, hipStream_t s);
+void launch_wall_count(const WallTable &T, uint64_t n, hipStream_t s);
+void gm_wall_free_all(gm_ctx *ctx);   // gm_destroy: the maps still alive
 // k_nearest.hip
 void launch_nearest(const float4 *pts, const uint32_t *n_ptr, uint32_t n_cap, const float4 *queries,
                     const uint32_t *nq_ptr, uint32_t nq_cap, unsigned long long *best, int32_t *idx, hipStream_t s,
@@ -298,6 +343,7 @@ gm_status gm_ensure_capacity(gm_ctx *ctx, Slot &sl, uint32_t n, size_t raw_bytes
 gm_status gm_ensure_ext(gm_ctx *ctx, Slot &sl, uint32_t H);
 gm_status gm_begin_stage(gm_ctx *ctx, Slot *&sl);
 gm_status gm_check_slot(gm_ctx *ctx, uint32_t slot);
+gm_status gm_upload_xyz(gm_ctx *ctx, Slot &sl, const float *xyz, uint32_t n, float4 *dst);   // gm_ext.hip: rows of 3 floats through the slot's staging
 void launch_minmax(const float4 *pts, const uint32_t *n_ptr, uint32_t n_cap, DevCounters *ctr, hipStream_t s);
 
 }  // namespace gm

@@ -1,0 +1,455 @@
+// gm_wall.hip -- C ABI of the persistent wall map (gm_wall_*; include/gm_hip.h states the rule).  Host logic only: the
+// design frame and the per-add frame in fp64, the station window of a frame, ownership.  Kernels are in k_wall.hip.
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "gm_internal.hpp"
+
+using namespace gm;
+
+struct gm_wall_map {
+    gm_ctx *ctx = nullptr;
+    gm_wall_params prm;
+    uint64_t ncell = 0;
+    uint8_t *base = nullptr;       // the device table (zeroed at creation)
+    WallTable table;
+    double o[3], a[3], u[3], v[3], R;   // the design frame, fp64, not rounded
+    uint32_t status = GM_SURF_OK;
+    uint64_t frames = 0;
+    hipStream_t stream = nullptr;  // the small kernels (read / merge / clear / count) and their copies
+    std::vector<uint8_t> pending;  // per slot of ctx: an add was enqueued on its stream since the last sync
+    uint8_t *stage = nullptr;      // device staging of the window calls, kStageCells records
+    float *pt_res = nullptr;       // gm_wall_map_add_points' per-point outputs (grow-only)
+    int32_t *pt_cell = nullptr;
+    uint32_t pt_cap = 0;
+    uint32_t points_per_block = 0; // 0: the kernel's default (GM_WALL_POINTS_PER_BLOCK: measurements)
+};
+
+namespace {
+
+constexpr uint64_t kStageCells = 1u << 20;   // cells per chunk of a window call (24 MiB of raw records)
+
+#define GMW_HIP(ctx, call)                                                           \
+    do {                                                                             \
+        hipError_t e__ = (call);                                                     \
+        if (e__ != hipSuccess) {                                                     \
+            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);         \
+            return (e__ == hipErrorOutOfMemory) ? GM_ERR_OOM : GM_ERR_DEVICE;        \
+        }                                                                            \
+    } while (0)
+
+double dot(const double *x, const double *y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2]; }
+
+gm_status check_params(const gm_wall_params *p)
+{
+    if (!p || p->struct_size != sizeof(gm_wall_params)) return GM_ERR_INVALID_ARG;
+    if (p->n_stations < 1u || p->n_sectors < 1u || p->n_sectors > GM_WALL_MAX_SECTORS ||
+        (uint64_t)p->n_stations * p->n_sectors > GM_WALL_MAX_CELLS)
+        return GM_ERR_INVALID_ARG;
+    if (!(p->station_length > 0.0) || !isfinite(p->station_length) || !((float)p->station_length > 0.0f) ||
+        !isfinite((float)p->station_length) || !isfinite(p->t_min) || !(p->gate > 0.0) || !(p->gate <= 8.0) ||
+        !(p->radius > 0.0) || !isfinite((float)p->radius))
+        return GM_ERR_INVALID_ARG;
+    double up2 = 0.0, fw2 = 0.0, d2 = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        if (!isfinite(p->up[k]) || !isfinite(p->forward[k]) || !isfinite(p->direction[k]) || !isfinite(p->point[k]))
+            return GM_ERR_INVALID_ARG;
+        up2 += p->up[k] * p->up[k];
+        fw2 += p->forward[k] * p->forward[k];
+        d2 += p->direction[k] * p->direction[k];
+    }
+    if (!(up2 > 0.0) || !(fw2 > 0.0) || !(d2 > 0.0) || !isfinite(up2) || !isfinite(fw2) || !isfinite(d2)) return GM_ERR_INVALID_ARG;
+    return GM_OK;
+}
+
+// the design frame of include/gm_hip.h: k_surface.hip's surf_frame on fp64 inputs, kept in fp64
+void design_frame(gm_wall_map *m)
+{
+    const gm_wall_params &p = m->prm;
+    const double dn = sqrt(dot(p.direction, p.direction));
+    const double s = dot(p.direction, p.forward);
+    for (int k = 0; k < 3; ++k) m->a[k] = (s >= 0.0 ? p.direction[k] : -p.direction[k]) / dn;
+    const double ca = dot(p.point, m->a), ua = dot(p.up, m->a);
+    double u[3];
+    for (int k = 0; k < 3; ++k) u[k] = p.up[k] - ua * m->a[k];
+    const double ul = sqrt(dot(u, u)), upl = sqrt(dot(p.up, p.up));
+    m->status = GM_SURF_OK;
+    if (ul < 0.1 * upl) {
+        double e2[3];
+        fit_basis(m->a, u, e2);
+        m->status |= GM_SURF_UP_FALLBACK;
+    } else {
+        for (int k = 0; k < 3; ++k) u[k] /= ul;
+    }
+    const double *a = m->a;
+    const double v[3] = {a[1] * u[2] - a[2] * u[1], a[2] * u[0] - a[0] * u[2], a[0] * u[1] - a[1] * u[0]};
+    for (int k = 0; k < 3; ++k) {
+        m->o[k] = p.point[k] - ca * a[k];
+        m->u[k] = u[k];
+        m->v[k] = v[k];
+    }
+    m->R = p.radius;
+}
+
+// The per-add frame: pose check, anchor, (o', a', u', v') in sensor coordinates, and the kernel's arguments but for the
+// buffers.  The context's crop bound (a cube around the sensor) sizes the LDS window.
+gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info *info, WallArgs &w)
+{
+    gm_ctx *ctx = m->ctx;
+    if (!pose) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: NULL pose");
+    double Rm[3][3], tr[3];
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 4; ++c)
+            if (!isfinite(pose[4 * r + c])) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose is not finite");
+        for (int c = 0; c < 3; ++c) Rm[r][c] = pose[4 * r + c];
+        tr[r] = pose[4 * r + 3];
+    }
+    double dev = 0.0;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const double g = Rm[0][i] * Rm[0][j] + Rm[1][i] * Rm[1][j] + Rm[2][i] * Rm[2][j] - (i == j ? 1.0 : 0.0);
+            dev = std::max(dev, fabs(g));
+        }
+    const double det = Rm[0][0] * (Rm[1][1] * Rm[2][2] - Rm[1][2] * Rm[2][1]) - Rm[0][1] * (Rm[1][0] * Rm[2][2] - Rm[1][2] * Rm[2][0]) +
+                       Rm[0][2] * (Rm[1][0] * Rm[2][1] - Rm[1][1] * Rm[2][0]);
+    if (!(dev <= 1e-6) || !(det > 0.0))
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose rotation is not orthonormal to 1e-6 or is a reflection");
+    const gm_wall_params &p = m->prm;
+    const double ds = p.station_length;
+    const double rel[3] = {tr[0] - m->o[0], tr[1] - m->o[1], tr[2] - m->o[2]};
+    const double s = dot(rel, m->a);
+    const double jd = floor((s - p.t_min) / ds);
+    if (!(fabs(jd) < 4.0e18)) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose is too far along the axis");
+    const int64_t jf = (int64_t)jd;
+    const double off = p.t_min + jd * ds;
+    double of[3];   // o_f - tr
+    for (int k = 0; k < 3; ++k) of[k] = m->o[k] + off * m->a[k] - tr[k];
+    memset(&w, 0, sizeof(w));
+    double a1 = 0.0;   // |a'|_1: the reach of the crop cube along the axis
+    for (int c = 0; c < 3; ++c) {   // Rm^T x
+        const double oo = Rm[0][c] * of[0] + Rm[1][c] * of[1] + Rm[2][c] * of[2];
+        const double aa = Rm[0][c] * m->a[0] + Rm[1][c] * m->a[1] + Rm[2][c] * m->a[2];
+        const double uu = Rm[0][c] * m->u[0] + Rm[1][c] * m->u[1] + Rm[2][c] * m->u[2];
+        const double vv = Rm[0][c] * m->v[0] + Rm[1][c] * m->v[1] + Rm[2][c] * m->v[2];
+        w.o[c] = (float)oo; w.a[c] = (float)aa; w.u[c] = (float)uu; w.v[c] = (float)vv;
+        a1 += fabs(aa);
+    }
+    const double two_pi = 6.283185307179586476925286766559;
+    w.R = (float)m->R;
+    w.station_length = (float)ds;
+    w.gate = (float)p.gate;
+    w.sector_angle = (float)(two_pi / (double)p.n_sectors);
+    w.two_pi = (float)two_pi;
+    w.n_stations = p.n_stations;
+    w.n_sectors = p.n_sectors;
+    w.anchor = jf;
+    w.table = m->table;
+    // The LDS window: t = p.a' + (s - chainage of the anchor station's start) lies in [-B |a'|_1, B |a'|_1 + ds) for the
+    // points of the crop cube |p|_inf <= B, so their stations relative to the anchor in [floor(-reach), floor(reach) + 1].
+    // Whole stations, as many as the LDS table holds; a footprint beyond it is centred (the rest goes to the map directly).
+    const uint32_t wmax = GM_SURF_MAX_CELLS / p.n_sectors;   // >= 1: n_sectors <= 4096
+    const double reach = std::min(ctx->cfg.boxFilterBound * a1 / ds, 1.0e6);
+    const int64_t first = (int64_t)floor(-reach) - 1, last = (int64_t)floor(reach) + 2;   // one station of fp32 slack each side
+    const int64_t need = last - first + 1;
+    if (need <= (int64_t)wmax) {
+        w.win_first = (int32_t)first;
+        w.win_stations = (uint32_t)need;
+    } else {
+        w.win_first = -(int32_t)(wmax / 2);
+        w.win_stations = wmax;
+    }
+    if (info) {
+        memset(info, 0, sizeof(*info));
+        info->struct_size = (uint32_t)sizeof(gm_wall_add_info);
+        info->status = m->status;
+        info->anchor_station = jf;
+        for (int k = 0; k < 3; ++k) { info->o[k] = w.o[k]; info->a[k] = w.a[k]; info->u[k] = w.u[k]; info->v[k] = w.v[k]; }
+        info->R = w.R;
+        info->station_length = w.station_length;
+        info->sector_angle = w.sector_angle;
+        info->gate = w.gate;
+    }
+    return GM_OK;
+}
+
+gm_status sync_map(gm_wall_map *m)
+{
+    gm_ctx *ctx = m->ctx;
+    if (hipSetDevice(ctx->device) != hipSuccess) return gm_fail(ctx, GM_ERR_DEVICE, "hipSetDevice failed");
+    for (uint32_t i = 0; i < ctx->n_slots; ++i)
+        if (m->pending[i]) {
+            GMW_HIP(ctx, hipStreamSynchronize(ctx->slots[i].stream));
+            m->pending[i] = 0;
+        }
+    GMW_HIP(ctx, hipStreamSynchronize(m->stream));
+    return GM_OK;
+}
+
+gm_status check_window(gm_wall_map *m, uint32_t station0, uint32_t n, uint64_t capacity, uint64_t *n_out, const char *who)
+{
+    if ((uint64_t)station0 + n > m->prm.n_stations)
+        return gm_fail(m->ctx, GM_ERR_INVALID_ARG, "gm_wall_map: the window leaves [0, n_stations]");
+    const uint64_t nc = (uint64_t)n * m->prm.n_sectors;
+    if (n_out) *n_out = nc;
+    if (nc > capacity) return gm_fail(m->ctx, GM_ERR_CAPACITY, who);
+    return GM_OK;
+}
+
+void free_map(gm_wall_map *m)
+{
+    hipSetDevice(m->ctx->device);
+    for (uint32_t i = 0; i < m->ctx->n_slots; ++i)
+        if (m->pending[i] && m->ctx->slots[i].stream) hipStreamSynchronize(m->ctx->slots[i].stream);
+    if (m->stream) { hipStreamSynchronize(m->stream); hipStreamDestroy(m->stream); }
+    hipFree(m->base); hipFree(m->stage); hipFree(m->pt_res); hipFree(m->pt_cell);
+    delete m;
+}
+
+// one window call in chunks of the staging buffer: raw true -> gm_wall_raw_cell, else gm_surface_cell
+gm_status read_window(gm_wall_map *m, uint32_t station0, uint32_t n, void *cells, bool raw)
+{
+    gm_ctx *ctx = m->ctx;
+    const uint64_t first = (uint64_t)station0 * m->prm.n_sectors, total = (uint64_t)n * m->prm.n_sectors;
+    const size_t rec = raw ? sizeof(gm_wall_raw_cell) : sizeof(gm_surface_cell);
+    for (uint64_t done = 0; done < total; done += kStageCells) {
+        const uint64_t c = std::min(kStageCells, total - done);
+        if (raw) launch_wall_read_raw(m->table, first + done, c, reinterpret_cast<gm_wall_raw_cell *>(m->stage), m->stream);
+        else launch_wall_read(m->table, first + done, c, reinterpret_cast<gm_surface_cell *>(m->stage), m->stream);
+        GMW_HIP(ctx, hipGetLastError());
+        GMW_HIP(ctx, hipMemcpyAsync((uint8_t *)cells + done * rec, m->stage, c * rec, hipMemcpyDeviceToHost, m->stream));
+        GMW_HIP(ctx, hipStreamSynchronize(m->stream));
+    }
+    return GM_OK;
+}
+
+}  // namespace
+
+namespace gm {
+void gm_wall_free_all(gm_ctx *ctx)
+{
+    for (gm_wall_map *m : ctx->walls) free_map(m);
+    ctx->walls.clear();
+}
+}  // namespace gm
+
+extern "C" {
+
+void gm_wall_default_params(gm_wall_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(gm_wall_params);
+    p->n_stations = 4000;
+    p->n_sectors = 90;
+    p->station_length = 0.25;
+    p->t_min = 0.0;
+    p->gate = 0.25;
+    p->direction[0] = 1.0;
+    p->radius = 2.0;
+    p->up[2] = 1.0;
+    p->forward[0] = 1.0;
+}
+
+gm_status gm_wall_map_create(gm_ctx *ctx, const gm_wall_params *params, gm_wall_map **map)
+{
+    if (!ctx) return GM_ERR_INVALID_ARG;
+    if (!map) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_create: NULL map");
+    *map = nullptr;
+    if (check_params(params) != GM_OK)
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_create: NULL, struct_size mismatch or a parameter outside its limits");
+    if (hipSetDevice(ctx->device) != hipSuccess) return gm_fail(ctx, GM_ERR_DEVICE, "hipSetDevice failed");
+    gm_wall_map *m = new gm_wall_map;
+    m->ctx = ctx;
+    m->prm = *params;
+    m->ncell = (uint64_t)params->n_stations * params->n_sectors;
+    m->pending.assign(ctx->n_slots, 0);
+    if (const char *e = getenv("GM_WALL_POINTS_PER_BLOCK")) m->points_per_block = (uint32_t)strtoul(e, nullptr, 10);
+    design_frame(m);
+    auto body = [&]() -> gm_status {
+        GMW_HIP(ctx, hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+        GMW_HIP(ctx, hipMalloc((void **)&m->base, wall_table_bytes(m->ncell)));
+        GMW_HIP(ctx, hipMalloc((void **)&m->stage, std::min(kStageCells, m->ncell) * sizeof(gm_wall_raw_cell)));
+        GMW_HIP(ctx, hipMemsetAsync(m->base, 0, wall_table_bytes(m->ncell), m->stream));
+        GMW_HIP(ctx, hipStreamSynchronize(m->stream));
+        return GM_OK;
+    };
+    const gm_status st = body();
+    if (st != GM_OK) {
+        (void)hipGetLastError();
+        free_map(m);
+        return st;
+    }
+    m->table = wall_table(m->base, m->ncell);
+    ctx->walls.push_back(m);
+    *map = m;
+    return GM_OK;
+}
+
+void gm_wall_map_destroy(gm_wall_map *map)
+{
+    if (!map) return;
+    std::vector<gm_wall_map *> &w = map->ctx->walls;
+    w.erase(std::remove(w.begin(), w.end(), map), w.end());
+    free_map(map);
+}
+
+gm_status gm_wall_map_add_frame(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, const double pose[12], gm_wall_add_info *add_info)
+{
+    if (!map || !ctx) return GM_ERR_INVALID_ARG;
+    if (ctx != map->ctx) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_add_frame: the map belongs to another context");
+    if (slot >= ctx->n_slots) return gm_fail(ctx, GM_ERR_INVALID_ARG, "slot out of range");
+    Slot &sl = ctx->slots[slot];
+    if (!sl.submitted) return gm_fail(ctx, GM_ERR_NOT_READY, "gm_wall_map_add_frame: the slot holds no frame");
+    WallArgs w;
+    const gm_status st = add_frame_args(map, pose, add_info, w);
+    if (st != GM_OK) return st;
+    if (hipSetDevice(ctx->device) != hipSuccess) return gm_fail(ctx, GM_ERR_DEVICE, "hipSetDevice failed");
+    w.pts = sl.valid4;
+    w.labels = (ctx->cfg.flags & GM_CFG_RANSAC_PLANE) ? sl.labels : nullptr;   // (label 1 exists with the plane RANSAC only)
+    w.n_ptr = &sl.ctr->n_valid;
+    w.n_host = sl.n_in;
+    launch_wall_add(w, sl.n_in, map->points_per_block, sl.stream);
+    GMW_HIP(ctx, hipGetLastError());
+    map->pending[slot] = 1;
+    ++map->frames;
+    return GM_OK;
+}
+
+gm_status gm_wall_map_add_points(gm_wall_map *map, const float *xyz, uint32_t n, const uint8_t *labels, const double pose[12],
+                                 gm_wall_add_info *add_info, float *residual, int32_t *cell)
+{
+    if (!map) return GM_ERR_INVALID_ARG;
+    gm_ctx *ctx = map->ctx;
+    if (n && !xyz) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_add_points: NULL xyz");
+    WallArgs w;
+    gm_status st = add_frame_args(map, pose, add_info, w);
+    if (st != GM_OK) return st;
+    Slot *slp;
+    st = gm_begin_stage(ctx, slp);
+    if (st != GM_OK) return st;
+    Slot &sl = *slp;
+    st = gm_ensure_capacity(ctx, sl, n ? n : 1u, (size_t)(n ? n : 1u) * 16, true);
+    if (st != GM_OK) return st;
+    if ((residual || cell) && map->pt_cap < n) {
+        hipFree(map->pt_res); hipFree(map->pt_cell);
+        map->pt_res = nullptr; map->pt_cell = nullptr; map->pt_cap = 0;
+        GMW_HIP(ctx, hipMalloc((void **)&map->pt_res, (size_t)n * 4));
+        GMW_HIP(ctx, hipMalloc((void **)&map->pt_cell, (size_t)n * 4));
+        map->pt_cap = n;
+    }
+    st = gm_upload_xyz(ctx, sl, xyz, n, sl.valid4);
+    if (st != GM_OK) return st;
+    if (labels && n) GMW_HIP(ctx, hipMemcpyAsync(sl.labels, labels, n, hipMemcpyHostToDevice, sl.stream));
+    w.pts = sl.valid4;
+    w.labels = labels ? sl.labels : nullptr;
+    w.n_ptr = nullptr;
+    w.n_host = n;
+    w.res = residual ? map->pt_res : nullptr;
+    w.cell = cell ? map->pt_cell : nullptr;
+    launch_wall_add(w, n, map->points_per_block, sl.stream);
+    GMW_HIP(ctx, hipGetLastError());
+    if (residual && n) GMW_HIP(ctx, hipMemcpyAsync(residual, map->pt_res, (size_t)n * 4, hipMemcpyDeviceToHost, sl.stream));
+    if (cell && n) GMW_HIP(ctx, hipMemcpyAsync(cell, map->pt_cell, (size_t)n * 4, hipMemcpyDeviceToHost, sl.stream));
+    GMW_HIP(ctx, hipStreamSynchronize(sl.stream));
+    ++map->frames;
+    return GM_OK;
+}
+
+gm_status gm_wall_map_sync(gm_wall_map *map)
+{
+    if (!map) return GM_ERR_INVALID_ARG;
+    return sync_map(map);
+}
+
+gm_status gm_wall_map_info(gm_wall_map *map, gm_wall_info *info)
+{
+    if (!map) return GM_ERR_INVALID_ARG;
+    gm_ctx *ctx = map->ctx;
+    if (!info) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_info: NULL info");
+    gm_status st = sync_map(map);
+    if (st != GM_OK) return st;
+    unsigned long long tot[kWallTotals];
+    GMW_HIP(ctx, hipMemsetAsync(map->table.totals + 4, 0, 8, map->stream));
+    launch_wall_count(map->table, map->ncell, map->stream);
+    GMW_HIP(ctx, hipGetLastError());
+    GMW_HIP(ctx, hipMemcpyAsync(tot, map->table.totals, sizeof(tot), hipMemcpyDeviceToHost, map->stream));
+    GMW_HIP(ctx, hipStreamSynchronize(map->stream));
+    memset(info, 0, sizeof(*info));
+    info->struct_size = (uint32_t)sizeof(gm_wall_info);
+    info->status = map->status;
+    info->n_stations = map->prm.n_stations;
+    info->n_sectors = map->prm.n_sectors;
+    info->frames = map->frames;
+    info->mapped = tot[0]; info->outside = tot[1]; info->beyond_gate = tot[2]; info->plane = tot[3];
+    info->cells_hit = tot[4];
+    for (int k = 0; k < 3; ++k) { info->o[k] = map->o[k]; info->a[k] = map->a[k]; info->u[k] = map->u[k]; info->v[k] = map->v[k]; }
+    info->R = map->R;
+    return GM_OK;
+}
+
+gm_status gm_wall_map_read(gm_wall_map *map, uint32_t station0, uint32_t n, gm_surface_cell *cells, uint64_t capacity,
+                           uint64_t *n_out)
+{
+    if (!map) return GM_ERR_INVALID_ARG;
+    gm_status st = check_window(map, station0, n, capacity, n_out, "gm_wall_map_read: cell buffer too small");
+    if (st != GM_OK) return st;
+    if (!n) return sync_map(map);
+    if (!cells) return gm_fail(map->ctx, GM_ERR_INVALID_ARG, "gm_wall_map_read: NULL cells");
+    st = sync_map(map);
+    if (st != GM_OK) return st;
+    return read_window(map, station0, n, cells, false);
+}
+
+gm_status gm_wall_map_read_raw(gm_wall_map *map, uint32_t station0, uint32_t n, gm_wall_raw_cell *cells, uint64_t capacity,
+                               uint64_t *n_out)
+{
+    if (!map) return GM_ERR_INVALID_ARG;
+    gm_status st = check_window(map, station0, n, capacity, n_out, "gm_wall_map_read_raw: cell buffer too small");
+    if (st != GM_OK) return st;
+    if (!n) return sync_map(map);
+    if (!cells) return gm_fail(map->ctx, GM_ERR_INVALID_ARG, "gm_wall_map_read_raw: NULL cells");
+    st = sync_map(map);
+    if (st != GM_OK) return st;
+    return read_window(map, station0, n, cells, true);
+}
+
+gm_status gm_wall_map_add_raw(gm_wall_map *map, uint32_t station0, uint32_t n, const gm_wall_raw_cell *cells)
+{
+    if (!map) return GM_ERR_INVALID_ARG;
+    gm_ctx *ctx = map->ctx;
+    gm_status st = check_window(map, station0, n, ~0ull, nullptr, "");
+    if (st != GM_OK) return st;
+    if (n && !cells) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_add_raw: NULL cells");
+    st = sync_map(map);
+    if (st != GM_OK) return st;
+    const uint64_t first = (uint64_t)station0 * map->prm.n_sectors, total = (uint64_t)n * map->prm.n_sectors;
+    for (uint64_t done = 0; done < total; done += kStageCells) {
+        const uint64_t c = std::min(kStageCells, total - done);
+        GMW_HIP(ctx, hipMemcpyAsync(map->stage, cells + done, c * sizeof(gm_wall_raw_cell), hipMemcpyHostToDevice, map->stream));
+        launch_wall_merge_raw(map->table, first + done, c, reinterpret_cast<const gm_wall_raw_cell *>(map->stage), map->stream);
+        GMW_HIP(ctx, hipGetLastError());
+        GMW_HIP(ctx, hipStreamSynchronize(map->stream));
+    }
+    return GM_OK;
+}
+
+gm_status gm_wall_map_clear(gm_wall_map *map, uint32_t station0, uint32_t n)
+{
+    if (!map) return GM_ERR_INVALID_ARG;
+    gm_ctx *ctx = map->ctx;
+    gm_status st = check_window(map, station0, n, ~0ull, nullptr, "");
+    if (st != GM_OK) return st;
+    st = sync_map(map);
+    if (st != GM_OK) return st;
+    const bool all = station0 == 0 && n == map->prm.n_stations;
+    launch_wall_clear(map->table, (uint64_t)station0 * map->prm.n_sectors, (uint64_t)n * map->prm.n_sectors, all, map->stream);
+    GMW_HIP(ctx, hipGetLastError());
+    GMW_HIP(ctx, hipStreamSynchronize(map->stream));
+    if (all) map->frames = 0;
+    return GM_OK;
+}
+
+}  // extern "C"

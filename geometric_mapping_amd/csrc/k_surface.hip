@@ -9,7 +9,7 @@
 // another slot and the gm_surface_map stage call give the same bytes.
 //   1. every thread derives the map frame from the fit row in fp64 (a few dozen flops, the same bits in every thread);
 //   2. a block zeroes its private LDS table: sum i64 of rint(e 2^20), count u32, ~ordered(min e) u32, ordered(max e)
-//      u32 -- 20 B per cell, GM_SURF_MAX_CELLS = 4096 cells = 80 KiB of static LDS (no scratch; 78 VGPRs, so one
+//      u32 -- 20 B per cell, GM_SURF_MAX_CELLS = 4096 cells = 80 KiB of static LDS (no scratch; 80 VGPRs, so one
 //      1024-thread block per CU: 16 waves; -Rpass-analysis=kernel-resource-usage);
 //   3. grid-stride over the points: per point the class, e and the cell, coalesced stores of e and the cell index, and
 //      LDS integer atomics.  A wave whose lanes hold runs of one cell (lidar frames: ring by azimuth, ~20 consecutive
@@ -105,11 +105,6 @@ __device__ inline SurfFrame surf_frame(const gm_cylinder_fit *fit, const SurfPar
     return f;
 }
 
-__device__ __forceinline__ float dot3(float x, float y, float z, const float (&b)[3])
-{
-    return __fmaf_rn(x, b[0], __fmaf_rn(y, b[1], __fmul_rn(z, b[2])));
-}
-
 __global__ __launch_bounds__(kSurfThreads) void k_surface_map(SurfArgs a)
 {
     __shared__ unsigned long long s_sum[kSurfCells];
@@ -156,21 +151,16 @@ __global__ __launch_bounds__(kSurfThreads) void k_surface_map(SurfArgs a)
                 if (lab[k] == 1u) {
                     ++cls[3];
                 } else {
-                    const float qx = __fsub_rn(q[k].x, F.o[0]), qy = __fsub_rn(q[k].y, F.o[1]), qz = __fsub_rn(q[k].z, F.o[2]);
-                    const float t = dot3(qx, qy, qz, F.a);
-                    const float wx = __fmaf_rn(-t, F.a[0], qx), wy = __fmaf_rn(-t, F.a[1], qy), wz = __fmaf_rn(-t, F.a[2], qz);
-                    e = __fsub_rn(__fsqrt_rn(__fmaf_rn(wx, wx, __fmaf_rn(wy, wy, __fmul_rn(wz, wz)))), F.R);
+                    float t, wx, wy, wz;
+                    e = surf_residual(q[k], F.o, F.a, F.R, t, wx, wy, wz);
                     if (!(fabsf(e) <= p.gate)) {
                         ++cls[2];
                     } else {
-                        const float jf = floorf(__fdiv_rn(__fsub_rn(t, p.t_min), p.station_length));
+                        const float jf = surf_station(t, p.t_min, p.station_length);
                         if (!(jf >= 0.0f && jf < nst_f)) {
                             ++cls[1];
                         } else {
-                            const float th = atan2f(dot3(wx, wy, wz, F.v), dot3(wx, wy, wz, F.u));
-                            const float phi = th < 0.0f ? __fadd_rn(th, p.two_pi) : th;
-                            uint32_t kk = (uint32_t)floorf(__fdiv_rn(phi, p.sector_angle));
-                            kk = kk < nsec - 1u ? kk : nsec - 1u;
+                            const uint32_t kk = surf_sector(wx, wy, wz, F.u, F.v, p.two_pi, p.sector_angle, nsec);
                             cell = (int)((uint32_t)jf * nsec + kk);
                             ++cls[0];
                         }
@@ -187,26 +177,7 @@ __global__ __launch_bounds__(kSurfThreads) void k_surface_map(SurfArgs a)
                 hi = float_to_ordered(e);
                 lo = ~hi;
             }
-            // runs of one cell in consecutive lanes -> the run's head lane (segmented reduction over the run)
-            const int prev = __shfl_up(cell, 1, kWave);
-            const bool dup = lane > 0 && cell >= 0 && prev == cell;
-            const unsigned long long dmask = __ballot(dup);
-            if (dmask) {
-                const unsigned long long above = lane < kWave - 1 ? (~dmask & (~0ull << (lane + 1))) : 0ull;
-                const int tail = above ? __ffsll((long long)above) - 2 : kWave - 1;   // last lane of this lane's run
-#pragma unroll
-                for (int o = 1; o < kWave; o <<= 1) {
-                    const uint32_t ocn = __shfl_down(cn, o, kWave), olo = __shfl_down(lo, o, kWave),
-                                   ohi = __shfl_down(hi, o, kWave);
-                    const unsigned long long osm = __shfl_down(sm, o, kWave);
-                    if (lane + o <= tail) {
-                        cn += ocn; sm += osm;
-                        lo = lo > olo ? lo : olo;
-                        hi = hi > ohi ? hi : ohi;
-                    }
-                }
-            }
-            if (cell >= 0 && !dup) {
+            if (surf_merge_runs(cell, cn, sm, lo, hi)) {
                 atomicAdd(&s_cnt[cell], cn);
                 atomicAdd(&s_sum[cell], sm);
                 atomicMax(&s_lo[cell], lo);

@@ -163,6 +163,49 @@ def tunnel_patches(n, seed=0, radius=2.0, length=12.0, sigma=0.01, floor_z=-1.2,
     return np.ascontiguousarray(p, dtype=np.float32)
 
 
+DRIVE_PATCHES = ((10.0, 12.0, 20.0, 44.0, 0.15), (25.0, 27.0, 316.0, 340.0, -0.15), (33.0, 34.0, 100.0, 140.0, 0.15))
+
+
+def pose_matrix(position, yaw_deg=0.0, roll_deg=0.0, pitch_deg=0.0):
+    """Row-major 3x4 [Rm | tr], sensor -> world: Rm = Rz(yaw) Ry(pitch) Rx(roll), tr = position.  float64."""
+    y, p, r = np.deg2rad([yaw_deg, pitch_deg, roll_deg])
+    rz = np.array([[np.cos(y), -np.sin(y), 0.0], [np.sin(y), np.cos(y), 0.0], [0.0, 0.0, 1.0]])
+    ry = np.array([[np.cos(p), 0.0, np.sin(p)], [0.0, 1.0, 0.0], [-np.sin(p), 0.0, np.cos(p)]])
+    rx = np.array([[1.0, 0.0, 0.0], [0.0, np.cos(r), -np.sin(r)], [0.0, np.sin(r), np.cos(r)]])
+    return np.concatenate([rz @ ry @ rx, np.asarray(position, np.float64).reshape(3, 1)], axis=1)
+
+
+def tunnel_drive(n_frames, n_points, seed=0, radius=2.0, length=48.0, start=6.0, step=3.5, reach=7.0, sigma=0.01,
+                 patches=DRIVE_PATCHES, yaw_deg=4.0, roll_deg=3.0, lateral=0.25):
+    """A drive through a straight tunnel for the persistent wall map (gm_wall_*).  The WORLD frame is the map frame: the
+    design cylinder has its axis along +x through the origin, `radius`, up = +z, and runs from chainage 0 to `length`.
+    The wall carries world-fixed patches (t0, t1, phi0_deg, phi1_deg, dr) in design-map coordinates (the SURFACE_PATCHES
+    form: phi from +z turning toward -y); the defaults are aligned with 0.25 m x 4 degree cells from t_min = 0.
+    Frame i sees the wall within `reach` metres of chainage start + i step from a sensor with a yaw / roll of up to
+    +-yaw_deg / +-roll_deg and a lateral offset of up to `lateral` metres in y and z (step < the crop length, so
+    neighbouring frames overlap).  Radial noise N(0, sigma).  Returns dict(frames=[(cloud float32 (n_points, 3) in SENSOR
+    coordinates, pose float64 (3, 4) sensor -> world), ...], design=dict(point, direction, radius, up, forward),
+    patches, sigma, length)."""
+    rng = np.random.default_rng(seed)
+    frames = []
+    for i in range(n_frames):
+        s = start + i * step
+        pose = pose_matrix((s, rng.uniform(-lateral, lateral), rng.uniform(-lateral, lateral)),
+                           yaw_deg=rng.uniform(-yaw_deg, yaw_deg), roll_deg=rng.uniform(-roll_deg, roll_deg))
+        t = rng.uniform(max(0.0, s - reach), min(length, s + reach), n_points)
+        phi = rng.uniform(0.0, 2 * np.pi, n_points)
+        rr = radius + rng.normal(0.0, sigma, n_points)
+        deg = np.rad2deg(phi)
+        for t0, t1, p0, p1, dr in patches:
+            rr = np.where((t >= t0) & (t < t1) & (deg >= p0) & (deg < p1), rr + dr, rr)
+        world = np.stack([t, -rr * np.sin(phi), rr * np.cos(phi)], axis=1)
+        sensor = (world - pose[:, 3]) @ pose[:, :3]   # Rm^T (p - tr)
+        frames.append((np.ascontiguousarray(sensor, dtype=np.float32), pose))
+    design = dict(point=(0.0, 0.0, 0.0), direction=(1.0, 0.0, 0.0), radius=float(radius), up=(0.0, 0.0, 1.0),
+                  forward=(1.0, 0.0, 0.0))
+    return dict(frames=frames, design=design, patches=tuple(patches), sigma=sigma, length=length)
+
+
 def drop_row_padding(msg):
     """What the node does with an organised cloud whose rows are padded (ros/geometric_mapping_node.cpp): the C ABI takes
     point_step-strided rows, so the row_step padding is dropped once on the host.  Returns the packed uint8 rows."""

@@ -12,7 +12,7 @@ void Processor::check(gm_status s, const char *what)
 }
 
 Processor::Processor(double b, double leaf, double r, double wf, int device, unsigned flags)
-    : ctx_(0), grp_(0), cur_(0), cur_slot_(0), n_slots_(1), next_slot_(0), pending_(0)
+    : ctx_(0), grp_(0), cur_(0), cur_slot_(0), n_slots_(1), next_slot_(0), pending_(0), wall_(0), newest_slot_(-1)
 {
     gm_config cfg;
     gm_default_config(&cfg);
@@ -26,7 +26,8 @@ Processor::Processor(double b, double leaf, double r, double wf, int device, uns
 
 Processor::Processor(double b, double leaf, double r, double wf, const std::vector<int> &devices, unsigned flags,
                      unsigned slots_per_device)
-    : ctx_(0), grp_(0), cur_(0), cur_slot_(0), n_slots_(slots_per_device ? slots_per_device : 1), next_slot_(0), pending_(0)
+    : ctx_(0), grp_(0), cur_(0), cur_slot_(0), n_slots_(slots_per_device ? slots_per_device : 1), next_slot_(0), pending_(0), wall_(0),
+      newest_slot_(-1)
 {
     if (devices.empty()) throw Error(GM_ERR_INVALID_ARG, "Processor: empty device list");
     gm_config cfg;
@@ -94,6 +95,7 @@ void Processor::submitFrame(const void *rows, unsigned n, unsigned step, unsigne
     }
     if (pending_ >= n_slots_) throw Error(GM_ERR_NOT_READY, "submitFrame: every slot holds a frame (waitFrame first)");
     check(gm_submit_frame(ctx_, next_slot_, &c), "submitFrame");
+    newest_slot_ = (int)next_slot_;
     next_slot_ = (next_slot_ + 1) % n_slots_;
     ++pending_;
 }
@@ -205,6 +207,7 @@ gm_frame_result Processor::processFrame(const void *rows, unsigned n, unsigned s
     gm_frame_result r;
     check(gm_process_frame(ctx_, &c, &r), "processFrame");
     cur_ = ctx_; cur_slot_ = 0;
+    newest_slot_ = 0;
     last_ = r;
     return r;
 }
@@ -362,6 +365,42 @@ void Processor::getSurfaceMap(gm_surface_info &info, std::vector<gm_surface_cell
     cells.resize(n);
     s = gm_get_surface_map(cur_, cur_slot_, &info, n ? &cells[0] : 0, n, &n);
     if (s != GM_OK) throw Error(s, std::string("getSurfaceMap: ") + gm_status_string(s) + ": " + gm_last_error(cur_));
+}
+
+void Processor::createWallMap(const gm_wall_params &params)
+{
+    if (grp_) throw Error(GM_ERR_UNSUPPORTED, "createWallMap: a wall map belongs to one context (single-device Processor)");
+    gm_wall_map *m = 0;
+    check(gm_wall_map_create(ctx_, &params, &m), "createWallMap");
+    if (wall_) gm_wall_map_destroy(wall_);
+    wall_ = m;
+}
+
+gm_wall_add_info Processor::addToWallMap(const double pose[12])
+{
+    if (!wall_) throw Error(GM_ERR_NOT_READY, "addToWallMap: createWallMap first");
+    if (newest_slot_ < 0) throw Error(GM_ERR_NOT_READY, "addToWallMap: no frame yet");
+    gm_wall_add_info info;
+    check(gm_wall_map_add_frame(wall_, ctx_, (unsigned)newest_slot_, pose, &info), "addToWallMap");
+    return info;
+}
+
+void Processor::readWallMap(unsigned station0, unsigned n, std::vector<gm_surface_cell> &cells)
+{
+    if (!wall_) throw Error(GM_ERR_NOT_READY, "readWallMap: createWallMap first");
+    uint64_t nc = 0;
+    gm_status s = gm_wall_map_read(wall_, station0, n, 0, 0, &nc);
+    if (s != GM_OK && s != GM_ERR_CAPACITY) check(s, "readWallMap");
+    cells.resize((size_t)nc);
+    if (nc) check(gm_wall_map_read(wall_, station0, n, &cells[0], nc, &nc), "readWallMap");
+}
+
+gm_wall_info Processor::wallMapInfo()
+{
+    if (!wall_) throw Error(GM_ERR_NOT_READY, "wallMapInfo: createWallMap first");
+    gm_wall_info info;
+    check(gm_wall_map_info(wall_, &info), "wallMapInfo");
+    return info;
 }
 
 MarkerArray Processor::rvizNormals(const double &leafSize, const PointCloud &cloud, const NormalCloud &nrm)

@@ -135,6 +135,16 @@ public:
     void setSurfaceParams(const gm_surface_params &params);
     // ... and the map of the frame the accessors refer to: info and the cells, row-major [n_stations][n_sectors]
     void getSurfaceMap(gm_surface_info &info, std::vector<gm_surface_cell> &cells);
+    // Persistent wall map (gm_wall_*, include/gm_hip.h): one map against a design cylinder, owned by the processor's
+    // context (single device; GM_ERR_UNSUPPORTED with several).  createWallMap replaces the map of an earlier call.
+    void createWallMap(const gm_wall_params &params);
+    // adds the frame just processed or submitted (the newest one) under pose = row-major 3x4 [R | t], sensor -> map.
+    // Enqueued behind the frame's work: call it right after submitFrame, or after processFrame / waitFrame.
+    gm_wall_add_info addToWallMap(const double pose[12]);
+    // stations [station0, station0 + n) as records, row-major [n][n_sectors] (waits for the adds enqueued so far)
+    void readWallMap(unsigned station0, unsigned n, std::vector<gm_surface_cell> &cells);
+    gm_wall_info wallMapInfo();
+    gm_wall_map *wallMap() { return wall_; }
 
     gm_ctx *ctx() { return ctx_; }
 
@@ -146,6 +156,8 @@ private:
     unsigned cur_slot_;    // ... and in which slot
     unsigned n_slots_, next_slot_, pending_;   // single device: ring of slots
     gm_frame_result last_;                     // of the frame the accessors refer to
+    gm_wall_map *wall_;                        // createWallMap (freed with the context)
+    int newest_slot_;                          // slot of the frame submitted last (-1: none yet)
     struct CloudBuf { gm_ctx *ctx; unsigned slot; float *rows; unsigned cap; };
     std::vector<CloudBuf> cloud_bufs_;         // enableCloudOutput: one per (device, slot)
     void growCloudOutput(unsigned n_points);

@@ -414,6 +414,121 @@ gm_status gm_surface_map(gm_ctx *ctx, const float *xyz, uint32_t n, const uint8_
                          const gm_surface_params *p, gm_surface_info *info, gm_surface_cell *cells, uint32_t capacity,
                          float *residual, int32_t *cell);
 
+/* ---- persistent wall map (gm_wall_*) ------------------------------------------------------------------------------
+ * A device-resident developed map of the wall against a DESIGN cylinder, by chainage: n_stations stations of
+ * station_length metres from t_min along the design axis, n_sectors sectors around it.  It outlives frames: every add
+ * bins the valid cloud of one frame, taken under a caller-supplied pose (sensor -> map), into the same table.  A cell
+ * holds integer accumulators only -- count (u32), sum of rint(e 2^20) (int64), min_key = ~ordered(min e) and
+ * max_key = ordered(max e) (u32, updated with an integer maximum; 0 = empty), where for the fp32 residual e with bits b
+ *     ordered(e) = b ^ 0x80000000 if the sign bit of b is clear, else ~b        (monotone in e; never 0 for a finite e)
+ * -- so a cell is a function of the multiset of (cell, e) pairs alone: adds in any order, from slots running
+ * concurrently, or merged from other maps / devices / files (gm_wall_map_add_raw) give the same bytes.
+ *   design frame  once at creation, fp64, NOT rounded: d = direction / |direction|; a = d if d.forward >= 0, else -d;
+ *                 o = point - (point.a) a;  u = normalize(up - (up.a) a), or, when that projection is shorter than
+ *                 0.1 |up|, the e1 of the fit basis of a (GM_SURF_UP_FALLBACK in status): e1 = (h x a) / |h x a| with
+ *                 h = (0,0,1) if |a_z| < 0.9, else (0,1,0);  v = a x u;  R = radius.
+ *   per add       host, fp64.  pose = row-major 3x4 [Rm | tr], sensor -> map (p_map = Rm p + tr); every entry finite,
+ *                 max |Rm^T Rm - I| <= 1e-6 and det Rm > 0, else GM_ERR_INVALID_ARG.  Sensor chainage s = (tr - o).a;
+ *                 anchor station j_f = floor((s - t_min) / ds) (|.| < 2^62, else GM_ERR_INVALID_ARG); frame-local
+ *                 origin o_f = o + (t_min + j_f ds) a.  In sensor coordinates o' = Rm^T (o_f - tr), a' = Rm^T a,
+ *                 u' = Rm^T u, v' = Rm^T v, each rounded to fp32 once; R, ds, gate and dtheta = 2 pi / n_sectors
+ *                 rounded to fp32 once.  All of it is reported in gm_wall_add_info.  The device therefore only sees
+ *                 coordinates of the size of the crop box: a frame at chainage 5 km is binned like one at 0.
+ *   per point     device, fp32, the per-point chain of the GM_CFG_SURFACE_MAP block above with (o', a', u', v', R) and
+ *                 a local t_min of 0: q = p - o', t = q.a', w = q - t a', e = sqrt(w.w) - R, phi, k as stated there;
+ *                 the station is j = j_f + floor(t / ds), taken in 64-bit integers.
+ *   classes       every point is in exactly one: plane (label 1), beyond_gate (|e| > gate or e not finite), outside
+ *                 (j not in [0, n_stations)), mapped (cell j * n_sectors + k).
+ *   read          gm_surface_cell records by the rule of the block above: mean = sum 2^-20 / count in fp64 rounded to
+ *                 fp32 once, min = ordered^-1(~min_key), max = ordered^-1(max_key); count 0 and NaN when empty.
+ * A map belongs to the context it was created from (several per context are allowed) and is freed with it. */
+#define GM_WALL_MAX_CELLS   (1u << 24)   /* n_stations * n_sectors limit (20 B of device memory per cell) */
+#define GM_WALL_MAX_SECTORS 4096u
+
+typedef struct gm_wall_map gm_wall_map;   /* opaque; owned by the context it was created from */
+
+typedef struct gm_wall_params {
+    uint32_t struct_size;     /* = sizeof(gm_wall_params) */
+    uint32_t n_stations;      /* >= 1 (default 4000: 1 km at the default station_length) */
+    uint32_t n_sectors;       /* 1 .. 4096 (default 90); n_stations * n_sectors <= GM_WALL_MAX_CELLS */
+    uint32_t reserved;        /* 0 */
+    double   station_length;  /* ds, metres, > 0 (default 0.25) */
+    double   t_min;           /* chainage of station 0's start, metres, finite (default 0) */
+    double   gate;            /* |e| above it is beyond_gate, metres, in (0, 8] (default 0.25) */
+    double   point[3];        /* the design cylinder in map coordinates: a point of the axis (default 0, 0, 0), */
+    double   direction[3];    /*   its direction, non-zero (default 1, 0, 0), */
+    double   radius;          /*   its radius, > 0 (default 2) */
+    double   up[3];           /* as gm_surface_params (default 0, 0, 1) */
+    double   forward[3];      /* as gm_surface_params (default 1, 0, 0) */
+} gm_wall_params;
+
+typedef struct gm_wall_raw_cell {   /* 24 bytes; the encoding stated above is fixed: files of raw cells stay readable */
+    int64_t  sum;             /* sum of rint(e 2^20) */
+    uint32_t count;
+    uint32_t min_key;         /* ~ordered(min e); 0 when empty */
+    uint32_t max_key;         /* ordered(max e); 0 when empty */
+    uint32_t reserved;        /* 0 */
+} gm_wall_raw_cell;
+
+typedef struct gm_wall_add_info {     /* filled on the host by every add, before the kernel has run */
+    uint32_t struct_size;     /* = sizeof(gm_wall_add_info), filled by the library */
+    uint32_t status;          /* GM_SURF_OK or GM_SURF_UP_FALLBACK: the design frame's */
+    int64_t  anchor_station;  /* j_f */
+    float    o[3], a[3], u[3], v[3];   /* o', a', u', v': the frame-local map frame in SENSOR coordinates (fp32, as binned with) */
+    float    R, station_length, sector_angle, gate;   /* fp32 binning constants */
+} gm_wall_add_info;
+
+typedef struct gm_wall_info {         /* cumulative; read after a synchronisation */
+    uint32_t struct_size;     /* = sizeof(gm_wall_info), filled by the library */
+    uint32_t status;          /* GM_SURF_OK or GM_SURF_UP_FALLBACK */
+    uint32_t n_stations, n_sectors;
+    uint64_t frames;          /* adds since create / the last full clear */
+    uint64_t mapped, outside, beyond_gate, plane;   /* points per class over those adds: points added as points only
+                                                       (gm_wall_map_add_raw changes cells and cells_hit, not these) */
+    uint64_t cells_hit;       /* cells with count > 0 in the whole map */
+    double   o[3], a[3], u[3], v[3], R;             /* the design frame in map coordinates (fp64) */
+} gm_wall_info;
+
+/* Host only: the defaults of the table above.  A NULL is ignored. */
+void gm_wall_default_params(gm_wall_params *p);
+/* A zeroed map on ctx's device.  GM_ERR_INVALID_ARG: NULL, struct_size mismatch or a parameter outside its limits;
+ * GM_ERR_OOM: the table does not fit; GM_ERR_DEVICE. */
+gm_status gm_wall_map_create(gm_ctx *ctx, const gm_wall_params *params, gm_wall_map **map);
+/* Waits for the map's adds and frees it (gm_destroy of the owning context frees the maps still alive).  NULL is ignored. */
+void gm_wall_map_destroy(gm_wall_map *map);
+/* Adds the valid cloud of the frame last submitted to `slot` of ctx (which must be the map's own context:
+ * GM_ERR_INVALID_ARG otherwise, as for a bad slot or pose or a NULL).  The add is enqueued on the slot's stream behind the
+ * frame's work and the call returns without waiting: it may follow gm_submit_frame directly or come after
+ * gm_wait_frame.  It reads the point count and the slot's final labels (those of gm_get_labels; no point is plane on a
+ * context without GM_CFG_RANSAC_PLANE) on the device and writes nothing per point.  A later submit to the slot is ordered
+ * behind it; adds from different slots may run concurrently into one map.  With GM_CFG_GRAPH it is a plain launch after
+ * the graph.  GM_ERR_NOT_READY: the slot holds no frame (never submitted, or reused by a stage call since).  add_info
+ * may be NULL. */
+gm_status gm_wall_map_add_frame(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, const double pose[12], gm_wall_add_info *add_info);
+/* The same kernel as one blocking stage call on host buffers (slot 0 of the map's context, refused with GM_ERR_NOT_READY
+ * while that slot holds a frame not waited for).  xyz rows of 3 floats; labels (may be NULL: no point is plane);
+ * residual (float[n]: e, NaN for plane points) and cell (int32_t[n]: j * n_sectors + k, -1 unless mapped) may be NULL.
+ * Fed the xyz of a slot's gm_get_cropped_xyz rows and its gm_get_labels with the same pose, it changes the map exactly
+ * as gm_wall_map_add_frame does.  GM_ERR_INVALID_ARG: NULL map / xyz with n > 0, bad pose. */
+gm_status gm_wall_map_add_points(gm_wall_map *map, const float *xyz, uint32_t n, const uint8_t *labels, const double pose[12],
+                                 gm_wall_add_info *add_info, float *residual, int32_t *cell);
+/* Waits for every add enqueued so far. */
+gm_status gm_wall_map_sync(gm_wall_map *map);
+/* The five calls below synchronise first (as gm_wall_map_sync), run a small device kernel and block.  A window is
+ * stations [station0, station0 + n); one outside [0, n_stations] is GM_ERR_INVALID_ARG.  Cell buffers are row-major
+ * [n][n_sectors]; *n_out (may be NULL) = n * n_sectors, and a smaller capacity (in cells) returns GM_ERR_CAPACITY. */
+gm_status gm_wall_map_info(gm_wall_map *map, gm_wall_info *info);
+gm_status gm_wall_map_read(gm_wall_map *map, uint32_t station0, uint32_t n, gm_surface_cell *cells, uint64_t capacity,
+                           uint64_t *n_out);
+gm_status gm_wall_map_read_raw(gm_wall_map *map, uint32_t station0, uint32_t n, gm_wall_raw_cell *cells, uint64_t capacity,
+                               uint64_t *n_out);
+/* Merges n stations of raw cells ([n][n_sectors]) into the window: counts and sums add, keys take the maximum.  This is
+ * how a map is restored from a file and how the maps of several devices or sessions become one.  It changes cells and
+ * cells_hit only: the per-class totals and `frames` count points added as points. */
+gm_status gm_wall_map_add_raw(gm_wall_map *map, uint32_t station0, uint32_t n, const gm_wall_raw_cell *cells);
+/* Zeroes the window; clearing the whole range [0, n_stations) also zeroes the cumulative totals and `frames`. */
+gm_status gm_wall_map_clear(gm_wall_map *map, uint32_t station0, uint32_t n);
+
 /* "Compressed map" record of a completed slot.  The reference defines no such
  * output; this is a build-defined format: header, primitive records,
  * then n_voxels rows of x,y,z,count (float32).  Returns the bytes needed in
