@@ -8,10 +8,16 @@ Tolerances: inlier counts and labels bit-exact (integer work, same fp32 fma
 chain on both sides); hypotheses 1e-6 (double arithmetic, fp contraction may
 differ); moments 1e-12 relative (fp64 sums, different order).
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 
 from geometric_mapping_amd import synth
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from ransac_np import staged_best  # noqa: E402  (the staging of launch_score_preemptive, restated)
 
 pytestmark = pytest.mark.gpu
 B, R, LEAF, WF, TAU = 5.0, 0.5, 0.5, 0.2, 0.03
@@ -100,21 +106,6 @@ def test_nearest(ctx, oc):
     assert ctx.nearest(xyz[:1], cen).tolist() == [0] * len(cen)
 
 
-def preemptive_best(score_fn, cloud, hyp, labels, want=0):
-    """The in-frame RANSAC's staged scoring (csrc/k_ransac.hip launch_score_preemptive), restated with the oracle's
-    exhaustive scorer: all hypotheses on every 64th point -> 128 best (count desc, index asc) -> those on every
-    16th point -> 8 best -> those on every point -> best full count (lowest index on ties).  H <= 128 starts at the
-    second stage, H <= 8 is exhaustive."""
-    ids = np.arange(len(hyp))
-    for stride, keep in ((64, 128), (16, 8)):
-        if len(ids) > keep:
-            c = score_fn(cloud[::stride], hyp[ids], TAU, labels[::stride], want)
-            ids = ids[np.lexsort((ids, -c))[:keep]]
-    c = score_fn(cloud, hyp[ids], TAU, labels, want)
-    k = np.lexsort((ids, -c))[0]
-    return int(ids[k]), int(c[k])
-
-
 def test_frame_ransac_plane_then_cylinder(gm, oc):
     from geometric_mapping_amd import _lib
     xyz = synth.tunnel_frame(60000, seed=2, floor_z=-1.2, outlier_frac=0.01)
@@ -128,17 +119,27 @@ def test_frame_ransac_plane_then_cylinder(gm, oc):
         nn = c.voxel_nearest()
         cen, _ = c.voxel_centroids()
         blob = c.compressed_map()
+        # the frame's own hypotheses, from the stage calls (same kernels, seeds and inputs; they reuse the slot, so last)
+        lab1 = np.zeros(len(cloud), np.uint8)
+        oc.label_plane(cloud, lab1, 0, 1, res["plane"], TAU)
+        dhp = c.plane_hypotheses(cloud, seed, H, None, 0)
+        dhc = c.cylinder_hypotheses(cloud, nrm, seed + 1, H, lab1, 0)
     # the same sequence on the CPU restatement, fed the GPU's own cloud+normals
     labels = np.zeros(len(cloud), np.uint8)
     hp = oc.plane_hypotheses(cloud, seed, H, labels, 0)
-    bp, nbp = preemptive_best(oc.score_planes, cloud, hp, labels)
+    bp, nbp, _ = staged_best(oc.score_planes, cloud, hp, labels, TAU)
     assert res["plane_inliers"] == nbp
     assert np.abs(res["plane"] - hp[bp]).max() < 1e-5
     assert nbp >= 0.98 * oc.score_planes(cloud, hp, TAU, labels, 0).max()   # pre-selection loses (almost) nothing
     assert oc.label_plane(cloud, labels, 0, 1, res["plane"], TAU) == res["plane_inliers"]
     hc = oc.cylinder_hypotheses(cloud, nrm, seed + 1, H, labels, 0)
-    bc, nbc = preemptive_best(oc.score_cylinders, cloud, hc, labels)
+    bc, nbc, _ = staged_best(oc.score_cylinders, cloud, hc, labels, TAU)
     assert abs(int(res["cylinder_inliers"]) - nbc) <= 2             # hypotheses agree to 1e-6, not bit for bit
+    # ... and on the device's own hypotheses the staged winners are exact: rows bit for bit, counts equal
+    dbp, dnbp, _ = staged_best(oc.score_planes, cloud, dhp, None, TAU)
+    assert res["plane_inliers"] == dnbp and np.array_equal(res["plane"], dhp[dbp])
+    dbc, dnbc, _ = staged_best(oc.score_cylinders, cloud, dhc, lab1, TAU)
+    assert res["cylinder_inliers"] == dnbc and np.array_equal(res["cylinder"], dhc[dbc])
     assert oc.label_cylinder(cloud, labels, 0, 2, res["cylinder"], TAU) == res["cylinder_inliers"]
     assert np.array_equal(lab, labels)
     # refits vs the restatement on the same labels
@@ -223,7 +224,7 @@ def test_frame_ransac_stage_boundaries(gm, oc, H):
     """The staged scoring switches shape at H = 8 (at or below: exhaustive, every hypothesis on every point) and at
     H = 128 (at or below: two stages, every 16th point then every point; above: three, starting on every 64th point;
     include/gm_hip.h, csrc/k_ransac.hip launch_score_preemptive): the plane winner must equal the restated staging
-    (preemptive_best above) on the oracle's scorer at, just below and just above each boundary."""
+    (tests/ransac_np.staged_best) on the oracle's scorer at, just below and just above each boundary."""
     from geometric_mapping_amd import _lib
     xyz = synth.tunnel_frame(50000, seed=4, floor_z=-1.2, outlier_frac=0.01)
     with gm.GeometricMapping(flags=_lib.GM_CFG_DEFAULT | _lib.GM_CFG_RANSAC_PLANE, ransac_hypotheses=H,
@@ -233,6 +234,6 @@ def test_frame_ransac_stage_boundaries(gm, oc, H):
         lab = c.labels()
     labels = np.zeros(len(cloud), np.uint8)
     hp = oc.plane_hypotheses(cloud, 11, H, labels, 0)
-    bp, nbp = preemptive_best(oc.score_planes, cloud, hp, labels)
+    bp, nbp, _ = staged_best(oc.score_planes, cloud, hp, labels, TAU)
     assert res["plane_inliers"] == nbp and np.abs(res["plane"] - hp[bp]).max() < 1e-5
     assert oc.label_plane(cloud, labels, 0, 1, res["plane"], TAU) == nbp and np.array_equal(lab, labels)
