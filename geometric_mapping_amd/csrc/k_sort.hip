@@ -20,8 +20,10 @@
 //   * the LAST pass of the cell sort does not write (key, value) pairs: the value is the cropped index, the pass
 //     fetches that row and writes the sorted cloud itself (GATHER), so no gather pass follows the sort.
 // Tiles are handed out by ticket, so a block only waits for tiles whose blocks are already running, whatever else
-// shares the chip (see gm_compact.hpp).  Records are never cleared: the epoch of a launch makes older records read as
-// "not there yet".
+// shares the chip (see gm_compact.hpp).  Records carry no epoch: a record word of 0 reads as "not there yet", so every
+// record a sort will look at -- and every digit total -- is zero before its first pass.  The cell sort's are cleared by
+// the frame's opening zero-fill (gm_api.hip; the crop then counts pass 0's totals), any other sort's by
+// launch_radix_sort itself (its unprepared path).  Nothing of one sort may survive into the next one.
 //
 // Round 3 ran two launches per pass (per-block histogram rows, then a scatter whose blocks summed the rows of the blocks
 // before them: 204 thin blocks, up to 25 dependent L2 round trips for the last one) and three 11-bit passes + a gather
@@ -129,7 +131,8 @@ __global__ __launch_bounds__(1024) void k_rs_hist_all(const uint32_t *__restrict
 //      travel as 16-bit records [ready:1 | count:14], eight digits per 16-byte load, the 16 x 64 threads of the block
 //      taking 16 tiles per load round -- the 101 tiles before the last one of a 1 M-point frame are 101 KB, one trip.
 //      Sorts of more than 112 tiles add, per tile, a row of 32-bit INCLUSIVE prefixes: a tile sums the 16-bit rows of the
-//      112 tiles before it and the inclusive row of the tile before those.  All records are cleared when the frame opens.
+//      112 tiles before it and the inclusive row of the tile before those (how records become invalid between sorts:
+//      the top of the file).
 template <int BITS, bool GATHER, int kRsThreads>
 __global__ __launch_bounds__(kRsThreads) void k_rs_pass(const uint32_t *__restrict__ keys_in,
                                                         const uint32_t *__restrict__ vals_in,
