@@ -61,6 +61,7 @@ GM_SURF_UP_FALLBACK = 1 << 8
 
 GM_WALL_MAX_CELLS = 1 << 24
 GM_WALL_MAX_SECTORS = 4096
+GM_WALL_REGION_TILE = (64, 64)   # stations x sectors: the labelling kernel's default tile
 
 GM_N_STAGES = 9
 STAGE_NAMES = ("upload", "crop", "grid", "normals", "compact", "frame", "voxel", "ransac", "total")
@@ -139,6 +140,30 @@ class WallInfo(C.Structure):
                 ("o", C.c_double * 3), ("a", C.c_double * 3), ("u", C.c_double * 3), ("v", C.c_double * 3), ("R", C.c_double)]
 
 
+class WallRegion(C.Structure):
+    _fields_ = [("label", C.c_uint32), ("sign", C.c_int32), ("cells", C.c_uint32),
+                ("station_min", C.c_uint32), ("station_max", C.c_uint32), ("sector_min", C.c_uint32), ("sector_max", C.c_uint32),
+                ("sector_min_turned", C.c_uint32), ("sector_max_turned", C.c_uint32), ("peak_cell", C.c_uint32),
+                ("peak", C.c_int64), ("sum_d", C.c_int64), ("points", C.c_uint64)]
+
+
+class WallRegionParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_count", C.c_uint32), ("min_cells", C.c_uint32), ("connectivity", C.c_uint32),
+                ("threshold", C.c_double), ("reserved", C.c_uint64)]
+
+
+class WallRegionsInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("station0", C.c_uint32), ("n_stations", C.c_uint32), ("n_sectors", C.c_uint32),
+                ("threshold_q", C.c_int64), ("flagged_pos", C.c_uint64), ("flagged_neg", C.c_uint64), ("unusable", C.c_uint64),
+                ("empty", C.c_uint64), ("components", C.c_uint64), ("regions", C.c_uint64), ("cell_area", C.c_double)]
+
+
+class WallRegionMetrics(C.Structure):
+    _fields_ = [("area_m2", C.c_double), ("volume_m3", C.c_double), ("peak_m", C.c_double), ("mean_m", C.c_double),
+                ("chainage_from", C.c_double), ("chainage_to", C.c_double), ("angle_from_deg", C.c_double),
+                ("angle_to_deg", C.c_double)]
+
+
 class GmError(RuntimeError):
     def __init__(self, status, message):
         super().__init__(f"libgm_hip: status {status}: {message}")
@@ -200,6 +225,8 @@ def load():
     sprmp, scellp, sinfop = C.POINTER(SurfaceParams), C.POINTER(SurfaceCell), C.POINTER(SurfaceInfo)
     wprmp, wrawp, waddp, winfop = C.POINTER(WallParams), C.POINTER(WallRawCell), C.POINTER(WallAddInfo), C.POINTER(WallInfo)
     u64, u64p = C.c_uint64, C.POINTER(C.c_uint64)
+    wregp, wrprmp, wrinfop, wrmetp = (C.POINTER(WallRegion), C.POINTER(WallRegionParams), C.POINTER(WallRegionsInfo),
+                                      C.POINTER(WallRegionMetrics))
     proto = {
         "gm_create": (C.c_int, [cfgp, C.POINTER(vp)]),
         "gm_destroy": (None, [vp]),
@@ -256,6 +283,9 @@ def load():
         "gm_wall_map_read_raw": (C.c_int, [vp, u32, u32, wrawp, u64, u64p]),
         "gm_wall_map_add_raw": (C.c_int, [vp, u32, u32, wrawp]),
         "gm_wall_map_clear": (C.c_int, [vp, u32, u32]),
+        "gm_wall_region_default_params": (None, [wrprmp]),
+        "gm_wall_map_regions": (C.c_int, [vp, vp, u32, u32, wrprmp, wrinfop, wregp, u32, u32p, i32p]),
+        "gm_wall_region_metrics": (C.c_int, [wprmp, wregp, wrmetp]),
         "gm_group_create": (C.c_int, [cfgp, i32p, u32, u32, C.POINTER(vp)]),
         "gm_group_destroy": (None, [vp]),
         "gm_group_size": (u32, [vp]),

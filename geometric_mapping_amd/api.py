@@ -496,6 +496,22 @@ class GeometricMapping:
 RAW_CELL = np.dtype([("sum", "<i8"), ("count", "<u4"), ("min_key", "<u4"), ("max_key", "<u4"), ("reserved", "<u4")])
 _CELL = np.dtype([("count", "<u4"), ("mean", "<f4"), ("min", "<f4"), ("max", "<f4")])
 _WALL_VEC = ("point", "direction", "up", "forward")
+REGION = np.dtype([("label", "<u4"), ("sign", "<i4"), ("cells", "<u4"), ("station_min", "<u4"), ("station_max", "<u4"),
+                   ("sector_min", "<u4"), ("sector_max", "<u4"), ("sector_min_turned", "<u4"), ("sector_max_turned", "<u4"),
+                   ("peak_cell", "<u4"), ("peak", "<i8"), ("sum_d", "<i8"), ("points", "<u8")])   # gm_wall_region, 64 bytes
+_REGION_INFO = ("station0", "n_stations", "n_sectors", "threshold_q", "flagged_pos", "flagged_neg", "unusable", "empty",
+                "components", "regions")
+_REGION_METRICS = tuple(k for k, _ in _lib.WallRegionMetrics._fields_)
+
+
+def wall_region_metrics(prm, region):
+    """gm_wall_region_metrics (host only): the fp64 metrics dict of one REGION record under the gm_wall_params `prm`."""
+    r = np.ascontiguousarray(np.asarray(region, dtype=REGION).reshape(1))
+    out = _lib.WallRegionMetrics()
+    st = _lib.load().gm_wall_region_metrics(C.byref(prm), r.ctypes.data_as(C.POINTER(_lib.WallRegion)), C.byref(out))
+    if st != _lib.GM_OK:
+        raise _lib.GmError(st, "gm_wall_region_metrics refused the record")
+    return {k: float(getattr(out, k)) for k in _REGION_METRICS}
 
 
 class WallMap:
@@ -636,6 +652,42 @@ class WallMap:
     def clear(self, station0=0, n=None):
         s0, n = self._window(station0, n)
         self._ctx._check(self._L.gm_wall_map_clear(self._h(), s0, n))
+
+    @staticmethod
+    def region_params(**kw):
+        """gm_wall_region_params with the library's defaults, then the keywords (min_count, min_cells, connectivity,
+        threshold)."""
+        p = _lib.WallRegionParams()
+        _lib.load().gm_wall_region_default_params(C.byref(p))
+        for k, v in kw.items():
+            if not hasattr(p, k) or k in ("struct_size", "reserved"):
+                raise TypeError(f"unknown region parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+    def regions(self, station0=0, n=None, baseline=None, labels=False, **params):
+        """gm_wall_map_regions: the connected deviation regions of stations [station0, station0 + n) against the design or,
+        with `baseline` (another WallMap of this context on the same grid), against that earlier epoch.  Returns
+        (info dict, regions REGION array ascending by label, metrics list of dicts, labels (n, n_sectors) int32 or None)."""
+        s0, n = self._window(station0, n)
+        p = self.region_params(**params)
+        bh = baseline._h() if baseline is not None else None
+        info = _lib.WallRegionsInfo()
+        got = C.c_uint32(0)
+        lab = np.empty(max(n * self.n_sectors, 1), dtype=np.int32) if labels else None
+        lp = lab.ctypes.data_as(C.POINTER(C.c_int32)) if labels else None
+        # a count query, then the list (the labels travel with the second call only)
+        self._ctx._check(self._L.gm_wall_map_regions(self._h(), bh, s0, n, C.byref(p), C.byref(info), None, 0, C.byref(got), None))
+        cap = int(got.value)
+        reg = np.zeros(max(cap, 1), dtype=REGION)
+        if cap or labels:
+            self._ctx._check(self._L.gm_wall_map_regions(self._h(), bh, s0, n, C.byref(p), C.byref(info),
+                                                         reg.ctypes.data_as(C.POINTER(_lib.WallRegion)), cap, C.byref(got), lp))
+        reg = reg[:int(got.value)].copy()
+        d = {k: int(getattr(info, k)) for k in _REGION_INFO}
+        d["cell_area"] = float(info.cell_area)
+        metrics = [wall_region_metrics(self.prm, reg[i]) for i in range(len(reg))]
+        return d, reg, metrics, (lab[:n * self.n_sectors].reshape(n, self.n_sectors).copy() if labels else None)
 
     def save(self, path):
         """The parameters and the raw cells as one .npz (numpy only)."""

@@ -331,6 +331,34 @@ void launch_wall_merge_raw(const WallTable &T, uint64_t first, uint64_t n, const
 void launch_wall_clear(const WallTable &T, uint64_t first, uint64_t n, bool totals_too, hipStream_t s);
 void launch_wall_count(const WallTable &T, uint64_t n, hipStream_t s);
 void gm_wall_free_all(gm_ctx *ctx);   // gm_destroy: the maps still alive
+// k_wall_regions.hip (gm_wall_map_regions): tiles -> seams -> flatten | reduce -> select | labels
+constexpr uint32_t kWallRegionTileCells = 4096;    // the most cells of a tile (its LDS tables)
+constexpr uint32_t kWallRegionNone = 0xFFFFFFFFu;  // parent of a cell that is not flagged
+constexpr int kWallRegionCounters = 8;             // u64: flagged_pos, flagged_neg, unusable, empty, components, regions, pad
+struct WallRegionAcc {   // 64 B, zero = empty: minima are kept inverted so that every extent is an integer maximum
+    uint32_t cells, label;
+    uint32_t st_min_inv, st_max, k_min_inv, k_max, t_min_inv, t_max;
+    unsigned long long sum_d, points, peak_key;   // peak_key = min(|d|, 2^32 - 1) << 32 | ~cell
+    unsigned long long pad;
+};
+struct WallRegionArgs {
+    WallTable map, base;       // base: the baseline's table when has_base
+    uint32_t has_base;
+    uint32_t n, nsec;          // the window's stations, the map's sectors
+    uint64_t first;            // station0 * nsec: map-wide index of window cell 0
+    uint32_t ts, tk, tiles_s, tiles_k;   // the tile and the tiles of the window
+    uint32_t conn8, min_count, min_cells;
+    long long T;
+    uint32_t *parent, *slot;   // [n * nsec] window-local parent (kWallRegionNone: not flagged); a root's region slot
+    long long *d;              // [n * nsec] d of the flagged cells
+    unsigned long long *ctr;   // [kWallRegionCounters]
+    WallRegionAcc *acc;        // [components]
+    gm_wall_region *out;       // [components]: the regions, in the order their slots were taken
+    uint32_t ncomp;
+};
+void launch_wall_region_label(const WallRegionArgs &a, hipStream_t s);    // three launches, up to the component count
+void launch_wall_region_reduce(const WallRegionArgs &a, hipStream_t s);   // two launches, up to the region list
+void launch_wall_region_labels(const WallRegionArgs &a, uint64_t first, uint64_t n, int32_t *out, hipStream_t s);
 // k_nearest.hip
 void launch_nearest(const float4 *pts, const uint32_t *n_ptr, uint32_t n_cap, const float4 *queries,
                     const uint32_t *nq_ptr, uint32_t nq_cap, unsigned long long *best, int32_t *idx, hipStream_t s,

@@ -1,6 +1,7 @@
 // gm_wall.hip -- C ABI of the persistent wall map (gm_wall_*; include/gm_hip.h states the rule).  Host logic only: the
 // design frame and the per-add frame in fp64, the station window of a frame, ownership.  Kernels are in k_wall.hip.
 #include <math.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -26,6 +27,13 @@ struct gm_wall_map {
     int32_t *pt_cell = nullptr;
     uint32_t pt_cap = 0;
     uint32_t points_per_block = 0; // 0: the kernel's default (GM_WALL_POINTS_PER_BLOCK: measurements)
+    // gm_wall_map_regions: the tile (GM_WALL_REGION_TILE: tests, measurements) and the scratch, allocated on first use, grow-only
+    uint32_t region_ts = GM_WALL_REGION_TILE_STATIONS, region_tk = GM_WALL_REGION_TILE_SECTORS;
+    uint8_t *rg_cells = nullptr;   // per window cell: d i64 [cap] | parent u32 [cap] | slot u32 [cap]
+    uint64_t rg_cells_cap = 0;
+    unsigned long long *rg_ctr = nullptr;   // [kWallRegionCounters]
+    uint8_t *rg_recs = nullptr;    // per component: WallRegionAcc [cap] | gm_wall_region [cap]
+    uint64_t rg_recs_cap = 0;
 };
 
 namespace {
@@ -205,6 +213,7 @@ void free_map(gm_wall_map *m)
         if (m->pending[i] && m->ctx->slots[i].stream) hipStreamSynchronize(m->ctx->slots[i].stream);
     if (m->stream) { hipStreamSynchronize(m->stream); hipStreamDestroy(m->stream); }
     hipFree(m->base); hipFree(m->stage); hipFree(m->pt_res); hipFree(m->pt_cell);
+    hipFree(m->rg_cells); hipFree(m->rg_ctr); hipFree(m->rg_recs);
     delete m;
 }
 
@@ -267,6 +276,13 @@ gm_status gm_wall_map_create(gm_ctx *ctx, const gm_wall_params *params, gm_wall_
     m->ncell = (uint64_t)params->n_stations * params->n_sectors;
     m->pending.assign(ctx->n_slots, 0);
     if (const char *e = getenv("GM_WALL_POINTS_PER_BLOCK")) m->points_per_block = (uint32_t)strtoul(e, nullptr, 10);
+    if (const char *e = getenv("GM_WALL_REGION_TILE")) {   // <stations>x<sectors>; anything else: the default
+        unsigned ts = 0, tk = 0;
+        if (sscanf(e, "%ux%u", &ts, &tk) == 2 && ts >= 1u && tk >= 1u && (uint64_t)ts * tk <= kWallRegionTileCells) {
+            m->region_ts = ts;
+            m->region_tk = tk;
+        }
+    }
     design_frame(m);
     auto body = [&]() -> gm_status {
         GMW_HIP(ctx, hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
@@ -449,6 +465,172 @@ gm_status gm_wall_map_clear(gm_wall_map *map, uint32_t station0, uint32_t n)
     GMW_HIP(ctx, hipGetLastError());
     GMW_HIP(ctx, hipStreamSynchronize(map->stream));
     if (all) map->frames = 0;
+    return GM_OK;
+}
+
+void gm_wall_region_default_params(gm_wall_region_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(gm_wall_region_params);
+    p->min_count = 8;
+    p->min_cells = 4;
+    p->connectivity = 8;
+    p->threshold = 0.05;
+}
+
+gm_status gm_wall_region_metrics(const gm_wall_params *p, const gm_wall_region *r, struct gm_wall_region_metrics *out)
+{
+    if (!p || !r || !out || p->struct_size != sizeof(gm_wall_params) || p->n_sectors < 1u || r->cells < 1u) return GM_ERR_INVALID_ARG;
+    const uint32_t ns = p->n_sectors, half = ns / 2u;
+    if (r->sector_min > r->sector_max || r->sector_max >= ns || r->sector_min_turned > r->sector_max_turned ||
+        r->sector_max_turned >= ns || r->station_min > r->station_max)
+        return GM_ERR_INVALID_ARG;
+    // (one operation per statement: the same roundings as the twin's, whatever the compiler may contract)
+    const double two_pi = 6.283185307179586476925286766559;
+    const double sr = p->station_length * p->radius;
+    const double ring = sr * two_pi;
+    const double cell_area = ring / (double)ns;
+    const double sum_m = (double)r->sum_d * 0x1p-20;
+    out->area_m2 = (double)r->cells * cell_area;
+    out->volume_m3 = sum_m * cell_area;
+    out->peak_m = (double)r->peak * 0x1p-20;
+    out->mean_m = sum_m / (double)r->cells;
+    const double from = (double)r->station_min * p->station_length;
+    const double to = (double)(r->station_max + 1.0) * p->station_length;
+    out->chainage_from = p->t_min + from;
+    out->chainage_to = p->t_min + to;
+    const uint32_t plain = r->sector_max - r->sector_min + 1u, turned = r->sector_max_turned - r->sector_min_turned + 1u;
+    uint32_t k_from = r->sector_min, k_end = r->sector_max + 1u;
+    if (turned < plain) {   // turned back: k = (t - n_sectors / 2) mod n_sectors
+        k_from = (r->sector_min_turned + ns - half) % ns;
+        k_end = (r->sector_max_turned + ns - half) % ns + 1u;
+    }
+    const double a0 = 360.0 * (double)k_from;
+    const double a1 = 360.0 * (double)k_end;
+    out->angle_from_deg = a0 / (double)ns;
+    out->angle_to_deg = a1 / (double)ns;
+    return GM_OK;
+}
+
+gm_status gm_wall_map_regions(gm_wall_map *map, gm_wall_map *baseline, uint32_t station0, uint32_t n,
+                              const gm_wall_region_params *prm, gm_wall_regions_info *info, gm_wall_region *regions,
+                              uint32_t capacity, uint32_t *n_out, int32_t *cell_labels)
+{
+    if (!map) return GM_ERR_INVALID_ARG;
+    gm_ctx *ctx = map->ctx;
+    if (n_out) *n_out = 0;
+    if (!info) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_regions: NULL info");
+    gm_wall_region_params rp;
+    gm_wall_region_default_params(&rp);
+    if (prm) rp = *prm;
+    if (rp.struct_size != sizeof(gm_wall_region_params) || rp.min_count < 1u || rp.min_cells < 1u ||
+        (rp.connectivity != 4u && rp.connectivity != 8u) || !(rp.threshold > 0.0) || !(rp.threshold <= 8.0))
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_regions: struct_size mismatch or a parameter outside its limits");
+    const long long T = (long long)rint(rp.threshold * 1048576.0);
+    if (T < 1) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_regions: the threshold rounds to 0");
+    if (!regions && capacity) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_regions: NULL regions with a capacity");
+    if (baseline) {
+        if (baseline == map) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_regions: the baseline is the map itself");
+        if (baseline->ctx != ctx) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_regions: the baseline belongs to another context");
+        const gm_wall_params &p = map->prm, &b = baseline->prm;
+        if (p.n_stations != b.n_stations || p.n_sectors != b.n_sectors || memcmp(&p.station_length, &b.station_length, 8) ||
+            memcmp(&p.t_min, &b.t_min, 8) || memcmp(p.point, b.point, 24) || memcmp(p.direction, b.direction, 24) ||
+            memcmp(&p.radius, &b.radius, 8) || memcmp(p.up, b.up, 24) || memcmp(p.forward, b.forward, 24))
+            return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_regions: the baseline is a map on another grid");
+    }
+    gm_status st = check_window(map, station0, n, ~0ull, nullptr, "");
+    if (st != GM_OK) return st;
+    st = sync_map(map);
+    if (st != GM_OK) return st;
+    if (baseline) {
+        st = sync_map(baseline);
+        if (st != GM_OK) return st;
+    }
+    const uint32_t nsec = map->prm.n_sectors;
+    memset(info, 0, sizeof(*info));
+    info->struct_size = (uint32_t)sizeof(gm_wall_regions_info);
+    info->station0 = station0;
+    info->n_stations = n;
+    info->n_sectors = nsec;
+    info->threshold_q = T;
+    info->cell_area = map->prm.station_length * map->prm.radius * 6.283185307179586476925286766559 / (double)nsec;
+    if (!n) return GM_OK;
+
+    const uint64_t total = (uint64_t)n * nsec;
+    if (map->rg_cells_cap < total) {
+        hipFree(map->rg_cells);
+        map->rg_cells = nullptr; map->rg_cells_cap = 0;
+        GMW_HIP(ctx, hipMalloc((void **)&map->rg_cells, total * 16));
+        map->rg_cells_cap = total;
+    }
+    if (!map->rg_ctr) GMW_HIP(ctx, hipMalloc((void **)&map->rg_ctr, kWallRegionCounters * 8));
+    WallRegionArgs a;
+    memset(&a, 0, sizeof(a));
+    a.map = map->table;
+    a.has_base = baseline ? 1u : 0u;
+    a.base = baseline ? baseline->table : map->table;
+    a.n = n;
+    a.nsec = nsec;
+    a.first = (uint64_t)station0 * nsec;
+    a.ts = map->region_ts;
+    a.tk = map->region_tk;
+    a.tiles_s = (n + a.ts - 1u) / a.ts;
+    a.tiles_k = (nsec + a.tk - 1u) / a.tk;
+    a.conn8 = rp.connectivity == 8u ? 1u : 0u;
+    a.min_count = rp.min_count;
+    a.min_cells = rp.min_cells;
+    a.T = T;
+    a.d = reinterpret_cast<long long *>(map->rg_cells);
+    a.parent = reinterpret_cast<uint32_t *>(map->rg_cells + 8 * total);
+    a.slot = a.parent + total;
+    a.ctr = map->rg_ctr;
+    unsigned long long ctr[kWallRegionCounters];
+    GMW_HIP(ctx, hipMemsetAsync(map->rg_ctr, 0, kWallRegionCounters * 8, map->stream));
+    launch_wall_region_label(a, map->stream);
+    GMW_HIP(ctx, hipGetLastError());
+    GMW_HIP(ctx, hipMemcpyAsync(ctr, map->rg_ctr, sizeof(ctr), hipMemcpyDeviceToHost, map->stream));
+    GMW_HIP(ctx, hipStreamSynchronize(map->stream));   // the one count the host needs: it sizes the records
+    const uint64_t ncomp = ctr[4];
+    info->flagged_pos = ctr[0]; info->flagged_neg = ctr[1]; info->unusable = ctr[2]; info->empty = ctr[3];
+    info->components = ncomp;
+    uint64_t nreg = 0;
+    if (ncomp) {
+        if (map->rg_recs_cap < ncomp) {
+            hipFree(map->rg_recs);
+            map->rg_recs = nullptr; map->rg_recs_cap = 0;
+            GMW_HIP(ctx, hipMalloc((void **)&map->rg_recs, ncomp * (sizeof(WallRegionAcc) + sizeof(gm_wall_region))));
+            map->rg_recs_cap = ncomp;
+        }
+        a.acc = reinterpret_cast<WallRegionAcc *>(map->rg_recs);
+        a.out = reinterpret_cast<gm_wall_region *>(map->rg_recs + map->rg_recs_cap * sizeof(WallRegionAcc));
+        a.ncomp = (uint32_t)ncomp;
+        GMW_HIP(ctx, hipMemsetAsync(a.acc, 0, ncomp * sizeof(WallRegionAcc), map->stream));
+        launch_wall_region_reduce(a, map->stream);
+        GMW_HIP(ctx, hipGetLastError());
+        GMW_HIP(ctx, hipMemcpyAsync(&nreg, map->rg_ctr + 5, 8, hipMemcpyDeviceToHost, map->stream));
+        GMW_HIP(ctx, hipStreamSynchronize(map->stream));
+    }
+    info->regions = nreg;
+    if (n_out) *n_out = (uint32_t)nreg;
+    const bool fits = nreg <= capacity;
+    if (regions && fits && nreg) {
+        GMW_HIP(ctx, hipMemcpyAsync(regions, a.out, nreg * sizeof(gm_wall_region), hipMemcpyDeviceToHost, map->stream));
+        GMW_HIP(ctx, hipStreamSynchronize(map->stream));
+        std::sort(regions, regions + nreg, [](const gm_wall_region &x, const gm_wall_region &y) { return x.label < y.label; });
+    }
+    if (cell_labels) {
+        int32_t *stage = reinterpret_cast<int32_t *>(map->stage);   // (kStageCells raw records: room for as many labels)
+        const uint64_t chunk = std::min(kStageCells, map->ncell);
+        for (uint64_t done = 0; done < total; done += chunk) {
+            const uint64_t c = std::min(chunk, total - done);
+            launch_wall_region_labels(a, done, c, stage, map->stream);
+            GMW_HIP(ctx, hipGetLastError());
+            GMW_HIP(ctx, hipMemcpyAsync(cell_labels + done, stage, c * 4, hipMemcpyDeviceToHost, map->stream));
+            GMW_HIP(ctx, hipStreamSynchronize(map->stream));
+        }
+    }
+    if (!fits && (regions || capacity)) return gm_fail(ctx, GM_ERR_CAPACITY, "gm_wall_map_regions: region buffer too small");
     return GM_OK;
 }
 

@@ -395,6 +395,19 @@ void Processor::readWallMap(unsigned station0, unsigned n, std::vector<gm_surfac
     if (nc) check(gm_wall_map_read(wall_, station0, n, &cells[0], nc, &nc), "readWallMap");
 }
 
+std::vector<gm_wall_region> Processor::wallMapRegions(unsigned station0, unsigned n, const gm_wall_region_params &prm, gm_wall_regions_info *info)
+{
+    if (!wall_) throw Error(GM_ERR_NOT_READY, "wallMapRegions: createWallMap first");
+    gm_wall_regions_info local;
+    gm_wall_regions_info *ip = info ? info : &local;
+    uint32_t count = 0;
+    check(gm_wall_map_regions(wall_, 0, station0, n, &prm, ip, 0, 0, &count, 0), "wallMapRegions");
+    std::vector<gm_wall_region> regions(count);
+    if (count) check(gm_wall_map_regions(wall_, 0, station0, n, &prm, ip, &regions[0], count, &count, 0), "wallMapRegions");
+    regions.resize(count);
+    return regions;
+}
+
 gm_wall_info Processor::wallMapInfo()
 {
     if (!wall_) throw Error(GM_ERR_NOT_READY, "wallMapInfo: createWallMap first");

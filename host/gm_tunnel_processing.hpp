@@ -144,6 +144,9 @@ public:
     // stations [station0, station0 + n) as records, row-major [n][n_sectors] (waits for the adds enqueued so far)
     void readWallMap(unsigned station0, unsigned n, std::vector<gm_surface_cell> &cells);
     gm_wall_info wallMapInfo();
+    // connected deviation regions of stations [station0, station0 + n) against the design (gm_wall_map_regions),
+    // ascending by label; info, when given, receives the call's counts
+    std::vector<gm_wall_region> wallMapRegions(unsigned station0, unsigned n, const gm_wall_region_params &prm, gm_wall_regions_info *info = nullptr);
     gm_wall_map *wallMap() { return wall_; }
 
     gm_ctx *ctx() { return ctx_; }

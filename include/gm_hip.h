@@ -529,6 +529,96 @@ gm_status gm_wall_map_add_raw(gm_wall_map *map, uint32_t station0, uint32_t n, c
 /* Zeroes the window; clearing the whole range [0, n_stations) also zeroes the cumulative totals and `frames`. */
 gm_status gm_wall_map_clear(gm_wall_map *map, uint32_t station0, uint32_t n);
 
+/* ---- connected deviation regions of the wall map (gm_wall_map_regions) ----------------------------------------------
+ * Where the wall departs from the design, or from an earlier survey (a second map, the BASELINE), as a short list.  The
+ * rule is integer throughout, so the result is a function of the raw cells alone:
+ *   value       q = sum / (int64) count by C integer division (toward zero), units of 2^-20 m.  Without a baseline
+ *               d = q and the cell is USABLE iff count >= min_count; with one d = q(map) - q(baseline), usable iff both
+ *               counts are >= min_count.
+ *   threshold   T = (int64) rint(threshold 2^20), fp64, once on the host; threshold in (0, 8] and T >= 1.
+ *   sign        +1 if usable and d >= T, -1 if usable and d <= -T, else 0 (not flagged).
+ *   window      stations [station0, station0 + n); cells outside it do not exist for the call.
+ *   neighbours  of (j, k), connectivity 4: (j +- 1, k) inside the window and (j, (k +- 1) mod n_sectors); connectivity
+ *               8: also (j +- 1, (k +- 1) mod n_sectors).  The sector index wraps, the station index does not.
+ *   component   a maximal set of cells connected through neighbours of the same non-zero sign.  Its LABEL is the
+ *               smallest map-wide cell index j * n_sectors + k in it.  A REGION is a component of >= min_cells cells.
+ *   classes     every window cell is flagged_pos, flagged_neg, EMPTY (count 0 in the map and, with a baseline, in the
+ *               baseline too), UNUSABLE (not empty, not usable) or usable and below the threshold (not counted).
+ *   peak        the cell of the largest |d|, the smallest index among equals (|d| compares saturated at 2^32 - 1 units,
+ *               4096 m: far beyond any gate).
+ * Labelling (a union-find over tiles and their seams), the per-region reduction and the min_cells filter run on the
+ * device in a fixed number of launches; only info, the region list and, when asked for, cell_labels leave it.  The
+ * result does not depend on the tile shape (environment GM_WALL_REGION_TILE=<stations>x<sectors>, product <= 4096, read
+ * at gm_wall_map_create: tests and measurements), the grid or the order blocks run in. */
+#define GM_WALL_REGION_TILE_STATIONS 64u   /* the default tile of the labelling kernel */
+#define GM_WALL_REGION_TILE_SECTORS  64u
+
+typedef struct gm_wall_region {     /* 64 bytes; every field is independent of the order cells were visited in */
+    uint32_t label;                 /* smallest cell index of the region: its identity */
+    int32_t  sign;                  /* +1 wall outside (overbreak / moved out), -1 inside (intrusion / moved in) */
+    uint32_t cells;
+    uint32_t station_min, station_max;             /* inclusive */
+    uint32_t sector_min, sector_max;               /* over k */
+    uint32_t sector_min_turned, sector_max_turned; /* over (k + n_sectors / 2) mod n_sectors: contiguous for a region across the seam */
+    uint32_t peak_cell;             /* cell of the largest |d|; the smallest index among equals */
+    int64_t  peak;                  /* its d, 2^-20 m */
+    int64_t  sum_d;                 /* sum of d over the cells, 2^-20 m (times the cell area: volume) */
+    uint64_t points;                /* sum of the map's counts (not the baseline's) */
+} gm_wall_region;
+
+typedef struct gm_wall_region_params {
+    uint32_t struct_size;     /* = sizeof(gm_wall_region_params) */
+    uint32_t min_count;       /* >= 1 (default 8): points a cell needs to be usable */
+    uint32_t min_cells;       /* >= 1 (default 4): cells a component needs to be a region */
+    uint32_t connectivity;    /* 4 or 8 (default 8) */
+    double   threshold;       /* metres, in (0, 8] with rint(threshold 2^20) >= 1 (default 0.05) */
+    uint64_t reserved;        /* 0 */
+} gm_wall_region_params;
+
+typedef struct gm_wall_regions_info {
+    uint32_t struct_size;     /* = sizeof(gm_wall_regions_info), filled by the library */
+    uint32_t station0, n_stations, n_sectors;   /* the window and the map's sectors */
+    int64_t  threshold_q;     /* T */
+    uint64_t flagged_pos, flagged_neg, unusable, empty;   /* window cells per class (stated above) */
+    uint64_t components;      /* before the min_cells filter */
+    uint64_t regions;         /* after it */
+    double   cell_area;       /* station_length * radius * 2 pi / n_sectors (the design radius), m^2 */
+} gm_wall_regions_info;
+
+/* (a struct tag only, no typedef: the function of the same name below fills it) */
+struct gm_wall_region_metrics {   /* fp64, derived on the host from one record and the map's parameters */
+    double area_m2;           /* cells * cell_area */
+    double volume_m3;         /* sum_d 2^-20 * cell_area */
+    double peak_m;            /* peak 2^-20 */
+    double mean_m;            /* sum_d 2^-20 / cells */
+    double chainage_from;     /* t_min + station_min * station_length */
+    double chainage_to;       /* t_min + (station_max + 1) * station_length */
+    double angle_from_deg;    /* 360 k / n_sectors at the first sector's start and the last sector's end, from whichever */
+    double angle_to_deg;      /*   of the plain and the turned sector extent is shorter (plain on a tie); a turned extent
+                                   is turned back, both in [0, 360] and from > to meaning "across 0"; a region on every
+                                   sector gives 0 and 360 */
+};
+
+/* Host only: the defaults of the table above.  A NULL is ignored. */
+void gm_wall_region_default_params(gm_wall_region_params *p);
+/* The regions of the window, ascending by label.  Synchronises both maps (as gm_wall_map_sync), runs on the device and
+ * blocks.  baseline (may be NULL) is an earlier epoch: another map of the same context whose n_stations, n_sectors,
+ * station_length, t_min, point, direction, radius, up and forward equal the map's bit for bit (gate may differ).  prm
+ * NULL: the defaults.  info and *n_out (n_out may be NULL) are filled whenever the call got as far as the device, also on
+ * GM_ERR_CAPACITY: *n_out is the number of regions.  regions NULL with capacity 0 is a count query (GM_OK); fewer than
+ * *n_out records of capacity returns GM_ERR_CAPACITY and writes no record.  cell_labels (may be NULL; [n][n_sectors])
+ * receives the region's label for every cell of a region and -1 for every other cell (unflagged, or in a component
+ * below min_cells).  n = 0 gives no regions.  The maps are not changed.  Scratch (16 B per window cell and 128 B per
+ * component) is allocated on first use, kept grow-only in the map and freed with it.
+ * GM_ERR_INVALID_ARG: NULL map / info, a window outside the map, a parameter outside its limits or a struct_size
+ * mismatch, regions NULL with capacity > 0, baseline == map, of another context or on another grid. */
+gm_status gm_wall_map_regions(gm_wall_map *map, gm_wall_map *baseline, uint32_t station0, uint32_t n,
+                              const gm_wall_region_params *prm, gm_wall_regions_info *info, gm_wall_region *regions,
+                              uint32_t capacity, uint32_t *n_out, int32_t *cell_labels);
+/* Host only, no device, no map: the fp64 derivation stated at gm_wall_region_metrics from the map's parameters.
+ * GM_ERR_INVALID_ARG: a NULL, p->struct_size mismatch, n_sectors 0, r->cells 0 or a sector extent outside n_sectors. */
+gm_status gm_wall_region_metrics(const gm_wall_params *p, const gm_wall_region *r, struct gm_wall_region_metrics *out);
+
 /* "Compressed map" record of a completed slot.  The reference defines no such
  * output; this is a build-defined format: header, primitive records,
  * then n_voxels rows of x,y,z,count (float32).  Returns the bytes needed in
