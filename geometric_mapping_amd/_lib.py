@@ -164,6 +164,22 @@ class WallRegionMetrics(C.Structure):
                 ("angle_to_deg", C.c_double)]
 
 
+class WallCloudParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("block_stations", C.c_uint32), ("block_sectors", C.c_uint32),
+                ("min_count", C.c_uint32), ("exaggeration", C.c_double), ("anchor", C.c_double * 3), ("reserved", C.c_uint64)]
+
+
+class WallCloudPoint(C.Structure):
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("mean", C.c_float), ("min", C.c_float),
+                ("max", C.c_float), ("block", C.c_uint32), ("cells", C.c_uint32), ("count", C.c_uint64)]
+
+
+class WallCloudInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("station0", C.c_uint32), ("n_stations", C.c_uint32), ("n_sectors", C.c_uint32),
+                ("blocks_stations", C.c_uint32), ("blocks_sectors", C.c_uint32),
+                ("blocks", C.c_uint64), ("points", C.c_uint64), ("below_min_count", C.c_uint64), ("empty", C.c_uint64)]
+
+
 class GmError(RuntimeError):
     def __init__(self, status, message):
         super().__init__(f"libgm_hip: status {status}: {message}")
@@ -227,6 +243,7 @@ def load():
     u64, u64p = C.c_uint64, C.POINTER(C.c_uint64)
     wregp, wrprmp, wrinfop, wrmetp = (C.POINTER(WallRegion), C.POINTER(WallRegionParams), C.POINTER(WallRegionsInfo),
                                       C.POINTER(WallRegionMetrics))
+    wcprmp, wcptp, wcinfop = C.POINTER(WallCloudParams), C.POINTER(WallCloudPoint), C.POINTER(WallCloudInfo)
     proto = {
         "gm_create": (C.c_int, [cfgp, C.POINTER(vp)]),
         "gm_destroy": (None, [vp]),
@@ -286,6 +303,9 @@ def load():
         "gm_wall_region_default_params": (None, [wrprmp]),
         "gm_wall_map_regions": (C.c_int, [vp, vp, u32, u32, wrprmp, wrinfop, wregp, u32, u32p, i32p]),
         "gm_wall_region_metrics": (C.c_int, [wprmp, wregp, wrmetp]),
+        "gm_wall_cloud_default_params": (None, [wcprmp]),
+        "gm_wall_cloud_directions": (C.c_int, [wprmp, wcprmp, dp, u32, u32p]),
+        "gm_wall_map_cloud": (C.c_int, [vp, u32, u32, wcprmp, wcinfop, wcptp, u64, u64p]),
         "gm_group_create": (C.c_int, [cfgp, i32p, u32, u32, C.POINTER(vp)]),
         "gm_group_destroy": (None, [vp]),
         "gm_group_size": (u32, [vp]),

@@ -502,6 +502,10 @@ REGION = np.dtype([("label", "<u4"), ("sign", "<i4"), ("cells", "<u4"), ("statio
 _REGION_INFO = ("station0", "n_stations", "n_sectors", "threshold_q", "flagged_pos", "flagged_neg", "unusable", "empty",
                 "components", "regions")
 _REGION_METRICS = tuple(k for k, _ in _lib.WallRegionMetrics._fields_)
+WALL_CLOUD_POINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("mean", "<f4"), ("min", "<f4"), ("max", "<f4"),
+                             ("block", "<u4"), ("cells", "<u4"), ("count", "<u8")])   # gm_wall_cloud_point, 40 bytes
+_CLOUD_INFO = ("station0", "n_stations", "n_sectors", "blocks_stations", "blocks_sectors", "blocks", "points",
+               "below_min_count", "empty")
 
 
 def wall_region_metrics(prm, region):
@@ -512,6 +516,35 @@ def wall_region_metrics(prm, region):
     if st != _lib.GM_OK:
         raise _lib.GmError(st, "gm_wall_region_metrics refused the record")
     return {k: float(getattr(out, k)) for k in _REGION_METRICS}
+
+
+def _wall_cloud_params(**kw):
+    p = _lib.WallCloudParams()
+    _lib.load().gm_wall_cloud_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k == "anchor":
+            p.anchor[:] = [float(x) for x in v]
+        elif not hasattr(p, k) or k in ("struct_size", "reserved"):
+            raise TypeError(f"unknown cloud parameter {k!r}")
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def wall_cloud_directions(prm, **params):
+    """gm_wall_cloud_directions (host only): the (NK, 2) float64 table of (cos, sin) that gm_wall_map_cloud uses on a map
+    with the gm_wall_params `prm` under the cloud parameters given as keywords (block_sectors decides)."""
+    L = _lib.load()
+    c = _wall_cloud_params(**params)
+    got = C.c_uint32(0)
+    st = L.gm_wall_cloud_directions(C.byref(prm), C.byref(c), None, 0, C.byref(got))
+    if st not in (_lib.GM_OK, _lib.GM_ERR_CAPACITY):
+        raise _lib.GmError(st, "gm_wall_cloud_directions refused the parameters")
+    out = np.empty((int(got.value), 2), dtype=np.float64)
+    st = L.gm_wall_cloud_directions(C.byref(prm), C.byref(c), out.ctypes.data_as(C.POINTER(C.c_double)), len(out), C.byref(got))
+    if st != _lib.GM_OK:
+        raise _lib.GmError(st, "gm_wall_cloud_directions failed")
+    return out
 
 
 class WallMap:
@@ -688,6 +721,28 @@ class WallMap:
         d["cell_area"] = float(info.cell_area)
         metrics = [wall_region_metrics(self.prm, reg[i]) for i in range(len(reg))]
         return d, reg, metrics, (lab[:n * self.n_sectors].reshape(n, self.n_sectors).copy() if labels else None)
+
+    @staticmethod
+    def cloud_params(**kw):
+        """gm_wall_cloud_params with the library's defaults, then the keywords (block_stations, block_sectors, min_count,
+        exaggeration, anchor)."""
+        return _wall_cloud_params(**kw)
+
+    def cloud(self, station0=0, n=None, **params):
+        """gm_wall_map_cloud: stations [station0, station0 + n) as a point list, one WALL_CLOUD_POINT record per block of
+        block_stations x block_sectors cells that holds min_count points, ascending by block.  Returns (info dict,
+        records).  A count query first, then the sized call."""
+        s0, n = self._window(station0, n)
+        p = self.cloud_params(**params)
+        info = _lib.WallCloudInfo()
+        got = C.c_uint64(0)
+        self._ctx._check(self._L.gm_wall_map_cloud(self._h(), s0, n, C.byref(p), C.byref(info), None, 0, C.byref(got)))
+        cap = int(got.value)
+        pts = np.zeros(max(cap, 1), dtype=WALL_CLOUD_POINT)
+        if cap:
+            self._ctx._check(self._L.gm_wall_map_cloud(self._h(), s0, n, C.byref(p), C.byref(info),
+                                                       pts.ctypes.data_as(C.POINTER(_lib.WallCloudPoint)), cap, C.byref(got)))
+        return {k: int(getattr(info, k)) for k in _CLOUD_INFO}, pts[:int(got.value)].copy()
 
     def save(self, path):
         """The parameters and the raw cells as one .npz (numpy only)."""

@@ -359,6 +359,27 @@ struct WallRegionArgs {
 void launch_wall_region_label(const WallRegionArgs &a, hipStream_t s);    // three launches, up to the component count
 void launch_wall_region_reduce(const WallRegionArgs &a, hipStream_t s);   // two launches, up to the region list
 void launch_wall_region_labels(const WallRegionArgs &a, uint64_t first, uint64_t n, int32_t *out, hipStream_t s);
+// k_wall_cloud.hip (gm_wall_map_cloud): per chunk of whole block rows merge (unless bs = bk = 1) -> compact + emit
+constexpr int kWallCloudCounters = 4;              // u64: empty, below_min_count, the chunk's points (low word), pad
+constexpr uint32_t kWallCloudAccBytes = 28;        // merged accumulators per block: sum u64 | count u64 | lo, hi, cells u32
+struct WallCloudArgs {
+    WallTable map;
+    uint64_t first;            // station0 * nsec: map-wide index of window cell 0
+    uint32_t station0, n, nsec;
+    uint32_t bs, bk, NK;       // the block (clamped to the window and the ring), blocks per block row
+    uint32_t merged;           // 0: bs = bk = 1, the table is the source
+    uint32_t min_count;
+    uint32_t J0, nJ;           // the chunk: block rows [J0, J0 + nJ)
+    unsigned long long *acc_sum, *acc_cnt;      // [nJ * NK] merged accumulators of the chunk (zeroed by the caller)
+    uint32_t *acc_lo, *acc_hi, *acc_cells;
+    const double *dirs;        // [NK][2] cos, sin
+    double oa[3], a[3], u[3], v[3];   // o - anchor, and the design frame (fp64, not rounded)
+    double R, g, t_min, ds;
+    gm_wall_cloud_point *out;  // the chunk's staging
+    unsigned long long *ctr;   // [kWallCloudCounters]
+};
+void launch_wall_cloud_merge(const WallCloudArgs &a, hipStream_t s);
+void launch_wall_cloud_compact(const WallCloudArgs &a, const ScanState &st, hipStream_t s);
 // k_nearest.hip
 void launch_nearest(const float4 *pts, const uint32_t *n_ptr, uint32_t n_cap, const float4 *queries,
                     const uint32_t *nq_ptr, uint32_t nq_cap, unsigned long long *best, int32_t *idx, hipStream_t s,

@@ -7,6 +7,7 @@
 
 #include <algorithm>
 
+#include "gm_compact.hpp"
 #include "gm_internal.hpp"
 
 using namespace gm;
@@ -34,6 +35,20 @@ struct gm_wall_map {
     unsigned long long *rg_ctr = nullptr;   // [kWallRegionCounters]
     uint8_t *rg_recs = nullptr;    // per component: WallRegionAcc [cap] | gm_wall_region [cap]
     uint64_t rg_recs_cap = 0;
+    // gm_wall_map_cloud: the chunk (GM_WALL_CLOUD_CHUNK: tests, measurements; 0: kStageCells blocks) and the scratch,
+    // allocated on first use, grow-only.  The chained scan has a state of the map's own: a slot's belongs to the frame
+    // that may be in flight on that slot.
+    uint32_t cloud_chunk = 0;
+    uint8_t *cl_acc = nullptr;     // merged accumulators of a chunk, kWallCloudAccBytes per block
+    uint64_t cl_acc_cap = 0;
+    gm_wall_cloud_point *cl_stage = nullptr;   // a chunk's records
+    uint64_t cl_stage_cap = 0;
+    unsigned long long *cl_rec = nullptr;      // [cl_rec_cap] tile records of the chained scan | the ticket word
+    uint32_t cl_rec_cap = 0;
+    uint32_t cl_epoch = 0;         // launches of k_compact on this map so far
+    unsigned long long *cl_ctr = nullptr;      // [kWallCloudCounters]
+    double *cl_dirs = nullptr;     // [GM_WALL_MAX_SECTORS][2]
+    std::vector<double> cl_dirs_host;          // the table of the call in progress
 };
 
 namespace {
@@ -214,6 +229,7 @@ void free_map(gm_wall_map *m)
     if (m->stream) { hipStreamSynchronize(m->stream); hipStreamDestroy(m->stream); }
     hipFree(m->base); hipFree(m->stage); hipFree(m->pt_res); hipFree(m->pt_cell);
     hipFree(m->rg_cells); hipFree(m->rg_ctr); hipFree(m->rg_recs);
+    hipFree(m->cl_acc); hipFree(m->cl_stage); hipFree(m->cl_rec); hipFree(m->cl_ctr); hipFree(m->cl_dirs);
     delete m;
 }
 
@@ -232,6 +248,43 @@ gm_status read_window(gm_wall_map *m, uint32_t station0, uint32_t n, void *cells
         GMW_HIP(ctx, hipStreamSynchronize(m->stream));
     }
     return GM_OK;
+}
+
+// record array + ticket word + a fresh epoch for the next k_compact launch on the map's stream (next_scan's rule)
+ScanState next_cloud_scan(gm_wall_map *m)
+{
+    if (m->cl_epoch >= 0x1FFFFFFEu) {   // the counter wraps: clear the records behind every launch that wrote them
+        (void)hipMemsetAsync(m->cl_rec, 0, sizeof(unsigned long long) * ((size_t)m->cl_rec_cap + 1), m->stream);
+        m->cl_epoch = 0;
+    }
+    m->cl_epoch += 1u;
+    ScanState st;
+    st.status = m->cl_rec;
+    st.ticket = reinterpret_cast<uint32_t *>(m->cl_rec + m->cl_rec_cap);
+    st.epoch = m->cl_epoch;
+    st.frame_ptr = nullptr;
+    return st;
+}
+
+bool cloud_params_ok(const gm_wall_cloud_params &c)
+{
+    if (c.struct_size != sizeof(gm_wall_cloud_params) || c.block_stations < 1u || c.block_sectors < 1u || c.min_count < 1u) return false;
+    if (!isfinite(c.exaggeration) || !(c.exaggeration >= 0.0)) return false;
+    return isfinite(c.anchor[0]) && isfinite(c.anchor[1]) && isfinite(c.anchor[2]);
+}
+
+// the direction table of include/gm_hip.h: NK pairs (one operation per statement, as stated there)
+void cloud_directions(uint32_t nsec, uint32_t bk, double *cos_sin)
+{
+    const double two_pi = 6.283185307179586476925286766559;
+    const uint32_t NK = (nsec + bk - 1u) / bk;
+    for (uint32_t K = 0; K < NK; ++K) {
+        const uint32_t nk = nsec - K * bk < bk ? nsec - K * bk : bk;
+        const double f = (double)(2u * K * bk + nk) / (double)(2u * nsec);
+        const double phi = two_pi * f;
+        cos_sin[2 * K] = cos(phi);
+        cos_sin[2 * K + 1] = sin(phi);
+    }
 }
 
 }  // namespace
@@ -282,6 +335,10 @@ gm_status gm_wall_map_create(gm_ctx *ctx, const gm_wall_params *params, gm_wall_
             m->region_ts = ts;
             m->region_tk = tk;
         }
+    }
+    if (const char *e = getenv("GM_WALL_CLOUD_CHUNK")) {   // blocks; 0 or more than the default: the default (scratch is sized by it)
+        const unsigned long long v = strtoull(e, nullptr, 10);
+        m->cloud_chunk = v < kStageCells ? (uint32_t)v : 0u;
     }
     design_frame(m);
     auto body = [&]() -> gm_status {
@@ -631,6 +688,153 @@ gm_status gm_wall_map_regions(gm_wall_map *map, gm_wall_map *baseline, uint32_t 
         }
     }
     if (!fits && (regions || capacity)) return gm_fail(ctx, GM_ERR_CAPACITY, "gm_wall_map_regions: region buffer too small");
+    return GM_OK;
+}
+
+void gm_wall_cloud_default_params(gm_wall_cloud_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(gm_wall_cloud_params);
+    p->block_stations = 1;
+    p->block_sectors = 1;
+    p->min_count = 1;
+    p->exaggeration = 1.0;
+}
+
+gm_status gm_wall_cloud_directions(const gm_wall_params *p, const gm_wall_cloud_params *c, double *cos_sin, uint32_t capacity,
+                                   uint32_t *n_out)
+{
+    if (n_out) *n_out = 0;
+    if (!p || p->struct_size != sizeof(gm_wall_params) || p->n_sectors < 1u || p->n_sectors > GM_WALL_MAX_SECTORS) return GM_ERR_INVALID_ARG;
+    if (c && (c->struct_size != sizeof(gm_wall_cloud_params) || c->block_sectors < 1u)) return GM_ERR_INVALID_ARG;
+    if (!cos_sin && capacity) return GM_ERR_INVALID_ARG;
+    const uint32_t bk = std::min(c ? c->block_sectors : 1u, p->n_sectors);
+    const uint32_t NK = (p->n_sectors + bk - 1u) / bk;
+    if (n_out) *n_out = NK;
+    if (capacity < NK) return GM_ERR_CAPACITY;
+    cloud_directions(p->n_sectors, bk, cos_sin);
+    return GM_OK;
+}
+
+gm_status gm_wall_map_cloud(gm_wall_map *map, uint32_t station0, uint32_t n, const gm_wall_cloud_params *prm,
+                            gm_wall_cloud_info *info, gm_wall_cloud_point *points, uint64_t capacity, uint64_t *n_out)
+{
+    if (!map) return GM_ERR_INVALID_ARG;
+    gm_ctx *ctx = map->ctx;
+    if (n_out) *n_out = 0;
+    if (!info) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_cloud: NULL info");
+    gm_wall_cloud_params cp;
+    gm_wall_cloud_default_params(&cp);
+    if (prm) cp = *prm;
+    if (!cloud_params_ok(cp))
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_cloud: struct_size mismatch or a parameter outside its limits");
+    if (!points && capacity) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_cloud: NULL points with a capacity");
+    gm_status st = check_window(map, station0, n, ~0ull, nullptr, "");
+    if (st != GM_OK) return st;
+    st = sync_map(map);
+    if (st != GM_OK) return st;
+    const uint32_t nsec = map->prm.n_sectors;
+    const uint32_t bk = std::min(cp.block_sectors, nsec), bs = std::min(cp.block_stations, std::max(n, 1u));
+    const uint32_t NK = (nsec + bk - 1u) / bk, NJ = (n + bs - 1u) / bs;
+    memset(info, 0, sizeof(*info));
+    info->struct_size = (uint32_t)sizeof(gm_wall_cloud_info);
+    info->station0 = station0;
+    info->n_stations = n;
+    info->n_sectors = nsec;
+    info->blocks_stations = NJ;
+    info->blocks_sectors = NK;
+    info->blocks = (uint64_t)NJ * NK;
+    if (!n) return GM_OK;
+
+    // chunks of whole block rows
+    const uint64_t chunk = map->cloud_chunk ? map->cloud_chunk : kStageCells;
+    const uint32_t rows = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(chunk / NK, 1u), NJ);
+    const uint64_t cb = (uint64_t)rows * NK;   // blocks of a full chunk
+    const bool merged = bs > 1u || bk > 1u;
+    if (merged && map->cl_acc_cap < cb) {
+        hipFree(map->cl_acc);
+        map->cl_acc = nullptr; map->cl_acc_cap = 0;
+        GMW_HIP(ctx, hipMalloc((void **)&map->cl_acc, cb * kWallCloudAccBytes));
+        map->cl_acc_cap = cb;
+    }
+    if (map->cl_stage_cap < cb) {
+        hipFree(map->cl_stage);
+        map->cl_stage = nullptr; map->cl_stage_cap = 0;
+        GMW_HIP(ctx, hipMalloc((void **)&map->cl_stage, cb * sizeof(gm_wall_cloud_point)));
+        map->cl_stage_cap = cb;
+    }
+    const uint32_t nrec = compact_records((uint32_t)cb);
+    if (map->cl_rec_cap < nrec) {   // (nothing of the map's is in flight: the call synchronised above)
+        hipFree(map->cl_rec);
+        map->cl_rec = nullptr; map->cl_rec_cap = 0;
+        GMW_HIP(ctx, hipMalloc((void **)&map->cl_rec, sizeof(unsigned long long) * ((size_t)nrec + 1)));
+        GMW_HIP(ctx, hipMemsetAsync(map->cl_rec, 0, sizeof(unsigned long long) * ((size_t)nrec + 1), map->stream));
+        map->cl_rec_cap = nrec;
+    }
+    if (!map->cl_ctr) GMW_HIP(ctx, hipMalloc((void **)&map->cl_ctr, kWallCloudCounters * 8));
+    if (!map->cl_dirs) GMW_HIP(ctx, hipMalloc((void **)&map->cl_dirs, (size_t)GM_WALL_MAX_SECTORS * 16));
+    map->cl_dirs_host.resize((size_t)2 * NK);
+    cloud_directions(nsec, bk, map->cl_dirs_host.data());
+    GMW_HIP(ctx, hipMemcpyAsync(map->cl_dirs, map->cl_dirs_host.data(), (size_t)NK * 16, hipMemcpyHostToDevice, map->stream));
+    GMW_HIP(ctx, hipMemsetAsync(map->cl_ctr, 0, kWallCloudCounters * 8, map->stream));
+
+    WallCloudArgs a;
+    memset(&a, 0, sizeof(a));
+    a.map = map->table;
+    a.first = (uint64_t)station0 * nsec;
+    a.station0 = station0; a.n = n; a.nsec = nsec;
+    a.bs = bs; a.bk = bk; a.NK = NK;
+    a.merged = merged ? 1u : 0u;
+    a.min_count = cp.min_count;
+    if (merged) {
+        a.acc_sum = reinterpret_cast<unsigned long long *>(map->cl_acc);
+        a.acc_cnt = a.acc_sum + cb;
+        a.acc_lo = reinterpret_cast<uint32_t *>(a.acc_cnt + cb);
+        a.acc_hi = a.acc_lo + cb;
+        a.acc_cells = a.acc_hi + cb;
+    }
+    a.dirs = map->cl_dirs;
+    for (int k = 0; k < 3; ++k) {
+        a.oa[k] = map->o[k] - cp.anchor[k];
+        a.a[k] = map->a[k]; a.u[k] = map->u[k]; a.v[k] = map->v[k];
+    }
+    a.R = map->R;
+    a.g = cp.exaggeration;
+    a.t_min = map->prm.t_min;
+    a.ds = map->prm.station_length;
+    a.out = map->cl_stage;
+    a.ctr = map->cl_ctr;
+
+    uint64_t total = 0;
+    unsigned long long ctr[kWallCloudCounters] = {0ull, 0ull, 0ull, 0ull};
+    bool copying = points != nullptr;
+    for (uint32_t J0 = 0; J0 < NJ; J0 += rows) {   // (the trip count depends on the window alone)
+        a.J0 = J0;
+        a.nJ = std::min(rows, NJ - J0);
+        if (merged) {
+            GMW_HIP(ctx, hipMemsetAsync(map->cl_acc, 0, cb * kWallCloudAccBytes, map->stream));
+            launch_wall_cloud_merge(a, map->stream);
+            GMW_HIP(ctx, hipGetLastError());
+        }
+        launch_wall_cloud_compact(a, next_cloud_scan(map), map->stream);
+        GMW_HIP(ctx, hipGetLastError());
+        GMW_HIP(ctx, hipMemcpyAsync(ctr, map->cl_ctr, sizeof(ctr), hipMemcpyDeviceToHost, map->stream));
+        GMW_HIP(ctx, hipStreamSynchronize(map->stream));
+        const uint64_t got = (uint32_t)ctr[2];
+        if (copying && total + got > capacity) copying = false;   // copying stops, counting goes on
+        if (copying && got) {
+            GMW_HIP(ctx, hipMemcpyAsync(points + total, map->cl_stage, got * sizeof(gm_wall_cloud_point), hipMemcpyDeviceToHost,
+                                        map->stream));
+            GMW_HIP(ctx, hipStreamSynchronize(map->stream));
+        }
+        total += got;
+    }
+    info->points = total;
+    info->empty = ctr[0];
+    info->below_min_count = ctr[1];
+    if (n_out) *n_out = total;
+    if (points && total > capacity) return gm_fail(ctx, GM_ERR_CAPACITY, "gm_wall_map_cloud: point buffer too small");
     return GM_OK;
 }
 

@@ -1,0 +1,200 @@
+// k_wall_cloud.hip -- BUILD-DEFINED EXTENSION: the persistent wall map as an ordered, decimated point list
+// (gm_wall_map_cloud), the device side.
+//
+// The rule is stated in include/gm_hip.h and DESIGN.md; the CPU twin is tests/wall_cloud_np.py.  The host walks the
+// window in chunks of whole block rows (gm_wall.hip); per chunk:
+//   1. k_wall_cloud_merge     (skipped when bs = bk = 1: the table is then the source)  one merged accumulator per block
+//      of the chunk -- sum i64, count u64, the two keys, the number of non-empty cells -- into scratch the host has
+//      zeroed.  A work item is (block row, segment of up to kWcRows stations, sector), the sector fastest: lanes take
+//      consecutive sectors, so the SoA table is read coalesced, and each lane sums its sector over the segment's station
+//      rows.  Runs of one block in consecutive lanes are merged in the wave (surf_merge_runs' segmented reduction with a
+//      64-bit count: wc_merge_runs); the run's head lane adds what is left with integer atomics.  Integers only: the
+//      result does not depend on the grid or the order.
+//   2. k_compact<WallCloudPred, WallCloudEmit>  (gm_compact.hpp)  the predicate loads the block's accumulators as its
+//      payload and keeps count >= min_count; the emit step builds the 40-byte record at the survivor's rank in the
+//      staging buffer: survivors leave in block order from one launch.  The two other classes are counted in LDS and
+//      added once per class and block.  The position is fp64 with explicit roundings (__dmul_rn / __dadd_rn: nothing
+//      the build flags could contract) on a direction table the host computed; no fp64 trigonometry on the device.
+#include <string.h>
+
+#include "gm_compact.hpp"
+#include "gm_internal.hpp"
+
+namespace gm {
+
+static_assert(sizeof(gm_wall_cloud_point) == 40, "a 40-byte PointCloud2 row");
+constexpr int kWcThreads = 256;
+constexpr uint32_t kWcMaxBlocks = 4096;
+constexpr uint32_t kWcRows = 32;   // station rows one lane sums: a block of many stations is spread over several lanes
+
+// ---- 1. merge ----
+
+// surf_merge_runs (gm_device.hpp) with a 64-bit count and the number of non-empty cells beside it: runs of one block in
+// consecutive lanes -> the run's head lane.  Wave-uniform call.  Returns whether this lane still has to add its (merged)
+// contribution.
+__device__ __forceinline__ bool wc_merge_runs(int blk, unsigned long long &cn, unsigned long long &sm, uint32_t &lo, uint32_t &hi,
+                                              uint32_t &cells)
+{
+    const int lane = lane_id();
+    const int prev = __shfl_up(blk, 1, kWave);
+    const bool dup = lane > 0 && blk >= 0 && prev == blk;
+    const unsigned long long dmask = __ballot(dup);
+    if (dmask) {
+        const unsigned long long above = lane < kWave - 1 ? (~dmask & (~0ull << (lane + 1))) : 0ull;
+        const int tail = above ? __ffsll((long long)above) - 2 : kWave - 1;   // last lane of this lane's run
+#pragma unroll
+        for (int o = 1; o < kWave; o <<= 1) {
+            const unsigned long long ocn = __shfl_down(cn, o, kWave), osm = __shfl_down(sm, o, kWave);
+            const uint32_t olo = __shfl_down(lo, o, kWave), ohi = __shfl_down(hi, o, kWave), oce = __shfl_down(cells, o, kWave);
+            if (lane + o <= tail) {
+                cn += ocn; sm += osm; cells += oce;
+                lo = lo > olo ? lo : olo;
+                hi = hi > ohi ? hi : ohi;
+            }
+        }
+    }
+    return blk >= 0 && !dup;
+}
+
+__global__ __launch_bounds__(kWcThreads) void k_wall_cloud_merge(WallCloudArgs a, uint32_t nseg, uint32_t items)
+{
+    const int lane = lane_id();
+    const uint32_t nsec = a.nsec;
+    // wave-uniform trips (the run merge shuffles across the wave)
+    for (uint32_t w0 = blockIdx.x * kWcThreads + (threadIdx.x & ~(uint32_t)(kWave - 1)); w0 < items; w0 += gridDim.x * kWcThreads) {
+        const uint32_t it = w0 + lane;
+        int blk = -1;
+        uint32_t cells = 0u, lo = 0u, hi = 0u;
+        unsigned long long sm = 0ull, cn = 0ull;
+        if (it < items) {
+            const uint32_t k = it % nsec, r = it / nsec, seg = r % nseg, jl = r / nseg;
+            const uint32_t j0 = (a.J0 + jl) * a.bs;                       // window-relative, < n
+            const uint32_t end = a.n - j0 < a.bs ? a.n : j0 + a.bs;       // the block row's stations end here (ragged last row)
+            const uint32_t jb = j0 + seg * kWcRows, je = jb + kWcRows;     // (a segment past the ragged end: no trip)
+            for (uint32_t j = jb; j < end && j < je; ++j) {
+                const uint64_t c = a.first + (uint64_t)j * nsec + k;
+                const uint32_t cc = a.map.cnt[c];
+                if (cc) {
+                    const uint32_t l = a.map.lo[c], h = a.map.hi[c];
+                    cn += cc;
+                    sm += a.map.sum[c];
+                    lo = lo > l ? lo : l;
+                    hi = hi > h ? hi : h;
+                    ++cells;
+                }
+            }
+            blk = (int)(jl * a.NK + k / a.bk);
+        }
+        if (wc_merge_runs(blk, cn, sm, lo, hi, cells) && cells) {
+            atomicAdd(&a.acc_sum[blk], sm);
+            atomicAdd(&a.acc_cnt[blk], cn);
+            atomicMax(&a.acc_lo[blk], lo);
+            atomicMax(&a.acc_hi[blk], hi);
+            atomicAdd(&a.acc_cells[blk], cells);
+        }
+    }
+}
+
+// ---- 2. compact + emit ----
+
+// the block's counts of the two classes that do not survive: empty, below_min_count
+__device__ __forceinline__ uint32_t *wc_class_counts()
+{
+    __shared__ uint32_t c[2];
+    return c;
+}
+
+struct WallCloudPred {
+    WallCloudArgs a;
+    struct Payload { unsigned long long sum, count; uint32_t lo, hi, cells; };
+    __device__ __forceinline__ bool operator()(uint32_t i, Payload &p) const
+    {
+        p.sum = 0ull; p.lo = 0u; p.hi = 0u;
+        bool keep;
+        if (a.merged) {
+            p.count = a.acc_cnt[i];
+            p.cells = a.acc_cells[i];
+            keep = p.count >= (unsigned long long)a.min_count;   // (min_count >= 1: an empty block never passes)
+            if (keep) { p.sum = a.acc_sum[i]; p.lo = a.acc_lo[i]; p.hi = a.acc_hi[i]; }
+        } else {   // one cell per block: block row = station, NK = n_sectors
+            const uint64_t c = a.first + (uint64_t)a.J0 * a.NK + i;
+            const uint32_t cc = a.map.cnt[c];
+            p.count = cc;
+            p.cells = cc ? 1u : 0u;
+            keep = cc >= a.min_count;
+            if (keep) { p.sum = a.map.sum[c]; p.lo = a.map.lo[c]; p.hi = a.map.hi[c]; }
+        }
+        // (the lanes past the end of the input are not here: the ballots see the active lanes only)
+        const bool empty = p.count == 0ull;
+        const unsigned long long em = __ballot(empty), bm = __ballot(!empty && !keep);
+        const int lane = lane_id();
+        if (em && lane == (int)__builtin_ctzll(em)) atomicAdd(&wc_class_counts()[0], (uint32_t)__popcll(em));
+        if (bm && lane == (int)__builtin_ctzll(bm)) atomicAdd(&wc_class_counts()[1], (uint32_t)__popcll(bm));
+        return keep;
+    }
+};
+
+struct WallCloudEmit {
+    static constexpr bool kHasFinish = true, kHasPrepare = true;
+    WallCloudArgs a;
+    __device__ __forceinline__ void prepare() const
+    {
+        if (threadIdx.x < 2) wc_class_counts()[threadIdx.x] = 0u;
+    }
+    __device__ __forceinline__ void finish(uint32_t) const
+    {
+        __syncthreads();
+        if (threadIdx.x < 2) {
+            const uint32_t c = wc_class_counts()[threadIdx.x];
+            if (c) atomicAdd(&a.ctr[threadIdx.x], (unsigned long long)c);
+        }
+    }
+    __device__ __forceinline__ void operator()(uint32_t src, uint32_t dst, const WallCloudPred::Payload &p) const
+    {
+        const uint32_t jl = src / a.NK, K = src % a.NK, J = a.J0 + jl;
+        const uint32_t jw = J * a.bs;                                   // window-relative first station, < n
+        const uint32_t ns = a.n - jw < a.bs ? a.n - jw : a.bs;
+        const uint32_t j0 = a.station0 + jw;
+        const double m = __ddiv_rn(__dmul_rn((double)(long long)p.sum, 0x1p-20), (double)p.count);
+        const double h = __dmul_rn((double)(2u * j0 + ns), 0.5);
+        const double tc = __dadd_rn(a.t_min, __dmul_rn(h, a.ds));
+        const double rho = __dadd_rn(a.R, __dmul_rn(a.g, m));
+        const double c = a.dirs[2u * K], s = a.dirs[2u * K + 1u];
+        float xyz[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const double w = __dadd_rn(__dmul_rn(c, a.u[i]), __dmul_rn(s, a.v[i]));
+            const double q = __dadd_rn(__dadd_rn(a.oa[i], __dmul_rn(tc, a.a[i])), __dmul_rn(rho, w));
+            xyz[i] = __double2float_rn(q);
+        }
+        gm_wall_cloud_point r;
+        r.x = xyz[0]; r.y = xyz[1]; r.z = xyz[2];
+        r.mean = __double2float_rn(m);
+        r.min = ordered_to_float(~p.lo);
+        r.max = ordered_to_float(p.hi);
+        r.block = J * a.NK + K;
+        r.cells = p.cells;
+        r.count = p.count;
+        a.out[dst] = r;
+    }
+};
+
+void launch_wall_cloud_merge(const WallCloudArgs &a, hipStream_t s)
+{
+    const uint32_t nseg = (a.bs + kWcRows - 1u) / kWcRows;
+    const uint64_t items = (uint64_t)a.nJ * nseg * a.nsec;   // < 2^25: nJ * bs < 2 n, n * nsec <= 2^24
+    uint64_t b = (items + kWcThreads - 1) / kWcThreads;
+    b = b < 1 ? 1 : (b > kWcMaxBlocks ? kWcMaxBlocks : b);
+    hipLaunchKernelGGL(k_wall_cloud_merge, dim3((uint32_t)b), dim3(kWcThreads), 0, s, a, nseg, (uint32_t)items);
+}
+
+void launch_wall_cloud_compact(const WallCloudArgs &a, const ScanState &st, hipStream_t s)
+{
+    const uint32_t nb = a.nJ * a.NK;   // >= 1
+    WallCloudPred pred{a};
+    WallCloudEmit emit{a};
+    hipLaunchKernelGGL((k_compact<WallCloudPred, WallCloudEmit>), dim3(compact_grid(nb)), dim3(kCpThreads), 0, s, pred, emit,
+                       (const uint32_t *)nullptr, nb, st, reinterpret_cast<uint32_t *>(a.ctr + 2), (uint32_t *)nullptr);
+}
+
+}  // namespace gm

@@ -408,6 +408,19 @@ std::vector<gm_wall_region> Processor::wallMapRegions(unsigned station0, unsigne
     return regions;
 }
 
+std::vector<gm_wall_cloud_point> Processor::wallMapCloud(unsigned station0, unsigned n, const gm_wall_cloud_params &prm, gm_wall_cloud_info *info)
+{
+    if (!wall_) throw Error(GM_ERR_NOT_READY, "wallMapCloud: createWallMap first");
+    gm_wall_cloud_info local;
+    gm_wall_cloud_info *ip = info ? info : &local;
+    uint64_t count = 0;
+    check(gm_wall_map_cloud(wall_, station0, n, &prm, ip, 0, 0, &count), "wallMapCloud");
+    std::vector<gm_wall_cloud_point> points((size_t)count);
+    if (count) check(gm_wall_map_cloud(wall_, station0, n, &prm, ip, &points[0], count, &count), "wallMapCloud");
+    points.resize((size_t)count);
+    return points;
+}
+
 gm_wall_info Processor::wallMapInfo()
 {
     if (!wall_) throw Error(GM_ERR_NOT_READY, "wallMapInfo: createWallMap first");

@@ -147,6 +147,9 @@ public:
     // connected deviation regions of stations [station0, station0 + n) against the design (gm_wall_map_regions),
     // ascending by label; info, when given, receives the call's counts
     std::vector<gm_wall_region> wallMapRegions(unsigned station0, unsigned n, const gm_wall_region_params &prm, gm_wall_regions_info *info = nullptr);
+    // stations [station0, station0 + n) as a point list (gm_wall_map_cloud): one record per block of cells that holds
+    // prm.min_count points, ascending by block; info, when given, receives the call's counts
+    std::vector<gm_wall_cloud_point> wallMapCloud(unsigned station0, unsigned n, const gm_wall_cloud_params &prm, gm_wall_cloud_info *info = nullptr);
     gm_wall_map *wallMap() { return wall_; }
 
     gm_ctx *ctx() { return ctx_; }

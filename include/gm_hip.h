@@ -619,6 +619,78 @@ gm_status gm_wall_map_regions(gm_wall_map *map, gm_wall_map *baseline, uint32_t 
  * GM_ERR_INVALID_ARG: a NULL, p->struct_size mismatch, n_sectors 0, r->cells 0 or a sector extent outside n_sectors. */
 gm_status gm_wall_region_metrics(const gm_wall_params *p, const gm_wall_region *r, struct gm_wall_region_metrics *out);
 
+/* ---- the wall map as an ordered, decimated point list (gm_wall_map_cloud) --------------------------------------------
+ * The surveyed wall as a cloud: one point per BLOCK of cells that holds enough points, sitting on the design cylinder
+ * displaced by the block's mean deviation, in block order.  Blocks are merged in integers, so a block is a function of
+ * the raw cells alone, and only the surviving records leave the device.
+ *   blocks      the window is stations [station0, station0 + n); NJ = ceil(n / bs), NK = ceil(n_sectors / bk).  Block
+ *               (J, K) covers stations j0 = station0 + J bs .. j0 + ns_J - 1, ns_J = min(bs, station0 + n - j0), and
+ *               sectors K bk .. K bk + nk_K - 1, nk_K = min(bk, n_sectors - K bk): the last blocks are ragged, nothing
+ *               wraps, and bs > n or bk > n_sectors is one block in that direction.
+ *   merge       count = u64 sum of the cells' counts, sum = int64 sum of their sums, min_key and max_key = the maxima of
+ *               their keys, cells = the number of cells with count > 0.
+ *   classes     every block is exactly one of EMPTY (count 0), BELOW_MIN_COUNT (0 < count < min_count) or a POINT.
+ *   record      m = (double) sum 2^-20 / (double) count (conversions round to nearest); mean = (float) m;
+ *               min = ordered^-1(~min_key), max = ordered^-1(max_key), as gm_wall_map_read does for one cell.
+ *   directions  host, once per call: phi_K = (2 pi) ((double)(2 K bk + nk_K) / (double)(2 n_sectors)), c_K = cos phi_K,
+ *               s_K = sin phi_K by the host's libm (phi is 0 toward u and grows toward v, as in the binning).  The
+ *               table (NK <= 4096 pairs) is uploaded: the device calls no fp64 trigonometric function, and
+ *               gm_wall_cloud_directions returns exactly the table the call uses.
+ *   position    fp64 on the map's unrounded design frame (o, a, u, v, R), t_min and ds = station_length; every
+ *               operation rounded once, none contracted, in this order:
+ *                   h = (double)(2 j0 + ns_J) 0.5,  t_c = t_min + h ds,  rho = R + g m,  w_i = c_K u_i + s_K v_i,
+ *                   p_i = ((o_i - anchor_i) + t_c a_i) + rho w_i,  x, y, z = (float) p_i
+ *               with g = exaggeration.  A map coordinate at chainage 5 km has 0.5 mm of fp32 resolution: a host sets
+ *               the anchor near the window and publishes with that offset in the frame transform.
+ *   order       ascending by block = J NK + K.
+ * On the device a window is processed in chunks of whole block rows of at most 2^20 blocks (environment
+ * GM_WALL_CLOUD_CHUNK=<blocks>, rounded down to whole block rows, at least one row, a value above 2^20 meaning 2^20, read
+ * at gm_wall_map_create: tests and measurements); the trip count depends on the window, never on the data, and the result does not depend on it. */
+typedef struct gm_wall_cloud_params {
+    uint32_t struct_size;      /* = sizeof(gm_wall_cloud_params) */
+    uint32_t block_stations;   /* bs >= 1 (default 1) */
+    uint32_t block_sectors;    /* bk >= 1 (default 1) */
+    uint32_t min_count;        /* >= 1 (default 1): merged points a block needs to become a point */
+    double   exaggeration;     /* g, finite, >= 0 (default 1): the point sits at radius R + g * mean */
+    double   anchor[3];        /* finite (default 0, 0, 0): subtracted in fp64 before the one rounding to fp32 */
+    uint64_t reserved;         /* 0 */
+} gm_wall_cloud_params;
+
+typedef struct gm_wall_cloud_point {   /* 40 bytes: a PointCloud2 row, x y z FLOAT32 at 0, 4, 8 */
+    float    x, y, z;          /* map coordinates minus anchor */
+    float    mean, min, max;   /* gm_wall_map_read's rule applied to the merged accumulators */
+    uint32_t block;            /* J * NK + K */
+    uint32_t cells;            /* non-empty source cells merged */
+    uint64_t count;            /* merged points */
+} gm_wall_cloud_point;
+
+typedef struct gm_wall_cloud_info {
+    uint32_t struct_size;      /* = sizeof(gm_wall_cloud_info), filled by the library */
+    uint32_t station0, n_stations, n_sectors;     /* the window and the map's sectors */
+    uint32_t blocks_stations, blocks_sectors;     /* NJ, NK */
+    uint64_t blocks, points, below_min_count, empty;   /* blocks = points + below_min_count + empty */
+} gm_wall_cloud_info;
+
+/* Host only: the defaults of the table above.  A NULL is ignored. */
+void gm_wall_cloud_default_params(gm_wall_cloud_params *p);
+/* Host only, no device, no map: the NK (cos, sin) pairs of the rule above for p->n_sectors and c->block_sectors (c NULL:
+ * the defaults), cos_sin[2 K] = c_K, cos_sin[2 K + 1] = s_K.  *n_out (may be NULL) = NK; a capacity (in pairs) below NK
+ * returns GM_ERR_CAPACITY and writes nothing.  GM_ERR_INVALID_ARG: p NULL, a struct_size mismatch, n_sectors outside
+ * 1 .. GM_WALL_MAX_SECTORS, block_sectors 0, cos_sin NULL with capacity > 0. */
+gm_status gm_wall_cloud_directions(const gm_wall_params *p, const gm_wall_cloud_params *c, double *cos_sin, uint32_t capacity,
+                                   uint32_t *n_out);
+/* The points of the window, ascending by block.  Synchronises the map (as gm_wall_map_sync), runs on the map's stream and
+ * blocks.  prm NULL: the defaults.  info is required; it and *n_out (may be NULL; the number of points) are filled
+ * whenever the call got as far as the device, also on GM_ERR_CAPACITY.  points NULL with capacity 0 is a count query
+ * (GM_OK); a capacity below *n_out returns GM_ERR_CAPACITY and leaves the contents of points unspecified (copying stops,
+ * counting goes on).  n = 0 gives no points.  The map is not changed.  Scratch (28 B per block of a chunk unless
+ * bs = bk = 1, 40 B per block of a chunk of staging, the chained scan's own records, the direction table) is allocated
+ * on first use, kept grow-only in the map and freed with it; a map that never calls this allocates nothing.
+ * GM_ERR_INVALID_ARG: NULL map / info, a window outside the map, a struct_size mismatch, a parameter outside its limits,
+ * points NULL with capacity > 0. */
+gm_status gm_wall_map_cloud(gm_wall_map *map, uint32_t station0, uint32_t n, const gm_wall_cloud_params *prm,
+                            gm_wall_cloud_info *info, gm_wall_cloud_point *points, uint64_t capacity, uint64_t *n_out);
+
 /* "Compressed map" record of a completed slot.  The reference defines no such
  * output; this is a build-defined format: header, primitive records,
  * then n_voxels rows of x,y,z,count (float32).  Returns the bytes needed in
