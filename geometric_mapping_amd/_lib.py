@@ -63,6 +63,10 @@ GM_WALL_MAX_CELLS = 1 << 24
 GM_WALL_MAX_SECTORS = 4096
 GM_WALL_REGION_TILE = (64, 64)   # stations x sectors: the labelling kernel's default tile
 
+GM_WALL_CHECK_MEAN, GM_WALL_CHECK_ENVELOPE = 0, 1
+(GM_WALL_CHECK_CLS_PLANE, GM_WALL_CHECK_CLS_BEYOND_GATE, GM_WALL_CHECK_CLS_OUTSIDE, GM_WALL_CHECK_CLS_UNSURVEYED,
+ GM_WALL_CHECK_CLS_UNCHANGED, GM_WALL_CHECK_CLS_CHANGED_POS, GM_WALL_CHECK_CLS_CHANGED_NEG) = range(7)
+
 GM_N_STAGES = 9
 STAGE_NAMES = ("upload", "crop", "grid", "normals", "compact", "frame", "voxel", "ransac", "total")
 
@@ -180,6 +184,23 @@ class WallCloudInfo(C.Structure):
                 ("blocks", C.c_uint64), ("points", C.c_uint64), ("below_min_count", C.c_uint64), ("empty", C.c_uint64)]
 
 
+class WallCheckParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reference", C.c_uint32), ("min_count", C.c_uint32), ("reserved", C.c_uint32),
+                ("threshold", C.c_double), ("gate", C.c_double)]
+
+
+class WallCheckPoint(C.Structure):
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("delta", C.c_float), ("e", C.c_float),
+                ("cell", C.c_int32), ("index", C.c_uint32), ("row", C.c_uint32)]
+
+
+class WallCheckInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("status", C.c_uint32), ("threshold_q", C.c_int64), ("n_points", C.c_uint32),
+                ("plane", C.c_uint32), ("beyond_gate", C.c_uint32), ("outside", C.c_uint32), ("unsurveyed", C.c_uint32),
+                ("unchanged", C.c_uint32), ("changed_pos", C.c_uint32), ("changed_neg", C.c_uint32),
+                ("peak_pos", C.c_int64), ("peak_neg", C.c_int64)]
+
+
 class GmError(RuntimeError):
     def __init__(self, status, message):
         super().__init__(f"libgm_hip: status {status}: {message}")
@@ -244,6 +265,7 @@ def load():
     wregp, wrprmp, wrinfop, wrmetp = (C.POINTER(WallRegion), C.POINTER(WallRegionParams), C.POINTER(WallRegionsInfo),
                                       C.POINTER(WallRegionMetrics))
     wcprmp, wcptp, wcinfop = C.POINTER(WallCloudParams), C.POINTER(WallCloudPoint), C.POINTER(WallCloudInfo)
+    wkprmp, wkptp, wkinfop = C.POINTER(WallCheckParams), C.POINTER(WallCheckPoint), C.POINTER(WallCheckInfo)
     proto = {
         "gm_create": (C.c_int, [cfgp, C.POINTER(vp)]),
         "gm_destroy": (None, [vp]),
@@ -306,6 +328,11 @@ def load():
         "gm_wall_cloud_default_params": (None, [wcprmp]),
         "gm_wall_cloud_directions": (C.c_int, [wprmp, wcprmp, dp, u32, u32p]),
         "gm_wall_map_cloud": (C.c_int, [vp, u32, u32, wcprmp, wcinfop, wcptp, u64, u64p]),
+        "gm_wall_check_default_params": (None, [wkprmp]),
+        "gm_wall_check_classify": (C.c_int, [wkprmp, wrawp, C.c_float, C.POINTER(C.c_int64), u32p]),
+        "gm_wall_map_check_frame": (C.c_int, [vp, vp, u32, dp, wkprmp, waddp]),
+        "gm_wall_map_get_check": (C.c_int, [vp, u32, wkinfop, wkptp, u32, u32p]),
+        "gm_wall_map_check_points": (C.c_int, [vp, fp, u32, u8p, dp, wkprmp, waddp, wkinfop, wkptp, u32, u32p, fp, i32p, i32p, u8p]),
         "gm_group_create": (C.c_int, [cfgp, i32p, u32, u32, C.POINTER(vp)]),
         "gm_group_destroy": (None, [vp]),
         "gm_group_size": (u32, [vp]),

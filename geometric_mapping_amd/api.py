@@ -506,6 +506,33 @@ WALL_CLOUD_POINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("mean", 
                              ("block", "<u4"), ("cells", "<u4"), ("count", "<u8")])   # gm_wall_cloud_point, 40 bytes
 _CLOUD_INFO = ("station0", "n_stations", "n_sectors", "blocks_stations", "blocks_sectors", "blocks", "points",
                "below_min_count", "empty")
+WALL_CHECK_POINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("delta", "<f4"), ("e", "<f4"), ("cell", "<i4"),
+                             ("index", "<u4"), ("row", "<u4")])   # gm_wall_check_point, 32 bytes
+_CHECK_INFO = ("status", "threshold_q", "n_points", "plane", "beyond_gate", "outside", "unsurveyed", "unchanged",
+               "changed_pos", "changed_neg", "peak_pos", "peak_neg")
+
+
+def _wall_check_params(**kw):
+    p = _lib.WallCheckParams()
+    _lib.load().gm_wall_check_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k in ("struct_size", "reserved"):
+            raise TypeError(f"unknown check parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def wall_check_classify(raw_cell, e, **params):
+    """gm_wall_check_classify (host only): (delta int, cls int) of one RAW_CELL record and one fp32 residual under the
+    check parameters given as keywords.  plane and outside are not decidable from these inputs."""
+    r = np.ascontiguousarray(np.asarray(raw_cell, dtype=RAW_CELL).reshape(1))
+    p = _wall_check_params(**params)
+    d, c = C.c_int64(0), C.c_uint32(0)
+    st = _lib.load().gm_wall_check_classify(C.byref(p), r.ctypes.data_as(C.POINTER(_lib.WallRawCell)), C.c_float(float(np.float32(e))),
+                                            C.byref(d), C.byref(c))
+    if st != _lib.GM_OK:
+        raise _lib.GmError(st, "gm_wall_check_classify refused the parameters")
+    return int(d.value), int(c.value)
 
 
 def wall_region_metrics(prm, region):
@@ -743,6 +770,63 @@ class WallMap:
             self._ctx._check(self._L.gm_wall_map_cloud(self._h(), s0, n, C.byref(p), C.byref(info),
                                                        pts.ctypes.data_as(C.POINTER(_lib.WallCloudPoint)), cap, C.byref(got)))
         return {k: int(getattr(info, k)) for k in _CLOUD_INFO}, pts[:int(got.value)].copy()
+
+    @staticmethod
+    def check_params(**kw):
+        """gm_wall_check_params with the library's defaults, then the keywords (reference, min_count, threshold, gate)."""
+        return _wall_check_params(**kw)
+
+    def check_frame(self, slot=0, pose=np.eye(4)[:3], **params):
+        """gm_wall_map_check_frame: enqueue the check of the slot's last submitted frame under `pose` against this map.
+        Returns the add info dict (its gate is the check's); check_result() fetches the result."""
+        m = self._pose(pose)
+        p = self.check_params(**params)
+        i = _lib.WallAddInfo()
+        self._ctx._check(self._L.gm_wall_map_check_frame(self._h(), self._ctx._ctx, slot, m.ctypes.data_as(C.POINTER(C.c_double)),
+                                                         C.byref(p), C.byref(i)))
+        return self._add_info(i)
+
+    @staticmethod
+    def _check_info(i):
+        return {k: int(getattr(i, k)) for k in _CHECK_INFO}
+
+    def check_result(self, slot=0):
+        """gm_wall_map_get_check: (info dict, WALL_CHECK_POINT records ascending by index) of the last check on the slot.
+        A count query first, then the sized call."""
+        info = _lib.WallCheckInfo()
+        got = C.c_uint32(0)
+        self._ctx._check(self._L.gm_wall_map_get_check(self._h(), slot, C.byref(info), None, 0, C.byref(got)))
+        cap = int(got.value)
+        pts = np.zeros(max(cap, 1), dtype=WALL_CHECK_POINT)
+        if cap:
+            self._ctx._check(self._L.gm_wall_map_get_check(self._h(), slot, C.byref(info),
+                                                           pts.ctypes.data_as(C.POINTER(_lib.WallCheckPoint)), cap, C.byref(got)))
+        return self._check_info(info), pts[:int(got.value)].copy()
+
+    def check_points(self, cloud, pose=np.eye(4)[:3], labels=None, outputs=True, **params):
+        """gm_wall_map_check_points on a host cloud [n,3]: (info dict, records, dict(e float32, cell int32, delta int32,
+        cls uint8) or None without outputs).  The list buffer holds n rows: one call."""
+        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+        m = self._pose(pose)
+        lab, lp = GeometricMapping._u8(labels)
+        p = self.check_params(**params)
+        n = len(xyz)
+        add, info, got = _lib.WallAddInfo(), _lib.WallCheckInfo(), C.c_uint32(0)
+        pts = np.zeros(max(n, 1), dtype=WALL_CHECK_POINT)
+        out = None
+        if outputs:
+            out = dict(e=np.empty(max(n, 1), np.float32), cell=np.empty(max(n, 1), np.int32), delta=np.empty(max(n, 1), np.int32),
+                       cls=np.empty(max(n, 1), np.uint8))
+        i32p = C.POINTER(C.c_int32)
+        self._ctx._check(self._L.gm_wall_map_check_points(
+            self._h(), _f32(xyz), n, lp, m.ctypes.data_as(C.POINTER(C.c_double)), C.byref(p), C.byref(add), C.byref(info),
+            pts.ctypes.data_as(C.POINTER(_lib.WallCheckPoint)), n, C.byref(got),
+            _f32(out["e"]) if outputs else None, out["cell"].ctypes.data_as(i32p) if outputs else None,
+            out["delta"].ctypes.data_as(i32p) if outputs else None,
+            out["cls"].ctypes.data_as(C.POINTER(C.c_uint8)) if outputs else None))
+        d = self._check_info(info)
+        d["add"] = self._add_info(add)
+        return d, pts[:int(got.value)].copy(), ({k: v[:n].copy() for k, v in out.items()} if outputs else None)
 
     def save(self, path):
         """The parameters and the raw cells as one .npz (numpy only)."""

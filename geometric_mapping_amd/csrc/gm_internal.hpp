@@ -380,6 +380,51 @@ struct WallCloudArgs {
 };
 void launch_wall_cloud_merge(const WallCloudArgs &a, hipStream_t s);
 void launch_wall_cloud_compact(const WallCloudArgs &a, const ScanState &st, hipStream_t s);
+// k_wall_check.hip (gm_wall_map_check_*): one k_compact launch per check
+// u64 words: the seven classes (GM_WALL_CHECK_CLS_* order), peak_pos, -peak_neg, the changed points (low word), n_points, pad
+constexpr int kWallCheckCounters = 12;
+struct WallCheckArgs {
+    WallArgs w;                // the add's arguments (its window fields unused); gate is the check's; res / cell: stage call only
+    uint32_t reference, min_count;
+    long long T;
+    uint32_t row_is_index;     // stage call: row = index (the frame path takes the valid cloud's pad word)
+    gm_wall_check_point *out;  // staging, >= n_cap rows
+    unsigned long long *ctr;   // [kWallCheckCounters], zeroed by the caller on the same stream
+    int32_t *delta;            // stage call only (nullptr in the frame path)
+    uint8_t *cls;
+};
+// n_cap: the most points the launch can see (the grid is sized by it)
+void launch_wall_check(const WallCheckArgs &a, uint32_t n_cap, const ScanState &st, hipStream_t s);
+// the rule's integers, shared by the kernel and gm_wall_check_classify
+__host__ __device__ inline long long wall_check_fix(float e)   // (int64) rint(e 2^20), saturating at int32, 0 for a NaN
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (long long)__float2int_rn(__fmul_rn(e, 1048576.0f));
+#else
+    const volatile float p = e * 1048576.0f;
+    if (p != p) return 0;
+    if (p >= 2147483648.0f) return 2147483647ll;
+    if (p <= -2147483648.0f) return -2147483647ll - 1;
+    return (long long)__builtin_rintf(p);
+#endif
+}
+// delta and class of a point with residual e (inside the gate) in a cell (sum, count, lo = ~ordered(min), hi = ordered(max))
+__host__ __device__ inline uint32_t wall_check_rule(uint32_t reference, uint32_t min_count, long long T, long long sum, uint32_t count,
+                                                    uint32_t lo, uint32_t hi, float e, long long &delta)
+{
+    delta = 0;
+    if (count < min_count) return GM_WALL_CHECK_CLS_UNSURVEYED;
+    const long long eq = wall_check_fix(e);
+    if (reference == GM_WALL_CHECK_ENVELOPE) {
+        const long long lq = wall_check_fix(ordered_to_float(~lo)), hq = wall_check_fix(ordered_to_float(hi));
+        delta = eq > hq ? eq - hq : (eq < lq ? eq - lq : 0);
+    } else {
+        const long long q = sum / (long long)count;
+        delta = (long long)((unsigned long long)eq - (unsigned long long)q);   // (wraps instead of overflowing on a merged cell of no survey)
+    }
+    return delta >= T ? GM_WALL_CHECK_CLS_CHANGED_POS : (delta <= -T ? GM_WALL_CHECK_CLS_CHANGED_NEG : GM_WALL_CHECK_CLS_UNCHANGED);
+}
+
 // k_nearest.hip
 void launch_nearest(const float4 *pts, const uint32_t *n_ptr, uint32_t n_cap, const float4 *queries,
                     const uint32_t *nq_ptr, uint32_t nq_cap, unsigned long long *best, int32_t *idx, hipStream_t s,

@@ -12,6 +12,23 @@
 
 using namespace gm;
 
+// gm_wall_map_check_*: the state of one (map, slot), allocated on first use, grow-only, freed with the map
+struct WallCheckSlot {
+    gm_wall_check_point *stage = nullptr;   // the changed rows of the last check, in order
+    uint32_t stage_cap = 0;
+    unsigned long long *rec = nullptr;      // [rec_cap] tile records of the chained scan | the ticket word: the check's own
+    uint32_t rec_cap = 0;                   //   (the slot's belongs to the frame that may be in flight)
+    uint32_t epoch = 0;                     // launches of k_compact on rec so far
+    unsigned long long *ctr = nullptr;      // device [kWallCheckCounters]
+    unsigned long long *h_ctr = nullptr;    // pinned copy, valid once `done` has passed
+    hipEvent_t done = nullptr;              // recorded behind the check and the copy of its counters
+    hipEvent_t adds = nullptr;              // recorded on this slot's stream by a check on another slot: the adds so far
+    bool have = false;                      // a check was enqueued: a result is (or will be) readable
+    bool outstanding = false;               // the host has not waited for `done` yet
+    uint32_t status = 0;
+    long long T = 0;
+};
+
 struct gm_wall_map {
     gm_ctx *ctx = nullptr;
     gm_wall_params prm;
@@ -49,6 +66,11 @@ struct gm_wall_map {
     unsigned long long *cl_ctr = nullptr;      // [kWallCloudCounters]
     double *cl_dirs = nullptr;     // [GM_WALL_MAX_SECTORS][2]
     std::vector<double> cl_dirs_host;          // the table of the call in progress
+    // gm_wall_map_check_*
+    std::vector<WallCheckSlot> checks;         // per slot of ctx
+    int32_t *ck_delta = nullptr;               // gm_wall_map_check_points' per-point outputs beside pt_res / pt_cell (grow-only)
+    uint8_t *ck_cls = nullptr;
+    uint32_t ck_cap = 0;
 };
 
 namespace {
@@ -207,6 +229,11 @@ gm_status sync_map(gm_wall_map *m)
             GMW_HIP(ctx, hipStreamSynchronize(ctx->slots[i].stream));
             m->pending[i] = 0;
         }
+    for (WallCheckSlot &c : m->checks)
+        if (c.outstanding) {
+            GMW_HIP(ctx, hipEventSynchronize(c.done));
+            c.outstanding = false;
+        }
     GMW_HIP(ctx, hipStreamSynchronize(m->stream));
     return GM_OK;
 }
@@ -226,6 +253,14 @@ void free_map(gm_wall_map *m)
     hipSetDevice(m->ctx->device);
     for (uint32_t i = 0; i < m->ctx->n_slots; ++i)
         if (m->pending[i] && m->ctx->slots[i].stream) hipStreamSynchronize(m->ctx->slots[i].stream);
+    for (WallCheckSlot &c : m->checks) {
+        if (c.outstanding) hipEventSynchronize(c.done);
+        hipFree(c.stage); hipFree(c.rec); hipFree(c.ctr);
+        if (c.h_ctr) hipHostFree(c.h_ctr);
+        if (c.done) hipEventDestroy(c.done);
+        if (c.adds) hipEventDestroy(c.adds);
+    }
+    hipFree(m->ck_delta); hipFree(m->ck_cls);
     if (m->stream) { hipStreamSynchronize(m->stream); hipStreamDestroy(m->stream); }
     hipFree(m->base); hipFree(m->stage); hipFree(m->pt_res); hipFree(m->pt_cell);
     hipFree(m->rg_cells); hipFree(m->rg_ctr); hipFree(m->rg_recs);
@@ -287,6 +322,129 @@ void cloud_directions(uint32_t nsec, uint32_t bk, double *cos_sin)
     }
 }
 
+// ---- gm_wall_map_check_* ----
+
+bool check_prm_ok(const gm_wall_check_params &c, long long &T)
+{
+    T = 0;
+    if (c.struct_size != sizeof(gm_wall_check_params) || c.reference > (uint32_t)GM_WALL_CHECK_ENVELOPE || c.min_count < 1u) return false;
+    if (!(c.threshold > 0.0) || !(c.threshold <= 8.0) || !(c.gate > 0.0) || !(c.gate <= 8.0)) return false;
+    T = (long long)rint(c.threshold * 1048576.0);
+    return T >= 1;
+}
+
+// The scratch of (map, slot) for a check of up to n_cap points, and everything a launch on `s` needs before it: zeroed
+// counters, a fresh scan state.
+gm_status check_prepare(gm_wall_map *m, uint32_t slot, uint32_t n_cap, hipStream_t s, ScanState &st)
+{
+    gm_ctx *ctx = m->ctx;
+    WallCheckSlot &c = m->checks[slot];
+    if (!c.done) GMW_HIP(ctx, hipEventCreateWithFlags(&c.done, hipEventDisableTiming));
+    if (!c.ctr) GMW_HIP(ctx, hipMalloc((void **)&c.ctr, kWallCheckCounters * 8));
+    if (!c.h_ctr) GMW_HIP(ctx, hipHostMalloc((void **)&c.h_ctr, kWallCheckCounters * 8, hipHostMallocDefault));
+    const uint32_t nrec = compact_records(n_cap);
+    if (c.stage_cap < n_cap || c.rec_cap < nrec) {
+        if (c.outstanding) {   // the slot's last check may still be writing the old blocks
+            GMW_HIP(ctx, hipEventSynchronize(c.done));
+            c.outstanding = false;
+        }
+        c.have = false;        // (its rows go with the block)
+    }
+    if (c.stage_cap < n_cap) {
+        hipFree(c.stage);
+        c.stage = nullptr; c.stage_cap = 0;
+        GMW_HIP(ctx, hipMalloc((void **)&c.stage, (size_t)n_cap * sizeof(gm_wall_check_point)));
+        c.stage_cap = n_cap;
+    }
+    if (c.rec_cap < nrec) {
+        hipFree(c.rec);
+        c.rec = nullptr; c.rec_cap = 0;
+        GMW_HIP(ctx, hipMalloc((void **)&c.rec, sizeof(unsigned long long) * ((size_t)nrec + 1)));
+        GMW_HIP(ctx, hipMemsetAsync(c.rec, 0, sizeof(unsigned long long) * ((size_t)nrec + 1), s));
+        c.rec_cap = nrec;
+    }
+    if (c.epoch >= 0x1FFFFFFEu) {   // next_scan's rule
+        GMW_HIP(ctx, hipMemsetAsync(c.rec, 0, sizeof(unsigned long long) * ((size_t)c.rec_cap + 1), s));
+        c.epoch = 0;
+    }
+    c.epoch += 1u;
+    st.status = c.rec;
+    st.ticket = reinterpret_cast<uint32_t *>(c.rec + c.rec_cap);
+    st.epoch = c.epoch;
+    st.frame_ptr = nullptr;
+    GMW_HIP(ctx, hipMemsetAsync(c.ctr, 0, kWallCheckCounters * 8, s));
+    return GM_OK;
+}
+
+// `s` (the stream of `slot`) waits for the adds enqueued so far on every other slot's stream: an event, no host block
+gm_status check_wait_adds(gm_wall_map *m, uint32_t slot, hipStream_t s)
+{
+    gm_ctx *ctx = m->ctx;
+    for (uint32_t i = 0; i < ctx->n_slots; ++i) {
+        if (i == slot || !m->pending[i]) continue;
+        WallCheckSlot &o = m->checks[i];
+        if (!o.adds) GMW_HIP(ctx, hipEventCreateWithFlags(&o.adds, hipEventDisableTiming));
+        GMW_HIP(ctx, hipEventRecord(o.adds, ctx->slots[i].stream));
+        GMW_HIP(ctx, hipStreamWaitEvent(s, o.adds, 0));
+    }
+    return GM_OK;
+}
+
+// the launch, the copy of its counters and the event behind both
+gm_status check_enqueue(gm_wall_map *m, uint32_t slot, const WallCheckArgs &a, uint32_t n_cap, const ScanState &st, hipStream_t s)
+{
+    gm_ctx *ctx = m->ctx;
+    WallCheckSlot &c = m->checks[slot];
+    launch_wall_check(a, n_cap, st, s);
+    GMW_HIP(ctx, hipGetLastError());
+    GMW_HIP(ctx, hipMemcpyAsync(c.h_ctr, c.ctr, kWallCheckCounters * 8, hipMemcpyDeviceToHost, s));
+    GMW_HIP(ctx, hipEventRecord(c.done, s));
+    c.have = true;
+    c.outstanding = true;
+    c.status = m->status;
+    c.T = a.T;
+    return GM_OK;
+}
+
+// the result of (map, slot) once `done` has passed
+gm_status check_result(gm_wall_map *m, uint32_t slot, gm_wall_check_info *info, gm_wall_check_point *points, uint32_t capacity,
+                       uint32_t *n_out)
+{
+    gm_ctx *ctx = m->ctx;
+    WallCheckSlot &c = m->checks[slot];
+    if (c.outstanding) {
+        GMW_HIP(ctx, hipEventSynchronize(c.done));
+        c.outstanding = false;
+    }
+    const unsigned long long *h = c.h_ctr;
+    if (info) {
+        memset(info, 0, sizeof(*info));
+        info->struct_size = (uint32_t)sizeof(gm_wall_check_info);
+        info->status = c.status;
+        info->threshold_q = c.T;
+        info->n_points = (uint32_t)h[10];
+        info->plane = (uint32_t)h[GM_WALL_CHECK_CLS_PLANE];
+        info->beyond_gate = (uint32_t)h[GM_WALL_CHECK_CLS_BEYOND_GATE];
+        info->outside = (uint32_t)h[GM_WALL_CHECK_CLS_OUTSIDE];
+        info->unsurveyed = (uint32_t)h[GM_WALL_CHECK_CLS_UNSURVEYED];
+        info->unchanged = (uint32_t)h[GM_WALL_CHECK_CLS_UNCHANGED];
+        info->changed_pos = (uint32_t)h[GM_WALL_CHECK_CLS_CHANGED_POS];
+        info->changed_neg = (uint32_t)h[GM_WALL_CHECK_CLS_CHANGED_NEG];
+        info->peak_pos = (int64_t)h[7];
+        info->peak_neg = (int64_t)(0ull - h[8]);
+    }
+    const uint32_t got = (uint32_t)h[9];
+    if (n_out) *n_out = got;
+    if (!points && capacity) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map check: NULL points with a capacity");
+    if (!points) return GM_OK;   // a count query
+    if (got > capacity) return gm_fail(ctx, GM_ERR_CAPACITY, "gm_wall_map check: point buffer too small");
+    if (got) {   // on the map's own stream: the slot's may be busy with the next frame
+        GMW_HIP(ctx, hipMemcpyAsync(points, c.stage, (size_t)got * sizeof(gm_wall_check_point), hipMemcpyDeviceToHost, m->stream));
+        GMW_HIP(ctx, hipStreamSynchronize(m->stream));
+    }
+    return GM_OK;
+}
+
 }  // namespace
 
 namespace gm {
@@ -328,6 +486,7 @@ gm_status gm_wall_map_create(gm_ctx *ctx, const gm_wall_params *params, gm_wall_
     m->prm = *params;
     m->ncell = (uint64_t)params->n_stations * params->n_sectors;
     m->pending.assign(ctx->n_slots, 0);
+    m->checks.resize(ctx->n_slots);
     if (const char *e = getenv("GM_WALL_POINTS_PER_BLOCK")) m->points_per_block = (uint32_t)strtoul(e, nullptr, 10);
     if (const char *e = getenv("GM_WALL_REGION_TILE")) {   // <stations>x<sectors>; anything else: the default
         unsigned ts = 0, tk = 0;
@@ -384,6 +543,9 @@ gm_status gm_wall_map_add_frame(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, co
     w.labels = (ctx->cfg.flags & GM_CFG_RANSAC_PLANE) ? sl.labels : nullptr;   // (label 1 exists with the plane RANSAC only)
     w.n_ptr = &sl.ctr->n_valid;
     w.n_host = sl.n_in;
+    // a check enqueued on another slot before this add must not see it (nothing to wait for on a map without checks)
+    for (uint32_t i = 0; i < ctx->n_slots; ++i)
+        if (i != slot && map->checks[i].outstanding) GMW_HIP(ctx, hipStreamWaitEvent(sl.stream, map->checks[i].done, 0));
     launch_wall_add(w, sl.n_in, map->points_per_block, sl.stream);
     GMW_HIP(ctx, hipGetLastError());
     map->pending[slot] = 1;
@@ -422,6 +584,8 @@ gm_status gm_wall_map_add_points(gm_wall_map *map, const float *xyz, uint32_t n,
     w.n_host = n;
     w.res = residual ? map->pt_res : nullptr;
     w.cell = cell ? map->pt_cell : nullptr;
+    for (uint32_t i = 1; i < ctx->n_slots; ++i)   // (as gm_wall_map_add_frame: behind the checks outstanding on other slots)
+        if (map->checks[i].outstanding) GMW_HIP(ctx, hipStreamWaitEvent(sl.stream, map->checks[i].done, 0));
     launch_wall_add(w, n, map->points_per_block, sl.stream);
     GMW_HIP(ctx, hipGetLastError());
     if (residual && n) GMW_HIP(ctx, hipMemcpyAsync(residual, map->pt_res, (size_t)n * 4, hipMemcpyDeviceToHost, sl.stream));
@@ -836,6 +1000,154 @@ gm_status gm_wall_map_cloud(gm_wall_map *map, uint32_t station0, uint32_t n, con
     if (n_out) *n_out = total;
     if (points && total > capacity) return gm_fail(ctx, GM_ERR_CAPACITY, "gm_wall_map_cloud: point buffer too small");
     return GM_OK;
+}
+
+void gm_wall_check_default_params(gm_wall_check_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(gm_wall_check_params);
+    p->reference = GM_WALL_CHECK_MEAN;
+    p->min_count = 8;
+    p->threshold = 0.05;
+    p->gate = 1.0;
+}
+
+gm_status gm_wall_check_classify(const gm_wall_check_params *prm, const gm_wall_raw_cell *cell, float e, int64_t *delta, uint32_t *cls)
+{
+    long long T;
+    if (!prm || !cell || !delta || !cls || !check_prm_ok(*prm, T)) return GM_ERR_INVALID_ARG;
+    *delta = 0;
+    if (!(fabsf(e) <= (float)prm->gate)) {
+        *cls = GM_WALL_CHECK_CLS_BEYOND_GATE;
+        return GM_OK;
+    }
+    long long d;
+    *cls = wall_check_rule(prm->reference, prm->min_count, T, cell->sum, cell->count, cell->min_key, cell->max_key, e, d);
+    *delta = d;
+    return GM_OK;
+}
+
+gm_status gm_wall_map_check_frame(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, const double pose[12],
+                                  const gm_wall_check_params *prm, gm_wall_add_info *add_info)
+{
+    if (!map || !ctx) return GM_ERR_INVALID_ARG;
+    if (ctx != map->ctx) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_check_frame: the map belongs to another context");
+    if (slot >= ctx->n_slots) return gm_fail(ctx, GM_ERR_INVALID_ARG, "slot out of range");
+    gm_wall_check_params cp;
+    gm_wall_check_default_params(&cp);
+    if (prm) cp = *prm;
+    WallCheckArgs a;
+    memset(&a, 0, sizeof(a));
+    if (!check_prm_ok(cp, a.T))
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_check_frame: struct_size mismatch or a parameter outside its limits");
+    Slot &sl = ctx->slots[slot];
+    if (!sl.submitted) return gm_fail(ctx, GM_ERR_NOT_READY, "gm_wall_map_check_frame: the slot holds no frame");
+    gm_status st = add_frame_args(map, pose, add_info, a.w);
+    if (st != GM_OK) return st;
+    a.w.gate = (float)cp.gate;
+    if (add_info) add_info->gate = a.w.gate;
+    if (hipSetDevice(ctx->device) != hipSuccess) return gm_fail(ctx, GM_ERR_DEVICE, "hipSetDevice failed");
+    const uint32_t n_cap = sl.n_in ? sl.n_in : 1u;
+    ScanState scan;
+    st = check_prepare(map, slot, n_cap, sl.stream, scan);
+    if (st != GM_OK) return st;
+    st = check_wait_adds(map, slot, sl.stream);
+    if (st != GM_OK) return st;
+    a.w.pts = sl.valid4;
+    a.w.labels = (ctx->cfg.flags & GM_CFG_RANSAC_PLANE) ? sl.labels : nullptr;
+    a.w.n_ptr = &sl.ctr->n_valid;
+    a.w.n_host = sl.n_in;
+    a.reference = cp.reference;
+    a.min_count = cp.min_count;
+    a.out = map->checks[slot].stage;
+    a.ctr = map->checks[slot].ctr;
+    return check_enqueue(map, slot, a, n_cap, scan, sl.stream);
+}
+
+gm_status gm_wall_map_get_check(gm_wall_map *map, uint32_t slot, gm_wall_check_info *info, gm_wall_check_point *points,
+                                uint32_t capacity, uint32_t *n_out)
+{
+    if (!map) return GM_ERR_INVALID_ARG;
+    gm_ctx *ctx = map->ctx;
+    if (n_out) *n_out = 0;
+    if (slot >= ctx->n_slots) return gm_fail(ctx, GM_ERR_INVALID_ARG, "slot out of range");
+    if (!map->checks[slot].have) return gm_fail(ctx, GM_ERR_NOT_READY, "gm_wall_map_get_check: no check was enqueued on this map and slot");
+    if (hipSetDevice(ctx->device) != hipSuccess) return gm_fail(ctx, GM_ERR_DEVICE, "hipSetDevice failed");
+    return check_result(map, slot, info, points, capacity, n_out);
+}
+
+gm_status gm_wall_map_check_points(gm_wall_map *map, const float *xyz, uint32_t n, const uint8_t *labels, const double pose[12],
+                                   const gm_wall_check_params *prm, gm_wall_add_info *add_info, gm_wall_check_info *info,
+                                   gm_wall_check_point *points, uint32_t capacity, uint32_t *n_out, float *residual,
+                                   int32_t *cell, int32_t *delta, uint8_t *cls)
+{
+    if (!map) return GM_ERR_INVALID_ARG;
+    gm_ctx *ctx = map->ctx;
+    if (n_out) *n_out = 0;
+    if (n && !xyz) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_check_points: NULL xyz");
+    if (!points && capacity) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_check_points: NULL points with a capacity");
+    gm_wall_check_params cp;
+    gm_wall_check_default_params(&cp);
+    if (prm) cp = *prm;
+    WallCheckArgs a;
+    memset(&a, 0, sizeof(a));
+    if (!check_prm_ok(cp, a.T))
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_check_points: struct_size mismatch or a parameter outside its limits");
+    gm_status st = add_frame_args(map, pose, add_info, a.w);
+    if (st != GM_OK) return st;
+    a.w.gate = (float)cp.gate;
+    if (add_info) add_info->gate = a.w.gate;
+    Slot *slp;
+    st = gm_begin_stage(ctx, slp);
+    if (st != GM_OK) return st;
+    Slot &sl = *slp;
+    const uint32_t n_cap = n ? n : 1u;
+    st = gm_ensure_capacity(ctx, sl, n_cap, (size_t)n_cap * 16, true);
+    if (st != GM_OK) return st;
+    if ((residual || cell) && map->pt_cap < n) {
+        hipFree(map->pt_res); hipFree(map->pt_cell);
+        map->pt_res = nullptr; map->pt_cell = nullptr; map->pt_cap = 0;
+        GMW_HIP(ctx, hipMalloc((void **)&map->pt_res, (size_t)n * 4));
+        GMW_HIP(ctx, hipMalloc((void **)&map->pt_cell, (size_t)n * 4));
+        map->pt_cap = n;
+    }
+    if ((delta || cls) && map->ck_cap < n) {
+        hipFree(map->ck_delta); hipFree(map->ck_cls);
+        map->ck_delta = nullptr; map->ck_cls = nullptr; map->ck_cap = 0;
+        GMW_HIP(ctx, hipMalloc((void **)&map->ck_delta, (size_t)n * 4));
+        GMW_HIP(ctx, hipMalloc((void **)&map->ck_cls, (size_t)n));
+        map->ck_cap = n;
+    }
+    ScanState scan;
+    st = check_prepare(map, 0, n_cap, sl.stream, scan);
+    if (st != GM_OK) return st;
+    st = check_wait_adds(map, 0, sl.stream);
+    if (st != GM_OK) return st;
+    st = gm_upload_xyz(ctx, sl, xyz, n, sl.valid4);
+    if (st != GM_OK) return st;
+    if (labels && n) GMW_HIP(ctx, hipMemcpyAsync(sl.labels, labels, n, hipMemcpyHostToDevice, sl.stream));
+    a.w.pts = sl.valid4;
+    a.w.labels = labels ? sl.labels : nullptr;
+    a.w.n_ptr = nullptr;
+    a.w.n_host = n;
+    a.w.res = residual ? map->pt_res : nullptr;
+    a.w.cell = cell ? map->pt_cell : nullptr;
+    a.delta = delta ? map->ck_delta : nullptr;
+    a.cls = cls ? map->ck_cls : nullptr;
+    a.reference = cp.reference;
+    a.min_count = cp.min_count;
+    a.row_is_index = 1u;
+    a.out = map->checks[0].stage;
+    a.ctr = map->checks[0].ctr;
+    st = check_enqueue(map, 0, a, n_cap, scan, sl.stream);
+    if (st != GM_OK) return st;
+    if (residual && n) GMW_HIP(ctx, hipMemcpyAsync(residual, map->pt_res, (size_t)n * 4, hipMemcpyDeviceToHost, sl.stream));
+    if (cell && n) GMW_HIP(ctx, hipMemcpyAsync(cell, map->pt_cell, (size_t)n * 4, hipMemcpyDeviceToHost, sl.stream));
+    if (delta && n) GMW_HIP(ctx, hipMemcpyAsync(delta, map->ck_delta, (size_t)n * 4, hipMemcpyDeviceToHost, sl.stream));
+    if (cls && n) GMW_HIP(ctx, hipMemcpyAsync(cls, map->ck_cls, (size_t)n, hipMemcpyDeviceToHost, sl.stream));
+    GMW_HIP(ctx, hipStreamSynchronize(sl.stream));
+    return check_result(map, 0, info, points, capacity, n_out);
 }
 
 }  // extern "C"

@@ -421,6 +421,22 @@ std::vector<gm_wall_cloud_point> Processor::wallMapCloud(unsigned station0, unsi
     return points;
 }
 
+std::vector<gm_wall_check_point> Processor::checkWallMap(const double pose[12], const gm_wall_check_params &prm, gm_wall_check_info *info)
+{
+    if (!wall_) throw Error(GM_ERR_NOT_READY, "checkWallMap: createWallMap first");
+    if (newest_slot_ < 0) throw Error(GM_ERR_NOT_READY, "checkWallMap: no frame yet");
+    const unsigned slot = (unsigned)newest_slot_;
+    check(gm_wall_map_check_frame(wall_, ctx_, slot, pose, &prm, 0), "checkWallMap");
+    gm_wall_check_info local;
+    gm_wall_check_info *ip = info ? info : &local;
+    uint32_t count = 0;
+    check(gm_wall_map_get_check(wall_, slot, ip, 0, 0, &count), "checkWallMap");
+    std::vector<gm_wall_check_point> points(count);
+    if (count) check(gm_wall_map_get_check(wall_, slot, ip, &points[0], count, &count), "checkWallMap");
+    points.resize(count);
+    return points;
+}
+
 gm_wall_info Processor::wallMapInfo()
 {
     if (!wall_) throw Error(GM_ERR_NOT_READY, "wallMapInfo: createWallMap first");

@@ -150,6 +150,10 @@ public:
     // stations [station0, station0 + n) as a point list (gm_wall_map_cloud): one record per block of cells that holds
     // prm.min_count points, ascending by block; info, when given, receives the call's counts
     std::vector<gm_wall_cloud_point> wallMapCloud(unsigned station0, unsigned n, const gm_wall_cloud_params &prm, gm_wall_cloud_info *info = nullptr);
+    // the changed points of the newest frame (as addToWallMap takes it) against the map under pose (gm_wall_map_check_frame +
+    // gm_wall_map_get_check), ascending by index; the map is not changed.  info, when given, receives the call's counts.
+    // Check, then addToWallMap: against what was there, then contribute.
+    std::vector<gm_wall_check_point> checkWallMap(const double pose[12], const gm_wall_check_params &prm, gm_wall_check_info *info = nullptr);
     gm_wall_map *wallMap() { return wall_; }
 
     gm_ctx *ctx() { return ctx_; }

@@ -691,6 +691,99 @@ gm_status gm_wall_cloud_directions(const gm_wall_params *p, const gm_wall_cloud_
 gm_status gm_wall_map_cloud(gm_wall_map *map, uint32_t station0, uint32_t n, const gm_wall_cloud_params *prm,
                             gm_wall_cloud_info *info, gm_wall_cloud_point *points, uint64_t capacity, uint64_t *n_out);
 
+/* ---- a frame's changed points against the wall map (gm_wall_map_check_*) ----------------------------------------------
+ * Which points of the frame in front of the sensor are NOT where the map says the wall is: rockfall, a fallen lining
+ * segment, a vehicle in the profile, new shotcrete.  One device pass over the frame's valid cloud under a pose; only the
+ * changed points and a few counters leave the device.  The rule is integer from e on:
+ *   per check     exactly gm_wall_map_add_frame's "per add" (fp64 on the host, the anchor station, o', a', u', v' rounded
+ *                 to fp32 once, the pose checks), reported in a gm_wall_add_info -- but for the gate, which is the
+ *                 CHECK's own parameter rounded to fp32 once, not the map's: an object standing in the profile lies far
+ *                 inside the map's gate and must not vanish.
+ *   per point     the add's fp32 chain unchanged: e, the station j = j_f + floor(t / ds) in 64-bit integers, the sector k.
+ *   integers      e_q = (int64) rint(e 2^20), the very integer the add sums (fp32 product rounded to nearest even, the
+ *                 conversion saturating at the int32 range, 0 for a NaN -- never reached by a gated e);
+ *                 T = (int64) rint(threshold 2^20), fp64, once on the host, threshold in (0, 8] and T >= 1.
+ *                 A cell is USABLE iff count >= min_count.
+ *   reference     GM_WALL_CHECK_MEAN: delta = e_q - q, q = sum / (int64) count by C integer division (toward zero): the
+ *                 value of gm_wall_map_regions.  GM_WALL_CHECK_ENVELOPE: lo_q, hi_q = the same rint of the cell's min and
+ *                 max decoded from min_key / max_key; delta = e_q - hi_q if e_q > hi_q, e_q - lo_q if e_q < lo_q, else 0
+ *                 (rough rock and shotcrete have wide cells; a point inside the surveyed spread is not a change).
+ *                 |delta| <= 2^24 for a map whose cells came from points (any gate <= 8).
+ *   classes       every valid point is in exactly one: plane (label 1), beyond_gate (|e| > gate or e not finite), outside
+ *                 (j not in [0, n_stations)), unsurveyed (mapped, cell not usable), unchanged (|delta| < T), changed_pos
+ *                 (delta >= T: farther from the axis than the survey), changed_neg (delta <= -T: inside the profile).
+ *   list          the changed points, ascending by index in the valid cloud, one 32-byte gm_wall_check_point each.
+ *   peaks         the largest delta of a changed_pos point and the smallest of a changed_neg point (integer device
+ *                 maxima), 0 when there is none.
+ * The map is not changed: not its cells, not its totals, not `frames`.  Ordering: a check sees every add enqueued on any
+ * slot before it and none enqueued after it (stream events, no host block), so the result is the same bytes on every
+ * path.  Scratch per (map, slot) -- 32 B per point of staging sized by the slot's frame, the chained scan's own records,
+ * a counter block -- is allocated on first use, kept grow-only and freed with the map. */
+enum { GM_WALL_CHECK_MEAN = 0, GM_WALL_CHECK_ENVELOPE = 1 };
+enum { GM_WALL_CHECK_CLS_PLANE = 0, GM_WALL_CHECK_CLS_BEYOND_GATE = 1, GM_WALL_CHECK_CLS_OUTSIDE = 2,
+       GM_WALL_CHECK_CLS_UNSURVEYED = 3, GM_WALL_CHECK_CLS_UNCHANGED = 4, GM_WALL_CHECK_CLS_CHANGED_POS = 5,
+       GM_WALL_CHECK_CLS_CHANGED_NEG = 6, GM_WALL_CHECK_N_CLS = 7 };
+
+typedef struct gm_wall_check_params {
+    uint32_t struct_size;     /* = sizeof(gm_wall_check_params) */
+    uint32_t reference;       /* GM_WALL_CHECK_MEAN (default) or GM_WALL_CHECK_ENVELOPE */
+    uint32_t min_count;       /* >= 1 (default 8): points a cell needs to be usable */
+    uint32_t reserved;        /* 0 */
+    double   threshold;       /* metres, in (0, 8] with rint(threshold 2^20) >= 1 (default 0.05) */
+    double   gate;            /* metres, in (0, 8] (default 1.0): the check's own, not the map's */
+} gm_wall_check_params;
+
+typedef struct gm_wall_check_point {   /* 32 bytes: a PointCloud2 row, x y z FLOAT32 at 0, 4, 8 */
+    float    x, y, z;         /* the valid cloud's SENSOR coordinates */
+    float    delta;           /* (float)(delta 2^-20), metres: exact for |delta| <= 2^24 */
+    float    e;               /* the point's residual against the design cylinder */
+    int32_t  cell;            /* j * n_sectors + k */
+    uint32_t index;           /* into gm_get_cropped_xyz's order */
+    uint32_t row;             /* the valid cloud's pad word: the input row (stage call: = index) */
+} gm_wall_check_point;
+
+typedef struct gm_wall_check_info {
+    uint32_t struct_size;     /* = sizeof(gm_wall_check_info), filled by the library */
+    uint32_t status;          /* GM_SURF_OK or GM_SURF_UP_FALLBACK: the design frame's */
+    int64_t  threshold_q;     /* T */
+    uint32_t n_points;        /* the valid cloud's points = the sum of the seven classes below */
+    uint32_t plane, beyond_gate, outside, unsurveyed, unchanged, changed_pos, changed_neg;
+    int64_t  peak_pos, peak_neg;   /* 2^-20 m; 0 when the class is empty */
+} gm_wall_check_info;
+
+/* Host only: the defaults of the table above.  A NULL is ignored. */
+void gm_wall_check_default_params(gm_wall_check_params *p);
+/* Host only, no device, no map: the integer rule applied to one (cell, e) pair, so that a host can restate a row.  It
+ * returns, in *cls, GM_WALL_CHECK_CLS_BEYOND_GATE, _UNSURVEYED, _UNCHANGED, _CHANGED_POS or _CHANGED_NEG; plane and
+ * outside are not decidable from its inputs (the label and the station are not among them).  *delta is 0 for beyond_gate
+ * and unsurveyed.  GM_ERR_INVALID_ARG: a NULL, a struct_size mismatch or a parameter outside its limits. */
+gm_status gm_wall_check_classify(const gm_wall_check_params *prm, const gm_wall_raw_cell *cell, float e, int64_t *delta,
+                                 uint32_t *cls);
+/* Checks the valid cloud of the frame last submitted to `slot` of ctx against the map.  Enqueued on the slot's stream
+ * behind the frame's work; returns without waiting.  It reads the point count and the slot's final labels on the device,
+ * as the add does; with GM_CFG_GRAPH it is a plain launch after the graph.  Arguments and readiness as for
+ * gm_wall_map_add_frame (prm NULL: the defaults; a parameter outside its limits is GM_ERR_INVALID_ARG).  Check followed
+ * by add on the same slot is the normal use: check against what was there, then contribute.  add_info may be NULL; its
+ * gate is the check's. */
+gm_status gm_wall_map_check_frame(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, const double pose[12],
+                                  const gm_wall_check_params *prm, gm_wall_add_info *add_info);
+/* The result of the last check enqueued on (map, slot).  Waits for that check only (an event recorded behind it, not the
+ * slot's stream), then fills info and *n_out (the number of changed points; either may be NULL).  points NULL with
+ * capacity 0 is a count query; fewer than *n_out rows of capacity returns GM_ERR_CAPACITY and writes no row.
+ * GM_ERR_NOT_READY: no check was enqueued on (map, slot).  The result stays readable until the next check on that
+ * (map, slot) -- gm_wall_map_check_points counts as one on slot 0 -- or until the map is destroyed. */
+gm_status gm_wall_map_get_check(gm_wall_map *map, uint32_t slot, gm_wall_check_info *info, gm_wall_check_point *points,
+                                uint32_t capacity, uint32_t *n_out);
+/* The same kernel as one blocking stage call on host buffers (slot 0 of the map's context; gm_wall_map_add_points'
+ * conventions).  info, points / capacity / n_out as gm_wall_map_get_check.  The per-point outputs may each be NULL:
+ * residual (float[n]: e, NaN for plane points), cell (int32_t[n]: j * n_sectors + k for the four mapped classes, else
+ * -1), delta (int32_t[n], saturated; 0 for the classes that have none), cls (uint8_t[n]: GM_WALL_CHECK_CLS_*).
+ * row = index.  Fed a slot's valid cloud and labels, it returns that slot's check bit for bit. */
+gm_status gm_wall_map_check_points(gm_wall_map *map, const float *xyz, uint32_t n, const uint8_t *labels, const double pose[12],
+                                   const gm_wall_check_params *prm, gm_wall_add_info *add_info, gm_wall_check_info *info,
+                                   gm_wall_check_point *points, uint32_t capacity, uint32_t *n_out, float *residual,
+                                   int32_t *cell, int32_t *delta, uint8_t *cls);
+
 /* "Compressed map" record of a completed slot.  The reference defines no such
  * output; this is a build-defined format: header, primitive records,
  * then n_voxels rows of x,y,z,count (float32).  Returns the bytes needed in
