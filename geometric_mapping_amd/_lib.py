@@ -63,6 +63,9 @@ GM_WALL_MAX_CELLS = 1 << 24
 GM_WALL_MAX_SECTORS = 4096
 GM_WALL_REGION_TILE = (64, 64)   # stations x sectors: the labelling kernel's default tile
 
+GM_WALL_OBJECT_MAX_BLOCKS = 1 << 20
+GM_WALL_OBJECT_TILE = (64, 64)   # block rows x block columns: the object labelling kernel's default tile
+
 GM_WALL_CHECK_MEAN, GM_WALL_CHECK_ENVELOPE = 0, 1
 (GM_WALL_CHECK_CLS_PLANE, GM_WALL_CHECK_CLS_BEYOND_GATE, GM_WALL_CHECK_CLS_OUTSIDE, GM_WALL_CHECK_CLS_UNSURVEYED,
  GM_WALL_CHECK_CLS_UNCHANGED, GM_WALL_CHECK_CLS_CHANGED_POS, GM_WALL_CHECK_CLS_CHANGED_NEG) = range(7)
@@ -201,6 +204,35 @@ class WallCheckInfo(C.Structure):
                 ("peak_pos", C.c_int64), ("peak_neg", C.c_int64)]
 
 
+class WallObject(C.Structure):
+    _fields_ = [("label", C.c_uint32), ("sign", C.c_int32), ("blocks", C.c_uint32), ("peak_index", C.c_uint32),
+                ("station_min", C.c_uint32), ("station_max", C.c_uint32), ("sector_min", C.c_uint32), ("sector_max", C.c_uint32),
+                ("sector_min_turned", C.c_uint32), ("sector_max_turned", C.c_uint32), ("points", C.c_uint64),
+                ("peak", C.c_int64), ("sum_delta", C.c_int64), ("sum_x", C.c_int64), ("sum_y", C.c_int64), ("sum_z", C.c_int64),
+                ("box_min", C.c_float * 3), ("box_max", C.c_float * 3), ("e_min", C.c_float), ("e_max", C.c_float),
+                ("reserved", C.c_uint64)]
+
+
+class WallObjectParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("block_stations", C.c_uint32), ("block_sectors", C.c_uint32),
+                ("min_block_points", C.c_uint32), ("min_points", C.c_uint32), ("connectivity", C.c_uint32),
+                ("half_window_stations", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class WallObjectsInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_rows", C.c_uint32), ("station0", C.c_uint32), ("n_stations", C.c_uint32),
+                ("blocks_stations", C.c_uint32), ("blocks_sectors", C.c_uint32), ("rejected", C.c_uint32),
+                ("outside_window", C.c_uint32), ("sparse", C.c_uint32), ("small", C.c_uint32), ("in_object", C.c_uint32),
+                ("flagged_pos", C.c_uint32), ("flagged_neg", C.c_uint32), ("components", C.c_uint32), ("objects", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class WallObjectMetrics(C.Structure):
+    _fields_ = [("centroid", C.c_double * 3), ("mean_m", C.c_double), ("peak_m", C.c_double), ("size", C.c_double * 3),
+                ("chainage_from", C.c_double), ("chainage_to", C.c_double), ("angle_from_deg", C.c_double),
+                ("angle_to_deg", C.c_double)]
+
+
 class GmError(RuntimeError):
     def __init__(self, status, message):
         super().__init__(f"libgm_hip: status {status}: {message}")
@@ -266,6 +298,8 @@ def load():
                                       C.POINTER(WallRegionMetrics))
     wcprmp, wcptp, wcinfop = C.POINTER(WallCloudParams), C.POINTER(WallCloudPoint), C.POINTER(WallCloudInfo)
     wkprmp, wkptp, wkinfop = C.POINTER(WallCheckParams), C.POINTER(WallCheckPoint), C.POINTER(WallCheckInfo)
+    woprmp, wobjp, woinfop, wometp = (C.POINTER(WallObjectParams), C.POINTER(WallObject), C.POINTER(WallObjectsInfo),
+                                      C.POINTER(WallObjectMetrics))
     proto = {
         "gm_create": (C.c_int, [cfgp, C.POINTER(vp)]),
         "gm_destroy": (None, [vp]),
@@ -333,6 +367,10 @@ def load():
         "gm_wall_map_check_frame": (C.c_int, [vp, vp, u32, dp, wkprmp, waddp]),
         "gm_wall_map_get_check": (C.c_int, [vp, u32, wkinfop, wkptp, u32, u32p]),
         "gm_wall_map_check_points": (C.c_int, [vp, fp, u32, u8p, dp, wkprmp, waddp, wkinfop, wkptp, u32, u32p, fp, i32p, i32p, u8p]),
+        "gm_wall_object_default_params": (None, [woprmp]),
+        "gm_wall_map_check_objects": (C.c_int, [vp, u32, woprmp, woinfop, wobjp, u32, u32p, i32p, u32]),
+        "gm_wall_check_objects": (C.c_int, [vp, wkptp, u32, C.c_int64, woprmp, woinfop, wobjp, u32, u32p, i32p]),
+        "gm_wall_object_metrics": (C.c_int, [wprmp, woprmp, wobjp, wometp]),
         "gm_group_create": (C.c_int, [cfgp, i32p, u32, u32, C.POINTER(vp)]),
         "gm_group_destroy": (None, [vp]),
         "gm_group_size": (u32, [vp]),

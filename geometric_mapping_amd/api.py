@@ -510,6 +510,13 @@ WALL_CHECK_POINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("delta",
                              ("index", "<u4"), ("row", "<u4")])   # gm_wall_check_point, 32 bytes
 _CHECK_INFO = ("status", "threshold_q", "n_points", "plane", "beyond_gate", "outside", "unsurveyed", "unchanged",
                "changed_pos", "changed_neg", "peak_pos", "peak_neg")
+WALL_OBJECT = np.dtype([("label", "<u4"), ("sign", "<i4"), ("blocks", "<u4"), ("peak_index", "<u4"), ("station_min", "<u4"),
+                        ("station_max", "<u4"), ("sector_min", "<u4"), ("sector_max", "<u4"), ("sector_min_turned", "<u4"),
+                        ("sector_max_turned", "<u4"), ("points", "<u8"), ("peak", "<i8"), ("sum_delta", "<i8"), ("sum_x", "<i8"),
+                        ("sum_y", "<i8"), ("sum_z", "<i8"), ("box_min", "<f4", (3,)), ("box_max", "<f4", (3,)), ("e_min", "<f4"),
+                        ("e_max", "<f4"), ("reserved", "<u8")])   # gm_wall_object, 128 bytes
+_OBJECTS_INFO = ("n_rows", "station0", "n_stations", "blocks_stations", "blocks_sectors", "rejected", "outside_window", "sparse",
+                 "small", "in_object", "flagged_pos", "flagged_neg", "components", "objects")
 
 
 def _wall_check_params(**kw):
@@ -533,6 +540,31 @@ def wall_check_classify(raw_cell, e, **params):
     if st != _lib.GM_OK:
         raise _lib.GmError(st, "gm_wall_check_classify refused the parameters")
     return int(d.value), int(c.value)
+
+
+def _wall_object_params(**kw):
+    p = _lib.WallObjectParams()
+    _lib.load().gm_wall_object_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k in ("struct_size", "reserved"):
+            raise TypeError(f"unknown object parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def object_metrics(prm, obj, **params):
+    """gm_wall_object_metrics (host only): the fp64 metrics dict (centroid and size as float64 [3]) of one WALL_OBJECT
+    record under the gm_wall_params `prm` and the object parameters given as keywords."""
+    r = np.ascontiguousarray(np.asarray(obj, dtype=WALL_OBJECT).reshape(1))
+    op = _wall_object_params(**params)
+    out = _lib.WallObjectMetrics()
+    st = _lib.load().gm_wall_object_metrics(C.byref(prm), C.byref(op), r.ctypes.data_as(C.POINTER(_lib.WallObject)), C.byref(out))
+    if st != _lib.GM_OK:
+        raise _lib.GmError(st, "gm_wall_object_metrics refused the record")
+    d = {k: float(getattr(out, k)) for k, _t in _lib.WallObjectMetrics._fields_ if k not in ("centroid", "size")}
+    d["centroid"] = np.array(out.centroid[:], dtype=np.float64)
+    d["size"] = np.array(out.size[:], dtype=np.float64)
+    return d
 
 
 def wall_region_metrics(prm, region):
@@ -827,6 +859,62 @@ class WallMap:
         d = self._check_info(info)
         d["add"] = self._add_info(add)
         return d, pts[:int(got.value)].copy(), ({k: v[:n].copy() for k, v in out.items()} if outputs else None)
+
+    @staticmethod
+    def object_params(**kw):
+        """gm_wall_object_params with the library's defaults, then the keywords (block_stations, block_sectors,
+        min_block_points, min_points, connectivity, half_window_stations)."""
+        return _wall_object_params(**kw)
+
+    def _objects(self, call, n_rows, rows, p):
+        """A count query, then the sized call; call(info, objects, capacity, got, object_of_row) is the bound ABI call.
+        Each of the two runs the whole device pipeline (the library keeps no result between calls), so this binding
+        launches every kernel twice per request; a caller that minds sizes the record buffer itself and calls the ABI
+        once, as tools/wall_objects_timing.py does."""
+        info = _lib.WallObjectsInfo()
+        got = C.c_uint32(0)
+        self._ctx._check(call(C.byref(info), None, 0, C.byref(got), None))
+        cap = int(got.value)
+        obj = np.zeros(max(cap, 1), dtype=WALL_OBJECT)
+        of_row = np.full(max(n_rows, 1), -1, dtype=np.int32) if rows else None
+        if cap or rows:
+            self._ctx._check(call(C.byref(info), obj.ctypes.data_as(C.POINTER(_lib.WallObject)), cap, C.byref(got),
+                                  of_row.ctypes.data_as(C.POINTER(C.c_int32)) if rows else None))
+        obj = obj[:int(got.value)].copy()
+        d = {k: int(getattr(info, k)) for k in _OBJECTS_INFO}
+        metrics = [object_metrics(self.prm, obj[i], **p) for i in range(len(obj))]
+        return d, obj, metrics, (of_row[:n_rows].copy() if rows else None)
+
+    def check_objects(self, slot=0, rows=False, **params):
+        """gm_wall_map_check_objects: the changed points of the last check on the slot grouped into objects on the device.
+        Returns (info dict, WALL_OBJECT records ascending by (label, sign), metrics list of dicts, object_of_row int32 per
+        changed row in check_result()'s order or None without rows).  Two device passes (see _objects); rows=True costs one
+        further gm_wall_map_get_check count query for the row count."""
+        p = self.object_params(**params)
+        n_rows = 0
+        if rows:
+            got = C.c_uint32(0)
+            self._ctx._check(self._L.gm_wall_map_get_check(self._h(), slot, None, None, 0, C.byref(got)))
+            n_rows = int(got.value)
+
+        def call(info, obj, cap, got, of_row):
+            return self._L.gm_wall_map_check_objects(self._h(), slot, C.byref(p), info, obj, cap, got, of_row, n_rows if of_row else 0)
+        return self._objects(call, n_rows, rows, params)
+
+    def objects_of_rows(self, rows, anchor_station, **params):
+        """gm_wall_check_objects: the same kernels on host rows (WALL_CHECK_POINT records in any order) around the anchor
+        station.  Returns (info dict, WALL_OBJECT records, metrics list, object_of_row int32 [len(rows)])."""
+        p = self.object_params(**params)
+        r = np.ascontiguousarray(rows, dtype=WALL_CHECK_POINT).reshape(-1)
+        rp = r.ctypes.data_as(C.POINTER(_lib.WallCheckPoint)) if len(r) else None
+
+        def call(info, obj, cap, got, of_row):
+            return self._L.gm_wall_check_objects(self._h(), rp, len(r), int(anchor_station), C.byref(p), info, obj, cap, got, of_row)
+        return self._objects(call, len(r), True, params)
+
+    def object_metrics(self, obj, **params):
+        """gm_wall_object_metrics of one WALL_OBJECT record under this map's parameters."""
+        return object_metrics(self.prm, obj, **params)
 
     def save(self, path):
         """The parameters and the raw cells as one .npz (numpy only)."""

@@ -424,6 +424,65 @@ __host__ __device__ inline uint32_t wall_check_rule(uint32_t reference, uint32_t
     }
     return delta >= T ? GM_WALL_CHECK_CLS_CHANGED_POS : (delta <= -T ? GM_WALL_CHECK_CLS_CHANGED_NEG : GM_WALL_CHECK_CLS_UNCHANGED);
 }
+// k_wall_objects.hip (gm_wall_map_check_objects, gm_wall_check_objects): bin -> tiles -> seams -> flatten | blocks ->
+// reduce -> select | rows
+constexpr uint32_t kWallObjectTileBlocks = 4096;      // the most window blocks of a tile (its LDS tables)
+// (two index spaces that never meet: kWallObjectNone is a value of parent[], kWallObjectRejected / kWallObjectOutside are
+// values of a row's decoded block index; both are above every real index, 2 NB <= 2^21)
+constexpr uint32_t kWallObjectNone = 0xFFFFFFFFu;     // parent of a (block, sign) that is not flagged
+constexpr uint32_t kWallObjectRejected = 0xFFFFFFFFu, kWallObjectOutside = 0xFFFFFFFEu;   // a row without a window block
+// u64 words 0 .. 8: rejected, outside_window, sparse, small, in_object, flagged_neg, flagged_pos, components, objects;
+// words 9 .. 15 unused: the block is 128 bytes so that its zero-fill and its copy are whole multiples of 16 bytes
+constexpr int kWallObjectCounters = 16;
+struct WallObjectAcc {   // 128 B, zero = empty: minima are kept inverted so that every extent is an integer maximum
+    uint32_t label, blocks;
+    uint32_t st_min_inv, st_max, k_min_inv, k_max, t_min_inv, t_max;
+    unsigned long long points, peak_key, sum_delta, sum_x, sum_y, sum_z;   // peak_key = min(|dq|, 2^32 - 1) << 32 | ~index
+    uint32_t box_min_inv[3], box_max[3], e_min_inv, e_max;                 // ordered() keys
+    uint32_t plane, pad0;                                                  // 0 the negative rows', 1 the positive rows'
+    unsigned long long pad1;
+};
+struct WallObjectArgs {
+    const gm_wall_check_point *rows;   // device rows, 32-byte aligned
+    uint32_t n_rows;
+    uint32_t nsec, cells;      // the map's sectors and cells
+    uint32_t bs, bk, NK;       // the block, blocks per block row
+    uint32_t J0, nJ, NB;       // the window: block rows [J0, J0 + nJ), NB = nJ * NK window blocks
+    uint32_t ts, tk, tiles_s, tiles_k;   // the tile (in blocks) and the tiles of the window
+    uint32_t conn8, min_block_points, min_points;
+    uint32_t *cnt, *parent, *slot;       // [2 NB]: plane p's block w at p * NB + w; parents index the same space
+    unsigned long long *ctr;   // [kWallObjectCounters]
+    WallObjectAcc *acc;        // [components]
+    gm_wall_object *out;       // [components]: the objects, in the order select took them
+    uint32_t *out_slot;        // [components]: the slot of each of them
+    const int32_t *pos;        // [components]: slot -> position in the sorted list, -1 for a small component
+    uint32_t ncomp;
+    int32_t *object_of_row;    // [n_rows]
+};
+void launch_wall_object_label(const WallObjectArgs &a, hipStream_t s);    // four launches, up to the component count
+void launch_wall_object_reduce(const WallObjectArgs &a, hipStream_t s);   // three launches, up to the object list
+void launch_wall_object_rows(const WallObjectArgs &a, hipStream_t s);     // object_of_row
+// the rule's per-row pieces, shared by the kernels and the host
+__host__ __device__ inline long long wall_object_fix16(float x)   // (int64) rint(x 2^16), saturating at int32, 0 for a NaN
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (long long)__float2int_rn(__fmul_rn(x, 65536.0f));
+#else
+    const volatile float p = x * 65536.0f;
+    if (p != p) return 0;
+    if (p >= 2147483648.0f) return 2147483647ll;
+    if (p <= -2147483648.0f) return -2147483647ll - 1;
+    return (long long)__builtin_rintf(p);
+#endif
+}
+// xb .. eb: the bits of x, y, z, e; dq = wall_check_fix(delta)
+__host__ __device__ inline bool wall_object_rejected(uint32_t xb, uint32_t yb, uint32_t zb, uint32_t eb, int32_t cell, long long dq,
+                                                     uint32_t cells)
+{
+    const uint32_t inf = 0x7F800000u;
+    return cell < 0 || (uint32_t)cell >= cells || dq == 0 || (xb & inf) == inf || (yb & inf) == inf || (zb & inf) == inf ||
+           (eb & inf) == inf;
+}
 
 // k_nearest.hip
 void launch_nearest(const float4 *pts, const uint32_t *n_ptr, uint32_t n_cap, const float4 *queries,

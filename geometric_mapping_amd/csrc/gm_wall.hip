@@ -27,6 +27,7 @@ struct WallCheckSlot {
     bool outstanding = false;               // the host has not waited for `done` yet
     uint32_t status = 0;
     long long T = 0;
+    int64_t anchor = 0;                     // the check's j_f (gm_wall_map_check_objects anchors its window on it)
 };
 
 struct gm_wall_map {
@@ -71,6 +72,21 @@ struct gm_wall_map {
     int32_t *ck_delta = nullptr;               // gm_wall_map_check_points' per-point outputs beside pt_res / pt_cell (grow-only)
     uint8_t *ck_cls = nullptr;
     uint32_t ck_cap = 0;
+    // gm_wall_map_check_objects / gm_wall_check_objects: the tile in blocks (GM_WALL_OBJECT_TILE: tests, measurements) and
+    // the scratch, allocated on first use, grow-only
+    uint32_t object_tr = GM_WALL_OBJECT_TILE_ROWS, object_tc = GM_WALL_OBJECT_TILE_COLS;
+    uint32_t *ob_blocks = nullptr;           // per window block and plane: cnt u32 [cap] | parent u32 [cap] | slot u32 [cap]
+    uint64_t ob_blocks_cap = 0;              //   (cap counts (block, plane) pairs)
+    unsigned long long *ob_ctr = nullptr;    // [kWallObjectCounters]
+    uint8_t *ob_recs = nullptr;              // per component: WallObjectAcc | gm_wall_object | out_slot u32 | pos i32, [cap] each
+    uint64_t ob_recs_cap = 0;
+    gm_wall_check_point *ob_rows = nullptr;  // the stage call's rows
+    uint32_t ob_rows_cap = 0;
+    int32_t *ob_of_row = nullptr;            // object_of_row
+    uint32_t ob_of_row_cap = 0;
+    std::vector<gm_wall_object> ob_host;     // the unsorted list, its slots, the sorting permutation, slot -> position
+    std::vector<uint32_t> ob_host_slot, ob_order;
+    std::vector<int32_t> ob_pos;
 };
 
 namespace {
@@ -264,6 +280,7 @@ void free_map(gm_wall_map *m)
     if (m->stream) { hipStreamSynchronize(m->stream); hipStreamDestroy(m->stream); }
     hipFree(m->base); hipFree(m->stage); hipFree(m->pt_res); hipFree(m->pt_cell);
     hipFree(m->rg_cells); hipFree(m->rg_ctr); hipFree(m->rg_recs);
+    hipFree(m->ob_blocks); hipFree(m->ob_ctr); hipFree(m->ob_recs); hipFree(m->ob_rows); hipFree(m->ob_of_row);
     hipFree(m->cl_acc); hipFree(m->cl_stage); hipFree(m->cl_rec); hipFree(m->cl_ctr); hipFree(m->cl_dirs);
     delete m;
 }
@@ -403,6 +420,7 @@ gm_status check_enqueue(gm_wall_map *m, uint32_t slot, const WallCheckArgs &a, u
     c.outstanding = true;
     c.status = m->status;
     c.T = a.T;
+    c.anchor = a.w.anchor;
     return GM_OK;
 }
 
@@ -442,6 +460,156 @@ gm_status check_result(gm_wall_map *m, uint32_t slot, gm_wall_check_info *info, 
         GMW_HIP(ctx, hipMemcpyAsync(points, c.stage, (size_t)got * sizeof(gm_wall_check_point), hipMemcpyDeviceToHost, m->stream));
         GMW_HIP(ctx, hipStreamSynchronize(m->stream));
     }
+    return GM_OK;
+}
+
+// ---- gm_wall_map_check_objects / gm_wall_check_objects ----
+
+bool object_prm_ok(const gm_wall_object_params &p)
+{
+    return p.struct_size == sizeof(gm_wall_object_params) && p.block_stations >= 1u && p.block_sectors >= 1u &&
+           p.min_block_points >= 1u && p.min_points >= 1u && (p.connectivity == 4u || p.connectivity == 8u) &&
+           p.half_window_stations >= 1u && p.half_window_stations <= (1u << 20);
+}
+
+struct ObjectWindow {
+    uint32_t J0 = 0, nJ = 0, NK = 0;         // block rows [J0, J0 + nJ) (nJ 0: empty), blocks per block row
+    uint32_t station0 = 0, n_stations = 0;   // the block rows' stations, clipped to the map
+};
+// the window of include/gm_hip.h around the anchor j_f; false: more than GM_WALL_OBJECT_MAX_BLOCKS blocks
+bool object_window(const gm_wall_params &p, const gm_wall_object_params &op, int64_t jf, ObjectWindow &w)
+{
+    const int64_t H = op.half_window_stations, ns = p.n_stations;   // (compared before added: j_f is any int64)
+    const int64_t lo = jf > H ? jf - H : 0, hi = jf >= ns - H ? ns : jf + H;
+    w = ObjectWindow();
+    w.NK = (p.n_sectors + op.block_sectors - 1u) / op.block_sectors;
+    if (lo >= hi) return true;
+    const uint64_t bs = op.block_stations, J0 = (uint64_t)lo / bs, J1 = (uint64_t)(hi - 1) / bs;
+    w.J0 = (uint32_t)J0;
+    w.nJ = (uint32_t)(J1 - J0 + 1u);
+    w.station0 = (uint32_t)(J0 * bs);
+    w.n_stations = (uint32_t)(std::min<uint64_t>((J1 + 1u) * bs, (uint64_t)ns) - J0 * bs);
+    return (uint64_t)w.nJ * w.NK <= GM_WALL_OBJECT_MAX_BLOCKS;
+}
+
+// The call on n_rows device rows (32-byte aligned), on the map's stream, blocking.  rejected_if_empty: the rejected rows,
+// used when nothing is launched (zero rows or an empty window).  objects / object_of_row may be NULL; the capacities were
+// checked by the caller but for the record count.
+gm_status objects_run(gm_wall_map *m, const gm_wall_check_point *d_rows, uint32_t n_rows, uint32_t rejected_if_empty,
+                      const gm_wall_object_params &op, const ObjectWindow &win, gm_wall_objects_info *info, gm_wall_object *objects,
+                      uint32_t capacity, uint32_t *n_out, int32_t *object_of_row, const char *who)
+{
+    gm_ctx *ctx = m->ctx;
+    memset(info, 0, sizeof(*info));
+    info->struct_size = (uint32_t)sizeof(gm_wall_objects_info);
+    info->n_rows = n_rows;
+    info->station0 = win.station0;
+    info->n_stations = win.n_stations;
+    info->blocks_stations = win.nJ;
+    info->blocks_sectors = win.NK;
+    if (!n_rows || !win.nJ) {   // nothing to launch
+        info->rejected = rejected_if_empty;
+        info->outside_window = n_rows - rejected_if_empty;
+        if (object_of_row) std::fill(object_of_row, object_of_row + n_rows, -1);
+        return GM_OK;
+    }
+    const uint64_t NB = (uint64_t)win.nJ * win.NK, pairs = 2u * NB;
+    if (m->ob_blocks_cap < pairs) {
+        hipFree(m->ob_blocks);
+        m->ob_blocks = nullptr; m->ob_blocks_cap = 0;
+        GMW_HIP(ctx, hipMalloc((void **)&m->ob_blocks, pairs * 12));
+        m->ob_blocks_cap = pairs;
+    }
+    if (!m->ob_ctr) GMW_HIP(ctx, hipMalloc((void **)&m->ob_ctr, kWallObjectCounters * 8));
+    if (object_of_row && m->ob_of_row_cap < n_rows) {
+        hipFree(m->ob_of_row);
+        m->ob_of_row = nullptr; m->ob_of_row_cap = 0;
+        GMW_HIP(ctx, hipMalloc((void **)&m->ob_of_row, (size_t)n_rows * 4));
+        m->ob_of_row_cap = n_rows;
+    }
+    WallObjectArgs a;
+    memset(&a, 0, sizeof(a));
+    a.rows = d_rows;
+    a.n_rows = n_rows;
+    a.nsec = m->prm.n_sectors;
+    a.cells = (uint32_t)m->ncell;   // <= GM_WALL_MAX_CELLS
+    a.bs = op.block_stations; a.bk = op.block_sectors; a.NK = win.NK;
+    a.J0 = win.J0; a.nJ = win.nJ; a.NB = (uint32_t)NB;
+    a.ts = m->object_tr; a.tk = m->object_tc;
+    a.tiles_s = (a.nJ + a.ts - 1u) / a.ts;
+    a.tiles_k = (a.NK + a.tk - 1u) / a.tk;
+    a.conn8 = op.connectivity == 8u ? 1u : 0u;
+    a.min_block_points = op.min_block_points;
+    a.min_points = op.min_points;
+    a.cnt = m->ob_blocks;
+    a.parent = a.cnt + m->ob_blocks_cap;
+    a.slot = a.parent + m->ob_blocks_cap;
+    a.ctr = m->ob_ctr;
+    a.object_of_row = m->ob_of_row;
+    unsigned long long ctr[kWallObjectCounters];
+    GMW_HIP(ctx, hipMemsetAsync(a.cnt, 0, pairs * 4, m->stream));
+    GMW_HIP(ctx, hipMemsetAsync(m->ob_ctr, 0, kWallObjectCounters * 8, m->stream));
+    launch_wall_object_label(a, m->stream);
+    GMW_HIP(ctx, hipGetLastError());
+    GMW_HIP(ctx, hipMemcpyAsync(ctr, m->ob_ctr, sizeof(ctr), hipMemcpyDeviceToHost, m->stream));
+    GMW_HIP(ctx, hipStreamSynchronize(m->stream));   // the one count the host needs: it sizes the records
+    const uint64_t ncomp = ctr[7];
+    if (ncomp) {
+        if (m->ob_recs_cap < ncomp) {
+            hipFree(m->ob_recs);
+            m->ob_recs = nullptr; m->ob_recs_cap = 0;
+            GMW_HIP(ctx, hipMalloc((void **)&m->ob_recs, ncomp * (sizeof(WallObjectAcc) + sizeof(gm_wall_object) + 8)));
+            m->ob_recs_cap = ncomp;
+        }
+        a.acc = reinterpret_cast<WallObjectAcc *>(m->ob_recs);
+        a.out = reinterpret_cast<gm_wall_object *>(m->ob_recs + m->ob_recs_cap * sizeof(WallObjectAcc));
+        a.out_slot = reinterpret_cast<uint32_t *>(m->ob_recs + m->ob_recs_cap * (sizeof(WallObjectAcc) + sizeof(gm_wall_object)));
+        int32_t *pos = reinterpret_cast<int32_t *>(a.out_slot + m->ob_recs_cap);
+        a.pos = pos;
+        a.ncomp = (uint32_t)ncomp;
+        GMW_HIP(ctx, hipMemsetAsync(a.acc, 0, ncomp * sizeof(WallObjectAcc), m->stream));
+        launch_wall_object_reduce(a, m->stream);
+        GMW_HIP(ctx, hipGetLastError());
+        GMW_HIP(ctx, hipMemcpyAsync(ctr, m->ob_ctr, sizeof(ctr), hipMemcpyDeviceToHost, m->stream));
+        GMW_HIP(ctx, hipStreamSynchronize(m->stream));
+    }
+    const uint32_t nobj = (uint32_t)ctr[8];
+    info->rejected = (uint32_t)ctr[0]; info->outside_window = (uint32_t)ctr[1]; info->sparse = (uint32_t)ctr[2];
+    info->small = (uint32_t)ctr[3]; info->in_object = (uint32_t)ctr[4];
+    info->flagged_neg = (uint32_t)ctr[5]; info->flagged_pos = (uint32_t)ctr[6];
+    info->components = (uint32_t)ncomp;
+    info->objects = nobj;
+    if (n_out) *n_out = nobj;
+    const bool fits = nobj <= capacity;
+    if (nobj && ((objects && fits) || object_of_row)) {   // the list in (label, sign) order
+        m->ob_host.resize(nobj);
+        m->ob_host_slot.resize(nobj);
+        m->ob_order.resize(nobj);
+        GMW_HIP(ctx, hipMemcpyAsync(m->ob_host.data(), a.out, (size_t)nobj * sizeof(gm_wall_object), hipMemcpyDeviceToHost, m->stream));
+        GMW_HIP(ctx, hipMemcpyAsync(m->ob_host_slot.data(), a.out_slot, (size_t)nobj * 4, hipMemcpyDeviceToHost, m->stream));
+        GMW_HIP(ctx, hipStreamSynchronize(m->stream));
+        for (uint32_t i = 0; i < nobj; ++i) m->ob_order[i] = i;
+        const std::vector<gm_wall_object> &h = m->ob_host;
+        std::sort(m->ob_order.begin(), m->ob_order.end(), [&h](uint32_t x, uint32_t y) {
+            return h[x].label != h[y].label ? h[x].label < h[y].label : h[x].sign < h[y].sign;
+        });
+        if (objects && fits)
+            for (uint32_t i = 0; i < nobj; ++i) objects[i] = h[m->ob_order[i]];
+    }
+    if (object_of_row) {
+        if (ncomp) {
+            m->ob_pos.assign((size_t)ncomp, -1);
+            for (uint32_t i = 0; i < nobj; ++i) m->ob_pos[m->ob_host_slot[m->ob_order[i]]] = (int32_t)i;
+            GMW_HIP(ctx, hipMemcpyAsync(const_cast<int32_t *>(a.pos), m->ob_pos.data(), (size_t)ncomp * 4, hipMemcpyHostToDevice, m->stream));
+            launch_wall_object_rows(a, m->stream);
+            GMW_HIP(ctx, hipGetLastError());
+            GMW_HIP(ctx, hipMemcpyAsync(object_of_row, m->ob_of_row, (size_t)n_rows * 4, hipMemcpyDeviceToHost, m->stream));
+            GMW_HIP(ctx, hipStreamSynchronize(m->stream));
+        } else {
+            std::fill(object_of_row, object_of_row + n_rows, -1);
+        }
+    }
+    if (!fits && (objects || capacity)) return gm_fail(ctx, GM_ERR_CAPACITY, who);
     return GM_OK;
 }
 
@@ -493,6 +661,13 @@ gm_status gm_wall_map_create(gm_ctx *ctx, const gm_wall_params *params, gm_wall_
         if (sscanf(e, "%ux%u", &ts, &tk) == 2 && ts >= 1u && tk >= 1u && (uint64_t)ts * tk <= kWallRegionTileCells) {
             m->region_ts = ts;
             m->region_tk = tk;
+        }
+    }
+    if (const char *e = getenv("GM_WALL_OBJECT_TILE")) {   // <block rows>x<block columns>; anything else: the default
+        unsigned tr = 0, tc = 0;
+        if (sscanf(e, "%ux%u", &tr, &tc) == 2 && tr >= 1u && tc >= 1u && (uint64_t)tr * tc <= kWallObjectTileBlocks) {
+            m->object_tr = tr;
+            m->object_tc = tc;
         }
     }
     if (const char *e = getenv("GM_WALL_CLOUD_CHUNK")) {   // blocks; 0 or more than the default: the default (scratch is sized by it)
@@ -1148,6 +1323,131 @@ gm_status gm_wall_map_check_points(gm_wall_map *map, const float *xyz, uint32_t 
     if (cls && n) GMW_HIP(ctx, hipMemcpyAsync(cls, map->ck_cls, (size_t)n, hipMemcpyDeviceToHost, sl.stream));
     GMW_HIP(ctx, hipStreamSynchronize(sl.stream));
     return check_result(map, 0, info, points, capacity, n_out);
+}
+
+void gm_wall_object_default_params(gm_wall_object_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(gm_wall_object_params);
+    p->block_stations = 1;
+    p->block_sectors = 1;
+    p->min_block_points = 2;
+    p->min_points = 8;
+    p->connectivity = 8;
+    p->half_window_stations = 128;
+}
+
+gm_status gm_wall_object_metrics(const gm_wall_params *p, const gm_wall_object_params *op, const gm_wall_object *o,
+                                 struct gm_wall_object_metrics *out)
+{
+    if (!p || !o || !out || p->struct_size != sizeof(gm_wall_params) || p->n_sectors < 1u || o->points < 1u) return GM_ERR_INVALID_ARG;
+    if (op && op->struct_size != sizeof(gm_wall_object_params)) return GM_ERR_INVALID_ARG;
+    const uint32_t ns = p->n_sectors, half = ns / 2u;
+    if (o->sector_min > o->sector_max || o->sector_max >= ns || o->sector_min_turned > o->sector_max_turned ||
+        o->sector_max_turned >= ns || o->station_min > o->station_max)
+        return GM_ERR_INVALID_ARG;
+    // (one operation per statement: the same roundings as the twin's, whatever the compiler may contract)
+    const double pts = (double)o->points;
+    const double sx = (double)o->sum_x * 0x1p-16, sy = (double)o->sum_y * 0x1p-16, sz = (double)o->sum_z * 0x1p-16;
+    out->centroid[0] = sx / pts;
+    out->centroid[1] = sy / pts;
+    out->centroid[2] = sz / pts;
+    const double sum_m = (double)o->sum_delta * 0x1p-20;
+    out->mean_m = sum_m / pts;
+    out->peak_m = (double)o->peak * 0x1p-20;
+    for (int k = 0; k < 3; ++k) out->size[k] = (double)o->box_max[k] - (double)o->box_min[k];
+    const double from = (double)o->station_min * p->station_length;
+    const double to = (double)(o->station_max + 1.0) * p->station_length;
+    out->chainage_from = p->t_min + from;
+    out->chainage_to = p->t_min + to;
+    const uint32_t plain = o->sector_max - o->sector_min + 1u, turned = o->sector_max_turned - o->sector_min_turned + 1u;
+    uint32_t k_from = o->sector_min, k_end = o->sector_max + 1u;
+    if (turned < plain) {   // turned back: k = (t - n_sectors / 2) mod n_sectors
+        k_from = (o->sector_min_turned + ns - half) % ns;
+        k_end = (o->sector_max_turned + ns - half) % ns + 1u;
+    }
+    const double a0 = 360.0 * (double)k_from;
+    const double a1 = 360.0 * (double)k_end;
+    out->angle_from_deg = a0 / (double)ns;
+    out->angle_to_deg = a1 / (double)ns;
+    return GM_OK;
+}
+
+gm_status gm_wall_map_check_objects(gm_wall_map *map, uint32_t slot, const gm_wall_object_params *prm, gm_wall_objects_info *info,
+                                    gm_wall_object *objects, uint32_t capacity, uint32_t *n_out, int32_t *object_of_row,
+                                    uint32_t row_capacity)
+{
+    if (!map) return GM_ERR_INVALID_ARG;
+    gm_ctx *ctx = map->ctx;
+    if (n_out) *n_out = 0;
+    if (!info) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_check_objects: NULL info");
+    if (slot >= ctx->n_slots) return gm_fail(ctx, GM_ERR_INVALID_ARG, "slot out of range");
+    gm_wall_object_params op;
+    gm_wall_object_default_params(&op);
+    if (prm) op = *prm;
+    if (!object_prm_ok(op))
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_check_objects: struct_size mismatch or a parameter outside its limits");
+    if (!objects && capacity) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_check_objects: NULL objects with a capacity");
+    if (!object_of_row && row_capacity)
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_check_objects: NULL object_of_row with a row capacity");
+    WallCheckSlot &c = map->checks[slot];
+    if (!c.have) return gm_fail(ctx, GM_ERR_NOT_READY, "gm_wall_map_check_objects: no check was enqueued on this map and slot");
+    ObjectWindow win;
+    if (!object_window(map->prm, op, c.anchor, win))
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_check_objects: the window holds more than GM_WALL_OBJECT_MAX_BLOCKS blocks");
+    if (hipSetDevice(ctx->device) != hipSuccess) return gm_fail(ctx, GM_ERR_DEVICE, "hipSetDevice failed");
+    if (c.outstanding) {   // that check only: the slot's stream may be busy with the next frame
+        GMW_HIP(ctx, hipEventSynchronize(c.done));
+        c.outstanding = false;
+    }
+    const uint32_t n_rows = (uint32_t)c.h_ctr[9];
+    const bool rows_fit = !object_of_row || row_capacity >= n_rows;
+    // (a check's own rows are never rejected: with nothing to launch they are all outside the window)
+    const gm_status st = objects_run(map, c.stage, n_rows, 0u, op, win, info, objects, capacity, n_out, rows_fit ? object_of_row : nullptr,
+                                     "gm_wall_map_check_objects: object buffer too small");
+    if (st != GM_OK) return st;
+    if (!rows_fit) return gm_fail(ctx, GM_ERR_CAPACITY, "gm_wall_map_check_objects: object_of_row buffer too small");
+    return GM_OK;
+}
+
+gm_status gm_wall_check_objects(gm_wall_map *map, const gm_wall_check_point *rows, uint32_t n_rows, int64_t anchor_station,
+                                const gm_wall_object_params *prm, gm_wall_objects_info *info, gm_wall_object *objects,
+                                uint32_t capacity, uint32_t *n_out, int32_t *object_of_row)
+{
+    if (!map) return GM_ERR_INVALID_ARG;
+    gm_ctx *ctx = map->ctx;
+    if (n_out) *n_out = 0;
+    if (!info) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_check_objects: NULL info");
+    if (n_rows && !rows) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_check_objects: NULL rows");
+    gm_wall_object_params op;
+    gm_wall_object_default_params(&op);
+    if (prm) op = *prm;
+    if (!object_prm_ok(op))
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_check_objects: struct_size mismatch or a parameter outside its limits");
+    if (!objects && capacity) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_check_objects: NULL objects with a capacity");
+    ObjectWindow win;
+    if (!object_window(map->prm, op, anchor_station, win))
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_check_objects: the window holds more than GM_WALL_OBJECT_MAX_BLOCKS blocks");
+    if (hipSetDevice(ctx->device) != hipSuccess) return gm_fail(ctx, GM_ERR_DEVICE, "hipSetDevice failed");
+    uint32_t rejected = 0;
+    if (n_rows && !win.nJ) {   // nothing will be launched: the one class that needs the rows, on the host
+        for (uint32_t i = 0; i < n_rows; ++i) {
+            uint32_t b[5];
+            memcpy(b, &rows[i], sizeof(b));   // x y z delta e
+            if (wall_object_rejected(b[0], b[1], b[2], b[4], rows[i].cell, wall_check_fix(rows[i].delta), (uint32_t)map->ncell)) ++rejected;
+        }
+    } else if (n_rows) {
+        if (map->ob_rows_cap < n_rows) {
+            hipFree(map->ob_rows);
+            map->ob_rows = nullptr; map->ob_rows_cap = 0;
+            GMW_HIP(ctx, hipMalloc((void **)&map->ob_rows, (size_t)n_rows * sizeof(gm_wall_check_point)));
+            map->ob_rows_cap = n_rows;
+        }
+        GMW_HIP(ctx, hipMemcpyAsync(map->ob_rows, rows, (size_t)n_rows * sizeof(gm_wall_check_point), hipMemcpyHostToDevice, map->stream));
+    }
+    return objects_run(map, map->ob_rows, n_rows, rejected, op, win, info, objects, capacity, n_out, object_of_row,
+                       "gm_wall_check_objects: object buffer too small");
 }
 
 }  // extern "C"

@@ -1,0 +1,417 @@
+// k_wall_objects.hip -- BUILD-DEFINED EXTENSION: a check's changed points as objects (gm_wall_map_check_objects,
+// gm_wall_check_objects), the device side.
+//
+// The rule is stated in include/gm_hip.h and DESIGN.md; the CPU twin is tests/wall_objects_np.py.  The staged rows of a
+// check are binned into map-anchored blocks of bs x bk cells, the blocks that hold enough rows of one sign are labelled as
+// connected components on a grid whose sector index wraps -- positive and negative rows apart, as two PLANES of the same
+// window: plane p's block w lives at p * NB + w in every per-block array, and parents index that space, so one
+// union-find serves both -- and every row adds into the record of its component.  A fixed number of launches, the shape of
+// k_wall_regions.hip:
+//   1. (memset)               the block counts and the counters.
+//   2. k_wall_object_bin      one thread per row: decode, count rejected / outside_window, one integer atomic on cnt.
+//   3. k_wall_object_tiles    one workgroup per tile of ts x tk <= 4096 window blocks, plane after plane: flag
+//      cnt >= min_block_points, label the tile with a union-find in LDS (left, up and, for 8-connectivity, the two upper
+//      diagonals; no wrap inside a tile), write one u32 parent per (block, plane) -- the index of its tile root, the
+//      smallest of its tile component; kWallObjectNone when not flagged.  Counts the flagged pairs and the sparse rows.
+//   4. k_wall_object_seams    one thread per border block and plane: the last column of every tile column against the
+//      next (the last one against column 0: the seam), the last row of every tile row against the next, with the diagonal
+//      pairs for 8-connectivity.  Workgroups of this launch read parents other workgroups are changing, so EVERY access to
+//      the parent array here is an agent-scope atomic (gm_unionfind.hpp).
+//   5. k_wall_object_flatten  every flagged pair finds its root and stores it; roots take a slot from a counter (one
+//      atomic per wave).  The component count goes to the host, which sizes the accumulators.
+//   6. k_wall_object_blocks   every flagged pair adds 1 to its slot's `blocks`; the root writes label and plane.
+//   7. k_wall_object_reduce   one thread per row: its slot through parent and slot, then integer atomics only into the
+//      128-byte accumulator (add: points, sum_delta, the three centroid sums; max: the six extents, the eight ordered()
+//      keys of box and e, minima kept inverted; one 64-bit max of |dq| << 32 | ~index: the peak).  Runs of one slot in
+//      consecutive lanes are merged in the wave first; the loop's trips are wave-uniform, so every lane is present at
+//      the shuffles.
+//   8. k_wall_object_select   one thread per slot: components of >= min_points rows become gm_wall_object records, in the
+//      order the slots come (the host sorts the copied list by label and sign); small / in_object row counts.
+//   9. k_wall_object_rows     only when the caller asks for object_of_row, after the host has uploaded slot -> position.
+// Launch boundaries order everything but the parents inside launch 4.  Every store index is a row index < n_rows, an index
+// < 2 NB or a slot < the component count by construction; nothing is clamped.  No floating-point arithmetic after the two
+// fixed-point conversions of a row.
+#include <stddef.h>
+#include <string.h>
+
+#include "gm_internal.hpp"
+#include "gm_unionfind.hpp"
+
+namespace gm {
+
+static_assert(sizeof(WallObjectAcc) == 128 && sizeof(gm_wall_object) == 128 && sizeof(gm_wall_check_point) == 32, "record sizes");
+// k_wall_object_select writes box_min, box_max, e_min, e_max as eight consecutive 32-bit words
+static_assert(offsetof(gm_wall_object, box_min) == 88 && offsetof(gm_wall_object, box_max) == 100 && offsetof(gm_wall_object, e_min) == 112 &&
+                  offsetof(gm_wall_object, e_max) == 116 && sizeof(float) == sizeof(uint32_t),
+              "the eight floats of gm_wall_object are contiguous");
+constexpr int kWoThreads = 256;
+constexpr uint32_t kWoMaxBlocks = 8192;
+
+// A row's index in the per-block arrays, kWallObjectRejected or kWallObjectOutside; p = x y z delta, q = e cell index row
+__device__ __forceinline__ uint32_t wo_decode(const WallObjectArgs &a, uint64_t i, uint4 &p, uint4 &q, long long &dq, uint32_t &j,
+                                              uint32_t &k)
+{
+    const uint4 *r = reinterpret_cast<const uint4 *>(a.rows + i);
+    p = r[0];
+    q = r[1];
+    dq = wall_check_fix(__uint_as_float(p.w));
+    const int32_t c = (int32_t)q.y;
+    j = 0u; k = 0u;
+    if (wall_object_rejected(p.x, p.y, p.z, q.x, c, dq, a.cells)) return kWallObjectRejected;
+    j = (uint32_t)c / a.nsec;
+    k = (uint32_t)c % a.nsec;
+    const uint32_t J = j / a.bs;
+    if (J < a.J0 || J - a.J0 >= a.nJ) return kWallObjectOutside;
+    return (dq > 0 ? a.NB : 0u) + (J - a.J0) * a.NK + k / a.bk;   // < 2 NB
+}
+
+// ---- 2. bin ----
+
+__global__ __launch_bounds__(kWoThreads) void k_wall_object_bin(WallObjectArgs a)
+{
+    uint32_t rej = 0u, outside = 0u;
+    for (uint64_t i = (uint64_t)blockIdx.x * kWoThreads + threadIdx.x; i < a.n_rows; i += (uint64_t)gridDim.x * kWoThreads) {
+        uint4 p, q;
+        long long dq;
+        uint32_t j, k;
+        const uint32_t b = wo_decode(a, i, p, q, dq, j, k);
+        if (b == kWallObjectRejected) ++rej;
+        else if (b == kWallObjectOutside) ++outside;
+        else atomicAdd(&a.cnt[b], 1u);
+    }
+    rej = wave_sum(rej);
+    outside = wave_sum(outside);
+    if (lane_id() == 0) {
+        if (rej) atomicAdd(&a.ctr[0], (unsigned long long)rej);
+        if (outside) atomicAdd(&a.ctr[1], (unsigned long long)outside);
+    }
+}
+
+// ---- 3. tiles ----
+
+__global__ __launch_bounds__(kWoThreads) void k_wall_object_tiles(WallObjectArgs a)
+{
+    __shared__ uint32_t L[kWallObjectTileBlocks];
+    __shared__ uint8_t S[kWallObjectTileBlocks];
+    __shared__ uint32_t s_cls[4];
+    const uint32_t ts = a.ts, tk = a.tk, NK = a.NK, cells = ts * tk;   // <= kWallObjectTileBlocks (the host checks)
+    const uint32_t j0 = (blockIdx.x / a.tiles_k) * ts, k0 = (blockIdx.x % a.tiles_k) * tk;
+    if (threadIdx.x < 4) s_cls[threadIdx.x] = 0u;
+    uint32_t cls[3] = {0u, 0u, 0u};   // flagged_neg, flagged_pos, sparse rows
+    for (uint32_t plane = 0; plane < 2u; ++plane) {
+        const uint32_t base = plane * a.NB;
+        for (uint32_t l = threadIdx.x; l < cells; l += kWoThreads) {
+            const uint32_t J = j0 + l / tk, K = k0 + l % tk;
+            bool flag = false;
+            if (J < a.nJ && K < NK) {
+                const uint32_t w = base + J * NK + K, c = a.cnt[w];
+                flag = c >= a.min_block_points;   // (min_block_points >= 1: an empty block is never flagged)
+                if (flag) ++cls[plane];
+                else {
+                    cls[2] += c;
+                    a.parent[w] = kWallObjectNone;
+                }
+            }
+            S[l] = flag ? 1 : 0;
+            L[l] = l;
+        }
+        __syncthreads();
+        for (uint32_t l = threadIdx.x; l < cells; l += kWoThreads) {
+            if (!S[l]) continue;
+            const uint32_t jl = l / tk, kl = l % tk;
+            if (kl > 0 && S[l - 1]) wr_lds_union(L, l, l - 1);
+            if (jl > 0) {
+                if (S[l - tk]) wr_lds_union(L, l, l - tk);
+                if (a.conn8) {
+                    if (kl > 0 && S[l - tk - 1]) wr_lds_union(L, l, l - tk - 1);
+                    if (kl + 1 < tk && S[l - tk + 1]) wr_lds_union(L, l, l - tk + 1);
+                }
+            }
+        }
+        __syncthreads();
+        // (tile-local and window-local indices are both row-major in (J, K): the smallest of one is the smallest of the other)
+        for (uint32_t l = threadIdx.x; l < cells; l += kWoThreads) {
+            if (!S[l]) continue;
+            const uint32_t r = wr_lds_find(L, l);
+            a.parent[base + (j0 + l / tk) * NK + k0 + l % tk] = base + (j0 + r / tk) * NK + k0 + r % tk;
+        }
+        __syncthreads();   // the next plane reuses L and S
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const uint32_t v = wave_sum(cls[k]);
+        if (lane_id() == 0 && v) atomicAdd(&s_cls[k], v);
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 && s_cls[threadIdx.x])
+        atomicAdd(&a.ctr[threadIdx.x == 2 ? 2 : 5 + threadIdx.x], (unsigned long long)s_cls[threadIdx.x]);
+}
+
+// ---- 4. seams ----
+
+// joins entries x and y of one plane when both are flagged
+__device__ __forceinline__ void wo_join(const WallObjectArgs &a, uint32_t x, uint32_t y)
+{
+    if (x == y || wr_load(&a.parent[x]) == kWallObjectNone || wr_load(&a.parent[y]) == kWallObjectNone) return;
+    wr_union(a.parent, x, y);
+}
+
+__global__ __launch_bounds__(kWoThreads) void k_wall_object_seams(WallObjectArgs a)
+{
+    const uint32_t NK = a.NK, n = a.nJ;
+    const uint64_t n_vert = (uint64_t)a.tiles_k * n, n_hor = (uint64_t)(a.tiles_s - 1u) * NK, per = n_vert + n_hor;
+    for (uint64_t g = (uint64_t)blockIdx.x * kWoThreads + threadIdx.x; g < 2u * per; g += (uint64_t)gridDim.x * kWoThreads) {
+        const uint32_t base = g < per ? 0u : a.NB;
+        const uint64_t i = g < per ? g : g - per;
+        if (i < n_vert) {   // the last column of tile column b against the next column, the seam for the last
+            const uint32_t b = (uint32_t)(i % a.tiles_k), j = (uint32_t)(i / a.tiles_k);
+            const uint32_t end = (b + 1u) * a.tk, k = (end < NK ? end : NK) - 1u, k2 = k + 1u < NK ? k + 1u : 0u;
+            const uint32_t x = base + j * NK + k;
+            wo_join(a, x, base + j * NK + k2);
+            if (a.conn8) {
+                if (j > 0u) wo_join(a, x, base + (j - 1u) * NK + k2);
+                if (j + 1u < n) wo_join(a, x, base + (j + 1u) * NK + k2);
+            }
+        } else {            // the last row of tile row b against the next row
+            const uint64_t h = i - n_vert;
+            const uint32_t b = (uint32_t)(h / NK), k = (uint32_t)(h % NK), j = (b + 1u) * a.ts - 1u;   // j + 1 < n
+            const uint32_t x = base + j * NK + k, y = base + (j + 1u) * NK;
+            wo_join(a, x, y + k);
+            if (a.conn8) {
+                wo_join(a, x, y + (k + 1u < NK ? k + 1u : 0u));
+                wo_join(a, x, y + (k > 0u ? k - 1u : NK - 1u));
+            }
+        }
+    }
+}
+
+// ---- 5. flatten ----
+
+__global__ __launch_bounds__(kWoThreads) void k_wall_object_flatten(WallObjectArgs a)
+{
+    const uint64_t total = 2ull * a.NB;
+    const int lane = lane_id();
+    // wave-uniform trips (the slot ranks come from a ballot)
+    for (uint64_t w0 = (uint64_t)blockIdx.x * kWoThreads + (threadIdx.x & ~(uint32_t)(kWave - 1)); w0 < total;
+         w0 += (uint64_t)gridDim.x * kWoThreads) {
+        const uint64_t w = w0 + lane;
+        bool root = false;
+        if (w < total) {
+            uint32_t x = wr_load(&a.parent[w]);
+            if (x != kWallObjectNone) {
+                // (other threads store roots meanwhile: every value ever stored is an ancestor, so the walk still ends at
+                // the root)
+                for (;;) {
+                    const uint32_t y = wr_load(&a.parent[x]);
+                    if (y == x) break;
+                    x = y;
+                }
+                root = x == (uint32_t)w;
+                if (!root) __hip_atomic_store(&a.parent[w], x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        const unsigned long long m = __ballot(root);
+        if (m) {
+            unsigned long long base = 0ull;
+            if (lane == (int)__builtin_ctzll(m)) base = atomicAdd(&a.ctr[7], (unsigned long long)__popcll(m));
+            base = __shfl(base, (int)__builtin_ctzll(m), kWave);
+            if (root) a.slot[w] = (uint32_t)base + (uint32_t)__popcll(m & lanemask_lt());
+        }
+    }
+}
+
+// ---- 6. blocks ----
+
+__global__ __launch_bounds__(kWoThreads) void k_wall_object_blocks(WallObjectArgs a)
+{
+    const uint64_t total = 2ull * a.NB;
+    for (uint64_t w = (uint64_t)blockIdx.x * kWoThreads + threadIdx.x; w < total; w += (uint64_t)gridDim.x * kWoThreads) {
+        const uint32_t r = a.parent[w];
+        if (r == kWallObjectNone) continue;
+        WallObjectAcc *acc = &a.acc[a.slot[r]];
+        atomicAdd(&acc->blocks, 1u);
+        if (r == (uint32_t)w) {   // the root alone
+            const uint32_t plane = w >= a.NB ? 1u : 0u;
+            acc->label = a.J0 * a.NK + ((uint32_t)w - plane * a.NB);
+            acc->plane = plane;
+        }
+    }
+}
+
+// ---- 7. reduce ----
+
+__global__ __launch_bounds__(kWoThreads) void k_wall_object_reduce(WallObjectArgs a)
+{
+    const uint32_t nsec = a.nsec, half = nsec / 2u;
+    const int lane = lane_id();
+    for (uint64_t i0 = (uint64_t)blockIdx.x * kWoThreads + (threadIdx.x & ~(uint32_t)(kWave - 1)); i0 < a.n_rows;
+         i0 += (uint64_t)gridDim.x * kWoThreads) {
+        const uint64_t i = i0 + lane;
+        int slot = -1;
+        uint32_t pts = 0u, smin = 0u, smax = 0u, kmin = 0u, kmax = 0u, tmin = 0u, tmax = 0u;
+        uint32_t key[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};   // ~ordered(x, y, z), ordered(x, y, z), ~ordered(e), ordered(e)
+        unsigned long long sum = 0ull, sx = 0ull, sy = 0ull, sz = 0ull, peak = 0ull;
+        if (i < a.n_rows) {
+            uint4 p, q;
+            long long dq;
+            uint32_t j, k;
+            const uint32_t b = wo_decode(a, i, p, q, dq, j, k);
+            const uint32_t r = b < kWallObjectOutside ? a.parent[b] : kWallObjectNone;
+            if (r != kWallObjectNone) {
+                slot = (int)a.slot[r];
+                const uint32_t t = k + half < nsec ? k + half : k + half - nsec;
+                const unsigned long long mag = dq < 0 ? 0ull - (unsigned long long)dq : (unsigned long long)dq;
+                pts = 1u;
+                smin = ~j; smax = j; kmin = ~k; kmax = k; tmin = ~t; tmax = t;
+                const uint32_t ox = float_to_ordered(__uint_as_float(p.x)), oy = float_to_ordered(__uint_as_float(p.y)),
+                               oz = float_to_ordered(__uint_as_float(p.z)), oe = float_to_ordered(__uint_as_float(q.x));
+                key[0] = ~ox; key[1] = ~oy; key[2] = ~oz; key[3] = ox; key[4] = oy; key[5] = oz; key[6] = ~oe; key[7] = oe;
+                sum = (unsigned long long)dq;
+                sx = (unsigned long long)wall_object_fix16(__uint_as_float(p.x));
+                sy = (unsigned long long)wall_object_fix16(__uint_as_float(p.y));
+                sz = (unsigned long long)wall_object_fix16(__uint_as_float(p.z));
+                peak = ((mag > 0xFFFFFFFFull ? 0xFFFFFFFFull : mag) << 32) | (uint32_t)~q.z;
+            }
+        }
+        // runs of one slot in consecutive lanes -> the run's head lane (k_wall_region_reduce's segmented reduction)
+        const int prev = __shfl_up(slot, 1, kWave);
+        const bool dup = lane > 0 && slot >= 0 && prev == slot;
+        const unsigned long long dmask = __ballot(dup);
+        if (dmask) {
+            const unsigned long long above = lane < kWave - 1 ? (~dmask & (~0ull << (lane + 1))) : 0ull;
+            const int tail = above ? __ffsll((long long)above) - 2 : kWave - 1;
+#pragma unroll
+            for (int o = 1; o < kWave; o <<= 1) {
+                const uint32_t oc = __shfl_down(pts, o, kWave), o1 = __shfl_down(smin, o, kWave), o2 = __shfl_down(smax, o, kWave),
+                               o3 = __shfl_down(kmin, o, kWave), o4 = __shfl_down(kmax, o, kWave), o5 = __shfl_down(tmin, o, kWave),
+                               o6 = __shfl_down(tmax, o, kWave);
+                uint32_t ok[8];
+#pragma unroll
+                for (int c = 0; c < 8; ++c) ok[c] = __shfl_down(key[c], o, kWave);
+                const unsigned long long os = __shfl_down(sum, o, kWave), ox = __shfl_down(sx, o, kWave), oy = __shfl_down(sy, o, kWave),
+                                         oz = __shfl_down(sz, o, kWave), op = __shfl_down(peak, o, kWave);
+                if (lane + o <= tail) {
+                    pts += oc; sum += os; sx += ox; sy += oy; sz += oz;
+                    smin = smin > o1 ? smin : o1; smax = smax > o2 ? smax : o2;
+                    kmin = kmin > o3 ? kmin : o3; kmax = kmax > o4 ? kmax : o4;
+                    tmin = tmin > o5 ? tmin : o5; tmax = tmax > o6 ? tmax : o6;
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) key[c] = key[c] > ok[c] ? key[c] : ok[c];
+                    peak = peak > op ? peak : op;
+                }
+            }
+        }
+        if (slot >= 0 && !dup) {
+            WallObjectAcc *r = &a.acc[slot];
+            atomicAdd(&r->points, (unsigned long long)pts);
+            atomicAdd(&r->sum_delta, sum);
+            atomicAdd(&r->sum_x, sx); atomicAdd(&r->sum_y, sy); atomicAdd(&r->sum_z, sz);
+            atomicMax(&r->st_min_inv, smin); atomicMax(&r->st_max, smax);
+            atomicMax(&r->k_min_inv, kmin); atomicMax(&r->k_max, kmax);
+            atomicMax(&r->t_min_inv, tmin); atomicMax(&r->t_max, tmax);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                atomicMax(&r->box_min_inv[c], key[c]);
+                atomicMax(&r->box_max[c], key[3 + c]);
+            }
+            atomicMax(&r->e_min_inv, key[6]); atomicMax(&r->e_max, key[7]);
+            atomicMax(&r->peak_key, peak);
+        }
+    }
+}
+
+// ---- 8. select ----
+
+// the bits of ordered_to_float(o)
+__device__ __forceinline__ uint32_t wo_unordered(uint32_t o) { return (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o; }
+
+__global__ __launch_bounds__(kWoThreads) void k_wall_object_select(WallObjectArgs a)
+{
+    uint32_t small = 0u, in_object = 0u;
+    for (uint32_t s = blockIdx.x * kWoThreads + threadIdx.x; s < a.ncomp; s += gridDim.x * kWoThreads) {
+        const WallObjectAcc *r = &a.acc[s];
+        const unsigned long long pts = r->points;
+        if (pts < a.min_points) {
+            small += (uint32_t)pts;
+            continue;
+        }
+        in_object += (uint32_t)pts;
+        const uint32_t at = (uint32_t)atomicAdd(&a.ctr[8], 1ull);   // (< ncomp: one per slot at the most)
+        const unsigned long long key = r->peak_key;
+        const long long mag = (long long)(key >> 32);
+        const uint32_t plane = r->plane;
+        gm_wall_object *g = &a.out[at];
+        g->label = r->label;
+        g->sign = plane ? 1 : -1;
+        g->blocks = r->blocks;
+        g->peak_index = ~(uint32_t)key;
+        g->station_min = ~r->st_min_inv; g->station_max = r->st_max;
+        g->sector_min = ~r->k_min_inv; g->sector_max = r->k_max;
+        g->sector_min_turned = ~r->t_min_inv; g->sector_max_turned = r->t_max;
+        g->points = pts;
+        g->peak = plane ? mag : -mag;   // (a plane holds one sign, and |dq| <= 2^31 is never saturated)
+        g->sum_delta = (long long)r->sum_delta;
+        g->sum_x = (long long)r->sum_x; g->sum_y = (long long)r->sum_y; g->sum_z = (long long)r->sum_z;
+        // The eight floats are decoded and stored as bits through one pointer; the static_assert above pins their layout.
+        // Workaround, to be removed with a later compiler: with `g->box_min[c] = ordered_to_float(~r->box_min_inv[c]);
+        // g->box_max[c] = ordered_to_float(r->box_max[c]);` in this loop, hipcc of ROCm 7.2.0 (clang 22.0.0git, roc-7.2.0
+        // 26014) -O3 --offload-arch=gfx950 dies with a segmentation fault in "AMDGPU DAG->DAG Pattern Instruction
+        // Selection" (MachineRegisterInfo::constrainRegClass) on this kernel; this kernel alone in a file reproduces it.
+        uint32_t *fb = reinterpret_cast<uint32_t *>(g->box_min);   // box_min[3] box_max[3] e_min e_max
+        for (int c = 0; c < 3; ++c) {
+            fb[c] = wo_unordered(~r->box_min_inv[c]);
+            fb[3 + c] = wo_unordered(r->box_max[c]);
+        }
+        fb[6] = wo_unordered(~r->e_min_inv);
+        fb[7] = wo_unordered(r->e_max);
+        g->reserved = 0ull;
+        a.out_slot[at] = s;
+    }
+    small = wave_sum(small);
+    in_object = wave_sum(in_object);
+    if (lane_id() == 0) {
+        if (small) atomicAdd(&a.ctr[3], (unsigned long long)small);
+        if (in_object) atomicAdd(&a.ctr[4], (unsigned long long)in_object);
+    }
+}
+
+// ---- 9. rows ----
+
+__global__ __launch_bounds__(kWoThreads) void k_wall_object_rows(WallObjectArgs a)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * kWoThreads + threadIdx.x; i < a.n_rows; i += (uint64_t)gridDim.x * kWoThreads) {
+        uint4 p, q;
+        long long dq;
+        uint32_t j, k;
+        const uint32_t b = wo_decode(a, i, p, q, dq, j, k);
+        const uint32_t r = b < kWallObjectOutside ? a.parent[b] : kWallObjectNone;
+        a.object_of_row[i] = r != kWallObjectNone ? a.pos[a.slot[r]] : -1;
+    }
+}
+
+static uint32_t wo_blocks(uint64_t n)
+{
+    const uint64_t b = (n + kWoThreads - 1) / kWoThreads;
+    return (uint32_t)(b < 1 ? 1 : (b > kWoMaxBlocks ? kWoMaxBlocks : b));
+}
+
+void launch_wall_object_label(const WallObjectArgs &a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_wall_object_bin, dim3(wo_blocks(a.n_rows)), dim3(kWoThreads), 0, s, a);
+    hipLaunchKernelGGL(k_wall_object_tiles, dim3(a.tiles_s * a.tiles_k), dim3(kWoThreads), 0, s, a);
+    hipLaunchKernelGGL(k_wall_object_seams, dim3(wo_blocks(2u * ((uint64_t)a.tiles_k * a.nJ + (uint64_t)(a.tiles_s - 1u) * a.NK))),
+                       dim3(kWoThreads), 0, s, a);
+    hipLaunchKernelGGL(k_wall_object_flatten, dim3(wo_blocks(2ull * a.NB)), dim3(kWoThreads), 0, s, a);
+}
+void launch_wall_object_reduce(const WallObjectArgs &a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_wall_object_blocks, dim3(wo_blocks(2ull * a.NB)), dim3(kWoThreads), 0, s, a);
+    hipLaunchKernelGGL(k_wall_object_reduce, dim3(wo_blocks(a.n_rows)), dim3(kWoThreads), 0, s, a);
+    hipLaunchKernelGGL(k_wall_object_select, dim3(wo_blocks(a.ncomp)), dim3(kWoThreads), 0, s, a);
+}
+void launch_wall_object_rows(const WallObjectArgs &a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_wall_object_rows, dim3(wo_blocks(a.n_rows)), dim3(kWoThreads), 0, s, a);
+}
+
+}  // namespace gm

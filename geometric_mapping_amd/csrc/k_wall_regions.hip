@@ -28,6 +28,7 @@
 #include <string.h>
 
 #include "gm_internal.hpp"
+#include "gm_unionfind.hpp"   // wr_load, wr_lds_find / wr_lds_union (tiles), wr_find / wr_union (seams)
 
 namespace gm {
 
@@ -35,33 +36,7 @@ static_assert(sizeof(WallRegionAcc) == 64 && sizeof(gm_wall_region) == 64, "64-b
 constexpr int kWrThreads = 256;
 constexpr uint32_t kWrMaxBlocks = 8192;
 
-__device__ __forceinline__ uint32_t wr_load(const uint32_t *p)
-{
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // ---- 1. tiles ----
-
-__device__ __forceinline__ uint32_t wr_lds_find(uint32_t *L, uint32_t x)
-{
-    for (;;) {
-        const uint32_t y = __hip_atomic_load(&L[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (y == x) return x;
-        x = y;
-    }
-}
-__device__ __forceinline__ void wr_lds_union(uint32_t *L, uint32_t a, uint32_t b)
-{
-    for (;;) {
-        a = wr_lds_find(L, a);
-        b = wr_lds_find(L, b);
-        if (a == b) return;
-        if (a < b) { const uint32_t t = a; a = b; b = t; }
-        const uint32_t old = atomicMin(&L[a], b);   // a was a root when read; old != a: another wave linked it meanwhile
-        if (old == a) return;
-        a = old;
-    }
-}
 
 __global__ __launch_bounds__(kWrThreads) void k_wall_region_tiles(WallRegionArgs a)
 {
@@ -134,29 +109,6 @@ __global__ __launch_bounds__(kWrThreads) void k_wall_region_tiles(WallRegionArgs
 
 // ---- 2. seams ----
 
-__device__ __forceinline__ uint32_t wr_find(uint32_t *p, uint32_t x)
-{
-    for (;;) {
-        const uint32_t y = wr_load(&p[x]);
-        if (y == x) return x;
-        const uint32_t z = wr_load(&p[y]);
-        if (z == y) return y;
-        atomicMin(&p[x], z);   // path halving: z is an ancestor of x, below its parent
-        x = z;
-    }
-}
-__device__ __forceinline__ void wr_union(uint32_t *p, uint32_t a, uint32_t b)
-{
-    for (;;) {
-        a = wr_find(p, a);
-        b = wr_find(p, b);
-        if (a == b) return;
-        if (a < b) { const uint32_t t = a; a = b; b = t; }
-        const uint32_t old = atomicMin(&p[a], b);
-        if (old == a) return;
-        a = old;   // a lost its root to another thread: what it pointed to still has to meet b
-    }
-}
 // joins window cells x and y when both are flagged with one sign
 __device__ __forceinline__ void wr_join(const WallRegionArgs &a, uint32_t x, uint32_t y)
 {

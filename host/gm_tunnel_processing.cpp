@@ -12,7 +12,7 @@ void Processor::check(gm_status s, const char *what)
 }
 
 Processor::Processor(double b, double leaf, double r, double wf, int device, unsigned flags)
-    : ctx_(0), grp_(0), cur_(0), cur_slot_(0), n_slots_(1), next_slot_(0), pending_(0), wall_(0), newest_slot_(-1)
+    : ctx_(0), grp_(0), cur_(0), cur_slot_(0), n_slots_(1), next_slot_(0), pending_(0), wall_(0), newest_slot_(-1), check_slot_(-1)
 {
     gm_config cfg;
     gm_default_config(&cfg);
@@ -27,7 +27,7 @@ Processor::Processor(double b, double leaf, double r, double wf, int device, uns
 Processor::Processor(double b, double leaf, double r, double wf, const std::vector<int> &devices, unsigned flags,
                      unsigned slots_per_device)
     : ctx_(0), grp_(0), cur_(0), cur_slot_(0), n_slots_(slots_per_device ? slots_per_device : 1), next_slot_(0), pending_(0), wall_(0),
-      newest_slot_(-1)
+      newest_slot_(-1), check_slot_(-1)
 {
     if (devices.empty()) throw Error(GM_ERR_INVALID_ARG, "Processor: empty device list");
     gm_config cfg;
@@ -374,6 +374,7 @@ void Processor::createWallMap(const gm_wall_params &params)
     check(gm_wall_map_create(ctx_, &params, &m), "createWallMap");
     if (wall_) gm_wall_map_destroy(wall_);
     wall_ = m;
+    check_slot_ = -1;
 }
 
 gm_wall_add_info Processor::addToWallMap(const double pose[12])
@@ -427,6 +428,7 @@ std::vector<gm_wall_check_point> Processor::checkWallMap(const double pose[12], 
     if (newest_slot_ < 0) throw Error(GM_ERR_NOT_READY, "checkWallMap: no frame yet");
     const unsigned slot = (unsigned)newest_slot_;
     check(gm_wall_map_check_frame(wall_, ctx_, slot, pose, &prm, 0), "checkWallMap");
+    check_slot_ = (int)slot;
     gm_wall_check_info local;
     gm_wall_check_info *ip = info ? info : &local;
     uint32_t count = 0;
@@ -435,6 +437,20 @@ std::vector<gm_wall_check_point> Processor::checkWallMap(const double pose[12], 
     if (count) check(gm_wall_map_get_check(wall_, slot, ip, &points[0], count, &count), "checkWallMap");
     points.resize(count);
     return points;
+}
+
+std::vector<gm_wall_object> Processor::wallCheckObjects(const gm_wall_object_params &prm, gm_wall_objects_info *info)
+{
+    if (!wall_) throw Error(GM_ERR_NOT_READY, "wallCheckObjects: createWallMap first");
+    if (check_slot_ < 0) throw Error(GM_ERR_NOT_READY, "wallCheckObjects: checkWallMap first");
+    gm_wall_objects_info local;
+    gm_wall_objects_info *ip = info ? info : &local;
+    uint32_t count = 0;
+    check(gm_wall_map_check_objects(wall_, (unsigned)check_slot_, &prm, ip, 0, 0, &count, 0, 0), "wallCheckObjects");
+    std::vector<gm_wall_object> objects(count);
+    if (count) check(gm_wall_map_check_objects(wall_, (unsigned)check_slot_, &prm, ip, &objects[0], count, &count, 0, 0), "wallCheckObjects");
+    objects.resize(count);
+    return objects;
 }
 
 gm_wall_info Processor::wallMapInfo()

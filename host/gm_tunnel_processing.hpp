@@ -154,6 +154,10 @@ public:
     // gm_wall_map_get_check), ascending by index; the map is not changed.  info, when given, receives the call's counts.
     // Check, then addToWallMap: against what was there, then contribute.
     std::vector<gm_wall_check_point> checkWallMap(const double pose[12], const gm_wall_check_params &prm, gm_wall_check_info *info = nullptr);
+    // the changed points of the last checkWallMap grouped into objects on the device (gm_wall_map_check_objects on the slot
+    // that check ran on), ascending by (label, sign); the check's result and the map are not changed, and the call may be
+    // repeated with other parameters.  info, when given, receives the call's counts.
+    std::vector<gm_wall_object> wallCheckObjects(const gm_wall_object_params &prm, gm_wall_objects_info *info = nullptr);
     gm_wall_map *wallMap() { return wall_; }
 
     gm_ctx *ctx() { return ctx_; }
@@ -168,6 +172,7 @@ private:
     gm_frame_result last_;                     // of the frame the accessors refer to
     gm_wall_map *wall_;                        // createWallMap (freed with the context)
     int newest_slot_;                          // slot of the frame submitted last (-1: none yet)
+    int check_slot_;                           // the slot of the last checkWallMap, -1 before it
     struct CloudBuf { gm_ctx *ctx; unsigned slot; float *rows; unsigned cap; };
     std::vector<CloudBuf> cloud_bufs_;         // enableCloudOutput: one per (device, slot)
     void growCloudOutput(unsigned n_points);

@@ -784,6 +784,135 @@ gm_status gm_wall_map_check_points(gm_wall_map *map, const float *xyz, uint32_t 
                                    gm_wall_check_point *points, uint32_t capacity, uint32_t *n_out, float *residual,
                                    int32_t *cell, int32_t *delta, uint8_t *cls);
 
+/* ---- a check's changed points as objects (gm_wall_map_check_objects, gm_wall_check_objects) ---------------------------
+ * The changed rows of a check grouped into a short list: "one object, 1.8 m long, between 20 and 44 degrees, 0.5 m inside
+ * the profile, at these sensor coordinates".  The result is a function of the MULTISET of rows (gm_wall_check_point), the
+ * map's n_stations and n_sectors, an anchor station and the parameters; it does not depend on the order of the rows, the
+ * tile shape, the grid or the order blocks run in.  From the decoding of a row on everything is integer; there are no
+ * floating-point atomics.
+ *   per row     c = cell, j = c / n_sectors, k = c % n_sectors; dq = (int64) rint(delta 2^20) by the check's own rule (fp32
+ *               product rounded to nearest even, saturating at the int32 range, 0 for a NaN: exact for the rows a check
+ *               wrote); sign = +1 if dq > 0, -1 if dq < 0.  A row is REJECTED if c is outside [0, n_stations n_sectors),
+ *               dq == 0 or any of x, y, z, e is not finite (never a check's own row; the stage call can be fed one).
+ *   blocks      anchored on the MAP, not on the window, so that a fixed object keeps its label from frame to frame:
+ *               bs = block_stations, bk = block_sectors, J = j / bs, K = k / bk, NK = ceil(n_sectors / bk),
+ *               B = J NK + K.  The last block in each direction is ragged, as in gm_wall_map_cloud.
+ *   window      stations [max(0, j_f - H), min(n_stations, j_f + H)) around the anchor station j_f (int64), H =
+ *               half_window_stations, widened to the whole block rows J0 .. J1.  A row whose J lies outside J0 .. J1 is
+ *               OUTSIDE_WINDOW; an empty window (an anchor far from the map) makes every row that is not rejected
+ *               OUTSIDE_WINDOW.  (J1 - J0 + 1) NK <= GM_WALL_OBJECT_MAX_BLOCKS, else GM_ERR_INVALID_ARG.
+ *   planes      positive and negative rows are clustered independently.  cnt_s[B] = rows of sign s in block B; (B, s) is
+ *               FLAGGED iff cnt_s[B] >= min_block_points; a row in an unflagged (B, s) is SPARSE.
+ *   neighbours  gm_wall_map_regions' rule on the block grid: (J +- 1, K) inside the window, (J, (K +- 1) mod NK) and, with
+ *               connectivity 8, (J +- 1, (K +- 1) mod NK).  The sector index wraps, the station index does not.
+ *   component   a maximal connected set of flagged blocks of one sign; its LABEL is the smallest B in it, its points the
+ *               sum of its cnt_s.  A component of >= min_points points is an OBJECT; the rows of a smaller one are SMALL.
+ *   classes     every row is in exactly one of rejected, outside_window, sparse, small, in_object.
+ *   record      station and sector extents over the rows' own j and k (the turned ones over (k + n_sectors / 2) mod
+ *               n_sectors, as in gm_wall_region); peak = the dq of the largest |dq|, peak_index = that row's `index`, the
+ *               smallest index among equals (one 64-bit integer maximum of |dq| << 32 | ~index); sum_delta = the int64 sum of
+ *               dq; sum_x, sum_y, sum_z = the int64 sums of (int64) rint(x 2^16) (fp32 product rounded to nearest even,
+ *               saturating at the int32 range); box_min, box_max, e_min, e_max = the exact extrema of the sensor
+ *               coordinates and of e, taken through ordered() keys (see the raw cells above) with integer maxima.
+ *   order       ascending by label, the negative object before the positive one at equal label.
+ *   object_of_row[i]  the position in that list of the object row i belongs to, -1 for every other row.
+ * On the device: the block counts are zeroed, one thread per row bins (B, s) with integer atomics, a tile of up to 4096
+ * window blocks per workgroup flags and labels both planes with a union-find in LDS, the tile borders and the sector seam
+ * are joined with agent-scope atomics, the forest is flattened and the roots take slots; after ONE host round trip for the
+ * component count every row adds into its slot's accumulator with integer atomics, components are selected at min_points,
+ * and, once the host has sorted the list, one thread per row writes object_of_row.  The tile shape (environment
+ * GM_WALL_OBJECT_TILE=<block rows>x<block columns>, product <= 4096, read at gm_wall_map_create: tests and measurements)
+ * changes nothing in the result. */
+#define GM_WALL_OBJECT_MAX_BLOCKS (1u << 20)   /* window blocks of one call */
+#define GM_WALL_OBJECT_TILE_ROWS 64u           /* the default tile of the labelling kernel, in blocks */
+#define GM_WALL_OBJECT_TILE_COLS 64u
+
+typedef struct gm_wall_object {     /* 128 bytes; every field is independent of the order rows were visited in */
+    uint32_t label;                 /* smallest block index B = J * NK + K of the object: its identity */
+    int32_t  sign;                  /* +1 farther from the axis than the survey, -1 inside the profile */
+    uint32_t blocks;                /* flagged blocks of the component */
+    uint32_t peak_index;            /* `index` of the row of the largest |dq|; the smallest index among equals */
+    uint32_t station_min, station_max;             /* inclusive, over the rows' j */
+    uint32_t sector_min, sector_max;               /* over the rows' k */
+    uint32_t sector_min_turned, sector_max_turned; /* over (k + n_sectors / 2) mod n_sectors */
+    uint64_t points;                /* rows of the object */
+    int64_t  peak;                  /* that row's dq, 2^-20 m */
+    int64_t  sum_delta;             /* sum of dq, 2^-20 m */
+    int64_t  sum_x, sum_y, sum_z;   /* sums of rint(x 2^16), sensor coordinates, 2^-16 m */
+    float    box_min[3], box_max[3];               /* sensor coordinates */
+    float    e_min, e_max;          /* the rows' residuals against the design cylinder */
+    uint64_t reserved;              /* 0 */
+} gm_wall_object;
+
+typedef struct gm_wall_object_params {
+    uint32_t struct_size;           /* = sizeof(gm_wall_object_params) */
+    uint32_t block_stations;        /* bs >= 1 (default 1) */
+    uint32_t block_sectors;         /* bk >= 1 (default 1) */
+    uint32_t min_block_points;      /* >= 1 (default 2): rows of one sign a block needs to be flagged */
+    uint32_t min_points;            /* >= 1 (default 8): rows a component needs to be an object */
+    uint32_t connectivity;          /* 4 or 8 (default 8) */
+    uint32_t half_window_stations;  /* H in 1 .. 2^20 (default 128) */
+    uint32_t reserved;              /* 0 */
+} gm_wall_object_params;
+
+typedef struct gm_wall_objects_info {
+    uint32_t struct_size;           /* = sizeof(gm_wall_objects_info), filled by the library */
+    uint32_t n_rows;                /* = the sum of the five classes below */
+    uint32_t station0, n_stations;  /* the block-aligned window, clipped to the map: stations [J0 bs, min((J1 + 1) bs,
+                                       n_stations)); 0, 0 when it is empty */
+    uint32_t blocks_stations, blocks_sectors;   /* J1 - J0 + 1 (0 for an empty window), NK */
+    uint32_t rejected, outside_window, sparse, small, in_object;   /* rows per class */
+    uint32_t flagged_pos, flagged_neg;          /* flagged (block, sign) pairs */
+    uint32_t components;            /* before the min_points filter */
+    uint32_t objects;               /* after it */
+    uint32_t reserved;              /* 0 */
+} gm_wall_objects_info;
+
+/* (a struct tag only, no typedef: the function of the same name below fills it) */
+struct gm_wall_object_metrics {     /* fp64, derived on the host from one record and the map's parameters */
+    double centroid[3];             /* sum 2^-16 / points, sensor coordinates */
+    double mean_m;                  /* sum_delta 2^-20 / points */
+    double peak_m;                  /* peak 2^-20 */
+    double size[3];                 /* box_max - box_min */
+    double chainage_from;           /* t_min + station_min * station_length */
+    double chainage_to;             /* t_min + (station_max + 1) * station_length */
+    double angle_from_deg;          /* gm_wall_region_metrics' rule on the four sector extents */
+    double angle_to_deg;
+};
+
+/* Host only: the defaults of the table above.  A NULL is ignored. */
+void gm_wall_object_default_params(gm_wall_object_params *p);
+/* The objects of the last check enqueued on (map, slot), ascending by (label, sign).  Waits for that check's event only
+ * (as gm_wall_map_get_check), takes the row count from the check's counters and the anchor j_f from the check, runs on the
+ * map's own stream over the staged rows where they lie -- no row crosses PCIe -- and blocks.  The check's result stays
+ * readable, the call may be repeated with other parameters, and neither the map nor the rows are changed.  prm NULL: the
+ * defaults.  info is required; it and *n_out (may be NULL; the number of objects) are filled whenever the call got as far
+ * as the device, also on GM_ERR_CAPACITY.  objects NULL with capacity 0 is a count query (GM_OK); fewer than *n_out
+ * records of capacity returns GM_ERR_CAPACITY and writes no record.  object_of_row (may be NULL, then row_capacity must
+ * be 0) receives one int32 per changed row, in the rows' order; a row_capacity below the row count returns
+ * GM_ERR_CAPACITY and writes nothing there.  Zero rows or an empty window launch nothing.  Scratch -- 12 B per window block
+ * and plane (count, parent, slot), 264 B per component (accumulator, record, two index words), 4 B per row of
+ * object_of_row -- is allocated on first use, kept grow-only in the map and freed with it; a map that never asks
+ * allocates nothing.
+ * GM_ERR_NOT_READY: no check was enqueued on (map, slot).  GM_ERR_INVALID_ARG: NULL map / info, a slot out of range, a
+ * struct_size mismatch, a parameter outside its limits, a window above GM_WALL_OBJECT_MAX_BLOCKS blocks, objects NULL with
+ * capacity > 0, object_of_row NULL with row_capacity > 0. */
+gm_status gm_wall_map_check_objects(gm_wall_map *map, uint32_t slot, const gm_wall_object_params *prm, gm_wall_objects_info *info,
+                                    gm_wall_object *objects, uint32_t capacity, uint32_t *n_out, int32_t *object_of_row,
+                                    uint32_t row_capacity);
+/* The same kernels as one blocking stage call on n_rows host rows in any order (32 B per row of device staging beside the
+ * scratch above; the map's cells are not read, only its grid).  object_of_row (may be NULL) holds n_rows entries.  Fed
+ * the rows of gm_wall_map_get_check and that check's add_info.anchor_station, it returns gm_wall_map_check_objects'
+ * bytes.  GM_ERR_INVALID_ARG as above, and for rows NULL with n_rows > 0. */
+gm_status gm_wall_check_objects(gm_wall_map *map, const gm_wall_check_point *rows, uint32_t n_rows, int64_t anchor_station,
+                                const gm_wall_object_params *prm, gm_wall_objects_info *info, gm_wall_object *objects,
+                                uint32_t capacity, uint32_t *n_out, int32_t *object_of_row);
+/* Host only, no device, no map: the fp64 derivation stated at gm_wall_object_metrics from the map's parameters (every
+ * operation rounded once).  op may be NULL (the derivation uses the rows' own extents, not the blocks).
+ * GM_ERR_INVALID_ARG: a NULL p / o / out, a struct_size mismatch, n_sectors 0, o->points 0 or an extent outside its range. */
+gm_status gm_wall_object_metrics(const gm_wall_params *p, const gm_wall_object_params *op, const gm_wall_object *o,
+                                 struct gm_wall_object_metrics *out);
+
 /* "Compressed map" record of a completed slot.  The reference defines no such
  * output; this is a build-defined format: header, primitive records,
  * then n_voxels rows of x,y,z,count (float32).  Returns the bytes needed in
