@@ -263,30 +263,52 @@ __device__ __forceinline__ uint32_t surf_sector(float wx, float wy, float wz, co
     const uint32_t kk = (uint32_t)floorf(__fdiv_rn(phi, sector_angle));
     return kk < nsec - 1u ? kk : nsec - 1u;
 }
-// runs of one cell in consecutive lanes -> the run's head lane (segmented reduction; lidar rings put ~20 consecutive
-// points into one sector).  Wave-uniform call.  Returns whether this lane still has to add its (merged) contribution.
+// ---- run merging: the common start of the segmented reductions (surf_merge_runs here, wc_merge_runs in k_wall_cloud.hip,
+// k_wall_region_reduce, k_wall_object_reduce).  Runs of one key in consecutive lanes are folded into the run's head lane
+// before anything goes to memory.  wave_runs finds the runs; the ladder stays with its caller, because its fields do:
+//     if (r.any) for (o = 1; o < kWave; o <<= 1) { w.. = __shfl_down(v.., o, kWave); if (r.lane + o <= r.tail) fold v.., w..; }
+// with EVERY shuffle of a step ahead of the one branch: the step's ds_bpermute are then issued back to back and waited for
+// once.  Folding value by value (shuffle, select, next value) saves a dozen VGPRs and costs a wait per value: measured 7 %
+// on k_wall_region_reduce over a sparsely flagged 2^24-cell map.  Wave-uniform: every lane is at the shuffles.
+struct WaveRuns {
+    int lane, tail;   // tail: the last lane of this lane's run (set when any)
+    bool dup, any;    // dup: this lane continues the run of the lane below; any: some lane of the wave does
+};
+// key < 0: this lane has nothing.  A lane with key >= 0 && !dup adds what the ladder left it.
+__device__ __forceinline__ WaveRuns wave_runs(int key)
+{
+    WaveRuns r;
+    r.lane = threadIdx.x & (kWave - 1);
+    const int prev = __shfl_up(key, 1, kWave);
+    r.dup = r.lane > 0 && key >= 0 && prev == key;
+    const unsigned long long dmask = __ballot(r.dup);
+    r.any = dmask != 0ull;
+    r.tail = r.lane;
+    if (r.any) {
+        const unsigned long long above = r.lane < kWave - 1 ? (~dmask & (~0ull << (r.lane + 1))) : 0ull;
+        r.tail = above ? __ffsll((long long)above) - 2 : kWave - 1;
+    }
+    return r;
+}
+// runs of one cell (lidar rings put ~20 consecutive points into one sector).  Returns whether this lane still has to add
+// its (merged) contribution.
 __device__ __forceinline__ bool surf_merge_runs(int cell, uint32_t &cn, unsigned long long &sm, uint32_t &lo, uint32_t &hi)
 {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int prev = __shfl_up(cell, 1, kWave);
-    const bool dup = lane > 0 && cell >= 0 && prev == cell;
-    const unsigned long long dmask = __ballot(dup);
-    if (dmask) {
-        const unsigned long long above = lane < kWave - 1 ? (~dmask & (~0ull << (lane + 1))) : 0ull;
-        const int tail = above ? __ffsll((long long)above) - 2 : kWave - 1;   // last lane of this lane's run
+    const WaveRuns r = wave_runs(cell);
+    if (r.any) {
 #pragma unroll
         for (int o = 1; o < kWave; o <<= 1) {
             const uint32_t ocn = __shfl_down(cn, o, kWave), olo = __shfl_down(lo, o, kWave),
                            ohi = __shfl_down(hi, o, kWave);
             const unsigned long long osm = __shfl_down(sm, o, kWave);
-            if (lane + o <= tail) {
+            if (r.lane + o <= r.tail) {
                 cn += ocn; sm += osm;
                 lo = lo > olo ? lo : olo;
                 hi = hi > ohi ? hi : ohi;
             }
         }
     }
-    return cell >= 0 && !dup;
+    return cell >= 0 && !r.dup;
 }
 
 __device__ __forceinline__ bool finite3(float x, float y, float z)

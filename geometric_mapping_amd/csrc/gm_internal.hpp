@@ -333,7 +333,6 @@ void launch_wall_count(const WallTable &T, uint64_t n, hipStream_t s);
 void gm_wall_free_all(gm_ctx *ctx);   // gm_destroy: the maps still alive
 // k_wall_regions.hip (gm_wall_map_regions): tiles -> seams -> flatten | reduce -> select | labels
 constexpr uint32_t kWallRegionTileCells = 4096;    // the most cells of a tile (its LDS tables)
-constexpr uint32_t kWallRegionNone = 0xFFFFFFFFu;  // parent of a cell that is not flagged
 constexpr int kWallRegionCounters = 8;             // u64: flagged_pos, flagged_neg, unusable, empty, components, regions, pad
 struct WallRegionAcc {   // 64 B, zero = empty: minima are kept inverted so that every extent is an integer maximum
     uint32_t cells, label;
@@ -349,7 +348,7 @@ struct WallRegionArgs {
     uint32_t ts, tk, tiles_s, tiles_k;   // the tile and the tiles of the window
     uint32_t conn8, min_count, min_cells;
     long long T;
-    uint32_t *parent, *slot;   // [n * nsec] window-local parent (kWallRegionNone: not flagged); a root's region slot
+    uint32_t *parent, *slot;   // [n * nsec] window-local parent (kCcNone, gm_gridcc.hpp: not flagged); a root's region slot
     long long *d;              // [n * nsec] d of the flagged cells
     unsigned long long *ctr;   // [kWallRegionCounters]
     WallRegionAcc *acc;        // [components]
@@ -427,9 +426,8 @@ __host__ __device__ inline uint32_t wall_check_rule(uint32_t reference, uint32_t
 // k_wall_objects.hip (gm_wall_map_check_objects, gm_wall_check_objects): bin -> tiles -> seams -> flatten | blocks ->
 // reduce -> select | rows
 constexpr uint32_t kWallObjectTileBlocks = 4096;      // the most window blocks of a tile (its LDS tables)
-// (two index spaces that never meet: kWallObjectNone is a value of parent[], kWallObjectRejected / kWallObjectOutside are
-// values of a row's decoded block index; both are above every real index, 2 NB <= 2^21)
-constexpr uint32_t kWallObjectNone = 0xFFFFFFFFu;     // parent of a (block, sign) that is not flagged
+// (two index spaces that never meet: kCcNone (gm_gridcc.hpp) is a value of parent[], kWallObjectRejected /
+// kWallObjectOutside are values of a row's decoded block index; both are above every real index, 2 NB <= 2^21)
 constexpr uint32_t kWallObjectRejected = 0xFFFFFFFFu, kWallObjectOutside = 0xFFFFFFFEu;   // a row without a window block
 // u64 words 0 .. 8: rejected, outside_window, sparse, small, in_object, flagged_neg, flagged_pos, components, objects;
 // words 9 .. 15 unused: the block is 128 bytes so that its zero-fill and its copy are whole multiples of 16 bytes

@@ -12,14 +12,102 @@
 
 using namespace gm;
 
-// gm_wall_map_check_*: the state of one (map, slot), allocated on first use, grow-only, freed with the map
+#define GMW_HIP(ctx, call)                                                           \
+    do {                                                                             \
+        hipError_t e__ = (call);                                                     \
+        if (e__ != hipSuccess) {                                                     \
+            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);         \
+            return (e__ == hipErrorOutOfMemory) ? GM_ERR_OOM : GM_ERR_DEVICE;        \
+        }                                                                            \
+    } while (0)
+#define GMW_OK(call)                       \
+    do {                                   \
+        const gm_status s__ = (call);      \
+        if (s__ != GM_OK) return s__;      \
+    } while (0)
+
+// A grow-only device array: the scratch of the map's calls, allocated on first use, freed with its owner (on the owner's
+// device).  reserve frees before it allocates (the peak is the larger block, never both), does not preserve the contents
+// and never shrinks; after a failure the array is empty.
+template <class T>
+struct DevArray {
+    T *p = nullptr;
+    uint64_t cap = 0;   // elements
+    DevArray() = default;
+    DevArray(DevArray &&o) : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }   // (a std::vector of owners grows)
+    DevArray(const DevArray &) = delete;
+    DevArray &operator=(const DevArray &) = delete;
+    ~DevArray() { release(); }
+    gm_status reserve(gm_ctx *ctx, uint64_t n)
+    {
+        if (cap >= n) return GM_OK;
+        release();
+        GMW_HIP(ctx, hipMalloc((void **)&p, n * sizeof(T)));
+        cap = n;
+        return GM_OK;
+    }
+    void release()
+    {
+        (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+// Consecutive arrays inside one DevArray<uint8_t> block.  Every such block is laid out by the count of the call that
+// uses it, not by the block's capacity: what a call touches is dense at the front, whatever larger call sized the block.
+struct Carve {
+    uint8_t *at;
+    template <class T>
+    T *take(uint64_t n)
+    {
+        T *r = reinterpret_cast<T *>(at);
+        at += n * sizeof(T);
+        return r;
+    }
+};
+
+// The records of a chained scan (gm_compact.hpp) that is not a frame's -- a slot's own belong to the frame that may be in
+// flight on it: the record array with the ticket word behind it, and the epoch of the launches on it so far.  The rule is
+// next_scan's (gm_internal.hpp): epochs run 1 .. 2^29-2 and never 0, and the records are cleared when the counter wraps,
+// behind every launch that wrote them.
+struct ScanRecords {
+    DevArray<unsigned long long> rec;   // [n] tile records | the ticket word
+    uint32_t n = 0;
+    uint32_t epoch = 0;
+    bool holds(uint32_t points) const { return n >= compact_records(points); }
+    // for launches over up to `points` inputs; a new block is zeroed on s.  Nothing may be in flight on the old one.
+    gm_status reserve(gm_ctx *ctx, uint32_t points, hipStream_t s)
+    {
+        if (holds(points)) return GM_OK;
+        n = 0;
+        const uint32_t want = compact_records(points);
+        GMW_OK(rec.reserve(ctx, (uint64_t)want + 1));
+        GMW_HIP(ctx, hipMemsetAsync(rec.p, 0, sizeof(unsigned long long) * ((size_t)want + 1), s));
+        n = want;
+        return GM_OK;
+    }
+    // the state of the next k_compact launch on s
+    ScanState next(hipStream_t s)
+    {
+        if (epoch >= 0x1FFFFFFEu) {
+            (void)hipMemsetAsync(rec.p, 0, sizeof(unsigned long long) * ((size_t)n + 1), s);
+            epoch = 0;
+        }
+        epoch += 1u;
+        ScanState st;
+        st.status = rec.p;
+        st.ticket = reinterpret_cast<uint32_t *>(rec.p + n);
+        st.epoch = epoch;
+        st.frame_ptr = nullptr;
+        return st;
+    }
+};
+
+// gm_wall_map_check_*: the state of one (map, slot), allocated on first use, freed with the map
 struct WallCheckSlot {
-    gm_wall_check_point *stage = nullptr;   // the changed rows of the last check, in order
-    uint32_t stage_cap = 0;
-    unsigned long long *rec = nullptr;      // [rec_cap] tile records of the chained scan | the ticket word: the check's own
-    uint32_t rec_cap = 0;                   //   (the slot's belongs to the frame that may be in flight)
-    uint32_t epoch = 0;                     // launches of k_compact on rec so far
-    unsigned long long *ctr = nullptr;      // device [kWallCheckCounters]
+    DevArray<gm_wall_check_point> stage;    // the changed rows of the last check, in order
+    ScanRecords scan;                       // the check's own chained scan
+    DevArray<unsigned long long> ctr;       // device [kWallCheckCounters]
     unsigned long long *h_ctr = nullptr;    // pinned copy, valid once `done` has passed
     hipEvent_t done = nullptr;              // recorded behind the check and the copy of its counters
     hipEvent_t adds = nullptr;              // recorded on this slot's stream by a check on another slot: the adds so far
@@ -34,56 +122,42 @@ struct gm_wall_map {
     gm_ctx *ctx = nullptr;
     gm_wall_params prm;
     uint64_t ncell = 0;
-    uint8_t *base = nullptr;       // the device table (zeroed at creation)
+    DevArray<uint8_t> base;        // the device table (zeroed at creation)
     WallTable table;
     double o[3], a[3], u[3], v[3], R;   // the design frame, fp64, not rounded
     uint32_t status = GM_SURF_OK;
     uint64_t frames = 0;
     hipStream_t stream = nullptr;  // the small kernels (read / merge / clear / count) and their copies
     std::vector<uint8_t> pending;  // per slot of ctx: an add was enqueued on its stream since the last sync
-    uint8_t *stage = nullptr;      // device staging of the window calls, kStageCells records
-    float *pt_res = nullptr;       // gm_wall_map_add_points' per-point outputs (grow-only)
-    int32_t *pt_cell = nullptr;
-    uint32_t pt_cap = 0;
+    DevArray<uint8_t> stage;       // device staging of the window calls, kStageCells records
+    // the stage calls' per-point outputs: gm_wall_map_add_points' and, beside them, gm_wall_map_check_points'
+    DevArray<float> pt_res;
+    DevArray<int32_t> pt_cell, ck_delta;
+    DevArray<uint8_t> ck_cls;
     uint32_t points_per_block = 0; // 0: the kernel's default (GM_WALL_POINTS_PER_BLOCK: measurements)
-    // gm_wall_map_regions: the tile (GM_WALL_REGION_TILE: tests, measurements) and the scratch, allocated on first use, grow-only
+    // gm_wall_map_regions: the tile (GM_WALL_REGION_TILE: tests, measurements) and the scratch
     uint32_t region_ts = GM_WALL_REGION_TILE_STATIONS, region_tk = GM_WALL_REGION_TILE_SECTORS;
-    uint8_t *rg_cells = nullptr;   // per window cell: d i64 [cap] | parent u32 [cap] | slot u32 [cap]
-    uint64_t rg_cells_cap = 0;
-    unsigned long long *rg_ctr = nullptr;   // [kWallRegionCounters]
-    uint8_t *rg_recs = nullptr;    // per component: WallRegionAcc [cap] | gm_wall_region [cap]
-    uint64_t rg_recs_cap = 0;
-    // gm_wall_map_cloud: the chunk (GM_WALL_CLOUD_CHUNK: tests, measurements; 0: kStageCells blocks) and the scratch,
-    // allocated on first use, grow-only.  The chained scan has a state of the map's own: a slot's belongs to the frame
-    // that may be in flight on that slot.
+    DevArray<uint8_t> rg_cells;    // per window cell: d i64 | parent u32 | slot u32
+    DevArray<unsigned long long> rg_ctr;   // [kWallRegionCounters]
+    DevArray<uint8_t> rg_recs;     // per component: WallRegionAcc | gm_wall_region
+    // gm_wall_map_cloud: the chunk (GM_WALL_CLOUD_CHUNK: tests, measurements; 0: kStageCells blocks) and the scratch
     uint32_t cloud_chunk = 0;
-    uint8_t *cl_acc = nullptr;     // merged accumulators of a chunk, kWallCloudAccBytes per block
-    uint64_t cl_acc_cap = 0;
-    gm_wall_cloud_point *cl_stage = nullptr;   // a chunk's records
-    uint64_t cl_stage_cap = 0;
-    unsigned long long *cl_rec = nullptr;      // [cl_rec_cap] tile records of the chained scan | the ticket word
-    uint32_t cl_rec_cap = 0;
-    uint32_t cl_epoch = 0;         // launches of k_compact on this map so far
-    unsigned long long *cl_ctr = nullptr;      // [kWallCloudCounters]
-    double *cl_dirs = nullptr;     // [GM_WALL_MAX_SECTORS][2]
+    DevArray<uint8_t> cl_acc;      // merged accumulators of a chunk, kWallCloudAccBytes per block (a merging call only)
+    DevArray<gm_wall_cloud_point> cl_stage;   // a chunk's records
+    ScanRecords cl_scan;           // the map's own chained scan
+    DevArray<unsigned long long> cl_ctr;      // [kWallCloudCounters]
+    DevArray<double> cl_dirs;      // [GM_WALL_MAX_SECTORS][2]
     std::vector<double> cl_dirs_host;          // the table of the call in progress
     // gm_wall_map_check_*
     std::vector<WallCheckSlot> checks;         // per slot of ctx
-    int32_t *ck_delta = nullptr;               // gm_wall_map_check_points' per-point outputs beside pt_res / pt_cell (grow-only)
-    uint8_t *ck_cls = nullptr;
-    uint32_t ck_cap = 0;
     // gm_wall_map_check_objects / gm_wall_check_objects: the tile in blocks (GM_WALL_OBJECT_TILE: tests, measurements) and
-    // the scratch, allocated on first use, grow-only
+    // the scratch
     uint32_t object_tr = GM_WALL_OBJECT_TILE_ROWS, object_tc = GM_WALL_OBJECT_TILE_COLS;
-    uint32_t *ob_blocks = nullptr;           // per window block and plane: cnt u32 [cap] | parent u32 [cap] | slot u32 [cap]
-    uint64_t ob_blocks_cap = 0;              //   (cap counts (block, plane) pairs)
-    unsigned long long *ob_ctr = nullptr;    // [kWallObjectCounters]
-    uint8_t *ob_recs = nullptr;              // per component: WallObjectAcc | gm_wall_object | out_slot u32 | pos i32, [cap] each
-    uint64_t ob_recs_cap = 0;
-    gm_wall_check_point *ob_rows = nullptr;  // the stage call's rows
-    uint32_t ob_rows_cap = 0;
-    int32_t *ob_of_row = nullptr;            // object_of_row
-    uint32_t ob_of_row_cap = 0;
+    DevArray<uint32_t> ob_blocks;            // per window block and plane: cnt | parent | slot
+    DevArray<unsigned long long> ob_ctr;     // [kWallObjectCounters]
+    DevArray<uint8_t> ob_recs;               // per component: WallObjectAcc | gm_wall_object | out_slot u32 | pos i32
+    DevArray<gm_wall_check_point> ob_rows;   // the stage call's rows
+    DevArray<int32_t> ob_of_row;             // object_of_row
     std::vector<gm_wall_object> ob_host;     // the unsorted list, its slots, the sorting permutation, slot -> position
     std::vector<uint32_t> ob_host_slot, ob_order;
     std::vector<int32_t> ob_pos;
@@ -92,15 +166,6 @@ struct gm_wall_map {
 namespace {
 
 constexpr uint64_t kStageCells = 1u << 20;   // cells per chunk of a window call (24 MiB of raw records)
-
-#define GMW_HIP(ctx, call)                                                           \
-    do {                                                                             \
-        hipError_t e__ = (call);                                                     \
-        if (e__ != hipSuccess) {                                                     \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);         \
-            return (e__ == hipErrorOutOfMemory) ? GM_ERR_OOM : GM_ERR_DEVICE;        \
-        }                                                                            \
-    } while (0)
 
 double dot(const double *x, const double *y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2]; }
 
@@ -271,18 +336,102 @@ void free_map(gm_wall_map *m)
         if (m->pending[i] && m->ctx->slots[i].stream) hipStreamSynchronize(m->ctx->slots[i].stream);
     for (WallCheckSlot &c : m->checks) {
         if (c.outstanding) hipEventSynchronize(c.done);
-        hipFree(c.stage); hipFree(c.rec); hipFree(c.ctr);
         if (c.h_ctr) hipHostFree(c.h_ctr);
         if (c.done) hipEventDestroy(c.done);
         if (c.adds) hipEventDestroy(c.adds);
     }
-    hipFree(m->ck_delta); hipFree(m->ck_cls);
     if (m->stream) { hipStreamSynchronize(m->stream); hipStreamDestroy(m->stream); }
-    hipFree(m->base); hipFree(m->stage); hipFree(m->pt_res); hipFree(m->pt_cell);
-    hipFree(m->rg_cells); hipFree(m->rg_ctr); hipFree(m->rg_recs);
-    hipFree(m->ob_blocks); hipFree(m->ob_ctr); hipFree(m->ob_recs); hipFree(m->ob_rows); hipFree(m->ob_of_row);
-    hipFree(m->cl_acc); hipFree(m->cl_stage); hipFree(m->cl_rec); hipFree(m->cl_ctr); hipFree(m->cl_dirs);
-    delete m;
+    delete m;   // (every DevArray goes with it)
+}
+
+// A stage call's points (gm_wall_map_add_points, gm_wall_map_check_points) on the staging slot: open, whatever the call
+// enqueues ahead of its points, upload, the call's launch, close.
+struct StageCall {
+    gm_wall_map *map;
+    uint32_t n;
+    float *residual;   // the caller's per-point outputs (NULL: not wanted)
+    int32_t *cell, *delta;
+    uint8_t *cls;
+    Slot *sl = nullptr;
+    // the slot, its capacity and the device side of the per-point outputs; nothing is enqueued
+    gm_status open()
+    {
+        gm_ctx *ctx = map->ctx;
+        GMW_OK(gm_begin_stage(ctx, sl));
+        GMW_OK(gm_ensure_capacity(ctx, *sl, n ? n : 1u, (size_t)(n ? n : 1u) * 16, true));
+        if (residual || cell) {
+            GMW_OK(map->pt_res.reserve(ctx, n));
+            GMW_OK(map->pt_cell.reserve(ctx, n));
+        }
+        if (delta || cls) {
+            GMW_OK(map->ck_delta.reserve(ctx, n));
+            GMW_OK(map->ck_cls.reserve(ctx, n));
+        }
+        return GM_OK;
+    }
+    // points and labels onto the slot's stream; w: the point fields of the launch
+    gm_status upload(const float *xyz, const uint8_t *labels, WallArgs &w)
+    {
+        gm_ctx *ctx = map->ctx;
+        GMW_OK(gm_upload_xyz(ctx, *sl, xyz, n, sl->valid4));
+        if (labels && n) GMW_HIP(ctx, hipMemcpyAsync(sl->labels, labels, n, hipMemcpyHostToDevice, sl->stream));
+        w.pts = sl->valid4;
+        w.labels = labels ? sl->labels : nullptr;
+        w.n_ptr = nullptr;
+        w.n_host = n;
+        w.res = residual ? map->pt_res.p : nullptr;
+        w.cell = cell ? map->pt_cell.p : nullptr;
+        return GM_OK;
+    }
+    // the per-point outputs back, behind the launch; blocks until the slot's stream has drained
+    gm_status close()
+    {
+        gm_ctx *ctx = map->ctx;
+        if (residual && n) GMW_HIP(ctx, hipMemcpyAsync(residual, map->pt_res.p, (size_t)n * 4, hipMemcpyDeviceToHost, sl->stream));
+        if (cell && n) GMW_HIP(ctx, hipMemcpyAsync(cell, map->pt_cell.p, (size_t)n * 4, hipMemcpyDeviceToHost, sl->stream));
+        if (delta && n) GMW_HIP(ctx, hipMemcpyAsync(delta, map->ck_delta.p, (size_t)n * 4, hipMemcpyDeviceToHost, sl->stream));
+        if (cls && n) GMW_HIP(ctx, hipMemcpyAsync(cls, map->ck_cls.p, (size_t)n, hipMemcpyDeviceToHost, sl->stream));
+        GMW_HIP(ctx, hipStreamSynchronize(sl->stream));
+        return GM_OK;
+    }
+};
+
+// the caller's parameters, or the defaults for NULL
+template <class P>
+P params_or(const P *prm, void (*defaults)(P *))
+{
+    P p;
+    defaults(&p);
+    if (prm) p = *prm;
+    return p;
+}
+
+// The extent outputs the two metrics calls share: chainage_from / _to and angle_from_deg / _to_deg of a record's station
+// and sector extents, the turned pair when it is the shorter (the record lies across the seam).  false, and nothing
+// written: the extents are not those of a record on this grid.  One operation per statement: the same roundings as the
+// twin's, whatever the compiler may contract.
+template <class R, class M>
+bool extent_metrics(const gm_wall_params &p, const R &r, M *out)
+{
+    const uint32_t ns = p.n_sectors, half = ns / 2u;
+    if (r.sector_min > r.sector_max || r.sector_max >= ns || r.sector_min_turned > r.sector_max_turned ||
+        r.sector_max_turned >= ns || r.station_min > r.station_max)
+        return false;
+    const double from = (double)r.station_min * p.station_length;
+    const double to = (double)(r.station_max + 1.0) * p.station_length;
+    out->chainage_from = p.t_min + from;
+    out->chainage_to = p.t_min + to;
+    const uint32_t plain = r.sector_max - r.sector_min + 1u, turned = r.sector_max_turned - r.sector_min_turned + 1u;
+    uint32_t k_from = r.sector_min, k_end = r.sector_max + 1u;
+    if (turned < plain) {   // turned back: k = (t - n_sectors / 2) mod n_sectors
+        k_from = (r.sector_min_turned + ns - half) % ns;
+        k_end = (r.sector_max_turned + ns - half) % ns + 1u;
+    }
+    const double a0 = 360.0 * (double)k_from;
+    const double a1 = 360.0 * (double)k_end;
+    out->angle_from_deg = a0 / (double)ns;
+    out->angle_to_deg = a1 / (double)ns;
+    return true;
 }
 
 // one window call in chunks of the staging buffer: raw true -> gm_wall_raw_cell, else gm_surface_cell
@@ -293,29 +442,13 @@ gm_status read_window(gm_wall_map *m, uint32_t station0, uint32_t n, void *cells
     const size_t rec = raw ? sizeof(gm_wall_raw_cell) : sizeof(gm_surface_cell);
     for (uint64_t done = 0; done < total; done += kStageCells) {
         const uint64_t c = std::min(kStageCells, total - done);
-        if (raw) launch_wall_read_raw(m->table, first + done, c, reinterpret_cast<gm_wall_raw_cell *>(m->stage), m->stream);
-        else launch_wall_read(m->table, first + done, c, reinterpret_cast<gm_surface_cell *>(m->stage), m->stream);
+        if (raw) launch_wall_read_raw(m->table, first + done, c, reinterpret_cast<gm_wall_raw_cell *>(m->stage.p), m->stream);
+        else launch_wall_read(m->table, first + done, c, reinterpret_cast<gm_surface_cell *>(m->stage.p), m->stream);
         GMW_HIP(ctx, hipGetLastError());
-        GMW_HIP(ctx, hipMemcpyAsync((uint8_t *)cells + done * rec, m->stage, c * rec, hipMemcpyDeviceToHost, m->stream));
+        GMW_HIP(ctx, hipMemcpyAsync((uint8_t *)cells + done * rec, m->stage.p, c * rec, hipMemcpyDeviceToHost, m->stream));
         GMW_HIP(ctx, hipStreamSynchronize(m->stream));
     }
     return GM_OK;
-}
-
-// record array + ticket word + a fresh epoch for the next k_compact launch on the map's stream (next_scan's rule)
-ScanState next_cloud_scan(gm_wall_map *m)
-{
-    if (m->cl_epoch >= 0x1FFFFFFEu) {   // the counter wraps: clear the records behind every launch that wrote them
-        (void)hipMemsetAsync(m->cl_rec, 0, sizeof(unsigned long long) * ((size_t)m->cl_rec_cap + 1), m->stream);
-        m->cl_epoch = 0;
-    }
-    m->cl_epoch += 1u;
-    ScanState st;
-    st.status = m->cl_rec;
-    st.ticket = reinterpret_cast<uint32_t *>(m->cl_rec + m->cl_rec_cap);
-    st.epoch = m->cl_epoch;
-    st.frame_ptr = nullptr;
-    return st;
 }
 
 bool cloud_params_ok(const gm_wall_cloud_params &c)
@@ -357,39 +490,19 @@ gm_status check_prepare(gm_wall_map *m, uint32_t slot, uint32_t n_cap, hipStream
     gm_ctx *ctx = m->ctx;
     WallCheckSlot &c = m->checks[slot];
     if (!c.done) GMW_HIP(ctx, hipEventCreateWithFlags(&c.done, hipEventDisableTiming));
-    if (!c.ctr) GMW_HIP(ctx, hipMalloc((void **)&c.ctr, kWallCheckCounters * 8));
+    GMW_OK(c.ctr.reserve(ctx, kWallCheckCounters));
     if (!c.h_ctr) GMW_HIP(ctx, hipHostMalloc((void **)&c.h_ctr, kWallCheckCounters * 8, hipHostMallocDefault));
-    const uint32_t nrec = compact_records(n_cap);
-    if (c.stage_cap < n_cap || c.rec_cap < nrec) {
+    if (c.stage.cap < n_cap || !c.scan.holds(n_cap)) {
         if (c.outstanding) {   // the slot's last check may still be writing the old blocks
             GMW_HIP(ctx, hipEventSynchronize(c.done));
             c.outstanding = false;
         }
         c.have = false;        // (its rows go with the block)
     }
-    if (c.stage_cap < n_cap) {
-        hipFree(c.stage);
-        c.stage = nullptr; c.stage_cap = 0;
-        GMW_HIP(ctx, hipMalloc((void **)&c.stage, (size_t)n_cap * sizeof(gm_wall_check_point)));
-        c.stage_cap = n_cap;
-    }
-    if (c.rec_cap < nrec) {
-        hipFree(c.rec);
-        c.rec = nullptr; c.rec_cap = 0;
-        GMW_HIP(ctx, hipMalloc((void **)&c.rec, sizeof(unsigned long long) * ((size_t)nrec + 1)));
-        GMW_HIP(ctx, hipMemsetAsync(c.rec, 0, sizeof(unsigned long long) * ((size_t)nrec + 1), s));
-        c.rec_cap = nrec;
-    }
-    if (c.epoch >= 0x1FFFFFFEu) {   // next_scan's rule
-        GMW_HIP(ctx, hipMemsetAsync(c.rec, 0, sizeof(unsigned long long) * ((size_t)c.rec_cap + 1), s));
-        c.epoch = 0;
-    }
-    c.epoch += 1u;
-    st.status = c.rec;
-    st.ticket = reinterpret_cast<uint32_t *>(c.rec + c.rec_cap);
-    st.epoch = c.epoch;
-    st.frame_ptr = nullptr;
-    GMW_HIP(ctx, hipMemsetAsync(c.ctr, 0, kWallCheckCounters * 8, s));
+    GMW_OK(c.stage.reserve(ctx, n_cap));
+    GMW_OK(c.scan.reserve(ctx, n_cap, s));
+    st = c.scan.next(s);
+    GMW_HIP(ctx, hipMemsetAsync(c.ctr.p, 0, kWallCheckCounters * 8, s));
     return GM_OK;
 }
 
@@ -414,7 +527,7 @@ gm_status check_enqueue(gm_wall_map *m, uint32_t slot, const WallCheckArgs &a, u
     WallCheckSlot &c = m->checks[slot];
     launch_wall_check(a, n_cap, st, s);
     GMW_HIP(ctx, hipGetLastError());
-    GMW_HIP(ctx, hipMemcpyAsync(c.h_ctr, c.ctr, kWallCheckCounters * 8, hipMemcpyDeviceToHost, s));
+    GMW_HIP(ctx, hipMemcpyAsync(c.h_ctr, c.ctr.p, kWallCheckCounters * 8, hipMemcpyDeviceToHost, s));
     GMW_HIP(ctx, hipEventRecord(c.done, s));
     c.have = true;
     c.outstanding = true;
@@ -457,7 +570,7 @@ gm_status check_result(gm_wall_map *m, uint32_t slot, gm_wall_check_info *info, 
     if (!points) return GM_OK;   // a count query
     if (got > capacity) return gm_fail(ctx, GM_ERR_CAPACITY, "gm_wall_map check: point buffer too small");
     if (got) {   // on the map's own stream: the slot's may be busy with the next frame
-        GMW_HIP(ctx, hipMemcpyAsync(points, c.stage, (size_t)got * sizeof(gm_wall_check_point), hipMemcpyDeviceToHost, m->stream));
+        GMW_HIP(ctx, hipMemcpyAsync(points, c.stage.p, (size_t)got * sizeof(gm_wall_check_point), hipMemcpyDeviceToHost, m->stream));
         GMW_HIP(ctx, hipStreamSynchronize(m->stream));
     }
     return GM_OK;
@@ -514,19 +627,9 @@ gm_status objects_run(gm_wall_map *m, const gm_wall_check_point *d_rows, uint32_
         return GM_OK;
     }
     const uint64_t NB = (uint64_t)win.nJ * win.NK, pairs = 2u * NB;
-    if (m->ob_blocks_cap < pairs) {
-        hipFree(m->ob_blocks);
-        m->ob_blocks = nullptr; m->ob_blocks_cap = 0;
-        GMW_HIP(ctx, hipMalloc((void **)&m->ob_blocks, pairs * 12));
-        m->ob_blocks_cap = pairs;
-    }
-    if (!m->ob_ctr) GMW_HIP(ctx, hipMalloc((void **)&m->ob_ctr, kWallObjectCounters * 8));
-    if (object_of_row && m->ob_of_row_cap < n_rows) {
-        hipFree(m->ob_of_row);
-        m->ob_of_row = nullptr; m->ob_of_row_cap = 0;
-        GMW_HIP(ctx, hipMalloc((void **)&m->ob_of_row, (size_t)n_rows * 4));
-        m->ob_of_row_cap = n_rows;
-    }
+    GMW_OK(m->ob_blocks.reserve(ctx, 3u * pairs));
+    GMW_OK(m->ob_ctr.reserve(ctx, kWallObjectCounters));
+    if (object_of_row) GMW_OK(m->ob_of_row.reserve(ctx, n_rows));
     WallObjectArgs a;
     memset(&a, 0, sizeof(a));
     a.rows = d_rows;
@@ -541,36 +644,31 @@ gm_status objects_run(gm_wall_map *m, const gm_wall_check_point *d_rows, uint32_
     a.conn8 = op.connectivity == 8u ? 1u : 0u;
     a.min_block_points = op.min_block_points;
     a.min_points = op.min_points;
-    a.cnt = m->ob_blocks;
-    a.parent = a.cnt + m->ob_blocks_cap;
-    a.slot = a.parent + m->ob_blocks_cap;
-    a.ctr = m->ob_ctr;
-    a.object_of_row = m->ob_of_row;
+    a.cnt = m->ob_blocks.p;   // cnt | parent | slot, [pairs] each
+    a.parent = a.cnt + pairs;
+    a.slot = a.parent + pairs;
+    a.ctr = m->ob_ctr.p;
+    a.object_of_row = m->ob_of_row.p;
     unsigned long long ctr[kWallObjectCounters];
     GMW_HIP(ctx, hipMemsetAsync(a.cnt, 0, pairs * 4, m->stream));
-    GMW_HIP(ctx, hipMemsetAsync(m->ob_ctr, 0, kWallObjectCounters * 8, m->stream));
+    GMW_HIP(ctx, hipMemsetAsync(a.ctr, 0, kWallObjectCounters * 8, m->stream));
     launch_wall_object_label(a, m->stream);
     GMW_HIP(ctx, hipGetLastError());
-    GMW_HIP(ctx, hipMemcpyAsync(ctr, m->ob_ctr, sizeof(ctr), hipMemcpyDeviceToHost, m->stream));
+    GMW_HIP(ctx, hipMemcpyAsync(ctr, a.ctr, sizeof(ctr), hipMemcpyDeviceToHost, m->stream));
     GMW_HIP(ctx, hipStreamSynchronize(m->stream));   // the one count the host needs: it sizes the records
     const uint64_t ncomp = ctr[7];
     if (ncomp) {
-        if (m->ob_recs_cap < ncomp) {
-            hipFree(m->ob_recs);
-            m->ob_recs = nullptr; m->ob_recs_cap = 0;
-            GMW_HIP(ctx, hipMalloc((void **)&m->ob_recs, ncomp * (sizeof(WallObjectAcc) + sizeof(gm_wall_object) + 8)));
-            m->ob_recs_cap = ncomp;
-        }
-        a.acc = reinterpret_cast<WallObjectAcc *>(m->ob_recs);
-        a.out = reinterpret_cast<gm_wall_object *>(m->ob_recs + m->ob_recs_cap * sizeof(WallObjectAcc));
-        a.out_slot = reinterpret_cast<uint32_t *>(m->ob_recs + m->ob_recs_cap * (sizeof(WallObjectAcc) + sizeof(gm_wall_object)));
-        int32_t *pos = reinterpret_cast<int32_t *>(a.out_slot + m->ob_recs_cap);
-        a.pos = pos;
+        GMW_OK(m->ob_recs.reserve(ctx, ncomp * (sizeof(WallObjectAcc) + sizeof(gm_wall_object) + 4 + 4)));
+        Carve recs{m->ob_recs.p};
+        a.acc = recs.take<WallObjectAcc>(ncomp);
+        a.out = recs.take<gm_wall_object>(ncomp);
+        a.out_slot = recs.take<uint32_t>(ncomp);
+        a.pos = recs.take<int32_t>(ncomp);
         a.ncomp = (uint32_t)ncomp;
         GMW_HIP(ctx, hipMemsetAsync(a.acc, 0, ncomp * sizeof(WallObjectAcc), m->stream));
         launch_wall_object_reduce(a, m->stream);
         GMW_HIP(ctx, hipGetLastError());
-        GMW_HIP(ctx, hipMemcpyAsync(ctr, m->ob_ctr, sizeof(ctr), hipMemcpyDeviceToHost, m->stream));
+        GMW_HIP(ctx, hipMemcpyAsync(ctr, a.ctr, sizeof(ctr), hipMemcpyDeviceToHost, m->stream));
         GMW_HIP(ctx, hipStreamSynchronize(m->stream));
     }
     const uint32_t nobj = (uint32_t)ctr[8];
@@ -603,7 +701,7 @@ gm_status objects_run(gm_wall_map *m, const gm_wall_check_point *d_rows, uint32_
             GMW_HIP(ctx, hipMemcpyAsync(const_cast<int32_t *>(a.pos), m->ob_pos.data(), (size_t)ncomp * 4, hipMemcpyHostToDevice, m->stream));
             launch_wall_object_rows(a, m->stream);
             GMW_HIP(ctx, hipGetLastError());
-            GMW_HIP(ctx, hipMemcpyAsync(object_of_row, m->ob_of_row, (size_t)n_rows * 4, hipMemcpyDeviceToHost, m->stream));
+            GMW_HIP(ctx, hipMemcpyAsync(object_of_row, a.object_of_row, (size_t)n_rows * 4, hipMemcpyDeviceToHost, m->stream));
             GMW_HIP(ctx, hipStreamSynchronize(m->stream));
         } else {
             std::fill(object_of_row, object_of_row + n_rows, -1);
@@ -677,9 +775,9 @@ gm_status gm_wall_map_create(gm_ctx *ctx, const gm_wall_params *params, gm_wall_
     design_frame(m);
     auto body = [&]() -> gm_status {
         GMW_HIP(ctx, hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-        GMW_HIP(ctx, hipMalloc((void **)&m->base, wall_table_bytes(m->ncell)));
-        GMW_HIP(ctx, hipMalloc((void **)&m->stage, std::min(kStageCells, m->ncell) * sizeof(gm_wall_raw_cell)));
-        GMW_HIP(ctx, hipMemsetAsync(m->base, 0, wall_table_bytes(m->ncell), m->stream));
+        GMW_OK(m->base.reserve(ctx, wall_table_bytes(m->ncell)));
+        GMW_OK(m->stage.reserve(ctx, std::min(kStageCells, m->ncell) * sizeof(gm_wall_raw_cell)));
+        GMW_HIP(ctx, hipMemsetAsync(m->base.p, 0, wall_table_bytes(m->ncell), m->stream));
         GMW_HIP(ctx, hipStreamSynchronize(m->stream));
         return GM_OK;
     };
@@ -689,7 +787,7 @@ gm_status gm_wall_map_create(gm_ctx *ctx, const gm_wall_params *params, gm_wall_
         free_map(m);
         return st;
     }
-    m->table = wall_table(m->base, m->ncell);
+    m->table = wall_table(m->base.p, m->ncell);
     ctx->walls.push_back(m);
     *map = m;
     return GM_OK;
@@ -711,8 +809,7 @@ gm_status gm_wall_map_add_frame(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, co
     Slot &sl = ctx->slots[slot];
     if (!sl.submitted) return gm_fail(ctx, GM_ERR_NOT_READY, "gm_wall_map_add_frame: the slot holds no frame");
     WallArgs w;
-    const gm_status st = add_frame_args(map, pose, add_info, w);
-    if (st != GM_OK) return st;
+    GMW_OK(add_frame_args(map, pose, add_info, w));
     if (hipSetDevice(ctx->device) != hipSuccess) return gm_fail(ctx, GM_ERR_DEVICE, "hipSetDevice failed");
     w.pts = sl.valid4;
     w.labels = (ctx->cfg.flags & GM_CFG_RANSAC_PLANE) ? sl.labels : nullptr;   // (label 1 exists with the plane RANSAC only)
@@ -735,37 +832,16 @@ gm_status gm_wall_map_add_points(gm_wall_map *map, const float *xyz, uint32_t n,
     gm_ctx *ctx = map->ctx;
     if (n && !xyz) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_add_points: NULL xyz");
     WallArgs w;
-    gm_status st = add_frame_args(map, pose, add_info, w);
-    if (st != GM_OK) return st;
-    Slot *slp;
-    st = gm_begin_stage(ctx, slp);
-    if (st != GM_OK) return st;
-    Slot &sl = *slp;
-    st = gm_ensure_capacity(ctx, sl, n ? n : 1u, (size_t)(n ? n : 1u) * 16, true);
-    if (st != GM_OK) return st;
-    if ((residual || cell) && map->pt_cap < n) {
-        hipFree(map->pt_res); hipFree(map->pt_cell);
-        map->pt_res = nullptr; map->pt_cell = nullptr; map->pt_cap = 0;
-        GMW_HIP(ctx, hipMalloc((void **)&map->pt_res, (size_t)n * 4));
-        GMW_HIP(ctx, hipMalloc((void **)&map->pt_cell, (size_t)n * 4));
-        map->pt_cap = n;
-    }
-    st = gm_upload_xyz(ctx, sl, xyz, n, sl.valid4);
-    if (st != GM_OK) return st;
-    if (labels && n) GMW_HIP(ctx, hipMemcpyAsync(sl.labels, labels, n, hipMemcpyHostToDevice, sl.stream));
-    w.pts = sl.valid4;
-    w.labels = labels ? sl.labels : nullptr;
-    w.n_ptr = nullptr;
-    w.n_host = n;
-    w.res = residual ? map->pt_res : nullptr;
-    w.cell = cell ? map->pt_cell : nullptr;
+    GMW_OK(add_frame_args(map, pose, add_info, w));
+    StageCall sc{map, n, residual, cell, nullptr, nullptr};
+    GMW_OK(sc.open());
+    GMW_OK(sc.upload(xyz, labels, w));
+    hipStream_t s = sc.sl->stream;
     for (uint32_t i = 1; i < ctx->n_slots; ++i)   // (as gm_wall_map_add_frame: behind the checks outstanding on other slots)
-        if (map->checks[i].outstanding) GMW_HIP(ctx, hipStreamWaitEvent(sl.stream, map->checks[i].done, 0));
-    launch_wall_add(w, n, map->points_per_block, sl.stream);
+        if (map->checks[i].outstanding) GMW_HIP(ctx, hipStreamWaitEvent(s, map->checks[i].done, 0));
+    launch_wall_add(w, n, map->points_per_block, s);
     GMW_HIP(ctx, hipGetLastError());
-    if (residual && n) GMW_HIP(ctx, hipMemcpyAsync(residual, map->pt_res, (size_t)n * 4, hipMemcpyDeviceToHost, sl.stream));
-    if (cell && n) GMW_HIP(ctx, hipMemcpyAsync(cell, map->pt_cell, (size_t)n * 4, hipMemcpyDeviceToHost, sl.stream));
-    GMW_HIP(ctx, hipStreamSynchronize(sl.stream));
+    GMW_OK(sc.close());
     ++map->frames;
     return GM_OK;
 }
@@ -781,8 +857,7 @@ gm_status gm_wall_map_info(gm_wall_map *map, gm_wall_info *info)
     if (!map) return GM_ERR_INVALID_ARG;
     gm_ctx *ctx = map->ctx;
     if (!info) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_info: NULL info");
-    gm_status st = sync_map(map);
-    if (st != GM_OK) return st;
+    GMW_OK(sync_map(map));
     unsigned long long tot[kWallTotals];
     GMW_HIP(ctx, hipMemsetAsync(map->table.totals + 4, 0, 8, map->stream));
     launch_wall_count(map->table, map->ncell, map->stream);
@@ -806,12 +881,10 @@ gm_status gm_wall_map_read(gm_wall_map *map, uint32_t station0, uint32_t n, gm_s
                            uint64_t *n_out)
 {
     if (!map) return GM_ERR_INVALID_ARG;
-    gm_status st = check_window(map, station0, n, capacity, n_out, "gm_wall_map_read: cell buffer too small");
-    if (st != GM_OK) return st;
+    GMW_OK(check_window(map, station0, n, capacity, n_out, "gm_wall_map_read: cell buffer too small"));
     if (!n) return sync_map(map);
     if (!cells) return gm_fail(map->ctx, GM_ERR_INVALID_ARG, "gm_wall_map_read: NULL cells");
-    st = sync_map(map);
-    if (st != GM_OK) return st;
+    GMW_OK(sync_map(map));
     return read_window(map, station0, n, cells, false);
 }
 
@@ -819,12 +892,10 @@ gm_status gm_wall_map_read_raw(gm_wall_map *map, uint32_t station0, uint32_t n, 
                                uint64_t *n_out)
 {
     if (!map) return GM_ERR_INVALID_ARG;
-    gm_status st = check_window(map, station0, n, capacity, n_out, "gm_wall_map_read_raw: cell buffer too small");
-    if (st != GM_OK) return st;
+    GMW_OK(check_window(map, station0, n, capacity, n_out, "gm_wall_map_read_raw: cell buffer too small"));
     if (!n) return sync_map(map);
     if (!cells) return gm_fail(map->ctx, GM_ERR_INVALID_ARG, "gm_wall_map_read_raw: NULL cells");
-    st = sync_map(map);
-    if (st != GM_OK) return st;
+    GMW_OK(sync_map(map));
     return read_window(map, station0, n, cells, true);
 }
 
@@ -832,16 +903,14 @@ gm_status gm_wall_map_add_raw(gm_wall_map *map, uint32_t station0, uint32_t n, c
 {
     if (!map) return GM_ERR_INVALID_ARG;
     gm_ctx *ctx = map->ctx;
-    gm_status st = check_window(map, station0, n, ~0ull, nullptr, "");
-    if (st != GM_OK) return st;
+    GMW_OK(check_window(map, station0, n, ~0ull, nullptr, ""));
     if (n && !cells) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_add_raw: NULL cells");
-    st = sync_map(map);
-    if (st != GM_OK) return st;
+    GMW_OK(sync_map(map));
     const uint64_t first = (uint64_t)station0 * map->prm.n_sectors, total = (uint64_t)n * map->prm.n_sectors;
     for (uint64_t done = 0; done < total; done += kStageCells) {
         const uint64_t c = std::min(kStageCells, total - done);
-        GMW_HIP(ctx, hipMemcpyAsync(map->stage, cells + done, c * sizeof(gm_wall_raw_cell), hipMemcpyHostToDevice, map->stream));
-        launch_wall_merge_raw(map->table, first + done, c, reinterpret_cast<const gm_wall_raw_cell *>(map->stage), map->stream);
+        GMW_HIP(ctx, hipMemcpyAsync(map->stage.p, cells + done, c * sizeof(gm_wall_raw_cell), hipMemcpyHostToDevice, map->stream));
+        launch_wall_merge_raw(map->table, first + done, c, reinterpret_cast<const gm_wall_raw_cell *>(map->stage.p), map->stream);
         GMW_HIP(ctx, hipGetLastError());
         GMW_HIP(ctx, hipStreamSynchronize(map->stream));
     }
@@ -852,10 +921,8 @@ gm_status gm_wall_map_clear(gm_wall_map *map, uint32_t station0, uint32_t n)
 {
     if (!map) return GM_ERR_INVALID_ARG;
     gm_ctx *ctx = map->ctx;
-    gm_status st = check_window(map, station0, n, ~0ull, nullptr, "");
-    if (st != GM_OK) return st;
-    st = sync_map(map);
-    if (st != GM_OK) return st;
+    GMW_OK(check_window(map, station0, n, ~0ull, nullptr, ""));
+    GMW_OK(sync_map(map));
     const bool all = station0 == 0 && n == map->prm.n_stations;
     launch_wall_clear(map->table, (uint64_t)station0 * map->prm.n_sectors, (uint64_t)n * map->prm.n_sectors, all, map->stream);
     GMW_HIP(ctx, hipGetLastError());
@@ -878,10 +945,8 @@ void gm_wall_region_default_params(gm_wall_region_params *p)
 gm_status gm_wall_region_metrics(const gm_wall_params *p, const gm_wall_region *r, struct gm_wall_region_metrics *out)
 {
     if (!p || !r || !out || p->struct_size != sizeof(gm_wall_params) || p->n_sectors < 1u || r->cells < 1u) return GM_ERR_INVALID_ARG;
-    const uint32_t ns = p->n_sectors, half = ns / 2u;
-    if (r->sector_min > r->sector_max || r->sector_max >= ns || r->sector_min_turned > r->sector_max_turned ||
-        r->sector_max_turned >= ns || r->station_min > r->station_max)
-        return GM_ERR_INVALID_ARG;
+    if (!extent_metrics(*p, *r, out)) return GM_ERR_INVALID_ARG;
+    const uint32_t ns = p->n_sectors;
     // (one operation per statement: the same roundings as the twin's, whatever the compiler may contract)
     const double two_pi = 6.283185307179586476925286766559;
     const double sr = p->station_length * p->radius;
@@ -892,20 +957,6 @@ gm_status gm_wall_region_metrics(const gm_wall_params *p, const gm_wall_region *
     out->volume_m3 = sum_m * cell_area;
     out->peak_m = (double)r->peak * 0x1p-20;
     out->mean_m = sum_m / (double)r->cells;
-    const double from = (double)r->station_min * p->station_length;
-    const double to = (double)(r->station_max + 1.0) * p->station_length;
-    out->chainage_from = p->t_min + from;
-    out->chainage_to = p->t_min + to;
-    const uint32_t plain = r->sector_max - r->sector_min + 1u, turned = r->sector_max_turned - r->sector_min_turned + 1u;
-    uint32_t k_from = r->sector_min, k_end = r->sector_max + 1u;
-    if (turned < plain) {   // turned back: k = (t - n_sectors / 2) mod n_sectors
-        k_from = (r->sector_min_turned + ns - half) % ns;
-        k_end = (r->sector_max_turned + ns - half) % ns + 1u;
-    }
-    const double a0 = 360.0 * (double)k_from;
-    const double a1 = 360.0 * (double)k_end;
-    out->angle_from_deg = a0 / (double)ns;
-    out->angle_to_deg = a1 / (double)ns;
     return GM_OK;
 }
 
@@ -917,9 +968,7 @@ gm_status gm_wall_map_regions(gm_wall_map *map, gm_wall_map *baseline, uint32_t 
     gm_ctx *ctx = map->ctx;
     if (n_out) *n_out = 0;
     if (!info) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_regions: NULL info");
-    gm_wall_region_params rp;
-    gm_wall_region_default_params(&rp);
-    if (prm) rp = *prm;
+    const gm_wall_region_params rp = params_or(prm, gm_wall_region_default_params);
     if (rp.struct_size != sizeof(gm_wall_region_params) || rp.min_count < 1u || rp.min_cells < 1u ||
         (rp.connectivity != 4u && rp.connectivity != 8u) || !(rp.threshold > 0.0) || !(rp.threshold <= 8.0))
         return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_regions: struct_size mismatch or a parameter outside its limits");
@@ -935,13 +984,10 @@ gm_status gm_wall_map_regions(gm_wall_map *map, gm_wall_map *baseline, uint32_t 
             memcmp(&p.radius, &b.radius, 8) || memcmp(p.up, b.up, 24) || memcmp(p.forward, b.forward, 24))
             return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_regions: the baseline is a map on another grid");
     }
-    gm_status st = check_window(map, station0, n, ~0ull, nullptr, "");
-    if (st != GM_OK) return st;
-    st = sync_map(map);
-    if (st != GM_OK) return st;
+    GMW_OK(check_window(map, station0, n, ~0ull, nullptr, ""));
+    GMW_OK(sync_map(map));
     if (baseline) {
-        st = sync_map(baseline);
-        if (st != GM_OK) return st;
+        GMW_OK(sync_map(baseline));
     }
     const uint32_t nsec = map->prm.n_sectors;
     memset(info, 0, sizeof(*info));
@@ -954,13 +1000,6 @@ gm_status gm_wall_map_regions(gm_wall_map *map, gm_wall_map *baseline, uint32_t 
     if (!n) return GM_OK;
 
     const uint64_t total = (uint64_t)n * nsec;
-    if (map->rg_cells_cap < total) {
-        hipFree(map->rg_cells);
-        map->rg_cells = nullptr; map->rg_cells_cap = 0;
-        GMW_HIP(ctx, hipMalloc((void **)&map->rg_cells, total * 16));
-        map->rg_cells_cap = total;
-    }
-    if (!map->rg_ctr) GMW_HIP(ctx, hipMalloc((void **)&map->rg_ctr, kWallRegionCounters * 8));
     WallRegionArgs a;
     memset(&a, 0, sizeof(a));
     a.map = map->table;
@@ -977,34 +1016,33 @@ gm_status gm_wall_map_regions(gm_wall_map *map, gm_wall_map *baseline, uint32_t 
     a.min_count = rp.min_count;
     a.min_cells = rp.min_cells;
     a.T = T;
-    a.d = reinterpret_cast<long long *>(map->rg_cells);
-    a.parent = reinterpret_cast<uint32_t *>(map->rg_cells + 8 * total);
-    a.slot = a.parent + total;
-    a.ctr = map->rg_ctr;
+    GMW_OK(map->rg_cells.reserve(ctx, total * (8 + 4 + 4)));
+    GMW_OK(map->rg_ctr.reserve(ctx, kWallRegionCounters));
+    Carve cells{map->rg_cells.p};
+    a.d = cells.take<long long>(total);
+    a.parent = cells.take<uint32_t>(total);
+    a.slot = cells.take<uint32_t>(total);
+    a.ctr = map->rg_ctr.p;
     unsigned long long ctr[kWallRegionCounters];
-    GMW_HIP(ctx, hipMemsetAsync(map->rg_ctr, 0, kWallRegionCounters * 8, map->stream));
+    GMW_HIP(ctx, hipMemsetAsync(a.ctr, 0, kWallRegionCounters * 8, map->stream));
     launch_wall_region_label(a, map->stream);
     GMW_HIP(ctx, hipGetLastError());
-    GMW_HIP(ctx, hipMemcpyAsync(ctr, map->rg_ctr, sizeof(ctr), hipMemcpyDeviceToHost, map->stream));
+    GMW_HIP(ctx, hipMemcpyAsync(ctr, a.ctr, sizeof(ctr), hipMemcpyDeviceToHost, map->stream));
     GMW_HIP(ctx, hipStreamSynchronize(map->stream));   // the one count the host needs: it sizes the records
     const uint64_t ncomp = ctr[4];
     info->flagged_pos = ctr[0]; info->flagged_neg = ctr[1]; info->unusable = ctr[2]; info->empty = ctr[3];
     info->components = ncomp;
     uint64_t nreg = 0;
     if (ncomp) {
-        if (map->rg_recs_cap < ncomp) {
-            hipFree(map->rg_recs);
-            map->rg_recs = nullptr; map->rg_recs_cap = 0;
-            GMW_HIP(ctx, hipMalloc((void **)&map->rg_recs, ncomp * (sizeof(WallRegionAcc) + sizeof(gm_wall_region))));
-            map->rg_recs_cap = ncomp;
-        }
-        a.acc = reinterpret_cast<WallRegionAcc *>(map->rg_recs);
-        a.out = reinterpret_cast<gm_wall_region *>(map->rg_recs + map->rg_recs_cap * sizeof(WallRegionAcc));
+        GMW_OK(map->rg_recs.reserve(ctx, ncomp * (sizeof(WallRegionAcc) + sizeof(gm_wall_region))));
+        Carve recs{map->rg_recs.p};
+        a.acc = recs.take<WallRegionAcc>(ncomp);
+        a.out = recs.take<gm_wall_region>(ncomp);
         a.ncomp = (uint32_t)ncomp;
         GMW_HIP(ctx, hipMemsetAsync(a.acc, 0, ncomp * sizeof(WallRegionAcc), map->stream));
         launch_wall_region_reduce(a, map->stream);
         GMW_HIP(ctx, hipGetLastError());
-        GMW_HIP(ctx, hipMemcpyAsync(&nreg, map->rg_ctr + 5, 8, hipMemcpyDeviceToHost, map->stream));
+        GMW_HIP(ctx, hipMemcpyAsync(&nreg, a.ctr + 5, 8, hipMemcpyDeviceToHost, map->stream));
         GMW_HIP(ctx, hipStreamSynchronize(map->stream));
     }
     info->regions = nreg;
@@ -1016,7 +1054,7 @@ gm_status gm_wall_map_regions(gm_wall_map *map, gm_wall_map *baseline, uint32_t 
         std::sort(regions, regions + nreg, [](const gm_wall_region &x, const gm_wall_region &y) { return x.label < y.label; });
     }
     if (cell_labels) {
-        int32_t *stage = reinterpret_cast<int32_t *>(map->stage);   // (kStageCells raw records: room for as many labels)
+        int32_t *stage = reinterpret_cast<int32_t *>(map->stage.p);   // (kStageCells raw records: room for as many labels)
         const uint64_t chunk = std::min(kStageCells, map->ncell);
         for (uint64_t done = 0; done < total; done += chunk) {
             const uint64_t c = std::min(chunk, total - done);
@@ -1063,16 +1101,12 @@ gm_status gm_wall_map_cloud(gm_wall_map *map, uint32_t station0, uint32_t n, con
     gm_ctx *ctx = map->ctx;
     if (n_out) *n_out = 0;
     if (!info) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_cloud: NULL info");
-    gm_wall_cloud_params cp;
-    gm_wall_cloud_default_params(&cp);
-    if (prm) cp = *prm;
+    const gm_wall_cloud_params cp = params_or(prm, gm_wall_cloud_default_params);
     if (!cloud_params_ok(cp))
         return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_cloud: struct_size mismatch or a parameter outside its limits");
     if (!points && capacity) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_cloud: NULL points with a capacity");
-    gm_status st = check_window(map, station0, n, ~0ull, nullptr, "");
-    if (st != GM_OK) return st;
-    st = sync_map(map);
-    if (st != GM_OK) return st;
+    GMW_OK(check_window(map, station0, n, ~0ull, nullptr, ""));
+    GMW_OK(sync_map(map));
     const uint32_t nsec = map->prm.n_sectors;
     const uint32_t bk = std::min(cp.block_sectors, nsec), bs = std::min(cp.block_stations, std::max(n, 1u));
     const uint32_t NK = (nsec + bk - 1u) / bk, NJ = (n + bs - 1u) / bs;
@@ -1091,32 +1125,16 @@ gm_status gm_wall_map_cloud(gm_wall_map *map, uint32_t station0, uint32_t n, con
     const uint32_t rows = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(chunk / NK, 1u), NJ);
     const uint64_t cb = (uint64_t)rows * NK;   // blocks of a full chunk
     const bool merged = bs > 1u || bk > 1u;
-    if (merged && map->cl_acc_cap < cb) {
-        hipFree(map->cl_acc);
-        map->cl_acc = nullptr; map->cl_acc_cap = 0;
-        GMW_HIP(ctx, hipMalloc((void **)&map->cl_acc, cb * kWallCloudAccBytes));
-        map->cl_acc_cap = cb;
-    }
-    if (map->cl_stage_cap < cb) {
-        hipFree(map->cl_stage);
-        map->cl_stage = nullptr; map->cl_stage_cap = 0;
-        GMW_HIP(ctx, hipMalloc((void **)&map->cl_stage, cb * sizeof(gm_wall_cloud_point)));
-        map->cl_stage_cap = cb;
-    }
-    const uint32_t nrec = compact_records((uint32_t)cb);
-    if (map->cl_rec_cap < nrec) {   // (nothing of the map's is in flight: the call synchronised above)
-        hipFree(map->cl_rec);
-        map->cl_rec = nullptr; map->cl_rec_cap = 0;
-        GMW_HIP(ctx, hipMalloc((void **)&map->cl_rec, sizeof(unsigned long long) * ((size_t)nrec + 1)));
-        GMW_HIP(ctx, hipMemsetAsync(map->cl_rec, 0, sizeof(unsigned long long) * ((size_t)nrec + 1), map->stream));
-        map->cl_rec_cap = nrec;
-    }
-    if (!map->cl_ctr) GMW_HIP(ctx, hipMalloc((void **)&map->cl_ctr, kWallCloudCounters * 8));
-    if (!map->cl_dirs) GMW_HIP(ctx, hipMalloc((void **)&map->cl_dirs, (size_t)GM_WALL_MAX_SECTORS * 16));
+    const uint64_t acc_bytes = cb * kWallCloudAccBytes;
+    if (merged) GMW_OK(map->cl_acc.reserve(ctx, acc_bytes));
+    GMW_OK(map->cl_stage.reserve(ctx, cb));
+    GMW_OK(map->cl_scan.reserve(ctx, (uint32_t)cb, map->stream));   // (nothing of the map's is in flight: the call synchronised above)
+    GMW_OK(map->cl_ctr.reserve(ctx, kWallCloudCounters));
+    GMW_OK(map->cl_dirs.reserve(ctx, (uint64_t)GM_WALL_MAX_SECTORS * 2));
     map->cl_dirs_host.resize((size_t)2 * NK);
     cloud_directions(nsec, bk, map->cl_dirs_host.data());
-    GMW_HIP(ctx, hipMemcpyAsync(map->cl_dirs, map->cl_dirs_host.data(), (size_t)NK * 16, hipMemcpyHostToDevice, map->stream));
-    GMW_HIP(ctx, hipMemsetAsync(map->cl_ctr, 0, kWallCloudCounters * 8, map->stream));
+    GMW_HIP(ctx, hipMemcpyAsync(map->cl_dirs.p, map->cl_dirs_host.data(), (size_t)NK * 16, hipMemcpyHostToDevice, map->stream));
+    GMW_HIP(ctx, hipMemsetAsync(map->cl_ctr.p, 0, kWallCloudCounters * 8, map->stream));
 
     WallCloudArgs a;
     memset(&a, 0, sizeof(a));
@@ -1127,13 +1145,14 @@ gm_status gm_wall_map_cloud(gm_wall_map *map, uint32_t station0, uint32_t n, con
     a.merged = merged ? 1u : 0u;
     a.min_count = cp.min_count;
     if (merged) {
-        a.acc_sum = reinterpret_cast<unsigned long long *>(map->cl_acc);
-        a.acc_cnt = a.acc_sum + cb;
-        a.acc_lo = reinterpret_cast<uint32_t *>(a.acc_cnt + cb);
-        a.acc_hi = a.acc_lo + cb;
-        a.acc_cells = a.acc_hi + cb;
+        Carve acc{map->cl_acc.p};   // kWallCloudAccBytes per block
+        a.acc_sum = acc.take<unsigned long long>(cb);
+        a.acc_cnt = acc.take<unsigned long long>(cb);
+        a.acc_lo = acc.take<uint32_t>(cb);
+        a.acc_hi = acc.take<uint32_t>(cb);
+        a.acc_cells = acc.take<uint32_t>(cb);
     }
-    a.dirs = map->cl_dirs;
+    a.dirs = map->cl_dirs.p;
     for (int k = 0; k < 3; ++k) {
         a.oa[k] = map->o[k] - cp.anchor[k];
         a.a[k] = map->a[k]; a.u[k] = map->u[k]; a.v[k] = map->v[k];
@@ -1142,8 +1161,8 @@ gm_status gm_wall_map_cloud(gm_wall_map *map, uint32_t station0, uint32_t n, con
     a.g = cp.exaggeration;
     a.t_min = map->prm.t_min;
     a.ds = map->prm.station_length;
-    a.out = map->cl_stage;
-    a.ctr = map->cl_ctr;
+    a.out = map->cl_stage.p;
+    a.ctr = map->cl_ctr.p;
 
     uint64_t total = 0;
     unsigned long long ctr[kWallCloudCounters] = {0ull, 0ull, 0ull, 0ull};
@@ -1152,18 +1171,18 @@ gm_status gm_wall_map_cloud(gm_wall_map *map, uint32_t station0, uint32_t n, con
         a.J0 = J0;
         a.nJ = std::min(rows, NJ - J0);
         if (merged) {
-            GMW_HIP(ctx, hipMemsetAsync(map->cl_acc, 0, cb * kWallCloudAccBytes, map->stream));
+            GMW_HIP(ctx, hipMemsetAsync(map->cl_acc.p, 0, acc_bytes, map->stream));
             launch_wall_cloud_merge(a, map->stream);
             GMW_HIP(ctx, hipGetLastError());
         }
-        launch_wall_cloud_compact(a, next_cloud_scan(map), map->stream);
+        launch_wall_cloud_compact(a, map->cl_scan.next(map->stream), map->stream);
         GMW_HIP(ctx, hipGetLastError());
-        GMW_HIP(ctx, hipMemcpyAsync(ctr, map->cl_ctr, sizeof(ctr), hipMemcpyDeviceToHost, map->stream));
+        GMW_HIP(ctx, hipMemcpyAsync(ctr, a.ctr, sizeof(ctr), hipMemcpyDeviceToHost, map->stream));
         GMW_HIP(ctx, hipStreamSynchronize(map->stream));
         const uint64_t got = (uint32_t)ctr[2];
         if (copying && total + got > capacity) copying = false;   // copying stops, counting goes on
         if (copying && got) {
-            GMW_HIP(ctx, hipMemcpyAsync(points + total, map->cl_stage, got * sizeof(gm_wall_cloud_point), hipMemcpyDeviceToHost,
+            GMW_HIP(ctx, hipMemcpyAsync(points + total, a.out, got * sizeof(gm_wall_cloud_point), hipMemcpyDeviceToHost,
                                         map->stream));
             GMW_HIP(ctx, hipStreamSynchronize(map->stream));
         }
@@ -1209,34 +1228,29 @@ gm_status gm_wall_map_check_frame(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, 
     if (!map || !ctx) return GM_ERR_INVALID_ARG;
     if (ctx != map->ctx) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_check_frame: the map belongs to another context");
     if (slot >= ctx->n_slots) return gm_fail(ctx, GM_ERR_INVALID_ARG, "slot out of range");
-    gm_wall_check_params cp;
-    gm_wall_check_default_params(&cp);
-    if (prm) cp = *prm;
+    const gm_wall_check_params cp = params_or(prm, gm_wall_check_default_params);
     WallCheckArgs a;
     memset(&a, 0, sizeof(a));
     if (!check_prm_ok(cp, a.T))
         return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_check_frame: struct_size mismatch or a parameter outside its limits");
     Slot &sl = ctx->slots[slot];
     if (!sl.submitted) return gm_fail(ctx, GM_ERR_NOT_READY, "gm_wall_map_check_frame: the slot holds no frame");
-    gm_status st = add_frame_args(map, pose, add_info, a.w);
-    if (st != GM_OK) return st;
+    GMW_OK(add_frame_args(map, pose, add_info, a.w));
     a.w.gate = (float)cp.gate;
     if (add_info) add_info->gate = a.w.gate;
     if (hipSetDevice(ctx->device) != hipSuccess) return gm_fail(ctx, GM_ERR_DEVICE, "hipSetDevice failed");
     const uint32_t n_cap = sl.n_in ? sl.n_in : 1u;
     ScanState scan;
-    st = check_prepare(map, slot, n_cap, sl.stream, scan);
-    if (st != GM_OK) return st;
-    st = check_wait_adds(map, slot, sl.stream);
-    if (st != GM_OK) return st;
+    GMW_OK(check_prepare(map, slot, n_cap, sl.stream, scan));
+    GMW_OK(check_wait_adds(map, slot, sl.stream));
     a.w.pts = sl.valid4;
     a.w.labels = (ctx->cfg.flags & GM_CFG_RANSAC_PLANE) ? sl.labels : nullptr;
     a.w.n_ptr = &sl.ctr->n_valid;
     a.w.n_host = sl.n_in;
     a.reference = cp.reference;
     a.min_count = cp.min_count;
-    a.out = map->checks[slot].stage;
-    a.ctr = map->checks[slot].ctr;
+    a.out = map->checks[slot].stage.p;
+    a.ctr = map->checks[slot].ctr.p;
     return check_enqueue(map, slot, a, n_cap, scan, sl.stream);
 }
 
@@ -1262,66 +1276,31 @@ gm_status gm_wall_map_check_points(gm_wall_map *map, const float *xyz, uint32_t 
     if (n_out) *n_out = 0;
     if (n && !xyz) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_check_points: NULL xyz");
     if (!points && capacity) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_check_points: NULL points with a capacity");
-    gm_wall_check_params cp;
-    gm_wall_check_default_params(&cp);
-    if (prm) cp = *prm;
+    const gm_wall_check_params cp = params_or(prm, gm_wall_check_default_params);
     WallCheckArgs a;
     memset(&a, 0, sizeof(a));
     if (!check_prm_ok(cp, a.T))
         return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_check_points: struct_size mismatch or a parameter outside its limits");
-    gm_status st = add_frame_args(map, pose, add_info, a.w);
-    if (st != GM_OK) return st;
+    GMW_OK(add_frame_args(map, pose, add_info, a.w));
     a.w.gate = (float)cp.gate;
     if (add_info) add_info->gate = a.w.gate;
-    Slot *slp;
-    st = gm_begin_stage(ctx, slp);
-    if (st != GM_OK) return st;
-    Slot &sl = *slp;
+    StageCall sc{map, n, residual, cell, delta, cls};
+    GMW_OK(sc.open());
+    hipStream_t s = sc.sl->stream;
     const uint32_t n_cap = n ? n : 1u;
-    st = gm_ensure_capacity(ctx, sl, n_cap, (size_t)n_cap * 16, true);
-    if (st != GM_OK) return st;
-    if ((residual || cell) && map->pt_cap < n) {
-        hipFree(map->pt_res); hipFree(map->pt_cell);
-        map->pt_res = nullptr; map->pt_cell = nullptr; map->pt_cap = 0;
-        GMW_HIP(ctx, hipMalloc((void **)&map->pt_res, (size_t)n * 4));
-        GMW_HIP(ctx, hipMalloc((void **)&map->pt_cell, (size_t)n * 4));
-        map->pt_cap = n;
-    }
-    if ((delta || cls) && map->ck_cap < n) {
-        hipFree(map->ck_delta); hipFree(map->ck_cls);
-        map->ck_delta = nullptr; map->ck_cls = nullptr; map->ck_cap = 0;
-        GMW_HIP(ctx, hipMalloc((void **)&map->ck_delta, (size_t)n * 4));
-        GMW_HIP(ctx, hipMalloc((void **)&map->ck_cls, (size_t)n));
-        map->ck_cap = n;
-    }
     ScanState scan;
-    st = check_prepare(map, 0, n_cap, sl.stream, scan);
-    if (st != GM_OK) return st;
-    st = check_wait_adds(map, 0, sl.stream);
-    if (st != GM_OK) return st;
-    st = gm_upload_xyz(ctx, sl, xyz, n, sl.valid4);
-    if (st != GM_OK) return st;
-    if (labels && n) GMW_HIP(ctx, hipMemcpyAsync(sl.labels, labels, n, hipMemcpyHostToDevice, sl.stream));
-    a.w.pts = sl.valid4;
-    a.w.labels = labels ? sl.labels : nullptr;
-    a.w.n_ptr = nullptr;
-    a.w.n_host = n;
-    a.w.res = residual ? map->pt_res : nullptr;
-    a.w.cell = cell ? map->pt_cell : nullptr;
-    a.delta = delta ? map->ck_delta : nullptr;
-    a.cls = cls ? map->ck_cls : nullptr;
+    GMW_OK(check_prepare(map, 0, n_cap, s, scan));
+    GMW_OK(check_wait_adds(map, 0, s));
+    GMW_OK(sc.upload(xyz, labels, a.w));
+    a.delta = delta ? map->ck_delta.p : nullptr;
+    a.cls = cls ? map->ck_cls.p : nullptr;
     a.reference = cp.reference;
     a.min_count = cp.min_count;
     a.row_is_index = 1u;
-    a.out = map->checks[0].stage;
-    a.ctr = map->checks[0].ctr;
-    st = check_enqueue(map, 0, a, n_cap, scan, sl.stream);
-    if (st != GM_OK) return st;
-    if (residual && n) GMW_HIP(ctx, hipMemcpyAsync(residual, map->pt_res, (size_t)n * 4, hipMemcpyDeviceToHost, sl.stream));
-    if (cell && n) GMW_HIP(ctx, hipMemcpyAsync(cell, map->pt_cell, (size_t)n * 4, hipMemcpyDeviceToHost, sl.stream));
-    if (delta && n) GMW_HIP(ctx, hipMemcpyAsync(delta, map->ck_delta, (size_t)n * 4, hipMemcpyDeviceToHost, sl.stream));
-    if (cls && n) GMW_HIP(ctx, hipMemcpyAsync(cls, map->ck_cls, (size_t)n, hipMemcpyDeviceToHost, sl.stream));
-    GMW_HIP(ctx, hipStreamSynchronize(sl.stream));
+    a.out = map->checks[0].stage.p;
+    a.ctr = map->checks[0].ctr.p;
+    GMW_OK(check_enqueue(map, 0, a, n_cap, scan, s));
+    GMW_OK(sc.close());
     return check_result(map, 0, info, points, capacity, n_out);
 }
 
@@ -1343,10 +1322,7 @@ gm_status gm_wall_object_metrics(const gm_wall_params *p, const gm_wall_object_p
 {
     if (!p || !o || !out || p->struct_size != sizeof(gm_wall_params) || p->n_sectors < 1u || o->points < 1u) return GM_ERR_INVALID_ARG;
     if (op && op->struct_size != sizeof(gm_wall_object_params)) return GM_ERR_INVALID_ARG;
-    const uint32_t ns = p->n_sectors, half = ns / 2u;
-    if (o->sector_min > o->sector_max || o->sector_max >= ns || o->sector_min_turned > o->sector_max_turned ||
-        o->sector_max_turned >= ns || o->station_min > o->station_max)
-        return GM_ERR_INVALID_ARG;
+    if (!extent_metrics(*p, *o, out)) return GM_ERR_INVALID_ARG;
     // (one operation per statement: the same roundings as the twin's, whatever the compiler may contract)
     const double pts = (double)o->points;
     const double sx = (double)o->sum_x * 0x1p-16, sy = (double)o->sum_y * 0x1p-16, sz = (double)o->sum_z * 0x1p-16;
@@ -1357,20 +1333,6 @@ gm_status gm_wall_object_metrics(const gm_wall_params *p, const gm_wall_object_p
     out->mean_m = sum_m / pts;
     out->peak_m = (double)o->peak * 0x1p-20;
     for (int k = 0; k < 3; ++k) out->size[k] = (double)o->box_max[k] - (double)o->box_min[k];
-    const double from = (double)o->station_min * p->station_length;
-    const double to = (double)(o->station_max + 1.0) * p->station_length;
-    out->chainage_from = p->t_min + from;
-    out->chainage_to = p->t_min + to;
-    const uint32_t plain = o->sector_max - o->sector_min + 1u, turned = o->sector_max_turned - o->sector_min_turned + 1u;
-    uint32_t k_from = o->sector_min, k_end = o->sector_max + 1u;
-    if (turned < plain) {   // turned back: k = (t - n_sectors / 2) mod n_sectors
-        k_from = (o->sector_min_turned + ns - half) % ns;
-        k_end = (o->sector_max_turned + ns - half) % ns + 1u;
-    }
-    const double a0 = 360.0 * (double)k_from;
-    const double a1 = 360.0 * (double)k_end;
-    out->angle_from_deg = a0 / (double)ns;
-    out->angle_to_deg = a1 / (double)ns;
     return GM_OK;
 }
 
@@ -1383,9 +1345,7 @@ gm_status gm_wall_map_check_objects(gm_wall_map *map, uint32_t slot, const gm_wa
     if (n_out) *n_out = 0;
     if (!info) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_check_objects: NULL info");
     if (slot >= ctx->n_slots) return gm_fail(ctx, GM_ERR_INVALID_ARG, "slot out of range");
-    gm_wall_object_params op;
-    gm_wall_object_default_params(&op);
-    if (prm) op = *prm;
+    const gm_wall_object_params op = params_or(prm, gm_wall_object_default_params);
     if (!object_prm_ok(op))
         return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_check_objects: struct_size mismatch or a parameter outside its limits");
     if (!objects && capacity) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_check_objects: NULL objects with a capacity");
@@ -1404,7 +1364,7 @@ gm_status gm_wall_map_check_objects(gm_wall_map *map, uint32_t slot, const gm_wa
     const uint32_t n_rows = (uint32_t)c.h_ctr[9];
     const bool rows_fit = !object_of_row || row_capacity >= n_rows;
     // (a check's own rows are never rejected: with nothing to launch they are all outside the window)
-    const gm_status st = objects_run(map, c.stage, n_rows, 0u, op, win, info, objects, capacity, n_out, rows_fit ? object_of_row : nullptr,
+    const gm_status st = objects_run(map, c.stage.p, n_rows, 0u, op, win, info, objects, capacity, n_out, rows_fit ? object_of_row : nullptr,
                                      "gm_wall_map_check_objects: object buffer too small");
     if (st != GM_OK) return st;
     if (!rows_fit) return gm_fail(ctx, GM_ERR_CAPACITY, "gm_wall_map_check_objects: object_of_row buffer too small");
@@ -1420,9 +1380,7 @@ gm_status gm_wall_check_objects(gm_wall_map *map, const gm_wall_check_point *row
     if (n_out) *n_out = 0;
     if (!info) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_check_objects: NULL info");
     if (n_rows && !rows) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_check_objects: NULL rows");
-    gm_wall_object_params op;
-    gm_wall_object_default_params(&op);
-    if (prm) op = *prm;
+    const gm_wall_object_params op = params_or(prm, gm_wall_object_default_params);
     if (!object_prm_ok(op))
         return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_check_objects: struct_size mismatch or a parameter outside its limits");
     if (!objects && capacity) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_check_objects: NULL objects with a capacity");
@@ -1438,15 +1396,10 @@ gm_status gm_wall_check_objects(gm_wall_map *map, const gm_wall_check_point *row
             if (wall_object_rejected(b[0], b[1], b[2], b[4], rows[i].cell, wall_check_fix(rows[i].delta), (uint32_t)map->ncell)) ++rejected;
         }
     } else if (n_rows) {
-        if (map->ob_rows_cap < n_rows) {
-            hipFree(map->ob_rows);
-            map->ob_rows = nullptr; map->ob_rows_cap = 0;
-            GMW_HIP(ctx, hipMalloc((void **)&map->ob_rows, (size_t)n_rows * sizeof(gm_wall_check_point)));
-            map->ob_rows_cap = n_rows;
-        }
-        GMW_HIP(ctx, hipMemcpyAsync(map->ob_rows, rows, (size_t)n_rows * sizeof(gm_wall_check_point), hipMemcpyHostToDevice, map->stream));
+        GMW_OK(map->ob_rows.reserve(ctx, n_rows));
+        GMW_HIP(ctx, hipMemcpyAsync(map->ob_rows.p, rows, (size_t)n_rows * sizeof(gm_wall_check_point), hipMemcpyHostToDevice, map->stream));
     }
-    return objects_run(map, map->ob_rows, n_rows, rejected, op, win, info, objects, capacity, n_out, object_of_row,
+    return objects_run(map, map->ob_rows.p, n_rows, rejected, op, win, info, objects, capacity, n_out, object_of_row,
                        "gm_wall_check_objects: object buffer too small");
 }
 

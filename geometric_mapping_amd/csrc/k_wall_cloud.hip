@@ -30,30 +30,25 @@ constexpr uint32_t kWcRows = 32;   // station rows one lane sums: a block of man
 // ---- 1. merge ----
 
 // surf_merge_runs (gm_device.hpp) with a 64-bit count and the number of non-empty cells beside it: runs of one block in
-// consecutive lanes -> the run's head lane.  Wave-uniform call.  Returns whether this lane still has to add its (merged)
+// consecutive lanes -> the run's head lane (wave_runs).  Returns whether this lane still has to add its (merged)
 // contribution.
 __device__ __forceinline__ bool wc_merge_runs(int blk, unsigned long long &cn, unsigned long long &sm, uint32_t &lo, uint32_t &hi,
                                               uint32_t &cells)
 {
-    const int lane = lane_id();
-    const int prev = __shfl_up(blk, 1, kWave);
-    const bool dup = lane > 0 && blk >= 0 && prev == blk;
-    const unsigned long long dmask = __ballot(dup);
-    if (dmask) {
-        const unsigned long long above = lane < kWave - 1 ? (~dmask & (~0ull << (lane + 1))) : 0ull;
-        const int tail = above ? __ffsll((long long)above) - 2 : kWave - 1;   // last lane of this lane's run
+    const WaveRuns r = wave_runs(blk);
+    if (r.any) {
 #pragma unroll
         for (int o = 1; o < kWave; o <<= 1) {
             const unsigned long long ocn = __shfl_down(cn, o, kWave), osm = __shfl_down(sm, o, kWave);
             const uint32_t olo = __shfl_down(lo, o, kWave), ohi = __shfl_down(hi, o, kWave), oce = __shfl_down(cells, o, kWave);
-            if (lane + o <= tail) {
+            if (r.lane + o <= r.tail) {
                 cn += ocn; sm += osm; cells += oce;
                 lo = lo > olo ? lo : olo;
                 hi = hi > ohi ? hi : ohi;
             }
         }
     }
-    return blk >= 0 && !dup;
+    return blk >= 0 && !r.dup;
 }
 
 __global__ __launch_bounds__(kWcThreads) void k_wall_cloud_merge(WallCloudArgs a, uint32_t nseg, uint32_t items)

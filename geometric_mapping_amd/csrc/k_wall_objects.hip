@@ -3,39 +3,33 @@
 //
 // The rule is stated in include/gm_hip.h and DESIGN.md; the CPU twin is tests/wall_objects_np.py.  The staged rows of a
 // check are binned into map-anchored blocks of bs x bk cells, the blocks that hold enough rows of one sign are labelled as
-// connected components on a grid whose sector index wraps -- positive and negative rows apart, as two PLANES of the same
-// window: plane p's block w lives at p * NB + w in every per-block array, and parents index that space, so one
-// union-find serves both -- and every row adds into the record of its component.  A fixed number of launches, the shape of
-// k_wall_regions.hip:
+// connected components -- positive and negative rows apart, as two PLANES of the same window: plane p's block w lives at
+// p * NB + w in every per-block array, and parents index that space, so one union-find serves both -- and every row adds
+// into the record of its component.  The labelling is gm_gridcc.hpp's, which states the union-find and the memory
+// ordering of the seams launch:
 //   1. (memset)               the block counts and the counters.
 //   2. k_wall_object_bin      one thread per row: decode, count rejected / outside_window, one integer atomic on cnt.
 //   3. k_wall_object_tiles    one workgroup per tile of ts x tk <= 4096 window blocks, plane after plane: flag
-//      cnt >= min_block_points, label the tile with a union-find in LDS (left, up and, for 8-connectivity, the two upper
-//      diagonals; no wrap inside a tile), write one u32 parent per (block, plane) -- the index of its tile root, the
-//      smallest of its tile component; kWallObjectNone when not flagged.  Counts the flagged pairs and the sparse rows.
-//   4. k_wall_object_seams    one thread per border block and plane: the last column of every tile column against the
-//      next (the last one against column 0: the seam), the last row of every tile row against the next, with the diagonal
-//      pairs for 8-connectivity.  Workgroups of this launch read parents other workgroups are changing, so EVERY access to
-//      the parent array here is an agent-scope atomic (gm_unionfind.hpp).
-//   5. k_wall_object_flatten  every flagged pair finds its root and stores it; roots take a slot from a counter (one
-//      atomic per wave).  The component count goes to the host, which sizes the accumulators.
+//      cnt >= min_block_points and label the tile (cc_label_tile).  Counts the flagged pairs and the sparse rows.
+//   4. k_wall_object_seams    one thread per border block and plane (cc_seam); flagged blocks of one plane join.
+//   5. k_wall_object_flatten  cc_flatten over the 2 NB pairs.  The component count goes to the host, which sizes the
+//      accumulators.
 //   6. k_wall_object_blocks   every flagged pair adds 1 to its slot's `blocks`; the root writes label and plane.
 //   7. k_wall_object_reduce   one thread per row: its slot through parent and slot, then integer atomics only into the
 //      128-byte accumulator (add: points, sum_delta, the three centroid sums; max: the six extents, the eight ordered()
 //      keys of box and e, minima kept inverted; one 64-bit max of |dq| << 32 | ~index: the peak).  Runs of one slot in
-//      consecutive lanes are merged in the wave first; the loop's trips are wave-uniform, so every lane is present at
-//      the shuffles.
+//      consecutive lanes are merged in the wave first (wave_runs, gm_device.hpp); the loop's trips are wave-uniform, so every lane is
+//      present at the shuffles.
 //   8. k_wall_object_select   one thread per slot: components of >= min_points rows become gm_wall_object records, in the
 //      order the slots come (the host sorts the copied list by label and sign); small / in_object row counts.
 //   9. k_wall_object_rows     only when the caller asks for object_of_row, after the host has uploaded slot -> position.
-// Launch boundaries order everything but the parents inside launch 4.  Every store index is a row index < n_rows, an index
-// < 2 NB or a slot < the component count by construction; nothing is clamped.  No floating-point arithmetic after the two
-// fixed-point conversions of a row.
+// Every store index is a row index < n_rows, an index < 2 NB or a slot < the component count by construction; nothing is
+// clamped.  No floating-point arithmetic after the two fixed-point conversions of a row.
 #include <stddef.h>
 #include <string.h>
 
 #include "gm_internal.hpp"
-#include "gm_unionfind.hpp"
+#include "gm_gridcc.hpp"
 
 namespace gm {
 
@@ -44,8 +38,6 @@ static_assert(sizeof(WallObjectAcc) == 128 && sizeof(gm_wall_object) == 128 && s
 static_assert(offsetof(gm_wall_object, box_min) == 88 && offsetof(gm_wall_object, box_max) == 100 && offsetof(gm_wall_object, e_min) == 112 &&
                   offsetof(gm_wall_object, e_max) == 116 && sizeof(float) == sizeof(uint32_t),
               "the eight floats of gm_wall_object are contiguous");
-constexpr int kWoThreads = 256;
-constexpr uint32_t kWoMaxBlocks = 8192;
 
 // A row's index in the per-block arrays, kWallObjectRejected or kWallObjectOutside; p = x y z delta, q = e cell index row
 __device__ __forceinline__ uint32_t wo_decode(const WallObjectArgs &a, uint64_t i, uint4 &p, uint4 &q, long long &dq, uint32_t &j,
@@ -67,10 +59,10 @@ __device__ __forceinline__ uint32_t wo_decode(const WallObjectArgs &a, uint64_t 
 
 // ---- 2. bin ----
 
-__global__ __launch_bounds__(kWoThreads) void k_wall_object_bin(WallObjectArgs a)
+__global__ __launch_bounds__(kCcThreads) void k_wall_object_bin(WallObjectArgs a)
 {
     uint32_t rej = 0u, outside = 0u;
-    for (uint64_t i = (uint64_t)blockIdx.x * kWoThreads + threadIdx.x; i < a.n_rows; i += (uint64_t)gridDim.x * kWoThreads) {
+    for (uint64_t i = (uint64_t)blockIdx.x * kCcThreads + threadIdx.x; i < a.n_rows; i += (uint64_t)gridDim.x * kCcThreads) {
         uint4 p, q;
         long long dq;
         uint32_t j, k;
@@ -89,7 +81,7 @@ __global__ __launch_bounds__(kWoThreads) void k_wall_object_bin(WallObjectArgs a
 
 // ---- 3. tiles ----
 
-__global__ __launch_bounds__(kWoThreads) void k_wall_object_tiles(WallObjectArgs a)
+__global__ __launch_bounds__(kCcThreads) void k_wall_object_tiles(WallObjectArgs a)
 {
     __shared__ uint32_t L[kWallObjectTileBlocks];
     __shared__ uint8_t S[kWallObjectTileBlocks];
@@ -100,7 +92,7 @@ __global__ __launch_bounds__(kWoThreads) void k_wall_object_tiles(WallObjectArgs
     uint32_t cls[3] = {0u, 0u, 0u};   // flagged_neg, flagged_pos, sparse rows
     for (uint32_t plane = 0; plane < 2u; ++plane) {
         const uint32_t base = plane * a.NB;
-        for (uint32_t l = threadIdx.x; l < cells; l += kWoThreads) {
+        for (uint32_t l = threadIdx.x; l < cells; l += kCcThreads) {
             const uint32_t J = j0 + l / tk, K = k0 + l % tk;
             bool flag = false;
             if (J < a.nJ && K < NK) {
@@ -109,32 +101,13 @@ __global__ __launch_bounds__(kWoThreads) void k_wall_object_tiles(WallObjectArgs
                 if (flag) ++cls[plane];
                 else {
                     cls[2] += c;
-                    a.parent[w] = kWallObjectNone;
+                    a.parent[w] = kCcNone;
                 }
             }
             S[l] = flag ? 1 : 0;
             L[l] = l;
         }
-        __syncthreads();
-        for (uint32_t l = threadIdx.x; l < cells; l += kWoThreads) {
-            if (!S[l]) continue;
-            const uint32_t jl = l / tk, kl = l % tk;
-            if (kl > 0 && S[l - 1]) wr_lds_union(L, l, l - 1);
-            if (jl > 0) {
-                if (S[l - tk]) wr_lds_union(L, l, l - tk);
-                if (a.conn8) {
-                    if (kl > 0 && S[l - tk - 1]) wr_lds_union(L, l, l - tk - 1);
-                    if (kl + 1 < tk && S[l - tk + 1]) wr_lds_union(L, l, l - tk + 1);
-                }
-            }
-        }
-        __syncthreads();
-        // (tile-local and window-local indices are both row-major in (J, K): the smallest of one is the smallest of the other)
-        for (uint32_t l = threadIdx.x; l < cells; l += kWoThreads) {
-            if (!S[l]) continue;
-            const uint32_t r = wr_lds_find(L, l);
-            a.parent[base + (j0 + l / tk) * NK + k0 + l % tk] = base + (j0 + r / tk) * NK + k0 + r % tk;
-        }
+        cc_label_tile(L, S, cells, tk, a.conn8 != 0u, a.parent, [=](uint32_t r, uint32_t c) { return base + (j0 + r) * NK + k0 + c; });
         __syncthreads();   // the next plane reuses L and S
     }
 #pragma unroll
@@ -149,85 +122,31 @@ __global__ __launch_bounds__(kWoThreads) void k_wall_object_tiles(WallObjectArgs
 
 // ---- 4. seams ----
 
-// joins entries x and y of one plane when both are flagged
-__device__ __forceinline__ void wo_join(const WallObjectArgs &a, uint32_t x, uint32_t y)
+__global__ __launch_bounds__(kCcThreads) void k_wall_object_seams(WallObjectArgs a)
 {
-    if (x == y || wr_load(&a.parent[x]) == kWallObjectNone || wr_load(&a.parent[y]) == kWallObjectNone) return;
-    wr_union(a.parent, x, y);
-}
-
-__global__ __launch_bounds__(kWoThreads) void k_wall_object_seams(WallObjectArgs a)
-{
-    const uint32_t NK = a.NK, n = a.nJ;
-    const uint64_t n_vert = (uint64_t)a.tiles_k * n, n_hor = (uint64_t)(a.tiles_s - 1u) * NK, per = n_vert + n_hor;
-    for (uint64_t g = (uint64_t)blockIdx.x * kWoThreads + threadIdx.x; g < 2u * per; g += (uint64_t)gridDim.x * kWoThreads) {
-        const uint32_t base = g < per ? 0u : a.NB;
-        const uint64_t i = g < per ? g : g - per;
-        if (i < n_vert) {   // the last column of tile column b against the next column, the seam for the last
-            const uint32_t b = (uint32_t)(i % a.tiles_k), j = (uint32_t)(i / a.tiles_k);
-            const uint32_t end = (b + 1u) * a.tk, k = (end < NK ? end : NK) - 1u, k2 = k + 1u < NK ? k + 1u : 0u;
-            const uint32_t x = base + j * NK + k;
-            wo_join(a, x, base + j * NK + k2);
-            if (a.conn8) {
-                if (j > 0u) wo_join(a, x, base + (j - 1u) * NK + k2);
-                if (j + 1u < n) wo_join(a, x, base + (j + 1u) * NK + k2);
-            }
-        } else {            // the last row of tile row b against the next row
-            const uint64_t h = i - n_vert;
-            const uint32_t b = (uint32_t)(h / NK), k = (uint32_t)(h % NK), j = (b + 1u) * a.ts - 1u;   // j + 1 < n
-            const uint32_t x = base + j * NK + k, y = base + (j + 1u) * NK;
-            wo_join(a, x, y + k);
-            if (a.conn8) {
-                wo_join(a, x, y + (k + 1u < NK ? k + 1u : 0u));
-                wo_join(a, x, y + (k > 0u ? k - 1u : NK - 1u));
-            }
-        }
-    }
+    const uint64_t per = cc_seam_count(a.nJ, a.NK, a.tiles_s, a.tiles_k);
+    for (uint64_t g = (uint64_t)blockIdx.x * kCcThreads + threadIdx.x; g < 2u * per; g += (uint64_t)gridDim.x * kCcThreads)
+        cc_seam(g < per ? g : g - per, a.nJ, a.NK, a.ts, a.tk, a.tiles_k, a.conn8 != 0u, g < per ? 0u : a.NB,
+                [&a](uint32_t x, uint32_t y) {   // entries of one plane join when both are flagged
+                    if (cc_joinable(a.parent, x, y)) cc_union(a.parent, x, y);
+                });
 }
 
 // ---- 5. flatten ----
 
-__global__ __launch_bounds__(kWoThreads) void k_wall_object_flatten(WallObjectArgs a)
+__global__ __launch_bounds__(kCcThreads) void k_wall_object_flatten(WallObjectArgs a)
 {
-    const uint64_t total = 2ull * a.NB;
-    const int lane = lane_id();
-    // wave-uniform trips (the slot ranks come from a ballot)
-    for (uint64_t w0 = (uint64_t)blockIdx.x * kWoThreads + (threadIdx.x & ~(uint32_t)(kWave - 1)); w0 < total;
-         w0 += (uint64_t)gridDim.x * kWoThreads) {
-        const uint64_t w = w0 + lane;
-        bool root = false;
-        if (w < total) {
-            uint32_t x = wr_load(&a.parent[w]);
-            if (x != kWallObjectNone) {
-                // (other threads store roots meanwhile: every value ever stored is an ancestor, so the walk still ends at
-                // the root)
-                for (;;) {
-                    const uint32_t y = wr_load(&a.parent[x]);
-                    if (y == x) break;
-                    x = y;
-                }
-                root = x == (uint32_t)w;
-                if (!root) __hip_atomic_store(&a.parent[w], x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        const unsigned long long m = __ballot(root);
-        if (m) {
-            unsigned long long base = 0ull;
-            if (lane == (int)__builtin_ctzll(m)) base = atomicAdd(&a.ctr[7], (unsigned long long)__popcll(m));
-            base = __shfl(base, (int)__builtin_ctzll(m), kWave);
-            if (root) a.slot[w] = (uint32_t)base + (uint32_t)__popcll(m & lanemask_lt());
-        }
-    }
+    cc_flatten(a.parent, a.slot, 2ull * a.NB, &a.ctr[7]);
 }
 
 // ---- 6. blocks ----
 
-__global__ __launch_bounds__(kWoThreads) void k_wall_object_blocks(WallObjectArgs a)
+__global__ __launch_bounds__(kCcThreads) void k_wall_object_blocks(WallObjectArgs a)
 {
     const uint64_t total = 2ull * a.NB;
-    for (uint64_t w = (uint64_t)blockIdx.x * kWoThreads + threadIdx.x; w < total; w += (uint64_t)gridDim.x * kWoThreads) {
+    for (uint64_t w = (uint64_t)blockIdx.x * kCcThreads + threadIdx.x; w < total; w += (uint64_t)gridDim.x * kCcThreads) {
         const uint32_t r = a.parent[w];
-        if (r == kWallObjectNone) continue;
+        if (r == kCcNone) continue;
         WallObjectAcc *acc = &a.acc[a.slot[r]];
         atomicAdd(&acc->blocks, 1u);
         if (r == (uint32_t)w) {   // the root alone
@@ -240,12 +159,12 @@ __global__ __launch_bounds__(kWoThreads) void k_wall_object_blocks(WallObjectArg
 
 // ---- 7. reduce ----
 
-__global__ __launch_bounds__(kWoThreads) void k_wall_object_reduce(WallObjectArgs a)
+__global__ __launch_bounds__(kCcThreads) void k_wall_object_reduce(WallObjectArgs a)
 {
     const uint32_t nsec = a.nsec, half = nsec / 2u;
     const int lane = lane_id();
-    for (uint64_t i0 = (uint64_t)blockIdx.x * kWoThreads + (threadIdx.x & ~(uint32_t)(kWave - 1)); i0 < a.n_rows;
-         i0 += (uint64_t)gridDim.x * kWoThreads) {
+    for (uint64_t i0 = (uint64_t)blockIdx.x * kCcThreads + (threadIdx.x & ~(uint32_t)(kWave - 1)); i0 < a.n_rows;
+         i0 += (uint64_t)gridDim.x * kCcThreads) {
         const uint64_t i = i0 + lane;
         int slot = -1;
         uint32_t pts = 0u, smin = 0u, smax = 0u, kmin = 0u, kmax = 0u, tmin = 0u, tmax = 0u;
@@ -256,8 +175,8 @@ __global__ __launch_bounds__(kWoThreads) void k_wall_object_reduce(WallObjectArg
             long long dq;
             uint32_t j, k;
             const uint32_t b = wo_decode(a, i, p, q, dq, j, k);
-            const uint32_t r = b < kWallObjectOutside ? a.parent[b] : kWallObjectNone;
-            if (r != kWallObjectNone) {
+            const uint32_t r = b < kWallObjectOutside ? a.parent[b] : kCcNone;
+            if (r != kCcNone) {
                 slot = (int)a.slot[r];
                 const uint32_t t = k + half < nsec ? k + half : k + half - nsec;
                 const unsigned long long mag = dq < 0 ? 0ull - (unsigned long long)dq : (unsigned long long)dq;
@@ -273,13 +192,8 @@ __global__ __launch_bounds__(kWoThreads) void k_wall_object_reduce(WallObjectArg
                 peak = ((mag > 0xFFFFFFFFull ? 0xFFFFFFFFull : mag) << 32) | (uint32_t)~q.z;
             }
         }
-        // runs of one slot in consecutive lanes -> the run's head lane (k_wall_region_reduce's segmented reduction)
-        const int prev = __shfl_up(slot, 1, kWave);
-        const bool dup = lane > 0 && slot >= 0 && prev == slot;
-        const unsigned long long dmask = __ballot(dup);
-        if (dmask) {
-            const unsigned long long above = lane < kWave - 1 ? (~dmask & (~0ull << (lane + 1))) : 0ull;
-            const int tail = above ? __ffsll((long long)above) - 2 : kWave - 1;
+        const WaveRuns run = wave_runs(slot);
+        if (run.any) {
 #pragma unroll
             for (int o = 1; o < kWave; o <<= 1) {
                 const uint32_t oc = __shfl_down(pts, o, kWave), o1 = __shfl_down(smin, o, kWave), o2 = __shfl_down(smax, o, kWave),
@@ -290,7 +204,7 @@ __global__ __launch_bounds__(kWoThreads) void k_wall_object_reduce(WallObjectArg
                 for (int c = 0; c < 8; ++c) ok[c] = __shfl_down(key[c], o, kWave);
                 const unsigned long long os = __shfl_down(sum, o, kWave), ox = __shfl_down(sx, o, kWave), oy = __shfl_down(sy, o, kWave),
                                          oz = __shfl_down(sz, o, kWave), op = __shfl_down(peak, o, kWave);
-                if (lane + o <= tail) {
+                if (run.lane + o <= run.tail) {
                     pts += oc; sum += os; sx += ox; sy += oy; sz += oz;
                     smin = smin > o1 ? smin : o1; smax = smax > o2 ? smax : o2;
                     kmin = kmin > o3 ? kmin : o3; kmax = kmax > o4 ? kmax : o4;
@@ -301,7 +215,7 @@ __global__ __launch_bounds__(kWoThreads) void k_wall_object_reduce(WallObjectArg
                 }
             }
         }
-        if (slot >= 0 && !dup) {
+        if (slot >= 0 && !run.dup) {
             WallObjectAcc *r = &a.acc[slot];
             atomicAdd(&r->points, (unsigned long long)pts);
             atomicAdd(&r->sum_delta, sum);
@@ -325,10 +239,10 @@ __global__ __launch_bounds__(kWoThreads) void k_wall_object_reduce(WallObjectArg
 // the bits of ordered_to_float(o)
 __device__ __forceinline__ uint32_t wo_unordered(uint32_t o) { return (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o; }
 
-__global__ __launch_bounds__(kWoThreads) void k_wall_object_select(WallObjectArgs a)
+__global__ __launch_bounds__(kCcThreads) void k_wall_object_select(WallObjectArgs a)
 {
     uint32_t small = 0u, in_object = 0u;
-    for (uint32_t s = blockIdx.x * kWoThreads + threadIdx.x; s < a.ncomp; s += gridDim.x * kWoThreads) {
+    for (uint32_t s = blockIdx.x * kCcThreads + threadIdx.x; s < a.ncomp; s += gridDim.x * kCcThreads) {
         const WallObjectAcc *r = &a.acc[s];
         const unsigned long long pts = r->points;
         if (pts < a.min_points) {
@@ -377,41 +291,35 @@ __global__ __launch_bounds__(kWoThreads) void k_wall_object_select(WallObjectArg
 
 // ---- 9. rows ----
 
-__global__ __launch_bounds__(kWoThreads) void k_wall_object_rows(WallObjectArgs a)
+__global__ __launch_bounds__(kCcThreads) void k_wall_object_rows(WallObjectArgs a)
 {
-    for (uint64_t i = (uint64_t)blockIdx.x * kWoThreads + threadIdx.x; i < a.n_rows; i += (uint64_t)gridDim.x * kWoThreads) {
+    for (uint64_t i = (uint64_t)blockIdx.x * kCcThreads + threadIdx.x; i < a.n_rows; i += (uint64_t)gridDim.x * kCcThreads) {
         uint4 p, q;
         long long dq;
         uint32_t j, k;
         const uint32_t b = wo_decode(a, i, p, q, dq, j, k);
-        const uint32_t r = b < kWallObjectOutside ? a.parent[b] : kWallObjectNone;
-        a.object_of_row[i] = r != kWallObjectNone ? a.pos[a.slot[r]] : -1;
+        const uint32_t r = b < kWallObjectOutside ? a.parent[b] : kCcNone;
+        a.object_of_row[i] = r != kCcNone ? a.pos[a.slot[r]] : -1;
     }
-}
-
-static uint32_t wo_blocks(uint64_t n)
-{
-    const uint64_t b = (n + kWoThreads - 1) / kWoThreads;
-    return (uint32_t)(b < 1 ? 1 : (b > kWoMaxBlocks ? kWoMaxBlocks : b));
 }
 
 void launch_wall_object_label(const WallObjectArgs &a, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_wall_object_bin, dim3(wo_blocks(a.n_rows)), dim3(kWoThreads), 0, s, a);
-    hipLaunchKernelGGL(k_wall_object_tiles, dim3(a.tiles_s * a.tiles_k), dim3(kWoThreads), 0, s, a);
-    hipLaunchKernelGGL(k_wall_object_seams, dim3(wo_blocks(2u * ((uint64_t)a.tiles_k * a.nJ + (uint64_t)(a.tiles_s - 1u) * a.NK))),
-                       dim3(kWoThreads), 0, s, a);
-    hipLaunchKernelGGL(k_wall_object_flatten, dim3(wo_blocks(2ull * a.NB)), dim3(kWoThreads), 0, s, a);
+    hipLaunchKernelGGL(k_wall_object_bin, dim3(cc_blocks(a.n_rows)), dim3(kCcThreads), 0, s, a);
+    hipLaunchKernelGGL(k_wall_object_tiles, dim3(a.tiles_s * a.tiles_k), dim3(kCcThreads), 0, s, a);
+    hipLaunchKernelGGL(k_wall_object_seams, dim3(cc_blocks(2u * cc_seam_count(a.nJ, a.NK, a.tiles_s, a.tiles_k))), dim3(kCcThreads),
+                       0, s, a);
+    hipLaunchKernelGGL(k_wall_object_flatten, dim3(cc_blocks(2ull * a.NB)), dim3(kCcThreads), 0, s, a);
 }
 void launch_wall_object_reduce(const WallObjectArgs &a, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_wall_object_blocks, dim3(wo_blocks(2ull * a.NB)), dim3(kWoThreads), 0, s, a);
-    hipLaunchKernelGGL(k_wall_object_reduce, dim3(wo_blocks(a.n_rows)), dim3(kWoThreads), 0, s, a);
-    hipLaunchKernelGGL(k_wall_object_select, dim3(wo_blocks(a.ncomp)), dim3(kWoThreads), 0, s, a);
+    hipLaunchKernelGGL(k_wall_object_blocks, dim3(cc_blocks(2ull * a.NB)), dim3(kCcThreads), 0, s, a);
+    hipLaunchKernelGGL(k_wall_object_reduce, dim3(cc_blocks(a.n_rows)), dim3(kCcThreads), 0, s, a);
+    hipLaunchKernelGGL(k_wall_object_select, dim3(cc_blocks(a.ncomp)), dim3(kCcThreads), 0, s, a);
 }
 void launch_wall_object_rows(const WallObjectArgs &a, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_wall_object_rows, dim3(wo_blocks(a.n_rows)), dim3(kWoThreads), 0, s, a);
+    hipLaunchKernelGGL(k_wall_object_rows, dim3(cc_blocks(a.n_rows)), dim3(kCcThreads), 0, s, a);
 }
 
 }  // namespace gm
