@@ -309,6 +309,7 @@ def load():
         "gm_host_register": (C.c_int, [vp, vp, C.c_size_t]),
         "gm_host_unregister": (C.c_int, [vp, vp]),
         "gm_abi_version": (u32, []),
+        "gm_debug_live_buffers": (C.c_longlong, []),
         "gm_status_string": (C.c_char_p, [C.c_int]),
         "gm_last_error": (C.c_char_p, [vp]),
         "gm_process_frame": (C.c_int, [vp, cloudp, resp]),

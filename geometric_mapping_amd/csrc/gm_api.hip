@@ -32,27 +32,6 @@ gm_status fail(gm_ctx *ctx, gm_status st, const char *msg)
     return st;
 }
 
-template <class T>
-hipError_t dmalloc(T *&p, size_t count)
-{
-    p = nullptr;
-    return hipMalloc((void **)&p, (count ? count : 1) * sizeof(T));
-}
-
-void free_slot_buffers(Slot &sl)
-{
-    hipFree(sl.d_raw); hipFree(sl.crop4); hipFree(sl.keys_a); hipFree(sl.keys_b); hipFree(sl.vals_a);
-    hipFree(sl.vals_b); hipFree(sl.spts4); hipFree(sl.normals4); hipFree(sl.counts); hipFree(sl.valid4);
-    hipFree(sl.vnorm4); hipFree(sl.tiles); hipFree(sl.row_bounds); hipFree(sl.blk); hipFree(sl.tile_partials); hipFree(sl.sort.totals); hipFree(sl.sort.rec);
-    hipFree(sl.sort.ticket); hipFree(sl.tile_rec); hipFree(sl.seg_start);
-    hipFree(sl.vox4); hipFree(sl.vox_nn); hipFree(sl.labels); hipFree(sl.inl_mask);
-    if (sl.h_raw) hipHostFree(sl.h_raw);
-    sl.d_raw = nullptr; sl.h_raw = nullptr; sl.crop4 = nullptr; sl.keys_a = sl.keys_b = sl.vals_a = sl.vals_b = nullptr;
-    sl.spts4 = sl.normals4 = sl.valid4 = sl.vnorm4 = sl.vox4 = nullptr; sl.counts = nullptr; sl.tiles = nullptr; sl.row_bounds = nullptr;
-    sl.blk = nullptr; sl.tile_partials = nullptr; sl.sort = SortScratch{}; sl.tile_rec = nullptr; sl.tile_rec_words = 0; sl.seg_start = nullptr; sl.vox_nn = nullptr; sl.labels = nullptr; sl.inl_mask = nullptr;
-    sl.cap = 0; sl.raw_cap = 0; sl.tiles_cap = 0; sl.tile_seg = 0;
-}
-
 // search grid over the crop box: cell edge >= 1.001 r in y and z (<= 1024 cells per axis), x binned
 // `fine` times finer (a power of two chosen so that the cell key still fits 31 bits)
 // The neighbour predicate of k_normals needs one ulp of r^2, scaled by a power of two <= 2^126, to reach 1: true for
@@ -193,43 +172,43 @@ int voxel_key_bits(double lo, double hi, double leaf)
     return bits_for((uint64_t)prod);
 }
 
+// Every device buffer of a slot grows through reserve(n, gen): gen counts the blocks that moved, and enqueue_frame's graph
+// key holds it, so a launch chain captured against the old addresses is never replayed.  Callers synchronise the slot's
+// stream before the first reserve that may free a block a launch on it could still use.
 gm_status ensure_capacity(gm_ctx *ctx, Slot &sl, uint32_t n, size_t raw_bytes, bool need_raw)
 {
+    uint32_t *gen = &sl.alloc_gen;
     if (need_raw && raw_bytes > sl.raw_cap) {
-        if (sl.h_raw) hipHostFree(sl.h_raw);
-        hipFree(sl.d_raw);
-        sl.h_raw = nullptr; sl.d_raw = nullptr;
-        size_t cap = raw_bytes + raw_bytes / 4 + 4096;
-        GM_HIP(ctx, hipHostMalloc((void **)&sl.h_raw, cap, hipHostMallocDefault));
-        GM_HIP(ctx, hipMalloc((void **)&sl.d_raw, cap));
+        // (not counted in gen: a capture reads the staging through the row address, which is in the graph key itself)
+        const size_t cap = raw_bytes + raw_bytes / 4 + 4096;
+        sl.raw_cap = 0;
+        GM_HIP(ctx, sl.h_raw.reserve(cap));
+        GM_HIP(ctx, sl.d_raw.reserve(cap));
         sl.raw_cap = cap;
     }
     if (n <= sl.cap) return GM_OK;
     GM_HIP(ctx, hipStreamSynchronize(sl.stream));
-    uint8_t *h_raw = sl.h_raw, *d_raw = sl.d_raw; size_t raw_cap = sl.raw_cap;
-    sl.h_raw = nullptr; sl.d_raw = nullptr;
-    free_slot_buffers(sl);
-    sl.h_raw = h_raw; sl.d_raw = d_raw; sl.raw_cap = raw_cap;
     uint32_t cap = n + n / 4 + 1024;
     if (cap < ctx->cfg.max_points) cap = ctx->cfg.max_points;
     cap = (cap + 3u) & ~3u;  // whole 16 B groups of keys (k_rows_and_tiles reads them as uint4)
-    GM_HIP(ctx, dmalloc(sl.crop4, cap));
-    GM_HIP(ctx, dmalloc(sl.keys_a, cap)); GM_HIP(ctx, dmalloc(sl.keys_b, cap));
-    GM_HIP(ctx, dmalloc(sl.vals_a, cap)); GM_HIP(ctx, dmalloc(sl.vals_b, cap));
-    GM_HIP(ctx, dmalloc(sl.spts4, cap)); GM_HIP(ctx, dmalloc(sl.normals4, cap));
-    GM_HIP(ctx, dmalloc(sl.counts, cap));
-    GM_HIP(ctx, dmalloc(sl.valid4, cap)); GM_HIP(ctx, dmalloc(sl.vnorm4, cap));
-    GM_HIP(ctx, dmalloc(sl.seg_start, cap)); GM_HIP(ctx, dmalloc(sl.vox4, cap));
-    GM_HIP(ctx, dmalloc(sl.vox_nn, cap)); GM_HIP(ctx, dmalloc(sl.labels, cap)); GM_HIP(ctx, dmalloc(sl.inl_mask, cap));
+    sl.cap = 0;              // until every array is in place: a failed growth starts over on the next call
+    GM_HIP(ctx, sl.crop4.reserve(cap, gen));
+    GM_HIP(ctx, sl.keys_a.reserve(cap, gen)); GM_HIP(ctx, sl.keys_b.reserve(cap, gen));
+    GM_HIP(ctx, sl.vals_a.reserve(cap, gen)); GM_HIP(ctx, sl.vals_b.reserve(cap, gen));
+    GM_HIP(ctx, sl.spts4.reserve(cap, gen)); GM_HIP(ctx, sl.normals4.reserve(cap, gen));
+    GM_HIP(ctx, sl.counts.reserve(cap, gen));
+    GM_HIP(ctx, sl.valid4.reserve(cap, gen)); GM_HIP(ctx, sl.vnorm4.reserve(cap, gen));
+    GM_HIP(ctx, sl.seg_start.reserve(cap, gen)); GM_HIP(ctx, sl.vox4.reserve(cap, gen));
+    GM_HIP(ctx, sl.vox_nn.reserve(cap, gen)); GM_HIP(ctx, sl.labels.reserve(cap, gen)); GM_HIP(ctx, sl.inl_mask.reserve(cap, gen));
     // tile list: kTileListClasses - 1 segments for the tiles with an x extent (>= 2 points each: none of them can hold more
     // than cap / 2 tiles) + one that holds every tile a frame can have (>= 1 point each).  No list can overflow.
     sl.tiles_cap = cap + 2u;
     sl.tile_seg = cap / 2u + 2u;
-    GM_HIP(ctx, dmalloc(sl.tiles, (size_t)(kTileListClasses - 1) * sl.tile_seg + sl.tiles_cap));
-    GM_HIP(ctx, dmalloc(sl.row_bounds, (size_t)1024 * 1024));  // make_grid caps every axis at 1024 cells
+    GM_HIP(ctx, sl.tiles.reserve((size_t)(kTileListClasses - 1) * sl.tile_seg + sl.tiles_cap, gen));
+    GM_HIP(ctx, sl.row_bounds.reserve((size_t)1024 * 1024, gen));  // make_grid caps every axis at 1024 cells (allocated once)
     sl.blk_cap = compact_records(cap > kVoxDenseMaxCells ? cap : kVoxDenseMaxCells) + 1;
-    GM_HIP(ctx, dmalloc(sl.tile_partials, (size_t)compact_blocks(cap) * 6));
-    GM_HIP(ctx, dmalloc(sl.blk, (size_t)sl.blk_cap + 1));  // + the ticket word
+    GM_HIP(ctx, sl.tile_partials.reserve((size_t)compact_blocks(cap) * 6, gen));
+    GM_HIP(ctx, sl.blk.reserve((size_t)sl.blk_cap + 1, gen));  // + the ticket word
     GM_HIP(ctx, hipMemsetAsync(sl.blk, 0, sizeof(unsigned long long) * ((size_t)sl.blk_cap + 1), sl.stream));
     {
         // tests only: start the chained scans' epoch counter just below its wrap (tests/test_gpu_parity.py)
@@ -237,16 +216,15 @@ gm_status ensure_capacity(gm_ctx *ctx, Slot &sl, uint32_t n, size_t raw_bytes, b
         sl.scan_epoch = e ? (uint32_t)strtoul(e, nullptr, 0) : 0u;
     }
     // radix sort scratch: digit totals, the passes' record array (both cleared per sort) and the ticket words (zeroed once)
-    GM_HIP(ctx, dmalloc(sl.sort.totals, radix_totals_bytes() / sizeof(uint32_t)));
+    GM_HIP(ctx, sl.sort.totals.reserve(radix_totals_bytes() / sizeof(uint32_t), gen));
     sl.sort.rec_words = (radix_record_words_max(cap) + 1u) & ~(size_t)1u;
-    GM_HIP(ctx, dmalloc(sl.sort.rec, sl.sort.rec_words));
-    GM_HIP(ctx, dmalloc(sl.sort.ticket, 4));
+    GM_HIP(ctx, sl.sort.rec.reserve(sl.sort.rec_words, gen));
+    GM_HIP(ctx, sl.sort.ticket.reserve(4, gen));
     GM_HIP(ctx, hipMemsetAsync(sl.sort.ticket, 0, 16, sl.stream));
     sl.tile_rec_words = (size_t)(tile_cutter_blocks(cap) + 1) * (size_t)kTileListClasses;
-    GM_HIP(ctx, dmalloc(sl.tile_rec, sl.tile_rec_words));
+    GM_HIP(ctx, sl.tile_rec.reserve(sl.tile_rec_words, gen));
     GM_HIP(ctx, hipMemsetAsync(sl.tile_rec, 0, sizeof(unsigned long long) * sl.tile_rec_words, sl.stream));
     sl.cap = cap;
-    ++sl.alloc_gen;
     return GM_OK;
 }
 
@@ -480,13 +458,9 @@ gm_status enqueue_frame(gm_ctx *ctx, Slot &sl, const gm_cloud *cloud, bool block
         vd = make_vox_dense(lo, hi, cf.voxelGridLeafSize, sl.cap, ctx->own_lo, ctx->own_hi);
     if (vd.enabled) {
         const uint32_t cells = (uint32_t)vd.dim * vd.dim * vd.dim;
-        if (cells > sl.vox_table_cap) {
+        if (cells > sl.vox_table.cap) {
             GM_HIP(ctx, hipStreamSynchronize(s));
-            hipFree(sl.vox_table);
-            sl.vox_table = nullptr;
-            GM_HIP(ctx, dmalloc(sl.vox_table, cells));
-            sl.vox_table_cap = cells;
-            ++sl.alloc_gen;
+            GM_HIP(ctx, sl.vox_table.reserve(cells, &sl.alloc_gen));
         }
     }
     // GM_CFG_GRAPH: the launch chain is captured once and replayed for every frame whose bucketed size, row layout,
@@ -657,33 +631,26 @@ gm_status gm_ensure_ext(gm_ctx *ctx, Slot &sl, uint32_t H)
     if (H == 0 || H > kMaxHypotheses) return fail(ctx, GM_ERR_INVALID_ARG, "ransac_hypotheses must be in [1, 8192]");
     if (H <= sl.ext_H && sl.cap <= sl.ext_cap) return GM_OK;
     GM_HIP(ctx, hipStreamSynchronize(sl.stream));
-    hipFree(sl.hyp_plane); hipFree(sl.hyp_cyl); hipFree(sl.band); hipFree(sl.score_partial); hipFree(sl.cnt_plane);
-    hipFree(sl.cnt_cyl); hipFree(sl.best_plane); hipFree(sl.best_cyl); hipFree(sl.mom_partial); hipFree(sl.mom_plane);
-    hipFree(sl.mom_cyl); hipFree(sl.nn_best); hipFree(sl.vox_nrm4);
-    hipFree(sl.fit_partial); hipFree(sl.fit_ticket); hipFree(sl.fit_work); hipFree(sl.fit_init); hipFree(sl.fit_stage);
-    // (a failed allocation below must not leave dangling pointers for gm_destroy to free again)
-    sl.hyp_plane = sl.hyp_cyl = nullptr; sl.band = nullptr; sl.score_partial = nullptr; sl.cnt_plane = sl.cnt_cyl = nullptr;
-    sl.best_plane = sl.best_cyl = nullptr; sl.mom_partial = sl.mom_plane = sl.mom_cyl = nullptr; sl.nn_best = nullptr; sl.vox_nrm4 = nullptr;
-    sl.fit_partial = nullptr; sl.fit_ticket = nullptr; sl.fit_work = nullptr; sl.fit_init = nullptr; sl.fit_stage = nullptr;
     const uint32_t HH = H > sl.ext_H ? H : sl.ext_H;
-    sl.ext_H = 0; sl.ext_cap = 0;
-    GM_HIP(ctx, dmalloc(sl.hyp_plane, (size_t)HH * 8)); GM_HIP(ctx, dmalloc(sl.hyp_cyl, (size_t)HH * 8));
-    GM_HIP(ctx, dmalloc(sl.band, HH));
-    GM_HIP(ctx, dmalloc(sl.score_partial, (size_t)4096));  // pre-selection scratch (k_ransac.hip kPre*: 577 words, replicated counters at 1024)
-    GM_HIP(ctx, dmalloc(sl.cnt_plane, HH)); GM_HIP(ctx, dmalloc(sl.cnt_cyl, HH));
-    GM_HIP(ctx, dmalloc(sl.best_plane, 2)); GM_HIP(ctx, dmalloc(sl.best_cyl, 2));
-    GM_HIP(ctx, dmalloc(sl.mom_partial, (size_t)kScatterBlocks * 16 * 2));  // [model][row][16]
-    GM_HIP(ctx, dmalloc(sl.mom_plane, 16)); GM_HIP(ctx, dmalloc(sl.mom_cyl, 16));
-    GM_HIP(ctx, dmalloc(sl.nn_best, sl.cap));
-    GM_HIP(ctx, dmalloc(sl.vox_nrm4, sl.cap));
-    GM_HIP(ctx, dmalloc(sl.fit_partial, (size_t)kFitBlocks * 24)); GM_HIP(ctx, dmalloc(sl.fit_ticket, 1));
-    GM_HIP(ctx, dmalloc(sl.fit_work, 1)); GM_HIP(ctx, dmalloc(sl.fit_init, 8)); GM_HIP(ctx, dmalloc(sl.fit_stage, 1));
+    const uint32_t pts = sl.cap ? sl.cap : 1u;   // (may run before the slot has seen a frame: the scratch is still non-null)
+    uint32_t *gen = &sl.alloc_gen;
+    sl.ext_H = 0; sl.ext_cap = 0;   // until every array is in place: a failed growth starts over on the next call
+    GM_HIP(ctx, sl.hyp_plane.reserve((size_t)HH * 8, gen)); GM_HIP(ctx, sl.hyp_cyl.reserve((size_t)HH * 8, gen));
+    GM_HIP(ctx, sl.band.reserve(HH, gen));
+    GM_HIP(ctx, sl.score_partial.reserve(4096, gen));  // pre-selection scratch (k_ransac.hip kPre*: 577 words, replicated counters at 1024)
+    GM_HIP(ctx, sl.cnt_plane.reserve(HH, gen)); GM_HIP(ctx, sl.cnt_cyl.reserve(HH, gen));
+    GM_HIP(ctx, sl.best_plane.reserve(2, gen)); GM_HIP(ctx, sl.best_cyl.reserve(2, gen));
+    GM_HIP(ctx, sl.mom_partial.reserve((size_t)kScatterBlocks * 16 * 2, gen));  // [model][row][16]
+    GM_HIP(ctx, sl.mom_plane.reserve(16, gen)); GM_HIP(ctx, sl.mom_cyl.reserve(16, gen));
+    GM_HIP(ctx, sl.nn_best.reserve(pts, gen));
+    GM_HIP(ctx, sl.vox_nrm4.reserve(pts, gen));
+    GM_HIP(ctx, sl.fit_partial.reserve((size_t)kFitBlocks * 24, gen)); GM_HIP(ctx, sl.fit_ticket.reserve(1, gen));
+    GM_HIP(ctx, sl.fit_work.reserve(1, gen)); GM_HIP(ctx, sl.fit_init.reserve(8, gen)); GM_HIP(ctx, sl.fit_stage.reserve(1, gen));
     GM_HIP(ctx, hipMemset(sl.fit_ticket, 0, sizeof(uint32_t)));   // the passes' last block resets it after every launch
     GM_HIP(ctx, hipMemset(sl.score_partial, 0, sizeof(uint32_t) * 4096));  // (holds the scoring launches' done-counter)
     GM_HIP(ctx, hipMemset(sl.best_plane, 0xFF, 8));
     GM_HIP(ctx, hipMemset(sl.best_cyl, 0xFF, 8));
     sl.ext_H = HH; sl.ext_cap = sl.cap;
-    ++sl.alloc_gen;
     return GM_OK;
 }
 
@@ -691,29 +658,24 @@ gm_status gm_ensure_ext(gm_ctx *ctx, Slot &sl, uint32_t H)
 // cell table is zeroed here and kept zero between launches by the map's last block.
 gm_status gm_ensure_surface(gm_ctx *ctx, Slot &sl)
 {
-    if (!sl.surf_table) {
+    uint32_t *gen = &sl.alloc_gen;
+    if (!sl.surf_table) {   // (the table comes last: until it is there, a failed first use starts over on the next call)
         GM_HIP(ctx, hipStreamSynchronize(sl.stream));
-        hipFree(sl.surf_prm); hipFree(sl.surf_cells); hipFree(sl.surf_info); hipFree(sl.surf_fit);
-        sl.surf_prm = nullptr; sl.surf_cells = nullptr; sl.surf_info = nullptr; sl.surf_fit = nullptr;
-        GM_HIP(ctx, dmalloc(sl.surf_prm, 2)); GM_HIP(ctx, dmalloc(sl.surf_cells, GM_SURF_MAX_CELLS));
-        GM_HIP(ctx, dmalloc(sl.surf_info, 1)); GM_HIP(ctx, dmalloc(sl.surf_fit, 1));
+        GM_HIP(ctx, sl.surf_prm.reserve(2, gen)); GM_HIP(ctx, sl.surf_cells.reserve(GM_SURF_MAX_CELLS, gen));
+        GM_HIP(ctx, sl.surf_info.reserve(1, gen)); GM_HIP(ctx, sl.surf_fit.reserve(1, gen));
         GM_HIP(ctx, hipMemsetAsync(sl.surf_info, 0, sizeof(gm_surface_info), sl.stream));
         const SurfParams prm[2] = {surface_device_params(ctx->surf), surface_device_params(ctx->surf)};
         GM_HIP(ctx, hipMemcpyAsync(sl.surf_prm, prm, sizeof(prm), hipMemcpyHostToDevice, sl.stream));
-        uint8_t *table = nullptr;
-        GM_HIP(ctx, dmalloc(table, surface_table_bytes()));
-        sl.surf_table = table;
+        GM_HIP(ctx, sl.surf_table.reserve(surface_table_bytes(), gen));
         GM_HIP(ctx, hipMemsetAsync(sl.surf_table, 0, surface_table_bytes(), sl.stream));
         GM_HIP(ctx, hipStreamSynchronize(sl.stream));
-        ++sl.alloc_gen;
     }
     if (sl.surf_cap < sl.cap || !sl.surf_res) {
         GM_HIP(ctx, hipStreamSynchronize(sl.stream));
-        hipFree(sl.surf_res); hipFree(sl.surf_cell);
-        sl.surf_res = nullptr; sl.surf_cell = nullptr; sl.surf_cap = 0;
-        GM_HIP(ctx, dmalloc(sl.surf_res, sl.cap)); GM_HIP(ctx, dmalloc(sl.surf_cell, sl.cap));
+        const uint32_t pts = sl.cap ? sl.cap : 1u;   // (non-null also before the slot has seen a frame)
+        sl.surf_cap = 0;
+        GM_HIP(ctx, sl.surf_res.reserve(pts, gen)); GM_HIP(ctx, sl.surf_cell.reserve(pts, gen));
         sl.surf_cap = sl.cap;
-        ++sl.alloc_gen;
     }
     return GM_OK;
 }
@@ -788,6 +750,8 @@ int gm_debug_graph_captures(gm_ctx *ctx, uint32_t slot)
     if (!ctx || slot >= ctx->n_slots) return -1;
     return (int)ctx->slots[slot].graph_captures;
 }
+
+long long gm_debug_live_buffers(void) { return g_live_buffers.load(std::memory_order_relaxed); }
 
 gm_status gm_host_alloc(gm_ctx *ctx, size_t bytes, void **out)
 {
@@ -918,19 +882,20 @@ gm_status gm_create(const gm_config *cfg, gm_ctx **out)
             GM_HIP(ctx, hipEventCreate(&sl.ev_k1));
             // (the /choppedCloud copy stream is created by gm_set_cloud_output: every stream of the process takes part in
             // the runtime's mapping of streams onto hardware queues, and an idle one can push two slots onto one queue)
-            GM_HIP(ctx, dmalloc(sl.ctr, 1));
-            GM_HIP(ctx, dmalloc(sl.voxp, 1));
-            GM_HIP(ctx, dmalloc(sl.d_out, 1));
-            GM_HIP(ctx, dmalloc(sl.partials, (size_t)kScatterBlocks * 6));
-            GM_HIP(ctx, dmalloc(sl.frame_in, 8));
+            uint32_t *gen = &sl.alloc_gen;
+            GM_HIP(ctx, sl.ctr.reserve(1, gen));
+            GM_HIP(ctx, sl.voxp.reserve(1, gen));
+            GM_HIP(ctx, sl.d_out.reserve(1, gen));
+            GM_HIP(ctx, sl.partials.reserve((size_t)kScatterBlocks * 6, gen));
+            GM_HIP(ctx, sl.frame_in.reserve(8, gen));
             GM_HIP(ctx, hipMemset(sl.frame_in, 0, 32));
             if (const char *e = getenv("GM_TEST_FRAME_COUNTER")) {   // tests only: start near the replayed epochs' wrap
                 const uint32_t v = (uint32_t)strtoul(e, nullptr, 0);
                 GM_HIP(ctx, hipMemcpy(sl.frame_in + 4, &v, 4, hipMemcpyHostToDevice));
                 sl.frames_enqueued = v;
             }
-            GM_HIP(ctx, hipHostMalloc((void **)&sl.h_frame_in, 16, hipHostMallocDefault));
-            GM_HIP(ctx, hipHostMalloc((void **)&sl.h_out, sizeof(FrameOut), hipHostMallocDefault));
+            GM_HIP(ctx, sl.h_frame_in.reserve(4));
+            GM_HIP(ctx, sl.h_out.reserve(1));
             GM_HIP(ctx, hipMemset(sl.voxp, 0, sizeof(VoxelParams)));
             GM_HIP(ctx, hipMemset(sl.d_out, 0, sizeof(FrameOut)));
             memset(sl.h_out, 0, sizeof(FrameOut));
@@ -960,18 +925,7 @@ void gm_destroy(gm_ctx *ctx)
         for (uint32_t i = 0; i < ctx->n_slots; ++i) {
             Slot &sl = ctx->slots[i];
             if (sl.stream) hipStreamSynchronize(sl.stream);
-            free_slot_buffers(sl);
-            hipFree(sl.ctr); hipFree(sl.voxp); hipFree(sl.d_out); hipFree(sl.partials); hipFree(sl.vox_table);
-            hipFree(sl.frame_in);
-            if (sl.h_frame_in) hipHostFree(sl.h_frame_in);
             for (int k = 0; k < Slot::kGraphs; ++k) if (sl.graph_exec[k]) hipGraphExecDestroy(sl.graph_exec[k]);
-            hipFree(sl.hyp_plane); hipFree(sl.hyp_cyl); hipFree(sl.band); hipFree(sl.score_partial);
-            hipFree(sl.cnt_plane); hipFree(sl.cnt_cyl); hipFree(sl.best_plane); hipFree(sl.best_cyl);
-            hipFree(sl.mom_partial); hipFree(sl.mom_plane); hipFree(sl.mom_cyl); hipFree(sl.nn_best); hipFree(sl.vox_nrm4);
-            hipFree(sl.fit_partial); hipFree(sl.fit_ticket); hipFree(sl.fit_work); hipFree(sl.fit_init); hipFree(sl.fit_stage);
-            hipFree(sl.surf_prm); hipFree(sl.surf_table); hipFree(sl.surf_cells); hipFree(sl.surf_info); hipFree(sl.surf_fit);
-            hipFree(sl.surf_res); hipFree(sl.surf_cell);
-            if (sl.h_out) hipHostFree(sl.h_out);
             for (int k = 0; k <= GM_N_STAGES; ++k) if (sl.ev[k]) hipEventDestroy(sl.ev[k]);
             if (sl.ev_k0) hipEventDestroy(sl.ev_k0);
             if (sl.ev_k1) hipEventDestroy(sl.ev_k1);
@@ -981,7 +935,7 @@ void gm_destroy(gm_ctx *ctx)
             if (sl.ev_copied) hipEventDestroy(sl.ev_copied);
             if (sl.stream) hipStreamDestroy(sl.stream);
         }
-        delete[] ctx->slots;
+        delete[] ctx->slots;   // (every buffer of the slots goes here: streams drained, the context's device current)
     }
     delete ctx;
 }
@@ -1234,7 +1188,7 @@ gm_status gm_voxel_grid(gm_ctx *ctx, const float *xyz, uint32_t n, double leaf, 
     st = reset_counters(ctx, sl);
     if (st != GM_OK) return st;
     float mn = 3e38f, mx = -3e38f;
-    float4 *stage = (float4 *)sl.h_raw;
+    float4 *stage = (float4 *)sl.h_raw.p;
     for (uint32_t i = 0; i < n; ++i) {
         const float *p = xyz + 3 * (size_t)i;
         stage[i] = make_float4(p[0], p[1], p[2], 0.f);

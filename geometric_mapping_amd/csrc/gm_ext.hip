@@ -25,7 +25,7 @@ namespace {
 gm_status upload_xyz(gm_ctx *ctx, Slot &sl, const float *xyz, uint32_t n, float4 *dst)
 {
     if (!n) return GM_OK;
-    float4 *stage = (float4 *)sl.h_raw;
+    float4 *stage = (float4 *)sl.h_raw.p;
     for (uint32_t i = 0; i < n; ++i) stage[i] = make_float4(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], 0.f);
     GMX_HIP(ctx, hipMemcpyAsync(dst, stage, (size_t)n * 16, hipMemcpyHostToDevice, sl.stream));
     GMX_HIP(ctx, hipStreamSynchronize(sl.stream));  // staging is reused by the caller right away
@@ -62,11 +62,11 @@ gm_status score(gm_ctx *ctx, int model, const float *xyz, uint32_t n, const uint
     if (st != GM_OK) return st;
     // caller rows (4 or 7 floats) -> internal rows of 8
     const int w = model == 0 ? 4 : 7;
-    float *stage = (float *)sl.h_raw;  // capacity >= n*16 bytes; H*32 must fit too
+    float *stage = (float *)sl.h_raw.p;  // capacity >= n*16 bytes; H*32 must fit too
     if ((size_t)H * 32 > sl.raw_cap) {
         st = gm_ensure_capacity(ctx, sl, n, (size_t)H * 32, true);
         if (st != GM_OK) return st;
-        stage = (float *)sl.h_raw;
+        stage = (float *)sl.h_raw.p;
     }
     memset(stage, 0, (size_t)H * 32);
     for (uint32_t h = 0; h < H; ++h)
@@ -150,7 +150,7 @@ gm_status gm_plane_hypotheses(gm_ctx *ctx, const float *xyz, uint32_t n, const u
         st = gm_ensure_capacity(ctx, sl, n, (size_t)H * 32, true);
         if (st != GM_OK) return st;
     }
-    float *stage = (float *)sl.h_raw;
+    float *stage = (float *)sl.h_raw.p;
     GMX_HIP(ctx, hipMemcpyAsync(stage, sl.hyp_plane, (size_t)H * 32, hipMemcpyDeviceToHost, sl.stream));
     GMX_HIP(ctx, hipStreamSynchronize(sl.stream));
     GMX_HIP(ctx, hipGetLastError());
@@ -179,7 +179,7 @@ gm_status gm_cylinder_hypotheses(gm_ctx *ctx, const float *xyz, const float *nxy
         st = gm_ensure_capacity(ctx, sl, n, (size_t)H * 32, true);
         if (st != GM_OK) return st;
     }
-    float *stage = (float *)sl.h_raw;
+    float *stage = (float *)sl.h_raw.p;
     GMX_HIP(ctx, hipMemcpyAsync(stage, sl.hyp_cyl, (size_t)H * 32, hipMemcpyDeviceToHost, sl.stream));
     GMX_HIP(ctx, hipStreamSynchronize(sl.stream));
     GMX_HIP(ctx, hipGetLastError());

@@ -156,14 +156,13 @@ struct gm_group {
     bool dead = false;               // a collective failed half-way: the ranks' streams can no longer be trusted
     std::vector<int> devices;
     std::vector<gm_ctx *> ctx;
-    std::vector<double *> d_rec;     // [n] device: this rank's record
-    std::vector<double *> d_all;     // [n] device: every rank's record (the all-gather's receive buffer)
+    std::vector<DevArray<double>> d_rec;   // [n] device: this rank's record
+    std::vector<DevArray<double>> d_all;   // [n] device: every rank's record (the all-gather's receive buffer)
     std::vector<hipEvent_t> ev;      // loopback: "record packed" per rank
-    double *h_all = nullptr;         // pinned host copy of rank 0's gathered buffer
+    HostArray<double> h_all;         // pinned host copy of rank 0's gathered buffer
     std::vector<ncclComm_t> comms;
     Rccl rccl;
-    std::vector<uint8_t *> prow;     // per rank: page-locked row buffer of the slab cut (grow-only)
-    std::vector<size_t> prow_cap;
+    std::vector<HostArray<uint8_t>> prow;   // per rank: page-locked row buffer of the slab cut (grow-only)
     std::vector<std::vector<uint32_t>> row_ids;  // per-rank: input row of every row sent
     std::vector<float> xs;           // x of every input row (scratch of the cut)
     std::vector<double> edges;
@@ -177,17 +176,17 @@ struct gm_group {
     bool vox_nrm_valid = false;
     // cylinder regression of the sharded frame (gm_group_fit_cylinder): per-rank device buffers, allocated on first use
     struct FitRank {
-        double *partial = nullptr;        // [kFitBlocks][24] the rank's partial rows of a pass
-        uint32_t *ticket = nullptr;       // last-block ticket (0 between launches)
-        CylFitWork *work = nullptr;       // the model between the passes (every rank writes the same bits)
-        gm_cylinder_fit *fit = nullptr;   // the rank's copy of the result record
-        float *rows8 = nullptr;           // [0..8) starting row, [8..16) published plane row
-        uint32_t *plane_best = nullptr;   // 0: the plane row labels; 0xFFFFFFFF: no plane, every label 0
-        double *row = nullptr;            // [4 passes][24] the rank's reduced row of each pass (exchange send buffer)
-        double *rows = nullptr;           // [4 passes][n][24] every rank's row of each pass (receive buffer)
+        DevArray<double> partial;         // [kFitBlocks][24] the rank's partial rows of a pass
+        DevArray<uint32_t> ticket;        // last-block ticket (0 between launches)
+        DevArray<CylFitWork> work;        // the model between the passes (every rank writes the same bits)
+        DevArray<gm_cylinder_fit> fit;    // the rank's copy of the result record
+        DevArray<float> rows8;            // [0..8) starting row, [8..16) published plane row
+        DevArray<uint32_t> plane_best;    // 0: the plane row labels; 0xFFFFFFFF: no plane, every label 0
+        DevArray<double> row;             // [4 passes][24] the rank's reduced row of each pass (exchange send buffer)
+        DevArray<double> rows;            // [4 passes][n][24] every rank's row of each pass (receive buffer; allocated last)
     };
     std::vector<FitRank> fitr;
-    gm_cylinder_fit *h_fit = nullptr;     // pinned: [n] the ranks' result records
+    HostArray<gm_cylinder_fit> h_fit;     // pinned: [n] the ranks' result records
     gm_cylinder_fit last_fit = {};
     bool have_fit = false;                // last_fit belongs to the sharded frame in `last`
     // streaming: frames in flight in submission order
@@ -310,13 +309,10 @@ gm_status cut_rows(gm_group &G, const gm_cloud *cloud, CutPlan &plan, std::vecto
         for (uint32_t t = 0; t < T; ++t) { off[t][r] = total[r]; total[r] += cnt[t][r]; }
     for (uint32_t r = 0; r < R; ++r) {
         const size_t need = (size_t)total[r] * step;
-        if (need > G.prow_cap[r]) {
-            if (G.prow[r]) hipHostFree(G.prow[r]);
-            G.prow[r] = nullptr; G.prow_cap[r] = 0;
+        if (need > G.prow[r].cap) {
             const size_t cap = need + need / 8 + 4096;
-            if (hipSetDevice(G.devices[r]) != hipSuccess || hipHostMalloc((void **)&G.prow[r], cap, hipHostMallocDefault) != hipSuccess)
+            if (hipSetDevice(G.devices[r]) != hipSuccess || G.prow[r].reserve(cap) != hipSuccess)
                 return gfail(&G, GM_ERR_OOM, "gm_group: page-locked row buffer allocation failed");
-            G.prow_cap[r] = cap;
         }
         G.row_ids[r].resize(total[r]);
     }
@@ -443,19 +439,14 @@ void gm_group_destroy(gm_group *grp)
     for (uint32_t r = 0; r < grp->n; ++r) {
         if (r < grp->ctx.size() && grp->ctx[r]) hipSetDevice(grp->devices[r]);
         if (r < grp->comms.size() && grp->comms[r] && grp->rccl.CommDestroy) grp->rccl.CommDestroy(grp->comms[r]);
-        if (r < grp->d_rec.size()) hipFree(grp->d_rec[r]);
-        if (r < grp->d_all.size()) hipFree(grp->d_all[r]);
         if (r < grp->ev.size() && grp->ev[r]) hipEventDestroy(grp->ev[r]);
         if (r < grp->ctx.size() && grp->ctx[r]) gm_destroy(grp->ctx[r]);   // (drains the rank's streams first)
-        if (r < grp->prow.size() && grp->prow[r]) hipHostFree(grp->prow[r]);
-        if (r < grp->fitr.size()) {
-            const gm_group::FitRank &f = grp->fitr[r];
-            hipFree(f.partial); hipFree(f.ticket); hipFree(f.work); hipFree(f.fit); hipFree(f.rows8); hipFree(f.plane_best);
-            hipFree(f.row); hipFree(f.rows);
-        }
+        // the rank's buffers go here, with its device current (not when the vectors are destroyed)
+        if (r < grp->d_rec.size()) grp->d_rec[r].release();
+        if (r < grp->d_all.size()) grp->d_all[r].release();
+        if (r < grp->prow.size()) grp->prow[r].release();
+        if (r < grp->fitr.size()) gm_group::FitRank(std::move(grp->fitr[r]));   // (a temporary that takes the blocks and dies here)
     }
-    if (grp->h_all) hipHostFree(grp->h_all);
-    if (grp->h_fit) hipHostFree(grp->h_fit);
     delete grp;
 }
 
@@ -476,9 +467,9 @@ gm_status gm_group_create(const gm_config *cfg, const int32_t *devices, uint32_t
         return gfail(nullptr, GM_ERR_INVALID_ARG, "gm_group_create: a device is listed twice (pass GM_GROUP_LOOPBACK to allow it)");
     }
     g->loopback = repeats;
-    g->ctx.assign(n_ranks, nullptr); g->d_rec.assign(n_ranks, nullptr); g->d_all.assign(n_ranks, nullptr);
+    g->ctx.assign(n_ranks, nullptr); g->d_rec.resize(n_ranks); g->d_all.resize(n_ranks);
     g->ev.assign(n_ranks, nullptr); g->comms.assign(n_ranks, nullptr);
-    g->prow.assign(n_ranks, nullptr); g->prow_cap.assign(n_ranks, 0); g->row_ids.resize(n_ranks);
+    g->prow.resize(n_ranks); g->row_ids.resize(n_ranks);
     g->next_slot.assign(n_ranks, 0u);
     auto bail = [&](gm_status st, const std::string &msg) { g_group_create_err = msg; gm_group_destroy(g); return st; };
     for (uint32_t r = 0; r < n_ranks; ++r) {
@@ -487,12 +478,12 @@ gm_status gm_group_create(const gm_config *cfg, const int32_t *devices, uint32_t
         c.ransac_seed = cfg->ransac_seed + r;   // ranks draw different hypotheses: more candidates for the vote
         const gm_status st = gm_create(&c, &g->ctx[r]);
         if (st != GM_OK) return bail(st, std::string("gm_group_create: rank ") + std::to_string(r) + ": " + gm_last_error(nullptr));
-        if (hipSetDevice(devices[r]) != hipSuccess || hipMalloc((void **)&g->d_rec[r], sizeof(double) * kRecLen) != hipSuccess ||
-            hipMalloc((void **)&g->d_all[r], sizeof(double) * kRecLen * n_ranks) != hipSuccess ||
+        if (hipSetDevice(devices[r]) != hipSuccess || g->d_rec[r].reserve(kRecLen) != hipSuccess ||
+            g->d_all[r].reserve((size_t)kRecLen * n_ranks) != hipSuccess ||
             hipEventCreateWithFlags(&g->ev[r], hipEventDisableTiming) != hipSuccess)
             return bail(GM_ERR_DEVICE, "gm_group_create: device allocation failed");
     }
-    if (hipHostMalloc((void **)&g->h_all, sizeof(double) * kRecLen * n_ranks, hipHostMallocDefault) != hipSuccess)
+    if (g->h_all.reserve((size_t)kRecLen * n_ranks) != hipSuccess)
         return bail(GM_ERR_OOM, "gm_group_create: hipHostMalloc failed");
     if (!g->loopback) {
         std::string e;
@@ -862,21 +853,18 @@ gm_status gm_group_fit_cylinder(gm_group *grp, const float init7[7], gm_cylinder
         gm_group::FitRank &f = G.fitr[r];
         if (f.rows) continue;
         if (hipSetDevice(G.devices[r]) != hipSuccess) return gfail(grp, GM_ERR_DEVICE, "hipSetDevice failed");
-        bool ok = (f.partial || hipMalloc((void **)&f.partial, sizeof(double) * kFitBlocks * kFitRowLen) == hipSuccess) &&
-                  (f.ticket || (hipMalloc((void **)&f.ticket, sizeof(uint32_t)) == hipSuccess &&
-                                hipMemset(f.ticket, 0, sizeof(uint32_t)) == hipSuccess)) &&   // k_cylfit resets it after every launch
-                  (f.work || hipMalloc((void **)&f.work, sizeof(CylFitWork)) == hipSuccess) &&
-                  (f.fit || hipMalloc((void **)&f.fit, sizeof(gm_cylinder_fit)) == hipSuccess) &&
-                  (f.rows8 || hipMalloc((void **)&f.rows8, sizeof(float) * 16) == hipSuccess) &&
-                  (f.plane_best || hipMalloc((void **)&f.plane_best, sizeof(uint32_t)) == hipSuccess) &&
-                  (f.row || hipMalloc((void **)&f.row, sizeof(double) * 4 * kFitRowLen) == hipSuccess) &&
-                  hipMalloc((void **)&f.rows, sizeof(double) * 4 * kFitRowLen * R) == hipSuccess;
-        if (!ok) { f.rows = nullptr; return gfail(grp, GM_ERR_OOM, "gm_group_fit_cylinder: device allocation failed"); }
+        hipError_t e = f.partial.reserve((size_t)kFitBlocks * kFitRowLen);
+        if (e == hipSuccess) e = f.ticket.reserve(1);
+        if (e == hipSuccess) e = hipMemset(f.ticket, 0, sizeof(uint32_t));   // k_cylfit resets it after every launch
+        if (e == hipSuccess) e = f.work.reserve(1);
+        if (e == hipSuccess) e = f.fit.reserve(1);
+        if (e == hipSuccess) e = f.rows8.reserve(16);
+        if (e == hipSuccess) e = f.plane_best.reserve(1);
+        if (e == hipSuccess) e = f.row.reserve((size_t)4 * kFitRowLen);
+        if (e == hipSuccess) e = f.rows.reserve((size_t)4 * kFitRowLen * R);
+        if (e != hipSuccess) return gfail(grp, GM_ERR_OOM, "gm_group_fit_cylinder: device allocation failed");
     }
-    if (!G.h_fit && hipHostMalloc((void **)&G.h_fit, sizeof(gm_cylinder_fit) * R, hipHostMallocDefault) != hipSuccess) {
-        G.h_fit = nullptr;
-        return gfail(grp, GM_ERR_OOM, "gm_group_fit_cylinder: hipHostMalloc failed");
-    }
+    if (G.h_fit.reserve(R) != hipSuccess) return gfail(grp, GM_ERR_OOM, "gm_group_fit_cylinder: hipHostMalloc failed");
     // the starting row (caller's, or the published cylinder: NaN when the frame has none) and the published plane
     const float nanf_ = std::numeric_limits<float>::quiet_NaN();
     float rows8[16];

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/gm_hip.h"
+#include "gm_dev_array.hpp"
 #include "gm_device.hpp"
 
 namespace gm {
@@ -26,37 +27,38 @@ struct RowLayout {
 };
 
 struct SortScratch {
-    uint32_t *totals = nullptr;           // [kRsMaxPasses][2048] digit totals of every pass (zero-filled when a frame opens)
-    uint32_t *rec = nullptr;              // [pass][tile][digit] records of the passes' chained scans (k_sort.hip), cleared per sort
+    DevArray<uint32_t> totals;            // [kRsMaxPasses][2048] digit totals of every pass (zero-filled when a frame opens)
+    DevArray<uint32_t> rec;               // [pass][tile][digit] records of the passes' chained scans (k_sort.hip), cleared per sort
     size_t rec_words = 0;
-    uint32_t *ticket = nullptr;           // ticket word of the passes (0 between launches); [1]: the tile cutter's
+    DevArray<uint32_t> ticket;            // ticket word of the passes (0 between launches); [1]: the tile cutter's
 };
 
 // passes x bits of the radix sort for a key width (k_sort.hip); the crop counts the digit totals of exactly this plan
 struct SortPlan { int passes, bits; };
 
-// One in-flight frame: its stream, staging and device buffers (grow-only).
+// One in-flight frame: its stream, staging and device buffers (grow-only).  Every DevArray / HostArray member owns its
+// block and frees it with the slot; a plain pointer is an alias into memory owned elsewhere.
 struct Slot {
     hipStream_t stream = nullptr;
     hipEvent_t ev[GM_N_STAGES + 1] = {};
     hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr;  // around the normals kernel alone
     uint32_t cap = 0;          // point capacity of the buffers below
     size_t raw_cap = 0;        // bytes
-    uint8_t *h_raw = nullptr;  // pinned staging for the incoming rows
-    uint8_t *d_raw = nullptr;
-    float4 *crop4 = nullptr;   // cropped cloud: x,y,z, bits(input row)
-    uint32_t *keys_a = nullptr, *keys_b = nullptr, *vals_a = nullptr, *vals_b = nullptr;
-    float4 *spts4 = nullptr;   // cropped cloud in cell-sorted order: x,y,z, bits(cropped index)
+    HostArray<uint8_t> h_raw;  // pinned staging for the incoming rows
+    DevArray<uint8_t> d_raw;
+    DevArray<float4> crop4;   // cropped cloud: x,y,z, bits(input row)
+    DevArray<uint32_t> keys_a, keys_b, vals_a, vals_b;
+    DevArray<float4> spts4;   // cropped cloud in cell-sorted order: x,y,z, bits(cropped index)
     uint32_t *skeys = nullptr; // == whichever of keys_a/keys_b holds the sorted keys
-    float4 *normals4 = nullptr;   // per cropped point: nx,ny,nz,curvature (NaN when <3 neighbours)
-    int32_t *counts = nullptr;    // per cropped point neighbour count (GM_CFG_KEEP_COUNTS)
-    float4 *valid4 = nullptr;     // compacted cloud (finite normals)
-    float4 *vnorm4 = nullptr;     // compacted normals
-    uint2 *tiles = nullptr;
+    DevArray<float4> normals4;   // per cropped point: nx,ny,nz,curvature (NaN when <3 neighbours)
+    DevArray<int32_t> counts;    // per cropped point neighbour count (GM_CFG_KEEP_COUNTS)
+    DevArray<float4> valid4;     // compacted cloud (finite normals)
+    DevArray<float4> vnorm4;     // compacted normals
+    DevArray<uint2> tiles;
     uint32_t tiles_cap = 0;   // entries of the tile list's last class (every tile of a frame fits)
     uint32_t tile_seg = 0;    // entries of each of its other kTileListClasses - 1 classes
-    uint2 *row_bounds = nullptr;  // [1024*1024] first / one-past-last sorted position per x-row of the search grid
-    unsigned long long *blk = nullptr;  // tile records of the single-pass compactions 
+    DevArray<uint2> row_bounds;  // [1024*1024] first / one-past-last sorted position per x-row of the search grid
+    DevArray<unsigned long long> blk;  // tile records of the single-pass compactions 
     uint32_t blk_cap = 0;
     uint32_t scan_epoch = 0;            // launches of k_compact on this slot so far (see gm_compact.hpp)
     uint32_t scan_seq = 0;              // index of the next k_compact launch inside the frame being captured
@@ -64,8 +66,8 @@ struct Slot {
     // graph replay (GM_CFG_GRAPH): the frame's launch chain is captured once per (sizes, layout, configuration) and replayed
     bool capturing = false;             // the launches being enqueued go into a stream capture
     bool kernel_timed = false;          // ev_k0 / ev_k1 bracket the last frame's k_normals (not in a replayed frame)
-    uint32_t *frame_in = nullptr;       // device: [0] = points of the frame, [2..3] = address of device-resident rows, [4] = frames replayed so far (epochs)
-    uint32_t *h_frame_in = nullptr;     // pinned: words [0..3] of frame_in (copied by a node of the graph)
+    DevArray<uint32_t> frame_in;       // device: [0] = points of the frame, [2..3] = address of device-resident rows, [4] = frames replayed so far (epochs)
+    HostArray<uint32_t> h_frame_in;     // pinned: words [0..3] of frame_in (copied by a node of the graph)
     static constexpr int kGraphs = 4;   // cached captures (a caller that rotates a few device buffers keeps them all)
     hipGraphExec_t graph_exec[kGraphs] = {};
     unsigned char graph_key[kGraphs][512] = {};  // everything the captured launches froze
@@ -73,49 +75,48 @@ struct Slot {
     uint64_t graph_used[kGraphs] = {};  // last use (least recently used is replaced)
     uint64_t graph_clock = 0;
     uint32_t graph_captures = 0;        // launch chains captured on this slot so far (gm_debug_graph_captures: tests)
-    uint32_t alloc_gen = 0;             // bumped whenever a device buffer of the slot is (re)allocated
-    SortScratch sort = {};
-    unsigned long long *tile_rec = nullptr;   // [cutter blocks + 1][kTileListClasses] records of the tile cutter's chained scan
+    uint32_t alloc_gen = 0;             // counts the (re)allocations of the slot's device buffers (every reserve is handed this word)
+    SortScratch sort;
+    DevArray<unsigned long long> tile_rec;   // [cutter blocks + 1][kTileListClasses] records of the tile cutter's chained scan
     size_t tile_rec_words = 0;
-    uint32_t *seg_start = nullptr;
-    float4 *vox4 = nullptr;       // voxel centroids: x,y,z,count
-    VoxCell *vox_table = nullptr; // dense voxel table (fast path)
-    uint32_t vox_table_cap = 0;   // cells
-    int32_t *vox_nn = nullptr;
-    double *partials = nullptr;   // [kScatterBlocks][6]  (gm_get_local_frame on caller-supplied normals)
-    double *tile_partials = nullptr;  // [compact_blocks(cap)][6]  scatter rows left by the NaN-normal compaction
-    uint8_t *labels = nullptr;
-    uint8_t *inl_mask = nullptr;   // per valid point: which of the last RANSAC stage's hypotheses it is an inlier of
-    DevCounters *ctr = nullptr;
-    VoxelParams *voxp = nullptr;
-    FrameOut *d_out = nullptr;
-    FrameOut *h_out = nullptr;    // pinned
+    DevArray<uint32_t> seg_start;
+    DevArray<float4> vox4;       // voxel centroids: x,y,z,count
+    DevArray<VoxCell> vox_table; // dense voxel table (fast path)
+    DevArray<int32_t> vox_nn;
+    DevArray<double> partials;   // [kScatterBlocks][6]  (gm_get_local_frame on caller-supplied normals)
+    DevArray<double> tile_partials;  // [compact_blocks(cap)][6]  scatter rows left by the NaN-normal compaction
+    DevArray<uint8_t> labels;
+    DevArray<uint8_t> inl_mask;   // per valid point: which of the last RANSAC stage's hypotheses it is an inlier of
+    DevArray<DevCounters> ctr;
+    DevArray<VoxelParams> voxp;
+    DevArray<FrameOut> d_out;
+    HostArray<FrameOut> h_out;    // pinned
     // extension scratch (allocated on first use)
     uint32_t ext_H = 0, ext_cap = 0;
-    float *hyp_plane = nullptr, *hyp_cyl = nullptr;   // [H][8]
-    float2 *band = nullptr;                           // [H]
-    uint32_t *score_partial = nullptr;                // [score_blocks][H]
-    int32_t *cnt_plane = nullptr, *cnt_cyl = nullptr; // [H]
-    uint32_t *best_plane = nullptr, *best_cyl = nullptr; // [2]
-    double *mom_partial = nullptr;                    // [kScatterBlocks][16]
-    double *mom_plane = nullptr, *mom_cyl = nullptr;  // [16]
-    unsigned long long *nn_best = nullptr;            // [cap]
-    float4 *vox_nrm4 = nullptr;                       // [cap] normal of each voxel centroid's nearest point (GM_CFG_NEAREST)
+    DevArray<float> hyp_plane, hyp_cyl;   // [H][8]
+    DevArray<float2> band;                           // [H]
+    DevArray<uint32_t> score_partial;                // [score_blocks][H]
+    DevArray<int32_t> cnt_plane, cnt_cyl; // [H]
+    DevArray<uint32_t> best_plane, best_cyl; // [2]
+    DevArray<double> mom_partial;                    // [kScatterBlocks][16]
+    DevArray<double> mom_plane, mom_cyl;  // [16]
+    DevArray<unsigned long long> nn_best;            // [cap]
+    DevArray<float4> vox_nrm4;                       // [cap] normal of each voxel centroid's nearest point (GM_CFG_NEAREST)
     // cylinder regression (k_cylfit.hip)
-    double *fit_partial = nullptr;                    // [kFitBlocks][24] partial rows of a pass
-    uint32_t *fit_ticket = nullptr;                   // last-block ticket of the passes (0 between launches)
-    CylFitWork *fit_work = nullptr;                   // model between the passes
-    float *fit_init = nullptr;                        // [8] gm_fit_cylinder's starting row
-    gm_cylinder_fit *fit_stage = nullptr;             // gm_fit_cylinder's result record
+    DevArray<double> fit_partial;                    // [kFitBlocks][24] partial rows of a pass
+    DevArray<uint32_t> fit_ticket;                   // last-block ticket of the passes (0 between launches)
+    DevArray<CylFitWork> fit_work;                   // model between the passes
+    DevArray<float> fit_init;                        // [8] gm_fit_cylinder's starting row
+    DevArray<gm_cylinder_fit> fit_stage;             // gm_fit_cylinder's result record
     gm_cylinder_fit last_fit = {};                    // the fit of the slot's last completed frame (GM_CFG_CYLINDER_FIT)
     // wall deviation map (k_surface.hip; GM_CFG_SURFACE_MAP or gm_surface_map, allocated on first use)
-    SurfParams *surf_prm = nullptr;                   // [2]: the frames' parameters, the stage call's
-    uint8_t *surf_table = nullptr;                    // global cell table + class counters + ticket (zero between launches)
-    gm_surface_cell *surf_cells = nullptr;            // [GM_SURF_MAX_CELLS]
-    gm_surface_info *surf_info = nullptr;
-    gm_cylinder_fit *surf_fit = nullptr;              // the stage call's model row
-    float *surf_res = nullptr;                        // [surf_cap] per valid point
-    int32_t *surf_cell = nullptr;                     // [surf_cap]
+    DevArray<SurfParams> surf_prm;                   // [2]: the frames' parameters, the stage call's
+    DevArray<uint8_t> surf_table;                    // global cell table + class counters + ticket (zero between launches)
+    DevArray<gm_surface_cell> surf_cells;            // [GM_SURF_MAX_CELLS]
+    DevArray<gm_surface_info> surf_info;
+    DevArray<gm_cylinder_fit> surf_fit;              // the stage call's model row
+    DevArray<float> surf_res;                        // [surf_cap] per valid point
+    DevArray<int32_t> surf_cell;                     // [surf_cap]
     uint32_t surf_cap = 0;
     // /choppedCloud output (gm_set_cloud_output): caller-owned page-locked rows, copied on a stream of their own
     float4 *cloud_out = nullptr;

@@ -26,46 +26,6 @@ using namespace gm;
         if (s__ != GM_OK) return s__;      \
     } while (0)
 
-// A grow-only device array: the scratch of the map's calls, allocated on first use, freed with its owner (on the owner's
-// device).  reserve frees before it allocates (the peak is the larger block, never both), does not preserve the contents
-// and never shrinks; after a failure the array is empty.
-template <class T>
-struct DevArray {
-    T *p = nullptr;
-    uint64_t cap = 0;   // elements
-    DevArray() = default;
-    DevArray(DevArray &&o) : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }   // (a std::vector of owners grows)
-    DevArray(const DevArray &) = delete;
-    DevArray &operator=(const DevArray &) = delete;
-    ~DevArray() { release(); }
-    gm_status reserve(gm_ctx *ctx, uint64_t n)
-    {
-        if (cap >= n) return GM_OK;
-        release();
-        GMW_HIP(ctx, hipMalloc((void **)&p, n * sizeof(T)));
-        cap = n;
-        return GM_OK;
-    }
-    void release()
-    {
-        (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-// Consecutive arrays inside one DevArray<uint8_t> block.  Every such block is laid out by the count of the call that
-// uses it, not by the block's capacity: what a call touches is dense at the front, whatever larger call sized the block.
-struct Carve {
-    uint8_t *at;
-    template <class T>
-    T *take(uint64_t n)
-    {
-        T *r = reinterpret_cast<T *>(at);
-        at += n * sizeof(T);
-        return r;
-    }
-};
-
 // The records of a chained scan (gm_compact.hpp) that is not a frame's -- a slot's own belong to the frame that may be in
 // flight on it: the record array with the ticket word behind it, and the epoch of the launches on it so far.  The rule is
 // next_scan's (gm_internal.hpp): epochs run 1 .. 2^29-2 and never 0, and the records are cleared when the counter wraps,
@@ -81,7 +41,7 @@ struct ScanRecords {
         if (holds(points)) return GM_OK;
         n = 0;
         const uint32_t want = compact_records(points);
-        GMW_OK(rec.reserve(ctx, (uint64_t)want + 1));
+        GMW_HIP(ctx, rec.reserve((uint64_t)want + 1));
         GMW_HIP(ctx, hipMemsetAsync(rec.p, 0, sizeof(unsigned long long) * ((size_t)want + 1), s));
         n = want;
         return GM_OK;
@@ -108,7 +68,7 @@ struct WallCheckSlot {
     DevArray<gm_wall_check_point> stage;    // the changed rows of the last check, in order
     ScanRecords scan;                       // the check's own chained scan
     DevArray<unsigned long long> ctr;       // device [kWallCheckCounters]
-    unsigned long long *h_ctr = nullptr;    // pinned copy, valid once `done` has passed
+    HostArray<unsigned long long> h_ctr;    // pinned copy, valid once `done` has passed
     hipEvent_t done = nullptr;              // recorded behind the check and the copy of its counters
     hipEvent_t adds = nullptr;              // recorded on this slot's stream by a check on another slot: the adds so far
     bool have = false;                      // a check was enqueued: a result is (or will be) readable
@@ -336,12 +296,11 @@ void free_map(gm_wall_map *m)
         if (m->pending[i] && m->ctx->slots[i].stream) hipStreamSynchronize(m->ctx->slots[i].stream);
     for (WallCheckSlot &c : m->checks) {
         if (c.outstanding) hipEventSynchronize(c.done);
-        if (c.h_ctr) hipHostFree(c.h_ctr);
         if (c.done) hipEventDestroy(c.done);
         if (c.adds) hipEventDestroy(c.adds);
     }
     if (m->stream) { hipStreamSynchronize(m->stream); hipStreamDestroy(m->stream); }
-    delete m;   // (every DevArray goes with it)
+    delete m;   // (every DevArray and HostArray goes with it)
 }
 
 // A stage call's points (gm_wall_map_add_points, gm_wall_map_check_points) on the staging slot: open, whatever the call
@@ -360,12 +319,12 @@ struct StageCall {
         GMW_OK(gm_begin_stage(ctx, sl));
         GMW_OK(gm_ensure_capacity(ctx, *sl, n ? n : 1u, (size_t)(n ? n : 1u) * 16, true));
         if (residual || cell) {
-            GMW_OK(map->pt_res.reserve(ctx, n));
-            GMW_OK(map->pt_cell.reserve(ctx, n));
+            GMW_HIP(ctx, map->pt_res.reserve(n));
+            GMW_HIP(ctx, map->pt_cell.reserve(n));
         }
         if (delta || cls) {
-            GMW_OK(map->ck_delta.reserve(ctx, n));
-            GMW_OK(map->ck_cls.reserve(ctx, n));
+            GMW_HIP(ctx, map->ck_delta.reserve(n));
+            GMW_HIP(ctx, map->ck_cls.reserve(n));
         }
         return GM_OK;
     }
@@ -490,8 +449,8 @@ gm_status check_prepare(gm_wall_map *m, uint32_t slot, uint32_t n_cap, hipStream
     gm_ctx *ctx = m->ctx;
     WallCheckSlot &c = m->checks[slot];
     if (!c.done) GMW_HIP(ctx, hipEventCreateWithFlags(&c.done, hipEventDisableTiming));
-    GMW_OK(c.ctr.reserve(ctx, kWallCheckCounters));
-    if (!c.h_ctr) GMW_HIP(ctx, hipHostMalloc((void **)&c.h_ctr, kWallCheckCounters * 8, hipHostMallocDefault));
+    GMW_HIP(ctx, c.ctr.reserve(kWallCheckCounters));
+    GMW_HIP(ctx, c.h_ctr.reserve(kWallCheckCounters));
     if (c.stage.cap < n_cap || !c.scan.holds(n_cap)) {
         if (c.outstanding) {   // the slot's last check may still be writing the old blocks
             GMW_HIP(ctx, hipEventSynchronize(c.done));
@@ -499,7 +458,7 @@ gm_status check_prepare(gm_wall_map *m, uint32_t slot, uint32_t n_cap, hipStream
         }
         c.have = false;        // (its rows go with the block)
     }
-    GMW_OK(c.stage.reserve(ctx, n_cap));
+    GMW_HIP(ctx, c.stage.reserve(n_cap));
     GMW_OK(c.scan.reserve(ctx, n_cap, s));
     st = c.scan.next(s);
     GMW_HIP(ctx, hipMemsetAsync(c.ctr.p, 0, kWallCheckCounters * 8, s));
@@ -627,9 +586,9 @@ gm_status objects_run(gm_wall_map *m, const gm_wall_check_point *d_rows, uint32_
         return GM_OK;
     }
     const uint64_t NB = (uint64_t)win.nJ * win.NK, pairs = 2u * NB;
-    GMW_OK(m->ob_blocks.reserve(ctx, 3u * pairs));
-    GMW_OK(m->ob_ctr.reserve(ctx, kWallObjectCounters));
-    if (object_of_row) GMW_OK(m->ob_of_row.reserve(ctx, n_rows));
+    GMW_HIP(ctx, m->ob_blocks.reserve(3u * pairs));
+    GMW_HIP(ctx, m->ob_ctr.reserve(kWallObjectCounters));
+    if (object_of_row) GMW_HIP(ctx, m->ob_of_row.reserve(n_rows));
     WallObjectArgs a;
     memset(&a, 0, sizeof(a));
     a.rows = d_rows;
@@ -658,7 +617,7 @@ gm_status objects_run(gm_wall_map *m, const gm_wall_check_point *d_rows, uint32_
     GMW_HIP(ctx, hipStreamSynchronize(m->stream));   // the one count the host needs: it sizes the records
     const uint64_t ncomp = ctr[7];
     if (ncomp) {
-        GMW_OK(m->ob_recs.reserve(ctx, ncomp * (sizeof(WallObjectAcc) + sizeof(gm_wall_object) + 4 + 4)));
+        GMW_HIP(ctx, m->ob_recs.reserve(ncomp * (sizeof(WallObjectAcc) + sizeof(gm_wall_object) + 4 + 4)));
         Carve recs{m->ob_recs.p};
         a.acc = recs.take<WallObjectAcc>(ncomp);
         a.out = recs.take<gm_wall_object>(ncomp);
@@ -775,8 +734,8 @@ gm_status gm_wall_map_create(gm_ctx *ctx, const gm_wall_params *params, gm_wall_
     design_frame(m);
     auto body = [&]() -> gm_status {
         GMW_HIP(ctx, hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-        GMW_OK(m->base.reserve(ctx, wall_table_bytes(m->ncell)));
-        GMW_OK(m->stage.reserve(ctx, std::min(kStageCells, m->ncell) * sizeof(gm_wall_raw_cell)));
+        GMW_HIP(ctx, m->base.reserve(wall_table_bytes(m->ncell)));
+        GMW_HIP(ctx, m->stage.reserve(std::min(kStageCells, m->ncell) * sizeof(gm_wall_raw_cell)));
         GMW_HIP(ctx, hipMemsetAsync(m->base.p, 0, wall_table_bytes(m->ncell), m->stream));
         GMW_HIP(ctx, hipStreamSynchronize(m->stream));
         return GM_OK;
@@ -1016,8 +975,8 @@ gm_status gm_wall_map_regions(gm_wall_map *map, gm_wall_map *baseline, uint32_t 
     a.min_count = rp.min_count;
     a.min_cells = rp.min_cells;
     a.T = T;
-    GMW_OK(map->rg_cells.reserve(ctx, total * (8 + 4 + 4)));
-    GMW_OK(map->rg_ctr.reserve(ctx, kWallRegionCounters));
+    GMW_HIP(ctx, map->rg_cells.reserve(total * (8 + 4 + 4)));
+    GMW_HIP(ctx, map->rg_ctr.reserve(kWallRegionCounters));
     Carve cells{map->rg_cells.p};
     a.d = cells.take<long long>(total);
     a.parent = cells.take<uint32_t>(total);
@@ -1034,7 +993,7 @@ gm_status gm_wall_map_regions(gm_wall_map *map, gm_wall_map *baseline, uint32_t 
     info->components = ncomp;
     uint64_t nreg = 0;
     if (ncomp) {
-        GMW_OK(map->rg_recs.reserve(ctx, ncomp * (sizeof(WallRegionAcc) + sizeof(gm_wall_region))));
+        GMW_HIP(ctx, map->rg_recs.reserve(ncomp * (sizeof(WallRegionAcc) + sizeof(gm_wall_region))));
         Carve recs{map->rg_recs.p};
         a.acc = recs.take<WallRegionAcc>(ncomp);
         a.out = recs.take<gm_wall_region>(ncomp);
@@ -1126,11 +1085,11 @@ gm_status gm_wall_map_cloud(gm_wall_map *map, uint32_t station0, uint32_t n, con
     const uint64_t cb = (uint64_t)rows * NK;   // blocks of a full chunk
     const bool merged = bs > 1u || bk > 1u;
     const uint64_t acc_bytes = cb * kWallCloudAccBytes;
-    if (merged) GMW_OK(map->cl_acc.reserve(ctx, acc_bytes));
-    GMW_OK(map->cl_stage.reserve(ctx, cb));
+    if (merged) GMW_HIP(ctx, map->cl_acc.reserve(acc_bytes));
+    GMW_HIP(ctx, map->cl_stage.reserve(cb));
     GMW_OK(map->cl_scan.reserve(ctx, (uint32_t)cb, map->stream));   // (nothing of the map's is in flight: the call synchronised above)
-    GMW_OK(map->cl_ctr.reserve(ctx, kWallCloudCounters));
-    GMW_OK(map->cl_dirs.reserve(ctx, (uint64_t)GM_WALL_MAX_SECTORS * 2));
+    GMW_HIP(ctx, map->cl_ctr.reserve(kWallCloudCounters));
+    GMW_HIP(ctx, map->cl_dirs.reserve((uint64_t)GM_WALL_MAX_SECTORS * 2));
     map->cl_dirs_host.resize((size_t)2 * NK);
     cloud_directions(nsec, bk, map->cl_dirs_host.data());
     GMW_HIP(ctx, hipMemcpyAsync(map->cl_dirs.p, map->cl_dirs_host.data(), (size_t)NK * 16, hipMemcpyHostToDevice, map->stream));
@@ -1396,7 +1355,7 @@ gm_status gm_wall_check_objects(gm_wall_map *map, const gm_wall_check_point *row
             if (wall_object_rejected(b[0], b[1], b[2], b[4], rows[i].cell, wall_check_fix(rows[i].delta), (uint32_t)map->ncell)) ++rejected;
         }
     } else if (n_rows) {
-        GMW_OK(map->ob_rows.reserve(ctx, n_rows));
+        GMW_HIP(ctx, map->ob_rows.reserve(n_rows));
         GMW_HIP(ctx, hipMemcpyAsync(map->ob_rows.p, rows, (size_t)n_rows * sizeof(gm_wall_check_point), hipMemcpyHostToDevice, map->stream));
     }
     return objects_run(map, map->ob_rows.p, n_rows, rejected, op, win, info, objects, capacity, n_out, object_of_row,

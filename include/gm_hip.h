@@ -148,6 +148,10 @@ gm_status gm_host_unregister(gm_ctx *ctx, void *ptr);
 void gm_default_config(gm_config *cfg);
 
 uint32_t gm_abi_version(void);
+/* Diagnostic (tests): device and page-locked blocks the library itself holds right now, process-wide.  Back at its
+ * earlier value once every context, wall map and group created since has been destroyed (gm_host_alloc memory is the
+ * caller's and is not counted). */
+long long gm_debug_live_buffers(void);
 const char *gm_status_string(gm_status s);
 /* Message of the last failure on this context ("" if none).  ctx may be NULL
  * for a failure inside gm_create. */
