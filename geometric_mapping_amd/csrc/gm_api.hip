@@ -32,6 +32,30 @@ gm_status fail(gm_ctx *ctx, gm_status st, const char *msg)
     return st;
 }
 
+// The stream a slot's frames run on.  The runtime maps a process's streams onto hardware queues, GPU_MAX_HW_QUEUES
+// (default 4) of them per stream priority: the null stream, the slots' streams, the /choppedCloud copy streams and a
+// wall map's stream at the default priority are more streams than queues once four frames are in flight, and a slot
+// that shares a queue runs behind the frame it shares with.  The slots therefore take their streams at the greatest
+// priority the device reports -- a pool they share with nothing else; every slot of every context gets the same one,
+// so the frames' order among themselves is what it was.  GM_STREAM_PRIORITY=default keeps them with the rest (A/B);
+// so does a device that reports no range or refuses the stream: a context never fails to open over this.
+hipError_t create_slot_stream(hipStream_t *s)
+{
+    static const bool high = [] {
+        const char *e = getenv("GM_STREAM_PRIORITY");   // default | high; unset or anything else: high
+        return !(e && strcmp(e, "default") == 0);
+    }();
+    if (high) {
+        int least = 0, greatest = 0;
+        if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least &&
+            hipStreamCreateWithPriority(s, hipStreamNonBlocking, greatest) == hipSuccess)
+            return hipSuccess;
+        (void)hipGetLastError();
+        *s = nullptr;
+    }
+    return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
+}
+
 // search grid over the crop box: cell edge >= 1.001 r in y and z (<= 1024 cells per axis), x binned
 // `fine` times finer (a power of two chosen so that the cell key still fits 31 bits)
 // The neighbour predicate of k_normals needs one ulp of r^2, scaled by a power of two <= 2^126, to reach 1: true for
@@ -876,12 +900,14 @@ gm_status gm_create(const gm_config *cfg, gm_ctx **out)
         for (uint32_t i = 0; i < ctx->n_slots; ++i) {
             Slot &sl = ctx->slots[i];
             sl.pipelined = ctx->n_slots > 1;
-            GM_HIP(ctx, hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
+            GM_HIP(ctx, create_slot_stream(&sl.stream));
             for (int k = 0; k <= GM_N_STAGES; ++k) GM_HIP(ctx, hipEventCreate(&sl.ev[k]));
             GM_HIP(ctx, hipEventCreate(&sl.ev_k0));
             GM_HIP(ctx, hipEventCreate(&sl.ev_k1));
-            // (the /choppedCloud copy stream is created by gm_set_cloud_output: every stream of the process takes part in
-            // the runtime's mapping of streams onto hardware queues, and an idle one can push two slots onto one queue)
+            // (the /choppedCloud copy stream is created by gm_set_cloud_output, at the default priority: there it draws on
+            // the queues of the null stream and the wall map, not on the slots' (create_slot_stream).  It stays lazy all the
+            // same: a context without an output holds no stream it never uses, and with GM_STREAM_PRIORITY=default, or on a
+            // device without priorities, an idle copy stream can still push two slots onto one queue)
             uint32_t *gen = &sl.alloc_gen;
             GM_HIP(ctx, sl.ctr.reserve(1, gen));
             GM_HIP(ctx, sl.voxp.reserve(1, gen));

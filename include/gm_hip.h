@@ -73,9 +73,10 @@ typedef struct gm_config {
     double   weightingFactor;    /* launch/mapping.launch:10 */
     int32_t  device;             /* HIP device ordinal */
     uint32_t n_slots;            /* frames in flight (>=1); 2 overlaps H2D of frame i+1 with compute of i.  Every slot has its own
-                                    HIP stream; ROCm maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), so
-                                    for more than 3 slots export GPU_MAX_HW_QUEUES=8 before the process's first HIP call (measured:
-                                    4 slots 0.211 ms per 1 M-point frame with 8 queues, 0.271 with 4; 3 slots 0.227) */
+                                    HIP stream, created at the device's greatest stream priority: ROCm maps a process's streams onto
+                                    GPU_MAX_HW_QUEUES hardware queues (default 4) per priority, so up to 4 slots have a queue each
+                                    whatever other streams the process holds (measured: 4 slots 0.198 ms per 1 M-point frame, 3 slots
+                                    0.210; more slots than queues share them and lose: DESIGN.md par. 7) */
     uint32_t max_points;         /* capacity hint; buffers grow on demand */
     uint32_t ransac_hypotheses;  /* H per model per frame (extension) */
     double   ransac_threshold;   /* tau, metres (extension) */
