@@ -327,6 +327,7 @@ def load():
         "gm_chop_cloud": (C.c_int, [vp, cloudp, C.c_double, fp, u32, u32p]),
         "gm_get_normals_stage": (C.c_int, [vp, fp, u32, C.c_double, fp, fp, u32, u32p]),
         "gm_get_local_frame": (C.c_int, [vp, fp, u32, C.c_double, fp, fp, dp]),
+        "gm_compact_valid_stage": (C.c_int, [vp, fp, fp, u32, C.c_double, fp, fp, u32, u32p, dp]),
         "gm_voxel_grid": (C.c_int, [vp, fp, u32, C.c_double, fp, u32, u32p, u32p]),
         "gm_nearest": (C.c_int, [vp, fp, u32, fp, u32, i32p]),
         "gm_solve_local_frame": (C.c_int, [dp, fp, fp]),

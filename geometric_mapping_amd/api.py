@@ -296,6 +296,24 @@ class GeometricMapping:
         M = np.array([[sc[0], sc[1], sc[2]], [sc[1], sc[3], sc[4]], [sc[2], sc[4], sc[5]]])
         return ev, V.reshape(3, 3).T.copy(), M
 
+    def compactValid(self, weightingFactor, rows, normals):
+        """The NaN-normal removal of getNormals and getLocalFrame's scatter sums on caller-supplied rows: rows [n,4]
+        (x,y,z,pad) and normals [n,4] (nx,ny,nz,curvature) in.  Returns (rows [n',4], normals [n',4], scatter6 [6] fp64):
+        the rows whose normal has three finite components, in order, bit for bit."""
+        r = np.ascontiguousarray(rows, dtype=np.float32)
+        nr = np.ascontiguousarray(normals, dtype=np.float32)
+        if r.ndim != 2 or r.shape[1] != 4 or nr.shape != r.shape:
+            raise ValueError("rows and normals must both be [n,4]")
+        n0 = r.shape[0]
+        cap = max(n0, 1)
+        oc = np.empty((cap, 4), dtype=np.float32)
+        on = np.empty((cap, 4), dtype=np.float32)
+        n = C.c_uint32(0)
+        sc = np.zeros(6, dtype=np.float64)
+        self._check(self._L.gm_compact_valid_stage(self._ctx, _f32(r), _f32(nr), n0, float(weightingFactor), _f32(oc),
+                                                   _f32(on), cap, C.byref(n), sc.ctypes.data_as(C.POINTER(C.c_double))))
+        return oc[:n.value].copy(), on[:n.value].copy(), sc
+
     def voxelGrid(self, leafSize, cloud):
         """The pcl::VoxelGrid half of rvizNormals (tunnel_processing.hpp:77-82).
         Returns (centroids [V,3], counts [V], passthrough flag)."""

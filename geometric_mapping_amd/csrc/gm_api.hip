@@ -221,7 +221,6 @@ gm_status ensure_capacity(gm_ctx *ctx, Slot &sl, uint32_t n, size_t raw_bytes, b
     GM_HIP(ctx, sl.vals_a.reserve(cap, gen)); GM_HIP(ctx, sl.vals_b.reserve(cap, gen));
     GM_HIP(ctx, sl.spts4.reserve(cap, gen)); GM_HIP(ctx, sl.normals4.reserve(cap, gen));
     GM_HIP(ctx, sl.counts.reserve(cap, gen));
-    GM_HIP(ctx, sl.valid4.reserve(cap, gen)); GM_HIP(ctx, sl.vnorm4.reserve(cap, gen));
     GM_HIP(ctx, sl.seg_start.reserve(cap, gen)); GM_HIP(ctx, sl.vox4.reserve(cap, gen));
     GM_HIP(ctx, sl.vox_nn.reserve(cap, gen)); GM_HIP(ctx, sl.labels.reserve(cap, gen)); GM_HIP(ctx, sl.inl_mask.reserve(cap, gen));
     // tile list: kTileListClasses - 1 segments for the tiles with an x extent (>= 2 points each: none of them can hold more
@@ -231,7 +230,7 @@ gm_status ensure_capacity(gm_ctx *ctx, Slot &sl, uint32_t n, size_t raw_bytes, b
     GM_HIP(ctx, sl.tiles.reserve((size_t)(kTileListClasses - 1) * sl.tile_seg + sl.tiles_cap, gen));
     GM_HIP(ctx, sl.row_bounds.reserve((size_t)1024 * 1024, gen));  // make_grid caps every axis at 1024 cells (allocated once)
     sl.blk_cap = compact_records(cap > kVoxDenseMaxCells ? cap : kVoxDenseMaxCells) + 1;
-    GM_HIP(ctx, sl.tile_partials.reserve((size_t)compact_blocks(cap) * 6, gen));
+    GM_HIP(ctx, sl.tile_partials.reserve((size_t)compact_records(cap) * 6, gen));
     GM_HIP(ctx, sl.blk.reserve((size_t)sl.blk_cap + 1, gen));  // + the ticket word
     GM_HIP(ctx, hipMemsetAsync(sl.blk, 0, sizeof(unsigned long long) * ((size_t)sl.blk_cap + 1), sl.stream));
     {
@@ -369,20 +368,21 @@ static gm_status enqueue_launches(gm_ctx *ctx, Slot &sl, const RowLayout &rows, 
     record(ctx, sl, 2);
     launch_grid_and_normals(g, vd, sl, ns, (cf.flags & GM_CFG_KEEP_COUNTS) != 0, true, s);
     record(ctx, sl, 3);  // end of grid+normals; the kernel alone is bracketed by ev_k0/ev_k1
-    // (getLocalFrame's scatter terms are summed by the compaction: one partial row per kCpTile cropped points)
+    // The NaN-normal compaction works in place: behind it crop4 / normals4 [0, n_valid) are the valid cloud and its normals.
+    // (getLocalFrame's scatter terms are summed by its first launch: one partial row per row_tile cropped points)
     uint32_t row_tile = kCpTile;
     const uint32_t nparts = launch_compact_valid(sl, ns, cf.weightingFactor, s, &row_tile);
     bool cloud_copy_pending = false;
     if (cloud_overlap) {
         GM_HIP(ctx, hipEventRecord(sl.ev_valid, s));
         GM_HIP(ctx, hipStreamWaitEvent(sl.copy_stream, sl.ev_valid, 0));
-        launch_rows_to_host(sl.valid4, sl.cloud_out_dev, &sl.ctr->first_drop_enc, &sl.ctr->n_valid, sl.copy_stream);
+        launch_rows_to_host(sl.crop4, sl.cloud_out_dev, &sl.ctr->first_drop_enc, &sl.ctr->n_valid, sl.copy_stream);
         GM_HIP(ctx, hipEventRecord(sl.ev_copied, sl.copy_stream));
         cloud_copy_pending = true;
     } else if (sl.cloud_out && n) {
         // (a captured copy's size is frozen: the bucketed size, as far as the buffer has rows -- both >= n_valid)
         const size_t frozen = (size_t)(ns < sl.cloud_out_cap ? ns : sl.cloud_out_cap) * sizeof(float4);
-        GM_HIP(ctx, hipMemcpyAsync(sl.cloud_out, sl.valid4, frozen, hipMemcpyDeviceToHost, s));
+        GM_HIP(ctx, hipMemcpyAsync(sl.cloud_out, sl.crop4, frozen, hipMemcpyDeviceToHost, s));
     }
     record(ctx, sl, 4);
     record(ctx, sl, 5);
@@ -391,7 +391,7 @@ static gm_status enqueue_launches(gm_ctx *ctx, Slot &sl, const RowLayout &rows, 
         if (vd.enabled) {
             launch_voxel_dense_finalize(vd, sl, s);
         } else {  // lattice too large for a table: min/max -> keys -> sort -> segmented mean
-            launch_minmax(sl.valid4, &sl.ctr->n_valid, ns, sl.ctr, s);
+            launch_minmax(sl.crop4, &sl.ctr->n_valid, ns, sl.ctr, s);
             launch_voxel_grid(sl, ns, (float)cf.voxelGridLeafSize, voxel_key_bits(lo, hi, cf.voxelGridLeafSize), s);
         }
     }
@@ -402,8 +402,8 @@ static gm_status enqueue_launches(gm_ctx *ctx, Slot &sl, const RowLayout &rows, 
     }
     if ((cf.flags & GM_CFG_NEAREST) && (cf.flags & GM_CFG_VOXEL_GRID)) {
         const uint32_t nq_cap = vd.enabled ? (uint32_t)vd.dim * vd.dim * vd.dim : ns;
-        launch_nearest(sl.valid4, &sl.ctr->n_valid, ns, sl.vox4, &sl.ctr->n_voxels, nq_cap < ns ? nq_cap : ns, sl.nn_best,
-                       sl.vox_nn, s, sl.vnorm4, sl.vox_nrm4);
+        launch_nearest(sl.crop4, &sl.ctr->n_valid, ns, sl.vox4, &sl.ctr->n_voxels, nq_cap < ns ? nq_cap : ns, sl.nn_best,
+                       sl.vox_nn, s, sl.normals4, sl.vox_nrm4);
     }
     record(ctx, sl, 7);
     if (!(cf.flags & (GM_CFG_RANSAC_PLANE | GM_CFG_RANSAC_CYLINDER)))
@@ -720,27 +720,27 @@ gm_status gm_enqueue_ransac(gm_ctx *ctx, Slot &sl, uint32_t n_cap, uint32_t scat
     uint32_t mom_rows = 0;
     if (do_plane) {
         uint8_t *lab = first ? nullptr : sl.labels;
-        launch_plane_hypotheses(sl.valid4, lab, 0, n_ptr, n_cap, cf.ransac_seed, H, sl.hyp_plane, sl.cnt_plane, s);
+        launch_plane_hypotheses(sl.crop4, lab, 0, n_ptr, n_cap, cf.ransac_seed, H, sl.hyp_plane, sl.cnt_plane, s);
         const uint32_t *fsel = nullptr; const int32_t *fcnt = nullptr; uint32_t fk = 0; bool fmask = false, frep = false;
-        launch_score_preemptive(0, sl.valid4, lab, 0, n_ptr, n_cap, sl.hyp_plane, sl.band, H, cf.ransac_threshold,
+        launch_score_preemptive(0, sl.crop4, lab, 0, n_ptr, n_cap, sl.hyp_plane, sl.band, H, cf.ransac_threshold,
                                 sl.score_partial, sl.cnt_plane, sl.best_plane, true, &fsel, &fcnt, &fk, s, sl.inl_mask, &fmask, &frep);
-        mom_rows = launch_label(0, sl.valid4, sl.labels, 0, 1, n_ptr, n_cap, sl.hyp_plane, sl.band, sl.best_plane,
-                                cf.ransac_threshold, first ? 1 : 0, fsel, fcnt, fk, s, sl.vnorm4, sl.mom_partial, fmask ? sl.inl_mask : nullptr, frep);
+        mom_rows = launch_label(0, sl.crop4, sl.labels, 0, 1, n_ptr, n_cap, sl.hyp_plane, sl.band, sl.best_plane,
+                                cf.ransac_threshold, first ? 1 : 0, fsel, fcnt, fk, s, sl.normals4, sl.mom_partial, fmask ? sl.inl_mask : nullptr, frep);
         first = false;
     }
     if (do_cyl) {
         uint8_t *lab = first ? nullptr : sl.labels;
-        launch_cylinder_hypotheses(sl.valid4, sl.vnorm4, lab, 0, n_ptr, n_cap, cf.ransac_seed + 1, H, sl.hyp_cyl,
+        launch_cylinder_hypotheses(sl.crop4, sl.normals4, lab, 0, n_ptr, n_cap, cf.ransac_seed + 1, H, sl.hyp_cyl,
                                    sl.cnt_cyl, sl.band, cf.ransac_threshold, s);
         const uint32_t *fsel = nullptr; const int32_t *fcnt = nullptr; uint32_t fk = 0; bool fmask = false, frep = false;
-        launch_score_preemptive(1, sl.valid4, lab, 0, n_ptr, n_cap, sl.hyp_cyl, sl.band, H, cf.ransac_threshold,
+        launch_score_preemptive(1, sl.crop4, lab, 0, n_ptr, n_cap, sl.hyp_cyl, sl.band, H, cf.ransac_threshold,
                                 sl.score_partial, sl.cnt_cyl, sl.best_cyl, true, &fsel, &fcnt, &fk, s, sl.inl_mask, &fmask, &frep);
-        mom_rows = launch_label(1, sl.valid4, sl.labels, 0, 2, n_ptr, n_cap, sl.hyp_cyl, sl.band, sl.best_cyl,
-                                cf.ransac_threshold, first ? 1 : 0, fsel, fcnt, fk, s, sl.vnorm4, sl.mom_partial, fmask ? sl.inl_mask : nullptr, frep);
+        mom_rows = launch_label(1, sl.crop4, sl.labels, 0, 2, n_ptr, n_cap, sl.hyp_cyl, sl.band, sl.best_cyl,
+                                cf.ransac_threshold, first ? 1 : 0, fsel, fcnt, fk, s, sl.normals4, sl.mom_partial, fmask ? sl.inl_mask : nullptr, frep);
         first = false;
         if (cf.flags & GM_CFG_CYLINDER_FIT) {   // regression of the winner; relabels the cylinder before the frame closes
             CylFitArgs a;
-            a.pts = sl.valid4; a.labels = sl.labels; a.out = sl.labels;
+            a.pts = sl.crop4; a.labels = sl.labels; a.out = sl.labels;
             a.want = 0; a.want2 = 2; a.mask_mode = 0;   // eligible: what the plane left (labels 0 and 2)
             a.n_ptr = n_ptr; a.n_host = n_cap;
             a.init = sl.hyp_cyl; a.best = sl.best_cyl;
@@ -749,7 +749,7 @@ gm_status gm_enqueue_ransac(gm_ctx *ctx, Slot &sl, uint32_t n_cap, uint32_t scat
             launch_cylinder_fit(a, s);
             if (cf.flags & GM_CFG_SURFACE_MAP) {   // wall deviation map against the fit's device-side record
                 SurfArgs m;
-                m.pts = sl.valid4; m.labels = sl.labels; m.n_ptr = n_ptr; m.n_host = n_cap;
+                m.pts = sl.crop4; m.labels = sl.labels; m.n_ptr = n_ptr; m.n_host = n_cap;
                 m.fit = &sl.d_out->fit; m.prm = sl.surf_prm;
                 m.table = sl.surf_table; m.cells = sl.surf_cells; m.info = sl.surf_info; m.res = sl.surf_res; m.cell = sl.surf_cell;
                 launch_surface_map(m, n_cap, s);
@@ -1056,7 +1056,7 @@ gm_status gm_get_cropped_xyz(gm_ctx *ctx, uint32_t slot, float *xyzw, uint32_t c
     gm_status st = check_slot(ctx, slot);
     if (st != GM_OK) return st;
     Slot &sl = ctx->slots[slot];
-    return fetch(ctx, slot, (const float4 *)sl.valid4, sl.last.n_valid, (float4 *)xyzw, capacity, n_out);
+    return fetch(ctx, slot, (const float4 *)sl.crop4, sl.last.n_valid, (float4 *)xyzw, capacity, n_out);
 }
 
 gm_status gm_get_normals(gm_ctx *ctx, uint32_t slot, float *nxyzc, uint32_t capacity, uint32_t *n_out)
@@ -1064,7 +1064,7 @@ gm_status gm_get_normals(gm_ctx *ctx, uint32_t slot, float *nxyzc, uint32_t capa
     gm_status st = check_slot(ctx, slot);
     if (st != GM_OK) return st;
     Slot &sl = ctx->slots[slot];
-    return fetch(ctx, slot, (const float4 *)sl.vnorm4, sl.last.n_valid, (float4 *)nxyzc, capacity, n_out);
+    return fetch(ctx, slot, (const float4 *)sl.normals4, sl.last.n_valid, (float4 *)nxyzc, capacity, n_out);
 }
 
 gm_status gm_get_voxel_centroids(gm_ctx *ctx, uint32_t slot, float *xyzc, uint32_t capacity, uint32_t *n_out)
@@ -1170,9 +1170,9 @@ gm_status gm_get_normals_stage(gm_ctx *ctx, const float *xyz, uint32_t n, double
     sl.last.n_valid = m[1];
     sl.submitted = true;  // accessors (neighbour counts) may read this slot
     sl.complete = true;
-    st = fetch(ctx, 0, (const float4 *)sl.valid4, m[1], (float4 *)xyzw_out, capacity, n_out);
+    st = fetch(ctx, 0, (const float4 *)sl.crop4, m[1], (float4 *)xyzw_out, capacity, n_out);
     if (st != GM_OK) return st;
-    return fetch(ctx, 0, (const float4 *)sl.vnorm4, m[1], (float4 *)nxyzc_out, capacity, n_out);
+    return fetch(ctx, 0, (const float4 *)sl.normals4, m[1], (float4 *)nxyzc_out, capacity, n_out);
 }
 
 gm_status gm_get_local_frame(gm_ctx *ctx, const float *nxyzc, uint32_t n, double wf, float eigenvalues[3],
@@ -1188,8 +1188,8 @@ gm_status gm_get_local_frame(gm_ctx *ctx, const float *nxyzc, uint32_t n, double
     if (st != GM_OK) return st;
     st = reset_counters(ctx, sl);
     if (st != GM_OK) return st;
-    if (n) GM_HIP(ctx, hipMemcpyAsync(sl.vnorm4, nxyzc, (size_t)n * 16, hipMemcpyHostToDevice, sl.stream));
-    const uint32_t np = launch_scatter_partials(sl.vnorm4, nullptr, n, wf, sl, sl.stream);
+    if (n) GM_HIP(ctx, hipMemcpyAsync(sl.normals4, nxyzc, (size_t)n * 16, hipMemcpyHostToDevice, sl.stream));
+    const uint32_t np = launch_scatter_partials(sl.normals4, nullptr, n, wf, sl, sl.stream);
     launch_frame_finalize(sl.partials, np, 0, sl, sl.stream);
     GM_HIP(ctx, hipMemcpyAsync(sl.h_out, sl.d_out, sizeof(FrameOut), hipMemcpyDeviceToHost, sl.stream));
     GM_HIP(ctx, hipStreamSynchronize(sl.stream));
@@ -1198,6 +1198,38 @@ gm_status gm_get_local_frame(gm_ctx *ctx, const float *nxyzc, uint32_t n, double
     if (eigenvectors) for (int k = 0; k < 9; ++k) eigenvectors[k] = sl.h_out->evecs[k];
     if (scatter6) for (int k = 0; k < 6; ++k) scatter6[k] = sl.h_out->scatter[k];
     return GM_OK;
+}
+
+gm_status gm_compact_valid_stage(gm_ctx *ctx, const float *xyzw, const float *nxyzc, uint32_t n, double wf, float *xyzw_out,
+                                 float *nxyzc_out, uint32_t capacity, uint32_t *n_out, double scatter6[6])
+{
+    Slot *slp;
+    gm_status st = begin_stage(ctx, slp);
+    if (st != GM_OK) return st;
+    if (n && (!xyzw || !nxyzc)) return fail(ctx, GM_ERR_INVALID_ARG, "rows pointer is NULL");
+    if (!(wf != 0.0)) return fail(ctx, GM_ERR_INVALID_ARG, "weighting factor must be non-zero");
+    Slot &sl = *slp;
+    st = ensure_capacity(ctx, sl, n ? n : 1u, 0, false);
+    if (st != GM_OK) return st;
+    st = reset_counters(ctx, sl);
+    if (st != GM_OK) return st;
+    if (n) {
+        GM_HIP(ctx, hipMemcpyAsync(sl.crop4, xyzw, (size_t)n * 16, hipMemcpyHostToDevice, sl.stream));
+        GM_HIP(ctx, hipMemcpyAsync(sl.normals4, nxyzc, (size_t)n * 16, hipMemcpyHostToDevice, sl.stream));
+    }
+    GM_HIP(ctx, hipMemcpyAsync(&sl.ctr->n_cropped, &n, 4, hipMemcpyHostToDevice, sl.stream));
+    uint32_t row_tile = kCpTile;
+    const uint32_t np = launch_compact_valid(sl, n, wf, sl.stream, &row_tile);
+    launch_frame_finalize(sl.tile_partials, np, row_tile, sl, sl.stream);
+    GM_HIP(ctx, hipMemcpyAsync(sl.h_out, sl.d_out, sizeof(FrameOut), hipMemcpyDeviceToHost, sl.stream));
+    GM_HIP(ctx, hipStreamSynchronize(sl.stream));
+    GM_HIP(ctx, hipGetLastError());
+    if (scatter6) for (int k = 0; k < 6; ++k) scatter6[k] = sl.h_out->scatter[k];
+    const uint32_t m = sl.h_out->ctr.n_valid;
+    if (m > n) return fail(ctx, GM_ERR_DEVICE, "gm_compact_valid_stage: more survivors than rows");
+    st = fetch(ctx, 0, (const float4 *)sl.crop4, m, (float4 *)xyzw_out, capacity, n_out);
+    if (st != GM_OK) return st;
+    return fetch(ctx, 0, (const float4 *)sl.normals4, m, (float4 *)nxyzc_out, capacity, n_out);
 }
 
 gm_status gm_voxel_grid(gm_ctx *ctx, const float *xyz, uint32_t n, double leaf, float *xyzc_out, uint32_t capacity,
@@ -1220,9 +1252,9 @@ gm_status gm_voxel_grid(gm_ctx *ctx, const float *xyz, uint32_t n, double leaf, 
         stage[i] = make_float4(p[0], p[1], p[2], 0.f);
         for (int k = 0; k < 3; ++k) { mn = fminf(mn, p[k]); mx = fmaxf(mx, p[k]); }
     }
-    if (n) GM_HIP(ctx, hipMemcpyAsync(sl.valid4, stage, (size_t)n * 16, hipMemcpyHostToDevice, sl.stream));
+    if (n) GM_HIP(ctx, hipMemcpyAsync(sl.crop4, stage, (size_t)n * 16, hipMemcpyHostToDevice, sl.stream));
     GM_HIP(ctx, hipMemcpyAsync(&sl.ctr->vox_n, &n, 4, hipMemcpyHostToDevice, sl.stream));
-    launch_minmax(sl.valid4, nullptr, n, sl.ctr, sl.stream);
+    launch_minmax(sl.crop4, nullptr, n, sl.ctr, sl.stream);
     launch_voxel_grid(sl, n, (float)leaf, n ? voxel_key_bits(mn, mx, leaf) : 1, sl.stream);
     uint32_t V = 0, pass = 0;
     GM_HIP(ctx, hipMemcpyAsync(&V, &sl.ctr->n_voxels, 4, hipMemcpyDeviceToHost, sl.stream));

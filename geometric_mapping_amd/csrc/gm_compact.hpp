@@ -22,13 +22,52 @@
 // epoch (a per-slot launch counter, never 0) makes the records of earlier launches read as "not there yet", so the array
 // is never cleared (zeroed once at allocation).  The block that takes the last ticket resets the ticket word for the
 // next launch on the stream.
+//
+// In place (Emit::kInPlace: the emit step stores into the arrays the predicate loads from, dst <= src; the NaN-normal
+// compaction, k_frame.hip).  A row may only be overwritten once its owner holds it in registers.  The rule:
+//   (1) a block publishes its first record only after ALL of its own payload loads have completed: every thread waits for
+//       its outstanding loads (s_waitcnt vmcnt(0): the data is in its registers -- the ballot alone only forces the wait for
+//       what the predicate tests) in front of the block barrier in front of the publish;
+//   (2) a block stores only after its look-back has seen a record of EVERY tile before it -- directly, or through an
+//       inclusive record, which its publisher wrote behind a walk of its own that had (induction over the tile index);
+//       the destinations are computed from the records read, and every thread issues an agent-scope acquire fence behind
+//       the walk;
+//   (3) dst <= src, so a block writes into its own tile and into tiles before it, nowhere else.
+// By (2) and (1) every tile a block can write into has finished loading when the block's first store is issued; inside
+// the block the barrier of (1) orders the waves' loads before any wave's stores.  No row is read after it was written: a
+// tile reads its own positions only, and they are written by itself or by later tiles, which (2) puts behind its loads.
+// Tiles are still handed out by ticket -- the progress argument above is untouched: a block waits only for blocks that
+// are already running.
+// (1) is a wait, not a release fence, and the records stay relaxed agent-scope atomics as in every other instantiation.
+// That is an argument about the machine, outside the C++ memory model (a relaxed store does not synchronise with an
+// acquire fence): a tile's loads have RETURNED before its record is issued (the asm's memory clobber keeps the compiler
+// from sinking them past the wait), a record is read only after it was issued, and the writer's destinations depend on
+// the records it read, so its stores are issued later still.  Nothing a block STORED is ever read by another block of
+// the launch except the record itself: there is nothing to make visible, only loads to be done with.  The rule written
+// with a release fence and release records (-DGM_CP_DIAG_INPLACE_FENCE builds it) costs three write-backs of the XCD's L2
+// (buffer_wbl2) per block, with the other blocks' moved rows dirty in that L2: a blocking 1 M-point frame with 1000
+// scattered drops takes 0.641-0.651 ms with it, 0.580-0.597 as built here, 0.545-0.553 with the two-buffer compaction
+// before (medians of three alternated runs of 20 frames; profiles/r15_valid_in_place.json, DESIGN.md par. 4).
+// Such an emit step also says where the first dropped element is (first_drop(), final before the launch: 0xFFFFFFFF =
+// nothing was dropped).  Nothing dropped: every block returns before taking a ticket, the shape of n == 0 -- the ticket
+// word stays 0 and the launch costs its dispatch.  A tile that ends at or before the first dropped element holds only
+// rows that stay where they are: behind its ticket it publishes INCLUSIVE | end and leaves without loading anything, so
+// nothing in front of the first dropped element is ever read or written (a copy of the head may be in flight elsewhere).
+// Such a record is the one inclusive record that has no walk behind it, and (2)'s induction does not need one there: a
+// moved row has dst >= the first dropped index, so no store of the launch lands in such a tile -- it has no loads that
+// anything would have to wait for.
 #pragma once
+
+#include <type_traits>
 
 #include "gm_device.hpp"
 
 namespace gm {
 
 struct NoPayload {};   // predicates that load nothing worth keeping
+
+template <class E, class = void> struct cp_in_place : std::false_type {};
+template <class E> struct cp_in_place<E, std::void_t<decltype(E::kInPlace)>> : std::bool_constant<E::kInPlace> {};
 
 #ifndef GM_CPTHREADS
 #define GM_CPTHREADS 512
@@ -52,7 +91,8 @@ inline uint32_t compact_grid(uint32_t n) { return compact_blocks(n); }          
 //       __device__ void finish(uint32_t tile) is called by every thread of the block once per tile that held input,
 //       after the tile's last emit (per-tile state lives in the functor; finish() resets it); static constexpr bool
 //       kHasPrepare; when true, __device__ void prepare() is called by every thread as the block starts (block-shared
-//       state of the emit step; a block barrier follows before the first emit)
+//       state of the emit step; a block barrier follows before the first emit); optional static constexpr bool kInPlace;
+//       when true, __device__ uint32_t first_drop() const and the rule in the head of this file
 // The element count is *n_ptr (device-resident) or n_host; the grid is compact_grid(capacity): a block per tile.  The number of survivors
 // goes to total_out / total_out2 (either may be null) -- also when it is 0.
 template <class Pred, class Emit, int THREADS = kCpThreads, int ITEMS = kCpItems>
@@ -63,6 +103,11 @@ __global__ __launch_bounds__(THREADS) void k_compact(Pred pred, Emit emit, const
 {
     static_assert(THREADS * ITEMS >= kCpMinTile, "tile below the size the record arrays are laid out for");
     constexpr uint64_t kAggregate = 1ull << 32, kInclusive = 2ull << 32;
+#ifdef GM_CP_DIAG_INPLACE_FENCE
+    constexpr int kPublish = cp_in_place<Emit>::value ? __ATOMIC_RELEASE : __ATOMIC_RELAXED;
+#else
+    constexpr int kPublish = __ATOMIC_RELAXED;
+#endif
     __shared__ uint32_t lb_sum[(THREADS / kWave)], lb_state[(THREADS / kWave)];
     __shared__ uint32_t wcnt[(THREADS / kWave)];
     const uint32_t n = n_ptr ? *n_ptr : n_host;
@@ -76,6 +121,12 @@ __global__ __launch_bounds__(THREADS) void k_compact(Pred pred, Emit emit, const
             if (total_out2) *total_out2 = 0;
         }
         return;
+    }
+    constexpr bool kInPlace = cp_in_place<Emit>::value;
+    uint32_t first_drop = 0xFFFFFFFFu;
+    if constexpr (kInPlace) {
+        first_drop = emit.first_drop();
+        if (first_drop == 0xFFFFFFFFu) return;  // every element stays where it is (no ticket is taken: the word stays 0)
     }
     __shared__ uint32_t s_tile;
     if constexpr (Emit::kHasPrepare) emit.prepare();
@@ -92,6 +143,15 @@ __global__ __launch_bounds__(THREADS) void k_compact(Pred pred, Emit emit, const
     const uint32_t tile = s_tile;
     if (tile < ntiles) {   // uniform per block; nothing after the end is ever looked at
         const uint32_t base = tile * (uint32_t)(THREADS * ITEMS);
+        if constexpr (kInPlace) {
+            // (first_drop < n, so such a tile is a whole one, every element of it survives and none of them moves)
+            if (base + (uint32_t)(THREADS * ITEMS) <= first_drop) {
+                if (threadIdx.x == 0)
+                    __hip_atomic_store(&st.status[tile], tag | kInclusive | (uint64_t)(base + (uint32_t)(THREADS * ITEMS)),
+                                       kPublish, __HIP_MEMORY_SCOPE_AGENT);
+                return;
+            }
+        }
         // A wave owns ITEMS * 64 CONSECUTIVE positions of the tile (item j of wave w: base + w * 64 ITEMS + 64 j + lane), so the
         // survivors of everything before item (w, j) are those of the waves before w -- one LDS word per wave -- plus those
         // of the wave's own earlier items, which it holds in scalar registers: the ranks need one barrier and (waves) LDS
@@ -110,6 +170,13 @@ __global__ __launch_bounds__(THREADS) void k_compact(Pred pred, Emit emit, const
             wtotal += (uint32_t)__popcll(mask[j]);
         }
         if (lane == 0) wcnt[w] = wtotal;
+        if constexpr (kInPlace) {   // rule (1): this thread's loads are done
+#ifdef GM_CP_DIAG_INPLACE_FENCE   // timing diagnostic only: the rule with a release fence and release records (see the head of this file)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+#else
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+        }
         __syncthreads();
         uint32_t total = 0, woff = 0;
 #pragma unroll
@@ -119,7 +186,7 @@ __global__ __launch_bounds__(THREADS) void k_compact(Pred pred, Emit emit, const
             total += c;
         }
         if (threadIdx.x == 0)
-            __hip_atomic_store(&st.status[tile], tag | (tile == 0 ? kInclusive : kAggregate) | total, __ATOMIC_RELAXED,
+            __hip_atomic_store(&st.status[tile], tag | (tile == 0 ? kInclusive : kAggregate) | total, kPublish,
                                __HIP_MEMORY_SCOPE_AGENT);
         // ---- look back.  The whole block does, one record per thread (tile-1-t): the blocks of a 1 M-point frame all
         // run at once, so inclusive prefixes are rare when the walk starts and a 64-wide window would need several
@@ -164,9 +231,10 @@ __global__ __launch_bounds__(THREADS) void k_compact(Pred pred, Emit emit, const
                 top -= THREADS;
             }
             if (threadIdx.x == 0)
-                __hip_atomic_store(&st.status[tile], tag | kInclusive | (uint64_t)(before + total), __ATOMIC_RELAXED,
+                __hip_atomic_store(&st.status[tile], tag | kInclusive | (uint64_t)(before + total), kPublish,
                                    __HIP_MEMORY_SCOPE_AGENT);
         }
+        if constexpr (kInPlace) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // rule (2)
         if (threadIdx.x == 0 && tile == ntiles - 1) {  // the last tile knows the number of survivors
 #ifdef GM_CP_DIAG_NOLOOKBACK
             if (total_out) *total_out = 0;    // (nothing downstream may look at the holes)

@@ -56,7 +56,7 @@ gm_status score(gm_ctx *ctx, int model, const float *xyz, uint32_t n, const uint
     gm_status st = prepare(ctx, slp, n, H);
     if (st != GM_OK) return st;
     Slot &sl = *slp;
-    st = upload_xyz(ctx, sl, xyz, n, sl.valid4);
+    st = upload_xyz(ctx, sl, xyz, n, sl.crop4);
     if (st != GM_OK) return st;
     st = upload_labels(ctx, sl, labels, n);
     if (st != GM_OK) return st;
@@ -73,7 +73,7 @@ gm_status score(gm_ctx *ctx, int model, const float *xyz, uint32_t n, const uint
         for (int k = 0; k < w; ++k) stage[8 * (size_t)h + k] = hyp[(size_t)w * h + k];
     float *dh = model == 0 ? sl.hyp_plane : sl.hyp_cyl;
     GMX_HIP(ctx, hipMemcpyAsync(dh, stage, (size_t)H * 32, hipMemcpyHostToDevice, sl.stream));
-    launch_score(model, sl.valid4, labels ? sl.labels : nullptr, want, nullptr, n, dh, sl.band, H, tau, sl.score_partial,
+    launch_score(model, sl.crop4, labels ? sl.labels : nullptr, want, nullptr, n, dh, sl.band, H, tau, sl.score_partial,
                  sl.cnt_plane, sl.best_plane, sl.stream);
     GMX_HIP(ctx, hipMemcpyAsync(counts, sl.cnt_plane, (size_t)H * 4, hipMemcpyDeviceToHost, sl.stream));
     GMX_HIP(ctx, hipStreamSynchronize(sl.stream));
@@ -123,7 +123,7 @@ gm_status gm_score_frame(gm_ctx *ctx, uint32_t slot, int model, const float *hyp
     GMX_HIP(ctx, hipMemcpyAsync(dh, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, sl.stream));
     GMX_HIP(ctx, hipStreamSynchronize(sl.stream));  // `rows` is pageable and about to go away
     // exhaustive scorer over the slot's resident valid cloud (owned points only: halo rows never reach it)
-    launch_score(model, sl.valid4, unlabelled_only ? sl.labels : nullptr, 0, &sl.ctr->n_valid, sl.last.n_valid, dh, sl.band,
+    launch_score(model, sl.crop4, unlabelled_only ? sl.labels : nullptr, 0, &sl.ctr->n_valid, sl.last.n_valid, dh, sl.band,
                  H, tau, nullptr, sl.cnt_plane, sl.score_partial + 600, sl.stream);
     GMX_HIP(ctx, hipMemcpyAsync(counts, sl.cnt_plane, (size_t)H * 4, hipMemcpyDeviceToHost, sl.stream));
     GMX_HIP(ctx, hipStreamSynchronize(sl.stream));
@@ -140,11 +140,11 @@ gm_status gm_plane_hypotheses(gm_ctx *ctx, const float *xyz, uint32_t n, const u
     gm_status st = prepare(ctx, slp, n, H);
     if (st != GM_OK) return st;
     Slot &sl = *slp;
-    st = upload_xyz(ctx, sl, xyz, n, sl.valid4);
+    st = upload_xyz(ctx, sl, xyz, n, sl.crop4);
     if (st != GM_OK) return st;
     st = upload_labels(ctx, sl, labels, n);
     if (st != GM_OK) return st;
-    launch_plane_hypotheses(sl.valid4, labels ? sl.labels : nullptr, want, nullptr, n, seed, H, sl.hyp_plane, nullptr,
+    launch_plane_hypotheses(sl.crop4, labels ? sl.labels : nullptr, want, nullptr, n, seed, H, sl.hyp_plane, nullptr,
                             sl.stream);
     if ((size_t)H * 32 > sl.raw_cap) {
         st = gm_ensure_capacity(ctx, sl, n, (size_t)H * 32, true);
@@ -168,12 +168,12 @@ gm_status gm_cylinder_hypotheses(gm_ctx *ctx, const float *xyz, const float *nxy
     gm_status st = prepare(ctx, slp, n, H);
     if (st != GM_OK) return st;
     Slot &sl = *slp;
-    st = upload_xyz(ctx, sl, xyz, n, sl.valid4);
+    st = upload_xyz(ctx, sl, xyz, n, sl.crop4);
     if (st != GM_OK) return st;
-    if (n) GMX_HIP(ctx, hipMemcpyAsync(sl.vnorm4, nxyzc, (size_t)n * 16, hipMemcpyHostToDevice, sl.stream));
+    if (n) GMX_HIP(ctx, hipMemcpyAsync(sl.normals4, nxyzc, (size_t)n * 16, hipMemcpyHostToDevice, sl.stream));
     st = upload_labels(ctx, sl, labels, n);
     if (st != GM_OK) return st;
-    launch_cylinder_hypotheses(sl.valid4, sl.vnorm4, labels ? sl.labels : nullptr, want, nullptr, n, seed, H, sl.hyp_cyl,
+    launch_cylinder_hypotheses(sl.crop4, sl.normals4, labels ? sl.labels : nullptr, want, nullptr, n, seed, H, sl.hyp_cyl,
                                nullptr, nullptr, 0.0, sl.stream);
     if ((size_t)H * 32 > sl.raw_cap) {
         st = gm_ensure_capacity(ctx, sl, n, (size_t)H * 32, true);
@@ -197,12 +197,12 @@ gm_status gm_segment_moments(gm_ctx *ctx, const float *xyz, const float *nxyzc, 
     gm_status st = prepare(ctx, slp, n, 1);
     if (st != GM_OK) return st;
     Slot &sl = *slp;
-    st = upload_xyz(ctx, sl, xyz, n, sl.valid4);
+    st = upload_xyz(ctx, sl, xyz, n, sl.crop4);
     if (st != GM_OK) return st;
-    if (n && nxyzc) GMX_HIP(ctx, hipMemcpyAsync(sl.vnorm4, nxyzc, (size_t)n * 16, hipMemcpyHostToDevice, sl.stream));
+    if (n && nxyzc) GMX_HIP(ctx, hipMemcpyAsync(sl.normals4, nxyzc, (size_t)n * 16, hipMemcpyHostToDevice, sl.stream));
     st = upload_labels(ctx, sl, labels, n);
     if (st != GM_OK) return st;
-    launch_segment_moments(sl.valid4, nxyzc ? sl.vnorm4 : nullptr, labels ? sl.labels : nullptr, label, nullptr, n,
+    launch_segment_moments(sl.crop4, nxyzc ? sl.normals4 : nullptr, labels ? sl.labels : nullptr, label, nullptr, n,
                            sl.mom_partial, sl.mom_plane, sl.stream);
     GMX_HIP(ctx, hipMemcpyAsync(mom16, sl.mom_plane, 16 * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
     GMX_HIP(ctx, hipStreamSynchronize(sl.stream));
@@ -219,11 +219,11 @@ gm_status gm_nearest(gm_ctx *ctx, const float *xyz, uint32_t n, const float *que
     gm_status st = prepare(ctx, slp, m, 1);
     if (st != GM_OK) return st;
     Slot &sl = *slp;
-    st = upload_xyz(ctx, sl, xyz, n, sl.valid4);
+    st = upload_xyz(ctx, sl, xyz, n, sl.crop4);
     if (st != GM_OK) return st;
     st = upload_xyz(ctx, sl, queries, nq, sl.vox4);
     if (st != GM_OK) return st;
-    launch_nearest(sl.valid4, nullptr, n, sl.vox4, nullptr, nq, sl.nn_best, sl.vox_nn, sl.stream);
+    launch_nearest(sl.crop4, nullptr, n, sl.vox4, nullptr, nq, sl.nn_best, sl.vox_nn, sl.stream);
     if (nq) GMX_HIP(ctx, hipMemcpyAsync(idx_out, sl.vox_nn, (size_t)nq * 4, hipMemcpyDeviceToHost, sl.stream));
     GMX_HIP(ctx, hipStreamSynchronize(sl.stream));
     GMX_HIP(ctx, hipGetLastError());
@@ -296,7 +296,7 @@ gm_status gm_fit_cylinder(gm_ctx *ctx, const float *xyz, uint32_t n, const uint8
     gm_status st = prepare(ctx, slp, n, 1);
     if (st != GM_OK) return st;
     Slot &sl = *slp;
-    st = upload_xyz(ctx, sl, xyz, n, sl.valid4);
+    st = upload_xyz(ctx, sl, xyz, n, sl.crop4);
     if (st != GM_OK) return st;
     st = upload_labels(ctx, sl, labels, n);
     if (st != GM_OK) return st;
@@ -305,7 +305,7 @@ gm_status gm_fit_cylinder(gm_ctx *ctx, const float *xyz, uint32_t n, const uint8
     GMX_HIP(ctx, hipMemcpyAsync(sl.fit_init, row, sizeof(row), hipMemcpyHostToDevice, sl.stream));
     if (n) GMX_HIP(ctx, hipMemsetAsync(sl.inl_mask, 0, n, sl.stream));
     CylFitArgs a;
-    a.pts = sl.valid4; a.labels = labels ? sl.labels : nullptr; a.out = sl.inl_mask;
+    a.pts = sl.crop4; a.labels = labels ? sl.labels : nullptr; a.out = sl.inl_mask;
     a.want = want; a.want2 = want; a.mask_mode = 1;
     a.n_ptr = nullptr; a.n_host = n;
     a.init = sl.fit_init; a.best = nullptr;
@@ -423,7 +423,7 @@ gm_status gm_surface_map(gm_ctx *ctx, const float *xyz, uint32_t n, const uint8_
     if (st != GM_OK) return st;
     st = gm_ensure_surface(ctx, sl);
     if (st != GM_OK) return st;
-    st = upload_xyz(ctx, sl, xyz, n, sl.valid4);
+    st = upload_xyz(ctx, sl, xyz, n, sl.crop4);
     if (st != GM_OK) return st;
     st = upload_labels(ctx, sl, labels, n);
     if (st != GM_OK) return st;
@@ -435,7 +435,7 @@ gm_status gm_surface_map(gm_ctx *ctx, const float *xyz, uint32_t n, const uint8_
     GMX_HIP(ctx, hipMemcpyAsync(sl.surf_fit, &f, sizeof(f), hipMemcpyHostToDevice, sl.stream));
     GMX_HIP(ctx, hipMemcpyAsync(sl.surf_prm + 1, &d, sizeof(d), hipMemcpyHostToDevice, sl.stream));
     SurfArgs a;
-    a.pts = sl.valid4; a.labels = labels ? sl.labels : nullptr; a.n_ptr = nullptr; a.n_host = n;
+    a.pts = sl.crop4; a.labels = labels ? sl.labels : nullptr; a.n_ptr = nullptr; a.n_host = n;
     a.fit = sl.surf_fit; a.prm = sl.surf_prm + 1;
     a.table = sl.surf_table; a.cells = sl.surf_cells; a.info = sl.surf_info; a.res = sl.surf_res; a.cell = sl.surf_cell;
     launch_surface_map(a, n, sl.stream);

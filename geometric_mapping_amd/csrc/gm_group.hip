@@ -758,9 +758,9 @@ gm_status gm_group_get_voxel_normals(gm_group *grp, float *nxyzc, uint32_t capac
                 const uint32_t nq = V - q0 < sl.cap ? V - q0 : sl.cap;
                 if (hipMemcpyAsync(sl.vox4, &G.vox_cen[(size_t)q0 * 4], (size_t)nq * 16, hipMemcpyHostToDevice, sl.stream) != hipSuccess)
                     return gfail(grp, GM_ERR_DEVICE, "gm_group: upload of the merged centroids failed");
-                launch_nearest(sl.valid4, &sl.ctr->n_valid, sl.cap, sl.vox4, nullptr, nq, sl.nn_best, sl.vox_nn, sl.stream, sl.vnorm4, sl.vox_nrm4);
+                launch_nearest(sl.crop4, &sl.ctr->n_valid, sl.cap, sl.vox4, nullptr, nq, sl.nn_best, sl.vox_nn, sl.stream, sl.normals4, sl.vox_nrm4);
                 hipLaunchKernelGGL(k_gather_nearest, dim3((nq + 255) / 256), dim3(256), 0, sl.stream, (const int32_t *)sl.vox_nn, nq,
-                                   (const float4 *)sl.valid4, sl.spts4);
+                                   (const float4 *)sl.crop4, sl.spts4);
                 keys.resize(nq); nrm.resize((size_t)nq * 4); pts.resize((size_t)nq * 4);
                 if (hipMemcpyAsync(keys.data(), sl.nn_best, (size_t)nq * 8, hipMemcpyDeviceToHost, sl.stream) != hipSuccess ||
                     hipMemcpyAsync(nrm.data(), sl.vox_nrm4, (size_t)nq * 16, hipMemcpyDeviceToHost, sl.stream) != hipSuccess ||
@@ -884,10 +884,10 @@ gm_status gm_group_fit_cylinder(gm_group *grp, const float init7[7], gm_cylinder
             hipMemcpyAsync(f.plane_best, &plane_best, sizeof(uint32_t), hipMemcpyHostToDevice, sl.stream) != hipSuccess)
             return fail_enqueued(GM_ERR_DEVICE, "gm_group_fit_cylinder: upload of the starting rows failed");
         // plane relabel: every valid point 1 if it is an inlier of the published plane (the RANSAC's fp32 predicate), else 0
-        launch_label(0, sl.valid4, sl.labels, 0, 1, &sl.ctr->n_valid, sl.last.n_valid, f.rows8 + 8, nullptr, f.plane_best,
+        launch_label(0, sl.crop4, sl.labels, 0, 1, &sl.ctr->n_valid, sl.last.n_valid, f.rows8 + 8, nullptr, f.plane_best,
                      tau, 1, nullptr, nullptr, 0, sl.stream);
         CylFitArgs &a = args[r];
-        a.pts = sl.valid4; a.labels = sl.labels; a.out = sl.labels;
+        a.pts = sl.crop4; a.labels = sl.labels; a.out = sl.labels;
         a.want = 0; a.want2 = 0; a.mask_mode = 0;   // eligible: what the published plane left
         a.n_ptr = &sl.ctr->n_valid; a.n_host = sl.last.n_valid;
         a.init = f.rows8; a.best = nullptr;

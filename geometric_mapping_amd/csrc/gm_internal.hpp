@@ -46,14 +46,14 @@ struct Slot {
     size_t raw_cap = 0;        // bytes
     HostArray<uint8_t> h_raw;  // pinned staging for the incoming rows
     DevArray<uint8_t> d_raw;
-    DevArray<float4> crop4;   // cropped cloud: x,y,z, bits(input row)
+    DevArray<float4> crop4;   // cropped cloud: x,y,z, bits(input row); behind the NaN-normal compaction, which works in place
+                              // (k_frame.hip), the valid cloud: rows [0, n_valid)
     DevArray<uint32_t> keys_a, keys_b, vals_a, vals_b;
     DevArray<float4> spts4;   // cropped cloud in cell-sorted order: x,y,z, bits(cropped index)
     uint32_t *skeys = nullptr; // == whichever of keys_a/keys_b holds the sorted keys
-    DevArray<float4> normals4;   // per cropped point: nx,ny,nz,curvature (NaN when <3 neighbours)
+    DevArray<float4> normals4;   // per cropped point: nx,ny,nz,curvature (NaN when <3 neighbours); behind the compaction the
+                                 // valid cloud's normals, row for row
     DevArray<int32_t> counts;    // per cropped point neighbour count (GM_CFG_KEEP_COUNTS)
-    DevArray<float4> valid4;     // compacted cloud (finite normals)
-    DevArray<float4> vnorm4;     // compacted normals
     DevArray<uint2> tiles;
     uint32_t tiles_cap = 0;   // entries of the tile list's last class (every tile of a frame fits)
     uint32_t tile_seg = 0;    // entries of each of its other kTileListClasses - 1 classes
@@ -84,7 +84,7 @@ struct Slot {
     DevArray<VoxCell> vox_table; // dense voxel table (fast path)
     DevArray<int32_t> vox_nn;
     DevArray<double> partials;   // [kScatterBlocks][6]  (gm_get_local_frame on caller-supplied normals)
-    DevArray<double> tile_partials;  // [compact_blocks(cap)][6]  scatter rows left by the NaN-normal compaction
+    DevArray<double> tile_partials;  // [compact_records(cap)][6]  scatter rows left by the NaN-normal compaction
     DevArray<uint8_t> labels;
     DevArray<uint8_t> inl_mask;   // per valid point: which of the last RANSAC stage's hypotheses it is an inlier of
     DevArray<DevCounters> ctr;
@@ -202,11 +202,12 @@ void launch_zero_fill(const ZeroJobs &jobs, hipStream_t s);
 uint32_t max_tiles(uint32_t n_cap, const GridParams &g);
 uint32_t tile_cutter_blocks(uint32_t n_cap);   // blocks (= chained-scan records per class) of k_rows_and_tiles
 // k_frame.hip
-// NaN-normal compaction; also leaves the scatter-matrix partial rows of the survivors in sl.tile_partials (one per
-// kCpTile cropped points); returns the number of rows launched
+// NaN-normal compaction, in place: crop4 / normals4 [0, n_valid) become the valid cloud and its normals (two launches:
+// k_valid_scan, then the move of the rows behind the first dropped point); also leaves the scatter-matrix partial rows of
+// the survivors in sl.tile_partials (one per *row_tile cropped points); returns the number of rows launched
 uint32_t launch_compact_valid(Slot &sl, uint32_t n_cap, double weightingFactor, hipStream_t s, uint32_t *row_tile = nullptr);
-// scatter partials over vnorm4[0..n); returns the number of partial rows written
-uint32_t launch_scatter_partials(const float4 *vnorm4, const uint32_t *n_ptr, uint32_t n_cap, double wf, Slot &sl,
+// scatter partials over nrm4[0..n); returns the number of partial rows written
+uint32_t launch_scatter_partials(const float4 *nrm4, const uint32_t *n_ptr, uint32_t n_cap, double wf, Slot &sl,
                                  hipStream_t s);
 void launch_rows_to_host(const float4 *src, float4 *dst_mapped, const uint32_t *begin_enc, const uint32_t *end_ptr, hipStream_t s);
 void launch_frame_finalize(const double *partials, uint32_t n_partials, uint32_t row_tile, Slot &sl, hipStream_t s);

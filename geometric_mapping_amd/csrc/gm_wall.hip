@@ -332,9 +332,9 @@ struct StageCall {
     gm_status upload(const float *xyz, const uint8_t *labels, WallArgs &w)
     {
         gm_ctx *ctx = map->ctx;
-        GMW_OK(gm_upload_xyz(ctx, *sl, xyz, n, sl->valid4));
+        GMW_OK(gm_upload_xyz(ctx, *sl, xyz, n, sl->crop4));
         if (labels && n) GMW_HIP(ctx, hipMemcpyAsync(sl->labels, labels, n, hipMemcpyHostToDevice, sl->stream));
-        w.pts = sl->valid4;
+        w.pts = sl->crop4;
         w.labels = labels ? sl->labels : nullptr;
         w.n_ptr = nullptr;
         w.n_host = n;
@@ -770,7 +770,7 @@ gm_status gm_wall_map_add_frame(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, co
     WallArgs w;
     GMW_OK(add_frame_args(map, pose, add_info, w));
     if (hipSetDevice(ctx->device) != hipSuccess) return gm_fail(ctx, GM_ERR_DEVICE, "hipSetDevice failed");
-    w.pts = sl.valid4;
+    w.pts = sl.crop4;
     w.labels = (ctx->cfg.flags & GM_CFG_RANSAC_PLANE) ? sl.labels : nullptr;   // (label 1 exists with the plane RANSAC only)
     w.n_ptr = &sl.ctr->n_valid;
     w.n_host = sl.n_in;
@@ -1202,7 +1202,7 @@ gm_status gm_wall_map_check_frame(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, 
     ScanState scan;
     GMW_OK(check_prepare(map, slot, n_cap, sl.stream, scan));
     GMW_OK(check_wait_adds(map, slot, sl.stream));
-    a.w.pts = sl.valid4;
+    a.w.pts = sl.crop4;
     a.w.labels = (ctx->cfg.flags & GM_CFG_RANSAC_PLANE) ? sl.labels : nullptr;
     a.w.n_ptr = &sl.ctr->n_valid;
     a.w.n_host = sl.n_in;

@@ -1,4 +1,4 @@
-// k_frame.hip -- NaN-normal compaction, the curvature-weighted normal scatter
+// k_frame.hip -- NaN-normal compaction (in place), the curvature-weighted normal scatter
 // matrix and its 3x3 eigen-decomposition (the "centre axis" fit).
 //
 // Replaces
@@ -17,22 +17,44 @@
 
 namespace gm {
 
-// ---- compaction of points with a finite normal ----------------------------------
+// ---- compaction of points with a finite normal, in place -------------------------
 // removeNaNNormalsFromPointCloud's predicate: all three components finite.  (k_normals stores no normal for a point the
-// rank does not own, so slab ownership needs no test of its own.)  The normal rides to the emit step in registers.
-struct ValidPred {
-    const float4 *__restrict__ normals4;
-    uint32_t *__restrict__ first_drop_enc;   // DevCounters::first_drop_enc: up to the first dropped point the valid cloud IS the cropped cloud
-    typedef float4 Payload;
+// rank does not own, so slab ownership needs no test of its own.)
+//
+// k_normals writes normals4[cropped index] and crop4 is in cropped order: up to the first point that loses its normal the
+// valid cloud IS the cropped cloud, row for row -- on a dense frame all of it.  So the valid cloud lives in crop4 and its
+// normals in normals4, and the compaction is two launches:
+//   k_valid_scan  reads the normals once: survivor count, first dropped index, getLocalFrame's scatter rows.  Moves nothing,
+//                 waits for nobody.
+//   k_compact<MovePred, MoveEmit>  moves the rows behind the first dropped point down, in place (gm_compact.hpp: the
+//                 in-place rule).  On a dense frame every block of it returns at once.
+struct MoveRow { float4 nrm, row; };
+struct MovePred {
+    const float4 *normals4;   // (not __restrict__: the emit step stores into both arrays)
+    const float4 *crop4;
+    typedef MoveRow Payload;
     __device__ __forceinline__ bool operator()(uint32_t i, Payload &p) const
     {
-        p = normals4[i];
-        const bool ok = finite3(p.x, p.y, p.z);
-        if (!ok) {   // (rare on dense frames; a lane only adds what can still raise the maximum it last saw)
-            const uint32_t enc = 0xFFFFFFFFu - i;
-            if (*first_drop_enc < enc) atomicMax(first_drop_enc, enc);
-        }
-        return ok;
+        // both loads at once: waiting for the normal before asking for the row would save the rows of the dropped points
+        // (rare) and put a second memory round trip into every item
+        p.nrm = normals4[i];
+        p.row = crop4[i];
+        return finite3(p.nrm.x, p.nrm.y, p.nrm.z);
+    }
+};
+struct MoveEmit {
+    static constexpr bool kHasFinish = false, kHasPrepare = false, kInPlace = true;
+    float4 *crop4;       // (not __restrict__: what the predicate loads from)
+    float4 *normals4;
+    const uint32_t *__restrict__ first_drop_enc;   // DevCounters::first_drop_enc, final: k_valid_scan ran before this launch
+    __device__ __forceinline__ uint32_t first_drop() const
+    {
+        const uint32_t e = *first_drop_enc;
+        return e ? 0xFFFFFFFFu - e : 0xFFFFFFFFu;
+    }
+    __device__ __forceinline__ void operator()(uint32_t src, uint32_t dst, const MoveRow &p)
+    {
+        if (dst != src) { crop4[dst] = p.row; normals4[dst] = p.nrm; }
     }
 };
 
@@ -90,30 +112,55 @@ __device__ __forceinline__ void scatter_row_store(const double m[6], double *__r
     }
 }
 
-// The compaction's emit step also accumulates the survivors' scatter terms -- the normals are in registers anyway -- and
-// leaves one partial row per tile (index = tile, i.e. position order: the rows do not depend on which block ran which
-// tile), so getLocalFrame needs no pass of its own over the compacted normals.
-struct ValidEmit {
-    static constexpr bool kHasFinish = true, kHasPrepare = false;
-    const float4 *__restrict__ crop4;
-    float4 *__restrict__ valid4;
-    float4 *__restrict__ vnorm4;
-    double k_wf;                     // .001 / weightingFactor
-    double *__restrict__ partials;   // [tiles][6]
-    double m[6];
-    __device__ __forceinline__ void operator()(uint32_t src, uint32_t dst, const float4 &v)
-    {
-        valid4[dst] = crop4[src];
-        vnorm4[dst] = v;
-        scatter_term(v, k_wf, m);
-    }
-    __device__ __forceinline__ void finish(uint32_t tile)
-    {
-        scatter_row_store(m, partials + (size_t)tile * 6);
+// One block per tile of THREADS * ITEMS cropped points, tile = blockIdx.x: no block waits for another.  Item ownership is
+// k_compact's (item j of wave w: base + w * 64 ITEMS + 64 j + lane) and a lane adds its survivors' scatter terms in j
+// order, so the partial row of a tile (index = tile, i.e. position order) holds the same fp64 sums, added in the same
+// order, as when the compaction's emit step summed them.  The survivor count goes to n_valid and vox_n (zero when the
+// frame opens / after reset_counters) by one integer atomic per tile, the first dropped index to first_drop_enc by
+// atomicMax: up to it the valid cloud IS the cropped cloud.
+template <int THREADS, int ITEMS>
+__global__ __launch_bounds__(THREADS) void k_valid_scan(const float4 *__restrict__ normals4, const uint32_t *__restrict__ n_ptr,
+                                                        double k_wf /* .001 / weightingFactor */,
+                                                        double *__restrict__ partials /* [tiles][6] */,
+                                                        DevCounters *__restrict__ ctr)
+{
+    __shared__ uint32_t wcnt[THREADS / kWave];
+    const uint32_t n = *n_ptr;
+    const uint32_t tile = blockIdx.x, base = tile * (uint32_t)(THREADS * ITEMS);
+    if (base >= n) return;   // (uniform per block; n == 0: nothing is written, the counters are 0 already)
+    const int w = threadIdx.x / kWave, lane = lane_id();
+    const uint32_t wbase = base + (uint32_t)w * (uint32_t)(kWave * ITEMS);
+    float4 v[ITEMS];
 #pragma unroll
-        for (int k = 0; k < 6; ++k) m[k] = 0;   // the block's next tile starts afresh
+    for (int j = 0; j < ITEMS; ++j) {
+        const uint32_t i = wbase + j * kWave + lane;
+        if (i < n) v[j] = normals4[i];
     }
-};
+    double m[6] = {0, 0, 0, 0, 0, 0};
+    uint32_t cnt = 0;
+#pragma unroll
+    for (int j = 0; j < ITEMS; ++j) {
+        const uint32_t i = wbase + j * kWave + lane;
+        if (i < n) {
+            if (finite3(v[j].x, v[j].y, v[j].z)) {
+                scatter_term(v[j], k_wf, m);
+                ++cnt;
+            } else {   // (rare on dense frames; a lane only adds what can still raise the maximum it last saw)
+                const uint32_t enc = 0xFFFFFFFFu - i;
+                if (ctr->first_drop_enc < enc) atomicMax(&ctr->first_drop_enc, enc);
+            }
+        }
+    }
+    cnt = wave_sum(cnt);
+    if (lane == 0) wcnt[w] = cnt;
+    scatter_row_store(m, partials + (size_t)tile * 6);   // (its barrier also covers wcnt)
+    if (threadIdx.x == 0) {
+        uint32_t total = 0;
+#pragma unroll
+        for (int k = 0; k < THREADS / kWave; ++k) total += wcnt[k];
+        if (total) { atomicAdd(&ctr->n_valid, total); atomicAdd(&ctr->vox_n, total); }
+    }
+}
 
 // min/max of x,y,z over pts[0..n) (getMinMax3D of pcl::VoxelGrid) -> ordered uints
 __global__ __launch_bounds__(256) void k_minmax(const float4 *__restrict__ pts, const uint32_t *__restrict__ n_ptr,
@@ -163,29 +210,42 @@ void launch_minmax(const float4 *pts, const uint32_t *n_ptr, uint32_t n_cap, Dev
 uint32_t launch_compact_valid(Slot &sl, uint32_t n_cap, double wf, hipStream_t s, uint32_t *row_tile)
 {
     // Tile: 4096 points (512 threads x 8); 8192 (1024 x 8) for frames of several million points, as for the crop
-    // (k_crop.hip: fewer tickets and look-backs per byte).  GM_VALID_TILE=<threads>x<items>: experiments.
+    // (k_crop.hip: fewer tickets and look-backs per byte).  GM_VALID_TILE=1024x8 | 512x8 | 256x8: experiments and tests.
     static const char *e = getenv("GM_VALID_TILE");
     int th = 512, it = 8;
     if (e) sscanf(e, "%dx%d", &th, &it);
     else if (n_cap > 2000000u) { th = 1024; it = 8; }   // (10 M points: 122 -> 109 us; 3 M: 44 -> 38)
-    const bool big = th == 1024 && it == 8;
-    const uint32_t tile = big ? 8192u : (uint32_t)kCpTile;
+    const bool big = th == 1024 && it == 8, small = th == 256 && it == 8;   // (any other value: the default tile)
+    const uint32_t tile = big ? 8192u : (small ? (uint32_t)kCpMinTile : (uint32_t)kCpTile);
     if (row_tile) *row_tile = tile;
     const uint32_t nb = (n_cap + tile - 1) / tile;
     if (nb == 0) return 0;
-    ValidPred pred{sl.normals4, &sl.ctr->first_drop_enc};
-    ValidEmit emit{sl.crop4, sl.valid4, sl.vnorm4, .001 / wf, sl.tile_partials, {0, 0, 0, 0, 0, 0}};
-    if (big)
-        hipLaunchKernelGGL((k_compact<ValidPred, ValidEmit, 1024, 8>), dim3(nb), dim3(1024), 0, s, pred, emit,
-                           (const uint32_t *)&sl.ctr->n_cropped, 0u, next_scan(sl), &sl.ctr->n_valid, &sl.ctr->vox_n);
-    else
-        hipLaunchKernelGGL((k_compact<ValidPred, ValidEmit>), dim3(nb), dim3(kCpThreads), 0, s, pred, emit,
-                           (const uint32_t *)&sl.ctr->n_cropped, 0u, next_scan(sl), &sl.ctr->n_valid, &sl.ctr->vox_n);
+    const uint32_t *n_ptr = &sl.ctr->n_cropped;
+    const float4 *nrm = sl.normals4;
+    double *rows = sl.tile_partials;   // [compact_records(cap)][6]: a row per tile of the finest shape
+    DevCounters *ctr = sl.ctr;
+    const double k_wf = .001 / wf;
+    MovePred pred{sl.normals4, sl.crop4};
+    MoveEmit emit{sl.crop4, sl.normals4, &sl.ctr->first_drop_enc};
+    uint32_t *const none = nullptr;   // (the counts are final before the move)
+    if (big) {
+        hipLaunchKernelGGL((k_valid_scan<1024, 8>), dim3(nb), dim3(1024), 0, s, nrm, n_ptr, k_wf, rows, ctr);
+        hipLaunchKernelGGL((k_compact<MovePred, MoveEmit, 1024, 8>), dim3(nb), dim3(1024), 0, s, pred, emit, n_ptr, 0u,
+                           next_scan(sl), none, none);
+    } else if (small) {
+        hipLaunchKernelGGL((k_valid_scan<256, 8>), dim3(nb), dim3(256), 0, s, nrm, n_ptr, k_wf, rows, ctr);
+        hipLaunchKernelGGL((k_compact<MovePred, MoveEmit, 256, 8>), dim3(nb), dim3(256), 0, s, pred, emit, n_ptr, 0u,
+                           next_scan(sl), none, none);
+    } else {
+        hipLaunchKernelGGL((k_valid_scan<kCpThreads, kCpItems>), dim3(nb), dim3(kCpThreads), 0, s, nrm, n_ptr, k_wf, rows, ctr);
+        hipLaunchKernelGGL((k_compact<MovePred, MoveEmit>), dim3(nb), dim3(kCpThreads), 0, s, pred, emit, n_ptr, 0u,
+                           next_scan(sl), none, none);
+    }
     return nb;  // partial rows: one per tile that held input (the finalizer derives how many from n_cropped)
 }
 
 // ---- scatter matrix: streaming pass ---------------------------------------------
-__global__ __launch_bounds__(256) void k_scatter_partials(const float4 *__restrict__ vnorm4,
+__global__ __launch_bounds__(256) void k_scatter_partials(const float4 *__restrict__ nrm4,
                                                           const uint32_t *__restrict__ n_ptr, uint32_t n_host,
                                                           double k_wf /* .001 / weightingFactor */,
                                                           double *__restrict__ partials)
@@ -193,7 +253,7 @@ __global__ __launch_bounds__(256) void k_scatter_partials(const float4 *__restri
     const uint32_t n = n_ptr ? *n_ptr : n_host;
     double m[6] = {0, 0, 0, 0, 0, 0};
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-        scatter_term(vnorm4[i], k_wf, m);  // one coalesced 16 B load per lane: nx,ny,nz,curvature
+        scatter_term(nrm4[i], k_wf, m);  // one coalesced 16 B load per lane: nx,ny,nz,curvature
     scatter_row_store(m, partials + (size_t)blockIdx.x * 6);
 }
 
@@ -207,7 +267,7 @@ __global__ __launch_bounds__(256) void k_frame_finalize(const double *__restrict
     frame_finalize_block(partials, nblocks, ctr, voxp, out, red, row_tile);
 }
 
-uint32_t launch_scatter_partials(const float4 *vnorm4, const uint32_t *n_ptr, uint32_t n_cap, double wf, Slot &sl,
+uint32_t launch_scatter_partials(const float4 *nrm4, const uint32_t *n_ptr, uint32_t n_cap, double wf, Slot &sl,
                                  hipStream_t s)
 {
     // ~4096 points per block (16 per thread in flight), at least 64 and at most kScatterBlocks blocks: a 1 M-point frame
@@ -216,7 +276,7 @@ uint32_t launch_scatter_partials(const float4 *vnorm4, const uint32_t *n_ptr, ui
     if (nb < 64u) nb = (n_cap + 255) / 256 < 64u ? (n_cap + 255) / 256 : 64u;
     if (nb > (uint32_t)kScatterBlocks) nb = kScatterBlocks;
     if (nb == 0) nb = 1;
-    hipLaunchKernelGGL(k_scatter_partials, dim3(nb), dim3(256), 0, s, vnorm4, n_ptr, n_cap, .001 / wf, sl.partials);
+    hipLaunchKernelGGL(k_scatter_partials, dim3(nb), dim3(256), 0, s, nrm4, n_ptr, n_cap, .001 / wf, sl.partials);
     return nb;
 }
 

@@ -131,7 +131,7 @@ void launch_voxel_grid(Slot &sl, uint32_t n_cap, float leaf, int key_bits, hipSt
     if (n_cap == 0) return;
     uint32_t gb = (n_cap + 255) / 256;
     if (gb > 2048) gb = 2048;
-    hipLaunchKernelGGL(k_voxel_keys, dim3(gb), dim3(256), 0, s, (const float4 *)sl.valid4, (const DevCounters *)sl.ctr,
+    hipLaunchKernelGGL(k_voxel_keys, dim3(gb), dim3(256), 0, s, (const float4 *)sl.crop4, (const DevCounters *)sl.ctr,
                        (const VoxelParams *)sl.voxp, sl.keys_a);
     const int where = launch_radix_sort(sl.keys_a, sl.vals_a, sl.keys_b, sl.vals_b, &sl.ctr->vox_n, n_cap, key_bits,
                                         sl, false, s);
@@ -141,7 +141,7 @@ void launch_voxel_grid(Slot &sl, uint32_t n_cap, float leaf, int key_bits, hipSt
     HeadEmit emit{sl.seg_start};
     hipLaunchKernelGGL((k_compact<HeadPred, HeadEmit>), dim3(compact_grid(n_cap)), dim3(kCpThreads), 0, s, pred, emit,
                        (const uint32_t *)&sl.ctr->vox_n, 0u, next_scan(sl), &sl.ctr->n_voxels, (uint32_t *)nullptr);
-    hipLaunchKernelGGL(k_voxel_centroids, dim3(gb), dim3(256), 0, s, (const float4 *)sl.valid4, perm,
+    hipLaunchKernelGGL(k_voxel_centroids, dim3(gb), dim3(256), 0, s, (const float4 *)sl.crop4, perm,
                        (const uint32_t *)sl.seg_start, (const DevCounters *)sl.ctr, sl.vox4);
 }
 

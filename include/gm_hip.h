@@ -233,6 +233,15 @@ gm_status gm_get_normals_stage(gm_ctx *ctx, const float *xyz, uint32_t n, double
 gm_status gm_get_local_frame(gm_ctx *ctx, const float *nxyzc, uint32_t n, double weighting_factor,
                              float eigenvalues[3], float eigenvectors[9], double scatter6[6]);
 
+/* The second half of getNormals alone (removeNaNNormalsFromPointCloud + ExtractIndices,
+ * src/tunnel_processing.cpp:74-85) with getLocalFrame's scatter sums: n cloud rows (x,y,z,pad)
+ * and n normal rows (nx,ny,nz,curvature) in; the rows whose normal has three finite
+ * components out, same order, bit for bit, and the six scatter sums of the survivors
+ * (scatter6 may be NULL). */
+gm_status gm_compact_valid_stage(gm_ctx *ctx, const float *xyzw, const float *nxyzc, uint32_t n,
+                                 double weighting_factor, float *xyzw_out, float *nxyzc_out,
+                                 uint32_t capacity, uint32_t *n_out, double scatter6[6]);
+
 /* The pcl::VoxelGrid half of rvizNormals: tunnel_processing.hpp:77-82,
  * src/tunnel_processing.cpp:214-220.  out rows x,y,z,count. */
 gm_status gm_voxel_grid(gm_ctx *ctx, const float *xyz, uint32_t n, double leaf,
