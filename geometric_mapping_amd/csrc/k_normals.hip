@@ -974,6 +974,9 @@ __device__ __forceinline__ void normals_tile_mx(const NormalsArgs &A, unsigned c
         if (thin) {
             // direct path, self-contained: every lane tests its own query against every candidate of the tile's row
             // ranges (wave-uniform loads straight from the sorted cloud) and sums the offsets from the query in fp64
+#if defined(GM_NORMALS_STATS) && !defined(GM_MD_DEBUG)
+            if (lane == 0) atomicAdd(&ctr->pad[4], 1u);   // tiles on this path (tools/normals_stats.py)
+#endif
             double tm[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
             for (int r = 0; r < 9; ++r) {
                 const uint32_t e = row_end(r);
@@ -1405,6 +1408,9 @@ __device__ __forceinline__ void normals_tile_mxd(const NormalsArgs &A, unsigned 
         if (thin) {
             // direct path, self-contained: every lane tests its own query against every candidate of the tile's row
             // ranges (wave-uniform loads straight from the sorted cloud) and sums the offsets from the query in fp64
+#if defined(GM_NORMALS_STATS) && !defined(GM_MD_DEBUG)
+            if (lane == 0) atomicAdd(&ctr->pad[4], 1u);   // tiles on this path (tools/normals_stats.py)
+#endif
             double tm[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
             for (int r = 0; r < 9; ++r) {
                 const uint32_t e = row_end(r);

@@ -11,10 +11,11 @@
 //   * the digit TOTALS of every pass are known before the first pass starts -- they do not depend on the order of
 //     the keys: the crop's emit step counts the first pass's as it produces the keys (k_crop.hip), the first pass those
 //     of the passes after it as it reads the keys; any other caller runs k_rs_hist_all (one read for all passes);
-//   * a block counts its tile's digits per wave in LDS, publishes the tile's count of every digit as one 64-bit
-//     record [epoch:30 | state:2 | count:32] and looks back over the records of the tiles before it, one digit per
-//     thread, 16 records in flight (decoupled look-back, as gm_compact.hpp does for one counter): the tile's items of
-//     digit d start at (totals scanned over the digits)[d] + (tiles before)[d];
+//   * a block counts its tile's digits per wave in LDS, publishes the tile's count of every digit as a 16-bit record
+//     [ready:1 | count:14] (and, once it knows them, a row of 32-bit inclusive prefixes [ready:1 | count:31]) and looks
+//     back over the records of the tiles before it, eight digits per 16-byte load (decoupled look-back, as
+//     gm_compact.hpp does for one counter, but with no epoch in the word -- see below): the tile's items of digit d
+//     start at (totals scanned over the digits)[d] + (tiles before)[d];
 //   * the items are ranked stably (wave ballot "match" inside a wave, the per-wave counts across waves: position
 //     order), put into digit order in LDS and written out as runs -- consecutive threads, consecutive slots;
 //   * the LAST pass of the cell sort does not write (key, value) pairs: the value is the cropped index, the pass

@@ -140,7 +140,8 @@ def test_get_normals_radius_extremes_vs_oracle(ctx, oc, gm):
     dup = np.repeat(base[:40], 3, axis=0)                                  # coincident triples
     near = (base[:60] + np.float32(1e-6) * rng.standard_normal((60, 3))).astype(np.float32)
     cloud = np.vstack([base, dup, near]).astype(np.float32)
-    for radius in (1e-12, 1e-7, 3e-6, 0.05, 0.7, 50.0, 1e6, 1e12):
+    # (1e-15 and 1e15: the two ends of the admitted range; at 1e15, r2 = 1e30 sits just under the far-slot marker 2^100)
+    for radius in (1e-15, 1e-12, 1e-7, 3e-6, 0.05, 0.7, 50.0, 1e6, 1e12, 1e15):
         ctx.getNormals(radius, cloud)
         _, o_cnt = oc.normals(cloud, radius, oc.F64)
         assert np.array_equal(ctx.neighbor_counts(), o_cnt), radius
@@ -609,7 +610,8 @@ def test_every_formulation_of_the_neighbourhood_kernel_finds_the_same_neighbours
     """GM_NORMALS_IMPL (read once per process -> child processes): the all-VALU kernel, the production kernel (distances
     and moments on the matrix cores, exact re-evaluation inside a band) forced onto every tile, and the variant that
     keeps the neighbour predicate on the VALU must report the neighbour counts and NaN pattern of the default build bit for bit, and normals
-    within 1e-5 rad -- on a dense frame and on a sparse one (thin neighbourhoods, long tiles).  rows2 / rows4: the same for
+    within 1e-5 rad -- on a dense frame and on a sparse one (thin neighbourhoods, long tiles) -- and the exact integer counts
+    of a lattice cloud with thousands of pairs exactly on the radius.  rows2 / rows4: the same for
     the fine-row mode of the production kernel (GM_NORMALS_ROWS: y/z cells r/2 and r/4 wide, 25 / 81 rows per tile in
     passes, per-row x-reach), forced onto frames it would not be chosen for."""
     import subprocess, sys, tempfile, os
@@ -624,8 +626,14 @@ def test_every_formulation_of_the_neighbourhood_kernel_finds_the_same_neighbours
         "    with g.GeometricMapping(neighborRadius=r, flags=_lib.GM_CFG_DEFAULT | _lib.GM_CFG_KEEP_COUNTS) as c:\n"
         "        res = c.process_frame(xyz)\n"
         "        out[name + '_nrm'] = c.normals(); out[name + '_cnt'] = c.neighbor_counts(); out[name + '_sc'] = res['scatter6']\n"
+        "sys.path.insert(0, %r)\n"
+        "import normals_np as nn\n"
+        "xyz, r = nn.case('tie_q7')\n"
+        "with g.GeometricMapping(neighborRadius=r, flags=_lib.GM_CFG_DEFAULT | _lib.GM_CFG_KEEP_COUNTS) as c:\n"
+        "    c.process_frame(xyz)\n"
+        "    out['tie_cnt'] = c.neighbor_counts()\n"
         "np.savez(sys.argv[1], **out)\n"
-    ) % root
+    ) % (root, os.path.join(root, "tests"))
     got = []
     with tempfile.TemporaryDirectory() as d:
         for tag in (None, impl):
@@ -651,6 +659,11 @@ def test_every_formulation_of_the_neighbourhood_kernel_finds_the_same_neighbours
         ok = np.isfinite(na[:, 0])
         assert np.quantile(ang(na[ok, :3], nb[ok, :3]), 0.999) < 1e-5
         assert np.abs(a[name + "_sc"] - b[name + "_sc"]).max() / np.abs(a[name + "_sc"]).max() < 1e-6
+    # a third cloud, counts only: thousands of pairs at exactly d2 == r2 (tests/normals_np.py), against the integer count
+    sys.path.insert(0, os.path.join(root, "tests"))
+    import normals_np as nn
+    want = nn.tie_counts(7, False)
+    assert np.array_equal(a["tie_cnt"], want) and np.array_equal(b["tie_cnt"], want)
 
 
 @pytest.mark.parametrize("ransac", [False, True, "nearest"])
