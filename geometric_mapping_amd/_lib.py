@@ -67,6 +67,13 @@ GM_WALL_OBJECT_MAX_BLOCKS = 1 << 20
 GM_WALL_OBJECT_TILE = (64, 64)   # block rows x block columns: the object labelling kernel's default tile
 
 GM_WALL_CHECK_MEAN, GM_WALL_CHECK_ENVELOPE = 0, 1
+GM_WALL_LOCATE_DESIGN, GM_WALL_LOCATE_MAP = 0, 1
+GM_LOCATE_OK = 0
+GM_LOCATE_DEGENERATE = 2
+GM_LOCATE_SINGULAR = 3
+GM_LOCATE_FAILED_MASK = 0xFF
+GM_LOCATE_NOT_CONVERGED = 1 << 8
+GM_LOCATE_PASSES = 3
 (GM_WALL_CHECK_CLS_PLANE, GM_WALL_CHECK_CLS_BEYOND_GATE, GM_WALL_CHECK_CLS_OUTSIDE, GM_WALL_CHECK_CLS_UNSURVEYED,
  GM_WALL_CHECK_CLS_UNCHANGED, GM_WALL_CHECK_CLS_CHANGED_POS, GM_WALL_CHECK_CLS_CHANGED_NEG) = range(7)
 
@@ -204,6 +211,23 @@ class WallCheckInfo(C.Structure):
                 ("peak_pos", C.c_int64), ("peak_neg", C.c_int64)]
 
 
+class WallLocateParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reference", C.c_uint32), ("min_count", C.c_uint32), ("reserved", C.c_uint32),
+                ("gate", C.c_double)]
+
+
+class WallLocatePass(C.Structure):
+    _fields_ = [("o", C.c_float * 3), ("a", C.c_float * 3), ("u", C.c_float * 3), ("v", C.c_float * 3), ("gate", C.c_float),
+                ("plane", C.c_uint32), ("outside", C.c_uint32), ("unsurveyed", C.c_uint32), ("gated", C.c_uint32),
+                ("used", C.c_uint32), ("rms", C.c_double), ("step", C.c_double * 4)]
+
+
+class WallLocateInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("status", C.c_uint32), ("passes", C.c_uint32), ("n_points", C.c_uint32),
+                ("anchor_station", C.c_int64), ("pose", C.c_double * 12), ("lateral", C.c_double * 2), ("tilt", C.c_double * 2),
+                ("pass_", WallLocatePass * 3)]
+
+
 class WallObject(C.Structure):
     _fields_ = [("label", C.c_uint32), ("sign", C.c_int32), ("blocks", C.c_uint32), ("peak_index", C.c_uint32),
                 ("station_min", C.c_uint32), ("station_max", C.c_uint32), ("sector_min", C.c_uint32), ("sector_max", C.c_uint32),
@@ -298,6 +322,7 @@ def load():
                                       C.POINTER(WallRegionMetrics))
     wcprmp, wcptp, wcinfop = C.POINTER(WallCloudParams), C.POINTER(WallCloudPoint), C.POINTER(WallCloudInfo)
     wkprmp, wkptp, wkinfop = C.POINTER(WallCheckParams), C.POINTER(WallCheckPoint), C.POINTER(WallCheckInfo)
+    wlprmp, wlinfop = C.POINTER(WallLocateParams), C.POINTER(WallLocateInfo)
     woprmp, wobjp, woinfop, wometp = (C.POINTER(WallObjectParams), C.POINTER(WallObject), C.POINTER(WallObjectsInfo),
                                       C.POINTER(WallObjectMetrics))
     proto = {
@@ -369,6 +394,11 @@ def load():
         "gm_wall_map_check_frame": (C.c_int, [vp, vp, u32, dp, wkprmp, waddp]),
         "gm_wall_map_get_check": (C.c_int, [vp, u32, wkinfop, wkptp, u32, u32p]),
         "gm_wall_map_check_points": (C.c_int, [vp, fp, u32, u8p, dp, wkprmp, waddp, wkinfop, wkptp, u32, u32p, fp, i32p, i32p, u8p]),
+        "gm_wall_locate_default_params": (None, [wlprmp]),
+        "gm_wall_locate_check_params": (C.c_int, [wlprmp]),
+        "gm_wall_map_locate_frame": (C.c_int, [vp, vp, u32, dp, wlprmp]),
+        "gm_wall_map_get_locate": (C.c_int, [vp, u32, wlinfop]),
+        "gm_wall_map_locate_points": (C.c_int, [vp, fp, u32, u8p, dp, wlprmp, wlinfop, fp, i32p]),
         "gm_wall_object_default_params": (None, [woprmp]),
         "gm_wall_map_check_objects": (C.c_int, [vp, u32, woprmp, woinfop, wobjp, u32, u32p, i32p, u32]),
         "gm_wall_check_objects": (C.c_int, [vp, wkptp, u32, C.c_int64, woprmp, woinfop, wobjp, u32, u32p, i32p]),

@@ -560,6 +560,16 @@ def wall_check_classify(raw_cell, e, **params):
     return int(d.value), int(c.value)
 
 
+def _wall_locate_params(**kw):
+    p = _lib.WallLocateParams()
+    _lib.load().gm_wall_locate_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k in ("struct_size", "reserved"):
+            raise TypeError(f"unknown locate parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
 def _wall_object_params(**kw):
     p = _lib.WallObjectParams()
     _lib.load().gm_wall_object_default_params(C.byref(p))
@@ -877,6 +887,58 @@ class WallMap:
         d = self._check_info(info)
         d["add"] = self._add_info(add)
         return d, pts[:int(got.value)].copy(), ({k: v[:n].copy() for k, v in out.items()} if outputs else None)
+
+    @staticmethod
+    def locate_params(**kw):
+        """gm_wall_locate_params with the library's defaults, then the keywords (reference, min_count, gate)."""
+        return _wall_locate_params(**kw)
+
+    @staticmethod
+    def _locate_info(i):
+        d = dict(status=int(i.status), passes=int(i.passes), n_points=int(i.n_points), anchor_station=int(i.anchor_station),
+                 pose=np.array(i.pose[:], dtype=np.float64).reshape(3, 4), lateral=np.array(i.lateral[:], dtype=np.float64),
+                 tilt=np.array(i.tilt[:], dtype=np.float64), bytes=bytes(i))
+        d["pass"] = []
+        for r in i.pass_:
+            q = {k: np.array(getattr(r, k)[:], dtype=np.float32) for k in ("o", "a", "u", "v")}
+            q["gate"] = np.float32(r.gate)
+            q.update({k: int(getattr(r, k)) for k in ("plane", "outside", "unsurveyed", "gated", "used")})
+            q["rms"] = float(r.rms)
+            q["step"] = np.array(r.step[:], dtype=np.float64)
+            d["pass"].append(q)
+        return d
+
+    def locate_frame(self, slot=0, pose=np.eye(4)[:3], **params):
+        """gm_wall_map_locate_frame: enqueue the correction of `pose` for the slot's last submitted frame against this map
+        (keywords: reference, min_count, gate).  Returns at once; locate_result() fetches the result."""
+        m = self._pose(pose)
+        p = self.locate_params(**params)
+        self._ctx._check(self._L.gm_wall_map_locate_frame(self._h(), self._ctx._ctx, slot, m.ctypes.data_as(C.POINTER(C.c_double)),
+                                                          C.byref(p)))
+
+    def locate_result(self, slot=0):
+        """gm_wall_map_get_locate: the info dict of the last locate on the slot -- status, passes, n_points,
+        anchor_station, pose (3, 4) float64 (NaN when status & GM_LOCATE_FAILED_MASK), lateral, tilt, pass (a list of three
+        dicts: o, a, u, v, gate, the five class counts, rms, step) and bytes (the raw gm_wall_locate_info)."""
+        info = _lib.WallLocateInfo()
+        self._ctx._check(self._L.gm_wall_map_get_locate(self._h(), slot, C.byref(info)))
+        return self._locate_info(info)
+
+    def locate_points(self, cloud, pose=np.eye(4)[:3], labels=None, outputs=True, **params):
+        """gm_wall_map_locate_points on a host cloud [n,3]: (info dict, residual [n] float32, cell [n] int32) of the last
+        pass that ran; outputs False skips the per-point arrays (None, None)."""
+        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+        m = self._pose(pose)
+        lab, lp = GeometricMapping._u8(labels)
+        p = self.locate_params(**params)
+        n = len(xyz)
+        info = _lib.WallLocateInfo()
+        res = np.empty(max(n, 1), dtype=np.float32) if outputs else None
+        cell = np.empty(max(n, 1), dtype=np.int32) if outputs else None
+        self._ctx._check(self._L.gm_wall_map_locate_points(
+            self._h(), _f32(xyz), n, lp, m.ctypes.data_as(C.POINTER(C.c_double)), C.byref(p), C.byref(info),
+            _f32(res) if outputs else None, cell.ctypes.data_as(C.POINTER(C.c_int32)) if outputs else None))
+        return self._locate_info(info), (res[:n].copy() if outputs else None), (cell[:n].copy() if outputs else None)
 
     @staticmethod
     def object_params(**kw):

@@ -240,14 +240,20 @@ __device__ __forceinline__ float surf_dot3(float x, float y, float z, const floa
 {
     return __fmaf_rn(x, b[0], __fmaf_rn(y, b[1], __fmul_rn(z, b[2])));
 }
-// q = p - o, t = q.a, w = q - t a; returns e = |w| - R
-__device__ __forceinline__ float surf_residual(const float4 &p, const float (&o)[3], const float (&a)[3], float R, float &t,
-                                               float &wx, float &wy, float &wz)
+// q = p - o, t = q.a, w = q - t a; returns rho = |w|
+__device__ __forceinline__ float surf_rho(const float4 &p, const float (&o)[3], const float (&a)[3], float &t, float &wx, float &wy,
+                                          float &wz)
 {
     const float qx = __fsub_rn(p.x, o[0]), qy = __fsub_rn(p.y, o[1]), qz = __fsub_rn(p.z, o[2]);
     t = surf_dot3(qx, qy, qz, a);
     wx = __fmaf_rn(-t, a[0], qx); wy = __fmaf_rn(-t, a[1], qy); wz = __fmaf_rn(-t, a[2], qz);
-    return __fsub_rn(__fsqrt_rn(__fmaf_rn(wx, wx, __fmaf_rn(wy, wy, __fmul_rn(wz, wz)))), R);
+    return __fsqrt_rn(__fmaf_rn(wx, wx, __fmaf_rn(wy, wy, __fmul_rn(wz, wz))));
+}
+// the same, returning e = |w| - R
+__device__ __forceinline__ float surf_residual(const float4 &p, const float (&o)[3], const float (&a)[3], float R, float &t,
+                                               float &wx, float &wy, float &wz)
+{
+    return __fsub_rn(surf_rho(p, o, a, t, wx, wy, wz), R);
 }
 // floor((t - t_min) / ds), still a float: the caller checks the range before it converts
 __device__ __forceinline__ float surf_station(float t, float t_min, float ds)

@@ -425,6 +425,25 @@ __host__ __device__ inline uint32_t wall_check_rule(uint32_t reference, uint32_t
     }
     return delta >= T ? GM_WALL_CHECK_CLS_CHANGED_POS : (delta <= -T ? GM_WALL_CHECK_CLS_CHANGED_NEG : GM_WALL_CHECK_CLS_UNCHANGED);
 }
+// k_wall_locate.hip (gm_wall_map_locate_*): one launch per pass on the cylinder regression's fixed grid
+// the state between the passes and the result: written by the last block of each pass, copied to the host behind pass 2
+struct WallLocateWork {
+    double c[3], d[3], u[3], v[3];   // the state in sensor coordinates, fp64
+    double lateral[2], tilt[2];      // the summed steps
+    double last_step;                // |x| of the last completed pass
+    uint32_t status, passes, n_points, pad;
+    gm_wall_locate_pass pass[GM_LOCATE_PASSES];
+};
+struct WallLocateArgs {
+    WallArgs w;                // the add's arguments: its o, a, u, v, gate and window fields unused; res / cell: stage call only
+    uint32_t reference, min_count;
+    double gate;               // of pass 0
+    double c0[3], d0[3], u0[3], v0[3], s0;   // the start, fp64, not rounded
+    WallLocateWork *work;
+    double *partial;           // [kFitBlocks][kFitRowLen]
+    uint32_t *ticket;          // 0 between launches
+};
+void launch_wall_locate(const WallLocateArgs &a, hipStream_t s);   // the three passes
 // k_wall_objects.hip (gm_wall_map_check_objects, gm_wall_check_objects): bin -> tiles -> seams -> flatten | blocks ->
 // reduce -> select | rows
 constexpr uint32_t kWallObjectTileBlocks = 4096;      // the most window blocks of a tile (its LDS tables)

@@ -78,6 +78,19 @@ struct WallCheckSlot {
     int64_t anchor = 0;                     // the check's j_f (gm_wall_map_check_objects anchors its window on it)
 };
 
+// gm_wall_map_locate_*: the state of one (map, slot), allocated on first use, freed with the map
+struct WallLocateSlot {
+    DevArray<WallLocateWork> work;          // the state between the passes, the result behind them
+    DevArray<double> partial;               // [kFitBlocks][kFitRowLen] partial rows of a pass
+    DevArray<uint32_t> ticket;              // last-block ticket of the passes (0 between launches)
+    HostArray<WallLocateWork> h_work;       // pinned copy, valid once `done` has passed
+    hipEvent_t done = nullptr;              // recorded behind the passes and the copy of the result
+    bool have = false;                      // a locate was enqueued: a result is (or will be) readable
+    bool outstanding = false;               // the host has not waited for `done` yet
+    int64_t anchor = 0;                     // the locate's j_f
+    double of[3] = {0.0, 0.0, 0.0};         // its o_f, map coordinates
+};
+
 struct gm_wall_map {
     gm_ctx *ctx = nullptr;
     gm_wall_params prm;
@@ -110,6 +123,8 @@ struct gm_wall_map {
     std::vector<double> cl_dirs_host;          // the table of the call in progress
     // gm_wall_map_check_*
     std::vector<WallCheckSlot> checks;         // per slot of ctx
+    // gm_wall_map_locate_*
+    std::vector<WallLocateSlot> locates;       // per slot of ctx
     // gm_wall_map_check_objects / gm_wall_check_objects: the tile in blocks (GM_WALL_OBJECT_TILE: tests, measurements) and
     // the scratch
     uint32_t object_tr = GM_WALL_OBJECT_TILE_ROWS, object_tc = GM_WALL_OBJECT_TILE_COLS;
@@ -182,7 +197,9 @@ void design_frame(gm_wall_map *m)
 
 // The per-add frame: pose check, anchor, (o', a', u', v') in sensor coordinates, and the kernel's arguments but for the
 // buffers.  The context's crop bound (a cube around the sensor) sizes the LDS window.
-gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info *info, WallArgs &w)
+// f64 (a locate's start): the same vectors before the rounding, and o_f in map coordinates.
+struct WallFrame64 { double c[3], d[3], u[3], v[3], of[3]; };
+gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info *info, WallArgs &w, WallFrame64 *f64 = nullptr)
 {
     gm_ctx *ctx = m->ctx;
     if (!pose) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: NULL pose");
@@ -221,6 +238,7 @@ gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info
         const double uu = Rm[0][c] * m->u[0] + Rm[1][c] * m->u[1] + Rm[2][c] * m->u[2];
         const double vv = Rm[0][c] * m->v[0] + Rm[1][c] * m->v[1] + Rm[2][c] * m->v[2];
         w.o[c] = (float)oo; w.a[c] = (float)aa; w.u[c] = (float)uu; w.v[c] = (float)vv;
+        if (f64) { f64->c[c] = oo; f64->d[c] = aa; f64->u[c] = uu; f64->v[c] = vv; f64->of[c] = m->o[c] + off * m->a[c]; }
         a1 += fabs(aa);
     }
     const double two_pi = 6.283185307179586476925286766559;
@@ -275,6 +293,11 @@ gm_status sync_map(gm_wall_map *m)
             GMW_HIP(ctx, hipEventSynchronize(c.done));
             c.outstanding = false;
         }
+    for (WallLocateSlot &l : m->locates)
+        if (l.outstanding) {
+            GMW_HIP(ctx, hipEventSynchronize(l.done));
+            l.outstanding = false;
+        }
     GMW_HIP(ctx, hipStreamSynchronize(m->stream));
     return GM_OK;
 }
@@ -298,6 +321,10 @@ void free_map(gm_wall_map *m)
         if (c.outstanding) hipEventSynchronize(c.done);
         if (c.done) hipEventDestroy(c.done);
         if (c.adds) hipEventDestroy(c.adds);
+    }
+    for (WallLocateSlot &l : m->locates) {
+        if (l.outstanding) hipEventSynchronize(l.done);
+        if (l.done) hipEventDestroy(l.done);
     }
     if (m->stream) { hipStreamSynchronize(m->stream); hipStreamDestroy(m->stream); }
     delete m;   // (every DevArray and HostArray goes with it)
@@ -535,6 +562,109 @@ gm_status check_result(gm_wall_map *m, uint32_t slot, gm_wall_check_info *info, 
     return GM_OK;
 }
 
+// ---- gm_wall_map_locate_* ----
+
+bool locate_prm_ok(const gm_wall_locate_params &p)
+{
+    return p.struct_size == sizeof(gm_wall_locate_params) && p.reference <= (uint32_t)GM_WALL_LOCATE_MAP && p.min_count >= 1u &&
+           p.gate > 0.0 && p.gate <= 8.0;
+}
+
+// the start of include/gm_hip.h: the add's frame before the rounding, and s0
+gm_status locate_args(gm_wall_map *m, uint32_t slot, const double pose[12], const gm_wall_locate_params &lp, WallLocateArgs &a)
+{
+    WallFrame64 f;
+    memset(&a, 0, sizeof(a));
+    GMW_OK(add_frame_args(m, pose, nullptr, a.w, &f));
+    a.reference = lp.reference;
+    a.min_count = lp.min_count;
+    a.gate = lp.gate;
+    for (int k = 0; k < 3; ++k) { a.c0[k] = f.c[k]; a.d0[k] = f.d[k]; a.u0[k] = f.u[k]; a.v0[k] = f.v[k]; }
+    a.s0 = -dot(f.c, f.d);
+    WallLocateSlot &l = m->locates[slot];
+    l.anchor = a.w.anchor;
+    for (int k = 0; k < 3; ++k) l.of[k] = f.of[k];
+    return GM_OK;
+}
+
+// the scratch of (map, slot); a new ticket is zeroed on `s`
+gm_status locate_prepare(gm_wall_map *m, uint32_t slot, hipStream_t s, WallLocateArgs &a)
+{
+    gm_ctx *ctx = m->ctx;
+    WallLocateSlot &l = m->locates[slot];
+    if (!l.done) GMW_HIP(ctx, hipEventCreateWithFlags(&l.done, hipEventDisableTiming));
+    GMW_HIP(ctx, l.work.reserve(1));
+    GMW_HIP(ctx, l.h_work.reserve(1));
+    GMW_HIP(ctx, l.partial.reserve((uint64_t)kFitBlocks * kFitRowLen));
+    if (!l.ticket) {
+        GMW_HIP(ctx, l.ticket.reserve(1));
+        GMW_HIP(ctx, hipMemsetAsync(l.ticket.p, 0, 4, s));
+    }
+    a.work = l.work.p;
+    a.partial = l.partial.p;
+    a.ticket = l.ticket.p;
+    return GM_OK;
+}
+
+// the three passes, the copy of the result and the event behind them
+gm_status locate_enqueue(gm_wall_map *m, uint32_t slot, const WallLocateArgs &a, hipStream_t s)
+{
+    gm_ctx *ctx = m->ctx;
+    WallLocateSlot &l = m->locates[slot];
+    launch_wall_locate(a, s);
+    GMW_HIP(ctx, hipGetLastError());
+    GMW_HIP(ctx, hipMemcpyAsync(l.h_work.p, l.work.p, sizeof(WallLocateWork), hipMemcpyDeviceToHost, s));
+    GMW_HIP(ctx, hipEventRecord(l.done, s));
+    l.have = true;
+    l.outstanding = true;
+    return GM_OK;
+}
+
+// the result of (map, slot) once `done` has passed: the device's record, and the pose composed in fp64
+gm_status locate_result(gm_wall_map *m, uint32_t slot, gm_wall_locate_info *info)
+{
+    gm_ctx *ctx = m->ctx;
+    WallLocateSlot &l = m->locates[slot];
+    if (l.outstanding) {
+        GMW_HIP(ctx, hipEventSynchronize(l.done));
+        l.outstanding = false;
+    }
+    const WallLocateWork &wk = *l.h_work.p;
+    memset(info, 0, sizeof(*info));
+    info->struct_size = (uint32_t)sizeof(gm_wall_locate_info);
+    info->status = wk.status;
+    info->passes = wk.passes;
+    info->n_points = wk.n_points;
+    info->anchor_station = l.anchor;
+    for (int k = 0; k < GM_LOCATE_PASSES; ++k) info->pass[k] = wk.pass[k];
+    if (wk.status & GM_LOCATE_FAILED_MASK) {
+        const double nan = __builtin_nan("");
+        for (int k = 0; k < 12; ++k) info->pose[k] = nan;
+        info->lateral[0] = info->lateral[1] = info->tilt[0] = info->tilt[1] = nan;
+        return GM_OK;
+    }
+    if (wk.last_step > GM_FIT_STEP_BOUND) info->status |= GM_LOCATE_NOT_CONVERGED;
+    for (int k = 0; k < 2; ++k) { info->lateral[k] = wk.lateral[k]; info->tilt[k] = wk.tilt[k]; }
+    for (int r = 0; r < 3; ++r) {   // Rm' = a d^T + u u'^T + v v'^T, tr' = o_f - Rm' c
+        double rc = 0.0;
+        for (int c = 0; c < 3; ++c) {
+            const double e = m->a[r] * wk.d[c] + m->u[r] * wk.u[c] + m->v[r] * wk.v[c];
+            info->pose[4 * r + c] = e;
+            rc += e * wk.c[c];
+        }
+        info->pose[4 * r + 3] = l.of[r] - rc;
+    }
+    return GM_OK;
+}
+
+// an add on `s` must not be seen by the locates enqueued before it on other slots
+gm_status add_wait_locates(gm_wall_map *m, uint32_t slot, hipStream_t s)
+{
+    for (uint32_t i = 0; i < m->ctx->n_slots; ++i)
+        if (i != slot && m->locates[i].outstanding) GMW_HIP(m->ctx, hipStreamWaitEvent(s, m->locates[i].done, 0));
+    return GM_OK;
+}
+
 // ---- gm_wall_map_check_objects / gm_wall_check_objects ----
 
 bool object_prm_ok(const gm_wall_object_params &p)
@@ -712,6 +842,7 @@ gm_status gm_wall_map_create(gm_ctx *ctx, const gm_wall_params *params, gm_wall_
     m->ncell = (uint64_t)params->n_stations * params->n_sectors;
     m->pending.assign(ctx->n_slots, 0);
     m->checks.resize(ctx->n_slots);
+    m->locates.resize(ctx->n_slots);
     if (const char *e = getenv("GM_WALL_POINTS_PER_BLOCK")) m->points_per_block = (uint32_t)strtoul(e, nullptr, 10);
     if (const char *e = getenv("GM_WALL_REGION_TILE")) {   // <stations>x<sectors>; anything else: the default
         unsigned ts = 0, tk = 0;
@@ -777,6 +908,7 @@ gm_status gm_wall_map_add_frame(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, co
     // a check enqueued on another slot before this add must not see it (nothing to wait for on a map without checks)
     for (uint32_t i = 0; i < ctx->n_slots; ++i)
         if (i != slot && map->checks[i].outstanding) GMW_HIP(ctx, hipStreamWaitEvent(sl.stream, map->checks[i].done, 0));
+    GMW_OK(add_wait_locates(map, slot, sl.stream));   // (nor a locate)
     launch_wall_add(w, sl.n_in, map->points_per_block, sl.stream);
     GMW_HIP(ctx, hipGetLastError());
     map->pending[slot] = 1;
@@ -798,6 +930,7 @@ gm_status gm_wall_map_add_points(gm_wall_map *map, const float *xyz, uint32_t n,
     hipStream_t s = sc.sl->stream;
     for (uint32_t i = 1; i < ctx->n_slots; ++i)   // (as gm_wall_map_add_frame: behind the checks outstanding on other slots)
         if (map->checks[i].outstanding) GMW_HIP(ctx, hipStreamWaitEvent(s, map->checks[i].done, 0));
+    GMW_OK(add_wait_locates(map, 0, s));
     launch_wall_add(w, n, map->points_per_block, s);
     GMW_HIP(ctx, hipGetLastError());
     GMW_OK(sc.close());
@@ -1261,6 +1394,86 @@ gm_status gm_wall_map_check_points(gm_wall_map *map, const float *xyz, uint32_t 
     GMW_OK(check_enqueue(map, 0, a, n_cap, scan, s));
     GMW_OK(sc.close());
     return check_result(map, 0, info, points, capacity, n_out);
+}
+
+void gm_wall_locate_default_params(gm_wall_locate_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(gm_wall_locate_params);
+    p->reference = GM_WALL_LOCATE_DESIGN;
+    p->min_count = 8;
+    p->gate = 0.25;
+}
+
+gm_status gm_wall_locate_check_params(const gm_wall_locate_params *p)
+{
+    return p && locate_prm_ok(*p) ? GM_OK : GM_ERR_INVALID_ARG;
+}
+
+gm_status gm_wall_map_locate_frame(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, const double pose[12],
+                                   const gm_wall_locate_params *prm)
+{
+    if (!map || !ctx) return GM_ERR_INVALID_ARG;
+    if (ctx != map->ctx) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_locate_frame: the map belongs to another context");
+    if (slot >= ctx->n_slots) return gm_fail(ctx, GM_ERR_INVALID_ARG, "slot out of range");
+    const gm_wall_locate_params lp = params_or(prm, gm_wall_locate_default_params);
+    if (!locate_prm_ok(lp))
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_locate_frame: struct_size mismatch or a parameter outside its limits");
+    Slot &sl = ctx->slots[slot];
+    if (!sl.submitted) return gm_fail(ctx, GM_ERR_NOT_READY, "gm_wall_map_locate_frame: the slot holds no frame");
+    WallLocateArgs a;
+    GMW_OK(locate_args(map, slot, pose, lp, a));
+    if (hipSetDevice(ctx->device) != hipSuccess) return gm_fail(ctx, GM_ERR_DEVICE, "hipSetDevice failed");
+    GMW_OK(locate_prepare(map, slot, sl.stream, a));
+    GMW_OK(check_wait_adds(map, slot, sl.stream));
+    a.w.pts = sl.crop4;
+    a.w.labels = (ctx->cfg.flags & GM_CFG_RANSAC_PLANE) ? sl.labels : nullptr;
+    a.w.n_ptr = &sl.ctr->n_valid;
+    a.w.n_host = sl.n_in;
+    return locate_enqueue(map, slot, a, sl.stream);
+}
+
+gm_status gm_wall_map_get_locate(gm_wall_map *map, uint32_t slot, gm_wall_locate_info *info)
+{
+    if (!map) return GM_ERR_INVALID_ARG;
+    gm_ctx *ctx = map->ctx;
+    if (!info) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_get_locate: NULL info");
+    if (slot >= ctx->n_slots) return gm_fail(ctx, GM_ERR_INVALID_ARG, "slot out of range");
+    if (!map->locates[slot].have) return gm_fail(ctx, GM_ERR_NOT_READY, "gm_wall_map_get_locate: no locate was enqueued on this map and slot");
+    if (hipSetDevice(ctx->device) != hipSuccess) return gm_fail(ctx, GM_ERR_DEVICE, "hipSetDevice failed");
+    return locate_result(map, slot, info);
+}
+
+gm_status gm_wall_map_locate_points(gm_wall_map *map, const float *xyz, uint32_t n, const uint8_t *labels, const double pose[12],
+                                    const gm_wall_locate_params *prm, gm_wall_locate_info *info, float *residual, int32_t *cell)
+{
+    if (!map) return GM_ERR_INVALID_ARG;
+    gm_ctx *ctx = map->ctx;
+    if (!info) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_locate_points: NULL info");
+    if (n && !xyz) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_locate_points: NULL xyz");
+    const gm_wall_locate_params lp = params_or(prm, gm_wall_locate_default_params);
+    if (!locate_prm_ok(lp))
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_locate_points: struct_size mismatch or a parameter outside its limits");
+    WallLocateSlot &l = map->locates[0];
+    const int64_t anchor = l.anchor;   // (a refused call leaves the slot's last result as it was)
+    const double of[3] = {l.of[0], l.of[1], l.of[2]};
+    WallLocateArgs a;
+    GMW_OK(locate_args(map, 0, pose, lp, a));
+    StageCall sc{map, n, residual, cell, nullptr, nullptr};
+    gm_status st = sc.open();
+    if (st == GM_OK) st = locate_prepare(map, 0, sc.sl->stream, a);
+    if (st != GM_OK) {
+        l.anchor = anchor;
+        for (int k = 0; k < 3; ++k) l.of[k] = of[k];
+        return st;
+    }
+    hipStream_t s = sc.sl->stream;
+    GMW_OK(check_wait_adds(map, 0, s));
+    GMW_OK(sc.upload(xyz, labels, a.w));
+    GMW_OK(locate_enqueue(map, 0, a, s));
+    GMW_OK(sc.close());
+    return locate_result(map, 0, info);
 }
 
 void gm_wall_object_default_params(gm_wall_object_params *p)

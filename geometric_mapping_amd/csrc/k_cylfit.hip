@@ -20,14 +20,12 @@
 // finish.  Those are __device__ functions shared with the single-device last block, so one rank gives its bits.
 #include <math.h>
 
+#include "gm_fit_reduce.hpp"
 #include "gm_internal.hpp"
 
 namespace gm {
 
-constexpr int kFitThreads = 256;
-constexpr int kFitCols = kFitRowLen;   // partial row: 22 GN sums (or 3 label sums), zero padded
 constexpr int kFitAcc = 22;
-constexpr int kFitUnroll = 4;  // points per thread and trip, loads issued together
 
 __device__ inline bool fit_eligible(const uint8_t *__restrict__ labels, uint32_t i, uint32_t want, uint32_t want2)
 {
@@ -52,62 +50,6 @@ __device__ inline void fit_fail(const CylFitArgs &a, uint32_t status, uint32_t p
     f.radius = nan; f.rms = nan; f.last_step = nan;
     for (int k = 0; k < 7; ++k) f.model[k] = __builtin_nanf("");
     *a.fit = f;
-}
-
-// the block's sums -> its partial row; then the ticket.  Returns true in every thread of the block that finished last,
-// after the rows of the whole grid have been reduced (fixed order) into tot[0..kFitCols).
-template <int NACC>
-__device__ inline bool fit_block_reduce(const CylFitArgs &a, const double (&acc)[NACC], double *tot)
-{
-    __shared__ double red[kFitThreads / kWave][kFitCols];
-    __shared__ uint32_t last;
-    const int w = threadIdx.x / kWave;
-#pragma unroll
-    for (int k = 0; k < NACC; ++k) {
-        const double r = wave_sum(acc[k]);
-        if (lane_id() == 0) red[w][k] = r;
-    }
-    __syncthreads();
-    if (threadIdx.x < (uint32_t)kFitCols) {
-        double r = 0.0;
-        if ((int)threadIdx.x < NACC)
-#pragma unroll
-            for (int j = 0; j < kFitThreads / kWave; ++j) r += red[j][threadIdx.x];
-        a.partial[(size_t)blockIdx.x * kFitCols + threadIdx.x] = r;   // blockIdx.x < gridDim.x <= kFitBlocks rows
-        __threadfence();
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) last = atomicAdd(a.ticket, 1u) == gridDim.x - 1u ? 1u : 0u;
-    __syncthreads();
-    if (!last) return false;
-    __threadfence();
-    // fixed-order reduction of the gridDim.x rows: thread t sums rows t, t + 256, ... (a row's columns are independent
-    // loads, all in flight together: a serial chain of dependent row loads cost ~30 us per launch), then wave_sum and
-    // the waves in order
-    double v[kFitCols];
-#pragma unroll
-    for (int k = 0; k < kFitCols; ++k) v[k] = 0.0;
-    for (uint32_t b = threadIdx.x; b < gridDim.x; b += kFitThreads) {
-        const double *row = a.partial + (size_t)b * kFitCols;
-#pragma unroll
-        for (int k = 0; k < NACC; ++k) v[k] += row[k];
-    }
-#pragma unroll
-    for (int k = 0; k < NACC; ++k) {
-        const double r = wave_sum(v[k]);
-        if (lane_id() == 0) red[w][k] = r;   // (every thread of the block is past the reads of red above)
-    }
-    __syncthreads();
-    if (threadIdx.x < (uint32_t)kFitCols) {
-        double t = 0.0;
-        if ((int)threadIdx.x < NACC)
-#pragma unroll
-            for (int j = 0; j < kFitThreads / kWave; ++j) t += red[j][threadIdx.x];
-        tot[threadIdx.x] = t;
-    }
-    if (threadIdx.x == 0) atomicExch(a.ticket, 0u);   // ready for the next launch
-    __syncthreads();
-    return true;
 }
 
 // the model a pass starts from: pass 0 the starting row (its failure is published by block 0), later passes CylFitWork.
@@ -270,7 +212,7 @@ __global__ __launch_bounds__(kFitThreads) void k_cylfit_gn(CylFitArgs a, int pas
         for (int u = 0; u < kFitUnroll; ++u)
             if (el[u]) accumulate(p[u]);
     }
-    if (!fit_block_reduce<kFitAcc>(a, s, tot)) return;
+    if (!fit_block_reduce<kFitAcc>(a.partial, a.ticket, s, tot)) return;
     if (a.rank_row) {   // group: the rank's row goes to the exchange, k_cylfit_merge solves
         if (threadIdx.x < (uint32_t)kFitCols) a.rank_row[threadIdx.x] = tot[threadIdx.x];
         return;
@@ -355,7 +297,7 @@ __global__ __launch_bounds__(kFitThreads) void k_cylfit_label(CylFitArgs a)
             else if (el[u]) a.out[i] = in ? (uint8_t)2 : (uint8_t)0;
         }
     }
-    if (!fit_block_reduce<3>(a, s, tot)) return;
+    if (!fit_block_reduce<3>(a.partial, a.ticket, s, tot)) return;
     if (a.rank_row) {   // group: the rank's row goes to the exchange, k_cylfit_merge publishes
         if (threadIdx.x < (uint32_t)kFitCols) a.rank_row[threadIdx.x] = tot[threadIdx.x];
         return;

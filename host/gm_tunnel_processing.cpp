@@ -439,6 +439,17 @@ std::vector<gm_wall_check_point> Processor::checkWallMap(const double pose[12], 
     return points;
 }
 
+gm_wall_locate_info Processor::locateWallMap(const double pose[12], const gm_wall_locate_params &prm)
+{
+    if (!wall_) throw Error(GM_ERR_NOT_READY, "locateWallMap: createWallMap first");
+    if (newest_slot_ < 0) throw Error(GM_ERR_NOT_READY, "locateWallMap: no frame yet");
+    const unsigned slot = (unsigned)newest_slot_;
+    check(gm_wall_map_locate_frame(wall_, ctx_, slot, pose, &prm), "locateWallMap");
+    gm_wall_locate_info info;
+    check(gm_wall_map_get_locate(wall_, slot, &info), "locateWallMap");
+    return info;
+}
+
 std::vector<gm_wall_object> Processor::wallCheckObjects(const gm_wall_object_params &prm, gm_wall_objects_info *info)
 {
     if (!wall_) throw Error(GM_ERR_NOT_READY, "wallCheckObjects: createWallMap first");

@@ -154,6 +154,11 @@ public:
     // gm_wall_map_get_check), ascending by index; the map is not changed.  info, when given, receives the call's counts.
     // Check, then addToWallMap: against what was there, then contribute.
     std::vector<gm_wall_check_point> checkWallMap(const double pose[12], const gm_wall_check_params &prm, gm_wall_check_info *info = nullptr);
+    // the pose of the newest frame corrected against the map (gm_wall_map_locate_frame + gm_wall_map_get_locate): the lateral
+    // offset and the tilt against the axis are estimated, chainage and roll stay the caller's; the map is not changed.
+    // info.pose is the corrected pose (NaN when info.status & GM_LOCATE_FAILED_MASK).  Locate, then checkWallMap and
+    // addToWallMap with the corrected pose.
+    gm_wall_locate_info locateWallMap(const double pose[12], const gm_wall_locate_params &prm);
     // the changed points of the last checkWallMap grouped into objects on the device (gm_wall_map_check_objects on the slot
     // that check ran on), ascending by (label, sign); the check's result and the map are not changed, and the call may be
     // repeated with other parameters.  info, when given, receives the call's counts.

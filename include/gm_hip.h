@@ -798,6 +798,107 @@ gm_status gm_wall_map_check_points(gm_wall_map *map, const float *xyz, uint32_t 
                                    gm_wall_check_point *points, uint32_t capacity, uint32_t *n_out, float *residual,
                                    int32_t *cell, int32_t *delta, uint8_t *cls);
 
+/* ---- a frame's pose corrected against the wall map (gm_wall_map_locate_*) ----------------------------------------------
+ * Every product above bins a point by e = |w| - R under the caller's pose and trusts it: odometry that is 3 cm off
+ * laterally puts a cos(phi)-shaped false deviation of that size into every cell an add touches and makes a check report
+ * half the wall as changed.  A locate estimates the four degrees of freedom a tube constrains -- the lateral offset of the
+ * sensor from the axis (2) and the tilt of the sensor against the axis (2) -- by three gated Gauss-Newton passes over the
+ * frame's valid cloud, and returns the corrected pose.  Chainage and roll about the axis are not observable on a smooth
+ * wall: they stay the caller's.  The normal order per frame is locate -> check with the corrected pose -> add with it.
+ *   start         host, fp64: gm_wall_map_add_frame's "per add" unchanged (the pose checks, j_f, o_f), NOT rounded.  In
+ *                 sensor coordinates c = Rm^T (o_f - tr), d = Rm^T a, u' = Rm^T u, v' = Rm^T v; s0 = -c.d, the sensor's
+ *                 t, is kept fixed.
+ *   pass k        k = 0, 1, 2 with the gate g_k = (float)(gate 2^-k).  The state (c, d, u', v') is rounded to fp32 once
+ *                 and reported in pass[k].  Every point runs the add's fp32 chain on those vectors with a local t_min of
+ *                 0: q = p - c, t = q.d, w = q - t d, rho = sqrt(w.w), e = rho - R (R rounded to fp32 once).
+ *   target        GM_WALL_LOCATE_DESIGN: m = 0; stations and cells are not consulted, so this works on an empty map.
+ *                 GM_WALL_LOCATE_MAP: the station j = j_f + floor(t / ds) in 64-bit integers; j outside
+ *                 [0, n_stations) is class OUTSIDE; the cell j n_sectors + k (the add's sector k) is USABLE iff
+ *                 count >= min_count, else the point is class UNSURVEYED; m = (float)((double) q 2^-20) with
+ *                 q = sum / (int64) count by C integer division: the value of the regions and the check, exact in fp32.
+ *   classes       every valid point is in exactly one, decided in this order: plane (label 1), gated (e not finite),
+ *                 outside, unsurveyed (those two in MAP only), then res = e - m (one fp32 subtraction) and
+ *                 used iff |res| < g_k and rho > 0, else gated.
+ *   sums          for a used point n = w (1 / rho) (fp32 reciprocal, rounded to nearest), a1 = -n.u', a2 = -n.v' (the fp32
+ *                 dot of the chain), J = (a1, a2, t a1, t a2) in fp64; the fp64 sums are the 10 of J_i J_j, the 4 of
+ *                 J_i res, the count and res^2, on the fixed grid and in the fixed order of the cylinder regression.  t is
+ *                 not recentred: c sits at a station start beside the sensor, so |t| is bounded by the crop box.
+ *   solve         fewer than 4 used points: GM_LOCATE_DEGENERATE.  4x4 fp64 Cholesky under the cylinder fit's pivot rule
+ *                 (piv > 1e-12 diag, else GM_LOCATE_SINGULAR; so is a step that is not finite): x = -(J^T J)^-1 J^T res.
+ *   update        c <- c + x0 u' + x1 v';  d <- normalize(d + x2 u' + x3 v');  u' <- normalize(u' - (u'.d) d);
+ *                 v' <- d x u';  then c <- c - (c.d) d - s0 d.  rms = sqrt(sum res^2 / used).
+ *   failure       a failed pass sets the status and stops the chain: later passes return at once.  `passes` counts the
+ *                 passes that completed; pass[passes] holds the failed pass's frame, gate and class counts with a NaN
+ *                 step, the records behind it are zero.  pose, lateral and tilt are NaN.
+ *   pose          host, fp64, from the final state: Rm' = [a u v] [d u' v']^T with the columns of the unrounded design
+ *                 frame, tr' = o_f - Rm' c.  lateral and tilt are the summed x0, x1 and x2, x3.  |x| of the last pass
+ *                 above GM_FIT_STEP_BOUND sets GM_LOCATE_NOT_CONVERGED; the pose is still published.  The pose passes
+ *                 the library's own pose check.
+ * The map is not changed: not its cells, not its totals, not `frames`.  Ordering as for a check: a locate sees every add
+ * enqueued on any slot before it and none enqueued after it.  No floating-point atomics; there is no host round trip
+ * between the passes.  Scratch per (map, slot) -- the working state, 96 KiB of partial rows, a pinned copy of the result
+ * -- is allocated on first use, kept grow-only and freed with the map; a map that never locates allocates nothing.
+ * A locate in MAP mode against a map built from uncorrected poses inherits their mean error: the first survey locates in
+ * DESIGN mode. */
+enum { GM_WALL_LOCATE_DESIGN = 0, GM_WALL_LOCATE_MAP = 1 };
+#define GM_LOCATE_OK            0u
+#define GM_LOCATE_DEGENERATE    2u         /* fewer than 4 used points in a pass */
+#define GM_LOCATE_SINGULAR      3u         /* a non-positive (or non-finite) Cholesky pivot, or a step that is not finite */
+#define GM_LOCATE_FAILED_MASK   0xFFu      /* status & mask != 0: the pose is NaN */
+#define GM_LOCATE_NOT_CONVERGED (1u << 8)  /* |last step| > GM_FIT_STEP_BOUND (the pose is still published) */
+#define GM_LOCATE_PASSES        3
+
+typedef struct gm_wall_locate_params {
+    uint32_t struct_size;     /* = sizeof(gm_wall_locate_params) */
+    uint32_t reference;       /* GM_WALL_LOCATE_DESIGN (default) or GM_WALL_LOCATE_MAP */
+    uint32_t min_count;       /* >= 1 (default 8): points a cell needs to be usable (MAP) */
+    uint32_t reserved;        /* 0 */
+    double   gate;            /* metres, in (0, 8] (default 0.25): the gate of pass 0, halved by every later pass */
+} gm_wall_locate_params;
+
+typedef struct gm_wall_locate_pass {   /* 112 bytes */
+    float    o[3], a[3], u[3], v[3];   /* the pass's state c, d, u', v' in SENSOR coordinates (fp32, as the points saw it) */
+    float    gate;                     /* g_k */
+    uint32_t plane, outside, unsurveyed, gated, used;   /* the classes: their sum is n_points */
+    double   rms;                      /* of res over the used points; NaN when there is none */
+    double   step[4];                  /* x: metres along u', v'; radians about them.  NaN for a failed pass */
+} gm_wall_locate_pass;
+
+typedef struct gm_wall_locate_info {   /* 488 bytes */
+    uint32_t struct_size;     /* = sizeof(gm_wall_locate_info), filled by the library */
+    uint32_t status;          /* GM_LOCATE_* */
+    uint32_t passes;          /* passes completed: 3 unless the chain failed */
+    uint32_t n_points;        /* the valid cloud's points */
+    int64_t  anchor_station;  /* j_f of the caller's pose */
+    double   pose[12];        /* the corrected pose, row-major 3x4 [Rm' | tr'], sensor -> map */
+    double   lateral[2], tilt[2];   /* the total correction along u', v' (metres) and about them (radians) */
+    gm_wall_locate_pass pass[GM_LOCATE_PASSES];
+} gm_wall_locate_info;
+
+/* Host only: the defaults of the table above.  A NULL is ignored. */
+void gm_wall_locate_default_params(gm_wall_locate_params *p);
+/* Host only, no device, no map: GM_OK for parameters a locate accepts; GM_ERR_INVALID_ARG for a NULL, a struct_size
+ * mismatch, a reference that is neither of the two, min_count 0 or a gate outside (0, 8] (a NaN included). */
+gm_status gm_wall_locate_check_params(const gm_wall_locate_params *p);
+/* Locates the valid cloud of the frame last submitted to `slot` of ctx against the map.  Enqueued on the slot's stream
+ * behind the frame's work; returns without waiting.  It reads the point count and the slot's final labels on the device,
+ * as the add and the check do; with GM_CFG_GRAPH it is plain launches after the graph.  Arguments, errors and readiness as
+ * for gm_wall_map_check_frame (prm NULL: the defaults; a bad reference, min_count 0 or a gate outside (0, 8] is
+ * GM_ERR_INVALID_ARG). */
+gm_status gm_wall_map_locate_frame(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, const double pose[12],
+                                   const gm_wall_locate_params *prm);
+/* The result of the last locate enqueued on (map, slot).  Waits for that locate only (an event recorded behind it, not
+ * the slot's stream).  GM_ERR_NOT_READY: no locate was enqueued on (map, slot); GM_ERR_INVALID_ARG: NULL map / info, a bad
+ * slot.  The result stays readable until the next locate on that (map, slot) -- gm_wall_map_locate_points counts as one
+ * on slot 0. */
+gm_status gm_wall_map_get_locate(gm_wall_map *map, uint32_t slot, gm_wall_locate_info *info);
+/* The same kernels as one blocking stage call on host buffers (slot 0 of the map's context; gm_wall_map_add_points'
+ * conventions).  The per-point outputs may each be NULL and are those of the last pass that ran: residual (float[n]: res,
+ * NaN unless the point was used), cell (int32_t[n]: j * n_sectors + k of a point that reached a cell in MAP, else -1;
+ * always -1 in DESIGN).  Fed a slot's valid cloud and labels, it returns that slot's locate bit for bit. */
+gm_status gm_wall_map_locate_points(gm_wall_map *map, const float *xyz, uint32_t n, const uint8_t *labels, const double pose[12],
+                                    const gm_wall_locate_params *prm, gm_wall_locate_info *info, float *residual, int32_t *cell);
+
 /* ---- a check's changed points as objects (gm_wall_map_check_objects, gm_wall_check_objects) ---------------------------
  * The changed rows of a check grouped into a short list: "one object, 1.8 m long, between 20 and 44 degrees, 0.5 m inside
  * the profile, at these sensor coordinates".  The result is a function of the MULTISET of rows (gm_wall_check_point), the
