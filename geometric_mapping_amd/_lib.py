@@ -74,6 +74,14 @@ GM_LOCATE_SINGULAR = 3
 GM_LOCATE_FAILED_MASK = 0xFF
 GM_LOCATE_NOT_CONVERGED = 1 << 8
 GM_LOCATE_PASSES = 3
+GM_WALL_ALIGN_MAX_PATCH_CELLS = 8192
+GM_WALL_ALIGN_MAX_SHIFT = 64
+GM_WALL_ALIGN_MAX_SHIFTS = 4096
+GM_ALIGN_OK = 0
+GM_ALIGN_NO_OVERLAP = 2
+GM_ALIGN_FAILED_MASK = 0xFF
+GM_ALIGN_AMBIGUOUS = 1 << 8
+GM_ALIGN_AT_BORDER = 1 << 9
 (GM_WALL_CHECK_CLS_PLANE, GM_WALL_CHECK_CLS_BEYOND_GATE, GM_WALL_CHECK_CLS_OUTSIDE, GM_WALL_CHECK_CLS_UNSURVEYED,
  GM_WALL_CHECK_CLS_UNCHANGED, GM_WALL_CHECK_CLS_CHANGED_POS, GM_WALL_CHECK_CLS_CHANGED_NEG) = range(7)
 
@@ -228,6 +236,27 @@ class WallLocateInfo(C.Structure):
                 ("pass_", WallLocatePass * 3)]
 
 
+class WallAlignParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("half_patch_stations", C.c_uint32), ("max_station_shift", C.c_uint32),
+                ("max_sector_shift", C.c_uint32), ("min_count", C.c_uint32), ("min_frame_count", C.c_uint32),
+                ("min_overlap", C.c_uint32), ("reserved", C.c_uint32), ("gate", C.c_double), ("clip", C.c_double),
+                ("min_distinction", C.c_double)]
+
+
+class WallAlignScore(C.Structure):
+    _fields_ = [("ssd", C.c_uint64), ("sum_d", C.c_int64), ("n", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class WallAlignInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("status", C.c_uint32), ("n_points", C.c_uint32), ("plane", C.c_uint32),
+                ("beyond_gate", C.c_uint32), ("outside_patch", C.c_uint32), ("binned", C.c_uint32),
+                ("patch_cells_usable", C.c_uint32), ("anchor_station", C.c_int64), ("half_patch_stations", C.c_uint32),
+                ("max_station_shift", C.c_uint32), ("max_sector_shift", C.c_uint32), ("overlap", C.c_uint32),
+                ("best_station", C.c_int32), ("best_sector", C.c_int32), ("frac_station", C.c_double),
+                ("frac_sector", C.c_double), ("shift_m", C.c_double), ("roll", C.c_double), ("bias_m", C.c_double),
+                ("rms_best", C.c_double), ("rms_runner", C.c_double), ("distinction", C.c_double), ("pose", C.c_double * 12)]
+
+
 class WallObject(C.Structure):
     _fields_ = [("label", C.c_uint32), ("sign", C.c_int32), ("blocks", C.c_uint32), ("peak_index", C.c_uint32),
                 ("station_min", C.c_uint32), ("station_max", C.c_uint32), ("sector_min", C.c_uint32), ("sector_max", C.c_uint32),
@@ -323,6 +352,7 @@ def load():
     wcprmp, wcptp, wcinfop = C.POINTER(WallCloudParams), C.POINTER(WallCloudPoint), C.POINTER(WallCloudInfo)
     wkprmp, wkptp, wkinfop = C.POINTER(WallCheckParams), C.POINTER(WallCheckPoint), C.POINTER(WallCheckInfo)
     wlprmp, wlinfop = C.POINTER(WallLocateParams), C.POINTER(WallLocateInfo)
+    waprmp, wascp, wainfop = C.POINTER(WallAlignParams), C.POINTER(WallAlignScore), C.POINTER(WallAlignInfo)
     woprmp, wobjp, woinfop, wometp = (C.POINTER(WallObjectParams), C.POINTER(WallObject), C.POINTER(WallObjectsInfo),
                                       C.POINTER(WallObjectMetrics))
     proto = {
@@ -399,6 +429,12 @@ def load():
         "gm_wall_map_locate_frame": (C.c_int, [vp, vp, u32, dp, wlprmp]),
         "gm_wall_map_get_locate": (C.c_int, [vp, u32, wlinfop]),
         "gm_wall_map_locate_points": (C.c_int, [vp, fp, u32, u8p, dp, wlprmp, wlinfop, fp, i32p]),
+        "gm_wall_align_default_params": (None, [waprmp]),
+        "gm_wall_align_check_params": (C.c_int, [waprmp, u32]),
+        "gm_wall_align_select": (C.c_int, [C.POINTER(WallParams), waprmp, dp, wascp, u32, wainfop]),
+        "gm_wall_map_align_frame": (C.c_int, [vp, vp, u32, dp, waprmp, waddp]),
+        "gm_wall_map_get_align": (C.c_int, [vp, u32, wainfop, wascp, u32, u32p]),
+        "gm_wall_map_align_points": (C.c_int, [vp, fp, u32, u8p, dp, waprmp, waddp, wainfop, wascp, u32, u32p, fp, i32p]),
         "gm_wall_object_default_params": (None, [woprmp]),
         "gm_wall_map_check_objects": (C.c_int, [vp, u32, woprmp, woinfop, wobjp, u32, u32p, i32p, u32]),
         "gm_wall_check_objects": (C.c_int, [vp, wkptp, u32, C.c_int64, woprmp, woinfop, wobjp, u32, u32p, i32p]),

@@ -570,6 +570,45 @@ def _wall_locate_params(**kw):
     return p
 
 
+WALL_ALIGN_SCORE = np.dtype([("ssd", "<u8"), ("sum_d", "<i8"), ("n", "<u4"), ("reserved", "<u4")])   # gm_wall_align_score, 24 bytes
+_ALIGN_INT = ("status", "n_points", "plane", "beyond_gate", "outside_patch", "binned", "patch_cells_usable", "anchor_station",
+              "half_patch_stations", "max_station_shift", "max_sector_shift", "overlap", "best_station", "best_sector")
+_ALIGN_F64 = ("frac_station", "frac_sector", "shift_m", "roll", "bias_m", "rms_best", "rms_runner", "distinction")
+
+
+def _wall_align_params(**kw):
+    p = _lib.WallAlignParams()
+    _lib.load().gm_wall_align_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k in ("struct_size", "reserved"):
+            raise TypeError(f"unknown align parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def _align_info(i):
+    d = {k: int(getattr(i, k)) for k in _ALIGN_INT}
+    d.update({k: float(getattr(i, k)) for k in _ALIGN_F64})
+    d["pose"] = np.array(i.pose[:], dtype=np.float64).reshape(3, 4)
+    d["bytes"] = bytes(i)
+    return d
+
+
+def align_select(wall_params, pose, table, **params):
+    """gm_wall_align_select (host only): the info dict of the selection and the pose from a WALL_ALIGN_SCORE table of
+    (2A + 1)(2B + 1) records, under the map parameters `wall_params` (a gm_wall_params, WallMap.params()) and the align
+    parameters given as keywords.  The device's counts (n_points, the classes, patch_cells_usable) are 0."""
+    t = np.ascontiguousarray(np.asarray(table, dtype=WALL_ALIGN_SCORE).reshape(-1))
+    m = WallMap._pose(pose)
+    p = _wall_align_params(**params)
+    info = _lib.WallAlignInfo()
+    st = _lib.load().gm_wall_align_select(C.byref(wall_params), C.byref(p), m.ctypes.data_as(C.POINTER(C.c_double)),
+                                          t.ctypes.data_as(C.POINTER(_lib.WallAlignScore)), len(t), C.byref(info))
+    if st != _lib.GM_OK:
+        raise _lib.GmError(st, "gm_wall_align_select refused its arguments")
+    return _align_info(info)
+
+
 def _wall_object_params(**kw):
     p = _lib.WallObjectParams()
     _lib.load().gm_wall_object_default_params(C.byref(p))
@@ -939,6 +978,58 @@ class WallMap:
             self._h(), _f32(xyz), n, lp, m.ctypes.data_as(C.POINTER(C.c_double)), C.byref(p), C.byref(info),
             _f32(res) if outputs else None, cell.ctypes.data_as(C.POINTER(C.c_int32)) if outputs else None))
         return self._locate_info(info), (res[:n].copy() if outputs else None), (cell[:n].copy() if outputs else None)
+
+    @staticmethod
+    def align_params(**kw):
+        """gm_wall_align_params with the library's defaults, then the keywords (half_patch_stations, max_station_shift,
+        max_sector_shift, min_count, min_frame_count, min_overlap, gate, clip, min_distinction)."""
+        return _wall_align_params(**kw)
+
+    def align_frame(self, slot=0, pose=np.eye(4)[:3], **params):
+        """gm_wall_map_align_frame: enqueue the chainage and roll alignment of `pose` for the slot's last submitted frame
+        against this map.  Returns the add info dict (its gate is the align's) at once; align_result() fetches the result."""
+        m = self._pose(pose)
+        p = self.align_params(**params)
+        i = _lib.WallAddInfo()
+        self._ctx._check(self._L.gm_wall_map_align_frame(self._h(), self._ctx._ctx, slot, m.ctypes.data_as(C.POINTER(C.c_double)),
+                                                         C.byref(p), C.byref(i)))
+        return self._add_info(i)
+
+    def align_result(self, slot=0):
+        """gm_wall_map_get_align: (info dict, WALL_ALIGN_SCORE table shaped (2A + 1, 2B + 1)) of the last align on the slot.
+        The info holds status, the class counts, anchor_station, P, A, B as used, overlap, best_station, best_sector, the
+        fractions, shift_m, roll, bias_m, rms_best, rms_runner, distinction, pose (3, 4) float64 (NaN when
+        status & GM_ALIGN_FAILED_MASK) and bytes (the raw gm_wall_align_info).  A count query first, then the sized call."""
+        info, got = _lib.WallAlignInfo(), C.c_uint32(0)
+        self._ctx._check(self._L.gm_wall_map_get_align(self._h(), slot, None, None, 0, C.byref(got)))
+        cap = int(got.value)
+        t = np.zeros(max(cap, 1), dtype=WALL_ALIGN_SCORE)
+        self._ctx._check(self._L.gm_wall_map_get_align(self._h(), slot, C.byref(info), t.ctypes.data_as(C.POINTER(_lib.WallAlignScore)),
+                                                       cap, C.byref(got)))
+        d = _align_info(info)
+        return d, t[:cap].reshape(2 * d["max_station_shift"] + 1, 2 * d["max_sector_shift"] + 1).copy()
+
+    def align_points(self, cloud, pose=np.eye(4)[:3], labels=None, outputs=True, **params):
+        """gm_wall_map_align_points on a host cloud [n,3]: (info dict with the add info under "add", table, residual [n]
+        float32, cell [n] int32: jr * n_sectors + k of a binned point, else -1); outputs False skips the per-point arrays
+        (None, None)."""
+        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+        m = self._pose(pose)
+        lab, lp = GeometricMapping._u8(labels)
+        p = self.align_params(**params)
+        n = len(xyz)
+        add, info, got = _lib.WallAddInfo(), _lib.WallAlignInfo(), C.c_uint32(0)
+        na, nb = 2 * int(p.max_station_shift) + 1, 2 * int(p.max_sector_shift) + 1
+        t = np.zeros(na * nb, dtype=WALL_ALIGN_SCORE)
+        res = np.empty(max(n, 1), dtype=np.float32) if outputs else None
+        cell = np.empty(max(n, 1), dtype=np.int32) if outputs else None
+        self._ctx._check(self._L.gm_wall_map_align_points(
+            self._h(), _f32(xyz), n, lp, m.ctypes.data_as(C.POINTER(C.c_double)), C.byref(p), C.byref(add), C.byref(info),
+            t.ctypes.data_as(C.POINTER(_lib.WallAlignScore)), len(t), C.byref(got),
+            _f32(res) if outputs else None, cell.ctypes.data_as(C.POINTER(C.c_int32)) if outputs else None))
+        d = _align_info(info)
+        d["add"] = self._add_info(add)
+        return d, t.reshape(na, nb), (res[:n].copy() if outputs else None), (cell[:n].copy() if outputs else None)
 
     @staticmethod
     def object_params(**kw):

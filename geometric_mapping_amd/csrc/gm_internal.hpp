@@ -444,6 +444,29 @@ struct WallLocateArgs {
     uint32_t *ticket;          // 0 between launches
 };
 void launch_wall_locate(const WallLocateArgs &a, hipStream_t s);   // the three passes
+// k_wall_align.hip (gm_wall_map_align_*): bin -> values -> score
+constexpr int kWallAlignCounters = 8;   // u64: plane, beyond_gate, outside_patch, binned, n_points, patch_cells_usable, pad
+constexpr int32_t kWallAlignNone = -2147483647 - 1;   // the value of an unusable cell in both int32 images
+constexpr int32_t kWallAlignSat = 1 << 30;            // |m| saturates here: far beyond every clamp C <= 2^23
+struct WallAlignArgs {
+    WallArgs w;                // the add's arguments (its window and table-totals fields unused); gate is the align's
+    uint32_t P, A, B;          // half_patch_stations, max_station_shift, max_sector_shift
+    uint32_t min_count, min_frame_count;
+    uint32_t rows;             // patch rows per block of k_wall_align_score, 1 .. 2P
+    long long C;               // the clamp, 1 .. 2^23
+    unsigned long long *ctr;   // [kWallAlignCounters]       } one block, zeroed by the caller on the same stream:
+    gm_wall_align_score *table;   // [(2A + 1)(2B + 1)]      }   ctr | table | p_sum | p_cnt
+    unsigned long long *p_sum; // [2P n_sectors] the patch   }
+    uint32_t *p_cnt;           // [2P n_sectors]             }
+    int32_t *f;                // [2P n_sectors] the patch's values
+    int32_t *m;                // [(2P + 2A) n_sectors] the map's values of stations j_f - P - A ...
+};
+uint32_t wall_blocks(uint32_t n_cap, uint32_t points_per_block);   // k_wall.hip: the add's grid
+// n_cap: the most points the launch can see (the grid is sized by it)
+void launch_wall_align_bin(const WallAlignArgs &a, uint32_t n_cap, hipStream_t s);
+void launch_wall_align_values(const WallAlignArgs &a, hipStream_t s);   // behind the wait on the adds
+void launch_wall_align_score(const WallAlignArgs &a, hipStream_t s);
+uint32_t wall_align_default_rows(uint32_t n_sectors);
 // k_wall_objects.hip (gm_wall_map_check_objects, gm_wall_check_objects): bin -> tiles -> seams -> flatten | blocks ->
 // reduce -> select | rows
 constexpr uint32_t kWallObjectTileBlocks = 4096;      // the most window blocks of a tile (its LDS tables)

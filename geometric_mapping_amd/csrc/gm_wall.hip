@@ -91,6 +91,19 @@ struct WallLocateSlot {
     double of[3] = {0.0, 0.0, 0.0};         // its o_f, map coordinates
 };
 
+// gm_wall_map_align_*: the state of one (map, slot), allocated on first use, freed with the map
+struct WallAlignSlot {
+    DevArray<uint8_t> zeroed;               // counters | score table | patch sums | patch counts: one zero-fill per align
+    DevArray<int32_t> f, m;                 // the two value images
+    HostArray<uint8_t> h_res;               // pinned copy of counters | score table, valid once `done` has passed
+    hipEvent_t done = nullptr;              // recorded behind the align and the copy of its result
+    bool have = false;                      // an align was enqueued: a result is (or will be) readable
+    bool outstanding = false;               // the host has not waited for `done` yet
+    gm_wall_align_params prm;               // of that align
+    double pose[12];                        // the caller's pose of that align
+    uint32_t n_shifts = 0;                  // (2A + 1)(2B + 1)
+};
+
 struct gm_wall_map {
     gm_ctx *ctx = nullptr;
     gm_wall_params prm;
@@ -125,6 +138,9 @@ struct gm_wall_map {
     std::vector<WallCheckSlot> checks;         // per slot of ctx
     // gm_wall_map_locate_*
     std::vector<WallLocateSlot> locates;       // per slot of ctx
+    // gm_wall_map_align_*: the patch rows per score block (GM_WALL_ALIGN_ROWS: tests, measurements; 0: the default rule)
+    std::vector<WallAlignSlot> aligns;         // per slot of ctx
+    uint32_t align_rows = 0;
     // gm_wall_map_check_objects / gm_wall_check_objects: the tile in blocks (GM_WALL_OBJECT_TILE: tests, measurements) and
     // the scratch
     uint32_t object_tr = GM_WALL_OBJECT_TILE_ROWS, object_tc = GM_WALL_OBJECT_TILE_COLS;
@@ -167,46 +183,48 @@ gm_status check_params(const gm_wall_params *p)
 }
 
 // the design frame of include/gm_hip.h: k_surface.hip's surf_frame on fp64 inputs, kept in fp64
-void design_frame(gm_wall_map *m)
+struct DesignFrame { double o[3], a[3], u[3], v[3], R; uint32_t status; };
+void design_frame_of(const gm_wall_params &p, DesignFrame &d)
 {
-    const gm_wall_params &p = m->prm;
     const double dn = sqrt(dot(p.direction, p.direction));
     const double s = dot(p.direction, p.forward);
-    for (int k = 0; k < 3; ++k) m->a[k] = (s >= 0.0 ? p.direction[k] : -p.direction[k]) / dn;
-    const double ca = dot(p.point, m->a), ua = dot(p.up, m->a);
+    for (int k = 0; k < 3; ++k) d.a[k] = (s >= 0.0 ? p.direction[k] : -p.direction[k]) / dn;
+    const double ca = dot(p.point, d.a), ua = dot(p.up, d.a);
     double u[3];
-    for (int k = 0; k < 3; ++k) u[k] = p.up[k] - ua * m->a[k];
+    for (int k = 0; k < 3; ++k) u[k] = p.up[k] - ua * d.a[k];
     const double ul = sqrt(dot(u, u)), upl = sqrt(dot(p.up, p.up));
-    m->status = GM_SURF_OK;
+    d.status = GM_SURF_OK;
     if (ul < 0.1 * upl) {
         double e2[3];
-        fit_basis(m->a, u, e2);
-        m->status |= GM_SURF_UP_FALLBACK;
+        fit_basis(d.a, u, e2);
+        d.status |= GM_SURF_UP_FALLBACK;
     } else {
         for (int k = 0; k < 3; ++k) u[k] /= ul;
     }
-    const double *a = m->a;
+    const double *a = d.a;
     const double v[3] = {a[1] * u[2] - a[2] * u[1], a[2] * u[0] - a[0] * u[2], a[0] * u[1] - a[1] * u[0]};
     for (int k = 0; k < 3; ++k) {
-        m->o[k] = p.point[k] - ca * a[k];
-        m->u[k] = u[k];
-        m->v[k] = v[k];
+        d.o[k] = p.point[k] - ca * a[k];
+        d.u[k] = u[k];
+        d.v[k] = v[k];
     }
-    m->R = p.radius;
+    d.R = p.radius;
+}
+void design_frame(gm_wall_map *m)
+{
+    DesignFrame d;
+    design_frame_of(m->prm, d);
+    for (int k = 0; k < 3; ++k) { m->o[k] = d.o[k]; m->a[k] = d.a[k]; m->u[k] = d.u[k]; m->v[k] = d.v[k]; }
+    m->R = d.R;
+    m->status = d.status;
 }
 
-// The per-add frame: pose check, anchor, (o', a', u', v') in sensor coordinates, and the kernel's arguments but for the
-// buffers.  The context's crop bound (a cube around the sensor) sizes the LDS window.
-// f64 (a locate's start): the same vectors before the rounding, and o_f in map coordinates.
-struct WallFrame64 { double c[3], d[3], u[3], v[3], of[3]; };
-gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info *info, WallArgs &w, WallFrame64 *f64 = nullptr)
+// the library's pose check: 0 the pose is accepted (Rm, tr filled), 1 an entry is not finite, 2 Rm is not a rotation
+int pose_split(const double pose[12], double Rm[3][3], double tr[3])
 {
-    gm_ctx *ctx = m->ctx;
-    if (!pose) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: NULL pose");
-    double Rm[3][3], tr[3];
     for (int r = 0; r < 3; ++r) {
         for (int c = 0; c < 4; ++c)
-            if (!isfinite(pose[4 * r + c])) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose is not finite");
+            if (!isfinite(pose[4 * r + c])) return 1;
         for (int c = 0; c < 3; ++c) Rm[r][c] = pose[4 * r + c];
         tr[r] = pose[4 * r + 3];
     }
@@ -218,8 +236,21 @@ gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info
         }
     const double det = Rm[0][0] * (Rm[1][1] * Rm[2][2] - Rm[1][2] * Rm[2][1]) - Rm[0][1] * (Rm[1][0] * Rm[2][2] - Rm[1][2] * Rm[2][0]) +
                        Rm[0][2] * (Rm[1][0] * Rm[2][1] - Rm[1][1] * Rm[2][0]);
-    if (!(dev <= 1e-6) || !(det > 0.0))
-        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose rotation is not orthonormal to 1e-6 or is a reflection");
+    return (!(dev <= 1e-6) || !(det > 0.0)) ? 2 : 0;
+}
+
+// The per-add frame: pose check, anchor, (o', a', u', v') in sensor coordinates, and the kernel's arguments but for the
+// buffers.  The context's crop bound (a cube around the sensor) sizes the LDS window.
+// f64 (a locate's start): the same vectors before the rounding, and o_f in map coordinates.
+struct WallFrame64 { double c[3], d[3], u[3], v[3], of[3]; };
+gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info *info, WallArgs &w, WallFrame64 *f64 = nullptr)
+{
+    gm_ctx *ctx = m->ctx;
+    if (!pose) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: NULL pose");
+    double Rm[3][3], tr[3];
+    const int bad = pose_split(pose, Rm, tr);
+    if (bad == 1) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose is not finite");
+    if (bad) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose rotation is not orthonormal to 1e-6 or is a reflection");
     const gm_wall_params &p = m->prm;
     const double ds = p.station_length;
     const double rel[3] = {tr[0] - m->o[0], tr[1] - m->o[1], tr[2] - m->o[2]};
@@ -298,6 +329,11 @@ gm_status sync_map(gm_wall_map *m)
             GMW_HIP(ctx, hipEventSynchronize(l.done));
             l.outstanding = false;
         }
+    for (WallAlignSlot &l : m->aligns)
+        if (l.outstanding) {
+            GMW_HIP(ctx, hipEventSynchronize(l.done));
+            l.outstanding = false;
+        }
     GMW_HIP(ctx, hipStreamSynchronize(m->stream));
     return GM_OK;
 }
@@ -323,6 +359,10 @@ void free_map(gm_wall_map *m)
         if (c.adds) hipEventDestroy(c.adds);
     }
     for (WallLocateSlot &l : m->locates) {
+        if (l.outstanding) hipEventSynchronize(l.done);
+        if (l.done) hipEventDestroy(l.done);
+    }
+    for (WallAlignSlot &l : m->aligns) {
         if (l.outstanding) hipEventSynchronize(l.done);
         if (l.done) hipEventDestroy(l.done);
     }
@@ -665,6 +705,216 @@ gm_status add_wait_locates(gm_wall_map *m, uint32_t slot, hipStream_t s)
     return GM_OK;
 }
 
+// ---- gm_wall_map_align_* ----
+
+bool align_prm_ok(const gm_wall_align_params &p, uint32_t nsec)
+{
+    if (p.struct_size != sizeof(gm_wall_align_params) || nsec < 1u || nsec > GM_WALL_MAX_SECTORS) return false;
+    if (p.half_patch_stations < 1u || 2ull * p.half_patch_stations * nsec > GM_WALL_ALIGN_MAX_PATCH_CELLS) return false;
+    if (p.max_station_shift > GM_WALL_ALIGN_MAX_SHIFT || p.max_sector_shift > GM_WALL_ALIGN_MAX_SHIFT) return false;
+    if (2u * p.max_sector_shift + 1u > nsec) return false;
+    if ((2u * p.max_station_shift + 1u) * (2u * p.max_sector_shift + 1u) > GM_WALL_ALIGN_MAX_SHIFTS) return false;
+    if (p.min_count < 1u || p.min_frame_count < 1u || p.min_overlap < 1u) return false;
+    if (!(p.gate > 0.0) || !(p.gate <= 8.0) || !(p.clip > 0.0) || !(p.clip <= 8.0) || !(rint(p.clip * 1048576.0) >= 1.0)) return false;
+    return p.min_distinction >= 1.0 && isfinite(p.min_distinction);
+}
+
+// The selection and the pose of include/gm_hip.h from a table of (2A + 1)(2B + 1) records.  Host only; fills everything
+// but the device's counts.
+void align_select(const DesignFrame &d, const gm_wall_params &wp, const gm_wall_align_params &ap, const double Rm[3][3],
+                  const double tr[3], const gm_wall_align_score *t, gm_wall_align_info *info)
+{
+    const int A = (int)ap.max_station_shift, B = (int)ap.max_sector_shift, nb = 2 * B + 1, ns = (2 * A + 1) * nb;
+    const double nan = __builtin_nan(""), inf = __builtin_inf();
+    const double ds = wp.station_length;
+    memset(info, 0, sizeof(*info));
+    info->struct_size = (uint32_t)sizeof(gm_wall_align_info);
+    const double rel[3] = {tr[0] - d.o[0], tr[1] - d.o[1], tr[2] - d.o[2]};
+    const double jd = floor((dot(rel, d.a) - wp.t_min) / ds);
+    info->anchor_station = fabs(jd) < 4.0e18 ? (int64_t)jd : 0;
+    info->half_patch_stations = ap.half_patch_stations;
+    info->max_station_shift = ap.max_station_shift;
+    info->max_sector_shift = ap.max_sector_shift;
+    auto cheb = [&](int i, int a0, int b0) { return std::max(abs(i / nb - A - a0), abs(i % nb - B - b0)); };
+    auto valid = [&](int i) { return t[i].n >= ap.min_overlap; };
+    auto cost = [&](int i) { return (double)t[i].ssd / (double)t[i].n; };
+    int best = -1;
+    for (int i = 0; i < ns; ++i) {
+        if (!valid(i)) continue;
+        if (best >= 0) {   // ssd_i / n_i against ssd_best / n_best, exactly
+            const unsigned __int128 l = (unsigned __int128)t[i].ssd * t[best].n, r = (unsigned __int128)t[best].ssd * t[i].n;
+            if (l > r || (l == r && cheb(i, 0, 0) >= cheb(best, 0, 0))) continue;
+        }
+        best = i;
+    }
+    if (best < 0) {
+        info->status = GM_ALIGN_NO_OVERLAP;
+        info->frac_station = info->frac_sector = info->shift_m = info->roll = info->bias_m = nan;
+        info->rms_best = info->rms_runner = info->distinction = nan;
+        for (int k = 0; k < 12; ++k) info->pose[k] = nan;
+        return;
+    }
+    const int ia = best / nb, ib = best % nb, sa = ia - A, sb = ib - B;
+    const double c0 = cost(best);
+    auto fraction = [&](int lo, int hi, bool have) {
+        if (!have || !valid(lo) || !valid(hi)) return 0.0;
+        const double cm = cost(lo), cp = cost(hi), den = cm - 2.0 * c0 + cp;
+        if (!(den > 0.0)) return 0.0;
+        const double f = 0.5 * (cm - cp) / den;
+        return f < -0.5 ? -0.5 : (f > 0.5 ? 0.5 : f);
+    };
+    const double fa = fraction(best - nb, best + nb, ia > 0 && ia < 2 * A);
+    const double fb = fraction(best - 1, best + 1, ib > 0 && ib < 2 * B);
+    double cr = inf;
+    bool runner = false;
+    for (int i = 0; i < ns; ++i)
+        if (valid(i) && cheb(i, sa, sb) > 1) {
+            const double c = cost(i);
+            if (!runner || c < cr) cr = c;
+            runner = true;
+        }
+    const double two_pi = 6.283185307179586476925286766559;
+    info->overlap = t[best].n;
+    info->best_station = sa;
+    info->best_sector = sb;
+    info->frac_station = fa;
+    info->frac_sector = fb;
+    info->shift_m = ((double)sa + fa) * ds;
+    info->roll = ((double)sb + fb) * (two_pi / (double)wp.n_sectors);
+    info->bias_m = ((double)t[best].sum_d * 0x1p-20) / (double)t[best].n;
+    info->rms_best = sqrt(c0) * 0x1p-20;
+    info->rms_runner = runner ? sqrt(cr) * 0x1p-20 : nan;
+    info->distinction = (c0 == 0.0 || !runner) ? inf : cr / c0;
+    info->status = GM_ALIGN_OK;
+    if (info->distinction < ap.min_distinction) info->status |= GM_ALIGN_AMBIGUOUS;
+    if ((A > 0 && abs(sa) == A) || (B > 0 && abs(sb) == B)) info->status |= GM_ALIGN_AT_BORDER;
+    // Rm' = Q Rm, tr' = o + Q (tr - o) + shift_m a;  Q = cos I + sin [a]x + (1 - cos) a a^T
+    const double cs = cos(info->roll), sn = sin(info->roll);
+    const double *a = d.a;
+    const double K[3][3] = {{0.0, -a[2], a[1]}, {a[2], 0.0, -a[0]}, {-a[1], a[0], 0.0}};
+    double Q[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) Q[r][c] = (r == c ? cs : 0.0) + sn * K[r][c] + (1.0 - cs) * a[r] * a[c];
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) info->pose[4 * r + c] = Q[r][0] * Rm[0][c] + Q[r][1] * Rm[1][c] + Q[r][2] * Rm[2][c];
+        info->pose[4 * r + 3] = d.o[r] + (Q[r][0] * rel[0] + Q[r][1] * rel[1] + Q[r][2] * rel[2]) + info->shift_m * a[r];
+    }
+}
+
+// the kernels' arguments but for the buffers
+gm_status align_args(gm_wall_map *m, const double pose[12], const gm_wall_align_params &ap, gm_wall_add_info *add_info, WallAlignArgs &a)
+{
+    memset(&a, 0, sizeof(a));
+    GMW_OK(add_frame_args(m, pose, add_info, a.w));
+    a.w.gate = (float)ap.gate;
+    if (add_info) add_info->gate = a.w.gate;
+    a.P = ap.half_patch_stations;
+    a.A = ap.max_station_shift;
+    a.B = ap.max_sector_shift;
+    a.min_count = ap.min_count;
+    a.min_frame_count = ap.min_frame_count;
+    a.C = (long long)rint(ap.clip * 1048576.0);
+    const uint32_t rows = m->align_rows ? m->align_rows : wall_align_default_rows(m->prm.n_sectors);
+    a.rows = std::min(rows, 2u * a.P);
+    return GM_OK;
+}
+
+// the scratch of (map, slot), laid out by this align's counts and zeroed on `s`
+gm_status align_prepare(gm_wall_map *m, uint32_t slot, hipStream_t s, WallAlignArgs &a)
+{
+    gm_ctx *ctx = m->ctx;
+    WallAlignSlot &l = m->aligns[slot];
+    if (!l.done) GMW_HIP(ctx, hipEventCreateWithFlags(&l.done, hipEventDisableTiming));
+    const uint64_t nsh = (uint64_t)(2u * a.A + 1u) * (2u * a.B + 1u);
+    const uint64_t pc = 2ull * a.P * m->prm.n_sectors, mc = (2ull * a.P + 2ull * a.A) * m->prm.n_sectors;
+    const uint64_t res_bytes = 8ull * kWallAlignCounters + nsh * sizeof(gm_wall_align_score), zero_bytes = res_bytes + pc * 12;
+    if (l.outstanding && (l.zeroed.cap < zero_bytes || l.f.cap < pc || l.m.cap < mc || l.h_res.cap < res_bytes)) {
+        GMW_HIP(ctx, hipEventSynchronize(l.done));   // the slot's last align may still be using the old blocks
+        l.outstanding = false;
+    }
+    if (l.h_res.cap < res_bytes) l.have = false;     // (its result goes with the block)
+    GMW_HIP(ctx, l.zeroed.reserve(zero_bytes));
+    GMW_HIP(ctx, l.f.reserve(pc));
+    GMW_HIP(ctx, l.m.reserve(mc));
+    GMW_HIP(ctx, l.h_res.reserve(res_bytes));
+    Carve cv{l.zeroed.p};
+    a.ctr = cv.take<unsigned long long>(kWallAlignCounters);
+    a.table = cv.take<gm_wall_align_score>(nsh);
+    a.p_sum = cv.take<unsigned long long>(pc);
+    a.p_cnt = cv.take<uint32_t>(pc);
+    a.f = l.f.p;
+    a.m = l.m.p;
+    GMW_HIP(ctx, hipMemsetAsync(l.zeroed.p, 0, zero_bytes, s));
+    return GM_OK;
+}
+
+// the three launches (the map is read behind the wait on the adds), the copy of the result and the event behind them
+gm_status align_enqueue(gm_wall_map *m, uint32_t slot, const WallAlignArgs &a, uint32_t n_cap, const gm_wall_align_params &ap,
+                        const double pose[12], hipStream_t s)
+{
+    gm_ctx *ctx = m->ctx;
+    WallAlignSlot &l = m->aligns[slot];
+    const uint32_t nsh = (2u * a.A + 1u) * (2u * a.B + 1u);
+    launch_wall_align_bin(a, n_cap, s);
+    GMW_HIP(ctx, hipGetLastError());
+    GMW_OK(check_wait_adds(m, slot, s));
+    launch_wall_align_values(a, s);
+    launch_wall_align_score(a, s);
+    GMW_HIP(ctx, hipGetLastError());
+    GMW_HIP(ctx, hipMemcpyAsync(l.h_res.p, l.zeroed.p, 8 * kWallAlignCounters + (size_t)nsh * sizeof(gm_wall_align_score),
+                                hipMemcpyDeviceToHost, s));
+    GMW_HIP(ctx, hipEventRecord(l.done, s));
+    l.have = true;
+    l.outstanding = true;
+    l.prm = ap;
+    memcpy(l.pose, pose, sizeof(l.pose));
+    l.n_shifts = nsh;
+    return GM_OK;
+}
+
+// the result of (map, slot) once `done` has passed: the device's table and counts, the selection and the pose in fp64
+gm_status align_result(gm_wall_map *m, uint32_t slot, gm_wall_align_info *info, gm_wall_align_score *scores, uint32_t capacity,
+                       uint32_t *n_out)
+{
+    gm_ctx *ctx = m->ctx;
+    WallAlignSlot &l = m->aligns[slot];
+    if (l.outstanding) {
+        GMW_HIP(ctx, hipEventSynchronize(l.done));
+        l.outstanding = false;
+    }
+    const unsigned long long *h = reinterpret_cast<const unsigned long long *>(l.h_res.p);
+    const gm_wall_align_score *table = reinterpret_cast<const gm_wall_align_score *>(l.h_res.p + 8 * kWallAlignCounters);
+    if (n_out) *n_out = l.n_shifts;
+    if (info) {
+        double Rm[3][3], tr[3];
+        (void)pose_split(l.pose, Rm, tr);   // (accepted at the enqueue)
+        DesignFrame d;
+        for (int k = 0; k < 3; ++k) { d.o[k] = m->o[k]; d.a[k] = m->a[k]; d.u[k] = m->u[k]; d.v[k] = m->v[k]; }
+        d.R = m->R;
+        d.status = m->status;
+        align_select(d, m->prm, l.prm, Rm, tr, table, info);
+        info->plane = (uint32_t)h[0];
+        info->beyond_gate = (uint32_t)h[1];
+        info->outside_patch = (uint32_t)h[2];
+        info->binned = (uint32_t)h[3];
+        info->n_points = (uint32_t)h[4];
+        info->patch_cells_usable = (uint32_t)h[5];
+    }
+    if (!scores && capacity) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map align: NULL scores with a capacity");
+    if (!scores) return GM_OK;   // a count query
+    if (l.n_shifts > capacity) return gm_fail(ctx, GM_ERR_CAPACITY, "gm_wall_map align: score buffer too small");
+    memcpy(scores, table, (size_t)l.n_shifts * sizeof(gm_wall_align_score));
+    return GM_OK;
+}
+
+// an add on `s` must not be seen by the aligns enqueued before it on other slots
+gm_status add_wait_aligns(gm_wall_map *m, uint32_t slot, hipStream_t s)
+{
+    for (uint32_t i = 0; i < m->ctx->n_slots; ++i)
+        if (i != slot && m->aligns[i].outstanding) GMW_HIP(m->ctx, hipStreamWaitEvent(s, m->aligns[i].done, 0));
+    return GM_OK;
+}
+
 // ---- gm_wall_map_check_objects / gm_wall_check_objects ----
 
 bool object_prm_ok(const gm_wall_object_params &p)
@@ -843,6 +1093,8 @@ gm_status gm_wall_map_create(gm_ctx *ctx, const gm_wall_params *params, gm_wall_
     m->pending.assign(ctx->n_slots, 0);
     m->checks.resize(ctx->n_slots);
     m->locates.resize(ctx->n_slots);
+    m->aligns.resize(ctx->n_slots);
+    if (const char *e = getenv("GM_WALL_ALIGN_ROWS")) m->align_rows = (uint32_t)strtoul(e, nullptr, 10);   // 0: the default
     if (const char *e = getenv("GM_WALL_POINTS_PER_BLOCK")) m->points_per_block = (uint32_t)strtoul(e, nullptr, 10);
     if (const char *e = getenv("GM_WALL_REGION_TILE")) {   // <stations>x<sectors>; anything else: the default
         unsigned ts = 0, tk = 0;
@@ -909,6 +1161,7 @@ gm_status gm_wall_map_add_frame(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, co
     for (uint32_t i = 0; i < ctx->n_slots; ++i)
         if (i != slot && map->checks[i].outstanding) GMW_HIP(ctx, hipStreamWaitEvent(sl.stream, map->checks[i].done, 0));
     GMW_OK(add_wait_locates(map, slot, sl.stream));   // (nor a locate)
+    GMW_OK(add_wait_aligns(map, slot, sl.stream));    // (nor an align)
     launch_wall_add(w, sl.n_in, map->points_per_block, sl.stream);
     GMW_HIP(ctx, hipGetLastError());
     map->pending[slot] = 1;
@@ -931,6 +1184,7 @@ gm_status gm_wall_map_add_points(gm_wall_map *map, const float *xyz, uint32_t n,
     for (uint32_t i = 1; i < ctx->n_slots; ++i)   // (as gm_wall_map_add_frame: behind the checks outstanding on other slots)
         if (map->checks[i].outstanding) GMW_HIP(ctx, hipStreamWaitEvent(s, map->checks[i].done, 0));
     GMW_OK(add_wait_locates(map, 0, s));
+    GMW_OK(add_wait_aligns(map, 0, s));
     launch_wall_add(w, n, map->points_per_block, s);
     GMW_HIP(ctx, hipGetLastError());
     GMW_OK(sc.close());
@@ -1474,6 +1728,103 @@ gm_status gm_wall_map_locate_points(gm_wall_map *map, const float *xyz, uint32_t
     GMW_OK(locate_enqueue(map, 0, a, s));
     GMW_OK(sc.close());
     return locate_result(map, 0, info);
+}
+
+void gm_wall_align_default_params(gm_wall_align_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(gm_wall_align_params);
+    p->half_patch_stations = 20;
+    p->max_station_shift = 8;
+    p->max_sector_shift = 4;
+    p->min_count = 8;
+    p->min_frame_count = 4;
+    p->min_overlap = 64;
+    p->gate = 0.25;
+    p->clip = 0.05;
+    p->min_distinction = 1.5;
+}
+
+gm_status gm_wall_align_check_params(const gm_wall_align_params *p, uint32_t n_sectors)
+{
+    return p && align_prm_ok(*p, n_sectors) ? GM_OK : GM_ERR_INVALID_ARG;
+}
+
+gm_status gm_wall_align_select(const gm_wall_params *wall, const gm_wall_align_params *prm, const double pose[12],
+                               const gm_wall_align_score *table, uint32_t n_scores, gm_wall_align_info *info)
+{
+    if (!wall || !pose || !table || !info || check_params(wall) != GM_OK) return GM_ERR_INVALID_ARG;
+    const gm_wall_align_params ap = params_or(prm, gm_wall_align_default_params);
+    if (!align_prm_ok(ap, wall->n_sectors)) return GM_ERR_INVALID_ARG;
+    if (n_scores != (2u * ap.max_station_shift + 1u) * (2u * ap.max_sector_shift + 1u)) return GM_ERR_INVALID_ARG;
+    double Rm[3][3], tr[3];
+    if (pose_split(pose, Rm, tr)) return GM_ERR_INVALID_ARG;
+    DesignFrame d;
+    design_frame_of(*wall, d);
+    const double rel[3] = {tr[0] - d.o[0], tr[1] - d.o[1], tr[2] - d.o[2]};
+    if (!(fabs(floor((dot(rel, d.a) - wall->t_min) / wall->station_length)) < 4.0e18)) return GM_ERR_INVALID_ARG;
+    align_select(d, *wall, ap, Rm, tr, table, info);
+    return GM_OK;
+}
+
+gm_status gm_wall_map_align_frame(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, const double pose[12],
+                                  const gm_wall_align_params *prm, gm_wall_add_info *add_info)
+{
+    if (!map || !ctx) return GM_ERR_INVALID_ARG;
+    if (ctx != map->ctx) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_align_frame: the map belongs to another context");
+    if (slot >= ctx->n_slots) return gm_fail(ctx, GM_ERR_INVALID_ARG, "slot out of range");
+    const gm_wall_align_params ap = params_or(prm, gm_wall_align_default_params);
+    if (!align_prm_ok(ap, map->prm.n_sectors))
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_align_frame: struct_size mismatch or a parameter outside its limits");
+    Slot &sl = ctx->slots[slot];
+    if (!sl.submitted) return gm_fail(ctx, GM_ERR_NOT_READY, "gm_wall_map_align_frame: the slot holds no frame");
+    WallAlignArgs a;
+    GMW_OK(align_args(map, pose, ap, add_info, a));
+    if (hipSetDevice(ctx->device) != hipSuccess) return gm_fail(ctx, GM_ERR_DEVICE, "hipSetDevice failed");
+    GMW_OK(align_prepare(map, slot, sl.stream, a));
+    a.w.pts = sl.crop4;
+    a.w.labels = (ctx->cfg.flags & GM_CFG_RANSAC_PLANE) ? sl.labels : nullptr;
+    a.w.n_ptr = &sl.ctr->n_valid;
+    a.w.n_host = sl.n_in;
+    return align_enqueue(map, slot, a, sl.n_in ? sl.n_in : 1u, ap, pose, sl.stream);
+}
+
+gm_status gm_wall_map_get_align(gm_wall_map *map, uint32_t slot, gm_wall_align_info *info, gm_wall_align_score *scores,
+                                uint32_t capacity, uint32_t *n_out)
+{
+    if (!map) return GM_ERR_INVALID_ARG;
+    gm_ctx *ctx = map->ctx;
+    if (n_out) *n_out = 0;
+    if (slot >= ctx->n_slots) return gm_fail(ctx, GM_ERR_INVALID_ARG, "slot out of range");
+    if (!map->aligns[slot].have) return gm_fail(ctx, GM_ERR_NOT_READY, "gm_wall_map_get_align: no align was enqueued on this map and slot");
+    if (hipSetDevice(ctx->device) != hipSuccess) return gm_fail(ctx, GM_ERR_DEVICE, "hipSetDevice failed");
+    return align_result(map, slot, info, scores, capacity, n_out);
+}
+
+gm_status gm_wall_map_align_points(gm_wall_map *map, const float *xyz, uint32_t n, const uint8_t *labels, const double pose[12],
+                                   const gm_wall_align_params *prm, gm_wall_add_info *add_info, gm_wall_align_info *info,
+                                   gm_wall_align_score *scores, uint32_t capacity, uint32_t *n_out, float *residual,
+                                   int32_t *cell)
+{
+    if (!map) return GM_ERR_INVALID_ARG;
+    gm_ctx *ctx = map->ctx;
+    if (n_out) *n_out = 0;
+    if (n && !xyz) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_align_points: NULL xyz");
+    if (!scores && capacity) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_align_points: NULL scores with a capacity");
+    const gm_wall_align_params ap = params_or(prm, gm_wall_align_default_params);
+    if (!align_prm_ok(ap, map->prm.n_sectors))
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_align_points: struct_size mismatch or a parameter outside its limits");
+    WallAlignArgs a;
+    GMW_OK(align_args(map, pose, ap, add_info, a));
+    StageCall sc{map, n, residual, cell, nullptr, nullptr};
+    GMW_OK(sc.open());
+    hipStream_t s = sc.sl->stream;
+    GMW_OK(align_prepare(map, 0, s, a));
+    GMW_OK(sc.upload(xyz, labels, a.w));
+    GMW_OK(align_enqueue(map, 0, a, n ? n : 1u, ap, pose, s));
+    GMW_OK(sc.close());
+    return align_result(map, 0, info, scores, capacity, n_out);
 }
 
 void gm_wall_object_default_params(gm_wall_object_params *p)

@@ -175,15 +175,43 @@ def pose_matrix(position, yaw_deg=0.0, roll_deg=0.0, pitch_deg=0.0):
     return np.concatenate([rz @ ry @ rx, np.asarray(position, np.float64).reshape(3, 1)], axis=1)
 
 
+def wall_texture(t, phi, seed=0, amplitude=0.04, length=48.0, bumps_per_metre=4.0, sigma_t=(0.15, 0.6), sigma_phi=(0.08, 0.4)):
+    """A deterministic, world-fixed radial texture of a tunnel wall (metres, same shape as t): a sum of Gaussian bumps of
+    heights up to +-amplitude at centres drawn by `seed` over chainage [0, length) and the whole ring, with widths drawn
+    from sigma_t (metres) and sigma_phi (radians); the angular distance wraps.  The value at (t, phi) depends on the seed
+    and the position alone, not on the other points of the call: joints, bolts, niches and rough rock for the align
+    (gm_wall_map_align_*), which a smooth lining cannot serve."""
+    t = np.asarray(t, np.float64)
+    phi = np.asarray(phi, np.float64)
+    rng = np.random.default_rng([int(seed), 0x7E87])
+    nb = max(1, int(round(bumps_per_metre * length)))
+    ct, cp = rng.uniform(0.0, length, nb), rng.uniform(0.0, 2 * np.pi, nb)
+    st, sp = rng.uniform(*sigma_t, nb), rng.uniform(*sigma_phi, nb)
+    h = rng.uniform(-amplitude, amplitude, nb)
+    out = np.zeros(t.shape, np.float64)
+    order = np.argsort(t.reshape(-1), kind="stable")
+    ts, ps = t.reshape(-1)[order], phi.reshape(-1)[order]
+    acc = np.zeros(len(ts), np.float64)
+    for i in range(nb):   # a bump reaches 4 sigma along the axis: only the points in that span see it
+        lo, hi = np.searchsorted(ts, (ct[i] - 4 * st[i], ct[i] + 4 * st[i]))
+        if lo == hi:
+            continue
+        dp = np.mod(ps[lo:hi] - cp[i] + np.pi, 2 * np.pi) - np.pi
+        acc[lo:hi] += h[i] * np.exp(-0.5 * (((ts[lo:hi] - ct[i]) / st[i]) ** 2 + (dp / sp[i]) ** 2))
+    out.reshape(-1)[order] = acc
+    return out
+
+
 def tunnel_drive(n_frames, n_points, seed=0, radius=2.0, length=48.0, start=6.0, step=3.5, reach=7.0, sigma=0.01,
-                 patches=DRIVE_PATCHES, yaw_deg=4.0, roll_deg=3.0, lateral=0.25):
+                 patches=DRIVE_PATCHES, yaw_deg=4.0, roll_deg=3.0, lateral=0.25, texture=None):
     """A drive through a straight tunnel for the persistent wall map (gm_wall_*).  The WORLD frame is the map frame: the
     design cylinder has its axis along +x through the origin, `radius`, up = +z, and runs from chainage 0 to `length`.
     The wall carries world-fixed patches (t0, t1, phi0_deg, phi1_deg, dr) in design-map coordinates (the SURFACE_PATCHES
     form: phi from +z turning toward -y); the defaults are aligned with 0.25 m x 4 degree cells from t_min = 0.
     Frame i sees the wall within `reach` metres of chainage start + i step from a sensor with a yaw / roll of up to
     +-yaw_deg / +-roll_deg and a lateral offset of up to `lateral` metres in y and z (step < the crop length, so
-    neighbouring frames overlap).  Radial noise N(0, sigma).  Returns dict(frames=[(cloud float32 (n_points, 3) in SENSOR
+    neighbouring frames overlap).  Radial noise N(0, sigma).  texture: None (a smooth wall) or the keywords of wall_texture
+    (seed, amplitude, ...), whose world-fixed bumps are added to the radius; the draws of the frame do not change.  Returns dict(frames=[(cloud float32 (n_points, 3) in SENSOR
     coordinates, pose float64 (3, 4) sensor -> world), ...], design=dict(point, direction, radius, up, forward),
     patches, sigma, length)."""
     rng = np.random.default_rng(seed)
@@ -198,6 +226,8 @@ def tunnel_drive(n_frames, n_points, seed=0, radius=2.0, length=48.0, start=6.0,
         deg = np.rad2deg(phi)
         for t0, t1, p0, p1, dr in patches:
             rr = np.where((t >= t0) & (t < t1) & (deg >= p0) & (deg < p1), rr + dr, rr)
+        if texture is not None:
+            rr = rr + wall_texture(t, phi, **texture)
         world = np.stack([t, -rr * np.sin(phi), rr * np.cos(phi)], axis=1)
         sensor = (world - pose[:, 3]) @ pose[:, :3]   # Rm^T (p - tr)
         frames.append((np.ascontiguousarray(sensor, dtype=np.float32), pose))

@@ -450,6 +450,22 @@ gm_wall_locate_info Processor::locateWallMap(const double pose[12], const gm_wal
     return info;
 }
 
+gm_wall_align_info Processor::alignWallMap(const double pose[12], const gm_wall_align_params &prm, std::vector<gm_wall_align_score> *scores)
+{
+    if (!wall_) throw Error(GM_ERR_NOT_READY, "alignWallMap: createWallMap first");
+    if (newest_slot_ < 0) throw Error(GM_ERR_NOT_READY, "alignWallMap: no frame yet");
+    const unsigned slot = (unsigned)newest_slot_;
+    check(gm_wall_map_align_frame(wall_, ctx_, slot, pose, &prm, nullptr), "alignWallMap");
+    gm_wall_align_info info;
+    uint32_t n = 0;
+    check(gm_wall_map_get_align(wall_, slot, &info, nullptr, 0, &n), "alignWallMap");
+    if (scores) {
+        scores->resize(n);
+        check(gm_wall_map_get_align(wall_, slot, nullptr, n ? &(*scores)[0] : nullptr, n, &n), "alignWallMap");
+    }
+    return info;
+}
+
 std::vector<gm_wall_object> Processor::wallCheckObjects(const gm_wall_object_params &prm, gm_wall_objects_info *info)
 {
     if (!wall_) throw Error(GM_ERR_NOT_READY, "wallCheckObjects: createWallMap first");

@@ -156,9 +156,16 @@ public:
     std::vector<gm_wall_check_point> checkWallMap(const double pose[12], const gm_wall_check_params &prm, gm_wall_check_info *info = nullptr);
     // the pose of the newest frame corrected against the map (gm_wall_map_locate_frame + gm_wall_map_get_locate): the lateral
     // offset and the tilt against the axis are estimated, chainage and roll stay the caller's; the map is not changed.
-    // info.pose is the corrected pose (NaN when info.status & GM_LOCATE_FAILED_MASK).  Locate, then checkWallMap and
-    // addToWallMap with the corrected pose.
+    // info.pose is the corrected pose (NaN when info.status & GM_LOCATE_FAILED_MASK).  The order per frame: locateWallMap,
+    // alignWallMap with the located pose, then checkWallMap and addToWallMap with the aligned pose.
     gm_wall_locate_info locateWallMap(const double pose[12], const gm_wall_locate_params &prm);
+    // chainage and roll of the newest frame's pose against the map's texture (gm_wall_map_align_frame +
+    // gm_wall_map_get_align): the frame's deviation image is slid over the map's in whole cells and refined by a parabola;
+    // the map is not changed.  info.pose is the aligned pose (NaN when info.status & GM_ALIGN_FAILED_MASK; published under
+    // GM_ALIGN_AMBIGUOUS and GM_ALIGN_AT_BORDER, which say how far to trust it).  scores, when given, receives the table of
+    // (2A + 1)(2B + 1) records.
+    gm_wall_align_info alignWallMap(const double pose[12], const gm_wall_align_params &prm,
+                                    std::vector<gm_wall_align_score> *scores = nullptr);
     // the changed points of the last checkWallMap grouped into objects on the device (gm_wall_map_check_objects on the slot
     // that check ran on), ascending by (label, sign); the check's result and the map are not changed, and the call may be
     // repeated with other parameters.  info, when given, receives the call's counts.

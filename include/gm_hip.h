@@ -899,6 +899,134 @@ gm_status gm_wall_map_get_locate(gm_wall_map *map, uint32_t slot, gm_wall_locate
 gm_status gm_wall_map_locate_points(gm_wall_map *map, const float *xyz, uint32_t n, const uint8_t *labels, const double pose[12],
                                     const gm_wall_locate_params *prm, gm_wall_locate_info *info, float *residual, int32_t *cell);
 
+/* ---- a frame's chainage and roll against the wall map (gm_wall_map_align_*) --------------------------------------------
+ * A locate leaves chainage and roll about the axis to the caller, because a smooth tube does not constrain them.  A
+ * surveyed wall is not smooth: joints, bolts, niches and rough rock are what the map's cell means hold.  An align bins the
+ * frame's own deviation image on a patch of cells around the sensor, slides it over the map's image in whole cells, takes
+ * the shift of least mean squared mismatch, refines it by a parabola per axis and returns the pose moved by it.  One
+ * station of chainage error makes a check compare every point with the wrong cell; the normal order per frame is
+ * locate -> align -> check -> add.  Everything from a point's residual e on is integer.
+ *   per align     host, fp64: gm_wall_map_add_frame's "per add" unchanged (the pose checks, j_f, o', a', u', v' rounded to
+ *                 fp32 once; reported in a gm_wall_add_info).  The gate is the align's own.  P = half_patch_stations,
+ *                 A = max_station_shift, B = max_sector_shift, C = (int64) rint(clip 2^20).
+ *   per point     the add's fp32 chain unchanged: e, jl = floor(t / ds) relative to the anchor, the sector k.  Classes,
+ *                 exactly one per valid point, decided in this order: plane (label 1); beyond_gate (|e| > gate, or e not
+ *                 finite); outside_patch (jl not in [-P, P)); binned (everything else).  The patch is anchored on j_f,
+ *                 not on the map's extent: a patch station outside [0, n_stations) is still binned and never overlaps.
+ *   patch         2P x n_sectors cells, row jr = jl + P.  A cell holds count (u32) and the sum of (int64) rint(e 2^20),
+ *                 the integer the add sums.  A patch cell is USABLE iff count >= min_frame_count; its value is
+ *                 f = sum / (int64) count by C integer division, toward zero (|f| <= 2^23: |e| <= gate <= 8).
+ *   map value     a map cell is USABLE iff count >= min_count; m = sum / (int64) count, the value of the regions, the
+ *                 check and the locate, saturated to [-2^30, 2^30] (a cell gm_wall_map_add_raw merged may hold any sum;
+ *                 beyond 2^30 the clamp below gives the same Dc either way).
+ *   score table   one record per shift (a, b), a in [-A, A] stations, b in [-B, B] sectors, at index
+ *                 (a + A)(2B + 1) + (b + B).  The sums run over the patch cells (jr, k) where f is usable,
+ *                 j = j_f - P + jr + a lies in [0, n_stations) and the map cell (j, (k + b) mod n_sectors) is usable (the
+ *                 modulus taken into [0, n_sectors)):  D = f - m, Dc = clamp(D, -C, C),
+ *                 ssd = sum Dc^2, sum_d = sum Dc, n = the cells summed.  C <= 2^23 and n <= 8192, so ssd < 2^60.  The
+ *                 table is a function of the patch and the raw map cells alone: not of the grid, the block shape
+ *                 (GM_WALL_ALIGN_ROWS) or the order blocks run in.
+ *   selection     host (gm_wall_align_select).  A shift is VALID iff n >= min_overlap.  best (a*, b*) has the smallest
+ *                 ssd / n, compared exactly by cross-multiplication in 128-bit integers; ties go to the smaller
+ *                 max(|a|, |b|), then to the smaller index.  Costs in fp64: c = (double) ssd / (double) n.  The subcell
+ *                 fraction, per axis: when both neighbours along the axis are in the table (no wrap) and valid and
+ *                 den = c- - 2 c0 + c+ > 0, delta = clamp(0.5 (c- - c+) / den, -0.5, 0.5); otherwise 0.  runner: the
+ *                 smallest cost among the valid shifts with max(|a - a*|, |b - b*|) > 1.  distinction = c_runner / c_best,
+ *                 +inf when c_best == 0 or there is no runner (rms_runner is then NaN).
+ *   results       shift_m = (a* + delta_a) ds;  roll = (b* + delta_b) (2 pi / n_sectors);  bias_m = sum_d 2^-20 / n of the
+ *                 best shift;  rms_best, rms_runner = sqrt(c) 2^-20;  overlap = the best shift's n.
+ *   status        GM_ALIGN_NO_OVERLAP: no valid shift (in GM_ALIGN_FAILED_MASK: every double of the info is NaN, the
+ *                 best shift 0).  GM_ALIGN_AMBIGUOUS: distinction < min_distinction -- the wall here does not tell the
+ *                 shifts apart (a smooth lining: about 1.01).  GM_ALIGN_AT_BORDER: |a*| == A > 0 or |b*| == B > 0 -- the
+ *                 true shift may lie outside the search.  The pose is still published under both flag bits.
+ *   pose          host, fp64.  A patch cell (j, k) that matches the map cell (j + a, k + b) means the frame really sits a
+ *                 stations further along and b sectors further round (phi grows from u toward v = a x u).  Q is the
+ *                 rotation by `roll` about the design axis a (Rodrigues' formula on the unrounded design frame):
+ *                 Rm' = Q Rm,  tr' = o + Q (tr - o) + shift_m a.  The pose passes the library's own pose check.
+ * The map is not changed.  Ordering as for a check and a locate: an align sees every add enqueued on any slot before it
+ * and none enqueued after it.  No floating-point atomics, no host round trip inside the align.  Scratch per (map, slot) --
+ * the patch, the two int32 value images, the table, a pinned copy of the result -- is allocated on first use, kept
+ * grow-only and freed with the map; a map that never aligns allocates nothing. */
+#define GM_WALL_ALIGN_MAX_PATCH_CELLS 8192u   /* 2P * n_sectors: the bin kernel's LDS table, 12 B per cell = 96 KiB */
+#define GM_WALL_ALIGN_MAX_SHIFT       64u     /* A and B */
+#define GM_WALL_ALIGN_MAX_SHIFTS      4096u   /* (2A + 1)(2B + 1) */
+#define GM_ALIGN_OK          0u
+#define GM_ALIGN_NO_OVERLAP  2u          /* no shift with n >= min_overlap */
+#define GM_ALIGN_FAILED_MASK 0xFFu       /* status & mask != 0: the pose is NaN */
+#define GM_ALIGN_AMBIGUOUS   (1u << 8)   /* distinction < min_distinction (the pose is still published) */
+#define GM_ALIGN_AT_BORDER   (1u << 9)   /* the best shift lies on the edge of the search (the pose is still published) */
+
+typedef struct gm_wall_align_params {   /* 56 bytes */
+    uint32_t struct_size;          /* = sizeof(gm_wall_align_params) */
+    uint32_t half_patch_stations;  /* P >= 1, 2P * n_sectors <= GM_WALL_ALIGN_MAX_PATCH_CELLS (default 20) */
+    uint32_t max_station_shift;    /* A in 0 .. 64 (default 8) */
+    uint32_t max_sector_shift;     /* B in 0 .. 64, 2B + 1 <= n_sectors (default 4); (2A + 1)(2B + 1) <= GM_WALL_ALIGN_MAX_SHIFTS */
+    uint32_t min_count;            /* >= 1 (default 8): points a map cell needs to be usable */
+    uint32_t min_frame_count;      /* >= 1 (default 4): points a patch cell needs to be usable */
+    uint32_t min_overlap;          /* >= 1 (default 64): cells a shift needs to be valid */
+    uint32_t reserved;             /* 0 */
+    double   gate;                 /* metres, in (0, 8] (default 0.25) */
+    double   clip;                 /* metres, in (0, 8] with rint(clip 2^20) >= 1 (default 0.05): the clamp of D */
+    double   min_distinction;      /* >= 1 and finite (default 1.5) */
+} gm_wall_align_params;
+
+typedef struct gm_wall_align_score {   /* 24 bytes */
+    uint64_t ssd;        /* sum Dc^2 */
+    int64_t  sum_d;      /* sum Dc */
+    uint32_t n;          /* cells summed */
+    uint32_t reserved;   /* 0 */
+} gm_wall_align_score;
+
+typedef struct gm_wall_align_info {   /* 224 bytes */
+    uint32_t struct_size;     /* = sizeof(gm_wall_align_info), filled by the library */
+    uint32_t status;          /* GM_ALIGN_* */
+    uint32_t n_points;        /* the valid cloud's points: the sum of the four classes */
+    uint32_t plane, beyond_gate, outside_patch, binned;
+    uint32_t patch_cells_usable;
+    int64_t  anchor_station;  /* j_f of the caller's pose */
+    uint32_t half_patch_stations, max_station_shift, max_sector_shift;   /* P, A, B as used */
+    uint32_t overlap;         /* the best shift's n */
+    int32_t  best_station, best_sector;       /* a*, b* */
+    double   frac_station, frac_sector;       /* delta_a, delta_b */
+    double   shift_m, roll, bias_m, rms_best, rms_runner, distinction;
+    double   pose[12];        /* the aligned pose, row-major 3x4 [Rm' | tr'], sensor -> map */
+} gm_wall_align_info;
+
+/* Host only: the defaults of the table above.  A NULL is ignored. */
+void gm_wall_align_default_params(gm_wall_align_params *p);
+/* Host only, no device, no map: GM_OK for parameters an align accepts on a map of n_sectors sectors; GM_ERR_INVALID_ARG for
+ * a NULL, a struct_size mismatch, n_sectors outside 1 .. GM_WALL_MAX_SECTORS or a parameter outside the limits above (a NaN
+ * included). */
+gm_status gm_wall_align_check_params(const gm_wall_align_params *p, uint32_t n_sectors);
+/* Host only, no device, no map: the selection and the pose of the rule above from a score table of
+ * (2A + 1)(2B + 1) records (n_scores must be that).  wall: the map's parameters (its design frame, station_length,
+ * n_sectors); prm NULL: the defaults.  Fills status, anchor_station, P, A, B, overlap, the best shift, the fractions, the
+ * six results and the pose; the class counts, n_points and patch_cells_usable are the device's and stay 0 here.
+ * GM_ERR_INVALID_ARG: a NULL, parameters either check refuses, a pose the library refuses, a wrong n_scores. */
+gm_status gm_wall_align_select(const gm_wall_params *wall, const gm_wall_align_params *prm, const double pose[12],
+                               const gm_wall_align_score *table, uint32_t n_scores, gm_wall_align_info *info);
+/* Aligns the valid cloud of the frame last submitted to `slot` of ctx against the map.  Enqueued on the slot's stream
+ * behind the frame's work; returns without waiting.  It reads the point count and the slot's final labels on the device,
+ * as the add, the check and the locate do; with GM_CFG_GRAPH it is plain launches after the graph.  Arguments, errors and
+ * readiness as for gm_wall_map_check_frame (prm NULL: the defaults; add_info may be NULL, its gate is the align's). */
+gm_status gm_wall_map_align_frame(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, const double pose[12],
+                                  const gm_wall_align_params *prm, gm_wall_add_info *add_info);
+/* The result of the last align enqueued on (map, slot).  Waits for that align only (an event recorded behind it, not the
+ * slot's stream).  *n_out (may be NULL) is the table's length (2A + 1)(2B + 1).  scores NULL with capacity 0 is a count
+ * query; otherwise capacity must hold the table (GM_ERR_CAPACITY).  info may be NULL.  GM_ERR_NOT_READY: no align was
+ * enqueued on (map, slot); GM_ERR_INVALID_ARG: NULL map, a bad slot, NULL scores with a capacity.  The result stays
+ * readable until the next align on that (map, slot) -- gm_wall_map_align_points counts as one on slot 0. */
+gm_status gm_wall_map_get_align(gm_wall_map *map, uint32_t slot, gm_wall_align_info *info, gm_wall_align_score *scores,
+                                uint32_t capacity, uint32_t *n_out);
+/* The same kernels as one blocking stage call on host buffers (slot 0 of the map's context; gm_wall_map_add_points'
+ * conventions).  The per-point outputs may each be NULL: residual (float[n]: e, NaN for plane points), cell (int32_t[n]:
+ * jr * n_sectors + k of a binned point, else -1).  Fed a slot's valid cloud and labels, it returns that slot's align bit
+ * for bit. */
+gm_status gm_wall_map_align_points(gm_wall_map *map, const float *xyz, uint32_t n, const uint8_t *labels, const double pose[12],
+                                   const gm_wall_align_params *prm, gm_wall_add_info *add_info, gm_wall_align_info *info,
+                                   gm_wall_align_score *scores, uint32_t capacity, uint32_t *n_out, float *residual,
+                                   int32_t *cell);
+
 /* ---- a check's changed points as objects (gm_wall_map_check_objects, gm_wall_check_objects) ---------------------------
  * The changed rows of a check grouped into a short list: "one object, 1.8 m long, between 20 and 44 degrees, 0.5 m inside
  * the profile, at these sensor coordinates".  The result is a function of the MULTISET of rows (gm_wall_check_point), the
