@@ -67,6 +67,9 @@ GM_WALL_OBJECT_MAX_BLOCKS = 1 << 20
 GM_WALL_OBJECT_TILE = (64, 64)   # block rows x block columns: the object labelling kernel's default tile
 
 GM_WALL_CHECK_MEAN, GM_WALL_CHECK_ENVELOPE = 0, 1
+GM_WALL_CLEAR_MIN, GM_WALL_CLEAR_MEAN = 0, 1
+GM_WALL_CLEAR_MAX_GAUGES = 256
+GM_WALL_GAUGE_MAX_VERTICES = 4096
 GM_WALL_LOCATE_DESIGN, GM_WALL_LOCATE_MAP = 0, 1
 GM_LOCATE_OK = 0
 GM_LOCATE_DEGENERATE = 2
@@ -200,6 +203,35 @@ class WallCloudInfo(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("station0", C.c_uint32), ("n_stations", C.c_uint32), ("n_sectors", C.c_uint32),
                 ("blocks_stations", C.c_uint32), ("blocks_sectors", C.c_uint32),
                 ("blocks", C.c_uint64), ("points", C.c_uint64), ("below_min_count", C.c_uint64), ("empty", C.c_uint64)]
+
+
+class WallClearanceParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reference", C.c_uint32), ("min_count", C.c_uint32), ("reserved", C.c_uint32),
+                ("margin", C.c_double)]
+
+
+class WallClearanceStation(C.Structure):
+    _fields_ = [("min_clearance", C.c_int64), ("min_sector", C.c_uint32), ("usable", C.c_uint32), ("tight", C.c_uint32),
+                ("infringed", C.c_uint32), ("unsurveyed", C.c_uint32), ("gauge", C.c_uint32)]
+
+
+class WallClearanceCell(C.Structure):
+    _fields_ = [("cell", C.c_uint32), ("count", C.c_uint32), ("clearance", C.c_int64)]
+
+
+class WallClearanceInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("station0", C.c_uint32), ("n_stations", C.c_uint32), ("n_sectors", C.c_uint32),
+                ("margin_q", C.c_int64), ("radius_q", C.c_int64), ("ungauged", C.c_uint64), ("empty", C.c_uint64),
+                ("unusable", C.c_uint64), ("infringed", C.c_uint64), ("tight", C.c_uint64), ("clear", C.c_uint64),
+                ("stations_tight", C.c_uint32), ("stations_infringed", C.c_uint32), ("min_clearance", C.c_int64),
+                ("min_cell", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class WallClearanceRun(C.Structure):
+    _fields_ = [("station_from", C.c_uint32), ("station_to", C.c_uint32), ("chainage_from", C.c_double),
+                ("chainage_to", C.c_double), ("min_clearance", C.c_int64), ("min_clearance_m", C.c_double),
+                ("min_station", C.c_uint32), ("min_sector", C.c_uint32), ("angle_deg", C.c_double), ("tight", C.c_uint64),
+                ("infringed", C.c_uint64)]
 
 
 class WallCheckParams(C.Structure):
@@ -350,6 +382,8 @@ def load():
     wregp, wrprmp, wrinfop, wrmetp = (C.POINTER(WallRegion), C.POINTER(WallRegionParams), C.POINTER(WallRegionsInfo),
                                       C.POINTER(WallRegionMetrics))
     wcprmp, wcptp, wcinfop = C.POINTER(WallCloudParams), C.POINTER(WallCloudPoint), C.POINTER(WallCloudInfo)
+    wgprmp, wgstp, wgcellp, wginfop, wgrunp = (C.POINTER(WallClearanceParams), C.POINTER(WallClearanceStation),
+                                               C.POINTER(WallClearanceCell), C.POINTER(WallClearanceInfo), C.POINTER(WallClearanceRun))
     wkprmp, wkptp, wkinfop = C.POINTER(WallCheckParams), C.POINTER(WallCheckPoint), C.POINTER(WallCheckInfo)
     wlprmp, wlinfop = C.POINTER(WallLocateParams), C.POINTER(WallLocateInfo)
     waprmp, wascp, wainfop = C.POINTER(WallAlignParams), C.POINTER(WallAlignScore), C.POINTER(WallAlignInfo)
@@ -419,6 +453,11 @@ def load():
         "gm_wall_cloud_default_params": (None, [wcprmp]),
         "gm_wall_cloud_directions": (C.c_int, [wprmp, wcprmp, dp, u32, u32p]),
         "gm_wall_map_cloud": (C.c_int, [vp, u32, u32, wcprmp, wcinfop, wcptp, u64, u64p]),
+        "gm_wall_clearance_default_params": (None, [wgprmp]),
+        "gm_wall_clearance_check_params": (C.c_int, [wprmp, wgprmp, i32p, u32, u8p, u32]),
+        "gm_wall_map_clearance": (C.c_int, [vp, u32, u32, i32p, u32, u8p, wgprmp, wginfop, wgstp, u32, wgcellp, u64, u64p]),
+        "gm_wall_gauge_from_polygon": (C.c_int, [wprmp, dp, u32, dp, i32p, u32, u32p]),
+        "gm_wall_clearance_runs": (C.c_int, [wprmp, wgstp, u32, u32, u32, wgrunp, u32, u32p]),
         "gm_wall_check_default_params": (None, [wkprmp]),
         "gm_wall_check_classify": (C.c_int, [wkprmp, wrawp, C.c_float, C.POINTER(C.c_int64), u32p]),
         "gm_wall_map_check_frame": (C.c_int, [vp, vp, u32, dp, wkprmp, waddp]),

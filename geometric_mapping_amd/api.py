@@ -644,6 +644,70 @@ def wall_region_metrics(prm, region):
     return {k: float(getattr(out, k)) for k in _REGION_METRICS}
 
 
+WALL_CLEARANCE_STATION = np.dtype([("min_clearance", "<i8"), ("min_sector", "<u4"), ("usable", "<u4"), ("tight", "<u4"),
+                                   ("infringed", "<u4"), ("unsurveyed", "<u4"), ("gauge", "<u4")])   # gm_wall_clearance_station, 32 bytes
+WALL_CLEARANCE_CELL = np.dtype([("cell", "<u4"), ("count", "<u4"), ("clearance", "<i8")])   # gm_wall_clearance_cell, 16 bytes
+WALL_CLEARANCE_RUN = np.dtype([("station_from", "<u4"), ("station_to", "<u4"), ("chainage_from", "<f8"), ("chainage_to", "<f8"),
+                               ("min_clearance", "<i8"), ("min_clearance_m", "<f8"), ("min_station", "<u4"), ("min_sector", "<u4"),
+                               ("angle_deg", "<f8"), ("tight", "<u8"), ("infringed", "<u8")])   # gm_wall_clearance_run, 72 bytes
+_CLEARANCE_INFO = ("station0", "n_stations", "n_sectors", "margin_q", "radius_q", "ungauged", "empty", "unusable", "infringed",
+                   "tight", "clear", "stations_tight", "stations_infringed", "min_clearance", "min_cell")
+
+
+def _wall_clearance_params(**kw):
+    p = _lib.WallClearanceParams()
+    _lib.load().gm_wall_clearance_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k in ("struct_size", "reserved"):
+            raise TypeError(f"unknown clearance parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def _gauge_tables(gauge_q, n_sectors):
+    g = np.ascontiguousarray(np.asarray(gauge_q, dtype=np.int32))
+    if g.ndim == 1:
+        g = g.reshape(1, -1)
+    if g.ndim != 2 or g.shape[1] != n_sectors or g.shape[0] < 1:
+        raise ValueError("gauge_q must be shaped (n_sectors,) or (n_gauges, n_sectors)")
+    return g
+
+
+def wall_gauge_from_polygon(prm, uv, offset=(0.0, 0.0)):
+    """gm_wall_gauge_from_polygon (host only): the int32 [n_sectors] gauge table (units of 2^-20 m) of the closed simple
+    polygon uv [n_vertices, 2] (along u, along v; metres about the design axis), shifted by `offset`, for a map with the
+    gm_wall_params `prm`."""
+    L = _lib.load()
+    p = np.ascontiguousarray(np.asarray(uv, dtype=np.float64).reshape(-1, 2))
+    off = np.ascontiguousarray(np.asarray(offset, dtype=np.float64).reshape(2))
+    out = np.zeros(int(prm.n_sectors), dtype=np.int32)
+    got = C.c_uint32(0)
+    st = L.gm_wall_gauge_from_polygon(C.byref(prm), p.ctypes.data_as(C.POINTER(C.c_double)), len(p),
+                                      off.ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(C.POINTER(C.c_int32)),
+                                      len(out), C.byref(got))
+    if st != _lib.GM_OK:
+        raise _lib.GmError(st, "gm_wall_gauge_from_polygon refused the polygon")
+    return out
+
+
+def wall_clearance_runs(prm, stations, station0=0, max_gap=0):
+    """gm_wall_clearance_runs (host only): the WALL_CLEARANCE_RUN records of the WALL_CLEARANCE_STATION records of a
+    window that starts at map station `station0`, flagged stations joined across at most `max_gap` quiet ones."""
+    L = _lib.load()
+    s = np.ascontiguousarray(np.asarray(stations, dtype=WALL_CLEARANCE_STATION).reshape(-1))
+    sp = s.ctypes.data_as(C.POINTER(_lib.WallClearanceStation)) if len(s) else None
+    got = C.c_uint32(0)
+    st = L.gm_wall_clearance_runs(C.byref(prm), sp, len(s), int(station0), int(max_gap), None, 0, C.byref(got))
+    if st != _lib.GM_OK:
+        raise _lib.GmError(st, "gm_wall_clearance_runs refused its arguments")
+    runs = np.zeros(max(int(got.value), 1), dtype=WALL_CLEARANCE_RUN)
+    st = L.gm_wall_clearance_runs(C.byref(prm), sp, len(s), int(station0), int(max_gap),
+                                  runs.ctypes.data_as(C.POINTER(_lib.WallClearanceRun)), len(runs), C.byref(got))
+    if st != _lib.GM_OK:
+        raise _lib.GmError(st, "gm_wall_clearance_runs failed")
+    return runs[:int(got.value)].copy()
+
+
 def _wall_cloud_params(**kw):
     p = _lib.WallCloudParams()
     _lib.load().gm_wall_cloud_default_params(C.byref(p))
@@ -869,6 +933,40 @@ class WallMap:
             self._ctx._check(self._L.gm_wall_map_cloud(self._h(), s0, n, C.byref(p), C.byref(info),
                                                        pts.ctypes.data_as(C.POINTER(_lib.WallCloudPoint)), cap, C.byref(got)))
         return {k: int(getattr(info, k)) for k in _CLOUD_INFO}, pts[:int(got.value)].copy()
+
+    @staticmethod
+    def clearance_params(**kw):
+        """gm_wall_clearance_params with the library's defaults, then the keywords (reference, min_count, margin)."""
+        return _wall_clearance_params(**kw)
+
+    def clearance(self, station0, n, gauge_q, station_gauge=None, **params):
+        """gm_wall_map_clearance: stations [station0, station0 + n) (n None: to the end) against the gauge table(s)
+        gauge_q, int32 (n_sectors,) or (n_gauges, n_sectors) in units of 2^-20 m; station_gauge (uint8 [n], optional)
+        picks the table of each window station.  Returns (info dict, WALL_CLEARANCE_STATION records, WALL_CLEARANCE_CELL
+        records ascending by cell).  A count query first, then the sized call."""
+        s0, n = self._window(station0, n)
+        p = self.clearance_params(**params)
+        g = _gauge_tables(gauge_q, self.n_sectors)
+        gp = g.ctypes.data_as(C.POINTER(C.c_int32))
+        sg = sgp = None
+        if station_gauge is not None:
+            sg = np.ascontiguousarray(np.asarray(station_gauge, dtype=np.uint8).reshape(-1))
+            if len(sg) != n:
+                raise ValueError("station_gauge must hold one entry per window station")
+            sgp = sg.ctypes.data_as(C.POINTER(C.c_uint8)) if n else None
+        info = _lib.WallClearanceInfo()
+        got = C.c_uint64(0)
+        self._ctx._check(self._L.gm_wall_map_clearance(self._h(), s0, n, gp, g.shape[0], sgp, C.byref(p), C.byref(info), None, 0,
+                                                       None, 0, C.byref(got)))
+        cap = int(got.value)
+        st = np.zeros(max(n, 1), dtype=WALL_CLEARANCE_STATION)
+        cells = np.zeros(max(cap, 1), dtype=WALL_CLEARANCE_CELL)
+        if n:
+            self._ctx._check(self._L.gm_wall_map_clearance(
+                self._h(), s0, n, gp, g.shape[0], sgp, C.byref(p), C.byref(info),
+                st.ctypes.data_as(C.POINTER(_lib.WallClearanceStation)), n,
+                cells.ctypes.data_as(C.POINTER(_lib.WallClearanceCell)), cap, C.byref(got)))
+        return {k: int(getattr(info, k)) for k in _CLEARANCE_INFO}, st[:n].copy(), cells[:int(got.value)].copy()
 
     @staticmethod
     def check_params(**kw):

@@ -467,6 +467,42 @@ void launch_wall_align_bin(const WallAlignArgs &a, uint32_t n_cap, hipStream_t s
 void launch_wall_align_values(const WallAlignArgs &a, hipStream_t s);   // behind the wait on the adds
 void launch_wall_align_score(const WallAlignArgs &a, hipStream_t s);
 uint32_t wall_align_default_rows(uint32_t n_sectors);
+// k_wall_clearance.hip (gm_wall_map_clearance): stations -> per chunk of whole stations compact + emit
+// u64 words 0 .. 5: the six classes (kWallClear* order); 6 stations_tight; 7 stations_infringed; 8 ~key of the least
+// clearance (0: none), key = (c + 2^34) << 24 | cell; 9 the chunk's list cells (low word); 10, 11 pad
+constexpr int kWallClearCounters = 12;
+constexpr uint32_t kWallClearUngauged = 0u, kWallClearEmpty = 1u, kWallClearUnusable = 2u, kWallClearInfringed = 3u,
+                   kWallClearTight = 4u, kWallClearClear = 5u;
+constexpr long long kWallClearBias = 1ll << 34;   // |c| < 2^34: R_q <= 2^32, |w| <= 2^31, 0 <= G < 2^31
+struct WallClearArgs {
+    WallTable map;
+    uint64_t first;            // station0 * nsec: map-wide index of window cell 0
+    uint32_t n, nsec;          // the window's stations, the map's sectors
+    uint32_t reference, min_count;
+    long long T, Rq;
+    const int32_t *gauge;      // [n_gauges][nsec]
+    const uint8_t *station_gauge;   // [n], nullptr: table 0
+    gm_wall_clearance_station *stations;   // [n]
+    unsigned long long *ctr;   // [kWallClearCounters], zeroed by the caller on the same stream
+    uint32_t j0, nj;           // the list's chunk: window stations [j0, j0 + nj)
+    gm_wall_clearance_cell *out;   // the chunk's staging
+};
+void launch_wall_clear_stations(const WallClearArgs &a, hipStream_t s);
+void launch_wall_clear_list(const WallClearArgs &a, const ScanState &st, hipStream_t s);
+// the rule's integers, shared by the kernels and the host
+__host__ __device__ inline long long wall_clear_value(uint32_t reference, long long sum, uint32_t count, uint32_t lo)   // count >= 1
+{
+    if (reference == GM_WALL_CLEAR_MEAN) {
+        const long long q = sum / (long long)count;
+        return q > kWallAlignSat ? (long long)kWallAlignSat : (q < -kWallAlignSat ? -(long long)kWallAlignSat : q);
+    }
+    return wall_check_fix(ordered_to_float(~lo));
+}
+// the class of a usable gauged cell of clearance c
+__host__ __device__ inline uint32_t wall_clear_class(long long c, long long T)
+{
+    return c < 0 ? kWallClearInfringed : (c < T ? kWallClearTight : kWallClearClear);
+}
 // k_wall_objects.hip (gm_wall_map_check_objects, gm_wall_check_objects): bin -> tiles -> seams -> flatten | blocks ->
 // reduce -> select | rows
 constexpr uint32_t kWallObjectTileBlocks = 4096;      // the most window blocks of a tile (its LDS tables)

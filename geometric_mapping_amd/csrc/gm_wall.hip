@@ -134,6 +134,14 @@ struct gm_wall_map {
     DevArray<unsigned long long> cl_ctr;      // [kWallCloudCounters]
     DevArray<double> cl_dirs;      // [GM_WALL_MAX_SECTORS][2]
     std::vector<double> cl_dirs_host;          // the table of the call in progress
+    // gm_wall_map_clearance: the chunk (GM_WALL_CLEAR_CHUNK: tests, measurements; 0: kStageCells cells) and the scratch
+    uint32_t clear_chunk = 0;
+    DevArray<int32_t> cr_gauge;    // the uploaded tables [n_gauges][n_sectors]
+    DevArray<uint8_t> cr_station_gauge;        // [n]
+    DevArray<gm_wall_clearance_station> cr_stations;   // [n]
+    DevArray<gm_wall_clearance_cell> cr_stage; // a chunk's list rows
+    ScanRecords cr_scan;           // the list's own chained scan
+    DevArray<unsigned long long> cr_ctr;       // [kWallClearCounters]
     // gm_wall_map_check_*
     std::vector<WallCheckSlot> checks;         // per slot of ctx
     // gm_wall_map_locate_*
@@ -496,6 +504,83 @@ void cloud_directions(uint32_t nsec, uint32_t bk, double *cos_sin)
         cos_sin[2 * K] = cos(phi);
         cos_sin[2 * K + 1] = sin(phi);
     }
+}
+
+// ---- gm_wall_map_clearance ----
+
+// gm_wall_clearance_check_params' rule; T and R_q of an accepted call
+bool clearance_ok(const gm_wall_params *p, const gm_wall_clearance_params &c, const int32_t *gauge_q, uint32_t n_gauges,
+                  const uint8_t *station_gauge, uint32_t n, long long &T, long long &Rq)
+{
+    T = 0; Rq = 0;
+    if (!p || !gauge_q || p->struct_size != sizeof(gm_wall_params) || p->n_sectors < 1u || p->n_sectors > GM_WALL_MAX_SECTORS) return false;
+    if (c.struct_size != sizeof(gm_wall_clearance_params) || c.reference > (uint32_t)GM_WALL_CLEAR_MEAN || c.min_count < 1u) return false;
+    if (!(c.margin >= 0.0) || !(c.margin <= 8.0)) return false;
+    if (!(p->radius > 0.0) || !isfinite(p->radius)) return false;
+    const double rq = rint(p->radius * 1048576.0);
+    if (!(rq <= 4294967296.0)) return false;
+    if (n_gauges < 1u || n_gauges > GM_WALL_CLEAR_MAX_GAUGES) return false;
+    const size_t entries = (size_t)n_gauges * p->n_sectors;
+    for (size_t i = 0; i < entries; ++i)
+        if (gauge_q[i] < 0) return false;
+    if (station_gauge)
+        for (uint32_t j = 0; j < n; ++j)
+            if (station_gauge[j] >= n_gauges) return false;
+    T = (long long)rint(c.margin * 1048576.0);
+    Rq = (long long)rq;
+    return true;
+}
+
+double cross2(const double a[2], const double b[2]) { return a[0] * b[1] - a[1] * b[0]; }
+
+// 1 when the closed segments ab and cd share a point
+bool segments_meet(const double a[2], const double b[2], const double c[2], const double d[2])
+{
+    const double ab[2] = {b[0] - a[0], b[1] - a[1]}, cd[2] = {d[0] - c[0], d[1] - c[1]};
+    const double ac[2] = {c[0] - a[0], c[1] - a[1]}, ad[2] = {d[0] - a[0], d[1] - a[1]};
+    const double ca[2] = {a[0] - c[0], a[1] - c[1]}, cb[2] = {b[0] - c[0], b[1] - c[1]};
+    const double o1 = cross2(ab, ac), o2 = cross2(ab, ad), o3 = cross2(cd, ca), o4 = cross2(cd, cb);
+    if (((o1 > 0.0 && o2 < 0.0) || (o1 < 0.0 && o2 > 0.0)) && ((o3 > 0.0 && o4 < 0.0) || (o3 < 0.0 && o4 > 0.0))) return true;
+    auto on = [](const double p[2], const double q[2], const double r[2]) {   // r collinear with pq: inside its box?
+        return std::min(p[0], q[0]) <= r[0] && r[0] <= std::max(p[0], q[0]) && std::min(p[1], q[1]) <= r[1] && r[1] <= std::max(p[1], q[1]);
+    };
+    return (o1 == 0.0 && on(a, b, c)) || (o2 == 0.0 && on(a, b, d)) || (o3 == 0.0 && on(c, d, a)) || (o4 == 0.0 && on(c, d, b));
+}
+
+// the polygon of gm_wall_gauge_from_polygon is accepted: finite, no edge of length 0, simple, the axis strictly inside
+bool gauge_polygon_ok(const std::vector<double> &P, uint32_t nv)
+{
+    for (uint32_t i = 0; i < 2u * nv; ++i)
+        if (!isfinite(P[i])) return false;
+    const double zero[2] = {0.0, 0.0};
+    int wn = 0;
+    for (uint32_t i = 0; i < nv; ++i) {
+        const double *a = &P[2 * i], *b = &P[2 * ((i + 1u) % nv)];
+        if (a[0] == b[0] && a[1] == b[1]) return false;
+        const double left = cross2(a, b);   // > 0: the axis lies to the left of a -> b
+        if (left == 0.0 && segments_meet(a, b, zero, zero)) return false;   // the axis on the boundary
+        if (a[1] <= 0.0) {
+            if (b[1] > 0.0 && left > 0.0) ++wn;
+        } else if (b[1] <= 0.0 && left < 0.0) {
+            --wn;
+        }
+    }
+    if (wn == 0) return false;
+    for (uint32_t i = 0; i < nv; ++i) {
+        const double *a = &P[2 * i], *b = &P[2 * ((i + 1u) % nv)];
+        for (uint32_t j = i + 1u; j < nv; ++j) {
+            const double *c = &P[2 * j], *d = &P[2 * ((j + 1u) % nv)];
+            const bool next = j == i + 1u, prev = i == 0u && j == nv - 1u;
+            if (next || prev) {   // neighbours share one vertex; they may not fold back onto each other
+                const double *s = next ? b : a, *x = next ? a : b, *y = next ? d : c;   // s shared; x, y the far ends
+                const double e[2] = {x[0] - s[0], x[1] - s[1]}, f[2] = {y[0] - s[0], y[1] - s[1]};
+                if (cross2(e, f) == 0.0 && e[0] * f[0] + e[1] * f[1] > 0.0) return false;
+            } else if (segments_meet(a, b, c, d)) {
+                return false;
+            }
+        }
+    }
+    return true;
 }
 
 // ---- gm_wall_map_check_* ----
@@ -1114,6 +1199,10 @@ gm_status gm_wall_map_create(gm_ctx *ctx, const gm_wall_params *params, gm_wall_
         const unsigned long long v = strtoull(e, nullptr, 10);
         m->cloud_chunk = v < kStageCells ? (uint32_t)v : 0u;
     }
+    if (const char *e = getenv("GM_WALL_CLEAR_CHUNK")) {   // cells; 0 or more than the default: the default (scratch is sized by it)
+        const unsigned long long v = strtoull(e, nullptr, 10);
+        m->clear_chunk = v < kStageCells ? (uint32_t)v : 0u;
+    }
     design_frame(m);
     auto body = [&]() -> gm_status {
         GMW_HIP(ctx, hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
@@ -1539,6 +1628,235 @@ gm_status gm_wall_map_cloud(gm_wall_map *map, uint32_t station0, uint32_t n, con
     info->below_min_count = ctr[1];
     if (n_out) *n_out = total;
     if (points && total > capacity) return gm_fail(ctx, GM_ERR_CAPACITY, "gm_wall_map_cloud: point buffer too small");
+    return GM_OK;
+}
+
+void gm_wall_clearance_default_params(gm_wall_clearance_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(gm_wall_clearance_params);
+    p->reference = GM_WALL_CLEAR_MIN;
+    p->min_count = 8;
+    p->margin = 0.10;
+}
+
+gm_status gm_wall_clearance_check_params(const gm_wall_params *p, const gm_wall_clearance_params *c, const int32_t *gauge_q,
+                                         uint32_t n_gauges, const uint8_t *station_gauge, uint32_t n)
+{
+    long long T, Rq;
+    const gm_wall_clearance_params cp = params_or(c, gm_wall_clearance_default_params);
+    return clearance_ok(p, cp, gauge_q, n_gauges, station_gauge, n, T, Rq) ? GM_OK : GM_ERR_INVALID_ARG;
+}
+
+gm_status gm_wall_map_clearance(gm_wall_map *map, uint32_t station0, uint32_t n, const int32_t *gauge_q, uint32_t n_gauges,
+                                const uint8_t *station_gauge, const gm_wall_clearance_params *prm, gm_wall_clearance_info *info,
+                                gm_wall_clearance_station *stations, uint32_t station_capacity, gm_wall_clearance_cell *cells,
+                                uint64_t cell_capacity, uint64_t *n_out)
+{
+    if (!map) return GM_ERR_INVALID_ARG;
+    gm_ctx *ctx = map->ctx;
+    if (n_out) *n_out = 0;
+    if (!info) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_clearance: NULL info");
+    const gm_wall_clearance_params cp = params_or(prm, gm_wall_clearance_default_params);
+    if ((uint64_t)station0 + n > map->prm.n_stations)   // (before the tables: station_gauge has n entries)
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: the window leaves [0, n_stations]");
+    long long T, Rq;
+    if (!clearance_ok(&map->prm, cp, gauge_q, n_gauges, station_gauge, n, T, Rq))
+        return gm_fail(ctx, GM_ERR_INVALID_ARG,
+                       "gm_wall_map_clearance: struct_size mismatch, a parameter outside its limits, a bad gauge table or a radius above 4096 m");
+    if ((!stations && station_capacity) || (!cells && cell_capacity))
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_clearance: NULL stations or cells with a capacity");
+    GMW_OK(sync_map(map));
+    const uint32_t nsec = map->prm.n_sectors;
+    memset(info, 0, sizeof(*info));
+    info->struct_size = (uint32_t)sizeof(gm_wall_clearance_info);
+    info->station0 = station0;
+    info->n_stations = n;
+    info->n_sectors = nsec;
+    info->margin_q = T;
+    info->radius_q = Rq;
+    info->min_clearance = INT64_MAX;
+    info->min_cell = UINT32_MAX;
+    if (!n) return GM_OK;
+
+    // chunks of whole stations
+    const uint64_t chunk = map->clear_chunk ? map->clear_chunk : kStageCells;
+    const uint32_t rows = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(chunk / nsec, 1u), n);
+    const uint64_t cc = (uint64_t)rows * nsec;   // cells of a full chunk, <= 2^20
+    const size_t entries = (size_t)n_gauges * nsec;
+    GMW_HIP(ctx, map->cr_gauge.reserve(entries));
+    if (station_gauge) GMW_HIP(ctx, map->cr_station_gauge.reserve(n));
+    GMW_HIP(ctx, map->cr_stations.reserve(n));
+    GMW_HIP(ctx, map->cr_ctr.reserve(kWallClearCounters));
+    GMW_HIP(ctx, hipMemcpyAsync(map->cr_gauge.p, gauge_q, entries * sizeof(int32_t), hipMemcpyHostToDevice, map->stream));
+    if (station_gauge) GMW_HIP(ctx, hipMemcpyAsync(map->cr_station_gauge.p, station_gauge, n, hipMemcpyHostToDevice, map->stream));
+    GMW_HIP(ctx, hipMemsetAsync(map->cr_ctr.p, 0, kWallClearCounters * 8, map->stream));
+
+    WallClearArgs a;
+    memset(&a, 0, sizeof(a));
+    a.map = map->table;
+    a.first = (uint64_t)station0 * nsec;
+    a.n = n; a.nsec = nsec;
+    a.reference = cp.reference;
+    a.min_count = cp.min_count;
+    a.T = T; a.Rq = Rq;
+    a.gauge = map->cr_gauge.p;
+    a.station_gauge = station_gauge ? map->cr_station_gauge.p : nullptr;
+    a.stations = map->cr_stations.p;
+    a.ctr = map->cr_ctr.p;
+
+    unsigned long long ctr[kWallClearCounters];
+    launch_wall_clear_stations(a, map->stream);
+    GMW_HIP(ctx, hipGetLastError());
+    GMW_HIP(ctx, hipMemcpyAsync(ctr, a.ctr, sizeof(ctr), hipMemcpyDeviceToHost, map->stream));
+    GMW_HIP(ctx, hipStreamSynchronize(map->stream));   // (the tables have left the caller's buffers, too)
+    info->ungauged = ctr[kWallClearUngauged];
+    info->empty = ctr[kWallClearEmpty];
+    info->unusable = ctr[kWallClearUnusable];
+    info->infringed = ctr[kWallClearInfringed];
+    info->tight = ctr[kWallClearTight];
+    info->clear = ctr[kWallClearClear];
+    info->stations_tight = (uint32_t)ctr[6];
+    info->stations_infringed = (uint32_t)ctr[7];
+    if (ctr[8]) {
+        const unsigned long long key = ~ctr[8];
+        info->min_clearance = (long long)(key >> 24) - kWallClearBias;
+        info->min_cell = (uint32_t)(key & 0xFFFFFFull);
+    }
+    const uint64_t total = info->tight + info->infringed;
+    if (n_out) *n_out = total;
+    if ((stations && station_capacity < n) || (cells && total > cell_capacity))
+        return gm_fail(ctx, GM_ERR_CAPACITY, "gm_wall_map_clearance: station or cell buffer too small");
+    if (stations) {
+        GMW_HIP(ctx, hipMemcpyAsync(stations, a.stations, (size_t)n * sizeof(gm_wall_clearance_station), hipMemcpyDeviceToHost, map->stream));
+        GMW_HIP(ctx, hipStreamSynchronize(map->stream));
+    }
+    if (!cells || !total) return GM_OK;
+
+    GMW_HIP(ctx, map->cr_stage.reserve(cc));
+    GMW_OK(map->cr_scan.reserve(ctx, (uint32_t)cc, map->stream));   // (nothing of the map's is in flight: the call synchronised above)
+    a.out = map->cr_stage.p;
+    uint64_t done = 0;
+    for (uint32_t j0 = 0; j0 < n; j0 += rows) {   // (the trip count depends on the window alone)
+        a.j0 = j0;
+        a.nj = std::min(rows, n - j0);
+        launch_wall_clear_list(a, map->cr_scan.next(map->stream), map->stream);
+        GMW_HIP(ctx, hipGetLastError());
+        GMW_HIP(ctx, hipMemcpyAsync(&ctr[9], a.ctr + 9, 8, hipMemcpyDeviceToHost, map->stream));
+        GMW_HIP(ctx, hipStreamSynchronize(map->stream));
+        const uint64_t got = (uint32_t)ctr[9];
+        if (done + got > total) return gm_fail(ctx, GM_ERR_DEVICE, "gm_wall_map_clearance: the list disagrees with the totals");
+        if (got) {
+            GMW_HIP(ctx, hipMemcpyAsync(cells + done, a.out, got * sizeof(gm_wall_clearance_cell), hipMemcpyDeviceToHost, map->stream));
+            GMW_HIP(ctx, hipStreamSynchronize(map->stream));
+        }
+        done += got;
+    }
+    if (done != total) return gm_fail(ctx, GM_ERR_DEVICE, "gm_wall_map_clearance: the list disagrees with the totals");
+    return GM_OK;
+}
+
+gm_status gm_wall_gauge_from_polygon(const gm_wall_params *p, const double *uv, uint32_t n_vertices, const double offset[2],
+                                     int32_t *gauge_q, uint32_t capacity, uint32_t *n_out)
+{
+    if (n_out) *n_out = 0;
+    if (!p || !uv || p->struct_size != sizeof(gm_wall_params) || p->n_sectors < 1u || p->n_sectors > GM_WALL_MAX_SECTORS) return GM_ERR_INVALID_ARG;
+    if (n_vertices < 3u || n_vertices > GM_WALL_GAUGE_MAX_VERTICES || (!gauge_q && capacity)) return GM_ERR_INVALID_ARG;
+    if (offset && (!isfinite(offset[0]) || !isfinite(offset[1]))) return GM_ERR_INVALID_ARG;
+    const uint32_t ns = p->n_sectors, nv = n_vertices;
+    std::vector<double> P(2 * (size_t)nv);
+    for (uint32_t i = 0; i < nv; ++i) {
+        P[2 * i] = uv[2 * i] + (offset ? offset[0] : 0.0);
+        P[2 * i + 1] = uv[2 * i + 1] + (offset ? offset[1] : 0.0);
+    }
+    if (!gauge_polygon_ok(P, nv)) return GM_ERR_INVALID_ARG;
+    const double two_pi = 6.283185307179586476925286766559;
+    std::vector<double> dirs(2 * (size_t)ns + 2), r(nv);
+    for (uint32_t k = 0; k < ns; ++k) {
+        const double f = (double)k / (double)ns;
+        const double phi = two_pi * f;
+        dirs[2 * k] = cos(phi);
+        dirs[2 * k + 1] = sin(phi);
+    }
+    dirs[2 * ns] = dirs[0]; dirs[2 * ns + 1] = dirs[1];   // the last ray is the first
+    for (uint32_t i = 0; i < nv; ++i) r[i] = sqrt(P[2 * i] * P[2 * i] + P[2 * i + 1] * P[2 * i + 1]);
+    // where the ray of every sector start leaves the polygon at the farthest: the largest t >= 0 over the edges it meets
+    std::vector<double> ray(ns, -1.0);
+    for (uint32_t k = 0; k < ns; ++k) {
+        const double *d = &dirs[2 * k];
+        for (uint32_t i = 0; i < nv; ++i) {
+            const double *a = &P[2 * i], *b = &P[2 * ((i + 1u) % nv)];
+            const double e[2] = {b[0] - a[0], b[1] - a[1]};
+            const double den = cross2(e, d);
+            if (den == 0.0) continue;   // parallel: its ends are vertices of the wedge
+            const double s = -cross2(a, d) / den;
+            if (!(s >= 0.0) || !(s <= 1.0)) continue;
+            const double x[2] = {a[0] + s * e[0], a[1] + s * e[1]};
+            const double t = x[0] * d[0] + x[1] * d[1];
+            if (t >= 0.0 && t > ray[k]) ray[k] = t;
+        }
+    }
+    std::vector<int32_t> out(ns);
+    for (uint32_t k = 0; k < ns; ++k) {
+        const double *d0 = &dirs[2 * k], *d1 = &dirs[2 * k + 2];
+        double g = std::max(ray[k], ray[(k + 1u) % ns]);
+        for (uint32_t i = 0; i < nv; ++i) {
+            const double *v = &P[2 * i];
+            if (ns == 1u || (cross2(d0, v) >= 0.0 && cross2(v, d1) >= 0.0)) g = std::max(g, r[i]);
+        }
+        const double q = ceil(g * 1048576.0);
+        if (!(g > 0.0) || !(q < 2147483648.0)) return GM_ERR_INVALID_ARG;
+        out[k] = (int32_t)q;
+    }
+    if (n_out) *n_out = ns;
+    if (capacity < ns) return GM_ERR_CAPACITY;
+    memcpy(gauge_q, out.data(), (size_t)ns * sizeof(int32_t));
+    return GM_OK;
+}
+
+gm_status gm_wall_clearance_runs(const gm_wall_params *p, const gm_wall_clearance_station *stations, uint32_t n,
+                                 uint32_t station0, uint32_t max_gap, gm_wall_clearance_run *runs, uint32_t capacity,
+                                 uint32_t *n_out)
+{
+    if (n_out) *n_out = 0;
+    if (!p || p->struct_size != sizeof(gm_wall_params) || p->n_sectors < 1u || (!stations && n) || (!runs && capacity) ||
+        (uint64_t)station0 + n > 4294967296ull)
+        return GM_ERR_INVALID_ARG;
+    auto flagged = [&](uint32_t i) { return stations[i].tight + stations[i].infringed > 0u; };
+    std::vector<gm_wall_clearance_run> out;
+    for (uint32_t i = 0; i < n;) {
+        if (!flagged(i)) { ++i; continue; }
+        uint32_t last = i;
+        for (uint32_t j = i + 1u; j < n && (uint64_t)j - last <= (uint64_t)max_gap + 1u; ++j)
+            if (flagged(j)) last = j;
+        gm_wall_clearance_run r;
+        memset(&r, 0, sizeof(r));
+        r.station_from = station0 + i;
+        r.station_to = station0 + last;
+        uint32_t at = i;
+        for (uint32_t j = i; j <= last; ++j) {
+            if (stations[j].min_clearance < stations[at].min_clearance) at = j;
+            r.tight += stations[j].tight;
+            r.infringed += stations[j].infringed;
+        }
+        // one operation per statement: the same roundings as the twin's, whatever the compiler may contract
+        const double from = (double)r.station_from * p->station_length;
+        const double to = ((double)r.station_to + 1.0) * p->station_length;
+        r.chainage_from = p->t_min + from;
+        r.chainage_to = p->t_min + to;
+        r.min_clearance = stations[at].min_clearance;
+        r.min_clearance_m = (double)r.min_clearance * 0x1p-20;
+        r.min_station = station0 + at;
+        r.min_sector = stations[at].min_sector;
+        const double num = 360.0 * ((double)r.min_sector * 2.0 + 1.0);
+        r.angle_deg = num / ((double)p->n_sectors * 2.0);
+        out.push_back(r);
+        i = last + 1u;
+    }
+    if (n_out) *n_out = (uint32_t)out.size();
+    if (runs && capacity < out.size()) return GM_ERR_CAPACITY;
+    if (runs && !out.empty()) memcpy(runs, out.data(), out.size() * sizeof(gm_wall_clearance_run));
     return GM_OK;
 }
 

@@ -422,6 +422,40 @@ std::vector<gm_wall_cloud_point> Processor::wallMapCloud(unsigned station0, unsi
     return points;
 }
 
+gm_wall_clearance_info Processor::wallMapClearance(unsigned station0, unsigned n, const std::vector<int32_t> &gauge_q,
+                                                   const std::vector<uint8_t> &station_gauge, const gm_wall_clearance_params &prm,
+                                                   std::vector<gm_wall_clearance_station> &stations,
+                                                   std::vector<gm_wall_clearance_cell> &cells)
+{
+    if (!wall_) throw Error(GM_ERR_NOT_READY, "wallMapClearance: createWallMap first");
+    gm_wall_info wi;
+    check(gm_wall_map_info(wall_, &wi), "wallMapClearance");
+    if (gauge_q.empty() || gauge_q.size() % wi.n_sectors) throw Error(GM_ERR_INVALID_ARG, "wallMapClearance: gauge_q is not whole tables of n_sectors entries");
+    if (!station_gauge.empty() && station_gauge.size() != n) throw Error(GM_ERR_INVALID_ARG, "wallMapClearance: station_gauge needs one entry per window station");
+    const unsigned n_gauges = (unsigned)(gauge_q.size() / wi.n_sectors);
+    const uint8_t *sg = station_gauge.empty() ? 0 : &station_gauge[0];
+    gm_wall_clearance_info info;
+    uint64_t count = 0;
+    check(gm_wall_map_clearance(wall_, station0, n, &gauge_q[0], n_gauges, sg, &prm, &info, 0, 0, 0, 0, &count), "wallMapClearance");
+    stations.resize(n);
+    cells.resize((size_t)count);
+    if (n)
+        check(gm_wall_map_clearance(wall_, station0, n, &gauge_q[0], n_gauges, sg, &prm, &info, &stations[0], n,
+                                    count ? &cells[0] : 0, count, &count), "wallMapClearance");
+    return info;
+}
+
+std::vector<int32_t> Processor::wallGaugeFromPolygon(const gm_wall_params &params, const std::vector<double> &uv, const double offset[2])
+{
+    if (uv.empty() || uv.size() % 2) throw Error(GM_ERR_INVALID_ARG, "wallGaugeFromPolygon: uv holds (u, v) pairs");
+    std::vector<int32_t> gauge(params.n_sectors ? params.n_sectors : 1);
+    uint32_t got = 0;
+    gm_status s = gm_wall_gauge_from_polygon(&params, &uv[0], (unsigned)(uv.size() / 2), offset, &gauge[0], (unsigned)gauge.size(), &got);
+    if (s != GM_OK) throw Error(s, "wallGaugeFromPolygon: the polygon or the parameters were refused");
+    gauge.resize(got);
+    return gauge;
+}
+
 std::vector<gm_wall_check_point> Processor::checkWallMap(const double pose[12], const gm_wall_check_params &prm, gm_wall_check_info *info)
 {
     if (!wall_) throw Error(GM_ERR_NOT_READY, "checkWallMap: createWallMap first");

@@ -150,6 +150,18 @@ public:
     // stations [station0, station0 + n) as a point list (gm_wall_map_cloud): one record per block of cells that holds
     // prm.min_count points, ascending by block; info, when given, receives the call's counts
     std::vector<gm_wall_cloud_point> wallMapCloud(unsigned station0, unsigned n, const gm_wall_cloud_params &prm, gm_wall_cloud_info *info = nullptr);
+    // stations [station0, station0 + n) against a structure gauge (gm_wall_map_clearance): gauge_q holds whole tables of
+    // n_sectors entries (2^-20 m, 0 = not gauged), station_gauge one table index per window station (empty: table 0
+    // everywhere).  stations receives one record per station, cells the tight and the infringed cells ascending by
+    // cell; the map is not changed.  A call for the end of a drive or for one window, not for every frame.
+    gm_wall_clearance_info wallMapClearance(unsigned station0, unsigned n, const std::vector<int32_t> &gauge_q,
+                                            const std::vector<uint8_t> &station_gauge, const gm_wall_clearance_params &prm,
+                                            std::vector<gm_wall_clearance_station> &stations,
+                                            std::vector<gm_wall_clearance_cell> &cells);
+    // one gauge table from a closed simple polygon uv = (u0, v0, u1, v1, ...) in the section plane, metres about the
+    // design axis, shifted by offset (may be null): gm_wall_gauge_from_polygon, host only
+    static std::vector<int32_t> wallGaugeFromPolygon(const gm_wall_params &params, const std::vector<double> &uv,
+                                                     const double offset[2] = 0);
     // the changed points of the newest frame (as addToWallMap takes it) against the map under pose (gm_wall_map_check_frame +
     // gm_wall_map_get_check), ascending by index; the map is not changed.  info, when given, receives the call's counts.
     // Check, then addToWallMap: against what was there, then contribute.

@@ -705,6 +705,137 @@ gm_status gm_wall_cloud_directions(const gm_wall_params *p, const gm_wall_cloud_
 gm_status gm_wall_map_cloud(gm_wall_map *map, uint32_t station0, uint32_t n, const gm_wall_cloud_params *prm,
                             gm_wall_cloud_info *info, gm_wall_cloud_point *points, uint64_t capacity, uint64_t *n_out);
 
+/* ---- the surveyed wall against a structure gauge (gm_wall_map_clearance) ---------------------------------------------
+ * Does the vehicle, train or equipment envelope fit, with how much room, and where does it not: every cell of a window
+ * of stations against a caller-supplied GAUGE, the radius about the design axis that the envelope needs in each sector.
+ * Everything on the device is integer, so the result is a function of the raw cells, the tables and the parameters
+ * alone; only the station records, the list of cells short of the margin and the totals leave the device.
+ *   gauge       int32 gauge_q[n_gauges][n_sectors], units of 2^-20 m, 1 <= n_gauges <= GM_WALL_CLEAR_MAX_GAUGES.
+ *               gauge_q[g][k] == 0: sector k is NOT GAUGED (the invert under the track); a negative entry is refused.
+ *               station_gauge (may be NULL: table 0 everywhere) holds one uint8 per WINDOW station, the table of that
+ *               station: the envelope moves with track offset and cant along the drive.  An entry >= n_gauges is refused.
+ *   integers    R_q = (int64) rint(radius 2^20) and T = (int64) rint(margin 2^20), fp64, once on the host; margin in
+ *               [0, 8]; a map with R_q > 2^32 (a radius above 4096 m) is refused.
+ *   wall value  a cell is USABLE iff count >= min_count.  GM_WALL_CLEAR_MEAN: w = sum / (int64) count by C integer
+ *               division (toward zero), the value of the regions, the check, the locate and the align, saturated at
+ *               +-2^30 as the align's.  GM_WALL_CLEAR_MIN (the default, conservative): w = fix(ordered^-1(~min_key)),
+ *               the innermost surveyed point, with fix(e) = (int64) rint(e 2^20) on the fp32 product, saturating at
+ *               the int32 range and 0 for a NaN, as in the check.
+ *   clearance   c = R_q + w - G[k] in int64 (|c| < 2^34).
+ *   classes     every window cell is in exactly one, decided in this order: UNGAUGED (G[k] == 0), EMPTY (count 0),
+ *               UNUSABLE (0 < count < min_count), INFRINGED (c < 0), TIGHT (0 <= c < T), CLEAR.
+ *   station     one record per window station: the least c over its usable gauged cells with the smallest sector
+ *               among equals (INT64_MAX and UINT32_MAX when there is none), the counts usable = infringed + tight +
+ *               clear, tight, infringed, unsurveyed = empty + unusable among the gauged sectors, and the table used.
+ *   list        the tight and the infringed cells, ascending by the map-wide cell index j n_sectors + k.
+ *   totals      the six classes (they sum to n n_sectors), the stations with tight + infringed > 0 and with
+ *               infringed > 0, and the least c of the window with the smallest cell among equals (INT64_MAX and
+ *               UINT32_MAX when there is none).
+ * On the device: one pass of one wave per station row for the records and the totals, then, when the list is asked
+ * for, one chained-scan compaction per chunk of whole stations of at most 2^20 cells (environment
+ * GM_WALL_CLEAR_CHUNK=<cells>, rounded down to whole stations, at least one, a value above 2^20 meaning 2^20, read at
+ * gm_wall_map_create: tests and measurements).  The result does not depend on the chunk, the grid or the order blocks
+ * run in. */
+#define GM_WALL_CLEAR_MIN  0u          /* against the innermost surveyed point of each cell */
+#define GM_WALL_CLEAR_MEAN 1u          /* against each cell's integer mean */
+#define GM_WALL_CLEAR_MAX_GAUGES   256u
+#define GM_WALL_GAUGE_MAX_VERTICES 4096u
+
+typedef struct gm_wall_clearance_params {   /* 24 bytes */
+    uint32_t struct_size;     /* = sizeof(gm_wall_clearance_params) */
+    uint32_t reference;       /* GM_WALL_CLEAR_MIN (default) or GM_WALL_CLEAR_MEAN */
+    uint32_t min_count;       /* >= 1 (default 8): points a cell needs to be usable */
+    uint32_t reserved;        /* 0 */
+    double   margin;          /* metres, in [0, 8] (default 0.10): clearance below it is tight */
+} gm_wall_clearance_params;
+
+typedef struct gm_wall_clearance_station {   /* 32 bytes */
+    int64_t  min_clearance;   /* least c of the station, 2^-20 m; INT64_MAX when no cell is usable and gauged */
+    uint32_t min_sector;      /* its sector, the smallest among equals; UINT32_MAX when there is none */
+    uint32_t usable;          /* gauged cells with count >= min_count: infringed + tight + clear */
+    uint32_t tight, infringed;
+    uint32_t unsurveyed;      /* gauged cells that are empty or unusable */
+    uint32_t gauge;           /* the table used */
+} gm_wall_clearance_station;
+
+typedef struct gm_wall_clearance_cell {   /* 16 bytes */
+    uint32_t cell;            /* map-wide j * n_sectors + k */
+    uint32_t count;
+    int64_t  clearance;       /* c < T, 2^-20 m */
+} gm_wall_clearance_cell;
+
+typedef struct gm_wall_clearance_info {   /* 104 bytes */
+    uint32_t struct_size;     /* = sizeof(gm_wall_clearance_info), filled by the library */
+    uint32_t station0, n_stations, n_sectors;   /* the window and the map's sectors */
+    int64_t  margin_q, radius_q;                /* T, R_q */
+    uint64_t ungauged, empty, unusable, infringed, tight, clear;   /* window cells per class */
+    uint32_t stations_tight;       /* stations with tight + infringed > 0 */
+    uint32_t stations_infringed;   /* stations with infringed > 0 */
+    int64_t  min_clearance;   /* least c of the window; INT64_MAX when no cell is usable and gauged */
+    uint32_t min_cell;        /* its map-wide cell, the smallest among equals; UINT32_MAX when there is none */
+    uint32_t reserved;        /* 0 */
+} gm_wall_clearance_info;
+
+typedef struct gm_wall_clearance_run {   /* 72 bytes; fp64 derived on the host, one rounding per operation */
+    uint32_t station_from, station_to;   /* map-wide, inclusive: the first and the last station short of the margin */
+    double   chainage_from;   /* t_min + station_from * station_length */
+    double   chainage_to;     /* t_min + (station_to + 1) * station_length */
+    int64_t  min_clearance;   /* least min_clearance of the run's stations, 2^-20 m */
+    double   min_clearance_m; /* min_clearance 2^-20 */
+    uint32_t min_station;     /* map-wide; the first among equals */
+    uint32_t min_sector;
+    double   angle_deg;       /* (360 (2 min_sector + 1)) / (2 n_sectors): the centre of the sector */
+    uint64_t tight, infringed;   /* summed over stations station_from .. station_to */
+} gm_wall_clearance_run;
+
+/* Host only: the defaults of the table above.  A NULL is ignored. */
+void gm_wall_clearance_default_params(gm_wall_clearance_params *p);
+/* Host only, no device, no map: everything gm_wall_map_clearance refuses but the window and the output buffers, for a
+ * map with the parameters p (n_sectors and radius decide) and a window of n stations.  c NULL: the defaults;
+ * station_gauge may be NULL.  GM_ERR_INVALID_ARG: p or gauge_q NULL, a struct_size mismatch, n_sectors outside
+ * 1 .. GM_WALL_MAX_SECTORS, rint(radius 2^20) > 2^32 or radius not positive and finite, reference above
+ * GM_WALL_CLEAR_MEAN, min_count 0, margin outside [0, 8], n_gauges outside 1 .. GM_WALL_CLEAR_MAX_GAUGES, a negative
+ * gauge entry, a station_gauge entry >= n_gauges. */
+gm_status gm_wall_clearance_check_params(const gm_wall_params *p, const gm_wall_clearance_params *c, const int32_t *gauge_q,
+                                         uint32_t n_gauges, const uint8_t *station_gauge, uint32_t n);
+/* The clearance of stations [station0, station0 + n).  Synchronises the map (as gm_wall_map_sync), runs on the map's
+ * stream and blocks.  prm NULL: the defaults.  info is required; it and *n_out (may be NULL; the number of list cells,
+ * tight + infringed) are filled whenever the call got as far as the device, also on GM_ERR_CAPACITY.  stations NULL
+ * with station_capacity 0 and cells NULL with cell_capacity 0 are count queries (GM_OK): info.n_stations records and
+ * *n_out cells are what a second call needs room for.  A station_capacity below n or a cell_capacity below *n_out with
+ * a buffer returns GM_ERR_CAPACITY and writes neither array.  n = 0 gives nothing.  The map is not changed.  Scratch
+ * (the uploaded tables, 32 B per window station, 16 B per cell of a chunk of staging, the chained scan's own records)
+ * is allocated on first use, kept grow-only in the map and freed with it; a map that never calls this allocates
+ * nothing.  GM_ERR_INVALID_ARG: NULL map / info, a window outside the map, whatever gm_wall_clearance_check_params
+ * refuses, stations or cells NULL with a capacity. */
+gm_status gm_wall_map_clearance(gm_wall_map *map, uint32_t station0, uint32_t n, const int32_t *gauge_q, uint32_t n_gauges,
+                                const uint8_t *station_gauge, const gm_wall_clearance_params *prm, gm_wall_clearance_info *info,
+                                gm_wall_clearance_station *stations, uint32_t station_capacity, gm_wall_clearance_cell *cells,
+                                uint64_t cell_capacity, uint64_t *n_out);
+/* Host only, no device, no map: one gauge table from a polygon in the section plane.  uv holds n_vertices rows
+ * (along u, along v) in metres about the design axis, shifted by offset[2] (may be NULL: no shift): P_i = uv_i + offset.
+ * The polygon is closed (the last vertex joins the first), simple, has 3 .. GM_WALL_GAUGE_MAX_VERTICES vertices and
+ * holds the axis strictly inside.  Sector k is the wedge between the rays at phi_k = 2 pi (k / n_sectors) and phi_k+1
+ * (phi is 0 toward u and grows toward v, as in the binning; the last ray is the first).  g_k is the largest distance
+ * from the axis over the vertices inside the wedge -- cross(d_k, P) >= 0 and cross(P, d_k+1) >= 0 with the ray
+ * directions d = (cos phi, sin phi) of the host's libm; every vertex with one sector -- and over the intersections of
+ * every edge with the wedge's two rays: exact for the boundary inside the wedge, distance being convex along an edge.
+ * gauge_q[k] = ceil(g_k 2^20).  *n_out (may be NULL) = n_sectors; a capacity below it returns GM_ERR_CAPACITY and
+ * writes nothing.  GM_ERR_INVALID_ARG: a NULL, p->struct_size mismatch, n_sectors outside 1 .. GM_WALL_MAX_SECTORS, a
+ * vertex count outside its limits, a coordinate that is not finite, an edge of length 0, edges that cross or touch,
+ * the axis outside or on the boundary, a g_k of 2048 m or more. */
+gm_status gm_wall_gauge_from_polygon(const gm_wall_params *p, const double *uv, uint32_t n_vertices, const double offset[2],
+                                     int32_t *gauge_q, uint32_t capacity, uint32_t *n_out);
+/* Host only, no device, no map: the n station records of a window that starts at map station station0, folded into
+ * chainage runs.  A station is FLAGGED iff tight + infringed > 0; flagged stations with at most max_gap stations that
+ * are not flagged between them belong to one run, which starts and ends on a flagged station.  *n_out (may be NULL) =
+ * the number of runs; runs NULL with capacity 0 is a count query, a capacity below *n_out returns GM_ERR_CAPACITY and
+ * writes nothing.  GM_ERR_INVALID_ARG: p NULL, p->struct_size mismatch, n_sectors 0, stations NULL with n > 0, runs
+ * NULL with a capacity, station0 + n above 2^32. */
+gm_status gm_wall_clearance_runs(const gm_wall_params *p, const gm_wall_clearance_station *stations, uint32_t n,
+                                 uint32_t station0, uint32_t max_gap, gm_wall_clearance_run *runs, uint32_t capacity,
+                                 uint32_t *n_out);
+
 /* ---- a frame's changed points against the wall map (gm_wall_map_check_*) ----------------------------------------------
  * Which points of the frame in front of the sensor are NOT where the map says the wall is: rockfall, a fallen lining
  * segment, a vehicle in the profile, new shotcrete.  One device pass over the frame's valid cloud under a pose; only the
