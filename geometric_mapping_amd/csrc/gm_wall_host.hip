@@ -1,0 +1,615 @@
+// gm_wall_host.hip -- the part of the wall map's C ABI that needs no device (include/gm_hip.h states each rule): the
+// defaults, the parameter checks, the classification of one cell, the metrics, the direction table, the gauge of a polygon,
+// the runs, the align's selection.  No device call, no context, no map: it links against libm and the C++ library alone,
+// and host/gm_wall_host_test.cpp runs it under the host sanitizers.
+#include <vector>
+
+#define GM_WALL_HOST_ONLY
+#include "gm_wall_map.hpp"
+
+using namespace gm;
+using namespace gm::wall;
+
+namespace gm {
+namespace wall {
+
+gm_status check_params(const gm_wall_params *p)
+{
+    if (!p || p->struct_size != sizeof(gm_wall_params)) return GM_ERR_INVALID_ARG;
+    if (p->n_stations < 1u || p->n_sectors < 1u || p->n_sectors > GM_WALL_MAX_SECTORS ||
+        (uint64_t)p->n_stations * p->n_sectors > GM_WALL_MAX_CELLS)
+        return GM_ERR_INVALID_ARG;
+    if (!(p->station_length > 0.0) || !isfinite(p->station_length) || !((float)p->station_length > 0.0f) ||
+        !isfinite((float)p->station_length) || !isfinite(p->t_min) || !(p->gate > 0.0) || !(p->gate <= 8.0) ||
+        !(p->radius > 0.0) || !isfinite((float)p->radius))
+        return GM_ERR_INVALID_ARG;
+    double up2 = 0.0, fw2 = 0.0, d2 = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        if (!isfinite(p->up[k]) || !isfinite(p->forward[k]) || !isfinite(p->direction[k]) || !isfinite(p->point[k]))
+            return GM_ERR_INVALID_ARG;
+        up2 += p->up[k] * p->up[k];
+        fw2 += p->forward[k] * p->forward[k];
+        d2 += p->direction[k] * p->direction[k];
+    }
+    if (!(up2 > 0.0) || !(fw2 > 0.0) || !(d2 > 0.0) || !isfinite(up2) || !isfinite(fw2) || !isfinite(d2)) return GM_ERR_INVALID_ARG;
+    return GM_OK;
+}
+
+void design_frame_of(const gm_wall_params &p, DesignFrame &d)
+{
+    const double dn = sqrt(dot(p.direction, p.direction));
+    const double s = dot(p.direction, p.forward);
+    for (int k = 0; k < 3; ++k) d.a[k] = (s >= 0.0 ? p.direction[k] : -p.direction[k]) / dn;
+    const double ca = dot(p.point, d.a), ua = dot(p.up, d.a);
+    double u[3];
+    for (int k = 0; k < 3; ++k) u[k] = p.up[k] - ua * d.a[k];
+    const double ul = sqrt(dot(u, u)), upl = sqrt(dot(p.up, p.up));
+    d.status = GM_SURF_OK;
+    if (ul < 0.1 * upl) {
+        double e2[3];
+        fit_basis(d.a, u, e2);
+        d.status |= GM_SURF_UP_FALLBACK;
+    } else {
+        for (int k = 0; k < 3; ++k) u[k] /= ul;
+    }
+    const double *a = d.a;
+    const double v[3] = {a[1] * u[2] - a[2] * u[1], a[2] * u[0] - a[0] * u[2], a[0] * u[1] - a[1] * u[0]};
+    for (int k = 0; k < 3; ++k) {
+        d.o[k] = p.point[k] - ca * a[k];
+        d.u[k] = u[k];
+        d.v[k] = v[k];
+    }
+    d.R = p.radius;
+}
+
+int pose_split(const double pose[12], double Rm[3][3], double tr[3])
+{
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 4; ++c)
+            if (!isfinite(pose[4 * r + c])) return 1;
+        for (int c = 0; c < 3; ++c) Rm[r][c] = pose[4 * r + c];
+        tr[r] = pose[4 * r + 3];
+    }
+    double dev = 0.0;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const double g = Rm[0][i] * Rm[0][j] + Rm[1][i] * Rm[1][j] + Rm[2][i] * Rm[2][j] - (i == j ? 1.0 : 0.0);
+            dev = std::max(dev, fabs(g));
+        }
+    const double det = Rm[0][0] * (Rm[1][1] * Rm[2][2] - Rm[1][2] * Rm[2][1]) - Rm[0][1] * (Rm[1][0] * Rm[2][2] - Rm[1][2] * Rm[2][0]) +
+                       Rm[0][2] * (Rm[1][0] * Rm[2][1] - Rm[1][1] * Rm[2][0]);
+    return (!(dev <= 1e-6) || !(det > 0.0)) ? 2 : 0;
+}
+
+void cloud_directions(uint32_t nsec, uint32_t bk, double *cos_sin)
+{
+    const uint32_t NK = (nsec + bk - 1u) / bk;
+    for (uint32_t K = 0; K < NK; ++K) {
+        const uint32_t nk = nsec - K * bk < bk ? nsec - K * bk : bk;
+        const double f = (double)(2u * K * bk + nk) / (double)(2u * nsec);
+        const double phi = kTwoPi * f;
+        cos_sin[2 * K] = cos(phi);
+        cos_sin[2 * K + 1] = sin(phi);
+    }
+}
+
+bool clearance_ok(const gm_wall_params *p, const gm_wall_clearance_params &c, const int32_t *gauge_q, uint32_t n_gauges,
+                  const uint8_t *station_gauge, uint32_t n, long long &T, long long &Rq)
+{
+    T = 0; Rq = 0;
+    if (!p || !gauge_q || p->struct_size != sizeof(gm_wall_params) || p->n_sectors < 1u || p->n_sectors > GM_WALL_MAX_SECTORS) return false;
+    if (c.struct_size != sizeof(gm_wall_clearance_params) || c.reference > (uint32_t)GM_WALL_CLEAR_MEAN || c.min_count < 1u) return false;
+    if (!(c.margin >= 0.0) || !(c.margin <= 8.0)) return false;
+    if (!(p->radius > 0.0) || !isfinite(p->radius)) return false;
+    const double rq = rint(p->radius * 1048576.0);
+    if (!(rq <= 4294967296.0)) return false;
+    if (n_gauges < 1u || n_gauges > GM_WALL_CLEAR_MAX_GAUGES) return false;
+    const size_t entries = (size_t)n_gauges * p->n_sectors;
+    for (size_t i = 0; i < entries; ++i)
+        if (gauge_q[i] < 0) return false;
+    if (station_gauge)
+        for (uint32_t j = 0; j < n; ++j)
+            if (station_gauge[j] >= n_gauges) return false;
+    T = (long long)rint(c.margin * 1048576.0);
+    Rq = (long long)rq;
+    return true;
+}
+
+bool check_prm_ok(const gm_wall_check_params &c, long long &T)
+{
+    T = 0;
+    if (c.struct_size != sizeof(gm_wall_check_params) || c.reference > (uint32_t)GM_WALL_CHECK_ENVELOPE || c.min_count < 1u) return false;
+    if (!(c.threshold > 0.0) || !(c.threshold <= 8.0) || !(c.gate > 0.0) || !(c.gate <= 8.0)) return false;
+    T = (long long)rint(c.threshold * 1048576.0);
+    return T >= 1;
+}
+
+bool locate_prm_ok(const gm_wall_locate_params &p)
+{
+    return p.struct_size == sizeof(gm_wall_locate_params) && p.reference <= (uint32_t)GM_WALL_LOCATE_MAP && p.min_count >= 1u &&
+           p.gate > 0.0 && p.gate <= 8.0;
+}
+
+bool align_prm_ok(const gm_wall_align_params &p, uint32_t nsec)
+{
+    if (p.struct_size != sizeof(gm_wall_align_params) || nsec < 1u || nsec > GM_WALL_MAX_SECTORS) return false;
+    if (p.half_patch_stations < 1u || 2ull * p.half_patch_stations * nsec > GM_WALL_ALIGN_MAX_PATCH_CELLS) return false;
+    if (p.max_station_shift > GM_WALL_ALIGN_MAX_SHIFT || p.max_sector_shift > GM_WALL_ALIGN_MAX_SHIFT) return false;
+    if (2u * p.max_sector_shift + 1u > nsec) return false;
+    if ((2u * p.max_station_shift + 1u) * (2u * p.max_sector_shift + 1u) > GM_WALL_ALIGN_MAX_SHIFTS) return false;
+    if (p.min_count < 1u || p.min_frame_count < 1u || p.min_overlap < 1u) return false;
+    if (!(p.gate > 0.0) || !(p.gate <= 8.0) || !(p.clip > 0.0) || !(p.clip <= 8.0) || !(rint(p.clip * 1048576.0) >= 1.0)) return false;
+    return p.min_distinction >= 1.0 && isfinite(p.min_distinction);
+}
+
+bool object_prm_ok(const gm_wall_object_params &p)
+{
+    return p.struct_size == sizeof(gm_wall_object_params) && p.block_stations >= 1u && p.block_sectors >= 1u &&
+           p.min_block_points >= 1u && p.min_points >= 1u && (p.connectivity == 4u || p.connectivity == 8u) &&
+           p.half_window_stations >= 1u && p.half_window_stations <= (1u << 20);
+}
+
+void align_select(const DesignFrame &d, const gm_wall_params &wp, const gm_wall_align_params &ap, const double Rm[3][3],
+                  const double tr[3], const gm_wall_align_score *t, gm_wall_align_info *info)
+{
+    const int A = (int)ap.max_station_shift, B = (int)ap.max_sector_shift, nb = 2 * B + 1, ns = (2 * A + 1) * nb;
+    const double nan = __builtin_nan(""), inf = __builtin_inf();
+    const double ds = wp.station_length;
+    memset(info, 0, sizeof(*info));
+    info->struct_size = (uint32_t)sizeof(gm_wall_align_info);
+    const double rel[3] = {tr[0] - d.o[0], tr[1] - d.o[1], tr[2] - d.o[2]};
+    const double jd = floor((dot(rel, d.a) - wp.t_min) / ds);
+    info->anchor_station = fabs(jd) < 4.0e18 ? (int64_t)jd : 0;
+    info->half_patch_stations = ap.half_patch_stations;
+    info->max_station_shift = ap.max_station_shift;
+    info->max_sector_shift = ap.max_sector_shift;
+    auto cheb = [&](int i, int a0, int b0) { return std::max(abs(i / nb - A - a0), abs(i % nb - B - b0)); };
+    auto valid = [&](int i) { return t[i].n >= ap.min_overlap; };
+    auto cost = [&](int i) { return (double)t[i].ssd / (double)t[i].n; };
+    int best = -1;
+    for (int i = 0; i < ns; ++i) {
+        if (!valid(i)) continue;
+        if (best >= 0) {   // ssd_i / n_i against ssd_best / n_best, exactly
+            const unsigned __int128 l = (unsigned __int128)t[i].ssd * t[best].n, r = (unsigned __int128)t[best].ssd * t[i].n;
+            if (l > r || (l == r && cheb(i, 0, 0) >= cheb(best, 0, 0))) continue;
+        }
+        best = i;
+    }
+    if (best < 0) {
+        info->status = GM_ALIGN_NO_OVERLAP;
+        info->frac_station = info->frac_sector = info->shift_m = info->roll = info->bias_m = nan;
+        info->rms_best = info->rms_runner = info->distinction = nan;
+        for (int k = 0; k < 12; ++k) info->pose[k] = nan;
+        return;
+    }
+    const int ia = best / nb, ib = best % nb, sa = ia - A, sb = ib - B;
+    const double c0 = cost(best);
+    auto fraction = [&](int lo, int hi, bool have) {
+        if (!have || !valid(lo) || !valid(hi)) return 0.0;
+        const double cm = cost(lo), cp = cost(hi), den = cm - 2.0 * c0 + cp;
+        if (!(den > 0.0)) return 0.0;
+        const double f = 0.5 * (cm - cp) / den;
+        return f < -0.5 ? -0.5 : (f > 0.5 ? 0.5 : f);
+    };
+    const double fa = fraction(best - nb, best + nb, ia > 0 && ia < 2 * A);
+    const double fb = fraction(best - 1, best + 1, ib > 0 && ib < 2 * B);
+    double cr = inf;
+    bool runner = false;
+    for (int i = 0; i < ns; ++i)
+        if (valid(i) && cheb(i, sa, sb) > 1) {
+            const double c = cost(i);
+            if (!runner || c < cr) cr = c;
+            runner = true;
+        }
+    info->overlap = t[best].n;
+    info->best_station = sa;
+    info->best_sector = sb;
+    info->frac_station = fa;
+    info->frac_sector = fb;
+    info->shift_m = ((double)sa + fa) * ds;
+    info->roll = ((double)sb + fb) * (kTwoPi / (double)wp.n_sectors);
+    info->bias_m = ((double)t[best].sum_d * 0x1p-20) / (double)t[best].n;
+    info->rms_best = sqrt(c0) * 0x1p-20;
+    info->rms_runner = runner ? sqrt(cr) * 0x1p-20 : nan;
+    info->distinction = (c0 == 0.0 || !runner) ? inf : cr / c0;
+    info->status = GM_ALIGN_OK;
+    if (info->distinction < ap.min_distinction) info->status |= GM_ALIGN_AMBIGUOUS;
+    if ((A > 0 && abs(sa) == A) || (B > 0 && abs(sb) == B)) info->status |= GM_ALIGN_AT_BORDER;
+    // Rm' = Q Rm, tr' = o + Q (tr - o) + shift_m a;  Q = cos I + sin [a]x + (1 - cos) a a^T
+    const double cs = cos(info->roll), sn = sin(info->roll);
+    const double *a = d.a;
+    const double K[3][3] = {{0.0, -a[2], a[1]}, {a[2], 0.0, -a[0]}, {-a[1], a[0], 0.0}};
+    double Q[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) Q[r][c] = (r == c ? cs : 0.0) + sn * K[r][c] + (1.0 - cs) * a[r] * a[c];
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) info->pose[4 * r + c] = Q[r][0] * Rm[0][c] + Q[r][1] * Rm[1][c] + Q[r][2] * Rm[2][c];
+        info->pose[4 * r + 3] = d.o[r] + (Q[r][0] * rel[0] + Q[r][1] * rel[1] + Q[r][2] * rel[2]) + info->shift_m * a[r];
+    }
+}
+
+}  // namespace wall
+}  // namespace gm
+
+namespace {
+
+// The extent outputs the two metrics calls share: chainage_from / _to and angle_from_deg / _to_deg of a record's station
+// and sector extents, the turned pair when it is the shorter (the record lies across the seam).  false, and nothing
+// written: the extents are not those of a record on this grid.  One operation per statement: the same roundings as the
+// twin's, whatever the compiler may contract.
+template <class R, class M>
+bool extent_metrics(const gm_wall_params &p, const R &r, M *out)
+{
+    const uint32_t ns = p.n_sectors, half = ns / 2u;
+    if (r.sector_min > r.sector_max || r.sector_max >= ns || r.sector_min_turned > r.sector_max_turned ||
+        r.sector_max_turned >= ns || r.station_min > r.station_max)
+        return false;
+    const double from = (double)r.station_min * p.station_length;
+    const double to = (double)(r.station_max + 1.0) * p.station_length;
+    out->chainage_from = p.t_min + from;
+    out->chainage_to = p.t_min + to;
+    const uint32_t plain = r.sector_max - r.sector_min + 1u, turned = r.sector_max_turned - r.sector_min_turned + 1u;
+    uint32_t k_from = r.sector_min, k_end = r.sector_max + 1u;
+    if (turned < plain) {   // turned back: k = (t - n_sectors / 2) mod n_sectors
+        k_from = (r.sector_min_turned + ns - half) % ns;
+        k_end = (r.sector_max_turned + ns - half) % ns + 1u;
+    }
+    const double a0 = 360.0 * (double)k_from;
+    const double a1 = 360.0 * (double)k_end;
+    out->angle_from_deg = a0 / (double)ns;
+    out->angle_to_deg = a1 / (double)ns;
+    return true;
+}
+
+double cross2(const double a[2], const double b[2]) { return a[0] * b[1] - a[1] * b[0]; }
+
+// 1 when the closed segments ab and cd share a point
+bool segments_meet(const double a[2], const double b[2], const double c[2], const double d[2])
+{
+    const double ab[2] = {b[0] - a[0], b[1] - a[1]}, cd[2] = {d[0] - c[0], d[1] - c[1]};
+    const double ac[2] = {c[0] - a[0], c[1] - a[1]}, ad[2] = {d[0] - a[0], d[1] - a[1]};
+    const double ca[2] = {a[0] - c[0], a[1] - c[1]}, cb[2] = {b[0] - c[0], b[1] - c[1]};
+    const double o1 = cross2(ab, ac), o2 = cross2(ab, ad), o3 = cross2(cd, ca), o4 = cross2(cd, cb);
+    if (((o1 > 0.0 && o2 < 0.0) || (o1 < 0.0 && o2 > 0.0)) && ((o3 > 0.0 && o4 < 0.0) || (o3 < 0.0 && o4 > 0.0))) return true;
+    auto on = [](const double p[2], const double q[2], const double r[2]) {   // r collinear with pq: inside its box?
+        return std::min(p[0], q[0]) <= r[0] && r[0] <= std::max(p[0], q[0]) && std::min(p[1], q[1]) <= r[1] && r[1] <= std::max(p[1], q[1]);
+    };
+    return (o1 == 0.0 && on(a, b, c)) || (o2 == 0.0 && on(a, b, d)) || (o3 == 0.0 && on(c, d, a)) || (o4 == 0.0 && on(c, d, b));
+}
+
+// the polygon of gm_wall_gauge_from_polygon is accepted: finite, no edge of length 0, simple, the axis strictly inside
+bool gauge_polygon_ok(const std::vector<double> &P, uint32_t nv)
+{
+    for (uint32_t i = 0; i < 2u * nv; ++i)
+        if (!isfinite(P[i])) return false;
+    const double zero[2] = {0.0, 0.0};
+    int wn = 0;
+    for (uint32_t i = 0; i < nv; ++i) {
+        const double *a = &P[2 * i], *b = &P[2 * ((i + 1u) % nv)];
+        if (a[0] == b[0] && a[1] == b[1]) return false;
+        const double left = cross2(a, b);   // > 0: the axis lies to the left of a -> b
+        if (left == 0.0 && segments_meet(a, b, zero, zero)) return false;   // the axis on the boundary
+        if (a[1] <= 0.0) {
+            if (b[1] > 0.0 && left > 0.0) ++wn;
+        } else if (b[1] <= 0.0 && left < 0.0) {
+            --wn;
+        }
+    }
+    if (wn == 0) return false;
+    for (uint32_t i = 0; i < nv; ++i) {
+        const double *a = &P[2 * i], *b = &P[2 * ((i + 1u) % nv)];
+        for (uint32_t j = i + 1u; j < nv; ++j) {
+            const double *c = &P[2 * j], *d = &P[2 * ((j + 1u) % nv)];
+            const bool next = j == i + 1u, prev = i == 0u && j == nv - 1u;
+            if (next || prev) {   // neighbours share one vertex; they may not fold back onto each other
+                const double *s = next ? b : a, *x = next ? a : b, *y = next ? d : c;   // s shared; x, y the far ends
+                const double e[2] = {x[0] - s[0], x[1] - s[1]}, f[2] = {y[0] - s[0], y[1] - s[1]};
+                if (cross2(e, f) == 0.0 && e[0] * f[0] + e[1] * f[1] > 0.0) return false;
+            } else if (segments_meet(a, b, c, d)) {
+                return false;
+            }
+        }
+    }
+    return true;
+}
+
+// a parameter block at its defaults: zeroed but for struct_size; the caller sets the rest
+template <class P>
+bool defaults_begin(P *p)
+{
+    if (!p) return false;
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(P);
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+void gm_wall_default_params(gm_wall_params *p)
+{
+    if (!defaults_begin(p)) return;
+    p->n_stations = 4000;
+    p->n_sectors = 90;
+    p->station_length = 0.25;
+    p->t_min = 0.0;
+    p->gate = 0.25;
+    p->direction[0] = 1.0;
+    p->radius = 2.0;
+    p->up[2] = 1.0;
+    p->forward[0] = 1.0;
+}
+
+void gm_wall_region_default_params(gm_wall_region_params *p)
+{
+    if (!defaults_begin(p)) return;
+    p->min_count = 8;
+    p->min_cells = 4;
+    p->connectivity = 8;
+    p->threshold = 0.05;
+}
+
+void gm_wall_cloud_default_params(gm_wall_cloud_params *p)
+{
+    if (!defaults_begin(p)) return;
+    p->block_stations = 1;
+    p->block_sectors = 1;
+    p->min_count = 1;
+    p->exaggeration = 1.0;
+}
+
+void gm_wall_clearance_default_params(gm_wall_clearance_params *p)
+{
+    if (!defaults_begin(p)) return;
+    p->reference = GM_WALL_CLEAR_MIN;
+    p->min_count = 8;
+    p->margin = 0.10;
+}
+
+void gm_wall_check_default_params(gm_wall_check_params *p)
+{
+    if (!defaults_begin(p)) return;
+    p->reference = GM_WALL_CHECK_MEAN;
+    p->min_count = 8;
+    p->threshold = 0.05;
+    p->gate = 1.0;
+}
+
+void gm_wall_locate_default_params(gm_wall_locate_params *p)
+{
+    if (!defaults_begin(p)) return;
+    p->reference = GM_WALL_LOCATE_DESIGN;
+    p->min_count = 8;
+    p->gate = 0.25;
+}
+
+void gm_wall_align_default_params(gm_wall_align_params *p)
+{
+    if (!defaults_begin(p)) return;
+    p->half_patch_stations = 20;
+    p->max_station_shift = 8;
+    p->max_sector_shift = 4;
+    p->min_count = 8;
+    p->min_frame_count = 4;
+    p->min_overlap = 64;
+    p->gate = 0.25;
+    p->clip = 0.05;
+    p->min_distinction = 1.5;
+}
+
+void gm_wall_object_default_params(gm_wall_object_params *p)
+{
+    if (!defaults_begin(p)) return;
+    p->block_stations = 1;
+    p->block_sectors = 1;
+    p->min_block_points = 2;
+    p->min_points = 8;
+    p->connectivity = 8;
+    p->half_window_stations = 128;
+}
+
+gm_status gm_wall_locate_check_params(const gm_wall_locate_params *p)
+{
+    return p && locate_prm_ok(*p) ? GM_OK : GM_ERR_INVALID_ARG;
+}
+
+gm_status gm_wall_align_check_params(const gm_wall_align_params *p, uint32_t n_sectors)
+{
+    return p && align_prm_ok(*p, n_sectors) ? GM_OK : GM_ERR_INVALID_ARG;
+}
+
+gm_status gm_wall_clearance_check_params(const gm_wall_params *p, const gm_wall_clearance_params *c, const int32_t *gauge_q,
+                                         uint32_t n_gauges, const uint8_t *station_gauge, uint32_t n)
+{
+    long long T, Rq;
+    const gm_wall_clearance_params cp = params_or(c, gm_wall_clearance_default_params);
+    return clearance_ok(p, cp, gauge_q, n_gauges, station_gauge, n, T, Rq) ? GM_OK : GM_ERR_INVALID_ARG;
+}
+
+gm_status gm_wall_check_classify(const gm_wall_check_params *prm, const gm_wall_raw_cell *cell, float e, int64_t *delta, uint32_t *cls)
+{
+    long long T;
+    if (!prm || !cell || !delta || !cls || !check_prm_ok(*prm, T)) return GM_ERR_INVALID_ARG;
+    *delta = 0;
+    if (!(fabsf(e) <= (float)prm->gate)) {
+        *cls = GM_WALL_CHECK_CLS_BEYOND_GATE;
+        return GM_OK;
+    }
+    long long d;
+    *cls = wall_check_rule(prm->reference, prm->min_count, T, cell->sum, cell->count, cell->min_key, cell->max_key, e, d);
+    *delta = d;
+    return GM_OK;
+}
+
+gm_status gm_wall_region_metrics(const gm_wall_params *p, const gm_wall_region *r, struct gm_wall_region_metrics *out)
+{
+    if (!p || !r || !out || p->struct_size != sizeof(gm_wall_params) || p->n_sectors < 1u || r->cells < 1u) return GM_ERR_INVALID_ARG;
+    if (!extent_metrics(*p, *r, out)) return GM_ERR_INVALID_ARG;
+    const uint32_t ns = p->n_sectors;
+    // (one operation per statement: the same roundings as the twin's, whatever the compiler may contract)
+    const double sr = p->station_length * p->radius;
+    const double ring = sr * kTwoPi;
+    const double cell_area = ring / (double)ns;
+    const double sum_m = (double)r->sum_d * 0x1p-20;
+    out->area_m2 = (double)r->cells * cell_area;
+    out->volume_m3 = sum_m * cell_area;
+    out->peak_m = (double)r->peak * 0x1p-20;
+    out->mean_m = sum_m / (double)r->cells;
+    return GM_OK;
+}
+
+gm_status gm_wall_object_metrics(const gm_wall_params *p, const gm_wall_object_params *op, const gm_wall_object *o,
+                                 struct gm_wall_object_metrics *out)
+{
+    if (!p || !o || !out || p->struct_size != sizeof(gm_wall_params) || p->n_sectors < 1u || o->points < 1u) return GM_ERR_INVALID_ARG;
+    if (op && op->struct_size != sizeof(gm_wall_object_params)) return GM_ERR_INVALID_ARG;
+    if (!extent_metrics(*p, *o, out)) return GM_ERR_INVALID_ARG;
+    // (one operation per statement: the same roundings as the twin's, whatever the compiler may contract)
+    const double pts = (double)o->points;
+    const double sx = (double)o->sum_x * 0x1p-16, sy = (double)o->sum_y * 0x1p-16, sz = (double)o->sum_z * 0x1p-16;
+    out->centroid[0] = sx / pts;
+    out->centroid[1] = sy / pts;
+    out->centroid[2] = sz / pts;
+    const double sum_m = (double)o->sum_delta * 0x1p-20;
+    out->mean_m = sum_m / pts;
+    out->peak_m = (double)o->peak * 0x1p-20;
+    for (int k = 0; k < 3; ++k) out->size[k] = (double)o->box_max[k] - (double)o->box_min[k];
+    return GM_OK;
+}
+
+gm_status gm_wall_cloud_directions(const gm_wall_params *p, const gm_wall_cloud_params *c, double *cos_sin, uint32_t capacity,
+                                   uint32_t *n_out)
+{
+    if (n_out) *n_out = 0;
+    if (!p || p->struct_size != sizeof(gm_wall_params) || p->n_sectors < 1u || p->n_sectors > GM_WALL_MAX_SECTORS) return GM_ERR_INVALID_ARG;
+    if (c && (c->struct_size != sizeof(gm_wall_cloud_params) || c->block_sectors < 1u)) return GM_ERR_INVALID_ARG;
+    if (!cos_sin && capacity) return GM_ERR_INVALID_ARG;
+    const uint32_t bk = std::min(c ? c->block_sectors : 1u, p->n_sectors);
+    const uint32_t NK = (p->n_sectors + bk - 1u) / bk;
+    if (n_out) *n_out = NK;
+    if (capacity < NK) return GM_ERR_CAPACITY;
+    cloud_directions(p->n_sectors, bk, cos_sin);
+    return GM_OK;
+}
+
+gm_status gm_wall_gauge_from_polygon(const gm_wall_params *p, const double *uv, uint32_t n_vertices, const double offset[2],
+                                     int32_t *gauge_q, uint32_t capacity, uint32_t *n_out)
+{
+    if (n_out) *n_out = 0;
+    if (!p || !uv || p->struct_size != sizeof(gm_wall_params) || p->n_sectors < 1u || p->n_sectors > GM_WALL_MAX_SECTORS) return GM_ERR_INVALID_ARG;
+    if (n_vertices < 3u || n_vertices > GM_WALL_GAUGE_MAX_VERTICES || (!gauge_q && capacity)) return GM_ERR_INVALID_ARG;
+    if (offset && (!isfinite(offset[0]) || !isfinite(offset[1]))) return GM_ERR_INVALID_ARG;
+    const uint32_t ns = p->n_sectors, nv = n_vertices;
+    std::vector<double> P(2 * (size_t)nv);
+    for (uint32_t i = 0; i < nv; ++i) {
+        P[2 * i] = uv[2 * i] + (offset ? offset[0] : 0.0);
+        P[2 * i + 1] = uv[2 * i + 1] + (offset ? offset[1] : 0.0);
+    }
+    if (!gauge_polygon_ok(P, nv)) return GM_ERR_INVALID_ARG;
+    std::vector<double> dirs(2 * (size_t)ns + 2), r(nv);
+    for (uint32_t k = 0; k < ns; ++k) {
+        const double f = (double)k / (double)ns;
+        const double phi = kTwoPi * f;
+        dirs[2 * k] = cos(phi);
+        dirs[2 * k + 1] = sin(phi);
+    }
+    dirs[2 * ns] = dirs[0]; dirs[2 * ns + 1] = dirs[1];   // the last ray is the first
+    for (uint32_t i = 0; i < nv; ++i) r[i] = sqrt(P[2 * i] * P[2 * i] + P[2 * i + 1] * P[2 * i + 1]);
+    // where the ray of every sector start leaves the polygon at the farthest: the largest t >= 0 over the edges it meets
+    std::vector<double> ray(ns, -1.0);
+    for (uint32_t k = 0; k < ns; ++k) {
+        const double *d = &dirs[2 * k];
+        for (uint32_t i = 0; i < nv; ++i) {
+            const double *a = &P[2 * i], *b = &P[2 * ((i + 1u) % nv)];
+            const double e[2] = {b[0] - a[0], b[1] - a[1]};
+            const double den = cross2(e, d);
+            if (den == 0.0) continue;   // parallel: its ends are vertices of the wedge
+            const double s = -cross2(a, d) / den;
+            if (!(s >= 0.0) || !(s <= 1.0)) continue;
+            const double x[2] = {a[0] + s * e[0], a[1] + s * e[1]};
+            const double t = x[0] * d[0] + x[1] * d[1];
+            if (t >= 0.0 && t > ray[k]) ray[k] = t;
+        }
+    }
+    std::vector<int32_t> out(ns);
+    for (uint32_t k = 0; k < ns; ++k) {
+        const double *d0 = &dirs[2 * k], *d1 = &dirs[2 * k + 2];
+        double g = std::max(ray[k], ray[(k + 1u) % ns]);
+        for (uint32_t i = 0; i < nv; ++i) {
+            const double *v = &P[2 * i];
+            if (ns == 1u || (cross2(d0, v) >= 0.0 && cross2(v, d1) >= 0.0)) g = std::max(g, r[i]);
+        }
+        const double q = ceil(g * 1048576.0);
+        if (!(g > 0.0) || !(q < 2147483648.0)) return GM_ERR_INVALID_ARG;
+        out[k] = (int32_t)q;
+    }
+    if (n_out) *n_out = ns;
+    if (capacity < ns) return GM_ERR_CAPACITY;
+    memcpy(gauge_q, out.data(), (size_t)ns * sizeof(int32_t));
+    return GM_OK;
+}
+
+gm_status gm_wall_clearance_runs(const gm_wall_params *p, const gm_wall_clearance_station *stations, uint32_t n,
+                                 uint32_t station0, uint32_t max_gap, gm_wall_clearance_run *runs, uint32_t capacity,
+                                 uint32_t *n_out)
+{
+    if (n_out) *n_out = 0;
+    if (!p || p->struct_size != sizeof(gm_wall_params) || p->n_sectors < 1u || (!stations && n) || (!runs && capacity) ||
+        (uint64_t)station0 + n > 4294967296ull)
+        return GM_ERR_INVALID_ARG;
+    auto flagged = [&](uint32_t i) { return stations[i].tight + stations[i].infringed > 0u; };
+    std::vector<gm_wall_clearance_run> out;
+    for (uint32_t i = 0; i < n;) {
+        if (!flagged(i)) { ++i; continue; }
+        uint32_t last = i;
+        for (uint32_t j = i + 1u; j < n && (uint64_t)j - last <= (uint64_t)max_gap + 1u; ++j)
+            if (flagged(j)) last = j;
+        gm_wall_clearance_run r;
+        memset(&r, 0, sizeof(r));
+        r.station_from = station0 + i;
+        r.station_to = station0 + last;
+        uint32_t at = i;
+        for (uint32_t j = i; j <= last; ++j) {
+            if (stations[j].min_clearance < stations[at].min_clearance) at = j;
+            r.tight += stations[j].tight;
+            r.infringed += stations[j].infringed;
+        }
+        // one operation per statement: the same roundings as the twin's, whatever the compiler may contract
+        const double from = (double)r.station_from * p->station_length;
+        const double to = ((double)r.station_to + 1.0) * p->station_length;
+        r.chainage_from = p->t_min + from;
+        r.chainage_to = p->t_min + to;
+        r.min_clearance = stations[at].min_clearance;
+        r.min_clearance_m = (double)r.min_clearance * 0x1p-20;
+        r.min_station = station0 + at;
+        r.min_sector = stations[at].min_sector;
+        const double num = 360.0 * ((double)r.min_sector * 2.0 + 1.0);
+        r.angle_deg = num / ((double)p->n_sectors * 2.0);
+        out.push_back(r);
+        i = last + 1u;
+    }
+    if (n_out) *n_out = (uint32_t)out.size();
+    if (runs && capacity < out.size()) return GM_ERR_CAPACITY;
+    if (runs && !out.empty()) memcpy(runs, out.data(), out.size() * sizeof(gm_wall_clearance_run));
+    return GM_OK;
+}
+
+gm_status gm_wall_align_select(const gm_wall_params *wall, const gm_wall_align_params *prm, const double pose[12],
+                               const gm_wall_align_score *table, uint32_t n_scores, gm_wall_align_info *info)
+{
+    if (!wall || !pose || !table || !info || check_params(wall) != GM_OK) return GM_ERR_INVALID_ARG;
+    const gm_wall_align_params ap = params_or(prm, gm_wall_align_default_params);
+    if (!align_prm_ok(ap, wall->n_sectors)) return GM_ERR_INVALID_ARG;
+    if (n_scores != (2u * ap.max_station_shift + 1u) * (2u * ap.max_sector_shift + 1u)) return GM_ERR_INVALID_ARG;
+    double Rm[3][3], tr[3];
+    if (pose_split(pose, Rm, tr)) return GM_ERR_INVALID_ARG;
+    DesignFrame d;
+    design_frame_of(*wall, d);
+    const double rel[3] = {tr[0] - d.o[0], tr[1] - d.o[1], tr[2] - d.o[2]};
+    if (!(fabs(floor((dot(rel, d.a) - wall->t_min) / wall->station_length)) < 4.0e18)) return GM_ERR_INVALID_ARG;
+    align_select(d, *wall, ap, Rm, tr, table, info);
+    return GM_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,287 @@
+// gm_wall_map.hpp -- what the three wall-map files share: the map, the state of one (map, slot), the pure rules.
+//   gm_wall_host.hip  every entry point that needs no device, and the rules the others share with them
+//   gm_wall.hip       the map itself and the window calls
+//   gm_wall_slot.hip  the per-(map, slot) calls: check, locate, align, objects
+#pragma once
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "gm_internal.hpp"
+#ifndef GM_WALL_HOST_ONLY   // (gm_wall_host.hip defines it)
+#include "gm_compact.hpp"
+#endif
+
+#define GMW_HIP(ctx, call)                                                           \
+    do {                                                                             \
+        hipError_t e__ = (call);                                                     \
+        if (e__ != hipSuccess) {                                                     \
+            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);         \
+            return (e__ == hipErrorOutOfMemory) ? GM_ERR_OOM : GM_ERR_DEVICE;        \
+        }                                                                            \
+    } while (0)
+#define GMW_OK(call)                       \
+    do {                                   \
+        const gm_status s__ = (call);      \
+        if (s__ != GM_OK) return s__;      \
+    } while (0)
+
+namespace gm {
+namespace wall {
+
+constexpr double kTwoPi = 6.283185307179586476925286766559;
+
+inline double dot(const double *x, const double *y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2]; }
+
+// ---- gm_wall_host.hip: no device, no context, no map ----
+
+// the design frame of include/gm_hip.h: k_surface.hip's surf_frame on fp64 inputs, kept in fp64
+struct DesignFrame { double o[3], a[3], u[3], v[3], R; uint32_t status; };
+void design_frame_of(const gm_wall_params &p, DesignFrame &d);
+gm_status check_params(const gm_wall_params *p);
+// the library's pose check: 0 the pose is accepted (Rm, tr filled), 1 an entry is not finite, 2 Rm is not a rotation
+int pose_split(const double pose[12], double Rm[3][3], double tr[3]);
+// the direction table of include/gm_hip.h: NK pairs (one operation per statement, as stated there)
+void cloud_directions(uint32_t nsec, uint32_t bk, double *cos_sin);
+// gm_wall_clearance_check_params' rule; T and R_q of an accepted call
+bool clearance_ok(const gm_wall_params *p, const gm_wall_clearance_params &c, const int32_t *gauge_q, uint32_t n_gauges,
+                  const uint8_t *station_gauge, uint32_t n, long long &T, long long &Rq);
+bool check_prm_ok(const gm_wall_check_params &c, long long &T);
+bool locate_prm_ok(const gm_wall_locate_params &p);
+bool align_prm_ok(const gm_wall_align_params &p, uint32_t nsec);
+bool object_prm_ok(const gm_wall_object_params &p);
+// The selection and the pose of include/gm_hip.h from a table of (2A + 1)(2B + 1) records.  Fills everything but the
+// device's counts.
+void align_select(const DesignFrame &d, const gm_wall_params &wp, const gm_wall_align_params &ap, const double Rm[3][3],
+                  const double tr[3], const gm_wall_align_score *t, gm_wall_align_info *info);
+
+// the caller's parameters, or the defaults for NULL
+template <class P>
+P params_or(const P *prm, void (*defaults)(P *))
+{
+    P p;
+    defaults(&p);
+    if (prm) p = *prm;
+    return p;
+}
+
+// ---- the map: from here to the end not for gm_wall_host.hip, which so sees nothing that calls the device ----
+#ifndef GM_WALL_HOST_ONLY
+
+constexpr uint64_t kStageCells = 1u << 20;   // cells per chunk of a window call (24 MiB of raw records)
+
+// The records of a chained scan (gm_compact.hpp) that is not a frame's -- a slot's own belong to the frame that may be in
+// flight on it: the record array with the ticket word behind it, and the epoch of the launches on it so far.  The rule is
+// next_scan's (gm_internal.hpp): epochs run 1 .. 2^29-2 and never 0, and the records are cleared when the counter wraps,
+// behind every launch that wrote them.
+struct ScanRecords {
+    DevArray<unsigned long long> rec;   // [n] tile records | the ticket word
+    uint32_t n = 0;
+    uint32_t epoch = 0;
+    bool holds(uint32_t points) const { return n >= compact_records(points); }
+    // for launches over up to `points` inputs; a new block is zeroed on s.  Nothing may be in flight on the old one.
+    gm_status reserve(gm_ctx *ctx, uint32_t points, hipStream_t s)
+    {
+        if (holds(points)) return GM_OK;
+        n = 0;
+        const uint32_t want = compact_records(points);
+        GMW_HIP(ctx, rec.reserve((uint64_t)want + 1));
+        GMW_HIP(ctx, hipMemsetAsync(rec.p, 0, sizeof(unsigned long long) * ((size_t)want + 1), s));
+        n = want;
+        return GM_OK;
+    }
+    // the state of the next k_compact launch on s
+    ScanState next(hipStream_t s)
+    {
+        if (epoch >= 0x1FFFFFFEu) {
+            (void)hipMemsetAsync(rec.p, 0, sizeof(unsigned long long) * ((size_t)n + 1), s);
+            epoch = 0;
+        }
+        epoch += 1u;
+        ScanState st;
+        st.status = rec.p;
+        st.ticket = reinterpret_cast<uint32_t *>(rec.p + n);
+        st.epoch = epoch;
+        st.frame_ptr = nullptr;
+        return st;
+    }
+};
+
+// The result of one per-slot call (a check, a locate, an align) of one (map, slot): enqueued on the slot's stream, read by
+// the host later.  Every reader of the result, every add on another slot and the map's sync and release go through here.
+struct PendingResult {
+    hipEvent_t done = nullptr;   // recorded behind the call and the copy of its result
+    bool have = false;           // a call was enqueued: a result is (or will be) readable
+    bool outstanding = false;    // the host has not waited for `done` yet
+    gm_status ensure(gm_ctx *ctx)
+    {
+        if (!done) GMW_HIP(ctx, hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        return GM_OK;
+    }
+    hipError_t done_passed() { return outstanding ? hipEventSynchronize(done) : hipSuccess; }   // the one host block on `done`
+    gm_status wait(gm_ctx *ctx)
+    {
+        GMW_HIP(ctx, done_passed());
+        outstanding = false;
+        return GM_OK;
+    }
+    gm_status record(gm_ctx *ctx, hipStream_t s)
+    {
+        GMW_HIP(ctx, hipEventRecord(done, s));
+        have = outstanding = true;
+        return GM_OK;
+    }
+    // the map is going: nothing may still be writing its blocks (an error has nowhere to go, as at any release)
+    void release() { (void)done_passed(); if (done) (void)hipEventDestroy(done); }
+};
+
+// gm_wall_map_check_*: the state of one (map, slot), allocated on first use, freed with the map
+struct WallCheckSlot {
+    DevArray<gm_wall_check_point> stage;    // the changed rows of the last check, in order
+    ScanRecords scan;                       // the check's own chained scan
+    DevArray<unsigned long long> ctr;       // device [kWallCheckCounters]
+    HostArray<unsigned long long> h_ctr;    // pinned copy, valid once the result has been waited for
+    PendingResult res;
+    uint32_t status = 0;
+    long long T = 0;
+    int64_t anchor = 0;                     // the check's j_f (gm_wall_map_check_objects anchors its window on it)
+};
+
+// gm_wall_map_locate_*: the state of one (map, slot), allocated on first use, freed with the map
+struct WallLocateSlot {
+    DevArray<WallLocateWork> work;          // the state between the passes, the result behind them
+    DevArray<double> partial;               // [kFitBlocks][kFitRowLen] partial rows of a pass
+    DevArray<uint32_t> ticket;              // last-block ticket of the passes (0 between launches)
+    HostArray<WallLocateWork> h_work;       // pinned copy, valid once the result has been waited for
+    PendingResult res;
+    int64_t anchor = 0;                     // the locate's j_f
+    double of[3] = {0.0, 0.0, 0.0};         // its o_f, map coordinates
+};
+
+// gm_wall_map_align_*: the state of one (map, slot), allocated on first use, freed with the map
+struct WallAlignSlot {
+    DevArray<uint8_t> zeroed;               // counters | score table | patch sums | patch counts: one zero-fill per align
+    DevArray<int32_t> f, m;                 // the two value images
+    HostArray<uint8_t> h_res;               // pinned copy of counters | score table, valid once the result has been waited for
+    PendingResult res;
+    gm_wall_align_params prm;               // of that align
+    double pose[12];                        // the caller's pose of that align
+    uint32_t n_shifts = 0;                  // (2A + 1)(2B + 1)
+};
+
+}  // namespace wall
+}  // namespace gm
+
+struct gm_wall_map {
+    gm_ctx *ctx = nullptr;
+    gm_wall_params prm;
+    uint64_t ncell = 0;
+    gm::DevArray<uint8_t> base;    // the device table (zeroed at creation)
+    gm::WallTable table;
+    gm::wall::DesignFrame frame;   // fp64, not rounded
+    uint64_t frames = 0;
+    hipStream_t stream = nullptr;  // the small kernels (read / merge / clear / count) and their copies
+    std::vector<uint8_t> pending;  // per slot of ctx: an add was enqueued on its stream since the last sync
+    std::vector<hipEvent_t> adds;  // per slot of ctx: recorded on its stream for a reader on another slot: the adds so far
+    gm::DevArray<uint8_t> stage;   // device staging of the window calls, kStageCells records
+    // the stage calls' per-point outputs: gm_wall_map_add_points' and, beside them, gm_wall_map_check_points'
+    gm::DevArray<float> pt_res;
+    gm::DevArray<int32_t> pt_cell, ck_delta;
+    gm::DevArray<uint8_t> ck_cls;
+    uint32_t points_per_block = 0; // 0: the kernel's default (GM_WALL_POINTS_PER_BLOCK: measurements)
+    // gm_wall_map_regions: the tile (GM_WALL_REGION_TILE: tests, measurements) and the scratch
+    uint32_t region_ts = GM_WALL_REGION_TILE_STATIONS, region_tk = GM_WALL_REGION_TILE_SECTORS;
+    gm::DevArray<uint8_t> rg_cells;    // per window cell: d i64 | parent u32 | slot u32
+    gm::DevArray<unsigned long long> rg_ctr;   // [kWallRegionCounters]
+    gm::DevArray<uint8_t> rg_recs;     // per component: WallRegionAcc | gm_wall_region
+    // gm_wall_map_cloud: the chunk (GM_WALL_CLOUD_CHUNK: tests, measurements; 0: kStageCells blocks) and the scratch
+    uint32_t cloud_chunk = 0;
+    gm::DevArray<uint8_t> cl_acc;      // merged accumulators of a chunk, kWallCloudAccBytes per block (a merging call only)
+    gm::DevArray<gm_wall_cloud_point> cl_stage;   // a chunk's records
+    gm::wall::ScanRecords cl_scan;     // the map's own chained scan
+    gm::DevArray<unsigned long long> cl_ctr;      // [kWallCloudCounters]
+    gm::DevArray<double> cl_dirs;      // [GM_WALL_MAX_SECTORS][2]
+    std::vector<double> cl_dirs_host;          // the table of the call in progress
+    // gm_wall_map_clearance: the chunk (GM_WALL_CLEAR_CHUNK: tests, measurements; 0: kStageCells cells) and the scratch
+    uint32_t clear_chunk = 0;
+    gm::DevArray<int32_t> cr_gauge;    // the uploaded tables [n_gauges][n_sectors]
+    gm::DevArray<uint8_t> cr_station_gauge;        // [n]
+    gm::DevArray<gm_wall_clearance_station> cr_stations;   // [n]
+    gm::DevArray<gm_wall_clearance_cell> cr_stage; // a chunk's list rows
+    gm::wall::ScanRecords cr_scan;     // the list's own chained scan
+    gm::DevArray<unsigned long long> cr_ctr;       // [kWallClearCounters]
+    // gm_wall_map_check_*, _locate_*, _align_*: per slot of ctx
+    std::vector<gm::wall::WallCheckSlot> checks;
+    std::vector<gm::wall::WallLocateSlot> locates;
+    std::vector<gm::wall::WallAlignSlot> aligns;
+    uint32_t align_rows = 0;   // the patch rows per score block (GM_WALL_ALIGN_ROWS: tests, measurements; 0: the default rule)
+    // gm_wall_map_check_objects / gm_wall_check_objects: the tile in blocks (GM_WALL_OBJECT_TILE: tests, measurements) and
+    // the scratch
+    uint32_t object_tr = GM_WALL_OBJECT_TILE_ROWS, object_tc = GM_WALL_OBJECT_TILE_COLS;
+    gm::DevArray<uint32_t> ob_blocks;            // per window block and plane: cnt | parent | slot
+    gm::DevArray<unsigned long long> ob_ctr;     // [kWallObjectCounters]
+    gm::DevArray<uint8_t> ob_recs;               // per component: WallObjectAcc | gm_wall_object | out_slot u32 | pos i32
+    gm::DevArray<gm_wall_check_point> ob_rows;   // the stage call's rows
+    gm::DevArray<int32_t> ob_of_row;             // object_of_row
+    std::vector<gm_wall_object> ob_host;     // the unsorted list, its slots, the sorting permutation, slot -> position
+    std::vector<uint32_t> ob_host_slot, ob_order;
+    std::vector<int32_t> ob_pos;
+};
+
+// ---- gm_wall.hip: what the per-slot calls share with the map's own ----
+
+namespace gm {
+namespace wall {
+
+inline gm_status set_device(gm_ctx *ctx)
+{
+    return hipSetDevice(ctx->device) == hipSuccess ? GM_OK : gm_fail(ctx, GM_ERR_DEVICE, "hipSetDevice failed");
+}
+
+// The head of a frame call `who`, its refusals in their order: NULL map or context, a foreign context, the slot's range,
+// the call's own parameters (prm_ok: run once the three before it hold), a slot without a frame.
+template <class PrmOk>
+gm_status frame_call_head(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, const char *who, PrmOk prm_ok, Slot *&sl)
+{
+    if (!map || !ctx) return GM_ERR_INVALID_ARG;
+    auto refuse = [&](gm_status st, const char *why) { return gm_fail(ctx, st, (std::string(who) + why).c_str()); };
+    if (ctx != map->ctx) return refuse(GM_ERR_INVALID_ARG, ": the map belongs to another context");
+    if (slot >= ctx->n_slots) return gm_fail(ctx, GM_ERR_INVALID_ARG, "slot out of range");
+    if (!prm_ok()) return refuse(GM_ERR_INVALID_ARG, ": struct_size mismatch or a parameter outside its limits");
+    sl = &ctx->slots[slot];
+    return sl->submitted ? GM_OK : refuse(GM_ERR_NOT_READY, ": the slot holds no frame");
+}
+
+// the point fields of a frame call's launch: the frame the slot holds
+inline void frame_points(const gm_ctx *ctx, const Slot &sl, WallArgs &w)
+{
+    w.pts = sl.crop4;
+    w.labels = (ctx->cfg.flags & GM_CFG_RANSAC_PLANE) ? sl.labels : nullptr;   // (label 1 exists with the plane RANSAC only)
+    w.n_ptr = &sl.ctr->n_valid;
+    w.n_host = sl.n_in;
+}
+
+// The per-add frame: pose check, anchor, (o', a', u', v') in sensor coordinates, and the kernel's arguments but for the
+// buffers.  The context's crop bound (a cube around the sensor) sizes the LDS window.
+// f64 (a locate's start): the same vectors before the rounding, and o_f in map coordinates.
+struct WallFrame64 { double c[3], d[3], u[3], v[3], of[3]; };
+gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info *info, WallArgs &w, WallFrame64 *f64 = nullptr);
+
+// A stage call's points (gm_wall_map_add_points, gm_wall_map_check_points, ...) on the staging slot: open, whatever the
+// call enqueues ahead of its points, upload, the call's launch, close.
+struct StageCall {
+    gm_wall_map *map;
+    uint32_t n;
+    float *residual;   // the caller's per-point outputs (NULL: not wanted)
+    int32_t *cell, *delta;
+    uint8_t *cls;
+    Slot *sl = nullptr;
+    gm_status open();    // the slot, its capacity and the device side of the per-point outputs; nothing is enqueued
+    gm_status upload(const float *xyz, const uint8_t *labels, WallArgs &w);   // points and labels onto the slot's stream; w: the point fields of the launch
+    gm_status close();   // the per-point outputs back, behind the launch; blocks until the slot's stream has drained
+};
+
+#endif  // GM_WALL_HOST_ONLY
+}  // namespace wall
+}  // namespace gm

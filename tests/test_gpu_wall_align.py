@@ -1,4 +1,4 @@
-"""GPU tests of the wall-map align (gm_wall_map_align_*, csrc/k_wall_align.hip + gm_wall.hip): the table, the counts and
+"""GPU tests of the wall-map align (gm_wall_map_align_*, csrc/k_wall_align.hip + gm_wall_slot.hip): the table, the counts and
 the info integers against the exact twin (tests/wall_align_np.py) fed the device's own (cell, e) pairs and read_raw, at every
 frame size where the bin kernel takes another path and at the edges of the score kernel; the table's independence of the
 block shape; the truth of shifted poses; the ambiguity on a smooth wall; what an align is for (the check it repairs); the

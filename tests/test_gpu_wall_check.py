@@ -1,4 +1,4 @@
-"""GPU tests of the wall-map check (gm_wall_map_check_*, csrc/k_wall_check.hip + gm_wall.hip): every size and tile edge
+"""GPU tests of the wall-map check (gm_wall_map_check_*, csrc/k_wall_check.hip + gm_wall_slot.hip): every size and tile edge
 byte for byte against the integer twin (tests/wall_check_np.py) on the device's own per-point (e, cell) pairs, all / none
 changed, analytic truth of a drive with world-fixed patches, the frame path against the stage path over every pipeline
 path and the ordering rule, independence of the chainage, the results' lifetime and the failures."""

@@ -1,4 +1,4 @@
-"""GPU tests of the wall-map locate (gm_wall_map_locate_*, csrc/k_wall_locate.hip + gm_wall.hip): every size at which the
+"""GPU tests of the wall-map locate (gm_wall_map_locate_*, csrc/k_wall_locate.hip + gm_wall_slot.hip): every size at which the
 fixed grid takes another path against the fp64 twin (tests/wall_locate_np.py) fed the frames the device reported, the
 truth of a drive located from perturbed poses, the failures, and the frame path against the stage path over every
 pipeline path and the ordering rule."""

@@ -1,5 +1,5 @@
 """GPU tests of the check's objects (gm_wall_map_check_objects / gm_wall_check_objects, csrc/k_wall_objects.hip +
-gm_wall.hip): crafted rows through the stage call at every row count, grid, shape, threshold, window and tie edge, byte
+gm_wall_slot.hip): crafted rows through the stage call at every row count, grid, shape, threshold, window and tie edge, byte
 for byte against the integer twin (tests/wall_objects_np.py: info, records, object_of_row); independence of the tile shape
 and of the row order; the slot call against the stage call over every pipeline path; analytic truth of a drive with
 world-fixed patches; the results' lifetime and the refusals."""

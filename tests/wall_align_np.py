@@ -1,4 +1,4 @@
-"""Twin of the wall-map align (gm_wall_map_align_*, csrc/k_wall_align.hip + gm_wall.hip; include/gm_hip.h states the rule).
+"""Twin of the wall-map align (gm_wall_map_align_*, csrc/k_wall_align.hip + gm_wall_slot.hip; include/gm_hip.h states the rule).
 
 Everything from a point's residual on is integer, so this twin is exact: patch_from() bins the device's own per-point
 (e, cell) pairs as wall_np.cells_from does for the add, values() and table() are the integer rule in numpy int64 (every

@@ -1,4 +1,4 @@
-"""numpy twin of the wall-map check (gm_wall_map_check_*, csrc/k_wall_check.hip + gm_wall.hip; include/gm_hip.h states
+"""numpy twin of the wall-map check (gm_wall_map_check_*, csrc/k_wall_check.hip + gm_wall_slot.hip; include/gm_hip.h states
 it).  The rule is integer from e on, so the twin is exact: classify() applies it to per-point (e fp32, cell) pairs -- the
 per-point outputs of an add or a check under the same pose and gate -- and a raw-cell table (wall_np.RAW_CELL, the
 checked map's read_raw()); check() builds the info and the records from it.

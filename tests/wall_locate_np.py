@@ -1,4 +1,4 @@
-"""fp64 numpy twin of the wall-map locate (gm_wall_map_locate_*, csrc/k_wall_locate.hip + gm_wall.hip; include/gm_hip.h
+"""fp64 numpy twin of the wall-map locate (gm_wall_map_locate_*, csrc/k_wall_locate.hip + gm_wall_slot.hip; include/gm_hip.h
 states the rule).
 
 one_pass() is one Gauss-Newton pass in fp64 on the fp32 frame a pass REPORTED (as wall_np.points does for the add): the

@@ -1,5 +1,5 @@
 """numpy twin of the check's objects (gm_wall_map_check_objects / gm_wall_check_objects, csrc/k_wall_objects.hip +
-gm_wall.hip; include/gm_hip.h states the rule).  Integer from the decoding of a row on, so the device must reproduce it
+gm_wall_slot.hip; include/gm_hip.h states the rule).  Integer from the decoding of a row on, so the device must reproduce it
 byte for byte: info, records, object_of_row.
 
 For rows (wall_check_np.POINT), the map's n_stations and n_sectors, an anchor station and the parameters:
