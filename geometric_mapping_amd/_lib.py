@@ -69,6 +69,11 @@ GM_WALL_OBJECT_TILE = (64, 64)   # block rows x block columns: the object labell
 GM_WALL_CHECK_MEAN, GM_WALL_CHECK_ENVELOPE = 0, 1
 GM_WALL_CLEAR_MIN, GM_WALL_CLEAR_MEAN = 0, 1
 GM_WALL_CLEAR_MAX_GAUGES = 256
+GM_SECTION_OK = 0
+GM_SECTION_TOO_FEW, GM_SECTION_SINGULAR, GM_SECTION_UNBOUNDED = 1 << 0, 1 << 1, 1 << 2
+GM_SECTION_FAILED_MASK = 0xFF
+GM_SECTION_OPEN_ARC = 1 << 8
+GM_WALL_SECTION_MAX_HARMONICS, GM_WALL_SECTION_MAX_PASSES = 4, 4
 GM_WALL_GAUGE_MAX_VERTICES = 4096
 GM_WALL_LOCATE_DESIGN, GM_WALL_LOCATE_MAP = 0, 1
 GM_LOCATE_OK = 0
@@ -234,6 +239,38 @@ class WallClearanceRun(C.Structure):
                 ("infringed", C.c_uint64)]
 
 
+class WallSectionParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("section_stations", C.c_uint32), ("harmonics", C.c_uint32), ("passes", C.c_uint32),
+                ("min_count", C.c_uint32), ("min_columns", C.c_uint32), ("max_gap_deg", C.c_double), ("reject", C.c_double)]
+
+
+class WallSectionSums(C.Structure):
+    _fields_ = [("N", C.c_int64 * 45), ("r", C.c_int64 * 9), ("fitted", C.c_uint32), ("largest_gap", C.c_uint32),
+                ("points", C.c_uint64)]
+
+
+class WallSection(C.Structure):
+    _fields_ = [("station_from", C.c_uint32), ("stations", C.c_uint32), ("status", C.c_uint32), ("usable", C.c_uint32),
+                ("fitted", C.c_uint32), ("accepted", C.c_uint32), ("rejected", C.c_uint32), ("largest_gap", C.c_uint32),
+                ("points", C.c_uint64), ("coef_q", C.c_int64 * 9), ("rss", C.c_uint64), ("peak_out", C.c_int64),
+                ("peak_in", C.c_int64), ("peak_out_sector", C.c_uint32), ("peak_in_sector", C.c_uint32)]
+
+
+class WallSectionsInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("station0", C.c_uint32), ("n_stations", C.c_uint32), ("n_sectors", C.c_uint32),
+                ("section_stations", C.c_uint32), ("sections", C.c_uint32), ("harmonics", C.c_uint32), ("passes", C.c_uint32),
+                ("reject_q", C.c_int64), ("max_gap_sectors", C.c_uint32), ("sections_ok", C.c_uint32),
+                ("sections_failed", C.c_uint32), ("sections_open_arc", C.c_uint32), ("empty", C.c_uint64),
+                ("unusable", C.c_uint64), ("usable", C.c_uint64), ("accepted", C.c_uint64), ("rejected", C.c_uint64)]
+
+
+class WallSectionMetrics(C.Structure):
+    _fields_ = [("chainage_from", C.c_double), ("chainage_to", C.c_double), ("radius_m", C.c_double), ("radial_m", C.c_double),
+                ("centre_u", C.c_double), ("centre_v", C.c_double), ("centre", C.c_double * 3), ("oval_m", C.c_double),
+                ("oval_angle_deg", C.c_double), ("diameter_max", C.c_double), ("diameter_min", C.c_double),
+                ("rms_m", C.c_double), ("area_m2", C.c_double), ("coverage", C.c_double)]
+
+
 class WallCheckParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reference", C.c_uint32), ("min_count", C.c_uint32), ("reserved", C.c_uint32),
                 ("threshold", C.c_double), ("gate", C.c_double)]
@@ -384,6 +421,8 @@ def load():
     wcprmp, wcptp, wcinfop = C.POINTER(WallCloudParams), C.POINTER(WallCloudPoint), C.POINTER(WallCloudInfo)
     wgprmp, wgstp, wgcellp, wginfop, wgrunp = (C.POINTER(WallClearanceParams), C.POINTER(WallClearanceStation),
                                                C.POINTER(WallClearanceCell), C.POINTER(WallClearanceInfo), C.POINTER(WallClearanceRun))
+    wsprmp, wssump, wssecp, wsinfop, wsmetp = (C.POINTER(WallSectionParams), C.POINTER(WallSectionSums), C.POINTER(WallSection),
+                                               C.POINTER(WallSectionsInfo), C.POINTER(WallSectionMetrics))
     wkprmp, wkptp, wkinfop = C.POINTER(WallCheckParams), C.POINTER(WallCheckPoint), C.POINTER(WallCheckInfo)
     wlprmp, wlinfop = C.POINTER(WallLocateParams), C.POINTER(WallLocateInfo)
     waprmp, wascp, wainfop = C.POINTER(WallAlignParams), C.POINTER(WallAlignScore), C.POINTER(WallAlignInfo)
@@ -458,6 +497,12 @@ def load():
         "gm_wall_map_clearance": (C.c_int, [vp, u32, u32, i32p, u32, u8p, wgprmp, wginfop, wgstp, u32, wgcellp, u64, u64p]),
         "gm_wall_gauge_from_polygon": (C.c_int, [wprmp, dp, u32, dp, i32p, u32, u32p]),
         "gm_wall_clearance_runs": (C.c_int, [wprmp, wgstp, u32, u32, u32, wgrunp, u32, u32p]),
+        "gm_wall_section_default_params": (None, [wsprmp]),
+        "gm_wall_section_check_params": (C.c_int, [wsprmp]),
+        "gm_wall_section_basis": (C.c_int, [u32, u32, i32p, u32, u32p]),
+        "gm_wall_section_solve": (C.c_int, [wssump, u32, u32, C.POINTER(C.c_int64), u32p]),
+        "gm_wall_section_metrics": (C.c_int, [wprmp, wssecp, u32, wsmetp]),
+        "gm_wall_map_sections": (C.c_int, [vp, vp, u32, u32, wsprmp, wsinfop, wssecp, u32, u32p, wssump]),
         "gm_wall_check_default_params": (None, [wkprmp]),
         "gm_wall_check_classify": (C.c_int, [wkprmp, wrawp, C.c_float, C.POINTER(C.c_int64), u32p]),
         "gm_wall_map_check_frame": (C.c_int, [vp, vp, u32, dp, wkprmp, waddp]),

@@ -708,6 +708,67 @@ def wall_clearance_runs(prm, stations, station0=0, max_gap=0):
     return runs[:int(got.value)].copy()
 
 
+WALL_SECTION = np.dtype([("station_from", "<u4"), ("stations", "<u4"), ("status", "<u4"), ("usable", "<u4"), ("fitted", "<u4"),
+                         ("accepted", "<u4"), ("rejected", "<u4"), ("largest_gap", "<u4"), ("points", "<u8"),
+                         ("coef_q", "<i8", (9,)), ("rss", "<u8"), ("peak_out", "<i8"), ("peak_in", "<i8"),
+                         ("peak_out_sector", "<u4"), ("peak_in_sector", "<u4")])   # gm_wall_section, 144 bytes
+WALL_SECTION_SUMS = np.dtype([("N", "<i8", (45,)), ("r", "<i8", (9,)), ("fitted", "<u4"), ("largest_gap", "<u4"),
+                              ("points", "<u8")])   # gm_wall_section_sums, 448 bytes
+_SECTIONS_INFO = ("station0", "n_stations", "n_sectors", "section_stations", "sections", "harmonics", "passes", "reject_q",
+                  "max_gap_sectors", "sections_ok", "sections_failed", "sections_open_arc", "empty", "unusable", "usable",
+                  "accepted", "rejected")
+
+
+def _wall_section_params(**kw):
+    p = _lib.WallSectionParams()
+    _lib.load().gm_wall_section_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k == "struct_size":
+            raise TypeError(f"unknown section parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def wall_section_basis(n_sectors, harmonics=2):
+    """gm_wall_section_basis (host only): the int32 (n_sectors, 1 + 2 harmonics) table gm_wall_map_sections uses."""
+    L = _lib.load()
+    got = C.c_uint32(0)
+    st = L.gm_wall_section_basis(int(n_sectors), int(harmonics), None, 0, C.byref(got))
+    if st != _lib.GM_OK:
+        raise _lib.GmError(st, "gm_wall_section_basis refused its arguments")
+    out = np.zeros(int(got.value), dtype=np.int32)
+    st = L.gm_wall_section_basis(int(n_sectors), int(harmonics), out.ctypes.data_as(C.POINTER(C.c_int32)), len(out), C.byref(got))
+    if st != _lib.GM_OK:
+        raise _lib.GmError(st, "gm_wall_section_basis failed")
+    return out.reshape(int(n_sectors), 1 + 2 * int(harmonics))
+
+
+def wall_section_solve(sums, harmonics=2, min_columns=24):
+    """gm_wall_section_solve (host only): (coef_q int64 [9], status) of one WALL_SECTION_SUMS record."""
+    s = np.ascontiguousarray(np.asarray(sums, dtype=WALL_SECTION_SUMS).reshape(1))
+    cq = np.zeros(9, dtype=np.int64)
+    status = C.c_uint32(0)
+    st = _lib.load().gm_wall_section_solve(s.ctypes.data_as(C.POINTER(_lib.WallSectionSums)), int(harmonics), int(min_columns),
+                                           cq.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(status))
+    if st != _lib.GM_OK:
+        raise _lib.GmError(st, "gm_wall_section_solve refused its arguments")
+    return cq, int(status.value)
+
+
+def wall_section_metrics(prm, section, harmonics=2):
+    """gm_wall_section_metrics (host only): the fp64 metrics dict (centre as float64 [3]) of one WALL_SECTION record under
+    the gm_wall_params `prm`."""
+    r = np.ascontiguousarray(np.asarray(section, dtype=WALL_SECTION).reshape(1))
+    out = _lib.WallSectionMetrics()
+    st = _lib.load().gm_wall_section_metrics(C.byref(prm), r.ctypes.data_as(C.POINTER(_lib.WallSection)), int(harmonics),
+                                             C.byref(out))
+    if st != _lib.GM_OK:
+        raise _lib.GmError(st, "gm_wall_section_metrics refused the record")
+    d = {k: float(getattr(out, k)) for k, _t in _lib.WallSectionMetrics._fields_ if k != "centre"}
+    d["centre"] = np.array(out.centre[:], dtype=np.float64)
+    return d
+
+
 def _wall_cloud_params(**kw):
     p = _lib.WallCloudParams()
     _lib.load().gm_wall_cloud_default_params(C.byref(p))
@@ -967,6 +1028,44 @@ class WallMap:
                 st.ctypes.data_as(C.POINTER(_lib.WallClearanceStation)), n,
                 cells.ctypes.data_as(C.POINTER(_lib.WallClearanceCell)), cap, C.byref(got)))
         return {k: int(getattr(info, k)) for k in _CLEARANCE_INFO}, st[:n].copy(), cells[:int(got.value)].copy()
+
+    @staticmethod
+    def section_params(**kw):
+        """gm_wall_section_params with the library's defaults, then the keywords (section_stations, harmonics, passes,
+        min_count, min_columns, max_gap_deg, reject)."""
+        return _wall_section_params(**kw)
+
+    def sections(self, station0=0, n=None, baseline=None, sums=False, **params):
+        """gm_wall_map_sections: the profile fit per section of stations [station0, station0 + n) against the design or,
+        with `baseline` (another WallMap of this context on the same grid), against that earlier epoch.  Returns
+        (info dict, WALL_SECTION records, WALL_SECTION_SUMS records of the last fitting pass or None)."""
+        s0, n = self._window(station0, n)
+        p = self.section_params(**params)
+        bh = baseline._h() if baseline is not None else None
+        info = _lib.WallSectionsInfo()
+        got = C.c_uint32(0)
+        S = max(int(p.section_stations), 1)
+        cap = (n + S - 1) // S
+        rec = np.zeros(max(cap, 1), dtype=WALL_SECTION)
+        sm = np.zeros(max(cap, 1), dtype=WALL_SECTION_SUMS) if sums else None
+        self._ctx._check(self._L.gm_wall_map_sections(
+            self._h(), bh, s0, n, C.byref(p), C.byref(info), rec.ctypes.data_as(C.POINTER(_lib.WallSection)), cap, C.byref(got),
+            sm.ctypes.data_as(C.POINTER(_lib.WallSectionSums)) if sums else None))
+        ns = int(got.value)
+        return {k: int(getattr(info, k)) for k in _SECTIONS_INFO}, rec[:ns].copy(), (sm[:ns].copy() if sums else None)
+
+    def section_basis(self, harmonics=2):
+        """gm_wall_section_basis for this map's n_sectors."""
+        return wall_section_basis(self.n_sectors, harmonics)
+
+    @staticmethod
+    def section_solve(sums, harmonics=2, min_columns=24):
+        """gm_wall_section_solve (host only)."""
+        return wall_section_solve(sums, harmonics, min_columns)
+
+    def section_metrics(self, section, harmonics=2):
+        """gm_wall_section_metrics of one WALL_SECTION record under this map's parameters."""
+        return wall_section_metrics(self.prm, section, harmonics)
 
     @staticmethod
     def check_params(**kw):

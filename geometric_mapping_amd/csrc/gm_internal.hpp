@@ -503,6 +503,45 @@ __host__ __device__ inline uint32_t wall_clear_class(long long c, long long T)
 {
     return c < 0 ? kWallClearInfringed : (c < T ? kWallClearTight : kWallClearClear);
 }
+// k_wall_sections.hip (gm_wall_map_sections): one kernel, launched once per fitting pass and once more for the evaluation
+constexpr uint32_t kWallSectionCoefs = 9;                   // P <= 1 + 2 GM_WALL_SECTION_MAX_HARMONICS
+constexpr long long kWallSectionSat = 1ll << 24;            // |m| and |c_q| end here
+constexpr long long kWallSectionBias = 1ll << 29;           // |rho| < 2^29: |m| <= 2^24, |M| <= 9 2^24 + 1
+struct WallSectionModel {   // 80 B per section, host -> device before every launch
+    long long c[kWallSectionCoefs];   // c_q of the pass before (0 before pass 1)
+    long long alive;                  // 0: the section has failed, the launch leaves its record alone
+};
+struct WallSectionOut {     // 512 B per section, device -> host behind every launch
+    gm_wall_section_sums sums;        // over the SELECTED columns (N and r: fitting launches only)
+    unsigned long long rss;           // sum rho^2 over the selected columns (meaningful with a threshold <= 2^23)
+    long long peak_out, peak_in;      // over the usable columns; 0 without one
+    uint32_t peak_out_sector, peak_in_sector;   // 0xFFFFFFFF without one
+    uint32_t empty, unusable, usable, pad0;
+    unsigned long long pad1[2];
+};
+struct WallSectionArgs {
+    WallTable map, base;       // base: the baseline's table when has_base
+    uint32_t has_base;
+    uint32_t n, nsec;          // the window's stations, the map's sectors
+    uint64_t first;            // station0 * nsec: map-wide index of window cell 0
+    uint32_t S, P;             // section_stations, 1 + 2 harmonics
+    uint32_t sec0, nsect;      // the chunk: sections [sec0, sec0 + nsect)
+    uint32_t min_count, fit;   // fit 1: N and r are summed (a fitting pass); 0: the evaluation
+    long long thr;             // selected: usable and |rho| <= thr (pass 1: above every |rho|)
+    const int32_t *basis;      // [nsec][P]
+    const WallSectionModel *model;   // [nsect]
+    WallSectionOut *out;       // [nsect]
+};
+void launch_wall_sections(const WallSectionArgs &a, hipStream_t s);
+// the rule's integers, shared by the kernel and the host
+__host__ __device__ inline long long wall_section_value(long long sum, unsigned long long count)   // count >= 1
+{
+    return sum / (long long)count;
+}
+__host__ __device__ inline long long wall_section_sat(long long m)
+{
+    return m > kWallSectionSat ? kWallSectionSat : (m < -kWallSectionSat ? -kWallSectionSat : m);
+}
 // k_wall_objects.hip (gm_wall_map_check_objects, gm_wall_check_objects): bin -> tiles -> seams -> flatten | blocks ->
 // reduce -> select | rows
 constexpr uint32_t kWallObjectTileBlocks = 4096;      // the most window blocks of a tile (its LDS tables)

@@ -159,6 +159,22 @@ gm_status check_window(gm_wall_map *m, uint32_t station0, uint32_t n, uint64_t c
     return GM_OK;
 }
 
+// the refusals of a baseline (NULL: none) in the call `who`: the map itself, another context, another grid
+gm_status check_baseline(gm_wall_map *map, gm_wall_map *baseline, const char *who)
+{
+    if (!baseline) return GM_OK;
+    gm_ctx *ctx = map->ctx;
+    auto refuse = [&](const char *why) { return gm_fail(ctx, GM_ERR_INVALID_ARG, (std::string(who) + why).c_str()); };
+    if (baseline == map) return refuse(": the baseline is the map itself");
+    if (baseline->ctx != ctx) return refuse(": the baseline belongs to another context");
+    const gm_wall_params &p = map->prm, &b = baseline->prm;
+    if (p.n_stations != b.n_stations || p.n_sectors != b.n_sectors || memcmp(&p.station_length, &b.station_length, 8) ||
+        memcmp(&p.t_min, &b.t_min, 8) || memcmp(p.point, b.point, 24) || memcmp(p.direction, b.direction, 24) ||
+        memcmp(&p.radius, &b.radius, 8) || memcmp(p.up, b.up, 24) || memcmp(p.forward, b.forward, 24))
+        return refuse(": the baseline is a map on another grid");
+    return GM_OK;
+}
+
 void free_map(gm_wall_map *m)
 {
     gm_ctx *ctx = m->ctx;
@@ -261,6 +277,10 @@ gm_status gm_wall_map_create(gm_ctx *ctx, const gm_wall_params *params, gm_wall_
     if (const char *e = getenv("GM_WALL_CLOUD_CHUNK")) {   // blocks; 0 or more than the default: the default (scratch is sized by it)
         const unsigned long long v = strtoull(e, nullptr, 10);
         m->cloud_chunk = v < kStageCells ? (uint32_t)v : 0u;
+    }
+    if (const char *e = getenv("GM_WALL_SECTION_CHUNK")) {   // sections; 0 or more than the default: the default (scratch is sized by it)
+        const unsigned long long v = strtoull(e, nullptr, 10);
+        m->section_chunk = v < kSectionChunk ? (uint32_t)v : 0u;
     }
     if (const char *e = getenv("GM_WALL_CLEAR_CHUNK")) {   // cells; 0 or more than the default: the default (scratch is sized by it)
         const unsigned long long v = strtoull(e, nullptr, 10);
@@ -422,15 +442,7 @@ gm_status gm_wall_map_regions(gm_wall_map *map, gm_wall_map *baseline, uint32_t 
     const long long T = (long long)rint(rp.threshold * 1048576.0);
     if (T < 1) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_regions: the threshold rounds to 0");
     if (!regions && capacity) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_regions: NULL regions with a capacity");
-    if (baseline) {
-        if (baseline == map) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_regions: the baseline is the map itself");
-        if (baseline->ctx != ctx) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_regions: the baseline belongs to another context");
-        const gm_wall_params &p = map->prm, &b = baseline->prm;
-        if (p.n_stations != b.n_stations || p.n_sectors != b.n_sectors || memcmp(&p.station_length, &b.station_length, 8) ||
-            memcmp(&p.t_min, &b.t_min, 8) || memcmp(p.point, b.point, 24) || memcmp(p.direction, b.direction, 24) ||
-            memcmp(&p.radius, &b.radius, 8) || memcmp(p.up, b.up, 24) || memcmp(p.forward, b.forward, 24))
-            return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_regions: the baseline is a map on another grid");
-    }
+    GMW_OK(check_baseline(map, baseline, "gm_wall_map_regions"));
     GMW_OK(check_window(map, station0, n, ~0ull, nullptr, ""));
     GMW_OK(sync_map(map));
     if (baseline) GMW_OK(sync_map(baseline));
@@ -721,6 +733,144 @@ gm_status gm_wall_map_clearance(gm_wall_map *map, uint32_t station0, uint32_t n,
         done += got;
     }
     if (done != total) return gm_fail(ctx, GM_ERR_DEVICE, "gm_wall_map_clearance: the list disagrees with the totals");
+    return GM_OK;
+}
+
+gm_status gm_wall_map_sections(gm_wall_map *map, gm_wall_map *baseline, uint32_t station0, uint32_t n,
+                               const gm_wall_section_params *prm, gm_wall_sections_info *info, gm_wall_section *sections,
+                               uint32_t capacity, uint32_t *n_out, gm_wall_section_sums *sums)
+{
+    if (!map) return GM_ERR_INVALID_ARG;
+    gm_ctx *ctx = map->ctx;
+    if (n_out) *n_out = 0;
+    if (!info) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_sections: NULL info");
+    const gm_wall_section_params sp = params_or(prm, gm_wall_section_default_params);
+    long long Tr;
+    if (!section_prm_ok(sp, Tr))
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_sections: struct_size mismatch or a parameter outside its limits");
+    if (!sections && (capacity || sums))
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_sections: NULL sections with a capacity or with sums");
+    GMW_OK(check_baseline(map, baseline, "gm_wall_map_sections"));
+    GMW_OK(check_window(map, station0, n, ~0ull, nullptr, ""));
+    GMW_OK(sync_map(map));
+    if (baseline) GMW_OK(sync_map(baseline));
+    const uint32_t nsec = map->prm.n_sectors, S = sp.section_stations, H = sp.harmonics, P = 1u + 2u * H, Pf = sp.passes;
+    const uint32_t NS = n ? (n - 1u) / S + 1u : 0u;
+    memset(info, 0, sizeof(*info));
+    info->struct_size = (uint32_t)sizeof(gm_wall_sections_info);
+    info->station0 = station0;
+    info->n_stations = n;
+    info->n_sectors = nsec;
+    info->section_stations = S;
+    info->sections = NS;
+    info->harmonics = H;
+    info->passes = Pf;
+    info->reject_q = Tr;
+    info->max_gap_sectors = (uint32_t)floor(sp.max_gap_deg * (double)nsec / 360.0);
+    if (n_out) *n_out = NS;
+    if (!n) return GM_OK;
+    if (sections && capacity < NS) return gm_fail(ctx, GM_ERR_CAPACITY, "gm_wall_map_sections: section buffer too small");
+
+    const uint32_t cs = std::min(map->section_chunk ? map->section_chunk : kSectionChunk, NS);   // sections of a full chunk
+    GMW_HIP(ctx, map->sc_basis.reserve((uint64_t)nsec * P));
+    GMW_HIP(ctx, map->sc_chunk.reserve((uint64_t)cs * (sizeof(WallSectionModel) + sizeof(WallSectionOut))));
+    map->sc_basis_host.resize((size_t)nsec * P);
+    section_basis(nsec, H, map->sc_basis_host.data());
+    GMW_HIP(ctx, hipMemcpyAsync(map->sc_basis.p, map->sc_basis_host.data(), (size_t)nsec * P * sizeof(int32_t), hipMemcpyHostToDevice,
+                                map->stream));
+    Carve chunk{map->sc_chunk.p};
+    WallSectionArgs a;
+    memset(&a, 0, sizeof(a));
+    a.map = map->table;
+    a.has_base = baseline ? 1u : 0u;
+    a.base = baseline ? baseline->table : map->table;
+    a.n = n; a.nsec = nsec;
+    a.first = (uint64_t)station0 * nsec;
+    a.S = S; a.P = P;
+    a.min_count = sp.min_count;
+    a.basis = map->sc_basis.p;
+    WallSectionModel *d_model = chunk.take<WallSectionModel>(cs);
+    WallSectionOut *d_out = chunk.take<WallSectionOut>(cs);
+    a.model = d_model;
+    a.out = d_out;
+
+    std::vector<WallSectionModel> &model = map->sc_model_host;
+    std::vector<WallSectionOut> &out = map->sc_out_host;
+    std::vector<gm_wall_section> rec;
+    for (uint32_t sec0 = 0; sec0 < NS; sec0 += cs) {   // (the trip count depends on the window alone)
+        const uint32_t ns = std::min(cs, NS - sec0);
+        a.sec0 = sec0;
+        a.nsect = ns;
+        WallSectionModel fresh;
+        memset(&fresh, 0, sizeof(fresh));
+        fresh.alive = 1;
+        model.assign(ns, fresh);
+        out.resize(ns);
+        gm_wall_section zero;
+        memset(&zero, 0, sizeof(zero));
+        rec.assign(ns, zero);
+        uint32_t alive = ns;
+        for (uint32_t pass = 1; pass <= Pf + 1u && alive; ++pass) {   // Pf fitting passes, then the evaluation
+            const bool eval = pass == Pf + 1u;
+            a.fit = eval ? 0u : 1u;
+            a.thr = pass == 1u ? INT64_MAX : (eval ? Tr : Tr << (Pf - pass));
+            GMW_HIP(ctx, hipMemcpyAsync(d_model, model.data(), (size_t)ns * sizeof(WallSectionModel), hipMemcpyHostToDevice, map->stream));
+            launch_wall_sections(a, map->stream);
+            GMW_HIP(ctx, hipGetLastError());
+            GMW_HIP(ctx, hipMemcpyAsync(out.data(), d_out, (size_t)ns * sizeof(WallSectionOut), hipMemcpyDeviceToHost, map->stream));
+            GMW_HIP(ctx, hipStreamSynchronize(map->stream));
+            for (uint32_t i = 0; i < ns; ++i) {
+                if (!model[i].alive) continue;
+                const WallSectionOut &o = out[i];
+                gm_wall_section &r = rec[i];
+                if (pass == 1u) {
+                    r.usable = o.usable;
+                    info->empty += o.empty;
+                    info->unusable += o.unusable;
+                    info->usable += o.usable;
+                }
+                if (eval) {
+                    r.accepted = o.sums.fitted;
+                    r.rejected = r.usable - r.accepted;
+                    r.points = o.sums.points;
+                    r.rss = o.rss;
+                    r.peak_out = o.peak_out;
+                    r.peak_in = o.peak_in;
+                    r.peak_out_sector = o.peak_out_sector;
+                    r.peak_in_sector = o.peak_in_sector;
+                    continue;
+                }
+                r.fitted = o.sums.fitted;
+                r.largest_gap = o.sums.largest_gap;
+                if (sums) sums[sec0 + i] = o.sums;
+                r.status = section_solve(o.sums, H, sp.min_columns, r.coef_q);   // (a failed solve leaves the coefficients 0)
+                if (r.status) {
+                    model[i].alive = 0;
+                    --alive;
+                }
+                memcpy(model[i].c, r.coef_q, sizeof(r.coef_q));
+            }
+        }
+        for (uint32_t i = 0; i < ns; ++i) {
+            gm_wall_section &r = rec[i];
+            const uint32_t j0 = (sec0 + i) * S;   // < n
+            r.station_from = station0 + j0;
+            r.stations = n - j0 < S ? n - j0 : S;
+            if (r.status) {
+                r.peak_out_sector = r.peak_in_sector = UINT32_MAX;
+                ++info->sections_failed;
+            } else {
+                ++info->sections_ok;
+                info->accepted += r.accepted;
+                info->rejected += r.rejected;
+            }
+            if (r.largest_gap > info->max_gap_sectors) {
+                r.status |= GM_SECTION_OPEN_ARC;
+                ++info->sections_open_arc;
+            }
+        }
+        if (sections) memcpy(sections + sec0, rec.data(), (size_t)ns * sizeof(gm_wall_section));
+    }
     return GM_OK;
 }
 

@@ -1,7 +1,8 @@
 // gm_wall_host.hip -- the part of the wall map's C ABI that needs no device (include/gm_hip.h states each rule): the
 // defaults, the parameter checks, the classification of one cell, the metrics, the direction table, the gauge of a polygon,
-// the runs, the align's selection.  No device call, no context, no map: it links against libm and the C++ library alone,
-// and host/gm_wall_host_test.cpp runs it under the host sanitizers.
+// the runs, the align's selection, the sections' basis, solve and metrics.  No device call, no context, no map: it links
+// against libm and the C++ library alone, and host/gm_wall_host_test.cpp and host/gm_wall_sections_host_test.cpp run it
+// under the host sanitizers.
 #include <vector>
 
 #define GM_WALL_HOST_ONLY
@@ -113,6 +114,102 @@ bool clearance_ok(const gm_wall_params *p, const gm_wall_clearance_params &c, co
     T = (long long)rint(c.margin * 1048576.0);
     Rq = (long long)rq;
     return true;
+}
+
+bool section_prm_ok(const gm_wall_section_params &p, long long &Tr)
+{
+    Tr = 0;
+    if (p.struct_size != sizeof(gm_wall_section_params) || p.section_stations < 1u || p.harmonics > GM_WALL_SECTION_MAX_HARMONICS ||
+        p.passes < 1u || p.passes > GM_WALL_SECTION_MAX_PASSES || p.min_count < 1u || p.min_columns < 1u)
+        return false;
+    if (!(p.max_gap_deg >= 0.0) || !(p.max_gap_deg <= 360.0) || !(p.reject > 0.0) || !(p.reject <= 8.0)) return false;
+    Tr = (long long)rint(p.reject * 1048576.0);
+    return Tr >= 1;
+}
+
+void section_basis(uint32_t nsec, uint32_t H, int32_t *B)
+{
+    const uint32_t P = 1u + 2u * H;
+    const double den = (double)(2u * nsec);
+    for (uint32_t k = 0; k < nsec; ++k) {
+        const double f = (double)(2u * k + 1u) / den;
+        const double phi = kTwoPi * f;
+        int32_t *row = B + (size_t)k * P;
+        row[0] = 1 << 20;
+        for (uint32_t h = 1; h <= H; ++h) {
+            const double ang = (double)h * phi;
+            const double c = cos(ang);
+            const double s = sin(ang);
+            const double cs = c * 1048576.0;
+            const double ss = s * 1048576.0;
+            row[2u * h - 1u] = (int32_t)rint(cs);
+            row[2u * h] = (int32_t)rint(ss);
+        }
+    }
+}
+
+uint32_t section_solve(const gm_wall_section_sums &s, uint32_t H, uint32_t min_columns, int64_t cq[9])
+{
+    const uint32_t P = 1u + 2u * H;
+    for (int p = 0; p < 9; ++p) cq[p] = 0;
+    if (s.fitted < std::max(min_columns, P)) return GM_SECTION_TOO_FEW;
+    // one operation per statement: the same roundings as the twin's, whatever the compiler may contract
+    double A[9][9], L[9][9], b[9], y[9], c[9];
+    uint32_t idx = 0;
+    for (uint32_t p = 0; p < P; ++p)
+        for (uint32_t q = p; q < P; ++q) {
+            const double v = (double)s.N[idx++];
+            A[p][q] = v * 0x1p-40;
+            A[q][p] = A[p][q];
+        }
+    for (uint32_t p = 0; p < P; ++p) {
+        const double v = (double)s.r[p];
+        b[p] = v * 0x1p-20;
+    }
+    for (uint32_t j = 0; j < P; ++j) {
+        double d = A[j][j];
+        for (uint32_t k = 0; k < j; ++k) {
+            const double t = L[j][k] * L[j][k];
+            d = d - t;
+        }
+        const double lim = 1e-12 * A[j][j];
+        if (!(d > lim)) return GM_SECTION_SINGULAR;
+        const double ljj = sqrt(d);
+        L[j][j] = ljj;
+        for (uint32_t i = j + 1u; i < P; ++i) {
+            double v = A[i][j];
+            for (uint32_t k = 0; k < j; ++k) {
+                const double t = L[i][k] * L[j][k];
+                v = v - t;
+            }
+            L[i][j] = v / ljj;
+        }
+    }
+    for (uint32_t i = 0; i < P; ++i) {
+        double v = b[i];
+        for (uint32_t k = 0; k < i; ++k) {
+            const double t = L[i][k] * y[k];
+            v = v - t;
+        }
+        y[i] = v / L[i][i];
+    }
+    for (uint32_t i = P; i-- > 0u;) {
+        double v = y[i];
+        for (uint32_t k = i + 1u; k < P; ++k) {
+            const double t = L[k][i] * c[k];
+            v = v - t;
+        }
+        c[i] = v / L[i][i];
+    }
+    for (uint32_t p = 0; p < P; ++p) {
+        const double rc = rint(c[p]);
+        if (!(fabs(rc) <= 16777216.0)) {
+            for (int q = 0; q < 9; ++q) cq[q] = 0;
+            return GM_SECTION_UNBOUNDED;
+        }
+        cq[p] = (int64_t)rc;
+    }
+    return GM_SECTION_OK;
 }
 
 bool check_prm_ok(const gm_wall_check_params &c, long long &T)
@@ -490,6 +587,111 @@ gm_status gm_wall_cloud_directions(const gm_wall_params *p, const gm_wall_cloud_
     if (n_out) *n_out = NK;
     if (capacity < NK) return GM_ERR_CAPACITY;
     cloud_directions(p->n_sectors, bk, cos_sin);
+    return GM_OK;
+}
+
+void gm_wall_section_default_params(gm_wall_section_params *p)
+{
+    if (!defaults_begin(p)) return;
+    p->section_stations = 4;
+    p->harmonics = 2;
+    p->passes = 3;
+    p->min_count = 8;
+    p->min_columns = 24;
+    p->max_gap_deg = 90.0;
+    p->reject = 0.05;
+}
+
+gm_status gm_wall_section_check_params(const gm_wall_section_params *p)
+{
+    long long Tr;
+    return p && section_prm_ok(*p, Tr) ? GM_OK : GM_ERR_INVALID_ARG;
+}
+
+gm_status gm_wall_section_basis(uint32_t n_sectors, uint32_t harmonics, int32_t *basis, uint32_t capacity, uint32_t *n_out)
+{
+    if (n_out) *n_out = 0;
+    if (n_sectors < 1u || n_sectors > GM_WALL_MAX_SECTORS || harmonics > GM_WALL_SECTION_MAX_HARMONICS || (!basis && capacity))
+        return GM_ERR_INVALID_ARG;
+    const uint32_t entries = n_sectors * (1u + 2u * harmonics);
+    if (n_out) *n_out = entries;
+    if (!basis && !capacity) return GM_OK;
+    if (capacity < entries) return GM_ERR_CAPACITY;
+    section_basis(n_sectors, harmonics, basis);
+    return GM_OK;
+}
+
+gm_status gm_wall_section_solve(const gm_wall_section_sums *sums, uint32_t harmonics, uint32_t min_columns, int64_t coef_q[9],
+                                uint32_t *status)
+{
+    if (!sums || !coef_q || !status || harmonics > GM_WALL_SECTION_MAX_HARMONICS || min_columns < 1u) return GM_ERR_INVALID_ARG;
+    *status = section_solve(*sums, harmonics, min_columns, coef_q);
+    return GM_OK;
+}
+
+gm_status gm_wall_section_metrics(const gm_wall_params *p, const gm_wall_section *s, uint32_t harmonics,
+                                  struct gm_wall_section_metrics *out)
+{
+    if (!p || !s || !out || check_params(p) != GM_OK || harmonics > GM_WALL_SECTION_MAX_HARMONICS || s->stations < 1u)
+        return GM_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    // (one operation per statement: the same roundings as the twin's, whatever the compiler may contract)
+    const double from = (double)s->station_from * p->station_length;
+    const double end = (double)s->station_from + (double)s->stations;
+    const double to = end * p->station_length;
+    out->chainage_from = p->t_min + from;
+    out->chainage_to = p->t_min + to;
+    if (s->status & GM_SECTION_FAILED_MASK) return GM_OK;
+    const uint32_t P = 1u + 2u * harmonics;
+    double c[9];
+    for (uint32_t q = 0; q < 9u; ++q) c[q] = q < P ? (double)s->coef_q[q] * 0x1p-20 : 0.0;
+    DesignFrame d;
+    design_frame_of(*p, d);
+    const double radius = d.R + c[0];
+    out->radius_m = radius;
+    out->radial_m = c[0];
+    out->centre_u = c[1];
+    out->centre_v = c[2];
+    const double both = out->chainage_from + out->chainage_to;
+    const double mid = both * 0.5;
+    for (int k = 0; k < 3; ++k) {
+        const double along = mid * d.a[k];
+        const double cu = c[1] * d.u[k];
+        const double cv = c[2] * d.v[k];
+        const double s1 = d.o[k] + along;
+        const double s2 = s1 + cu;
+        out->centre[k] = s2 + cv;
+    }
+    const double oval = hypot(c[3], c[4]);
+    out->oval_m = oval;
+    if (oval > 0.0) {
+        const double ang = atan2(c[4], c[3]);
+        const double half = ang * 0.5;
+        const double scaled = half * 180.0;
+        double deg = scaled / 3.14159265358979323846;
+        if (deg < 0.0) deg = deg + 180.0;
+        if (deg >= 180.0) deg = deg - 180.0;
+        out->oval_angle_deg = deg;
+    }
+    const double rmax = radius + oval;
+    const double rmin = radius - oval;
+    out->diameter_max = 2.0 * rmax;
+    out->diameter_min = 2.0 * rmin;
+    if (s->accepted) {
+        const double msq = (double)s->rss / (double)s->accepted;
+        const double root = sqrt(msq);
+        out->rms_m = root * 0x1p-20;
+    }
+    const double r2 = radius * radius;
+    double sq = 0.0;
+    for (uint32_t q = 1; q < P; ++q) {
+        const double t = c[q] * c[q];
+        sq = sq + t;
+    }
+    const double a0 = 3.14159265358979323846 * r2;
+    const double a1 = 1.57079632679489661923 * sq;
+    out->area_m2 = a0 + a1;
+    out->coverage = (double)s->accepted / (double)p->n_sectors;
     return GM_OK;
 }
 

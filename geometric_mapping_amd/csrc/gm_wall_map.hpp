@@ -47,6 +47,12 @@ void cloud_directions(uint32_t nsec, uint32_t bk, double *cos_sin);
 // gm_wall_clearance_check_params' rule; T and R_q of an accepted call
 bool clearance_ok(const gm_wall_params *p, const gm_wall_clearance_params &c, const int32_t *gauge_q, uint32_t n_gauges,
                   const uint8_t *station_gauge, uint32_t n, long long &T, long long &Rq);
+// gm_wall_section_check_params' rule; Tr of an accepted block
+bool section_prm_ok(const gm_wall_section_params &p, long long &Tr);
+// the basis table of include/gm_hip.h: B[nsec][1 + 2 H] (one operation per statement, as stated there)
+void section_basis(uint32_t nsec, uint32_t H, int32_t *B);
+// the solve of include/gm_hip.h on one record of sums: the status, and c_q[9] (0 unless the status is GM_SECTION_OK)
+uint32_t section_solve(const gm_wall_section_sums &s, uint32_t H, uint32_t min_columns, int64_t cq[9]);
 bool check_prm_ok(const gm_wall_check_params &c, long long &T);
 bool locate_prm_ok(const gm_wall_locate_params &p);
 bool align_prm_ok(const gm_wall_align_params &p, uint32_t nsec);
@@ -70,6 +76,7 @@ P params_or(const P *prm, void (*defaults)(P *))
 #ifndef GM_WALL_HOST_ONLY
 
 constexpr uint64_t kStageCells = 1u << 20;   // cells per chunk of a window call (24 MiB of raw records)
+constexpr uint32_t kSectionChunk = 1u << 16; // sections per chunk of gm_wall_map_sections (37 MiB of scratch)
 
 // The records of a chained scan (gm_compact.hpp) that is not a frame's -- a slot's own belong to the frame that may be in
 // flight on it: the record array with the ticket word behind it, and the epoch of the launches on it so far.  The rule is
@@ -211,6 +218,13 @@ struct gm_wall_map {
     gm::DevArray<gm_wall_clearance_cell> cr_stage; // a chunk's list rows
     gm::wall::ScanRecords cr_scan;     // the list's own chained scan
     gm::DevArray<unsigned long long> cr_ctr;       // [kWallClearCounters]
+    // gm_wall_map_sections: the chunk (GM_WALL_SECTION_CHUNK: tests; 0: kSectionChunk sections) and the scratch
+    uint32_t section_chunk = 0;
+    gm::DevArray<int32_t> sc_basis;    // the uploaded table [n_sectors][P]
+    gm::DevArray<uint8_t> sc_chunk;    // per section of a chunk: WallSectionModel | WallSectionOut
+    std::vector<int32_t> sc_basis_host;            // the tables of the call in progress
+    std::vector<gm::WallSectionModel> sc_model_host;
+    std::vector<gm::WallSectionOut> sc_out_host;
     // gm_wall_map_check_*, _locate_*, _align_*: per slot of ctx
     std::vector<gm::wall::WallCheckSlot> checks;
     std::vector<gm::wall::WallLocateSlot> locates;

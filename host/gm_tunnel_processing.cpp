@@ -445,6 +445,31 @@ gm_wall_clearance_info Processor::wallMapClearance(unsigned station0, unsigned n
     return info;
 }
 
+gm_wall_sections_info Processor::wallMapSections(unsigned station0, unsigned n, const gm_wall_section_params &prm,
+                                                 std::vector<gm_wall_section> &sections, gm_wall_map *baseline,
+                                                 std::vector<gm_wall_section_sums> *sums)
+{
+    if (!wall_) throw Error(GM_ERR_NOT_READY, "wallMapSections: createWallMap first");
+    gm_wall_sections_info info;
+    uint32_t count = 0;
+    check(gm_wall_map_sections(wall_, baseline, station0, n, &prm, &info, 0, 0, &count, 0), "wallMapSections");
+    sections.assign(count, gm_wall_section());
+    if (sums) sums->assign(count, gm_wall_section_sums());
+    if (count)
+        check(gm_wall_map_sections(wall_, baseline, station0, n, &prm, &info, &sections[0], count, &count, sums ? &(*sums)[0] : 0),
+              "wallMapSections");
+    return info;
+}
+
+struct gm_wall_section_metrics Processor::wallSectionMetrics(const gm_wall_params &params, const gm_wall_section &section,
+                                                             unsigned harmonics)
+{
+    struct gm_wall_section_metrics out;
+    gm_status s = gm_wall_section_metrics(&params, &section, harmonics, &out);
+    if (s != GM_OK) throw Error(s, "wallSectionMetrics: the record or the parameters were refused");
+    return out;
+}
+
 std::vector<int32_t> Processor::wallGaugeFromPolygon(const gm_wall_params &params, const std::vector<double> &uv, const double offset[2])
 {
     if (uv.empty() || uv.size() % 2) throw Error(GM_ERR_INVALID_ARG, "wallGaugeFromPolygon: uv holds (u, v) pairs");

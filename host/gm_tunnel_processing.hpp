@@ -162,6 +162,16 @@ public:
     // design axis, shifted by offset (may be null): gm_wall_gauge_from_polygon, host only
     static std::vector<int32_t> wallGaugeFromPolygon(const gm_wall_params &params, const std::vector<double> &uv,
                                                      const double offset[2] = 0);
+    // the profile fit per section of stations [station0, station0 + n) (gm_wall_map_sections): convergence, centre and
+    // ovalisation per chainage, against the design or, with baseline (another map on the same grid, of this context),
+    // against that epoch.  One record per section; sums, when given, receives each section's last fitting pass; the map
+    // is not changed.  A call for the end of a drive or for a service, not for every frame.
+    gm_wall_sections_info wallMapSections(unsigned station0, unsigned n, const gm_wall_section_params &prm,
+                                          std::vector<gm_wall_section> &sections, gm_wall_map *baseline = 0,
+                                          std::vector<gm_wall_section_sums> *sums = 0);
+    // the fp64 metrics of one record of wallMapSections under the map's parameters (gm_wall_section_metrics, host only)
+    static struct gm_wall_section_metrics wallSectionMetrics(const gm_wall_params &params, const gm_wall_section &section,
+                                                             unsigned harmonics);
     // the changed points of the newest frame (as addToWallMap takes it) against the map under pose (gm_wall_map_check_frame +
     // gm_wall_map_get_check), ascending by index; the map is not changed.  info, when given, receives the call's counts.
     // Check, then addToWallMap: against what was there, then contribute.

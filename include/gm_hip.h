@@ -836,6 +836,165 @@ gm_status gm_wall_clearance_runs(const gm_wall_params *p, const gm_wall_clearanc
                                  uint32_t station0, uint32_t max_gap, gm_wall_clearance_run *runs, uint32_t capacity,
                                  uint32_t *n_out);
 
+/* ---- a robust profile fit per chainage section (gm_wall_map_sections) -------------------------------------------------
+ * The as-built cross-section per chainage: how far the tube has closed or opened against the design radius, where its
+ * centre sits against the design axis, how oval it is and in which direction -- per section of the drive and, with a
+ * baseline map, between two epochs.  A station's row of sector means is a sampled rho(phi) - R; its low Fourier
+ * harmonics are these quantities (h = 0 radius change, h = 1 centre offset, h = 2 ovalisation, h = 3, 4 squatting and
+ * local shape).  Everything on the device is integer; the one fp64 step, a small solve per section and pass, runs on
+ * the host and is exported (gm_wall_section_solve), so the records are a function of the raw cells, the basis table
+ * and the parameters alone.
+ *   sections    the window is stations [station0, station0 + n), S = section_stations, NS = ceil(n / S); section i is
+ *               window stations [i S, min((i + 1) S, n)).
+ *   column      column (i, k) is the cells of sector k over the section's stations, merged exactly as
+ *               gm_wall_map_cloud merges a block: the count a u64 sum, the sum an int64 sum (empty cells add nothing),
+ *               q = sum / (int64) count by C division.  Without a baseline m = q and the column is USABLE iff
+ *               count >= min_count.  With a baseline (the refusals of gm_wall_map_regions) m = q(map) - q(baseline) and
+ *               the column is USABLE iff both counts are >= min_count.  m saturates at +-2^24 units of 2^-20 m (16 m,
+ *               twice the largest gate).  Every column is in exactly one class: EMPTY (count 0, and with a baseline
+ *               count 0 there too), UNUSABLE, usable.
+ *   basis       P = 1 + 2 H unknowns, H = harmonics in 0 .. 4.  The table is made once per call on the host with libm:
+ *               int32 B[k][P], B[k][0] = 2^20, B[k][2h - 1] = rint(cos(h phi_k) 2^20), B[k][2h] = rint(sin(h phi_k) 2^20),
+ *               phi_k = 2 pi (2k + 1) / (2 n_sectors), the sector's centre (the angle of gm_wall_clearance_run.angle_deg);
+ *               one operation per statement.  gm_wall_section_basis returns the table the call uses.
+ *   sums        of a pass, over the FITTED columns of a section, all int64: N[p][q] = sum B_p B_q for p <= q, packed
+ *               row-major in the call's P (slot p P - p (p - 1) / 2 + q - p of 45, the unused slots 0), r[p] = sum B_p m,
+ *               the fitted count, the fitted points (their merged counts, of the map) and largest_gap, the longest
+ *               cyclic run of consecutive sectors that are not fitted (n_sectors when none is, 0 when all are).
+ *               |N| <= 2^40 4096 = 2^52 and |r| <= 2^20 2^24 2^12 = 2^56.  This is gm_wall_section_sums.
+ *   solve       on the host in fp64, one operation per statement so that nothing can contract: A = N 2^-40 (exact),
+ *               b = r 2^-20 (one rounding, the conversion), a Cholesky solve A c = b.  In this order: a fitted count
+ *               below max(min_columns, P) gives GM_SECTION_TOO_FEW; a pivot that is not above 1e-12 of its diagonal
+ *               entry gives GM_SECTION_SINGULAR; c_q[p] = (int64) rint(c[p]), units of 2^-20 m, and |c_q| > 2^24 gives
+ *               GM_SECTION_UNBOUNDED.  Each of the three FAILS the section: its later passes are skipped, its
+ *               coefficients, accepted, rejected, points and residual fields are 0 and its peak sectors UINT32_MAX.
+ *   model       integer: M_k = (sum_p B[k][p] c_q[p] + 2^19) >> 20 (an arithmetic shift), rho_k = m_k - M_k.
+ *   passes      P_f = passes in 1 .. 4.  Pass 1 fits every usable column; pass p >= 2 fits the usable columns with
+ *               |rho| <= Tr 2^(P_f - p) against the model of pass p - 1, Tr = (int64) rint(reject 2^20) >= 1, reject in
+ *               (0, 8]: the tightening of the cylinder regression's 4 tau, 2 tau, tau.
+ *   evaluation  one more launch against the last model: ACCEPTED are the usable columns with |rho| <= Tr, rejected =
+ *               usable - accepted, rss = sum rho^2 over the accepted (<= 2^46 2^12), peak_out and peak_in the largest
+ *               and the smallest rho over ALL usable columns (a rejected niche is what one wants to see) with their
+ *               sectors, the smallest among equals (0 and UINT32_MAX without a usable column), points the merged count
+ *               of the accepted columns, of the map.
+ *   flag        GM_SECTION_OPEN_ARC: largest_gap of the last fitting pass that ran exceeds floor(max_gap_deg n_sectors /
+ *               360).  It fails nothing and the values are kept, as GM_FIT_NOT_CONVERGED keeps its own: on a 120 degree
+ *               arc the harmonics trade against each other (with H = 4 the least Cholesky pivot ratio falls to about
+ *               1e-5), and the caller must be told.
+ * h = 1 is the centre offset to FIRST ORDER only: a circle of radius R' displaced by delta also contributes
+ * -delta^2 / (4 R') to h = 0 and delta^2 / (4 R') to h = 2.
+ * On the device: one kernel, launched passes + 1 times per chunk of sections (2^16 by default; environment
+ * GM_WALL_SECTION_CHUNK=<sections>, 0 or more than 2^16 meaning 2^16, read at gm_wall_map_create: tests only); the sums
+ * go to the host and the coefficients come back between the launches.  No floating point and no floating-point atomics
+ * on the device: the result does not depend on the chunk, the grid or the order. */
+#define GM_SECTION_OK         0u
+#define GM_SECTION_TOO_FEW    (1u << 0)   /* fewer fitted columns than max(min_columns, P) */
+#define GM_SECTION_SINGULAR   (1u << 1)   /* a Cholesky pivot not above 1e-12 of its diagonal entry */
+#define GM_SECTION_UNBOUNDED  (1u << 2)   /* a coefficient beyond 2^24 units (16 m) */
+#define GM_SECTION_FAILED_MASK 0xFFu      /* status & mask != 0: no fit, the values are 0 */
+#define GM_SECTION_OPEN_ARC   (1u << 8)   /* the fitted sectors leave a gap above max_gap_deg: the values are kept */
+#define GM_WALL_SECTION_MAX_HARMONICS 4u
+#define GM_WALL_SECTION_MAX_PASSES    4u
+
+typedef struct gm_wall_section_params {   /* 40 bytes */
+    uint32_t struct_size;       /* = sizeof(gm_wall_section_params) */
+    uint32_t section_stations;  /* S >= 1 (default 4) */
+    uint32_t harmonics;         /* H in 0 .. 4 (default 2) */
+    uint32_t passes;            /* P_f in 1 .. 4 (default 3) */
+    uint32_t min_count;         /* >= 1 (default 8): points a column needs to be usable */
+    uint32_t min_columns;       /* >= 1 (default 24): fitted columns a pass needs (and never fewer than P) */
+    double   max_gap_deg;       /* in [0, 360] (default 90): a larger gap sets GM_SECTION_OPEN_ARC */
+    double   reject;            /* metres, in (0, 8] (default 0.05): Tr */
+} gm_wall_section_params;
+
+typedef struct gm_wall_section_sums {   /* 448 bytes: the sums of one pass of one section */
+    int64_t  N[45];             /* the upper triangle, packed row-major in the call's P; unused slots 0 */
+    int64_t  r[9];              /* unused slots 0 */
+    uint32_t fitted;            /* the columns summed */
+    uint32_t largest_gap;       /* sectors */
+    uint64_t points;            /* merged count of the fitted columns */
+} gm_wall_section_sums;
+
+typedef struct gm_wall_section {   /* 144 bytes */
+    uint32_t station_from;      /* map-wide first station */
+    uint32_t stations;          /* 1 .. S */
+    uint32_t status;            /* GM_SECTION_* */
+    uint32_t usable;            /* columns */
+    uint32_t fitted;            /* of the last fitting pass that ran */
+    uint32_t accepted, rejected;
+    uint32_t largest_gap;       /* of the last fitting pass that ran, sectors */
+    uint64_t points;            /* merged count of the accepted columns */
+    int64_t  coef_q[9];         /* c0, a1, b1, a2, b2, ..., units of 2^-20 m; unused slots 0 */
+    uint64_t rss;               /* sum rho^2 over the accepted columns, units of 2^-40 m^2 */
+    int64_t  peak_out, peak_in; /* the largest and the smallest rho over the usable columns */
+    uint32_t peak_out_sector, peak_in_sector;
+} gm_wall_section;
+
+typedef struct gm_wall_sections_info {   /* 96 bytes */
+    uint32_t struct_size;       /* = sizeof(gm_wall_sections_info), filled by the library */
+    uint32_t station0, n_stations, n_sectors;   /* the window and the map's sectors */
+    uint32_t section_stations, sections;        /* S, NS */
+    uint32_t harmonics, passes;                 /* H, P_f */
+    int64_t  reject_q;          /* Tr */
+    uint32_t max_gap_sectors;   /* floor(max_gap_deg n_sectors / 360) */
+    uint32_t sections_ok;       /* status & GM_SECTION_FAILED_MASK == 0 */
+    uint32_t sections_failed;
+    uint32_t sections_open_arc; /* GM_SECTION_OPEN_ARC set (failed or not) */
+    uint64_t empty, unusable, usable;   /* columns per class: they sum to NS n_sectors */
+    uint64_t accepted, rejected;        /* of the sections that did not fail */
+} gm_wall_sections_info;
+
+struct gm_wall_section_metrics {   /* 128 bytes; fp64 derived on the host, one rounding per operation */
+    double chainage_from;       /* t_min + station_from * station_length */
+    double chainage_to;         /* t_min + (station_from + stations) * station_length */
+    double radius_m;            /* R + c0 */
+    double radial_m;            /* c0: convergence (negative: the tube has closed) */
+    double centre_u, centre_v;  /* a1, b1: the centre against the design axis, to first order (see above) */
+    double centre[3];           /* o + t_mid a + a1 u + b1 v in map coordinates, t_mid the section's mid chainage */
+    double oval_m;              /* hypot(a2, b2) */
+    double oval_angle_deg;      /* atan2(b2, a2) / 2 in [0, 180): the direction of the long axis; 0 without h = 2 */
+    double diameter_max;        /* 2 (R + c0 + oval_m) */
+    double diameter_min;        /* 2 (R + c0 - oval_m) */
+    double rms_m;               /* sqrt(rss / accepted) 2^-20; 0 without an accepted column */
+    double area_m2;             /* pi (R + c0)^2 + (pi / 2) sum_{h >= 1} (a_h^2 + b_h^2): 1/2 the ring integral of rho^2 */
+    double coverage;            /* accepted / n_sectors */
+};
+
+/* Host only: the defaults of the table above.  A NULL is ignored. */
+void gm_wall_section_default_params(gm_wall_section_params *p);
+/* Host only, no device, no map: what gm_wall_map_sections refuses of its parameters.  GM_ERR_INVALID_ARG: NULL, a
+ * struct_size mismatch, section_stations 0, harmonics above 4, passes outside 1 .. 4, min_count 0, min_columns 0,
+ * max_gap_deg outside [0, 360], reject outside (0, 8] or rounding to Tr = 0. */
+gm_status gm_wall_section_check_params(const gm_wall_section_params *p);
+/* Host only: the basis table B[n_sectors][1 + 2 harmonics] of a map with n_sectors sectors, the one the call uploads.
+ * *n_out (may be NULL) = the number of entries; basis NULL with capacity 0 is a count query, a capacity below *n_out
+ * returns GM_ERR_CAPACITY and writes nothing.  GM_ERR_INVALID_ARG: n_sectors outside 1 .. GM_WALL_MAX_SECTORS, harmonics
+ * above 4, basis NULL with a capacity. */
+gm_status gm_wall_section_basis(uint32_t n_sectors, uint32_t harmonics, int32_t *basis, uint32_t capacity, uint32_t *n_out);
+/* Host only: the solve above on one record of sums.  coef_q receives 9 entries (0 in the unused slots and on a failed
+ * section), *status one of GM_SECTION_OK, _TOO_FEW, _SINGULAR, _UNBOUNDED.  GM_ERR_INVALID_ARG: a NULL, harmonics above
+ * 4, min_columns 0. */
+gm_status gm_wall_section_solve(const gm_wall_section_sums *sums, uint32_t harmonics, uint32_t min_columns, int64_t coef_q[9],
+                                uint32_t *status);
+/* Host only: the metrics of one record under the map's parameters.  A failed section gives GM_OK and zeros but for the
+ * chainage interval.  GM_ERR_INVALID_ARG: a NULL, p->struct_size mismatch, n_sectors 0, harmonics above 4, a record of 0
+ * stations. */
+gm_status gm_wall_section_metrics(const gm_wall_params *p, const gm_wall_section *s, uint32_t harmonics,
+                                  struct gm_wall_section_metrics *out);
+/* The sections of stations [station0, station0 + n).  Synchronises the map and the baseline (as gm_wall_map_sync),
+ * runs on the map's stream and blocks.  baseline NULL: against the design; else another map of the same context on
+ * the same grid (refused as gm_wall_map_regions refuses it).  prm NULL: the defaults.  info is required; it and *n_out
+ * (may be NULL; NS) are filled whenever the call got past its refusals, also on GM_ERR_CAPACITY.  sections NULL with
+ * capacity 0 is a count query (GM_OK; info is complete, NS records are what a second call needs room for); a capacity
+ * below NS with a buffer returns GM_ERR_CAPACITY before anything runs on the device: the totals of info are 0 then.  sums (may be NULL) receives the NS records of each section's
+ * last fitting pass that ran.  n = 0 gives nothing.  Neither map is changed.  Scratch (the basis table and 592 B per
+ * section of a chunk) is allocated on first use, kept grow-only in the map and freed with it; a map that never calls
+ * this allocates and launches nothing new.  GM_ERR_INVALID_ARG: NULL map / info, a window outside the map, whatever
+ * gm_wall_section_check_params refuses, a refused baseline, sections NULL with a capacity or with sums. */
+gm_status gm_wall_map_sections(gm_wall_map *map, gm_wall_map *baseline, uint32_t station0, uint32_t n,
+                               const gm_wall_section_params *prm, gm_wall_sections_info *info, gm_wall_section *sections,
+                               uint32_t capacity, uint32_t *n_out, gm_wall_section_sums *sums);
+
 /* ---- a frame's changed points against the wall map (gm_wall_map_check_*) ----------------------------------------------
  * Which points of the frame in front of the sensor are NOT where the map says the wall is: rockfall, a fallen lining
  * segment, a vehicle in the profile, new shotcrete.  One device pass over the frame's valid cloud under a pose; only the
