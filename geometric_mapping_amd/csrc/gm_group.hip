@@ -10,13 +10,11 @@
 // Sharded frame.  The path shards because every per-point stage depends only on points within neighborRadius and the
 // final fit is a SUM (M = sum w^2 n n^T) followed by a 3x3 solve.  Rank g owns the points with x in [edge[g], edge[g+1])
 // and also receives halo points within 1.01 r of its edges -- neighbours only, never outputs (gm_set_owned_range).
-//   * The cut is made on the host before H2D (no device-to-device halo exchange): ONE parallel pass histograms the x of
-//     the in-box rows over the VoxelGrid lattice, the edges are put on lattice planes -- exactly, through the device's
-//     own float expression floorf(x * inv_leaf) -- so that no voxel of pcl::VoxelGrid (src/tunnel_processing.cpp:217-220)
-//     straddles two ranks, and a second parallel pass scatters every row once into per-rank page-locked buffers.
-//   * The only exchange step of the path is one ncclAllGather of a 24-double record per rank (scatter partials, counts,
-//     the rank's fitted plane / cylinder): latency bound, a few hundred bytes over xGMI.  RCCL is loaded at run time
-//     (dlopen) so that a single-GPU host needs no librccl.
+//   * The cut is made on the host before H2D (no device-to-device halo exchange), by the device-free gm_group_cut.hpp:
+//     edges on planes of the VoxelGrid lattice, every row scattered once into per-rank page-locked buffers.
+//   * The only exchange step of the path is one all-gather (all_gather below, also behind gm_group_fit_cylinder) of a
+//     24-double record per rank (scatter partials, counts, the rank's fitted plane / cylinder): latency bound, a few
+//     hundred bytes over xGMI.  RCCL is loaded at run time (dlopen) so that a single-GPU host needs no librccl.
 //   * Voxel outputs of the group (centroids, and the normal of every centroid's nearest point: the /surfaceNormals
 //     markers, src/tunnel_processing.cpp:237-252) are the ranks' own, merged into ascending pcl key order; the nearest
 //     point of a centroid is searched on every rank (it may lie across an edge) and the closest wins.
@@ -35,9 +33,9 @@
 #include <limits>
 #include <new>
 #include <string>
-#include <thread>
 #include <vector>
 
+#include "gm_group_cut.hpp"
 #include "gm_internal.hpp"
 
 using namespace gm;
@@ -107,75 +105,29 @@ __global__ __launch_bounds__(256) void k_gather_nearest(const int32_t *__restric
     pts_out[i] = j >= 0 ? pts[j] : make_float4(0.f, 0.f, 0.f, __uint_as_float(0xFFFFFFFFu));
 }
 
-inline float load_f32(const uint8_t *p, bool bswap)
-{
-    uint32_t u;
-    memcpy(&u, p, 4);
-    if (bswap) u = __builtin_bswap32(u);
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
-// fn(t) for t in [0, T) on T threads (the caller's included)
-template <class F>
-void parallel_for(uint32_t T, F fn)
-{
-    if (T <= 1) { fn(0u); return; }
-    std::vector<std::thread> th;
-    th.reserve(T - 1);
-    for (uint32_t t = 1; t < T; ++t) th.emplace_back([&fn, t]() { fn(t); });
-    fn(0u);
-    for (auto &x : th) x.join();
-}
-
 double now_ms()
 {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-// pcl::VoxelGrid's lattice index of a coordinate, as every kernel computes it (k_normals.hip voxel_sums, k_voxel.hip)
-inline long long lattice_cell(float x, float inv_leaf) { return (long long)floorf(x * inv_leaf); }
-
-// smallest float t with lattice_cell(t) >= k: the plane between cells k-1 and k in float space (the map is monotone)
-float lattice_plane(long long k, float inv_leaf)
-{
-    float t = (float)((double)k / (double)inv_leaf);
-    for (int it = 0; it < 64 && lattice_cell(t, inv_leaf) >= k; ++it) t = nextafterf(t, -std::numeric_limits<float>::infinity());
-    for (int it = 0; it < 128 && lattice_cell(t, inv_leaf) < k; ++it) t = nextafterf(t, std::numeric_limits<float>::infinity());
-    return t;
 }
 
 }  // namespace
 
 struct gm_group {
     gm_config cfg;
-    uint32_t flags = 0;
     uint32_t n = 0;
     bool loopback = false;           // ranks share a device: records travel by device copies, no communicator
     bool dead = false;               // a collective failed half-way: the ranks' streams can no longer be trusted
-    std::vector<int> devices;
-    std::vector<gm_ctx *> ctx;
-    std::vector<DevArray<double>> d_rec;   // [n] device: this rank's record
-    std::vector<DevArray<double>> d_all;   // [n] device: every rank's record (the all-gather's receive buffer)
-    std::vector<hipEvent_t> ev;      // loopback: "record packed" per rank
-    HostArray<double> h_all;         // pinned host copy of rank 0's gathered buffer
-    std::vector<ncclComm_t> comms;
-    Rccl rccl;
-    std::vector<HostArray<uint8_t>> prow;   // per rank: page-locked row buffer of the slab cut (grow-only)
-    std::vector<std::vector<uint32_t>> row_ids;  // per-rank: input row of every row sent
-    std::vector<float> xs;           // x of every input row (scratch of the cut)
-    std::vector<double> edges;
-    bool edges_on_lattice = false;
-    gm_frame_result last = {};
-    bool have_frame = false;         // `last`, row_ids and the ranks' slot 0 hold one sharded frame
-    double timing[GM_GROUP_N_TIMINGS] = {};
-    std::vector<float> vox_cen;      // merged voxel centroids of the last sharded frame: x, y, z, count per voxel
-    std::vector<float> vox_nrm;      // ... and the normal of each centroid's nearest point (filled on demand)
-    std::vector<int32_t> vox_near;   // ... and that point's index in the merged /choppedCloud
-    bool vox_nrm_valid = false;
-    // cylinder regression of the sharded frame (gm_group_fit_cylinder): per-rank device buffers, allocated on first use
-    struct FitRank {
+    // everything one rank owns.  Lives and dies with its device current (gm_group_create, release).
+    struct Rank {
+        int device = 0;
+        gm_ctx *ctx = nullptr;
+        DevArray<double> d_rec;           // this rank's record
+        DevArray<double> d_all;           // every rank's record (the all-gather's receive buffer)
+        hipEvent_t ev = nullptr;          // loopback: "what this rank sends is written"
+        HostArray<uint8_t> prow;          // page-locked row buffer of the slab cut (grow-only)
+        std::vector<uint32_t> row_ids;    // input row of every row sent
+        uint32_t next_slot = 0;           // streaming
+        // cylinder regression of the sharded frame (gm_group_fit_cylinder): allocated on first use
         DevArray<double> partial;         // [kFitBlocks][24] the rank's partial rows of a pass
         DevArray<uint32_t> ticket;        // last-block ticket (0 between launches)
         DevArray<CylFitWork> work;        // the model between the passes (every rank writes the same bits)
@@ -184,16 +136,37 @@ struct gm_group {
         DevArray<uint32_t> plane_best;    // 0: the plane row labels; 0xFFFFFFFF: no plane, every label 0
         DevArray<double> row;             // [4 passes][24] the rank's reduced row of each pass (exchange send buffer)
         DevArray<double> rows;            // [4 passes][n][24] every rank's row of each pass (receive buffer; allocated last)
+        hipStream_t stream() const { return ctx->slots[0].stream; }   // of the sharded frame: slot 0
+        void release()   // the event, the context (gm_destroy drains the rank's streams first), then the rank's blocks
+        {
+            if (ev) hipEventDestroy(ev);
+            if (ctx) gm_destroy(ctx);
+            d_rec.release(); d_all.release(); prow.release(); partial.release(); ticket.release(); work.release();
+            fit.release(); rows8.release(); plane_best.release(); row.release(); rows.release();
+        }
     };
-    std::vector<FitRank> fitr;
-    HostArray<gm_cylinder_fit> h_fit;     // pinned: [n] the ranks' result records
+    std::vector<Rank> rank;          // [n]
+    std::vector<int> devices;        // [n] and
+    std::vector<ncclComm_t> comms;   // [n], contiguous for ncclCommInitAll
+    HostArray<double> h_all;         // pinned host copy of rank 0's gathered buffer
+    Rccl rccl;
+    std::vector<float> xs;           // x of every input row (scratch of the cut)
+    std::vector<double> edges;       // of the last cut, and whether they lie on planes of the voxel lattice
+    bool edges_on_lattice = false;
+    gm_frame_result last = {};
+    bool have_frame = false;         // `last`, row_ids and the ranks' slot 0 hold one sharded frame
+    double timing[GM_GROUP_N_TIMINGS] = {};
+    std::vector<float> vox_cen;      // merged voxel centroids of the last sharded frame: x, y, z, count per voxel
+    std::vector<float> vox_nrm;      // ... and the normal of each centroid's nearest point (filled on demand)
+    std::vector<int32_t> vox_near;   // ... and that point's index in the merged /choppedCloud
+    bool vox_nrm_valid = false;
+    HostArray<gm_cylinder_fit> h_fit;     // pinned: [n] the ranks' result records of gm_group_fit_cylinder
     gm_cylinder_fit last_fit = {};
     bool have_fit = false;                // last_fit belongs to the sharded frame in `last`
     // streaming: frames in flight in submission order
     struct Ticket { uint32_t rank, slot; };
     std::deque<Ticket> inflight;
     uint32_t next_rank = 0;
-    std::vector<uint32_t> next_slot;
     std::string err;
 };
 
@@ -206,130 +179,83 @@ gm_status gfail(gm_group *g, gm_status st, const std::string &msg)
     return st;
 }
 
-// after a failure behind the first submit: nothing of the frame may still be in flight when we return
-void drain(gm_group &G)
+// a failure behind the first submit: nothing of the frame may still be in flight when we return
+gm_status fail_drained(gm_group &G, gm_status st, const std::string &msg)
 {
-    for (uint32_t r = 0; r < G.n; ++r) {
-        if (!G.ctx[r]) continue;
-        hipSetDevice(G.devices[r]);
-        for (uint32_t s = 0; s < G.ctx[r]->n_slots; ++s) hipStreamSynchronize(G.ctx[r]->slots[s].stream);
+    for (gm_group::Rank &k : G.rank) {
+        if (!k.ctx) continue;
+        hipSetDevice(k.device);
+        for (uint32_t s = 0; s < k.ctx->n_slots; ++s) hipStreamSynchronize(k.ctx->slots[s].stream);
     }
     (void)hipGetLastError();
+    return gfail(&G, st, msg);
 }
 
-struct CutPlan {
-    std::vector<double> edges;
-    bool on_lattice = false;
-    uint32_t n_inside = 0;
-};
-
-// ---- the host side of the cut (see the header of this file).  Returns per-rank row counts in total[].
-gm_status cut_rows(gm_group &G, const gm_cloud *cloud, CutPlan &plan, std::vector<uint32_t> &total)
+// The one exchange step: `count` doubles of every rank q, send(q), to recv(r) + q * count on every rank r, on the ranks'
+// slot-0 streams.  RCCL, or between ranks on one device (tests on a 1-GPU box) device copies ordered by the ranks' events.
+template <class Send, class Recv>
+gm_status all_gather(gm_group &G, size_t count, Send send, Recv recv)
 {
-    const uint32_t n = cloud->n_points, R = G.n;
-    const uint64_t step = cloud->point_step;
-    const bool bswap = (cloud->flags & GM_CLOUD_BIGENDIAN) != 0;
-    const uint8_t *base = (const uint8_t *)cloud->data;
-    const float lo = (float)(-G.cfg.boxFilterBound), hi = (float)G.cfg.boxFilterBound;
-    const float inv_leaf = 1.0f / (float)G.cfg.voxelGridLeafSize;
-    uint32_t T = std::thread::hardware_concurrency();
-    if (const char *e = getenv("GM_GROUP_THREADS")) T = (uint32_t)atoi(e);
-    if (T > 16) T = 16;
-    if (T < 1 || n < 262144u) T = 1;
-    // histogram bins: lattice cells of the box along x (several cells per bin when the lattice is very fine); when the
-    // lattice is too coarse to balance the ranks, 4096 uniform bins instead (a voxel may then straddle an edge: the
-    // dense tables of the ranks are merged exactly, see merge_voxels)
-    const long long c_lo = lattice_cell(lo, inv_leaf), c_hi = lattice_cell(hi, inv_leaf);
-    const long long ncell = c_hi - c_lo + 1;
-    const bool want_voxels = (G.cfg.flags & GM_CFG_VOXEL_GRID) != 0;
-    plan.on_lattice = want_voxels && ncell >= (long long)4 * R;
-    int shift = 0;
-    while (plan.on_lattice && (ncell >> shift) > (1ll << 20)) ++shift;
-    const uint32_t nbins = plan.on_lattice ? (uint32_t)((ncell + (1ll << shift) - 1) >> shift) : 4096u;
-    const double ubin = (double)nbins / ((double)hi - (double)lo > 0 ? (double)hi - (double)lo : 1.0);
-    G.xs.resize(n);
-    std::vector<std::vector<uint32_t>> hist(T, std::vector<uint32_t>(nbins, 0u));
-    std::vector<uint32_t> inside(T, 0u);
-    parallel_for(T, [&](uint32_t t) {
-        const uint32_t i0 = (uint32_t)((uint64_t)n * t / T), i1 = (uint32_t)((uint64_t)n * (t + 1) / T);
-        std::vector<uint32_t> &h = hist[t];
-        uint32_t in = 0;
-        for (uint32_t i = i0; i < i1; ++i) {
-            const uint8_t *row = base + (size_t)i * step;
-            const float x = load_f32(row + cloud->off_x, bswap), y = load_f32(row + cloud->off_y, bswap), z = load_f32(row + cloud->off_z, bswap);
-            G.xs[i] = x;
-            if (std::isfinite(x) && std::isfinite(y) && std::isfinite(z) && !(x < lo || y < lo || z < lo || x > hi || y > hi || z > hi)) {
-                uint32_t b;
-                if (plan.on_lattice) b = (uint32_t)((lattice_cell(x, inv_leaf) - c_lo) >> shift);
-                else { const double u = ((double)x - (double)lo) * ubin; b = u < 0 ? 0u : (uint32_t)u; }
-                ++h[b < nbins ? b : nbins - 1];
-                ++in;
-            }
+    if (!G.loopback) {
+        ncclResult_t rc = G.rccl.GroupStart();
+        for (uint32_t r = 0; r < G.n && rc == ncclSuccess; ++r) {
+            hipSetDevice(G.rank[r].device);
+            rc = G.rccl.AllGather(send(r), recv(r), count, ncclDouble, G.comms[r], G.rank[r].stream());
         }
-        inside[t] = in;
-    });
-    uint64_t n_in = 0;
-    for (uint32_t t = 0; t < T; ++t) n_in += inside[t];
-    plan.n_inside = (uint32_t)n_in;
-    // edges: the bin boundary at which the running count first reaches g / R of the in-box rows
-    plan.edges.assign(R + 1, 0.0);
-    plan.edges[0] = -std::numeric_limits<double>::infinity();
-    plan.edges[R] = std::numeric_limits<double>::infinity();
-    {
-        uint64_t run = 0;
-        uint32_t g = 1;
-        for (uint32_t b = 0; b < nbins && g < R; ++b) {
-            uint64_t c = 0;
-            for (uint32_t t = 0; t < T; ++t) c += hist[t][b];
-            run += c;
-            while (g < R && run * R >= n_in * (uint64_t)g && n_in) {   // the edge behind bin b
-                if (plan.on_lattice) plan.edges[g] = (double)lattice_plane(c_lo + ((long long)(b + 1) << shift), inv_leaf);
-                else plan.edges[g] = (double)(float)((double)lo + (double)(b + 1) / ubin);
-                ++g;
-            }
-        }
-        for (; g < R; ++g) plan.edges[g] = n_in ? plan.edges[g - 1] : 0.0;   // (an empty frame: every edge at 0)
-        for (uint32_t k = 1; k < R; ++k) if (plan.edges[k] < plan.edges[k - 1]) plan.edges[k] = plan.edges[k - 1];
+        const ncclResult_t rc2 = G.rccl.GroupEnd();
+        if (rc == ncclSuccess) rc = rc2;
+        if (rc == ncclSuccess) return GM_OK;
+        // some ranks may have posted their half of the collective: their streams can block for good.  No drain (it
+        // could hang with them); the group refuses further work.
+        G.dead = true;
+        return gfail(&G, GM_ERR_COMM, std::string("ncclAllGather: ") + G.rccl.GetErrorString(rc));
     }
-    // membership: rank r takes the rows with x in [edge[r] - halo, edge[r+1] + halo)   (NaN rows fail both comparisons:
-    // every rank's crop would drop them anyway)
-    const double halo = 1.01 * G.cfg.neighborRadius;
-    std::vector<std::vector<uint32_t>> cnt(T, std::vector<uint32_t>(R, 0u));
-    parallel_for(T, [&](uint32_t t) {
-        const uint32_t i0 = (uint32_t)((uint64_t)n * t / T), i1 = (uint32_t)((uint64_t)n * (t + 1) / T);
-        std::vector<uint32_t> &c = cnt[t];
-        for (uint32_t i = i0; i < i1; ++i) {
-            const double x = (double)G.xs[i];
-            for (uint32_t r = 0; r < R; ++r) c[r] += (x >= plan.edges[r] - halo && x < plan.edges[r + 1] + halo) ? 1u : 0u;
-        }
-    });
-    total.assign(R, 0u);
-    std::vector<std::vector<uint32_t>> off(T, std::vector<uint32_t>(R, 0u));
-    for (uint32_t r = 0; r < R; ++r)
-        for (uint32_t t = 0; t < T; ++t) { off[t][r] = total[r]; total[r] += cnt[t][r]; }
-    for (uint32_t r = 0; r < R; ++r) {
-        const size_t need = (size_t)total[r] * step;
-        if (need > G.prow[r].cap) {
-            const size_t cap = need + need / 8 + 4096;
-            if (hipSetDevice(G.devices[r]) != hipSuccess || G.prow[r].reserve(cap) != hipSuccess)
-                return gfail(&G, GM_ERR_OOM, "gm_group: page-locked row buffer allocation failed");
-        }
-        G.row_ids[r].resize(total[r]);
+    for (gm_group::Rank &k : G.rank) {
+        hipSetDevice(k.device);
+        hipEventRecord(k.ev, k.stream());
     }
-    parallel_for(T, [&](uint32_t t) {
-        const uint32_t i0 = (uint32_t)((uint64_t)n * t / T), i1 = (uint32_t)((uint64_t)n * (t + 1) / T);
-        std::vector<uint32_t> at(off[t]);
-        for (uint32_t i = i0; i < i1; ++i) {
-            const double x = (double)G.xs[i];
-            for (uint32_t r = 0; r < R; ++r)
-                if (x >= plan.edges[r] - halo && x < plan.edges[r + 1] + halo) {
-                    memcpy(G.prow[r] + (size_t)at[r] * step, base + (size_t)i * step, step);
-                    G.row_ids[r][at[r]] = i;
-                    ++at[r];
-                }
+    for (uint32_t r = 0; r < G.n; ++r) {
+        hipSetDevice(G.rank[r].device);
+        for (uint32_t q = 0; q < G.n; ++q) {
+            if (q != r) hipStreamWaitEvent(G.rank[r].stream(), G.rank[q].ev, 0);
+            hipMemcpyAsync(recv(r) + q * count, send(q), sizeof(double) * count, hipMemcpyDeviceToDevice, G.rank[r].stream());
         }
-    });
+    }
     return GM_OK;
+}
+
+// ---- the cut (gm_group_cut.hpp) with the ranks' page-locked buffers allocated between its two calls
+gm_status cut_slabs(gm_group &G, const gm_cloud *cloud, CutPlan &plan)
+{
+    try {   // (the cut allocates and starts threads: nothing may leave through the C ABI)
+        const uint32_t T = cut_threads(cloud->n_points);
+        cut_plan(G.cfg, G.n, *cloud, T, G.xs, plan);
+        std::vector<uint8_t *> rows(G.n);
+        std::vector<uint32_t *> ids(G.n);
+        for (uint32_t r = 0; r < G.n; ++r) {
+            gm_group::Rank &k = G.rank[r];
+            const size_t need = (size_t)plan.total[r] * cloud->point_step;
+            if (need > k.prow.cap && (hipSetDevice(k.device) != hipSuccess || k.prow.reserve(need + need / 8 + 4096) != hipSuccess))
+                return gfail(&G, GM_ERR_OOM, "gm_group: page-locked row buffer allocation failed");
+            k.row_ids.resize(plan.total[r]);
+            rows[r] = k.prow; ids[r] = k.row_ids.data();
+        }
+        cut_scatter(*cloud, T, G.xs, plan, rows.data(), ids.data());
+    } catch (const std::bad_alloc &) {
+        return gfail(&G, GM_ERR_OOM, "gm_group_process_frame: host allocation failed in the slab cut");
+    } catch (const std::exception &e) {
+        return gfail(&G, GM_ERR_DEVICE, std::string("gm_group_process_frame: the slab cut failed: ") + e.what());
+    }
+    return GM_OK;
+}
+
+// the input row behind the .w of a row of rank r's valid cloud (the bits of its index among the rows sent to r)
+bool input_row(const gm_group &G, uint32_t r, const float *w, uint32_t *row)
+{
+    uint32_t local;
+    memcpy(&local, w, 4);
+    if (local < G.rank[r].row_ids.size()) *row = G.rank[r].row_ids[local];
+    return local < G.rank[r].row_ids.size();
 }
 
 struct MergedRow { uint32_t id; float x, y, z; uint8_t label; };
@@ -343,25 +269,22 @@ gm_status merged_rows(gm_group &G, bool with_labels, std::vector<MergedRow> &all
     std::vector<float> buf;
     std::vector<uint8_t> lab;
     for (uint32_t r = 0; r < G.n; ++r) {
-        uint32_t m = 0;
-        gm_status st = gm_get_cropped_xyz(G.ctx[r], 0, nullptr, 0, &m);
-        if (st != GM_OK && st != GM_ERR_CAPACITY) return gfail(&G, st, gm_last_error(G.ctx[r]));
+        uint32_t m = G.rank[r].ctx->slots[0].last.n_valid;
         buf.resize((size_t)(m ? m : 1) * 4);
-        st = gm_get_cropped_xyz(G.ctx[r], 0, buf.data(), m ? m : 1, &m);
-        if (st != GM_OK) return gfail(&G, st, gm_last_error(G.ctx[r]));
+        const gm_status st = gm_get_cropped_xyz(G.rank[r].ctx, 0, buf.data(), m ? m : 1, &m);
+        if (st != GM_OK) return gfail(&G, st, gm_last_error(G.rank[r].ctx));
         lab.assign(m ? m : 1, 0);
         if (with_labels && m) {
-            Slot &sl = G.ctx[r]->slots[0];
-            if (hipSetDevice(G.devices[r]) != hipSuccess ||
+            Slot &sl = G.rank[r].ctx->slots[0];
+            if (hipSetDevice(G.rank[r].device) != hipSuccess ||
                 hipMemcpyAsync(lab.data(), sl.labels, m, hipMemcpyDeviceToHost, sl.stream) != hipSuccess ||
                 hipStreamSynchronize(sl.stream) != hipSuccess)
                 return gfail(&G, GM_ERR_DEVICE, "gm_group: D2H of a rank's labels failed");
         }
         for (uint32_t i = 0; i < m; ++i) {
-            uint32_t local;
-            memcpy(&local, &buf[4 * (size_t)i + 3], 4);
-            if (local >= G.row_ids[r].size()) return gfail(&G, GM_ERR_DEVICE, "gm_group: a rank's row index is out of range");
-            all.push_back(MergedRow{G.row_ids[r][local], buf[4 * (size_t)i], buf[4 * (size_t)i + 1], buf[4 * (size_t)i + 2], lab[i]});
+            uint32_t row;
+            if (!input_row(G, r, &buf[4 * (size_t)i + 3], &row)) return gfail(&G, GM_ERR_DEVICE, "gm_group: a rank's row index is out of range");
+            all.push_back(MergedRow{row, buf[4 * (size_t)i], buf[4 * (size_t)i + 1], buf[4 * (size_t)i + 2], lab[i]});
         }
     }
     std::stable_sort(all.begin(), all.end(), [](const MergedRow &a, const MergedRow &b) { return a.id < b.id; });
@@ -383,8 +306,8 @@ gm_status merge_voxels(gm_group &G, const std::vector<gm_frame_result> &rr)
         for (uint32_t r = 0; r < G.n; ++r) {
             uint32_t v = rr[r].n_voxels, got = 0;
             cen.resize((size_t)(v ? v : 1) * 4);
-            const gm_status st = gm_get_voxel_centroids(G.ctx[r], 0, cen.data(), v ? v : 1, &got);
-            if (st != GM_OK) return gfail(&G, st, gm_last_error(G.ctx[r]));
+            const gm_status st = gm_get_voxel_centroids(G.rank[r].ctx, 0, cen.data(), v ? v : 1, &got);
+            if (st != GM_OK) return gfail(&G, st, gm_last_error(G.rank[r].ctx));
             for (uint32_t i = 0; i < got; ++i) {
                 VoxRow w;
                 w.kx = lattice_cell(cen[4 * i], inv); w.ky = lattice_cell(cen[4 * i + 1], inv); w.kz = lattice_cell(cen[4 * i + 2], inv);
@@ -393,14 +316,14 @@ gm_status merge_voxels(gm_group &G, const std::vector<gm_frame_result> &rr)
             }
         }
     } else {
-        const VoxDense vd = gm_make_vox_dense(G.ctx[0], G.ctx[0]->slots[0].cap);
+        const VoxDense vd = gm_make_vox_dense(G.rank[0].ctx, G.rank[0].ctx->slots[0].cap);
         if (!vd.enabled) return gfail(&G, GM_ERR_UNSUPPORTED, "gm_group: voxel lattice neither cuttable nor dense");
         const size_t cells = (size_t)vd.dim * vd.dim * vd.dim;
         std::vector<VoxCell> sum(cells), part(cells);
         memset(sum.data(), 0, cells * sizeof(VoxCell));
         for (uint32_t r = 0; r < G.n; ++r) {
-            Slot &sl = G.ctx[r]->slots[0];
-            if (hipSetDevice(G.devices[r]) != hipSuccess ||
+            Slot &sl = G.rank[r].ctx->slots[0];
+            if (hipSetDevice(G.rank[r].device) != hipSuccess ||
                 hipMemcpy(part.data(), sl.vox_table, cells * sizeof(VoxCell), hipMemcpyDeviceToHost) != hipSuccess)
                 return gfail(&G, GM_ERR_DEVICE, "gm_group: D2H of a rank's voxel table failed");
             for (size_t c = 0; c < cells; ++c) { sum[c].sx += part[c].sx; sum[c].sy += part[c].sy; sum[c].sz += part[c].sz; sum[c].cnt += part[c].cnt; }
@@ -425,27 +348,143 @@ gm_status merge_voxels(gm_group &G, const std::vector<gm_frame_result> &rr)
     return GM_OK;
 }
 
+// ---- the steps of gm_group_process_frame, in its order.  Reset (whatever happens to the new frame, the accessors must
+// not pair its rows with an older frame's results), then what a sharded frame asks of its cloud
+gm_status begin_frame(gm_group &G, const gm_cloud *cloud)
+{
+    G.have_frame = false;
+    G.have_fit = false;
+    G.last = gm_frame_result{};
+    G.vox_cen.clear(); G.vox_nrm.clear(); G.vox_near.clear(); G.vox_nrm_valid = false;
+    if (cloud->flags & GM_CLOUD_DEVICE) return gfail(&G, GM_ERR_UNSUPPORTED, "gm_group_process_frame cuts the slabs on the host: pass host rows");
+    // (the fit of a sharded frame is a stage call of its own on the resident slabs: gm_group_fit_cylinder)
+    if (G.cfg.flags & GM_CFG_CYLINDER_FIT) return gfail(&G, GM_ERR_UNSUPPORTED, "gm_group_process_frame: GM_CFG_CYLINDER_FIT is not supported on sharded frames (call gm_group_fit_cylinder after the frame, or stream frames instead)");
+    const uint64_t n = cloud->n_points, step = cloud->point_step;
+    if (n && !cloud->data) return gfail(&G, GM_ERR_INVALID_ARG, "gm_cloud.data is NULL");
+    if (n && (step < 12 || (uint64_t)cloud->off_x + 4 > step || (uint64_t)cloud->off_y + 4 > step || (uint64_t)cloud->off_z + 4 > step))
+        return gfail(&G, GM_ERR_INVALID_ARG, "gm_cloud: x/y/z offsets do not fit in point_step");
+    return GM_OK;
+}
+
+// every rank runs the unchanged single-GPU pipeline on its slab, asynchronously, and packs its record behind it
+gm_status submit_slabs(gm_group &G, const gm_cloud *cloud, const CutPlan &plan)
+{
+    for (uint32_t r = 0; r < G.n; ++r) {
+        gm_group::Rank &k = G.rank[r];
+        gm_status st = gm_set_owned_range(k.ctx, G.edges[r], G.edges[r + 1]);
+        if (st != GM_OK) return fail_drained(G, st, gm_last_error(k.ctx));
+        gm_cloud c = *cloud;
+        c.data = plan.total[r] ? k.prow.p : nullptr;
+        c.n_points = plan.total[r];
+        c.flags = (cloud->flags & GM_CLOUD_BIGENDIAN) | GM_CLOUD_PINNED;
+        st = gm_submit_frame(k.ctx, 0, &c);
+        if (st != GM_OK) return fail_drained(G, st, std::string("rank ") + std::to_string(r) + ": " + gm_last_error(k.ctx));
+        hipLaunchKernelGGL(k_pack_record, dim3(1), dim3(64), 0, k.stream(), (const FrameOut *)k.ctx->slots[0].d_out, c.n_points, k.d_rec.p);
+    }
+    return GM_OK;
+}
+
+// the frame's exchange, rank 0's copy of the gathered records on the host, and every rank's frame done
+gm_status gather_records(gm_group &G, std::vector<gm_frame_result> &rr)
+{
+    gm_status st;
+    if ((st = all_gather(G, kRecLen, [&](uint32_t q) { return G.rank[q].d_rec.p; }, [&](uint32_t r) { return G.rank[r].d_all.p; })) != GM_OK) return st;
+    hipSetDevice(G.rank[0].device);
+    if (hipMemcpyAsync(G.h_all, G.rank[0].d_all, sizeof(double) * kRecLen * G.n, hipMemcpyDeviceToHost, G.rank[0].stream()) != hipSuccess)
+        return fail_drained(G, GM_ERR_DEVICE, "D2H of the gathered records failed");
+    for (uint32_t r = 0; r < G.n; ++r) {
+        st = gm_wait_frame(G.rank[r].ctx, 0, &rr[r]);
+        if (st != GM_OK) return fail_drained(G, st, std::string("rank ") + std::to_string(r) + ": " + gm_last_error(G.rank[r].ctx));
+    }
+    hipSetDevice(G.rank[0].device);
+    if (hipStreamSynchronize(G.rank[0].stream()) != hipSuccess) return fail_drained(G, GM_ERR_DEVICE, "stream sync failed");
+    return GM_OK;
+}
+
+// scatter summed in rank order (deterministic) and solved; every rank holds the same gathered records, rank 0's copy is read
+gm_frame_result merge_records(const gm_group &G, uint32_t n_in, uint32_t n_inside)
+{
+    gm_frame_result out = {};
+    out.n_in = n_in; out.n_cropped = n_inside;
+    for (uint32_t r = 0; r < G.n; ++r) {
+        const double *rec = G.h_all + (size_t)r * kRecLen;
+        for (int k = 0; k < 6; ++k) out.scatter[k] += rec[k];
+        out.n_valid += (uint32_t)rec[8];
+    }
+    double w[3], V[9];
+    eig3_sym_eigen_signs(out.scatter, w, V);
+    for (int k = 0; k < 3; ++k) { out.eigenvalues[k] = (float)w[k]; out.center_axis[k] = (float)V[k]; }
+    for (int k = 0; k < 9; ++k) out.eigenvectors[k] = (float)V[k];
+    return out;
+}
+
+// Fitted primitives (model 0: plane, 1: cylinder): every rank's fit is a candidate for the whole frame; each rank counts
+// every candidate's inliers on its own resident valid cloud (owned points only: the counts add up to the count on the
+// unsharded frame); the largest total wins, lowest rank on ties.  One process sees every rank: the counts are summed here.
+gm_status vote(gm_group &G, int model, const std::vector<gm_frame_result> &rr, gm_frame_result &out)
+{
+    if (!(G.cfg.flags & (model == 0 ? GM_CFG_RANSAC_PLANE : GM_CFG_RANSAC_CYLINDER))) return GM_OK;
+    const int w0 = model == 0 ? 10 : 14, wl = model == 0 ? 4 : 7;
+    std::vector<float> cand;
+    std::vector<uint32_t> owner;
+    for (uint32_t r = 0; r < G.n; ++r) {
+        const double *rec = G.h_all + (size_t)r * kRecLen;
+        bool ok = rec[21 + model] > 0;
+        for (int k = 0; k < wl; ++k) ok = ok && std::isfinite(rec[w0 + k]);
+        if (!ok) continue;
+        for (int k = 0; k < wl; ++k) cand.push_back((float)rec[w0 + k]);
+        owner.push_back(r);
+    }
+    if (owner.empty()) return GM_OK;
+    std::vector<long long> totalc(owner.size(), 0);
+    std::vector<int32_t> cnt(owner.size());
+    for (uint32_t r = 0; r < G.n; ++r) {
+        const gm_status st = gm_score_frame(G.rank[r].ctx, 0, model, cand.data(), (uint32_t)owner.size(), G.cfg.ransac_threshold, 0, cnt.data());
+        if (st != GM_OK) return gfail(&G, st, gm_last_error(G.rank[r].ctx));
+        for (size_t k = 0; k < owner.size(); ++k) totalc[k] += cnt[k];
+    }
+    size_t best = 0;
+    for (size_t k = 1; k < owner.size(); ++k) if (totalc[k] > totalc[best]) best = k;
+    const gm_frame_result &src = rr[owner[best]];
+    if (model == 0) {
+        out.plane_inliers = (uint32_t)totalc[best];
+        for (int k = 0; k < 4; ++k) { out.plane[k] = src.plane[k]; out.plane_refit[k] = src.plane_refit[k]; }
+    } else {
+        out.cylinder_inliers = (uint32_t)totalc[best];
+        for (int k = 0; k < 7; ++k) out.cylinder[k] = src.cylinder[k];
+        for (int k = 0; k < 3; ++k) out.cylinder_axis_refit[k] = src.cylinder_axis_refit[k];
+    }
+    return GM_OK;
+}
+
+// The head of the calls that write `count` rows of the sharded frame.  unmet: the message of the call's own precondition
+// where it does not hold.  On GM_OK with a count there are rows to write and a buffer that takes them.
+gm_status get_head(gm_group &G, const char *unmet, uint32_t count, const void *out, uint32_t capacity, uint32_t *n_out)
+{
+    if (!G.have_frame) { if (n_out) *n_out = 0; return gfail(&G, GM_ERR_NOT_READY, "gm_group: no completed sharded frame"); }
+    if (unmet) return gfail(&G, GM_ERR_NOT_READY, unmet);
+    if (n_out) *n_out = count;
+    if (count > capacity) return gfail(&G, GM_ERR_CAPACITY, "output buffer too small");
+    if (count && !out) return gfail(&G, GM_ERR_INVALID_ARG, "output pointer is NULL");
+    return GM_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 const char *gm_group_last_error(const gm_group *grp) { return grp ? grp->err.c_str() : g_group_create_err.c_str(); }
 uint32_t gm_group_size(const gm_group *grp) { return grp ? grp->n : 0u; }
-gm_ctx *gm_group_ctx(gm_group *grp, uint32_t rank) { return (grp && rank < grp->n) ? grp->ctx[rank] : nullptr; }
+gm_ctx *gm_group_ctx(gm_group *grp, uint32_t rank) { return (grp && rank < grp->n) ? grp->rank[rank].ctx : nullptr; }
 
 void gm_group_destroy(gm_group *grp)
 {
     if (!grp) return;
-    for (uint32_t r = 0; r < grp->n; ++r) {
-        if (r < grp->ctx.size() && grp->ctx[r]) hipSetDevice(grp->devices[r]);
-        if (r < grp->comms.size() && grp->comms[r] && grp->rccl.CommDestroy) grp->rccl.CommDestroy(grp->comms[r]);
-        if (r < grp->ev.size() && grp->ev[r]) hipEventDestroy(grp->ev[r]);
-        if (r < grp->ctx.size() && grp->ctx[r]) gm_destroy(grp->ctx[r]);   // (drains the rank's streams first)
-        // the rank's buffers go here, with its device current (not when the vectors are destroyed)
-        if (r < grp->d_rec.size()) grp->d_rec[r].release();
-        if (r < grp->d_all.size()) grp->d_all[r].release();
-        if (r < grp->prow.size()) grp->prow[r].release();
-        if (r < grp->fitr.size()) gm_group::FitRank(std::move(grp->fitr[r]));   // (a temporary that takes the blocks and dies here)
+    // per rank: communicator (one exists only behind a loaded RCCL, so CommDestroy is set), event, context, blocks
+    for (size_t r = 0; r < grp->rank.size(); ++r) {
+        if (grp->rank[r].ctx) hipSetDevice(grp->rank[r].device);
+        if (grp->comms[r]) grp->rccl.CommDestroy(grp->comms[r]);
+        grp->rank[r].release();
     }
     delete grp;
 }
@@ -457,8 +496,7 @@ gm_status gm_group_create(const gm_config *cfg, const int32_t *devices, uint32_t
     *out = nullptr;
     gm_group *g = new (std::nothrow) gm_group();
     if (!g) return gfail(nullptr, GM_ERR_OOM, "host allocation failed");
-    g->cfg = *cfg; g->flags = flags; g->n = n_ranks;
-    g->devices.assign(devices, devices + n_ranks);
+    g->cfg = *cfg; g->n = n_ranks;
     bool repeats = false;
     for (uint32_t a = 0; a < n_ranks; ++a)
         for (uint32_t b = a + 1; b < n_ranks; ++b) repeats |= devices[a] == devices[b];
@@ -467,20 +505,19 @@ gm_status gm_group_create(const gm_config *cfg, const int32_t *devices, uint32_t
         return gfail(nullptr, GM_ERR_INVALID_ARG, "gm_group_create: a device is listed twice (pass GM_GROUP_LOOPBACK to allow it)");
     }
     g->loopback = repeats;
-    g->ctx.assign(n_ranks, nullptr); g->d_rec.resize(n_ranks); g->d_all.resize(n_ranks);
-    g->ev.assign(n_ranks, nullptr); g->comms.assign(n_ranks, nullptr);
-    g->prow.resize(n_ranks); g->row_ids.resize(n_ranks);
-    g->next_slot.assign(n_ranks, 0u);
+    g->rank.resize(n_ranks);
+    g->devices.assign(devices, devices + n_ranks); g->comms.assign(n_ranks, nullptr);
     auto bail = [&](gm_status st, const std::string &msg) { g_group_create_err = msg; gm_group_destroy(g); return st; };
     for (uint32_t r = 0; r < n_ranks; ++r) {
+        gm_group::Rank &k = g->rank[r];
         gm_config c = *cfg;
-        c.device = devices[r];
+        c.device = k.device = devices[r];
         c.ransac_seed = cfg->ransac_seed + r;   // ranks draw different hypotheses: more candidates for the vote
-        const gm_status st = gm_create(&c, &g->ctx[r]);
+        const gm_status st = gm_create(&c, &k.ctx);
         if (st != GM_OK) return bail(st, std::string("gm_group_create: rank ") + std::to_string(r) + ": " + gm_last_error(nullptr));
-        if (hipSetDevice(devices[r]) != hipSuccess || g->d_rec[r].reserve(kRecLen) != hipSuccess ||
-            g->d_all[r].reserve((size_t)kRecLen * n_ranks) != hipSuccess ||
-            hipEventCreateWithFlags(&g->ev[r], hipEventDisableTiming) != hipSuccess)
+        if (hipSetDevice(k.device) != hipSuccess || k.d_rec.reserve(kRecLen) != hipSuccess ||
+            k.d_all.reserve((size_t)kRecLen * n_ranks) != hipSuccess ||
+            hipEventCreateWithFlags(&k.ev, hipEventDisableTiming) != hipSuccess)
             return bail(GM_ERR_DEVICE, "gm_group_create: device allocation failed");
     }
     if (g->h_all.reserve((size_t)kRecLen * n_ranks) != hipSuccess)
@@ -501,149 +538,27 @@ gm_status gm_group_process_frame(gm_group *grp, const gm_cloud *cloud, gm_frame_
     gm_group &G = *grp;
     if (G.dead) return gfail(grp, GM_ERR_COMM, "gm_group: an earlier collective failed; destroy the group");
     if (!G.inflight.empty()) return gfail(grp, GM_ERR_NOT_READY, "gm_group_process_frame: streamed frames are still in flight (gm_group_wait_frame)");
-    // whatever happens below, the accessors must not pair this frame's rows with an older frame's results
-    G.have_frame = false;
-    G.have_fit = false;
-    G.last = gm_frame_result{};
-    G.vox_cen.clear(); G.vox_nrm.clear(); G.vox_near.clear(); G.vox_nrm_valid = false;
-    if (cloud->flags & GM_CLOUD_DEVICE) return gfail(grp, GM_ERR_UNSUPPORTED, "gm_group_process_frame cuts the slabs on the host: pass host rows");
-    // (the fit of a sharded frame is a stage call of its own on the resident slabs: gm_group_fit_cylinder)
-    if (G.cfg.flags & GM_CFG_CYLINDER_FIT) return gfail(grp, GM_ERR_UNSUPPORTED, "gm_group_process_frame: GM_CFG_CYLINDER_FIT is not supported on sharded frames (call gm_group_fit_cylinder after the frame, or stream frames instead)");
-    const uint32_t n = cloud->n_points;
-    const uint64_t step = cloud->point_step;
-    if (n && !cloud->data) return gfail(grp, GM_ERR_INVALID_ARG, "gm_cloud.data is NULL");
-    if (n && (step < 12 || (uint64_t)cloud->off_x + 4 > step || (uint64_t)cloud->off_y + 4 > step || (uint64_t)cloud->off_z + 4 > step))
-        return gfail(grp, GM_ERR_INVALID_ARG, "gm_cloud: x/y/z offsets do not fit in point_step");
+    gm_status st;
+    if ((st = begin_frame(G, cloud)) != GM_OK) return st;
     for (int k = 0; k < GM_GROUP_N_TIMINGS; ++k) G.timing[k] = 0.0;
     const double t0 = now_ms();
     CutPlan plan;
-    std::vector<uint32_t> total;
-    gm_status st;
-    try {   // (the cut allocates and starts threads: nothing may leave through the C ABI)
-        st = cut_rows(G, cloud, plan, total);
-    } catch (const std::bad_alloc &) {
-        return gfail(grp, GM_ERR_OOM, "gm_group_process_frame: host allocation failed in the slab cut");
-    } catch (const std::exception &e) {
-        return gfail(grp, GM_ERR_DEVICE, std::string("gm_group_process_frame: the slab cut failed: ") + e.what());
-    }
-    if (st != GM_OK) return st;
-    G.edges = plan.edges;
-    G.edges_on_lattice = plan.on_lattice;
+    if ((st = cut_slabs(G, cloud, plan)) != GM_OK) return st;
+    G.edges = plan.edges; G.edges_on_lattice = plan.on_lattice;
     const double t1 = now_ms();
-    // ---- every rank runs the unchanged single-GPU pipeline on its slab, asynchronously
-    auto fail_after_submit = [&](gm_status s, const std::string &msg) { drain(G); return gfail(grp, s, msg); };
-    for (uint32_t r = 0; r < G.n; ++r) {
-        st = gm_set_owned_range(G.ctx[r], G.edges[r], G.edges[r + 1]);
-        if (st != GM_OK) return fail_after_submit(st, gm_last_error(G.ctx[r]));
-        gm_cloud c = *cloud;
-        c.data = total[r] ? G.prow[r] : nullptr;
-        c.n_points = total[r];
-        c.flags = (cloud->flags & GM_CLOUD_BIGENDIAN) | GM_CLOUD_PINNED;
-        st = gm_submit_frame(G.ctx[r], 0, &c);
-        if (st != GM_OK) return fail_after_submit(st, std::string("rank ") + std::to_string(r) + ": " + gm_last_error(G.ctx[r]));
-        Slot &sl = G.ctx[r]->slots[0];
-        hipLaunchKernelGGL(k_pack_record, dim3(1), dim3(64), 0, sl.stream, (const FrameOut *)sl.d_out, c.n_points, G.d_rec[r]);
-        if (G.loopback) hipEventRecord(G.ev[r], sl.stream);
-    }
+    if ((st = submit_slabs(G, cloud, plan)) != GM_OK) return st;
     const double t2 = now_ms();
-    // ---- the one exchange step: all-gather of the per-rank records
-    if (!G.loopback) {
-        ncclResult_t rc = G.rccl.GroupStart();
-        for (uint32_t r = 0; r < G.n && rc == ncclSuccess; ++r) {
-            hipSetDevice(G.devices[r]);
-            rc = G.rccl.AllGather(G.d_rec[r], G.d_all[r], kRecLen, ncclDouble, G.comms[r], G.ctx[r]->slots[0].stream);
-        }
-        const ncclResult_t rc2 = G.rccl.GroupEnd();
-        if (rc == ncclSuccess) rc = rc2;
-        if (rc != ncclSuccess) {
-            // some ranks may have posted their half of the collective: their streams can block for good.  No drain (it
-            // could hang with them); the group refuses further work.
-            G.dead = true;
-            return gfail(grp, GM_ERR_COMM, std::string("ncclAllGather: ") + G.rccl.GetErrorString(rc));
-        }
-    } else {
-        // ranks on one device (tests on a 1-GPU box): the same gather by device copies, ordered by events
-        for (uint32_t r = 0; r < G.n; ++r) {
-            hipStream_t s = G.ctx[r]->slots[0].stream;
-            for (uint32_t q = 0; q < G.n; ++q) {
-                if (q != r) hipStreamWaitEvent(s, G.ev[q], 0);
-                hipMemcpyAsync(G.d_all[r] + (size_t)q * kRecLen, G.d_rec[q], sizeof(double) * kRecLen, hipMemcpyDeviceToDevice, s);
-            }
-        }
-    }
-    hipSetDevice(G.devices[0]);
-    if (hipMemcpyAsync(G.h_all, G.d_all[0], sizeof(double) * kRecLen * G.n, hipMemcpyDeviceToHost, G.ctx[0]->slots[0].stream) != hipSuccess)
-        return fail_after_submit(GM_ERR_DEVICE, "D2H of the gathered records failed");
     std::vector<gm_frame_result> rr(G.n);
-    for (uint32_t r = 0; r < G.n; ++r) {
-        st = gm_wait_frame(G.ctx[r], 0, &rr[r]);
-        if (st != GM_OK) return fail_after_submit(st, std::string("rank ") + std::to_string(r) + ": " + gm_last_error(G.ctx[r]));
-    }
-    hipSetDevice(G.devices[0]);
-    if (hipStreamSynchronize(G.ctx[0]->slots[0].stream) != hipSuccess) return fail_after_submit(GM_ERR_DEVICE, "stream sync failed");
+    if ((st = gather_records(G, rr)) != GM_OK) return st;
     const double t3 = now_ms();
-    // ---- merge (every rank holds the same gathered records; rank 0's copy is read)
-    gm_frame_result out;
-    memset(&out, 0, sizeof(out));
-    out.n_in = n;
-    out.n_cropped = plan.n_inside;
-    double M[6] = {0, 0, 0, 0, 0, 0};
-    for (uint32_t r = 0; r < G.n; ++r) {   // rank order: deterministic
-        const double *rec = G.h_all + (size_t)r * kRecLen;
-        for (int k = 0; k < 6; ++k) M[k] += rec[k];
-        out.n_valid += (uint32_t)rec[8];
-    }
-    for (int k = 0; k < 6; ++k) out.scatter[k] = M[k];
-    double w[3], V[9];
-    eig3_sym_eigen_signs(M, w, V);
-    for (int k = 0; k < 3; ++k) { out.eigenvalues[k] = (float)w[k]; out.center_axis[k] = (float)V[k]; }
-    for (int k = 0; k < 9; ++k) out.eigenvectors[k] = (float)V[k];
-    G.last = out;
+    gm_frame_result out = merge_records(G, cloud->n_points, plan.n_inside);
     if (G.cfg.flags & GM_CFG_VOXEL_GRID) {
         st = merge_voxels(G, rr);
-        if (st != GM_OK) { G.last = gm_frame_result{}; return st; }
-        out.n_voxels = G.last.n_voxels;
+        if (st == GM_OK) out.n_voxels = G.last.n_voxels;
     }
-    // fitted primitives: every rank's fit is a candidate for the whole frame; each rank counts every candidate's
-    // inliers on its own resident valid cloud (owned points only: the counts add up to the count on the unsharded
-    // frame); the largest total wins, lowest rank on ties.  One process sees every rank: the counts are summed here.
-    for (int model = 0; model < 2; ++model) {
-        const uint32_t flag = model == 0 ? GM_CFG_RANSAC_PLANE : GM_CFG_RANSAC_CYLINDER;
-        if (!(G.cfg.flags & flag)) continue;
-        const int w0 = model == 0 ? 10 : 14, wl = model == 0 ? 4 : 7;
-        std::vector<float> cand;
-        std::vector<uint32_t> owner;
-        for (uint32_t r = 0; r < G.n; ++r) {
-            const double *rec = G.h_all + (size_t)r * kRecLen;
-            bool ok = rec[21 + model] > 0;
-            for (int k = 0; k < wl; ++k) ok = ok && std::isfinite(rec[w0 + k]);
-            if (!ok) continue;
-            for (int k = 0; k < wl; ++k) cand.push_back((float)rec[w0 + k]);
-            owner.push_back(r);
-        }
-        if (owner.empty()) continue;
-        std::vector<long long> totalc(owner.size(), 0);
-        std::vector<int32_t> cnt(owner.size());
-        for (uint32_t r = 0; r < G.n; ++r) {
-            st = gm_score_frame(G.ctx[r], 0, model, cand.data(), (uint32_t)owner.size(), G.cfg.ransac_threshold, 0, cnt.data());
-            if (st != GM_OK) { G.last = gm_frame_result{}; return gfail(grp, st, gm_last_error(G.ctx[r])); }
-            for (size_t k = 0; k < owner.size(); ++k) totalc[k] += cnt[k];
-        }
-        size_t best = 0;
-        for (size_t k = 1; k < owner.size(); ++k) if (totalc[k] > totalc[best]) best = k;
-        const gm_frame_result &src = rr[owner[best]];
-        if (model == 0) {
-            out.plane_inliers = (uint32_t)totalc[best];
-            for (int k = 0; k < 4; ++k) { out.plane[k] = src.plane[k]; out.plane_refit[k] = src.plane_refit[k]; }
-        } else {
-            out.cylinder_inliers = (uint32_t)totalc[best];
-            for (int k = 0; k < 7; ++k) out.cylinder[k] = src.cylinder[k];
-            for (int k = 0; k < 3; ++k) out.cylinder_axis_refit[k] = src.cylinder_axis_refit[k];
-        }
-    }
-    float km = 0.f;
-    for (uint32_t r = 0; r < G.n; ++r) km = fmaxf(km, rr[r].normals_kernel_ms);
-    out.normals_kernel_ms = km;
+    for (int model = 0; model < 2 && st == GM_OK; ++model) st = vote(G, model, rr, out);
+    if (st != GM_OK) { G.last = gm_frame_result{}; return st; }
+    for (uint32_t r = 0; r < G.n; ++r) out.normals_kernel_ms = fmaxf(out.normals_kernel_ms, rr[r].normals_kernel_ms);
     const double t4 = now_ms();
     G.timing[GM_GROUP_T_CUT] = t1 - t0; G.timing[GM_GROUP_T_SUBMIT] = t2 - t1; G.timing[GM_GROUP_T_DEVICE] = t3 - t2;
     G.timing[GM_GROUP_T_MERGE] = t4 - t3; G.timing[GM_GROUP_T_TOTAL] = t4 - t0;
@@ -674,16 +589,10 @@ gm_status gm_group_get_edges(const gm_group *grp, double *edges, uint32_t capaci
 gm_status gm_group_get_cropped_xyz(gm_group *grp, float *xyzw, uint32_t capacity, uint32_t *n_out)
 {
     if (!grp) return GM_ERR_INVALID_ARG;
-    gm_group &G = *grp;
-    if (!G.have_frame) { if (n_out) *n_out = 0; return gfail(grp, GM_ERR_NOT_READY, "gm_group: no completed sharded frame"); }
-    const uint32_t total = G.last.n_valid;
-    if (n_out) *n_out = total;
-    if (total > capacity) return gfail(grp, GM_ERR_CAPACITY, "output buffer too small");
-    if (!total) return GM_OK;
-    if (!xyzw) return gfail(grp, GM_ERR_INVALID_ARG, "output pointer is NULL");
+    gm_status st = get_head(*grp, nullptr, grp->last.n_valid, xyzw, capacity, n_out);
+    if (st != GM_OK || !grp->last.n_valid) return st;
     std::vector<MergedRow> all;
-    const gm_status st = merged_rows(G, false, all);
-    if (st != GM_OK) return st;
+    if ((st = merged_rows(*grp, false, all)) != GM_OK) return st;
     for (size_t i = 0; i < all.size() && i < capacity; ++i) {
         xyzw[4 * i] = all[i].x; xyzw[4 * i + 1] = all[i].y; xyzw[4 * i + 2] = all[i].z;
         memcpy(&xyzw[4 * i + 3], &all[i].id, 4);
@@ -695,20 +604,13 @@ gm_status gm_group_get_cropped_xyz(gm_group *grp, float *xyzw, uint32_t capacity
 gm_status gm_group_get_labels(gm_group *grp, uint8_t *labels, uint32_t capacity, uint32_t *n_out)
 {
     if (!grp) return GM_ERR_INVALID_ARG;
-    gm_group &G = *grp;
-    if (!G.have_frame) { if (n_out) *n_out = 0; return gfail(grp, GM_ERR_NOT_READY, "gm_group: no completed sharded frame"); }
-    if (!(G.cfg.flags & (GM_CFG_RANSAC_PLANE | GM_CFG_RANSAC_CYLINDER)) && !G.have_fit) {
-        if (n_out) *n_out = 0;
-        return gfail(grp, GM_ERR_NOT_READY, "gm_group_get_labels: group created without a GM_CFG_RANSAC_* flag and no gm_group_fit_cylinder on this frame");
-    }
-    const uint32_t total = G.last.n_valid;
-    if (n_out) *n_out = total;
-    if (total > capacity) return gfail(grp, GM_ERR_CAPACITY, "output buffer too small");
-    if (!total) return GM_OK;
-    if (!labels) return gfail(grp, GM_ERR_INVALID_ARG, "output pointer is NULL");
+    const bool fitted = (grp->cfg.flags & (GM_CFG_RANSAC_PLANE | GM_CFG_RANSAC_CYLINDER)) || grp->have_fit;
+    if (!fitted && n_out) *n_out = 0;
+    gm_status st = get_head(*grp, fitted ? nullptr : "gm_group_get_labels: group created without a GM_CFG_RANSAC_* flag and no gm_group_fit_cylinder on this frame",
+                            grp->last.n_valid, labels, capacity, n_out);
+    if (st != GM_OK || !grp->last.n_valid) return st;
     std::vector<MergedRow> all;
-    const gm_status st = merged_rows(G, true, all);
-    if (st != GM_OK) return st;
+    if ((st = merged_rows(*grp, true, all)) != GM_OK) return st;
     for (size_t i = 0; i < all.size() && i < capacity; ++i) labels[i] = all[i].label;
     return GM_OK;
 }
@@ -716,15 +618,11 @@ gm_status gm_group_get_labels(gm_group *grp, uint8_t *labels, uint32_t capacity,
 gm_status gm_group_get_voxel_centroids(gm_group *grp, float *xyzc, uint32_t capacity, uint32_t *n_out)
 {
     if (!grp) return GM_ERR_INVALID_ARG;
-    gm_group &G = *grp;
-    if (!G.have_frame) { if (n_out) *n_out = 0; return gfail(grp, GM_ERR_NOT_READY, "gm_group: no completed sharded frame"); }
-    if (!(G.cfg.flags & GM_CFG_VOXEL_GRID)) return gfail(grp, GM_ERR_NOT_READY, "group created without GM_CFG_VOXEL_GRID");
-    const uint32_t V = (uint32_t)(G.vox_cen.size() / 4);
-    if (n_out) *n_out = V;
-    if (V > capacity) return gfail(grp, GM_ERR_CAPACITY, "output buffer too small");
-    if (V && !xyzc) return gfail(grp, GM_ERR_INVALID_ARG, "output pointer is NULL");
-    if (V) memcpy(xyzc, G.vox_cen.data(), (size_t)V * 16);
-    return GM_OK;
+    const char *unmet = (grp->cfg.flags & GM_CFG_VOXEL_GRID) ? nullptr : "group created without GM_CFG_VOXEL_GRID";
+    const uint32_t V = (uint32_t)(grp->vox_cen.size() / 4);
+    const gm_status st = get_head(*grp, unmet, V, xyzc, capacity, n_out);
+    if (st == GM_OK && V) memcpy(xyzc, grp->vox_cen.data(), (size_t)V * 16);
+    return st;
 }
 
 // The normal of every centroid's nearest valid point (normals->at(kIndices[0]) of the marker loop, src/tunnel_processing.cpp:
@@ -734,23 +632,18 @@ gm_status gm_group_get_voxel_normals(gm_group *grp, float *nxyzc, uint32_t capac
 {
     if (!grp) return GM_ERR_INVALID_ARG;
     gm_group &G = *grp;
-    if (!G.have_frame) { if (n_out) *n_out = 0; return gfail(grp, GM_ERR_NOT_READY, "gm_group: no completed sharded frame"); }
-    if ((G.cfg.flags & (GM_CFG_NEAREST | GM_CFG_VOXEL_GRID)) != (GM_CFG_NEAREST | GM_CFG_VOXEL_GRID))
-        return gfail(grp, GM_ERR_NOT_READY, "group created without GM_CFG_NEAREST | GM_CFG_VOXEL_GRID");
+    const bool flags_ok = (G.cfg.flags & (GM_CFG_NEAREST | GM_CFG_VOXEL_GRID)) == (GM_CFG_NEAREST | GM_CFG_VOXEL_GRID);
     const uint32_t V = (uint32_t)(G.vox_cen.size() / 4);
-    if (n_out) *n_out = V;
-    if (V > capacity) return gfail(grp, GM_ERR_CAPACITY, "output buffer too small");
-    if (!V) return GM_OK;
-    if (!nxyzc) return gfail(grp, GM_ERR_INVALID_ARG, "output pointer is NULL");
+    gm_status st = get_head(G, flags_ok ? nullptr : "group created without GM_CFG_NEAREST | GM_CFG_VOXEL_GRID", V, nxyzc, capacity, n_out);
+    if (st != GM_OK || !V) return st;
     if (!G.vox_nrm_valid) {
         G.vox_nrm.assign((size_t)V * 4, std::numeric_limits<float>::quiet_NaN());
         std::vector<unsigned long long> best_key(V, ~0ull);   // (distance bits << 32 | input row) of the winner so far
         std::vector<unsigned long long> keys;
         std::vector<float> nrm, pts;
         for (uint32_t r = 0; r < G.n; ++r) {
-            gm_ctx *c = G.ctx[r];
-            Slot &sl = c->slots[0];
-            if (hipSetDevice(G.devices[r]) != hipSuccess) return gfail(grp, GM_ERR_DEVICE, "hipSetDevice failed");
+            Slot &sl = G.rank[r].ctx->slots[0];
+            if (hipSetDevice(G.rank[r].device) != hipSuccess) return gfail(grp, GM_ERR_DEVICE, "hipSetDevice failed");
             if (sl.last.n_valid == 0) continue;
             // queries go through the rank's own centroid buffer in pieces of at most its capacity (its own centroids
             // were fetched by the merge already); results through its nearest-point scratch
@@ -769,10 +662,9 @@ gm_status gm_group_get_voxel_normals(gm_group *grp, float *nxyzc, uint32_t capac
                     return gfail(grp, GM_ERR_DEVICE, "gm_group: nearest-point search failed");
                 for (uint32_t i = 0; i < nq; ++i) {
                     if (keys[i] == ~0ull) continue;
-                    uint32_t local;
-                    memcpy(&local, &pts[4 * (size_t)i + 3], 4);
-                    if (local >= G.row_ids[r].size()) return gfail(grp, GM_ERR_DEVICE, "gm_group: a rank's row index is out of range");
-                    const unsigned long long k = (keys[i] & 0xFFFFFFFF00000000ull) | G.row_ids[r][local];
+                    uint32_t row;
+                    if (!input_row(G, r, &pts[4 * (size_t)i + 3], &row)) return gfail(grp, GM_ERR_DEVICE, "gm_group: a rank's row index is out of range");
+                    const unsigned long long k = (keys[i] & 0xFFFFFFFF00000000ull) | row;
                     if (k < best_key[q0 + i]) {
                         best_key[q0 + i] = k;
                         memcpy(&G.vox_nrm[4 * (size_t)(q0 + i)], &nrm[4 * (size_t)i], 16);
@@ -781,29 +673,14 @@ gm_status gm_group_get_voxel_normals(gm_group *grp, float *nxyzc, uint32_t capac
             }
         }
         // the winners' positions in the merged /choppedCloud (gm_group_get_voxel_nearest): rank of their input row
-        // among the valid rows
+        // among the valid rows, which merged_rows lists in ascending order
+        std::vector<MergedRow> all;
+        if ((st = merged_rows(G, false, all)) != GM_OK) return st;
         G.vox_near.assign(V, -1);
-        {
-            std::vector<uint32_t> valid_rows;
-            valid_rows.reserve(G.last.n_valid);
-            std::vector<float> buf;
-            for (uint32_t r = 0; r < G.n; ++r) {
-                uint32_t m = G.ctx[r]->slots[0].last.n_valid;
-                buf.resize((size_t)(m ? m : 1) * 4);
-                const gm_status st = gm_get_cropped_xyz(G.ctx[r], 0, buf.data(), m ? m : 1, &m);
-                if (st != GM_OK) return gfail(grp, st, gm_last_error(G.ctx[r]));
-                for (uint32_t i = 0; i < m; ++i) {
-                    uint32_t local;
-                    memcpy(&local, &buf[4 * (size_t)i + 3], 4);
-                    if (local < G.row_ids[r].size()) valid_rows.push_back(G.row_ids[r][local]);
-                }
-            }
-            std::sort(valid_rows.begin(), valid_rows.end());
-            for (uint32_t i = 0; i < V; ++i) {
-                if (best_key[i] == ~0ull) continue;
-                const uint32_t row = (uint32_t)(best_key[i] & 0xFFFFFFFFull);
-                G.vox_near[i] = (int32_t)(std::lower_bound(valid_rows.begin(), valid_rows.end(), row) - valid_rows.begin());
-            }
+        for (uint32_t i = 0; i < V; ++i) {
+            if (best_key[i] == ~0ull) continue;
+            const uint32_t row = (uint32_t)(best_key[i] & 0xFFFFFFFFull);
+            G.vox_near[i] = (int32_t)(std::lower_bound(all.begin(), all.end(), row, [](const MergedRow &a, uint32_t v) { return a.id < v; }) - all.begin());
         }
         G.vox_nrm_valid = true;
     }
@@ -814,19 +691,14 @@ gm_status gm_group_get_voxel_normals(gm_group *grp, float *nxyzc, uint32_t capac
 gm_status gm_group_get_voxel_nearest(gm_group *grp, int32_t *idx, uint32_t capacity, uint32_t *n_out)
 {
     if (!grp) return GM_ERR_INVALID_ARG;
-    gm_group &G = *grp;
-    if (!G.have_frame) { if (n_out) *n_out = 0; return gfail(grp, GM_ERR_NOT_READY, "gm_group: no completed sharded frame"); }
-    const uint32_t V = (uint32_t)(G.vox_cen.size() / 4);
-    if (n_out) *n_out = V;
-    if (V > capacity) return gfail(grp, GM_ERR_CAPACITY, "output buffer too small");
-    if (!V) return GM_OK;
-    if (!idx) return gfail(grp, GM_ERR_INVALID_ARG, "output pointer is NULL");
-    if (!G.vox_nrm_valid) {
+    const uint32_t V = (uint32_t)(grp->vox_cen.size() / 4);
+    gm_status st = get_head(*grp, nullptr, V, idx, capacity, n_out);
+    if (st != GM_OK || !V) return st;
+    if (!grp->vox_nrm_valid) {
         std::vector<float> tmp((size_t)V * 4);
-        const gm_status st = gm_group_get_voxel_normals(grp, tmp.data(), V, nullptr);
-        if (st != GM_OK) return st;
+        if ((st = gm_group_get_voxel_normals(grp, tmp.data(), V, nullptr)) != GM_OK) return st;
     }
-    memcpy(idx, G.vox_near.data(), (size_t)V * 4);
+    memcpy(idx, grp->vox_near.data(), (size_t)V * 4);
     return GM_OK;
 }
 
@@ -848,21 +720,15 @@ gm_status gm_group_fit_cylinder(gm_group *grp, const float init7[7], gm_cylinder
     const double tau = G.cfg.ransac_threshold;
     if (!(tau > 0.0) || !std::isfinite(tau)) return gfail(grp, GM_ERR_INVALID_ARG, "gm_group_fit_cylinder: ransac_threshold must be > 0");
     // work buffers (first call; a context created without GM_CFG_CYLINDER_FIT has none of its own)
-    G.fitr.resize(R);
-    for (uint32_t r = 0; r < R; ++r) {
-        gm_group::FitRank &f = G.fitr[r];
+    for (gm_group::Rank &f : G.rank) {
         if (f.rows) continue;
-        if (hipSetDevice(G.devices[r]) != hipSuccess) return gfail(grp, GM_ERR_DEVICE, "hipSetDevice failed");
-        hipError_t e = f.partial.reserve((size_t)kFitBlocks * kFitRowLen);
-        if (e == hipSuccess) e = f.ticket.reserve(1);
-        if (e == hipSuccess) e = hipMemset(f.ticket, 0, sizeof(uint32_t));   // k_cylfit resets it after every launch
-        if (e == hipSuccess) e = f.work.reserve(1);
-        if (e == hipSuccess) e = f.fit.reserve(1);
-        if (e == hipSuccess) e = f.rows8.reserve(16);
-        if (e == hipSuccess) e = f.plane_best.reserve(1);
-        if (e == hipSuccess) e = f.row.reserve((size_t)4 * kFitRowLen);
-        if (e == hipSuccess) e = f.rows.reserve((size_t)4 * kFitRowLen * R);
-        if (e != hipSuccess) return gfail(grp, GM_ERR_OOM, "gm_group_fit_cylinder: device allocation failed");
+        if (hipSetDevice(f.device) != hipSuccess) return gfail(grp, GM_ERR_DEVICE, "hipSetDevice failed");
+        if (f.partial.reserve((size_t)kFitBlocks * kFitRowLen) != hipSuccess || f.ticket.reserve(1) != hipSuccess ||
+            hipMemset(f.ticket, 0, sizeof(uint32_t)) != hipSuccess ||   // (k_cylfit resets it after every launch)
+            f.work.reserve(1) != hipSuccess || f.fit.reserve(1) != hipSuccess || f.rows8.reserve(16) != hipSuccess ||
+            f.plane_best.reserve(1) != hipSuccess || f.row.reserve((size_t)4 * kFitRowLen) != hipSuccess ||
+            f.rows.reserve((size_t)4 * kFitRowLen * R) != hipSuccess)
+            return gfail(grp, GM_ERR_OOM, "gm_group_fit_cylinder: device allocation failed");
     }
     if (G.h_fit.reserve(R) != hipSuccess) return gfail(grp, GM_ERR_OOM, "gm_group_fit_cylinder: hipHostMalloc failed");
     // the starting row (caller's, or the published cylinder: NaN when the frame has none) and the published plane
@@ -875,14 +741,13 @@ gm_status gm_group_fit_cylinder(gm_group *grp, const float init7[7], gm_cylinder
     for (int k = 0; k < 4; ++k) { rows8[8 + k] = G.last.plane[k]; has_plane = has_plane && std::isfinite(G.last.plane[k]); }
     const uint32_t plane_best = has_plane ? 0u : 0xFFFFFFFFu;
     std::vector<CylFitArgs> args(R);
-    auto fail_enqueued = [&](gm_status s, const std::string &msg) { drain(G); return gfail(grp, s, msg); };
     for (uint32_t r = 0; r < R; ++r) {
-        gm_group::FitRank &f = G.fitr[r];
-        Slot &sl = G.ctx[r]->slots[0];
-        if (hipSetDevice(G.devices[r]) != hipSuccess ||
+        gm_group::Rank &f = G.rank[r];
+        Slot &sl = f.ctx->slots[0];
+        if (hipSetDevice(f.device) != hipSuccess ||
             hipMemcpyAsync(f.rows8, rows8, sizeof(rows8), hipMemcpyHostToDevice, sl.stream) != hipSuccess ||
             hipMemcpyAsync(f.plane_best, &plane_best, sizeof(uint32_t), hipMemcpyHostToDevice, sl.stream) != hipSuccess)
-            return fail_enqueued(GM_ERR_DEVICE, "gm_group_fit_cylinder: upload of the starting rows failed");
+            return fail_drained(G, GM_ERR_DEVICE, "gm_group_fit_cylinder: upload of the starting rows failed");
         // plane relabel: every valid point 1 if it is an inlier of the published plane (the RANSAC's fp32 predicate), else 0
         launch_label(0, sl.crop4, sl.labels, 0, 1, &sl.ctr->n_valid, sl.last.n_valid, f.rows8 + 8, nullptr, f.plane_best,
                      tau, 1, nullptr, nullptr, 0, sl.stream);
@@ -895,66 +760,40 @@ gm_status gm_group_fit_cylinder(gm_group *grp, const float init7[7], gm_cylinder
         a.tau = tau;
     }
     for (int pass = 0; pass < 4; ++pass) {
+        // rank q's row -> rows[pass][q] on every rank (per-pass buffers: no rank overwrites a row still being copied)
+        auto row = [&](uint32_t q) { return G.rank[q].row + (size_t)pass * kFitRowLen; };
+        auto rows = [&](uint32_t r) { return G.rank[r].rows + (size_t)pass * kFitRowLen * R; };
         for (uint32_t r = 0; r < R; ++r) {
-            hipSetDevice(G.devices[r]);
-            hipStream_t s = G.ctx[r]->slots[0].stream;
+            hipSetDevice(G.rank[r].device);
             CylFitArgs a = args[r];
-            a.rank_row = G.fitr[r].row + (size_t)pass * kFitRowLen;
-            launch_cylinder_fit_pass(a, pass, s);
-            if (G.loopback) hipEventRecord(G.ev[r], s);
+            a.rank_row = row(r);
+            launch_cylinder_fit_pass(a, pass, G.rank[r].stream());
         }
-        // the exchange of this pass: rank q's row -> rows[pass][q] on every rank (per-pass buffers: no rank overwrites a
-        // row that another rank may still be copying)
-        if (!G.loopback) {
-            ncclResult_t rc = G.rccl.GroupStart();
-            for (uint32_t r = 0; r < R && rc == ncclSuccess; ++r) {
-                hipSetDevice(G.devices[r]);
-                rc = G.rccl.AllGather(G.fitr[r].row + (size_t)pass * kFitRowLen, G.fitr[r].rows + (size_t)pass * kFitRowLen * R, kFitRowLen,
-                                      ncclDouble, G.comms[r], G.ctx[r]->slots[0].stream);
-            }
-            const ncclResult_t rc2 = G.rccl.GroupEnd();
-            if (rc == ncclSuccess) rc = rc2;
-            if (rc != ncclSuccess) {   // as in gm_group_process_frame: no drain, the group refuses further work
-                G.dead = true;
-                return gfail(grp, GM_ERR_COMM, std::string("ncclAllGather: ") + G.rccl.GetErrorString(rc));
-            }
-        } else {
-            for (uint32_t r = 0; r < R; ++r) {
-                hipSetDevice(G.devices[r]);
-                hipStream_t s = G.ctx[r]->slots[0].stream;
-                double *dst = G.fitr[r].rows + (size_t)pass * kFitRowLen * R;
-                for (uint32_t q = 0; q < R; ++q) {
-                    if (q != r) hipStreamWaitEvent(s, G.ev[q], 0);
-                    hipMemcpyAsync(dst + (size_t)q * kFitRowLen, G.fitr[q].row + (size_t)pass * kFitRowLen, sizeof(double) * kFitRowLen,
-                                   hipMemcpyDeviceToDevice, s);
-                }
-            }
-        }
+        if (const gm_status st = all_gather(G, kFitRowLen, row, rows); st != GM_OK) return st;
         for (uint32_t r = 0; r < R; ++r) {
-            hipSetDevice(G.devices[r]);
-            launch_cylinder_fit_merge(args[r], pass, G.fitr[r].rows + (size_t)pass * kFitRowLen * R, R, G.ctx[r]->slots[0].stream);
+            hipSetDevice(G.rank[r].device);
+            launch_cylinder_fit_merge(args[r], pass, rows(r), R, G.rank[r].stream());
         }
     }
     for (uint32_t r = 0; r < R; ++r) {
-        hipSetDevice(G.devices[r]);
-        if (hipMemcpyAsync(&G.h_fit[r], G.fitr[r].fit, sizeof(gm_cylinder_fit), hipMemcpyDeviceToHost, G.ctx[r]->slots[0].stream) != hipSuccess)
-            return fail_enqueued(GM_ERR_DEVICE, "gm_group_fit_cylinder: D2H of a rank's fit failed");
+        hipSetDevice(G.rank[r].device);
+        if (hipMemcpyAsync(&G.h_fit[r], G.rank[r].fit, sizeof(gm_cylinder_fit), hipMemcpyDeviceToHost, G.rank[r].stream()) != hipSuccess)
+            return fail_drained(G, GM_ERR_DEVICE, "gm_group_fit_cylinder: D2H of a rank's fit failed");
     }
     for (uint32_t r = 0; r < R; ++r) {
-        hipSetDevice(G.devices[r]);
-        if (hipStreamSynchronize(G.ctx[r]->slots[0].stream) != hipSuccess || hipGetLastError() != hipSuccess)
-            return fail_enqueued(GM_ERR_DEVICE, std::string("gm_group_fit_cylinder: rank ") + std::to_string(r) + ": the fit's launches failed");
+        hipSetDevice(G.rank[r].device);
+        if (hipStreamSynchronize(G.rank[r].stream()) != hipSuccess || hipGetLastError() != hipSuccess)
+            return fail_drained(G, GM_ERR_DEVICE, std::string("gm_group_fit_cylinder: rank ") + std::to_string(r) + ": the fit's launches failed");
     }
     // every rank solved the same sums: the records must agree bit for bit (padding excluded)
     const size_t cmp = offsetof(gm_cylinder_fit, model) + sizeof(((gm_cylinder_fit *)nullptr)->model);
     for (uint32_t r = 1; r < R; ++r)
         if (memcmp(&G.h_fit[r], &G.h_fit[0], cmp) != 0)
             return gfail(grp, GM_ERR_DEVICE, std::string("gm_group_fit_cylinder: rank ") + std::to_string(r) + "'s fit differs from rank 0's");
-    gm_cylinder_fit f = G.h_fit[0];
-    f.struct_size = (uint32_t)sizeof(gm_cylinder_fit);
-    G.last_fit = f;
+    G.last_fit = G.h_fit[0];
+    G.last_fit.struct_size = (uint32_t)sizeof(gm_cylinder_fit);
     G.have_fit = true;
-    *out = f;
+    *out = G.last_fit;
     return GM_OK;
 }
 
@@ -977,27 +816,27 @@ gm_status gm_group_submit_frame(gm_group *grp, const gm_cloud *cloud)
     gm_group &G = *grp;
     if (G.dead) return gfail(grp, GM_ERR_COMM, "gm_group: an earlier collective failed; destroy the group");
     uint32_t cap = 0;
-    for (uint32_t r = 0; r < G.n; ++r) cap += G.ctx[r]->n_slots;
+    for (uint32_t r = 0; r < G.n; ++r) cap += G.rank[r].ctx->n_slots;
     if (G.inflight.size() >= cap) return gfail(grp, GM_ERR_NOT_READY, "gm_group_submit_frame: every slot holds a frame (gm_group_wait_frame first)");
     // the next device in turn that has a free slot (slots of a rank are used in ring order, so the oldest frees first)
     for (uint32_t tries = 0; tries < G.n; ++tries) {
         const uint32_t r = (G.next_rank + tries) % G.n;
         uint32_t used = 0;
         for (const gm_group::Ticket &t : G.inflight) used += t.rank == r ? 1u : 0u;
-        if (used >= G.ctx[r]->n_slots) continue;
-        const uint32_t slot = G.next_slot[r];
+        if (used >= G.rank[r].ctx->n_slots) continue;
+        const uint32_t slot = G.rank[r].next_slot;
         // a sharded frame (also one that failed half-way) leaves the ranks with slab ranges: rank 0 owns (-inf, edge[1]),
         // so BOTH ends have to be looked at -- a streamed frame is a whole frame, every point of it is the rank's own
-        if (G.ctx[r]->own_lo != -std::numeric_limits<double>::infinity() ||
-            G.ctx[r]->own_hi != std::numeric_limits<double>::infinity()) {
-            const gm_status st = gm_set_owned_range(G.ctx[r], -std::numeric_limits<double>::infinity(), std::numeric_limits<double>::infinity());
-            if (st != GM_OK) return gfail(grp, st, gm_last_error(G.ctx[r]));
+        if (G.rank[r].ctx->own_lo != -std::numeric_limits<double>::infinity() ||
+            G.rank[r].ctx->own_hi != std::numeric_limits<double>::infinity()) {
+            const gm_status st = gm_set_owned_range(G.rank[r].ctx, -std::numeric_limits<double>::infinity(), std::numeric_limits<double>::infinity());
+            if (st != GM_OK) return gfail(grp, st, gm_last_error(G.rank[r].ctx));
         }
-        const gm_status st = gm_submit_frame(G.ctx[r], slot, cloud);
-        if (st != GM_OK) return gfail(grp, st, std::string("rank ") + std::to_string(r) + ": " + gm_last_error(G.ctx[r]));
+        const gm_status st = gm_submit_frame(G.rank[r].ctx, slot, cloud);
+        if (st != GM_OK) return gfail(grp, st, std::string("rank ") + std::to_string(r) + ": " + gm_last_error(G.rank[r].ctx));
         G.have_frame = false;   // slot 0 of the ranks no longer holds a sharded frame
         G.inflight.push_back(gm_group::Ticket{r, slot});
-        G.next_slot[r] = (slot + 1) % G.ctx[r]->n_slots;
+        G.rank[r].next_slot = (slot + 1) % G.rank[r].ctx->n_slots;
         G.next_rank = (r + 1) % G.n;
         return GM_OK;
     }
@@ -1010,8 +849,8 @@ gm_status gm_group_poll_frame(gm_group *grp)
     gm_group &G = *grp;
     if (G.inflight.empty()) return GM_ERR_NOT_READY;
     const gm_group::Ticket t = G.inflight.front();
-    const gm_status st = gm_poll_frame(G.ctx[t.rank], t.slot);
-    if (st != GM_OK && st != GM_ERR_NOT_READY) return gfail(grp, st, std::string("rank ") + std::to_string(t.rank) + ": " + gm_last_error(G.ctx[t.rank]));
+    const gm_status st = gm_poll_frame(G.rank[t.rank].ctx, t.slot);
+    if (st != GM_OK && st != GM_ERR_NOT_READY) return gfail(grp, st, std::string("rank ") + std::to_string(t.rank) + ": " + gm_last_error(G.rank[t.rank].ctx));
     return st;
 }
 
@@ -1024,8 +863,8 @@ gm_status gm_group_wait_frame(gm_group *grp, gm_frame_result *res, uint32_t *ran
     G.inflight.pop_front();
     if (rank_out) *rank_out = t.rank;
     if (slot_out) *slot_out = t.slot;
-    const gm_status st = gm_wait_frame(G.ctx[t.rank], t.slot, res);
-    if (st != GM_OK) return gfail(grp, st, std::string("rank ") + std::to_string(t.rank) + ": " + gm_last_error(G.ctx[t.rank]));
+    const gm_status st = gm_wait_frame(G.rank[t.rank].ctx, t.slot, res);
+    if (st != GM_OK) return gfail(grp, st, std::string("rank ") + std::to_string(t.rank) + ": " + gm_last_error(G.rank[t.rank].ctx));
     return GM_OK;
 }
 
