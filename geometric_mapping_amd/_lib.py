@@ -210,6 +210,25 @@ class WallCloudInfo(C.Structure):
                 ("blocks", C.c_uint64), ("points", C.c_uint64), ("below_min_count", C.c_uint64), ("empty", C.c_uint64)]
 
 
+GM_WALL_MESH_OUTWARD = 1 << 0
+GM_WALL_MESH_NO_WRAP = 1 << 1
+
+
+class WallMeshParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("cloud", WallCloudParams), ("max_step", C.c_double),
+                ("reserved", C.c_uint64)]
+
+
+class WallMeshTriangle(C.Structure):
+    _fields_ = [("v", C.c_uint32 * 3)]
+
+
+class WallMeshInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("wrapped", C.c_uint32), ("cloud", WallCloudInfo), ("quads", C.c_uint64),
+                ("quads_two", C.c_uint64), ("quads_one", C.c_uint64), ("quads_none", C.c_uint64), ("cut_by_step", C.c_uint64),
+                ("triangles", C.c_uint64)]
+
+
 class WallClearanceParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reference", C.c_uint32), ("min_count", C.c_uint32), ("reserved", C.c_uint32),
                 ("margin", C.c_double)]
@@ -419,6 +438,7 @@ def load():
     wregp, wrprmp, wrinfop, wrmetp = (C.POINTER(WallRegion), C.POINTER(WallRegionParams), C.POINTER(WallRegionsInfo),
                                       C.POINTER(WallRegionMetrics))
     wcprmp, wcptp, wcinfop = C.POINTER(WallCloudParams), C.POINTER(WallCloudPoint), C.POINTER(WallCloudInfo)
+    wmprmp, wmtrip, wminfop = C.POINTER(WallMeshParams), C.POINTER(WallMeshTriangle), C.POINTER(WallMeshInfo)
     wgprmp, wgstp, wgcellp, wginfop, wgrunp = (C.POINTER(WallClearanceParams), C.POINTER(WallClearanceStation),
                                                C.POINTER(WallClearanceCell), C.POINTER(WallClearanceInfo), C.POINTER(WallClearanceRun))
     wsprmp, wssump, wssecp, wsinfop, wsmetp = (C.POINTER(WallSectionParams), C.POINTER(WallSectionSums), C.POINTER(WallSection),
@@ -492,6 +512,10 @@ def load():
         "gm_wall_cloud_default_params": (None, [wcprmp]),
         "gm_wall_cloud_directions": (C.c_int, [wprmp, wcprmp, dp, u32, u32p]),
         "gm_wall_map_cloud": (C.c_int, [vp, u32, u32, wcprmp, wcinfop, wcptp, u64, u64p]),
+        "gm_wall_mesh_default_params": (None, [wmprmp]),
+        "gm_wall_map_mesh": (C.c_int, [vp, u32, u32, wmprmp, wminfop, wcptp, u64, wmtrip, u64, u64p, u64p]),
+        "gm_wall_mesh_triangulate": (C.c_int, [u32, u32, wcptp, u64, u32, C.c_double, wminfop, wmtrip, u64, u64p]),
+        "gm_wall_mesh_write_ply": (C.c_int, [C.c_char_p, wcptp, u64, wmtrip, u64]),
         "gm_wall_clearance_default_params": (None, [wgprmp]),
         "gm_wall_clearance_check_params": (C.c_int, [wprmp, wgprmp, i32p, u32, u8p, u32]),
         "gm_wall_map_clearance": (C.c_int, [vp, u32, u32, i32p, u32, u8p, wgprmp, wginfop, wgstp, u32, wgcellp, u64, u64p]),

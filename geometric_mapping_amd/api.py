@@ -12,6 +12,7 @@ Clouds are numpy float32 arrays [n,3]; normals are [n,4] = (nx,ny,nz,curvature).
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -524,6 +525,8 @@ WALL_CLOUD_POINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("mean", 
                              ("block", "<u4"), ("cells", "<u4"), ("count", "<u8")])   # gm_wall_cloud_point, 40 bytes
 _CLOUD_INFO = ("station0", "n_stations", "n_sectors", "blocks_stations", "blocks_sectors", "blocks", "points",
                "below_min_count", "empty")
+WALL_MESH_TRIANGLE = np.dtype("<u4")   # gm_wall_mesh_triangle is three of them: meshes are uint32 [nt, 3]
+_MESH_INFO = ("wrapped", "quads", "quads_two", "quads_one", "quads_none", "cut_by_step", "triangles")
 WALL_CHECK_POINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("delta", "<f4"), ("e", "<f4"), ("cell", "<i4"),
                              ("index", "<u4"), ("row", "<u4")])   # gm_wall_check_point, 32 bytes
 _CHECK_INFO = ("status", "threshold_q", "n_points", "plane", "beyond_gate", "outside", "unsurveyed", "unchanged",
@@ -798,6 +801,47 @@ def wall_cloud_directions(prm, **params):
     return out
 
 
+def _wall_mesh_info(info):
+    d = {k: int(getattr(info, k)) for k in _MESH_INFO}
+    d["cloud"] = {k: int(getattr(info.cloud, k)) for k in _CLOUD_INFO}
+    return d
+
+
+def _wall_mesh_rows(vertices):
+    v = np.ascontiguousarray(vertices, dtype=WALL_CLOUD_POINT).reshape(-1)
+    return v, (v.ctypes.data_as(C.POINTER(_lib.WallCloudPoint)) if len(v) else None)
+
+
+def wall_mesh_triangulate(NJ, NK, vertices, flags=0, max_step=0.0):
+    """gm_wall_mesh_triangulate (host only): the mesh's triangle rule on a vertex list -- WALL_CLOUD_POINT rows of a cloud
+    of NJ x NK blocks.  Returns (info dict with the mesh's counts and the cloud's grid under "cloud", uint32 [nt, 3])."""
+    L = _lib.load()
+    v, vp = _wall_mesh_rows(vertices)
+    info, got = _lib.WallMeshInfo(), C.c_uint64(0)
+    args = (int(NJ), int(NK), vp, len(v), int(flags), float(max_step), C.byref(info))
+    st = L.gm_wall_mesh_triangulate(*args, None, 0, C.byref(got))
+    if st != _lib.GM_OK:
+        raise _lib.GmError(st, "gm_wall_mesh_triangulate refused the arguments")
+    cap = int(got.value)
+    tri = np.zeros((max(cap, 1), 3), dtype=WALL_MESH_TRIANGLE)
+    if cap:
+        st = L.gm_wall_mesh_triangulate(*args, tri.ctypes.data_as(C.POINTER(_lib.WallMeshTriangle)), cap, C.byref(got))
+        if st != _lib.GM_OK:
+            raise _lib.GmError(st, "gm_wall_mesh_triangulate failed")
+    return _wall_mesh_info(info), tri[:cap].copy()
+
+
+def wall_mesh_write_ply(path, vertices, triangles):
+    """gm_wall_mesh_write_ply (host only): the mesh as a binary little-endian PLY file (x, y, z, mean, min, max per vertex;
+    uint vertex_indices per face)."""
+    v, vp = _wall_mesh_rows(vertices)
+    t = np.ascontiguousarray(triangles, dtype=WALL_MESH_TRIANGLE).reshape(-1, 3)
+    tp = t.ctypes.data_as(C.POINTER(_lib.WallMeshTriangle)) if len(t) else None
+    st = _lib.load().gm_wall_mesh_write_ply(os.fsencode(path), vp, len(v), tp, len(t))
+    if st != _lib.GM_OK:
+        raise _lib.GmError(st, f"gm_wall_mesh_write_ply could not write {path!r}")
+
+
 class WallMap:
     """One gm_wall_map: a device-resident developed wall map against a design cylinder, accumulated over posed frames
     (include/gm_hip.h states the rule).  Created by GeometricMapping.wall_map(); dies with its context."""
@@ -994,6 +1038,28 @@ class WallMap:
             self._ctx._check(self._L.gm_wall_map_cloud(self._h(), s0, n, C.byref(p), C.byref(info),
                                                        pts.ctypes.data_as(C.POINTER(_lib.WallCloudPoint)), cap, C.byref(got)))
         return {k: int(getattr(info, k)) for k in _CLOUD_INFO}, pts[:int(got.value)].copy()
+
+    def mesh(self, station0=0, n=None, flags=0, max_step=0.0, **cloud_params):
+        """gm_wall_map_mesh: stations [station0, station0 + n) as an indexed triangle mesh.  The vertices are cloud()'s rows
+        under the same cloud parameters; flags are GM_WALL_MESH_*; max_step > 0 drops triangles whose corners' means differ
+        by more.  Returns (info dict with the cloud's under "cloud", vertices, uint32 [nt, 3]).  A count query first, then
+        the sized call."""
+        s0, n = self._window(station0, n)
+        p = _lib.WallMeshParams()
+        self._L.gm_wall_mesh_default_params(C.byref(p))
+        p.flags, p.max_step, p.cloud = int(flags), float(max_step), self.cloud_params(**cloud_params)
+        info = _lib.WallMeshInfo()
+        nv, nt = C.c_uint64(0), C.c_uint64(0)
+        self._ctx._check(self._L.gm_wall_map_mesh(self._h(), s0, n, C.byref(p), C.byref(info), None, 0, None, 0, C.byref(nv),
+                                                  C.byref(nt)))
+        cv, ct = int(nv.value), int(nt.value)
+        pts = np.zeros(max(cv, 1), dtype=WALL_CLOUD_POINT)
+        tri = np.zeros((max(ct, 1), 3), dtype=WALL_MESH_TRIANGLE)
+        if cv:
+            self._ctx._check(self._L.gm_wall_map_mesh(
+                self._h(), s0, n, C.byref(p), C.byref(info), pts.ctypes.data_as(C.POINTER(_lib.WallCloudPoint)), cv,
+                tri.ctypes.data_as(C.POINTER(_lib.WallMeshTriangle)) if ct else None, ct, C.byref(nv), C.byref(nt)))
+        return _wall_mesh_info(info), pts[:int(nv.value)].copy(), tri[:int(nt.value)].copy()
 
     @staticmethod
     def clearance_params(**kw):

@@ -381,6 +381,24 @@ struct WallCloudArgs {
 };
 void launch_wall_cloud_merge(const WallCloudArgs &a, hipStream_t s);
 void launch_wall_cloud_compact(const WallCloudArgs &a, const ScanState &st, hipStream_t s);
+// k_wall_mesh.hip (gm_wall_map_mesh): the cloud's compaction with an emit step that also stores the survivor's index
+// (rank_base + its rank in the chunk) into rank[block of the window] and, for a step cut, its mean into mean[block]; then
+// per chunk of whole quad rows one k_compact over the chunk's 2 * quads slots
+constexpr int kWallMeshCounters = 6;               // u64: quads_two, quads_one, quads_none, cut_by_step, the chunk's triangles (low word), pad
+constexpr uint32_t kWallMeshDead = 0xFFFFFFFFu;    // rank of a block that did not become a point
+struct WallMeshArgs {
+    const uint32_t *rank;      // [NJ * NK] vertex index per block of the window, kWallMeshDead: not alive
+    const float *mean;         // [NJ * NK] the vertex's mean, written for alive blocks only; nullptr: no step cut
+    uint32_t NK, NKq;          // blocks and quads per row (NKq = NK: the last column wraps onto the first)
+    uint32_t Q0, nq;           // the chunk: quads [Q0, Q0 + nq), whole quad rows
+    uint32_t outward;
+    float max_step;
+    gm_wall_mesh_triangle *out;   // the chunk's staging, 2 * nq records
+    unsigned long long *ctr;   // [kWallMeshCounters]
+};
+void launch_wall_mesh_vertices(const WallCloudArgs &a, uint32_t *rank, float *mean, uint32_t rank_base, const ScanState &st,
+                               hipStream_t s);
+void launch_wall_mesh_triangles(const WallMeshArgs &a, const ScanState &st, hipStream_t s);
 // k_wall_check.hip (gm_wall_map_check_*): one k_compact launch per check
 // u64 words: the seven classes (GM_WALL_CHECK_CLS_* order), peak_pos, -peak_neg, the changed points (low word), n_points, pad
 constexpr int kWallCheckCounters = 12;

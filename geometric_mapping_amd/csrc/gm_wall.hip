@@ -229,6 +229,112 @@ bool cloud_params_ok(const gm_wall_cloud_params &c)
     return isfinite(c.anchor[0]) && isfinite(c.anchor[1]) && isfinite(c.anchor[2]);
 }
 
+// the head of a cloud's info: the window and its block grid (bs, bk clamped to the window and the ring)
+void cloud_info_head(gm_wall_map *map, uint32_t station0, uint32_t n, const gm_wall_cloud_params &cp, gm_wall_cloud_info *info)
+{
+    const uint32_t nsec = map->prm.n_sectors;
+    const uint32_t bk = std::min(cp.block_sectors, nsec), bs = std::min(cp.block_stations, std::max(n, 1u));
+    const uint32_t NK = (nsec + bk - 1u) / bk, NJ = (n + bs - 1u) / bs;
+    memset(info, 0, sizeof(*info));
+    info->struct_size = (uint32_t)sizeof(gm_wall_cloud_info);
+    info->station0 = station0;
+    info->n_stations = n;
+    info->n_sectors = nsec;
+    info->blocks_stations = NJ;
+    info->blocks_sectors = NK;
+    info->blocks = (uint64_t)NJ * NK;
+}
+
+// gm_wall_map_mesh's vertex pass: the tables its emit step fills beside the records (k_wall_mesh.hip)
+struct MeshTables { uint32_t *rank; float *mean; };
+
+// The chunks of gm_wall_map_cloud over the window of `info` (cloud_info_head's, n_stations >= 1; the map synchronised):
+// the records to points (may be NULL) while they fit capacity, the three class counts to info.  mesh (gm_wall_map_mesh):
+// the same passes with the emit step that also fills the tables.
+gm_status cloud_chunks(gm_wall_map *map, const gm_wall_cloud_params &cp, gm_wall_cloud_info *info, gm_wall_cloud_point *points,
+                       uint64_t capacity, const MeshTables *mesh)
+{
+    gm_ctx *ctx = map->ctx;
+    const uint32_t station0 = info->station0, n = info->n_stations, nsec = info->n_sectors;
+    const uint32_t bk = std::min(cp.block_sectors, nsec), bs = std::min(cp.block_stations, n);
+    const uint32_t NK = info->blocks_sectors, NJ = info->blocks_stations;
+
+    // chunks of whole block rows
+    const uint64_t chunk = map->cloud_chunk ? map->cloud_chunk : kStageCells;
+    const uint32_t rows = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(chunk / NK, 1u), NJ);
+    const uint64_t cb = (uint64_t)rows * NK;   // blocks of a full chunk
+    const bool merged = bs > 1u || bk > 1u;
+    const uint64_t acc_bytes = cb * kWallCloudAccBytes;
+    if (merged) GMW_HIP(ctx, map->cl_acc.reserve(acc_bytes));
+    GMW_HIP(ctx, map->cl_stage.reserve(cb));
+    GMW_OK(map->cl_scan.reserve(ctx, (uint32_t)cb, map->stream));   // (nothing of the map's is in flight: the call synchronised above)
+    GMW_HIP(ctx, map->cl_ctr.reserve(kWallCloudCounters));
+    GMW_HIP(ctx, map->cl_dirs.reserve((uint64_t)GM_WALL_MAX_SECTORS * 2));
+    map->cl_dirs_host.resize((size_t)2 * NK);
+    cloud_directions(nsec, bk, map->cl_dirs_host.data());
+    GMW_HIP(ctx, hipMemcpyAsync(map->cl_dirs.p, map->cl_dirs_host.data(), (size_t)NK * 16, hipMemcpyHostToDevice, map->stream));
+    GMW_HIP(ctx, hipMemsetAsync(map->cl_ctr.p, 0, kWallCloudCounters * 8, map->stream));
+
+    WallCloudArgs a;
+    memset(&a, 0, sizeof(a));
+    a.map = map->table;
+    a.first = (uint64_t)station0 * nsec;
+    a.station0 = station0; a.n = n; a.nsec = nsec;
+    a.bs = bs; a.bk = bk; a.NK = NK;
+    a.merged = merged ? 1u : 0u;
+    a.min_count = cp.min_count;
+    if (merged) {
+        Carve acc{map->cl_acc.p};   // kWallCloudAccBytes per block
+        a.acc_sum = acc.take<unsigned long long>(cb);
+        a.acc_cnt = acc.take<unsigned long long>(cb);
+        a.acc_lo = acc.take<uint32_t>(cb);
+        a.acc_hi = acc.take<uint32_t>(cb);
+        a.acc_cells = acc.take<uint32_t>(cb);
+    }
+    a.dirs = map->cl_dirs.p;
+    const DesignFrame &d = map->frame;
+    for (int k = 0; k < 3; ++k) {
+        a.oa[k] = d.o[k] - cp.anchor[k];
+        a.a[k] = d.a[k]; a.u[k] = d.u[k]; a.v[k] = d.v[k];
+    }
+    a.R = d.R;
+    a.g = cp.exaggeration;
+    a.t_min = map->prm.t_min;
+    a.ds = map->prm.station_length;
+    a.out = map->cl_stage.p;
+    a.ctr = map->cl_ctr.p;
+
+    uint64_t total = 0;
+    unsigned long long ctr[kWallCloudCounters] = {0ull, 0ull, 0ull, 0ull};
+    bool copying = points != nullptr;
+    for (uint32_t J0 = 0; J0 < NJ; J0 += rows) {   // (the trip count depends on the window alone)
+        a.J0 = J0;
+        a.nJ = std::min(rows, NJ - J0);
+        if (merged) {
+            GMW_HIP(ctx, hipMemsetAsync(map->cl_acc.p, 0, acc_bytes, map->stream));
+            launch_wall_cloud_merge(a, map->stream);
+            GMW_HIP(ctx, hipGetLastError());
+        }
+        if (mesh) launch_wall_mesh_vertices(a, mesh->rank, mesh->mean, (uint32_t)total, map->cl_scan.next(map->stream), map->stream);
+        else launch_wall_cloud_compact(a, map->cl_scan.next(map->stream), map->stream);
+        GMW_HIP(ctx, hipGetLastError());
+        GMW_HIP(ctx, hipMemcpyAsync(ctr, a.ctr, sizeof(ctr), hipMemcpyDeviceToHost, map->stream));
+        GMW_HIP(ctx, hipStreamSynchronize(map->stream));
+        const uint64_t got = (uint32_t)ctr[2];
+        if (copying && total + got > capacity) copying = false;   // copying stops, counting goes on
+        if (copying && got) {
+            GMW_HIP(ctx, hipMemcpyAsync(points + total, a.out, got * sizeof(gm_wall_cloud_point), hipMemcpyDeviceToHost,
+                                        map->stream));
+            GMW_HIP(ctx, hipStreamSynchronize(map->stream));
+        }
+        total += got;
+    }
+    info->points = total;
+    info->empty = ctr[0];
+    info->below_min_count = ctr[1];
+    return GM_OK;
+}
+
 }  // namespace
 
 namespace gm {
@@ -538,93 +644,97 @@ gm_status gm_wall_map_cloud(gm_wall_map *map, uint32_t station0, uint32_t n, con
     if (!points && capacity) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_cloud: NULL points with a capacity");
     GMW_OK(check_window(map, station0, n, ~0ull, nullptr, ""));
     GMW_OK(sync_map(map));
-    const uint32_t nsec = map->prm.n_sectors;
-    const uint32_t bk = std::min(cp.block_sectors, nsec), bs = std::min(cp.block_stations, std::max(n, 1u));
-    const uint32_t NK = (nsec + bk - 1u) / bk, NJ = (n + bs - 1u) / bs;
+    cloud_info_head(map, station0, n, cp, info);
+    if (!n) return GM_OK;
+    GMW_OK(cloud_chunks(map, cp, info, points, capacity, nullptr));
+    if (n_out) *n_out = info->points;
+    if (points && info->points > capacity) return gm_fail(ctx, GM_ERR_CAPACITY, "gm_wall_map_cloud: point buffer too small");
+    return GM_OK;
+}
+
+gm_status gm_wall_map_mesh(gm_wall_map *map, uint32_t station0, uint32_t n, const gm_wall_mesh_params *prm,
+                           gm_wall_mesh_info *info, gm_wall_cloud_point *vertices, uint64_t vertex_capacity,
+                           gm_wall_mesh_triangle *triangles, uint64_t triangle_capacity, uint64_t *n_vertices,
+                           uint64_t *n_triangles)
+{
+    if (!map) return GM_ERR_INVALID_ARG;
+    gm_ctx *ctx = map->ctx;
+    if (n_vertices) *n_vertices = 0;
+    if (n_triangles) *n_triangles = 0;
+    if (!info) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_mesh: NULL info");
+    const gm_wall_mesh_params mp = params_or(prm, gm_wall_mesh_default_params);
+    if (mp.struct_size != sizeof(gm_wall_mesh_params) || mp.reserved || !mesh_rule_ok(mp.flags, mp.max_step) || !cloud_params_ok(mp.cloud))
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_mesh: struct_size mismatch, an unknown flag or a parameter outside its limits");
+    if ((!vertices && vertex_capacity) || (!triangles && triangle_capacity))
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_mesh: NULL vertices or triangles with a capacity");
+    GMW_OK(check_window(map, station0, n, ~0ull, nullptr, ""));
+    GMW_OK(sync_map(map));
     memset(info, 0, sizeof(*info));
-    info->struct_size = (uint32_t)sizeof(gm_wall_cloud_info);
-    info->station0 = station0;
-    info->n_stations = n;
-    info->n_sectors = nsec;
-    info->blocks_stations = NJ;
-    info->blocks_sectors = NK;
-    info->blocks = (uint64_t)NJ * NK;
+    info->struct_size = (uint32_t)sizeof(gm_wall_mesh_info);
+    cloud_info_head(map, station0, n, mp.cloud, &info->cloud);
+    const uint32_t NJ = info->cloud.blocks_stations, NK = info->cloud.blocks_sectors;
+    const MeshGrid g = mesh_grid(NJ, NK, mp.flags);
+    info->wrapped = g.wrapped;
+    info->quads = g.quads;
     if (!n) return GM_OK;
 
-    // chunks of whole block rows
-    const uint64_t chunk = map->cloud_chunk ? map->cloud_chunk : kStageCells;
-    const uint32_t rows = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(chunk / NK, 1u), NJ);
-    const uint64_t cb = (uint64_t)rows * NK;   // blocks of a full chunk
-    const bool merged = bs > 1u || bk > 1u;
-    const uint64_t acc_bytes = cb * kWallCloudAccBytes;
-    if (merged) GMW_HIP(ctx, map->cl_acc.reserve(acc_bytes));
-    GMW_HIP(ctx, map->cl_stage.reserve(cb));
-    GMW_OK(map->cl_scan.reserve(ctx, (uint32_t)cb, map->stream));   // (nothing of the map's is in flight: the call synchronised above)
-    GMW_HIP(ctx, map->cl_ctr.reserve(kWallCloudCounters));
-    GMW_HIP(ctx, map->cl_dirs.reserve((uint64_t)GM_WALL_MAX_SECTORS * 2));
-    map->cl_dirs_host.resize((size_t)2 * NK);
-    cloud_directions(nsec, bk, map->cl_dirs_host.data());
-    GMW_HIP(ctx, hipMemcpyAsync(map->cl_dirs.p, map->cl_dirs_host.data(), (size_t)NK * 16, hipMemcpyHostToDevice, map->stream));
-    GMW_HIP(ctx, hipMemsetAsync(map->cl_ctr.p, 0, kWallCloudCounters * 8, map->stream));
+    // 1. the vertices: the cloud's chunks, with the index (and, for a step cut, the mean) of every survivor on the side
+    const uint64_t nb = info->cloud.blocks;   // <= 2^24
+    const bool cutting = mp.max_step > 0.0;
+    GMW_HIP(ctx, map->ms_rank.reserve(nb));
+    if (cutting) GMW_HIP(ctx, map->ms_mean.reserve(nb));
+    GMW_HIP(ctx, hipMemsetAsync(map->ms_rank.p, 0xFF, nb * sizeof(uint32_t), map->stream));   // kWallMeshDead everywhere
+    const MeshTables tables{map->ms_rank.p, cutting ? map->ms_mean.p : nullptr};
+    GMW_OK(cloud_chunks(map, mp.cloud, &info->cloud, vertices, vertex_capacity, &tables));
+    const uint64_t nv = info->cloud.points;
+    if (n_vertices) *n_vertices = nv;
 
-    WallCloudArgs a;
-    memset(&a, 0, sizeof(a));
-    a.map = map->table;
-    a.first = (uint64_t)station0 * nsec;
-    a.station0 = station0; a.n = n; a.nsec = nsec;
-    a.bs = bs; a.bk = bk; a.NK = NK;
-    a.merged = merged ? 1u : 0u;
-    a.min_count = cp.min_count;
-    if (merged) {
-        Carve acc{map->cl_acc.p};   // kWallCloudAccBytes per block
-        a.acc_sum = acc.take<unsigned long long>(cb);
-        a.acc_cnt = acc.take<unsigned long long>(cb);
-        a.acc_lo = acc.take<uint32_t>(cb);
-        a.acc_hi = acc.take<uint32_t>(cb);
-        a.acc_cells = acc.take<uint32_t>(cb);
-    }
-    a.dirs = map->cl_dirs.p;
-    const DesignFrame &d = map->frame;
-    for (int k = 0; k < 3; ++k) {
-        a.oa[k] = d.o[k] - cp.anchor[k];
-        a.a[k] = d.a[k]; a.u[k] = d.u[k]; a.v[k] = d.v[k];
-    }
-    a.R = d.R;
-    a.g = cp.exaggeration;
-    a.t_min = map->prm.t_min;
-    a.ds = map->prm.station_length;
-    a.out = map->cl_stage.p;
-    a.ctr = map->cl_ctr.p;
-
+    // 2. the triangles: chunks of as many whole quad rows as a vertex chunk has block rows
     uint64_t total = 0;
-    unsigned long long ctr[kWallCloudCounters] = {0ull, 0ull, 0ull, 0ull};
-    bool copying = points != nullptr;
-    for (uint32_t J0 = 0; J0 < NJ; J0 += rows) {   // (the trip count depends on the window alone)
-        a.J0 = J0;
-        a.nJ = std::min(rows, NJ - J0);
-        if (merged) {
-            GMW_HIP(ctx, hipMemsetAsync(map->cl_acc.p, 0, acc_bytes, map->stream));
-            launch_wall_cloud_merge(a, map->stream);
+    unsigned long long ctr[kWallMeshCounters] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+    if (g.quads) {
+        const uint64_t chunk = map->cloud_chunk ? map->cloud_chunk : kStageCells;
+        const uint32_t rows = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(chunk / NK, 1u), NJ - 1u);
+        const uint64_t slots = 2ull * rows * g.NKq;   // of a full chunk, <= 2^21
+        GMW_HIP(ctx, map->ms_stage.reserve(slots));
+        GMW_OK(map->ms_scan.reserve(ctx, (uint32_t)slots, map->stream));   // (nothing of the map's is in flight: the call synchronised above)
+        GMW_HIP(ctx, map->ms_ctr.reserve(kWallMeshCounters));
+        GMW_HIP(ctx, hipMemsetAsync(map->ms_ctr.p, 0, kWallMeshCounters * 8, map->stream));
+        WallMeshArgs a;
+        memset(&a, 0, sizeof(a));
+        a.rank = tables.rank;
+        a.mean = tables.mean;
+        a.NK = NK; a.NKq = g.NKq;
+        a.outward = (mp.flags & GM_WALL_MESH_OUTWARD) ? 1u : 0u;
+        a.max_step = (float)mp.max_step;
+        a.out = map->ms_stage.p;
+        a.ctr = map->ms_ctr.p;
+        bool copying = triangles != nullptr;
+        for (uint32_t J0 = 0; J0 < NJ - 1u; J0 += rows) {   // (the trip count depends on the window alone)
+            a.Q0 = J0 * g.NKq;
+            a.nq = std::min(rows, NJ - 1u - J0) * g.NKq;
+            launch_wall_mesh_triangles(a, map->ms_scan.next(map->stream), map->stream);
             GMW_HIP(ctx, hipGetLastError());
-        }
-        launch_wall_cloud_compact(a, map->cl_scan.next(map->stream), map->stream);
-        GMW_HIP(ctx, hipGetLastError());
-        GMW_HIP(ctx, hipMemcpyAsync(ctr, a.ctr, sizeof(ctr), hipMemcpyDeviceToHost, map->stream));
-        GMW_HIP(ctx, hipStreamSynchronize(map->stream));
-        const uint64_t got = (uint32_t)ctr[2];
-        if (copying && total + got > capacity) copying = false;   // copying stops, counting goes on
-        if (copying && got) {
-            GMW_HIP(ctx, hipMemcpyAsync(points + total, a.out, got * sizeof(gm_wall_cloud_point), hipMemcpyDeviceToHost,
-                                        map->stream));
+            GMW_HIP(ctx, hipMemcpyAsync(ctr, a.ctr, sizeof(ctr), hipMemcpyDeviceToHost, map->stream));
             GMW_HIP(ctx, hipStreamSynchronize(map->stream));
+            const uint64_t got = (uint32_t)ctr[4];
+            if (copying && total + got > triangle_capacity) copying = false;   // copying stops, counting goes on
+            if (copying && got) {
+                GMW_HIP(ctx, hipMemcpyAsync(triangles + total, a.out, got * sizeof(gm_wall_mesh_triangle), hipMemcpyDeviceToHost,
+                                            map->stream));
+                GMW_HIP(ctx, hipStreamSynchronize(map->stream));
+            }
+            total += got;
         }
-        total += got;
     }
-    info->points = total;
-    info->empty = ctr[0];
-    info->below_min_count = ctr[1];
-    if (n_out) *n_out = total;
-    if (points && total > capacity) return gm_fail(ctx, GM_ERR_CAPACITY, "gm_wall_map_cloud: point buffer too small");
+    info->quads_two = ctr[0];
+    info->quads_one = ctr[1];
+    info->quads_none = ctr[2];
+    info->cut_by_step = ctr[3];
+    info->triangles = total;
+    if (n_triangles) *n_triangles = total;
+    if ((vertices && nv > vertex_capacity) || (triangles && total > triangle_capacity))
+        return gm_fail(ctx, GM_ERR_CAPACITY, "gm_wall_map_mesh: vertex or triangle buffer too small");
     return GM_OK;
 }
 

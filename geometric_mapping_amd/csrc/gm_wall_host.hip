@@ -1,8 +1,10 @@
 // gm_wall_host.hip -- the part of the wall map's C ABI that needs no device (include/gm_hip.h states each rule): the
-// defaults, the parameter checks, the classification of one cell, the metrics, the direction table, the gauge of a polygon,
-// the runs, the align's selection, the sections' basis, solve and metrics.  No device call, no context, no map: it links
-// against libm and the C++ library alone, and host/gm_wall_host_test.cpp and host/gm_wall_sections_host_test.cpp run it
-// under the host sanitizers.
+// defaults, the parameter checks, the classification of one cell, the metrics, the direction table, the mesh's triangle
+// rule and its PLY file, the gauge of a polygon, the runs, the align's selection, the sections' basis, solve and metrics.
+// No device call, no context, no map: it links against libm and the C++ library alone, and host/gm_wall_host_test.cpp,
+// host/gm_wall_sections_host_test.cpp and host/gm_wall_mesh_host_test.cpp run it under the host sanitizers.
+#include <stdio.h>
+
 #include <vector>
 
 #define GM_WALL_HOST_ONLY
@@ -588,6 +590,119 @@ gm_status gm_wall_cloud_directions(const gm_wall_params *p, const gm_wall_cloud_
     if (capacity < NK) return GM_ERR_CAPACITY;
     cloud_directions(p->n_sectors, bk, cos_sin);
     return GM_OK;
+}
+
+void gm_wall_mesh_default_params(gm_wall_mesh_params *p)
+{
+    if (!defaults_begin(p)) return;
+    gm_wall_cloud_default_params(&p->cloud);
+}
+
+gm_status gm_wall_mesh_triangulate(uint32_t NJ, uint32_t NK, const gm_wall_cloud_point *vertices, uint64_t n_vertices,
+                                   uint32_t flags, double max_step, gm_wall_mesh_info *info, gm_wall_mesh_triangle *triangles,
+                                   uint64_t capacity, uint64_t *n_out)
+{
+    if (n_out) *n_out = 0;
+    if (!info || (!vertices && n_vertices) || (!triangles && capacity) || !mesh_rule_ok(flags, max_step)) return GM_ERR_INVALID_ARG;
+    const uint64_t nb = (uint64_t)NJ * NK;
+    if (nb > GM_WALL_MAX_CELLS || NK > GM_WALL_MAX_SECTORS) return GM_ERR_INVALID_ARG;
+    for (uint64_t i = 0; i < n_vertices; ++i)
+        if (vertices[i].block >= nb || (i && vertices[i].block <= vertices[i - 1].block)) return GM_ERR_INVALID_ARG;
+    const MeshGrid g = mesh_grid(NJ, NK, flags);
+    memset(info, 0, sizeof(*info));
+    info->struct_size = (uint32_t)sizeof(gm_wall_mesh_info);
+    info->wrapped = g.wrapped;
+    info->cloud.blocks_stations = NJ;
+    info->cloud.blocks_sectors = NK;
+    info->cloud.blocks = nb;
+    info->cloud.points = n_vertices;
+    info->quads = g.quads;
+    std::vector<uint32_t> rank((size_t)nb, 0xFFFFFFFFu);
+    for (uint64_t i = 0; i < n_vertices; ++i) rank[vertices[i].block] = (uint32_t)i;
+    const bool cutting = max_step > 0.0, outward = (flags & GM_WALL_MESH_OUTWARD) != 0;
+    const float step = (float)max_step;
+    // two walks of the quads: the counts, then (when they fit) the records
+    for (int pass = 0; pass < 2; ++pass) {
+        uint64_t nt = 0;
+        for (uint64_t Q = 0; Q < g.quads; ++Q) {
+            const uint32_t J = (uint32_t)(Q / g.NKq), K = (uint32_t)(Q % g.NKq), K1 = K + 1u == NK ? 0u : K + 1u;
+            const uint32_t r[4] = {rank[(size_t)J * NK + K], rank[(size_t)(J + 1u) * NK + K], rank[(size_t)(J + 1u) * NK + K1],
+                                   rank[(size_t)J * NK + K1]};
+            uint32_t alive = 0, dead = 0;
+            for (uint32_t c = 0; c < 4u; ++c) {
+                if (r[c] != 0xFFFFFFFFu) ++alive;
+                else dead = c;
+            }
+            if (!pass) ++(alive == 4u ? info->quads_two : alive == 3u ? info->quads_one : info->quads_none);
+            if (alive < 3u) continue;
+            // every triangle is the cyclic order A, B, C, D with one corner left out
+            const uint32_t drops[2] = {alive == 4u ? 3u : dead, 1u};
+            for (uint32_t t = 0; t < (alive == 4u ? 2u : 1u); ++t) {
+                uint32_t v[3], k = 0;
+                for (uint32_t c = 0; c < 4u; ++c)
+                    if (c != drops[t]) v[k++] = r[c];
+                bool cut = false;
+                if (cutting)
+                    for (int x = 0; x < 3 && !cut; ++x) {
+                        volatile float d = vertices[v[x]].mean - vertices[v[(x + 1) % 3]].mean;   // one fp32 operation, rounded once
+                        cut = fabsf(d) > step;
+                    }
+                if (cut) {
+                    if (!pass) ++info->cut_by_step;
+                    continue;
+                }
+                if (pass) {
+                    gm_wall_mesh_triangle &o = triangles[nt];
+                    o.v[0] = v[0];
+                    o.v[1] = outward ? v[2] : v[1];
+                    o.v[2] = outward ? v[1] : v[2];
+                }
+                ++nt;
+            }
+        }
+        if (!pass) {
+            info->triangles = nt;
+            if (n_out) *n_out = nt;
+            if (!triangles) return GM_OK;                  // (capacity 0: a count query)
+            if (capacity < nt) return GM_ERR_CAPACITY;
+        }
+    }
+    return GM_OK;
+}
+
+gm_status gm_wall_mesh_write_ply(const char *path, const gm_wall_cloud_point *vertices, uint64_t n_vertices,
+                                 const gm_wall_mesh_triangle *triangles, uint64_t n_triangles)
+{
+    const uint16_t probe = 1;
+    if (!path || (!vertices && n_vertices) || (!triangles && n_triangles) || *(const uint8_t *)&probe != 1u) return GM_ERR_INVALID_ARG;
+    for (uint64_t i = 0; i < n_triangles; ++i)
+        for (int k = 0; k < 3; ++k)
+            if (triangles[i].v[k] >= n_vertices) return GM_ERR_INVALID_ARG;
+    FILE *f = fopen(path, "wb");
+    if (!f) return GM_ERR_DEVICE;
+    bool ok = fprintf(f,
+                      "ply\nformat binary_little_endian 1.0\ncomment gm_wall_map_mesh\nelement vertex %llu\n"
+                      "property float x\nproperty float y\nproperty float z\nproperty float mean\nproperty float min\n"
+                      "property float max\nelement face %llu\nproperty list uchar uint vertex_indices\nend_header\n",
+                      (unsigned long long)n_vertices, (unsigned long long)n_triangles) > 0;
+    std::vector<uint8_t> buf;
+    const size_t kRows = 4096;   // records per write
+    buf.resize(kRows * 24);
+    for (uint64_t i = 0; ok && i < n_vertices; i += kRows) {
+        const size_t m = (size_t)std::min<uint64_t>(kRows, n_vertices - i);
+        for (size_t j = 0; j < m; ++j) memcpy(&buf[j * 24], &vertices[i + j], 24);   // x, y, z, mean, min, max lead the record
+        ok = fwrite(buf.data(), 24, m, f) == m;
+    }
+    for (uint64_t i = 0; ok && i < n_triangles; i += kRows) {
+        const size_t m = (size_t)std::min<uint64_t>(kRows, n_triangles - i);
+        for (size_t j = 0; j < m; ++j) {
+            buf[j * 13] = 3u;
+            memcpy(&buf[j * 13 + 1], triangles[i + j].v, 12);
+        }
+        ok = fwrite(buf.data(), 13, m, f) == m;
+    }
+    ok = (fclose(f) == 0) && ok;
+    return ok ? GM_OK : GM_ERR_DEVICE;
 }
 
 void gm_wall_section_default_params(gm_wall_section_params *p)

@@ -62,6 +62,21 @@ bool object_prm_ok(const gm_wall_object_params &p);
 void align_select(const DesignFrame &d, const gm_wall_params &wp, const gm_wall_align_params &ap, const double Rm[3][3],
                   const double tr[3], const gm_wall_align_score *t, gm_wall_align_info *info);
 
+// the mesh rule of include/gm_hip.h: its two scalar parameters, and the quad grid over NJ x NK blocks
+inline bool mesh_rule_ok(uint32_t flags, double max_step)
+{
+    return !(flags & ~(uint32_t)(GM_WALL_MESH_OUTWARD | GM_WALL_MESH_NO_WRAP)) && isfinite(max_step) && max_step >= 0.0;
+}
+struct MeshGrid { uint32_t wrapped, NKq; uint64_t quads; };
+inline MeshGrid mesh_grid(uint32_t NJ, uint32_t NK, uint32_t flags)
+{
+    MeshGrid g;
+    g.wrapped = (NK >= 3u && !(flags & GM_WALL_MESH_NO_WRAP)) ? 1u : 0u;
+    g.NKq = g.wrapped ? NK : (NK ? NK - 1u : 0u);
+    g.quads = NJ ? (uint64_t)(NJ - 1u) * g.NKq : 0u;
+    return g;
+}
+
 // the caller's parameters, or the defaults for NULL
 template <class P>
 P params_or(const P *prm, void (*defaults)(P *))
@@ -210,6 +225,12 @@ struct gm_wall_map {
     gm::DevArray<unsigned long long> cl_ctr;      // [kWallCloudCounters]
     gm::DevArray<double> cl_dirs;      // [GM_WALL_MAX_SECTORS][2]
     std::vector<double> cl_dirs_host;          // the table of the call in progress
+    // gm_wall_map_mesh: its vertex pass runs on the cloud's scratch above; its own
+    gm::DevArray<uint32_t> ms_rank;    // [NJ * NK] of the window: a block's vertex index, kWallMeshDead otherwise
+    gm::DevArray<float> ms_mean;       // [NJ * NK]: the vertices' means (a call with a step cut only)
+    gm::DevArray<gm_wall_mesh_triangle> ms_stage;   // a chunk's triangles
+    gm::wall::ScanRecords ms_scan;     // the triangle pass's own chained scan
+    gm::DevArray<unsigned long long> ms_ctr;      // [kWallMeshCounters]
     // gm_wall_map_clearance: the chunk (GM_WALL_CLEAR_CHUNK: tests, measurements; 0: kStageCells cells) and the scratch
     uint32_t clear_chunk = 0;
     gm::DevArray<int32_t> cr_gauge;    // the uploaded tables [n_gauges][n_sectors]

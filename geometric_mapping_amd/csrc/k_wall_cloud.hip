@@ -19,6 +19,7 @@
 
 #include "gm_compact.hpp"
 #include "gm_internal.hpp"
+#include "gm_wall_cloud_emit.hpp"
 
 namespace gm {
 
@@ -91,88 +92,7 @@ __global__ __launch_bounds__(kWcThreads) void k_wall_cloud_merge(WallCloudArgs a
 }
 
 // ---- 2. compact + emit ----
-
-// the block's counts of the two classes that do not survive: empty, below_min_count
-__device__ __forceinline__ uint32_t *wc_class_counts()
-{
-    __shared__ uint32_t c[2];
-    return c;
-}
-
-struct WallCloudPred {
-    WallCloudArgs a;
-    struct Payload { unsigned long long sum, count; uint32_t lo, hi, cells; };
-    __device__ __forceinline__ bool operator()(uint32_t i, Payload &p) const
-    {
-        p.sum = 0ull; p.lo = 0u; p.hi = 0u;
-        bool keep;
-        if (a.merged) {
-            p.count = a.acc_cnt[i];
-            p.cells = a.acc_cells[i];
-            keep = p.count >= (unsigned long long)a.min_count;   // (min_count >= 1: an empty block never passes)
-            if (keep) { p.sum = a.acc_sum[i]; p.lo = a.acc_lo[i]; p.hi = a.acc_hi[i]; }
-        } else {   // one cell per block: block row = station, NK = n_sectors
-            const uint64_t c = a.first + (uint64_t)a.J0 * a.NK + i;
-            const uint32_t cc = a.map.cnt[c];
-            p.count = cc;
-            p.cells = cc ? 1u : 0u;
-            keep = cc >= a.min_count;
-            if (keep) { p.sum = a.map.sum[c]; p.lo = a.map.lo[c]; p.hi = a.map.hi[c]; }
-        }
-        // (the lanes past the end of the input are not here: the ballots see the active lanes only)
-        const bool empty = p.count == 0ull;
-        const unsigned long long em = __ballot(empty), bm = __ballot(!empty && !keep);
-        const int lane = lane_id();
-        if (em && lane == (int)__builtin_ctzll(em)) atomicAdd(&wc_class_counts()[0], (uint32_t)__popcll(em));
-        if (bm && lane == (int)__builtin_ctzll(bm)) atomicAdd(&wc_class_counts()[1], (uint32_t)__popcll(bm));
-        return keep;
-    }
-};
-
-struct WallCloudEmit {
-    static constexpr bool kHasFinish = true, kHasPrepare = true;
-    WallCloudArgs a;
-    __device__ __forceinline__ void prepare() const
-    {
-        if (threadIdx.x < 2) wc_class_counts()[threadIdx.x] = 0u;
-    }
-    __device__ __forceinline__ void finish(uint32_t) const
-    {
-        __syncthreads();
-        if (threadIdx.x < 2) {
-            const uint32_t c = wc_class_counts()[threadIdx.x];
-            if (c) atomicAdd(&a.ctr[threadIdx.x], (unsigned long long)c);
-        }
-    }
-    __device__ __forceinline__ void operator()(uint32_t src, uint32_t dst, const WallCloudPred::Payload &p) const
-    {
-        const uint32_t jl = src / a.NK, K = src % a.NK, J = a.J0 + jl;
-        const uint32_t jw = J * a.bs;                                   // window-relative first station, < n
-        const uint32_t ns = a.n - jw < a.bs ? a.n - jw : a.bs;
-        const uint32_t j0 = a.station0 + jw;
-        const double m = __ddiv_rn(__dmul_rn((double)(long long)p.sum, 0x1p-20), (double)p.count);
-        const double h = __dmul_rn((double)(2u * j0 + ns), 0.5);
-        const double tc = __dadd_rn(a.t_min, __dmul_rn(h, a.ds));
-        const double rho = __dadd_rn(a.R, __dmul_rn(a.g, m));
-        const double c = a.dirs[2u * K], s = a.dirs[2u * K + 1u];
-        float xyz[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const double w = __dadd_rn(__dmul_rn(c, a.u[i]), __dmul_rn(s, a.v[i]));
-            const double q = __dadd_rn(__dadd_rn(a.oa[i], __dmul_rn(tc, a.a[i])), __dmul_rn(rho, w));
-            xyz[i] = __double2float_rn(q);
-        }
-        gm_wall_cloud_point r;
-        r.x = xyz[0]; r.y = xyz[1]; r.z = xyz[2];
-        r.mean = __double2float_rn(m);
-        r.min = ordered_to_float(~p.lo);
-        r.max = ordered_to_float(p.hi);
-        r.block = J * a.NK + K;
-        r.cells = p.cells;
-        r.count = p.count;
-        a.out[dst] = r;
-    }
-};
+// (WallCloudPred, WallCloudEmit: gm_wall_cloud_emit.hpp, shared with the mesh's vertex pass in k_wall_mesh.hip)
 
 void launch_wall_cloud_merge(const WallCloudArgs &a, hipStream_t s)
 {

@@ -422,6 +422,23 @@ std::vector<gm_wall_cloud_point> Processor::wallMapCloud(unsigned station0, unsi
     return points;
 }
 
+void Processor::wallMapMesh(unsigned station0, unsigned n, const gm_wall_mesh_params &prm, std::vector<gm_wall_cloud_point> *vertices,
+                            std::vector<gm_wall_mesh_triangle> *triangles, gm_wall_mesh_info *info)
+{
+    if (!wall_) throw Error(GM_ERR_NOT_READY, "wallMapMesh: createWallMap first");
+    gm_wall_mesh_info local;
+    gm_wall_mesh_info *ip = info ? info : &local;
+    uint64_t nv = 0, nt = 0;
+    check(gm_wall_map_mesh(wall_, station0, n, &prm, ip, 0, 0, 0, 0, &nv, &nt), "wallMapMesh");
+    if (vertices) vertices->resize((size_t)nv);
+    if (triangles) triangles->resize((size_t)nt);
+    const bool wv = vertices && nv, wt = triangles && nt;
+    if (wv || wt)
+        check(gm_wall_map_mesh(wall_, station0, n, &prm, ip, wv ? &(*vertices)[0] : 0, wv ? nv : 0, wt ? &(*triangles)[0] : 0,
+                               wt ? nt : 0, &nv, &nt),
+              "wallMapMesh");
+}
+
 gm_wall_clearance_info Processor::wallMapClearance(unsigned station0, unsigned n, const std::vector<int32_t> &gauge_q,
                                                    const std::vector<uint8_t> &station_gauge, const gm_wall_clearance_params &prm,
                                                    std::vector<gm_wall_clearance_station> &stations,

@@ -150,6 +150,10 @@ public:
     // stations [station0, station0 + n) as a point list (gm_wall_map_cloud): one record per block of cells that holds
     // prm.min_count points, ascending by block; info, when given, receives the call's counts
     std::vector<gm_wall_cloud_point> wallMapCloud(unsigned station0, unsigned n, const gm_wall_cloud_params &prm, gm_wall_cloud_info *info = nullptr);
+    // stations [station0, station0 + n) as an indexed triangle mesh (gm_wall_map_mesh): vertices receives wallMapCloud's
+    // rows under prm.cloud, triangles three indices into them per face (either may be null: not wanted); info, when
+    // given, receives the call's counts.  A TRIANGLE_LIST marker takes the vertices' x, y, z in the triangles' order.
+    void wallMapMesh(unsigned station0, unsigned n, const gm_wall_mesh_params &prm, std::vector<gm_wall_cloud_point> *vertices, std::vector<gm_wall_mesh_triangle> *triangles, gm_wall_mesh_info *info = nullptr);
     // stations [station0, station0 + n) against a structure gauge (gm_wall_map_clearance): gauge_q holds whole tables of
     // n_sectors entries (2^-20 m, 0 = not gauged), station_gauge one table index per window station (empty: table 0
     // everywhere).  stations receives one record per station, cells the tight and the infringed cells ascending by

@@ -705,6 +705,85 @@ gm_status gm_wall_cloud_directions(const gm_wall_params *p, const gm_wall_cloud_
 gm_status gm_wall_map_cloud(gm_wall_map *map, uint32_t station0, uint32_t n, const gm_wall_cloud_params *prm,
                             gm_wall_cloud_info *info, gm_wall_cloud_point *points, uint64_t capacity, uint64_t *n_out);
 
+/* ---- the wall map as an indexed triangle mesh (gm_wall_map_mesh) ------------------------------------------------------
+ * The cloud above with faces: a surface a viewer can shade and section, a TRIANGLE_LIST marker or a shape_msgs/Mesh.
+ *   vertices    exactly the rows gm_wall_map_cloud returns for the same map, window and gm_wall_cloud_params: the same
+ *               records in the same block order with the same bytes.  The index of a vertex is its position in that list.
+ *   quads       NJ, NK are the cloud's block counts; block (J, K) is ALIVE when it became a point.  The sectors close the
+ *               tube (wrapped = 1) when NK >= 3 and GM_WALL_MESH_NO_WRAP is not set: then NKq = NK, else NKq = NK - 1.
+ *               There are (NJ - 1) NKq quads (none when NJ = 1 or NKq = 0: vertices without triangles), quad
+ *               Q = J NKq + K with the corners, in cyclic order, A = (J, K), B = (J + 1, K), C = (J + 1, K'), D = (J, K'),
+ *               K' = (K + 1) mod NK.
+ *   triangles   four alive corners: (A, B, C) in slot 2 Q and (A, C, D) in slot 2 Q + 1 (quads_two).  Three alive
+ *               corners: the one triangle of the alive corners in the cyclic order above with the dead corner left out, in
+ *               slot 2 Q (quads_one).  Fewer: nothing (quads_none).  With the cloud's block order (phi grows from u toward
+ *               v, v = a x u) the normal (v1 - v0) x (v2 - v0) faces the axis: the viewer stands in the tunnel.
+ *               GM_WALL_MESH_OUTWARD swaps the second and the third index of every triangle.
+ *   step cut    max_step > 0: a triangle is dropped (cut_by_step) when for any two of its corners
+ *               fabsf(mean_a - mean_b) > (float) max_step, mean the fp32 field of the vertex row, the subtraction one fp32
+ *               operation: a niche or an installation grows no skirts to the wall around it.  0: no cut.  The cut is
+ *               applied per triangle, after the corner rule: a quad may keep one of its two.
+ *   order       ascending by slot.
+ * quads = quads_two + quads_one + quads_none and triangles = 2 quads_two + quads_one - cut_by_step, always.  The result is a
+ * function of the raw cells and the parameters alone.  On the device the vertex pass is the cloud's, chunked as the cloud
+ * is (GM_WALL_CLOUD_CHUNK), and stores every survivor's index into a table of one uint32 per block of the window; the
+ * triangle pass follows in chunks of as many whole quad rows. */
+#define GM_WALL_MESH_OUTWARD (1u << 0)
+#define GM_WALL_MESH_NO_WRAP (1u << 1)
+
+typedef struct gm_wall_mesh_params {
+    uint32_t struct_size;      /* = sizeof(gm_wall_mesh_params) */
+    uint32_t flags;            /* GM_WALL_MESH_* (default 0) */
+    gm_wall_cloud_params cloud;   /* the vertices' parameters (its own struct_size set) */
+    double   max_step;         /* finite, >= 0 (default 0: no cut), metres of mean deviation */
+    uint64_t reserved;         /* 0 */
+} gm_wall_mesh_params;
+
+typedef struct gm_wall_mesh_triangle {   /* 12 bytes */
+    uint32_t v[3];             /* indices into the vertex list */
+} gm_wall_mesh_triangle;
+
+typedef struct gm_wall_mesh_info {
+    uint32_t struct_size;      /* = sizeof(gm_wall_mesh_info), filled by the library */
+    uint32_t wrapped;          /* 0 or 1 */
+    gm_wall_cloud_info cloud;  /* the vertices: what gm_wall_map_cloud reports */
+    uint64_t quads, quads_two, quads_one, quads_none;   /* by the corner rule, before the step cut */
+    uint64_t cut_by_step, triangles;
+} gm_wall_mesh_info;
+
+/* Host only: the cloud's defaults, flags 0, max_step 0.  A NULL is ignored. */
+void gm_wall_mesh_default_params(gm_wall_mesh_params *p);
+/* The mesh of the window.  Synchronises the map (as gm_wall_map_sync), runs on the map's stream and blocks.  prm NULL: the
+ * defaults.  info is required; it, *n_vertices and *n_triangles (either may be NULL) are filled whenever the call got as
+ * far as the device, also on GM_ERR_CAPACITY.  A NULL buffer with capacity 0 is not filled; both NULL is a count query
+ * (GM_OK).  A non-NULL buffer whose capacity is below its count returns GM_ERR_CAPACITY and leaves the contents of both
+ * unspecified (copying stops, counting goes on).  n = 0 gives nothing.  The map is not changed.  Scratch (the cloud's, 4 B
+ * per block of the window for the indices, 4 B more per block with a step cut, 12 B per slot of a chunk of triangle
+ * staging, a chained scan's records) is allocated on first use, kept grow-only in the map and freed with it; a map that
+ * never calls this allocates nothing.
+ * GM_ERR_INVALID_ARG: NULL map / info, a window outside the map, a struct_size mismatch (prm's or prm->cloud's), an unknown
+ * flag, a parameter outside its limits, reserved not 0, a NULL buffer with capacity > 0. */
+gm_status gm_wall_map_mesh(gm_wall_map *map, uint32_t station0, uint32_t n, const gm_wall_mesh_params *prm,
+                           gm_wall_mesh_info *info, gm_wall_cloud_point *vertices, uint64_t vertex_capacity,
+                           gm_wall_mesh_triangle *triangles, uint64_t triangle_capacity, uint64_t *n_vertices,
+                           uint64_t *n_triangles);
+/* Host only, no device, no map: the triangle rule above on a vertex list -- rows of a cloud of NJ x NK blocks, whose
+ * block field says which blocks are alive and whose mean feeds the step cut.  Fills the mesh half of info (struct_size,
+ * wrapped, the quad and triangle counts; info->cloud is zeroed but for blocks_stations, blocks_sectors, blocks and points)
+ * and *n_out (may be NULL) whenever the arguments are accepted, also on GM_ERR_CAPACITY.  triangles NULL with capacity 0 is
+ * a count query; a capacity below *n_out returns GM_ERR_CAPACITY and writes nothing.
+ * GM_ERR_INVALID_ARG: NULL info, vertices NULL with n_vertices > 0, NJ NK above GM_WALL_MAX_CELLS, NK above
+ * GM_WALL_MAX_SECTORS, rows whose block is not strictly ascending or is >= NJ NK, an unknown flag, max_step not
+ * finite or negative, triangles NULL with capacity > 0. */
+gm_status gm_wall_mesh_triangulate(uint32_t NJ, uint32_t NK, const gm_wall_cloud_point *vertices, uint64_t n_vertices,
+                                   uint32_t flags, double max_step, gm_wall_mesh_info *info, gm_wall_mesh_triangle *triangles,
+                                   uint64_t capacity, uint64_t *n_out);
+/* Host only: a binary_little_endian 1.0 PLY file of the mesh -- vertex properties float x, y, z, mean, min, max; faces
+ * `list uchar uint vertex_indices` -- as CloudCompare and MeshLab open it.  GM_ERR_INVALID_ARG: NULL path, a NULL array
+ * with a count, an index >= n_vertices, a big-endian host.  GM_ERR_DEVICE: the path cannot be written. */
+gm_status gm_wall_mesh_write_ply(const char *path, const gm_wall_cloud_point *vertices, uint64_t n_vertices,
+                                 const gm_wall_mesh_triangle *triangles, uint64_t n_triangles);
+
 /* ---- the surveyed wall against a structure gauge (gm_wall_map_clearance) ---------------------------------------------
  * Does the vehicle, train or equipment envelope fit, with how much room, and where does it not: every cell of a window
  * of stations against a caller-supplied GAUGE, the radius about the design axis that the envelope needs in each sector.

@@ -1,0 +1,21 @@
+"""The device-free half of the wall mesh (csrc/gm_wall_host.hip: gm_wall_mesh_triangulate, gm_wall_mesh_write_ply) on the
+CPU, under AddressSanitizer and UBSan.
+
+host/gm_wall_mesh_host_test.cpp is a stand-alone program linked with that one source file and nothing else of the
+library: it initialises no device and calls no HIP function.  Nothing loaded into Python is sanitised."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
+
+
+def test_device_free_mesh_calls_run_cleanly_under_sanitizers(tmp_path):
+    exe = str(tmp_path / "gm_wall_mesh_host_test")
+    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all"]
+    subprocess.run([os.path.join(ROCM, "bin", "hipcc"), "--offload-host-only", "-std=c++17", "-O1", "-g"] + san +
+                   ["-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "geometric_mapping_amd", "csrc", "gm_wall_host.hip"),
+                    os.path.join(ROOT, "host", "gm_wall_mesh_host_test.cpp"), "-o", exe], check=True, capture_output=True)
+    r = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.rstrip().endswith("gm_wall_mesh_host_test ok"), r.stdout + r.stderr
