@@ -67,6 +67,7 @@ GM_WALL_OBJECT_MAX_BLOCKS = 1 << 20
 GM_WALL_OBJECT_TILE = (64, 64)   # block rows x block columns: the object labelling kernel's default tile
 
 GM_WALL_CHECK_MEAN, GM_WALL_CHECK_ENVELOPE = 0, 1
+GM_WALL_SKIP_NEG, GM_WALL_SKIP_POS = 1, 2
 GM_WALL_CLEAR_MIN, GM_WALL_CLEAR_MEAN = 0, 1
 GM_WALL_CLEAR_MAX_GAUGES = 256
 GM_SECTION_OK = 0
@@ -307,6 +308,17 @@ class WallCheckInfo(C.Structure):
                 ("peak_pos", C.c_int64), ("peak_neg", C.c_int64)]
 
 
+class WallAddCheckedParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("skip", C.c_uint32), ("min_delta", C.c_double)]
+
+
+class WallAddCheckedInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("status", C.c_uint32), ("min_delta_q", C.c_int64), ("n_points", C.c_uint32),
+                ("n_rows", C.c_uint32), ("rows_neg", C.c_uint32), ("rows_pos", C.c_uint32), ("rows_kept", C.c_uint32),
+                ("rows_rejected", C.c_uint32), ("skipped", C.c_uint32), ("plane", C.c_uint32), ("beyond_gate", C.c_uint32),
+                ("outside", C.c_uint32), ("mapped", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class WallLocateParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reference", C.c_uint32), ("min_count", C.c_uint32), ("reserved", C.c_uint32),
                 ("gate", C.c_double)]
@@ -444,6 +456,7 @@ def load():
     wsprmp, wssump, wssecp, wsinfop, wsmetp = (C.POINTER(WallSectionParams), C.POINTER(WallSectionSums), C.POINTER(WallSection),
                                                C.POINTER(WallSectionsInfo), C.POINTER(WallSectionMetrics))
     wkprmp, wkptp, wkinfop = C.POINTER(WallCheckParams), C.POINTER(WallCheckPoint), C.POINTER(WallCheckInfo)
+    wcaprmp, wcainfop = C.POINTER(WallAddCheckedParams), C.POINTER(WallAddCheckedInfo)
     wlprmp, wlinfop = C.POINTER(WallLocateParams), C.POINTER(WallLocateInfo)
     waprmp, wascp, wainfop = C.POINTER(WallAlignParams), C.POINTER(WallAlignScore), C.POINTER(WallAlignInfo)
     woprmp, wobjp, woinfop, wometp = (C.POINTER(WallObjectParams), C.POINTER(WallObject), C.POINTER(WallObjectsInfo),
@@ -532,6 +545,11 @@ def load():
         "gm_wall_map_check_frame": (C.c_int, [vp, vp, u32, dp, wkprmp, waddp]),
         "gm_wall_map_get_check": (C.c_int, [vp, u32, wkinfop, wkptp, u32, u32p]),
         "gm_wall_map_check_points": (C.c_int, [vp, fp, u32, u8p, dp, wkprmp, waddp, wkinfop, wkptp, u32, u32p, fp, i32p, i32p, u8p]),
+        "gm_wall_add_checked_default_params": (None, [wcaprmp]),
+        "gm_wall_add_checked_check_params": (C.c_int, [wcaprmp]),
+        "gm_wall_map_add_frame_checked": (C.c_int, [vp, vp, u32, dp, wcaprmp, waddp]),
+        "gm_wall_map_get_add_checked": (C.c_int, [vp, u32, wcainfop]),
+        "gm_wall_map_add_points_checked": (C.c_int, [vp, fp, u32, u8p, dp, wcaprmp, wkptp, u32, waddp, wcainfop, fp, i32p]),
         "gm_wall_locate_default_params": (None, [wlprmp]),
         "gm_wall_locate_check_params": (C.c_int, [wlprmp]),
         "gm_wall_map_locate_frame": (C.c_int, [vp, vp, u32, dp, wlprmp]),

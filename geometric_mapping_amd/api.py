@@ -531,6 +531,8 @@ WALL_CHECK_POINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("delta",
                              ("index", "<u4"), ("row", "<u4")])   # gm_wall_check_point, 32 bytes
 _CHECK_INFO = ("status", "threshold_q", "n_points", "plane", "beyond_gate", "outside", "unsurveyed", "unchanged",
                "changed_pos", "changed_neg", "peak_pos", "peak_neg")
+_ADD_CHECKED_INFO = ("status", "min_delta_q", "n_points", "n_rows", "rows_neg", "rows_pos", "rows_kept", "rows_rejected",
+                     "skipped", "plane", "beyond_gate", "outside", "mapped", "reserved")
 WALL_OBJECT = np.dtype([("label", "<u4"), ("sign", "<i4"), ("blocks", "<u4"), ("peak_index", "<u4"), ("station_min", "<u4"),
                         ("station_max", "<u4"), ("sector_min", "<u4"), ("sector_max", "<u4"), ("sector_min_turned", "<u4"),
                         ("sector_max_turned", "<u4"), ("points", "<u8"), ("peak", "<i8"), ("sum_delta", "<i8"), ("sum_x", "<i8"),
@@ -1189,6 +1191,58 @@ class WallMap:
         d = self._check_info(info)
         d["add"] = self._add_info(add)
         return d, pts[:int(got.value)].copy(), ({k: v[:n].copy() for k, v in out.items()} if outputs else None)
+
+    @staticmethod
+    def add_checked_params(**kw):
+        """gm_wall_add_checked_params with the library's defaults, then the keywords (skip, min_delta)."""
+        p = _lib.WallAddCheckedParams()
+        _lib.load().gm_wall_add_checked_default_params(C.byref(p))
+        for k, v in kw.items():
+            if k not in ("skip", "min_delta"):
+                raise TypeError(f"unknown checked-add parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+    @staticmethod
+    def _add_checked_info(i):
+        return {k: int(getattr(i, k)) for k in _ADD_CHECKED_INFO}
+
+    def add_frame_checked(self, slot=0, pose=np.eye(4)[:3], **params):
+        """gm_wall_map_add_frame_checked: enqueue the add of the slot's last submitted frame under `pose`, less the points
+        the slot's last check_frame on this map selected.  Returns the add info dict; add_checked_result() fetches the counts."""
+        m = self._pose(pose)
+        p = self.add_checked_params(**params)
+        i = _lib.WallAddInfo()
+        self._ctx._check(self._L.gm_wall_map_add_frame_checked(self._h(), self._ctx._ctx, slot, m.ctypes.data_as(C.POINTER(C.c_double)),
+                                                               C.byref(p), C.byref(i)))
+        return self._add_info(i)
+
+    def add_checked_result(self, slot=0):
+        """gm_wall_map_get_add_checked: the info dict of the last checked add on the slot (waits for that call only)."""
+        info = _lib.WallAddCheckedInfo()
+        self._ctx._check(self._L.gm_wall_map_get_add_checked(self._h(), slot, C.byref(info)))
+        return self._add_checked_info(info)
+
+    def add_points_checked(self, cloud, pose, rows, labels=None, outputs=True, **params):
+        """gm_wall_map_add_points_checked on a host cloud [n,3] and WALL_CHECK_POINT rows (any order, duplicates allowed):
+        (info dict with the add info under "add", residual [n] float32, cell [n] int32); outputs False skips the per-point
+        arrays (None, None)."""
+        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+        m = self._pose(pose)
+        lab, lp = GeometricMapping._u8(labels)
+        p = self.add_checked_params(**params)
+        r = np.ascontiguousarray(np.asarray(rows, dtype=WALL_CHECK_POINT).reshape(-1))
+        add, info = _lib.WallAddInfo(), _lib.WallAddCheckedInfo()
+        n = len(xyz)
+        res = np.empty(max(n, 1), dtype=np.float32) if outputs else None
+        cell = np.empty(max(n, 1), dtype=np.int32) if outputs else None
+        self._ctx._check(self._L.gm_wall_map_add_points_checked(
+            self._h(), _f32(xyz), n, lp, m.ctypes.data_as(C.POINTER(C.c_double)), C.byref(p),
+            r.ctypes.data_as(C.POINTER(_lib.WallCheckPoint)) if len(r) else None, len(r), C.byref(add), C.byref(info),
+            _f32(res) if outputs else None, cell.ctypes.data_as(C.POINTER(C.c_int32)) if outputs else None))
+        d = self._add_checked_info(info)
+        d["add"] = self._add_info(add)
+        return d, (res[:n].copy() if outputs else None), (cell[:n].copy() if outputs else None)
 
     @staticmethod
     def locate_params(**kw):

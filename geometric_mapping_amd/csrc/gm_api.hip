@@ -437,6 +437,7 @@ gm_status enqueue_frame(gm_ctx *ctx, Slot &sl, const gm_cloud *cloud, bool block
     }
     hipStream_t s = sl.stream;
     sl.n_in = n;
+    ++sl.cloud_seq;
     // Epochs of replayed (graph) scans are (frame counter * 32 + launch index) mod 2^29: they repeat every 2^24 frames of
     // the slot.  Twice per period the records are cleared between two frames (all of them are stale there), so that a
     // record can never be as old as a period.
@@ -626,6 +627,7 @@ gm_status begin_stage(gm_ctx *ctx, Slot *&sl)
     GM_HIP(ctx, hipStreamSynchronize(sl->stream));
     sl->submitted = false;
     sl->complete = false;
+    ++sl->cloud_seq;
     return GM_OK;
 }
 

@@ -62,6 +62,7 @@ struct Slot {
     uint32_t blk_cap = 0;
     uint32_t scan_epoch = 0;            // launches of k_compact on this slot so far (see gm_compact.hpp)
     uint32_t scan_seq = 0;              // index of the next k_compact launch inside the frame being captured
+    uint64_t cloud_seq = 0;             // counts the clouds the slot has held: every submit and every stage call takes the next
     uint32_t frames_enqueued = 0;       // host mirror of the device-side frame counter (frame_in[1]) that replayed scans take their epochs from
     // graph replay (GM_CFG_GRAPH): the frame's launch chain is captured once per (sizes, layout, configuration) and replayed
     bool capturing = false;             // the launches being enqueued go into a stream capture
@@ -327,6 +328,35 @@ __host__ __device__ inline WallTable wall_table(uint8_t *base, uint64_t ncell)
 size_t wall_table_bytes(uint64_t ncell);
 // n_cap: the most points the launch can see (the grid is sized by it); points_per_block 0: the default rule
 void launch_wall_add(const WallArgs &a, uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
+// k_wall_add_checked.hip (gm_wall_map_add_*_checked): mark the selected rows' points in a bit mask, then k_wall_add's masked
+// instantiation.  u64 words of the call's counter block: rows_neg, rows_pos, rows_kept, rows_rejected | skipped, mapped,
+// outside, beyond_gate, plane | n_rows, n_points, pad
+constexpr int kWallAddCheckedCounters = 12;
+struct WallMarkArgs {
+    const gm_wall_check_point *rows;
+    const unsigned long long *n_rows_ptr;   // the check's counter word (low 32 bits); nullptr: n_rows_host
+    uint32_t n_rows_host;
+    uint32_t rows_cap;         // rows the buffer holds: the count is clamped to it
+    const uint32_t *n_ptr;     // device point count (nullptr: n_host)
+    uint32_t n_host;
+    uint32_t skip;             // GM_WALL_SKIP_* bits
+    long long S;
+    uint32_t *mask;            // one bit per point, >= n_points bits rounded up to whole 64-bit words   } zeroed by the caller
+    unsigned long long *ctr;   // [kWallAddCheckedCounters]                                              } on the same stream
+};
+// n_cap: the most rows the launch can see (the grid is sized by it)
+void launch_wall_mark(const WallMarkArgs &a, uint32_t n_cap, hipStream_t s);
+// k_wall_add over the points whose mask bit is clear; the five point classes also go to ctr[4 .. 8]
+void launch_wall_add_masked(const WallArgs &a, const unsigned long long *mask, unsigned long long *ctr, uint32_t n_cap,
+                            uint32_t points_per_block, hipStream_t s);
+// the class of one row: 0 selected negative, 1 selected positive, 2 kept, 3 rejected (delta_bits: the row's delta)
+__host__ __device__ inline uint32_t wall_mark_class(uint32_t delta_bits, long long dq, uint32_t index, uint32_t n_points,
+                                                    uint32_t skip, long long S)
+{
+    if (dq == 0 || (delta_bits & 0x7F800000u) == 0x7F800000u || index >= n_points) return 3u;
+    if (dq < 0) return ((skip & GM_WALL_SKIP_NEG) && -dq >= S) ? 0u : 2u;
+    return ((skip & GM_WALL_SKIP_POS) && dq >= S) ? 1u : 2u;
+}
 void launch_wall_read(const WallTable &T, uint64_t first, uint64_t n, gm_surface_cell *out, hipStream_t s);
 void launch_wall_read_raw(const WallTable &T, uint64_t first, uint64_t n, gm_wall_raw_cell *out, hipStream_t s);
 void launch_wall_merge_raw(const WallTable &T, uint64_t first, uint64_t n, const gm_wall_raw_cell *in, hipStream_t s);

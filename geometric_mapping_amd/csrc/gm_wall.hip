@@ -120,18 +120,27 @@ gm_status StageCall::close()
     return GM_OK;
 }
 
+gm_status add_wait_readers(gm_wall_map *m, uint32_t slot, hipStream_t s)
+{
+    for (uint32_t i = 0; i < m->ctx->n_slots; ++i)
+        for (const PendingResult *r : {&m->checks[i].res, &m->locates[i].res, &m->aligns[i].res})
+            if (i != slot && r->outstanding) GMW_HIP(m->ctx, hipStreamWaitEvent(s, r->done, 0));
+    return GM_OK;
+}
+
 }  // namespace wall
 }  // namespace gm
 
 namespace {
 
-// every pending result of the map: the checks', the locates', the aligns'
+// every pending result of the map: the checks', the locates', the aligns', the checked adds'
 template <class F>
 gm_status each_result(gm_wall_map *m, F f)
 {
     for (WallCheckSlot &c : m->checks) GMW_OK(f(c.res));
     for (WallLocateSlot &l : m->locates) GMW_OK(f(l.res));
     for (WallAlignSlot &l : m->aligns) GMW_OK(f(l.res));
+    for (WallAddCheckedSlot &l : m->add_checks) GMW_OK(f(l.res));
     return GM_OK;
 }
 
@@ -186,16 +195,6 @@ void free_map(gm_wall_map *m)
         if (e) hipEventDestroy(e);
     if (m->stream) { hipStreamSynchronize(m->stream); hipStreamDestroy(m->stream); }
     delete m;   // (every DevArray and HostArray goes with it)
-}
-
-// An add on `s` (the stream of `slot`) must not be seen by a reader -- a check, a locate, an align -- enqueued before it
-// on another slot: `s` waits for every result outstanding there (nothing to wait for on a map without readers).
-gm_status add_wait_readers(gm_wall_map *m, uint32_t slot, hipStream_t s)
-{
-    for (uint32_t i = 0; i < m->ctx->n_slots; ++i)
-        for (const PendingResult *r : {&m->checks[i].res, &m->locates[i].res, &m->aligns[i].res})
-            if (i != slot && r->outstanding) GMW_HIP(m->ctx, hipStreamWaitEvent(s, r->done, 0));
-    return GM_OK;
 }
 
 // gm_wall_map_read (raw false: gm_surface_cell) and gm_wall_map_read_raw (gm_wall_raw_cell): the window in chunks of the
@@ -364,6 +363,7 @@ gm_status gm_wall_map_create(gm_ctx *ctx, const gm_wall_params *params, gm_wall_
     m->checks.resize(ctx->n_slots);
     m->locates.resize(ctx->n_slots);
     m->aligns.resize(ctx->n_slots);
+    m->add_checks.resize(ctx->n_slots);
     if (const char *e = getenv("GM_WALL_ALIGN_ROWS")) m->align_rows = (uint32_t)strtoul(e, nullptr, 10);   // 0: the default
     if (const char *e = getenv("GM_WALL_POINTS_PER_BLOCK")) m->points_per_block = (uint32_t)strtoul(e, nullptr, 10);
     if (const char *e = getenv("GM_WALL_REGION_TILE")) {   // <stations>x<sectors>; anything else: the default

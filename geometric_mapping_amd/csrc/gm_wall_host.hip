@@ -223,6 +223,15 @@ bool check_prm_ok(const gm_wall_check_params &c, long long &T)
     return T >= 1;
 }
 
+bool add_checked_prm_ok(const gm_wall_add_checked_params &p, long long &S)
+{
+    S = 0;
+    if (p.struct_size != sizeof(gm_wall_add_checked_params) || p.skip < 1u || p.skip > (uint32_t)(GM_WALL_SKIP_NEG | GM_WALL_SKIP_POS)) return false;
+    if (!(p.min_delta >= 0.0) || !(p.min_delta <= 8.0)) return false;
+    S = (long long)rint(p.min_delta * 1048576.0);
+    return true;
+}
+
 bool locate_prm_ok(const gm_wall_locate_params &p)
 {
     return p.struct_size == sizeof(gm_wall_locate_params) && p.reference <= (uint32_t)GM_WALL_LOCATE_MAP && p.min_count >= 1u &&
@@ -506,6 +515,19 @@ void gm_wall_object_default_params(gm_wall_object_params *p)
     p->min_points = 8;
     p->connectivity = 8;
     p->half_window_stations = 128;
+}
+
+void gm_wall_add_checked_default_params(gm_wall_add_checked_params *p)
+{
+    if (!defaults_begin(p)) return;
+    p->skip = GM_WALL_SKIP_NEG | GM_WALL_SKIP_POS;
+    p->min_delta = 0.0;
+}
+
+gm_status gm_wall_add_checked_check_params(const gm_wall_add_checked_params *p)
+{
+    long long S;
+    return p && add_checked_prm_ok(*p, S) ? GM_OK : GM_ERR_INVALID_ARG;
 }
 
 gm_status gm_wall_locate_check_params(const gm_wall_locate_params *p)

@@ -1,7 +1,8 @@
-// gm_wall_map.hpp -- what the three wall-map files share: the map, the state of one (map, slot), the pure rules.
+// gm_wall_map.hpp -- what the four wall-map files share: the map, the state of one (map, slot), the pure rules.
 //   gm_wall_host.hip  every entry point that needs no device, and the rules the others share with them
 //   gm_wall.hip       the map itself and the window calls
 //   gm_wall_slot.hip  the per-(map, slot) calls: check, locate, align, objects
+//   gm_wall_add_checked.hip  the add less the check's changed rows: a slot's check and the map's add in one call
 #pragma once
 #include <math.h>
 #include <string.h>
@@ -57,6 +58,7 @@ bool check_prm_ok(const gm_wall_check_params &c, long long &T);
 bool locate_prm_ok(const gm_wall_locate_params &p);
 bool align_prm_ok(const gm_wall_align_params &p, uint32_t nsec);
 bool object_prm_ok(const gm_wall_object_params &p);
+bool add_checked_prm_ok(const gm_wall_add_checked_params &p, long long &S);   // S of an accepted block
 // The selection and the pose of include/gm_hip.h from a table of (2A + 1)(2B + 1) records.  Fills everything but the
 // device's counts.
 void align_select(const DesignFrame &d, const gm_wall_params &wp, const gm_wall_align_params &ap, const double Rm[3][3],
@@ -168,6 +170,17 @@ struct WallCheckSlot {
     uint32_t status = 0;
     long long T = 0;
     int64_t anchor = 0;                     // the check's j_f (gm_wall_map_check_objects anchors its window on it)
+    uint64_t cloud_seq = 0;                 // the slot's cloud_seq at the enqueue: the cloud whose indices the rows carry
+};
+
+// gm_wall_map_add_frame_checked: the state of one (map, slot), allocated on first use, freed with the map
+struct WallAddCheckedSlot {
+    DevArray<unsigned long long> blk;       // device [kWallAddCheckedCounters] | the mask: one bit per point of the slot's
+                                            // frame in whole 64-bit words (one block: one fill zeroes both per call)
+    HostArray<unsigned long long> h_ctr;    // pinned copy, valid once the result has been waited for
+    PendingResult res;                      // (also what check_prepare waits for before it frees the rows the mark reads)
+    uint32_t status = 0;
+    long long S = 0;
 };
 
 // gm_wall_map_locate_*: the state of one (map, slot), allocated on first use, freed with the map
@@ -250,7 +263,11 @@ struct gm_wall_map {
     std::vector<gm::wall::WallCheckSlot> checks;
     std::vector<gm::wall::WallLocateSlot> locates;
     std::vector<gm::wall::WallAlignSlot> aligns;
-    uint32_t align_rows = 0;   // the patch rows per score block (GM_WALL_ALIGN_ROWS: tests, measurements; 0: the default rule)
+    // gm_wall_map_add_frame_checked: per slot of ctx; gm_wall_map_add_points_checked: the stage call's own rows and block
+    std::vector<gm::wall::WallAddCheckedSlot> add_checks;
+    gm::DevArray<gm_wall_check_point> ac_rows;
+    gm::DevArray<unsigned long long> ac_blk;
+    uint32_t align_rows = 0;  // the patch rows per score block (GM_WALL_ALIGN_ROWS: tests, measurements; 0: the default rule)
     // gm_wall_map_check_objects / gm_wall_check_objects: the tile in blocks (GM_WALL_OBJECT_TILE: tests, measurements) and
     // the scratch
     uint32_t object_tr = GM_WALL_OBJECT_TILE_ROWS, object_tc = GM_WALL_OBJECT_TILE_COLS;
@@ -302,6 +319,9 @@ inline void frame_points(const gm_ctx *ctx, const Slot &sl, WallArgs &w)
 // f64 (a locate's start): the same vectors before the rounding, and o_f in map coordinates.
 struct WallFrame64 { double c[3], d[3], u[3], v[3], of[3]; };
 gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info *info, WallArgs &w, WallFrame64 *f64 = nullptr);
+// An add on `s` (the stream of `slot`) must not be seen by a reader -- a check, a locate, an align -- enqueued before it
+// on another slot: `s` waits for every result outstanding there (nothing to wait for on a map without readers).
+gm_status add_wait_readers(gm_wall_map *m, uint32_t slot, hipStream_t s);
 
 // A stage call's points (gm_wall_map_add_points, gm_wall_map_check_points, ...) on the staging slot: open, whatever the
 // call enqueues ahead of its points, upload, the call's launch, close.

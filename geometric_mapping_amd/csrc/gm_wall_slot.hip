@@ -35,6 +35,7 @@ gm_status check_prepare(gm_wall_map *m, uint32_t slot, uint32_t n_cap, hipStream
     GMW_HIP(ctx, c.h_ctr.reserve(kWallCheckCounters));
     if (c.stage.cap < n_cap || !c.scan.holds(n_cap)) {
         GMW_OK(c.res.wait(ctx));   // the slot's last check may still be writing the old blocks
+        GMW_OK(m->add_checks[slot].res.wait(ctx));   // ... and a checked add behind it still reading the rows
         c.res.have = false;        // (its rows go with the block)
     }
     GMW_HIP(ctx, c.stage.reserve(n_cap));
@@ -58,6 +59,7 @@ gm_status check_enqueue(gm_wall_map *m, uint32_t slot, const WallCheckArgs &a, u
     c.status = m->frame.status;
     c.T = a.T;
     c.anchor = a.w.anchor;
+    c.cloud_seq = ctx->slots[slot].cloud_seq;
     return GM_OK;
 }
 

@@ -42,13 +42,29 @@ __device__ __forceinline__ void wall_global_add(const WallTable &T, uint64_t c, 
     atomicMax(&T.hi[c], hi);
 }
 
-__global__ __launch_bounds__(kWallThreads) void k_wall_add(WallArgs a)
+// kMasked (gm_wall_map_add_*_checked, k_wall_add_checked.hip marks the bits): bit i of m.words set = point i is SKIPPED,
+// decided before every other class: it takes cell -1 and no count ahead of the run merge (every lane still takes part in
+// it) and reaches neither the table nor T.totals.  A wave's 64 points are one aligned 64-bit word of the mask (w0 is a
+// multiple of 64 in every trip: stride is a multiple of kWallThreads), so the mask costs one wave-uniform 8-byte load per
+// trip.  The call's five class counts go to m.ctr[4 ..] beside T.totals.  The unmasked instantiation carries none of it,
+// and each instantiation has an entry point of its own below, so that k_wall_add keeps its name and its arguments.
+template <bool kMasked>
+struct WallMask {};
+template <>
+struct WallMask<true> {
+    const unsigned long long *words;   // ceil(n / 64) words at least
+    unsigned long long *ctr;           // [kWallAddCheckedCounters]
+};
+
+template <bool kMasked>
+__device__ __forceinline__ void wall_add(const WallArgs a, const WallMask<kMasked> m)
 {
+    constexpr int kCls = kMasked ? 5 : 4;
     __shared__ unsigned long long s_sum[kWallCells];
     __shared__ uint32_t s_cnt[kWallCells];
     __shared__ uint32_t s_lo[kWallCells];
     __shared__ uint32_t s_hi[kWallCells];
-    __shared__ uint32_t s_cls[4][kWallWaves];
+    __shared__ uint32_t s_cls[kCls][kWallWaves];
     const uint32_t n = a.n_ptr ? *a.n_ptr : a.n_host;
     const uint32_t nsec = a.n_sectors;
     const uint32_t wcells = a.win_stations * nsec;   // <= kWallCells (the host sizes the window)
@@ -60,18 +76,24 @@ __global__ __launch_bounds__(kWallThreads) void k_wall_add(WallArgs a)
     for (uint32_t c = threadIdx.x; c < wcells; c += kWallThreads) { s_sum[c] = 0ull; s_cnt[c] = 0u; s_lo[c] = 0u; s_hi[c] = 0u; }
     __syncthreads();
 
-    uint32_t cls[4] = {0u, 0u, 0u, 0u};   // mapped, outside, beyond_gate, plane
+    uint32_t cls[kCls] = {};   // mapped, outside, beyond_gate, plane (, skipped)
     const uint64_t stride = (uint64_t)gridDim.x * kWallThreads;
     // wave-uniform trips (the run merge shuffles across the wave)
     for (uint64_t w0 = (uint64_t)blockIdx.x * kWallThreads + (threadIdx.x & ~(uint32_t)(kWave - 1)); w0 < n;
          w0 += kWallUnroll * stride) {
         float4 q[kWallUnroll];
         uint32_t lab[kWallUnroll];
+        unsigned long long mw[kWallUnroll];
 #pragma unroll
         for (int k = 0; k < kWallUnroll; ++k) {
             const uint64_t i = w0 + lane + (uint64_t)k * stride;
             lab[k] = 0u;
             q[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+            mw[k] = 0ull;
+            if constexpr (kMasked) {
+                const uint64_t wk = w0 + (uint64_t)k * stride;   // (wave-uniform; < n <= 2^32)
+                if (wk < n) mw[k] = m.words[__builtin_amdgcn_readfirstlane((uint32_t)(wk >> 6))];
+            }
             if (i < n) {
                 q[k] = a.pts[i];
                 if (a.labels) lab[k] = a.labels[i];
@@ -82,32 +104,36 @@ __global__ __launch_bounds__(kWallThreads) void k_wall_add(WallArgs a)
             const uint64_t i = w0 + lane + (uint64_t)k * stride;
             if (w0 + (uint64_t)k * stride >= n) break;   // (wave-uniform)
             const bool in = i < n;
+            const bool skip = kMasked && ((mw[k] >> lane) & 1ull);
+            const uint32_t live = skip ? 0u : 1u;
             float e = __builtin_nanf("");
             int cell = -1;      // global cell j * n_sectors + k (< 2^24)
             int lcell = -1;     // the same cell in the block's window, -1 outside it
             if (in) {
+                if constexpr (kMasked) cls[kCls - 1] += 1u - live;
                 if (lab[k] == 1u) {
-                    ++cls[3];
+                    cls[3] += live;
                 } else {
                     float t, wx, wy, wz;
                     e = surf_residual(q[k], a.o, a.a, a.R, t, wx, wy, wz);
                     if (!(fabsf(e) <= a.gate)) {
-                        ++cls[2];
+                        cls[2] += live;
                     } else {
                         const float jl = surf_station(t, 0.0f, a.station_length);   // relative to the anchor
                         // (|jl| < 2^62 before the conversion: a far point of the stage call must not overflow it)
                         const int64_t j = fabsf(jl) < 4.0e18f ? a.anchor + (int64_t)jl : -1;
                         if (!(j >= 0 && j < nst)) {
-                            ++cls[1];
+                            cls[1] += live;
                         } else {
                             const uint32_t kk = surf_sector(wx, wy, wz, a.u, a.v, a.two_pi, a.sector_angle, nsec);
                             cell = (int)((uint32_t)j * nsec + kk);
                             if (jl >= win_lo && jl < win_hi) lcell = (int)((uint32_t)((int32_t)jl - a.win_first) * nsec + kk);
-                            ++cls[0];
+                            cls[0] += live;
                         }
                     }
                 }
             }
+            if (skip) { cell = -1; lcell = -1; }
             if (in && a.res) a.res[i] = e;
             if (in && a.cell) a.cell[i] = cell;
             uint32_t cn = 0u, lo = 0u, hi = 0u;
@@ -141,17 +167,23 @@ __global__ __launch_bounds__(kWallThreads) void k_wall_add(WallArgs a)
     }
     // class counts: one atomic per class and block
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < kCls; ++k) {
         const uint32_t v = wave_sum(cls[k]);
         if (lane == 0) s_cls[k][threadIdx.x / kWave] = v;
     }
     __syncthreads();
-    if (threadIdx.x < 4) {
+    if (threadIdx.x < kCls) {
         unsigned long long v = 0ull;
         for (int w = 0; w < kWallWaves; ++w) v += s_cls[threadIdx.x][w];
-        if (v) atomicAdd(&T.totals[threadIdx.x], v);
+        if (v && threadIdx.x < 4) atomicAdd(&T.totals[threadIdx.x], v);
+        if constexpr (kMasked) {   // skipped | mapped, outside, beyond_gate, plane
+            if (v) atomicAdd(&m.ctr[threadIdx.x == kCls - 1 ? 4 : 5 + threadIdx.x], v);
+        }
     }
 }
+
+__global__ __launch_bounds__(kWallThreads) void k_wall_add(WallArgs a) { wall_add<false>(a, WallMask<false>()); }
+__global__ __launch_bounds__(kWallThreads) void k_wall_add_masked(WallArgs a, WallMask<true> m) { wall_add<true>(a, m); }
 
 // ---- the small kernels: convert / copy out a window, merge a raw window, clear, count ----
 
@@ -252,6 +284,14 @@ uint32_t wall_blocks(uint32_t n_cap, uint32_t points_per_block)
 void launch_wall_add(const WallArgs &a, uint32_t n_cap, uint32_t points_per_block, hipStream_t s)
 {
     hipLaunchKernelGGL(k_wall_add, dim3(wall_blocks(n_cap, points_per_block)), dim3(kWallThreads), 0, s, a);
+}
+void launch_wall_add_masked(const WallArgs &a, const unsigned long long *mask, unsigned long long *ctr, uint32_t n_cap,
+                            uint32_t points_per_block, hipStream_t s)
+{
+    WallMask<true> m;
+    m.words = mask;
+    m.ctr = ctr;
+    hipLaunchKernelGGL(k_wall_add_masked, dim3(wall_blocks(n_cap, points_per_block)), dim3(kWallThreads), 0, s, a, m);
 }
 void launch_wall_read(const WallTable &T, uint64_t first, uint64_t n, gm_surface_cell *out, hipStream_t s)
 {

@@ -515,6 +515,17 @@ std::vector<gm_wall_check_point> Processor::checkWallMap(const double pose[12], 
     return points;
 }
 
+gm_wall_add_info Processor::addToWallMapChecked(const double pose[12], const gm_wall_add_checked_params &prm, gm_wall_add_checked_info *info)
+{
+    if (!wall_) throw Error(GM_ERR_NOT_READY, "addToWallMapChecked: createWallMap first");
+    if (newest_slot_ < 0) throw Error(GM_ERR_NOT_READY, "addToWallMapChecked: no frame yet");
+    const unsigned slot = (unsigned)newest_slot_;
+    gm_wall_add_info add;
+    check(gm_wall_map_add_frame_checked(wall_, ctx_, slot, pose, &prm, &add), "addToWallMapChecked");
+    if (info) check(gm_wall_map_get_add_checked(wall_, slot, info), "addToWallMapChecked");
+    return add;
+}
+
 gm_wall_locate_info Processor::locateWallMap(const double pose[12], const gm_wall_locate_params &prm)
 {
     if (!wall_) throw Error(GM_ERR_NOT_READY, "locateWallMap: createWallMap first");

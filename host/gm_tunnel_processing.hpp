@@ -180,6 +180,10 @@ public:
     // gm_wall_map_get_check), ascending by index; the map is not changed.  info, when given, receives the call's counts.
     // Check, then addToWallMap: against what was there, then contribute.
     std::vector<gm_wall_check_point> checkWallMap(const double pose[12], const gm_wall_check_params &prm, gm_wall_check_info *info = nullptr);
+    // addToWallMap less the points the last checkWallMap of the newest frame selected (gm_wall_map_add_frame_checked +
+    // gm_wall_map_get_add_checked): the order per frame is then locate, align, checkWallMap, addToWallMapChecked.  info, when
+    // given, receives the call's counts (and the call waits for them).  GM_ERR_NOT_READY without a check of this frame.
+    gm_wall_add_info addToWallMapChecked(const double pose[12], const gm_wall_add_checked_params &prm, gm_wall_add_checked_info *info = nullptr);
     // the pose of the newest frame corrected against the map (gm_wall_map_locate_frame + gm_wall_map_get_locate): the lateral
     // offset and the tilt against the axis are estimated, chainage and roll stay the caller's; the map is not changed.
     // info.pose is the corrected pose (NaN when info.status & GM_LOCATE_FAILED_MASK).  The order per frame: locateWallMap,

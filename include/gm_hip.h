@@ -1525,6 +1525,78 @@ gm_status gm_wall_check_objects(gm_wall_map *map, const gm_wall_check_point *row
 gm_status gm_wall_object_metrics(const gm_wall_params *p, const gm_wall_object_params *op, const gm_wall_object *o,
                                  struct gm_wall_object_metrics *out);
 
+/* ---- an add less the check's changed rows (gm_wall_map_add_frame_checked, gm_wall_map_add_points_checked) ---------------
+ * A cell is count, sum, min_key, max_key, and integer sums and maxima cannot be taken back: a person at the wall binned
+ * once stays in the clearance's innermost point, in the envelope and in the mean for the rest of the map's life.  The map's
+ * gate only keeps out what is far from the DESIGN; the check that runs before the add knows what is far from the SURVEY,
+ * and its changed rows still lie on the device.  This add leaves out the points those rows name:
+ *   params   skip      bits GM_WALL_SKIP_NEG = 1 (rows inside the profile), GM_WALL_SKIP_POS = 2 (rows farther out);
+ *                      default 3; 0 or any other bit is GM_ERR_INVALID_ARG
+ *            min_delta metres in [0, 8], default 0;  S = (int64) rint(min_delta * 2^20), fp64, once on the host
+ *   per row  dq = (int64) rint(delta * 2^20) by gm_wall_map_check_objects' own rule (exact for a check's rows).
+ *            REJECTED  if dq == 0, delta not finite, or index >= n_points.
+ *            SELECTED  if (dq < 0 and skip & NEG and -dq >= S) or (dq > 0 and skip & POS and dq >= S).
+ *            KEPT      otherwise.
+ *   per point  SKIPPED if some selected row names its index; otherwise exactly gm_wall_map_add_frame's classes and
+ *              updates (plane, beyond_gate under the MAP's gate, outside, mapped).  Skipped is decided first.
+ *   map      cells, cells_hit and the four cumulative class totals receive the non-skipped points only; skipped points
+ *            enter no total; `frames` counts the call as one add.
+ * After a check and a checked add the map's raw cells and totals are, byte for byte, those of gm_wall_map_add_points of
+ * the valid cloud with the skipped indices deleted, under the same pose and labels; with no selected row they are
+ * gm_wall_map_add_frame's.  On the device: one bit per point of the slot's frame in a mask that is zeroed per call, one
+ * thread per staged row marks (a 32-bit atomic OR; the row count is the check's device counter, n_points the device word
+ * n_valid: no host round trip), then gm_wall_map_add_frame's kernel in an instantiation that reads one 64-bit mask word
+ * per wave and trip.  When to use which add: INTEGRATION.md, "Changed points, node side". */
+enum { GM_WALL_SKIP_NEG = 1, GM_WALL_SKIP_POS = 2 };
+
+typedef struct gm_wall_add_checked_params {
+    uint32_t struct_size;     /* = sizeof(gm_wall_add_checked_params) */
+    uint32_t skip;            /* GM_WALL_SKIP_NEG | GM_WALL_SKIP_POS (default both); not 0 */
+    double   min_delta;       /* metres, in [0, 8] (default 0): a selected row has |delta| >= min_delta */
+} gm_wall_add_checked_params;
+
+typedef struct gm_wall_add_checked_info {
+    uint32_t struct_size;     /* = sizeof(gm_wall_add_checked_info), filled by the library */
+    uint32_t status;          /* GM_SURF_OK or GM_SURF_UP_FALLBACK: the design frame's */
+    int64_t  min_delta_q;     /* S */
+    uint32_t n_points;        /* the valid cloud's points = skipped + plane + beyond_gate + outside + mapped */
+    uint32_t n_rows;          /* the rows seen = rows_neg + rows_pos + rows_kept + rows_rejected */
+    uint32_t rows_neg, rows_pos;      /* selected rows, by sign */
+    uint32_t rows_kept, rows_rejected;
+    uint32_t skipped;         /* POINTS some selected row names (rows may name a point twice) */
+    uint32_t plane, beyond_gate, outside, mapped;   /* the add's classes over the points that are not skipped */
+    uint32_t reserved;        /* 0 */
+} gm_wall_add_checked_info;
+
+/* Host only: the defaults of the table above.  A NULL is ignored. */
+void gm_wall_add_checked_default_params(gm_wall_add_checked_params *p);
+/* Host only: GM_OK iff the block would be accepted (struct_size, skip in 1 .. 3, min_delta in [0, 8]). */
+gm_status gm_wall_add_checked_check_params(const gm_wall_add_checked_params *p);
+/* gm_wall_map_add_frame less the points that the last check on (map, slot) selected.  Enqueued on the slot's stream behind
+ * the frame and behind that check; returns without waiting; with GM_CFG_GRAPH it is plain launches after the graph.
+ * Arguments and readiness as gm_wall_map_add_frame (prm NULL: the defaults).  In addition GM_ERR_NOT_READY when no check
+ * was enqueued on (map, slot) FOR THE FRAME THE SLOT NOW HOLDS: a check left over from an earlier frame is refused, not
+ * applied to another cloud's indices.  The pose need not be the check's.  The check's result stays readable and its rows
+ * are not changed.  Other slots' checks, locates and aligns are ordered against it as against a plain add.  Scratch per
+ * (map, slot) -- one bit per point of the slot's frame, a counter block -- is allocated on first use, kept grow-only and
+ * freed with the map; a map that never asks allocates nothing. */
+gm_status gm_wall_map_add_frame_checked(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, const double pose[12],
+                                        const gm_wall_add_checked_params *prm, gm_wall_add_info *add_info);
+/* The counts of the last checked add enqueued on (map, slot).  Waits for that call only (an event recorded behind it, not
+ * the slot's stream).  GM_ERR_NOT_READY: no checked add was enqueued on (map, slot); GM_ERR_INVALID_ARG: NULL map / info,
+ * a slot out of range.  gm_wall_map_add_points_checked does not count as one. */
+gm_status gm_wall_map_get_add_checked(gm_wall_map *map, uint32_t slot, gm_wall_add_checked_info *info);
+/* The same kernels as one blocking stage call on host buffers (slot 0 of the map's context; gm_wall_map_add_points'
+ * conventions).  rows: n_rows gm_wall_check_points in any order, duplicates allowed (NULL with n_rows 0); they are uploaded
+ * into scratch of the call's own (32 B per row), so the check result stored for slot 0 is not touched.  info (may be NULL)
+ * as gm_wall_map_get_add_checked.  residual / cell (may be NULL) of a skipped point are the e of the add's chain and -1.
+ * Fed a slot's valid cloud, labels and gm_wall_map_get_check's rows, it changes the map exactly as the frame call does.
+ * GM_ERR_INVALID_ARG: NULL map / xyz with n > 0 / rows with n_rows > 0, bad pose, bad params. */
+gm_status gm_wall_map_add_points_checked(gm_wall_map *map, const float *xyz, uint32_t n, const uint8_t *labels,
+                                         const double pose[12], const gm_wall_add_checked_params *prm,
+                                         const gm_wall_check_point *rows, uint32_t n_rows, gm_wall_add_info *add_info,
+                                         gm_wall_add_checked_info *info, float *residual, int32_t *cell);
+
 /* "Compressed map" record of a completed slot.  The reference defines no such
  * output; this is a build-defined format: header, primitive records,
  * then n_voxels rows of x,y,z,count (float32).  Returns the bytes needed in
