@@ -291,6 +291,49 @@ class WallSectionMetrics(C.Structure):
                 ("rms_m", C.c_double), ("area_m2", C.c_double), ("coverage", C.c_double)]
 
 
+class WallQuantityParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("section_stations", C.c_uint32), ("min_count", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class WallQuantity(C.Structure):
+    _fields_ = [("station_from", C.c_uint32), ("stations", C.c_uint32), ("zone", C.c_uint32), ("profile", C.c_uint32),
+                ("under", C.c_uint32), ("within", C.c_uint32), ("over", C.c_uint32), ("unsurveyed", C.c_uint32),
+                ("points", C.c_uint64), ("under_area", C.c_int64), ("over_area", C.c_int64), ("excess_area", C.c_int64),
+                ("peak_under", C.c_int64), ("peak_over", C.c_int64), ("peak_under_sector", C.c_uint32),
+                ("peak_over_sector", C.c_uint32)]
+
+
+class WallQuantitiesInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("station0", C.c_uint32), ("n_stations", C.c_uint32), ("n_sectors", C.c_uint32),
+                ("section_stations", C.c_uint32), ("sections", C.c_uint32), ("n_zones", C.c_uint32), ("n_profiles", C.c_uint32),
+                ("radius_q", C.c_int64), ("unmeasured", C.c_uint64), ("empty", C.c_uint64), ("unusable", C.c_uint64),
+                ("under", C.c_uint64), ("over", C.c_uint64), ("within", C.c_uint64), ("sections_under", C.c_uint32),
+                ("sections_over", C.c_uint32)]
+
+
+class WallQuantityColumnResult(C.Structure):
+    _fields_ = [("cls", C.c_uint32), ("v", C.c_int32), ("under_area", C.c_int64), ("over_area", C.c_int64),
+                ("excess_area", C.c_int64), ("over_line", C.c_int64)]
+
+
+class WallQuantityMetrics(C.Structure):
+    _fields_ = [("chainage_from", C.c_double), ("chainage_to", C.c_double), ("length", C.c_double),
+                ("under_area_m2", C.c_double), ("over_area_m2", C.c_double), ("excess_area_m2", C.c_double),
+                ("paid_area_m2", C.c_double), ("under_volume_m3", C.c_double), ("over_volume_m3", C.c_double),
+                ("excess_volume_m3", C.c_double), ("paid_volume_m3", C.c_double), ("peak_under_m", C.c_double),
+                ("peak_over_m", C.c_double), ("peak_under_angle_deg", C.c_double), ("peak_over_angle_deg", C.c_double),
+                ("coverage", C.c_double), ("reserved", C.c_double)]
+
+
+class WallQuantityRun(C.Structure):
+    _fields_ = [("station_from", C.c_uint32), ("stations", C.c_uint32), ("zone", C.c_uint32), ("sections", C.c_uint32),
+                ("chainage_from", C.c_double), ("chainage_to", C.c_double), ("under", C.c_uint64), ("within", C.c_uint64),
+                ("over", C.c_uint64), ("unsurveyed", C.c_uint64), ("points", C.c_uint64), ("under_volume_m3", C.c_double),
+                ("over_volume_m3", C.c_double), ("excess_volume_m3", C.c_double), ("paid_volume_m3", C.c_double),
+                ("peak_under", C.c_int64), ("peak_over", C.c_int64), ("peak_under_station", C.c_uint32),
+                ("peak_under_sector", C.c_uint32), ("peak_over_station", C.c_uint32), ("peak_over_sector", C.c_uint32)]
+
+
 class WallCheckParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reference", C.c_uint32), ("min_count", C.c_uint32), ("reserved", C.c_uint32),
                 ("threshold", C.c_double), ("gate", C.c_double)]
@@ -455,6 +498,9 @@ def load():
                                                C.POINTER(WallClearanceCell), C.POINTER(WallClearanceInfo), C.POINTER(WallClearanceRun))
     wsprmp, wssump, wssecp, wsinfop, wsmetp = (C.POINTER(WallSectionParams), C.POINTER(WallSectionSums), C.POINTER(WallSection),
                                                C.POINTER(WallSectionsInfo), C.POINTER(WallSectionMetrics))
+    wqprmp, wqrecp, wqinfop, wqcolp, wqmetp, wqrunp = (C.POINTER(WallQuantityParams), C.POINTER(WallQuantity),
+                                                       C.POINTER(WallQuantitiesInfo), C.POINTER(WallQuantityColumnResult),
+                                                       C.POINTER(WallQuantityMetrics), C.POINTER(WallQuantityRun))
     wkprmp, wkptp, wkinfop = C.POINTER(WallCheckParams), C.POINTER(WallCheckPoint), C.POINTER(WallCheckInfo)
     wcaprmp, wcainfop = C.POINTER(WallAddCheckedParams), C.POINTER(WallAddCheckedInfo)
     wlprmp, wlinfop = C.POINTER(WallLocateParams), C.POINTER(WallLocateInfo)
@@ -540,6 +586,14 @@ def load():
         "gm_wall_section_solve": (C.c_int, [wssump, u32, u32, C.POINTER(C.c_int64), u32p]),
         "gm_wall_section_metrics": (C.c_int, [wprmp, wssecp, u32, wsmetp]),
         "gm_wall_map_sections": (C.c_int, [vp, vp, u32, u32, wsprmp, wsinfop, wssecp, u32, u32p, wssump]),
+        "gm_wall_quantity_default_params": (None, [wqprmp]),
+        "gm_wall_quantity_check_params": (C.c_int, [wprmp, wqprmp, i32p, i32p, u32, u8p, u32, u8p, u32]),
+        "gm_wall_quantity_column": (C.c_int, [C.c_int64, u64, C.c_int64, C.c_int, u64, C.c_int64, u32, C.c_int32, C.c_int32, u32,
+                                              wqcolp]),
+        "gm_wall_quantity_metrics": (C.c_int, [wprmp, wqrecp, wqmetp]),
+        "gm_wall_quantity_runs": (C.c_int, [wprmp, wqrecp, u32, u32, u32, u32, wqrunp, u32, u32p]),
+        "gm_wall_map_quantities": (C.c_int, [vp, vp, u32, u32, i32p, i32p, u32, u8p, u8p, u32, wqprmp, wqinfop, wqrecp, u32, u32p,
+                                             i32p]),
         "gm_wall_check_default_params": (None, [wkprmp]),
         "gm_wall_check_classify": (C.c_int, [wkprmp, wrawp, C.c_float, C.POINTER(C.c_int64), u32p]),
         "gm_wall_map_check_frame": (C.c_int, [vp, vp, u32, dp, wkprmp, waddp]),

@@ -713,6 +713,112 @@ def wall_clearance_runs(prm, stations, station0=0, max_gap=0):
     return runs[:int(got.value)].copy()
 
 
+WALL_QUANTITY = np.dtype([("station_from", "<u4"), ("stations", "<u4"), ("zone", "<u4"), ("profile", "<u4"), ("under", "<u4"),
+                          ("within", "<u4"), ("over", "<u4"), ("unsurveyed", "<u4"), ("points", "<u8"), ("under_area", "<i8"),
+                          ("over_area", "<i8"), ("excess_area", "<i8"), ("peak_under", "<i8"), ("peak_over", "<i8"),
+                          ("peak_under_sector", "<u4"), ("peak_over_sector", "<u4")])   # gm_wall_quantity, 88 bytes
+WALL_QUANTITY_RUN = np.dtype([("station_from", "<u4"), ("stations", "<u4"), ("zone", "<u4"), ("sections", "<u4"),
+                              ("chainage_from", "<f8"), ("chainage_to", "<f8"), ("under", "<u8"), ("within", "<u8"),
+                              ("over", "<u8"), ("unsurveyed", "<u8"), ("points", "<u8"), ("under_volume_m3", "<f8"),
+                              ("over_volume_m3", "<f8"), ("excess_volume_m3", "<f8"), ("paid_volume_m3", "<f8"),
+                              ("peak_under", "<i8"), ("peak_over", "<i8"), ("peak_under_station", "<u4"),
+                              ("peak_under_sector", "<u4"), ("peak_over_station", "<u4"),
+                              ("peak_over_sector", "<u4")])   # gm_wall_quantity_run, 136 bytes
+WALL_QUANTITY_UNMEASURED = 0xFF
+WALL_QUANTITY_CLASSES = ("unmeasured", "empty", "unusable", "under", "over", "within")   # GM_WALL_QUANTITY_CLASS_* order
+WALL_QUANTITY_RUNS_ALL_ZONES = 1
+_QUANTITIES_INFO = ("station0", "n_stations", "n_sectors", "section_stations", "sections", "n_zones", "n_profiles", "radius_q",
+                    "unmeasured", "empty", "unusable", "under", "over", "within", "sections_under", "sections_over")
+
+
+def _wall_quantity_params(**kw):
+    p = _lib.WallQuantityParams()
+    _lib.load().gm_wall_quantity_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k == "struct_size":
+            raise TypeError(f"unknown quantity parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def _quantity_tables(lo_q, hi_q, n_sectors):
+    lo, hi = _gauge_tables(lo_q, n_sectors), _gauge_tables(hi_q, n_sectors)
+    if lo.shape != hi.shape:
+        raise ValueError("lo_q and hi_q must have the same shape")
+    return lo, hi
+
+
+def _u8_or_none(a):
+    """(the array kept alive, its uint8 pointer) of an optional uint8 vector."""
+    if a is None:
+        return None, None
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.uint8).reshape(-1))
+    return a, (a.ctypes.data_as(C.POINTER(C.c_uint8)) if len(a) else None)
+
+
+def wall_quantity_check_params(prm, lo_q, hi_q, n=0, section_profile=None, zone=None, n_zones=1, params=None, n_profiles=None):
+    """gm_wall_quantity_check_params (host only): the status for a map with the gm_wall_params `prm`, a window of `n`
+    stations, the line tables lo_q / hi_q (int32 (n_sectors,) or (n_profiles, n_sectors), passed as they are; n_profiles
+    None: their first dimension) and the optional tables; params: a gm_wall_quantity_params or None."""
+    lo = np.ascontiguousarray(np.asarray(lo_q, dtype=np.int32))
+    hi = np.ascontiguousarray(np.asarray(hi_q, dtype=np.int32))
+    if n_profiles is None:
+        n_profiles = lo.shape[0] if lo.ndim == 2 else 1
+    sp, spp = _u8_or_none(section_profile)
+    zn, znp = _u8_or_none(zone)
+    return _lib.load().gm_wall_quantity_check_params(
+        C.byref(prm), C.byref(params) if params is not None else None, lo.ctypes.data_as(C.POINTER(C.c_int32)),
+        hi.ctypes.data_as(C.POINTER(C.c_int32)), n_profiles, spp, int(n), znp, int(n_zones))
+
+
+def wall_quantity_column(radius_q, count, total, lo, hi, base=None, min_count=8, zone_entry=0):
+    """gm_wall_quantity_column (host only): one column restated -- (count, total) its merged raw pair, base the
+    baseline's (count, sum) or None.  Returns a dict: cls (an index into WALL_QUANTITY_CLASSES), v (None when the column
+    is not usable), under_area, over_area, excess_area, over_line."""
+    out = _lib.WallQuantityColumnResult()
+    bc, bs = (int(base[0]), int(base[1])) if base is not None else (0, 0)
+    st = _lib.load().gm_wall_quantity_column(int(radius_q), int(count), int(total), int(base is not None), bc, bs, int(min_count),
+                                             int(lo), int(hi), int(zone_entry), C.byref(out))
+    if st != _lib.GM_OK:
+        raise _lib.GmError(st, "gm_wall_quantity_column refused its arguments")
+    d = {k: int(getattr(out, k)) for k, _t in _lib.WallQuantityColumnResult._fields_}
+    if d["v"] == -2 ** 31:
+        d["v"] = None
+    return d
+
+
+def wall_quantity_metrics(prm, record):
+    """gm_wall_quantity_metrics (host only): the fp64 metrics dict of one WALL_QUANTITY record under the gm_wall_params
+    `prm`."""
+    r = np.ascontiguousarray(np.asarray(record, dtype=WALL_QUANTITY).reshape(1))
+    out = _lib.WallQuantityMetrics()
+    st = _lib.load().gm_wall_quantity_metrics(C.byref(prm), r.ctypes.data_as(C.POINTER(_lib.WallQuantity)), C.byref(out))
+    if st != _lib.GM_OK:
+        raise _lib.GmError(st, "gm_wall_quantity_metrics refused the record")
+    return {k: float(getattr(out, k)) for k, _t in _lib.WallQuantityMetrics._fields_ if k != "reserved"}
+
+
+def wall_quantity_runs(prm, records, n_zones=1, run_sections=1, all_zones=False):
+    """gm_wall_quantity_runs (host only): the WALL_QUANTITY_RUN records of the WALL_QUANTITY records [sections, n_zones]
+    of one call, folded into pay intervals of `run_sections` sections, per zone or over all zones."""
+    L = _lib.load()
+    r = np.ascontiguousarray(np.asarray(records, dtype=WALL_QUANTITY).reshape(-1))
+    if int(n_zones) < 1 or len(r) % int(n_zones):
+        raise ValueError("records must hold n_zones records per section")
+    rp = r.ctypes.data_as(C.POINTER(_lib.WallQuantity)) if len(r) else None
+    ns, flags = len(r) // int(n_zones), WALL_QUANTITY_RUNS_ALL_ZONES if all_zones else 0
+    got = C.c_uint32(0)
+    st = L.gm_wall_quantity_runs(C.byref(prm), rp, ns, int(n_zones), int(run_sections), flags, None, 0, C.byref(got))
+    if st != _lib.GM_OK:
+        raise _lib.GmError(st, "gm_wall_quantity_runs refused its arguments")
+    runs = np.zeros(max(int(got.value), 1), dtype=WALL_QUANTITY_RUN)
+    st = L.gm_wall_quantity_runs(C.byref(prm), rp, ns, int(n_zones), int(run_sections), flags,
+                                 runs.ctypes.data_as(C.POINTER(_lib.WallQuantityRun)), len(runs), C.byref(got))
+    if st != _lib.GM_OK:
+        raise _lib.GmError(st, "gm_wall_quantity_runs failed")
+    return runs[:int(got.value)].copy()
+
+
 WALL_SECTION = np.dtype([("station_from", "<u4"), ("stations", "<u4"), ("status", "<u4"), ("usable", "<u4"), ("fitted", "<u4"),
                          ("accepted", "<u4"), ("rejected", "<u4"), ("largest_gap", "<u4"), ("points", "<u8"),
                          ("coef_q", "<i8", (9,)), ("rss", "<u8"), ("peak_out", "<i8"), ("peak_in", "<i8"),
@@ -1134,6 +1240,53 @@ class WallMap:
     def section_metrics(self, section, harmonics=2):
         """gm_wall_section_metrics of one WALL_SECTION record under this map's parameters."""
         return wall_section_metrics(self.prm, section, harmonics)
+
+    @staticmethod
+    def quantity_params(**kw):
+        """gm_wall_quantity_params with the library's defaults, then the keywords (section_stations, min_count)."""
+        return _wall_quantity_params(**kw)
+
+    def quantities(self, lo_q, hi_q, station0=0, n=None, baseline=None, section_profile=None, zone=None, n_zones=1,
+                   profile_rows=False, **params):
+        """gm_wall_map_quantities: under- and overbreak per section and zone of stations [station0, station0 + n) against
+        the two lines lo_q / hi_q, int32 (n_sectors,) or (n_profiles, n_sectors), offsets in units of 2^-20 m from the
+        design radius or, with `baseline` (another WallMap of this context on the same grid), from that earlier wall.
+        section_profile (uint8 per section, optional) picks each section's table; zone (uint8 [n_sectors], optional, 0xFF:
+        not measured) its sectors' zones.  Returns (info dict, WALL_QUANTITY records [sections, n_zones], the int32
+        profile rows [sections, n_sectors] or None)."""
+        s0, n = self._window(station0, n)
+        p = self.quantity_params(**params)
+        lo, hi = _quantity_tables(lo_q, hi_q, self.n_sectors)
+        i32 = C.POINTER(C.c_int32)
+        S = max(int(p.section_stations), 1)
+        NS, nz = (n + S - 1) // S, int(n_zones)
+        sp, spp = _u8_or_none(section_profile)
+        zn, znp = _u8_or_none(zone)
+        if sp is not None and len(sp) != NS:
+            raise ValueError("section_profile must hold one entry per section")
+        if zn is not None and len(zn) != self.n_sectors:
+            raise ValueError("zone must hold one entry per sector")
+        bh = baseline._h() if baseline is not None else None
+        info = _lib.WallQuantitiesInfo()
+        got = C.c_uint32(0)
+        cap = NS * max(nz, 0)
+        rec = np.zeros(max(cap, 1), dtype=WALL_QUANTITY)
+        rows = np.zeros(max(NS * self.n_sectors, 1), dtype=np.int32) if profile_rows else None
+        self._ctx._check(self._L.gm_wall_map_quantities(
+            self._h(), bh, s0, n, lo.ctypes.data_as(i32), hi.ctypes.data_as(i32), lo.shape[0], spp, znp, nz, C.byref(p),
+            C.byref(info), rec.ctypes.data_as(C.POINTER(_lib.WallQuantity)), cap, C.byref(got),
+            rows.ctypes.data_as(i32) if profile_rows else None))
+        nr = int(got.value)
+        out_rows = rows[:NS * self.n_sectors].reshape(NS, self.n_sectors).copy() if profile_rows else None
+        return {k: int(getattr(info, k)) for k in _QUANTITIES_INFO}, rec[:nr].reshape(NS, nz).copy(), out_rows
+
+    def quantity_metrics(self, record):
+        """gm_wall_quantity_metrics of one WALL_QUANTITY record under this map's parameters."""
+        return wall_quantity_metrics(self.prm, record)
+
+    def quantity_runs(self, records, n_zones=1, run_sections=1, all_zones=False):
+        """gm_wall_quantity_runs of one call's records under this map's parameters."""
+        return wall_quantity_runs(self.prm, records, n_zones, run_sections, all_zones)
 
     @staticmethod
     def check_params(**kw):

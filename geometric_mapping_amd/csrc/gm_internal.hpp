@@ -590,6 +590,63 @@ __host__ __device__ inline long long wall_section_sat(long long m)
 {
     return m > kWallSectionSat ? kWallSectionSat : (m < -kWallSectionSat ? -kWallSectionSat : m);
 }
+// k_wall_quantities.hip (gm_wall_map_quantities): one kernel per chunk of whole sections
+// u64 words 0 .. 5: the six classes (GM_WALL_QUANTITY_CLASS_* order); 6 sections_under; 7 sections_over
+constexpr int kWallQuantityCounters = 8;
+constexpr int32_t kWallQuantityNoValue = -2147483647 - 1;   // the profile entry of a column that is not usable
+struct WallQuantityArgs {
+    WallTable map, base;       // base: the baseline's table when has_base
+    uint32_t has_base;
+    uint32_t n, nsec;          // the window's stations, the map's sectors
+    uint64_t first;            // station0 * nsec: map-wide index of window cell 0
+    uint32_t station0, S;      // the window's first station, section_stations
+    uint32_t sec0, nsect;      // the chunk: sections [sec0, sec0 + nsect)
+    uint32_t min_count, n_zones;
+    long long Rq;
+    const int32_t *lo, *hi;    // [n_profiles][nsec]
+    const uint8_t *section_profile;   // [NS], nullptr: table 0
+    const uint8_t *zone;       // [nsec], nullptr: zone 0
+    gm_wall_quantity *records; // [nsect][n_zones]: the chunk's staging
+    int32_t *rows;             // [nsect][nsec] or nullptr
+    unsigned long long *ctr;   // [kWallQuantityCounters], zeroed by the caller on the same stream
+};
+void launch_wall_quantities(const WallQuantityArgs &a, hipStream_t s);
+// the rule's integers of one column, shared by the kernel and the host (gm_wall_quantity_column)
+struct WallQuantityColumn {
+    uint32_t cls;
+    bool usable;
+    long long v;               // x - b0 of a usable column
+    long long line;            // x - L of a usable column
+    long long under, over, excess;   // the three area terms
+};
+__host__ __device__ inline long long wall_quantity_ann(long long a, long long b)   // b >= a >= 0
+{
+    return ((b - a) * (b + a)) >> 20;
+}
+__host__ __device__ inline WallQuantityColumn wall_quantity_column(long long Rq, unsigned long long cn, long long sm, bool has_base,
+                                                                   unsigned long long bcn, long long bsm, uint32_t min_count,
+                                                                   long long lo, long long hi, bool unmeasured)
+{
+    WallQuantityColumn c;
+    c.v = c.line = c.under = c.over = c.excess = 0;
+    c.usable = cn >= (unsigned long long)min_count && (!has_base || bcn >= (unsigned long long)min_count);
+    const bool empty = cn == 0ull && (!has_base || bcn == 0ull);
+    c.cls = unmeasured ? GM_WALL_QUANTITY_CLASS_UNMEASURED : (empty ? GM_WALL_QUANTITY_CLASS_EMPTY : GM_WALL_QUANTITY_CLASS_UNUSABLE);
+    if (!c.usable) return c;
+    const long long b0 = Rq + (has_base ? wall_section_sat(wall_section_value(bsm, bcn)) : 0ll);
+    const long long x = Rq + wall_section_sat(wall_section_value(sm, cn));
+    const long long L = b0 + lo, H = b0 + hi;
+    c.v = x - b0;
+    c.line = x - L;
+    if (unmeasured) return c;   // (its value is drawn, its areas are nobody's)
+    const long long xc = x < 0 ? 0 : x, Lc = L < 0 ? 0 : L, Hc = H < 0 ? 0 : H;
+    const bool under = c.v < lo, over = c.v > hi;
+    c.cls = under ? GM_WALL_QUANTITY_CLASS_UNDER : (over ? GM_WALL_QUANTITY_CLASS_OVER : GM_WALL_QUANTITY_CLASS_WITHIN);
+    if (under) c.under = wall_quantity_ann(xc, Lc);
+    if (c.line > 0) c.over = wall_quantity_ann(Lc, xc);
+    if (over) c.excess = wall_quantity_ann(Hc, xc);
+    return c;
+}
 // k_wall_objects.hip (gm_wall_map_check_objects, gm_wall_check_objects): bin -> tiles -> seams -> flatten | blocks ->
 // reduce -> select | rows
 constexpr uint32_t kWallObjectTileBlocks = 4096;      // the most window blocks of a tile (its LDS tables)

@@ -392,6 +392,10 @@ gm_status gm_wall_map_create(gm_ctx *ctx, const gm_wall_params *params, gm_wall_
         const unsigned long long v = strtoull(e, nullptr, 10);
         m->clear_chunk = v < kStageCells ? (uint32_t)v : 0u;
     }
+    if (const char *e = getenv("GM_WALL_QUANTITY_CHUNK")) {   // sections; 0 or more than the default: the default (scratch is sized by it)
+        const unsigned long long v = strtoull(e, nullptr, 10);
+        m->quantity_chunk = v < kStageBytes ? (uint32_t)v : 0u;
+    }
     design_frame_of(m->prm, m->frame);
     auto body = [&]() -> gm_status {
         GMW_HIP(ctx, hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
@@ -981,6 +985,111 @@ gm_status gm_wall_map_sections(gm_wall_map *map, gm_wall_map *baseline, uint32_t
         }
         if (sections) memcpy(sections + sec0, rec.data(), (size_t)ns * sizeof(gm_wall_section));
     }
+    return GM_OK;
+}
+
+gm_status gm_wall_map_quantities(gm_wall_map *map, gm_wall_map *baseline, uint32_t station0, uint32_t n, const int32_t *lo_q,
+                                 const int32_t *hi_q, uint32_t n_profiles, const uint8_t *section_profile,
+                                 const uint8_t *zone, uint32_t n_zones, const gm_wall_quantity_params *prm,
+                                 gm_wall_quantities_info *info, gm_wall_quantity *records, uint32_t capacity, uint32_t *n_out,
+                                 int32_t *profile_rows)
+{
+    if (!map) return GM_ERR_INVALID_ARG;
+    gm_ctx *ctx = map->ctx;
+    if (n_out) *n_out = 0;
+    if (!info) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_quantities: NULL info");
+    const gm_wall_quantity_params qp = params_or(prm, gm_wall_quantity_default_params);
+    GMW_OK(check_window(map, station0, n, ~0ull, nullptr, ""));   // (before the tables: section_profile has ceil(n / S) entries)
+    long long Rq;
+    if (!quantity_ok(&map->prm, qp, lo_q, hi_q, n_profiles, section_profile, n, zone, n_zones, Rq))
+        return gm_fail(ctx, GM_ERR_INVALID_ARG,
+                       "gm_wall_map_quantities: struct_size mismatch, a parameter outside its limits, a bad line, profile or zone table or a radius above 4096 m");
+    if (!records && (capacity || profile_rows))
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_quantities: NULL records with a capacity or with profile rows");
+    GMW_OK(check_baseline(map, baseline, "gm_wall_map_quantities"));
+    GMW_OK(sync_map(map));
+    if (baseline) GMW_OK(sync_map(baseline));
+    const uint32_t nsec = map->prm.n_sectors, S = qp.section_stations;
+    const uint32_t NS = n ? (n - 1u) / S + 1u : 0u;
+    memset(info, 0, sizeof(*info));
+    info->struct_size = (uint32_t)sizeof(gm_wall_quantities_info);
+    info->station0 = station0;
+    info->n_stations = n;
+    info->n_sectors = nsec;
+    info->section_stations = S;
+    info->sections = NS;
+    info->n_zones = n_zones;
+    info->n_profiles = n_profiles;
+    info->radius_q = Rq;
+    const uint32_t total = NS * n_zones;   // <= 2^24 8
+    if (n_out) *n_out = total;
+    if (!n) return GM_OK;
+
+    // chunks of whole sections: the staging of a full one stays within kStageBytes
+    const uint64_t per_section = (uint64_t)n_zones * sizeof(gm_wall_quantity) + (profile_rows ? (uint64_t)nsec * sizeof(int32_t) : 0u);
+    const uint32_t fit = (uint32_t)std::max<uint64_t>(kStageBytes / per_section, 1u);
+    const uint32_t cs = std::min(map->quantity_chunk ? std::min(map->quantity_chunk, fit) : fit, NS);   // sections of a full chunk
+    const size_t entries = (size_t)n_profiles * nsec;
+    GMW_HIP(ctx, map->qt_lines.reserve(2u * entries));
+    GMW_HIP(ctx, map->qt_index.reserve((uint64_t)NS + nsec));
+    GMW_HIP(ctx, map->qt_stage.reserve((uint64_t)cs * per_section));
+    GMW_HIP(ctx, map->qt_ctr.reserve(kWallQuantityCounters));
+    int32_t *d_lo = map->qt_lines.p, *d_hi = map->qt_lines.p + entries;
+    uint8_t *d_profile = map->qt_index.p, *d_zone = map->qt_index.p + NS;
+    GMW_HIP(ctx, hipMemcpyAsync(d_lo, lo_q, entries * sizeof(int32_t), hipMemcpyHostToDevice, map->stream));
+    GMW_HIP(ctx, hipMemcpyAsync(d_hi, hi_q, entries * sizeof(int32_t), hipMemcpyHostToDevice, map->stream));
+    if (section_profile) GMW_HIP(ctx, hipMemcpyAsync(d_profile, section_profile, NS, hipMemcpyHostToDevice, map->stream));
+    if (zone) GMW_HIP(ctx, hipMemcpyAsync(d_zone, zone, nsec, hipMemcpyHostToDevice, map->stream));
+    GMW_HIP(ctx, hipMemsetAsync(map->qt_ctr.p, 0, kWallQuantityCounters * 8, map->stream));
+
+    Carve stage{map->qt_stage.p};
+    WallQuantityArgs a;
+    memset(&a, 0, sizeof(a));
+    a.map = map->table;
+    a.has_base = baseline ? 1u : 0u;
+    a.base = baseline ? baseline->table : map->table;
+    a.n = n; a.nsec = nsec;
+    a.first = (uint64_t)station0 * nsec;
+    a.station0 = station0; a.S = S;
+    a.min_count = qp.min_count; a.n_zones = n_zones;
+    a.Rq = Rq;
+    a.lo = d_lo; a.hi = d_hi;
+    a.section_profile = section_profile ? d_profile : nullptr;
+    a.zone = zone ? d_zone : nullptr;
+    a.records = stage.take<gm_wall_quantity>((uint64_t)cs * n_zones);
+    a.rows = profile_rows ? stage.take<int32_t>((uint64_t)cs * nsec) : nullptr;
+    a.ctr = map->qt_ctr.p;
+
+    // A count query and a call without room run the same launches: the totals of info are the device's.  Only the copies
+    // of the two arrays depend on the buffers.
+    const bool copying = records && capacity >= total;
+    unsigned long long ctr[kWallQuantityCounters];
+    for (uint32_t sec0 = 0; sec0 < NS; sec0 += cs) {   // (the trip count depends on the window alone)
+        const uint32_t ns = std::min(cs, NS - sec0);
+        a.sec0 = sec0;
+        a.nsect = ns;
+        launch_wall_quantities(a, map->stream);
+        GMW_HIP(ctx, hipGetLastError());
+        if (copying) {
+            GMW_HIP(ctx, hipMemcpyAsync(records + (size_t)sec0 * n_zones, a.records, (size_t)ns * n_zones * sizeof(gm_wall_quantity),
+                                        hipMemcpyDeviceToHost, map->stream));
+            if (profile_rows)
+                GMW_HIP(ctx, hipMemcpyAsync(profile_rows + (size_t)sec0 * nsec, a.rows, (size_t)ns * nsec * sizeof(int32_t),
+                                            hipMemcpyDeviceToHost, map->stream));
+        }
+        if (NS - sec0 <= cs)   // the last chunk: the totals ride on its wait
+            GMW_HIP(ctx, hipMemcpyAsync(ctr, a.ctr, sizeof(ctr), hipMemcpyDeviceToHost, map->stream));
+        GMW_HIP(ctx, hipStreamSynchronize(map->stream));   // (the next chunk rewrites the staging; the tables have left the caller's buffers)
+    }
+    info->unmeasured = ctr[GM_WALL_QUANTITY_CLASS_UNMEASURED];
+    info->empty = ctr[GM_WALL_QUANTITY_CLASS_EMPTY];
+    info->unusable = ctr[GM_WALL_QUANTITY_CLASS_UNUSABLE];
+    info->under = ctr[GM_WALL_QUANTITY_CLASS_UNDER];
+    info->over = ctr[GM_WALL_QUANTITY_CLASS_OVER];
+    info->within = ctr[GM_WALL_QUANTITY_CLASS_WITHIN];
+    info->sections_under = (uint32_t)ctr[6];
+    info->sections_over = (uint32_t)ctr[7];
+    if (records && capacity < total) return gm_fail(ctx, GM_ERR_CAPACITY, "gm_wall_map_quantities: record buffer too small");
     return GM_OK;
 }
 

@@ -1,8 +1,10 @@
 // gm_wall_host.hip -- the part of the wall map's C ABI that needs no device (include/gm_hip.h states each rule): the
 // defaults, the parameter checks, the classification of one cell, the metrics, the direction table, the mesh's triangle
-// rule and its PLY file, the gauge of a polygon, the runs, the align's selection, the sections' basis, solve and metrics.
+// rule and its PLY file, the gauge of a polygon, the runs, the align's selection, the sections' basis, solve and metrics,
+// the quantities' column, metrics and runs.
 // No device call, no context, no map: it links against libm and the C++ library alone, and host/gm_wall_host_test.cpp,
-// host/gm_wall_sections_host_test.cpp and host/gm_wall_mesh_host_test.cpp run it under the host sanitizers.
+// host/gm_wall_sections_host_test.cpp, host/gm_wall_mesh_host_test.cpp and host/gm_wall_quantities_host_test.cpp run it
+// under the host sanitizers.
 #include <stdio.h>
 
 #include <vector>
@@ -127,6 +129,33 @@ bool section_prm_ok(const gm_wall_section_params &p, long long &Tr)
     if (!(p.max_gap_deg >= 0.0) || !(p.max_gap_deg <= 360.0) || !(p.reject > 0.0) || !(p.reject <= 8.0)) return false;
     Tr = (long long)rint(p.reject * 1048576.0);
     return Tr >= 1;
+}
+
+bool quantity_ok(const gm_wall_params *p, const gm_wall_quantity_params &q, const int32_t *lo_q, const int32_t *hi_q,
+                 uint32_t n_profiles, const uint8_t *section_profile, uint32_t n, const uint8_t *zone, uint32_t n_zones,
+                 long long &Rq)
+{
+    Rq = 0;
+    if (!p || !lo_q || !hi_q || p->struct_size != sizeof(gm_wall_params) || p->n_sectors < 1u || p->n_sectors > GM_WALL_MAX_SECTORS)
+        return false;
+    if (q.struct_size != sizeof(gm_wall_quantity_params) || q.section_stations < 1u || q.min_count < 1u) return false;
+    if (!(p->radius > 0.0) || !isfinite(p->radius)) return false;
+    const double rq = rint(p->radius * 1048576.0);
+    if (!(rq <= 4294967296.0)) return false;
+    if (n_profiles < 1u || n_profiles > GM_WALL_QUANTITY_MAX_PROFILES || n_zones < 1u || n_zones > GM_WALL_QUANTITY_MAX_ZONES) return false;
+    const size_t entries = (size_t)n_profiles * p->n_sectors;
+    for (size_t i = 0; i < entries; ++i)
+        if (lo_q[i] < -(int32_t)kWallSectionSat || hi_q[i] > (int32_t)kWallSectionSat || lo_q[i] > hi_q[i]) return false;
+    if (section_profile) {
+        const uint32_t NS = n ? (n - 1u) / q.section_stations + 1u : 0u;
+        for (uint32_t i = 0; i < NS; ++i)
+            if (section_profile[i] >= n_profiles) return false;
+    }
+    if (zone)
+        for (uint32_t k = 0; k < p->n_sectors; ++k)
+            if (zone[k] >= n_zones && zone[k] != GM_WALL_QUANTITY_UNMEASURED) return false;
+    Rq = (long long)rq;
+    return true;
 }
 
 void section_basis(uint32_t nsec, uint32_t H, int32_t *B)
@@ -829,6 +858,147 @@ gm_status gm_wall_section_metrics(const gm_wall_params *p, const gm_wall_section
     const double a1 = 1.57079632679489661923 * sq;
     out->area_m2 = a0 + a1;
     out->coverage = (double)s->accepted / (double)p->n_sectors;
+    return GM_OK;
+}
+
+void gm_wall_quantity_default_params(gm_wall_quantity_params *p)
+{
+    if (!defaults_begin(p)) return;
+    p->section_stations = 4;
+    p->min_count = 8;
+}
+
+gm_status gm_wall_quantity_check_params(const gm_wall_params *p, const gm_wall_quantity_params *q, const int32_t *lo_q,
+                                        const int32_t *hi_q, uint32_t n_profiles, const uint8_t *section_profile, uint32_t n,
+                                        const uint8_t *zone, uint32_t n_zones)
+{
+    long long Rq;
+    return quantity_ok(p, params_or(q, gm_wall_quantity_default_params), lo_q, hi_q, n_profiles, section_profile, n, zone, n_zones, Rq)
+               ? GM_OK
+               : GM_ERR_INVALID_ARG;
+}
+
+gm_status gm_wall_quantity_column(int64_t radius_q, uint64_t count, int64_t sum, int has_baseline, uint64_t base_count,
+                                  int64_t base_sum, uint32_t min_count, int32_t lo, int32_t hi, uint32_t zone_entry,
+                                  gm_wall_quantity_column_result *out)
+{
+    if (!out || radius_q < 1 || radius_q > (1ll << 32) || min_count < 1u || lo < -(int32_t)kWallSectionSat ||
+        hi > (int32_t)kWallSectionSat || lo > hi)
+        return GM_ERR_INVALID_ARG;
+    const WallQuantityColumn c = wall_quantity_column(radius_q, count, sum, has_baseline != 0, base_count, base_sum, min_count, lo, hi,
+                                                      zone_entry == GM_WALL_QUANTITY_UNMEASURED);
+    out->cls = c.cls;
+    out->v = c.usable ? (int32_t)c.v : kWallQuantityNoValue;
+    out->under_area = c.under;
+    out->over_area = c.over;
+    out->excess_area = c.excess;
+    out->over_line = c.line;
+    return GM_OK;
+}
+
+// ((area 2^-20) pi) / n_sectors, then times the length: one operation per statement
+struct QuantityVolumes { double area[4], volume[4]; };   // under, over, excess, paid
+static QuantityVolumes quantity_volumes(const gm_wall_params &p, const gm_wall_quantity &r, double length)
+{
+    const int64_t units[4] = {r.under_area, r.over_area, r.excess_area, r.over_area - r.excess_area};
+    QuantityVolumes q;
+    for (int i = 0; i < 4; ++i) {
+        const double scaled = (double)units[i] * 0x1p-20;
+        const double ring = scaled * 3.14159265358979323846;
+        q.area[i] = ring / (double)p.n_sectors;
+        q.volume[i] = q.area[i] * length;
+    }
+    return q;
+}
+
+static double quantity_angle(uint32_t sector, uint32_t nsec)   // gm_wall_clearance_run.angle_deg
+{
+    const double num = 360.0 * ((double)sector * 2.0 + 1.0);
+    return num / ((double)nsec * 2.0);
+}
+
+gm_status gm_wall_quantity_metrics(const gm_wall_params *p, const gm_wall_quantity *r, struct gm_wall_quantity_metrics *out)
+{
+    if (!p || !r || !out || check_params(p) != GM_OK || r->stations < 1u) return GM_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    // (one operation per statement: the same roundings as the twin's, whatever the compiler may contract)
+    const double from = (double)r->station_from * p->station_length;
+    const double end = (double)r->station_from + (double)r->stations;
+    const double to = end * p->station_length;
+    out->chainage_from = p->t_min + from;
+    out->chainage_to = p->t_min + to;
+    out->length = (double)r->stations * p->station_length;
+    const QuantityVolumes q = quantity_volumes(*p, *r, out->length);
+    out->under_area_m2 = q.area[0]; out->over_area_m2 = q.area[1]; out->excess_area_m2 = q.area[2]; out->paid_area_m2 = q.area[3];
+    out->under_volume_m3 = q.volume[0]; out->over_volume_m3 = q.volume[1]; out->excess_volume_m3 = q.volume[2];
+    out->paid_volume_m3 = q.volume[3];
+    out->peak_under_m = (double)r->peak_under * 0x1p-20;
+    out->peak_over_m = (double)r->peak_over * 0x1p-20;
+    if (r->peak_under_sector != UINT32_MAX) out->peak_under_angle_deg = quantity_angle(r->peak_under_sector, p->n_sectors);
+    if (r->peak_over_sector != UINT32_MAX) out->peak_over_angle_deg = quantity_angle(r->peak_over_sector, p->n_sectors);
+    const uint64_t usable = (uint64_t)r->under + r->within + r->over, measured = usable + r->unsurveyed;
+    if (measured) out->coverage = (double)usable / (double)measured;
+    return GM_OK;
+}
+
+gm_status gm_wall_quantity_runs(const gm_wall_params *p, const gm_wall_quantity *records, uint32_t n_sections, uint32_t n_zones,
+                                uint32_t run_sections, uint32_t flags, gm_wall_quantity_run *runs, uint32_t capacity,
+                                uint32_t *n_out)
+{
+    if (n_out) *n_out = 0;
+    if (!p || check_params(p) != GM_OK || (!records && n_sections) || n_zones < 1u || n_zones > GM_WALL_QUANTITY_MAX_ZONES ||
+        run_sections < 1u || (flags & ~(uint32_t)GM_WALL_QUANTITY_RUNS_ALL_ZONES) || (!runs && capacity))
+        return GM_ERR_INVALID_ARG;
+    const bool all = (flags & GM_WALL_QUANTITY_RUNS_ALL_ZONES) != 0u;
+    const uint32_t NR = n_sections ? (n_sections - 1u) / run_sections + 1u : 0u, per = all ? 1u : n_zones;
+    const uint64_t total = (uint64_t)NR * per;
+    if (total > UINT32_MAX) return GM_ERR_INVALID_ARG;
+    if (n_out) *n_out = (uint32_t)total;
+    if (!runs) return GM_OK;
+    if (capacity < total) return GM_ERR_CAPACITY;
+    for (uint32_t R = 0; R < NR; ++R) {
+        const uint32_t s0 = R * run_sections, s1 = n_sections - s0 < run_sections ? n_sections : s0 + run_sections;
+        for (uint32_t o = 0; o < per; ++o) {
+            gm_wall_quantity_run run;
+            memset(&run, 0, sizeof(run));
+            const gm_wall_quantity &head = records[(size_t)s0 * n_zones];
+            run.station_from = head.station_from;
+            run.zone = all ? UINT32_MAX : o;
+            run.sections = s1 - s0;
+            run.peak_under_station = run.peak_under_sector = run.peak_over_station = run.peak_over_sector = UINT32_MAX;
+            for (uint32_t s = s0; s < s1; ++s) {
+                const gm_wall_quantity &first = records[(size_t)s * n_zones];
+                run.stations += first.stations;
+                const double length = (double)first.stations * p->station_length;
+                for (uint32_t z = all ? 0u : o; z < (all ? n_zones : o + 1u); ++z) {
+                    const gm_wall_quantity &r = records[(size_t)s * n_zones + z];
+                    run.under += r.under; run.within += r.within; run.over += r.over; run.unsurveyed += r.unsurveyed;
+                    run.points += r.points;
+                    const QuantityVolumes q = quantity_volumes(*p, r, length);
+                    run.under_volume_m3 = run.under_volume_m3 + q.volume[0];
+                    run.over_volume_m3 = run.over_volume_m3 + q.volume[1];
+                    run.excess_volume_m3 = run.excess_volume_m3 + q.volume[2];
+                    run.paid_volume_m3 = run.paid_volume_m3 + q.volume[3];
+                    if (r.peak_under_sector != UINT32_MAX && r.peak_under > run.peak_under) {
+                        run.peak_under = r.peak_under;
+                        run.peak_under_station = r.station_from;
+                        run.peak_under_sector = r.peak_under_sector;
+                    }
+                    if (r.peak_over_sector != UINT32_MAX && r.peak_over > run.peak_over) {
+                        run.peak_over = r.peak_over;
+                        run.peak_over_station = r.station_from;
+                        run.peak_over_sector = r.peak_over_sector;
+                    }
+                }
+            }
+            const double from = (double)run.station_from * p->station_length;
+            const double end = (double)run.station_from + (double)run.stations;
+            const double to = end * p->station_length;
+            run.chainage_from = p->t_min + from;
+            run.chainage_to = p->t_min + to;
+            runs[(size_t)R * per + o] = run;
+        }
+    }
     return GM_OK;
 }
 

@@ -54,6 +54,10 @@ bool section_prm_ok(const gm_wall_section_params &p, long long &Tr);
 void section_basis(uint32_t nsec, uint32_t H, int32_t *B);
 // the solve of include/gm_hip.h on one record of sums: the status, and c_q[9] (0 unless the status is GM_SECTION_OK)
 uint32_t section_solve(const gm_wall_section_sums &s, uint32_t H, uint32_t min_columns, int64_t cq[9]);
+// gm_wall_quantity_check_params' rule; R_q of an accepted call
+bool quantity_ok(const gm_wall_params *p, const gm_wall_quantity_params &q, const int32_t *lo_q, const int32_t *hi_q,
+                 uint32_t n_profiles, const uint8_t *section_profile, uint32_t n, const uint8_t *zone, uint32_t n_zones,
+                 long long &Rq);
 bool check_prm_ok(const gm_wall_check_params &c, long long &T);
 bool locate_prm_ok(const gm_wall_locate_params &p);
 bool align_prm_ok(const gm_wall_align_params &p, uint32_t nsec);
@@ -94,6 +98,7 @@ P params_or(const P *prm, void (*defaults)(P *))
 
 constexpr uint64_t kStageCells = 1u << 20;   // cells per chunk of a window call (24 MiB of raw records)
 constexpr uint32_t kSectionChunk = 1u << 16; // sections per chunk of gm_wall_map_sections (37 MiB of scratch)
+constexpr uint64_t kStageBytes = kStageCells * 24u;   // the staging of a chunk of gm_wall_map_quantities: what the other window calls use
 
 // The records of a chained scan (gm_compact.hpp) that is not a frame's -- a slot's own belong to the frame that may be in
 // flight on it: the record array with the ticket word behind it, and the epoch of the launches on it so far.  The rule is
@@ -259,6 +264,12 @@ struct gm_wall_map {
     std::vector<int32_t> sc_basis_host;            // the tables of the call in progress
     std::vector<gm::WallSectionModel> sc_model_host;
     std::vector<gm::WallSectionOut> sc_out_host;
+    // gm_wall_map_quantities: the chunk (GM_WALL_QUANTITY_CHUNK: tests, measurements; 0: what kStageBytes holds) and the scratch
+    uint32_t quantity_chunk = 0;
+    gm::DevArray<int32_t> qt_lines;    // the uploaded tables lo [n_profiles][n_sectors] | hi [n_profiles][n_sectors]
+    gm::DevArray<uint8_t> qt_index;    // section_profile [NS] | zone [n_sectors]
+    gm::DevArray<uint8_t> qt_stage;    // a chunk's records [cs][n_zones] | its profile rows [cs][n_sectors]
+    gm::DevArray<unsigned long long> qt_ctr;       // [kWallQuantityCounters]
     // gm_wall_map_check_*, _locate_*, _align_*: per slot of ctx
     std::vector<gm::wall::WallCheckSlot> checks;
     std::vector<gm::wall::WallLocateSlot> locates;

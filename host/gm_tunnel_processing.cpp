@@ -487,6 +487,60 @@ struct gm_wall_section_metrics Processor::wallSectionMetrics(const gm_wall_param
     return out;
 }
 
+gm_wall_quantities_info Processor::wallMapQuantities(unsigned station0, unsigned n, const std::vector<int32_t> &lo_q,
+                                                     const std::vector<int32_t> &hi_q, const gm_wall_quantity_params &prm,
+                                                     std::vector<gm_wall_quantity> &records, gm_wall_map *baseline,
+                                                     const std::vector<uint8_t> &section_profile, const std::vector<uint8_t> &zone,
+                                                     unsigned n_zones, std::vector<int32_t> *profile_rows)
+{
+    if (!wall_) throw Error(GM_ERR_NOT_READY, "wallMapQuantities: createWallMap first");
+    gm_wall_info wi;
+    check(gm_wall_map_info(wall_, &wi), "wallMapQuantities");
+    if (lo_q.empty() || lo_q.size() % wi.n_sectors || hi_q.size() != lo_q.size())
+        throw Error(GM_ERR_INVALID_ARG, "wallMapQuantities: lo_q and hi_q are not the same whole tables of n_sectors entries");
+    if (!zone.empty() && zone.size() != wi.n_sectors) throw Error(GM_ERR_INVALID_ARG, "wallMapQuantities: zone needs one entry per sector");
+    const unsigned S = prm.section_stations ? prm.section_stations : 1, NS = n ? (n - 1) / S + 1 : 0;
+    if (!section_profile.empty() && section_profile.size() != NS)
+        throw Error(GM_ERR_INVALID_ARG, "wallMapQuantities: section_profile needs one entry per section");
+    const unsigned n_profiles = (unsigned)(lo_q.size() / wi.n_sectors);
+    const uint8_t *sp = section_profile.empty() ? 0 : &section_profile[0], *zn = zone.empty() ? 0 : &zone[0];
+    gm_wall_quantities_info info;
+    uint32_t count = 0;
+    check(gm_wall_map_quantities(wall_, baseline, station0, n, &lo_q[0], &hi_q[0], n_profiles, sp, zn, n_zones, &prm, &info, 0, 0,
+                                 &count, 0), "wallMapQuantities");
+    records.assign(count, gm_wall_quantity());
+    if (profile_rows) profile_rows->assign((size_t)info.sections * wi.n_sectors, 0);
+    if (count)
+        check(gm_wall_map_quantities(wall_, baseline, station0, n, &lo_q[0], &hi_q[0], n_profiles, sp, zn, n_zones, &prm, &info,
+                                     &records[0], count, &count, profile_rows ? &(*profile_rows)[0] : 0), "wallMapQuantities");
+    return info;
+}
+
+struct gm_wall_quantity_metrics Processor::wallQuantityMetrics(const gm_wall_params &params, const gm_wall_quantity &record)
+{
+    struct gm_wall_quantity_metrics out;
+    gm_status s = gm_wall_quantity_metrics(&params, &record, &out);
+    if (s != GM_OK) throw Error(s, "wallQuantityMetrics: the record or the parameters were refused");
+    return out;
+}
+
+std::vector<gm_wall_quantity_run> Processor::wallQuantityRuns(const gm_wall_params &params, const std::vector<gm_wall_quantity> &records,
+                                                              unsigned n_zones, unsigned run_sections, bool all_zones)
+{
+    if (!n_zones || records.size() % n_zones) throw Error(GM_ERR_INVALID_ARG, "wallQuantityRuns: records holds n_zones records per section");
+    const unsigned ns = (unsigned)(records.size() / n_zones), flags = all_zones ? GM_WALL_QUANTITY_RUNS_ALL_ZONES : 0u;
+    const gm_wall_quantity *rp = records.empty() ? 0 : &records[0];
+    uint32_t count = 0;
+    gm_status s = gm_wall_quantity_runs(&params, rp, ns, n_zones, run_sections, flags, 0, 0, &count);
+    if (s != GM_OK) throw Error(s, "wallQuantityRuns: the records or the parameters were refused");
+    std::vector<gm_wall_quantity_run> runs(count);
+    if (count) {
+        s = gm_wall_quantity_runs(&params, rp, ns, n_zones, run_sections, flags, &runs[0], count, &count);
+        if (s != GM_OK) throw Error(s, "wallQuantityRuns failed");
+    }
+    return runs;
+}
+
 std::vector<int32_t> Processor::wallGaugeFromPolygon(const gm_wall_params &params, const std::vector<double> &uv, const double offset[2])
 {
     if (uv.empty() || uv.size() % 2) throw Error(GM_ERR_INVALID_ARG, "wallGaugeFromPolygon: uv holds (u, v) pairs");

@@ -176,6 +176,22 @@ public:
     // the fp64 metrics of one record of wallMapSections under the map's parameters (gm_wall_section_metrics, host only)
     static struct gm_wall_section_metrics wallSectionMetrics(const gm_wall_params &params, const gm_wall_section &section,
                                                              unsigned harmonics);
+    // under- and overbreak per section and zone of stations [station0, station0 + n) (gm_wall_map_quantities) against the
+    // two lines lo_q / hi_q (whole tables of n_sectors offsets, units of 2^-20 m) about the design radius or, with baseline
+    // (another map on the same grid, of this context), about that epoch's wall.  section_profile (empty: table 0) picks each
+    // section's table, zone (empty: zone 0; 0xFF: not measured) each sector's zone.  One record per section and zone,
+    // ordered [sections][n_zones]; profile_rows, when given, receives [sections][n_sectors]; the map is not changed.
+    gm_wall_quantities_info wallMapQuantities(unsigned station0, unsigned n, const std::vector<int32_t> &lo_q,
+                                              const std::vector<int32_t> &hi_q, const gm_wall_quantity_params &prm,
+                                              std::vector<gm_wall_quantity> &records, gm_wall_map *baseline = 0,
+                                              const std::vector<uint8_t> &section_profile = std::vector<uint8_t>(),
+                                              const std::vector<uint8_t> &zone = std::vector<uint8_t>(), unsigned n_zones = 1,
+                                              std::vector<int32_t> *profile_rows = 0);
+    // the fp64 metrics of one record of wallMapQuantities under the map's parameters (gm_wall_quantity_metrics, host only)
+    static struct gm_wall_quantity_metrics wallQuantityMetrics(const gm_wall_params &params, const gm_wall_quantity &record);
+    // the records folded into pay intervals of run_sections sections (gm_wall_quantity_runs, host only)
+    static std::vector<gm_wall_quantity_run> wallQuantityRuns(const gm_wall_params &params, const std::vector<gm_wall_quantity> &records,
+                                                              unsigned n_zones, unsigned run_sections, bool all_zones = false);
     // the changed points of the newest frame (as addToWallMap takes it) against the map under pose (gm_wall_map_check_frame +
     // gm_wall_map_get_check), ascending by index; the map is not changed.  info, when given, receives the call's counts.
     // Check, then addToWallMap: against what was there, then contribute.

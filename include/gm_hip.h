@@ -1074,6 +1074,180 @@ gm_status gm_wall_map_sections(gm_wall_map *map, gm_wall_map *baseline, uint32_t
                                const gm_wall_section_params *prm, gm_wall_sections_info *info, gm_wall_section *sections,
                                uint32_t capacity, uint32_t *n_out, gm_wall_section_sums *sums);
 
+/* ---- over- and underbreak per section and zone (gm_wall_map_quantities) -----------------------------------------------
+ * What a survey is paid by: per advance the underbreak, the overbreak and the unpaid excess against the contract's two
+ * lines -- the minimum excavation line, inside which rock must still come out, and the pay line, beyond which overbreak
+ * is not paid -- as areas by crown, side walls and invert, and how much of the ring was surveyed at all; with a baseline
+ * map the same between two epochs: how much lining went on and where it is thinner than required.  Everything on the
+ * device is integer, so the records are a function of the raw cells, the tables and the parameters alone.
+ *   sections    exactly those of gm_wall_map_sections: S = section_stations, NS = ceil(n / S), section i is window
+ *               stations [i S, min((i + 1) S, n)).
+ *   column      column (i, k) merges sector k over the section's stations as there: the count a u64 sum, the sum an
+ *               int64 sum (empty cells add nothing), q = sum / (int64) count by C division, saturated at +-2^24 units
+ *               of 2^-20 m.  USABLE iff count >= min_count and, with a baseline (the refusals of gm_wall_map_regions),
+ *               the baseline's count too.
+ *   value       R_q = (int64) rint(radius 2^20), fp64, once on the host; a map with R_q > 2^32 is refused.  The base
+ *               radius is b0 = R_q without a baseline and b0 = R_q + q(baseline) with one; the wall radius is
+ *               x = R_q + q(map); the compared value is v = x - b0.
+ *   lines       int32 lo_q[n_profiles][n_sectors] and hi_q[n_profiles][n_sectors], offsets from the base radius in
+ *               units of 2^-20 m, |entry| <= 2^24 and lo <= hi, 1 <= n_profiles <= GM_WALL_QUANTITY_MAX_PROFILES.
+ *               L = b0 + lo and H = b0 + hi.  section_profile (may be NULL: table 0) holds one uint8 per SECTION, the
+ *               table of that section, as gm_wall_map_clearance's station_gauge; an entry >= n_profiles is refused.
+ *               Without a baseline the lines are the contract's two lines about the design axis: such a table is
+ *               gm_wall_gauge_from_polygon's output minus R_q.  That helper rounds OUTWARD (the farthest point of the
+ *               polygon inside the sector's wedge, then ceil): right for a pay line, a few units generous for a minimum
+ *               excavation line.  With a baseline the lines are offsets from the earlier wall: lo = hi = 0 splits
+ *               "moved in" from "moved out", lo = hi = -t finds lining thinner than t.
+ *   zones       uint8 zone[n_sectors] (may be NULL: zone 0 everywhere), 1 <= n_zones <= GM_WALL_QUANTITY_MAX_ZONES;
+ *               GM_WALL_QUANTITY_UNMEASURED (0xFF): the sector is not measured (the invert under the muck); any other
+ *               entry >= n_zones is refused.
+ *   classes     every column is in exactly one, decided in this order: UNMEASURED (zone 0xFF), EMPTY (count 0, and
+ *               with a baseline count 0 there too), UNUSABLE, UNDER (v < lo), OVER (v > hi), WITHIN.
+ *   area term   for b >= a >= 0, ann(a, b) = ((b - a) (b + a)) >> 20 in int64: twice the area of the sector between
+ *               the two radii divided by the sector angle, units of 2^-20 m^2; the truncation, at most one unit per
+ *               column, is part of the rule.  L, H and x are clamped at 0 from below before they enter an area term
+ *               (the peaks and the classes use them as they are).  b - a < 2^26 and b + a < 2^34, so no product
+ *               exceeds 2^60 and a record's sums stay below 2^52.
+ *   record      per (section, zone), over the zone's columns: the counts under, within, over and unsurveyed = empty +
+ *               unusable; points, the map's merged count over the usable columns; under_area = sum ann(x, L) over
+ *               UNDER; over_area = sum ann(L, x) over the usable columns with x > L, WITHIN or OVER; excess_area = sum
+ *               ann(H, x) over OVER -- the paid overbreak is over_area - excess_area; peak_under = max (L - x) over
+ *               UNDER and peak_over = max (x - L) over x > L, each with its sector, the smallest among equals (0 and
+ *               UINT32_MAX without such a column).  A zone without a sector gives zeros (and both sectors UINT32_MAX).
+ *               Records are ordered [NS][n_zones].
+ *   profile     optional, int32 [NS][n_sectors]: v of the column, INT32_MIN when it is not usable.  An unmeasured
+ *               sector that is usable still gets its value: the drawing wants the invert too.
+ *   totals      the six classes (they sum to NS n_sectors) and the sections with at least one UNDER and with at least
+ *               one OVER column.  No area totals: a window's could exceed 64 bits, a record's cannot.
+ * On the device: one wave per section over chunks of whole sections; it reads count and sum only.  The default chunk
+ * keeps the staging (88 B per record, 4 B per profile entry) within 24 MiB; environment
+ * GM_WALL_QUANTITY_CHUNK=<sections>, 0 or more than the default meaning the default, read at gm_wall_map_create: tests
+ * and measurements.  No floating point and no floating-point atomics on the device: the result does not depend on the
+ * chunk, the grid, the block shape or the order blocks run in. */
+#define GM_WALL_QUANTITY_MAX_PROFILES 256u
+#define GM_WALL_QUANTITY_MAX_ZONES    8u
+#define GM_WALL_QUANTITY_UNMEASURED   0xFFu
+#define GM_WALL_QUANTITY_CLASS_UNMEASURED 0u
+#define GM_WALL_QUANTITY_CLASS_EMPTY      1u
+#define GM_WALL_QUANTITY_CLASS_UNUSABLE   2u
+#define GM_WALL_QUANTITY_CLASS_UNDER      3u
+#define GM_WALL_QUANTITY_CLASS_OVER       4u
+#define GM_WALL_QUANTITY_CLASS_WITHIN     5u
+#define GM_WALL_QUANTITY_RUNS_ALL_ZONES   1u   /* gm_wall_quantity_runs: one run per interval over all zones */
+
+typedef struct gm_wall_quantity_params {   /* 16 bytes */
+    uint32_t struct_size;       /* = sizeof(gm_wall_quantity_params) */
+    uint32_t section_stations;  /* S >= 1 (default 4) */
+    uint32_t min_count;         /* >= 1 (default 8): points a column needs to be usable */
+    uint32_t reserved;          /* 0 */
+} gm_wall_quantity_params;
+
+typedef struct gm_wall_quantity {   /* 88 bytes: one (section, zone) */
+    uint32_t station_from;      /* map-wide first station */
+    uint32_t stations;          /* 1 .. S */
+    uint32_t zone;
+    uint32_t profile;           /* the table used */
+    uint32_t under, within, over;
+    uint32_t unsurveyed;        /* measured columns that are empty or unusable */
+    uint64_t points;            /* merged count of the usable columns, of the map */
+    int64_t  under_area, over_area, excess_area;   /* sums of ann, units of 2^-20 m^2 */
+    int64_t  peak_under, peak_over;                /* units of 2^-20 m; 0 without such a column */
+    uint32_t peak_under_sector, peak_over_sector;  /* the smallest among equals; UINT32_MAX without such a column */
+} gm_wall_quantity;
+
+typedef struct gm_wall_quantities_info {   /* 96 bytes */
+    uint32_t struct_size;       /* = sizeof(gm_wall_quantities_info), filled by the library */
+    uint32_t station0, n_stations, n_sectors;   /* the window and the map's sectors */
+    uint32_t section_stations, sections;        /* S, NS */
+    uint32_t n_zones, n_profiles;
+    int64_t  radius_q;          /* R_q */
+    uint64_t unmeasured, empty, unusable, under, over, within;   /* columns per class: they sum to NS n_sectors */
+    uint32_t sections_under;    /* sections with at least one UNDER column */
+    uint32_t sections_over;     /* sections with at least one OVER column */
+} gm_wall_quantities_info;
+
+typedef struct gm_wall_quantity_column_result {   /* 40 bytes: one column restated on the host */
+    uint32_t cls;               /* GM_WALL_QUANTITY_CLASS_* */
+    int32_t  v;                 /* x - b0; INT32_MIN when the column is not usable */
+    int64_t  under_area, over_area, excess_area;   /* the column's three area terms (0 where its class has none) */
+    int64_t  over_line;         /* x - L of a usable column (negative: the depth of the underbreak), else 0 */
+} gm_wall_quantity_column_result;
+
+struct gm_wall_quantity_metrics {   /* 136 bytes; fp64 derived on the host, one rounding per operation */
+    double chainage_from;       /* t_min + station_from * station_length */
+    double chainage_to;         /* t_min + (station_from + stations) * station_length */
+    double length;              /* stations * station_length */
+    double under_area_m2, over_area_m2, excess_area_m2;   /* ((area 2^-20) pi) / n_sectors */
+    double paid_area_m2;        /* the same of over_area - excess_area */
+    double under_volume_m3, over_volume_m3, excess_volume_m3, paid_volume_m3;   /* area * length */
+    double peak_under_m, peak_over_m;                     /* peak 2^-20 */
+    double peak_under_angle_deg, peak_over_angle_deg;     /* (360 (2 sector + 1)) / (2 n_sectors); 0 without a peak */
+    double coverage;            /* usable / measured, usable = under + within + over, measured = usable + unsurveyed; 0 of 0 */
+    double reserved;            /* 0 */
+};
+
+typedef struct gm_wall_quantity_run {   /* 136 bytes: a pay interval; fp64 derived on the host */
+    uint32_t station_from;      /* map-wide first station of the interval */
+    uint32_t stations;
+    uint32_t zone;              /* UINT32_MAX: over all zones */
+    uint32_t sections;          /* 1 .. run_sections */
+    double   chainage_from, chainage_to;
+    uint64_t under, within, over, unsurveyed, points;   /* integer sums over the interval's records */
+    double   under_volume_m3, over_volume_m3, excess_volume_m3, paid_volume_m3;   /* summed in section order, then zone */
+    int64_t  peak_under, peak_over;                     /* the largest of the interval, the first among equals */
+    uint32_t peak_under_station, peak_under_sector;     /* station_from of that section; UINT32_MAX without a peak */
+    uint32_t peak_over_station, peak_over_sector;
+} gm_wall_quantity_run;
+
+/* Host only: the defaults of the table above.  A NULL is ignored. */
+void gm_wall_quantity_default_params(gm_wall_quantity_params *p);
+/* Host only, no device, no map: everything gm_wall_map_quantities refuses but the window, the baseline and the output
+ * buffers, for a map with the parameters p (n_sectors and radius decide) and a window of n stations.  q NULL: the
+ * defaults; section_profile (ceil(n / S) entries) and zone may be NULL.  GM_ERR_INVALID_ARG: p, lo_q or hi_q NULL, a
+ * struct_size mismatch, n_sectors outside 1 .. GM_WALL_MAX_SECTORS, rint(radius 2^20) > 2^32 or radius not positive and
+ * finite, section_stations 0, min_count 0, n_profiles outside 1 .. 256, an entry beyond +-2^24, lo > hi, a
+ * section_profile entry >= n_profiles, n_zones outside 1 .. 8, a zone entry in n_zones .. 0xFE. */
+gm_status gm_wall_quantity_check_params(const gm_wall_params *p, const gm_wall_quantity_params *q, const int32_t *lo_q,
+                                        const int32_t *hi_q, uint32_t n_profiles, const uint8_t *section_profile, uint32_t n,
+                                        const uint8_t *zone, uint32_t n_zones);
+/* Host only: one column restated -- what gm_wall_check_classify is to the check.  (count, sum) is the column merged
+ * over the map, (base_count, base_sum) over the baseline when has_baseline is not 0; zone_entry is the sector's zone
+ * table entry (0xFF: unmeasured).  GM_ERR_INVALID_ARG: out NULL, radius_q outside 1 .. 2^32, min_count 0, an entry
+ * beyond +-2^24, lo > hi. */
+gm_status gm_wall_quantity_column(int64_t radius_q, uint64_t count, int64_t sum, int has_baseline, uint64_t base_count,
+                                  int64_t base_sum, uint32_t min_count, int32_t lo, int32_t hi, uint32_t zone_entry,
+                                  gm_wall_quantity_column_result *out);
+/* Host only: the metrics of one record under the map's parameters.  GM_ERR_INVALID_ARG: a NULL, p->struct_size mismatch
+ * or parameters gm_wall_map_create refuses, a record of 0 stations. */
+gm_status gm_wall_quantity_metrics(const gm_wall_params *p, const gm_wall_quantity *r, struct gm_wall_quantity_metrics *out);
+/* Host only: the records [n_sections][n_zones] of a call folded into pay intervals of run_sections consecutive
+ * sections, the last one shorter: NR = ceil(n_sections / run_sections) intervals.  Without flags one run per interval
+ * and zone, ordered [NR][n_zones]; with GM_WALL_QUANTITY_RUNS_ALL_ZONES one per interval over all zones.  Counts are
+ * integer sums; each volume is the record's (gm_wall_quantity_metrics') summed in fp64 in section order, zones in
+ * order within a section; the peaks are the largest of the interval, the first among equals in that order.  *n_out
+ * (may be NULL) = the number of runs; runs NULL with capacity 0 is a count query, a capacity below *n_out returns
+ * GM_ERR_CAPACITY and writes nothing.  GM_ERR_INVALID_ARG: p as above, records NULL with sections, n_zones outside
+ * 1 .. 8, run_sections 0, an unknown flag, runs NULL with a capacity. */
+gm_status gm_wall_quantity_runs(const gm_wall_params *p, const gm_wall_quantity *records, uint32_t n_sections, uint32_t n_zones,
+                                uint32_t run_sections, uint32_t flags, gm_wall_quantity_run *runs, uint32_t capacity,
+                                uint32_t *n_out);
+/* The quantities of stations [station0, station0 + n).  Synchronises the map and the baseline (as gm_wall_map_sync),
+ * runs on the map's stream and blocks.  baseline NULL: against the design; else another map of the same context on
+ * the same grid (refused as gm_wall_map_regions refuses it).  prm NULL: the defaults; section_profile NULL: table 0;
+ * zone NULL: zone 0 everywhere.  info is required; it and *n_out (may be NULL; NS n_zones records) are filled whenever
+ * the call got past its refusals, also on GM_ERR_CAPACITY.  records NULL with capacity 0 is a count query (GM_OK; info
+ * is complete); a capacity below NS n_zones with a buffer returns GM_ERR_CAPACITY and writes neither array.
+ * profile_rows (may be NULL) receives NS n_sectors entries.  n = 0 gives nothing.  Neither map is changed.  Scratch
+ * (the uploaded tables and the staging of a chunk) is allocated on first use, kept grow-only in the map and freed with
+ * it; a map that never calls this allocates and launches nothing new.  GM_ERR_INVALID_ARG: NULL map / info, a window
+ * outside the map, whatever gm_wall_quantity_check_params refuses, a refused baseline, records NULL with a capacity or
+ * with profile_rows. */
+gm_status gm_wall_map_quantities(gm_wall_map *map, gm_wall_map *baseline, uint32_t station0, uint32_t n, const int32_t *lo_q,
+                                 const int32_t *hi_q, uint32_t n_profiles, const uint8_t *section_profile,
+                                 const uint8_t *zone, uint32_t n_zones, const gm_wall_quantity_params *prm,
+                                 gm_wall_quantities_info *info, gm_wall_quantity *records, uint32_t capacity, uint32_t *n_out,
+                                 int32_t *profile_rows);
+
 /* ---- a frame's changed points against the wall map (gm_wall_map_check_*) ----------------------------------------------
  * Which points of the frame in front of the sensor are NOT where the map says the wall is: rockfall, a fallen lining
  * segment, a vehicle in the profile, new shotcrete.  One device pass over the frame's valid cloud under a pose; only the
