@@ -146,6 +146,20 @@ class SurfaceInfo(C.Structure):
                 ("R", C.c_float), ("t_min", C.c_float), ("station_length", C.c_float), ("sector_angle", C.c_float)]
 
 
+class WallArc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("curvature", C.c_double * 3),
+                ("point_chainage", C.c_double)]
+
+
+class WallArcAddInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("status", C.c_uint32), ("anchor_station", C.c_int64),
+                ("sensor_chainage", C.c_double), ("anchor_chainage", C.c_double),
+                ("o", C.c_float * 3), ("a", C.c_float * 3), ("n", C.c_float * 3), ("b", C.c_float * 3),
+                ("kappa", C.c_float), ("un", C.c_float), ("ub", C.c_float), ("vn", C.c_float), ("vb", C.c_float),
+                ("R", C.c_float), ("station_length", C.c_float), ("sector_angle", C.c_float), ("gate", C.c_float),
+                ("reserved", C.c_uint32)]
+
+
 class WallParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_stations", C.c_uint32), ("n_sectors", C.c_uint32), ("reserved", C.c_uint32),
                 ("station_length", C.c_double), ("t_min", C.c_double), ("gate", C.c_double),
@@ -490,6 +504,7 @@ def load():
     sprmp, scellp, sinfop = C.POINTER(SurfaceParams), C.POINTER(SurfaceCell), C.POINTER(SurfaceInfo)
     wprmp, wrawp, waddp, winfop = C.POINTER(WallParams), C.POINTER(WallRawCell), C.POINTER(WallAddInfo), C.POINTER(WallInfo)
     u64, u64p = C.c_uint64, C.POINTER(C.c_uint64)
+    warcp, warcaddp = C.POINTER(WallArc), C.POINTER(WallArcAddInfo)
     wregp, wrprmp, wrinfop, wrmetp = (C.POINTER(WallRegion), C.POINTER(WallRegionParams), C.POINTER(WallRegionsInfo),
                                       C.POINTER(WallRegionMetrics))
     wcprmp, wcptp, wcinfop = C.POINTER(WallCloudParams), C.POINTER(WallCloudPoint), C.POINTER(WallCloudInfo)
@@ -557,6 +572,13 @@ def load():
         "gm_wall_default_params": (None, [wprmp]),
         "gm_wall_map_create": (C.c_int, [vp, wprmp, C.POINTER(vp)]),
         "gm_wall_map_destroy": (None, [vp]),
+        "gm_wall_map_create_arc": (C.c_int, [vp, wprmp, warcp, C.POINTER(vp)]),
+        "gm_wall_map_get_arc": (C.c_int, [vp, warcp]),
+        "gm_wall_arc_check_params": (C.c_int, [wprmp, warcp]),
+        "gm_wall_arc_add_frame": (C.c_int, [wprmp, warcp, dp, warcaddp]),
+        "gm_wall_arc_frame": (C.c_int, [wprmp, warcp, C.c_double, dp, dp, dp, dp]),
+        "gm_wall_arc_project": (C.c_int, [wprmp, warcp, dp, dp, dp, dp]),
+        "gm_wall_arc_point": (C.c_int, [wprmp, warcp, C.c_double, C.c_double, C.c_double, dp]),
         "gm_wall_map_add_frame": (C.c_int, [vp, vp, u32, dp, waddp]),
         "gm_wall_map_add_points": (C.c_int, [vp, fp, u32, u8p, dp, waddp, fp, i32p]),
         "gm_wall_map_sync": (C.c_int, [vp]),

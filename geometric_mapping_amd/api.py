@@ -506,10 +506,11 @@ class GeometricMapping:
                                            nc, _f32(res), cell.ctypes.data_as(C.POINTER(C.c_int32))))
         return (*self._surface(info, cells), res[:len(xyz)].copy(), cell[:len(xyz)].copy())
 
-    def wall_map(self, **params):
+    def wall_map(self, arc=None, **params):
         """A persistent wall map owned by this context (gm_wall_map_create): WallMap.  Keywords: gm_wall_params fields
-        (n_stations, n_sectors, station_length, t_min, gate, point, direction, radius, up, forward)."""
-        return WallMap(self, **params)
+        (n_stations, n_sectors, station_length, t_min, gate, point, direction, radius, up, forward).
+        arc=dict(curvature=(x, y, z), point_chainage=s0): a map on a circular-arc design axis (gm_wall_map_create_arc)."""
+        return WallMap(self, arc=arc, **params)
 
 
 RAW_CELL = np.dtype([("sum", "<i8"), ("count", "<u4"), ("min_key", "<u4"), ("max_key", "<u4"), ("reserved", "<u4")])
@@ -909,6 +910,77 @@ def wall_cloud_directions(prm, **params):
     return out
 
 
+def wall_arc(curvature, point_chainage=0.0):
+    """gm_wall_arc from its two fields."""
+    a = _lib.WallArc()
+    a.struct_size = C.sizeof(_lib.WallArc)
+    a.curvature[:] = [float(x) for x in curvature]
+    a.point_chainage = float(point_chainage)
+    return a
+
+
+def _arc_call(name, st):
+    if st != _lib.GM_OK:
+        raise _lib.GmError(st, f"{name} refused the arguments")
+
+
+def _d3():
+    return np.empty(3, dtype=np.float64)
+
+
+def _dptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def wall_arc_add_frame(prm, arc, pose):
+    """gm_wall_arc_add_frame (host only): the per-add frame of an arc map with the gm_wall_params `prm` and the gm_wall_arc
+    `arc` under `pose`: dict of anchor_station, sensor_chainage, anchor_chainage, o, a, n, b (float32 [3]) and the fp32
+    constants kappa, un, ub, vn, vb, R, station_length, sector_angle, gate."""
+    m = WallMap._pose(pose)
+    i = _lib.WallArcAddInfo()
+    _arc_call("gm_wall_arc_add_frame", _lib.load().gm_wall_arc_add_frame(C.byref(prm), C.byref(arc), _dptr(m), C.byref(i)))
+    d = dict(status=int(i.status), anchor_station=int(i.anchor_station), sensor_chainage=float(i.sensor_chainage),
+             anchor_chainage=float(i.anchor_chainage))
+    for k in ("o", "a", "n", "b"):
+        d[k] = np.array(getattr(i, k)[:], dtype=np.float32)
+    for k in ("kappa", "un", "ub", "vn", "vb", "R", "station_length", "sector_angle", "gate"):
+        d[k] = np.float32(getattr(i, k))
+    return d
+
+
+def wall_arc_frame(prm, arc, chainage):
+    """gm_wall_arc_frame (host only): the design frame (o, a, u, v) at `chainage`, float64 [3] each."""
+    o, a, u, v = _d3(), _d3(), _d3(), _d3()
+    _arc_call("gm_wall_arc_frame", _lib.load().gm_wall_arc_frame(C.byref(prm), C.byref(arc), float(chainage), _dptr(o), _dptr(a),
+                                                                 _dptr(u), _dptr(v)))
+    return o, a, u, v
+
+
+def wall_arc_project(prm, arc, xyz):
+    """gm_wall_arc_project (host only) on map points [n, 3]: (chainage, angle, e), float64 [n] each."""
+    x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+    L = _lib.load()
+    out = np.empty((len(x), 3), dtype=np.float64)
+    s, ph, e = C.c_double(), C.c_double(), C.c_double()
+    for k in range(len(x)):
+        _arc_call("gm_wall_arc_project", L.gm_wall_arc_project(C.byref(prm), C.byref(arc), _dptr(x[k]), C.byref(s), C.byref(ph),
+                                                               C.byref(e)))
+        out[k] = (s.value, ph.value, e.value)
+    return out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
+
+
+def wall_arc_point(prm, arc, chainage, angle, rho):
+    """gm_wall_arc_point (host only): the map points at (chainage, angle, rho), broadcast; float64 [n, 3]."""
+    s, ph, r = np.broadcast_arrays(np.asarray(chainage, np.float64), np.asarray(angle, np.float64), np.asarray(rho, np.float64))
+    s, ph, r = s.reshape(-1), ph.reshape(-1), r.reshape(-1)
+    L = _lib.load()
+    out = np.empty((len(s), 3), dtype=np.float64)
+    for k in range(len(s)):
+        _arc_call("gm_wall_arc_point", L.gm_wall_arc_point(C.byref(prm), C.byref(arc), float(s[k]), float(ph[k]), float(r[k]),
+                                                           _dptr(out[k])))
+    return out
+
+
 def _wall_mesh_info(info):
     d = {k: int(getattr(info, k)) for k in _MESH_INFO}
     d["cloud"] = {k: int(getattr(info.cloud, k)) for k in _CLOUD_INFO}
@@ -954,12 +1026,16 @@ class WallMap:
     """One gm_wall_map: a device-resident developed wall map against a design cylinder, accumulated over posed frames
     (include/gm_hip.h states the rule).  Created by GeometricMapping.wall_map(); dies with its context."""
 
-    def __init__(self, ctx, **params):
+    def __init__(self, ctx, arc=None, **params):
         self._ctx, self._L = ctx, ctx._L
         self._map = None
         p = self.params(**params)
         h = C.c_void_p()
-        ctx._check(self._L.gm_wall_map_create(ctx._ctx, C.byref(p), C.byref(h)))
+        if arc is None:
+            ctx._check(self._L.gm_wall_map_create(ctx._ctx, C.byref(p), C.byref(h)))
+        else:
+            a = arc if isinstance(arc, _lib.WallArc) else wall_arc(**arc)
+            ctx._check(self._L.gm_wall_map_create_arc(ctx._ctx, C.byref(p), C.byref(a), C.byref(h)))
         self._map, self.prm = h, p
         self.n_stations, self.n_sectors = int(p.n_stations), int(p.n_sectors)
         if not hasattr(ctx, "_walls"):
@@ -979,6 +1055,19 @@ class WallMap:
             else:
                 setattr(p, k, v)
         return p
+
+    @property
+    def arc(self):
+        """gm_wall_map_get_arc: dict(curvature float64 [3], point_chainage), or None on a straight map."""
+        a = self.arc_struct()
+        c = np.array(a.curvature[:], dtype=np.float64)
+        return dict(curvature=c, point_chainage=float(a.point_chainage)) if np.any(c != 0.0) else None
+
+    def arc_struct(self):
+        """The map's gm_wall_arc (curvature 0 on a straight map), as the host helpers wall_arc_* take it."""
+        a = _lib.WallArc()
+        self._ctx._check(self._L.gm_wall_map_get_arc(self._h(), C.byref(a)))
+        return a
 
     def close(self):
         if self._map is not None:
@@ -1558,9 +1647,12 @@ class WallMap:
         return object_metrics(self.prm, obj, **params)
 
     def save(self, path):
-        """The parameters and the raw cells as one .npz (numpy only)."""
+        """The parameters, the arc of a map on one, and the raw cells as one .npz (numpy only)."""
         p = self.prm
         kw = {k: np.array(getattr(p, k)[:], dtype=np.float64) for k in _WALL_VEC}
+        arc = self.arc
+        if arc is not None:
+            kw.update(arc_curvature=arc["curvature"], arc_point_chainage=np.float64(arc["point_chainage"]))
         np.savez_compressed(path, n_stations=np.uint32(p.n_stations), n_sectors=np.uint32(p.n_sectors),
                             station_length=np.float64(p.station_length), t_min=np.float64(p.t_min), gate=np.float64(p.gate),
                             radius=np.float64(p.radius), raw=self.read_raw(), **kw)
@@ -1570,6 +1662,8 @@ class WallMap:
         """A new map on ctx with the file's parameters and cells (the per-class totals are not part of a file)."""
         with np.load(path) as z:
             kw = {k: z[k].tolist() for k in _WALL_VEC}
+            if "arc_curvature" in z.files:
+                kw["arc"] = dict(curvature=z["arc_curvature"].tolist(), point_chainage=float(z["arc_point_chainage"]))
             m = WallMap(ctx, n_stations=int(z["n_stations"]), n_sectors=int(z["n_sectors"]),
                         station_length=float(z["station_length"]), t_min=float(z["t_min"]), gate=float(z["gate"]),
                         radius=float(z["radius"]), **kw)

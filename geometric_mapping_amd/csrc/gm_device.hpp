@@ -269,6 +269,33 @@ __device__ __forceinline__ uint32_t surf_sector(float wx, float wy, float wz, co
     const uint32_t kk = (uint32_t)floorf(__fdiv_rn(phi, sector_angle));
     return kk < nsec - 1u ? kk : nsec - 1u;
 }
+// ---- the same chain on a circular-arc design axis (include/gm_hip.h states it; k_wall.hip's and k_wall_check.hip's arc
+// instantiations).  (o, a, n, b): the section at the anchor station in sensor coordinates.  Returns e; t: the arc length
+// from the anchor section, (yc, z): the offset in the point's own section along n(s) and b; cy <= 0: a quarter turn or more
+// from the anchor section (the caller classes it beyond_gate).
+__device__ __forceinline__ float arc_residual(const float4 &p, const float (&o)[3], const float (&a)[3], const float (&n)[3],
+                                              const float (&b)[3], float kappa, float R, float &t, float &yc, float &z, float &cy)
+{
+    const float qx = __fsub_rn(p.x, o[0]), qy = __fsub_rn(p.y, o[1]), qz = __fsub_rn(p.z, o[2]);
+    const float x = surf_dot3(qx, qy, qz, a), y = surf_dot3(qx, qy, qz, n);
+    z = surf_dot3(qx, qy, qz, b);
+    const float cx = __fmul_rn(kappa, x);
+    cy = __fmaf_rn(-kappa, y, 1.0f);
+    const float d = __fsqrt_rn(__fmaf_rn(cx, cx, __fmul_rn(cy, cy)));
+    t = __fdiv_rn(atan2f(cx, cy), kappa);
+    const float h = __fmaf_rn(x, x, __fmul_rn(y, y));
+    yc = __fdiv_rn(__fmaf_rn(-kappa, h, __fadd_rn(y, y)), __fadd_rn(1.0f, d));
+    return __fsub_rn(__fsqrt_rn(__fmaf_rn(yc, yc, __fmul_rn(z, z))), R);
+}
+// surf_sector on (yc, z): phi = atan2(yc vn + z vb, yc un + z ub)
+__device__ __forceinline__ uint32_t arc_sector(float yc, float z, float un, float ub, float vn, float vb, float two_pi,
+                                               float sector_angle, uint32_t nsec)
+{
+    const float th = atan2f(__fmaf_rn(yc, vn, __fmul_rn(z, vb)), __fmaf_rn(yc, un, __fmul_rn(z, ub)));
+    const float phi = th < 0.0f ? __fadd_rn(th, two_pi) : th;
+    const uint32_t kk = (uint32_t)floorf(__fdiv_rn(phi, sector_angle));
+    return kk < nsec - 1u ? kk : nsec - 1u;
+}
 // ---- run merging: the common start of the segmented reductions (surf_merge_runs here, wc_merge_runs in k_wall_cloud.hip,
 // k_wall_region_reduce, k_wall_object_reduce).  Runs of one key in consecutive lanes are folded into the run's head lane
 // before anything goes to memory.  wave_runs finds the runs; the ladder stays with its caller, because its fields do:

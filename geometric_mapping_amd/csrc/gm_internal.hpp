@@ -314,6 +314,12 @@ struct WallArgs {
     float *res;                // stage call only (nullptr in the frame path)
     int32_t *cell;
 };
+// A map on a circular-arc design axis (gm_wall_map_create_arc): what the arc instantiations take by value beside WallArgs,
+// whose o, a are then o', a' at the anchor section (u, v are reported, not read).
+struct WallArc {
+    float n[3], b[3];          // n', b' in sensor coordinates
+    float kappa, un, ub, vn, vb;
+};
 // the arrays of a table of ncell cells at base: sum i64 | count u32 | lo u32 | hi u32 | totals u64 [kWallTotals]
 __host__ __device__ inline WallTable wall_table(uint8_t *base, uint64_t ncell)
 {
@@ -328,6 +334,7 @@ __host__ __device__ inline WallTable wall_table(uint8_t *base, uint64_t ncell)
 size_t wall_table_bytes(uint64_t ncell);
 // n_cap: the most points the launch can see (the grid is sized by it); points_per_block 0: the default rule
 void launch_wall_add(const WallArgs &a, uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
+void launch_wall_add_arc(const WallArgs &a, const WallArc &arc, uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
 // k_wall_add_checked.hip (gm_wall_map_add_*_checked): mark the selected rows' points in a bit mask, then k_wall_add's masked
 // instantiation.  u64 words of the call's counter block: rows_neg, rows_pos, rows_kept, rows_rejected | skipped, mapped,
 // outside, beyond_gate, plane | n_rows, n_points, pad
@@ -349,6 +356,8 @@ void launch_wall_mark(const WallMarkArgs &a, uint32_t n_cap, hipStream_t s);
 // k_wall_add over the points whose mask bit is clear; the five point classes also go to ctr[4 .. 8]
 void launch_wall_add_masked(const WallArgs &a, const unsigned long long *mask, unsigned long long *ctr, uint32_t n_cap,
                             uint32_t points_per_block, hipStream_t s);
+void launch_wall_add_arc_masked(const WallArgs &a, const WallArc &arc, const unsigned long long *mask, unsigned long long *ctr,
+                                uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
 // the class of one row: 0 selected negative, 1 selected positive, 2 kept, 3 rejected (delta_bits: the row's delta)
 __host__ __device__ inline uint32_t wall_mark_class(uint32_t delta_bits, long long dq, uint32_t index, uint32_t n_points,
                                                     uint32_t skip, long long S)
@@ -409,8 +418,15 @@ struct WallCloudArgs {
     gm_wall_cloud_point *out;  // the chunk's staging
     unsigned long long *ctr;   // [kWallCloudCounters]
 };
+// the arc position rule beside WallCloudArgs, whose oa, u, v are then not read (a: the design direction at params.point)
+struct WallCloudArc {
+    const double *rows;        // [nJ][2] cos psi, sin psi of the chunk's block rows (host-computed)
+    double ca[3], n[3], b[3];  // C - anchor, n, b
+    double inv_kappa, un, ub, vn, vb;
+};
 void launch_wall_cloud_merge(const WallCloudArgs &a, hipStream_t s);
 void launch_wall_cloud_compact(const WallCloudArgs &a, const ScanState &st, hipStream_t s);
+void launch_wall_cloud_compact_arc(const WallCloudArgs &a, const WallCloudArc &arc, const ScanState &st, hipStream_t s);
 // k_wall_mesh.hip (gm_wall_map_mesh): the cloud's compaction with an emit step that also stores the survivor's index
 // (rank_base + its rank in the chunk) into rank[block of the window] and, for a step cut, its mean into mean[block]; then
 // per chunk of whole quad rows one k_compact over the chunk's 2 * quads slots
@@ -428,6 +444,8 @@ struct WallMeshArgs {
 };
 void launch_wall_mesh_vertices(const WallCloudArgs &a, uint32_t *rank, float *mean, uint32_t rank_base, const ScanState &st,
                                hipStream_t s);
+void launch_wall_mesh_vertices_arc(const WallCloudArgs &a, const WallCloudArc &arc, uint32_t *rank, float *mean, uint32_t rank_base,
+                                   const ScanState &st, hipStream_t s);
 void launch_wall_mesh_triangles(const WallMeshArgs &a, const ScanState &st, hipStream_t s);
 // k_wall_check.hip (gm_wall_map_check_*): one k_compact launch per check
 // u64 words: the seven classes (GM_WALL_CHECK_CLS_* order), peak_pos, -peak_neg, the changed points (low word), n_points, pad
@@ -444,6 +462,7 @@ struct WallCheckArgs {
 };
 // n_cap: the most points the launch can see (the grid is sized by it)
 void launch_wall_check(const WallCheckArgs &a, uint32_t n_cap, const ScanState &st, hipStream_t s);
+void launch_wall_check_arc(const WallCheckArgs &a, const WallArc &arc, uint32_t n_cap, const ScanState &st, hipStream_t s);
 // the rule's integers, shared by the kernel and gm_wall_check_classify
 __host__ __device__ inline long long wall_check_fix(float e)   // (int64) rint(e 2^20), saturating at int32, 0 for a NaN
 {

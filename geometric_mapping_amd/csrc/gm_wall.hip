@@ -12,7 +12,75 @@ using namespace gm::wall;
 namespace gm {
 namespace wall {
 
-gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info *info, WallArgs &w, WallFrame64 *f64)
+// the LDS window of an add: whole stations around the anchor for |t| / ds <= reach, as many as the LDS table holds; a
+// footprint beyond it is centred (the rest goes to the map directly)
+static void add_window(const gm_wall_params &p, double reach_stations, WallArgs &w)
+{
+    const uint32_t wmax = GM_SURF_MAX_CELLS / p.n_sectors;   // >= 1: n_sectors <= 4096
+    const double reach = std::min(reach_stations, 1.0e6);
+    const int64_t first = (int64_t)floor(-reach) - 1, last = (int64_t)floor(reach) + 2;   // one station of fp32 slack each side
+    const int64_t need = last - first + 1;
+    if (need <= (int64_t)wmax) {
+        w.win_first = (int32_t)first;
+        w.win_stations = (uint32_t)need;
+    } else {
+        w.win_first = -(int32_t)(wmax / 2);
+        w.win_stations = wmax;
+    }
+}
+
+// add_frame_args on an arc map (include/gm_hip.h: per add)
+static gm_status add_frame_args_arc(gm_wall_map *m, const double Rm[3][3], const double tr[3], gm_wall_add_info *info, WallArgs &w,
+                                    WallArc &arc)
+{
+    gm_ctx *ctx = m->ctx;
+    const gm_wall_params &p = m->prm;
+    gm_wall_arc_add_info ai;
+    double u64[3], v64[3], a1 = 0.0;
+    if (!arc_add_frame(p, m->frame, m->af, Rm, tr, ai, u64, v64, &a1))
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose is too far along the axis");
+    memset(&w, 0, sizeof(w));
+    for (int k = 0; k < 3; ++k) {
+        w.o[k] = ai.o[k]; w.a[k] = ai.a[k]; w.u[k] = (float)u64[k]; w.v[k] = (float)v64[k];
+        arc.n[k] = ai.n[k]; arc.b[k] = ai.b[k];
+    }
+    arc.kappa = ai.kappa;
+    arc.un = ai.un; arc.ub = ai.ub; arc.vn = ai.vn; arc.vb = ai.vb;
+    w.R = ai.R;
+    w.station_length = ai.station_length;
+    w.gate = ai.gate;
+    w.sector_angle = ai.sector_angle;
+    w.two_pi = (float)kTwoPi;
+    w.n_stations = p.n_stations;
+    w.n_sectors = p.n_sectors;
+    w.anchor = ai.anchor_station;
+    w.table = m->table;
+    // The LDS window, which affects speed only (a mapped point outside it goes to the map directly): wherever cy >= 0.5,
+    // |t| = |atan2(cx, cy)| / kappa <= |cx| / (cy kappa) <= 2 |x|, and |x| <= B |a'|_1 + ds over the crop cube
+    // |p|_inf <= B as on a straight map (the sensor lies within ds of the anchor section: the stations that costs at the
+    // window's ends take the global path).
+    add_window(p, 2.0 * ctx->cfg.boxFilterBound * a1 / p.station_length, w);
+    if (info) {
+        memset(info, 0, sizeof(*info));
+        info->struct_size = (uint32_t)sizeof(gm_wall_add_info);
+        info->status = m->frame.status;
+        info->anchor_station = w.anchor;
+        for (int k = 0; k < 3; ++k) { info->o[k] = w.o[k]; info->a[k] = w.a[k]; info->u[k] = w.u[k]; info->v[k] = w.v[k]; }
+        info->R = w.R;
+        info->station_length = w.station_length;
+        info->sector_angle = w.sector_angle;
+        info->gate = w.gate;
+    }
+    return GM_OK;
+}
+
+void launch_add(gm_wall_map *m, const WallArgs &w, const WallArc &arc, uint32_t n_cap, hipStream_t s)
+{
+    if (m->is_arc()) launch_wall_add_arc(w, arc, n_cap, m->points_per_block, s);
+    else launch_wall_add(w, n_cap, m->points_per_block, s);
+}
+
+gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info *info, WallArgs &w, WallFrame64 *f64, WallArc *arc)
 {
     gm_ctx *ctx = m->ctx;
     if (!pose) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: NULL pose");
@@ -20,6 +88,10 @@ gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info
     const int bad = pose_split(pose, Rm, tr);
     if (bad == 1) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose is not finite");
     if (bad) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose rotation is not orthonormal to 1e-6 or is a reflection");
+    if (m->is_arc()) {
+        if (!arc) return gm_fail(ctx, GM_ERR_UNSUPPORTED, "gm_wall_map: this call is not available on a map with an arc design axis");
+        return add_frame_args_arc(m, Rm, tr, info, w, *arc);
+    }
     const gm_wall_params &p = m->prm;
     const DesignFrame &d = m->frame;
     const double ds = p.station_length;
@@ -53,18 +125,7 @@ gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info
     w.table = m->table;
     // The LDS window: t = p.a' + (s - chainage of the anchor station's start) lies in [-B |a'|_1, B |a'|_1 + ds) for the
     // points of the crop cube |p|_inf <= B, so their stations relative to the anchor in [floor(-reach), floor(reach) + 1].
-    // Whole stations, as many as the LDS table holds; a footprint beyond it is centred (the rest goes to the map directly).
-    const uint32_t wmax = GM_SURF_MAX_CELLS / p.n_sectors;   // >= 1: n_sectors <= 4096
-    const double reach = std::min(ctx->cfg.boxFilterBound * a1 / ds, 1.0e6);
-    const int64_t first = (int64_t)floor(-reach) - 1, last = (int64_t)floor(reach) + 2;   // one station of fp32 slack each side
-    const int64_t need = last - first + 1;
-    if (need <= (int64_t)wmax) {
-        w.win_first = (int32_t)first;
-        w.win_stations = (uint32_t)need;
-    } else {
-        w.win_first = -(int32_t)(wmax / 2);
-        w.win_stations = wmax;
-    }
+    add_window(p, ctx->cfg.boxFilterBound * a1 / ds, w);
     if (info) {
         memset(info, 0, sizeof(*info));
         info->struct_size = (uint32_t)sizeof(gm_wall_add_info);
@@ -181,6 +242,7 @@ gm_status check_baseline(gm_wall_map *map, gm_wall_map *baseline, const char *wh
         memcmp(&p.t_min, &b.t_min, 8) || memcmp(p.point, b.point, 24) || memcmp(p.direction, b.direction, 24) ||
         memcmp(&p.radius, &b.radius, 8) || memcmp(p.up, b.up, 24) || memcmp(p.forward, b.forward, 24))
         return refuse(": the baseline is a map on another grid");
+    if (memcmp(&map->arc, &baseline->arc, sizeof(gm_wall_arc))) return refuse(": the baseline is a map on another arc");
     return GM_OK;
 }
 
@@ -302,6 +364,18 @@ gm_status cloud_chunks(gm_wall_map *map, const gm_wall_cloud_params &cp, gm_wall
     a.ds = map->prm.station_length;
     a.out = map->cl_stage.p;
     a.ctr = map->cl_ctr.p;
+    const bool on_arc = map->is_arc();
+    WallCloudArc ca;
+    memset(&ca, 0, sizeof(ca));
+    if (on_arc) {
+        const ArcFrame &f = map->af;
+        GMW_HIP(ctx, map->cl_rows.reserve((uint64_t)rows * 2));
+        map->cl_rows_host.resize((size_t)rows * 2);
+        ca.rows = map->cl_rows.p;
+        for (int k = 0; k < 3; ++k) { ca.ca[k] = f.C[k] - cp.anchor[k]; ca.n[k] = f.n[k]; ca.b[k] = f.b[k]; }
+        ca.inv_kappa = f.inv_kappa;
+        ca.un = f.un; ca.ub = f.ub; ca.vn = f.vn; ca.vb = f.vb;
+    }
 
     uint64_t total = 0;
     unsigned long long ctr[kWallCloudCounters] = {0ull, 0ull, 0ull, 0ull};
@@ -314,8 +388,22 @@ gm_status cloud_chunks(gm_wall_map *map, const gm_wall_cloud_params &cp, gm_wall
             launch_wall_cloud_merge(a, map->stream);
             GMW_HIP(ctx, hipGetLastError());
         }
-        if (mesh) launch_wall_mesh_vertices(a, mesh->rank, mesh->mean, (uint32_t)total, map->cl_scan.next(map->stream), map->stream);
-        else launch_wall_cloud_compact(a, map->cl_scan.next(map->stream), map->stream);
+        if (on_arc) {   // (cos psi, sin psi) of the chunk's block rows: tc by the emit step's rule
+            for (uint32_t jl = 0; jl < a.nJ; ++jl) {
+                const uint32_t jw = (J0 + jl) * bs, ns = std::min(n - jw, bs);
+                const double h = (double)(2u * (station0 + jw) + ns) * 0.5;
+                const double tc = a.t_min + h * a.ds;
+                const double psi = map->af.kappa * (tc - map->af.s0);
+                map->cl_rows_host[2 * (size_t)jl] = cos(psi);
+                map->cl_rows_host[2 * (size_t)jl + 1] = sin(psi);
+            }   // (the last chunk's copy has been waited for: every trip ends with a synchronisation)
+            GMW_HIP(ctx, hipMemcpyAsync(map->cl_rows.p, map->cl_rows_host.data(), (size_t)a.nJ * 16, hipMemcpyHostToDevice, map->stream));
+        }
+        const ScanState st = map->cl_scan.next(map->stream);
+        if (mesh && on_arc) launch_wall_mesh_vertices_arc(a, ca, mesh->rank, mesh->mean, (uint32_t)total, st, map->stream);
+        else if (mesh) launch_wall_mesh_vertices(a, mesh->rank, mesh->mean, (uint32_t)total, st, map->stream);
+        else if (on_arc) launch_wall_cloud_compact_arc(a, ca, st, map->stream);
+        else launch_wall_cloud_compact(a, st, map->stream);
         GMW_HIP(ctx, hipGetLastError());
         GMW_HIP(ctx, hipMemcpyAsync(ctr, a.ctr, sizeof(ctr), hipMemcpyDeviceToHost, map->stream));
         GMW_HIP(ctx, hipStreamSynchronize(map->stream));
@@ -346,13 +434,19 @@ void gm_wall_free_all(gm_ctx *ctx)
 
 extern "C" {
 
-gm_status gm_wall_map_create(gm_ctx *ctx, const gm_wall_params *params, gm_wall_map **map)
+// gm_wall_map_create (arc NULL) and gm_wall_map_create_arc
+static gm_status create_map(gm_ctx *ctx, const gm_wall_params *params, const gm_wall_arc *arc, gm_wall_map **map)
 {
     if (!ctx) return GM_ERR_INVALID_ARG;
     if (!map) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_create: NULL map");
     *map = nullptr;
     if (check_params(params) != GM_OK)
         return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_create: NULL, struct_size mismatch or a parameter outside its limits");
+    DesignFrame arc_d;
+    ArcFrame arc_f;
+    memset(&arc_f, 0, sizeof(arc_f));
+    if (arc && arc_check(params, arc, arc_d, arc_f) != GM_OK)
+        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_create_arc: struct_size mismatch, or a curvature outside its limits for this map");
     GMW_OK(set_device(ctx));
     gm_wall_map *m = new gm_wall_map;
     m->ctx = ctx;
@@ -397,6 +491,10 @@ gm_status gm_wall_map_create(gm_ctx *ctx, const gm_wall_params *params, gm_wall_
         m->quantity_chunk = v < kStageBytes ? (uint32_t)v : 0u;
     }
     design_frame_of(m->prm, m->frame);
+    memset(&m->arc, 0, sizeof(m->arc));
+    m->arc.struct_size = (uint32_t)sizeof(gm_wall_arc);
+    if (arc) { m->arc = *arc; m->arc.reserved = 0u; }
+    m->af = arc_f;
     auto body = [&]() -> gm_status {
         GMW_HIP(ctx, hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
         GMW_HIP(ctx, m->base.reserve(wall_table_bytes(m->ncell)));
@@ -417,6 +515,23 @@ gm_status gm_wall_map_create(gm_ctx *ctx, const gm_wall_params *params, gm_wall_
     return GM_OK;
 }
 
+gm_status gm_wall_map_create(gm_ctx *ctx, const gm_wall_params *params, gm_wall_map **map) { return create_map(ctx, params, nullptr, map); }
+
+gm_status gm_wall_map_create_arc(gm_ctx *ctx, const gm_wall_params *params, const gm_wall_arc *arc, gm_wall_map **map)
+{
+    if (!ctx) return GM_ERR_INVALID_ARG;
+    if (map) *map = nullptr;
+    if (!arc) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_create_arc: NULL arc");
+    return create_map(ctx, params, arc, map);
+}
+
+gm_status gm_wall_map_get_arc(gm_wall_map *map, gm_wall_arc *arc)
+{
+    if (!map || !arc) return GM_ERR_INVALID_ARG;
+    *arc = map->arc;
+    return GM_OK;
+}
+
 void gm_wall_map_destroy(gm_wall_map *map)
 {
     if (!map) return;
@@ -430,11 +545,12 @@ gm_status gm_wall_map_add_frame(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, co
     Slot *sl = nullptr;
     GMW_OK(frame_call_head(map, ctx, slot, "gm_wall_map_add_frame", [] { return true; }, sl));
     WallArgs w;
-    GMW_OK(add_frame_args(map, pose, add_info, w));
+    WallArc arc;
+    GMW_OK(add_frame_args(map, pose, add_info, w, nullptr, &arc));
     GMW_OK(set_device(ctx));
     frame_points(ctx, *sl, w);
     GMW_OK(add_wait_readers(map, slot, sl->stream));
-    launch_wall_add(w, sl->n_in, map->points_per_block, sl->stream);
+    launch_add(map, w, arc, sl->n_in, sl->stream);
     GMW_HIP(ctx, hipGetLastError());
     map->pending[slot] = 1;
     ++map->frames;
@@ -448,13 +564,14 @@ gm_status gm_wall_map_add_points(gm_wall_map *map, const float *xyz, uint32_t n,
     gm_ctx *ctx = map->ctx;
     if (n && !xyz) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_add_points: NULL xyz");
     WallArgs w;
-    GMW_OK(add_frame_args(map, pose, add_info, w));
+    WallArc arc;
+    GMW_OK(add_frame_args(map, pose, add_info, w, nullptr, &arc));
     StageCall sc{map, n, residual, cell, nullptr, nullptr};
     GMW_OK(sc.open());
     GMW_OK(sc.upload(xyz, labels, w));
     hipStream_t s = sc.sl->stream;
     GMW_OK(add_wait_readers(map, 0, s));   // (as gm_wall_map_add_frame; the staging slot is slot 0)
-    launch_wall_add(w, n, map->points_per_block, s);
+    launch_add(map, w, arc, n, s);
     GMW_HIP(ctx, hipGetLastError());
     GMW_OK(sc.close());
     ++map->frames;

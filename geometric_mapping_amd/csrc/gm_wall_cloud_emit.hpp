@@ -48,48 +48,98 @@ struct WallCloudPred {
     }
 };
 
-struct WallCloudEmit {
-    static constexpr bool kHasFinish = true, kHasPrepare = true;
-    WallCloudArgs a;
-    __device__ __forceinline__ void prepare() const
+// the straight position rule: p = (o - anchor) + tc a + rho (c u + s v)
+struct WallCloudStraight {
+    __device__ __forceinline__ void operator()(const WallCloudArgs &a, uint32_t, double tc, double rho, double c, double s,
+                                               float (&xyz)[3]) const
     {
-        if (threadIdx.x < 2) wc_class_counts()[threadIdx.x] = 0u;
-    }
-    __device__ __forceinline__ void finish(uint32_t) const
-    {
-        __syncthreads();
-        if (threadIdx.x < 2) {
-            const uint32_t c = wc_class_counts()[threadIdx.x];
-            if (c) atomicAdd(&a.ctr[threadIdx.x], (unsigned long long)c);
-        }
-    }
-    __device__ __forceinline__ void operator()(uint32_t src, uint32_t dst, const WallCloudPred::Payload &p) const
-    {
-        const uint32_t jl = src / a.NK, K = src % a.NK, J = a.J0 + jl;
-        const uint32_t jw = J * a.bs;                                   // window-relative first station, < n
-        const uint32_t ns = a.n - jw < a.bs ? a.n - jw : a.bs;
-        const uint32_t j0 = a.station0 + jw;
-        const double m = __ddiv_rn(__dmul_rn((double)(long long)p.sum, 0x1p-20), (double)p.count);
-        const double h = __dmul_rn((double)(2u * j0 + ns), 0.5);
-        const double tc = __dadd_rn(a.t_min, __dmul_rn(h, a.ds));
-        const double rho = __dadd_rn(a.R, __dmul_rn(a.g, m));
-        const double c = a.dirs[2u * K], s = a.dirs[2u * K + 1u];
-        float xyz[3];
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             const double w = __dadd_rn(__dmul_rn(c, a.u[i]), __dmul_rn(s, a.v[i]));
             const double q = __dadd_rn(__dadd_rn(a.oa[i], __dmul_rn(tc, a.a[i])), __dmul_rn(rho, w));
             xyz[i] = __double2float_rn(q);
         }
-        gm_wall_cloud_point r;
-        r.x = xyz[0]; r.y = xyz[1]; r.z = xyz[2];
-        r.mean = __double2float_rn(m);
-        r.min = ordered_to_float(~p.lo);
-        r.max = ordered_to_float(p.hi);
-        r.block = J * a.NK + K;
-        r.cells = p.cells;
-        r.count = p.count;
-        a.out[dst] = r;
+    }
+};
+// the arc position rule (a map of gm_wall_map_create_arc): p = (C - anchor) + (yc - 1 / kappa) n(tc) + zb b, with (cos, sin)
+// of the block row's psi from the host's table: no fp64 trigonometry here either
+struct WallCloudOnArc {
+    WallCloudArc arc;
+    __device__ __forceinline__ void operator()(const WallCloudArgs &a, uint32_t jl, double, double rho, double c, double s,
+                                               float (&xyz)[3]) const
+    {
+        const double cp = arc.rows[2u * jl], sp = arc.rows[2u * jl + 1u];
+        const double yc = __dmul_rn(rho, __dadd_rn(__dmul_rn(c, arc.un), __dmul_rn(s, arc.vn)));
+        const double zb = __dmul_rn(rho, __dadd_rn(__dmul_rn(c, arc.ub), __dmul_rn(s, arc.vb)));
+        const double r = __dsub_rn(yc, arc.inv_kappa);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const double nr = __dsub_rn(__dmul_rn(arc.n[i], cp), __dmul_rn(a.a[i], sp));
+            const double q = __dadd_rn(__dadd_rn(arc.ca[i], __dmul_rn(r, nr)), __dmul_rn(zb, arc.b[i]));
+            xyz[i] = __double2float_rn(q);
+        }
+    }
+};
+
+// the record of survivor `src` of the chunk at rank `dst`, its position by `pos`
+template <class Position>
+__device__ __forceinline__ void wc_emit(const WallCloudArgs &a, const Position &pos, uint32_t src, uint32_t dst,
+                                        const WallCloudPred::Payload &p)
+{
+    const uint32_t jl = src / a.NK, K = src % a.NK, J = a.J0 + jl;
+    const uint32_t jw = J * a.bs;                                   // window-relative first station, < n
+    const uint32_t ns = a.n - jw < a.bs ? a.n - jw : a.bs;
+    const uint32_t j0 = a.station0 + jw;
+    const double m = __ddiv_rn(__dmul_rn((double)(long long)p.sum, 0x1p-20), (double)p.count);
+    const double h = __dmul_rn((double)(2u * j0 + ns), 0.5);
+    const double tc = __dadd_rn(a.t_min, __dmul_rn(h, a.ds));
+    const double rho = __dadd_rn(a.R, __dmul_rn(a.g, m));
+    const double c = a.dirs[2u * K], s = a.dirs[2u * K + 1u];
+    float xyz[3];
+    pos(a, jl, tc, rho, c, s, xyz);
+    gm_wall_cloud_point r;
+    r.x = xyz[0]; r.y = xyz[1]; r.z = xyz[2];
+    r.mean = __double2float_rn(m);
+    r.min = ordered_to_float(~p.lo);
+    r.max = ordered_to_float(p.hi);
+    r.block = J * a.NK + K;
+    r.cells = p.cells;
+    r.count = p.count;
+    a.out[dst] = r;
+}
+__device__ __forceinline__ void wc_prepare()
+{
+    if (threadIdx.x < 2) wc_class_counts()[threadIdx.x] = 0u;
+}
+__device__ __forceinline__ void wc_finish(const WallCloudArgs &a)
+{
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const uint32_t c = wc_class_counts()[threadIdx.x];
+        if (c) atomicAdd(&a.ctr[threadIdx.x], (unsigned long long)c);
+    }
+}
+
+struct WallCloudEmit {
+    static constexpr bool kHasFinish = true, kHasPrepare = true;
+    WallCloudArgs a;
+    __device__ __forceinline__ void prepare() const { wc_prepare(); }
+    __device__ __forceinline__ void finish(uint32_t) const { wc_finish(a); }
+    __device__ __forceinline__ void operator()(uint32_t src, uint32_t dst, const WallCloudPred::Payload &p) const
+    {
+        wc_emit(a, WallCloudStraight(), src, dst, p);
+    }
+};
+// a map of gm_wall_map_create_arc: an emit step, hence a kernel, of its own
+struct WallCloudEmitArc {
+    static constexpr bool kHasFinish = true, kHasPrepare = true;
+    WallCloudArgs a;
+    WallCloudOnArc pos;
+    __device__ __forceinline__ void prepare() const { wc_prepare(); }
+    __device__ __forceinline__ void finish(uint32_t) const { wc_finish(a); }
+    __device__ __forceinline__ void operator()(uint32_t src, uint32_t dst, const WallCloudPred::Payload &p) const
+    {
+        wc_emit(a, pos, src, dst, p);
     }
 };
 

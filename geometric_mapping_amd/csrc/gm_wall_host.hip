@@ -1,10 +1,10 @@
 // gm_wall_host.hip -- the part of the wall map's C ABI that needs no device (include/gm_hip.h states each rule): the
 // defaults, the parameter checks, the classification of one cell, the metrics, the direction table, the mesh's triangle
 // rule and its PLY file, the gauge of a polygon, the runs, the align's selection, the sections' basis, solve and metrics,
-// the quantities' column, metrics and runs.
+// the quantities' column, metrics and runs, the rules of a map on a circular-arc design axis (gm_wall_arc_*).
 // No device call, no context, no map: it links against libm and the C++ library alone, and host/gm_wall_host_test.cpp,
-// host/gm_wall_sections_host_test.cpp, host/gm_wall_mesh_host_test.cpp and host/gm_wall_quantities_host_test.cpp run it
-// under the host sanitizers.
+// host/gm_wall_sections_host_test.cpp, host/gm_wall_mesh_host_test.cpp, host/gm_wall_quantities_host_test.cpp and
+// host/gm_wall_arc_host_test.cpp run it under the host sanitizers.
 #include <stdio.h>
 
 #include <vector>
@@ -65,6 +65,86 @@ void design_frame_of(const gm_wall_params &p, DesignFrame &d)
         d.v[k] = v[k];
     }
     d.R = p.radius;
+}
+
+gm_status arc_check(const gm_wall_params *p, const gm_wall_arc *arc, DesignFrame &d, ArcFrame &f)
+{
+    if (check_params(p) != GM_OK || !arc || arc->struct_size != sizeof(gm_wall_arc)) return GM_ERR_INVALID_ARG;
+    if (!isfinite(arc->curvature[0]) || !isfinite(arc->curvature[1]) || !isfinite(arc->curvature[2]) || !isfinite(arc->point_chainage))
+        return GM_ERR_INVALID_ARG;
+    design_frame_of(*p, d);
+    memset(&f, 0, sizeof(f));
+    const double ca = dot(arc->curvature, d.a);
+    double c[3];
+    for (int k = 0; k < 3; ++k) c[k] = arc->curvature[k] - ca * d.a[k];
+    const double kappa = sqrt(dot(c, c));
+    if (!isfinite(kappa) || kappa < 1e-6 || (p->radius + p->gate) * kappa > 0.5) return GM_ERR_INVALID_ARG;
+    const double s0 = arc->point_chainage, s_end = p->t_min + (double)p->n_stations * p->station_length;
+    if (!(fabs(kappa * (p->t_min - s0)) <= 3.0) || !(fabs(kappa * (s_end - s0)) <= 3.0)) return GM_ERR_INVALID_ARG;
+    f.kappa = kappa;
+    f.inv_kappa = 1.0 / kappa;
+    f.s0 = s0;
+    for (int k = 0; k < 3; ++k) f.n[k] = c[k] / kappa;
+    const double *a = d.a, *n = f.n;
+    f.b[0] = a[1] * n[2] - a[2] * n[1]; f.b[1] = a[2] * n[0] - a[0] * n[2]; f.b[2] = a[0] * n[1] - a[1] * n[0];
+    for (int k = 0; k < 3; ++k) f.C[k] = p->point[k] + f.n[k] * f.inv_kappa;
+    f.un = dot(d.u, f.n); f.ub = dot(d.u, f.b);
+    f.vn = dot(d.v, f.n); f.vb = dot(d.v, f.b);
+    return GM_OK;
+}
+
+void arc_section(const DesignFrame &d, const ArcFrame &f, double s, double as[3], double ns[3], double P[3])
+{
+    const double psi = f.kappa * (s - f.s0);
+    const double cp = cos(psi), sp = sin(psi);
+    for (int k = 0; k < 3; ++k) {
+        as[k] = d.a[k] * cp + f.n[k] * sp;
+        ns[k] = f.n[k] * cp - d.a[k] * sp;
+        P[k] = f.C[k] - ns[k] * f.inv_kappa;
+    }
+}
+
+double arc_chainage(const DesignFrame &d, const ArcFrame &f, const double x[3])
+{
+    const double r[3] = {x[0] - f.C[0], x[1] - f.C[1], x[2] - f.C[2]};
+    const double psi = atan2(dot(r, d.a), -dot(r, f.n));
+    return f.s0 + psi / f.kappa;
+}
+
+bool arc_add_frame(const gm_wall_params &p, const DesignFrame &d, const ArcFrame &f, const double Rm[3][3], const double tr[3],
+                   gm_wall_arc_add_info &out, double *u64, double *v64, double *a1)
+{
+    const double ds = p.station_length;
+    const double s = arc_chainage(d, f, tr);
+    const double jd = floor((s - p.t_min) / ds);
+    if (!(fabs(jd) < 4.0e18)) return false;
+    const double sf = p.t_min + jd * ds;
+    double as[3], ns[3], P[3];
+    arc_section(d, f, sf, as, ns, P);
+    const double of[3] = {P[0] - tr[0], P[1] - tr[1], P[2] - tr[2]};
+    out.anchor_station = (int64_t)jd;
+    out.sensor_chainage = s;
+    out.anchor_chainage = sf;
+    double l1 = 0.0;
+    for (int c = 0; c < 3; ++c) {   // Rm^T x
+        const double oo = Rm[0][c] * of[0] + Rm[1][c] * of[1] + Rm[2][c] * of[2];
+        const double aa = Rm[0][c] * as[0] + Rm[1][c] * as[1] + Rm[2][c] * as[2];
+        const double nn = Rm[0][c] * ns[0] + Rm[1][c] * ns[1] + Rm[2][c] * ns[2];
+        const double bb = Rm[0][c] * f.b[0] + Rm[1][c] * f.b[1] + Rm[2][c] * f.b[2];
+        out.o[c] = (float)oo; out.a[c] = (float)aa; out.n[c] = (float)nn; out.b[c] = (float)bb;
+        if (u64) u64[c] = f.un * nn + f.ub * bb;
+        if (v64) v64[c] = f.vn * nn + f.vb * bb;
+        l1 += fabs(aa);
+    }
+    if (a1) *a1 = l1;
+    out.kappa = (float)f.kappa;
+    out.un = (float)f.un; out.ub = (float)f.ub; out.vn = (float)f.vn; out.vb = (float)f.vb;
+    out.R = (float)d.R;
+    out.station_length = (float)ds;
+    out.sector_angle = (float)(kTwoPi / (double)p.n_sectors);
+    out.gate = (float)p.gate;
+    out.reserved = 0u;
+    return true;
 }
 
 int pose_split(const double pose[12], double Rm[3][3], double tr[3])
@@ -476,6 +556,77 @@ void gm_wall_default_params(gm_wall_params *p)
     p->radius = 2.0;
     p->up[2] = 1.0;
     p->forward[0] = 1.0;
+}
+
+gm_status gm_wall_arc_check_params(const gm_wall_params *params, const gm_wall_arc *arc)
+{
+    DesignFrame d;
+    ArcFrame f;
+    return arc_check(params, arc, d, f);
+}
+
+gm_status gm_wall_arc_add_frame(const gm_wall_params *params, const gm_wall_arc *arc, const double pose[12],
+                                gm_wall_arc_add_info *info)
+{
+    DesignFrame d;
+    ArcFrame f;
+    double Rm[3][3], tr[3];
+    if (!pose || !info || arc_check(params, arc, d, f) != GM_OK || pose_split(pose, Rm, tr)) return GM_ERR_INVALID_ARG;
+    memset(info, 0, sizeof(*info));
+    if (!arc_add_frame(*params, d, f, Rm, tr, *info, nullptr, nullptr, nullptr)) return GM_ERR_INVALID_ARG;
+    info->struct_size = (uint32_t)sizeof(gm_wall_arc_add_info);
+    info->status = d.status;
+    return GM_OK;
+}
+
+gm_status gm_wall_arc_frame(const gm_wall_params *params, const gm_wall_arc *arc, double chainage, double o[3], double a[3],
+                            double u[3], double v[3])
+{
+    DesignFrame d;
+    ArcFrame f;
+    if (!o || !a || !u || !v || !isfinite(chainage) || arc_check(params, arc, d, f) != GM_OK) return GM_ERR_INVALID_ARG;
+    double ns[3];
+    arc_section(d, f, chainage, a, ns, o);
+    for (int k = 0; k < 3; ++k) {
+        u[k] = f.un * ns[k] + f.ub * f.b[k];
+        v[k] = f.vn * ns[k] + f.vb * f.b[k];
+    }
+    return GM_OK;
+}
+
+gm_status gm_wall_arc_project(const gm_wall_params *params, const gm_wall_arc *arc, const double xyz[3], double *chainage,
+                              double *angle, double *e)
+{
+    DesignFrame d;
+    ArcFrame f;
+    if (!xyz || !chainage || !angle || !e || arc_check(params, arc, d, f) != GM_OK) return GM_ERR_INVALID_ARG;
+    if (!isfinite(xyz[0]) || !isfinite(xyz[1]) || !isfinite(xyz[2])) return GM_ERR_INVALID_ARG;
+    const double r[3] = {xyz[0] - f.C[0], xyz[1] - f.C[1], xyz[2] - f.C[2]};
+    const double xa = dot(r, d.a), xn = dot(r, f.n), zb = dot(r, f.b);
+    *chainage = f.s0 + atan2(xa, -xn) / f.kappa;
+    const double yc = f.inv_kappa - sqrt(xa * xa + xn * xn);
+    *e = sqrt(yc * yc + zb * zb) - d.R;
+    const double th = atan2(yc * f.vn + zb * f.vb, yc * f.un + zb * f.ub);
+    *angle = th < 0.0 ? th + kTwoPi : th;
+    return GM_OK;
+}
+
+gm_status gm_wall_arc_point(const gm_wall_params *params, const gm_wall_arc *arc, double chainage, double angle, double rho,
+                            double xyz[3])
+{
+    DesignFrame d;
+    ArcFrame f;
+    if (!xyz || !isfinite(chainage) || !isfinite(angle) || !isfinite(rho) || arc_check(params, arc, d, f) != GM_OK)
+        return GM_ERR_INVALID_ARG;
+    const double psi = f.kappa * (chainage - f.s0);
+    const double cp = cos(psi), sp = sin(psi), c = cos(angle), s = sin(angle);
+    const double yc = rho * (c * f.un + s * f.vn), zb = rho * (c * f.ub + s * f.vb);
+    const double r = yc - f.inv_kappa;
+    for (int k = 0; k < 3; ++k) {
+        const double nr = f.n[k] * cp - d.a[k] * sp;
+        xyz[k] = (f.C[k] + r * nr) + zb * f.b[k];
+    }
+    return GM_OK;
 }
 
 void gm_wall_region_default_params(gm_wall_region_params *p)

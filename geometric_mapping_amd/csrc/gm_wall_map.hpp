@@ -41,6 +41,19 @@ inline double dot(const double *x, const double *y) { return x[0] * y[0] + x[1] 
 struct DesignFrame { double o[3], a[3], u[3], v[3], R; uint32_t status; };
 void design_frame_of(const gm_wall_params &p, DesignFrame &d);
 gm_status check_params(const gm_wall_params *p);
+// The arc design frame of include/gm_hip.h (fp64, not rounded) beside the DesignFrame at params.point.  kappa = 0: a
+// straight map, nothing else is set.
+struct ArcFrame { double kappa, inv_kappa, s0, n[3], b[3], C[3], un, ub, vn, vb; };
+// gm_wall_map_create_arc's refusals; d and f of an accepted pair
+gm_status arc_check(const gm_wall_params *p, const gm_wall_arc *arc, DesignFrame &d, ArcFrame &f);
+// the section at chainage s: a(s), n(s), P(s)
+void arc_section(const DesignFrame &d, const ArcFrame &f, double s, double as[3], double ns[3], double P[3]);
+// the chainage of a map point
+double arc_chainage(const DesignFrame &d, const ArcFrame &f, const double x[3]);
+// The per-add frame of an accepted (Rm, tr): everything but struct_size and status.  u64 / v64 (may be NULL): Rm^T u(s_f)
+// and Rm^T v(s_f) before the rounding; a1 (may be NULL): |a'|_1 before the rounding.  false: the anchor is out of range.
+bool arc_add_frame(const gm_wall_params &p, const DesignFrame &d, const ArcFrame &f, const double Rm[3][3], const double tr[3],
+                   gm_wall_arc_add_info &out, double *u64, double *v64, double *a1);
 // the library's pose check: 0 the pose is accepted (Rm, tr filled), 1 an entry is not finite, 2 Rm is not a rotation
 int pose_split(const double pose[12], double Rm[3][3], double tr[3]);
 // the direction table of include/gm_hip.h: NK pairs (one operation per statement, as stated there)
@@ -220,6 +233,9 @@ struct gm_wall_map {
     gm::DevArray<uint8_t> base;    // the device table (zeroed at creation)
     gm::WallTable table;
     gm::wall::DesignFrame frame;   // fp64, not rounded
+    gm_wall_arc arc;               // gm_wall_map_create_arc's (zero on a straight map)
+    gm::wall::ArcFrame af;         // af.kappa > 0: the design axis is an arc
+    bool is_arc() const { return af.kappa > 0.0; }
     uint64_t frames = 0;
     hipStream_t stream = nullptr;  // the small kernels (read / merge / clear / count) and their copies
     std::vector<uint8_t> pending;  // per slot of ctx: an add was enqueued on its stream since the last sync
@@ -243,6 +259,8 @@ struct gm_wall_map {
     gm::DevArray<unsigned long long> cl_ctr;      // [kWallCloudCounters]
     gm::DevArray<double> cl_dirs;      // [GM_WALL_MAX_SECTORS][2]
     std::vector<double> cl_dirs_host;          // the table of the call in progress
+    gm::DevArray<double> cl_rows;      // an arc map: [block rows of a chunk][2] cos psi, sin psi
+    std::vector<double> cl_rows_host;
     // gm_wall_map_mesh: its vertex pass runs on the cloud's scratch above; its own
     gm::DevArray<uint32_t> ms_rank;    // [NJ * NK] of the window: a block's vertex index, kWallMeshDead otherwise
     gm::DevArray<float> ms_mean;       // [NJ * NK]: the vertices' means (a call with a step cut only)
@@ -329,7 +347,12 @@ inline void frame_points(const gm_ctx *ctx, const Slot &sl, WallArgs &w)
 // buffers.  The context's crop bound (a cube around the sensor) sizes the LDS window.
 // f64 (a locate's start): the same vectors before the rounding, and o_f in map coordinates.
 struct WallFrame64 { double c[3], d[3], u[3], v[3], of[3]; };
-gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info *info, WallArgs &w, WallFrame64 *f64 = nullptr);
+// arc: what the arc kernels take beside w.  An arc map refuses a caller without one (a locate, an align) with
+// GM_ERR_UNSUPPORTED; a straight map leaves it alone.
+gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info *info, WallArgs &w, WallFrame64 *f64 = nullptr,
+                         WallArc *arc = nullptr);
+// the add and the check of a map, straight or arc (arc: add_frame_args')
+void launch_add(gm_wall_map *m, const WallArgs &w, const WallArc &arc, uint32_t n_cap, hipStream_t s);
 // An add on `s` (the stream of `slot`) must not be seen by a reader -- a check, a locate, an align -- enqueued before it
 // on another slot: `s` waits for every result outstanding there (nothing to wait for on a map without readers).
 gm_status add_wait_readers(gm_wall_map *m, uint32_t slot, hipStream_t s);

@@ -56,8 +56,16 @@ struct WallMask<true> {
     unsigned long long *ctr;           // [kWallAddCheckedCounters]
 };
 
-template <bool kMasked>
-__device__ __forceinline__ void wall_add(const WallArgs a, const WallMask<kMasked> m)
+// kArc (a map of gm_wall_map_create_arc): the per-point chain is arc_residual / arc_sector (gm_device.hpp) on the by-value
+// WallArc; everything behind (e, t, k) -- classes, window, run merge, flush -- is shared.  The straight instantiations
+// carry none of it, and the arc ones have entry points of their own below.
+template <bool kArc>
+struct WallArcArg {};
+template <>
+struct WallArcArg<true> { WallArc arc; };
+
+template <bool kMasked, bool kArc>
+__device__ __forceinline__ void wall_add(const WallArgs a, const WallMask<kMasked> m, const WallArcArg<kArc> c)
 {
     constexpr int kCls = kMasked ? 5 : 4;
     __shared__ unsigned long long s_sum[kWallCells];
@@ -114,9 +122,10 @@ __device__ __forceinline__ void wall_add(const WallArgs a, const WallMask<kMaske
                 if (lab[k] == 1u) {
                     cls[3] += live;
                 } else {
-                    float t, wx, wy, wz;
-                    e = surf_residual(q[k], a.o, a.a, a.R, t, wx, wy, wz);
-                    if (!(fabsf(e) <= a.gate)) {
+                    float t, wx, wy, wz;   // (kArc: wx = yc, wy = z, wz = cy)
+                    if constexpr (kArc) e = arc_residual(q[k], a.o, a.a, c.arc.n, c.arc.b, c.arc.kappa, a.R, t, wx, wy, wz);
+                    else e = surf_residual(q[k], a.o, a.a, a.R, t, wx, wy, wz);
+                    if (!(fabsf(e) <= a.gate) || (kArc && !(wz > 0.0f))) {
                         cls[2] += live;
                     } else {
                         const float jl = surf_station(t, 0.0f, a.station_length);   // relative to the anchor
@@ -125,7 +134,10 @@ __device__ __forceinline__ void wall_add(const WallArgs a, const WallMask<kMaske
                         if (!(j >= 0 && j < nst)) {
                             cls[1] += live;
                         } else {
-                            const uint32_t kk = surf_sector(wx, wy, wz, a.u, a.v, a.two_pi, a.sector_angle, nsec);
+                            uint32_t kk;
+                            if constexpr (kArc)
+                                kk = arc_sector(wx, wy, c.arc.un, c.arc.ub, c.arc.vn, c.arc.vb, a.two_pi, a.sector_angle, nsec);
+                            else kk = surf_sector(wx, wy, wz, a.u, a.v, a.two_pi, a.sector_angle, nsec);
                             cell = (int)((uint32_t)j * nsec + kk);
                             if (jl >= win_lo && jl < win_hi) lcell = (int)((uint32_t)((int32_t)jl - a.win_first) * nsec + kk);
                             cls[0] += live;
@@ -182,8 +194,22 @@ __device__ __forceinline__ void wall_add(const WallArgs a, const WallMask<kMaske
     }
 }
 
-__global__ __launch_bounds__(kWallThreads) void k_wall_add(WallArgs a) { wall_add<false>(a, WallMask<false>()); }
-__global__ __launch_bounds__(kWallThreads) void k_wall_add_masked(WallArgs a, WallMask<true> m) { wall_add<true>(a, m); }
+__global__ __launch_bounds__(kWallThreads) void k_wall_add(WallArgs a)
+{
+    wall_add<false, false>(a, WallMask<false>(), WallArcArg<false>());
+}
+__global__ __launch_bounds__(kWallThreads) void k_wall_add_masked(WallArgs a, WallMask<true> m)
+{
+    wall_add<true, false>(a, m, WallArcArg<false>());
+}
+__global__ __launch_bounds__(kWallThreads) void k_wall_add_arc(WallArgs a, WallArcArg<true> c)
+{
+    wall_add<false, true>(a, WallMask<false>(), c);
+}
+__global__ __launch_bounds__(kWallThreads) void k_wall_add_arc_masked(WallArgs a, WallMask<true> m, WallArcArg<true> c)
+{
+    wall_add<true, true>(a, m, c);
+}
 
 // ---- the small kernels: convert / copy out a window, merge a raw window, clear, count ----
 
@@ -292,6 +318,19 @@ void launch_wall_add_masked(const WallArgs &a, const unsigned long long *mask, u
     m.words = mask;
     m.ctr = ctr;
     hipLaunchKernelGGL(k_wall_add_masked, dim3(wall_blocks(n_cap, points_per_block)), dim3(kWallThreads), 0, s, a, m);
+}
+void launch_wall_add_arc(const WallArgs &a, const WallArc &arc, uint32_t n_cap, uint32_t points_per_block, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_wall_add_arc, dim3(wall_blocks(n_cap, points_per_block)), dim3(kWallThreads), 0, s, a, WallArcArg<true>{arc});
+}
+void launch_wall_add_arc_masked(const WallArgs &a, const WallArc &arc, const unsigned long long *mask, unsigned long long *ctr,
+                                uint32_t n_cap, uint32_t points_per_block, hipStream_t s)
+{
+    WallMask<true> m;
+    m.words = mask;
+    m.ctr = ctr;
+    hipLaunchKernelGGL(k_wall_add_arc_masked, dim3(wall_blocks(n_cap, points_per_block)), dim3(kWallThreads), 0, s, a, m,
+                       WallArcArg<true>{arc});
 }
 void launch_wall_read(const WallTable &T, uint64_t first, uint64_t n, gm_surface_cell *out, hipStream_t s)
 {

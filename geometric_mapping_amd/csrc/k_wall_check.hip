@@ -36,61 +36,76 @@ __device__ __forceinline__ unsigned long long *wk_peaks()
     return p;
 }
 
-struct WallCheckPred {
-    WallCheckArgs a;
-    struct Payload { float4 q; long long delta; float e; int cell; };
-    __device__ __forceinline__ bool operator()(uint32_t i, Payload &p) const
-    {
-        const WallArgs &w = a.w;
-        p.q = w.pts[i];
-        const uint32_t lab = w.labels ? w.labels[i] : 0u;
-        if (i == 0u) a.ctr[10] = w.n_ptr ? *w.n_ptr : w.n_host;   // n_points (>= 1 here; the caller's zero stands for 0)
-        float e = __builtin_nanf("");
-        int cell = -1;
-        long long delta = 0;
-        uint32_t cls;
-        if (lab == 1u) {
-            cls = GM_WALL_CHECK_CLS_PLANE;
+// the predicate's body; kArc (a map of gm_wall_map_create_arc): k_wall_add_arc's chain on the by-value WallArc
+struct WallCheckPayload { float4 q; long long delta; float e; int cell; };
+template <bool kArc, class Arc>
+__device__ __forceinline__ bool wall_check_point(const WallCheckArgs &a, const Arc &arc, uint32_t i, WallCheckPayload &p)
+{
+    const WallArgs &w = a.w;
+    p.q = w.pts[i];
+    const uint32_t lab = w.labels ? w.labels[i] : 0u;
+    if (i == 0u) a.ctr[10] = w.n_ptr ? *w.n_ptr : w.n_host;   // n_points (>= 1 here; the caller's zero stands for 0)
+    float e = __builtin_nanf("");
+    int cell = -1;
+    long long delta = 0;
+    uint32_t cls;
+    if (lab == 1u) {
+        cls = GM_WALL_CHECK_CLS_PLANE;
+    } else {
+        float t, wx, wy, wz;   // (kArc: wx = yc, wy = z, wz = cy)
+        if constexpr (kArc) e = arc_residual(p.q, w.o, w.a, arc.n, arc.b, arc.kappa, w.R, t, wx, wy, wz);
+        else e = surf_residual(p.q, w.o, w.a, w.R, t, wx, wy, wz);
+        if (!(fabsf(e) <= w.gate) || (kArc && !(wz > 0.0f))) {
+            cls = GM_WALL_CHECK_CLS_BEYOND_GATE;
         } else {
-            float t, wx, wy, wz;
-            e = surf_residual(p.q, w.o, w.a, w.R, t, wx, wy, wz);
-            if (!(fabsf(e) <= w.gate)) {
-                cls = GM_WALL_CHECK_CLS_BEYOND_GATE;
+            const float jl = surf_station(t, 0.0f, w.station_length);   // relative to the anchor
+            const int64_t j = fabsf(jl) < 4.0e18f ? w.anchor + (int64_t)jl : -1;
+            if (!(j >= 0 && j < (int64_t)w.n_stations)) {
+                cls = GM_WALL_CHECK_CLS_OUTSIDE;
             } else {
-                const float jl = surf_station(t, 0.0f, w.station_length);   // relative to the anchor
-                const int64_t j = fabsf(jl) < 4.0e18f ? w.anchor + (int64_t)jl : -1;
-                if (!(j >= 0 && j < (int64_t)w.n_stations)) {
-                    cls = GM_WALL_CHECK_CLS_OUTSIDE;
-                } else {
-                    const uint32_t kk = surf_sector(wx, wy, wz, w.u, w.v, w.two_pi, w.sector_angle, w.n_sectors);
-                    cell = (int)((uint32_t)j * w.n_sectors + kk);   // < n_stations * n_sectors <= 2^24
-                    const uint32_t cn = w.table.cnt[cell];
-                    long long sum = 0;
-                    uint32_t lo = 0u, hi = 0u;
-                    if (cn >= a.min_count) {
-                        if (a.reference == GM_WALL_CHECK_ENVELOPE) { lo = w.table.lo[cell]; hi = w.table.hi[cell]; }
-                        else sum = (long long)w.table.sum[cell];
-                    }
-                    cls = wall_check_rule(a.reference, a.min_count, a.T, sum, cn, lo, hi, e, delta);
+                uint32_t kk;
+                if constexpr (kArc) kk = arc_sector(wx, wy, arc.un, arc.ub, arc.vn, arc.vb, w.two_pi, w.sector_angle, w.n_sectors);
+                else kk = surf_sector(wx, wy, wz, w.u, w.v, w.two_pi, w.sector_angle, w.n_sectors);
+                cell = (int)((uint32_t)j * w.n_sectors + kk);   // < n_stations * n_sectors <= 2^24
+                const uint32_t cn = w.table.cnt[cell];
+                long long sum = 0;
+                uint32_t lo = 0u, hi = 0u;
+                if (cn >= a.min_count) {
+                    if (a.reference == GM_WALL_CHECK_ENVELOPE) { lo = w.table.lo[cell]; hi = w.table.hi[cell]; }
+                    else sum = (long long)w.table.sum[cell];
                 }
+                cls = wall_check_rule(a.reference, a.min_count, a.T, sum, cn, lo, hi, e, delta);
             }
         }
-        if (w.res) w.res[i] = e;
-        if (w.cell) w.cell[i] = cell;
-        if (a.delta) a.delta[i] = delta > 2147483647ll ? 2147483647 : (delta < -2147483648ll ? (int32_t)(-2147483647 - 1) : (int32_t)delta);
-        if (a.cls) a.cls[i] = (uint8_t)cls;
-        p.e = e;
-        p.cell = cell;
-        p.delta = delta;
-        // (the lanes past the end of the input are not here: the ballots see the active lanes only)
-        const int lane = lane_id();
-#pragma unroll
-        for (uint32_t k = 0; k < (uint32_t)GM_WALL_CHECK_N_CLS; ++k) {
-            const unsigned long long m = __ballot(cls == k);
-            if (m && lane == (int)__builtin_ctzll(m)) atomicAdd(&wk_class_counts()[k], (uint32_t)__popcll(m));
-        }
-        return cls >= (uint32_t)GM_WALL_CHECK_CLS_CHANGED_POS;
     }
+    if (w.res) w.res[i] = e;
+    if (w.cell) w.cell[i] = cell;
+    if (a.delta) a.delta[i] = delta > 2147483647ll ? 2147483647 : (delta < -2147483648ll ? (int32_t)(-2147483647 - 1) : (int32_t)delta);
+    if (a.cls) a.cls[i] = (uint8_t)cls;
+    p.e = e;
+    p.cell = cell;
+    p.delta = delta;
+    // (the lanes past the end of the input are not here: the ballots see the active lanes only)
+    const int lane = lane_id();
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)GM_WALL_CHECK_N_CLS; ++k) {
+        const unsigned long long m = __ballot(cls == k);
+        if (m && lane == (int)__builtin_ctzll(m)) atomicAdd(&wk_class_counts()[k], (uint32_t)__popcll(m));
+    }
+    return cls >= (uint32_t)GM_WALL_CHECK_CLS_CHANGED_POS;
+}
+
+struct WallNoArc {};
+struct WallCheckPred {
+    WallCheckArgs a;
+    using Payload = WallCheckPayload;
+    __device__ __forceinline__ bool operator()(uint32_t i, Payload &p) const { return wall_check_point<false>(a, WallNoArc(), i, p); }
+};
+struct WallCheckPredArc {
+    WallCheckArgs a;
+    WallArc arc;
+    using Payload = WallCheckPayload;
+    __device__ __forceinline__ bool operator()(uint32_t i, Payload &p) const { return wall_check_point<true>(a, arc, i, p); }
 };
 
 struct WallCheckEmit {
@@ -144,6 +159,16 @@ void launch_wall_check(const WallCheckArgs &a, uint32_t n_cap, const ScanState &
     emit.a = a;
     hipLaunchKernelGGL((k_compact<WallCheckPred, WallCheckEmit>), dim3(compact_grid(n_cap ? n_cap : 1u)), dim3(kCpThreads), 0, s, pred,
                        emit, a.w.n_ptr, a.w.n_host, st, reinterpret_cast<uint32_t *>(a.ctr + 9), (uint32_t *)nullptr);
+}
+
+void launch_wall_check_arc(const WallCheckArgs &a, const WallArc &arc, uint32_t n_cap, const ScanState &st, hipStream_t s)
+{
+    WallCheckPredArc pred{a, arc};
+    WallCheckEmit emit;
+    memset(&emit, 0, sizeof(emit));
+    emit.a = a;
+    hipLaunchKernelGGL((k_compact<WallCheckPredArc, WallCheckEmit>), dim3(compact_grid(n_cap ? n_cap : 1u)), dim3(kCpThreads), 0, s,
+                       pred, emit, a.w.n_ptr, a.w.n_host, st, reinterpret_cast<uint32_t *>(a.ctr + 9), (uint32_t *)nullptr);
 }
 
 }  // namespace gm

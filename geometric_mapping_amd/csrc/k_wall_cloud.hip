@@ -112,4 +112,13 @@ void launch_wall_cloud_compact(const WallCloudArgs &a, const ScanState &st, hipS
                        (const uint32_t *)nullptr, nb, st, reinterpret_cast<uint32_t *>(a.ctr + 2), (uint32_t *)nullptr);
 }
 
+void launch_wall_cloud_compact_arc(const WallCloudArgs &a, const WallCloudArc &arc, const ScanState &st, hipStream_t s)
+{
+    const uint32_t nb = a.nJ * a.NK;   // >= 1
+    WallCloudPred pred{a};
+    WallCloudEmitArc emit{a, WallCloudOnArc{arc}};
+    hipLaunchKernelGGL((k_compact<WallCloudPred, WallCloudEmitArc>), dim3(compact_grid(nb)), dim3(kCpThreads), 0, s, pred, emit,
+                       (const uint32_t *)nullptr, nb, st, reinterpret_cast<uint32_t *>(a.ctr + 2), (uint32_t *)nullptr);
+}
+
 }  // namespace gm

@@ -26,9 +26,12 @@ static_assert(sizeof(gm_wall_mesh_triangle) == 12, "three indices");
 
 // ---- 1. vertices ----
 
-struct WallMeshVertexEmit {
+// (CloudEmit: WallCloudEmit, or WallCloudEmitArc on a map of gm_wall_map_create_arc; the straight one is not a template
+// specialisation, so that its kernel keeps its name)
+template <class CloudEmit>
+struct WallMeshVertexEmitT {
     static constexpr bool kHasFinish = true, kHasPrepare = true;
-    WallCloudEmit cloud;
+    CloudEmit cloud;
     uint32_t *rank;        // [NJ * NK] of the window
     float *mean;           // [NJ * NK] or nullptr
     uint32_t rank_base;    // the vertices of the chunks before this one
@@ -42,6 +45,9 @@ struct WallMeshVertexEmit {
         if (mean) mean[block] = cloud.a.out[dst].mean;          // (the value this thread has just stored)
     }
 };
+
+struct WallMeshVertexEmit : WallMeshVertexEmitT<WallCloudEmit> {};
+struct WallMeshVertexEmitArc : WallMeshVertexEmitT<WallCloudEmitArc> {};
 
 // ---- 2. triangles ----
 
@@ -130,8 +136,18 @@ void launch_wall_mesh_vertices(const WallCloudArgs &a, uint32_t *rank, float *me
 {
     const uint32_t nb = a.nJ * a.NK;   // >= 1
     WallCloudPred pred{a};
-    WallMeshVertexEmit emit{WallCloudEmit{a}, rank, mean, rank_base};
+    WallMeshVertexEmit emit{{WallCloudEmit{a}, rank, mean, rank_base}};
     hipLaunchKernelGGL((k_compact<WallCloudPred, WallMeshVertexEmit>), dim3(compact_grid(nb)), dim3(kCpThreads), 0, s, pred, emit,
+                       (const uint32_t *)nullptr, nb, st, reinterpret_cast<uint32_t *>(a.ctr + 2), (uint32_t *)nullptr);
+}
+
+void launch_wall_mesh_vertices_arc(const WallCloudArgs &a, const WallCloudArc &arc, uint32_t *rank, float *mean, uint32_t rank_base,
+                                   const ScanState &st, hipStream_t s)
+{
+    const uint32_t nb = a.nJ * a.NK;   // >= 1
+    WallCloudPred pred{a};
+    WallMeshVertexEmitArc emit{{WallCloudEmitArc{a, WallCloudOnArc{arc}}, rank, mean, rank_base}};
+    hipLaunchKernelGGL((k_compact<WallCloudPred, WallMeshVertexEmitArc>), dim3(compact_grid(nb)), dim3(kCpThreads), 0, s, pred, emit,
                        (const uint32_t *)nullptr, nb, st, reinterpret_cast<uint32_t *>(a.ctr + 2), (uint32_t *)nullptr);
 }
 

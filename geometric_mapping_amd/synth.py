@@ -236,6 +236,64 @@ def tunnel_drive(n_frames, n_points, seed=0, radius=2.0, length=48.0, start=6.0,
     return dict(frames=frames, design=design, patches=tuple(patches), sigma=sigma, length=length)
 
 
+def arc_sections(t, arc_radius, toward):
+    """The sections of the arc design axis of arc_drive at chainages t [n]: (P, a, u, v), float64 [n, 3] each.  The axis
+    starts at the origin along +x with up = +z and turns toward `toward` (made perpendicular to x) at 1 / arc_radius:
+    a(s) = a cos psi + n sin psi, n(s) = n cos psi - a sin psi, P(s) = C - arc_radius n(s), psi = s / arc_radius; u and v
+    turn with the section about b = a x n."""
+    t = np.asarray(t, np.float64).reshape(-1)
+    a = np.array([1.0, 0.0, 0.0])
+    n = np.asarray(toward, np.float64) - np.dot(toward, a) * a
+    n = n / np.linalg.norm(n)
+    b = np.cross(a, n)
+    u0, v0 = np.array([0.0, 0.0, 1.0]), np.array([0.0, -1.0, 0.0])
+    psi = t / float(arc_radius)
+    c, s = np.cos(psi)[:, None], np.sin(psi)[:, None]
+    a_s = a * c + n * s
+    n_s = n * c - a * s
+    P = arc_radius * n - arc_radius * n_s
+    u = (u0 @ n) * n_s + (u0 @ b) * b
+    v = (v0 @ n) * n_s + (v0 @ b) * b
+    return P, a_s, u, v
+
+
+def arc_drive(n_frames, n_points, arc_radius=80.0, toward=(0.0, 1.0, 0.0), seed=0, radius=2.0, length=48.0, start=6.0,
+              step=3.5, reach=7.0, sigma=0.01, patches=DRIVE_PATCHES, yaw_deg=4.0, roll_deg=3.0, lateral=0.25, texture=None):
+    """tunnel_drive on a curved tube, for a wall map on a circular-arc design axis (gm_wall_map_create_arc).  The design
+    axis starts at the world origin along +x (chainage 0, up = +z) and is a circle of `arc_radius` whose centre lies
+    toward `toward` from the origin: (0, 1, 0) a horizontal curve to the left, (0, 0, +-1) a vertical curve, anything
+    else perpendicular to x an oblique plane of curvature.  Patches and texture stay in (chainage, phi), phi in the
+    section's own (u(s), v(s)); the sensor rides the axis: its pose is the section's frame at chainage start + i step
+    times tunnel_drive's yaw / roll, offset laterally in the section.  The draws are tunnel_drive's, in its order.  Returns
+    tunnel_drive's dict plus arc=dict(curvature, point_chainage) for GeometricMapping.wall_map(arc=...)."""
+    rng = np.random.default_rng(seed)
+    frames = []
+    for i in range(n_frames):
+        s = start + i * step
+        ly, lz = rng.uniform(-lateral, lateral), rng.uniform(-lateral, lateral)
+        local = pose_matrix((0.0, 0.0, 0.0), yaw_deg=rng.uniform(-yaw_deg, yaw_deg), roll_deg=rng.uniform(-roll_deg, roll_deg))
+        P, a_s, u_s, v_s = (x[0] for x in arc_sections([s], arc_radius, toward))
+        F = np.stack([a_s, -v_s, u_s], axis=1)   # the section as a sensor frame: x forward, y left, z up
+        pose = np.concatenate([F @ local[:, :3], (P - ly * v_s + lz * u_s).reshape(3, 1)], axis=1)
+        t = rng.uniform(max(0.0, s - reach), min(length, s + reach), n_points)
+        phi = rng.uniform(0.0, 2 * np.pi, n_points)
+        rr = radius + rng.normal(0.0, sigma, n_points)
+        deg = np.rad2deg(phi)
+        for t0, t1, p0, p1, dr in patches:
+            rr = np.where((t >= t0) & (t < t1) & (deg >= p0) & (deg < p1), rr + dr, rr)
+        if texture is not None:
+            rr = rr + wall_texture(t, phi, **texture)
+        Pt, _, ut, vt = arc_sections(t, arc_radius, toward)
+        world = Pt + (rr * np.cos(phi))[:, None] * ut + (rr * np.sin(phi))[:, None] * vt
+        sensor = (world - pose[:, 3]) @ pose[:, :3]   # Rm^T (p - tr)
+        frames.append((np.ascontiguousarray(sensor, dtype=np.float32), pose))
+    design = dict(point=(0.0, 0.0, 0.0), direction=(1.0, 0.0, 0.0), radius=float(radius), up=(0.0, 0.0, 1.0),
+                  forward=(1.0, 0.0, 0.0))
+    n = np.asarray(toward, np.float64) - np.array([float(toward[0]), 0.0, 0.0])
+    arc = dict(curvature=tuple(n / np.linalg.norm(n) / float(arc_radius)), point_chainage=0.0)
+    return dict(frames=frames, design=design, arc=arc, patches=tuple(patches), sigma=sigma, length=length)
+
+
 def drop_row_padding(msg):
     """What the node does with an organised cloud whose rows are padded (ros/geometric_mapping_node.cpp): the C ABI takes
     point_step-strided rows, so the row_step padding is dropped once on the host.  Returns the packed uint8 rows."""

@@ -367,11 +367,13 @@ void Processor::getSurfaceMap(gm_surface_info &info, std::vector<gm_surface_cell
     if (s != GM_OK) throw Error(s, std::string("getSurfaceMap: ") + gm_status_string(s) + ": " + gm_last_error(cur_));
 }
 
-void Processor::createWallMap(const gm_wall_params &params)
+void Processor::createWallMap(const gm_wall_params &params) { createWallMap(params, 0); }
+
+void Processor::createWallMap(const gm_wall_params &params, const gm_wall_arc *arc)
 {
     if (grp_) throw Error(GM_ERR_UNSUPPORTED, "createWallMap: a wall map belongs to one context (single-device Processor)");
     gm_wall_map *m = 0;
-    check(gm_wall_map_create(ctx_, &params, &m), "createWallMap");
+    check(arc ? gm_wall_map_create_arc(ctx_, &params, arc, &m) : gm_wall_map_create(ctx_, &params, &m), "createWallMap");
     if (wall_) gm_wall_map_destroy(wall_);
     wall_ = m;
     check_slot_ = -1;

@@ -138,6 +138,9 @@ public:
     // Persistent wall map (gm_wall_*, include/gm_hip.h): one map against a design cylinder, owned by the processor's
     // context (single device; GM_ERR_UNSUPPORTED with several).  createWallMap replaces the map of an earlier call.
     void createWallMap(const gm_wall_params &params);
+    // the same on a circular-arc design axis (gm_wall_map_create_arc): one map per alignment element, straight or arc.
+    // locateWallMap and alignWallMap throw GM_ERR_UNSUPPORTED on such a map.
+    void createWallMap(const gm_wall_params &params, const gm_wall_arc *arc);
     // adds the frame just processed or submitted (the newest one) under pose = row-major 3x4 [R | t], sensor -> map.
     // Enqueued behind the frame's work: call it right after submitFrame, or after processFrame / waitFrame.
     gm_wall_add_info addToWallMap(const double pose[12]);

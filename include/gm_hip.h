@@ -1771,6 +1771,87 @@ gm_status gm_wall_map_add_points_checked(gm_wall_map *map, const float *xyz, uin
                                          const gm_wall_check_point *rows, uint32_t n_rows, gm_wall_add_info *add_info,
                                          gm_wall_add_checked_info *info, float *residual, int32_t *cell);
 
+/* ---- a wall map on a circular-arc design axis (gm_wall_map_create_arc) -------------------------------------------------
+ * The design axis of such a map is a circular arc of constant curvature in any plane that holds the design direction:
+ * horizontal curves, vertical curves (portal ramps) and oblique ones.  An alignment is one map per alignment element,
+ * straight (gm_wall_map_create) or circular arc; clothoids are not covered.  The table, its cells and every cell-space
+ * product are those of a straight map: only the per-point chain and the position rule of the cloud and the mesh see the
+ * axis.  One operation per statement; fp64 on the host, not rounded, unless a rounding is named.
+ *   design frame  (a, u, v, R) of the straight map's rule above, valid AT params.point, which lies on the axis at chainage
+ *                 s0 = point_chainage.  c = curvature - (curvature.a) a;  kappa = |c|;  n = c / kappa;  b = a x n;
+ *                 C = point + n / kappa (the centre);  un = u.n, ub = u.b, vn = v.n, vb = v.b (u and v turn with the
+ *                 section about b, so the four are constants of the map).  At chainage s, psi = kappa (s - s0):
+ *                 a(s) = a cos psi + n sin psi;  n(s) = n cos psi - a sin psi;  P(s) = C - n(s) / kappa;
+ *                 u(s) = un n(s) + ub b;  v(s) = vn n(s) + vb b.
+ *   refusals      GM_ERR_INVALID_ARG: a curvature entry or point_chainage not finite; kappa < 1e-6 (a flatter curve is a
+ *                 straight map); (R + gate) kappa > 0.5; |kappa (t_min - s0)| > 3 or |kappa (t_min + n_stations ds - s0)| > 3.
+ *   chainage of x r = x - C;  psi = atan2(r.a, -(r.n));  s = s0 + psi / kappa.
+ *   per add       host, fp64.  The pose check of the straight rule.  Sensor chainage s = the chainage of tr; anchor station
+ *                 j_f = floor((s - t_min) / ds) as above; s_f = t_min + j_f ds; psi_f = kappa (s_f - s0).  In sensor
+ *                 coordinates o' = Rm^T (P(s_f) - tr), a' = Rm^T a(s_f), n' = Rm^T n(s_f), b' = Rm^T b, each rounded to
+ *                 fp32 once; kappa, un, ub, vn, vb, R, ds, gate and dtheta rounded to fp32 once: gm_wall_arc_add_info
+ *                 (gm_wall_arc_add_frame, host only).  The adds still fill gm_wall_add_info, with u' = Rm^T u(s_f) and
+ *                 v' = Rm^T v(s_f) rounded to fp32 once; the device does not read those two.
+ *   per point     device, fp32, every operation rounded to nearest (dot products as the chain above: x = fma(qx, a'x,
+ *                 fma(qy, a'y, qz a'z))):
+ *                   q = p - o';  x = q.a';  y = q.n';  z = q.b'
+ *                   cx = kappa x;  cy = fma(-kappa, y, 1);  d = sqrt(fma(cx, cx, cy cy))
+ *                   t = atan2f(cx, cy) / kappa
+ *                   h = fma(x, x, y y);  yc = fma(-kappa, h, y + y) / (1 + d)      (= (1 - d) / kappa without the cancellation)
+ *                   e = sqrt(fma(yc, yc, z z)) - R
+ *                   phi = atan2f(fma(yc, vn, z vb), fma(yc, un, z ub)), folded to [0, 2 pi) and binned as above
+ *                   j = j_f + floor(t / ds)
+ *   classes       as above; in addition a point with cy <= 0 (a quarter turn or more from the anchor section) is beyond_gate.
+ *   cloud, mesh   fp64 with the roundings of gm_wall_map_cloud's rule, (c, s) the block's entry of its direction table and
+ *                 (cp, sp) = (cos, sin) of psi = kappa (tc - s0) for the block row's centre chainage tc, computed on the
+ *                 host per block row:  yc = rho (c un + s vn);  zb = rho (c ub + s vb);  r = yc - 1 / kappa;
+ *                 nr_i = n_i cp - a_i sp;  p_i = ((C_i - anchor_i) + r nr_i) + zb b_i, rounded to fp32 once.
+ * gm_wall_map_locate_* and gm_wall_map_align_* return GM_ERR_UNSUPPORTED on an arc map: their Jacobians and the "move
+ * along the axis" pose assume a straight axis.  The window calls (read, read_raw, add_raw, clear, info, regions,
+ * clearance, sections, quantities) are unchanged; a baseline must be a map with a bitwise-equal arc (two straight maps
+ * included), else GM_ERR_INVALID_ARG.  The *_metrics helpers stay centreline values: a cell's true area differs from
+ * theirs by the factor 1 - kappa yc. */
+typedef struct gm_wall_arc {
+    uint32_t struct_size;      /* = sizeof(gm_wall_arc) */
+    uint32_t reserved;         /* 0 */
+    double   curvature[3];     /* map coordinates: points from the axis at `point` toward the centre of curvature,
+                                  |.| = 1 / (radius of the axis); its component along the design direction is removed */
+    double   point_chainage;   /* chainage of params.point, finite */
+} gm_wall_arc;
+
+typedef struct gm_wall_arc_add_info {   /* 120 bytes */
+    uint32_t struct_size;      /* = sizeof(gm_wall_arc_add_info), filled by the library */
+    uint32_t status;           /* GM_SURF_OK or GM_SURF_UP_FALLBACK: the design frame's */
+    int64_t  anchor_station;   /* j_f */
+    double   sensor_chainage;  /* s */
+    double   anchor_chainage;  /* s_f */
+    float    o[3], a[3], n[3], b[3];   /* o', a', n', b' in SENSOR coordinates (fp32, as binned with) */
+    float    kappa, un, ub, vn, vb;
+    float    R, station_length, sector_angle, gate;
+    uint32_t reserved;         /* 0 */
+} gm_wall_arc_add_info;
+
+/* gm_wall_map_create with the arc.  GM_ERR_INVALID_ARG also for a NULL arc, a struct_size mismatch and the refusals above. */
+gm_status gm_wall_map_create_arc(gm_ctx *ctx, const gm_wall_params *params, const gm_wall_arc *arc, gm_wall_map **map);
+/* The map's arc; curvature 0 and point_chainage 0 on a straight map.  GM_ERR_INVALID_ARG: NULL. */
+gm_status gm_wall_map_get_arc(gm_wall_map *map, gm_wall_arc *arc);
+/* Host only, no context: the four below restate the rules above in fp64 for callers and tests.  GM_ERR_INVALID_ARG: NULL,
+ * struct_size mismatch, params or arc refused by gm_wall_map_create_arc, an input that is not finite, a refused pose. */
+gm_status gm_wall_arc_check_params(const gm_wall_params *params, const gm_wall_arc *arc);
+/* The per-add frame of `pose`. */
+gm_status gm_wall_arc_add_frame(const gm_wall_params *params, const gm_wall_arc *arc, const double pose[12],
+                                gm_wall_arc_add_info *info);
+/* The design frame at `chainage`: o = P(s), a(s), u(s), v(s).  It is (point, direction, up) of the NEXT element's map. */
+gm_status gm_wall_arc_frame(const gm_wall_params *params, const gm_wall_arc *arc, double chainage, double o[3], double a[3],
+                            double u[3], double v[3]);
+/* A map point's chainage, angle phi in [0, 2 pi) and residual e: r = x - C; xa = r.a, xn = r.n, zb = r.b;
+ * yc = 1 / kappa - sqrt(xa xa + xn xn); e = sqrt(yc yc + zb zb) - R; phi = atan2(yc vn + zb vb, yc un + zb ub). */
+gm_status gm_wall_arc_project(const gm_wall_params *params, const gm_wall_arc *arc, const double xyz[3], double *chainage,
+                              double *angle, double *e);
+/* The map point at (chainage, angle, rho = R + e): the cloud's position rule with anchor 0 and (c, s) = (cos, sin) angle. */
+gm_status gm_wall_arc_point(const gm_wall_params *params, const gm_wall_arc *arc, double chainage, double angle, double rho,
+                            double xyz[3]);
+
 /* "Compressed map" record of a completed slot.  The reference defines no such
  * output; this is a build-defined format: header, primitive records,
  * then n_voxels rows of x,y,z,count (float32).  Returns the bytes needed in
