@@ -296,6 +296,48 @@ __device__ __forceinline__ uint32_t arc_sector(float yc, float z, float un, floa
     const uint32_t kk = (uint32_t)floorf(__fdiv_rn(phi, sector_angle));
     return kk < nsec - 1u ? kk : nsec - 1u;
 }
+// A map on a circular-arc design axis (gm_wall_map_create_arc): what the arc instantiations take by value beside WallArgs
+// (gm_internal.hpp), whose o, a are then o', a' at the anchor section (u, v are reported, not read).
+struct WallArc {
+    float n[3], b[3];          // n', b' in sensor coordinates
+    float kappa, un, ub, vn, vb;
+};
+// the arc as a kernel argument: nothing on a straight map
+template <bool kArc>
+struct WallArcArg {};
+template <>
+struct WallArcArg<true> { WallArc arc; };
+
+// ---- the head of the chain against a map (k_wall_add*, the check's predicate, k_wall_align_bin): label, residual, gate,
+// station relative to the anchor, range, sector.  w: the WallArgs.  in_range(jl) is the caller's range rule (the map's
+// stations by wall_station, an align's patch rows); the sector, and its atan2f, is computed only for a point that passed
+// gate and range.  The point's class goes to count(a literal kChain*); returns whether it is kChainMapped.  e is set
+// unless the point is plane, jl from kChainOutside on, kk for kChainMapped.
+enum : uint32_t { kChainPlane = 0u, kChainBeyondGate = 1u, kChainOutside = 2u, kChainMapped = 3u };
+template <bool kArc, class Args, class InRange, class Count>
+__device__ __forceinline__ bool wall_chain(const float4 &q, uint32_t lab, const Args &w, const WallArcArg<kArc> &c, InRange in_range,
+                                           Count count, float &e, float &jl, uint32_t &kk)
+{
+    if (lab == 1u) { count(kChainPlane); return false; }
+    float t, wx, wy, wz;   // (kArc: wx = yc, wy = z, wz = cy)
+    if constexpr (kArc) e = arc_residual(q, w.o, w.a, c.arc.n, c.arc.b, c.arc.kappa, w.R, t, wx, wy, wz);
+    else e = surf_residual(q, w.o, w.a, w.R, t, wx, wy, wz);
+    if (!(fabsf(e) <= w.gate) || (kArc && !(wz > 0.0f))) { count(kChainBeyondGate); return false; }
+    jl = surf_station(t, 0.0f, w.station_length);
+    if (!in_range(jl)) { count(kChainOutside); return false; }
+    if constexpr (kArc) kk = arc_sector(wx, wy, c.arc.un, c.arc.ub, c.arc.vn, c.arc.vb, w.two_pi, w.sector_angle, w.n_sectors);
+    else kk = surf_sector(wx, wy, wz, w.u, w.v, w.two_pi, w.sector_angle, w.n_sectors);
+    count(kChainMapped);
+    return true;
+}
+// the map's station of jl, -1 outside [0, n_stations) (|jl| < 2^62 before the conversion: a far point of a stage call must
+// not overflow it)
+template <class Args>
+__device__ __forceinline__ int64_t wall_station(const Args &w, float jl)
+{
+    const int64_t j = fabsf(jl) < 4.0e18f ? w.anchor + (int64_t)jl : -1;
+    return j >= 0 && j < (int64_t)w.n_stations ? j : -1;
+}
 // ---- run merging: the common start of the segmented reductions (surf_merge_runs here, wc_merge_runs in k_wall_cloud.hip,
 // k_wall_region_reduce, k_wall_object_reduce).  Runs of one key in consecutive lanes are folded into the run's head lane
 // before anything goes to memory.  wave_runs finds the runs; the ladder stays with its caller, because its fields do:

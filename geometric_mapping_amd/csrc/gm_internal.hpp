@@ -314,12 +314,6 @@ struct WallArgs {
     float *res;                // stage call only (nullptr in the frame path)
     int32_t *cell;
 };
-// A map on a circular-arc design axis (gm_wall_map_create_arc): what the arc instantiations take by value beside WallArgs,
-// whose o, a are then o', a' at the anchor section (u, v are reported, not read).
-struct WallArc {
-    float n[3], b[3];          // n', b' in sensor coordinates
-    float kappa, un, ub, vn, vb;
-};
 // the arrays of a table of ncell cells at base: sum i64 | count u32 | lo u32 | hi u32 | totals u64 [kWallTotals]
 __host__ __device__ inline WallTable wall_table(uint8_t *base, uint64_t ncell)
 {

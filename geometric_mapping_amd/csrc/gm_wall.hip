@@ -29,51 +29,6 @@ static void add_window(const gm_wall_params &p, double reach_stations, WallArgs 
     }
 }
 
-// add_frame_args on an arc map (include/gm_hip.h: per add)
-static gm_status add_frame_args_arc(gm_wall_map *m, const double Rm[3][3], const double tr[3], gm_wall_add_info *info, WallArgs &w,
-                                    WallArc &arc)
-{
-    gm_ctx *ctx = m->ctx;
-    const gm_wall_params &p = m->prm;
-    gm_wall_arc_add_info ai;
-    double u64[3], v64[3], a1 = 0.0;
-    if (!arc_add_frame(p, m->frame, m->af, Rm, tr, ai, u64, v64, &a1))
-        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose is too far along the axis");
-    memset(&w, 0, sizeof(w));
-    for (int k = 0; k < 3; ++k) {
-        w.o[k] = ai.o[k]; w.a[k] = ai.a[k]; w.u[k] = (float)u64[k]; w.v[k] = (float)v64[k];
-        arc.n[k] = ai.n[k]; arc.b[k] = ai.b[k];
-    }
-    arc.kappa = ai.kappa;
-    arc.un = ai.un; arc.ub = ai.ub; arc.vn = ai.vn; arc.vb = ai.vb;
-    w.R = ai.R;
-    w.station_length = ai.station_length;
-    w.gate = ai.gate;
-    w.sector_angle = ai.sector_angle;
-    w.two_pi = (float)kTwoPi;
-    w.n_stations = p.n_stations;
-    w.n_sectors = p.n_sectors;
-    w.anchor = ai.anchor_station;
-    w.table = m->table;
-    // The LDS window, which affects speed only (a mapped point outside it goes to the map directly): wherever cy >= 0.5,
-    // |t| = |atan2(cx, cy)| / kappa <= |cx| / (cy kappa) <= 2 |x|, and |x| <= B |a'|_1 + ds over the crop cube
-    // |p|_inf <= B as on a straight map (the sensor lies within ds of the anchor section: the stations that costs at the
-    // window's ends take the global path).
-    add_window(p, 2.0 * ctx->cfg.boxFilterBound * a1 / p.station_length, w);
-    if (info) {
-        memset(info, 0, sizeof(*info));
-        info->struct_size = (uint32_t)sizeof(gm_wall_add_info);
-        info->status = m->frame.status;
-        info->anchor_station = w.anchor;
-        for (int k = 0; k < 3; ++k) { info->o[k] = w.o[k]; info->a[k] = w.a[k]; info->u[k] = w.u[k]; info->v[k] = w.v[k]; }
-        info->R = w.R;
-        info->station_length = w.station_length;
-        info->sector_angle = w.sector_angle;
-        info->gate = w.gate;
-    }
-    return GM_OK;
-}
-
 void launch_add(gm_wall_map *m, const WallArgs &w, const WallArc &arc, uint32_t n_cap, hipStream_t s)
 {
     if (m->is_arc()) launch_wall_add_arc(w, arc, n_cap, m->points_per_block, s);
@@ -88,31 +43,53 @@ gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info
     const int bad = pose_split(pose, Rm, tr);
     if (bad == 1) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose is not finite");
     if (bad) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose rotation is not orthonormal to 1e-6 or is a reflection");
-    if (m->is_arc()) {
-        if (!arc) return gm_fail(ctx, GM_ERR_UNSUPPORTED, "gm_wall_map: this call is not available on a map with an arc design axis");
-        return add_frame_args_arc(m, Rm, tr, info, w, *arc);
-    }
     const gm_wall_params &p = m->prm;
     const DesignFrame &d = m->frame;
     const double ds = p.station_length;
-    const double rel[3] = {tr[0] - d.o[0], tr[1] - d.o[1], tr[2] - d.o[2]};
-    const double s = dot(rel, d.a);
-    const double jd = floor((s - p.t_min) / ds);
-    if (!(fabs(jd) < 4.0e18)) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose is too far along the axis");
-    const int64_t jf = (int64_t)jd;
-    const double off = p.t_min + jd * ds;
-    double of[3];   // o_f - tr
-    for (int k = 0; k < 3; ++k) of[k] = d.o[k] + off * d.a[k] - tr[k];
-    memset(&w, 0, sizeof(w));
-    double a1 = 0.0;   // |a'|_1: the reach of the crop cube along the axis
-    for (int c = 0; c < 3; ++c) {   // Rm^T x
-        const double oo = Rm[0][c] * of[0] + Rm[1][c] * of[1] + Rm[2][c] * of[2];
-        const double aa = Rm[0][c] * d.a[0] + Rm[1][c] * d.a[1] + Rm[2][c] * d.a[2];
-        const double uu = Rm[0][c] * d.u[0] + Rm[1][c] * d.u[1] + Rm[2][c] * d.u[2];
-        const double vv = Rm[0][c] * d.v[0] + Rm[1][c] * d.v[1] + Rm[2][c] * d.v[2];
-        w.o[c] = (float)oo; w.a[c] = (float)aa; w.u[c] = (float)uu; w.v[c] = (float)vv;
-        if (f64) { f64->c[c] = oo; f64->d[c] = aa; f64->u[c] = uu; f64->v[c] = vv; f64->of[c] = d.o[c] + off * d.a[c]; }
-        a1 += fabs(aa);
+    // what the two axes compute: (o', a', u', v') rounded once, the arc block, the anchor, the crop cube's reach in stations
+    double reach;
+    if (m->is_arc()) {   // (include/gm_hip.h: per add)
+        if (!arc) return gm_fail(ctx, GM_ERR_UNSUPPORTED, "gm_wall_map: this call is not available on a map with an arc design axis");
+        gm_wall_arc_add_info ai;
+        double u64[3], v64[3], a1 = 0.0;
+        if (!arc_add_frame(p, d, m->af, Rm, tr, ai, u64, v64, &a1))
+            return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose is too far along the axis");
+        memset(&w, 0, sizeof(w));
+        for (int k = 0; k < 3; ++k) {
+            w.o[k] = ai.o[k]; w.a[k] = ai.a[k]; w.u[k] = (float)u64[k]; w.v[k] = (float)v64[k];
+            arc->n[k] = ai.n[k]; arc->b[k] = ai.b[k];
+        }
+        arc->kappa = ai.kappa;
+        arc->un = ai.un; arc->ub = ai.ub; arc->vn = ai.vn; arc->vb = ai.vb;
+        w.anchor = ai.anchor_station;
+        // The LDS window, which affects speed only (a mapped point outside it goes to the map directly): wherever cy >= 0.5,
+        // |t| = |atan2(cx, cy)| / kappa <= |cx| / (cy kappa) <= 2 |x|, and |x| <= B |a'|_1 + ds over the crop cube
+        // |p|_inf <= B as on a straight map (the sensor lies within ds of the anchor section: the stations that costs at the
+        // window's ends take the global path).
+        reach = 2.0 * ctx->cfg.boxFilterBound * a1 / ds;
+    } else {
+        const double rel[3] = {tr[0] - d.o[0], tr[1] - d.o[1], tr[2] - d.o[2]};
+        const double s = dot(rel, d.a);
+        const double jd = floor((s - p.t_min) / ds);
+        if (!(fabs(jd) < 4.0e18)) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose is too far along the axis");
+        const double off = p.t_min + jd * ds;
+        double of[3];   // o_f - tr
+        for (int k = 0; k < 3; ++k) of[k] = d.o[k] + off * d.a[k] - tr[k];
+        memset(&w, 0, sizeof(w));
+        double a1 = 0.0;   // |a'|_1: the reach of the crop cube along the axis
+        for (int c = 0; c < 3; ++c) {   // Rm^T x
+            const double oo = Rm[0][c] * of[0] + Rm[1][c] * of[1] + Rm[2][c] * of[2];
+            const double aa = Rm[0][c] * d.a[0] + Rm[1][c] * d.a[1] + Rm[2][c] * d.a[2];
+            const double uu = Rm[0][c] * d.u[0] + Rm[1][c] * d.u[1] + Rm[2][c] * d.u[2];
+            const double vv = Rm[0][c] * d.v[0] + Rm[1][c] * d.v[1] + Rm[2][c] * d.v[2];
+            w.o[c] = (float)oo; w.a[c] = (float)aa; w.u[c] = (float)uu; w.v[c] = (float)vv;
+            if (f64) { f64->c[c] = oo; f64->d[c] = aa; f64->u[c] = uu; f64->v[c] = vv; f64->of[c] = d.o[c] + off * d.a[c]; }
+            a1 += fabs(aa);
+        }
+        w.anchor = (int64_t)jd;
+        // The LDS window: t = p.a' + (s - chainage of the anchor station's start) lies in [-B |a'|_1, B |a'|_1 + ds) for the
+        // points of the crop cube |p|_inf <= B, so their stations relative to the anchor in [floor(-reach), floor(reach) + 1].
+        reach = ctx->cfg.boxFilterBound * a1 / ds;
     }
     w.R = (float)d.R;
     w.station_length = (float)ds;
@@ -121,16 +98,13 @@ gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info
     w.two_pi = (float)kTwoPi;
     w.n_stations = p.n_stations;
     w.n_sectors = p.n_sectors;
-    w.anchor = jf;
     w.table = m->table;
-    // The LDS window: t = p.a' + (s - chainage of the anchor station's start) lies in [-B |a'|_1, B |a'|_1 + ds) for the
-    // points of the crop cube |p|_inf <= B, so their stations relative to the anchor in [floor(-reach), floor(reach) + 1].
-    add_window(p, ctx->cfg.boxFilterBound * a1 / ds, w);
+    add_window(p, reach, w);
     if (info) {
         memset(info, 0, sizeof(*info));
         info->struct_size = (uint32_t)sizeof(gm_wall_add_info);
         info->status = d.status;
-        info->anchor_station = jf;
+        info->anchor_station = w.anchor;
         for (int k = 0; k < 3; ++k) { info->o[k] = w.o[k]; info->a[k] = w.a[k]; info->u[k] = w.u[k]; info->v[k] = w.v[k]; }
         info->R = w.R;
         info->station_length = w.station_length;

@@ -11,8 +11,8 @@
 //   2. a block zeroes its private LDS table: sum i64 of rint(e 2^20), count u32, ~ordered(min e) u32, ordered(max e)
 //      u32 -- 20 B per cell, GM_SURF_MAX_CELLS = 4096 cells = 80 KiB of static LDS (no scratch; 80 VGPRs, so one
 //      1024-thread block per CU: 16 waves; -Rpass-analysis=kernel-resource-usage);
-//   3. grid-stride over the points: per point the class, e and the cell, coalesced stores of e and the cell index, and
-//      LDS integer atomics.  A wave whose lanes hold runs of one cell (lidar frames: ring by azimuth, ~20 consecutive
+//   3. the point stream of gm_point_stream.hpp (stream_points): per point the class, e and the cell, coalesced stores of
+//      e and the cell index, and LDS integer atomics.  A wave whose lanes hold runs of one cell (lidar frames: ring by azimuth, ~20 consecutive
 //      points per 4-degree sector) first reduces each run into its head lane (segmented shuffles), so a run costs one
 //      set of LDS atomics instead of ~20 on one address; a wave without such runs skips that step;
 //   4. the block flushes its touched cells to the global table, lane <-> cell (contiguous), integer device atomics,
@@ -25,6 +25,7 @@
 #include <string.h>
 
 #include "gm_internal.hpp"
+#include "gm_point_stream.hpp"
 
 namespace gm {
 
@@ -124,67 +125,46 @@ __global__ __launch_bounds__(kSurfThreads) void k_surface_map(SurfArgs a)
     __syncthreads();
 
     uint32_t cls[4] = {0u, 0u, 0u, 0u};   // mapped, outside, beyond_gate, plane
-    const uint64_t stride = (uint64_t)gridDim.x * kSurfThreads;
-    // wave-uniform trips (the run merge shuffles across the wave): the wave's first index decides, every lane checks its own
-    for (uint64_t w0 = (uint64_t)blockIdx.x * kSurfThreads + (threadIdx.x & ~(uint32_t)(kWave - 1)); w0 < n;
-         w0 += kSurfUnroll * stride) {
-        float4 q[kSurfUnroll];
-        uint32_t lab[kSurfUnroll];
-#pragma unroll
-        for (int k = 0; k < kSurfUnroll; ++k) {
-            const uint64_t i = w0 + lane + (uint64_t)k * stride;
-            lab[k] = 0u;
-            q[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (i < n) {
-                q[k] = a.pts[i];
-                if (a.labels) lab[k] = a.labels[i];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < kSurfUnroll; ++k) {
-            const uint64_t i = w0 + lane + (uint64_t)k * stride;
-            if (w0 + (uint64_t)k * stride >= n) break;   // (wave-uniform)
-            const bool in = i < n;
-            float e = __builtin_nanf("");
-            int cell = -1;
-            if (in && model) {
-                if (lab[k] == 1u) {
-                    ++cls[3];
+    stream_points<kSurfThreads, kSurfUnroll>(a.pts, a.labels, n, [&](uint64_t i, bool in, const float4 &q, uint32_t lab) {
+        float e = __builtin_nanf("");
+        int cell = -1;
+        if (in && model) {
+            if (lab == 1u) {
+                ++cls[3];
+            } else {
+                float t, wx, wy, wz;
+                e = surf_residual(q, F.o, F.a, F.R, t, wx, wy, wz);
+                if (!(fabsf(e) <= p.gate)) {
+                    ++cls[2];
                 } else {
-                    float t, wx, wy, wz;
-                    e = surf_residual(q[k], F.o, F.a, F.R, t, wx, wy, wz);
-                    if (!(fabsf(e) <= p.gate)) {
-                        ++cls[2];
+                    const float jf = surf_station(t, p.t_min, p.station_length);
+                    if (!(jf >= 0.0f && jf < nst_f)) {
+                        ++cls[1];
                     } else {
-                        const float jf = surf_station(t, p.t_min, p.station_length);
-                        if (!(jf >= 0.0f && jf < nst_f)) {
-                            ++cls[1];
-                        } else {
-                            const uint32_t kk = surf_sector(wx, wy, wz, F.u, F.v, p.two_pi, p.sector_angle, nsec);
-                            cell = (int)((uint32_t)jf * nsec + kk);
-                            ++cls[0];
-                        }
+                        const uint32_t kk = surf_sector(wx, wy, wz, F.u, F.v, p.two_pi, p.sector_angle, nsec);
+                        cell = (int)((uint32_t)jf * nsec + kk);
+                        ++cls[0];
                     }
                 }
             }
-            if (in) { a.res[i] = e; a.cell[i] = cell; }
-            // the point's contribution: count, fixed-point sum, ~ordered(e), ordered(e) (all 0, neutral, unless mapped)
-            uint32_t cn = 0u, lo = 0u, hi = 0u;
-            unsigned long long sm = 0ull;
-            if (cell >= 0) {
-                cn = 1u;
-                sm = (unsigned long long)(long long)__float2int_rn(__fmul_rn(e, kFix));
-                hi = float_to_ordered(e);
-                lo = ~hi;
-            }
-            if (surf_merge_runs(cell, cn, sm, lo, hi)) {
-                atomicAdd(&s_cnt[cell], cn);
-                atomicAdd(&s_sum[cell], sm);
-                atomicMax(&s_lo[cell], lo);
-                atomicMax(&s_hi[cell], hi);
-            }
         }
-    }
+        if (in) { a.res[i] = e; a.cell[i] = cell; }
+        // the point's contribution: count, fixed-point sum, ~ordered(e), ordered(e) (all 0, neutral, unless mapped)
+        uint32_t cn = 0u, lo = 0u, hi = 0u;
+        unsigned long long sm = 0ull;
+        if (cell >= 0) {
+            cn = 1u;
+            sm = (unsigned long long)(long long)__float2int_rn(__fmul_rn(e, kFix));
+            hi = float_to_ordered(e);
+            lo = ~hi;
+        }
+        if (surf_merge_runs(cell, cn, sm, lo, hi)) {
+            atomicAdd(&s_cnt[cell], cn);
+            atomicAdd(&s_sum[cell], sm);
+            atomicMax(&s_lo[cell], lo);
+            atomicMax(&s_hi[cell], hi);
+        }
+    });
     __syncthreads();
     // flush the touched cells, lane <-> cell, integer device atomics
     for (uint32_t c = threadIdx.x; c < ncell; c += kSurfThreads) {

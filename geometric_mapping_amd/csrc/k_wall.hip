@@ -11,25 +11,27 @@
 // also knows a window of whole stations around j_f that the frame's points fall into.
 //   1. a block zeroes its private LDS table for the window: win_stations x n_sectors <= GM_SURF_MAX_CELLS cells of
 //      sum i64, count u32, ~ordered(min e) u32, ordered(max e) u32 (80 KiB of static LDS, one block per CU);
-//   2. grid-stride over the points: 16 B of point + 1 B of label read, nothing written per point (the stage call's
-//      optional residual / cell outputs apart).  The in-wave run merge of the surface kernel, then LDS integer atomics
-//      for cells inside the window; a mapped point outside it (fine grids, long crop boxes, oblique axes) goes straight
-//      to the map with the same device atomics -- slower, identical result;
+//   2. the point stream of gm_point_stream.hpp (stream_points: 16 B of point + 1 B of label read) with the chain head of
+//      gm_device.hpp (wall_chain); nothing written per point (the stage call's optional residual / cell outputs apart).
+//      The in-wave run merge of the surface kernel, then LDS integer atomics for cells inside the window; a mapped point
+//      outside it (fine grids, long crop boxes, oblique axes) goes straight to the map with the same device atomics --
+//      slower, identical result;
 //   3. the block flushes the window cells it touched to the map at (j_f + win_first) * n_sectors + cell with integer
-//      device atomics (atomicAdd u32 / i64, atomicMax u32) and adds its class counts, one atomic per class.
+//      device atomics (atomicAdd u32 / i64, atomicMax u32) and adds its class counts, one atomic per class
+//      (block_class_counts).
 // No floating-point atomics, no ticket, no host round trip: the point count is the device word n_valid.  Adds from
 // several streams may interleave in the map: every update is an integer atomic, so the result does not depend on it.
 #include <math.h>
 #include <string.h>
 
 #include "gm_internal.hpp"
+#include "gm_point_stream.hpp"
 
 namespace gm {
 
 constexpr int kWallThreads = 1024;
 constexpr uint32_t kWallMaxBlocks = 256;          // one per CU
 constexpr int kWallUnroll = 2;
-constexpr int kWallWaves = kWallThreads / kWave;
 constexpr uint32_t kWallCells = GM_SURF_MAX_CELLS;
 constexpr float kWallFix = 1048576.0f;   // 2^20, as k_surface.hip
 
@@ -56,14 +58,9 @@ struct WallMask<true> {
     unsigned long long *ctr;           // [kWallAddCheckedCounters]
 };
 
-// kArc (a map of gm_wall_map_create_arc): the per-point chain is arc_residual / arc_sector (gm_device.hpp) on the by-value
-// WallArc; everything behind (e, t, k) -- classes, window, run merge, flush -- is shared.  The straight instantiations
-// carry none of it, and the arc ones have entry points of their own below.
-template <bool kArc>
-struct WallArcArg {};
-template <>
-struct WallArcArg<true> { WallArc arc; };
-
+// kArc (a map of gm_wall_map_create_arc): the chain head runs on the by-value WallArc (wall_chain, gm_device.hpp); everything
+// behind (e, jl, k) -- classes, window, run merge, flush -- is shared.  The straight instantiations carry none of it, and
+// the arc ones have entry points of their own below.
 template <bool kMasked, bool kArc>
 __device__ __forceinline__ void wall_add(const WallArgs a, const WallMask<kMasked> m, const WallArcArg<kArc> c)
 {
@@ -72,12 +69,10 @@ __device__ __forceinline__ void wall_add(const WallArgs a, const WallMask<kMaske
     __shared__ uint32_t s_cnt[kWallCells];
     __shared__ uint32_t s_lo[kWallCells];
     __shared__ uint32_t s_hi[kWallCells];
-    __shared__ uint32_t s_cls[kCls][kWallWaves];
     const uint32_t n = a.n_ptr ? *a.n_ptr : a.n_host;
     const uint32_t nsec = a.n_sectors;
     const uint32_t wcells = a.win_stations * nsec;   // <= kWallCells (the host sizes the window)
     const float win_lo = (float)a.win_first, win_hi = (float)(a.win_first + (int32_t)a.win_stations);
-    const int64_t nst = (int64_t)a.n_stations;
     const WallTable T = a.table;
     const int lane = lane_id();
 
@@ -85,88 +80,52 @@ __device__ __forceinline__ void wall_add(const WallArgs a, const WallMask<kMaske
     __syncthreads();
 
     uint32_t cls[kCls] = {};   // mapped, outside, beyond_gate, plane (, skipped)
-    const uint64_t stride = (uint64_t)gridDim.x * kWallThreads;
-    // wave-uniform trips (the run merge shuffles across the wave)
-    for (uint64_t w0 = (uint64_t)blockIdx.x * kWallThreads + (threadIdx.x & ~(uint32_t)(kWave - 1)); w0 < n;
-         w0 += kWallUnroll * stride) {
-        float4 q[kWallUnroll];
-        uint32_t lab[kWallUnroll];
-        unsigned long long mw[kWallUnroll];
-#pragma unroll
-        for (int k = 0; k < kWallUnroll; ++k) {
-            const uint64_t i = w0 + lane + (uint64_t)k * stride;
-            lab[k] = 0u;
-            q[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-            mw[k] = 0ull;
-            if constexpr (kMasked) {
-                const uint64_t wk = w0 + (uint64_t)k * stride;   // (wave-uniform; < n <= 2^32)
-                if (wk < n) mw[k] = m.words[__builtin_amdgcn_readfirstlane((uint32_t)(wk >> 6))];
-            }
-            if (i < n) {
-                q[k] = a.pts[i];
-                if (a.labels) lab[k] = a.labels[i];
+    auto point = [&](uint64_t i, bool in, const float4 &q, uint32_t lab, unsigned long long mw) {
+        const bool skip = kMasked && ((mw >> lane) & 1ull);
+        const uint32_t live = skip ? 0u : 1u;
+        float e = __builtin_nanf("");
+        int cell = -1;      // global cell j * n_sectors + k (< 2^24)
+        int lcell = -1;     // the same cell in the block's window, -1 outside it
+        if (in) {
+            if constexpr (kMasked) cls[kCls - 1] += 1u - live;
+            int64_t j;
+            float jl;
+            uint32_t kk;
+            if (wall_chain(q, lab, a, c, [&](float s) { return (j = wall_station(a, s)) >= 0; },
+                           [&](uint32_t k) { cls[kChainMapped - k] += live; }, e, jl, kk)) {
+                cell = (int)((uint32_t)j * nsec + kk);
+                if (jl >= win_lo && jl < win_hi) lcell = (int)((uint32_t)((int32_t)jl - a.win_first) * nsec + kk);
             }
         }
-#pragma unroll
-        for (int k = 0; k < kWallUnroll; ++k) {
-            const uint64_t i = w0 + lane + (uint64_t)k * stride;
-            if (w0 + (uint64_t)k * stride >= n) break;   // (wave-uniform)
-            const bool in = i < n;
-            const bool skip = kMasked && ((mw[k] >> lane) & 1ull);
-            const uint32_t live = skip ? 0u : 1u;
-            float e = __builtin_nanf("");
-            int cell = -1;      // global cell j * n_sectors + k (< 2^24)
-            int lcell = -1;     // the same cell in the block's window, -1 outside it
-            if (in) {
-                if constexpr (kMasked) cls[kCls - 1] += 1u - live;
-                if (lab[k] == 1u) {
-                    cls[3] += live;
-                } else {
-                    float t, wx, wy, wz;   // (kArc: wx = yc, wy = z, wz = cy)
-                    if constexpr (kArc) e = arc_residual(q[k], a.o, a.a, c.arc.n, c.arc.b, c.arc.kappa, a.R, t, wx, wy, wz);
-                    else e = surf_residual(q[k], a.o, a.a, a.R, t, wx, wy, wz);
-                    if (!(fabsf(e) <= a.gate) || (kArc && !(wz > 0.0f))) {
-                        cls[2] += live;
-                    } else {
-                        const float jl = surf_station(t, 0.0f, a.station_length);   // relative to the anchor
-                        // (|jl| < 2^62 before the conversion: a far point of the stage call must not overflow it)
-                        const int64_t j = fabsf(jl) < 4.0e18f ? a.anchor + (int64_t)jl : -1;
-                        if (!(j >= 0 && j < nst)) {
-                            cls[1] += live;
-                        } else {
-                            uint32_t kk;
-                            if constexpr (kArc)
-                                kk = arc_sector(wx, wy, c.arc.un, c.arc.ub, c.arc.vn, c.arc.vb, a.two_pi, a.sector_angle, nsec);
-                            else kk = surf_sector(wx, wy, wz, a.u, a.v, a.two_pi, a.sector_angle, nsec);
-                            cell = (int)((uint32_t)j * nsec + kk);
-                            if (jl >= win_lo && jl < win_hi) lcell = (int)((uint32_t)((int32_t)jl - a.win_first) * nsec + kk);
-                            cls[0] += live;
-                        }
-                    }
-                }
-            }
-            if (skip) { cell = -1; lcell = -1; }
-            if (in && a.res) a.res[i] = e;
-            if (in && a.cell) a.cell[i] = cell;
-            uint32_t cn = 0u, lo = 0u, hi = 0u;
-            unsigned long long sm = 0ull;
-            if (cell >= 0) {
-                cn = 1u;
-                sm = (unsigned long long)(long long)__float2int_rn(__fmul_rn(e, kWallFix));
-                hi = float_to_ordered(e);
-                lo = ~hi;
-            }
-            if (surf_merge_runs(cell, cn, sm, lo, hi)) {   // (lanes of one run share the cell, hence lcell)
-                if (lcell >= 0) {
-                    atomicAdd(&s_cnt[lcell], cn);
-                    atomicAdd(&s_sum[lcell], sm);
-                    atomicMax(&s_lo[lcell], lo);
-                    atomicMax(&s_hi[lcell], hi);
-                } else {
-                    wall_global_add(T, (uint64_t)cell, cn, sm, lo, hi);
-                }
+        if (skip) { cell = -1; lcell = -1; }
+        if (in && a.res) a.res[i] = e;
+        if (in && a.cell) a.cell[i] = cell;
+        uint32_t cn = 0u, lo = 0u, hi = 0u;
+        unsigned long long sm = 0ull;
+        if (cell >= 0) {
+            cn = 1u;
+            sm = (unsigned long long)(long long)__float2int_rn(__fmul_rn(e, kWallFix));
+            hi = float_to_ordered(e);
+            lo = ~hi;
+        }
+        if (surf_merge_runs(cell, cn, sm, lo, hi)) {   // (lanes of one run share the cell, hence lcell)
+            if (lcell >= 0) {
+                atomicAdd(&s_cnt[lcell], cn);
+                atomicAdd(&s_sum[lcell], sm);
+                atomicMax(&s_lo[lcell], lo);
+                atomicMax(&s_hi[lcell], hi);
+            } else {
+                wall_global_add(T, (uint64_t)cell, cn, sm, lo, hi);
             }
         }
+    };
+    if constexpr (kMasked) {   // the slot's mask word rides with the slot's loads (wk: wave-uniform, < n <= 2^32)
+        stream_points_with<kWallThreads, kWallUnroll>(
+            a.pts, a.labels, n, [&](uint64_t wk) { return wk < n ? m.words[__builtin_amdgcn_readfirstlane((uint32_t)(wk >> 6))] : 0ull; },
+            point);
+    } else {
+        stream_points<kWallThreads, kWallUnroll>(a.pts, a.labels, n,
+                                                 [&](uint64_t i, bool in, const float4 &q, uint32_t lab) { point(i, in, q, lab, 0ull); });
     }
     __syncthreads();
     // flush the touched window cells, lane <-> cell (contiguous in the map: the window is whole stations).  A touched
@@ -178,20 +137,12 @@ __device__ __forceinline__ void wall_add(const WallArgs a, const WallMask<kMaske
         wall_global_add(T, (uint64_t)(base + (int64_t)c), cn, s_sum[c], s_lo[c], s_hi[c]);
     }
     // class counts: one atomic per class and block
-#pragma unroll
-    for (int k = 0; k < kCls; ++k) {
-        const uint32_t v = wave_sum(cls[k]);
-        if (lane == 0) s_cls[k][threadIdx.x / kWave] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < kCls) {
-        unsigned long long v = 0ull;
-        for (int w = 0; w < kWallWaves; ++w) v += s_cls[threadIdx.x][w];
-        if (v && threadIdx.x < 4) atomicAdd(&T.totals[threadIdx.x], v);
+    block_class_counts<kWallThreads>(cls, [&](uint32_t k, unsigned long long v) {
+        if (v && k < 4u) atomicAdd(&T.totals[k], v);
         if constexpr (kMasked) {   // skipped | mapped, outside, beyond_gate, plane
-            if (v) atomicAdd(&m.ctr[threadIdx.x == kCls - 1 ? 4 : 5 + threadIdx.x], v);
+            if (v) atomicAdd(&m.ctr[k == (uint32_t)kCls - 1u ? 4u : 5u + k], v);
         }
-    }
+    });
 }
 
 __global__ __launch_bounds__(kWallThreads) void k_wall_add(WallArgs a)

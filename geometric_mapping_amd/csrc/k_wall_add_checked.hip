@@ -7,9 +7,10 @@
 // round trip.  A row reads its delta and index (two of its eight words), takes its class by wall_mark_class
 // (gm_internal.hpp), and a selected row sets bit `index` of the mask with a vector atomicOr on the
 // 32-bit word: index < n_points <= the mask's bits, checked by the rule itself before the store.  The four row classes are
-// counted by ballots into wave-uniform registers and leave as one integer atomic per class and block.  Thread 0 of block 0
-// writes n_rows and n_points into the counter block.
+// counted by ballots into wave-uniform registers and leave as one integer atomic per class and block (block_row_sums,
+// gm_point_stream.hpp).  Thread 0 of block 0 writes n_rows and n_points into the counter block.
 #include "gm_internal.hpp"
+#include "gm_point_stream.hpp"
 
 namespace gm {
 
@@ -43,12 +44,9 @@ __global__ __launch_bounds__(kMarkThreads) void k_wall_mark(WallMarkArgs a)
 #pragma unroll
         for (int k = 0; k < 4; ++k) s_cls[k][threadIdx.x / kWave] = cnt[k];
     }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        unsigned long long v = 0ull;
-        for (int w = 0; w < kMarkWaves; ++w) v += s_cls[threadIdx.x][w];
-        if (v) atomicAdd(&a.ctr[threadIdx.x], v);
-    }
+    block_row_sums(s_cls, [&](uint32_t k, unsigned long long v) {
+        if (v) atomicAdd(&a.ctr[k], v);
+    });
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         a.ctr[9] = n_rows;
         a.ctr[10] = n_points;

@@ -3,12 +3,12 @@
 //
 // The rule is stated in include/gm_hip.h and DESIGN.md; the CPU twin is tests/wall_align_np.py.  Three launches per align,
 // everything from a point's residual on in integers:
-//   k_wall_align_bin     k_wall_add's shape on a patch instead of the map: one streaming pass over the valid cloud (16 B
-//                        of point + 1 B of label read, nothing written per point, the stage call's optional outputs
-//                        apart), the per-point chain of gm_device.hpp, the in-wave run merge, LDS integer atomics into a
-//                        block-private patch table of 2P x n_sectors <= 8192 cells (sum i64, count u32: 96 KiB of static
-//                        LDS, one block per CU), then a flush of the touched cells into the zeroed (map, slot) patch with
-//                        integer device atomics.  One atomic per class and block.  The point count is the device word.
+//   k_wall_align_bin     k_wall_add on a patch instead of the map: the same point stream and class counts
+//                        (gm_point_stream.hpp) and chain head (wall_chain, gm_device.hpp) under the patch's range, the
+//                        in-wave run merge, LDS integer atomics into a block-private patch table of 2P x n_sectors <= 8192
+//                        cells (sum i64, count u32: 96 KiB of static LDS, one block per CU), then a flush of the touched
+//                        cells into the zeroed (map, slot) patch with integer device atomics.  The point count is the
+//                        device word.
 //   k_wall_align_values  the patch becomes the int32 image f, the map rows [j_f - P - A, j_f + P + A) the int32 image m;
 //                        an unusable cell, and a row outside the map, is kWallAlignNone.  Behind the wait on the adds.
 //   k_wall_align_score   the hot kernel: one block per (station shift a, run of `rows` patch rows).  It stages the run of
@@ -22,12 +22,12 @@
 #include <string.h>
 
 #include "gm_internal.hpp"
+#include "gm_point_stream.hpp"
 
 namespace gm {
 
 constexpr int kAlignBinThreads = 1024;
 constexpr int kAlignBinUnroll = 2;
-constexpr int kAlignBinWaves = kAlignBinThreads / kWave;
 constexpr uint32_t kAlignCells = GM_WALL_ALIGN_MAX_PATCH_CELLS;
 constexpr int kAlignThreads = 256;
 constexpr uint32_t kAlignMaxB = 2 * GM_WALL_ALIGN_MAX_SHIFT + 1;
@@ -53,75 +53,37 @@ __global__ __launch_bounds__(kAlignBinThreads) void k_wall_align_bin(WallAlignAr
 {
     __shared__ unsigned long long s_sum[kAlignCells];
     __shared__ uint32_t s_cnt[kAlignCells];
-    __shared__ uint32_t s_cls[4][kAlignBinWaves];
     const WallArgs &w = a.w;
     const uint32_t n = w.n_ptr ? *w.n_ptr : w.n_host;
     const uint32_t nsec = w.n_sectors;
     const uint32_t pcells = 2u * a.P * nsec;   // <= kAlignCells (the host checks the parameters)
     const float p_lo = -(float)a.P, p_hi = (float)a.P;
-    const int lane = lane_id();
 
     for (uint32_t c = threadIdx.x; c < pcells; c += kAlignBinThreads) { s_sum[c] = 0ull; s_cnt[c] = 0u; }
     __syncthreads();
 
-    uint32_t cls[4] = {0u, 0u, 0u, 0u};   // plane, beyond_gate, outside_patch, binned
-    const uint64_t stride = (uint64_t)gridDim.x * kAlignBinThreads;
-    // wave-uniform trips (the run merge shuffles across the wave)
-    for (uint64_t w0 = (uint64_t)blockIdx.x * kAlignBinThreads + (threadIdx.x & ~(uint32_t)(kWave - 1)); w0 < n;
-         w0 += kAlignBinUnroll * stride) {
-        float4 q[kAlignBinUnroll];
-        uint32_t lab[kAlignBinUnroll];
-#pragma unroll
-        for (int k = 0; k < kAlignBinUnroll; ++k) {
-            const uint64_t i = w0 + lane + (uint64_t)k * stride;
-            lab[k] = 0u;
-            q[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (i < n) {
-                q[k] = w.pts[i];
-                if (w.labels) lab[k] = w.labels[i];
-            }
+    uint32_t cls[4] = {0u, 0u, 0u, 0u};   // plane, beyond_gate, outside_patch, binned: wall_chain's order
+    stream_points<kAlignBinThreads, kAlignBinUnroll>(w.pts, w.labels, n, [&](uint64_t i, bool in, const float4 &q, uint32_t lab) {
+        float e = __builtin_nanf("");
+        int cell = -1;      // jr * n_sectors + k (< 8192)
+        float jl;
+        uint32_t kk;
+        if (in && wall_chain(q, lab, w, WallArcArg<false>(), [&](float s) { return s >= p_lo && s < p_hi; },
+                             [&](uint32_t k) { ++cls[k]; }, e, jl, kk))
+            cell = (int)((uint32_t)((int32_t)jl + (int32_t)a.P) * nsec + kk);
+        if (in && w.res) w.res[i] = e;
+        if (in && w.cell) w.cell[i] = cell;
+        uint32_t cn = 0u;
+        unsigned long long sm = 0ull;
+        if (cell >= 0) {
+            cn = 1u;
+            sm = (unsigned long long)wall_check_fix(e);
         }
-#pragma unroll
-        for (int k = 0; k < kAlignBinUnroll; ++k) {
-            const uint64_t i = w0 + lane + (uint64_t)k * stride;
-            if (w0 + (uint64_t)k * stride >= n) break;   // (wave-uniform)
-            const bool in = i < n;
-            float e = __builtin_nanf("");
-            int cell = -1;      // jr * n_sectors + k (< 8192)
-            if (in) {
-                if (lab[k] == 1u) {
-                    ++cls[0];
-                } else {
-                    float t, wx, wy, wz;
-                    e = surf_residual(q[k], w.o, w.a, w.R, t, wx, wy, wz);
-                    if (!(fabsf(e) <= w.gate)) {
-                        ++cls[1];
-                    } else {
-                        const float jl = surf_station(t, 0.0f, w.station_length);   // relative to the anchor
-                        if (!(jl >= p_lo && jl < p_hi)) {
-                            ++cls[2];
-                        } else {
-                            const uint32_t kk = surf_sector(wx, wy, wz, w.u, w.v, w.two_pi, w.sector_angle, nsec);
-                            cell = (int)((uint32_t)((int32_t)jl + (int32_t)a.P) * nsec + kk);
-                            ++cls[3];
-                        }
-                    }
-                }
-            }
-            if (in && w.res) w.res[i] = e;
-            if (in && w.cell) w.cell[i] = cell;
-            uint32_t cn = 0u;
-            unsigned long long sm = 0ull;
-            if (cell >= 0) {
-                cn = 1u;
-                sm = (unsigned long long)wall_check_fix(e);
-            }
-            if (align_merge_runs(cell, cn, sm)) {
-                atomicAdd(&s_cnt[cell], cn);
-                atomicAdd(&s_sum[cell], sm);
-            }
+        if (align_merge_runs(cell, cn, sm)) {
+            atomicAdd(&s_cnt[cell], cn);
+            atomicAdd(&s_sum[cell], sm);
         }
-    }
+    });
     __syncthreads();
     // flush the touched cells, lane <-> cell
     for (uint32_t c = threadIdx.x; c < pcells; c += kAlignBinThreads) {
@@ -131,17 +93,9 @@ __global__ __launch_bounds__(kAlignBinThreads) void k_wall_align_bin(WallAlignAr
         atomicAdd(&a.p_sum[c], s_sum[c]);
     }
     // class counts: one atomic per class and block
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t v = wave_sum(cls[k]);
-        if (lane == 0) s_cls[k][threadIdx.x / kWave] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        unsigned long long v = 0ull;
-        for (int i = 0; i < kAlignBinWaves; ++i) v += s_cls[threadIdx.x][i];
-        if (v) atomicAdd(&a.ctr[threadIdx.x], v);
-    }
+    block_class_counts<kAlignBinThreads>(cls, [&](uint32_t k, unsigned long long v) {
+        if (v) atomicAdd(&a.ctr[k], v);
+    });
     if (blockIdx.x == 0 && threadIdx.x == 4) a.ctr[4] = n;
 }
 

@@ -3,7 +3,7 @@
 //
 // The rule is stated in include/gm_hip.h and DESIGN.md; the CPU twin is tests/wall_check_np.py.  ONE launch per check:
 // k_compact<WallCheckPred, WallCheckEmit> (gm_compact.hpp) over the valid cloud.
-//   predicate   16 B of point + 1 B of label read, k_wall_add's per-point chain (gm_device.hpp) under the check's own gate,
+//   predicate   16 B of point + 1 B of label read, k_wall_add's chain head (wall_chain, gm_device.hpp) under the check's own gate,
 //               then for a mapped point one gather of the cell's accumulators (count first; 8 B of sum or the two keys only
 //               for a usable cell) from a table that is hot in L2, and the integer rule (wall_check_rule, shared with the
 //               host's gm_wall_check_classify).  A point survives iff it is changed.  The point, e, the cell and delta stay
@@ -36,10 +36,12 @@ __device__ __forceinline__ unsigned long long *wk_peaks()
     return p;
 }
 
-// the predicate's body; kArc (a map of gm_wall_map_create_arc): k_wall_add_arc's chain on the by-value WallArc
+// the predicate's body: the adds' chain head (wall_chain, gm_device.hpp), straight or on the by-value WallArc
 struct WallCheckPayload { float4 q; long long delta; float e; int cell; };
-template <bool kArc, class Arc>
-__device__ __forceinline__ bool wall_check_point(const WallCheckArgs &a, const Arc &arc, uint32_t i, WallCheckPayload &p)
+static_assert(GM_WALL_CHECK_CLS_PLANE == kChainPlane && GM_WALL_CHECK_CLS_BEYOND_GATE == kChainBeyondGate &&
+                  GM_WALL_CHECK_CLS_OUTSIDE == kChainOutside, "the check's first classes are wall_chain's");
+template <bool kArc>
+__device__ __forceinline__ bool wall_check_point(const WallCheckArgs &a, const WallArcArg<kArc> &arc, uint32_t i, WallCheckPayload &p)
 {
     const WallArgs &w = a.w;
     p.q = w.pts[i];
@@ -48,35 +50,20 @@ __device__ __forceinline__ bool wall_check_point(const WallCheckArgs &a, const A
     float e = __builtin_nanf("");
     int cell = -1;
     long long delta = 0;
-    uint32_t cls;
-    if (lab == 1u) {
-        cls = GM_WALL_CHECK_CLS_PLANE;
-    } else {
-        float t, wx, wy, wz;   // (kArc: wx = yc, wy = z, wz = cy)
-        if constexpr (kArc) e = arc_residual(p.q, w.o, w.a, arc.n, arc.b, arc.kappa, w.R, t, wx, wy, wz);
-        else e = surf_residual(p.q, w.o, w.a, w.R, t, wx, wy, wz);
-        if (!(fabsf(e) <= w.gate) || (kArc && !(wz > 0.0f))) {
-            cls = GM_WALL_CHECK_CLS_BEYOND_GATE;
-        } else {
-            const float jl = surf_station(t, 0.0f, w.station_length);   // relative to the anchor
-            const int64_t j = fabsf(jl) < 4.0e18f ? w.anchor + (int64_t)jl : -1;
-            if (!(j >= 0 && j < (int64_t)w.n_stations)) {
-                cls = GM_WALL_CHECK_CLS_OUTSIDE;
-            } else {
-                uint32_t kk;
-                if constexpr (kArc) kk = arc_sector(wx, wy, arc.un, arc.ub, arc.vn, arc.vb, w.two_pi, w.sector_angle, w.n_sectors);
-                else kk = surf_sector(wx, wy, wz, w.u, w.v, w.two_pi, w.sector_angle, w.n_sectors);
-                cell = (int)((uint32_t)j * w.n_sectors + kk);   // < n_stations * n_sectors <= 2^24
-                const uint32_t cn = w.table.cnt[cell];
-                long long sum = 0;
-                uint32_t lo = 0u, hi = 0u;
-                if (cn >= a.min_count) {
-                    if (a.reference == GM_WALL_CHECK_ENVELOPE) { lo = w.table.lo[cell]; hi = w.table.hi[cell]; }
-                    else sum = (long long)w.table.sum[cell];
-                }
-                cls = wall_check_rule(a.reference, a.min_count, a.T, sum, cn, lo, hi, e, delta);
-            }
+    uint32_t cls, kk;
+    int64_t j;
+    float jl;
+    if (wall_chain(p.q, lab, w, arc, [&](float s) { return (j = wall_station(w, s)) >= 0; }, [&](uint32_t k) { cls = k; }, e, jl,
+                   kk)) {
+        cell = (int)((uint32_t)j * w.n_sectors + kk);   // < n_stations * n_sectors <= 2^24
+        const uint32_t cn = w.table.cnt[cell];
+        long long sum = 0;
+        uint32_t lo = 0u, hi = 0u;
+        if (cn >= a.min_count) {
+            if (a.reference == GM_WALL_CHECK_ENVELOPE) { lo = w.table.lo[cell]; hi = w.table.hi[cell]; }
+            else sum = (long long)w.table.sum[cell];
         }
+        cls = wall_check_rule(a.reference, a.min_count, a.T, sum, cn, lo, hi, e, delta);
     }
     if (w.res) w.res[i] = e;
     if (w.cell) w.cell[i] = cell;
@@ -95,17 +82,16 @@ __device__ __forceinline__ bool wall_check_point(const WallCheckArgs &a, const A
     return cls >= (uint32_t)GM_WALL_CHECK_CLS_CHANGED_POS;
 }
 
-struct WallNoArc {};
 struct WallCheckPred {
     WallCheckArgs a;
     using Payload = WallCheckPayload;
-    __device__ __forceinline__ bool operator()(uint32_t i, Payload &p) const { return wall_check_point<false>(a, WallNoArc(), i, p); }
+    __device__ __forceinline__ bool operator()(uint32_t i, Payload &p) const { return wall_check_point(a, WallArcArg<false>(), i, p); }
 };
 struct WallCheckPredArc {
     WallCheckArgs a;
-    WallArc arc;
+    WallArcArg<true> arc;
     using Payload = WallCheckPayload;
-    __device__ __forceinline__ bool operator()(uint32_t i, Payload &p) const { return wall_check_point<true>(a, arc, i, p); }
+    __device__ __forceinline__ bool operator()(uint32_t i, Payload &p) const { return wall_check_point(a, arc, i, p); }
 };
 
 struct WallCheckEmit {
@@ -163,7 +149,7 @@ void launch_wall_check(const WallCheckArgs &a, uint32_t n_cap, const ScanState &
 
 void launch_wall_check_arc(const WallCheckArgs &a, const WallArc &arc, uint32_t n_cap, const ScanState &st, hipStream_t s)
 {
-    WallCheckPredArc pred{a, arc};
+    WallCheckPredArc pred{a, {arc}};
     WallCheckEmit emit;
     memset(&emit, 0, sizeof(emit));
     emit.a = a;

@@ -244,6 +244,61 @@ def test_check_and_checked_add(gm):
         assert seen["pos"] > 50 and seen["neg"] > 50 and seen["skipped"] > 50
 
 
+EDGE_SIZES = (0, 1, 63, 64, 65, 1025, 2049)   # one 1024-thread block: its stride plus 1, two strides plus 1
+
+
+@pytest.mark.parametrize("axis", ["arc", "straight"])
+def test_checked_add_at_trip_and_window_edges(gm, monkeypatch, axis):
+    """The masked add on both axes at the edges of its point stream -- no point, a last wave with lanes past n, a trip
+    whose second slot lies wholly past n -- on two-centimetre stations, where the LDS window holds the 11 stations around
+    the anchor and the rest of the 5 m box goes to the map directly.  Every third point is a selected row; the map, the
+    per-point outputs and the counts are those of the plain add of the points that stay (the twin's selection)."""
+    monkeypatch.setenv("GM_WALL_POINTS_PER_BLOCK", "4096")   # read when a map is created: one block for every size here
+    n_max = max(EDGE_SIZES)
+    if axis == "arc":
+        drive = synth.arc_drive(len(EDGE_SIZES), n_max, seed=5, arc_radius=400.0, toward=OBLIQUE)
+        kw = dict(arc=drive["arc"])
+    else:
+        drive = synth.tunnel_drive(len(EDGE_SIZES), n_max, seed=5)
+        kw = dict()
+    p = wn.params(**dict(drive["design"], **twm.GRIDS["fine_stations"]))
+    nsec = p["n_sectors"]
+    wmax = 4096 // nsec                                     # the window: stations [-(wmax // 2), wmax - wmax // 2) from the anchor
+    sides = np.zeros(2, np.int64)
+    with gm.GeometricMapping() as c:
+        for (cloud, pose), n in zip(drive["frames"], EDGE_SIZES):
+            xyz = np.ascontiguousarray(cloud[:n])
+            lab = (np.arange(n) % 7 == 0).astype(np.uint8)
+            rows = np.zeros(len(range(1, n, 3)), kn.POINT)
+            rows["index"] = np.arange(1, n, 3)
+            rows["delta"] = np.where(rows["index"] % 2 == 0, 1.0, -1.0)
+            a, b = c.wall_map(**kw, **p), c.wall_map(**kw, **p)
+            info, res, cell = a.add_points_checked(xyz, pose, rows, labels=lab)
+            _, skipped = an.select(rows, n)
+            keep = an.keep(n, skipped)
+            binfo, pe, pc = b.add_points(xyz[keep], pose, labels=lab[keep])
+            assert a.read_raw().tobytes() == b.read_raw().tobytes()
+            assert info["n_points"] == n and info["n_rows"] == len(rows) and info["skipped"] == len(skipped) == len(rows)
+            assert np.all(cell[:n][~keep] == -1) and np.array_equal(cell[:n][keep], pc[:keep.sum()])
+            assert np.array_equal(res[:n][keep].view(np.uint32), pe[:keep.sum()].view(np.uint32))
+            ia, ib = a.info(), b.info()
+            for key in ("mapped", "outside", "beyond_gate", "plane"):
+                assert info[key] == ia[key] == ib[key], key
+            assert ia["cells_hit"] == ib["cells_hit"] and info["plane"] == int(lab[keep].sum())
+            rel = pc[:keep.sum()][pc[:keep.sum()] >= 0].astype(np.int64) // nsec - binfo["anchor_station"]
+            inside = (rel >= -(wmax // 2)) & (rel < wmax - wmax // 2)
+            if n >= 1025:
+                assert inside.sum() > 0 and (~inside).sum() > 0, (n, inside.sum())
+            sides += (inside.sum(), (~inside).sum())
+            if n == 0:                                      # and the check of no point, on this axis
+                cinfo, crows, _ = a.check_points(xyz, pose, outputs=False)
+                assert len(crows) == 0 and cinfo["n_points"] == 0
+            a.close()
+            b.close()
+    print(f"{axis}: {sides[0]} mapped points inside the LDS window, {sides[1]} outside it")
+    assert sides[0] > 10 and sides[1] > 1000
+
+
 @pytest.mark.parametrize("blocks", [(1, 1), (3, 4)])
 def test_cloud_and_mesh(gm, blocks):
     bs, bk = blocks
