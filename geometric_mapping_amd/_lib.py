@@ -160,6 +160,20 @@ class WallArcAddInfo(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class WallClothoid(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("normal", C.c_double * 3), ("curvature", C.c_double),
+                ("rate", C.c_double), ("point_chainage", C.c_double)]
+
+
+class WallClothoidAddInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("status", C.c_uint32), ("anchor_station", C.c_int64),
+                ("sensor_chainage", C.c_double), ("anchor_chainage", C.c_double),
+                ("o", C.c_float * 3), ("a", C.c_float * 3), ("n", C.c_float * 3), ("b", C.c_float * 3),
+                ("kappa", C.c_float), ("un", C.c_float), ("ub", C.c_float), ("vn", C.c_float), ("vb", C.c_float),
+                ("R", C.c_float), ("station_length", C.c_float), ("sector_angle", C.c_float), ("gate", C.c_float),
+                ("rate", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
 class WallParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_stations", C.c_uint32), ("n_sectors", C.c_uint32), ("reserved", C.c_uint32),
                 ("station_length", C.c_double), ("t_min", C.c_double), ("gate", C.c_double),
@@ -505,6 +519,7 @@ def load():
     wprmp, wrawp, waddp, winfop = C.POINTER(WallParams), C.POINTER(WallRawCell), C.POINTER(WallAddInfo), C.POINTER(WallInfo)
     u64, u64p = C.c_uint64, C.POINTER(C.c_uint64)
     warcp, warcaddp = C.POINTER(WallArc), C.POINTER(WallArcAddInfo)
+    wclp, wcladdp = C.POINTER(WallClothoid), C.POINTER(WallClothoidAddInfo)
     wregp, wrprmp, wrinfop, wrmetp = (C.POINTER(WallRegion), C.POINTER(WallRegionParams), C.POINTER(WallRegionsInfo),
                                       C.POINTER(WallRegionMetrics))
     wcprmp, wcptp, wcinfop = C.POINTER(WallCloudParams), C.POINTER(WallCloudPoint), C.POINTER(WallCloudInfo)
@@ -579,6 +594,13 @@ def load():
         "gm_wall_arc_frame": (C.c_int, [wprmp, warcp, C.c_double, dp, dp, dp, dp]),
         "gm_wall_arc_project": (C.c_int, [wprmp, warcp, dp, dp, dp, dp]),
         "gm_wall_arc_point": (C.c_int, [wprmp, warcp, C.c_double, C.c_double, C.c_double, dp]),
+        "gm_wall_map_create_clothoid": (C.c_int, [vp, wprmp, wclp, C.POINTER(vp)]),
+        "gm_wall_map_get_clothoid": (C.c_int, [vp, wclp]),
+        "gm_wall_clothoid_check_params": (C.c_int, [wprmp, wclp]),
+        "gm_wall_clothoid_add_frame": (C.c_int, [wprmp, wclp, dp, wcladdp]),
+        "gm_wall_clothoid_frame": (C.c_int, [wprmp, wclp, C.c_double, dp, dp, dp, dp, dp, dp]),
+        "gm_wall_clothoid_project": (C.c_int, [wprmp, wclp, dp, dp, dp, dp]),
+        "gm_wall_clothoid_point": (C.c_int, [wprmp, wclp, C.c_double, C.c_double, C.c_double, dp]),
         "gm_wall_map_add_frame": (C.c_int, [vp, vp, u32, dp, waddp]),
         "gm_wall_map_add_points": (C.c_int, [vp, fp, u32, u8p, dp, waddp, fp, i32p]),
         "gm_wall_map_sync": (C.c_int, [vp]),

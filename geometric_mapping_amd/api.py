@@ -506,11 +506,13 @@ class GeometricMapping:
                                            nc, _f32(res), cell.ctypes.data_as(C.POINTER(C.c_int32))))
         return (*self._surface(info, cells), res[:len(xyz)].copy(), cell[:len(xyz)].copy())
 
-    def wall_map(self, arc=None, **params):
+    def wall_map(self, arc=None, clothoid=None, **params):
         """A persistent wall map owned by this context (gm_wall_map_create): WallMap.  Keywords: gm_wall_params fields
         (n_stations, n_sectors, station_length, t_min, gate, point, direction, radius, up, forward).
-        arc=dict(curvature=(x, y, z), point_chainage=s0): a map on a circular-arc design axis (gm_wall_map_create_arc)."""
-        return WallMap(self, arc=arc, **params)
+        arc=dict(curvature=(x, y, z), point_chainage=s0): a map on a circular-arc design axis (gm_wall_map_create_arc).
+        clothoid=dict(normal=(x, y, z), curvature=k0, rate=c, point_chainage=s0): a map on a transition curve
+        (gm_wall_map_create_clothoid); not together with arc."""
+        return WallMap(self, arc=arc, clothoid=clothoid, **params)
 
 
 RAW_CELL = np.dtype([("sum", "<i8"), ("count", "<u4"), ("min_key", "<u4"), ("max_key", "<u4"), ("reserved", "<u4")])
@@ -981,6 +983,73 @@ def wall_arc_point(prm, arc, chainage, angle, rho):
     return out
 
 
+def wall_clothoid(normal, curvature=0.0, rate=0.0, point_chainage=0.0):
+    """gm_wall_clothoid from its four fields."""
+    c = _lib.WallClothoid()
+    c.struct_size = C.sizeof(_lib.WallClothoid)
+    c.normal[:] = [float(x) for x in normal]
+    c.curvature, c.rate, c.point_chainage = float(curvature), float(rate), float(point_chainage)
+    return c
+
+
+def wall_clothoid_check_params(prm, clothoid):
+    """gm_wall_clothoid_check_params (host only): the status (GM_OK or GM_ERR_INVALID_ARG)."""
+    return int(_lib.load().gm_wall_clothoid_check_params(C.byref(prm), C.byref(clothoid)))
+
+
+def wall_clothoid_add_frame(prm, clothoid, pose):
+    """gm_wall_clothoid_add_frame (host only): the per-add frame of a clothoid map with the gm_wall_params `prm` and the
+    gm_wall_clothoid `clothoid` under `pose`: wall_arc_add_frame's dict, kappa being the curvature at the anchor section,
+    plus rate."""
+    m = WallMap._pose(pose)
+    i = _lib.WallClothoidAddInfo()
+    _arc_call("gm_wall_clothoid_add_frame",
+              _lib.load().gm_wall_clothoid_add_frame(C.byref(prm), C.byref(clothoid), _dptr(m), C.byref(i)))
+    d = dict(status=int(i.status), anchor_station=int(i.anchor_station), sensor_chainage=float(i.sensor_chainage),
+             anchor_chainage=float(i.anchor_chainage))
+    for k in ("o", "a", "n", "b"):
+        d[k] = np.array(getattr(i, k)[:], dtype=np.float32)
+    for k in ("kappa", "rate", "un", "ub", "vn", "vb", "R", "station_length", "sector_angle", "gate"):
+        d[k] = np.float32(getattr(i, k))
+    return d
+
+
+def wall_clothoid_frame(prm, clothoid, chainage):
+    """gm_wall_clothoid_frame (host only): the design frame (o, a, u, v) at `chainage`, float64 [3] each, the signed
+    curvature there and the normal n(s) it turns toward."""
+    o, a, u, v, n = _d3(), _d3(), _d3(), _d3(), _d3()
+    k = C.c_double()
+    _arc_call("gm_wall_clothoid_frame",
+              _lib.load().gm_wall_clothoid_frame(C.byref(prm), C.byref(clothoid), float(chainage), _dptr(o), _dptr(a), _dptr(u),
+                                                 _dptr(v), C.byref(k), _dptr(n)))
+    return o, a, u, v, float(k.value), n
+
+
+def wall_clothoid_project(prm, clothoid, xyz):
+    """gm_wall_clothoid_project (host only) on map points [n, 3]: (chainage, angle, e), float64 [n] each."""
+    x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+    L = _lib.load()
+    out = np.empty((len(x), 3), dtype=np.float64)
+    s, ph, e = C.c_double(), C.c_double(), C.c_double()
+    for k in range(len(x)):
+        _arc_call("gm_wall_clothoid_project",
+                  L.gm_wall_clothoid_project(C.byref(prm), C.byref(clothoid), _dptr(x[k]), C.byref(s), C.byref(ph), C.byref(e)))
+        out[k] = (s.value, ph.value, e.value)
+    return out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
+
+
+def wall_clothoid_point(prm, clothoid, chainage, angle, rho):
+    """gm_wall_clothoid_point (host only): the map points at (chainage, angle, rho), broadcast; float64 [n, 3]."""
+    s, ph, r = np.broadcast_arrays(np.asarray(chainage, np.float64), np.asarray(angle, np.float64), np.asarray(rho, np.float64))
+    s, ph, r = s.reshape(-1), ph.reshape(-1), r.reshape(-1)
+    L = _lib.load()
+    out = np.empty((len(s), 3), dtype=np.float64)
+    for k in range(len(s)):
+        _arc_call("gm_wall_clothoid_point",
+                  L.gm_wall_clothoid_point(C.byref(prm), C.byref(clothoid), float(s[k]), float(ph[k]), float(r[k]), _dptr(out[k])))
+    return out
+
+
 def _wall_mesh_info(info):
     d = {k: int(getattr(info, k)) for k in _MESH_INFO}
     d["cloud"] = {k: int(getattr(info.cloud, k)) for k in _CLOUD_INFO}
@@ -1026,12 +1095,17 @@ class WallMap:
     """One gm_wall_map: a device-resident developed wall map against a design cylinder, accumulated over posed frames
     (include/gm_hip.h states the rule).  Created by GeometricMapping.wall_map(); dies with its context."""
 
-    def __init__(self, ctx, arc=None, **params):
+    def __init__(self, ctx, arc=None, clothoid=None, **params):
         self._ctx, self._L = ctx, ctx._L
         self._map = None
         p = self.params(**params)
         h = C.c_void_p()
-        if arc is None:
+        if arc is not None and clothoid is not None:
+            raise ValueError("wall_map: arc= and clothoid= exclude each other")
+        if clothoid is not None:
+            cl = clothoid if isinstance(clothoid, _lib.WallClothoid) else wall_clothoid(**clothoid)
+            ctx._check(self._L.gm_wall_map_create_clothoid(ctx._ctx, C.byref(p), C.byref(cl), C.byref(h)))
+        elif arc is None:
             ctx._check(self._L.gm_wall_map_create(ctx._ctx, C.byref(p), C.byref(h)))
         else:
             a = arc if isinstance(arc, _lib.WallArc) else wall_arc(**arc)
@@ -1068,6 +1142,21 @@ class WallMap:
         a = _lib.WallArc()
         self._ctx._check(self._L.gm_wall_map_get_arc(self._h(), C.byref(a)))
         return a
+
+    @property
+    def clothoid(self):
+        """gm_wall_map_get_clothoid: dict(normal float64 [3], curvature, rate, point_chainage), or None on other maps."""
+        c = self.clothoid_struct()
+        if not c.struct_size:
+            return None
+        return dict(normal=np.array(c.normal[:], dtype=np.float64), curvature=float(c.curvature), rate=float(c.rate),
+                    point_chainage=float(c.point_chainage))
+
+    def clothoid_struct(self):
+        """The map's gm_wall_clothoid (all-zero on other maps), as the host helpers wall_clothoid_* take it."""
+        c = _lib.WallClothoid()
+        self._ctx._check(self._L.gm_wall_map_get_clothoid(self._h(), C.byref(c)))
+        return c
 
     def close(self):
         if self._map is not None:
@@ -1647,12 +1736,16 @@ class WallMap:
         return object_metrics(self.prm, obj, **params)
 
     def save(self, path):
-        """The parameters, the arc of a map on one, and the raw cells as one .npz (numpy only)."""
+        """The parameters, the arc or the clothoid of a map on one, and the raw cells as one .npz (numpy only)."""
         p = self.prm
         kw = {k: np.array(getattr(p, k)[:], dtype=np.float64) for k in _WALL_VEC}
         arc = self.arc
         if arc is not None:
             kw.update(arc_curvature=arc["curvature"], arc_point_chainage=np.float64(arc["point_chainage"]))
+        cl = self.clothoid
+        if cl is not None:
+            kw.update(clothoid_normal=cl["normal"], clothoid_scalars=np.array([cl["curvature"], cl["rate"], cl["point_chainage"]],
+                                                                              dtype=np.float64))
         np.savez_compressed(path, n_stations=np.uint32(p.n_stations), n_sectors=np.uint32(p.n_sectors),
                             station_length=np.float64(p.station_length), t_min=np.float64(p.t_min), gate=np.float64(p.gate),
                             radius=np.float64(p.radius), raw=self.read_raw(), **kw)
@@ -1664,6 +1757,9 @@ class WallMap:
             kw = {k: z[k].tolist() for k in _WALL_VEC}
             if "arc_curvature" in z.files:
                 kw["arc"] = dict(curvature=z["arc_curvature"].tolist(), point_chainage=float(z["arc_point_chainage"]))
+            if "clothoid_normal" in z.files:
+                k0, rate, s0 = (float(x) for x in z["clothoid_scalars"])
+                kw["clothoid"] = dict(normal=z["clothoid_normal"].tolist(), curvature=k0, rate=rate, point_chainage=s0)
             m = WallMap(ctx, n_stations=int(z["n_stations"]), n_sectors=int(z["n_sectors"]),
                         station_length=float(z["station_length"]), t_min=float(z["t_min"]), gate=float(z["gate"]),
                         radius=float(z["radius"]), **kw)

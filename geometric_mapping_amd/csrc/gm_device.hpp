@@ -302,11 +302,108 @@ struct WallArc {
     float n[3], b[3];          // n', b' in sensor coordinates
     float kappa, un, ub, vn, vb;
 };
-// the arc as a kernel argument: nothing on a straight map
+// A map on a clothoid design axis (gm_wall_map_create_clothoid): the arc block, whose kappa is then kappa_f at the anchor
+// section, plus the curvature's rate.
+struct WallClothoid {
+    WallArc arc;
+    float rate;
+};
+// The design axis a chain is instantiated for, and the axis as a kernel argument: nothing on a straight map.  (The
+// straight and the arc arguments are the two WallArcArg the kernels have always taken; the clothoid's is a type of its own.)
+enum : int { kAxisStraight = 0, kAxisArc = 1, kAxisClothoid = 2 };
 template <bool kArc>
-struct WallArcArg {};
+struct WallArcArg { static constexpr int kAxis = kAxisStraight; };
 template <>
-struct WallArcArg<true> { WallArc arc; };
+struct WallArcArg<true> {
+    static constexpr int kAxis = kAxisArc;
+    WallArc arc;
+};
+struct WallClothoidArg {
+    static constexpr int kAxis = kAxisClothoid;
+    WallClothoid cl;
+};
+
+// ---- the same chain on a clothoid design axis (include/gm_hip.h states it).  (o, a, n, b): the section at the anchor
+// station in sensor coordinates, kappa there, rate along the chainage.  The foot of the perpendicular by a start on the
+// osculating arc (on the tangent where |kappa| < 1e-6: a uniform branch) and GM_WALL_CLOTHOID_STEPS Newton steps, a fixed
+// count, so every grid and launch site gives the same bits.  Returns e; t: the arc length from the anchor section,
+// (yc, z): the offset in the point's own section; ok <= 0: the point is beyond_gate whatever e says (the start a quarter
+// turn away, a Newton denominator <= 0.25, a t that is not finite, a final |g| above GM_WALL_CLOTHOID_G_BOUND).
+// (sin, cos) of the header's sincos rule: a three-term reduction by pi / 2 and the two Cephes single-precision polynomials
+// on [-pi / 4, pi / 4], every operation rounded to nearest.  Fifteen of them per point: the library's sinf / cosf, each
+// with its large-argument reduction inlined, made the unrolled point loops too long to unroll and their per-item arrays
+// private memory.  An angle of 2^20 or more, or a NaN, gives NaN without an integer conversion (such a point is then
+// classed by its g).
+__device__ __forceinline__ void clothoid_sincos(float ps, float &sn, float &cs)
+{
+    const bool fin = fabsf(ps) < 1048576.0f;
+    const float k = fin ? rintf(__fmul_rn(ps, 0.63661977236758134f)) : 0.0f;
+    float r = __fmaf_rn(-k, 1.5703125f, ps);
+    r = __fmaf_rn(-k, 4.837512969970703125e-4f, r);
+    r = __fmaf_rn(-k, 7.54978995489188216e-8f, r);
+    const float z = __fmul_rn(r, r);
+    float ps_ = __fmaf_rn(-1.9515295891e-4f, z, 8.3321608736e-3f);
+    ps_ = __fmaf_rn(ps_, z, -1.6666654611e-1f);
+    const float s = __fmaf_rn(__fmul_rn(ps_, z), r, r);
+    float pc = __fmaf_rn(2.443315711809948e-5f, z, -1.388731625493765e-3f);
+    pc = __fmaf_rn(pc, z, 4.166664568298827e-2f);
+    const float c = __fadd_rn(__fmaf_rn(__fmul_rn(pc, z), z, __fmul_rn(-0.5f, z)), 1.0f);
+    const int q = (int)k & 3;
+    const float s1 = (q & 1) ? c : s, c1 = (q & 1) ? s : c;
+    const float nan = __builtin_nanf("");
+    sn = fin ? ((q & 2) ? -s1 : s1) : nan;
+    cs = fin ? (((q + 1) & 2) ? -c1 : c1) : nan;
+}
+// node i of the 4-node Gauss-Legendre rule on [0, 1]: (c_i, w_i) = (c, w)
+template <bool kFirst>
+__device__ __forceinline__ void clothoid_node(float kappa, float hr, float t, float c, float w, float &sx, float &sy)
+{
+    const float sg = __fmul_rn(t, c);
+    const float ps = __fmul_rn(__fmaf_rn(hr, sg, kappa), sg);
+    float sn, cs;
+    clothoid_sincos(ps, sn, cs);
+    sx = kFirst ? __fmul_rn(w, cs) : __fmaf_rn(cs, w, sx);
+    sy = kFirst ? __fmul_rn(w, sn) : __fmaf_rn(sn, w, sy);
+}
+// E(t) of the header: g and yc of the trial t
+__device__ __forceinline__ void clothoid_eval(float x, float y, float kappa, float hr, float t, float &g, float &yc)
+{
+    float sx, sy;
+    clothoid_node<true>(kappa, hr, t, 0.06943184420297371f, 0.17392742256872692f, sx, sy);
+    clothoid_node<false>(kappa, hr, t, 0.33000947820757187f, 0.32607257743127305f, sx, sy);
+    clothoid_node<false>(kappa, hr, t, 0.6699905217924281f, 0.32607257743127305f, sx, sy);
+    clothoid_node<false>(kappa, hr, t, 0.9305681557970262f, 0.17392742256872692f, sx, sy);
+    const float dx = __fsub_rn(x, __fmul_rn(t, sx)), dy = __fsub_rn(y, __fmul_rn(t, sy));
+    const float ps = __fmul_rn(__fmaf_rn(hr, t, kappa), t);
+    float sn, cs;
+    clothoid_sincos(ps, sn, cs);
+    g = __fmaf_rn(dx, cs, __fmul_rn(dy, sn));
+    yc = __fmaf_rn(dy, cs, -__fmul_rn(dx, sn));
+}
+__device__ __forceinline__ float clothoid_residual(const float4 &p, const float (&o)[3], const float (&a)[3], const float (&n)[3],
+                                                   const float (&b)[3], float kappa, float rate, float R, float &t, float &yc,
+                                                   float &z, float &ok)
+{
+    const float qx = __fsub_rn(p.x, o[0]), qy = __fsub_rn(p.y, o[1]), qz = __fsub_rn(p.z, o[2]);
+    const float x = surf_dot3(qx, qy, qz, a), y = surf_dot3(qx, qy, qz, n);
+    z = surf_dot3(qx, qy, qz, b);
+    const float cy = __fmaf_rn(-kappa, y, 1.0f);
+    t = fabsf(kappa) < 1.0e-6f ? x : __fdiv_rn(atan2f(__fmul_rn(kappa, x), cy), kappa);
+    const float hr = __fmul_rn(0.5f, rate);
+    bool good = cy > 0.0f;
+    float g;
+#pragma unroll
+    for (int it = 0; it < GM_WALL_CLOTHOID_STEPS; ++it) {
+        clothoid_eval(x, y, kappa, hr, t, g, yc);
+        const float den = __fmaf_rn(-__fmaf_rn(t, rate, kappa), yc, 1.0f);
+        good = good && den > 0.25f;
+        t = __fadd_rn(t, __fdiv_rn(g, den));
+    }
+    clothoid_eval(x, y, kappa, hr, t, g, yc);
+    good = good && fabsf(t) < __builtin_inff() && fabsf(g) <= GM_WALL_CLOTHOID_G_BOUND;
+    ok = good ? 1.0f : 0.0f;
+    return __fsub_rn(__fsqrt_rn(__fmaf_rn(yc, yc, __fmul_rn(z, z))), R);
+}
 
 // ---- the head of the chain against a map (k_wall_add*, the check's predicate, k_wall_align_bin): label, residual, gate,
 // station relative to the anchor, range, sector.  w: the WallArgs.  in_range(jl) is the caller's range rule (the map's
@@ -314,18 +411,24 @@ struct WallArcArg<true> { WallArc arc; };
 // gate and range.  The point's class goes to count(a literal kChain*); returns whether it is kChainMapped.  e is set
 // unless the point is plane, jl from kChainOutside on, kk for kChainMapped.
 enum : uint32_t { kChainPlane = 0u, kChainBeyondGate = 1u, kChainOutside = 2u, kChainMapped = 3u };
-template <bool kArc, class Args, class InRange, class Count>
-__device__ __forceinline__ bool wall_chain(const float4 &q, uint32_t lab, const Args &w, const WallArcArg<kArc> &c, InRange in_range,
-                                           Count count, float &e, float &jl, uint32_t &kk)
+template <class Axis, class Args, class InRange, class Count>
+__device__ __forceinline__ bool wall_chain(const float4 &q, uint32_t lab, const Args &w, const Axis &c, InRange in_range, Count count,
+                                           float &e, float &jl, uint32_t &kk)
 {
+    constexpr int kAxis = Axis::kAxis;
     if (lab == 1u) { count(kChainPlane); return false; }
-    float t, wx, wy, wz;   // (kArc: wx = yc, wy = z, wz = cy)
-    if constexpr (kArc) e = arc_residual(q, w.o, w.a, c.arc.n, c.arc.b, c.arc.kappa, w.R, t, wx, wy, wz);
+    float t, wx, wy, wz;   // (arc: wx = yc, wy = z, wz = cy; clothoid: wx = yc, wy = z, wz = ok)
+    if constexpr (kAxis == kAxisClothoid)
+        e = clothoid_residual(q, w.o, w.a, c.cl.arc.n, c.cl.arc.b, c.cl.arc.kappa, c.cl.rate, w.R, t, wx, wy, wz);
+    else if constexpr (kAxis == kAxisArc) e = arc_residual(q, w.o, w.a, c.arc.n, c.arc.b, c.arc.kappa, w.R, t, wx, wy, wz);
     else e = surf_residual(q, w.o, w.a, w.R, t, wx, wy, wz);
-    if (!(fabsf(e) <= w.gate) || (kArc && !(wz > 0.0f))) { count(kChainBeyondGate); return false; }
+    if (!(fabsf(e) <= w.gate) || (kAxis != kAxisStraight && !(wz > 0.0f))) { count(kChainBeyondGate); return false; }
     jl = surf_station(t, 0.0f, w.station_length);
     if (!in_range(jl)) { count(kChainOutside); return false; }
-    if constexpr (kArc) kk = arc_sector(wx, wy, c.arc.un, c.arc.ub, c.arc.vn, c.arc.vb, w.two_pi, w.sector_angle, w.n_sectors);
+    if constexpr (kAxis == kAxisClothoid)
+        kk = arc_sector(wx, wy, c.cl.arc.un, c.cl.arc.ub, c.cl.arc.vn, c.cl.arc.vb, w.two_pi, w.sector_angle, w.n_sectors);
+    else if constexpr (kAxis == kAxisArc)
+        kk = arc_sector(wx, wy, c.arc.un, c.arc.ub, c.arc.vn, c.arc.vb, w.two_pi, w.sector_angle, w.n_sectors);
     else kk = surf_sector(wx, wy, wz, w.u, w.v, w.two_pi, w.sector_angle, w.n_sectors);
     count(kChainMapped);
     return true;

@@ -329,6 +329,7 @@ size_t wall_table_bytes(uint64_t ncell);
 // n_cap: the most points the launch can see (the grid is sized by it); points_per_block 0: the default rule
 void launch_wall_add(const WallArgs &a, uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
 void launch_wall_add_arc(const WallArgs &a, const WallArc &arc, uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
+void launch_wall_add_clothoid(const WallArgs &a, const WallClothoid &cl, uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
 // k_wall_add_checked.hip (gm_wall_map_add_*_checked): mark the selected rows' points in a bit mask, then k_wall_add's masked
 // instantiation.  u64 words of the call's counter block: rows_neg, rows_pos, rows_kept, rows_rejected | skipped, mapped,
 // outside, beyond_gate, plane | n_rows, n_points, pad
@@ -352,6 +353,8 @@ void launch_wall_add_masked(const WallArgs &a, const unsigned long long *mask, u
                             uint32_t points_per_block, hipStream_t s);
 void launch_wall_add_arc_masked(const WallArgs &a, const WallArc &arc, const unsigned long long *mask, unsigned long long *ctr,
                                 uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
+void launch_wall_add_clothoid_masked(const WallArgs &a, const WallClothoid &cl, const unsigned long long *mask, unsigned long long *ctr,
+                                     uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
 // the class of one row: 0 selected negative, 1 selected positive, 2 kept, 3 rejected (delta_bits: the row's delta)
 __host__ __device__ inline uint32_t wall_mark_class(uint32_t delta_bits, long long dq, uint32_t index, uint32_t n_points,
                                                     uint32_t skip, long long S)
@@ -418,9 +421,16 @@ struct WallCloudArc {
     double ca[3], n[3], b[3];  // C - anchor, n, b
     double inv_kappa, un, ub, vn, vb;
 };
+// the clothoid position rule beside WallCloudArgs (oa, u, v not read either)
+struct WallCloudClothoid {
+    const double *rows;        // [nJ][5] (P(tc) - anchor)[3], cos psi, sin psi of the chunk's block rows (host-computed)
+    double n[3], b[3];
+    double un, ub, vn, vb;
+};
 void launch_wall_cloud_merge(const WallCloudArgs &a, hipStream_t s);
 void launch_wall_cloud_compact(const WallCloudArgs &a, const ScanState &st, hipStream_t s);
 void launch_wall_cloud_compact_arc(const WallCloudArgs &a, const WallCloudArc &arc, const ScanState &st, hipStream_t s);
+void launch_wall_cloud_compact_clothoid(const WallCloudArgs &a, const WallCloudClothoid &cl, const ScanState &st, hipStream_t s);
 // k_wall_mesh.hip (gm_wall_map_mesh): the cloud's compaction with an emit step that also stores the survivor's index
 // (rank_base + its rank in the chunk) into rank[block of the window] and, for a step cut, its mean into mean[block]; then
 // per chunk of whole quad rows one k_compact over the chunk's 2 * quads slots
@@ -440,6 +450,8 @@ void launch_wall_mesh_vertices(const WallCloudArgs &a, uint32_t *rank, float *me
                                hipStream_t s);
 void launch_wall_mesh_vertices_arc(const WallCloudArgs &a, const WallCloudArc &arc, uint32_t *rank, float *mean, uint32_t rank_base,
                                    const ScanState &st, hipStream_t s);
+void launch_wall_mesh_vertices_clothoid(const WallCloudArgs &a, const WallCloudClothoid &cl, uint32_t *rank, float *mean,
+                                        uint32_t rank_base, const ScanState &st, hipStream_t s);
 void launch_wall_mesh_triangles(const WallMeshArgs &a, const ScanState &st, hipStream_t s);
 // k_wall_check.hip (gm_wall_map_check_*): one k_compact launch per check
 // u64 words: the seven classes (GM_WALL_CHECK_CLS_* order), peak_pos, -peak_neg, the changed points (low word), n_points, pad
@@ -457,6 +469,7 @@ struct WallCheckArgs {
 // n_cap: the most points the launch can see (the grid is sized by it)
 void launch_wall_check(const WallCheckArgs &a, uint32_t n_cap, const ScanState &st, hipStream_t s);
 void launch_wall_check_arc(const WallCheckArgs &a, const WallArc &arc, uint32_t n_cap, const ScanState &st, hipStream_t s);
+void launch_wall_check_clothoid(const WallCheckArgs &a, const WallClothoid &cl, uint32_t n_cap, const ScanState &st, hipStream_t s);
 // the rule's integers, shared by the kernel and gm_wall_check_classify
 __host__ __device__ inline long long wall_check_fix(float e)   // (int64) rint(e 2^20), saturating at int32, 0 for a NaN
 {

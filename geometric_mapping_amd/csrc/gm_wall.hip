@@ -29,13 +29,14 @@ static void add_window(const gm_wall_params &p, double reach_stations, WallArgs 
     }
 }
 
-void launch_add(gm_wall_map *m, const WallArgs &w, const WallArc &arc, uint32_t n_cap, hipStream_t s)
+void launch_add(gm_wall_map *m, const WallArgs &w, const WallClothoid &ax, uint32_t n_cap, hipStream_t s)
 {
-    if (m->is_arc()) launch_wall_add_arc(w, arc, n_cap, m->points_per_block, s);
+    if (m->is_clothoid()) launch_wall_add_clothoid(w, ax, n_cap, m->points_per_block, s);
+    else if (m->is_arc()) launch_wall_add_arc(w, ax.arc, n_cap, m->points_per_block, s);
     else launch_wall_add(w, n_cap, m->points_per_block, s);
 }
 
-gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info *info, WallArgs &w, WallFrame64 *f64, WallArc *arc)
+gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info *info, WallArgs &w, WallFrame64 *f64, WallClothoid *ax)
 {
     gm_ctx *ctx = m->ctx;
     if (!pose) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: NULL pose");
@@ -46,10 +47,34 @@ gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info
     const gm_wall_params &p = m->prm;
     const DesignFrame &d = m->frame;
     const double ds = p.station_length;
-    // what the two axes compute: (o', a', u', v') rounded once, the arc block, the anchor, the crop cube's reach in stations
+    // what the three axes compute: (o', a', u', v') rounded once, the axis block, the anchor, the crop cube's reach in stations
     double reach;
-    if (m->is_arc()) {   // (include/gm_hip.h: per add)
-        if (!arc) return gm_fail(ctx, GM_ERR_UNSUPPORTED, "gm_wall_map: this call is not available on a map with an arc design axis");
+    if ((m->is_arc() || m->is_clothoid()) && !ax)
+        return gm_fail(ctx, GM_ERR_UNSUPPORTED, "gm_wall_map: this call is not available on a map with an arc or a clothoid design axis");
+    if (m->is_clothoid()) {   // (include/gm_hip.h: per add)
+        gm_wall_clothoid_add_info ai;
+        double u64[3], v64[3], a1 = 0.0;
+        if (!clothoid_add_frame(p, d, m->cf, Rm, tr, ai, u64, v64, &a1))
+            return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose is too far along the axis");
+        memset(&w, 0, sizeof(w));
+        WallArc *arc = &ax->arc;
+        for (int k = 0; k < 3; ++k) {
+            w.o[k] = ai.o[k]; w.a[k] = ai.a[k]; w.u[k] = (float)u64[k]; w.v[k] = (float)v64[k];
+            arc->n[k] = ai.n[k]; arc->b[k] = ai.b[k];
+        }
+        arc->kappa = ai.kappa;
+        arc->un = ai.un; arc->ub = ai.ub; arc->vn = ai.vn; arc->vb = ai.vb;
+        ax->rate = ai.rate;
+        w.anchor = ai.anchor_station;
+        // The LDS window, which affects speed only (a mapped point outside it goes to the map directly), sized from the
+        // largest |kappa| of the map: a mapped point and the sensor both lie within rho = R + gate of the axis, and
+        // rho max |kappa| <= 0.5 (a refusal of the creation), where the foot of the perpendicular moves by at most
+        // 1 / (1 - rho max |kappa|) <= 2 times the distance between two points.  A point of the crop cube |p|_inf <= B is
+        // within sqrt(3) B of the sensor, whose own foot lies less than ds past the anchor section: |t| <= 2 sqrt(3) B + ds
+        // (the one station goes into add_window's slack).  The tangent turns along the reach, so |a'|_1 does not sharpen it.
+        reach = 2.0 * ctx->cfg.boxFilterBound * 1.7320508075688772 / ds;
+    } else if (m->is_arc()) {   // (include/gm_hip.h: per add)
+        WallArc *arc = &ax->arc;
         gm_wall_arc_add_info ai;
         double u64[3], v64[3], a1 = 0.0;
         if (!arc_add_frame(p, d, m->af, Rm, tr, ai, u64, v64, &a1))
@@ -217,6 +242,7 @@ gm_status check_baseline(gm_wall_map *map, gm_wall_map *baseline, const char *wh
         memcmp(&p.radius, &b.radius, 8) || memcmp(p.up, b.up, 24) || memcmp(p.forward, b.forward, 24))
         return refuse(": the baseline is a map on another grid");
     if (memcmp(&map->arc, &baseline->arc, sizeof(gm_wall_arc))) return refuse(": the baseline is a map on another arc");
+    if (memcmp(&map->clothoid, &baseline->clothoid, sizeof(gm_wall_clothoid))) return refuse(": the baseline is a map on another clothoid");
     return GM_OK;
 }
 
@@ -338,7 +364,17 @@ gm_status cloud_chunks(gm_wall_map *map, const gm_wall_cloud_params &cp, gm_wall
     a.ds = map->prm.station_length;
     a.out = map->cl_stage.p;
     a.ctr = map->cl_ctr.p;
-    const bool on_arc = map->is_arc();
+    const bool on_arc = map->is_arc(), on_cl = map->is_clothoid();
+    WallCloudClothoid cc;
+    memset(&cc, 0, sizeof(cc));
+    if (on_cl) {
+        const ClothoidFrame &f = map->cf;
+        GMW_HIP(ctx, map->cl_rows.reserve((uint64_t)rows * 5));
+        map->cl_rows_host.resize((size_t)rows * 5);
+        cc.rows = map->cl_rows.p;
+        for (int k = 0; k < 3; ++k) { cc.n[k] = f.n[k]; cc.b[k] = f.b[k]; }
+        cc.un = f.un; cc.ub = f.ub; cc.vn = f.vn; cc.vb = f.vb;
+    }
     WallCloudArc ca;
     memset(&ca, 0, sizeof(ca));
     if (on_arc) {
@@ -373,8 +409,27 @@ gm_status cloud_chunks(gm_wall_map *map, const gm_wall_cloud_params &cp, gm_wall
             }   // (the last chunk's copy has been waited for: every trip ends with a synchronisation)
             GMW_HIP(ctx, hipMemcpyAsync(map->cl_rows.p, map->cl_rows_host.data(), (size_t)a.nJ * 16, hipMemcpyHostToDevice, map->stream));
         }
+        if (on_cl) {   // (P(tc) - anchor, cos psi, sin psi) of the chunk's block rows: tc by the emit step's rule
+            const ClothoidFrame &f = map->cf;
+            for (uint32_t jl = 0; jl < a.nJ; ++jl) {
+                const uint32_t jw = (J0 + jl) * bs, ns = std::min(n - jw, bs);
+                const double h = (double)(2u * (station0 + jw) + ns) * 0.5;
+                const double tc = a.t_min + h * a.ds;
+                double as[3], nsec_[3], P[3];
+                const double tau = tc - f.s0;
+                clothoid_section(d, f, tau, as, nsec_, P);
+                const double psi = f.psi(tau);
+                double *row = &map->cl_rows_host[5 * (size_t)jl];
+                for (int k = 0; k < 3; ++k) row[k] = P[k] - cp.anchor[k];
+                row[3] = cos(psi);
+                row[4] = sin(psi);
+            }   // (the last chunk's copy has been waited for: every trip ends with a synchronisation)
+            GMW_HIP(ctx, hipMemcpyAsync(map->cl_rows.p, map->cl_rows_host.data(), (size_t)a.nJ * 40, hipMemcpyHostToDevice, map->stream));
+        }
         const ScanState st = map->cl_scan.next(map->stream);
-        if (mesh && on_arc) launch_wall_mesh_vertices_arc(a, ca, mesh->rank, mesh->mean, (uint32_t)total, st, map->stream);
+        if (mesh && on_cl) launch_wall_mesh_vertices_clothoid(a, cc, mesh->rank, mesh->mean, (uint32_t)total, st, map->stream);
+        else if (on_cl) launch_wall_cloud_compact_clothoid(a, cc, st, map->stream);
+        else if (mesh && on_arc) launch_wall_mesh_vertices_arc(a, ca, mesh->rank, mesh->mean, (uint32_t)total, st, map->stream);
         else if (mesh) launch_wall_mesh_vertices(a, mesh->rank, mesh->mean, (uint32_t)total, st, map->stream);
         else if (on_arc) launch_wall_cloud_compact_arc(a, ca, st, map->stream);
         else launch_wall_cloud_compact(a, st, map->stream);
@@ -408,8 +463,9 @@ void gm_wall_free_all(gm_ctx *ctx)
 
 extern "C" {
 
-// gm_wall_map_create (arc NULL) and gm_wall_map_create_arc
-static gm_status create_map(gm_ctx *ctx, const gm_wall_params *params, const gm_wall_arc *arc, gm_wall_map **map)
+// gm_wall_map_create (arc and cl NULL), gm_wall_map_create_arc and gm_wall_map_create_clothoid
+static gm_status create_map(gm_ctx *ctx, const gm_wall_params *params, const gm_wall_arc *arc, const gm_wall_clothoid *cl,
+                            gm_wall_map **map)
 {
     if (!ctx) return GM_ERR_INVALID_ARG;
     if (!map) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_create: NULL map");
@@ -421,6 +477,14 @@ static gm_status create_map(gm_ctx *ctx, const gm_wall_params *params, const gm_
     memset(&arc_f, 0, sizeof(arc_f));
     if (arc && arc_check(params, arc, arc_d, arc_f) != GM_OK)
         return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_create_arc: struct_size mismatch, or a curvature outside its limits for this map");
+    ClothoidFrame cl_f;
+    if (cl) {
+        const gm_status st = clothoid_check(params, cl, arc_d, cl_f);
+        if (st == GM_ERR_OOM) return gm_fail(ctx, GM_ERR_OOM, "gm_wall_map_create_clothoid: no memory for the table of station starts");
+        if (st != GM_OK)
+            return gm_fail(ctx, GM_ERR_INVALID_ARG,
+                           "gm_wall_map_create_clothoid: struct_size mismatch, or a normal, curvature or rate outside its limits for this map");
+    }
     GMW_OK(set_device(ctx));
     gm_wall_map *m = new gm_wall_map;
     m->ctx = ctx;
@@ -469,6 +533,9 @@ static gm_status create_map(gm_ctx *ctx, const gm_wall_params *params, const gm_
     m->arc.struct_size = (uint32_t)sizeof(gm_wall_arc);
     if (arc) { m->arc = *arc; m->arc.reserved = 0u; }
     m->af = arc_f;
+    memset(&m->clothoid, 0, sizeof(m->clothoid));
+    if (cl) m->clothoid = *cl;
+    m->cf = std::move(cl_f);
     auto body = [&]() -> gm_status {
         GMW_HIP(ctx, hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
         GMW_HIP(ctx, m->base.reserve(wall_table_bytes(m->ncell)));
@@ -489,14 +556,32 @@ static gm_status create_map(gm_ctx *ctx, const gm_wall_params *params, const gm_
     return GM_OK;
 }
 
-gm_status gm_wall_map_create(gm_ctx *ctx, const gm_wall_params *params, gm_wall_map **map) { return create_map(ctx, params, nullptr, map); }
+gm_status gm_wall_map_create(gm_ctx *ctx, const gm_wall_params *params, gm_wall_map **map)
+{
+    return create_map(ctx, params, nullptr, nullptr, map);
+}
 
 gm_status gm_wall_map_create_arc(gm_ctx *ctx, const gm_wall_params *params, const gm_wall_arc *arc, gm_wall_map **map)
 {
     if (!ctx) return GM_ERR_INVALID_ARG;
     if (map) *map = nullptr;
     if (!arc) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_create_arc: NULL arc");
-    return create_map(ctx, params, arc, map);
+    return create_map(ctx, params, arc, nullptr, map);
+}
+
+gm_status gm_wall_map_create_clothoid(gm_ctx *ctx, const gm_wall_params *params, const gm_wall_clothoid *clothoid, gm_wall_map **map)
+{
+    if (!ctx) return GM_ERR_INVALID_ARG;
+    if (map) *map = nullptr;
+    if (!clothoid) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_create_clothoid: NULL clothoid");
+    return create_map(ctx, params, nullptr, clothoid, map);
+}
+
+gm_status gm_wall_map_get_clothoid(gm_wall_map *map, gm_wall_clothoid *clothoid)
+{
+    if (!map || !clothoid) return GM_ERR_INVALID_ARG;
+    *clothoid = map->clothoid;
+    return GM_OK;
 }
 
 gm_status gm_wall_map_get_arc(gm_wall_map *map, gm_wall_arc *arc)
@@ -519,12 +604,12 @@ gm_status gm_wall_map_add_frame(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, co
     Slot *sl = nullptr;
     GMW_OK(frame_call_head(map, ctx, slot, "gm_wall_map_add_frame", [] { return true; }, sl));
     WallArgs w;
-    WallArc arc;
-    GMW_OK(add_frame_args(map, pose, add_info, w, nullptr, &arc));
+    WallClothoid ax;
+    GMW_OK(add_frame_args(map, pose, add_info, w, nullptr, &ax));
     GMW_OK(set_device(ctx));
     frame_points(ctx, *sl, w);
     GMW_OK(add_wait_readers(map, slot, sl->stream));
-    launch_add(map, w, arc, sl->n_in, sl->stream);
+    launch_add(map, w, ax, sl->n_in, sl->stream);
     GMW_HIP(ctx, hipGetLastError());
     map->pending[slot] = 1;
     ++map->frames;
@@ -538,14 +623,14 @@ gm_status gm_wall_map_add_points(gm_wall_map *map, const float *xyz, uint32_t n,
     gm_ctx *ctx = map->ctx;
     if (n && !xyz) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_add_points: NULL xyz");
     WallArgs w;
-    WallArc arc;
-    GMW_OK(add_frame_args(map, pose, add_info, w, nullptr, &arc));
+    WallClothoid ax;
+    GMW_OK(add_frame_args(map, pose, add_info, w, nullptr, &ax));
     StageCall sc{map, n, residual, cell, nullptr, nullptr};
     GMW_OK(sc.open());
     GMW_OK(sc.upload(xyz, labels, w));
     hipStream_t s = sc.sl->stream;
     GMW_OK(add_wait_readers(map, 0, s));   // (as gm_wall_map_add_frame; the staging slot is slot 0)
-    launch_add(map, w, arc, n, s);
+    launch_add(map, w, ax, n, s);
     GMW_HIP(ctx, hipGetLastError());
     GMW_OK(sc.close());
     ++map->frames;

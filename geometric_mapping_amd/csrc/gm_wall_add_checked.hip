@@ -15,7 +15,7 @@ uint64_t block_words(uint32_t n_cap) { return kWallAddCheckedCounters + ((uint64
 
 // What one call enqueues on `s`, in this order: its block -- counters | mask words of n_cap points -- zeroed by ONE fill, the
 // mark over up to rows_cap rows, the masked add.  mk: rows, counts and parameters filled by the caller; blk: the call's.
-gm_status add_checked_enqueue(gm_wall_map *m, WallMarkArgs &mk, const WallArgs &w, const WallArc &arc, uint32_t n_cap,
+gm_status add_checked_enqueue(gm_wall_map *m, WallMarkArgs &mk, const WallArgs &w, const WallClothoid &ax, uint32_t n_cap,
                               DevArray<unsigned long long> &blk, hipStream_t s)
 {
     gm_ctx *ctx = m->ctx;
@@ -24,7 +24,8 @@ gm_status add_checked_enqueue(gm_wall_map *m, WallMarkArgs &mk, const WallArgs &
     mk.ctr = blk.p;
     mk.mask = reinterpret_cast<uint32_t *>(blk.p + kWallAddCheckedCounters);
     launch_wall_mark(mk, mk.rows_cap, s);
-    if (m->is_arc()) launch_wall_add_arc_masked(w, arc, blk.p + kWallAddCheckedCounters, blk.p, n_cap, m->points_per_block, s);
+    if (m->is_clothoid()) launch_wall_add_clothoid_masked(w, ax, blk.p + kWallAddCheckedCounters, blk.p, n_cap, m->points_per_block, s);
+    else if (m->is_arc()) launch_wall_add_arc_masked(w, ax.arc, blk.p + kWallAddCheckedCounters, blk.p, n_cap, m->points_per_block, s);
     else launch_wall_add_masked(w, blk.p + kWallAddCheckedCounters, blk.p, n_cap, m->points_per_block, s);
     GMW_HIP(ctx, hipGetLastError());
     return GM_OK;
@@ -57,8 +58,8 @@ gm_status gm_wall_map_add_frame_checked(gm_wall_map *map, gm_ctx *ctx, uint32_t 
     Slot *sl = nullptr;
     GMW_OK(frame_call_head(map, ctx, slot, "gm_wall_map_add_frame_checked", [&] { return add_checked_prm_ok(ap, mk.S); }, sl));
     WallArgs w;
-    WallArc arc;
-    GMW_OK(add_frame_args(map, pose, add_info, w, nullptr, &arc));
+    WallClothoid ax;
+    GMW_OK(add_frame_args(map, pose, add_info, w, nullptr, &ax));
     WallCheckSlot &c = map->checks[slot];
     if (!c.res.have || c.cloud_seq != sl->cloud_seq)
         return gm_fail(ctx, GM_ERR_NOT_READY, "gm_wall_map_add_frame_checked: no check was enqueued on this map and slot for the frame the slot holds");
@@ -77,7 +78,7 @@ gm_status gm_wall_map_add_frame_checked(gm_wall_map *map, gm_ctx *ctx, uint32_t 
     mk.n_host = w.n_host;
     mk.skip = ap.skip;
     GMW_OK(add_wait_readers(map, slot, sl->stream));
-    GMW_OK(add_checked_enqueue(map, mk, w, arc, n_cap, ac.blk, sl->stream));
+    GMW_OK(add_checked_enqueue(map, mk, w, ax, n_cap, ac.blk, sl->stream));
     GMW_HIP(ctx, hipMemcpyAsync(ac.h_ctr.p, ac.blk.p, kWallAddCheckedCounters * 8, hipMemcpyDeviceToHost, sl->stream));
     GMW_OK(ac.res.record(ctx, sl->stream));
     ac.status = map->frame.status;
@@ -116,8 +117,8 @@ gm_status gm_wall_map_add_points_checked(gm_wall_map *map, const float *xyz, uin
     if (!add_checked_prm_ok(ap, mk.S))
         return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_add_points_checked: struct_size mismatch or a parameter outside its limits");
     WallArgs w;
-    WallArc arc;
-    GMW_OK(add_frame_args(map, pose, add_info, w, nullptr, &arc));
+    WallClothoid ax;
+    GMW_OK(add_frame_args(map, pose, add_info, w, nullptr, &ax));
     StageCall sc{map, n, residual, cell, nullptr, nullptr};
     GMW_OK(sc.open());
     GMW_OK(sc.upload(xyz, labels, w));
@@ -130,7 +131,7 @@ gm_status gm_wall_map_add_points_checked(gm_wall_map *map, const float *xyz, uin
     mk.n_host = n;
     mk.skip = ap.skip;
     GMW_OK(add_wait_readers(map, 0, s));   // (as gm_wall_map_add_points; the staging slot is slot 0)
-    GMW_OK(add_checked_enqueue(map, mk, w, arc, n, map->ac_blk, s));
+    GMW_OK(add_checked_enqueue(map, mk, w, ax, n, map->ac_blk, s));
     unsigned long long h[kWallAddCheckedCounters];
     GMW_HIP(ctx, hipMemcpyAsync(h, map->ac_blk.p, sizeof(h), hipMemcpyDeviceToHost, s));
     GMW_OK(sc.close());   // (blocks: h is filled)

@@ -81,6 +81,26 @@ struct WallCloudOnArc {
     }
 };
 
+// the clothoid position rule (a map of gm_wall_map_create_clothoid): p = ((P(tc) - anchor) + yc n(tc)) + zb b, with
+// P(tc) - anchor and (cos, sin) of the block row's psi from the host's table: no fp64 trigonometry and no quadrature here
+struct WallCloudOnClothoid {
+    WallCloudClothoid cl;
+    __device__ __forceinline__ void operator()(const WallCloudArgs &a, uint32_t jl, double, double rho, double c, double s,
+                                               float (&xyz)[3]) const
+    {
+        const double *row = cl.rows + 5u * (size_t)jl;
+        const double cp = row[3], sp = row[4];
+        const double yc = __dmul_rn(rho, __dadd_rn(__dmul_rn(c, cl.un), __dmul_rn(s, cl.vn)));
+        const double zb = __dmul_rn(rho, __dadd_rn(__dmul_rn(c, cl.ub), __dmul_rn(s, cl.vb)));
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const double nr = __dsub_rn(__dmul_rn(cl.n[i], cp), __dmul_rn(a.a[i], sp));
+            const double q = __dadd_rn(__dadd_rn(row[i], __dmul_rn(yc, nr)), __dmul_rn(zb, cl.b[i]));
+            xyz[i] = __double2float_rn(q);
+        }
+    }
+};
+
 // the record of survivor `src` of the chunk at rank `dst`, its position by `pos`
 template <class Position>
 __device__ __forceinline__ void wc_emit(const WallCloudArgs &a, const Position &pos, uint32_t src, uint32_t dst,
@@ -135,6 +155,18 @@ struct WallCloudEmitArc {
     static constexpr bool kHasFinish = true, kHasPrepare = true;
     WallCloudArgs a;
     WallCloudOnArc pos;
+    __device__ __forceinline__ void prepare() const { wc_prepare(); }
+    __device__ __forceinline__ void finish(uint32_t) const { wc_finish(a); }
+    __device__ __forceinline__ void operator()(uint32_t src, uint32_t dst, const WallCloudPred::Payload &p) const
+    {
+        wc_emit(a, pos, src, dst, p);
+    }
+};
+// a map of gm_wall_map_create_clothoid: likewise
+struct WallCloudEmitClothoid {
+    static constexpr bool kHasFinish = true, kHasPrepare = true;
+    WallCloudArgs a;
+    WallCloudOnClothoid pos;
     __device__ __forceinline__ void prepare() const { wc_prepare(); }
     __device__ __forceinline__ void finish(uint32_t) const { wc_finish(a); }
     __device__ __forceinline__ void operator()(uint32_t src, uint32_t dst, const WallCloudPred::Payload &p) const

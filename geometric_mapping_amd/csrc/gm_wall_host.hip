@@ -147,6 +147,174 @@ bool arc_add_frame(const gm_wall_params &p, const DesignFrame &d, const ArcFrame
     return true;
 }
 
+// ---- a clothoid design axis (include/gm_hip.h: gm_wall_map_create_clothoid) ----
+
+// the 8-node Gauss-Legendre rule on [-1, 1]
+static const double kGl8X[8] = {-0.9602898564975362, -0.7966664774136267, -0.525532409916329, -0.18343464249564978,
+                                0.18343464249564978, 0.525532409916329,   0.7966664774136267, 0.9602898564975362};
+static const double kGl8W[8] = {0.10122853629037669, 0.22238103445337434, 0.31370664587788705, 0.36268378337836177,
+                                0.36268378337836177, 0.31370664587788705, 0.22238103445337434, 0.10122853629037669};
+
+// I(ta, tb) of the header, added to (X, Y)
+static void clothoid_integrate(const ClothoidFrame &f, double ta, double tb, double &X, double &Y)
+{
+    const double ka = fabs(f.kappa(ta)), kb = fabs(f.kappa(tb));
+    const double load = std::min(std::max(ka, kb) * fabs(tb - ta) / 0.25, 4095.0);
+    const int K = 1 + (load >= 0.0 ? (int)load : 0);   // (a NaN: one panel; the caller refuses what is not finite)
+    const double w = (tb - ta) / (double)K, h = 0.5 * w;
+    double sx_all = 0.0, sy_all = 0.0;
+    for (int q = 0; q < K; ++q) {
+        const double mid = ta + ((double)q + 0.5) * w;
+        double sx = 0.0, sy = 0.0;
+        for (int i = 0; i < 8; ++i) {
+            const double ps = f.psi(mid + h * kGl8X[i]);
+            sx += kGl8W[i] * cos(ps);
+            sy += kGl8W[i] * sin(ps);
+        }
+        sx_all += h * sx;
+        sy_all += h * sy;
+    }
+    X += sx_all;
+    Y += sy_all;
+}
+
+gm_status clothoid_check(const gm_wall_params *p, const gm_wall_clothoid *cl, DesignFrame &d, ClothoidFrame &f)
+{
+    if (check_params(p) != GM_OK || !cl || cl->struct_size != sizeof(gm_wall_clothoid) || cl->reserved != 0u) return GM_ERR_INVALID_ARG;
+    if (!isfinite(cl->normal[0]) || !isfinite(cl->normal[1]) || !isfinite(cl->normal[2]) || !isfinite(cl->curvature) ||
+        !isfinite(cl->rate) || !isfinite(cl->point_chainage))
+        return GM_ERR_INVALID_ARG;
+    design_frame_of(*p, d);
+    f = ClothoidFrame();
+    const double na = dot(cl->normal, d.a);
+    double m[3];
+    for (int k = 0; k < 3; ++k) m[k] = cl->normal[k] - na * d.a[k];
+    const double lm = sqrt(dot(m, m)), l0 = sqrt(dot(cl->normal, cl->normal));
+    if (!isfinite(lm) || !(lm > 1e-6 * l0) || !(lm > 0.0)) return GM_ERR_INVALID_ARG;
+    const double L = (double)p->n_stations * p->station_length;
+    if (fabs(cl->rate) * L < 1e-6) return GM_ERR_INVALID_ARG;
+    f.k0 = cl->curvature;
+    f.rate = cl->rate;
+    f.s0 = cl->point_chainage;
+    f.tau0 = p->t_min - f.s0;
+    f.ds = p->station_length;
+    f.nst = p->n_stations;
+    const double t0 = f.tau0, t1 = f.tau0 + L;
+    const double kmax = std::max(fabs(f.kappa(t0)), fabs(f.kappa(t1)));
+    if (!((p->radius + p->gate) * kmax <= 0.5)) return GM_ERR_INVALID_ARG;
+    if (!(fabs(f.psi(t0)) <= 3.0) || !(fabs(f.psi(t1)) <= 3.0)) return GM_ERR_INVALID_ARG;
+    const double tz = -f.k0 / f.rate;   // kappa = 0 there
+    if (t0 < tz && tz < t1 && !(fabs(f.psi(tz)) <= 3.0)) return GM_ERR_INVALID_ARG;
+    for (int k = 0; k < 3; ++k) { f.pt[k] = p->point[k]; f.n[k] = m[k] / lm; }
+    const double *a = d.a, *n = f.n;
+    f.b[0] = a[1] * n[2] - a[2] * n[1]; f.b[1] = a[2] * n[0] - a[0] * n[2]; f.b[2] = a[0] * n[1] - a[1] * n[0];
+    f.un = dot(d.u, f.n); f.ub = dot(d.u, f.b);
+    f.vn = dot(d.v, f.n); f.vb = dot(d.v, f.b);
+    try {
+        f.tab.assign(2 * ((size_t)f.nst + 1), 0.0);
+    } catch (...) {
+        return GM_ERR_OOM;
+    }
+    double X = 0.0, Y = 0.0;
+    clothoid_integrate(f, 0.0, f.tau0, X, Y);
+    f.tab[0] = X; f.tab[1] = Y;
+    for (uint32_t j = 0; j < f.nst; ++j) {
+        clothoid_integrate(f, f.tau0 + (double)j * f.ds, f.tau0 + (double)(j + 1u) * f.ds, X, Y);
+        f.tab[2 * ((size_t)j + 1)] = X; f.tab[2 * ((size_t)j + 1) + 1] = Y;
+    }
+    f.on = true;
+    return GM_OK;
+}
+
+void clothoid_xy(const ClothoidFrame &f, double tau, double &X, double &Y)
+{
+    const double jd = floor((tau - f.tau0) / f.ds);
+    const size_t j = jd >= 0.0 ? (jd < (double)f.nst ? (size_t)jd : (size_t)f.nst) : 0;   // (a NaN: 0)
+    X = f.tab[2 * j];
+    Y = f.tab[2 * j + 1];
+    clothoid_integrate(f, f.tau0 + (double)j * f.ds, tau, X, Y);
+}
+
+double clothoid_section(const DesignFrame &d, const ClothoidFrame &f, double tau, double as[3], double ns[3], double P[3])
+{
+    const double psi = f.psi(tau);
+    const double cp = cos(psi), sp = sin(psi);
+    double X, Y;
+    clothoid_xy(f, tau, X, Y);
+    for (int k = 0; k < 3; ++k) {
+        as[k] = d.a[k] * cp + f.n[k] * sp;
+        ns[k] = f.n[k] * cp - d.a[k] * sp;
+        P[k] = (f.pt[k] + X * d.a[k]) + Y * f.n[k];
+    }
+    return f.kappa(tau);
+}
+
+double clothoid_foot(const DesignFrame &d, const ClothoidFrame &f, const double x[3], double *yc_out, double *g_out)
+{
+    const double r[3] = {x[0] - f.pt[0], x[1] - f.pt[1], x[2] - f.pt[2]};
+    const double xa = dot(r, d.a), xn = dot(r, f.n);
+    size_t best = 0;
+    double best_d2 = INFINITY;
+    for (size_t j = 0; j <= (size_t)f.nst; ++j) {
+        const double ex = xa - f.tab[2 * j], ey = xn - f.tab[2 * j + 1];
+        const double d2 = ex * ex + ey * ey;
+        if (d2 < best_d2) { best_d2 = d2; best = j; }
+    }
+    double tau = f.tau0 + (double)best * f.ds, g = 0.0, yc = 0.0;
+    for (int it = 0; it <= GM_WALL_CLOTHOID_HOST_STEPS; ++it) {
+        double X, Y;
+        clothoid_xy(f, tau, X, Y);
+        const double psi = f.psi(tau);
+        const double c = cos(psi), s = sin(psi);
+        const double dx = xa - X, dy = xn - Y;
+        g = dx * c + dy * s;
+        yc = dy * c - dx * s;
+        if (it < GM_WALL_CLOTHOID_HOST_STEPS) tau = tau + g / (1.0 - f.kappa(tau) * yc);
+    }
+    if (yc_out) *yc_out = yc;
+    if (g_out) *g_out = g;
+    return tau;
+}
+
+bool clothoid_add_frame(const gm_wall_params &p, const DesignFrame &d, const ClothoidFrame &f, const double Rm[3][3],
+                        const double tr[3], gm_wall_clothoid_add_info &out, double *u64, double *v64, double *a1)
+{
+    const double ds = p.station_length;
+    const double tau = clothoid_foot(d, f, tr, nullptr, nullptr);
+    const double s = f.s0 + tau;
+    const double jd = floor((tau - f.tau0) / ds);   // (s - t_min, taken in tau: moving s0 and t_min together moves no anchor)
+    if (!(fabs(jd) < 4.0e18)) return false;
+    const double sf = p.t_min + jd * ds;
+    double as[3], ns[3], P[3];
+    // (s_f - s0 as tau_0 + j_f ds: the chainage's size does not enter)
+    const double kf = clothoid_section(d, f, f.tau0 + jd * ds, as, ns, P);
+    const double of[3] = {P[0] - tr[0], P[1] - tr[1], P[2] - tr[2]};
+    out.anchor_station = (int64_t)jd;
+    out.sensor_chainage = s;
+    out.anchor_chainage = sf;
+    double l1 = 0.0;
+    for (int c = 0; c < 3; ++c) {   // Rm^T x
+        const double oo = Rm[0][c] * of[0] + Rm[1][c] * of[1] + Rm[2][c] * of[2];
+        const double aa = Rm[0][c] * as[0] + Rm[1][c] * as[1] + Rm[2][c] * as[2];
+        const double nn = Rm[0][c] * ns[0] + Rm[1][c] * ns[1] + Rm[2][c] * ns[2];
+        const double bb = Rm[0][c] * f.b[0] + Rm[1][c] * f.b[1] + Rm[2][c] * f.b[2];
+        out.o[c] = (float)oo; out.a[c] = (float)aa; out.n[c] = (float)nn; out.b[c] = (float)bb;
+        if (u64) u64[c] = f.un * nn + f.ub * bb;
+        if (v64) v64[c] = f.vn * nn + f.vb * bb;
+        l1 += fabs(aa);
+    }
+    if (a1) *a1 = l1;
+    out.kappa = (float)kf;
+    out.rate = (float)f.rate;
+    out.un = (float)f.un; out.ub = (float)f.ub; out.vn = (float)f.vn; out.vb = (float)f.vb;
+    out.R = (float)d.R;
+    out.station_length = (float)ds;
+    out.sector_angle = (float)(kTwoPi / (double)p.n_sectors);
+    out.gate = (float)p.gate;
+    out.reserved[0] = out.reserved[1] = 0u;
+    return true;
+}
+
 int pose_split(const double pose[12], double Rm[3][3], double tr[3])
 {
     for (int r = 0; r < 3; ++r) {
@@ -626,6 +794,77 @@ gm_status gm_wall_arc_point(const gm_wall_params *params, const gm_wall_arc *arc
         const double nr = f.n[k] * cp - d.a[k] * sp;
         xyz[k] = (f.C[k] + r * nr) + zb * f.b[k];
     }
+    return GM_OK;
+}
+
+gm_status gm_wall_clothoid_check_params(const gm_wall_params *params, const gm_wall_clothoid *clothoid)
+{
+    DesignFrame d;
+    ClothoidFrame f;
+    return clothoid_check(params, clothoid, d, f) == GM_OK ? GM_OK : GM_ERR_INVALID_ARG;
+}
+
+gm_status gm_wall_clothoid_add_frame(const gm_wall_params *params, const gm_wall_clothoid *clothoid, const double pose[12],
+                                     gm_wall_clothoid_add_info *info)
+{
+    DesignFrame d;
+    ClothoidFrame f;
+    double Rm[3][3], tr[3];
+    if (!pose || !info || clothoid_check(params, clothoid, d, f) != GM_OK || pose_split(pose, Rm, tr)) return GM_ERR_INVALID_ARG;
+    memset(info, 0, sizeof(*info));
+    if (!clothoid_add_frame(*params, d, f, Rm, tr, *info, nullptr, nullptr, nullptr)) return GM_ERR_INVALID_ARG;
+    info->struct_size = (uint32_t)sizeof(gm_wall_clothoid_add_info);
+    info->status = d.status;
+    return GM_OK;
+}
+
+gm_status gm_wall_clothoid_frame(const gm_wall_params *params, const gm_wall_clothoid *clothoid, double chainage, double o[3],
+                                 double a[3], double u[3], double v[3], double *curvature, double n[3])
+{
+    DesignFrame d;
+    ClothoidFrame f;
+    if (!o || !a || !u || !v || !curvature || !isfinite(chainage) || clothoid_check(params, clothoid, d, f) != GM_OK)
+        return GM_ERR_INVALID_ARG;
+    double ns[3];
+    *curvature = clothoid_section(d, f, chainage - f.s0, a, ns, o);
+    for (int k = 0; k < 3; ++k) {
+        u[k] = f.un * ns[k] + f.ub * f.b[k];
+        v[k] = f.vn * ns[k] + f.vb * f.b[k];
+        if (n) n[k] = ns[k];
+    }
+    return GM_OK;
+}
+
+gm_status gm_wall_clothoid_project(const gm_wall_params *params, const gm_wall_clothoid *clothoid, const double xyz[3],
+                                   double *chainage, double *angle, double *e)
+{
+    DesignFrame d;
+    ClothoidFrame f;
+    if (!xyz || !chainage || !angle || !e || clothoid_check(params, clothoid, d, f) != GM_OK) return GM_ERR_INVALID_ARG;
+    if (!isfinite(xyz[0]) || !isfinite(xyz[1]) || !isfinite(xyz[2])) return GM_ERR_INVALID_ARG;
+    double yc = 0.0;
+    const double tau = clothoid_foot(d, f, xyz, &yc, nullptr);
+    const double r[3] = {xyz[0] - f.pt[0], xyz[1] - f.pt[1], xyz[2] - f.pt[2]};
+    const double zb = dot(r, f.b);
+    *chainage = f.s0 + tau;
+    *e = sqrt(yc * yc + zb * zb) - d.R;
+    const double th = atan2(yc * f.vn + zb * f.vb, yc * f.un + zb * f.ub);
+    *angle = th < 0.0 ? th + kTwoPi : th;
+    return GM_OK;
+}
+
+gm_status gm_wall_clothoid_point(const gm_wall_params *params, const gm_wall_clothoid *clothoid, double chainage, double angle,
+                                 double rho, double xyz[3])
+{
+    DesignFrame d;
+    ClothoidFrame f;
+    if (!xyz || !isfinite(chainage) || !isfinite(angle) || !isfinite(rho) || clothoid_check(params, clothoid, d, f) != GM_OK)
+        return GM_ERR_INVALID_ARG;
+    double as[3], ns[3], P[3];
+    clothoid_section(d, f, chainage - f.s0, as, ns, P);
+    const double c = cos(angle), s = sin(angle);
+    const double yc = rho * (c * f.un + s * f.vn), zb = rho * (c * f.ub + s * f.vb);
+    for (int k = 0; k < 3; ++k) xyz[k] = (P[k] + yc * ns[k]) + zb * f.b[k];
     return GM_OK;
 }
 

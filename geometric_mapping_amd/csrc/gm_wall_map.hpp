@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <vector>
 
 #include "gm_internal.hpp"
 #ifndef GM_WALL_HOST_ONLY   // (gm_wall_host.hip defines it)
@@ -54,6 +55,27 @@ double arc_chainage(const DesignFrame &d, const ArcFrame &f, const double x[3]);
 // and Rm^T v(s_f) before the rounding; a1 (may be NULL): |a'|_1 before the rounding.  false: the anchor is out of range.
 bool arc_add_frame(const gm_wall_params &p, const DesignFrame &d, const ArcFrame &f, const double Rm[3][3], const double tr[3],
                    gm_wall_arc_add_info &out, double *u64, double *v64, double *a1);
+// The clothoid design frame of include/gm_hip.h (fp64, not rounded) beside the DesignFrame at params.point.  on false: not
+// a clothoid map, nothing else is set.  tab: (X, Y) at the n_stations + 1 station starts.
+struct ClothoidFrame {
+    bool on = false;
+    double k0 = 0.0, rate = 0.0, s0 = 0.0, tau0 = 0.0, ds = 0.0, pt[3] = {}, n[3] = {}, b[3] = {}, un = 0.0, ub = 0.0, vn = 0.0, vb = 0.0;
+    uint32_t nst = 0;
+    std::vector<double> tab;
+    double kappa(double tau) const { return k0 + rate * tau; }
+    double psi(double tau) const { return tau * (k0 + (0.5 * rate) * tau); }
+};
+// gm_wall_map_create_clothoid's refusals; d and f (its table included) of an accepted pair
+gm_status clothoid_check(const gm_wall_params *p, const gm_wall_clothoid *cl, DesignFrame &d, ClothoidFrame &f);
+// (X, Y) at tau = s - s0: the table entry at or below it plus the panels from there
+void clothoid_xy(const ClothoidFrame &f, double tau, double &X, double &Y);
+// the section at tau = s - s0: a(s), n(s), P(s); returns kappa(s)
+double clothoid_section(const DesignFrame &d, const ClothoidFrame &f, double tau, double as[3], double ns[3], double P[3]);
+// the foot of the perpendicular of a map point: returns tau; yc, g of the final evaluation (may be NULL)
+double clothoid_foot(const DesignFrame &d, const ClothoidFrame &f, const double x[3], double *yc, double *g);
+// arc_add_frame on a clothoid map
+bool clothoid_add_frame(const gm_wall_params &p, const DesignFrame &d, const ClothoidFrame &f, const double Rm[3][3],
+                        const double tr[3], gm_wall_clothoid_add_info &out, double *u64, double *v64, double *a1);
 // the library's pose check: 0 the pose is accepted (Rm, tr filled), 1 an entry is not finite, 2 Rm is not a rotation
 int pose_split(const double pose[12], double Rm[3][3], double tr[3]);
 // the direction table of include/gm_hip.h: NK pairs (one operation per statement, as stated there)
@@ -236,6 +258,9 @@ struct gm_wall_map {
     gm_wall_arc arc;               // gm_wall_map_create_arc's (zero on a straight map)
     gm::wall::ArcFrame af;         // af.kappa > 0: the design axis is an arc
     bool is_arc() const { return af.kappa > 0.0; }
+    gm_wall_clothoid clothoid;     // gm_wall_map_create_clothoid's (zero on other maps)
+    gm::wall::ClothoidFrame cf;    // cf.on: the design axis is a clothoid
+    bool is_clothoid() const { return cf.on; }
     uint64_t frames = 0;
     hipStream_t stream = nullptr;  // the small kernels (read / merge / clear / count) and their copies
     std::vector<uint8_t> pending;  // per slot of ctx: an add was enqueued on its stream since the last sync
@@ -259,7 +284,7 @@ struct gm_wall_map {
     gm::DevArray<unsigned long long> cl_ctr;      // [kWallCloudCounters]
     gm::DevArray<double> cl_dirs;      // [GM_WALL_MAX_SECTORS][2]
     std::vector<double> cl_dirs_host;          // the table of the call in progress
-    gm::DevArray<double> cl_rows;      // an arc map: [block rows of a chunk][2] cos psi, sin psi
+    gm::DevArray<double> cl_rows;      // an arc map: [block rows of a chunk][2] cos psi, sin psi; a clothoid map: [..][5]
     std::vector<double> cl_rows_host;
     // gm_wall_map_mesh: its vertex pass runs on the cloud's scratch above; its own
     gm::DevArray<uint32_t> ms_rank;    // [NJ * NK] of the window: a block's vertex index, kWallMeshDead otherwise
@@ -347,12 +372,12 @@ inline void frame_points(const gm_ctx *ctx, const Slot &sl, WallArgs &w)
 // buffers.  The context's crop bound (a cube around the sensor) sizes the LDS window.
 // f64 (a locate's start): the same vectors before the rounding, and o_f in map coordinates.
 struct WallFrame64 { double c[3], d[3], u[3], v[3], of[3]; };
-// arc: what the arc kernels take beside w.  An arc map refuses a caller without one (a locate, an align) with
-// GM_ERR_UNSUPPORTED; a straight map leaves it alone.
+// ax: what the arc and the clothoid kernels take beside w (an arc map fills ax->arc alone).  An arc or a clothoid map
+// refuses a caller without one (a locate, an align) with GM_ERR_UNSUPPORTED; a straight map leaves it alone.
 gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info *info, WallArgs &w, WallFrame64 *f64 = nullptr,
-                         WallArc *arc = nullptr);
-// the add and the check of a map, straight or arc (arc: add_frame_args')
-void launch_add(gm_wall_map *m, const WallArgs &w, const WallArc &arc, uint32_t n_cap, hipStream_t s);
+                         WallClothoid *ax = nullptr);
+// the add and the check of a map, straight, arc or clothoid (ax: add_frame_args')
+void launch_add(gm_wall_map *m, const WallArgs &w, const WallClothoid &ax, uint32_t n_cap, hipStream_t s);
 // An add on `s` (the stream of `slot`) must not be seen by a reader -- a check, a locate, an align -- enqueued before it
 // on another slot: `s` waits for every result outstanding there (nothing to wait for on a map without readers).
 gm_status add_wait_readers(gm_wall_map *m, uint32_t slot, hipStream_t s);

@@ -48,12 +48,13 @@ gm_status check_prepare(gm_wall_map *m, uint32_t slot, uint32_t n_cap, hipStream
 }
 
 // the launch, the copy of its counters and the event behind both
-gm_status check_enqueue(gm_wall_map *m, uint32_t slot, const WallCheckArgs &a, const WallArc &arc, uint32_t n_cap, const ScanState &st,
+gm_status check_enqueue(gm_wall_map *m, uint32_t slot, const WallCheckArgs &a, const WallClothoid &ax, uint32_t n_cap, const ScanState &st,
                         hipStream_t s)
 {
     gm_ctx *ctx = m->ctx;
     WallCheckSlot &c = m->checks[slot];
-    if (m->is_arc()) launch_wall_check_arc(a, arc, n_cap, st, s);
+    if (m->is_clothoid()) launch_wall_check_clothoid(a, ax, n_cap, st, s);
+    else if (m->is_arc()) launch_wall_check_arc(a, ax.arc, n_cap, st, s);
     else launch_wall_check(a, n_cap, st, s);
     GMW_HIP(ctx, hipGetLastError());
     GMW_HIP(ctx, hipMemcpyAsync(c.h_ctr, c.ctr.p, kWallCheckCounters * 8, hipMemcpyDeviceToHost, s));
@@ -420,8 +421,8 @@ gm_status gm_wall_map_check_frame(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, 
     memset(&a, 0, sizeof(a));
     Slot *sl = nullptr;
     GMW_OK(frame_call_head(map, ctx, slot, "gm_wall_map_check_frame", [&] { return check_prm_ok(cp, a.T); }, sl));
-    WallArc arc;
-    GMW_OK(add_frame_args(map, pose, add_info, a.w, nullptr, &arc));
+    WallClothoid ax;
+    GMW_OK(add_frame_args(map, pose, add_info, a.w, nullptr, &ax));
     a.w.gate = (float)cp.gate;
     if (add_info) add_info->gate = a.w.gate;
     GMW_OK(set_device(ctx));
@@ -432,7 +433,7 @@ gm_status gm_wall_map_check_frame(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, 
     frame_points(ctx, *sl, a.w);
     a.reference = cp.reference;
     a.min_count = cp.min_count;
-    return check_enqueue(map, slot, a, arc, n_cap, scan, sl->stream);
+    return check_enqueue(map, slot, a, ax, n_cap, scan, sl->stream);
 }
 
 gm_status gm_wall_map_get_check(gm_wall_map *map, uint32_t slot, gm_wall_check_info *info, gm_wall_check_point *points,
@@ -462,8 +463,8 @@ gm_status gm_wall_map_check_points(gm_wall_map *map, const float *xyz, uint32_t 
     memset(&a, 0, sizeof(a));
     if (!check_prm_ok(cp, a.T))
         return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_check_points: struct_size mismatch or a parameter outside its limits");
-    WallArc arc;
-    GMW_OK(add_frame_args(map, pose, add_info, a.w, nullptr, &arc));
+    WallClothoid ax;
+    GMW_OK(add_frame_args(map, pose, add_info, a.w, nullptr, &ax));
     a.w.gate = (float)cp.gate;
     if (add_info) add_info->gate = a.w.gate;
     StageCall sc{map, n, residual, cell, delta, cls};
@@ -479,7 +480,7 @@ gm_status gm_wall_map_check_points(gm_wall_map *map, const float *xyz, uint32_t 
     a.reference = cp.reference;
     a.min_count = cp.min_count;
     a.row_is_index = 1u;
-    GMW_OK(check_enqueue(map, 0, a, arc, n_cap, scan, s));
+    GMW_OK(check_enqueue(map, 0, a, ax, n_cap, scan, s));
     GMW_OK(sc.close());
     return check_result(map, 0, info, points, capacity, n_out);
 }

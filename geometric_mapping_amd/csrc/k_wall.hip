@@ -58,11 +58,12 @@ struct WallMask<true> {
     unsigned long long *ctr;           // [kWallAddCheckedCounters]
 };
 
-// kArc (a map of gm_wall_map_create_arc): the chain head runs on the by-value WallArc (wall_chain, gm_device.hpp); everything
+// Axis (WallArcArg<false> straight, WallArcArg<true> a map of gm_wall_map_create_arc, WallClothoidArg one of
+// gm_wall_map_create_clothoid): the chain head runs on the by-value axis block (wall_chain, gm_device.hpp); everything
 // behind (e, jl, k) -- classes, window, run merge, flush -- is shared.  The straight instantiations carry none of it, and
-// the arc ones have entry points of their own below.
-template <bool kMasked, bool kArc>
-__device__ __forceinline__ void wall_add(const WallArgs a, const WallMask<kMasked> m, const WallArcArg<kArc> c)
+// the arc and clothoid ones have entry points of their own below.
+template <bool kMasked, class Axis>
+__device__ __forceinline__ void wall_add(const WallArgs a, const WallMask<kMasked> m, const Axis c)
 {
     constexpr int kCls = kMasked ? 5 : 4;
     __shared__ unsigned long long s_sum[kWallCells];
@@ -147,19 +148,27 @@ __device__ __forceinline__ void wall_add(const WallArgs a, const WallMask<kMaske
 
 __global__ __launch_bounds__(kWallThreads) void k_wall_add(WallArgs a)
 {
-    wall_add<false, false>(a, WallMask<false>(), WallArcArg<false>());
+    wall_add<false>(a, WallMask<false>(), WallArcArg<false>());
 }
 __global__ __launch_bounds__(kWallThreads) void k_wall_add_masked(WallArgs a, WallMask<true> m)
 {
-    wall_add<true, false>(a, m, WallArcArg<false>());
+    wall_add<true>(a, m, WallArcArg<false>());
 }
 __global__ __launch_bounds__(kWallThreads) void k_wall_add_arc(WallArgs a, WallArcArg<true> c)
 {
-    wall_add<false, true>(a, WallMask<false>(), c);
+    wall_add<false>(a, WallMask<false>(), c);
 }
 __global__ __launch_bounds__(kWallThreads) void k_wall_add_arc_masked(WallArgs a, WallMask<true> m, WallArcArg<true> c)
 {
-    wall_add<true, true>(a, m, c);
+    wall_add<true>(a, m, c);
+}
+__global__ __launch_bounds__(kWallThreads) void k_wall_add_clothoid(WallArgs a, WallClothoidArg c)
+{
+    wall_add<false>(a, WallMask<false>(), c);
+}
+__global__ __launch_bounds__(kWallThreads) void k_wall_add_clothoid_masked(WallArgs a, WallMask<true> m, WallClothoidArg c)
+{
+    wall_add<true>(a, m, c);
 }
 
 // ---- the small kernels: convert / copy out a window, merge a raw window, clear, count ----
@@ -282,6 +291,19 @@ void launch_wall_add_arc_masked(const WallArgs &a, const WallArc &arc, const uns
     m.ctr = ctr;
     hipLaunchKernelGGL(k_wall_add_arc_masked, dim3(wall_blocks(n_cap, points_per_block)), dim3(kWallThreads), 0, s, a, m,
                        WallArcArg<true>{arc});
+}
+void launch_wall_add_clothoid(const WallArgs &a, const WallClothoid &cl, uint32_t n_cap, uint32_t points_per_block, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_wall_add_clothoid, dim3(wall_blocks(n_cap, points_per_block)), dim3(kWallThreads), 0, s, a, WallClothoidArg{cl});
+}
+void launch_wall_add_clothoid_masked(const WallArgs &a, const WallClothoid &cl, const unsigned long long *mask, unsigned long long *ctr,
+                                     uint32_t n_cap, uint32_t points_per_block, hipStream_t s)
+{
+    WallMask<true> m;
+    m.words = mask;
+    m.ctr = ctr;
+    hipLaunchKernelGGL(k_wall_add_clothoid_masked, dim3(wall_blocks(n_cap, points_per_block)), dim3(kWallThreads), 0, s, a, m,
+                       WallClothoidArg{cl});
 }
 void launch_wall_read(const WallTable &T, uint64_t first, uint64_t n, gm_surface_cell *out, hipStream_t s)
 {

@@ -36,12 +36,12 @@ __device__ __forceinline__ unsigned long long *wk_peaks()
     return p;
 }
 
-// the predicate's body: the adds' chain head (wall_chain, gm_device.hpp), straight or on the by-value WallArc
+// the predicate's body: the adds' chain head (wall_chain, gm_device.hpp), straight or on the by-value arc or clothoid block
 struct WallCheckPayload { float4 q; long long delta; float e; int cell; };
 static_assert(GM_WALL_CHECK_CLS_PLANE == kChainPlane && GM_WALL_CHECK_CLS_BEYOND_GATE == kChainBeyondGate &&
                   GM_WALL_CHECK_CLS_OUTSIDE == kChainOutside, "the check's first classes are wall_chain's");
-template <bool kArc>
-__device__ __forceinline__ bool wall_check_point(const WallCheckArgs &a, const WallArcArg<kArc> &arc, uint32_t i, WallCheckPayload &p)
+template <class Axis>
+__device__ __forceinline__ bool wall_check_point(const WallCheckArgs &a, const Axis &arc, uint32_t i, WallCheckPayload &p)
 {
     const WallArgs &w = a.w;
     p.q = w.pts[i];
@@ -92,6 +92,13 @@ struct WallCheckPredArc {
     WallArcArg<true> arc;
     using Payload = WallCheckPayload;
     __device__ __forceinline__ bool operator()(uint32_t i, Payload &p) const { return wall_check_point(a, arc, i, p); }
+};
+
+struct WallCheckPredClothoid {
+    WallCheckArgs a;
+    WallClothoidArg cl;
+    using Payload = WallCheckPayload;
+    __device__ __forceinline__ bool operator()(uint32_t i, Payload &p) const { return wall_check_point(a, cl, i, p); }
 };
 
 struct WallCheckEmit {
@@ -155,6 +162,16 @@ void launch_wall_check_arc(const WallCheckArgs &a, const WallArc &arc, uint32_t 
     emit.a = a;
     hipLaunchKernelGGL((k_compact<WallCheckPredArc, WallCheckEmit>), dim3(compact_grid(n_cap ? n_cap : 1u)), dim3(kCpThreads), 0, s,
                        pred, emit, a.w.n_ptr, a.w.n_host, st, reinterpret_cast<uint32_t *>(a.ctr + 9), (uint32_t *)nullptr);
+}
+
+void launch_wall_check_clothoid(const WallCheckArgs &a, const WallClothoid &cl, uint32_t n_cap, const ScanState &st, hipStream_t s)
+{
+    WallCheckPredClothoid pred{a, {cl}};
+    WallCheckEmit emit;
+    memset(&emit, 0, sizeof(emit));
+    emit.a = a;
+    hipLaunchKernelGGL((k_compact<WallCheckPredClothoid, WallCheckEmit>), dim3(compact_grid(n_cap ? n_cap : 1u)), dim3(kCpThreads), 0,
+                       s, pred, emit, a.w.n_ptr, a.w.n_host, st, reinterpret_cast<uint32_t *>(a.ctr + 9), (uint32_t *)nullptr);
 }
 
 }  // namespace gm

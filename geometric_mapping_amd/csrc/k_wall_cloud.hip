@@ -121,4 +121,13 @@ void launch_wall_cloud_compact_arc(const WallCloudArgs &a, const WallCloudArc &a
                        (const uint32_t *)nullptr, nb, st, reinterpret_cast<uint32_t *>(a.ctr + 2), (uint32_t *)nullptr);
 }
 
+void launch_wall_cloud_compact_clothoid(const WallCloudArgs &a, const WallCloudClothoid &cl, const ScanState &st, hipStream_t s)
+{
+    const uint32_t nb = a.nJ * a.NK;   // >= 1
+    WallCloudPred pred{a};
+    WallCloudEmitClothoid emit{a, WallCloudOnClothoid{cl}};
+    hipLaunchKernelGGL((k_compact<WallCloudPred, WallCloudEmitClothoid>), dim3(compact_grid(nb)), dim3(kCpThreads), 0, s, pred, emit,
+                       (const uint32_t *)nullptr, nb, st, reinterpret_cast<uint32_t *>(a.ctr + 2), (uint32_t *)nullptr);
+}
+
 }  // namespace gm

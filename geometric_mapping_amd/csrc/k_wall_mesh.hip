@@ -26,7 +26,7 @@ static_assert(sizeof(gm_wall_mesh_triangle) == 12, "three indices");
 
 // ---- 1. vertices ----
 
-// (CloudEmit: WallCloudEmit, or WallCloudEmitArc on a map of gm_wall_map_create_arc; the straight one is not a template
+// (CloudEmit: WallCloudEmit, or WallCloudEmitArc / WallCloudEmitClothoid on a curved axis; the straight one is not a template
 // specialisation, so that its kernel keeps its name)
 template <class CloudEmit>
 struct WallMeshVertexEmitT {
@@ -48,6 +48,7 @@ struct WallMeshVertexEmitT {
 
 struct WallMeshVertexEmit : WallMeshVertexEmitT<WallCloudEmit> {};
 struct WallMeshVertexEmitArc : WallMeshVertexEmitT<WallCloudEmitArc> {};
+struct WallMeshVertexEmitClothoid : WallMeshVertexEmitT<WallCloudEmitClothoid> {};
 
 // ---- 2. triangles ----
 
@@ -149,6 +150,16 @@ void launch_wall_mesh_vertices_arc(const WallCloudArgs &a, const WallCloudArc &a
     WallMeshVertexEmitArc emit{{WallCloudEmitArc{a, WallCloudOnArc{arc}}, rank, mean, rank_base}};
     hipLaunchKernelGGL((k_compact<WallCloudPred, WallMeshVertexEmitArc>), dim3(compact_grid(nb)), dim3(kCpThreads), 0, s, pred, emit,
                        (const uint32_t *)nullptr, nb, st, reinterpret_cast<uint32_t *>(a.ctr + 2), (uint32_t *)nullptr);
+}
+
+void launch_wall_mesh_vertices_clothoid(const WallCloudArgs &a, const WallCloudClothoid &cl, uint32_t *rank, float *mean,
+                                        uint32_t rank_base, const ScanState &st, hipStream_t s)
+{
+    const uint32_t nb = a.nJ * a.NK;   // >= 1
+    WallCloudPred pred{a};
+    WallMeshVertexEmitClothoid emit{{WallCloudEmitClothoid{a, WallCloudOnClothoid{cl}}, rank, mean, rank_base}};
+    hipLaunchKernelGGL((k_compact<WallCloudPred, WallMeshVertexEmitClothoid>), dim3(compact_grid(nb)), dim3(kCpThreads), 0, s, pred,
+                       emit, (const uint32_t *)nullptr, nb, st, reinterpret_cast<uint32_t *>(a.ctr + 2), (uint32_t *)nullptr);
 }
 
 void launch_wall_mesh_triangles(const WallMeshArgs &a, const ScanState &st, hipStream_t s)

@@ -294,6 +294,72 @@ def arc_drive(n_frames, n_points, arc_radius=80.0, toward=(0.0, 1.0, 0.0), seed=
     return dict(frames=frames, design=design, arc=arc, patches=tuple(patches), sigma=sigma, length=length)
 
 
+def clothoid_sections(t, curvature, rate, toward):
+    """The sections of the clothoid design axis of clothoid_drive at chainages t [n]: (P, a, u, v), float64 [n, 3] each,
+    and the signed curvature there [n].  The axis starts at the origin along +x with up = +z; its curvature toward
+    `toward` (made perpendicular to x) is curvature + rate s, so psi = curvature s + rate s^2 / 2,
+    a(s) = a cos psi + n sin psi, n(s) = n cos psi - a sin psi and P(s) = the integral of a from 0 to s: four panels of a
+    20-node Gauss-Legendre rule per point (a quadrature of its own: the library's and the test twin's are others)."""
+    t = np.asarray(t, np.float64).reshape(-1)
+    a = np.array([1.0, 0.0, 0.0])
+    n = np.asarray(toward, np.float64) - np.dot(toward, a) * a
+    n = n / np.linalg.norm(n)
+    b = np.cross(a, n)
+    u0, v0 = np.array([0.0, 0.0, 1.0]), np.array([0.0, -1.0, 0.0])
+    k0, c = float(curvature), float(rate)
+    x, w = np.polynomial.legendre.leggauss(20)
+    X, Y = np.zeros(len(t)), np.zeros(len(t))
+    for q in range(4):
+        sg = (t[:, None] / 4.0) * (q + 0.5 + 0.5 * x[None, :])
+        ps = k0 * sg + 0.5 * c * sg * sg
+        X += (t / 8.0) * (np.cos(ps) @ w)
+        Y += (t / 8.0) * (np.sin(ps) @ w)
+    psi = k0 * t + 0.5 * c * t * t
+    cs, sn = np.cos(psi)[:, None], np.sin(psi)[:, None]
+    a_s = a * cs + n * sn
+    n_s = n * cs - a * sn
+    P = X[:, None] * a + Y[:, None] * n
+    u = (u0 @ n) * n_s + (u0 @ b) * b
+    v = (v0 @ n) * n_s + (v0 @ b) * b
+    return P, a_s, u, v, k0 + c * t
+
+
+def clothoid_drive(n_frames, n_points, curvature=0.0, rate=1.0 / (80.0 * 48.0), toward=(0.0, 1.0, 0.0), seed=0, radius=2.0,
+                   length=48.0, start=6.0, step=3.5, reach=7.0, sigma=0.01, patches=DRIVE_PATCHES, yaw_deg=4.0, roll_deg=3.0,
+                   lateral=0.25, texture=None):
+    """arc_drive on a tube whose axis is a clothoid, for a wall map on a transition curve (gm_wall_map_create_clothoid).
+    The design axis starts at the world origin along +x (chainage 0, up = +z) with the signed curvature `curvature` toward
+    `toward`, which grows by `rate` per metre (the default: from straight to an 80 m radius over `length`).  Everything
+    else, the draws and their order included, is arc_drive's.  Returns tunnel_drive's dict plus
+    clothoid=dict(normal, curvature, rate, point_chainage) for GeometricMapping.wall_map(clothoid=...)."""
+    rng = np.random.default_rng(seed)
+    frames = []
+    for i in range(n_frames):
+        s = start + i * step
+        ly, lz = rng.uniform(-lateral, lateral), rng.uniform(-lateral, lateral)
+        local = pose_matrix((0.0, 0.0, 0.0), yaw_deg=rng.uniform(-yaw_deg, yaw_deg), roll_deg=rng.uniform(-roll_deg, roll_deg))
+        P, a_s, u_s, v_s = (x[0] for x in clothoid_sections([s], curvature, rate, toward)[:4])
+        F = np.stack([a_s, -v_s, u_s], axis=1)   # the section as a sensor frame: x forward, y left, z up
+        pose = np.concatenate([F @ local[:, :3], (P - ly * v_s + lz * u_s).reshape(3, 1)], axis=1)
+        t = rng.uniform(max(0.0, s - reach), min(length, s + reach), n_points)
+        phi = rng.uniform(0.0, 2 * np.pi, n_points)
+        rr = radius + rng.normal(0.0, sigma, n_points)
+        deg = np.rad2deg(phi)
+        for t0, t1, p0, p1, dr in patches:
+            rr = np.where((t >= t0) & (t < t1) & (deg >= p0) & (deg < p1), rr + dr, rr)
+        if texture is not None:
+            rr = rr + wall_texture(t, phi, **texture)
+        Pt, _, ut, vt, _ = clothoid_sections(t, curvature, rate, toward)
+        world = Pt + (rr * np.cos(phi))[:, None] * ut + (rr * np.sin(phi))[:, None] * vt
+        sensor = (world - pose[:, 3]) @ pose[:, :3]   # Rm^T (p - tr)
+        frames.append((np.ascontiguousarray(sensor, dtype=np.float32), pose))
+    design = dict(point=(0.0, 0.0, 0.0), direction=(1.0, 0.0, 0.0), radius=float(radius), up=(0.0, 0.0, 1.0),
+                  forward=(1.0, 0.0, 0.0))
+    n = np.asarray(toward, np.float64) - np.array([float(toward[0]), 0.0, 0.0])
+    clothoid = dict(normal=tuple(n / np.linalg.norm(n)), curvature=float(curvature), rate=float(rate), point_chainage=0.0)
+    return dict(frames=frames, design=design, clothoid=clothoid, patches=tuple(patches), sigma=sigma, length=length)
+
+
 def drop_row_padding(msg):
     """What the node does with an organised cloud whose rows are padded (ros/geometric_mapping_node.cpp): the C ABI takes
     point_step-strided rows, so the row_step padding is dropped once on the host.  Returns the packed uint8 rows."""

@@ -369,11 +369,15 @@ void Processor::getSurfaceMap(gm_surface_info &info, std::vector<gm_surface_cell
 
 void Processor::createWallMap(const gm_wall_params &params) { createWallMap(params, 0); }
 
-void Processor::createWallMap(const gm_wall_params &params, const gm_wall_arc *arc)
+void Processor::createWallMap(const gm_wall_params &params, const gm_wall_arc *arc) { createWallMap(params, arc, 0); }
+
+void Processor::createWallMap(const gm_wall_params &params, const gm_wall_arc *arc, const gm_wall_clothoid *clothoid)
 {
     if (grp_) throw Error(GM_ERR_UNSUPPORTED, "createWallMap: a wall map belongs to one context (single-device Processor)");
+    if (arc && clothoid) throw Error(GM_ERR_INVALID_ARG, "createWallMap: an arc and a clothoid exclude each other");
     gm_wall_map *m = 0;
-    check(arc ? gm_wall_map_create_arc(ctx_, &params, arc, &m) : gm_wall_map_create(ctx_, &params, &m), "createWallMap");
+    if (clothoid) check(gm_wall_map_create_clothoid(ctx_, &params, clothoid, &m), "createWallMap");
+    else check(arc ? gm_wall_map_create_arc(ctx_, &params, arc, &m) : gm_wall_map_create(ctx_, &params, &m), "createWallMap");
     if (wall_) gm_wall_map_destroy(wall_);
     wall_ = m;
     check_slot_ = -1;

@@ -141,6 +141,10 @@ public:
     // the same on a circular-arc design axis (gm_wall_map_create_arc): one map per alignment element, straight or arc.
     // locateWallMap and alignWallMap throw GM_ERR_UNSUPPORTED on such a map.
     void createWallMap(const gm_wall_params &params, const gm_wall_arc *arc);
+    // the same on a clothoid design axis (gm_wall_map_create_clothoid; arc must then be NULL): with it an alignment of
+    // straights, transition curves and arcs is one map per element.  locateWallMap and alignWallMap throw
+    // GM_ERR_UNSUPPORTED on such a map too.
+    void createWallMap(const gm_wall_params &params, const gm_wall_arc *arc, const gm_wall_clothoid *clothoid);
     // adds the frame just processed or submitted (the newest one) under pose = row-major 3x4 [R | t], sensor -> map.
     // Enqueued behind the frame's work: call it right after submitFrame, or after processFrame / waitFrame.
     gm_wall_add_info addToWallMap(const double pose[12]);

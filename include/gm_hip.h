@@ -1774,7 +1774,7 @@ gm_status gm_wall_map_add_points_checked(gm_wall_map *map, const float *xyz, uin
 /* ---- a wall map on a circular-arc design axis (gm_wall_map_create_arc) -------------------------------------------------
  * The design axis of such a map is a circular arc of constant curvature in any plane that holds the design direction:
  * horizontal curves, vertical curves (portal ramps) and oblique ones.  An alignment is one map per alignment element,
- * straight (gm_wall_map_create) or circular arc; clothoids are not covered.  The table, its cells and every cell-space
+ * straight (gm_wall_map_create), circular arc or clothoid (gm_wall_map_create_clothoid below).  The table, its cells and every cell-space
  * product are those of a straight map: only the per-point chain and the position rule of the cloud and the mesh see the
  * axis.  One operation per statement; fp64 on the host, not rounded, unless a rounding is named.
  *   design frame  (a, u, v, R) of the straight map's rule above, valid AT params.point, which lies on the axis at chainage
@@ -1851,6 +1851,118 @@ gm_status gm_wall_arc_project(const gm_wall_params *params, const gm_wall_arc *a
 /* The map point at (chainage, angle, rho = R + e): the cloud's position rule with anchor 0 and (c, s) = (cos, sin) angle. */
 gm_status gm_wall_arc_point(const gm_wall_params *params, const gm_wall_arc *arc, double chainage, double angle, double rho,
                             double xyz[3]);
+
+/* ---- a wall map on a clothoid design axis (gm_wall_map_create_clothoid) ------------------------------------------------
+ * The design axis of such a map is a transition curve: its curvature grows linearly with the chainage, in any plane that
+ * holds the design direction.  With it an alignment of straights, clothoids and arcs is one map per element.  Everything
+ * said of an arc map holds: only the per-point chain and the position rule of the cloud and the mesh see the axis.  One
+ * operation per statement; fp64 on the host, not rounded, unless a rounding is named.  All arithmetic runs in
+ * tau = s - s0, never in s, so a map at chainage 5 km evaluates like one at 0.
+ *   design frame  (a, u, v, R) of the straight rule AT params.point, which lies on the axis at chainage s0 = point_chainage.
+ *                 m = normal - (normal.a) a;  n = m / |m|;  b = a x n;  un = u.n, ub = u.b, vn = v.n, vb = v.b.
+ *                 kappa(tau) = curvature + rate tau;  psi(tau) = tau (curvature + (0.5 rate) tau);
+ *                 a(s) = a cos psi + n sin psi;  n(s) = n cos psi - a sin psi;  u(s) = un n(s) + ub b;  v(s) = vn n(s) + vb b;
+ *                 P(s) = (point + X(tau) a) + Y(tau) n,  (X, Y)(tau) = the integral of (cos psi, sin psi) from 0 to tau.
+ *                 The sign of kappa may change inside the map (an S-transition).
+ *   quadrature    I(ta, tb), the integral from ta to tb:  K = 1 + floor(min(max(|kappa(ta)|, |kappa(tb)|) |tb - ta| / 0.25,
+ *                 4095)) equal panels of width w = (tb - ta) / K, each by the 8-node Gauss-Legendre rule (nodes x_i, weights
+ *                 w_i, i ascending in x):  mid = ta + (q + 0.5) w;  sx = sum_i w_i cos psi(mid + (0.5 w) x_i) in the order
+ *                 of i;  X += (0.5 w) sx;  Y alike.  A table holds (X, Y) at every station start, built at creation:
+ *                 tau_0 = t_min - s0,  T_0 = I(0, tau_0),  tau_j = tau_0 + j ds,  T_(j+1) = T_j + I(tau_j, tau_(j+1)),
+ *                 j = 0 .. n_stations.  (X, Y)(tau) = T_jd + I(tau_jd, tau),  jd = floor((tau - tau_0) / ds) clamped to
+ *                 [0, n_stations].
+ *   refusals      GM_ERR_INVALID_ARG: struct_size or reserved wrong; a field not finite; |m| <= 1e-6 |normal| or 0;
+ *                 |rate| (n_stations ds) < 1e-6 (the element is an arc or a straight);  (R + gate) max |kappa| > 0.5 over
+ *                 tau in [tau_0, tau_0 + n_stations ds] (kappa is linear: at an end);  |psi| > 3 at either end, or where
+ *                 kappa = 0 if that lies strictly inside.
+ *   chainage of x r = x - point;  xa = r.a;  xn = r.n.  Start at the tau_j whose T_j is nearest to (xa, xn) (squared distance,
+ *                 ties to the lowest j).  Then GM_WALL_CLOTHOID_HOST_STEPS = 6 Newton steps, no data-dependent exit:
+ *                 dx = xa - X;  dy = xn - Y;  g = dx cos psi + dy sin psi;  yc = dy cos psi - dx sin psi;
+ *                 tau = tau + g / (1 - kappa(tau) yc).  One more evaluation gives the reported yc (and g, which is at most
+ *                 1e-10 m over the twin's sweep).  s = s0 + tau.
+ *   per add       host, fp64: as on an arc.  Pose check; tau and s = s0 + tau: the chainage of tr;
+ *                 j_f = floor((tau - tau_0) / ds) (that is (s - t_min) / ds, taken in tau);  s_f = t_min + j_f ds, and the
+ *                 section there is evaluated at tau_0 + j_f ds.  o' = Rm^T (P(s_f) - tr), a' = Rm^T a(s_f), n' = Rm^T n(s_f), b' = Rm^T b, each rounded
+ *                 to fp32 once;  kappa_f = kappa(s_f - s0) and rate rounded to fp32 once;  un, ub, vn, vb, R, ds, gate and
+ *                 dtheta as on an arc: gm_wall_clothoid_add_info (gm_wall_clothoid_add_frame, host only).
+ *                 gm_wall_add_info is filled as on an arc.
+ *   per point     device, fp32, every operation rounded to nearest; atan2f as on an arc; (sin, cos) ps by the rule
+ *                 k = rint(0.63661977236758134 ps);  r = fma(-k, 1.5703125, ps);  r = fma(-k, 4.837512969970703125e-4, r);
+ *                 r = fma(-k, 7.54978995489188216e-8, r);  z = r r;
+ *                 S = fma(fma(fma(-1.9515295891e-4, z, 8.3321608736e-3), z, -1.6666654611e-1) z, r, r);
+ *                 C = fma(fma(fma(2.443315711809948e-5, z, -1.388731625493765e-3), z, 4.166664568298827e-2) z, z, -0.5 z) + 1;
+ *                 (sin, cos) = (S, C), (C, -S), (-S, -C), (-C, S) for k mod 4 = 0, 1, 2, 3;  NaN for |ps| >= 2^20 or a NaN.
+ *                   q = p - o';  x = q.a';  y = q.n';  z = q.b'                       (dot products as the chains above)
+ *                   cy = fma(-kappa_f, y, 1);  t = |kappa_f| < 1e-6 ? x : atan2f(kappa_f x, cy) / kappa_f    (the arc's t)
+ *                   hr = 0.5 rate.  E(t), the evaluation at a trial t, with the 4-node Gauss-Legendre rule on [0, 1]
+ *                   (c_i, w_i as fp32 constants):
+ *                     sg_i = t c_i;  ps_i = fma(hr, sg_i, kappa_f) sg_i;
+ *                     sx = w_0 cos ps_0, then sx = fma(cos ps_i, w_i, sx), i = 1, 2, 3;  sy alike with sin
+ *                     dx = x - t sx;  dy = y - t sy;  ps = fma(hr, t, kappa_f) t
+ *                     g = fma(dx, cos ps, dy sin ps);  yc = fma(dy, cos ps, -(dx sin ps))
+ *                   GM_WALL_CLOTHOID_STEPS = 2 Newton steps:  E(t);  den = fma(-fma(t, rate, kappa_f), yc, 1);
+ *                   t = t + g / den.  Then E(t) once more for (g, yc).
+ *                   e = sqrt(fma(yc, yc, z z)) - R;  phi and its sector from (yc, z) as on an arc;  j = j_f + floor(t / ds)
+ *   classes       as on an arc; in addition beyond_gate: cy <= 0; a den <= 0.25; t or e not finite; a final
+ *                 |g| > GM_WALL_CLOTHOID_G_BOUND = 2^-14 m (8 times the worst final |g| of the CPU sweep in
+ *                 tests/test_wall_clothoid_np.py, rounded up to a power of two).  Such a point is classed before any
+ *                 integer conversion or table index.
+ *   cloud, mesh   fp64, (c, s) the block's direction entry; per block row of a chunk the host computes, at the row's centre
+ *                 chainage tc, Pa = P(tc) - anchor (per component (point_i + X a_i) + Y n_i, then - anchor_i) and
+ *                 (cp, sp) = (cos, sin) psi(tc - s0):  yc = rho (c un + s vn);  zb = rho (c ub + s vb);
+ *                 nr_i = n_i cp - a_i sp;  p_i = (Pa_i + yc nr_i) + zb b_i, rounded to fp32 once.
+ * gm_wall_map_locate_* and gm_wall_map_align_* return GM_ERR_UNSUPPORTED on a clothoid map, as on an arc map; a baseline
+ * must be a map with a bitwise-equal clothoid (and arc), else GM_ERR_INVALID_ARG. */
+#define GM_WALL_CLOTHOID_HOST_STEPS 6
+#define GM_WALL_CLOTHOID_STEPS 2
+#define GM_WALL_CLOTHOID_G_BOUND 6.103515625e-05f   /* 2^-14 */
+typedef struct gm_wall_clothoid {
+    uint32_t struct_size;      /* = sizeof(gm_wall_clothoid) */
+    uint32_t reserved;         /* 0 */
+    double   normal[3];        /* map coordinates: the side positive curvature turns toward; its component along the design
+                                  direction is removed, then it is normalised */
+    double   curvature;        /* signed, 1/m, at params.point (may be 0: the element starts on a straight) */
+    double   rate;             /* d(curvature) / d(chainage), signed, 1/m^2 */
+    double   point_chainage;   /* chainage of params.point, finite */
+} gm_wall_clothoid;
+
+typedef struct gm_wall_clothoid_add_info {   /* 128 bytes */
+    uint32_t struct_size;      /* = sizeof(gm_wall_clothoid_add_info), filled by the library */
+    uint32_t status;           /* GM_SURF_OK or GM_SURF_UP_FALLBACK: the design frame's */
+    int64_t  anchor_station;   /* j_f */
+    double   sensor_chainage;  /* s */
+    double   anchor_chainage;  /* s_f */
+    float    o[3], a[3], n[3], b[3];   /* o', a', n', b' in SENSOR coordinates (fp32, as binned with) */
+    float    kappa, un, ub, vn, vb;    /* kappa: kappa_f, the curvature at the anchor section */
+    float    R, station_length, sector_angle, gate;
+    float    rate;
+    uint32_t reserved[2];      /* 0 */
+} gm_wall_clothoid_add_info;
+
+/* gm_wall_map_create with the clothoid.  GM_ERR_INVALID_ARG also for a NULL clothoid and the refusals above. */
+gm_status gm_wall_map_create_clothoid(gm_ctx *ctx, const gm_wall_params *params, const gm_wall_clothoid *clothoid,
+                                      gm_wall_map **map);
+/* The map's clothoid; all-zero on other maps.  GM_ERR_INVALID_ARG: NULL. */
+gm_status gm_wall_map_get_clothoid(gm_wall_map *map, gm_wall_clothoid *clothoid);
+/* Host only, no context: the five below restate the rules above in fp64 for callers and tests (each builds the table of
+ * station starts anew: n_stations panels).  GM_ERR_INVALID_ARG: NULL, struct_size mismatch, params or clothoid refused by
+ * gm_wall_map_create_clothoid, an input that is not finite, a refused pose. */
+gm_status gm_wall_clothoid_check_params(const gm_wall_params *params, const gm_wall_clothoid *clothoid);
+/* The per-add frame of `pose`. */
+gm_status gm_wall_clothoid_add_frame(const gm_wall_params *params, const gm_wall_clothoid *clothoid, const double pose[12],
+                                     gm_wall_clothoid_add_info *info);
+/* The design frame at `chainage`: o = P(s), a(s), u(s), v(s), and the signed curvature kappa(s) toward n(s).  It is
+ * (point, direction, up) of the NEXT element's map; n(s) goes to `n` (may be NULL), so that a following arc map's
+ * gm_wall_arc.curvature is *curvature times n (a negative kappa turns it to the other side, as it should). */
+gm_status gm_wall_clothoid_frame(const gm_wall_params *params, const gm_wall_clothoid *clothoid, double chainage, double o[3],
+                                 double a[3], double u[3], double v[3], double *curvature, double n[3]);
+/* A map point's chainage, angle phi in [0, 2 pi) and residual e by the chainage rule above: zb = r.b;
+ * e = sqrt(yc yc + zb zb) - R; phi = atan2(yc vn + zb vb, yc un + zb ub). */
+gm_status gm_wall_clothoid_project(const gm_wall_params *params, const gm_wall_clothoid *clothoid, const double xyz[3],
+                                   double *chainage, double *angle, double *e);
+/* The map point at (chainage, angle, rho = R + e): the cloud's position rule with anchor 0 and (c, s) = (cos, sin) angle. */
+gm_status gm_wall_clothoid_point(const gm_wall_params *params, const gm_wall_clothoid *clothoid, double chainage, double angle,
+                                 double rho, double xyz[3]);
 
 /* "Compressed map" record of a completed slot.  The reference defines no such
  * output; this is a build-defined format: header, primitive records,
