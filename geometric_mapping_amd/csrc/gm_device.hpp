@@ -269,6 +269,15 @@ __device__ __forceinline__ uint32_t surf_sector(float wx, float wy, float wz, co
     const uint32_t kk = (uint32_t)floorf(__fdiv_rn(phi, sector_angle));
     return kk < nsec - 1u ? kk : nsec - 1u;
 }
+// sqrt rounded to nearest, as the curved chains' rule has every operation.  (__fsqrt_rn is not that here: without
+// OCML_BASIC_ROUNDED_OPERATIONS the HIP headers make it the bare v_sqrt_f32, which is good to an ulp and moved e by one on
+// a tenth of an arc frame's points against the rule's twin, tests/test_gpu_wall_curved_chain.py.  The builtin is the
+// compiler's correctly rounded expansion, v_sqrt_f32 and one fma test of each neighbour, which hipcc's default
+// -fhip-fp32-correctly-rounded-divide-sqrt keeps on.)
+__device__ __forceinline__ float sqrt_rn(float x)
+{
+    return __builtin_sqrtf(x);
+}
 // ---- the same chain on a circular-arc design axis (include/gm_hip.h states it; k_wall.hip's and k_wall_check.hip's arc
 // instantiations).  (o, a, n, b): the section at the anchor station in sensor coordinates.  Returns e; t: the arc length
 // from the anchor section, (yc, z): the offset in the point's own section along n(s) and b; cy <= 0: a quarter turn or more
@@ -281,11 +290,11 @@ __device__ __forceinline__ float arc_residual(const float4 &p, const float (&o)[
     z = surf_dot3(qx, qy, qz, b);
     const float cx = __fmul_rn(kappa, x);
     cy = __fmaf_rn(-kappa, y, 1.0f);
-    const float d = __fsqrt_rn(__fmaf_rn(cx, cx, __fmul_rn(cy, cy)));
+    const float d = sqrt_rn(__fmaf_rn(cx, cx, __fmul_rn(cy, cy)));
     t = __fdiv_rn(atan2f(cx, cy), kappa);
     const float h = __fmaf_rn(x, x, __fmul_rn(y, y));
     yc = __fdiv_rn(__fmaf_rn(-kappa, h, __fadd_rn(y, y)), __fadd_rn(1.0f, d));
-    return __fsub_rn(__fsqrt_rn(__fmaf_rn(yc, yc, __fmul_rn(z, z))), R);
+    return __fsub_rn(sqrt_rn(__fmaf_rn(yc, yc, __fmul_rn(z, z))), R);
 }
 // surf_sector on (yc, z): phi = atan2(yc vn + z vb, yc un + z ub)
 __device__ __forceinline__ uint32_t arc_sector(float yc, float z, float un, float ub, float vn, float vb, float two_pi,
@@ -402,7 +411,7 @@ __device__ __forceinline__ float clothoid_residual(const float4 &p, const float 
     clothoid_eval(x, y, kappa, hr, t, g, yc);
     good = good && fabsf(t) < __builtin_inff() && fabsf(g) <= GM_WALL_CLOTHOID_G_BOUND;
     ok = good ? 1.0f : 0.0f;
-    return __fsub_rn(__fsqrt_rn(__fmaf_rn(yc, yc, __fmul_rn(z, z))), R);
+    return __fsub_rn(sqrt_rn(__fmaf_rn(yc, yc, __fmul_rn(z, z))), R);
 }
 
 // ---- the head of the chain against a map (k_wall_add*, the check's predicate, k_wall_align_bin): label, residual, gate,

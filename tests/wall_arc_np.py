@@ -4,13 +4,15 @@ design() is the arc design frame, add_frame() the per-add frame, frame() / proje
 (gm_wall_arc_*), all in the header's operation order on Python floats: the library's host code is plain fp64 C without
 contraction, so these agree with it to the last bit or two (atan2, cos and sin come from the same libm through math.*).
 points() is the per-point chain in fp64 on the frame the library REPORTED (gm_wall_arc_add_frame), with wall_np.points'
-ambiguous mask; points_f32() is the same chain in emulated fp32, one rounding per operation as the device does it.
+ambiguous mask; points_f32() is the same chain in float32, one rounding per operation as the device does it, up to the
+class and the cell, with an `uncertain` mask around the one library call (atan2f) it cannot reproduce.
 cloud() is gm_wall_map_cloud's records with the arc position rule, byte for byte.
 """
 import math
 
 import numpy as np
 
+import fp32_np as fp
 import wall_cloud_np as wc
 import wall_np as wn
 
@@ -191,28 +193,107 @@ def points(xyz, labels, f, p, gate=None):
     return dict(e=np.where(plane, np.nan, e), t=t, phi=phi, cls=cls, cell=cell, ambiguous=amb, yc=yc, z=z)
 
 
-def points_f32(xyz, f):
-    """The device's chain in emulated fp32 (numpy float32 arithmetic rounds each operation to nearest; an fma is taken in
-    fp64 and rounded once, which is exact for a product of two fp32 plus an fp32 up to a double rounding that moves the
-    result by at most one fp32 ulp in rare ties): e, t, yc, z as float32."""
-    F = np.float32
+F = np.float32
+ATAN2_ULPS = 6                       # OpenCL's bound for atan2 in single precision, which the device library's atan2f is built to
+SHIFTS = tuple([0] + [d for d in range(-ATAN2_ULPS, ATAN2_ULPS + 1) if d])   # the nominal angle first
+fma = fp.fma32                       # the twins' fused multiply-add (the sensitivity test swaps it for the old double rounding)
+GUARD_CY = True                      # the cy > 0 test of both curved chains (the sensitivity test drops it)
+
+
+def atan2_f32(y, x):
+    """atan2 taken in fp64 and rounded to fp32 once: the one operation of the chains a twin cannot reproduce, because the
+    device's atan2f is a library call."""
+    with np.errstate(all="ignore"):
+        return np.arctan2(np.asarray(y, F).astype(np.float64), np.asarray(x, F).astype(np.float64)).astype(F)
+
+
+def _frame_consts(f, p, gate):
+    """(anchor, ds, gate, dtheta, two_pi, n_stations, n_sectors) of a reported frame or of add_frame()'s; gate: the
+    check's own (None: the frame's, which is the map's)."""
+    anchor = int(f["anchor"] if "anchor" in f else f["anchor_station"])
+    ds = F(f["ds"] if "ds" in f else f["station_length"])
+    dth = F(f["dtheta"] if "dtheta" in f else f["sector_angle"])
+    return anchor, ds, F(f["gate"] if gate is None else gate), dth, F(2 * np.pi), int(p["n_stations"]), int(p["n_sectors"])
+
+
+def sector_f32(yc, z, f, dth, two_pi, nsec, shift=0):
+    """arc_sector's operations, the angle moved by `shift` fp32 ulps: k as int64."""
+    un, ub, vn, vb = (F(f[k]) for k in ("un", "ub", "vn", "vb"))
+    with np.errstate(all="ignore"):
+        th = fp.ulp_steps(atan2_f32(fma(yc, vn, z * vb), fma(yc, un, z * ub)), shift)
+        phi = np.where(th < F(0.0), th + two_pi, th).astype(F)
+        kf = np.floor(phi / dth)
+    return np.minimum(np.where(np.isfinite(kf), kf, 0.0).astype(np.int64), nsec - 1)
+
+
+def bin_f32(variants, f, p, labels, gate, shifts=None):
+    """The rest of wall_chain after the residual, in float32: class (plane, gate-or-guard, range, then sector), jl by
+    surf_station's operations (floor((t - 0) / ds)), the |jl| < 4e18 rule of wall_station, the sector by arc_sector's
+    operations and the global cell.  variants: (e, ok, t, yc, z) float32 arrays per point, the nominal chain first and then
+    the chains whose atan2f was moved by the other SHIFTS; every one is binned with the sector's own angle moved by every
+    shift as well.  Returns dict(cls, cell, jl of the nominal variant, uncertain: a point that is not plane and whose
+    class or cell differs from the nominal in any of those combinations)."""
+    anchor, ds, gate, dth, two_pi, nst, nsec = _frame_consts(f, p, gate)
+    n_pts = len(variants[0][0])
+    plane = (np.zeros(n_pts, np.uint8) if labels is None else np.asarray(labels, np.uint8)) == 1
+    first, uncertain = None, np.zeros(n_pts, bool)
+    for e, ok, t, yc, z in variants:
+        with np.errstate(all="ignore"):
+            beyond = ~(np.abs(e) <= gate) | ~ok
+            jl = np.floor(((t - F(0.0)) / ds).astype(F)).astype(F)
+            fin = np.abs(jl) < F(4.0e18)
+        j = anchor + np.where(fin, jl, F(0.0)).astype(np.int64)
+        inr = fin & (j >= 0) & (j < nst)
+        cls = np.where(plane, PLANE, np.where(beyond, BEYOND, np.where(inr, MAPPED, OUTSIDE))).astype(np.int8)
+        for d in (SHIFTS if shifts is None else shifts):
+            cell = np.where(cls == MAPPED, j * nsec + sector_f32(yc, z, f, dth, two_pi, nsec, d), -1)
+            if first is None:
+                first = dict(cls=cls, cell=cell, jl=jl)
+            else:
+                uncertain |= ~plane & ((cls != first["cls"]) | (cell != first["cell"]))
+    first["uncertain"] = uncertain
+    return first
+
+
+def class_counts(r, keep=None):
+    """(mapped, outside, beyond_gate, plane) of a twin's classes over the points of `keep` (all)."""
+    c = r["cls"] if keep is None else r["cls"][keep]
+    return tuple(int((c == k).sum()) for k in (MAPPED, OUTSIDE, BEYOND, PLANE))
+
+
+def points_f32(xyz, f, labels=None, p=None, gate=None, shifts=None):
+    """The device's chain in float32, operation by operation (numpy rounds each float32 operation to nearest; fma is
+    fp32_np.fma32, rounded once): e, t, yc, z, cy as float32.  e, yc, z and cy do not depend on atan2f at all.
+
+    With the map's parameters p it is the whole of wall_chain and returns what points() returns: e (NaN for plane
+    points), cls, cell, jl, and `uncertain` in the place of `ambiguous`.  atan2f is taken in fp64 and rounded once, and
+    whatever an angle decides is recomputed with that angle moved by -6 .. +6 fp32 ulps (bin_f32).  That the device's
+    atan2f lies within 6 ulps of the true angle is an ASSUMPTION: it is OpenCL's bound for atan2, which the device
+    library follows; nothing in this project measures it.  uncertain is built from the twin alone.  shifts: the ulps the
+    angles are moved by, the nominal 0 first (SHIFTS; (0,) for the nominal chain alone, with an empty mask)."""
     x = np.asarray(xyz, F).reshape(-1, 3)
     o, a, n, b = (np.asarray(f[k], F) for k in ("o", "a", "n", "b"))
     k, R = F(f["kappa"]), F(f["R"])
-    fma = lambda p, q, r: (p.astype(np.float64) * np.float64(q) + r.astype(np.float64)).astype(F)  # noqa: E731
-    q = x - o
-    dot3 = lambda w: fma(q[:, 0], w[0], fma(q[:, 1], w[1], q[:, 2] * w[2]))  # noqa: E731
-    xx, y, z = dot3(a), dot3(n), dot3(b)
-    cx = k * xx
-    cy = fma(y, -k, np.ones_like(y))
-    sq = lambda p, r: (p.astype(np.float64) * p.astype(np.float64) + (r * r).astype(np.float64)).astype(F)  # noqa: E731  fma(p, p, r r)
-    d = np.sqrt(sq(cx, cy))
-    t = (np.arctan2(cx.astype(np.float64), cy.astype(np.float64)).astype(F) / k).astype(F)
-    h = sq(xx, y)
-    num = (-np.float64(k) * h.astype(np.float64) + (y + y).astype(np.float64)).astype(F)
-    yc = (num / (F(1.0) + d)).astype(F)
-    e = (np.sqrt(sq(yc, z)) - R).astype(F)
-    return dict(e=e, t=t, yc=yc, z=z)
+    with np.errstate(all="ignore"):
+        q = x - o
+        dot3 = lambda w: fma(q[:, 0], w[0], fma(q[:, 1], w[1], q[:, 2] * w[2]))  # noqa: E731
+        xx, y, z = dot3(a), dot3(n), dot3(b)
+        cx = k * xx
+        cy = fma(-k, y, F(1.0))
+        d = np.sqrt(fma(cx, cx, cy * cy))
+        th = atan2_f32(cx, cy)
+        t = (th / k).astype(F)
+        h = fma(xx, xx, y * y)
+        yc = (fma(-k, h, y + y) / (F(1.0) + d)).astype(F)
+        e = (np.sqrt(fma(yc, yc, z * z)) - R).astype(F)
+        out = dict(e=e, t=t, yc=yc, z=z, cy=cy)
+        if p is None:
+            return out
+        ok = (cy > F(0.0)) if GUARD_CY else np.ones(len(x), bool)
+        shifts = SHIFTS if shifts is None else shifts
+        out.update(bin_f32([(e, ok, (fp.ulp_steps(th, s) / k).astype(F), yc, z) for s in shifts], f, p, labels, gate, shifts))
+    out["e"] = np.where(out["cls"] == PLANE, F(np.nan), e)
+    return out
 
 
 def row_angles(D, p, station0, n, bs):

@@ -4,13 +4,15 @@ design() is the clothoid design frame with its table of station starts, xy() / s
 project() / point() the host-only companions (gm_wall_clothoid_*) in fp64, add_frame() the per-add frame.  points() is
 the per-point chain in fp64 on the frame the library REPORTED (gm_wall_clothoid_add_frame): the foot of the
 perpendicular converged by eight Newton steps on a 16-node quadrature, with wall_np.points' ambiguous mask;
-points_f32() is the device's chain in emulated fp32, one rounding per operation.  cloud() is gm_wall_map_cloud's
-records with the clothoid position rule.
+points_f32() is the device's chain in float32, one rounding per operation, up to the class and the cell, with an
+`uncertain` mask and an envelope of e around the one library call (atan2f) it cannot reproduce.  cloud() is
+gm_wall_map_cloud's records with the clothoid position rule.
 """
 import math
 
 import numpy as np
 
+import fp32_np as fp
 import wall_arc_np as wa
 import wall_cloud_np as wc
 import wall_np as wn
@@ -281,66 +283,114 @@ def points(xyz, labels, f, p, gate=None):
     return dict(e=np.where(plane, np.nan, e), t=t, phi=phi, cls=cls, cell=cell, ambiguous=amb, yc=yc, z=z, g=np.abs(g))
 
 
-def points_f32(xyz, f):
-    """The device's chain in emulated fp32 (numpy float32 arithmetic rounds each operation to nearest; an fma is taken in
-    fp64 and rounded once; atan2 is taken in fp64 and rounded once, where the device's is good to an ulp or two; sin and
-    cos follow the header's own rule): e, t, yc, z, the final g and the smaller of the two Newton denominators as float32,
-    and cy."""
-    F = np.float32
+F = np.float32
+# the header's sincos rule: pi / 2 in three terms, the sine's and the cosine's polynomial (highest power first)
+PIO2 = np.array([1.5703125, 4.837512969970703125e-4, 7.54978995489188216e-8], F)
+SIN_C = np.array([-1.9515295891e-4, 8.3321608736e-3, -1.6666654611e-1], F)
+COS_C = np.array([2.443315711809948e-5, -1.388731625493765e-3, 4.166664568298827e-2], F)
+GUARD_DEN = True                     # the den > 0.25 test (the sensitivity test drops it; the cy > 0 test is wall_arc_np.GUARD_CY)
+
+
+def sincos_f32(ps):
+    """The header's sincos rule, operation by operation: (sin, cos) as float32, NaN for |ps| >= 2^20 or a NaN."""
+    fma = wa.fma
+    ps = np.asarray(ps, F)
+    with np.errstate(all="ignore"):
+        fin = np.abs(ps) < F(1048576.0)
+        k = np.where(fin, np.rint(ps * F(0.63661977236758134)), F(0.0)).astype(F)
+        r = fma(-k, PIO2[0], ps)
+        r = fma(-k, PIO2[1], r)
+        r = fma(-k, PIO2[2], r)
+        z = r * r
+        sp = fma(fma(SIN_C[0], z, SIN_C[1]), z, SIN_C[2])
+        sv = fma(sp * z, r, r)
+        cp = fma(fma(COS_C[0], z, COS_C[1]), z, COS_C[2])
+        cv = (fma(cp * z, z, F(-0.5) * z) + F(1.0)).astype(F)
+        q = k.astype(np.int64) & 3
+    s1, c1 = np.where(q & 1, cv, sv), np.where(q & 1, sv, cv)
+    sn = np.where(fin, np.where(q & 2, -s1, s1), F(np.nan)).astype(F)
+    cs = np.where(fin, np.where((q + 1) & 2, -c1, c1), F(np.nan)).astype(F)
+    return sn, cs
+
+
+def _eval_f32(xx, y, k, hr, t):
+    """E(t) of the header: g and yc of the trial t."""
+    fma = wa.fma
+    sx = sy = None
+    for i in range(4):
+        sg = t * GL4_C[i]
+        sn, cs = sincos_f32(fma(hr, sg, k) * sg)
+        sx = GL4_W[i] * cs if sx is None else fma(cs, GL4_W[i], sx)
+        sy = GL4_W[i] * sn if sy is None else fma(sn, GL4_W[i], sy)
+    dx, dy = xx - t * sx, y - t * sy
+    sn, cs = sincos_f32(fma(hr, t, k) * t)
+    return fma(dx, cs, dy * sn), fma(dy, cs, -(dx * sn))
+
+
+def _newton_f32(xx, y, z, k, c, R, t):
+    """The DEVICE_NEWTON steps from the start t and the closing evaluation: e, t, yc, g, the two denominators [2, n]."""
+    fma = wa.fma
+    hr = F(0.5) * c
+    dens = []
+    for _ in range(DEVICE_NEWTON):
+        g, yc = _eval_f32(xx, y, k, hr, t)
+        den = fma(-fma(t, c, k), yc, F(1.0))
+        dens.append(den)
+        t = (t + (g / den).astype(F)).astype(F)
+    g, yc = _eval_f32(xx, y, k, hr, t)
+    e = (np.sqrt(fma(yc, yc, z * z)) - R).astype(F)
+    return e, t, yc, g, np.array(dens, F).reshape(DEVICE_NEWTON, -1)
+
+
+def points_f32(xyz, f, labels=None, p=None, gate=None, shifts=None):
+    """The device's chain in float32, operation by operation (numpy rounds each float32 operation to nearest; fma is
+    fp32_np.fma32, rounded once; sin and cos follow the header's own rule): e, t, yc, z, the final g, the smaller of the
+    Newton denominators (den) and each of them (dens [steps, n]), cy, and tangent: whether the frame takes the tangent start
+    (|kappa_f| < 1e-6).  On such a frame nothing up to the station depends on atan2f; on the others the osculating-arc
+    start does, through t0 = atan2f(kappa_f x, cy) / kappa_f, which is taken in fp64 and rounded once.
+
+    With the map's parameters p it is the whole of wall_chain and returns what points() returns: e (NaN for plane
+    points), cls, cell, jl, `uncertain` in the place of `ambiguous` (wall_arc_np.bin_f32: the class or the cell changes
+    when the start's or the sector's angle is moved by -6 .. +6 fp32 ulps -- an ASSUMPTION about the device's atan2f, see
+    wall_arc_np.points_f32, also for `shifts`), e_lo / e_hi: per point the lowest and the highest e over the thirteen starts
+    (both e on a tangent-start frame), and e_mixed: some of the starts give a NaN e and some do not."""
+    fma = wa.fma
     x = np.asarray(xyz, F).reshape(-1, 3)
     o, a, n, b = (np.asarray(f[k], F) for k in ("o", "a", "n", "b"))
     k, c, R = F(f["kappa"]), F(f["rate"]), F(f["R"])
-    d64 = lambda v: np.asarray(v).astype(np.float64)  # noqa: E731
-    fma = lambda p, q, r: (d64(p) * d64(q) + d64(r)).astype(F)  # noqa: E731
-    q = x - o
-    dot3 = lambda w: fma(q[:, 0], w[0], fma(q[:, 1], w[1], q[:, 2] * w[2]))  # noqa: E731
-    xx, y, z = dot3(a), dot3(n), dot3(b)
-    cy = fma(y, -k, np.ones_like(y))
-    if abs(float(k)) < 1e-6:
-        t = xx.copy()
-    else:
-        t = (np.arctan2(d64(k * xx), d64(cy)).astype(F) / k).astype(F)
-    hr = F(0.5) * c
-
-    def sincos(ps):
-        """The header's sincos rule, operation by operation."""
-        fin = np.abs(ps) < F(1048576.0)
-        k = np.where(fin, np.rint(ps * F(0.63661977236758134)), F(0.0)).astype(F)
-        r = fma(-k, F(1.5703125), ps)
-        r = fma(-k, F(4.837512969970703125e-4), r)
-        r = fma(-k, F(7.54978995489188216e-8), r)
-        z = r * r
-        sp = fma(fma(np.full_like(z, F(-1.9515295891e-4)), z, F(8.3321608736e-3)), z, F(-1.6666654611e-1))
-        sv = fma(sp * z, r, r)
-        cp = fma(fma(np.full_like(z, F(2.443315711809948e-5)), z, F(-1.388731625493765e-3)), z, F(4.166664568298827e-2))
-        cv = (fma(cp * z, z, F(-0.5) * z) + F(1.0)).astype(F)
-        q = np.where(fin, k, 0).astype(np.int64) & 3
-        s1, c1 = np.where(q & 1, cv, sv), np.where(q & 1, sv, cv)
-        sn = np.where(fin, np.where(q & 2, -s1, s1), F(np.nan)).astype(F)
-        cs = np.where(fin, np.where((q + 1) & 2, -c1, c1), F(np.nan)).astype(F)
-        return sn, cs
-
-    def ev(t):
-        sx = sy = None
-        for i in range(4):
-            sg = t * GL4_C[i]
-            sn, cs = sincos(fma(hr, sg, np.full_like(sg, k)) * sg)
-            sx = GL4_W[i] * cs if sx is None else fma(cs, GL4_W[i], sx)
-            sy = GL4_W[i] * sn if sy is None else fma(sn, GL4_W[i], sy)
-        dx, dy = xx - t * sx, y - t * sy
-        sn, cs = sincos(fma(hr, t, np.full_like(t, k)) * t)
-        return fma(dx, cs, dy * sn), fma(dy, cs, -(dx * sn))
-
-    den_min = np.full(len(x), np.inf, F)
+    tangent = bool(abs(k) < F(1.0e-6))
     with np.errstate(all="ignore"):
-        for _ in range(DEVICE_NEWTON):
-            g, yc = ev(t)
-            den = fma(-fma(t, c, np.full_like(t, k)), yc, np.ones_like(t))
-            den_min = np.minimum(den_min, den)
-            t = (t + (g / den).astype(F)).astype(F)
-        g, yc = ev(t)
-        e = (np.sqrt(fma(yc, yc, z * z)) - R).astype(F)
-    return dict(e=e, t=t, yc=yc, z=z, g=g, den=den_min, cy=cy)
+        q = x - o
+        dot3 = lambda w: fma(q[:, 0], w[0], fma(q[:, 1], w[1], q[:, 2] * w[2]))  # noqa: E731
+        xx, y, z = dot3(a), dot3(n), dot3(b)
+        cy = fma(-k, y, F(1.0))
+        th = None if tangent else wa.atan2_f32(k * xx, cy)
+        t0 = xx.copy() if tangent else (th / k).astype(F)
+        e, t, yc, g, dens = _newton_f32(xx, y, z, k, c, R, t0)
+        den_min = np.minimum.reduce(dens, axis=0) if DEVICE_NEWTON else np.full(len(x), np.inf, F)
+        out = dict(e=e, t=t, yc=yc, z=z, g=g, den=den_min, dens=dens, cy=cy, tangent=tangent)
+        if p is None:
+            return out
+
+        def ok_of(t, g, dens):
+            good = (cy > F(0.0)) if wa.GUARD_CY else np.ones(len(x), bool)
+            if GUARD_DEN:
+                good = good & np.all(dens > F(MIN_DEN), axis=0)
+            return good & (np.abs(t) < F(np.inf)) & (np.abs(g) <= F(G_BOUND))
+
+        variants = [(e, ok_of(t, g, dens), t, yc, z)]
+        shifts = wa.SHIFTS if shifts is None else shifts
+        for s in (() if tangent else shifts[1:]):
+            ev, tv, ycv, gv, dv = _newton_f32(xx, y, z, k, c, R, (fp.ulp_steps(th, s) / k).astype(F))
+            variants.append((ev, ok_of(tv, gv, dv), tv, ycv, z))
+        out.update(wa.bin_f32(variants, f, p, labels, gate, shifts))
+        es = np.array([v[0] for v in variants], F)
+        nan = np.isnan(es)
+        out["e_mixed"] = nan.any(axis=0) & ~nan.all(axis=0)
+        out["e_lo"] = np.where(nan.any(axis=0), F(np.nan), np.min(np.where(nan, F(np.inf), es), axis=0))
+        out["e_hi"] = np.where(nan.any(axis=0), F(np.nan), np.max(np.where(nan, F(-np.inf), es), axis=0))
+    out["e"] = np.where(out["cls"] == PLANE, F(np.nan), e)
+    return out
 
 
 def row_table(D, p, station0, n, bs, anchor):
