@@ -1945,16 +1945,20 @@ class GeometricMappingGroup:
         return GeometricMapping._fit(f)
 
     def rank_fetch(self, rank, slot, what):
-        """Bulky output of a streamed frame: what in {"cropped_xyz", "normals", "voxel_centroids"} -> float32 [n,4]."""
+        """Bulky output of a streamed frame: what in {"cropped_xyz", "normals", "voxel_centroids"} -> float32 [n,4];
+        "neighbor_counts" (GM_CFG_KEEP_COUNTS) -> int32 [n_cropped], one per row that passed the rank's crop, in the order
+        the rows were sent (gm_get_neighbor_counts).  After process_frame, slot 0 of every rank holds that rank's slab of
+        the sharded frame: the rows it was sent (its own and its halo), of which only the rows it owns are valid."""
         fn = getattr(self._L, "gm_get_" + what)
         ctx = self._L.gm_group_ctx(self._grp, rank)
         n = C.c_uint32(0)
         st = fn(ctx, slot, None, 0, C.byref(n))
         if st not in (GM_OK, GM_ERR_CAPACITY):
             raise GmError(st, self._L.gm_last_error(ctx).decode())
-        out = np.empty((n.value, 4), dtype=np.float32)
+        counts = what == "neighbor_counts"
+        out = np.empty((n.value,) if counts else (n.value, 4), dtype=np.int32 if counts else np.float32)
         if n.value:
-            st = fn(ctx, slot, _f32(out), n.value, C.byref(n))
+            st = fn(ctx, slot, out.ctypes.data_as(fn.argtypes[2]), n.value, C.byref(n))
             if st != GM_OK:
                 raise GmError(st, self._L.gm_last_error(ctx).decode())
         return out
