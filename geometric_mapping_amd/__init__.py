@@ -16,8 +16,8 @@ def load_library():
 
 
 def __getattr__(name):
-    if name in ("GeometricMapping", "GeometricMappingGroup", "WallMap", "GmError", "solve_local_frame", "decode_compressed_map",
-                "GM_CFG_CYLINDER_FIT"):
+    if name in ("GeometricMapping", "GeometricMappingGroup", "WallMap", "WallAlignment", "WallAlignmentRule", "wall_element",
+                "GmError", "solve_local_frame", "decode_compressed_map", "GM_CFG_CYLINDER_FIT"):
         from . import api
         return getattr(api, name)
     raise AttributeError(name)

@@ -174,6 +174,28 @@ class WallClothoidAddInfo(C.Structure):
                 ("rate", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
+class WallElement(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_uint32), ("n_stations", C.c_uint32), ("reserved", C.c_uint32),
+                ("turn", C.c_double * 2), ("curvature", C.c_double), ("rate", C.c_double)]
+
+
+class WallAlignmentPiece(C.Structure):
+    _fields_ = [("element", C.c_uint32), ("station0", C.c_uint32), ("n_stations", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class WallAlignmentAddInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("status", C.c_uint32), ("element", C.c_uint32), ("n_sides", C.c_uint32),
+                ("chainage", C.c_double), ("reach", C.c_double), ("side_element", C.c_uint32 * 4),
+                ("side_anchor", C.c_int64 * 4), ("joint_o", (C.c_float * 3) * 3), ("joint_a", (C.c_float * 3) * 3),
+                ("offset", C.c_double)]
+
+
+class WallAlignmentTotals(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_elements", C.c_uint32), ("n_stations", C.c_uint64),
+                ("chainage_min", C.c_double), ("chainage_max", C.c_double), ("frames", C.c_uint64),
+                ("mapped", C.c_uint64), ("outside", C.c_uint64), ("beyond_gate", C.c_uint64), ("plane", C.c_uint64)]
+
+
 class WallParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_stations", C.c_uint32), ("n_sectors", C.c_uint32), ("reserved", C.c_uint32),
                 ("station_length", C.c_double), ("t_min", C.c_double), ("gate", C.c_double),
@@ -520,6 +542,8 @@ def load():
     u64, u64p = C.c_uint64, C.POINTER(C.c_uint64)
     warcp, warcaddp = C.POINTER(WallArc), C.POINTER(WallArcAddInfo)
     wclp, wcladdp = C.POINTER(WallClothoid), C.POINTER(WallClothoidAddInfo)
+    welp, wpcp, waladdp, waltotp = (C.POINTER(WallElement), C.POINTER(WallAlignmentPiece), C.POINTER(WallAlignmentAddInfo),
+                                    C.POINTER(WallAlignmentTotals))
     wregp, wrprmp, wrinfop, wrmetp = (C.POINTER(WallRegion), C.POINTER(WallRegionParams), C.POINTER(WallRegionsInfo),
                                       C.POINTER(WallRegionMetrics))
     wcprmp, wcptp, wcinfop = C.POINTER(WallCloudParams), C.POINTER(WallCloudPoint), C.POINTER(WallCloudInfo)
@@ -601,6 +625,19 @@ def load():
         "gm_wall_clothoid_frame": (C.c_int, [wprmp, wclp, C.c_double, dp, dp, dp, dp, dp, dp]),
         "gm_wall_clothoid_project": (C.c_int, [wprmp, wclp, dp, dp, dp, dp]),
         "gm_wall_clothoid_point": (C.c_int, [wprmp, wclp, C.c_double, C.c_double, C.c_double, dp]),
+        "gm_wall_alignment_check": (C.c_int, [wprmp, welp, u32]),
+        "gm_wall_alignment_element_params": (C.c_int, [wprmp, welp, u32, u32, wprmp, warcp, wclp]),
+        "gm_wall_alignment_project": (C.c_int, [wprmp, welp, u32, dp, u32p, dp, dp, dp]),
+        "gm_wall_alignment_point": (C.c_int, [wprmp, welp, u32, C.c_double, C.c_double, C.c_double, dp]),
+        "gm_wall_alignment_add_plan": (C.c_int, [wprmp, welp, u32, dp, C.c_double, waladdp]),
+        "gm_wall_alignment_window": (C.c_int, [wprmp, welp, u32, C.c_double, C.c_double, wpcp, u32, u32p]),
+        "gm_wall_alignment_create": (C.c_int, [vp, wprmp, welp, u32, C.POINTER(vp)]),
+        "gm_wall_alignment_destroy": (None, [vp]),
+        "gm_wall_alignment_map": (C.c_int, [vp, u32, C.POINTER(vp)]),
+        "gm_wall_alignment_add_frame": (C.c_int, [vp, vp, u32, dp, waladdp]),
+        "gm_wall_alignment_add_points": (C.c_int, [vp, fp, u32, u8p, dp, waladdp, fp, i32p, i32p]),
+        "gm_wall_alignment_sync": (C.c_int, [vp]),
+        "gm_wall_alignment_info": (C.c_int, [vp, waltotp]),
         "gm_wall_map_add_frame": (C.c_int, [vp, vp, u32, dp, waddp]),
         "gm_wall_map_add_points": (C.c_int, [vp, fp, u32, u8p, dp, waddp, fp, i32p]),
         "gm_wall_map_sync": (C.c_int, [vp]),

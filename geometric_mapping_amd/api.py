@@ -514,6 +514,12 @@ class GeometricMapping:
         (gm_wall_map_create_clothoid); not together with arc."""
         return WallMap(self, arc=arc, clothoid=clothoid, **params)
 
+    def wall_alignment(self, elements, **params):
+        """A wall alignment owned by this context (gm_wall_alignment_create): WallAlignment.  elements: wall_element()
+        structs or dicts of its keywords, in order; keywords: the template gm_wall_params of element 0 (n_stations is
+        not read)."""
+        return WallAlignment(self, elements, **params)
+
 
 RAW_CELL = np.dtype([("sum", "<i8"), ("count", "<u4"), ("min_key", "<u4"), ("max_key", "<u4"), ("reserved", "<u4")])
 _CELL = np.dtype([("count", "<u4"), ("mean", "<f4"), ("min", "<f4"), ("max", "<f4")])
@@ -1158,9 +1164,21 @@ class WallMap:
         self._ctx._check(self._L.gm_wall_map_get_clothoid(self._h(), C.byref(c)))
         return c
 
+    @classmethod
+    def _borrowed(cls, ctx, handle, prm):
+        """A WallMap on a handle somebody else owns (an alignment's element map): close() leaves the map alone."""
+        m = cls.__new__(cls)
+        m._ctx, m._L, m._map, m.prm, m._owned = ctx, ctx._L, handle, prm, False
+        m.n_stations, m.n_sectors = int(prm.n_stations), int(prm.n_sectors)
+        if not hasattr(ctx, "_walls"):
+            ctx._walls = []
+        ctx._walls.append(m)
+        return m
+
     def close(self):
         if self._map is not None:
-            self._L.gm_wall_map_destroy(self._map)
+            if getattr(self, "_owned", True):
+                self._L.gm_wall_map_destroy(self._map)
             self._map = None
             if self in getattr(self._ctx, "_walls", []):
                 self._ctx._walls.remove(self)
@@ -1765,6 +1783,191 @@ class WallMap:
                         radius=float(z["radius"]), **kw)
             m.add_raw(z["raw"].astype(RAW_CELL, copy=False))
         return m
+
+
+WALL_ELEMENT_KINDS = dict(straight=0, arc=1, clothoid=2)
+
+
+def wall_element(kind, n_stations, turn=(0.0, 0.0), curvature=0.0, rate=0.0):
+    """gm_wall_element: kind "straight", "arc" or "clothoid" (or the GM_WALL_ELEMENT_* number)."""
+    e = _lib.WallElement()
+    e.struct_size = C.sizeof(_lib.WallElement)
+    e.kind = WALL_ELEMENT_KINDS.get(kind, kind)
+    e.n_stations = int(n_stations)
+    e.turn[:] = [float(x) for x in turn]
+    e.curvature, e.rate = float(curvature), float(rate)
+    return e
+
+
+def _wall_elements(elements):
+    els = [e if isinstance(e, _lib.WallElement) else wall_element(**e) for e in elements]
+    return (_lib.WallElement * max(len(els), 1))(*els), len(els)
+
+
+def _alignment_add_info(i):
+    ns = int(i.n_sides)
+    return dict(status=int(i.status), element=int(i.element), n_sides=ns, chainage=float(i.chainage), reach=float(i.reach),
+                offset=float(i.offset), side_element=[int(x) for x in i.side_element[:ns]],
+                side_anchor=[int(x) for x in i.side_anchor[:ns]],
+                joint_o=np.array([list(r) for r in i.joint_o], dtype=np.float32)[:max(ns - 1, 0)],
+                joint_a=np.array([list(r) for r in i.joint_a], dtype=np.float32)[:max(ns - 1, 0)])
+
+
+class WallAlignmentRule:
+    """The device-free half of a wall alignment (gm_wall_alignment_check, _element_params, _project, _point, _window,
+    _add_plan; include/gm_hip.h states the rule): a template gm_wall_params and the elements.  Needs no context."""
+
+    wall_element = staticmethod(wall_element)
+
+    def __init__(self, elements, **params):
+        self._L = _lib.load()
+        self.prm = WallMap.params(**params)
+        self._els, self.n_elements = _wall_elements(elements)
+
+    def _head(self):
+        return C.byref(self.prm), self._els, self.n_elements
+
+    def check(self):
+        """gm_wall_alignment_check: the status."""
+        return int(self._L.gm_wall_alignment_check(*self._head()))
+
+    def element_params(self, i):
+        """gm_wall_alignment_element_params: (gm_wall_params, gm_wall_arc or None, gm_wall_clothoid or None) of element i,
+        what GeometricMapping.wall_map(arc=, clothoid=, **params) takes for a bitwise-equal map."""
+        p, a, c = _lib.WallParams(), _lib.WallArc(), _lib.WallClothoid()
+        _arc_call("gm_wall_alignment_element_params",
+                  self._L.gm_wall_alignment_element_params(*self._head(), int(i), C.byref(p), C.byref(a), C.byref(c)))
+        return p, (a if a.struct_size else None), (c if c.struct_size else None)
+
+    def project(self, xyz):
+        """gm_wall_alignment_project on map points [n, 3]: (element int64 [n], chainage, angle, e float64 [n]).  One
+        library call per point, and each call chains the alignment anew (include/gm_hip.h gives the cost): for poses,
+        windows and synthetic frames, not for a cloud per frame."""
+        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        el = np.empty(len(x), dtype=np.int64)
+        out = np.empty((len(x), 3), dtype=np.float64)
+        k_, s, ph, e = C.c_uint32(), C.c_double(), C.c_double(), C.c_double()
+        for k in range(len(x)):
+            _arc_call("gm_wall_alignment_project", self._L.gm_wall_alignment_project(
+                *self._head(), _dptr(x[k]), C.byref(k_), C.byref(s), C.byref(ph), C.byref(e)))
+            el[k] = k_.value
+            out[k] = (s.value, ph.value, e.value)
+        return el, out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
+
+    def point(self, chainage, angle, rho):
+        """gm_wall_alignment_point: the map points at (chainage, angle, rho), broadcast; float64 [n, 3].  One library call
+        per point, as project."""
+        s, ph, r = np.broadcast_arrays(np.asarray(chainage, np.float64), np.asarray(angle, np.float64), np.asarray(rho, np.float64))
+        s, ph, r = s.reshape(-1), ph.reshape(-1), r.reshape(-1)
+        out = np.empty((len(s), 3), dtype=np.float64)
+        for k in range(len(s)):
+            _arc_call("gm_wall_alignment_point", self._L.gm_wall_alignment_point(
+                *self._head(), float(s[k]), float(ph[k]), float(r[k]), _dptr(out[k])))
+        return out
+
+    def window(self, s_from, s_to):
+        """gm_wall_alignment_window: the pieces (element, station0, n_stations) of the chainage interval, in order."""
+        got = C.c_uint32(0)
+        st = self._L.gm_wall_alignment_window(*self._head(), float(s_from), float(s_to), None, 0, C.byref(got))
+        if st not in (_lib.GM_OK, _lib.GM_ERR_CAPACITY):
+            raise _lib.GmError(st, "gm_wall_alignment_window refused the arguments")
+        buf = (_lib.WallAlignmentPiece * max(int(got.value), 1))()
+        _arc_call("gm_wall_alignment_window",
+                  self._L.gm_wall_alignment_window(*self._head(), float(s_from), float(s_to), buf, int(got.value), C.byref(got)))
+        return [(int(b.element), int(b.station0), int(b.n_stations)) for b in buf[:int(got.value)]]
+
+    def add_plan(self, pose, bound):
+        """gm_wall_alignment_add_plan: the plan dict of an add under `pose` on a context whose boxFilterBound is `bound`;
+        GmError with GM_ERR_UNSUPPORTED for more than four sides."""
+        m = WallMap._pose(pose)
+        i = _lib.WallAlignmentAddInfo()
+        st = self._L.gm_wall_alignment_add_plan(*self._head(), _dptr(m), float(bound), C.byref(i))
+        if st != _lib.GM_OK:
+            raise _lib.GmError(st, "gm_wall_alignment_add_plan refused the arguments")
+        return _alignment_add_info(i)
+
+
+class WallAlignment(WallAlignmentRule):
+    """One gm_wall_alignment: the element maps of an alignment of straights, arcs and clothoids, chained end to end, and
+    the add of a frame to the elements it reaches in one launch.  Created by GeometricMapping.wall_alignment(); dies with
+    its context."""
+
+    def __init__(self, ctx, elements, **params):
+        super().__init__(elements, **params)
+        self._ctx, self._al = ctx, None
+        h = C.c_void_p()
+        ctx._check(self._L.gm_wall_alignment_create(ctx._ctx, *self._head(), C.byref(h)))
+        self._al = h
+        self._maps = {}
+
+    def _h(self):
+        if self._al is None or not self._ctx._ctx:
+            raise ValueError("the wall alignment is closed (or its context is)")
+        return self._al
+
+    def close(self):
+        if self._al is not None:
+            for m in self._maps.values():
+                m.close()
+            self._maps = {}
+            if self._ctx._ctx:
+                self._L.gm_wall_alignment_destroy(self._al)
+            self._al = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def element(self, i):
+        """gm_wall_alignment_map: element i's WallMap (non-owning: the alignment keeps the map)."""
+        i = int(i)
+        if i not in self._maps:
+            h = C.c_void_p()
+            self._ctx._check(self._L.gm_wall_alignment_map(self._h(), i, C.byref(h)))
+            self._maps[i] = WallMap._borrowed(self._ctx, h, self.element_params(i)[0])
+        return self._maps[i]
+
+    def add_frame(self, slot=0, pose=np.eye(4)[:3]):
+        """gm_wall_alignment_add_frame: enqueue the slot's last submitted frame under `pose`.  Returns the plan dict."""
+        m = WallMap._pose(pose)
+        i = _lib.WallAlignmentAddInfo()
+        self._ctx._check(self._L.gm_wall_alignment_add_frame(self._h(), self._ctx._ctx, slot, _dptr(m), C.byref(i)))
+        return _alignment_add_info(i)
+
+    def add_points(self, cloud, pose=np.eye(4)[:3], labels=None, outputs=True):
+        """gm_wall_alignment_add_points on a host cloud [n,3]: (plan, residual [n] float32, cell [n] int32 relative to the
+        owner's map, element [n] int32); outputs False skips the per-point arrays (None each)."""
+        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+        m = WallMap._pose(pose)
+        lab, lp = GeometricMapping._u8(labels)
+        i = _lib.WallAlignmentAddInfo()
+        n = len(xyz)
+        res = np.empty(max(n, 1), dtype=np.float32) if outputs else None
+        cell = np.empty(max(n, 1), dtype=np.int32) if outputs else None
+        el = np.empty(max(n, 1), dtype=np.int32) if outputs else None
+        i32 = C.POINTER(C.c_int32)
+        self._ctx._check(self._L.gm_wall_alignment_add_points(
+            self._h(), _f32(xyz), n, lp, _dptr(m), C.byref(i), _f32(res) if outputs else None,
+            cell.ctypes.data_as(i32) if outputs else None, el.ctypes.data_as(i32) if outputs else None))
+        if not outputs:
+            return _alignment_add_info(i), None, None, None
+        return _alignment_add_info(i), res[:n].copy(), cell[:n].copy(), el[:n].copy()
+
+    def sync(self):
+        self._ctx._check(self._L.gm_wall_alignment_sync(self._h()))
+
+    def info(self):
+        """gm_wall_alignment_info: n_elements, n_stations, chainage_min, chainage_max and the summed frames and classes."""
+        i = _lib.WallAlignmentTotals()
+        self._ctx._check(self._L.gm_wall_alignment_info(self._h(), C.byref(i)))
+        d = {k: int(getattr(i, k)) for k in ("n_elements", "n_stations", "frames", "mapped", "outside", "beyond_gate", "plane")}
+        d.update(chainage_min=float(i.chainage_min), chainage_max=float(i.chainage_max))
+        return d
+
+    def add_plan(self, pose, bound=None):
+        return super().add_plan(pose, float(self._ctx.cfg.boxFilterBound) if bound is None else bound)
 
 
 def decode_compressed_map(buf):

@@ -169,6 +169,7 @@ struct gm_ctx {
     bool force_voxel_sort = false;
     gm_surface_params surf;   // gm_set_surface_params (the frames' map parameters)
     std::vector<gm_wall_map *> walls;   // persistent wall maps created from this context (gm_wall.hip), freed with it
+    std::vector<gm_wall_alignment *> alignments;   // wall alignments (gm_wall_alignment.hip): their element maps are in `walls`
     std::string err;
 };
 
@@ -330,6 +331,37 @@ size_t wall_table_bytes(uint64_t ncell);
 void launch_wall_add(const WallArgs &a, uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
 void launch_wall_add_arc(const WallArgs &a, const WallArc &arc, uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
 void launch_wall_add_clothoid(const WallArgs &a, const WallClothoid &cl, uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
+// k_wall_joint.hip (gm_wall_alignment_add_*): one launch for a frame that straddles joints of an alignment.  Each point is
+// owned by one side (an element map) and runs that side's chain alone.
+struct WallJointSide {
+    int64_t anchor;            // j_f of this side's own add
+    float o[3], a[3], u[3], v[3];   // its frame-local map frame, as WallArgs
+    WallClothoid ax;           // its axis block (an arc side fills ax.arc alone, a straight side nothing)
+    WallTable table;
+    uint32_t n_stations;
+    int32_t win_first;         // its LDS window, as WallArgs: whole stations of the element
+    uint32_t win_stations;
+    uint32_t lds_first;        // the window's first cell in the block's LDS table
+    int32_t axis;              // kAxisStraight, kAxisArc, kAxisClothoid
+    int32_t element;           // the element's index in the alignment
+};
+struct WallJointArgs {
+    const float4 *pts;
+    const uint8_t *labels;     // nullptr: no point is plane
+    const uint32_t *n_ptr;     // device point count (nullptr: n_host)
+    uint32_t n_host;
+    uint32_t n_sides;          // 2 .. GM_WALL_JOINT_MAX_SIDES
+    uint32_t n_sectors;
+    uint32_t lds_cells;        // the cells of the LDS table dealt to the sides' windows, <= GM_SURF_MAX_CELLS
+    float R, station_length, gate, sector_angle, two_pi;   // one grid for every element
+    float jo[GM_WALL_JOINT_MAX_SIDES - 1][3];   // Jo' of the joint between side i and side i + 1
+    float ja[GM_WALL_JOINT_MAX_SIDES - 1][3];   // aJ'
+    float *res;                // stage call only (nullptr in the frame path)
+    int32_t *cell;
+    int32_t *element;
+    WallJointSide side[GM_WALL_JOINT_MAX_SIDES];
+};
+void launch_wall_add_joint(const WallJointArgs &a, uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
 // k_wall_add_checked.hip (gm_wall_map_add_*_checked): mark the selected rows' points in a bit mask, then k_wall_add's masked
 // instantiation.  u64 words of the call's counter block: rows_neg, rows_pos, rows_kept, rows_rejected | skipped, mapped,
 // outside, beyond_gate, plane | n_rows, n_points, pad
@@ -369,6 +401,7 @@ void launch_wall_merge_raw(const WallTable &T, uint64_t first, uint64_t n, const
 void launch_wall_clear(const WallTable &T, uint64_t first, uint64_t n, bool totals_too, hipStream_t s);
 void launch_wall_count(const WallTable &T, uint64_t n, hipStream_t s);
 void gm_wall_free_all(gm_ctx *ctx);   // gm_destroy: the maps still alive
+void gm_wall_alignment_free_all(gm_ctx *ctx);   // ... and, ahead of them, the alignments (their maps go with the maps)
 // k_wall_regions.hip (gm_wall_map_regions): tiles -> seams -> flatten | reduce -> select | labels
 constexpr uint32_t kWallRegionTileCells = 4096;    // the most cells of a tile (its LDS tables)
 constexpr int kWallRegionCounters = 8;             // u64: flagged_pos, flagged_neg, unusable, empty, components, regions, pad

@@ -456,6 +456,7 @@ gm_status cloud_chunks(gm_wall_map *map, const gm_wall_cloud_params &cp, gm_wall
 namespace gm {
 void gm_wall_free_all(gm_ctx *ctx)
 {
+    gm_wall_alignment_free_all(ctx);
     for (gm_wall_map *m : ctx->walls) free_map(m);
     ctx->walls.clear();
 }

@@ -1,0 +1,362 @@
+// gm_wall_alignment_host.hip -- the part of the wall alignment's C ABI that needs no device (include/gm_hip.h states the
+// rule): the chaining of the element maps, the joint planes, ownership, project, point, the chainage window and the plan
+// of an add.  Like gm_wall_host.hip it links against libm and the C++ library alone; host/gm_wall_alignment_host_test.cpp
+// runs it under the host sanitizers.
+#include <stdio.h>
+
+#include <vector>
+
+#define GM_WALL_HOST_ONLY
+#include "gm_wall_map.hpp"
+
+using namespace gm;
+using namespace gm::wall;
+
+namespace gm {
+namespace wall {
+
+// the section at the element's end: P(s_end), a(s_end), u(s_end)
+static void element_end(const AlignElem &E, double P[3], double a[3], double u[3])
+{
+    if (E.kind == GM_WALL_ELEMENT_ARC) {
+        double ns[3];
+        arc_section(E.d, E.af, E.s_end, a, ns, P);
+        for (int k = 0; k < 3; ++k) u[k] = E.af.un * ns[k] + E.af.ub * E.af.b[k];
+    } else if (E.kind == GM_WALL_ELEMENT_CLOTHOID) {
+        double ns[3];
+        clothoid_section(E.d, E.cf, E.s_end - E.cf.s0, a, ns, P);
+        for (int k = 0; k < 3; ++k) u[k] = E.cf.un * ns[k] + E.cf.ub * E.cf.b[k];
+    } else {
+        const double t = E.p.t_min + (double)E.p.n_stations * E.p.station_length;
+        for (int k = 0; k < 3; ++k) { P[k] = E.d.o[k] + t * E.d.a[k]; a[k] = E.d.a[k]; u[k] = E.d.u[k]; }
+    }
+}
+
+gm_status alignment_build(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n, Alignment &A)
+{
+    A.el.clear();
+    if (!params || !elements || n < 1u || n > GM_WALL_ALIGNMENT_MAX_ELEMENTS) return GM_ERR_INVALID_ARG;
+    gm_wall_params t = *params;
+    t.n_stations = 1u;
+    if (check_params(&t) != GM_OK) return GM_ERR_INVALID_ARG;
+    const double ds = params->station_length;
+    try {
+        A.el.resize(n);
+    } catch (...) {
+        return GM_ERR_OOM;
+    }
+    double s = params->t_min;
+    for (uint32_t i = 0; i < n; ++i) {
+        const gm_wall_element &e = elements[i];
+        if (e.struct_size != sizeof(gm_wall_element) || e.reserved != 0u || e.kind > GM_WALL_ELEMENT_CLOTHOID || e.n_stations < 1u)
+            return GM_ERR_INVALID_ARG;
+        AlignElem &E = A.el[i];
+        E.kind = e.kind;
+        E.p = t;
+        E.p.n_stations = e.n_stations;
+        E.s_start = s;
+        E.s_end = s + (double)e.n_stations * ds;
+        E.offset = 0.0;
+        memset(&E.arc, 0, sizeof(E.arc));
+        memset(&E.cl, 0, sizeof(E.cl));
+        memset(&E.af, 0, sizeof(E.af));
+        if (!isfinite(E.s_end)) return GM_ERR_INVALID_ARG;
+        if (i > 0u) {
+            double P[3], a[3], u[3];
+            element_end(A.el[i - 1u], P, a, u);
+            for (int k = 0; k < 3; ++k) { E.p.point[k] = P[k]; E.p.direction[k] = a[k]; E.p.forward[k] = a[k]; E.p.up[k] = u[k]; }
+            E.p.t_min = s;
+        }
+        if (check_params(&E.p) != GM_OK) return GM_ERR_INVALID_ARG;
+        design_frame_of(E.p, E.d);
+        double m[3] = {0.0, 0.0, 0.0};
+        if (e.kind != GM_WALL_ELEMENT_STRAIGHT) {
+            const double tl = sqrt(e.turn[0] * e.turn[0] + e.turn[1] * e.turn[1]);
+            if (!isfinite(tl) || !(tl > 0.0) || !isfinite(e.curvature)) return GM_ERR_INVALID_ARG;
+            const double t0 = e.turn[0] / tl, t1 = e.turn[1] / tl;
+            for (int k = 0; k < 3; ++k) m[k] = t0 * E.d.u[k] + t1 * E.d.v[k];
+        }
+        if (e.kind == GM_WALL_ELEMENT_ARC) {
+            if (!(e.curvature > 0.0)) return GM_ERR_INVALID_ARG;
+            E.arc.struct_size = (uint32_t)sizeof(gm_wall_arc);
+            for (int k = 0; k < 3; ++k) E.arc.curvature[k] = e.curvature * m[k];
+            E.arc.point_chainage = s;
+            if (arc_check(&E.p, &E.arc, E.d, E.af) != GM_OK) return GM_ERR_INVALID_ARG;
+        } else if (e.kind == GM_WALL_ELEMENT_CLOTHOID) {
+            E.cl.struct_size = (uint32_t)sizeof(gm_wall_clothoid);
+            for (int k = 0; k < 3; ++k) E.cl.normal[k] = m[k];
+            E.cl.curvature = e.curvature;
+            E.cl.rate = e.rate;
+            E.cl.point_chainage = s;
+            const gm_status st = clothoid_check(&E.p, &E.cl, E.d, E.cf);
+            if (st != GM_OK) return st == GM_ERR_OOM ? GM_ERR_OOM : GM_ERR_INVALID_ARG;
+        } else if (i > 0u) {   // the straight rule's own chainage of `point`
+            E.p.t_min = dot(E.p.point, E.d.a);
+            if (check_params(&E.p) != GM_OK) return GM_ERR_INVALID_ARG;
+            E.offset = s - E.p.t_min;
+        }
+        s = E.s_end;
+    }
+    A.ds = ds;
+    return GM_OK;
+}
+
+// the element's own project rule on x: chainage along the alignment, angle, e
+static void element_project(const AlignElem &E, const double x[3], double &chainage, double &angle, double &e)
+{
+    double yc, zb, un, ub, vn, vb;
+    if (E.kind == GM_WALL_ELEMENT_STRAIGHT) {
+        const double r[3] = {x[0] - E.d.o[0], x[1] - E.d.o[1], x[2] - E.d.o[2]};
+        const double t = dot(r, E.d.a);
+        const double w[3] = {r[0] - t * E.d.a[0], r[1] - t * E.d.a[1], r[2] - t * E.d.a[2]};
+        chainage = t + E.offset;
+        e = sqrt(dot(w, w)) - E.d.R;
+        const double th = atan2(dot(w, E.d.v), dot(w, E.d.u));
+        angle = th < 0.0 ? th + kTwoPi : th;
+        return;
+    }
+    if (E.kind == GM_WALL_ELEMENT_ARC) {   // gm_wall_arc_project
+        const ArcFrame &f = E.af;
+        const double r[3] = {x[0] - f.C[0], x[1] - f.C[1], x[2] - f.C[2]};
+        const double xa = dot(r, E.d.a), xn = dot(r, f.n);
+        zb = dot(r, f.b);
+        chainage = f.s0 + atan2(xa, -xn) / f.kappa;
+        yc = f.inv_kappa - sqrt(xa * xa + xn * xn);
+        un = f.un; ub = f.ub; vn = f.vn; vb = f.vb;
+    } else {   // gm_wall_clothoid_project
+        const ClothoidFrame &f = E.cf;
+        yc = 0.0;
+        const double tau = clothoid_foot(E.d, f, x, &yc, nullptr);
+        const double r[3] = {x[0] - f.pt[0], x[1] - f.pt[1], x[2] - f.pt[2]};
+        zb = dot(r, f.b);
+        chainage = f.s0 + tau;
+        un = f.un; ub = f.ub; vn = f.vn; vb = f.vb;
+    }
+    e = sqrt(yc * yc + zb * zb) - E.d.R;
+    const double th = atan2(yc * vn + zb * vb, yc * un + zb * ub);
+    angle = th < 0.0 ? th + kTwoPi : th;
+}
+
+// d_i(x) < 0 for joint i (between elements i and i + 1)
+static bool before_joint(const Alignment &A, uint32_t i, const double x[3])
+{
+    const AlignElem &N = A.el[i + 1u];
+    const double r[3] = {x[0] - N.p.point[0], x[1] - N.p.point[1], x[2] - N.p.point[2]};
+    return dot(r, N.d.a) < 0.0;
+}
+
+// The owner looks at an element's OWN two joints only: element i is a candidate when x lies on its side of both (not before
+// the joint at its start, before the joint at its end; the alignment's two ends are open).  There is always one: the element
+// before the first joint x lies before, or the last.  An alignment that turns a quarter turn or more brings x between the
+// joints of an element far away as well; of several candidates the owner is the one whose axis, cut to its span, is
+// nearest to x (ties: the lowest index).
+void alignment_project(const Alignment &A, const double x[3], uint32_t &element, double &chainage, double &angle, double &e)
+{
+    const uint32_t n = (uint32_t)A.el.size();
+    double best = INFINITY;
+    bool have = false;
+    bool after_prev = true;   // x is not before the joint at this element's start
+    for (uint32_t i = 0; i < n; ++i) {
+        const bool before_next = i + 1u < n ? before_joint(A, i, x) : true;
+        const bool candidate = after_prev && before_next;
+        after_prev = !before_next;
+        if (!candidate) continue;
+        double s, ph, ee;
+        element_project(A.el[i], x, s, ph, ee);
+        const AlignElem &E = A.el[i];
+        const double over = s < E.s_start ? E.s_start - s : (s > E.s_end ? s - E.s_end : 0.0);
+        const double rho = ee + E.d.R;
+        double dist = sqrt(rho * rho + over * over);
+        if (!isfinite(dist)) dist = INFINITY;
+        if (!have || dist < best) {
+            have = true;
+            best = dist;
+            element = i;
+            chainage = s;
+            angle = ph;
+            e = ee;
+        }
+    }
+}
+
+uint32_t alignment_owner(const Alignment &A, const double x[3])
+{
+    uint32_t el = 0;
+    double s, ph, e;
+    alignment_project(A, x, el, s, ph, e);
+    return el;
+}
+
+void alignment_point(const Alignment &A, double chainage, double angle, double rho, double xyz[3])
+{
+    uint32_t i = 0;
+    while (i + 1u < (uint32_t)A.el.size() && chainage >= A.el[i].s_end) ++i;
+    const AlignElem &E = A.el[i];
+    const double c = cos(angle), s = sin(angle);
+    if (E.kind == GM_WALL_ELEMENT_STRAIGHT) {
+        const double t = chainage - E.offset;
+        for (int k = 0; k < 3; ++k) xyz[k] = (E.d.o[k] + t * E.d.a[k]) + rho * (c * E.d.u[k] + s * E.d.v[k]);
+    } else if (E.kind == GM_WALL_ELEMENT_ARC) {   // gm_wall_arc_point
+        const ArcFrame &f = E.af;
+        const double psi = f.kappa * (chainage - f.s0);
+        const double cp = cos(psi), sp = sin(psi);
+        const double yc = rho * (c * f.un + s * f.vn), zb = rho * (c * f.ub + s * f.vb);
+        const double r = yc - f.inv_kappa;
+        for (int k = 0; k < 3; ++k) {
+            const double nr = f.n[k] * cp - E.d.a[k] * sp;
+            xyz[k] = (f.C[k] + r * nr) + zb * f.b[k];
+        }
+    } else {   // gm_wall_clothoid_point
+        const ClothoidFrame &f = E.cf;
+        double as[3], ns[3], P[3];
+        clothoid_section(E.d, f, chainage - f.s0, as, ns, P);
+        const double yc = rho * (c * f.un + s * f.vn), zb = rho * (c * f.ub + s * f.vb);
+        for (int k = 0; k < 3; ++k) xyz[k] = (P[k] + yc * ns[k]) + zb * f.b[k];
+    }
+}
+
+// the anchor station of the element map's own add under (Rm, tr); false: out of range
+static bool element_anchor(const AlignElem &E, const double Rm[3][3], const double tr[3], int64_t &anchor)
+{
+    if (E.kind == GM_WALL_ELEMENT_ARC) {
+        gm_wall_arc_add_info ai;
+        if (!arc_add_frame(E.p, E.d, E.af, Rm, tr, ai, nullptr, nullptr, nullptr)) return false;
+        anchor = ai.anchor_station;
+    } else if (E.kind == GM_WALL_ELEMENT_CLOTHOID) {
+        gm_wall_clothoid_add_info ai;
+        if (!clothoid_add_frame(E.p, E.d, E.cf, Rm, tr, ai, nullptr, nullptr, nullptr)) return false;
+        anchor = ai.anchor_station;
+    } else {   // add_frame_args' straight rule
+        const double rel[3] = {tr[0] - E.d.o[0], tr[1] - E.d.o[1], tr[2] - E.d.o[2]};
+        const double jd = floor((dot(rel, E.d.a) - E.p.t_min) / E.p.station_length);
+        if (!(fabs(jd) < 4.0e18)) return false;
+        anchor = (int64_t)jd;
+    }
+    return true;
+}
+
+gm_status alignment_add_plan(const Alignment &A, const double pose[12], double bound, gm_wall_alignment_add_info *info)
+{
+    double Rm[3][3], tr[3];
+    if (!pose || !info || !isfinite(bound) || !(bound > 0.0) || pose_split(pose, Rm, tr)) return GM_ERR_INVALID_ARG;
+    memset(info, 0, sizeof(*info));
+    info->struct_size = (uint32_t)sizeof(gm_wall_alignment_add_info);
+    uint32_t el = 0;
+    double s = 0.0, angle = 0.0, e = 0.0;
+    alignment_project(A, tr, el, s, angle, e);
+    if (!isfinite(s)) return GM_ERR_INVALID_ARG;
+    const double L = 2.0 * bound * 1.7320508075688772 + A.ds;
+    info->element = el;
+    info->chainage = s;
+    info->reach = L;
+    info->offset = A.el[el].offset;
+    uint32_t lo = el, hi = el;
+    while (lo > 0u && A.el[lo - 1u].s_end > s - L) --lo;
+    while (hi + 1u < (uint32_t)A.el.size() && A.el[hi + 1u].s_start < s + L) ++hi;
+    const uint32_t ns = hi - lo + 1u;
+    if (ns > GM_WALL_JOINT_MAX_SIDES) return GM_ERR_UNSUPPORTED;
+    info->n_sides = ns;
+    for (uint32_t k = 0; k < ns; ++k) {
+        const AlignElem &E = A.el[lo + k];
+        info->side_element[k] = lo + k;
+        info->status |= E.d.status;
+        if (!element_anchor(E, Rm, tr, info->side_anchor[k])) return GM_ERR_INVALID_ARG;
+        if (k + 1u < ns) {
+            const AlignElem &N = A.el[lo + k + 1u];
+            const double r[3] = {N.p.point[0] - tr[0], N.p.point[1] - tr[1], N.p.point[2] - tr[2]};
+            for (int c = 0; c < 3; ++c) {   // Rm^T x
+                info->joint_o[k][c] = (float)(Rm[0][c] * r[0] + Rm[1][c] * r[1] + Rm[2][c] * r[2]);
+                info->joint_a[k][c] = (float)(Rm[0][c] * N.d.a[0] + Rm[1][c] * N.d.a[1] + Rm[2][c] * N.d.a[2]);
+            }
+        }
+    }
+    return GM_OK;
+}
+
+gm_status alignment_window(const Alignment &A, double s_from, double s_to, gm_wall_alignment_piece *pieces, uint32_t capacity,
+                           uint32_t *n_out)
+{
+    if (!n_out || !isfinite(s_from) || !isfinite(s_to) || s_from > s_to || (capacity && !pieces)) return GM_ERR_INVALID_ARG;
+    uint32_t got = 0;
+    for (uint32_t i = 0; i < (uint32_t)A.el.size(); ++i) {
+        const AlignElem &E = A.el[i];
+        const double lo = std::max(s_from, E.s_start), hi = std::min(s_to, E.s_end);
+        if (!(lo < hi)) continue;
+        const double nst = (double)E.p.n_stations;
+        const double j0 = std::min(std::max(floor((lo - E.s_start) / A.ds), 0.0), nst);
+        const double j1 = std::min(std::max(ceil((hi - E.s_start) / A.ds), 0.0), nst);
+        if (!(j0 < j1)) continue;
+        if (got < capacity) {
+            pieces[got].element = i;
+            pieces[got].station0 = (uint32_t)j0;
+            pieces[got].n_stations = (uint32_t)(j1 - j0);
+            pieces[got].reserved = 0u;
+        }
+        ++got;
+    }
+    *n_out = got;
+    return got > capacity ? GM_ERR_CAPACITY : GM_OK;
+}
+
+}  // namespace wall
+}  // namespace gm
+
+extern "C" {
+
+gm_status gm_wall_alignment_check(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n)
+{
+    Alignment A;
+    return alignment_build(params, elements, n, A);
+}
+
+gm_status gm_wall_alignment_element_params(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n, uint32_t i,
+                                           gm_wall_params *out, gm_wall_arc *arc, gm_wall_clothoid *clothoid)
+{
+    Alignment A;
+    if (!out) return GM_ERR_INVALID_ARG;
+    GMW_OK(alignment_build(params, elements, n, A));
+    if (i >= n) return GM_ERR_INVALID_ARG;
+    *out = A.el[i].p;
+    if (arc) *arc = A.el[i].arc;
+    if (clothoid) *clothoid = A.el[i].cl;
+    return GM_OK;
+}
+
+gm_status gm_wall_alignment_project(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n, const double xyz[3],
+                                    uint32_t *element, double *chainage, double *angle, double *e)
+{
+    Alignment A;
+    if (!xyz || !element || !chainage || !angle || !e) return GM_ERR_INVALID_ARG;
+    GMW_OK(alignment_build(params, elements, n, A));
+    if (!isfinite(xyz[0]) || !isfinite(xyz[1]) || !isfinite(xyz[2])) return GM_ERR_INVALID_ARG;
+    alignment_project(A, xyz, *element, *chainage, *angle, *e);
+    return GM_OK;
+}
+
+gm_status gm_wall_alignment_point(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n, double chainage,
+                                  double angle, double rho, double xyz[3])
+{
+    Alignment A;
+    if (!xyz || !isfinite(chainage) || !isfinite(angle) || !isfinite(rho)) return GM_ERR_INVALID_ARG;
+    GMW_OK(alignment_build(params, elements, n, A));
+    alignment_point(A, chainage, angle, rho, xyz);
+    return GM_OK;
+}
+
+gm_status gm_wall_alignment_add_plan(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n,
+                                     const double pose[12], double bound, gm_wall_alignment_add_info *info)
+{
+    Alignment A;
+    GMW_OK(alignment_build(params, elements, n, A));
+    return alignment_add_plan(A, pose, bound, info);
+}
+
+gm_status gm_wall_alignment_window(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n, double s_from,
+                                   double s_to, gm_wall_alignment_piece *pieces, uint32_t capacity, uint32_t *n_out)
+{
+    Alignment A;
+    GMW_OK(alignment_build(params, elements, n, A));
+    return alignment_window(A, s_from, s_to, pieces, capacity, n_out);
+}
+
+}  // extern "C"

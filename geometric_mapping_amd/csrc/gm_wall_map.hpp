@@ -76,6 +76,32 @@ double clothoid_foot(const DesignFrame &d, const ClothoidFrame &f, const double 
 // arc_add_frame on a clothoid map
 bool clothoid_add_frame(const gm_wall_params &p, const DesignFrame &d, const ClothoidFrame &f, const double Rm[3][3],
                         const double tr[3], gm_wall_clothoid_add_info &out, double *u64, double *v64, double *a1);
+// ---- gm_wall_alignment_host.hip: a wall alignment (include/gm_hip.h: gm_wall_alignment_create), no device either ----
+// One element: its derived structs (what its map is created from), their frames, its chainage span in the alignment and
+// the offset of a straight element (alignment chainage = map chainage + offset).
+struct AlignElem {
+    uint32_t kind = 0;
+    gm_wall_params p;
+    gm_wall_arc arc;
+    gm_wall_clothoid cl;
+    DesignFrame d;
+    ArcFrame af;
+    ClothoidFrame cf;
+    double s_start = 0.0, s_end = 0.0, offset = 0.0;
+};
+struct Alignment {
+    std::vector<AlignElem> el;
+    double ds = 0.0;
+};
+// the chaining and every refusal of it; GM_ERR_OOM or GM_ERR_INVALID_ARG
+gm_status alignment_build(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n, Alignment &A);
+uint32_t alignment_owner(const Alignment &A, const double x[3]);
+void alignment_project(const Alignment &A, const double x[3], uint32_t &element, double &chainage, double &angle, double &e);
+void alignment_point(const Alignment &A, double chainage, double angle, double rho, double xyz[3]);
+// the plan of an add: everything of info; GM_ERR_UNSUPPORTED: too many sides
+gm_status alignment_add_plan(const Alignment &A, const double pose[12], double bound, gm_wall_alignment_add_info *info);
+gm_status alignment_window(const Alignment &A, double s_from, double s_to, gm_wall_alignment_piece *pieces, uint32_t capacity,
+                           uint32_t *n_out);
 // the library's pose check: 0 the pose is accepted (Rm, tr filled), 1 an entry is not finite, 2 Rm is not a rotation
 int pose_split(const double pose[12], double Rm[3][3], double tr[3]);
 // the direction table of include/gm_hip.h: NK pairs (one operation per statement, as stated there)

@@ -24,25 +24,9 @@
 #include <math.h>
 #include <string.h>
 
-#include "gm_internal.hpp"
-#include "gm_point_stream.hpp"
+#include "gm_wall_add.hpp"   // the launch shape and the map's integer update, shared with k_wall_joint.hip
 
 namespace gm {
-
-constexpr int kWallThreads = 1024;
-constexpr uint32_t kWallMaxBlocks = 256;          // one per CU
-constexpr int kWallUnroll = 2;
-constexpr uint32_t kWallCells = GM_SURF_MAX_CELLS;
-constexpr float kWallFix = 1048576.0f;   // 2^20, as k_surface.hip
-
-__device__ __forceinline__ void wall_global_add(const WallTable &T, uint64_t c, uint32_t cn, unsigned long long sm, uint32_t lo,
-                                                uint32_t hi)
-{
-    atomicAdd(&T.cnt[c], cn);
-    atomicAdd(&T.sum[c], sm);
-    atomicMax(&T.lo[c], lo);
-    atomicMax(&T.hi[c], hi);
-}
 
 // kMasked (gm_wall_map_add_*_checked, k_wall_add_checked.hip marks the bits): bit i of m.words set = point i is SKIPPED,
 // decided before every other class: it takes cell -1 and no count ahead of the run merge (every lane still takes part in

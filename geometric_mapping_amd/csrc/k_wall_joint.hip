@@ -1,0 +1,155 @@
+// k_wall_joint.hip -- BUILD-DEFINED EXTENSION: the add of a frame that straddles joints of a wall alignment
+// (gm_wall_alignment_add_*; include/gm_hip.h states the rule), the device side.
+//
+// k_wall_add's shape (gm_wall_add.hpp: kWallThreads per block, the wall_blocks grid, one streaming pass, the 80 KiB LDS
+// table, the in-wave run merge, integer atomics only), over up to GM_WALL_JOINT_MAX_SIDES element maps at once:
+//   1. every point is given its owner: d_i = (p - Jo'_i).aJ'_i for the joint planes in ascending order, the side before
+//      the first d_i < 0, the last side if there is none;
+//   2. the point runs its owner's chain and no other: a loop over the sides, wave-uniform, with a wave-uniform switch on
+//      the side's axis kind in front of the three chain heads of gm_device.hpp (wall_chain, exactly as k_wall_add,
+//      k_wall_add_arc and k_wall_add_clothoid instantiate it).  A wave whose lanes have different owners runs each of
+//      their chains once, under the lanes' mask; the side's frame stays in scalar registers;
+//   3. the run merge on the key side << 24 | cell (two sides have equal cell indices; a cell is < 2^24), every shuffle
+//      wave-uniform; the run's head lane adds to the LDS table when the cell lies in its side's window -- the table's
+//      GM_SURF_MAX_CELLS cells are dealt to the sides in order by the host -- and to the owner's map otherwise;
+//   4. one flush per side, and the class counts to the owner's totals: a wave counts its points per (side, class) by
+//      ballot into lane side * 4 + class, and the block's rows are summed by block_row_sums.
+#include "gm_wall_add.hpp"
+
+namespace gm {
+
+constexpr int kJointSides = GM_WALL_JOINT_MAX_SIDES;
+constexpr int kJointCls = 4 * kJointSides;   // (side, class): mapped, outside, beyond_gate, plane per side
+
+// what wall_chain and wall_station read of WallArgs, of one side
+struct JointChainArgs {
+    float o[3], a[3], u[3], v[3];
+    float R, station_length, gate, sector_angle, two_pi;
+    uint32_t n_sectors, n_stations;
+    int64_t anchor;
+};
+
+__global__ __launch_bounds__(kWallThreads) void k_wall_add_joint(WallJointArgs a)
+{
+    __shared__ unsigned long long s_sum[kWallCells];
+    __shared__ uint32_t s_cnt[kWallCells];
+    __shared__ uint32_t s_lo[kWallCells];
+    __shared__ uint32_t s_hi[kWallCells];
+    __shared__ uint32_t s_cls[kJointCls][kWallThreads / kWave];
+    // the joint planes, read per point from LDS (a broadcast): 18 scalar registers less beside the sides' frames, which
+    // keeps the kernel free of scalar spills
+    __shared__ float s_plane[kJointSides - 1][6];
+    const uint32_t n = a.n_ptr ? *a.n_ptr : a.n_host;
+    const uint32_t nsec = a.n_sectors;
+    const uint32_t nside = a.n_sides;
+    const uint32_t wcells = a.lds_cells;   // <= kWallCells (the host deals the windows)
+    const int lane = lane_id();
+
+    for (uint32_t c = threadIdx.x; c < wcells; c += kWallThreads) { s_sum[c] = 0ull; s_cnt[c] = 0u; s_lo[c] = 0u; s_hi[c] = 0u; }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int jn = 0; jn < kJointSides - 1; ++jn)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { s_plane[jn][k] = a.jo[jn][k]; s_plane[jn][3 + k] = a.ja[jn][k]; }
+    }
+    __syncthreads();
+
+    uint32_t mine = 0u;   // lane c < 4 n_sides: this wave's points of class c & 3 owned by side c >> 2
+    auto point = [&](uint64_t i, bool in, const float4 &q, uint32_t lab) {
+        uint32_t owner = nside - 1u;
+#pragma unroll
+        for (int jn = kJointSides - 2; jn >= 0; --jn) {   // descending: the lowest joint with d < 0 stays
+            if ((uint32_t)jn + 1u < nside) {              // (wave-uniform)
+                const float(&pl)[6] = s_plane[jn];
+                const float qx = __fsub_rn(q.x, pl[0]), qy = __fsub_rn(q.y, pl[1]), qz = __fsub_rn(q.z, pl[2]);
+                const float aj[3] = {pl[3], pl[4], pl[5]};
+                if (surf_dot3(qx, qy, qz, aj) < 0.0f) owner = (uint32_t)jn;
+            }
+        }
+        float e = __builtin_nanf("");
+        int cell = -1;      // the owner's cell j * n_sectors + k (< 2^24)
+        int lidx = -1;      // the same cell in the block's LDS table, -1 outside the owner's window
+        uint32_t kcls = kChainPlane;
+#pragma unroll 1
+        for (uint32_t s = 0; s < nside; ++s) {   // s is wave-uniform: the side's block is read once per wave
+            if (!in || owner != s) continue;
+            const WallJointSide &S = a.side[s];
+            JointChainArgs w;
+            for (int k = 0; k < 3; ++k) { w.o[k] = S.o[k]; w.a[k] = S.a[k]; w.u[k] = S.u[k]; w.v[k] = S.v[k]; }
+            w.R = a.R; w.station_length = a.station_length; w.gate = a.gate; w.sector_angle = a.sector_angle; w.two_pi = a.two_pi;
+            w.n_sectors = nsec; w.n_stations = S.n_stations; w.anchor = S.anchor;
+            int64_t j = -1;
+            float jl = 0.0f;
+            uint32_t kk = 0u;
+            auto in_range = [&](float x) { return (j = wall_station(w, x)) >= 0; };
+            auto count = [&](uint32_t k) { kcls = k; };
+            bool mapped;
+            if (S.axis == kAxisClothoid) mapped = wall_chain(q, lab, w, WallClothoidArg{S.ax}, in_range, count, e, jl, kk);
+            else if (S.axis == kAxisArc) mapped = wall_chain(q, lab, w, WallArcArg<true>{S.ax.arc}, in_range, count, e, jl, kk);
+            else mapped = wall_chain(q, lab, w, WallArcArg<false>(), in_range, count, e, jl, kk);
+            if (mapped) {
+                cell = (int)((uint32_t)j * nsec + kk);
+                const float win_lo = (float)S.win_first, win_hi = (float)(S.win_first + (int32_t)S.win_stations);
+                if (jl >= win_lo && jl < win_hi) lidx = (int)(S.lds_first + (uint32_t)((int32_t)jl - S.win_first) * nsec + kk);
+            }
+            if (a.element) a.element[i] = S.element;
+        }
+        if (in && a.res) a.res[i] = e;
+        if (in && a.cell) a.cell[i] = cell;
+        const uint32_t cidx = in ? owner * 4u + (kChainMapped - kcls) : 0xFFFFFFFFu;
+        for (uint32_t c = 0; c < 4u * nside; ++c) {   // (wave-uniform)
+            const uint32_t v = (uint32_t)__popcll(__ballot(cidx == c));
+            if ((uint32_t)lane == c) mine += v;
+        }
+        uint32_t cn = 0u, lo = 0u, hi = 0u;
+        unsigned long long sm = 0ull;
+        if (cell >= 0) {
+            cn = 1u;
+            sm = (unsigned long long)(long long)__float2int_rn(__fmul_rn(e, kWallFix));
+            hi = float_to_ordered(e);
+            lo = ~hi;
+        }
+        const int key = cell >= 0 ? (int)(owner << 24 | (uint32_t)cell) : -1;
+        if (surf_merge_runs(key, cn, sm, lo, hi)) {   // (lanes of one run share side and cell, hence lidx)
+            if (lidx >= 0) {
+                atomicAdd(&s_cnt[lidx], cn);
+                atomicAdd(&s_sum[lidx], sm);
+                atomicMax(&s_lo[lidx], lo);
+                atomicMax(&s_hi[lidx], hi);
+            } else {
+#pragma unroll 1
+                for (uint32_t s = 0; s < nside; ++s)
+                    if (owner == s) wall_global_add(a.side[s].table, (uint64_t)cell, cn, sm, lo, hi);
+            }
+        }
+    };
+    stream_points<kWallThreads, kWallUnroll>(a.pts, a.labels, n, point);
+    __syncthreads();
+    // one flush per side: the touched cells of its window, lane <-> cell.  A window lies inside its map.
+#pragma unroll 1
+    for (uint32_t s = 0; s < nside; ++s) {
+        const WallJointSide &S = a.side[s];
+        const uint32_t wc = S.win_stations * nsec;
+        const int64_t base = (S.anchor + (int64_t)S.win_first) * (int64_t)nsec;
+        for (uint32_t c = threadIdx.x; c < wc; c += kWallThreads) {
+            const uint32_t l = S.lds_first + c;
+            const uint32_t cn = s_cnt[l];
+            if (!cn) continue;
+            wall_global_add(S.table, (uint64_t)(base + (int64_t)c), cn, s_sum[l], s_lo[l], s_hi[l]);
+        }
+    }
+    // class counts: one atomic per (side, class) and block, to the owner's totals
+    if (lane < kJointCls) s_cls[lane][threadIdx.x / kWave] = mine;
+    block_row_sums(s_cls, [&](uint32_t k, unsigned long long v) {
+#pragma unroll 1
+        for (uint32_t s = 0; s < nside; ++s)
+            if (v && (k >> 2) == s) atomicAdd(&a.side[s].table.totals[k & 3u], v);
+    });
+}
+
+void launch_wall_add_joint(const WallJointArgs &a, uint32_t n_cap, uint32_t points_per_block, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_wall_add_joint, dim3(wall_blocks(n_cap, points_per_block)), dim3(kWallThreads), 0, s, a);
+}
+
+}  // namespace gm

@@ -12,7 +12,7 @@ void Processor::check(gm_status s, const char *what)
 }
 
 Processor::Processor(double b, double leaf, double r, double wf, int device, unsigned flags)
-    : ctx_(0), grp_(0), cur_(0), cur_slot_(0), n_slots_(1), next_slot_(0), pending_(0), wall_(0), newest_slot_(-1), check_slot_(-1)
+    : ctx_(0), grp_(0), cur_(0), cur_slot_(0), n_slots_(1), next_slot_(0), pending_(0), wall_(0), alignment_(0), newest_slot_(-1), check_slot_(-1)
 {
     gm_config cfg;
     gm_default_config(&cfg);
@@ -26,7 +26,7 @@ Processor::Processor(double b, double leaf, double r, double wf, int device, uns
 
 Processor::Processor(double b, double leaf, double r, double wf, const std::vector<int> &devices, unsigned flags,
                      unsigned slots_per_device)
-    : ctx_(0), grp_(0), cur_(0), cur_slot_(0), n_slots_(slots_per_device ? slots_per_device : 1), next_slot_(0), pending_(0), wall_(0),
+    : ctx_(0), grp_(0), cur_(0), cur_slot_(0), n_slots_(slots_per_device ? slots_per_device : 1), next_slot_(0), pending_(0), wall_(0), alignment_(0),
       newest_slot_(-1), check_slot_(-1)
 {
     if (devices.empty()) throw Error(GM_ERR_INVALID_ARG, "Processor: empty device list");
@@ -381,6 +381,25 @@ void Processor::createWallMap(const gm_wall_params &params, const gm_wall_arc *a
     if (wall_) gm_wall_map_destroy(wall_);
     wall_ = m;
     check_slot_ = -1;
+}
+
+void Processor::createWallAlignment(const gm_wall_params &params, const std::vector<gm_wall_element> &elements)
+{
+    if (grp_) throw Error(GM_ERR_UNSUPPORTED, "createWallAlignment: a wall alignment belongs to one context (single-device Processor)");
+    gm_wall_alignment *al = 0;
+    check(gm_wall_alignment_create(ctx_, &params, elements.empty() ? 0 : &elements[0], (uint32_t)elements.size(), &al),
+          "createWallAlignment");
+    if (alignment_) gm_wall_alignment_destroy(alignment_);
+    alignment_ = al;
+}
+
+gm_wall_alignment_add_info Processor::addToWallAlignment(const double pose[12])
+{
+    if (!alignment_) throw Error(GM_ERR_NOT_READY, "addToWallAlignment: createWallAlignment first");
+    if (newest_slot_ < 0) throw Error(GM_ERR_NOT_READY, "addToWallAlignment: no frame yet");
+    gm_wall_alignment_add_info info;
+    check(gm_wall_alignment_add_frame(alignment_, ctx_, (unsigned)newest_slot_, pose, &info), "addToWallAlignment");
+    return info;
 }
 
 gm_wall_add_info Processor::addToWallMap(const double pose[12])

@@ -224,6 +224,15 @@ public:
     // repeated with other parameters.  info, when given, receives the call's counts.
     std::vector<gm_wall_object> wallCheckObjects(const gm_wall_object_params &prm, gm_wall_objects_info *info = nullptr);
     gm_wall_map *wallMap() { return wall_; }
+    // Wall alignment (gm_wall_alignment_*, include/gm_hip.h): one wall map per element -- straight, arc, clothoid -- chained
+    // end to end from the template `params` (element 0's frame and the grid of every element), owned by the processor's
+    // context (single device).  createWallAlignment replaces the alignment of an earlier call.
+    void createWallAlignment(const gm_wall_params &params, const std::vector<gm_wall_element> &elements);
+    // adds the newest frame (as addToWallMap takes it) to the element maps within its reach in one launch
+    // (gm_wall_alignment_add_frame): every point goes to the one element that owns it.  The products run per element map,
+    // gm_wall_alignment_map(wallAlignment(), i, &map), over the pieces of gm_wall_alignment_window.
+    gm_wall_alignment_add_info addToWallAlignment(const double pose[12]);
+    gm_wall_alignment *wallAlignment() { return alignment_; }
 
     gm_ctx *ctx() { return ctx_; }
 
@@ -236,6 +245,7 @@ private:
     unsigned n_slots_, next_slot_, pending_;   // single device: ring of slots
     gm_frame_result last_;                     // of the frame the accessors refer to
     gm_wall_map *wall_;                        // createWallMap (freed with the context)
+    gm_wall_alignment *alignment_;             // createWallAlignment (freed with the context)
     int newest_slot_;                          // slot of the frame submitted last (-1: none yet)
     int check_slot_;                           // the slot of the last checkWallMap, -1 before it
     struct CloudBuf { gm_ctx *ctx; unsigned slot; float *rows; unsigned cap; };

@@ -1964,6 +1964,164 @@ gm_status gm_wall_clothoid_project(const gm_wall_params *params, const gm_wall_c
 gm_status gm_wall_clothoid_point(const gm_wall_params *params, const gm_wall_clothoid *clothoid, double chainage, double angle,
                                  double rho, double xyz[3]);
 
+/* ---- a wall alignment: one wall map per element, chained end to end (gm_wall_alignment_create) --------------------------
+ * An alignment is a sequence of up to GM_WALL_ALIGNMENT_MAX_ELEMENTS elements, straight, circular arc or clothoid, each an
+ * ordinary wall map of the rules above on one grid (n_sectors, station_length, gate, radius).  The alignment derives every
+ * element's map from the end of the one before it, decides per frame which element maps the frame goes to, and adds a frame
+ * that straddles joints in ONE launch in which every point is owned by exactly one element.  One operation per statement;
+ * fp64 on the host, not rounded, unless a rounding is named.
+ *   template      One gm_wall_params describes element 0: the design frame and the chainage t_min at its start, and
+ *                 n_sectors, station_length, gate and radius of every element.  Its n_stations is not read (it may be 0).
+ *   chaining      host, fp64.  s_start_0 = t_min;  L_i = n_stations_i ds;  s_end_i = s_start_i + L_i;  s_start_(i+1) = s_end_i.
+ *                 Element 0 takes the template with its own n_stations.  Element i + 1 takes point = P(s_end_i),
+ *                 direction = forward = a(s_end_i) and up = u(s_end_i) of element i: gm_wall_arc_frame's or
+ *                 gm_wall_clothoid_frame's (o, a, u) at s_end_i, copied;  on a straight element P = o + (t_min_i + L_i) a
+ *                 per component, a and u its design frame's.  With (a, u, v) the design frame of the derived params and
+ *                 t = turn / |turn|,  m = t_0 u + t_1 v (per component):
+ *                   arc       gm_wall_arc.curvature = curvature m,  point_chainage = t_min = s_start
+ *                   clothoid  gm_wall_clothoid.normal = m,  curvature, rate the element's,  point_chainage = t_min = s_start
+ *                   straight  t_min = point.a, the chainage the straight rule gives `point` (that rule measures chainage
+ *                             from the foot of the map's origin on the axis and has no point_chainage), and the alignment
+ *                             keeps the element's offset = s_start - t_min:  alignment chainage = map chainage + offset.
+ *                             Element 0 takes the template's t_min as it is (offset 0): its start is o + t_min a.
+ *                 The pair (u, v) turns rigidly with the section, so a horizontal left curve is the same `turn` on every
+ *                 element and the sector angle is continuous across the joints.  Each element must pass gm_wall_map_create's,
+ *                 _create_arc's or _create_clothoid's refusals with its derived structs.
+ *   refusals      GM_ERR_INVALID_ARG: NULL; n = 0 or n > GM_WALL_ALIGNMENT_MAX_ELEMENTS; the template refused by
+ *                 gm_wall_map_create with n_stations set to 1; an element's struct_size or reserved wrong, kind unknown,
+ *                 n_stations = 0; on an arc or a clothoid a turn that is not finite or 0; a derived element refused.
+ *   joint i       between elements i and i + 1: the plane through J_i = point of element i + 1 with the normal
+ *                 aJ_i = that element's design a.  d_i(x) = (x - J_i).aJ_i.
+ *   owner of x    an element looks at its OWN two joints only: element i is a candidate when d_(i-1)(x) >= 0 (none for the
+ *                 first element) and d_i(x) < 0 (none for the last).  There is always one: the element before the first
+ *                 joint, ascending, with d_i(x) < 0, or the last element -- and on an alignment that nowhere turns a
+ *                 quarter turn away from a joint's normal it is the only one.  Where the alignment turns further, x may
+ *                 lie between the joints of a distant element too: of several candidates the owner is the one whose
+ *                 axis, cut to its span, is nearest to x: with (s, e) the candidate's own project of x,
+ *                 over = max(s_start - s, s - s_end, 0);  dist = sqrt((e + R)^2 + over^2);  the smallest dist, ties to the
+ *                 lowest index.  (The add below decides among its sides alone, by the joints between them.)
+ *   project       owner by the rule above in fp64, then the owner's gm_wall_arc_project / gm_wall_clothoid_project; on a
+ *                 straight element r = x - o;  t = r.a;  w = r - t a;  e = |w| - R;  phi = atan2(w.v, w.u) folded to
+ *                 [0, 2 pi);  chainage = t + offset.
+ *   point         the element with s_start <= chainage < s_end (the first before, the last from the end on), then its
+ *                 gm_wall_arc_point / gm_wall_clothoid_point; on a straight element
+ *                 x = (o + (chainage - offset) a) + rho (cos phi u + sin phi v) per component.
+ *   window        [s_from, s_to], cut to the alignment: per element that it meets in more than a point,
+ *                 station0 = floor((max(s_from, s_start) - s_start) / ds),  last = ceil((min(s_to, s_end) - s_start) / ds)
+ *                 cut to n_stations,  n_stations = last - station0: whole stations that cover the interval, in order.
+ *   per add       host.  The pose check of the straight rule.  (element, s) = project of tr.  Reach
+ *                 L = 2 sqrt(3) boxFilterBound + ds, the bound of the clothoid window above.  The sides are the elements
+ *                 with s_start < s + L and s_end > s - L, and the sensor's element: consecutive elements.  More than
+ *                 GM_WALL_JOINT_MAX_SIDES of them: GM_ERR_UNSUPPORTED, nothing is enqueued.  One side: the add IS that
+ *                 element map's add, the same launch.  Two or more: each side gets exactly the per-add frame its own map's
+ *                 add computes for this pose (its anchor may lie before station 0 or past the end), and for each joint
+ *                 between consecutive sides Jo' = Rm^T (J - tr) and aJ' = Rm^T aJ, each rounded to fp32 once.
+ *   per point     device, fp32, every operation rounded to nearest.  For the joints of the sides, ascending:  q = p - Jo'_i;
+ *                 d_i = fma(qx, ax, fma(qy, ay, qz az)).  The owner is the side before the first joint with d_i < 0, the
+ *                 last side if there is none (a NaN is not < 0).  The point runs its owner's chain and no other, and is
+ *                 classed and binned as an add of it alone to the owner's map under the same pose would: a point that the
+ *                 owner's chain places past the owner's end is `outside` in the owner's totals, nothing is clamped.
+ * So an alignment add changes every element map exactly as gm_wall_map_add_points of the sub-cloud that element owns would,
+ * and every point is classed exactly once.  The LDS table's GM_SURF_MAX_CELLS cells are dealt to the sides in order (a
+ * side's window: the stations of its own add's window that lie in the element, cut to what is left); a mapped point outside
+ * its side's window goes to the map directly, which affects speed only.
+ * Out of scope: the checked add, and check, locate and align through the alignment (they remain calls on an element map,
+ * gm_wall_alignment_map); element maps of different grids; closed loops. */
+#define GM_WALL_ALIGNMENT_MAX_ELEMENTS 256
+#define GM_WALL_JOINT_MAX_SIDES 4
+enum { GM_WALL_ELEMENT_STRAIGHT = 0, GM_WALL_ELEMENT_ARC = 1, GM_WALL_ELEMENT_CLOTHOID = 2 };
+typedef struct gm_wall_element {   /* 48 bytes */
+    uint32_t struct_size;      /* = sizeof(gm_wall_element) */
+    uint32_t kind;             /* GM_WALL_ELEMENT_* */
+    uint32_t n_stations;       /* >= 1 */
+    uint32_t reserved;         /* 0 */
+    double   turn[2];          /* arc, clothoid: the side positive curvature turns toward, in the (u, v) basis of the element's
+                                  START section; non-zero, normalised by the library; not read on a straight */
+    double   curvature;        /* arc: > 0; clothoid: signed, at the element's start; straight: not read */
+    double   rate;             /* clothoid only */
+} gm_wall_element;
+
+typedef struct gm_wall_alignment gm_wall_alignment;   /* opaque; owned by the context it was created from */
+
+typedef struct gm_wall_alignment_piece {   /* 16 bytes */
+    uint32_t element, station0, n_stations;
+    uint32_t reserved;         /* 0 */
+} gm_wall_alignment_piece;
+
+typedef struct gm_wall_alignment_add_info {   /* 160 bytes; filled on the host by every add, before the kernel has run */
+    uint32_t struct_size;      /* = sizeof(gm_wall_alignment_add_info), filled by the library */
+    uint32_t status;           /* GM_SURF_OK or GM_SURF_UP_FALLBACK: the OR of the sides' design frames' */
+    uint32_t element;          /* the sensor's element */
+    uint32_t n_sides;          /* 1 .. GM_WALL_JOINT_MAX_SIDES */
+    double   chainage;         /* the sensor's chainage s */
+    double   reach;            /* L */
+    uint32_t side_element[GM_WALL_JOINT_MAX_SIDES];   /* ascending, consecutive; entries from n_sides on are 0 */
+    int64_t  side_anchor[GM_WALL_JOINT_MAX_SIDES];    /* j_f of each side's own add */
+    float    joint_o[GM_WALL_JOINT_MAX_SIDES - 1][3]; /* Jo' of the joint behind side i, as the kernel receives it */
+    float    joint_a[GM_WALL_JOINT_MAX_SIDES - 1][3]; /* aJ' */
+    double   offset;           /* the sensor element's chainage offset (0 unless a straight element behind the first) */
+} gm_wall_alignment_add_info;
+
+typedef struct gm_wall_alignment_totals {   /* 72 bytes; cumulative, read after a synchronisation */
+    uint32_t struct_size;      /* = sizeof(gm_wall_alignment_totals), filled by the library */
+    uint32_t n_elements;
+    uint64_t n_stations;       /* summed over the elements */
+    double   chainage_min, chainage_max;   /* s_start of the first element, s_end of the last */
+    uint64_t frames;           /* the element maps' frames, summed: an add counts once per side */
+    uint64_t mapped, outside, beyond_gate, plane;   /* the element maps' class totals, summed */
+} gm_wall_alignment_totals;
+
+/* Host only, no context.  GM_ERR_INVALID_ARG: NULL, the refusals above, an input that is not finite, a refused pose;
+ * GM_ERR_OOM: no memory for the elements or a clothoid's table.  Each of the six calls chains the alignment anew -- every
+ * element's frame, and each clothoid element's table of station starts (n_stations panels) -- so a call costs about a
+ * microsecond per element plus a few per hundred clothoid stations, per point for project and point: fine for a pose, a
+ * window or a synthetic frame, not for a cloud per frame. */
+gm_status gm_wall_alignment_check(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n);
+/* The derived structs of element i, what gm_wall_map_create / _create_arc / _create_clothoid take to create a bitwise-equal
+ * map: *out always; *arc on an arc element, zeroed otherwise; *clothoid on a clothoid element, zeroed otherwise (either may
+ * be NULL).  The element's s_start is the template's t_min plus the lengths before it. */
+gm_status gm_wall_alignment_element_params(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n, uint32_t i,
+                                           gm_wall_params *out, gm_wall_arc *arc, gm_wall_clothoid *clothoid);
+/* A map point's owner, alignment chainage, angle phi in [0, 2 pi) and residual e (the project rule above). */
+gm_status gm_wall_alignment_project(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n, const double xyz[3],
+                                    uint32_t *element, double *chainage, double *angle, double *e);
+/* The map point at (chainage, angle, rho = R + e) (the point rule above). */
+gm_status gm_wall_alignment_point(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n, double chainage,
+                                  double angle, double rho, double xyz[3]);
+/* The plan of an add under `pose` on a context whose boxFilterBound is `bound` (> 0, finite): the sensor's element and
+ * chainage, the sides and the fp32 joint planes exactly as the kernel receives them.  GM_ERR_UNSUPPORTED: more than
+ * GM_WALL_JOINT_MAX_SIDES sides (info is filled but for the sides and the joints). */
+gm_status gm_wall_alignment_add_plan(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n,
+                                     const double pose[12], double bound, gm_wall_alignment_add_info *info);
+/* The pieces of [s_from, s_to] (finite, s_from <= s_to), the window rule above; *n_out: their number.  GM_ERR_CAPACITY: more
+ * than `capacity` (pieces may be NULL with capacity 0).  A product over a chainage interval runs once per piece on
+ * gm_wall_alignment_map(al, piece.element) with (piece.station0, piece.n_stations). */
+gm_status gm_wall_alignment_window(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n, double s_from,
+                                   double s_to, gm_wall_alignment_piece *pieces, uint32_t capacity, uint32_t *n_out);
+
+/* The alignment and its n element maps on ctx's device.  GM_ERR_INVALID_ARG: NULL, the refusals above; GM_ERR_OOM;
+ * GM_ERR_DEVICE.  It belongs to the context and is freed with it. */
+gm_status gm_wall_alignment_create(gm_ctx *ctx, const gm_wall_params *params, const gm_wall_element *elements, uint32_t n,
+                                   gm_wall_alignment **alignment);
+/* Waits for the adds and frees the alignment and its element maps.  NULL is ignored. */
+void gm_wall_alignment_destroy(gm_wall_alignment *alignment);
+/* Element i's ordinary gm_wall_map, owned by the alignment (it must not be destroyed by the caller): every window call and
+ * every per-slot call works on it, ordered against the alignment's adds as against its own. */
+gm_status gm_wall_alignment_map(gm_wall_alignment *alignment, uint32_t i, gm_wall_map **map);
+/* gm_wall_map_add_frame on the alignment: enqueued on the slot's stream behind the frame's work; for every side's map it
+ * does what an add does (it waits for readers on other slots and marks the slot pending).  info may be NULL. */
+gm_status gm_wall_alignment_add_frame(gm_wall_alignment *alignment, gm_ctx *ctx, uint32_t slot, const double pose[12],
+                                      gm_wall_alignment_add_info *info);
+/* gm_wall_map_add_points on the alignment.  residual, cell, element may be NULL; cell is relative to the owner's map and
+ * element (int32_t[n]) is the owner's element index, set for every point. */
+gm_status gm_wall_alignment_add_points(gm_wall_alignment *alignment, const float *xyz, uint32_t n, const uint8_t *labels,
+                                       const double pose[12], gm_wall_alignment_add_info *info, float *residual, int32_t *cell,
+                                       int32_t *element);
+/* gm_wall_map_sync on every element map. */
+gm_status gm_wall_alignment_sync(gm_wall_alignment *alignment);
+/* Synchronises, then the sums above. */
+gm_status gm_wall_alignment_info(gm_wall_alignment *alignment, gm_wall_alignment_totals *info);
+
 /* "Compressed map" record of a completed slot.  The reference defines no such
  * output; this is a build-defined format: header, primitive records,
  * then n_voxels rows of x,y,z,count (float32).  Returns the bytes needed in
