@@ -429,6 +429,25 @@ class WallLocateInfo(C.Structure):
                 ("pass_", WallLocatePass * 3)]
 
 
+class WallAlignmentLocatePass(C.Structure):
+    _fields_ = WallLocatePass._fields_ + [("side", (C.c_float * 12) * 4), ("joint_o", (C.c_float * 3) * 3),
+                                          ("joint_a", (C.c_float * 3) * 3)]
+
+
+class WallAlignmentLocateInfo(C.Structure):
+    _fields_ = WallLocateInfo._fields_[:-1] + [
+        ("element", C.c_uint32), ("n_sides", C.c_uint32), ("side_element", C.c_uint32 * 4), ("side_kind", C.c_uint32 * 4),
+        ("side_anchor", C.c_int64 * 4), ("side_axis", (C.c_float * 6) * 4), ("pass_", WallAlignmentLocatePass * 3)]
+
+
+class WallAlignmentLocateStart(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("home", C.c_uint32), ("add", WallAlignmentAddInfo),
+                ("c", C.c_double * 3), ("d", C.c_double * 3), ("u", C.c_double * 3), ("v", C.c_double * 3), ("s0", C.c_double),
+                ("o_f", C.c_double * 3), ("a", C.c_double * 3), ("fu", C.c_double * 3), ("fv", C.c_double * 3),
+                ("side", (C.c_double * 12) * 4), ("joint", (C.c_double * 6) * 3), ("side_axis", (C.c_float * 6) * 4),
+                ("side_kind", C.c_uint32 * 4)]
+
+
 class WallAlignParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("half_patch_stations", C.c_uint32), ("max_station_shift", C.c_uint32),
                 ("max_sector_shift", C.c_uint32), ("min_count", C.c_uint32), ("min_frame_count", C.c_uint32),
@@ -637,6 +656,10 @@ def load():
         "gm_wall_alignment_add_frame": (C.c_int, [vp, vp, u32, dp, waladdp]),
         "gm_wall_alignment_add_points": (C.c_int, [vp, fp, u32, u8p, dp, waladdp, fp, i32p, i32p]),
         "gm_wall_alignment_sync": (C.c_int, [vp]),
+        "gm_wall_alignment_locate_plan": (C.c_int, [wprmp, welp, u32, dp, C.c_double, C.POINTER(WallAlignmentLocateStart)]),
+        "gm_wall_alignment_locate_frame": (C.c_int, [vp, vp, u32, dp, wlprmp]),
+        "gm_wall_alignment_get_locate": (C.c_int, [vp, u32, C.POINTER(WallAlignmentLocateInfo)]),
+        "gm_wall_alignment_locate_points": (C.c_int, [vp, fp, u32, u8p, dp, wlprmp, C.POINTER(WallAlignmentLocateInfo), fp, i32p, i32p]),
         "gm_wall_alignment_info": (C.c_int, [vp, waltotp]),
         "gm_wall_map_add_frame": (C.c_int, [vp, vp, u32, dp, waddp]),
         "gm_wall_map_add_points": (C.c_int, [vp, fp, u32, u8p, dp, waddp, fp, i32p]),

@@ -1886,6 +1886,25 @@ class WallAlignmentRule:
             raise _lib.GmError(st, "gm_wall_alignment_add_plan refused the arguments")
         return _alignment_add_info(i)
 
+    def locate_plan(self, pose, bound):
+        """gm_wall_alignment_locate_plan: what a locate under `pose` starts from -- home (index among the sides), add (the
+        add's plan dict), the state c, d, u, v and s0, the home section o_f, a, fu, fv in map coordinates, side [n_sides, 4, 3]
+        and joint [n_sides - 1, 2, 3] (the attached vectors in the home section), side_axis [n_sides, 6] float32 (kappa_f,
+        rate, un, ub, vn, vb) and side_kind."""
+        m = WallMap._pose(pose)
+        s = _lib.WallAlignmentLocateStart()
+        st = self._L.gm_wall_alignment_locate_plan(*self._head(), _dptr(m), float(bound), C.byref(s))
+        if st != _lib.GM_OK:
+            raise _lib.GmError(st, "gm_wall_alignment_locate_plan refused the arguments")
+        ns = int(s.add.n_sides)
+        d = {k: np.array(getattr(s, k)[:], dtype=np.float64) for k in ("c", "d", "u", "v", "o_f", "a", "fu", "fv")}
+        d.update(home=int(s.home), add=_alignment_add_info(s.add), s0=float(s.s0),
+                 side=np.array([list(r) for r in s.side], dtype=np.float64)[:ns].reshape(ns, 4, 3),
+                 joint=np.array([list(r) for r in s.joint], dtype=np.float64)[:max(ns - 1, 0)].reshape(max(ns - 1, 0), 2, 3),
+                 side_axis=np.array([list(r) for r in s.side_axis], dtype=np.float32)[:ns],
+                 side_kind=[int(x) for x in s.side_kind[:ns]])
+        return d
+
 
 class WallAlignment(WallAlignmentRule):
     """One gm_wall_alignment: the element maps of an alignment of straights, arcs and clothoids, chained end to end, and
@@ -1968,6 +1987,59 @@ class WallAlignment(WallAlignmentRule):
 
     def add_plan(self, pose, bound=None):
         return super().add_plan(pose, float(self._ctx.cfg.boxFilterBound) if bound is None else bound)
+
+    def locate_plan(self, pose, bound=None):
+        return super().locate_plan(pose, float(self._ctx.cfg.boxFilterBound) if bound is None else bound)
+
+    @staticmethod
+    def _locate_info(i):
+        """The dict of a gm_wall_alignment_locate_info: WallMap.locate_result()'s keys, element, n_sides, side_element,
+        side_kind, side_anchor, side_axis [n_sides, 6] float32, and in every pass side [n_sides, 4, 3] and joint_o, joint_a
+        [n_sides - 1, 3] float32: the blocks the pass's points saw."""
+        d = WallMap._locate_info(i)
+        ns = int(i.n_sides)
+        d.update(element=int(i.element), n_sides=ns, side_element=[int(x) for x in i.side_element[:ns]],
+                 side_kind=[int(x) for x in i.side_kind[:ns]], side_anchor=[int(x) for x in i.side_anchor[:ns]],
+                 side_axis=np.array([list(r) for r in i.side_axis], dtype=np.float32)[:ns])
+        for q, r in zip(d["pass"], i.pass_):
+            q["side"] = np.array([list(x) for x in r.side], dtype=np.float32)[:ns].reshape(ns, 4, 3)
+            q["joint_o"] = np.array([list(x) for x in r.joint_o], dtype=np.float32)[:max(ns - 1, 0)]
+            q["joint_a"] = np.array([list(x) for x in r.joint_a], dtype=np.float32)[:max(ns - 1, 0)]
+        return d
+
+    def locate_frame(self, slot=0, pose=np.eye(4)[:3], **params):
+        """gm_wall_alignment_locate_frame: enqueue the correction of `pose` for the slot's last submitted frame against the
+        alignment (keywords: reference, min_count, gate).  Returns at once; locate_result() fetches the result."""
+        m = WallMap._pose(pose)
+        p = WallMap.locate_params(**params)
+        self._ctx._check(self._L.gm_wall_alignment_locate_frame(self._h(), self._ctx._ctx, slot, _dptr(m), C.byref(p)))
+
+    def locate_result(self, slot=0):
+        """gm_wall_alignment_get_locate: the info dict (_locate_info) of the last locate on the slot."""
+        info = _lib.WallAlignmentLocateInfo()
+        self._ctx._check(self._L.gm_wall_alignment_get_locate(self._h(), slot, C.byref(info)))
+        return self._locate_info(info)
+
+    def locate_points(self, cloud, pose=np.eye(4)[:3], labels=None, outputs=True, **params):
+        """gm_wall_alignment_locate_points on a host cloud [n,3]: (info dict, residual [n] float32, cell [n] int32 relative
+        to the owner's map) of the last pass that ran and element [n] int32, the owner under the caller's pose; outputs False
+        skips the per-point arrays."""
+        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+        m = WallMap._pose(pose)
+        lab, lp = GeometricMapping._u8(labels)
+        p = WallMap.locate_params(**params)
+        n = len(xyz)
+        info = _lib.WallAlignmentLocateInfo()
+        res = np.empty(max(n, 1), dtype=np.float32) if outputs else None
+        cell = np.empty(max(n, 1), dtype=np.int32) if outputs else None
+        el = np.empty(max(n, 1), dtype=np.int32) if outputs else None
+        i32 = C.POINTER(C.c_int32)
+        self._ctx._check(self._L.gm_wall_alignment_locate_points(
+            self._h(), _f32(xyz), n, lp, _dptr(m), C.byref(p), C.byref(info), _f32(res) if outputs else None,
+            cell.ctypes.data_as(i32) if outputs else None, el.ctypes.data_as(i32) if outputs else None))
+        if not outputs:
+            return self._locate_info(info), None, None, None
+        return self._locate_info(info), res[:n].copy(), cell[:n].copy(), el[:n].copy()
 
 
 def decode_compressed_map(buf):

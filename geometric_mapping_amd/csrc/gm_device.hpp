@@ -282,8 +282,12 @@ __device__ __forceinline__ float sqrt_rn(float x)
 // instantiations).  (o, a, n, b): the section at the anchor station in sensor coordinates.  Returns e; t: the arc length
 // from the anchor section, (yc, z): the offset in the point's own section along n(s) and b; cy <= 0: a quarter turn or more
 // from the anchor section (the caller classes it beyond_gate).
-__device__ __forceinline__ float arc_residual(const float4 &p, const float (&o)[3], const float (&a)[3], const float (&n)[3],
-                                              const float (&b)[3], float kappa, float R, float &t, float &yc, float &z, float &cy)
+// The chain itself also hands out rho = e + R before the subtraction and (cs, sn) = (cy, cx) / d, the cosine and sine of
+// the turn psi from the anchor section to the point's own (the alignment's locate builds the radial direction from them);
+// arc_residual is the chain for the callers that bin.
+__device__ __forceinline__ float arc_chain(const float4 &p, const float (&o)[3], const float (&a)[3], const float (&n)[3],
+                                           const float (&b)[3], float kappa, float R, float &t, float &yc, float &z, float &cy,
+                                           float &rho, float &cs, float &sn)
 {
     const float qx = __fsub_rn(p.x, o[0]), qy = __fsub_rn(p.y, o[1]), qz = __fsub_rn(p.z, o[2]);
     const float x = surf_dot3(qx, qy, qz, a), y = surf_dot3(qx, qy, qz, n);
@@ -294,7 +298,16 @@ __device__ __forceinline__ float arc_residual(const float4 &p, const float (&o)[
     t = __fdiv_rn(atan2f(cx, cy), kappa);
     const float h = __fmaf_rn(x, x, __fmul_rn(y, y));
     yc = __fdiv_rn(__fmaf_rn(-kappa, h, __fadd_rn(y, y)), __fadd_rn(1.0f, d));
-    return __fsub_rn(sqrt_rn(__fmaf_rn(yc, yc, __fmul_rn(z, z))), R);
+    cs = __fdiv_rn(cy, d);
+    sn = __fdiv_rn(cx, d);
+    rho = sqrt_rn(__fmaf_rn(yc, yc, __fmul_rn(z, z)));
+    return __fsub_rn(rho, R);
+}
+__device__ __forceinline__ float arc_residual(const float4 &p, const float (&o)[3], const float (&a)[3], const float (&n)[3],
+                                              const float (&b)[3], float kappa, float R, float &t, float &yc, float &z, float &cy)
+{
+    float rho, cs, sn;
+    return arc_chain(p, o, a, n, b, kappa, R, t, yc, z, cy, rho, cs, sn);
 }
 // surf_sector on (yc, z): phi = atan2(yc vn + z vb, yc un + z ub)
 __device__ __forceinline__ uint32_t arc_sector(float yc, float z, float un, float ub, float vn, float vb, float two_pi,
@@ -375,7 +388,8 @@ __device__ __forceinline__ void clothoid_node(float kappa, float hr, float t, fl
     sy = kFirst ? __fmul_rn(w, sn) : __fmaf_rn(sn, w, sy);
 }
 // E(t) of the header: g and yc of the trial t
-__device__ __forceinline__ void clothoid_eval(float x, float y, float kappa, float hr, float t, float &g, float &yc)
+// (sn, cs): the sine and cosine of ps = psi(t), the turn from the anchor section to the section at t
+__device__ __forceinline__ void clothoid_eval(float x, float y, float kappa, float hr, float t, float &g, float &yc, float &sn, float &cs)
 {
     float sx, sy;
     clothoid_node<true>(kappa, hr, t, 0.06943184420297371f, 0.17392742256872692f, sx, sy);
@@ -384,14 +398,15 @@ __device__ __forceinline__ void clothoid_eval(float x, float y, float kappa, flo
     clothoid_node<false>(kappa, hr, t, 0.9305681557970262f, 0.17392742256872692f, sx, sy);
     const float dx = __fsub_rn(x, __fmul_rn(t, sx)), dy = __fsub_rn(y, __fmul_rn(t, sy));
     const float ps = __fmul_rn(__fmaf_rn(hr, t, kappa), t);
-    float sn, cs;
     clothoid_sincos(ps, sn, cs);
     g = __fmaf_rn(dx, cs, __fmul_rn(dy, sn));
     yc = __fmaf_rn(dy, cs, -__fmul_rn(dx, sn));
 }
-__device__ __forceinline__ float clothoid_residual(const float4 &p, const float (&o)[3], const float (&a)[3], const float (&n)[3],
-                                                   const float (&b)[3], float kappa, float rate, float R, float &t, float &yc,
-                                                   float &z, float &ok)
+// The chain; as arc_chain it also hands out rho and the (cs, sn) of the closing evaluation.  clothoid_residual is the chain
+// for the callers that bin.
+__device__ __forceinline__ float clothoid_chain(const float4 &p, const float (&o)[3], const float (&a)[3], const float (&n)[3],
+                                                const float (&b)[3], float kappa, float rate, float R, float &t, float &yc,
+                                                float &z, float &ok, float &rho, float &cs, float &sn)
 {
     const float qx = __fsub_rn(p.x, o[0]), qy = __fsub_rn(p.y, o[1]), qz = __fsub_rn(p.z, o[2]);
     const float x = surf_dot3(qx, qy, qz, a), y = surf_dot3(qx, qy, qz, n);
@@ -403,15 +418,23 @@ __device__ __forceinline__ float clothoid_residual(const float4 &p, const float 
     float g;
 #pragma unroll
     for (int it = 0; it < GM_WALL_CLOTHOID_STEPS; ++it) {
-        clothoid_eval(x, y, kappa, hr, t, g, yc);
+        clothoid_eval(x, y, kappa, hr, t, g, yc, sn, cs);
         const float den = __fmaf_rn(-__fmaf_rn(t, rate, kappa), yc, 1.0f);
         good = good && den > 0.25f;
         t = __fadd_rn(t, __fdiv_rn(g, den));
     }
-    clothoid_eval(x, y, kappa, hr, t, g, yc);
+    clothoid_eval(x, y, kappa, hr, t, g, yc, sn, cs);
     good = good && fabsf(t) < __builtin_inff() && fabsf(g) <= GM_WALL_CLOTHOID_G_BOUND;
     ok = good ? 1.0f : 0.0f;
-    return __fsub_rn(sqrt_rn(__fmaf_rn(yc, yc, __fmul_rn(z, z))), R);
+    rho = sqrt_rn(__fmaf_rn(yc, yc, __fmul_rn(z, z)));
+    return __fsub_rn(rho, R);
+}
+__device__ __forceinline__ float clothoid_residual(const float4 &p, const float (&o)[3], const float (&a)[3], const float (&n)[3],
+                                                   const float (&b)[3], float kappa, float rate, float R, float &t, float &yc,
+                                                   float &z, float &ok)
+{
+    float rho, cs, sn;
+    return clothoid_chain(p, o, a, n, b, kappa, rate, R, t, yc, z, ok, rho, cs, sn);
 }
 
 // ---- the head of the chain against a map (k_wall_add*, the check's predicate, k_wall_align_bin): label, residual, gate,

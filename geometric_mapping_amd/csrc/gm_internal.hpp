@@ -551,6 +551,72 @@ struct WallLocateArgs {
     uint32_t *ticket;          // 0 between launches
 };
 void launch_wall_locate(const WallLocateArgs &a, hipStream_t s);   // the three passes
+// k_wall_locate_joint.hip (gm_wall_alignment_locate_*): k_wall_locate over the sides of an alignment's plan, every point on
+// its owner's chain.  The fp32 blocks of a pass -- every side's four vectors, the joint planes -- are the images of the
+// attached vectors (h: home-section coordinates, fp64) under the pass's state.
+struct WallLocateJointBlocks {
+    float side[GM_WALL_JOINT_MAX_SIDES][12];        // o', a', n', b' (straight: o', a', u', v')
+    float jo[GM_WALL_JOINT_MAX_SIDES - 1][3];       // Jo'
+    float ja[GM_WALL_JOINT_MAX_SIDES - 1][3];       // aJ'
+};
+struct WallLocateJointWork {
+    double c[3], d[3], u[3], v[3];   // the state in sensor coordinates, fp64
+    double lateral[2], tilt[2];
+    double last_step;
+    uint32_t status, passes, n_points, pad;
+    WallLocateJointBlocks next;      // the blocks of the pass to come, written by the solve of the pass before
+    gm_wall_alignment_locate_pass pass[GM_LOCATE_PASSES];
+};
+struct WallLocateJointSide {
+    WallTable table;
+    int64_t anchor;            // j_f of this side's own add
+    uint32_t n_stations;
+    int32_t axis;              // kAxisStraight, kAxisArc, kAxisClothoid
+    int32_t element;
+    float kappa, rate, un, ub, vn, vb;
+};
+struct WallLocateJointArgs {
+    const float4 *pts;
+    const uint8_t *labels;     // nullptr: no point is plane
+    const uint32_t *n_ptr;     // device point count (nullptr: n_host)
+    uint32_t n_host;
+    uint32_t n_sides;          // 1 .. GM_WALL_JOINT_MAX_SIDES
+    uint32_t n_sectors, reference, min_count;
+    float R, station_length, sector_angle, two_pi;
+    double gate;               // of pass 0
+    double c0[3], d0[3], u0[3], v0[3], s0;   // the start, fp64, not rounded
+    WallLocateJointBlocks first;             // the blocks of pass 0
+    double h_side[GM_WALL_JOINT_MAX_SIDES][12];      // the attached vectors: a point's h, then three directions' per side
+    double h_joint[GM_WALL_JOINT_MAX_SIDES - 1][6];  // h of J, h of aJ
+    WallLocateJointSide side[GM_WALL_JOINT_MAX_SIDES];
+    WallLocateJointWork *work;
+    double *partial;           // [kFitBlocks][kFitRowLen]
+    uint32_t *ticket;          // 0 between launches
+    float *res;                // stage call only: all three or none (nullptr in the frame path)
+    int32_t *cell;
+    int32_t *element;
+};
+void launch_wall_locate_joint(const WallLocateJointArgs &a, hipStream_t s);   // the three passes
+// the image of an attached vector h under the state (c, d, u, v): a point or a direction, rounded to fp32 once
+__host__ __device__ inline void wall_locate_image(const double *h, bool point, const double *c, const double *d, const double *u,
+                                                  const double *v, float *out)
+{
+    for (int k = 0; k < 3; ++k) {
+        const double r = (h[0] * d[k] + h[1] * u[k]) + h[2] * v[k];
+        out[k] = (float)(point ? c[k] + r : r);
+    }
+}
+// every block of a pass: the images of a's attached vectors under the state
+__host__ __device__ inline void wall_locate_blocks(const WallLocateJointArgs &a, const double *c, const double *d, const double *u,
+                                                   const double *v, WallLocateJointBlocks &b)
+{
+    for (int s = 0; s < GM_WALL_JOINT_MAX_SIDES; ++s)
+        for (int q = 0; q < 4; ++q) wall_locate_image(&a.h_side[s][3 * q], q == 0, c, d, u, v, &b.side[s][3 * q]);
+    for (int j = 0; j < GM_WALL_JOINT_MAX_SIDES - 1; ++j) {
+        wall_locate_image(&a.h_joint[j][0], true, c, d, u, v, b.jo[j]);
+        wall_locate_image(&a.h_joint[j][3], false, c, d, u, v, b.ja[j]);
+    }
+}
 // k_wall_align.hip (gm_wall_map_align_*): bin -> values -> score
 constexpr int kWallAlignCounters = 8;   // u64: plane, beyond_gate, outside_patch, binned, n_points, patch_cells_usable, pad
 constexpr int32_t kWallAlignNone = -2147483647 - 1;   // the value of an unusable cell in both int32 images

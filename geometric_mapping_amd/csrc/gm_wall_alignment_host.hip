@@ -273,6 +273,84 @@ gm_status alignment_add_plan(const Alignment &A, const double pose[12], double b
     return GM_OK;
 }
 
+// The section of element E at its own add's anchor station in map coordinates, not rounded: S = o, a, n, b on a curved
+// element (o, a, u, v on a straight one), (u, v) = u(s_f), v(s_f), and ax = kappa_f, rate, un, ub, vn, vb as the add rounds them.
+static void element_anchor_section(const AlignElem &E, int64_t anchor, double S[4][3], double u[3], double v[3], float ax[6])
+{
+    const double ds = E.p.station_length;
+    for (int k = 0; k < 6; ++k) ax[k] = 0.0f;
+    if (E.kind == GM_WALL_ELEMENT_STRAIGHT) {
+        const double off = E.p.t_min + (double)anchor * ds;
+        for (int k = 0; k < 3; ++k) {
+            S[0][k] = E.d.o[k] + off * E.d.a[k];
+            S[1][k] = E.d.a[k]; S[2][k] = u[k] = E.d.u[k]; S[3][k] = v[k] = E.d.v[k];
+        }
+        return;
+    }
+    double un, ub, vn, vb;
+    if (E.kind == GM_WALL_ELEMENT_ARC) {
+        arc_section(E.d, E.af, E.p.t_min + (double)anchor * ds, S[1], S[2], S[0]);
+        for (int k = 0; k < 3; ++k) S[3][k] = E.af.b[k];
+        un = E.af.un; ub = E.af.ub; vn = E.af.vn; vb = E.af.vb;
+        ax[0] = (float)E.af.kappa;
+    } else {
+        ax[0] = (float)clothoid_section(E.d, E.cf, E.cf.tau0 + (double)anchor * ds, S[1], S[2], S[0]);
+        for (int k = 0; k < 3; ++k) S[3][k] = E.cf.b[k];
+        un = E.cf.un; ub = E.cf.ub; vn = E.cf.vn; vb = E.cf.vb;
+        ax[1] = (float)E.cf.rate;
+    }
+    ax[2] = (float)un; ax[3] = (float)ub; ax[4] = (float)vn; ax[5] = (float)vb;
+    for (int k = 0; k < 3; ++k) { u[k] = un * S[2][k] + ub * S[3][k]; v[k] = vn * S[2][k] + vb * S[3][k]; }
+}
+
+gm_status alignment_locate_start(const Alignment &A, const double pose[12], double bound, gm_wall_alignment_locate_start *out)
+{
+    if (!out) return GM_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    out->struct_size = (uint32_t)sizeof(gm_wall_alignment_locate_start);
+    GMW_OK(alignment_add_plan(A, pose, bound, &out->add));
+    double Rm[3][3], tr[3];
+    (void)pose_split(pose, Rm, tr);   // (accepted by the plan)
+    const gm_wall_alignment_add_info &pl = out->add;
+    out->home = pl.element - pl.side_element[0];
+    // the home section and the start
+    double H[4][3], hu[3], hv[3];
+    float ax[6];
+    element_anchor_section(A.el[pl.element], pl.side_anchor[out->home], H, hu, hv, ax);
+    const double *of = H[0], *ha = H[1];
+    for (int c = 0; c < 3; ++c) {   // Rm^T x
+        const double r[3] = {of[0] - tr[0], of[1] - tr[1], of[2] - tr[2]};
+        out->c[c] = Rm[0][c] * r[0] + Rm[1][c] * r[1] + Rm[2][c] * r[2];
+        out->d[c] = Rm[0][c] * ha[0] + Rm[1][c] * ha[1] + Rm[2][c] * ha[2];
+        out->u[c] = Rm[0][c] * hu[0] + Rm[1][c] * hu[1] + Rm[2][c] * hu[2];
+        out->v[c] = Rm[0][c] * hv[0] + Rm[1][c] * hv[1] + Rm[2][c] * hv[2];
+        out->o_f[c] = of[c]; out->a[c] = ha[c]; out->fu[c] = hu[c]; out->fv[c] = hv[c];
+    }
+    out->s0 = -dot(out->c, out->d);
+    auto coords = [&](const double *x, bool point, double *h) {
+        const double r[3] = {point ? x[0] - of[0] : x[0], point ? x[1] - of[1] : x[1], point ? x[2] - of[2] : x[2]};
+        h[0] = dot(r, ha); h[1] = dot(r, hu); h[2] = dot(r, hv);
+    };
+    for (uint32_t k = 0; k < pl.n_sides; ++k) {
+        const AlignElem &E = A.el[pl.side_element[k]];
+        double S[4][3], su[3], sv[3];
+        element_anchor_section(E, pl.side_anchor[k], S, su, sv, out->side_axis[k]);
+        out->side_kind[k] = E.kind;
+        for (int q = 0; q < 4; ++q) coords(S[q], q == 0, &out->side[k][3 * q]);
+        if (k == out->home) {   // exactly itself
+            const bool straight = E.kind == GM_WALL_ELEMENT_STRAIGHT;
+            for (int q = 0; q < (straight ? 4 : 2); ++q)
+                for (int c = 0; c < 3; ++c) out->side[k][3 * q + c] = q > 0 && c == q - 1 ? 1.0 : 0.0;
+        }
+        if (k + 1u < pl.n_sides) {
+            const AlignElem &N = A.el[pl.side_element[k] + 1u];
+            coords(N.p.point, true, &out->joint[k][0]);
+            coords(N.d.a, false, &out->joint[k][3]);
+        }
+    }
+    return GM_OK;
+}
+
 gm_status alignment_window(const Alignment &A, double s_from, double s_to, gm_wall_alignment_piece *pieces, uint32_t capacity,
                            uint32_t *n_out)
 {
@@ -349,6 +427,14 @@ gm_status gm_wall_alignment_add_plan(const gm_wall_params *params, const gm_wall
     Alignment A;
     GMW_OK(alignment_build(params, elements, n, A));
     return alignment_add_plan(A, pose, bound, info);
+}
+
+gm_status gm_wall_alignment_locate_plan(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n,
+                                        const double pose[12], double bound, gm_wall_alignment_locate_start *start)
+{
+    Alignment A;
+    GMW_OK(alignment_build(params, elements, n, A));
+    return alignment_locate_start(A, pose, bound, start);
 }
 
 gm_status gm_wall_alignment_window(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n, double s_from,

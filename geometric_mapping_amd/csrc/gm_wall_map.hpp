@@ -102,6 +102,8 @@ void alignment_point(const Alignment &A, double chainage, double angle, double r
 gm_status alignment_add_plan(const Alignment &A, const double pose[12], double bound, gm_wall_alignment_add_info *info);
 gm_status alignment_window(const Alignment &A, double s_from, double s_to, gm_wall_alignment_piece *pieces, uint32_t capacity,
                            uint32_t *n_out);
+// what a locate on the alignment starts from: the plan, the home section, the state, the attached vectors
+gm_status alignment_locate_start(const Alignment &A, const double pose[12], double bound, gm_wall_alignment_locate_start *out);
 // the library's pose check: 0 the pose is accepted (Rm, tr filled), 1 an entry is not finite, 2 Rm is not a rotation
 int pose_split(const double pose[12], double Rm[3][3], double tr[3]);
 // the direction table of include/gm_hip.h: NK pairs (one operation per statement, as stated there)
@@ -343,6 +345,9 @@ struct gm_wall_map {
     std::vector<gm::wall::WallCheckSlot> checks;
     std::vector<gm::wall::WallLocateSlot> locates;
     std::vector<gm::wall::WallAlignSlot> aligns;
+    // gm_wall_alignment_locate_*: the pending locates, per slot, of the alignment this map is an element of (they read the
+    // map as its own locates do); nullptr on any other map and until that alignment first locates across elements
+    std::vector<gm::wall::PendingResult> *al_locates = nullptr;
     // gm_wall_map_add_frame_checked: per slot of ctx; gm_wall_map_add_points_checked: the stage call's own rows and block
     std::vector<gm::wall::WallAddCheckedSlot> add_checks;
     gm::DevArray<gm_wall_check_point> ac_rows;
@@ -407,6 +412,9 @@ void launch_add(gm_wall_map *m, const WallArgs &w, const WallClothoid &ax, uint3
 // An add on `s` (the stream of `slot`) must not be seen by a reader -- a check, a locate, an align -- enqueued before it
 // on another slot: `s` waits for every result outstanding there (nothing to wait for on a map without readers).
 gm_status add_wait_readers(gm_wall_map *m, uint32_t slot, hipStream_t s);
+// The other way round, for a reader on `s` (the stream of `slot`): it waits for the adds enqueued so far on every other
+// slot's stream -- an event, no host block.
+gm_status wait_adds(gm_wall_map *m, uint32_t slot, hipStream_t s);
 
 // A stage call's points (gm_wall_map_add_points, gm_wall_map_check_points, ...) on the staging slot: open, whatever the
 // call enqueues ahead of its points, upload, the call's launch, close.

@@ -7,9 +7,9 @@
 using namespace gm;
 using namespace gm::wall;
 
-namespace {
+namespace gm {
+namespace wall {
 
-// `s` (the stream of `slot`) waits for the adds enqueued so far on every other slot's stream: an event, no host block
 gm_status wait_adds(gm_wall_map *m, uint32_t slot, hipStream_t s)
 {
     gm_ctx *ctx = m->ctx;
@@ -21,6 +21,11 @@ gm_status wait_adds(gm_wall_map *m, uint32_t slot, hipStream_t s)
     }
     return GM_OK;
 }
+
+}  // namespace wall
+}  // namespace gm
+
+namespace {
 
 // ---- gm_wall_map_check_* ----
 

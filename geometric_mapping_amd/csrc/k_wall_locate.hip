@@ -13,16 +13,9 @@
 // Bound: HBM (17 B per point and pass, 12 B more from L2 in MAP).
 #include <math.h>
 
-#include "gm_fit_reduce.hpp"
-#include "gm_internal.hpp"
+#include "gm_wall_locate.hpp"
 
 namespace gm {
-
-// the columns of a partial row
-constexpr int kLocUsed = 14, kLocRes2 = 15, kLocPlane = 16, kLocOutside = 17, kLocUnsurveyed = 18, kLocGated = 19;
-constexpr int kLocAcc = 20;
-
-__device__ inline double loc_dot(const double (&x)[3], const double (&y)[3]) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2]; }
 
 // the state a pass starts from: pass 0 the launch's arguments, later passes WallLocateWork.  Returns false when the
 // chain has failed (uniform over the grid: every thread reads the same word, written by the launch before).
@@ -63,64 +56,13 @@ __device__ inline void loc_solve(const WallLocateArgs &a, int pass, uint32_t n, 
     }
     wk->n_points = n;
     wk->pad = 0u;
-    uint32_t status = GM_LOCATE_OK;
-    double x[4] = {nan, nan, nan, nan};
-    if (!(used >= 4.0)) {
-        status = GM_LOCATE_DEGENERATE;
-    } else {
-        double M[4][4] = {{tot[0], tot[1], tot[2], tot[3]}, {tot[1], tot[4], tot[5], tot[6]},
-                          {tot[2], tot[5], tot[7], tot[8]}, {tot[3], tot[6], tot[8], tot[9]}};
-        // Cholesky M = L L^T (lower triangle in place); a pivot that is not positive relative to its diagonal is singular
-        for (int k = 0; k < 4 && status == GM_LOCATE_OK; ++k) {
-            const double diag = M[k][k];
-            double piv = diag;
-            for (int j = 0; j < k; ++j) piv -= M[k][j] * M[k][j];
-            if (!(piv > 1e-12 * diag) || !isfinite(piv)) { status = GM_LOCATE_SINGULAR; break; }
-            const double l = sqrt(piv);
-            M[k][k] = l;
-            for (int i = k + 1; i < 4; ++i) {
-                double t = M[i][k];
-                for (int j = 0; j < k; ++j) t -= M[i][j] * M[k][j];
-                M[i][k] = t / l;
-            }
-        }
-        if (status == GM_LOCATE_OK) {
-            double y[4];
-            for (int i = 0; i < 4; ++i) {
-                double t = -tot[10 + i];
-                for (int j = 0; j < i; ++j) t -= M[i][j] * y[j];
-                y[i] = t / M[i][i];
-            }
-            for (int i = 3; i >= 0; --i) {
-                double t = y[i];
-                for (int j = i + 1; j < 4; ++j) t -= M[j][i] * x[j];
-                x[i] = t / M[i][i];
-            }
-        }
-    }
+    double x[4];
+    uint32_t status = loc_normal_solve(tot, x);
     double cn[3], dn[3], un[3], vn[3];
     double step = nan;
     if (status == GM_LOCATE_OK) {
-        const double s0 = a.s0;
-        for (int k = 0; k < 3; ++k) {
-            cn[k] = c[k] + x[0] * u[k] + x[1] * v[k];
-            dn[k] = d[k] + x[2] * u[k] + x[3] * v[k];
-        }
-        const double dl = sqrt(loc_dot(dn, dn));
-        for (int k = 0; k < 3; ++k) dn[k] /= dl;
-        const double ud = loc_dot(u, dn);
-        for (int k = 0; k < 3; ++k) un[k] = u[k] - ud * dn[k];
-        const double ul = sqrt(loc_dot(un, un));
-        for (int k = 0; k < 3; ++k) un[k] /= ul;
-        vn[0] = dn[1] * un[2] - dn[2] * un[1];
-        vn[1] = dn[2] * un[0] - dn[0] * un[2];
-        vn[2] = dn[0] * un[1] - dn[1] * un[0];
-        const double cd = loc_dot(cn, dn);
-        for (int k = 0; k < 3; ++k) cn[k] = cn[k] - cd * dn[k] - s0 * dn[k];
-        step = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3]);
-        bool ok = isfinite(step) && isfinite(dl) && isfinite(ul) && dl > 0.0 && ul > 0.0;
-        for (int k = 0; k < 3; ++k) ok = ok && isfinite(cn[k]) && isfinite(dn[k]) && isfinite(un[k]);
-        if (!ok) status = GM_LOCATE_SINGULAR;
+        for (int k = 0; k < 3; ++k) cn[k] = c[k] + x[0] * u[k] + x[1] * v[k];
+        if (!loc_update(d, u, v, x, a.s0, cn, dn, un, vn, step)) status = GM_LOCATE_SINGULAR;
     }
     if (status != GM_LOCATE_OK) {   // the chain stops here: the state stays that of this pass
         wk->pass[pass] = rec;
@@ -142,9 +84,7 @@ __device__ inline void loc_solve(const WallLocateArgs &a, int pass, uint32_t n, 
     wk->passes = (uint32_t)pass + 1u;
 }
 
-// One pass.  Sums (fp64) over the used points:
-//   0..9   J_i J_j, i <= j in 1..4 (11 12 13 14 22 23 24 33 34 44)      J = (a1, a2, t a1, t a2), a_k = -n.e_k
-//   10..13 J_i res    14 count    15 res^2    16..19 the other classes: plane, outside, unsurveyed, gated
+// One pass.  Sums (fp64, the columns of gm_wall_locate.hpp) over the used points: J = (a1, a2, t a1, t a2), a_k = -n.e_k
 __global__ __launch_bounds__(kFitThreads) void k_wall_locate(WallLocateArgs a, int pass)
 {
     __shared__ double tot[kFitCols];
@@ -209,11 +149,7 @@ __global__ __launch_bounds__(kFitThreads) void k_wall_locate(WallLocateArgs a, i
                     const double a2 = -(double)surf_dot3(nx, ny, nz, vf);
                     const double td = t, rs = r;
                     const double j3 = td * a1, j4 = td * a2;
-                    s[0] += a1 * a1; s[1] += a1 * a2; s[2] += a1 * j3; s[3] += a1 * j4;
-                    s[4] += a2 * a2; s[5] += a2 * j3; s[6] += a2 * j4;
-                    s[7] += j3 * j3; s[8] += j3 * j4; s[9] += j4 * j4;
-                    s[10] += a1 * rs; s[11] += a2 * rs; s[12] += j3 * rs; s[13] += j4 * rs;
-                    s[kLocRes2] += rs * rs;
+                    loc_sum_row(s, a1, a2, j3, j4, rs);
                     ++n_used;
                 }
             }

@@ -402,6 +402,17 @@ gm_wall_alignment_add_info Processor::addToWallAlignment(const double pose[12])
     return info;
 }
 
+gm_wall_alignment_locate_info Processor::locateWallAlignment(const double pose[12], const gm_wall_locate_params &prm)
+{
+    if (!alignment_) throw Error(GM_ERR_NOT_READY, "locateWallAlignment: createWallAlignment first");
+    if (newest_slot_ < 0) throw Error(GM_ERR_NOT_READY, "locateWallAlignment: no frame yet");
+    const unsigned slot = (unsigned)newest_slot_;
+    check(gm_wall_alignment_locate_frame(alignment_, ctx_, slot, pose, &prm), "locateWallAlignment");
+    gm_wall_alignment_locate_info info;
+    check(gm_wall_alignment_get_locate(alignment_, slot, &info), "locateWallAlignment");
+    return info;
+}
+
 gm_wall_add_info Processor::addToWallMap(const double pose[12])
 {
     if (!wall_) throw Error(GM_ERR_NOT_READY, "addToWallMap: createWallMap first");

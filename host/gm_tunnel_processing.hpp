@@ -139,7 +139,7 @@ public:
     // context (single device; GM_ERR_UNSUPPORTED with several).  createWallMap replaces the map of an earlier call.
     void createWallMap(const gm_wall_params &params);
     // the same on a circular-arc design axis (gm_wall_map_create_arc): one map per alignment element, straight or arc.
-    // locateWallMap and alignWallMap throw GM_ERR_UNSUPPORTED on such a map.
+    // locateWallMap and alignWallMap throw GM_ERR_UNSUPPORTED on such a map (locateWallAlignment below locates on curves).
     void createWallMap(const gm_wall_params &params, const gm_wall_arc *arc);
     // the same on a clothoid design axis (gm_wall_map_create_clothoid; arc must then be NULL): with it an alignment of
     // straights, transition curves and arcs is one map per element.  locateWallMap and alignWallMap throw
@@ -232,6 +232,11 @@ public:
     // (gm_wall_alignment_add_frame): every point goes to the one element that owns it.  The products run per element map,
     // gm_wall_alignment_map(wallAlignment(), i, &map), over the pieces of gm_wall_alignment_window.
     gm_wall_alignment_add_info addToWallAlignment(const double pose[12]);
+    // corrects the newest frame's pose against the alignment (gm_wall_alignment_locate_frame + gm_wall_alignment_get_locate):
+    // locateWallMap on straight, arc and clothoid elements and across their joints; the element maps are not changed.
+    // info.pose is the corrected pose (NaN when info.status & GM_LOCATE_FAILED_MASK).  The order per frame on an alignment:
+    // locateWallAlignment, the check on the element map the piece falls in, addToWallAlignment with the located pose.
+    gm_wall_alignment_locate_info locateWallAlignment(const double pose[12], const gm_wall_locate_params &prm);
     gm_wall_alignment *wallAlignment() { return alignment_; }
 
     gm_ctx *ctx() { return ctx_; }

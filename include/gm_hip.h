@@ -2025,8 +2025,8 @@ gm_status gm_wall_clothoid_point(const gm_wall_params *params, const gm_wall_clo
  * and every point is classed exactly once.  The LDS table's GM_SURF_MAX_CELLS cells are dealt to the sides in order (a
  * side's window: the stations of its own add's window that lie in the element, cut to what is left); a mapped point outside
  * its side's window goes to the map directly, which affects speed only.
- * Out of scope: the checked add, and check, locate and align through the alignment (they remain calls on an element map,
- * gm_wall_alignment_map); element maps of different grids; closed loops. */
+ * Out of scope: the checked add, and check and align through the alignment (they remain calls on an element map,
+ * gm_wall_alignment_map); element maps of different grids; closed loops.  The locate is gm_wall_alignment_locate_* below. */
 #define GM_WALL_ALIGNMENT_MAX_ELEMENTS 256
 #define GM_WALL_JOINT_MAX_SIDES 4
 enum { GM_WALL_ELEMENT_STRAIGHT = 0, GM_WALL_ELEMENT_ARC = 1, GM_WALL_ELEMENT_CLOTHOID = 2 };
@@ -2121,6 +2121,133 @@ gm_status gm_wall_alignment_add_points(gm_wall_alignment *alignment, const float
 gm_status gm_wall_alignment_sync(gm_wall_alignment *alignment);
 /* Synchronises, then the sums above. */
 gm_status gm_wall_alignment_info(gm_wall_alignment *alignment, gm_wall_alignment_totals *info);
+
+/* ---- a frame's pose corrected against a wall alignment (gm_wall_alignment_locate_*) ------------------------------------
+ * gm_wall_map_locate_* on the alignment: the same four degrees of freedom, the same three gated Gauss-Newton passes, the
+ * same parameters (gm_wall_locate_params, gm_wall_locate_check_params), statuses (GM_LOCATE_*) and GM_FIT_STEP_BOUND, on
+ * straight, arc and clothoid elements and across their joints.  A single-element alignment is the locate of a lone arc or
+ * clothoid map (gm_wall_map_locate_* keeps refusing those).  Per frame on an alignment: locate here -> check on the element
+ * map the piece falls in with the corrected pose -> gm_wall_alignment_add_frame with it.  One operation per statement.
+ *   plan          host, fp64: gm_wall_alignment_add_plan's, unchanged: the sensor's ("home") element, the sides within the
+ *                 reach, each side's own per-add frame, the joint planes.  More than GM_WALL_JOINT_MAX_SIDES sides:
+ *                 GM_ERR_UNSUPPORTED, nothing is enqueued.  ONE side that is a straight element: the locate IS
+ *                 gm_wall_map_locate_* of that element map, the same launches; the info's first 152 bytes (but for
+ *                 struct_size) and each pass record's first 112 are gm_wall_locate_info's and gm_wall_locate_pass's, byte
+ *                 for byte; the record's side block 0 repeats (o, a, u, v).  Everything below is the other plans'.
+ *   start         host, fp64, not rounded.  (o_f, a, u, v): the home element's section at its anchor chainage s_f, from
+ *                 gm_wall_arc_frame, gm_wall_clothoid_frame (evaluated in tau, as its per-add rule) or the straight frame
+ *                 (o_f = o + (t_min + j_f ds) a).  The state is that section in sensor coordinates: c = Rm^T (o_f - tr),
+ *                 d = Rm^T a, u' = Rm^T u, v' = Rm^T v;  s0 = -c.d is kept fixed.
+ *   attached      host, fp64, once per locate.  Every vector of every side's per-add block -- o', a', n', b' of a curved
+ *                 side at ITS anchor section, o', a', u', v' of a straight side -- and of every joint plane (J, aJ) is
+ *                 expressed in the home section: a point X as h = ((X - o_f).a, (X - o_f).u, (X - o_f).v), a direction D as
+ *                 h = (D.a, D.u, D.v).  The home side's own o and a are h = (0, 0, 0) and (1, 0, 0) exactly, and on a
+ *                 straight home side u, v are (0, 1, 0) and (0, 0, 1).  kappa_f, rate, un, ub, vn, vb (rounded to fp32 once,
+ *                 as the side's add has them) and the anchor stations do not move.
+ *   image         of an attached vector under a state, fp64: a point c + ((h0 d + h1 u') + h2 v'), a direction
+ *                 (h0 d + h1 u') + h2 v', per component; rounded to fp32 once.
+ *   pass k        k = 0, 1, 2 with the gate g_k = (float)(gate 2^-k).  The state is rounded to fp32 once and reported in
+ *                 pass[k].o, a, u, v; every side's block and every joint plane is the image under the pass's state and is
+ *                 reported in pass[k].side and pass[k].joint_o / joint_a.  Pass 0's are computed by the host and travel in
+ *                 the launch arguments; after pass k the thread that solves it writes those of pass k + 1.
+ *   per point     device, fp32, every operation rounded to nearest.
+ *                 owner   the add's rule on the pass's planes:  q = p - Jo'_i;  d_i = fma(qx, ax, fma(qy, ay, qz az));  the
+ *                         side before the first joint, ascending, with d_i < 0, else the last side.
+ *                 chain   the owner's alone, on its block of the pass, exactly the add's chain of that axis above:
+ *                         straight  q, t, w of the locate's chain above;  rho = sqrt(fma(wx, wx, fma(wy, wy, wz wz))),
+ *                                   the root rounded to nearest as on the curved sides;  e = rho - R;
+ *                                   nrm = w (1 / rho) (fp32 reciprocal, rounded to nearest);  guard: none.
+ *                         arc       x, y, z, cx, cy, d, t, yc of the arc rule;  rho = sqrt(fma(yc, yc, z z));  e = rho - R;
+ *                                   cs = cy / d;  sn = cx / d;  guard: cy > 0.
+ *                         clothoid  x, y, z, t, g, yc of the clothoid rule;  rho and e alike;  (sn, cs) = the (sin, cos) of
+ *                                   ps in the closing E(t);  guard: the clothoid rule's (cy > 0, every den > 0.25, t finite,
+ *                                   |g| <= GM_WALL_CLOTHOID_G_BOUND).
+ *                         curved    nt_i = fma(cs, n'_i, -(sn a'_i));  nrm_i = fma(yc, nt_i, z b'_i) (1 / rho)  (the same
+ *                                   reciprocal): the unit radial direction (yc n(t) + z b) / rho in sensor coordinates.
+ *                 target  GM_WALL_LOCATE_DESIGN: m = 0.  GM_WALL_LOCATE_MAP: j = the owner's j_f + floor(t / ds) in 64-bit
+ *                         integers against the owner's n_stations; the sector by the owner's rule (a straight side from
+ *                         (w.v', w.u') of its block, a curved side from (yc, z) and its un, ub, vn, vb); count, sum and the
+ *                         min_count and sum / count rules of gm_wall_map_locate_* on the OWNER's table.
+ *                 classes in this order: plane (label 1); gated (e not finite, or the guard fails: before any integer
+ *                         conversion or table index); outside, unsurveyed (MAP only); res = e - m;  used iff |res| < g_k and
+ *                         rho > 0, else gated.
+ *   sums          for a used point, fp64 from the fp32 values nrm, p and the pass's fp32 state (o, a, u, v):
+ *                 c0_i = o_i + s0 a_i;  q = p - c0;  J = -(nrm.u, nrm.v, nrm.(v x q), -(nrm.(u x q))), dot and cross products
+ *                 in the order x, y, z.  These are the lateral offset along u', v' and the tilt of d toward u', v', the tilt
+ *                 turning the map about the sensor's own foot c0 (on a straight side the columns span (a1, a2, t a1, t a2)
+ *                 of gm_wall_map_locate_*: J_3 = (t - s0) a1).  The 10 J_i J_j, the 4 J_i res, the count and res^2, their
+ *                 grid and order, the solve, its pivot rule and its failures are gm_wall_map_locate_*'s.
+ *   update        c0 = c + s0 d + x0 u' + x1 v';  d <- normalize(d + x2 u' + x3 v');  u' <- normalize(u' - (u'.d) d);
+ *                 v' <- d x u';  c <- c0 - (c0.d) d - s0 d.  (That is gm_wall_map_locate_*'s update of the same correction.)
+ *                 Every attached vector follows by its image.
+ *   pose          host, fp64: Rm' = [a u v] [d u' v']^T with the home section's unrounded columns, tr' = o_f - Rm' c;
+ *                 lateral, tilt, GM_LOCATE_NOT_CONVERGED and the failure rules as gm_wall_map_locate_*.
+ * The element maps are not changed.  Ordering as for a check, against every side's map: the locate sees every add enqueued
+ * before it on any slot, through the alignment or through an element map, and none enqueued after it.  No floating-point
+ * atomics, no host round trip between the passes, one pending result per (alignment, slot).  Scratch per (alignment,
+ * slot) -- the working state, 96 KiB of partial rows, a pinned copy of the result -- and the stage call's three per-point
+ * arrays are allocated on first use, kept grow-only and freed with the alignment; an alignment that never locates across
+ * a joint or on a curved element allocates nothing.  Out of scope: chainage and roll (they stay the caller's), align and
+ * check through the alignment. */
+typedef struct gm_wall_alignment_locate_pass {   /* 376 bytes; the first 112 are gm_wall_locate_pass */
+    float    o[3], a[3], u[3], v[3];   /* the pass's state c, d, u', v' in SENSOR coordinates (fp32, as the points saw it) */
+    float    gate;                     /* g_k */
+    uint32_t plane, outside, unsurveyed, gated, used;   /* the classes over all sides: their sum is n_points */
+    double   rms;
+    double   step[4];
+    float    side[GM_WALL_JOINT_MAX_SIDES][12];         /* per side o', a', n', b' (straight: o', a', u', v') of the pass */
+    float    joint_o[GM_WALL_JOINT_MAX_SIDES - 1][3];   /* Jo' of the pass */
+    float    joint_a[GM_WALL_JOINT_MAX_SIDES - 1][3];   /* aJ' */
+} gm_wall_alignment_locate_pass;
+
+typedef struct gm_wall_alignment_locate_info {   /* 1448 bytes; the first 152 are gm_wall_locate_info's */
+    uint32_t struct_size;      /* = sizeof(gm_wall_alignment_locate_info), filled by the library */
+    uint32_t status;           /* GM_LOCATE_* */
+    uint32_t passes;
+    uint32_t n_points;
+    int64_t  anchor_station;   /* j_f of the home side */
+    double   pose[12];         /* the corrected pose, row-major 3x4 [Rm' | tr'], sensor -> map */
+    double   lateral[2], tilt[2];
+    uint32_t element;          /* the home element */
+    uint32_t n_sides;
+    uint32_t side_element[GM_WALL_JOINT_MAX_SIDES];   /* as gm_wall_alignment_add_info */
+    uint32_t side_kind[GM_WALL_JOINT_MAX_SIDES];      /* GM_WALL_ELEMENT_* */
+    int64_t  side_anchor[GM_WALL_JOINT_MAX_SIDES];
+    float    side_axis[GM_WALL_JOINT_MAX_SIDES][6];   /* kappa_f, rate, un, ub, vn, vb as the chains took them (0 where unused) */
+    gm_wall_alignment_locate_pass pass[GM_LOCATE_PASSES];
+} gm_wall_alignment_locate_info;
+
+typedef struct gm_wall_alignment_locate_start {   /* 1008 bytes: what a locate starts from, host only */
+    uint32_t struct_size;      /* = sizeof(gm_wall_alignment_locate_start), filled by the library */
+    uint32_t home;             /* the home element's index among the sides */
+    gm_wall_alignment_add_info add;   /* the plan of the add under the same pose */
+    double   c[3], d[3], u[3], v[3];  /* the start, sensor coordinates */
+    double   s0;
+    double   o_f[3], a[3], fu[3], fv[3];   /* the home section in map coordinates, not rounded */
+    double   side[GM_WALL_JOINT_MAX_SIDES][12];      /* h of each side's four vectors */
+    double   joint[GM_WALL_JOINT_MAX_SIDES - 1][6];  /* h of J and of aJ */
+    float    side_axis[GM_WALL_JOINT_MAX_SIDES][6];
+    uint32_t side_kind[GM_WALL_JOINT_MAX_SIDES];
+} gm_wall_alignment_locate_start;
+
+/* Host only, no context: the start, the attached vectors and the constants of a locate under `pose` on a context whose
+ * boxFilterBound is `bound`.  Errors as gm_wall_alignment_add_plan. */
+gm_status gm_wall_alignment_locate_plan(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n,
+                                        const double pose[12], double bound, gm_wall_alignment_locate_start *start);
+/* gm_wall_map_locate_frame on the alignment (prm NULL: the defaults).  GM_ERR_INVALID_ARG: NULL, a foreign context, a bad
+ * slot, bad parameters, a refused pose; GM_ERR_NOT_READY: the slot holds no frame; GM_ERR_UNSUPPORTED: too many sides. */
+gm_status gm_wall_alignment_locate_frame(gm_wall_alignment *alignment, gm_ctx *ctx, uint32_t slot, const double pose[12],
+                                         const gm_wall_locate_params *prm);
+/* The result of the last locate enqueued on (alignment, slot); waits for that locate only.  GM_ERR_NOT_READY: none was
+ * enqueued; GM_ERR_INVALID_ARG: NULL, a bad slot.  gm_wall_alignment_locate_points counts as a locate on slot 0. */
+gm_status gm_wall_alignment_get_locate(gm_wall_alignment *alignment, uint32_t slot, gm_wall_alignment_locate_info *info);
+/* The same kernels as one blocking stage call on host buffers (slot 0).  The per-point outputs may each be NULL and are
+ * those of the last pass that ran: residual (res, NaN unless used), cell (relative to the map of that pass's owner, -1
+ * unless the point reached a cell in MAP); element is the owner's element index in pass 0, set for every point: the owner
+ * under the caller's pose, which is gm_wall_alignment_add_points' under the same pose. */
+gm_status gm_wall_alignment_locate_points(gm_wall_alignment *alignment, const float *xyz, uint32_t n, const uint8_t *labels,
+                                          const double pose[12], const gm_wall_locate_params *prm,
+                                          gm_wall_alignment_locate_info *info, float *residual, int32_t *cell, int32_t *element);
 
 /* "Compressed map" record of a completed slot.  The reference defines no such
  * output; this is a build-defined format: header, primitive records,

@@ -1,0 +1,31 @@
+"""The C++ host mirror's locate on a wall alignment (host/gm_wall_alignment_locate_test.cpp, plain g++ over the C ABI):
+Processor::locateWallAlignment across the clothoid -> arc joint must give the C ABI's info, byte for byte."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXE = os.path.join(ROOT, "host", "gm_wall_alignment_locate_test")
+
+
+def _build():
+    subprocess.run(["make", "-C", os.path.join(ROOT, "host"), "gm_wall_alignment_locate_test"], check=True, capture_output=True)
+
+
+def test_host_wall_alignment_locate_builds_and_is_declared():
+    _build()
+    assert os.path.exists(EXE)
+    hdr = open(os.path.join(ROOT, "host", "gm_tunnel_processing.hpp")).read()
+    assert "gm_wall_alignment_locate_info locateWallAlignment(const double pose[12], const gm_wall_locate_params &prm);" in hdr
+    lines = open(os.path.join(ROOT, "host", "Makefile")).read().splitlines()
+    for head in ("all:", "gm_wall_alignment_locate_test:", "\trm -f "):   # all, the rule, clean each know the binary, once
+        assert [ln.replace(":", " ").split().count("gm_wall_alignment_locate_test") for ln in lines if ln.startswith(head)] == [1], head
+
+
+@pytest.mark.gpu
+def test_host_wall_alignment_locate_on_gpu():
+    _build()
+    r = subprocess.run([EXE], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "gm_wall_alignment_locate_test ok" in r.stdout
