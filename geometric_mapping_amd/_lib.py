@@ -401,6 +401,10 @@ class WallCheckInfo(C.Structure):
                 ("peak_pos", C.c_int64), ("peak_neg", C.c_int64)]
 
 
+class WallAlignmentCheckInfo(C.Structure):
+    _fields_ = WallCheckInfo._fields_ + [("n_sides", C.c_uint32), ("reserved", C.c_uint32), ("side_class", (C.c_uint32 * 7) * 4)]
+
+
 class WallAddCheckedParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("skip", C.c_uint32), ("min_delta", C.c_double)]
 
@@ -660,6 +664,14 @@ def load():
         "gm_wall_alignment_locate_frame": (C.c_int, [vp, vp, u32, dp, wlprmp]),
         "gm_wall_alignment_get_locate": (C.c_int, [vp, u32, C.POINTER(WallAlignmentLocateInfo)]),
         "gm_wall_alignment_locate_points": (C.c_int, [vp, fp, u32, u8p, dp, wlprmp, C.POINTER(WallAlignmentLocateInfo), fp, i32p, i32p]),
+        "gm_wall_alignment_check_frame": (C.c_int, [vp, vp, u32, dp, wkprmp, waladdp]),
+        "gm_wall_alignment_get_check": (C.c_int, [vp, u32, C.POINTER(WallAlignmentCheckInfo), wkptp, u32, u32p]),
+        "gm_wall_alignment_check_points": (C.c_int, [vp, fp, u32, u8p, dp, wkprmp, waladdp, C.POINTER(WallAlignmentCheckInfo), wkptp,
+                                                     u32, u32p, fp, i32p, i32p, u8p, i32p]),
+        "gm_wall_alignment_add_frame_checked": (C.c_int, [vp, vp, u32, dp, wcaprmp, waladdp]),
+        "gm_wall_alignment_get_add_checked": (C.c_int, [vp, u32, wcainfop]),
+        "gm_wall_alignment_add_points_checked": (C.c_int, [vp, fp, u32, u8p, dp, wcaprmp, wkptp, u32, waladdp, wcainfop, fp, i32p,
+                                                           i32p]),
         "gm_wall_alignment_info": (C.c_int, [vp, waltotp]),
         "gm_wall_map_add_frame": (C.c_int, [vp, vp, u32, dp, waddp]),
         "gm_wall_map_add_points": (C.c_int, [vp, fp, u32, u8p, dp, waddp, fp, i32p]),

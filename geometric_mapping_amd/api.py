@@ -2041,6 +2041,114 @@ class WallAlignment(WallAlignmentRule):
             return self._locate_info(info), None, None, None
         return self._locate_info(info), res[:n].copy(), cell[:n].copy(), el[:n].copy()
 
+    @staticmethod
+    def split_cell(rows):
+        """(side, cell) of WALL_CHECK_POINT rows of a check through the alignment: cell holds side << 24 | cell, side indexes
+        the check plan's side_element, cell is relative to that element's map."""
+        c = np.asarray(rows["cell"]).view(np.uint32)
+        return (c >> np.uint32(24)).astype(np.int32), (c & np.uint32(0xFFFFFF)).astype(np.int32)
+
+    @staticmethod
+    def _check_info(i):
+        """The dict of a gm_wall_alignment_check_info: WallMap.check_result()'s keys, n_sides and side_class
+        [n_sides, 7] uint32 in GM_WALL_CHECK_CLS_* order."""
+        d = WallMap._check_info(i)
+        ns = int(i.n_sides)
+        d.update(n_sides=ns, side_class=np.array([list(r) for r in i.side_class], dtype=np.uint32)[:ns])
+        return d
+
+    def check_frame(self, slot=0, pose=np.eye(4)[:3], **params):
+        """gm_wall_alignment_check_frame: enqueue the check of the slot's last submitted frame under `pose`, every point
+        against its owner's map (keywords: reference, min_count, threshold, gate).  Returns the plan dict; check_result()
+        fetches the result."""
+        m = WallMap._pose(pose)
+        p = WallMap.check_params(**params)
+        i = _lib.WallAlignmentAddInfo()
+        self._ctx._check(self._L.gm_wall_alignment_check_frame(self._h(), self._ctx._ctx, slot, _dptr(m), C.byref(p), C.byref(i)))
+        return _alignment_add_info(i)
+
+    def check_result(self, slot=0):
+        """gm_wall_alignment_get_check: (info dict, WALL_CHECK_POINT records ascending by index) of the last check on the
+        slot; split_cell() splits their cell.  A count query first, then the sized call."""
+        info = _lib.WallAlignmentCheckInfo()
+        got = C.c_uint32(0)
+        self._ctx._check(self._L.gm_wall_alignment_get_check(self._h(), slot, C.byref(info), None, 0, C.byref(got)))
+        cap = int(got.value)
+        pts = np.zeros(max(cap, 1), dtype=WALL_CHECK_POINT)
+        if cap:
+            self._ctx._check(self._L.gm_wall_alignment_get_check(self._h(), slot, C.byref(info),
+                                                                 pts.ctypes.data_as(C.POINTER(_lib.WallCheckPoint)), cap, C.byref(got)))
+        return self._check_info(info), pts[:int(got.value)].copy()
+
+    def check_points(self, cloud, pose=np.eye(4)[:3], labels=None, outputs=True, **params):
+        """gm_wall_alignment_check_points on a host cloud [n,3]: (info dict with the plan under "plan", records,
+        dict(e float32, cell int32 relative to the owner's map, delta int32, cls uint8, element int32) or None without
+        outputs)."""
+        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+        m = WallMap._pose(pose)
+        lab, lp = GeometricMapping._u8(labels)
+        p = WallMap.check_params(**params)
+        n = len(xyz)
+        plan, info, got = _lib.WallAlignmentAddInfo(), _lib.WallAlignmentCheckInfo(), C.c_uint32(0)
+        pts = np.zeros(max(n, 1), dtype=WALL_CHECK_POINT)
+        out = None
+        if outputs:
+            out = dict(e=np.empty(max(n, 1), np.float32), cell=np.empty(max(n, 1), np.int32), delta=np.empty(max(n, 1), np.int32),
+                       cls=np.empty(max(n, 1), np.uint8), element=np.empty(max(n, 1), np.int32))
+        i32p = C.POINTER(C.c_int32)
+        self._ctx._check(self._L.gm_wall_alignment_check_points(
+            self._h(), _f32(xyz), n, lp, _dptr(m), C.byref(p), C.byref(plan), C.byref(info),
+            pts.ctypes.data_as(C.POINTER(_lib.WallCheckPoint)), n, C.byref(got),
+            _f32(out["e"]) if outputs else None, out["cell"].ctypes.data_as(i32p) if outputs else None,
+            out["delta"].ctypes.data_as(i32p) if outputs else None,
+            out["cls"].ctypes.data_as(C.POINTER(C.c_uint8)) if outputs else None,
+            out["element"].ctypes.data_as(i32p) if outputs else None))
+        d = self._check_info(info)
+        d["plan"] = _alignment_add_info(plan)
+        return d, pts[:int(got.value)].copy(), ({k: v[:n].copy() for k, v in out.items()} if outputs else None)
+
+    def add_frame_checked(self, slot=0, pose=np.eye(4)[:3], **params):
+        """gm_wall_alignment_add_frame_checked: enqueue the add of the slot's last submitted frame under `pose`, less the
+        points the slot's last check_frame through this alignment selected (keywords: skip, min_delta).  Returns the plan
+        dict; add_checked_result() fetches the counts."""
+        m = WallMap._pose(pose)
+        p = WallMap.add_checked_params(**params)
+        i = _lib.WallAlignmentAddInfo()
+        self._ctx._check(self._L.gm_wall_alignment_add_frame_checked(self._h(), self._ctx._ctx, slot, _dptr(m), C.byref(p), C.byref(i)))
+        return _alignment_add_info(i)
+
+    def add_checked_result(self, slot=0):
+        """gm_wall_alignment_get_add_checked: the info dict of the last checked add on the slot (waits for that call only)."""
+        info = _lib.WallAddCheckedInfo()
+        self._ctx._check(self._L.gm_wall_alignment_get_add_checked(self._h(), slot, C.byref(info)))
+        return WallMap._add_checked_info(info)
+
+    def add_points_checked(self, cloud, pose, rows, labels=None, outputs=True, **params):
+        """gm_wall_alignment_add_points_checked on a host cloud [n,3] and WALL_CHECK_POINT rows (any order, duplicates
+        allowed): (info dict with the plan under "plan", residual [n] float32, cell [n] int32 relative to the owner's map,
+        element [n] int32); outputs False skips the per-point arrays (None each)."""
+        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+        m = WallMap._pose(pose)
+        lab, lp = GeometricMapping._u8(labels)
+        p = WallMap.add_checked_params(**params)
+        r = np.ascontiguousarray(np.asarray(rows, dtype=WALL_CHECK_POINT).reshape(-1))
+        plan, info = _lib.WallAlignmentAddInfo(), _lib.WallAddCheckedInfo()
+        n = len(xyz)
+        res = np.empty(max(n, 1), dtype=np.float32) if outputs else None
+        cell = np.empty(max(n, 1), dtype=np.int32) if outputs else None
+        el = np.empty(max(n, 1), dtype=np.int32) if outputs else None
+        i32 = C.POINTER(C.c_int32)
+        self._ctx._check(self._L.gm_wall_alignment_add_points_checked(
+            self._h(), _f32(xyz), n, lp, _dptr(m), C.byref(p),
+            r.ctypes.data_as(C.POINTER(_lib.WallCheckPoint)) if len(r) else None, len(r), C.byref(plan), C.byref(info),
+            _f32(res) if outputs else None, cell.ctypes.data_as(i32) if outputs else None,
+            el.ctypes.data_as(i32) if outputs else None))
+        d = WallMap._add_checked_info(info)
+        d["plan"] = _alignment_add_info(plan)
+        if not outputs:
+            return d, None, None, None
+        return d, res[:n].copy(), cell[:n].copy(), el[:n].copy()
+
 
 def decode_compressed_map(buf):
     """Parse gm_get_compressed_map bytes (gm_map_header / gm_map_primitive in include/gm_hip.h)."""

@@ -387,6 +387,10 @@ void launch_wall_add_arc_masked(const WallArgs &a, const WallArc &arc, const uns
                                 uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
 void launch_wall_add_clothoid_masked(const WallArgs &a, const WallClothoid &cl, const unsigned long long *mask, unsigned long long *ctr,
                                      uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
+// k_wall_add_joint over the points whose mask bit is clear (gm_wall_alignment_add_*_checked): skipped and the four point
+// classes, summed over the sides, also go to ctr[4 .. 8]
+void launch_wall_add_joint_masked(const WallJointArgs &a, const unsigned long long *mask, unsigned long long *ctr, uint32_t n_cap,
+                                  uint32_t points_per_block, hipStream_t s);
 // the class of one row: 0 selected negative, 1 selected positive, 2 kept, 3 rejected (delta_bits: the row's delta)
 __host__ __device__ inline uint32_t wall_mark_class(uint32_t delta_bits, long long dq, uint32_t index, uint32_t n_points,
                                                     uint32_t skip, long long S)
@@ -503,6 +507,43 @@ struct WallCheckArgs {
 void launch_wall_check(const WallCheckArgs &a, uint32_t n_cap, const ScanState &st, hipStream_t s);
 void launch_wall_check_arc(const WallCheckArgs &a, const WallArc &arc, uint32_t n_cap, const ScanState &st, hipStream_t s);
 void launch_wall_check_clothoid(const WallCheckArgs &a, const WallClothoid &cl, uint32_t n_cap, const ScanState &st, hipStream_t s);
+// k_wall_check_joint.hip (gm_wall_alignment_check_*): one k_compact launch over the sides of an alignment's plan, every
+// point on its owner's chain and against its owner's table.  u64 words: the first kWallCheckCounters as above (the seven
+// summed classes are left to the host), then the classes per side [GM_WALL_JOINT_MAX_SIDES][GM_WALL_CHECK_N_CLS].
+constexpr int kWallCheckJointCounters = kWallCheckCounters + GM_WALL_JOINT_MAX_SIDES * GM_WALL_CHECK_N_CLS;
+struct WallCheckJointSide {
+    int64_t anchor;            // j_f of this side's own check
+    float o[3], a[3], u[3], v[3];   // its frame-local map frame, as WallArgs
+    WallClothoid ax;           // its axis block (an arc side fills ax.arc alone, a straight side nothing)
+    WallTable table;
+    uint32_t n_stations;
+    int32_t axis;              // kAxisStraight, kAxisArc, kAxisClothoid
+    int32_t element;           // the element's index in the alignment
+};
+struct WallCheckJointArgs {
+    const float4 *pts;
+    const uint8_t *labels;     // nullptr: no point is plane
+    const uint32_t *n_ptr;     // device point count (nullptr: n_host)
+    uint32_t n_host;
+    uint32_t n_sides;          // 2 .. GM_WALL_JOINT_MAX_SIDES
+    uint32_t n_sectors, reference, min_count;
+    uint32_t row_is_index;     // stage call: row = index
+    uint32_t outputs;          // set by the launch: one of the five per-point outputs below is wanted
+    uint32_t pad;
+    long long T;
+    float R, station_length, gate, sector_angle, two_pi;   // one grid for every element; gate is the check's
+    float jo[GM_WALL_JOINT_MAX_SIDES - 1][3];   // Jo' of the joint between side i and side i + 1
+    float ja[GM_WALL_JOINT_MAX_SIDES - 1][3];   // aJ'
+    gm_wall_check_point *out;  // staging, >= n_cap rows
+    unsigned long long *ctr;   // [kWallCheckJointCounters], zeroed by the caller on the same stream
+    float *res;                // stage call only (nullptr in the frame path)
+    int32_t *cell;
+    int32_t *delta;
+    uint8_t *cls;
+    int32_t *element;
+    WallCheckJointSide side[GM_WALL_JOINT_MAX_SIDES];
+};
+void launch_wall_check_joint(const WallCheckJointArgs &a, uint32_t n_cap, const ScanState &st, hipStream_t s);
 // the rule's integers, shared by the kernel and gm_wall_check_classify
 __host__ __device__ inline long long wall_check_fix(float e)   // (int64) rint(e 2^20), saturating at int32, 0 for a NaN
 {

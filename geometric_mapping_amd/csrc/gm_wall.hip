@@ -185,9 +185,10 @@ gm_status add_wait_readers(gm_wall_map *m, uint32_t slot, hipStream_t s)
     for (uint32_t i = 0; i < m->ctx->n_slots; ++i)
         for (const PendingResult *r : {&m->checks[i].res, &m->locates[i].res, &m->aligns[i].res})
             if (i != slot && r->outstanding) GMW_HIP(m->ctx, hipStreamWaitEvent(s, r->done, 0));
-    if (m->al_locates)
-        for (uint32_t i = 0; i < m->ctx->n_slots; ++i)
-            if (i != slot && (*m->al_locates)[i].outstanding) GMW_HIP(m->ctx, hipStreamWaitEvent(s, (*m->al_locates)[i].done, 0));
+    for (const std::vector<PendingResult> *al : {m->al_locates, m->al_checks})
+        if (al)
+            for (uint32_t i = 0; i < m->ctx->n_slots; ++i)
+                if (i != slot && (*al)[i].outstanding) GMW_HIP(m->ctx, hipStreamWaitEvent(s, (*al)[i].done, 0));
     return GM_OK;
 }
 

@@ -22,4 +22,22 @@ __device__ __forceinline__ void wall_global_add(const WallTable &T, uint64_t c, 
     atomicMax(&T.hi[c], hi);
 }
 
+// the mask of a checked add (k_wall_add*_masked, k_wall_add_joint_masked): bit i of words set = point i is skipped; the
+// unmasked instantiations carry nothing
+template <bool kMasked>
+struct WallMask {};
+template <>
+struct WallMask<true> {
+    const unsigned long long *words;   // ceil(n / 64) words at least
+    unsigned long long *ctr;           // [kWallAddCheckedCounters]
+};
+
+// what wall_chain and wall_station read of WallArgs, of one side of a joint kernel (k_wall_add_joint, k_wall_check_joint)
+struct JointChainArgs {
+    float o[3], a[3], u[3], v[3];
+    float R, station_length, gate, sector_angle, two_pi;
+    uint32_t n_sectors, n_stations;
+    int64_t anchor;
+};
+
 }  // namespace gm

@@ -7,11 +7,31 @@
 using namespace gm;
 using namespace gm::wall;
 
+namespace gm {
+namespace wall {
+
+uint64_t add_checked_block_words(uint32_t n_cap) { return kWallAddCheckedCounters + ((uint64_t)n_cap + 63u) / 64u; }
+
+void add_checked_fill_info(gm_wall_add_checked_info *info, uint32_t status, long long S, const unsigned long long *h)
+{
+    memset(info, 0, sizeof(*info));
+    info->struct_size = (uint32_t)sizeof(gm_wall_add_checked_info);
+    info->status = status;
+    info->min_delta_q = S;
+    info->n_points = (uint32_t)h[10];
+    info->n_rows = (uint32_t)h[9];
+    info->rows_neg = (uint32_t)h[0]; info->rows_pos = (uint32_t)h[1];
+    info->rows_kept = (uint32_t)h[2]; info->rows_rejected = (uint32_t)h[3];
+    info->skipped = (uint32_t)h[4];
+    info->mapped = (uint32_t)h[5]; info->outside = (uint32_t)h[6]; info->beyond_gate = (uint32_t)h[7]; info->plane = (uint32_t)h[8];
+}
+
+}  // namespace wall
+}  // namespace gm
+
 namespace {
 
-// the 64-bit words of a call's block: the counters, then one mask bit per point of n_cap (the masked add loads one word per
-// wave and trip)
-uint64_t block_words(uint32_t n_cap) { return kWallAddCheckedCounters + ((uint64_t)n_cap + 63u) / 64u; }
+uint64_t block_words(uint32_t n_cap) { return add_checked_block_words(n_cap); }
 
 // What one call enqueues on `s`, in this order: its block -- counters | mask words of n_cap points -- zeroed by ONE fill, the
 // mark over up to rows_cap rows, the masked add.  mk: rows, counts and parameters filled by the caller; blk: the call's.
@@ -33,16 +53,7 @@ gm_status add_checked_enqueue(gm_wall_map *m, WallMarkArgs &mk, const WallArgs &
 
 void fill_info(gm_wall_add_checked_info *info, uint32_t status, long long S, const unsigned long long *h)
 {
-    memset(info, 0, sizeof(*info));
-    info->struct_size = (uint32_t)sizeof(gm_wall_add_checked_info);
-    info->status = status;
-    info->min_delta_q = S;
-    info->n_points = (uint32_t)h[10];
-    info->n_rows = (uint32_t)h[9];
-    info->rows_neg = (uint32_t)h[0]; info->rows_pos = (uint32_t)h[1];
-    info->rows_kept = (uint32_t)h[2]; info->rows_rejected = (uint32_t)h[3];
-    info->skipped = (uint32_t)h[4];
-    info->mapped = (uint32_t)h[5]; info->outside = (uint32_t)h[6]; info->beyond_gate = (uint32_t)h[7]; info->plane = (uint32_t)h[8];
+    add_checked_fill_info(info, status, S, h);
 }
 
 }  // namespace

@@ -348,6 +348,8 @@ struct gm_wall_map {
     // gm_wall_alignment_locate_*: the pending locates, per slot, of the alignment this map is an element of (they read the
     // map as its own locates do); nullptr on any other map and until that alignment first locates across elements
     std::vector<gm::wall::PendingResult> *al_locates = nullptr;
+    // gm_wall_alignment_check_*: the same for that alignment's pending checks
+    std::vector<gm::wall::PendingResult> *al_checks = nullptr;
     // gm_wall_map_add_frame_checked: per slot of ctx; gm_wall_map_add_points_checked: the stage call's own rows and block
     std::vector<gm::wall::WallAddCheckedSlot> add_checks;
     gm::DevArray<gm_wall_check_point> ac_rows;
@@ -415,6 +417,11 @@ gm_status add_wait_readers(gm_wall_map *m, uint32_t slot, hipStream_t s);
 // The other way round, for a reader on `s` (the stream of `slot`): it waits for the adds enqueued so far on every other
 // slot's stream -- an event, no host block.
 gm_status wait_adds(gm_wall_map *m, uint32_t slot, hipStream_t s);
+
+// gm_wall_add_checked.hip, shared with the alignment's checked add: the 64-bit words of a call's block -- the counters, then
+// one mask bit per point of n_cap (the masked add loads one word per wave and trip) -- and the info of a block's counters
+uint64_t add_checked_block_words(uint32_t n_cap);
+void add_checked_fill_info(gm_wall_add_checked_info *info, uint32_t status, long long S, const unsigned long long *h);
 
 // A stage call's points (gm_wall_map_add_points, gm_wall_map_check_points, ...) on the staging slot: open, whatever the
 // call enqueues ahead of its points, upload, the call's launch, close.

@@ -34,13 +34,7 @@ namespace gm {
 // multiple of 64 in every trip: stride is a multiple of kWallThreads), so the mask costs one wave-uniform 8-byte load per
 // trip.  The call's five class counts go to m.ctr[4 ..] beside T.totals.  The unmasked instantiation carries none of it,
 // and each instantiation has an entry point of its own below, so that k_wall_add keeps its name and its arguments.
-template <bool kMasked>
-struct WallMask {};
-template <>
-struct WallMask<true> {
-    const unsigned long long *words;   // ceil(n / 64) words at least
-    unsigned long long *ctr;           // [kWallAddCheckedCounters]
-};
+// (WallMask: gm_wall_add.hpp, shared with k_wall_add_joint)
 
 // Axis (WallArcArg<false> straight, WallArcArg<true> a map of gm_wall_map_create_arc, WallClothoidArg one of
 // gm_wall_map_create_clothoid): the chain head runs on the by-value axis block (wall_chain, gm_device.hpp); everything

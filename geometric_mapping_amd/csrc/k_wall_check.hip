@@ -17,29 +17,11 @@
 // index < n.  No floating-point atomics, no LDS table to zero or flush.
 #include <string.h>
 
-#include "gm_compact.hpp"
-#include "gm_internal.hpp"
+#include "gm_wall_check.hpp"   // the payload, the cell rule, the row, the peaks: shared with k_wall_check_joint.hip
 
 namespace gm {
 
-static_assert(sizeof(gm_wall_check_point) == 32, "a 32-byte PointCloud2 row");
-
-// block-shared: the seven class counts, then the two peaks (magnitudes)
-__device__ __forceinline__ uint32_t *wk_class_counts()
-{
-    __shared__ uint32_t c[GM_WALL_CHECK_N_CLS];
-    return c;
-}
-__device__ __forceinline__ unsigned long long *wk_peaks()
-{
-    __shared__ unsigned long long p[2];
-    return p;
-}
-
 // the predicate's body: the adds' chain head (wall_chain, gm_device.hpp), straight or on the by-value arc or clothoid block
-struct WallCheckPayload { float4 q; long long delta; float e; int cell; };
-static_assert(GM_WALL_CHECK_CLS_PLANE == kChainPlane && GM_WALL_CHECK_CLS_BEYOND_GATE == kChainBeyondGate &&
-                  GM_WALL_CHECK_CLS_OUTSIDE == kChainOutside, "the check's first classes are wall_chain's");
 template <class Axis>
 __device__ __forceinline__ bool wall_check_point(const WallCheckArgs &a, const Axis &arc, uint32_t i, WallCheckPayload &p)
 {
@@ -56,29 +38,16 @@ __device__ __forceinline__ bool wall_check_point(const WallCheckArgs &a, const A
     if (wall_chain(p.q, lab, w, arc, [&](float s) { return (j = wall_station(w, s)) >= 0; }, [&](uint32_t k) { cls = k; }, e, jl,
                    kk)) {
         cell = (int)((uint32_t)j * w.n_sectors + kk);   // < n_stations * n_sectors <= 2^24
-        const uint32_t cn = w.table.cnt[cell];
-        long long sum = 0;
-        uint32_t lo = 0u, hi = 0u;
-        if (cn >= a.min_count) {
-            if (a.reference == GM_WALL_CHECK_ENVELOPE) { lo = w.table.lo[cell]; hi = w.table.hi[cell]; }
-            else sum = (long long)w.table.sum[cell];
-        }
-        cls = wall_check_rule(a.reference, a.min_count, a.T, sum, cn, lo, hi, e, delta);
+        cls = wall_check_cell(w.table, cell, a.reference, a.min_count, a.T, e, delta);
     }
     if (w.res) w.res[i] = e;
     if (w.cell) w.cell[i] = cell;
-    if (a.delta) a.delta[i] = delta > 2147483647ll ? 2147483647 : (delta < -2147483648ll ? (int32_t)(-2147483647 - 1) : (int32_t)delta);
+    if (a.delta) a.delta[i] = wall_check_delta32(delta);
     if (a.cls) a.cls[i] = (uint8_t)cls;
     p.e = e;
     p.cell = cell;
     p.delta = delta;
-    // (the lanes past the end of the input are not here: the ballots see the active lanes only)
-    const int lane = lane_id();
-#pragma unroll
-    for (uint32_t k = 0; k < (uint32_t)GM_WALL_CHECK_N_CLS; ++k) {
-        const unsigned long long m = __ballot(cls == k);
-        if (m && lane == (int)__builtin_ctzll(m)) atomicAdd(&wk_class_counts()[k], (uint32_t)__popcll(m));
-    }
+    wall_check_count<GM_WALL_CHECK_N_CLS>(cls, 0u);
     return cls >= (uint32_t)GM_WALL_CHECK_CLS_CHANGED_POS;
 }
 
@@ -107,41 +76,14 @@ struct WallCheckEmit {
     long long q_pos, q_neg;           // this thread's largest / smallest emitted delta
     __device__ __forceinline__ void prepare()
     {
-        if (threadIdx.x < (uint32_t)GM_WALL_CHECK_N_CLS) wk_class_counts()[threadIdx.x] = 0u;
-        if (threadIdx.x < 2u) wk_peaks()[threadIdx.x] = 0ull;
+        wall_check_prepare<GM_WALL_CHECK_N_CLS>();
         q_pos = 0; q_neg = 0;
     }
     __device__ __forceinline__ void operator()(uint32_t src, uint32_t dst, const WallCheckPred::Payload &p)
     {
-        float4 *o = reinterpret_cast<float4 *>(a.out + dst);
-        o[0] = make_float4(p.q.x, p.q.y, p.q.z, __fmul_rn((float)p.delta, 0x1p-20f));
-        o[1] = make_float4(p.e, __int_as_float(p.cell), __uint_as_float(src), a.row_is_index ? __uint_as_float(src) : p.q.w);
-        if (p.delta > q_pos) q_pos = p.delta;
-        if (p.delta < q_neg) q_neg = p.delta;
+        wall_check_row(a.out, a.row_is_index, src, dst, p, q_pos, q_neg);
     }
-    __device__ __forceinline__ void finish(uint32_t)
-    {
-        // every thread of the block is here: full waves
-        unsigned long long hp = (unsigned long long)q_pos, hn = (unsigned long long)(-q_neg);
-#pragma unroll
-        for (int o = kWave / 2; o > 0; o >>= 1) {
-            const unsigned long long op = __shfl_xor(hp, o, kWave), on = __shfl_xor(hn, o, kWave);
-            hp = hp > op ? hp : op;
-            hn = hn > on ? hn : on;
-        }
-        if (lane_id() == 0) {
-            if (hp) atomicMax(&wk_peaks()[0], hp);
-            if (hn) atomicMax(&wk_peaks()[1], hn);
-        }
-        __syncthreads();
-        if (threadIdx.x < (uint32_t)GM_WALL_CHECK_N_CLS) {
-            const uint32_t c = wk_class_counts()[threadIdx.x];
-            if (c) atomicAdd(&a.ctr[threadIdx.x], (unsigned long long)c);
-        } else if (threadIdx.x < (uint32_t)GM_WALL_CHECK_N_CLS + 2u) {
-            const unsigned long long v = wk_peaks()[threadIdx.x - GM_WALL_CHECK_N_CLS];
-            if (v) atomicMax(&a.ctr[threadIdx.x], v);
-        }
-    }
+    __device__ __forceinline__ void finish(uint32_t) { wall_check_finish<GM_WALL_CHECK_N_CLS>(a.ctr, a.ctr + GM_WALL_CHECK_N_CLS, q_pos, q_neg); }
 };
 
 void launch_wall_check(const WallCheckArgs &a, uint32_t n_cap, const ScanState &st, hipStream_t s)

@@ -21,21 +21,21 @@ namespace gm {
 constexpr int kJointSides = GM_WALL_JOINT_MAX_SIDES;
 constexpr int kJointCls = 4 * kJointSides;   // (side, class): mapped, outside, beyond_gate, plane per side
 
-// what wall_chain and wall_station read of WallArgs, of one side
-struct JointChainArgs {
-    float o[3], a[3], u[3], v[3];
-    float R, station_length, gate, sector_angle, two_pi;
-    uint32_t n_sectors, n_stations;
-    int64_t anchor;
-};
-
-__global__ __launch_bounds__(kWallThreads) void k_wall_add_joint(WallJointArgs a)
+// kMasked (gm_wall_alignment_add_*_checked; k_wall_mark sets the bits): wall_add<kMasked>'s rule (k_wall.hip) over the sides.
+// Bit i of m.words set = point i is SKIPPED, decided before its owner matters: it still runs its owner's chain (the stage
+// call's residual), but takes cell -1 and no class ahead of the run merge, and reaches neither a table nor a side's totals.
+// One wave-uniform 8-byte load of the mask per trip; the call's counts -- skipped, then the four classes summed over the
+// sides -- go to m.ctr[4 ..], beside the mask block.  The unmasked instantiation carries none of it and keeps its name and
+// its arguments.
+template <bool kMasked>
+__device__ __forceinline__ void wall_add_joint(const WallJointArgs &a, const WallMask<kMasked> m)
 {
+    constexpr int kRows = kJointCls + (kMasked ? 1 : 0);   // masked: row kJointCls counts the skipped points
     __shared__ unsigned long long s_sum[kWallCells];
     __shared__ uint32_t s_cnt[kWallCells];
     __shared__ uint32_t s_lo[kWallCells];
     __shared__ uint32_t s_hi[kWallCells];
-    __shared__ uint32_t s_cls[kJointCls][kWallThreads / kWave];
+    __shared__ uint32_t s_cls[kRows][kWallThreads / kWave];
     // the joint planes, read per point from LDS (a broadcast): 18 scalar registers less beside the sides' frames, which
     // keeps the kernel free of scalar spills
     __shared__ float s_plane[kJointSides - 1][6];
@@ -55,7 +55,8 @@ __global__ __launch_bounds__(kWallThreads) void k_wall_add_joint(WallJointArgs a
     __syncthreads();
 
     uint32_t mine = 0u;   // lane c < 4 n_sides: this wave's points of class c & 3 owned by side c >> 2
-    auto point = [&](uint64_t i, bool in, const float4 &q, uint32_t lab) {
+    auto point = [&](uint64_t i, bool in, const float4 &q, uint32_t lab, uint32_t mbit) {
+        const bool skip = kMasked && mbit;
         uint32_t owner = nside - 1u;
 #pragma unroll
         for (int jn = kJointSides - 2; jn >= 0; --jn) {   // descending: the lowest joint with d < 0 stays
@@ -94,9 +95,10 @@ __global__ __launch_bounds__(kWallThreads) void k_wall_add_joint(WallJointArgs a
             }
             if (a.element) a.element[i] = S.element;
         }
+        if (skip) { cell = -1; lidx = -1; }
         if (in && a.res) a.res[i] = e;
         if (in && a.cell) a.cell[i] = cell;
-        const uint32_t cidx = in ? owner * 4u + (kChainMapped - kcls) : 0xFFFFFFFFu;
+        const uint32_t cidx = in && !skip ? owner * 4u + (kChainMapped - kcls) : 0xFFFFFFFFu;
         for (uint32_t c = 0; c < 4u * nside; ++c) {   // (wave-uniform)
             const uint32_t v = (uint32_t)__popcll(__ballot(cidx == c));
             if ((uint32_t)lane == c) mine += v;
@@ -123,7 +125,22 @@ __global__ __launch_bounds__(kWallThreads) void k_wall_add_joint(WallJointArgs a
             }
         }
     };
-    stream_points<kWallThreads, kWallUnroll>(a.pts, a.labels, n, point);
+    uint32_t nskip = 0u;   // wave-uniform: this wave's skipped points
+    if constexpr (kMasked) {
+        // the slot's mask word rides with the slot's loads (wk: wave-uniform, < n <= 2^32): one scalar 8-byte load per wave
+        // and trip; each lane keeps its own bit alone, so no scalar pair stays live across the trip
+        stream_points_with<kWallThreads, kWallUnroll>(
+            a.pts, a.labels, n,
+            [&](uint64_t wk) {
+                const unsigned long long mw = wk < n ? m.words[__builtin_amdgcn_readfirstlane((uint32_t)(wk >> 6))] : 0ull;
+                nskip += (uint32_t)__popcll(mw);   // (no bit is set at or past n: k_wall_mark's rule)
+                return (uint32_t)((mw >> lane) & 1ull);
+            },
+            point);
+    } else {
+        stream_points<kWallThreads, kWallUnroll>(a.pts, a.labels, n,
+                                                 [&](uint64_t i, bool in, const float4 &q, uint32_t lab) { point(i, in, q, lab, 0u); });
+    }
     __syncthreads();
     // one flush per side: the touched cells of its window, lane <-> cell.  A window lies inside its map.
 #pragma unroll 1
@@ -139,17 +156,38 @@ __global__ __launch_bounds__(kWallThreads) void k_wall_add_joint(WallJointArgs a
         }
     }
     // class counts: one atomic per (side, class) and block, to the owner's totals
-    if (lane < kJointCls) s_cls[lane][threadIdx.x / kWave] = mine;
+    if (kMasked && lane == kJointCls) mine = nskip;
+    if (lane < kRows) s_cls[lane][threadIdx.x / kWave] = mine;
     block_row_sums(s_cls, [&](uint32_t k, unsigned long long v) {
 #pragma unroll 1
         for (uint32_t s = 0; s < nside; ++s)
             if (v && (k >> 2) == s) atomicAdd(&a.side[s].table.totals[k & 3u], v);
+        if constexpr (kMasked) {   // skipped | mapped, outside, beyond_gate, plane
+            if (v) atomicAdd(&m.ctr[k == (uint32_t)kJointCls ? 4u : 5u + (k & 3u)], v);
+        }
     });
+}
+
+__global__ __launch_bounds__(kWallThreads) void k_wall_add_joint(WallJointArgs a)
+{
+    wall_add_joint<false>(a, WallMask<false>());
+}
+__global__ __launch_bounds__(kWallThreads) void k_wall_add_joint_masked(WallJointArgs a, WallMask<true> m)
+{
+    wall_add_joint<true>(a, m);
 }
 
 void launch_wall_add_joint(const WallJointArgs &a, uint32_t n_cap, uint32_t points_per_block, hipStream_t s)
 {
     hipLaunchKernelGGL(k_wall_add_joint, dim3(wall_blocks(n_cap, points_per_block)), dim3(kWallThreads), 0, s, a);
+}
+void launch_wall_add_joint_masked(const WallJointArgs &a, const unsigned long long *mask, unsigned long long *ctr, uint32_t n_cap,
+                                  uint32_t points_per_block, hipStream_t s)
+{
+    WallMask<true> m;
+    m.words = mask;
+    m.ctr = ctr;
+    hipLaunchKernelGGL(k_wall_add_joint_masked, dim3(wall_blocks(n_cap, points_per_block)), dim3(kWallThreads), 0, s, a, m);
 }
 
 }  // namespace gm

@@ -413,6 +413,35 @@ gm_wall_alignment_locate_info Processor::locateWallAlignment(const double pose[1
     return info;
 }
 
+std::vector<gm_wall_check_point> Processor::checkWallAlignment(const double pose[12], const gm_wall_check_params &prm,
+                                                               gm_wall_alignment_check_info *info, gm_wall_alignment_add_info *plan)
+{
+    if (!alignment_) throw Error(GM_ERR_NOT_READY, "checkWallAlignment: createWallAlignment first");
+    if (newest_slot_ < 0) throw Error(GM_ERR_NOT_READY, "checkWallAlignment: no frame yet");
+    const unsigned slot = (unsigned)newest_slot_;
+    check(gm_wall_alignment_check_frame(alignment_, ctx_, slot, pose, &prm, plan), "checkWallAlignment");
+    gm_wall_alignment_check_info local;
+    gm_wall_alignment_check_info *ip = info ? info : &local;
+    uint32_t count = 0;
+    check(gm_wall_alignment_get_check(alignment_, slot, ip, 0, 0, &count), "checkWallAlignment");
+    std::vector<gm_wall_check_point> points(count);
+    if (count) check(gm_wall_alignment_get_check(alignment_, slot, ip, &points[0], count, &count), "checkWallAlignment");
+    points.resize(count);
+    return points;
+}
+
+gm_wall_alignment_add_info Processor::addToWallAlignmentChecked(const double pose[12], const gm_wall_add_checked_params &prm,
+                                                                gm_wall_add_checked_info *info)
+{
+    if (!alignment_) throw Error(GM_ERR_NOT_READY, "addToWallAlignmentChecked: createWallAlignment first");
+    if (newest_slot_ < 0) throw Error(GM_ERR_NOT_READY, "addToWallAlignmentChecked: no frame yet");
+    const unsigned slot = (unsigned)newest_slot_;
+    gm_wall_alignment_add_info plan;
+    check(gm_wall_alignment_add_frame_checked(alignment_, ctx_, slot, pose, &prm, &plan), "addToWallAlignmentChecked");
+    if (info) check(gm_wall_alignment_get_add_checked(alignment_, slot, info), "addToWallAlignmentChecked");
+    return plan;
+}
+
 gm_wall_add_info Processor::addToWallMap(const double pose[12])
 {
     if (!wall_) throw Error(GM_ERR_NOT_READY, "addToWallMap: createWallMap first");

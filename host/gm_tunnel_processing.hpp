@@ -235,8 +235,20 @@ public:
     // corrects the newest frame's pose against the alignment (gm_wall_alignment_locate_frame + gm_wall_alignment_get_locate):
     // locateWallMap on straight, arc and clothoid elements and across their joints; the element maps are not changed.
     // info.pose is the corrected pose (NaN when info.status & GM_LOCATE_FAILED_MASK).  The order per frame on an alignment:
-    // locateWallAlignment, the check on the element map the piece falls in, addToWallAlignment with the located pose.
+    // locateWallAlignment, checkWallAlignment with the located pose, addToWallAlignmentChecked with it.
     gm_wall_alignment_locate_info locateWallAlignment(const double pose[12], const gm_wall_locate_params &prm);
+    // the changed points of the newest frame against the alignment under pose (gm_wall_alignment_check_frame +
+    // gm_wall_alignment_get_check): every point against the map of the element that owns it, ascending by index; a row's
+    // cell holds side << 24 | cell (GM_WALL_ROW_SIDE, GM_WALL_ROW_CELL; side indexes plan->side_element).  The element maps
+    // are not changed.  info and plan, when given, receive the call's counts and the plan of its sides.
+    std::vector<gm_wall_check_point> checkWallAlignment(const double pose[12], const gm_wall_check_params &prm,
+                                                        gm_wall_alignment_check_info *info = nullptr,
+                                                        gm_wall_alignment_add_info *plan = nullptr);
+    // addToWallAlignment less the points the last checkWallAlignment of the newest frame selected
+    // (gm_wall_alignment_add_frame_checked + gm_wall_alignment_get_add_checked).  info, when given, receives the call's counts
+    // (and the call waits for them).  GM_ERR_NOT_READY without a check of this frame through the alignment.
+    gm_wall_alignment_add_info addToWallAlignmentChecked(const double pose[12], const gm_wall_add_checked_params &prm,
+                                                         gm_wall_add_checked_info *info = nullptr);
     gm_wall_alignment *wallAlignment() { return alignment_; }
 
     gm_ctx *ctx() { return ctx_; }

@@ -2025,8 +2025,9 @@ gm_status gm_wall_clothoid_point(const gm_wall_params *params, const gm_wall_clo
  * and every point is classed exactly once.  The LDS table's GM_SURF_MAX_CELLS cells are dealt to the sides in order (a
  * side's window: the stations of its own add's window that lie in the element, cut to what is left); a mapped point outside
  * its side's window goes to the map directly, which affects speed only.
- * Out of scope: the checked add, and check and align through the alignment (they remain calls on an element map,
- * gm_wall_alignment_map); element maps of different grids; closed loops.  The locate is gm_wall_alignment_locate_* below. */
+ * Out of scope: align (chainage and roll) and check objects through the alignment (they remain calls on an element map,
+ * gm_wall_alignment_map); element maps of different grids; closed loops.  The locate is gm_wall_alignment_locate_*, the
+ * check and the checked add gm_wall_alignment_check_* and gm_wall_alignment_add_*_checked below. */
 #define GM_WALL_ALIGNMENT_MAX_ELEMENTS 256
 #define GM_WALL_JOINT_MAX_SIDES 4
 enum { GM_WALL_ELEMENT_STRAIGHT = 0, GM_WALL_ELEMENT_ARC = 1, GM_WALL_ELEMENT_CLOTHOID = 2 };
@@ -2126,8 +2127,9 @@ gm_status gm_wall_alignment_info(gm_wall_alignment *alignment, gm_wall_alignment
  * gm_wall_map_locate_* on the alignment: the same four degrees of freedom, the same three gated Gauss-Newton passes, the
  * same parameters (gm_wall_locate_params, gm_wall_locate_check_params), statuses (GM_LOCATE_*) and GM_FIT_STEP_BOUND, on
  * straight, arc and clothoid elements and across their joints.  A single-element alignment is the locate of a lone arc or
- * clothoid map (gm_wall_map_locate_* keeps refusing those).  Per frame on an alignment: locate here -> check on the element
- * map the piece falls in with the corrected pose -> gm_wall_alignment_add_frame with it.  One operation per statement.
+ * clothoid map (gm_wall_map_locate_* keeps refusing those).  Per frame on an alignment: locate here ->
+ * gm_wall_alignment_check_frame with the corrected pose -> gm_wall_alignment_add_frame_checked with it.  One operation per
+ * statement.
  *   plan          host, fp64: gm_wall_alignment_add_plan's, unchanged: the sensor's ("home") element, the sides within the
  *                 reach, each side's own per-add frame, the joint planes.  More than GM_WALL_JOINT_MAX_SIDES sides:
  *                 GM_ERR_UNSUPPORTED, nothing is enqueued.  ONE side that is a straight element: the locate IS
@@ -2187,8 +2189,8 @@ gm_status gm_wall_alignment_info(gm_wall_alignment *alignment, gm_wall_alignment
  * atomics, no host round trip between the passes, one pending result per (alignment, slot).  Scratch per (alignment,
  * slot) -- the working state, 96 KiB of partial rows, a pinned copy of the result -- and the stage call's three per-point
  * arrays are allocated on first use, kept grow-only and freed with the alignment; an alignment that never locates across
- * a joint or on a curved element allocates nothing.  Out of scope: chainage and roll (they stay the caller's), align and
- * check through the alignment. */
+ * a joint or on a curved element allocates nothing.  Out of scope: chainage and roll (they stay the caller's) and align
+ * through the alignment. */
 typedef struct gm_wall_alignment_locate_pass {   /* 376 bytes; the first 112 are gm_wall_locate_pass */
     float    o[3], a[3], u[3], v[3];   /* the pass's state c, d, u', v' in SENSOR coordinates (fp32, as the points saw it) */
     float    gate;                     /* g_k */
@@ -2248,6 +2250,91 @@ gm_status gm_wall_alignment_get_locate(gm_wall_alignment *alignment, uint32_t sl
 gm_status gm_wall_alignment_locate_points(gm_wall_alignment *alignment, const float *xyz, uint32_t n, const uint8_t *labels,
                                           const double pose[12], const gm_wall_locate_params *prm,
                                           gm_wall_alignment_locate_info *info, float *residual, int32_t *cell, int32_t *element);
+
+/* ---- a frame's changed points against a wall alignment, and the add less them (gm_wall_alignment_check_*,
+ * gm_wall_alignment_add_*_checked) ------------------------------------------------------------------------------------------
+ * gm_wall_map_check_* and gm_wall_map_add_*_checked on the alignment: the same parameters (gm_wall_check_params,
+ * gm_wall_add_checked_params), the same seven classes, the same 32-byte row, across the joints.  Per frame on an alignment:
+ * gm_wall_alignment_locate_frame -> gm_wall_alignment_check_frame with the located pose -> gm_wall_alignment_add_frame_checked.
+ *   per check     host, fp64.  The plan is gm_wall_alignment_add_plan's for this pose, unchanged: the sensor's element, the
+ *                 sides within the reach L, the fp32 joint planes Jo', aJ'; it is reported in a gm_wall_alignment_add_info.
+ *                 Each side's per-add frame is the one its own map's CHECK computes: the add's frame, except that the gate
+ *                 is the check's parameter rounded to fp32 once.  More than GM_WALL_JOINT_MAX_SIDES sides:
+ *                 GM_ERR_UNSUPPORTED, nothing is enqueued.  Parameters and their refusals are gm_wall_check_params'.
+ *   per point     device, fp32.  The owner by the add's rule:  q = p - Jo'_i;  d_i = fma(qx, ax, fma(qy, ay, qz az)) over
+ *                 the joints in ascending order; the side before the first d_i < 0, else the last side.  The point runs its
+ *                 owner's chain alone (straight, arc or clothoid, as gm_wall_map_check_* of that map runs it) under the
+ *                 check's gate, and a mapped point takes the check's integer rule against the OWNER's table: the count
+ *                 first, then sum or keys only for a usable cell.  Every valid point is in exactly one of the seven
+ *                 classes, and the class counts are kept per side.
+ *   rows          gm_wall_check_point, ascending by index in the valid cloud, from the one launch.  cell holds
+ *                 side << 24 | cell: the low 24 bits are the cell in the owner's map (a cell is < 2^24), side indexes
+ *                 side_element[] of the check's plan (GM_WALL_ROW_SIDE, GM_WALL_ROW_CELL).  With one side this is the
+ *                 element map's row, byte for byte.
+ *   one side      the check IS that element map's gm_wall_map_check_frame / _check_points: the same launch, the shared
+ *                 fields byte for byte; gm_wall_alignment_get_check then reads that map's result.
+ *   ordering      no map is changed.  The check sees every add enqueued before it on any slot of every side's map, through
+ *                 the alignment or through an element map, and none enqueued after: a later add on any slot waits for it
+ *                 through the alignment's pending results, as for a locate.
+ *   checked add   gm_wall_map_add_*_checked's parameters, row classes (rejected, selected, kept) and
+ *                 gm_wall_add_checked_info, unchanged.  A row is read for delta and index only: the side bits of cell do not
+ *                 matter.  The add plan is computed for the add's own pose, which need not be the check's; its sides need
+ *                 not be the check's sides.  Point i is skipped iff a selected row names it, decided before ownership;
+ *                 every element map then changes exactly as gm_wall_map_add_points of the sub-cloud it owns with the
+ *                 skipped indices deleted, and with no selected row the result is gm_wall_alignment_add_frame's.  `frames`
+ *                 counts once per side; skipped points enter no total.  The info's status is the OR of the sides'.
+ * The frame call takes the rows of the last check enqueued THROUGH THE ALIGNMENT on that slot, wherever they are staged (a
+ * one-side check: the element map's buffer), and returns GM_ERR_NOT_READY when there is none for the frame the slot now
+ * holds, or when a check on that element map itself has since replaced a one-side check's rows.  Scratch per (alignment,
+ * slot) -- 32 B per point of staging, the scan records, the counter block, one mask bit per point, pinned copies of the
+ * results -- is allocated by the first call that is not an element map's own, kept grow-only and freed with the alignment;
+ * an alignment that never checks allocates nothing. */
+#define GM_WALL_ROW_SIDE(cell) ((uint32_t)(cell) >> 24)
+#define GM_WALL_ROW_CELL(cell) ((uint32_t)(cell) & 0xFFFFFFu)
+typedef struct gm_wall_alignment_check_info {   /* 184 bytes; filled by gm_wall_alignment_get_check / _check_points */
+    uint32_t struct_size;      /* = sizeof(gm_wall_alignment_check_info), filled by the library */
+    uint32_t status;           /* GM_SURF_OK or GM_SURF_UP_FALLBACK: the OR of the sides' design frames' */
+    int64_t  threshold_q;      /* T */
+    uint32_t n_points;         /* the valid cloud's points = the sum of the seven classes below */
+    uint32_t plane, beyond_gate, outside, unsurveyed, unchanged, changed_pos, changed_neg;   /* summed over the sides */
+    int64_t  peak_pos, peak_neg;   /* 2^-20 m over all sides; 0 when the class is empty */
+    uint32_t n_sides;          /* of the check's plan */
+    uint32_t reserved;         /* 0 */
+    uint32_t side_class[GM_WALL_JOINT_MAX_SIDES][GM_WALL_CHECK_N_CLS];   /* GM_WALL_CHECK_CLS_* order; 0 from n_sides on */
+} gm_wall_alignment_check_info;
+
+/* gm_wall_map_check_frame on the alignment (prm NULL: the defaults).  plan may be NULL.  GM_ERR_INVALID_ARG: NULL, a foreign
+ * context, a bad slot, bad parameters, a refused pose; GM_ERR_NOT_READY: the slot holds no frame; GM_ERR_UNSUPPORTED: too
+ * many sides. */
+gm_status gm_wall_alignment_check_frame(gm_wall_alignment *alignment, gm_ctx *ctx, uint32_t slot, const double pose[12],
+                                        const gm_wall_check_params *prm, gm_wall_alignment_add_info *plan);
+/* The result of the last check enqueued on (alignment, slot), as gm_wall_map_get_check: waits for that check only; info,
+ * n_out may be NULL; points NULL with capacity 0 is a count query; GM_ERR_CAPACITY writes no row.  GM_ERR_NOT_READY: none
+ * was enqueued; GM_ERR_INVALID_ARG: NULL, a bad slot.  gm_wall_alignment_check_points counts as a check on slot 0. */
+gm_status gm_wall_alignment_get_check(gm_wall_alignment *alignment, uint32_t slot, gm_wall_alignment_check_info *info,
+                                      gm_wall_check_point *points, uint32_t capacity, uint32_t *n_out);
+/* The same kernel as one blocking stage call on host buffers (slot 0).  The per-point outputs may each be NULL: residual
+ * (e, NaN for plane points), cell (relative to the owner's map, -1 if unmapped), delta (saturated), cls
+ * (GM_WALL_CHECK_CLS_*), element (the owner's element index, set for every point).  row = index. */
+gm_status gm_wall_alignment_check_points(gm_wall_alignment *alignment, const float *xyz, uint32_t n, const uint8_t *labels,
+                                         const double pose[12], const gm_wall_check_params *prm, gm_wall_alignment_add_info *plan,
+                                         gm_wall_alignment_check_info *info, gm_wall_check_point *points, uint32_t capacity,
+                                         uint32_t *n_out, float *residual, int32_t *cell, int32_t *delta, uint8_t *cls,
+                                         int32_t *element);
+/* gm_wall_alignment_add_frame less the points that the last check on (alignment, slot) selected (prm NULL: the defaults).
+ * Errors as gm_wall_alignment_add_frame and gm_wall_map_add_frame_checked.  plan may be NULL. */
+gm_status gm_wall_alignment_add_frame_checked(gm_wall_alignment *alignment, gm_ctx *ctx, uint32_t slot, const double pose[12],
+                                              const gm_wall_add_checked_params *prm, gm_wall_alignment_add_info *plan);
+/* The counts of the last checked add enqueued on (alignment, slot); waits for that call only.  GM_ERR_NOT_READY: none was
+ * enqueued; GM_ERR_INVALID_ARG: NULL, a bad slot.  gm_wall_alignment_add_points_checked does not count as one. */
+gm_status gm_wall_alignment_get_add_checked(gm_wall_alignment *alignment, uint32_t slot, gm_wall_add_checked_info *info);
+/* The same kernels as one blocking stage call on host buffers (slot 0).  rows: n_rows gm_wall_check_points in any order,
+ * duplicates allowed (NULL with n_rows 0).  plan, info, residual, cell, element may be NULL; residual / cell of a skipped
+ * point are the e of its owner's chain and -1. */
+gm_status gm_wall_alignment_add_points_checked(gm_wall_alignment *alignment, const float *xyz, uint32_t n, const uint8_t *labels,
+                                               const double pose[12], const gm_wall_add_checked_params *prm,
+                                               const gm_wall_check_point *rows, uint32_t n_rows, gm_wall_alignment_add_info *plan,
+                                               gm_wall_add_checked_info *info, float *residual, int32_t *cell, int32_t *element);
 
 /* "Compressed map" record of a completed slot.  The reference defines no such
  * output; this is a build-defined format: header, primitive records,
