@@ -331,37 +331,6 @@ size_t wall_table_bytes(uint64_t ncell);
 void launch_wall_add(const WallArgs &a, uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
 void launch_wall_add_arc(const WallArgs &a, const WallArc &arc, uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
 void launch_wall_add_clothoid(const WallArgs &a, const WallClothoid &cl, uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
-// k_wall_joint.hip (gm_wall_alignment_add_*): one launch for a frame that straddles joints of an alignment.  Each point is
-// owned by one side (an element map) and runs that side's chain alone.
-struct WallJointSide {
-    int64_t anchor;            // j_f of this side's own add
-    float o[3], a[3], u[3], v[3];   // its frame-local map frame, as WallArgs
-    WallClothoid ax;           // its axis block (an arc side fills ax.arc alone, a straight side nothing)
-    WallTable table;
-    uint32_t n_stations;
-    int32_t win_first;         // its LDS window, as WallArgs: whole stations of the element
-    uint32_t win_stations;
-    uint32_t lds_first;        // the window's first cell in the block's LDS table
-    int32_t axis;              // kAxisStraight, kAxisArc, kAxisClothoid
-    int32_t element;           // the element's index in the alignment
-};
-struct WallJointArgs {
-    const float4 *pts;
-    const uint8_t *labels;     // nullptr: no point is plane
-    const uint32_t *n_ptr;     // device point count (nullptr: n_host)
-    uint32_t n_host;
-    uint32_t n_sides;          // 2 .. GM_WALL_JOINT_MAX_SIDES
-    uint32_t n_sectors;
-    uint32_t lds_cells;        // the cells of the LDS table dealt to the sides' windows, <= GM_SURF_MAX_CELLS
-    float R, station_length, gate, sector_angle, two_pi;   // one grid for every element
-    float jo[GM_WALL_JOINT_MAX_SIDES - 1][3];   // Jo' of the joint between side i and side i + 1
-    float ja[GM_WALL_JOINT_MAX_SIDES - 1][3];   // aJ'
-    float *res;                // stage call only (nullptr in the frame path)
-    int32_t *cell;
-    int32_t *element;
-    WallJointSide side[GM_WALL_JOINT_MAX_SIDES];
-};
-void launch_wall_add_joint(const WallJointArgs &a, uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
 // k_wall_add_checked.hip (gm_wall_map_add_*_checked): mark the selected rows' points in a bit mask, then k_wall_add's masked
 // instantiation.  u64 words of the call's counter block: rows_neg, rows_pos, rows_kept, rows_rejected | skipped, mapped,
 // outside, beyond_gate, plane | n_rows, n_points, pad
@@ -387,10 +356,6 @@ void launch_wall_add_arc_masked(const WallArgs &a, const WallArc &arc, const uns
                                 uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
 void launch_wall_add_clothoid_masked(const WallArgs &a, const WallClothoid &cl, const unsigned long long *mask, unsigned long long *ctr,
                                      uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
-// k_wall_add_joint over the points whose mask bit is clear (gm_wall_alignment_add_*_checked): skipped and the four point
-// classes, summed over the sides, also go to ctr[4 .. 8]
-void launch_wall_add_joint_masked(const WallJointArgs &a, const unsigned long long *mask, unsigned long long *ctr, uint32_t n_cap,
-                                  uint32_t points_per_block, hipStream_t s);
 // the class of one row: 0 selected negative, 1 selected positive, 2 kept, 3 rejected (delta_bits: the row's delta)
 __host__ __device__ inline uint32_t wall_mark_class(uint32_t delta_bits, long long dq, uint32_t index, uint32_t n_points,
                                                     uint32_t skip, long long S)
@@ -507,43 +472,6 @@ struct WallCheckArgs {
 void launch_wall_check(const WallCheckArgs &a, uint32_t n_cap, const ScanState &st, hipStream_t s);
 void launch_wall_check_arc(const WallCheckArgs &a, const WallArc &arc, uint32_t n_cap, const ScanState &st, hipStream_t s);
 void launch_wall_check_clothoid(const WallCheckArgs &a, const WallClothoid &cl, uint32_t n_cap, const ScanState &st, hipStream_t s);
-// k_wall_check_joint.hip (gm_wall_alignment_check_*): one k_compact launch over the sides of an alignment's plan, every
-// point on its owner's chain and against its owner's table.  u64 words: the first kWallCheckCounters as above (the seven
-// summed classes are left to the host), then the classes per side [GM_WALL_JOINT_MAX_SIDES][GM_WALL_CHECK_N_CLS].
-constexpr int kWallCheckJointCounters = kWallCheckCounters + GM_WALL_JOINT_MAX_SIDES * GM_WALL_CHECK_N_CLS;
-struct WallCheckJointSide {
-    int64_t anchor;            // j_f of this side's own check
-    float o[3], a[3], u[3], v[3];   // its frame-local map frame, as WallArgs
-    WallClothoid ax;           // its axis block (an arc side fills ax.arc alone, a straight side nothing)
-    WallTable table;
-    uint32_t n_stations;
-    int32_t axis;              // kAxisStraight, kAxisArc, kAxisClothoid
-    int32_t element;           // the element's index in the alignment
-};
-struct WallCheckJointArgs {
-    const float4 *pts;
-    const uint8_t *labels;     // nullptr: no point is plane
-    const uint32_t *n_ptr;     // device point count (nullptr: n_host)
-    uint32_t n_host;
-    uint32_t n_sides;          // 2 .. GM_WALL_JOINT_MAX_SIDES
-    uint32_t n_sectors, reference, min_count;
-    uint32_t row_is_index;     // stage call: row = index
-    uint32_t outputs;          // set by the launch: one of the five per-point outputs below is wanted
-    uint32_t pad;
-    long long T;
-    float R, station_length, gate, sector_angle, two_pi;   // one grid for every element; gate is the check's
-    float jo[GM_WALL_JOINT_MAX_SIDES - 1][3];   // Jo' of the joint between side i and side i + 1
-    float ja[GM_WALL_JOINT_MAX_SIDES - 1][3];   // aJ'
-    gm_wall_check_point *out;  // staging, >= n_cap rows
-    unsigned long long *ctr;   // [kWallCheckJointCounters], zeroed by the caller on the same stream
-    float *res;                // stage call only (nullptr in the frame path)
-    int32_t *cell;
-    int32_t *delta;
-    uint8_t *cls;
-    int32_t *element;
-    WallCheckJointSide side[GM_WALL_JOINT_MAX_SIDES];
-};
-void launch_wall_check_joint(const WallCheckJointArgs &a, uint32_t n_cap, const ScanState &st, hipStream_t s);
 // the rule's integers, shared by the kernel and gm_wall_check_classify
 __host__ __device__ inline long long wall_check_fix(float e)   // (int64) rint(e 2^20), saturating at int32, 0 for a NaN
 {
@@ -592,72 +520,6 @@ struct WallLocateArgs {
     uint32_t *ticket;          // 0 between launches
 };
 void launch_wall_locate(const WallLocateArgs &a, hipStream_t s);   // the three passes
-// k_wall_locate_joint.hip (gm_wall_alignment_locate_*): k_wall_locate over the sides of an alignment's plan, every point on
-// its owner's chain.  The fp32 blocks of a pass -- every side's four vectors, the joint planes -- are the images of the
-// attached vectors (h: home-section coordinates, fp64) under the pass's state.
-struct WallLocateJointBlocks {
-    float side[GM_WALL_JOINT_MAX_SIDES][12];        // o', a', n', b' (straight: o', a', u', v')
-    float jo[GM_WALL_JOINT_MAX_SIDES - 1][3];       // Jo'
-    float ja[GM_WALL_JOINT_MAX_SIDES - 1][3];       // aJ'
-};
-struct WallLocateJointWork {
-    double c[3], d[3], u[3], v[3];   // the state in sensor coordinates, fp64
-    double lateral[2], tilt[2];
-    double last_step;
-    uint32_t status, passes, n_points, pad;
-    WallLocateJointBlocks next;      // the blocks of the pass to come, written by the solve of the pass before
-    gm_wall_alignment_locate_pass pass[GM_LOCATE_PASSES];
-};
-struct WallLocateJointSide {
-    WallTable table;
-    int64_t anchor;            // j_f of this side's own add
-    uint32_t n_stations;
-    int32_t axis;              // kAxisStraight, kAxisArc, kAxisClothoid
-    int32_t element;
-    float kappa, rate, un, ub, vn, vb;
-};
-struct WallLocateJointArgs {
-    const float4 *pts;
-    const uint8_t *labels;     // nullptr: no point is plane
-    const uint32_t *n_ptr;     // device point count (nullptr: n_host)
-    uint32_t n_host;
-    uint32_t n_sides;          // 1 .. GM_WALL_JOINT_MAX_SIDES
-    uint32_t n_sectors, reference, min_count;
-    float R, station_length, sector_angle, two_pi;
-    double gate;               // of pass 0
-    double c0[3], d0[3], u0[3], v0[3], s0;   // the start, fp64, not rounded
-    WallLocateJointBlocks first;             // the blocks of pass 0
-    double h_side[GM_WALL_JOINT_MAX_SIDES][12];      // the attached vectors: a point's h, then three directions' per side
-    double h_joint[GM_WALL_JOINT_MAX_SIDES - 1][6];  // h of J, h of aJ
-    WallLocateJointSide side[GM_WALL_JOINT_MAX_SIDES];
-    WallLocateJointWork *work;
-    double *partial;           // [kFitBlocks][kFitRowLen]
-    uint32_t *ticket;          // 0 between launches
-    float *res;                // stage call only: all three or none (nullptr in the frame path)
-    int32_t *cell;
-    int32_t *element;
-};
-void launch_wall_locate_joint(const WallLocateJointArgs &a, hipStream_t s);   // the three passes
-// the image of an attached vector h under the state (c, d, u, v): a point or a direction, rounded to fp32 once
-__host__ __device__ inline void wall_locate_image(const double *h, bool point, const double *c, const double *d, const double *u,
-                                                  const double *v, float *out)
-{
-    for (int k = 0; k < 3; ++k) {
-        const double r = (h[0] * d[k] + h[1] * u[k]) + h[2] * v[k];
-        out[k] = (float)(point ? c[k] + r : r);
-    }
-}
-// every block of a pass: the images of a's attached vectors under the state
-__host__ __device__ inline void wall_locate_blocks(const WallLocateJointArgs &a, const double *c, const double *d, const double *u,
-                                                   const double *v, WallLocateJointBlocks &b)
-{
-    for (int s = 0; s < GM_WALL_JOINT_MAX_SIDES; ++s)
-        for (int q = 0; q < 4; ++q) wall_locate_image(&a.h_side[s][3 * q], q == 0, c, d, u, v, &b.side[s][3 * q]);
-    for (int j = 0; j < GM_WALL_JOINT_MAX_SIDES - 1; ++j) {
-        wall_locate_image(&a.h_joint[j][0], true, c, d, u, v, b.jo[j]);
-        wall_locate_image(&a.h_joint[j][3], false, c, d, u, v, b.ja[j]);
-    }
-}
 // k_wall_align.hip (gm_wall_map_align_*): bin -> values -> score
 constexpr int kWallAlignCounters = 8;   // u64: plane, beyond_gate, outside_patch, binned, n_points, patch_cells_usable, pad
 constexpr int32_t kWallAlignNone = -2147483647 - 1;   // the value of an unusable cell in both int32 images

@@ -139,20 +139,41 @@ gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info
     return GM_OK;
 }
 
+gm_status PointOutputs::reserve(gm_ctx *ctx, uint64_t n, uint32_t want, uint32_t hold)
+{
+    wanted = want;
+    if (hold & kPtRes) GMW_HIP(ctx, res.reserve(n));
+    if (hold & kPtCell) GMW_HIP(ctx, cell.reserve(n));
+    if (hold & kPtDelta) GMW_HIP(ctx, delta.reserve(n));
+    if (hold & kPtCls) GMW_HIP(ctx, cls.reserve(n));
+    if (hold & kPtElement) GMW_HIP(ctx, element.reserve(n));
+    return GM_OK;
+}
+
+gm_status PointOutputs::copy_back(gm_ctx *ctx, hipStream_t s, uint32_t n, float *h_res, int32_t *h_cell, int32_t *h_delta,
+                                  uint8_t *h_cls, int32_t *h_element) const
+{
+    if (h_res && n) GMW_HIP(ctx, hipMemcpyAsync(h_res, res.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    if (h_cell && n) GMW_HIP(ctx, hipMemcpyAsync(h_cell, cell.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    if (h_delta && n) GMW_HIP(ctx, hipMemcpyAsync(h_delta, delta.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    if (h_cls && n) GMW_HIP(ctx, hipMemcpyAsync(h_cls, cls.p, (size_t)n, hipMemcpyDeviceToHost, s));
+    if (h_element && n) GMW_HIP(ctx, hipMemcpyAsync(h_element, element.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    return GM_OK;
+}
+
 gm_status StageCall::open()
 {
     gm_ctx *ctx = map->ctx;
     GMW_OK(gm_begin_stage(ctx, sl));
     GMW_OK(gm_ensure_capacity(ctx, *sl, n ? n : 1u, (size_t)(n ? n : 1u) * 16, true));
-    if (residual || cell) {
-        GMW_HIP(ctx, map->pt_res.reserve(n));
-        GMW_HIP(ctx, map->pt_cell.reserve(n));
+    const uint32_t want = (residual ? kPtRes : 0u) | (cell ? kPtCell : 0u) | (delta ? kPtDelta : 0u) | (cls ? kPtCls : 0u) |
+                          (element ? kPtElement : 0u);
+    uint32_t hold = want;
+    if (&out == &map->pt) {   // a map's own call holds residual with cell and delta with cls
+        if (want & (kPtRes | kPtCell)) hold |= kPtRes | kPtCell;
+        if (want & (kPtDelta | kPtCls)) hold |= kPtDelta | kPtCls;
     }
-    if (delta || cls) {
-        GMW_HIP(ctx, map->ck_delta.reserve(n));
-        GMW_HIP(ctx, map->ck_cls.reserve(n));
-    }
-    return GM_OK;
+    return out.reserve(ctx, n, want, hold);
 }
 
 gm_status StageCall::upload(const float *xyz, const uint8_t *labels, WallArgs &w)
@@ -164,18 +185,15 @@ gm_status StageCall::upload(const float *xyz, const uint8_t *labels, WallArgs &w
     w.labels = labels ? sl->labels : nullptr;
     w.n_ptr = nullptr;
     w.n_host = n;
-    w.res = residual ? map->pt_res.p : nullptr;
-    w.cell = cell ? map->pt_cell.p : nullptr;
+    w.res = out.dev_res();
+    w.cell = out.dev_cell();
     return GM_OK;
 }
 
 gm_status StageCall::close()
 {
     gm_ctx *ctx = map->ctx;
-    if (residual && n) GMW_HIP(ctx, hipMemcpyAsync(residual, map->pt_res.p, (size_t)n * 4, hipMemcpyDeviceToHost, sl->stream));
-    if (cell && n) GMW_HIP(ctx, hipMemcpyAsync(cell, map->pt_cell.p, (size_t)n * 4, hipMemcpyDeviceToHost, sl->stream));
-    if (delta && n) GMW_HIP(ctx, hipMemcpyAsync(delta, map->ck_delta.p, (size_t)n * 4, hipMemcpyDeviceToHost, sl->stream));
-    if (cls && n) GMW_HIP(ctx, hipMemcpyAsync(cls, map->ck_cls.p, (size_t)n, hipMemcpyDeviceToHost, sl->stream));
+    GMW_OK(out.copy_back(ctx, sl->stream, n, residual, cell, delta, cls, element));
     GMW_HIP(ctx, hipStreamSynchronize(sl->stream));
     return GM_OK;
 }
@@ -630,7 +648,7 @@ gm_status gm_wall_map_add_points(gm_wall_map *map, const float *xyz, uint32_t n,
     WallArgs w;
     WallClothoid ax;
     GMW_OK(add_frame_args(map, pose, add_info, w, nullptr, &ax));
-    StageCall sc{map, n, residual, cell, nullptr, nullptr};
+    StageCall sc{map, n, map->pt, residual, cell, nullptr, nullptr, nullptr};
     GMW_OK(sc.open());
     GMW_OK(sc.upload(xyz, labels, w));
     hipStream_t s = sc.sl->stream;

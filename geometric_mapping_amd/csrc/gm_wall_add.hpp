@@ -32,12 +32,4 @@ struct WallMask<true> {
     unsigned long long *ctr;           // [kWallAddCheckedCounters]
 };
 
-// what wall_chain and wall_station read of WallArgs, of one side of a joint kernel (k_wall_add_joint, k_wall_check_joint)
-struct JointChainArgs {
-    float o[3], a[3], u[3], v[3];
-    float R, station_length, gate, sector_angle, two_pi;
-    uint32_t n_sectors, n_stations;
-    int64_t anchor;
-};
-
 }  // namespace gm

@@ -130,7 +130,7 @@ gm_status gm_wall_map_add_points_checked(gm_wall_map *map, const float *xyz, uin
     WallArgs w;
     WallClothoid ax;
     GMW_OK(add_frame_args(map, pose, add_info, w, nullptr, &ax));
-    StageCall sc{map, n, residual, cell, nullptr, nullptr};
+    StageCall sc{map, n, map->pt, residual, cell, nullptr, nullptr, nullptr};
     GMW_OK(sc.open());
     GMW_OK(sc.upload(xyz, labels, w));
     hipStream_t s = sc.sl->stream;

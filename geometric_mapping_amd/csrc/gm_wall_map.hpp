@@ -273,6 +273,27 @@ struct WallAlignSlot {
     uint32_t n_shifts = 0;                  // (2A + 1)(2B + 1)
 };
 
+// The per-point outputs of a stage call, device side: the one owner of their buffers (a map's, an alignment's) and the one
+// path a call's wanted ones take -- reserved ahead of the launch, handed to the kernel, copied back behind it.
+enum : uint32_t { kPtRes = 1u, kPtCell = 2u, kPtDelta = 4u, kPtCls = 8u, kPtElement = 16u };
+struct PointOutputs {
+    DevArray<float> res;
+    DevArray<int32_t> cell, delta, element;
+    DevArray<uint8_t> cls;
+    uint32_t wanted = 0;   // kPt* bits of the call in progress: the outputs its kernel writes
+    // n points of every output in `hold` (which includes `want`); the kernel is to write those in `want`
+    gm_status reserve(gm_ctx *ctx, uint64_t n, uint32_t want, uint32_t hold);
+    // the kernel's pointers: nullptr for an output that is not wanted
+    float *dev_res() const { return (wanted & kPtRes) ? res.p : nullptr; }
+    int32_t *dev_cell() const { return (wanted & kPtCell) ? cell.p : nullptr; }
+    int32_t *dev_delta() const { return (wanted & kPtDelta) ? delta.p : nullptr; }
+    uint8_t *dev_cls() const { return (wanted & kPtCls) ? cls.p : nullptr; }
+    int32_t *dev_element() const { return (wanted & kPtElement) ? element.p : nullptr; }
+    // n points of each output the caller gave a pointer for, onto `s` behind the launch
+    gm_status copy_back(gm_ctx *ctx, hipStream_t s, uint32_t n, float *h_res, int32_t *h_cell, int32_t *h_delta, uint8_t *h_cls,
+                        int32_t *h_element) const;
+};
+
 }  // namespace wall
 }  // namespace gm
 
@@ -294,10 +315,7 @@ struct gm_wall_map {
     std::vector<uint8_t> pending;  // per slot of ctx: an add was enqueued on its stream since the last sync
     std::vector<hipEvent_t> adds;  // per slot of ctx: recorded on its stream for a reader on another slot: the adds so far
     gm::DevArray<uint8_t> stage;   // device staging of the window calls, kStageCells records
-    // the stage calls' per-point outputs: gm_wall_map_add_points' and, beside them, gm_wall_map_check_points'
-    gm::DevArray<float> pt_res;
-    gm::DevArray<int32_t> pt_cell, ck_delta;
-    gm::DevArray<uint8_t> ck_cls;
+    gm::wall::PointOutputs pt;     // the stage calls' per-point outputs: gm_wall_map_add_points', gm_wall_map_check_points'
     uint32_t points_per_block = 0; // 0: the kernel's default (GM_WALL_POINTS_PER_BLOCK: measurements)
     // gm_wall_map_regions: the tile (GM_WALL_REGION_TILE: tests, measurements) and the scratch
     uint32_t region_ts = GM_WALL_REGION_TILE_STATIONS, region_tk = GM_WALL_REGION_TILE_SECTORS;
@@ -346,7 +364,7 @@ struct gm_wall_map {
     std::vector<gm::wall::WallLocateSlot> locates;
     std::vector<gm::wall::WallAlignSlot> aligns;
     // gm_wall_alignment_locate_*: the pending locates, per slot, of the alignment this map is an element of (they read the
-    // map as its own locates do); nullptr on any other map and until that alignment first locates across elements
+    // map as its own locates do); nullptr on any other map
     std::vector<gm::wall::PendingResult> *al_locates = nullptr;
     // gm_wall_alignment_check_*: the same for that alignment's pending checks
     std::vector<gm::wall::PendingResult> *al_checks = nullptr;
@@ -423,14 +441,16 @@ gm_status wait_adds(gm_wall_map *m, uint32_t slot, hipStream_t s);
 uint64_t add_checked_block_words(uint32_t n_cap);
 void add_checked_fill_info(gm_wall_add_checked_info *info, uint32_t status, long long S, const unsigned long long *h);
 
-// A stage call's points (gm_wall_map_add_points, gm_wall_map_check_points, ...) on the staging slot: open, whatever the
-// call enqueues ahead of its points, upload, the call's launch, close.
+// A stage call's points (gm_wall_map_add_points, gm_wall_map_check_points, gm_wall_alignment_add_points, ...) on the staging
+// slot: open, whatever the call enqueues ahead of its points, upload, the call's launch, close.
 struct StageCall {
     gm_wall_map *map;
     uint32_t n;
-    float *residual;   // the caller's per-point outputs (NULL: not wanted)
+    PointOutputs &out;   // where the per-point outputs are staged: the map's owner, or that of the alignment map is side 0 of
+    float *residual;     // the caller's per-point outputs (NULL: not wanted)
     int32_t *cell, *delta;
     uint8_t *cls;
+    int32_t *element;
     Slot *sl = nullptr;
     gm_status open();    // the slot, its capacity and the device side of the per-point outputs; nothing is enqueued
     gm_status upload(const float *xyz, const uint8_t *labels, WallArgs &w);   // points and labels onto the slot's stream; w: the point fields of the launch

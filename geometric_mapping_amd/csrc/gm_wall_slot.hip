@@ -472,7 +472,7 @@ gm_status gm_wall_map_check_points(gm_wall_map *map, const float *xyz, uint32_t 
     GMW_OK(add_frame_args(map, pose, add_info, a.w, nullptr, &ax));
     a.w.gate = (float)cp.gate;
     if (add_info) add_info->gate = a.w.gate;
-    StageCall sc{map, n, residual, cell, delta, cls};
+    StageCall sc{map, n, map->pt, residual, cell, delta, cls, nullptr};
     GMW_OK(sc.open());
     hipStream_t s = sc.sl->stream;
     const uint32_t n_cap = n ? n : 1u;
@@ -480,8 +480,8 @@ gm_status gm_wall_map_check_points(gm_wall_map *map, const float *xyz, uint32_t 
     GMW_OK(check_prepare(map, 0, n_cap, s, scan, a));
     GMW_OK(wait_adds(map, 0, s));
     GMW_OK(sc.upload(xyz, labels, a.w));
-    a.delta = delta ? map->ck_delta.p : nullptr;
-    a.cls = cls ? map->ck_cls.p : nullptr;
+    a.delta = map->pt.dev_delta();
+    a.cls = map->pt.dev_cls();
     a.reference = cp.reference;
     a.min_count = cp.min_count;
     a.row_is_index = 1u;
@@ -530,7 +530,7 @@ gm_status gm_wall_map_locate_points(gm_wall_map *map, const float *xyz, uint32_t
     WallLocateArgs a;
     WallFrame64 f;
     GMW_OK(locate_args(map, pose, lp, a, f));
-    StageCall sc{map, n, residual, cell, nullptr, nullptr};
+    StageCall sc{map, n, map->pt, residual, cell, nullptr, nullptr, nullptr};
     GMW_OK(sc.open());
     hipStream_t s = sc.sl->stream;
     GMW_OK(locate_prepare(map, 0, s, a));
@@ -582,7 +582,7 @@ gm_status gm_wall_map_align_points(gm_wall_map *map, const float *xyz, uint32_t 
         return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_align_points: struct_size mismatch or a parameter outside its limits");
     WallAlignArgs a;
     GMW_OK(align_args(map, pose, ap, add_info, a));
-    StageCall sc{map, n, residual, cell, nullptr, nullptr};
+    StageCall sc{map, n, map->pt, residual, cell, nullptr, nullptr, nullptr};
     GMW_OK(sc.open());
     hipStream_t s = sc.sl->stream;
     GMW_OK(align_prepare(map, 0, s, a));

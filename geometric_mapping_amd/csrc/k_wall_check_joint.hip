@@ -3,14 +3,13 @@
 //
 // k_wall_check's shape (gm_wall_check.hpp: ONE k_compact launch over the valid cloud, the payload in registers, rows out in
 // the cloud's order, integer atomics only), over up to GM_WALL_JOINT_MAX_SIDES element maps at once:
-//   1. every point is given its owner by k_wall_add_joint's rule: d_i = (p - Jo'_i).aJ'_i for the joint planes in ascending
-//      order, the side before the first d_i < 0, the last side if there is none.  The planes are read from LDS (a
-//      broadcast; the emit step's prepare() stores them ahead of the block's barrier), as in k_wall_add_joint and
-//      k_wall_locate_joint: 18 scalar registers less beside a side's frame;
-//   2. the point runs its owner's chain and no other: a loop over the sides, wave-uniform, with a wave-uniform switch on the
-//      side's axis kind in front of the three chain heads of gm_device.hpp (wall_chain, exactly as k_wall_check,
-//      k_wall_check_arc and k_wall_check_clothoid instantiate it) under the check's gate.  A wave whose lanes have
-//      different owners runs each of their chains once, under the lanes' mask; the side's frame stays in scalar registers;
+//   1. every point is given its owner by joint_owner (gm_wall_joint.hpp states the rule).  The planes are read from LDS
+//      (the emit step's prepare() stores them ahead of the block's barrier), as in k_wall_add_joint and
+//      k_wall_locate_joint;
+//   2. the point runs its owner's chain and no other: a loop over the sides, wave-uniform, each trip joint_side_chain
+//      (gm_wall_joint.hpp: wall_chain exactly as k_wall_check, k_wall_check_arc and k_wall_check_clothoid instantiate it)
+//      under the check's gate.  A wave whose lanes have different owners runs each of their chains once, under the lanes'
+//      mask; the side's frame stays in scalar registers;
 //   3. inside the same trip of the loop a mapped point gathers its cell from the OWNER's table (wall_check_cell: the count
 //      first, sum or keys only for a usable cell) and takes the integer rule, and the wave counts its seven classes: one
 //      ballot per class over the lanes the side owns, into the side's seven LDS words.  A wave of one owner -- nearly every
@@ -22,8 +21,8 @@
 // a rank < n or a point index < n; owner < n_sides <= GM_WALL_JOINT_MAX_SIDES.
 #include <string.h>
 
-#include "gm_wall_add.hpp"     // JointChainArgs
 #include "gm_wall_check.hpp"
+#include "gm_wall_joint.hpp"   // the side, the owner rule, the side's chain
 
 namespace gm {
 
@@ -44,10 +43,10 @@ __device__ __forceinline__ WallCheckJointOut *wkj_out()
     __shared__ WallCheckJointOut o;
     return &o;
 }
-// block-shared: the joint planes, Jo' then aJ'
-__device__ __forceinline__ float (*wkj_planes())[6]
+// block-shared: the joint planes
+__device__ __forceinline__ JointPlaneLds &wkj_planes()
 {
-    __shared__ float pl[kCheckJointSides - 1][6];
+    __shared__ JointPlaneLds pl;
     return pl;
 }
 
@@ -60,16 +59,7 @@ struct WallCheckJointPred {
         p.q = a.pts[i];
         const float4 q = p.q;
         const uint32_t lab = a.labels ? a.labels[i] : 0u;
-        uint32_t owner = nside - 1u;
-#pragma unroll
-        for (int jn = kCheckJointSides - 2; jn >= 0; --jn) {   // descending: the lowest joint with d < 0 stays
-            if ((uint32_t)jn + 1u < nside) {                   // (wave-uniform)
-                const float *pl = wkj_planes()[jn];
-                const float qx = __fsub_rn(q.x, pl[0]), qy = __fsub_rn(q.y, pl[1]), qz = __fsub_rn(q.z, pl[2]);
-                const float aj[3] = {pl[3], pl[4], pl[5]};
-                if (surf_dot3(qx, qy, qz, aj) < 0.0f) owner = (uint32_t)jn;
-            }
-        }
+        const uint32_t owner = joint_owner(q, wkj_planes(), nside);
         float e = __builtin_nanf("");
         int cell = -1;      // the owner's cell j * n_sectors + k (< 2^24)
         long long delta = 0;
@@ -77,22 +67,13 @@ struct WallCheckJointPred {
 #pragma unroll 1
         for (uint32_t s = 0; s < nside; ++s) {   // s is wave-uniform: the side's block is read once per wave
             if (owner != s) continue;
-            const WallCheckJointSide &S = a.side[s];
-            JointChainArgs w;
-            for (int k = 0; k < 3; ++k) { w.o[k] = S.o[k]; w.a[k] = S.a[k]; w.u[k] = S.u[k]; w.v[k] = S.v[k]; }
-            w.R = a.R; w.station_length = a.station_length; w.gate = a.gate; w.sector_angle = a.sector_angle; w.two_pi = a.two_pi;
-            w.n_sectors = a.n_sectors; w.n_stations = S.n_stations; w.anchor = S.anchor;
+            const WallJointSide &S = a.side[s];
             int64_t j = -1;
             float jl = 0.0f;
             uint32_t kk = 0u;
-            auto in_range = [&](float x) { return (j = wall_station(w, x)) >= 0; };
-            auto count = [&](uint32_t k) { cls = k; };
-            bool mapped;
-            if (S.axis == kAxisClothoid) mapped = wall_chain(q, lab, w, WallClothoidArg{S.ax}, in_range, count, e, jl, kk);
-            else if (S.axis == kAxisArc) mapped = wall_chain(q, lab, w, WallArcArg<true>{S.ax.arc}, in_range, count, e, jl, kk);
-            else mapped = wall_chain(q, lab, w, WallArcArg<false>(), in_range, count, e, jl, kk);
+            const bool mapped = joint_side_chain(q, lab, S, a.grid, a.gate, e, jl, kk, j, cls);
             if (mapped) {
-                cell = (int)((uint32_t)j * a.n_sectors + kk);   // < the owner's n_stations * n_sectors <= 2^24
+                cell = (int)((uint32_t)j * a.grid.n_sectors + kk);   // < the owner's n_stations * n_sectors <= 2^24
                 cls = wall_check_cell(S.table, cell, a.reference, a.min_count, a.T, e, delta);
             }
             wall_check_count<kCheckJointWords>(cls, s * (uint32_t)GM_WALL_CHECK_N_CLS);   // (the lanes this side owns)
@@ -131,7 +112,7 @@ struct WallCheckJointEmit {
     static constexpr bool kHasFinish = true, kHasPrepare = true;
     WallCheckJointTail tail;
     WallCheckJointOut outputs;
-    float plane[kCheckJointSides - 1][6];
+    WallJointPlanes planes;
     long long q_pos, q_neg;           // this thread's largest / smallest emitted delta
     __device__ __forceinline__ void prepare()
     {
@@ -139,10 +120,7 @@ struct WallCheckJointEmit {
         if (threadIdx.x == 0) {   // (constant indices: the blocks stay kernel arguments, in scalar registers)
             *wkj_tail() = tail;
             *wkj_out() = outputs;
-#pragma unroll
-            for (int jn = 0; jn < kCheckJointSides - 1; ++jn)
-#pragma unroll
-                for (int k = 0; k < 6; ++k) wkj_planes()[jn][k] = plane[jn][k];
+            joint_planes_store(wkj_planes(), planes);
         }
         q_pos = 0; q_neg = 0;
     }
@@ -166,8 +144,7 @@ void launch_wall_check_joint(const WallCheckJointArgs &a, uint32_t n_cap, const 
     memset(&emit, 0, sizeof(emit));
     emit.tail = WallCheckJointTail{a.out, a.ctr, a.n_ptr, a.n_host, a.row_is_index};
     emit.outputs = WallCheckJointOut{a.res, a.cell, a.delta, a.cls, a.element};
-    for (int j = 0; j < kCheckJointSides - 1; ++j)
-        for (int k = 0; k < 3; ++k) { emit.plane[j][k] = a.jo[j][k]; emit.plane[j][3 + k] = a.ja[j][k]; }
+    emit.planes = a.planes;
     hipLaunchKernelGGL((k_compact<WallCheckJointPred, WallCheckJointEmit>), dim3(compact_grid(n_cap ? n_cap : 1u)), dim3(kCpThreads), 0, s,
                        pred, emit, a.n_ptr, a.n_host, st, reinterpret_cast<uint32_t *>(a.ctr + 9), (uint32_t *)nullptr);
 }

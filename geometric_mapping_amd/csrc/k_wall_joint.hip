@@ -3,18 +3,18 @@
 //
 // k_wall_add's shape (gm_wall_add.hpp: kWallThreads per block, the wall_blocks grid, one streaming pass, the 80 KiB LDS
 // table, the in-wave run merge, integer atomics only), over up to GM_WALL_JOINT_MAX_SIDES element maps at once:
-//   1. every point is given its owner: d_i = (p - Jo'_i).aJ'_i for the joint planes in ascending order, the side before
-//      the first d_i < 0, the last side if there is none;
-//   2. the point runs its owner's chain and no other: a loop over the sides, wave-uniform, with a wave-uniform switch on
-//      the side's axis kind in front of the three chain heads of gm_device.hpp (wall_chain, exactly as k_wall_add,
-//      k_wall_add_arc and k_wall_add_clothoid instantiate it).  A wave whose lanes have different owners runs each of
-//      their chains once, under the lanes' mask; the side's frame stays in scalar registers;
+//   1. every point is given its owner by the joint planes (gm_wall_joint.hpp states the rule; the planes in LDS);
+//   2. the point runs its owner's chain and no other: a loop over the sides, wave-uniform, each trip joint_side_chain
+//      (gm_wall_joint.hpp: wall_chain exactly as k_wall_add, k_wall_add_arc and k_wall_add_clothoid instantiate it).  A
+//      wave whose lanes have different owners runs each of their chains once, under the lanes' mask; the side's frame
+//      stays in scalar registers;
 //   3. the run merge on the key side << 24 | cell (two sides have equal cell indices; a cell is < 2^24), every shuffle
 //      wave-uniform; the run's head lane adds to the LDS table when the cell lies in its side's window -- the table's
 //      GM_SURF_MAX_CELLS cells are dealt to the sides in order by the host -- and to the owner's map otherwise;
 //   4. one flush per side, and the class counts to the owner's totals: a wave counts its points per (side, class) by
 //      ballot into lane side * 4 + class, and the block's rows are summed by block_row_sums.
 #include "gm_wall_add.hpp"
+#include "gm_wall_joint.hpp"   // the side, the joint planes, the side's chain
 
 namespace gm {
 
@@ -38,33 +38,27 @@ __device__ __forceinline__ void wall_add_joint(const WallJointArgs &a, const Wal
     __shared__ uint32_t s_cls[kRows][kWallThreads / kWave];
     // the joint planes, read per point from LDS (a broadcast): 18 scalar registers less beside the sides' frames, which
     // keeps the kernel free of scalar spills
-    __shared__ float s_plane[kJointSides - 1][6];
+    __shared__ JointPlaneLds s_plane;
     const uint32_t n = a.n_ptr ? *a.n_ptr : a.n_host;
-    const uint32_t nsec = a.n_sectors;
+    const uint32_t nsec = a.grid.n_sectors;
     const uint32_t nside = a.n_sides;
     const uint32_t wcells = a.lds_cells;   // <= kWallCells (the host deals the windows)
     const int lane = lane_id();
 
     for (uint32_t c = threadIdx.x; c < wcells; c += kWallThreads) { s_sum[c] = 0ull; s_cnt[c] = 0u; s_lo[c] = 0u; s_hi[c] = 0u; }
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int jn = 0; jn < kJointSides - 1; ++jn)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { s_plane[jn][k] = a.jo[jn][k]; s_plane[jn][3 + k] = a.ja[jn][k]; }
-    }
+    if (threadIdx.x == 0) joint_planes_store(s_plane, a.planes);
     __syncthreads();
 
     uint32_t mine = 0u;   // lane c < 4 n_sides: this wave's points of class c & 3 owned by side c >> 2
     auto point = [&](uint64_t i, bool in, const float4 &q, uint32_t lab, uint32_t mbit) {
         const bool skip = kMasked && mbit;
+        // joint_owner's loop, written out: through the call k_wall_add_joint takes two scalar spills and three vector
+        // registers (SGPRs 104 -> 106, VGPRs 105 -> 108), k_wall_add_joint_masked two vector registers (113 -> 115)
         uint32_t owner = nside - 1u;
 #pragma unroll
         for (int jn = kJointSides - 2; jn >= 0; --jn) {   // descending: the lowest joint with d < 0 stays
             if ((uint32_t)jn + 1u < nside) {              // (wave-uniform)
-                const float(&pl)[6] = s_plane[jn];
-                const float qx = __fsub_rn(q.x, pl[0]), qy = __fsub_rn(q.y, pl[1]), qz = __fsub_rn(q.z, pl[2]);
-                const float aj[3] = {pl[3], pl[4], pl[5]};
-                if (surf_dot3(qx, qy, qz, aj) < 0.0f) owner = (uint32_t)jn;
+                if (joint_behind(q, s_plane[jn])) owner = (uint32_t)jn;
             }
         }
         float e = __builtin_nanf("");
@@ -75,19 +69,10 @@ __device__ __forceinline__ void wall_add_joint(const WallJointArgs &a, const Wal
         for (uint32_t s = 0; s < nside; ++s) {   // s is wave-uniform: the side's block is read once per wave
             if (!in || owner != s) continue;
             const WallJointSide &S = a.side[s];
-            JointChainArgs w;
-            for (int k = 0; k < 3; ++k) { w.o[k] = S.o[k]; w.a[k] = S.a[k]; w.u[k] = S.u[k]; w.v[k] = S.v[k]; }
-            w.R = a.R; w.station_length = a.station_length; w.gate = a.gate; w.sector_angle = a.sector_angle; w.two_pi = a.two_pi;
-            w.n_sectors = nsec; w.n_stations = S.n_stations; w.anchor = S.anchor;
             int64_t j = -1;
             float jl = 0.0f;
             uint32_t kk = 0u;
-            auto in_range = [&](float x) { return (j = wall_station(w, x)) >= 0; };
-            auto count = [&](uint32_t k) { kcls = k; };
-            bool mapped;
-            if (S.axis == kAxisClothoid) mapped = wall_chain(q, lab, w, WallClothoidArg{S.ax}, in_range, count, e, jl, kk);
-            else if (S.axis == kAxisArc) mapped = wall_chain(q, lab, w, WallArcArg<true>{S.ax.arc}, in_range, count, e, jl, kk);
-            else mapped = wall_chain(q, lab, w, WallArcArg<false>(), in_range, count, e, jl, kk);
+            const bool mapped = joint_side_chain(q, lab, S, a.grid, a.gate, e, jl, kk, j, kcls);
             if (mapped) {
                 cell = (int)((uint32_t)j * nsec + kk);
                 const float win_lo = (float)S.win_first, win_hi = (float)(S.win_first + (int32_t)S.win_stations);

@@ -4,7 +4,7 @@
 //
 // Shape: k_wall_locate's (the cylinder regression's): one streaming launch per pass, three per locate, on the FIXED grid
 // kFitBlocks x kFitThreads with the 4-point unroll, fit_block_reduce, the ticket, and the solve by thread 0 of the block
-// that finished last.  What differs is the point: it is given its owner by the joint planes of the pass (k_wall_joint.hip's
+// that finished last.  What differs is the point: it is given its owner by the joint planes of the pass (gm_wall_joint.hpp's
 // rule, the planes in LDS) and runs that side's chain alone -- a loop over the sides that is wave-uniform, with a
 // wave-uniform switch on the side's axis in front of surf_rho, arc_chain and clothoid_chain (gm_device.hpp); the side's
 // block is read through uniform addresses and stays in scalar registers.  The chain yields e, t and the unit radial
@@ -17,6 +17,7 @@
 // point), 33 us for k_wall_locate on a straight map: 17 B per point and pass, so none of them is bound by HBM.
 #include <math.h>
 
+#include "gm_wall_joint.hpp"   // the grid, the planes, the owner rule
 #include "gm_wall_locate.hpp"
 
 namespace gm {
@@ -58,7 +59,7 @@ __device__ __forceinline__ void locj_solve(const WallLocateJointArgs &a, int pas
     for (int s = 0; s < kLocSides; ++s)
         for (int k = 0; k < 12; ++k) rec.side[s][k] = blk.side[s][k];
     for (int j = 0; j < kLocSides - 1; ++j)
-        for (int k = 0; k < 3; ++k) { rec.joint_o[j][k] = blk.jo[j][k]; rec.joint_a[j][k] = blk.ja[j][k]; }
+        for (int k = 0; k < 3; ++k) { rec.joint_o[j][k] = blk.planes.jo[j][k]; rec.joint_a[j][k] = blk.planes.ja[j][k]; }
     if (pass == 0) {   // the records behind a failed pass stay zero
         const gm_wall_alignment_locate_pass zero = {};
         wk->pass[1] = zero;
@@ -99,7 +100,7 @@ __global__ __launch_bounds__(kFitThreads) void k_wall_locate_joint(WallLocateJoi
     __shared__ double tot[kFitCols];
     // the joint planes, read per point from LDS (a broadcast), as in k_wall_add_joint: the scalar registers go to the
     // owner's block
-    __shared__ float s_plane[kLocSides - 1][6];
+    __shared__ JointPlaneLds s_plane;
     __shared__ double s_home[9];   // c0, u, v
     const uint32_t n = a.n_ptr ? *a.n_ptr : a.n_host;
     const WallLocateJointWork *wk = a.work;
@@ -109,10 +110,9 @@ __global__ __launch_bounds__(kFitThreads) void k_wall_locate_joint(WallLocateJoi
     if (threadIdx.x == 0) {
         double c[3], d[3], u[3], v[3];
         locj_state(a, pass, c, d, u, v);
-#pragma unroll
-        for (int jn = 0; jn < kLocSides - 1; ++jn)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { s_plane[jn][k] = blk.jo[jn][k]; s_plane[jn][3 + k] = blk.ja[jn][k]; }
+        // (a call per branch: through blk, a select of two pointers, the whole argument block goes to private memory)
+        if (pass == 0) joint_planes_store(s_plane, a.first.planes);
+        else joint_planes_store(s_plane, wk->next.planes);
         // the pass's fp32 state, as fp64, and c0 = o + s0 a: what J is taken against (LDS too: eighteen scalar registers)
         for (int k = 0; k < 3; ++k) {
             s_home[k] = (double)(float)c[k] + a.s0 * (double)(float)d[k];
@@ -123,8 +123,8 @@ __global__ __launch_bounds__(kFitThreads) void k_wall_locate_joint(WallLocateJoi
     __syncthreads();
     const float gate = (float)(a.gate * (1.0 / (double)(1 << pass)));
     const bool map_mode = a.reference == (uint32_t)GM_WALL_LOCATE_MAP;
-    const float R = a.R, ds = a.station_length, two_pi = a.two_pi, dtheta = a.sector_angle;
-    const uint32_t nsec = a.n_sectors, min_count = a.min_count, nside = a.n_sides;
+    const float R = a.grid.R, ds = a.grid.station_length, two_pi = a.grid.two_pi, dtheta = a.grid.sector_angle;
+    const uint32_t nsec = a.grid.n_sectors, min_count = a.min_count, nside = a.n_sides;
     const float inf = __builtin_inff();
 
     double s[kLocAcc];
@@ -135,16 +135,9 @@ __global__ __launch_bounds__(kFitThreads) void k_wall_locate_joint(WallLocateJoi
     uint32_t n_plane = 0u, n_used = 0u;
     unsigned long long n_cls = 0ull;
     auto accumulate = [&](const float4 p, uint32_t lab, uint32_t i) {
-        uint32_t owner = nside - 1u;
-#pragma unroll
-        // descending: the lowest joint with d < 0 stays.  (A joint the plan does not have is attached as h = 0: its aJ' is
-        // (0, 0, 0) in every pass, its d is 0 or a NaN and never < 0 -- three uniform conditions less in the scalar file.)
-        for (int jn = kLocSides - 2; jn >= 0; --jn) {
-            const float(&pl)[6] = s_plane[jn];
-            const float qx = __fsub_rn(p.x, pl[0]), qy = __fsub_rn(p.y, pl[1]), qz = __fsub_rn(p.z, pl[2]);
-            const float aj[3] = {pl[3], pl[4], pl[5]};
-            if (surf_dot3(qx, qy, qz, aj) < 0.0f) owner = (uint32_t)jn;
-        }
+        // without the guard on the plan's joints: a joint the plan does not have is attached as h = 0, so its aJ' is
+        // (0, 0, 0) in every pass, its d is 0 or a NaN and never < 0 -- three uniform conditions less in the scalar file
+        const uint32_t owner = joint_owner<false>(p, s_plane, nside);
         float res = __builtin_nanf("");
         int cell = -1;
         int32_t element = 0;
