@@ -940,6 +940,41 @@ def _dptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def _axis_add_info(i):
+    """A gm_wall_arc_add_info or gm_wall_clothoid_add_info as a dict (rate: where the struct has one)."""
+    d = dict(status=int(i.status), anchor_station=int(i.anchor_station), sensor_chainage=float(i.sensor_chainage),
+             anchor_chainage=float(i.anchor_chainage))
+    for k in ("o", "a", "n", "b"):
+        d[k] = np.array(getattr(i, k)[:], dtype=np.float32)
+    for k in ("kappa", "rate", "un", "ub", "vn", "vb", "R", "station_length", "sector_angle", "gate"):
+        if hasattr(i, k):
+            d[k] = np.float32(getattr(i, k))
+    return d
+
+
+def _project_each(name, call, xyz):
+    """The project entry `name` on map points [n, 3], one `call(x, chainage, angle, e)` per point: (chainage, angle, e),
+    float64 [n] each."""
+    x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+    out = np.empty((len(x), 3), dtype=np.float64)
+    s, ph, e = C.c_double(), C.c_double(), C.c_double()
+    for k in range(len(x)):
+        _arc_call(name, call(_dptr(x[k]), C.byref(s), C.byref(ph), C.byref(e)))
+        out[k] = (s.value, ph.value, e.value)
+    return out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
+
+
+def _point_each(name, call, chainage, angle, rho):
+    """The point entry `name` at (chainage, angle, rho), broadcast, one `call(chainage, angle, rho, xyz)` per point:
+    float64 [n, 3]."""
+    s, ph, r = np.broadcast_arrays(np.asarray(chainage, np.float64), np.asarray(angle, np.float64), np.asarray(rho, np.float64))
+    s, ph, r = s.reshape(-1), ph.reshape(-1), r.reshape(-1)
+    out = np.empty((len(s), 3), dtype=np.float64)
+    for k in range(len(s)):
+        _arc_call(name, call(float(s[k]), float(ph[k]), float(r[k]), _dptr(out[k])))
+    return out
+
+
 def wall_arc_add_frame(prm, arc, pose):
     """gm_wall_arc_add_frame (host only): the per-add frame of an arc map with the gm_wall_params `prm` and the gm_wall_arc
     `arc` under `pose`: dict of anchor_station, sensor_chainage, anchor_chainage, o, a, n, b (float32 [3]) and the fp32
@@ -947,13 +982,7 @@ def wall_arc_add_frame(prm, arc, pose):
     m = WallMap._pose(pose)
     i = _lib.WallArcAddInfo()
     _arc_call("gm_wall_arc_add_frame", _lib.load().gm_wall_arc_add_frame(C.byref(prm), C.byref(arc), _dptr(m), C.byref(i)))
-    d = dict(status=int(i.status), anchor_station=int(i.anchor_station), sensor_chainage=float(i.sensor_chainage),
-             anchor_chainage=float(i.anchor_chainage))
-    for k in ("o", "a", "n", "b"):
-        d[k] = np.array(getattr(i, k)[:], dtype=np.float32)
-    for k in ("kappa", "un", "ub", "vn", "vb", "R", "station_length", "sector_angle", "gate"):
-        d[k] = np.float32(getattr(i, k))
-    return d
+    return _axis_add_info(i)
 
 
 def wall_arc_frame(prm, arc, chainage):
@@ -966,27 +995,14 @@ def wall_arc_frame(prm, arc, chainage):
 
 def wall_arc_project(prm, arc, xyz):
     """gm_wall_arc_project (host only) on map points [n, 3]: (chainage, angle, e), float64 [n] each."""
-    x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
     L = _lib.load()
-    out = np.empty((len(x), 3), dtype=np.float64)
-    s, ph, e = C.c_double(), C.c_double(), C.c_double()
-    for k in range(len(x)):
-        _arc_call("gm_wall_arc_project", L.gm_wall_arc_project(C.byref(prm), C.byref(arc), _dptr(x[k]), C.byref(s), C.byref(ph),
-                                                               C.byref(e)))
-        out[k] = (s.value, ph.value, e.value)
-    return out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
+    return _project_each("gm_wall_arc_project", lambda *a: L.gm_wall_arc_project(C.byref(prm), C.byref(arc), *a), xyz)
 
 
 def wall_arc_point(prm, arc, chainage, angle, rho):
     """gm_wall_arc_point (host only): the map points at (chainage, angle, rho), broadcast; float64 [n, 3]."""
-    s, ph, r = np.broadcast_arrays(np.asarray(chainage, np.float64), np.asarray(angle, np.float64), np.asarray(rho, np.float64))
-    s, ph, r = s.reshape(-1), ph.reshape(-1), r.reshape(-1)
     L = _lib.load()
-    out = np.empty((len(s), 3), dtype=np.float64)
-    for k in range(len(s)):
-        _arc_call("gm_wall_arc_point", L.gm_wall_arc_point(C.byref(prm), C.byref(arc), float(s[k]), float(ph[k]), float(r[k]),
-                                                           _dptr(out[k])))
-    return out
+    return _point_each("gm_wall_arc_point", lambda *a: L.gm_wall_arc_point(C.byref(prm), C.byref(arc), *a), chainage, angle, rho)
 
 
 def wall_clothoid(normal, curvature=0.0, rate=0.0, point_chainage=0.0):
@@ -1011,13 +1027,7 @@ def wall_clothoid_add_frame(prm, clothoid, pose):
     i = _lib.WallClothoidAddInfo()
     _arc_call("gm_wall_clothoid_add_frame",
               _lib.load().gm_wall_clothoid_add_frame(C.byref(prm), C.byref(clothoid), _dptr(m), C.byref(i)))
-    d = dict(status=int(i.status), anchor_station=int(i.anchor_station), sensor_chainage=float(i.sensor_chainage),
-             anchor_chainage=float(i.anchor_chainage))
-    for k in ("o", "a", "n", "b"):
-        d[k] = np.array(getattr(i, k)[:], dtype=np.float32)
-    for k in ("kappa", "rate", "un", "ub", "vn", "vb", "R", "station_length", "sector_angle", "gate"):
-        d[k] = np.float32(getattr(i, k))
-    return d
+    return _axis_add_info(i)
 
 
 def wall_clothoid_frame(prm, clothoid, chainage):
@@ -1033,27 +1043,15 @@ def wall_clothoid_frame(prm, clothoid, chainage):
 
 def wall_clothoid_project(prm, clothoid, xyz):
     """gm_wall_clothoid_project (host only) on map points [n, 3]: (chainage, angle, e), float64 [n] each."""
-    x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
     L = _lib.load()
-    out = np.empty((len(x), 3), dtype=np.float64)
-    s, ph, e = C.c_double(), C.c_double(), C.c_double()
-    for k in range(len(x)):
-        _arc_call("gm_wall_clothoid_project",
-                  L.gm_wall_clothoid_project(C.byref(prm), C.byref(clothoid), _dptr(x[k]), C.byref(s), C.byref(ph), C.byref(e)))
-        out[k] = (s.value, ph.value, e.value)
-    return out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
+    return _project_each("gm_wall_clothoid_project", lambda *a: L.gm_wall_clothoid_project(C.byref(prm), C.byref(clothoid), *a), xyz)
 
 
 def wall_clothoid_point(prm, clothoid, chainage, angle, rho):
     """gm_wall_clothoid_point (host only): the map points at (chainage, angle, rho), broadcast; float64 [n, 3]."""
-    s, ph, r = np.broadcast_arrays(np.asarray(chainage, np.float64), np.asarray(angle, np.float64), np.asarray(rho, np.float64))
-    s, ph, r = s.reshape(-1), ph.reshape(-1), r.reshape(-1)
     L = _lib.load()
-    out = np.empty((len(s), 3), dtype=np.float64)
-    for k in range(len(s)):
-        _arc_call("gm_wall_clothoid_point",
-                  L.gm_wall_clothoid_point(C.byref(prm), C.byref(clothoid), float(s[k]), float(ph[k]), float(r[k]), _dptr(out[k])))
-    return out
+    return _point_each("gm_wall_clothoid_point", lambda *a: L.gm_wall_clothoid_point(C.byref(prm), C.byref(clothoid), *a),
+                       chainage, angle, rho)
 
 
 def _wall_mesh_info(info):
@@ -1843,27 +1841,21 @@ class WallAlignmentRule:
         """gm_wall_alignment_project on map points [n, 3]: (element int64 [n], chainage, angle, e float64 [n]).  One
         library call per point, and each call chains the alignment anew (include/gm_hip.h gives the cost): for poses,
         windows and synthetic frames, not for a cloud per frame."""
-        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-        el = np.empty(len(x), dtype=np.int64)
-        out = np.empty((len(x), 3), dtype=np.float64)
-        k_, s, ph, e = C.c_uint32(), C.c_double(), C.c_double(), C.c_double()
-        for k in range(len(x)):
-            _arc_call("gm_wall_alignment_project", self._L.gm_wall_alignment_project(
-                *self._head(), _dptr(x[k]), C.byref(k_), C.byref(s), C.byref(ph), C.byref(e)))
-            el[k] = k_.value
-            out[k] = (s.value, ph.value, e.value)
-        return el, out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
+        k_, el = C.c_uint32(), []
+
+        def call(x, *out):
+            st = self._L.gm_wall_alignment_project(*self._head(), x, C.byref(k_), *out)
+            el.append(k_.value)
+            return st
+
+        s, ph, e = _project_each("gm_wall_alignment_project", call, xyz)
+        return np.array(el, dtype=np.int64), s, ph, e
 
     def point(self, chainage, angle, rho):
         """gm_wall_alignment_point: the map points at (chainage, angle, rho), broadcast; float64 [n, 3].  One library call
         per point, as project."""
-        s, ph, r = np.broadcast_arrays(np.asarray(chainage, np.float64), np.asarray(angle, np.float64), np.asarray(rho, np.float64))
-        s, ph, r = s.reshape(-1), ph.reshape(-1), r.reshape(-1)
-        out = np.empty((len(s), 3), dtype=np.float64)
-        for k in range(len(s)):
-            _arc_call("gm_wall_alignment_point", self._L.gm_wall_alignment_point(
-                *self._head(), float(s[k]), float(ph[k]), float(r[k]), _dptr(out[k])))
-        return out
+        return _point_each("gm_wall_alignment_point", lambda *a: self._L.gm_wall_alignment_point(*self._head(), *a),
+                           chainage, angle, rho)
 
     def window(self, s_from, s_to):
         """gm_wall_alignment_window: the pieces (element, station0, n_stations) of the chainage interval, in order."""

@@ -327,10 +327,17 @@ __host__ __device__ inline WallTable wall_table(uint8_t *base, uint64_t ncell)
     return t;
 }
 size_t wall_table_bytes(uint64_t ncell);
-// n_cap: the most points the launch can see (the grid is sized by it); points_per_block 0: the default rule
-void launch_wall_add(const WallArgs &a, uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
-void launch_wall_add_arc(const WallArgs &a, const WallArc &arc, uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
-void launch_wall_add_clothoid(const WallArgs &a, const WallClothoid &cl, uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
+// The design axis of a launch, host side: the kind (gm_device.hpp: kAxis*) and what the arc and the clothoid kernels take
+// beside the arguments (an arc reads ax.arc alone, a straight axis nothing).  One launch front per kernel family takes it
+// and launches the instantiation of its kind.
+struct WallAxis {
+    int kind;
+    WallClothoid ax;
+};
+// n_cap: the most points the launch can see (the grid is sized by it); points_per_block 0: the default rule.  mask (NULL:
+// none): k_wall_add over the points whose mask bit is clear; the five point classes also go to ctr[4 .. 8].
+void launch_wall_add(const WallArgs &a, const WallAxis &axis, const unsigned long long *mask, unsigned long long *ctr, uint32_t n_cap,
+                     uint32_t points_per_block, hipStream_t s);
 // k_wall_add_checked.hip (gm_wall_map_add_*_checked): mark the selected rows' points in a bit mask, then k_wall_add's masked
 // instantiation.  u64 words of the call's counter block: rows_neg, rows_pos, rows_kept, rows_rejected | skipped, mapped,
 // outside, beyond_gate, plane | n_rows, n_points, pad
@@ -349,13 +356,6 @@ struct WallMarkArgs {
 };
 // n_cap: the most rows the launch can see (the grid is sized by it)
 void launch_wall_mark(const WallMarkArgs &a, uint32_t n_cap, hipStream_t s);
-// k_wall_add over the points whose mask bit is clear; the five point classes also go to ctr[4 .. 8]
-void launch_wall_add_masked(const WallArgs &a, const unsigned long long *mask, unsigned long long *ctr, uint32_t n_cap,
-                            uint32_t points_per_block, hipStream_t s);
-void launch_wall_add_arc_masked(const WallArgs &a, const WallArc &arc, const unsigned long long *mask, unsigned long long *ctr,
-                                uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
-void launch_wall_add_clothoid_masked(const WallArgs &a, const WallClothoid &cl, const unsigned long long *mask, unsigned long long *ctr,
-                                     uint32_t n_cap, uint32_t points_per_block, hipStream_t s);
 // the class of one row: 0 selected negative, 1 selected positive, 2 kept, 3 rejected (delta_bits: the row's delta)
 __host__ __device__ inline uint32_t wall_mark_class(uint32_t delta_bits, long long dq, uint32_t index, uint32_t n_points,
                                                     uint32_t skip, long long S)
@@ -429,10 +429,14 @@ struct WallCloudClothoid {
     double n[3], b[3];
     double un, ub, vn, vb;
 };
+// The position rule's axis of a cloud or mesh launch, host side: the kind and the arc's struct, of which a clothoid takes
+// rows ([nJ][5] then), n, b and un .. vb, a straight axis nothing.
+struct WallCloudAxis {
+    int kind;
+    WallCloudArc arc;
+};
 void launch_wall_cloud_merge(const WallCloudArgs &a, hipStream_t s);
-void launch_wall_cloud_compact(const WallCloudArgs &a, const ScanState &st, hipStream_t s);
-void launch_wall_cloud_compact_arc(const WallCloudArgs &a, const WallCloudArc &arc, const ScanState &st, hipStream_t s);
-void launch_wall_cloud_compact_clothoid(const WallCloudArgs &a, const WallCloudClothoid &cl, const ScanState &st, hipStream_t s);
+void launch_wall_cloud_compact(const WallCloudArgs &a, const WallCloudAxis &axis, const ScanState &st, hipStream_t s);
 // k_wall_mesh.hip (gm_wall_map_mesh): the cloud's compaction with an emit step that also stores the survivor's index
 // (rank_base + its rank in the chunk) into rank[block of the window] and, for a step cut, its mean into mean[block]; then
 // per chunk of whole quad rows one k_compact over the chunk's 2 * quads slots
@@ -448,12 +452,8 @@ struct WallMeshArgs {
     gm_wall_mesh_triangle *out;   // the chunk's staging, 2 * nq records
     unsigned long long *ctr;   // [kWallMeshCounters]
 };
-void launch_wall_mesh_vertices(const WallCloudArgs &a, uint32_t *rank, float *mean, uint32_t rank_base, const ScanState &st,
-                               hipStream_t s);
-void launch_wall_mesh_vertices_arc(const WallCloudArgs &a, const WallCloudArc &arc, uint32_t *rank, float *mean, uint32_t rank_base,
-                                   const ScanState &st, hipStream_t s);
-void launch_wall_mesh_vertices_clothoid(const WallCloudArgs &a, const WallCloudClothoid &cl, uint32_t *rank, float *mean,
-                                        uint32_t rank_base, const ScanState &st, hipStream_t s);
+void launch_wall_mesh_vertices(const WallCloudArgs &a, const WallCloudAxis &axis, uint32_t *rank, float *mean, uint32_t rank_base,
+                               const ScanState &st, hipStream_t s);
 void launch_wall_mesh_triangles(const WallMeshArgs &a, const ScanState &st, hipStream_t s);
 // k_wall_check.hip (gm_wall_map_check_*): one k_compact launch per check
 // u64 words: the seven classes (GM_WALL_CHECK_CLS_* order), peak_pos, -peak_neg, the changed points (low word), n_points, pad
@@ -469,9 +469,7 @@ struct WallCheckArgs {
     uint8_t *cls;
 };
 // n_cap: the most points the launch can see (the grid is sized by it)
-void launch_wall_check(const WallCheckArgs &a, uint32_t n_cap, const ScanState &st, hipStream_t s);
-void launch_wall_check_arc(const WallCheckArgs &a, const WallArc &arc, uint32_t n_cap, const ScanState &st, hipStream_t s);
-void launch_wall_check_clothoid(const WallCheckArgs &a, const WallClothoid &cl, uint32_t n_cap, const ScanState &st, hipStream_t s);
+void launch_wall_check(const WallCheckArgs &a, const WallAxis &axis, uint32_t n_cap, const ScanState &st, hipStream_t s);
 // the rule's integers, shared by the kernel and gm_wall_check_classify
 __host__ __device__ inline long long wall_check_fix(float e)   // (int64) rint(e 2^20), saturating at int32, 0 for a NaN
 {

@@ -1,6 +1,7 @@
 // gm_wall.hip -- C ABI of the persistent wall map (gm_wall_*; include/gm_hip.h states the rule): the map itself and the
-// window calls.  Host logic only: the per-add frame in fp64, the station window of a frame, ownership.  Kernels are in
-// k_wall*.hip, the device-free calls in gm_wall_host.hip, the per-(map, slot) calls in gm_wall_slot.hip.
+// window calls.  Host logic only: the arguments of an add from the axis' per-add frame (DesignAxis, gm_wall_host.hip), the
+// station window of a frame, ownership.  Kernels are in k_wall*.hip behind one launch front per family, the device-free
+// calls in gm_wall_host.hip, the per-(map, slot) calls in gm_wall_slot.hip.
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -29,14 +30,7 @@ static void add_window(const gm_wall_params &p, double reach_stations, WallArgs 
     }
 }
 
-void launch_add(gm_wall_map *m, const WallArgs &w, const WallClothoid &ax, uint32_t n_cap, hipStream_t s)
-{
-    if (m->is_clothoid()) launch_wall_add_clothoid(w, ax, n_cap, m->points_per_block, s);
-    else if (m->is_arc()) launch_wall_add_arc(w, ax.arc, n_cap, m->points_per_block, s);
-    else launch_wall_add(w, n_cap, m->points_per_block, s);
-}
-
-gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info *info, WallArgs &w, WallFrame64 *f64, WallClothoid *ax)
+gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info *info, WallArgs &w, WallFrame64 *f64, WallAxis *ax)
 {
     gm_ctx *ctx = m->ctx;
     if (!pose) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: NULL pose");
@@ -45,86 +39,37 @@ gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info
     if (bad == 1) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose is not finite");
     if (bad) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose rotation is not orthonormal to 1e-6 or is a reflection");
     const gm_wall_params &p = m->prm;
-    const DesignFrame &d = m->frame;
-    const double ds = p.station_length;
-    // what the three axes compute: (o', a', u', v') rounded once, the axis block, the anchor, the crop cube's reach in stations
-    double reach;
-    if ((m->is_arc() || m->is_clothoid()) && !ax)
+    const DesignFrame &d = m->axis.d;
+    if (m->axis.kind != kAxisStraight && !ax)
         return gm_fail(ctx, GM_ERR_UNSUPPORTED, "gm_wall_map: this call is not available on a map with an arc or a clothoid design axis");
-    if (m->is_clothoid()) {   // (include/gm_hip.h: per add)
-        gm_wall_clothoid_add_info ai;
-        double u64[3], v64[3], a1 = 0.0;
-        if (!clothoid_add_frame(p, d, m->cf, Rm, tr, ai, u64, v64, &a1))
-            return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose is too far along the axis");
-        memset(&w, 0, sizeof(w));
-        WallArc *arc = &ax->arc;
-        for (int k = 0; k < 3; ++k) {
-            w.o[k] = ai.o[k]; w.a[k] = ai.a[k]; w.u[k] = (float)u64[k]; w.v[k] = (float)v64[k];
-            arc->n[k] = ai.n[k]; arc->b[k] = ai.b[k];
-        }
-        arc->kappa = ai.kappa;
-        arc->un = ai.un; arc->ub = ai.ub; arc->vn = ai.vn; arc->vb = ai.vb;
-        ax->rate = ai.rate;
-        w.anchor = ai.anchor_station;
-        // The LDS window, which affects speed only (a mapped point outside it goes to the map directly), sized from the
-        // largest |kappa| of the map: a mapped point and the sensor both lie within rho = R + gate of the axis, and
-        // rho max |kappa| <= 0.5 (a refusal of the creation), where the foot of the perpendicular moves by at most
-        // 1 / (1 - rho max |kappa|) <= 2 times the distance between two points.  A point of the crop cube |p|_inf <= B is
-        // within sqrt(3) B of the sensor, whose own foot lies less than ds past the anchor section: |t| <= 2 sqrt(3) B + ds
-        // (the one station goes into add_window's slack).  The tangent turns along the reach, so |a'|_1 does not sharpen it.
-        reach = 2.0 * ctx->cfg.boxFilterBound * 1.7320508075688772 / ds;
-    } else if (m->is_arc()) {   // (include/gm_hip.h: per add)
-        WallArc *arc = &ax->arc;
-        gm_wall_arc_add_info ai;
-        double u64[3], v64[3], a1 = 0.0;
-        if (!arc_add_frame(p, d, m->af, Rm, tr, ai, u64, v64, &a1))
-            return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose is too far along the axis");
-        memset(&w, 0, sizeof(w));
-        for (int k = 0; k < 3; ++k) {
-            w.o[k] = ai.o[k]; w.a[k] = ai.a[k]; w.u[k] = (float)u64[k]; w.v[k] = (float)v64[k];
-            arc->n[k] = ai.n[k]; arc->b[k] = ai.b[k];
-        }
-        arc->kappa = ai.kappa;
-        arc->un = ai.un; arc->ub = ai.ub; arc->vn = ai.vn; arc->vb = ai.vb;
-        w.anchor = ai.anchor_station;
-        // The LDS window, which affects speed only (a mapped point outside it goes to the map directly): wherever cy >= 0.5,
-        // |t| = |atan2(cx, cy)| / kappa <= |cx| / (cy kappa) <= 2 |x|, and |x| <= B |a'|_1 + ds over the crop cube
-        // |p|_inf <= B as on a straight map (the sensor lies within ds of the anchor section: the stations that costs at the
-        // window's ends take the global path).
-        reach = 2.0 * ctx->cfg.boxFilterBound * a1 / ds;
-    } else {
-        const double rel[3] = {tr[0] - d.o[0], tr[1] - d.o[1], tr[2] - d.o[2]};
-        const double s = dot(rel, d.a);
-        const double jd = floor((s - p.t_min) / ds);
-        if (!(fabs(jd) < 4.0e18)) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose is too far along the axis");
-        const double off = p.t_min + jd * ds;
-        double of[3];   // o_f - tr
-        for (int k = 0; k < 3; ++k) of[k] = d.o[k] + off * d.a[k] - tr[k];
-        memset(&w, 0, sizeof(w));
-        double a1 = 0.0;   // |a'|_1: the reach of the crop cube along the axis
-        for (int c = 0; c < 3; ++c) {   // Rm^T x
-            const double oo = Rm[0][c] * of[0] + Rm[1][c] * of[1] + Rm[2][c] * of[2];
-            const double aa = Rm[0][c] * d.a[0] + Rm[1][c] * d.a[1] + Rm[2][c] * d.a[2];
-            const double uu = Rm[0][c] * d.u[0] + Rm[1][c] * d.u[1] + Rm[2][c] * d.u[2];
-            const double vv = Rm[0][c] * d.v[0] + Rm[1][c] * d.v[1] + Rm[2][c] * d.v[2];
-            w.o[c] = (float)oo; w.a[c] = (float)aa; w.u[c] = (float)uu; w.v[c] = (float)vv;
-            if (f64) { f64->c[c] = oo; f64->d[c] = aa; f64->u[c] = uu; f64->v[c] = vv; f64->of[c] = d.o[c] + off * d.a[c]; }
-            a1 += fabs(aa);
-        }
-        w.anchor = (int64_t)jd;
-        // The LDS window: t = p.a' + (s - chainage of the anchor station's start) lies in [-B |a'|_1, B |a'|_1 + ds) for the
-        // points of the crop cube |p|_inf <= B, so their stations relative to the anchor in [floor(-reach), floor(reach) + 1].
-        reach = ctx->cfg.boxFilterBound * a1 / ds;
+    // what every axis computes (include/gm_hip.h: per add): (o', a', u', v') rounded once, the axis block, the anchor
+    AxisAddFrame f;
+    if (!m->axis.add_frame(p, Rm, tr, f)) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map: pose is too far along the axis");
+    memset(&w, 0, sizeof(w));
+    for (int k = 0; k < 3; ++k) {
+        w.o[k] = f.o[k]; w.a[k] = f.a[k]; w.u[k] = (float)f.u64[k]; w.v[k] = (float)f.v64[k];
+        if (f64) { f64->c[k] = f.o64[k]; f64->d[k] = f.a64[k]; f64->u[k] = f.u64[k]; f64->v[k] = f.v64[k]; f64->of[k] = f.P[k]; }
     }
+    if (ax) {   // (a straight map: the kind alone, the block zero)
+        memset(ax, 0, sizeof(*ax));
+        ax->kind = m->axis.kind;
+    }
+    if (ax && ax->kind != kAxisStraight) {
+        for (int k = 0; k < 3; ++k) { ax->ax.arc.n[k] = f.n[k]; ax->ax.arc.b[k] = f.b[k]; }
+        ax->ax.arc.kappa = f.kappa;
+        ax->ax.arc.un = f.un; ax->ax.arc.ub = f.ub; ax->ax.arc.vn = f.vn; ax->ax.arc.vb = f.vb;
+        ax->ax.rate = f.rate;
+    }
+    w.anchor = f.anchor;
     w.R = (float)d.R;
-    w.station_length = (float)ds;
+    w.station_length = (float)p.station_length;
     w.gate = (float)p.gate;
     w.sector_angle = (float)(kTwoPi / (double)p.n_sectors);
     w.two_pi = (float)kTwoPi;
     w.n_stations = p.n_stations;
     w.n_sectors = p.n_sectors;
     w.table = m->table;
-    add_window(p, reach, w);
+    add_window(p, m->axis.reach(p, ctx->cfg.boxFilterBound, f.a1), w);
     if (info) {
         memset(info, 0, sizeof(*info));
         info->struct_size = (uint32_t)sizeof(gm_wall_add_info);
@@ -375,7 +320,7 @@ gm_status cloud_chunks(gm_wall_map *map, const gm_wall_cloud_params &cp, gm_wall
         a.acc_cells = acc.take<uint32_t>(cb);
     }
     a.dirs = map->cl_dirs.p;
-    const DesignFrame &d = map->frame;
+    const DesignFrame &d = map->axis.d;
     for (int k = 0; k < 3; ++k) {
         a.oa[k] = d.o[k] - cp.anchor[k];
         a.a[k] = d.a[k]; a.u[k] = d.u[k]; a.v[k] = d.v[k];
@@ -386,27 +331,19 @@ gm_status cloud_chunks(gm_wall_map *map, const gm_wall_cloud_params &cp, gm_wall
     a.ds = map->prm.station_length;
     a.out = map->cl_stage.p;
     a.ctr = map->cl_ctr.p;
-    const bool on_arc = map->is_arc(), on_cl = map->is_clothoid();
-    WallCloudClothoid cc;
-    memset(&cc, 0, sizeof(cc));
-    if (on_cl) {
-        const ClothoidFrame &f = map->cf;
-        GMW_HIP(ctx, map->cl_rows.reserve((uint64_t)rows * 5));
-        map->cl_rows_host.resize((size_t)rows * 5);
-        cc.rows = map->cl_rows.p;
-        for (int k = 0; k < 3; ++k) { cc.n[k] = f.n[k]; cc.b[k] = f.b[k]; }
-        cc.un = f.un; cc.ub = f.ub; cc.vn = f.vn; cc.vb = f.vb;
-    }
-    WallCloudArc ca;
+    // the position rule of a curved axis: its constants, and a table of the chunk's block rows (DesignAxis::row)
+    const DesignAxis &axis = map->axis;
+    const uint32_t rw = axis.row_width();
+    WallCloudAxis ca;
     memset(&ca, 0, sizeof(ca));
-    if (on_arc) {
-        const ArcFrame &f = map->af;
-        GMW_HIP(ctx, map->cl_rows.reserve((uint64_t)rows * 2));
-        map->cl_rows_host.resize((size_t)rows * 2);
-        ca.rows = map->cl_rows.p;
-        for (int k = 0; k < 3; ++k) { ca.ca[k] = f.C[k] - cp.anchor[k]; ca.n[k] = f.n[k]; ca.b[k] = f.b[k]; }
-        ca.inv_kappa = f.inv_kappa;
-        ca.un = f.un; ca.ub = f.ub; ca.vn = f.vn; ca.vb = f.vb;
+    ca.kind = axis.kind;
+    if (rw) {
+        GMW_HIP(ctx, map->cl_rows.reserve((uint64_t)rows * rw));
+        map->cl_rows_host.resize((size_t)rows * rw);
+        ca.arc.rows = map->cl_rows.p;
+        for (int k = 0; k < 3; ++k) { ca.arc.ca[k] = axis.arc.C[k] - cp.anchor[k]; ca.arc.n[k] = axis.n[k]; ca.arc.b[k] = axis.b[k]; }
+        ca.arc.inv_kappa = axis.arc.inv_kappa;
+        ca.arc.un = axis.un; ca.arc.ub = axis.ub; ca.arc.vn = axis.vn; ca.arc.vb = axis.vb;
     }
 
     uint64_t total = 0;
@@ -420,41 +357,18 @@ gm_status cloud_chunks(gm_wall_map *map, const gm_wall_cloud_params &cp, gm_wall
             launch_wall_cloud_merge(a, map->stream);
             GMW_HIP(ctx, hipGetLastError());
         }
-        if (on_arc) {   // (cos psi, sin psi) of the chunk's block rows: tc by the emit step's rule
+        if (rw) {   // the rows at their centre chainages: tc by the emit step's rule
             for (uint32_t jl = 0; jl < a.nJ; ++jl) {
                 const uint32_t jw = (J0 + jl) * bs, ns = std::min(n - jw, bs);
                 const double h = (double)(2u * (station0 + jw) + ns) * 0.5;
-                const double tc = a.t_min + h * a.ds;
-                const double psi = map->af.kappa * (tc - map->af.s0);
-                map->cl_rows_host[2 * (size_t)jl] = cos(psi);
-                map->cl_rows_host[2 * (size_t)jl + 1] = sin(psi);
+                axis.row(a.t_min + h * a.ds, cp.anchor, &map->cl_rows_host[(size_t)rw * jl]);
             }   // (the last chunk's copy has been waited for: every trip ends with a synchronisation)
-            GMW_HIP(ctx, hipMemcpyAsync(map->cl_rows.p, map->cl_rows_host.data(), (size_t)a.nJ * 16, hipMemcpyHostToDevice, map->stream));
-        }
-        if (on_cl) {   // (P(tc) - anchor, cos psi, sin psi) of the chunk's block rows: tc by the emit step's rule
-            const ClothoidFrame &f = map->cf;
-            for (uint32_t jl = 0; jl < a.nJ; ++jl) {
-                const uint32_t jw = (J0 + jl) * bs, ns = std::min(n - jw, bs);
-                const double h = (double)(2u * (station0 + jw) + ns) * 0.5;
-                const double tc = a.t_min + h * a.ds;
-                double as[3], nsec_[3], P[3];
-                const double tau = tc - f.s0;
-                clothoid_section(d, f, tau, as, nsec_, P);
-                const double psi = f.psi(tau);
-                double *row = &map->cl_rows_host[5 * (size_t)jl];
-                for (int k = 0; k < 3; ++k) row[k] = P[k] - cp.anchor[k];
-                row[3] = cos(psi);
-                row[4] = sin(psi);
-            }   // (the last chunk's copy has been waited for: every trip ends with a synchronisation)
-            GMW_HIP(ctx, hipMemcpyAsync(map->cl_rows.p, map->cl_rows_host.data(), (size_t)a.nJ * 40, hipMemcpyHostToDevice, map->stream));
+            GMW_HIP(ctx, hipMemcpyAsync(map->cl_rows.p, map->cl_rows_host.data(), (size_t)a.nJ * rw * 8, hipMemcpyHostToDevice,
+                                        map->stream));
         }
         const ScanState st = map->cl_scan.next(map->stream);
-        if (mesh && on_cl) launch_wall_mesh_vertices_clothoid(a, cc, mesh->rank, mesh->mean, (uint32_t)total, st, map->stream);
-        else if (on_cl) launch_wall_cloud_compact_clothoid(a, cc, st, map->stream);
-        else if (mesh && on_arc) launch_wall_mesh_vertices_arc(a, ca, mesh->rank, mesh->mean, (uint32_t)total, st, map->stream);
-        else if (mesh) launch_wall_mesh_vertices(a, mesh->rank, mesh->mean, (uint32_t)total, st, map->stream);
-        else if (on_arc) launch_wall_cloud_compact_arc(a, ca, st, map->stream);
-        else launch_wall_cloud_compact(a, st, map->stream);
+        if (mesh) launch_wall_mesh_vertices(a, ca, mesh->rank, mesh->mean, (uint32_t)total, st, map->stream);
+        else launch_wall_cloud_compact(a, ca, st, map->stream);
         GMW_HIP(ctx, hipGetLastError());
         GMW_HIP(ctx, hipMemcpyAsync(ctr, a.ctr, sizeof(ctr), hipMemcpyDeviceToHost, map->stream));
         GMW_HIP(ctx, hipStreamSynchronize(map->stream));
@@ -495,21 +409,16 @@ static gm_status create_map(gm_ctx *ctx, const gm_wall_params *params, const gm_
     *map = nullptr;
     if (check_params(params) != GM_OK)
         return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_create: NULL, struct_size mismatch or a parameter outside its limits");
-    DesignFrame arc_d;
-    ArcFrame arc_f;
-    memset(&arc_f, 0, sizeof(arc_f));
-    if (arc && arc_check(params, arc, arc_d, arc_f) != GM_OK)
-        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_create_arc: struct_size mismatch, or a curvature outside its limits for this map");
-    ClothoidFrame cl_f;
-    if (cl) {
-        const gm_status st = clothoid_check(params, cl, arc_d, cl_f);
-        if (st == GM_ERR_OOM) return gm_fail(ctx, GM_ERR_OOM, "gm_wall_map_create_clothoid: no memory for the table of station starts");
-        if (st != GM_OK)
-            return gm_fail(ctx, GM_ERR_INVALID_ARG,
-                           "gm_wall_map_create_clothoid: struct_size mismatch, or a normal, curvature or rate outside its limits for this map");
-    }
+    DesignAxis axis;
+    const gm_status ast = axis_check(params, arc, cl, axis);
+    if (ast == GM_ERR_OOM) return gm_fail(ctx, GM_ERR_OOM, "gm_wall_map_create_clothoid: no memory for the table of station starts");
+    if (ast != GM_OK)
+        return gm_fail(ctx, GM_ERR_INVALID_ARG,
+                       arc ? "gm_wall_map_create_arc: struct_size mismatch, or a curvature outside its limits for this map"
+                           : "gm_wall_map_create_clothoid: struct_size mismatch, or a normal, curvature or rate outside its limits for this map");
     GMW_OK(set_device(ctx));
     gm_wall_map *m = new gm_wall_map;
+    m->axis = std::move(axis);
     m->ctx = ctx;
     m->prm = *params;
     m->ncell = (uint64_t)params->n_stations * params->n_sectors;
@@ -551,14 +460,11 @@ static gm_status create_map(gm_ctx *ctx, const gm_wall_params *params, const gm_
         const unsigned long long v = strtoull(e, nullptr, 10);
         m->quantity_chunk = v < kStageBytes ? (uint32_t)v : 0u;
     }
-    design_frame_of(m->prm, m->frame);
     memset(&m->arc, 0, sizeof(m->arc));
     m->arc.struct_size = (uint32_t)sizeof(gm_wall_arc);
     if (arc) { m->arc = *arc; m->arc.reserved = 0u; }
-    m->af = arc_f;
     memset(&m->clothoid, 0, sizeof(m->clothoid));
     if (cl) m->clothoid = *cl;
-    m->cf = std::move(cl_f);
     auto body = [&]() -> gm_status {
         GMW_HIP(ctx, hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
         GMW_HIP(ctx, m->base.reserve(wall_table_bytes(m->ncell)));
@@ -627,12 +533,12 @@ gm_status gm_wall_map_add_frame(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, co
     Slot *sl = nullptr;
     GMW_OK(frame_call_head(map, ctx, slot, "gm_wall_map_add_frame", [] { return true; }, sl));
     WallArgs w;
-    WallClothoid ax;
+    WallAxis ax;
     GMW_OK(add_frame_args(map, pose, add_info, w, nullptr, &ax));
     GMW_OK(set_device(ctx));
     frame_points(ctx, *sl, w);
     GMW_OK(add_wait_readers(map, slot, sl->stream));
-    launch_add(map, w, ax, sl->n_in, sl->stream);
+    launch_wall_add(w, ax, nullptr, nullptr, sl->n_in, map->points_per_block, sl->stream);
     GMW_HIP(ctx, hipGetLastError());
     map->pending[slot] = 1;
     ++map->frames;
@@ -646,14 +552,14 @@ gm_status gm_wall_map_add_points(gm_wall_map *map, const float *xyz, uint32_t n,
     gm_ctx *ctx = map->ctx;
     if (n && !xyz) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_add_points: NULL xyz");
     WallArgs w;
-    WallClothoid ax;
+    WallAxis ax;
     GMW_OK(add_frame_args(map, pose, add_info, w, nullptr, &ax));
     StageCall sc{map, n, map->pt, residual, cell, nullptr, nullptr, nullptr};
     GMW_OK(sc.open());
     GMW_OK(sc.upload(xyz, labels, w));
     hipStream_t s = sc.sl->stream;
     GMW_OK(add_wait_readers(map, 0, s));   // (as gm_wall_map_add_frame; the staging slot is slot 0)
-    launch_add(map, w, ax, n, s);
+    launch_wall_add(w, ax, nullptr, nullptr, n, map->points_per_block, s);
     GMW_HIP(ctx, hipGetLastError());
     GMW_OK(sc.close());
     ++map->frames;
@@ -678,7 +584,7 @@ gm_status gm_wall_map_info(gm_wall_map *map, gm_wall_info *info)
     GMW_HIP(ctx, hipGetLastError());
     GMW_HIP(ctx, hipMemcpyAsync(tot, map->table.totals, sizeof(tot), hipMemcpyDeviceToHost, map->stream));
     GMW_HIP(ctx, hipStreamSynchronize(map->stream));
-    const DesignFrame &d = map->frame;
+    const DesignFrame &d = map->axis.d;
     memset(info, 0, sizeof(*info));
     info->struct_size = (uint32_t)sizeof(gm_wall_info);
     info->status = d.status;

@@ -35,7 +35,7 @@ uint64_t block_words(uint32_t n_cap) { return add_checked_block_words(n_cap); }
 
 // What one call enqueues on `s`, in this order: its block -- counters | mask words of n_cap points -- zeroed by ONE fill, the
 // mark over up to rows_cap rows, the masked add.  mk: rows, counts and parameters filled by the caller; blk: the call's.
-gm_status add_checked_enqueue(gm_wall_map *m, WallMarkArgs &mk, const WallArgs &w, const WallClothoid &ax, uint32_t n_cap,
+gm_status add_checked_enqueue(gm_wall_map *m, WallMarkArgs &mk, const WallArgs &w, const WallAxis &ax, uint32_t n_cap,
                               DevArray<unsigned long long> &blk, hipStream_t s)
 {
     gm_ctx *ctx = m->ctx;
@@ -44,9 +44,7 @@ gm_status add_checked_enqueue(gm_wall_map *m, WallMarkArgs &mk, const WallArgs &
     mk.ctr = blk.p;
     mk.mask = reinterpret_cast<uint32_t *>(blk.p + kWallAddCheckedCounters);
     launch_wall_mark(mk, mk.rows_cap, s);
-    if (m->is_clothoid()) launch_wall_add_clothoid_masked(w, ax, blk.p + kWallAddCheckedCounters, blk.p, n_cap, m->points_per_block, s);
-    else if (m->is_arc()) launch_wall_add_arc_masked(w, ax.arc, blk.p + kWallAddCheckedCounters, blk.p, n_cap, m->points_per_block, s);
-    else launch_wall_add_masked(w, blk.p + kWallAddCheckedCounters, blk.p, n_cap, m->points_per_block, s);
+    launch_wall_add(w, ax, blk.p + kWallAddCheckedCounters, blk.p, n_cap, m->points_per_block, s);
     GMW_HIP(ctx, hipGetLastError());
     return GM_OK;
 }
@@ -69,7 +67,7 @@ gm_status gm_wall_map_add_frame_checked(gm_wall_map *map, gm_ctx *ctx, uint32_t 
     Slot *sl = nullptr;
     GMW_OK(frame_call_head(map, ctx, slot, "gm_wall_map_add_frame_checked", [&] { return add_checked_prm_ok(ap, mk.S); }, sl));
     WallArgs w;
-    WallClothoid ax;
+    WallAxis ax;
     GMW_OK(add_frame_args(map, pose, add_info, w, nullptr, &ax));
     WallCheckSlot &c = map->checks[slot];
     if (!c.res.have || c.cloud_seq != sl->cloud_seq)
@@ -92,7 +90,7 @@ gm_status gm_wall_map_add_frame_checked(gm_wall_map *map, gm_ctx *ctx, uint32_t 
     GMW_OK(add_checked_enqueue(map, mk, w, ax, n_cap, ac.blk, sl->stream));
     GMW_HIP(ctx, hipMemcpyAsync(ac.h_ctr.p, ac.blk.p, kWallAddCheckedCounters * 8, hipMemcpyDeviceToHost, sl->stream));
     GMW_OK(ac.res.record(ctx, sl->stream));
-    ac.status = map->frame.status;
+    ac.status = map->axis.d.status;
     ac.S = mk.S;
     map->pending[slot] = 1;
     ++map->frames;
@@ -128,7 +126,7 @@ gm_status gm_wall_map_add_points_checked(gm_wall_map *map, const float *xyz, uin
     if (!add_checked_prm_ok(ap, mk.S))
         return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_add_points_checked: struct_size mismatch or a parameter outside its limits");
     WallArgs w;
-    WallClothoid ax;
+    WallAxis ax;
     GMW_OK(add_frame_args(map, pose, add_info, w, nullptr, &ax));
     StageCall sc{map, n, map->pt, residual, cell, nullptr, nullptr, nullptr};
     GMW_OK(sc.open());
@@ -147,7 +145,7 @@ gm_status gm_wall_map_add_points_checked(gm_wall_map *map, const float *xyz, uin
     GMW_HIP(ctx, hipMemcpyAsync(h, map->ac_blk.p, sizeof(h), hipMemcpyDeviceToHost, s));
     GMW_OK(sc.close());   // (blocks: h is filled)
     ++map->frames;
-    if (info) fill_info(info, map->frame.status, mk.S, h);
+    if (info) fill_info(info, map->axis.d.status, mk.S, h);
     return GM_OK;
 }
 

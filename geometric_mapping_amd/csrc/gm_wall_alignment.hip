@@ -36,18 +36,17 @@ gm_status joint_sides(gm_wall_map *const (&map)[GM_WALL_JOINT_MAX_SIDES], const 
     for (uint32_t k = 0; k < ns; ++k) {
         gm_wall_map *m = map[k];
         WallArgs w;
-        WallClothoid ax;
-        memset(&ax, 0, sizeof(ax));
+        WallAxis ax;
         GMW_OK(add_frame_args(m, pose, nullptr, w, nullptr, &ax));
         WallJointSide &S = side[k];
         S.anchor = w.anchor;
         for (int c = 0; c < 3; ++c) { S.o[c] = w.o[c]; S.a[c] = w.a[c]; S.u[c] = w.u[c]; S.v[c] = w.v[c]; }
-        S.ax = ax;
+        S.ax = ax.ax;
         S.table = w.table;
         S.n_stations = w.n_stations;
         S.win_first = w.win_first;
         S.win_stations = w.win_stations;
-        S.axis = m->is_clothoid() ? kAxisClothoid : (m->is_arc() ? kAxisArc : kAxisStraight);
+        S.axis = ax.kind;
         S.element = (int32_t)plan.side_element[k];
         if (k == 0u) grid = WallJointGrid{w.R, w.station_length, w.sector_angle, w.two_pi, w.n_sectors};
     }
@@ -132,8 +131,8 @@ gm_status gm_wall_alignment_create(gm_ctx *ctx, const gm_wall_params *params, co
     for (const AlignElem &E : al->A.el) {
         gm_wall_map *m = nullptr;
         gm_status ms;
-        if (E.kind == GM_WALL_ELEMENT_CLOTHOID) ms = gm_wall_map_create_clothoid(ctx, &E.p, &E.cl, &m);
-        else if (E.kind == GM_WALL_ELEMENT_ARC) ms = gm_wall_map_create_arc(ctx, &E.p, &E.arc, &m);
+        if (E.ax.is_clothoid()) ms = gm_wall_map_create_clothoid(ctx, &E.p, &E.cl, &m);
+        else if (E.ax.is_arc()) ms = gm_wall_map_create_arc(ctx, &E.p, &E.arc, &m);
         else ms = gm_wall_map_create(ctx, &E.p, &m);
         if (ms != GM_OK) {
             free_alignment(al, true);

@@ -159,14 +159,11 @@ gm_status joint_add_masked(gm_wall_alignment *al, JointAdd &j, const double pose
     } else {
         gm_wall_map *m = j.side[0];
         WallArgs w;
-        WallClothoid ax;
-        memset(&ax, 0, sizeof(ax));
+        WallAxis ax;
         GMW_OK(add_frame_args(m, pose, nullptr, w, nullptr, &ax));
         w.pts = pts.pts; w.labels = pts.labels; w.n_ptr = pts.n_ptr; w.n_host = pts.n_host;
         w.res = pts.res; w.cell = pts.cell;
-        if (m->is_clothoid()) launch_wall_add_clothoid_masked(w, ax, mask, blk, n_cap, m->points_per_block, s);
-        else if (m->is_arc()) launch_wall_add_arc_masked(w, ax.arc, mask, blk, n_cap, m->points_per_block, s);
-        else launch_wall_add_masked(w, mask, blk, n_cap, m->points_per_block, s);
+        launch_wall_add(w, ax, mask, blk, n_cap, m->points_per_block, s);
     }
     GMW_HIP(al->ctx, hipGetLastError());
     return GM_OK;

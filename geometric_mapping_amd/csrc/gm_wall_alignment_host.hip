@@ -1,7 +1,8 @@
 // gm_wall_alignment_host.hip -- the part of the wall alignment's C ABI that needs no device (include/gm_hip.h states the
 // rule): the chaining of the element maps, the joint planes, ownership, project, point, the chainage window and the plan
-// of an add.  Like gm_wall_host.hip it links against libm and the C++ library alone; host/gm_wall_alignment_host_test.cpp
-// runs it under the host sanitizers.
+// of an add.  Every element is a DesignAxis (gm_wall_map.hpp): its section, project, point and per-add frame are the
+// element map's own, asked of the axis.  Like gm_wall_host.hip it links against libm and the C++ library alone;
+// host/gm_wall_alignment_host_test.cpp runs it under the host sanitizers.
 #include <stdio.h>
 
 #include <vector>
@@ -15,22 +16,8 @@ using namespace gm::wall;
 namespace gm {
 namespace wall {
 
-// the section at the element's end: P(s_end), a(s_end), u(s_end)
-static void element_end(const AlignElem &E, double P[3], double a[3], double u[3])
-{
-    if (E.kind == GM_WALL_ELEMENT_ARC) {
-        double ns[3];
-        arc_section(E.d, E.af, E.s_end, a, ns, P);
-        for (int k = 0; k < 3; ++k) u[k] = E.af.un * ns[k] + E.af.ub * E.af.b[k];
-    } else if (E.kind == GM_WALL_ELEMENT_CLOTHOID) {
-        double ns[3];
-        clothoid_section(E.d, E.cf, E.s_end - E.cf.s0, a, ns, P);
-        for (int k = 0; k < 3; ++k) u[k] = E.cf.un * ns[k] + E.cf.ub * E.cf.b[k];
-    } else {
-        const double t = E.p.t_min + (double)E.p.n_stations * E.p.station_length;
-        for (int k = 0; k < 3; ++k) { P[k] = E.d.o[k] + t * E.d.a[k]; a[k] = E.d.a[k]; u[k] = E.d.u[k]; }
-    }
-}
+static_assert(GM_WALL_ELEMENT_STRAIGHT == kAxisStraight && GM_WALL_ELEMENT_ARC == kAxisArc && GM_WALL_ELEMENT_CLOTHOID == kAxisClothoid,
+              "an element's kind is its axis' kind");
 
 gm_status alignment_build(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n, Alignment &A)
 {
@@ -51,90 +38,51 @@ gm_status alignment_build(const gm_wall_params *params, const gm_wall_element *e
         if (e.struct_size != sizeof(gm_wall_element) || e.reserved != 0u || e.kind > GM_WALL_ELEMENT_CLOTHOID || e.n_stations < 1u)
             return GM_ERR_INVALID_ARG;
         AlignElem &E = A.el[i];
-        E.kind = e.kind;
         E.p = t;
         E.p.n_stations = e.n_stations;
         E.s_start = s;
         E.s_end = s + (double)e.n_stations * ds;
-        E.offset = 0.0;
         memset(&E.arc, 0, sizeof(E.arc));
         memset(&E.cl, 0, sizeof(E.cl));
-        memset(&E.af, 0, sizeof(E.af));
         if (!isfinite(E.s_end)) return GM_ERR_INVALID_ARG;
-        if (i > 0u) {
-            double P[3], a[3], u[3];
-            element_end(A.el[i - 1u], P, a, u);
-            for (int k = 0; k < 3; ++k) { E.p.point[k] = P[k]; E.p.direction[k] = a[k]; E.p.forward[k] = a[k]; E.p.up[k] = u[k]; }
+        if (i > 0u) {   // the frame at the end of the element before: its point, direction = forward, up
+            const AlignElem &B = A.el[i - 1u];
+            double v[3];
+            B.ax.frame(B.p.t_min + (double)B.p.n_stations * B.p.station_length, E.p.point, E.p.direction, E.p.up, v);
+            for (int k = 0; k < 3; ++k) E.p.forward[k] = E.p.direction[k];
             E.p.t_min = s;
         }
         if (check_params(&E.p) != GM_OK) return GM_ERR_INVALID_ARG;
-        design_frame_of(E.p, E.d);
-        double m[3] = {0.0, 0.0, 0.0};
+        DesignFrame d;
+        design_frame_of(E.p, d);
         if (e.kind != GM_WALL_ELEMENT_STRAIGHT) {
             const double tl = sqrt(e.turn[0] * e.turn[0] + e.turn[1] * e.turn[1]);
             if (!isfinite(tl) || !(tl > 0.0) || !isfinite(e.curvature)) return GM_ERR_INVALID_ARG;
             const double t0 = e.turn[0] / tl, t1 = e.turn[1] / tl;
-            for (int k = 0; k < 3; ++k) m[k] = t0 * E.d.u[k] + t1 * E.d.v[k];
-        }
-        if (e.kind == GM_WALL_ELEMENT_ARC) {
-            if (!(e.curvature > 0.0)) return GM_ERR_INVALID_ARG;
-            E.arc.struct_size = (uint32_t)sizeof(gm_wall_arc);
-            for (int k = 0; k < 3; ++k) E.arc.curvature[k] = e.curvature * m[k];
-            E.arc.point_chainage = s;
-            if (arc_check(&E.p, &E.arc, E.d, E.af) != GM_OK) return GM_ERR_INVALID_ARG;
-        } else if (e.kind == GM_WALL_ELEMENT_CLOTHOID) {
-            E.cl.struct_size = (uint32_t)sizeof(gm_wall_clothoid);
-            for (int k = 0; k < 3; ++k) E.cl.normal[k] = m[k];
-            E.cl.curvature = e.curvature;
-            E.cl.rate = e.rate;
-            E.cl.point_chainage = s;
-            const gm_status st = clothoid_check(&E.p, &E.cl, E.d, E.cf);
-            if (st != GM_OK) return st == GM_ERR_OOM ? GM_ERR_OOM : GM_ERR_INVALID_ARG;
+            double m[3];
+            for (int k = 0; k < 3; ++k) m[k] = t0 * d.u[k] + t1 * d.v[k];
+            if (e.kind == GM_WALL_ELEMENT_ARC) {
+                if (!(e.curvature > 0.0)) return GM_ERR_INVALID_ARG;
+                E.arc.struct_size = (uint32_t)sizeof(gm_wall_arc);
+                for (int k = 0; k < 3; ++k) E.arc.curvature[k] = e.curvature * m[k];
+                E.arc.point_chainage = s;
+            } else {
+                E.cl.struct_size = (uint32_t)sizeof(gm_wall_clothoid);
+                for (int k = 0; k < 3; ++k) E.cl.normal[k] = m[k];
+                E.cl.curvature = e.curvature;
+                E.cl.rate = e.rate;
+                E.cl.point_chainage = s;
+            }
         } else if (i > 0u) {   // the straight rule's own chainage of `point`
-            E.p.t_min = dot(E.p.point, E.d.a);
-            if (check_params(&E.p) != GM_OK) return GM_ERR_INVALID_ARG;
-            E.offset = s - E.p.t_min;
+            E.p.t_min = dot(E.p.point, d.a);
         }
+        const gm_status st = axis_check(&E.p, E.arc.struct_size ? &E.arc : nullptr, E.cl.struct_size ? &E.cl : nullptr, E.ax);
+        if (st != GM_OK) return st == GM_ERR_OOM ? GM_ERR_OOM : GM_ERR_INVALID_ARG;
+        E.ax.offset = s - E.p.t_min;   // (0 but on a straight element behind the first)
         s = E.s_end;
     }
     A.ds = ds;
     return GM_OK;
-}
-
-// the element's own project rule on x: chainage along the alignment, angle, e
-static void element_project(const AlignElem &E, const double x[3], double &chainage, double &angle, double &e)
-{
-    double yc, zb, un, ub, vn, vb;
-    if (E.kind == GM_WALL_ELEMENT_STRAIGHT) {
-        const double r[3] = {x[0] - E.d.o[0], x[1] - E.d.o[1], x[2] - E.d.o[2]};
-        const double t = dot(r, E.d.a);
-        const double w[3] = {r[0] - t * E.d.a[0], r[1] - t * E.d.a[1], r[2] - t * E.d.a[2]};
-        chainage = t + E.offset;
-        e = sqrt(dot(w, w)) - E.d.R;
-        const double th = atan2(dot(w, E.d.v), dot(w, E.d.u));
-        angle = th < 0.0 ? th + kTwoPi : th;
-        return;
-    }
-    if (E.kind == GM_WALL_ELEMENT_ARC) {   // gm_wall_arc_project
-        const ArcFrame &f = E.af;
-        const double r[3] = {x[0] - f.C[0], x[1] - f.C[1], x[2] - f.C[2]};
-        const double xa = dot(r, E.d.a), xn = dot(r, f.n);
-        zb = dot(r, f.b);
-        chainage = f.s0 + atan2(xa, -xn) / f.kappa;
-        yc = f.inv_kappa - sqrt(xa * xa + xn * xn);
-        un = f.un; ub = f.ub; vn = f.vn; vb = f.vb;
-    } else {   // gm_wall_clothoid_project
-        const ClothoidFrame &f = E.cf;
-        yc = 0.0;
-        const double tau = clothoid_foot(E.d, f, x, &yc, nullptr);
-        const double r[3] = {x[0] - f.pt[0], x[1] - f.pt[1], x[2] - f.pt[2]};
-        zb = dot(r, f.b);
-        chainage = f.s0 + tau;
-        un = f.un; ub = f.ub; vn = f.vn; vb = f.vb;
-    }
-    e = sqrt(yc * yc + zb * zb) - E.d.R;
-    const double th = atan2(yc * vn + zb * vb, yc * un + zb * ub);
-    angle = th < 0.0 ? th + kTwoPi : th;
 }
 
 // d_i(x) < 0 for joint i (between elements i and i + 1)
@@ -142,7 +90,7 @@ static bool before_joint(const Alignment &A, uint32_t i, const double x[3])
 {
     const AlignElem &N = A.el[i + 1u];
     const double r[3] = {x[0] - N.p.point[0], x[1] - N.p.point[1], x[2] - N.p.point[2]};
-    return dot(r, N.d.a) < 0.0;
+    return dot(r, N.ax.d.a) < 0.0;
 }
 
 // The owner looks at an element's OWN two joints only: element i is a candidate when x lies on its side of both (not before
@@ -161,11 +109,11 @@ void alignment_project(const Alignment &A, const double x[3], uint32_t &element,
         const bool candidate = after_prev && before_next;
         after_prev = !before_next;
         if (!candidate) continue;
-        double s, ph, ee;
-        element_project(A.el[i], x, s, ph, ee);
         const AlignElem &E = A.el[i];
+        double s, ph, ee;
+        E.ax.project(x, s, ph, ee);   // the element's own rule, in the alignment's chainage
         const double over = s < E.s_start ? E.s_start - s : (s > E.s_end ? s - E.s_end : 0.0);
-        const double rho = ee + E.d.R;
+        const double rho = ee + E.ax.d.R;
         double dist = sqrt(rho * rho + over * over);
         if (!isfinite(dist)) dist = INFINITY;
         if (!have || dist < best) {
@@ -191,48 +139,7 @@ void alignment_point(const Alignment &A, double chainage, double angle, double r
 {
     uint32_t i = 0;
     while (i + 1u < (uint32_t)A.el.size() && chainage >= A.el[i].s_end) ++i;
-    const AlignElem &E = A.el[i];
-    const double c = cos(angle), s = sin(angle);
-    if (E.kind == GM_WALL_ELEMENT_STRAIGHT) {
-        const double t = chainage - E.offset;
-        for (int k = 0; k < 3; ++k) xyz[k] = (E.d.o[k] + t * E.d.a[k]) + rho * (c * E.d.u[k] + s * E.d.v[k]);
-    } else if (E.kind == GM_WALL_ELEMENT_ARC) {   // gm_wall_arc_point
-        const ArcFrame &f = E.af;
-        const double psi = f.kappa * (chainage - f.s0);
-        const double cp = cos(psi), sp = sin(psi);
-        const double yc = rho * (c * f.un + s * f.vn), zb = rho * (c * f.ub + s * f.vb);
-        const double r = yc - f.inv_kappa;
-        for (int k = 0; k < 3; ++k) {
-            const double nr = f.n[k] * cp - E.d.a[k] * sp;
-            xyz[k] = (f.C[k] + r * nr) + zb * f.b[k];
-        }
-    } else {   // gm_wall_clothoid_point
-        const ClothoidFrame &f = E.cf;
-        double as[3], ns[3], P[3];
-        clothoid_section(E.d, f, chainage - f.s0, as, ns, P);
-        const double yc = rho * (c * f.un + s * f.vn), zb = rho * (c * f.ub + s * f.vb);
-        for (int k = 0; k < 3; ++k) xyz[k] = (P[k] + yc * ns[k]) + zb * f.b[k];
-    }
-}
-
-// the anchor station of the element map's own add under (Rm, tr); false: out of range
-static bool element_anchor(const AlignElem &E, const double Rm[3][3], const double tr[3], int64_t &anchor)
-{
-    if (E.kind == GM_WALL_ELEMENT_ARC) {
-        gm_wall_arc_add_info ai;
-        if (!arc_add_frame(E.p, E.d, E.af, Rm, tr, ai, nullptr, nullptr, nullptr)) return false;
-        anchor = ai.anchor_station;
-    } else if (E.kind == GM_WALL_ELEMENT_CLOTHOID) {
-        gm_wall_clothoid_add_info ai;
-        if (!clothoid_add_frame(E.p, E.d, E.cf, Rm, tr, ai, nullptr, nullptr, nullptr)) return false;
-        anchor = ai.anchor_station;
-    } else {   // add_frame_args' straight rule
-        const double rel[3] = {tr[0] - E.d.o[0], tr[1] - E.d.o[1], tr[2] - E.d.o[2]};
-        const double jd = floor((dot(rel, E.d.a) - E.p.t_min) / E.p.station_length);
-        if (!(fabs(jd) < 4.0e18)) return false;
-        anchor = (int64_t)jd;
-    }
-    return true;
+    A.el[i].ax.point(chainage, angle, rho, xyz);
 }
 
 gm_status alignment_add_plan(const Alignment &A, const double pose[12], double bound, gm_wall_alignment_add_info *info)
@@ -249,7 +156,7 @@ gm_status alignment_add_plan(const Alignment &A, const double pose[12], double b
     info->element = el;
     info->chainage = s;
     info->reach = L;
-    info->offset = A.el[el].offset;
+    info->offset = A.el[el].ax.offset;
     uint32_t lo = el, hi = el;
     while (lo > 0u && A.el[lo - 1u].s_end > s - L) --lo;
     while (hi + 1u < (uint32_t)A.el.size() && A.el[hi + 1u].s_start < s + L) ++hi;
@@ -259,14 +166,16 @@ gm_status alignment_add_plan(const Alignment &A, const double pose[12], double b
     for (uint32_t k = 0; k < ns; ++k) {
         const AlignElem &E = A.el[lo + k];
         info->side_element[k] = lo + k;
-        info->status |= E.d.status;
-        if (!element_anchor(E, Rm, tr, info->side_anchor[k])) return GM_ERR_INVALID_ARG;
+        info->status |= E.ax.d.status;
+        AxisAddFrame f;   // of the element map's own add
+        if (!E.ax.add_frame(E.p, Rm, tr, f)) return GM_ERR_INVALID_ARG;
+        info->side_anchor[k] = f.anchor;
         if (k + 1u < ns) {
             const AlignElem &N = A.el[lo + k + 1u];
             const double r[3] = {N.p.point[0] - tr[0], N.p.point[1] - tr[1], N.p.point[2] - tr[2]};
             for (int c = 0; c < 3; ++c) {   // Rm^T x
                 info->joint_o[k][c] = (float)(Rm[0][c] * r[0] + Rm[1][c] * r[1] + Rm[2][c] * r[2]);
-                info->joint_a[k][c] = (float)(Rm[0][c] * N.d.a[0] + Rm[1][c] * N.d.a[1] + Rm[2][c] * N.d.a[2]);
+                info->joint_a[k][c] = (float)(Rm[0][c] * N.ax.d.a[0] + Rm[1][c] * N.ax.d.a[1] + Rm[2][c] * N.ax.d.a[2]);
             }
         }
     }
@@ -277,30 +186,16 @@ gm_status alignment_add_plan(const Alignment &A, const double pose[12], double b
 // element (o, a, u, v on a straight one), (u, v) = u(s_f), v(s_f), and ax = kappa_f, rate, un, ub, vn, vb as the add rounds them.
 static void element_anchor_section(const AlignElem &E, int64_t anchor, double S[4][3], double u[3], double v[3], float ax[6])
 {
-    const double ds = E.p.station_length;
-    for (int k = 0; k < 6; ++k) ax[k] = 0.0f;
-    if (E.kind == GM_WALL_ELEMENT_STRAIGHT) {
-        const double off = E.p.t_min + (double)anchor * ds;
-        for (int k = 0; k < 3; ++k) {
-            S[0][k] = E.d.o[k] + off * E.d.a[k];
-            S[1][k] = E.d.a[k]; S[2][k] = u[k] = E.d.u[k]; S[3][k] = v[k] = E.d.v[k];
-        }
-        return;
+    const DesignAxis &X = E.ax;
+    const bool straight = X.kind == kAxisStraight;
+    const double kf = X.station_section(E.p, (double)anchor, S[1], S[2], S[0]);
+    for (int k = 0; k < 3; ++k) {
+        S[3][k] = straight ? X.d.v[k] : X.b[k];
+        u[k] = straight ? S[2][k] : X.un * S[2][k] + X.ub * S[3][k];
+        v[k] = straight ? S[3][k] : X.vn * S[2][k] + X.vb * S[3][k];
     }
-    double un, ub, vn, vb;
-    if (E.kind == GM_WALL_ELEMENT_ARC) {
-        arc_section(E.d, E.af, E.p.t_min + (double)anchor * ds, S[1], S[2], S[0]);
-        for (int k = 0; k < 3; ++k) S[3][k] = E.af.b[k];
-        un = E.af.un; ub = E.af.ub; vn = E.af.vn; vb = E.af.vb;
-        ax[0] = (float)E.af.kappa;
-    } else {
-        ax[0] = (float)clothoid_section(E.d, E.cf, E.cf.tau0 + (double)anchor * ds, S[1], S[2], S[0]);
-        for (int k = 0; k < 3; ++k) S[3][k] = E.cf.b[k];
-        un = E.cf.un; ub = E.cf.ub; vn = E.cf.vn; vb = E.cf.vb;
-        ax[1] = (float)E.cf.rate;
-    }
-    ax[2] = (float)un; ax[3] = (float)ub; ax[4] = (float)vn; ax[5] = (float)vb;
-    for (int k = 0; k < 3; ++k) { u[k] = un * S[2][k] + ub * S[3][k]; v[k] = vn * S[2][k] + vb * S[3][k]; }
+    ax[0] = (float)kf; ax[1] = (float)X.cl.rate;   // (0 where the axis has none)
+    ax[2] = (float)X.un; ax[3] = (float)X.ub; ax[4] = (float)X.vn; ax[5] = (float)X.vb;
 }
 
 gm_status alignment_locate_start(const Alignment &A, const double pose[12], double bound, gm_wall_alignment_locate_start *out)
@@ -335,17 +230,17 @@ gm_status alignment_locate_start(const Alignment &A, const double pose[12], doub
         const AlignElem &E = A.el[pl.side_element[k]];
         double S[4][3], su[3], sv[3];
         element_anchor_section(E, pl.side_anchor[k], S, su, sv, out->side_axis[k]);
-        out->side_kind[k] = E.kind;
+        out->side_kind[k] = (uint32_t)E.ax.kind;
         for (int q = 0; q < 4; ++q) coords(S[q], q == 0, &out->side[k][3 * q]);
         if (k == out->home) {   // exactly itself
-            const bool straight = E.kind == GM_WALL_ELEMENT_STRAIGHT;
+            const bool straight = E.ax.kind == kAxisStraight;
             for (int q = 0; q < (straight ? 4 : 2); ++q)
                 for (int c = 0; c < 3; ++c) out->side[k][3 * q + c] = q > 0 && c == q - 1 ? 1.0 : 0.0;
         }
         if (k + 1u < pl.n_sides) {
             const AlignElem &N = A.el[pl.side_element[k] + 1u];
             coords(N.p.point, true, &out->joint[k][0]);
-            coords(N.d.a, false, &out->joint[k][3]);
+            coords(N.ax.d.a, false, &out->joint[k][3]);
         }
     }
     return GM_OK;

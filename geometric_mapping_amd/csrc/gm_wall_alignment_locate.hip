@@ -38,7 +38,7 @@ gm_status joint_locate_args(gm_wall_alignment *al, const double pose[12], const 
     a.n_sides = ns;
     a.reference = lp.reference;
     a.min_count = lp.min_count;
-    a.grid = WallJointGrid{(float)m0->frame.R, (float)m0->prm.station_length, (float)(kTwoPi / (double)m0->prm.n_sectors), (float)kTwoPi,
+    a.grid = WallJointGrid{(float)m0->axis.d.R, (float)m0->prm.station_length, (float)(kTwoPi / (double)m0->prm.n_sectors), (float)kTwoPi,
                            m0->prm.n_sectors};
     a.gate = lp.gate;
     a.s0 = S.s0;

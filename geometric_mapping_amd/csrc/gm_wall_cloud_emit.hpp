@@ -175,4 +175,22 @@ struct WallCloudEmitClothoid {
     }
 };
 
+// host side: the clothoid rule's struct of a launch's axis, and the compaction of a chunk's blocks under the emit step `emit`
+inline WallCloudClothoid wall_cloud_clothoid(const WallCloudAxis &axis)
+{
+    WallCloudClothoid cl;
+    cl.rows = axis.arc.rows;
+    for (int k = 0; k < 3; ++k) { cl.n[k] = axis.arc.n[k]; cl.b[k] = axis.arc.b[k]; }
+    cl.un = axis.arc.un; cl.ub = axis.arc.ub; cl.vn = axis.arc.vn; cl.vb = axis.arc.vb;
+    return cl;
+}
+template <class Emit>
+void wall_cloud_launch(const WallCloudArgs &a, const Emit &emit, const ScanState &st, hipStream_t s)
+{
+    const uint32_t nb = a.nJ * a.NK;   // >= 1
+    WallCloudPred pred{a};
+    hipLaunchKernelGGL((k_compact<WallCloudPred, Emit>), dim3(compact_grid(nb)), dim3(kCpThreads), 0, s, pred, emit,
+                       (const uint32_t *)nullptr, nb, st, reinterpret_cast<uint32_t *>(a.ctr + 2), (uint32_t *)nullptr);
+}
+
 }  // namespace gm

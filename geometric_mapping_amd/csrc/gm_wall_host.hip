@@ -1,10 +1,12 @@
 // gm_wall_host.hip -- the part of the wall map's C ABI that needs no device (include/gm_hip.h states each rule): the
 // defaults, the parameter checks, the classification of one cell, the metrics, the direction table, the mesh's triangle
 // rule and its PLY file, the gauge of a polygon, the runs, the align's selection, the sections' basis, solve and metrics,
-// the quantities' column, metrics and runs, the rules of a map on a circular-arc design axis (gm_wall_arc_*).
+// the quantities' column, metrics and runs, and the design axis of a map, straight, arc or clothoid (DesignAxis: what the
+// gm_wall_arc_* and gm_wall_clothoid_* entries, the alignment and the map's add, cloud and mesh all ask).
 // No device call, no context, no map: it links against libm and the C++ library alone, and host/gm_wall_host_test.cpp,
-// host/gm_wall_sections_host_test.cpp, host/gm_wall_mesh_host_test.cpp, host/gm_wall_quantities_host_test.cpp and
-// host/gm_wall_arc_host_test.cpp run it under the host sanitizers.
+// host/gm_wall_sections_host_test.cpp, host/gm_wall_mesh_host_test.cpp, host/gm_wall_quantities_host_test.cpp,
+// host/gm_wall_arc_host_test.cpp and host/gm_wall_clothoid_host_test.cpp run it under the host sanitizers;
+// host/gm_wall_axis_dump.cpp prints the axis entries' results for a comparison of two builds.
 #include <stdio.h>
 
 #include <vector>
@@ -67,87 +69,7 @@ void design_frame_of(const gm_wall_params &p, DesignFrame &d)
     d.R = p.radius;
 }
 
-gm_status arc_check(const gm_wall_params *p, const gm_wall_arc *arc, DesignFrame &d, ArcFrame &f)
-{
-    if (check_params(p) != GM_OK || !arc || arc->struct_size != sizeof(gm_wall_arc)) return GM_ERR_INVALID_ARG;
-    if (!isfinite(arc->curvature[0]) || !isfinite(arc->curvature[1]) || !isfinite(arc->curvature[2]) || !isfinite(arc->point_chainage))
-        return GM_ERR_INVALID_ARG;
-    design_frame_of(*p, d);
-    memset(&f, 0, sizeof(f));
-    const double ca = dot(arc->curvature, d.a);
-    double c[3];
-    for (int k = 0; k < 3; ++k) c[k] = arc->curvature[k] - ca * d.a[k];
-    const double kappa = sqrt(dot(c, c));
-    if (!isfinite(kappa) || kappa < 1e-6 || (p->radius + p->gate) * kappa > 0.5) return GM_ERR_INVALID_ARG;
-    const double s0 = arc->point_chainage, s_end = p->t_min + (double)p->n_stations * p->station_length;
-    if (!(fabs(kappa * (p->t_min - s0)) <= 3.0) || !(fabs(kappa * (s_end - s0)) <= 3.0)) return GM_ERR_INVALID_ARG;
-    f.kappa = kappa;
-    f.inv_kappa = 1.0 / kappa;
-    f.s0 = s0;
-    for (int k = 0; k < 3; ++k) f.n[k] = c[k] / kappa;
-    const double *a = d.a, *n = f.n;
-    f.b[0] = a[1] * n[2] - a[2] * n[1]; f.b[1] = a[2] * n[0] - a[0] * n[2]; f.b[2] = a[0] * n[1] - a[1] * n[0];
-    for (int k = 0; k < 3; ++k) f.C[k] = p->point[k] + f.n[k] * f.inv_kappa;
-    f.un = dot(d.u, f.n); f.ub = dot(d.u, f.b);
-    f.vn = dot(d.v, f.n); f.vb = dot(d.v, f.b);
-    return GM_OK;
-}
-
-void arc_section(const DesignFrame &d, const ArcFrame &f, double s, double as[3], double ns[3], double P[3])
-{
-    const double psi = f.kappa * (s - f.s0);
-    const double cp = cos(psi), sp = sin(psi);
-    for (int k = 0; k < 3; ++k) {
-        as[k] = d.a[k] * cp + f.n[k] * sp;
-        ns[k] = f.n[k] * cp - d.a[k] * sp;
-        P[k] = f.C[k] - ns[k] * f.inv_kappa;
-    }
-}
-
-double arc_chainage(const DesignFrame &d, const ArcFrame &f, const double x[3])
-{
-    const double r[3] = {x[0] - f.C[0], x[1] - f.C[1], x[2] - f.C[2]};
-    const double psi = atan2(dot(r, d.a), -dot(r, f.n));
-    return f.s0 + psi / f.kappa;
-}
-
-bool arc_add_frame(const gm_wall_params &p, const DesignFrame &d, const ArcFrame &f, const double Rm[3][3], const double tr[3],
-                   gm_wall_arc_add_info &out, double *u64, double *v64, double *a1)
-{
-    const double ds = p.station_length;
-    const double s = arc_chainage(d, f, tr);
-    const double jd = floor((s - p.t_min) / ds);
-    if (!(fabs(jd) < 4.0e18)) return false;
-    const double sf = p.t_min + jd * ds;
-    double as[3], ns[3], P[3];
-    arc_section(d, f, sf, as, ns, P);
-    const double of[3] = {P[0] - tr[0], P[1] - tr[1], P[2] - tr[2]};
-    out.anchor_station = (int64_t)jd;
-    out.sensor_chainage = s;
-    out.anchor_chainage = sf;
-    double l1 = 0.0;
-    for (int c = 0; c < 3; ++c) {   // Rm^T x
-        const double oo = Rm[0][c] * of[0] + Rm[1][c] * of[1] + Rm[2][c] * of[2];
-        const double aa = Rm[0][c] * as[0] + Rm[1][c] * as[1] + Rm[2][c] * as[2];
-        const double nn = Rm[0][c] * ns[0] + Rm[1][c] * ns[1] + Rm[2][c] * ns[2];
-        const double bb = Rm[0][c] * f.b[0] + Rm[1][c] * f.b[1] + Rm[2][c] * f.b[2];
-        out.o[c] = (float)oo; out.a[c] = (float)aa; out.n[c] = (float)nn; out.b[c] = (float)bb;
-        if (u64) u64[c] = f.un * nn + f.ub * bb;
-        if (v64) v64[c] = f.vn * nn + f.vb * bb;
-        l1 += fabs(aa);
-    }
-    if (a1) *a1 = l1;
-    out.kappa = (float)f.kappa;
-    out.un = (float)f.un; out.ub = (float)f.ub; out.vn = (float)f.vn; out.vb = (float)f.vb;
-    out.R = (float)d.R;
-    out.station_length = (float)ds;
-    out.sector_angle = (float)(kTwoPi / (double)p.n_sectors);
-    out.gate = (float)p.gate;
-    out.reserved = 0u;
-    return true;
-}
-
-// ---- a clothoid design axis (include/gm_hip.h: gm_wall_map_create_clothoid) ----
+// ---- the design axis (gm_wall_map.hpp: DesignAxis).  The clothoid's quadrature, table and Newton foot first ----
 
 // the 8-node Gauss-Legendre rule on [-1, 1]
 static const double kGl8X[8] = {-0.9602898564975362, -0.7966664774136267, -0.525532409916329, -0.18343464249564978,
@@ -178,55 +100,8 @@ static void clothoid_integrate(const ClothoidFrame &f, double ta, double tb, dou
     Y += sy_all;
 }
 
-gm_status clothoid_check(const gm_wall_params *p, const gm_wall_clothoid *cl, DesignFrame &d, ClothoidFrame &f)
-{
-    if (check_params(p) != GM_OK || !cl || cl->struct_size != sizeof(gm_wall_clothoid) || cl->reserved != 0u) return GM_ERR_INVALID_ARG;
-    if (!isfinite(cl->normal[0]) || !isfinite(cl->normal[1]) || !isfinite(cl->normal[2]) || !isfinite(cl->curvature) ||
-        !isfinite(cl->rate) || !isfinite(cl->point_chainage))
-        return GM_ERR_INVALID_ARG;
-    design_frame_of(*p, d);
-    f = ClothoidFrame();
-    const double na = dot(cl->normal, d.a);
-    double m[3];
-    for (int k = 0; k < 3; ++k) m[k] = cl->normal[k] - na * d.a[k];
-    const double lm = sqrt(dot(m, m)), l0 = sqrt(dot(cl->normal, cl->normal));
-    if (!isfinite(lm) || !(lm > 1e-6 * l0) || !(lm > 0.0)) return GM_ERR_INVALID_ARG;
-    const double L = (double)p->n_stations * p->station_length;
-    if (fabs(cl->rate) * L < 1e-6) return GM_ERR_INVALID_ARG;
-    f.k0 = cl->curvature;
-    f.rate = cl->rate;
-    f.s0 = cl->point_chainage;
-    f.tau0 = p->t_min - f.s0;
-    f.ds = p->station_length;
-    f.nst = p->n_stations;
-    const double t0 = f.tau0, t1 = f.tau0 + L;
-    const double kmax = std::max(fabs(f.kappa(t0)), fabs(f.kappa(t1)));
-    if (!((p->radius + p->gate) * kmax <= 0.5)) return GM_ERR_INVALID_ARG;
-    if (!(fabs(f.psi(t0)) <= 3.0) || !(fabs(f.psi(t1)) <= 3.0)) return GM_ERR_INVALID_ARG;
-    const double tz = -f.k0 / f.rate;   // kappa = 0 there
-    if (t0 < tz && tz < t1 && !(fabs(f.psi(tz)) <= 3.0)) return GM_ERR_INVALID_ARG;
-    for (int k = 0; k < 3; ++k) { f.pt[k] = p->point[k]; f.n[k] = m[k] / lm; }
-    const double *a = d.a, *n = f.n;
-    f.b[0] = a[1] * n[2] - a[2] * n[1]; f.b[1] = a[2] * n[0] - a[0] * n[2]; f.b[2] = a[0] * n[1] - a[1] * n[0];
-    f.un = dot(d.u, f.n); f.ub = dot(d.u, f.b);
-    f.vn = dot(d.v, f.n); f.vb = dot(d.v, f.b);
-    try {
-        f.tab.assign(2 * ((size_t)f.nst + 1), 0.0);
-    } catch (...) {
-        return GM_ERR_OOM;
-    }
-    double X = 0.0, Y = 0.0;
-    clothoid_integrate(f, 0.0, f.tau0, X, Y);
-    f.tab[0] = X; f.tab[1] = Y;
-    for (uint32_t j = 0; j < f.nst; ++j) {
-        clothoid_integrate(f, f.tau0 + (double)j * f.ds, f.tau0 + (double)(j + 1u) * f.ds, X, Y);
-        f.tab[2 * ((size_t)j + 1)] = X; f.tab[2 * ((size_t)j + 1) + 1] = Y;
-    }
-    f.on = true;
-    return GM_OK;
-}
-
-void clothoid_xy(const ClothoidFrame &f, double tau, double &X, double &Y)
+// (X, Y) at tau = s - s0: the table entry at or below it plus the panels from there
+static void clothoid_xy(const ClothoidFrame &f, double tau, double &X, double &Y)
 {
     const double jd = floor((tau - f.tau0) / f.ds);
     const size_t j = jd >= 0.0 ? (jd < (double)f.nst ? (size_t)jd : (size_t)f.nst) : 0;   // (a NaN: 0)
@@ -235,24 +110,12 @@ void clothoid_xy(const ClothoidFrame &f, double tau, double &X, double &Y)
     clothoid_integrate(f, f.tau0 + (double)j * f.ds, tau, X, Y);
 }
 
-double clothoid_section(const DesignFrame &d, const ClothoidFrame &f, double tau, double as[3], double ns[3], double P[3])
+// the foot of the perpendicular of a map point on a clothoid axis: returns tau; yc of the final evaluation
+static double clothoid_foot(const DesignAxis &ax, const double x[3], double &yc)
 {
-    const double psi = f.psi(tau);
-    const double cp = cos(psi), sp = sin(psi);
-    double X, Y;
-    clothoid_xy(f, tau, X, Y);
-    for (int k = 0; k < 3; ++k) {
-        as[k] = d.a[k] * cp + f.n[k] * sp;
-        ns[k] = f.n[k] * cp - d.a[k] * sp;
-        P[k] = (f.pt[k] + X * d.a[k]) + Y * f.n[k];
-    }
-    return f.kappa(tau);
-}
-
-double clothoid_foot(const DesignFrame &d, const ClothoidFrame &f, const double x[3], double *yc_out, double *g_out)
-{
+    const ClothoidFrame &f = ax.cl;
     const double r[3] = {x[0] - f.pt[0], x[1] - f.pt[1], x[2] - f.pt[2]};
-    const double xa = dot(r, d.a), xn = dot(r, f.n);
+    const double xa = dot(r, ax.d.a), xn = dot(r, ax.n);
     size_t best = 0;
     double best_d2 = INFINITY;
     for (size_t j = 0; j <= (size_t)f.nst; ++j) {
@@ -260,59 +123,258 @@ double clothoid_foot(const DesignFrame &d, const ClothoidFrame &f, const double 
         const double d2 = ex * ex + ey * ey;
         if (d2 < best_d2) { best_d2 = d2; best = j; }
     }
-    double tau = f.tau0 + (double)best * f.ds, g = 0.0, yc = 0.0;
+    double tau = f.tau0 + (double)best * f.ds;
     for (int it = 0; it <= GM_WALL_CLOTHOID_HOST_STEPS; ++it) {
         double X, Y;
         clothoid_xy(f, tau, X, Y);
         const double psi = f.psi(tau);
         const double c = cos(psi), s = sin(psi);
         const double dx = xa - X, dy = xn - Y;
-        g = dx * c + dy * s;
+        const double g = dx * c + dy * s;
         yc = dy * c - dx * s;
         if (it < GM_WALL_CLOTHOID_HOST_STEPS) tau = tau + g / (1.0 - f.kappa(tau) * yc);
     }
-    if (yc_out) *yc_out = yc;
-    if (g_out) *g_out = g;
     return tau;
 }
 
-bool clothoid_add_frame(const gm_wall_params &p, const DesignFrame &d, const ClothoidFrame &f, const double Rm[3][3],
-                        const double tr[3], gm_wall_clothoid_add_info &out, double *u64, double *v64, double *a1)
+// the section of a curved axis at tau = s - s0: a(s), n(s), P(s); returns kappa(s)
+static double curved_section(const DesignAxis &ax, double tau, double as[3], double ns[3], double P[3])
+{
+    const bool on_cl = ax.kind == kAxisClothoid;
+    const double psi = on_cl ? ax.cl.psi(tau) : ax.arc.kappa * tau;
+    const double cp = cos(psi), sp = sin(psi);
+    double X = 0.0, Y = 0.0;
+    if (on_cl) clothoid_xy(ax.cl, tau, X, Y);
+    for (int k = 0; k < 3; ++k) {
+        as[k] = ax.d.a[k] * cp + ax.n[k] * sp;
+        ns[k] = ax.n[k] * cp - ax.d.a[k] * sp;
+        if (on_cl) P[k] = (ax.cl.pt[k] + X * ax.d.a[k]) + Y * ax.n[k];
+        else P[k] = ax.arc.C[k] - ns[k] * ax.arc.inv_kappa;
+    }
+    return on_cl ? ax.cl.kappa(tau) : ax.arc.kappa;
+}
+
+gm_status axis_check(const gm_wall_params *p, const gm_wall_arc *arc, const gm_wall_clothoid *cl, DesignAxis &ax)
+{
+    if (check_params(p) != GM_OK) return GM_ERR_INVALID_ARG;
+    if (arc && (arc->struct_size != sizeof(gm_wall_arc) || !isfinite(arc->curvature[0]) || !isfinite(arc->curvature[1]) ||
+                !isfinite(arc->curvature[2]) || !isfinite(arc->point_chainage)))
+        return GM_ERR_INVALID_ARG;
+    if (cl && (cl->struct_size != sizeof(gm_wall_clothoid) || cl->reserved != 0u || !isfinite(cl->normal[0]) || !isfinite(cl->normal[1]) ||
+               !isfinite(cl->normal[2]) || !isfinite(cl->curvature) || !isfinite(cl->rate) || !isfinite(cl->point_chainage)))
+        return GM_ERR_INVALID_ARG;
+    ax = DesignAxis();
+    design_frame_of(*p, ax.d);
+    if (!arc && !cl) return GM_OK;
+    // n: the curvature vector's, or the normal's, direction across the design direction
+    const double *side = arc ? arc->curvature : cl->normal;
+    const double na = dot(side, ax.d.a);
+    double m[3];
+    for (int k = 0; k < 3; ++k) m[k] = side[k] - na * ax.d.a[k];
+    const double lm = sqrt(dot(m, m));
+    if (arc) {
+        ArcFrame &f = ax.arc;
+        const double kappa = lm;
+        if (!isfinite(kappa) || kappa < 1e-6 || (p->radius + p->gate) * kappa > 0.5) return GM_ERR_INVALID_ARG;
+        const double s0 = arc->point_chainage, s_end = p->t_min + (double)p->n_stations * p->station_length;
+        if (!(fabs(kappa * (p->t_min - s0)) <= 3.0) || !(fabs(kappa * (s_end - s0)) <= 3.0)) return GM_ERR_INVALID_ARG;
+        f.kappa = kappa;
+        f.inv_kappa = 1.0 / kappa;
+        f.s0 = s0;
+        for (int k = 0; k < 3; ++k) {
+            ax.n[k] = m[k] / kappa;
+            f.C[k] = p->point[k] + ax.n[k] * f.inv_kappa;
+        }
+    } else {
+        ClothoidFrame &f = ax.cl;
+        const double l0 = sqrt(dot(cl->normal, cl->normal));
+        if (!isfinite(lm) || !(lm > 1e-6 * l0) || !(lm > 0.0)) return GM_ERR_INVALID_ARG;
+        const double L = (double)p->n_stations * p->station_length;
+        if (fabs(cl->rate) * L < 1e-6) return GM_ERR_INVALID_ARG;
+        f.k0 = cl->curvature;
+        f.rate = cl->rate;
+        f.s0 = cl->point_chainage;
+        f.tau0 = p->t_min - f.s0;
+        f.ds = p->station_length;
+        f.nst = p->n_stations;
+        const double t0 = f.tau0, t1 = f.tau0 + L;
+        const double kmax = std::max(fabs(f.kappa(t0)), fabs(f.kappa(t1)));
+        if (!((p->radius + p->gate) * kmax <= 0.5)) return GM_ERR_INVALID_ARG;
+        if (!(fabs(f.psi(t0)) <= 3.0) || !(fabs(f.psi(t1)) <= 3.0)) return GM_ERR_INVALID_ARG;
+        const double tz = -f.k0 / f.rate;   // kappa = 0 there
+        if (t0 < tz && tz < t1 && !(fabs(f.psi(tz)) <= 3.0)) return GM_ERR_INVALID_ARG;
+        for (int k = 0; k < 3; ++k) { f.pt[k] = p->point[k]; ax.n[k] = m[k] / lm; }
+        try {
+            f.tab.assign(2 * ((size_t)f.nst + 1), 0.0);
+        } catch (...) {
+            return GM_ERR_OOM;
+        }
+        double X = 0.0, Y = 0.0;
+        clothoid_integrate(f, 0.0, f.tau0, X, Y);
+        f.tab[0] = X; f.tab[1] = Y;
+        for (uint32_t j = 0; j < f.nst; ++j) {
+            clothoid_integrate(f, f.tau0 + (double)j * f.ds, f.tau0 + (double)(j + 1u) * f.ds, X, Y);
+            f.tab[2 * ((size_t)j + 1)] = X; f.tab[2 * ((size_t)j + 1) + 1] = Y;
+        }
+    }
+    const double *a = ax.d.a, *n = ax.n;
+    ax.b[0] = a[1] * n[2] - a[2] * n[1]; ax.b[1] = a[2] * n[0] - a[0] * n[2]; ax.b[2] = a[0] * n[1] - a[1] * n[0];
+    ax.un = dot(ax.d.u, ax.n); ax.ub = dot(ax.d.u, ax.b);
+    ax.vn = dot(ax.d.v, ax.n); ax.vb = dot(ax.d.v, ax.b);
+    ax.kind = arc ? kAxisArc : kAxisClothoid;
+    return GM_OK;
+}
+
+double DesignAxis::section(double s, double as[3], double ns[3], double P[3]) const
+{
+    if (kind != kAxisStraight) return curved_section(*this, s - (kind == kAxisClothoid ? cl.s0 : arc.s0), as, ns, P);
+    for (int k = 0; k < 3; ++k) { as[k] = d.a[k]; ns[k] = d.u[k]; P[k] = d.o[k] + s * d.a[k]; }
+    return 0.0;
+}
+
+double DesignAxis::station_section(const gm_wall_params &p, double j, double as[3], double ns[3], double P[3]) const
+{
+    if (kind == kAxisClothoid) return curved_section(*this, cl.tau0 + j * p.station_length, as, ns, P);
+    return section(p.t_min + j * p.station_length, as, ns, P);
+}
+
+double DesignAxis::frame(double s, double o[3], double a[3], double u[3], double v[3], double *n_out) const
+{
+    double ns[3];
+    const double kappa = section(s, a, ns, o);
+    for (int k = 0; k < 3; ++k) {
+        u[k] = kind == kAxisStraight ? d.u[k] : un * ns[k] + ub * b[k];
+        v[k] = kind == kAxisStraight ? d.v[k] : vn * ns[k] + vb * b[k];
+        if (n_out) n_out[k] = ns[k];
+    }
+    return kappa;
+}
+
+double DesignAxis::foot(const double x[3], double &yc, double &zb) const
+{
+    const double *org = kind == kAxisClothoid ? cl.pt : (kind == kAxisArc ? arc.C : d.o);
+    const double r[3] = {x[0] - org[0], x[1] - org[1], x[2] - org[2]};
+    if (kind == kAxisStraight) {
+        yc = dot(r, d.u);
+        zb = dot(r, d.v);
+        return dot(r, d.a);
+    }
+    zb = dot(r, b);
+    if (kind == kAxisClothoid) return cl.s0 + clothoid_foot(*this, x, yc);
+    const double xa = dot(r, d.a), xn = dot(r, n);
+    yc = arc.inv_kappa - sqrt(xa * xa + xn * xn);
+    return arc.s0 + atan2(xa, -xn) / arc.kappa;
+}
+
+void DesignAxis::project(const double x[3], double &chainage, double &angle, double &e) const
+{
+    double th;
+    if (kind == kAxisStraight) {
+        const double r[3] = {x[0] - d.o[0], x[1] - d.o[1], x[2] - d.o[2]};
+        const double t = dot(r, d.a);
+        const double w[3] = {r[0] - t * d.a[0], r[1] - t * d.a[1], r[2] - t * d.a[2]};
+        chainage = t + offset;
+        e = sqrt(dot(w, w)) - d.R;
+        th = atan2(dot(w, d.v), dot(w, d.u));
+    } else {
+        double yc = 0.0, zb;
+        chainage = foot(x, yc, zb);
+        e = sqrt(yc * yc + zb * zb) - d.R;
+        th = atan2(yc * vn + zb * vb, yc * un + zb * ub);
+    }
+    angle = th < 0.0 ? th + kTwoPi : th;
+}
+
+void DesignAxis::point(double chainage, double angle, double rho, double xyz[3]) const
+{
+    const double c = cos(angle), s = sin(angle);
+    const double yc = rho * (c * un + s * vn), zb = rho * (c * ub + s * vb);
+    if (kind == kAxisStraight) {
+        const double t = chainage - offset;
+        for (int k = 0; k < 3; ++k) xyz[k] = (d.o[k] + t * d.a[k]) + rho * (c * d.u[k] + s * d.v[k]);
+    } else if (kind == kAxisClothoid) {
+        double as[3], ns[3], P[3];
+        section(chainage, as, ns, P);
+        for (int k = 0; k < 3; ++k) xyz[k] = (P[k] + yc * ns[k]) + zb * b[k];
+    } else {   // (about the centre: P(s) is not formed)
+        const double psi = arc.kappa * (chainage - arc.s0);
+        const double cp = cos(psi), sp = sin(psi);
+        const double r = yc - arc.inv_kappa;
+        for (int k = 0; k < 3; ++k) {
+            const double nr = n[k] * cp - d.a[k] * sp;
+            xyz[k] = (arc.C[k] + r * nr) + zb * b[k];
+        }
+    }
+}
+
+bool DesignAxis::add_frame(const gm_wall_params &p, const double Rm[3][3], const double tr[3], AxisAddFrame &out) const
 {
     const double ds = p.station_length;
-    const double tau = clothoid_foot(d, f, tr, nullptr, nullptr);
-    const double s = f.s0 + tau;
-    const double jd = floor((tau - f.tau0) / ds);   // (s - t_min, taken in tau: moving s0 and t_min together moves no anchor)
+    double jd, yc, zb;
+    if (kind == kAxisClothoid) {
+        const double tau = clothoid_foot(*this, tr, yc);
+        out.s = cl.s0 + tau;
+        jd = floor((tau - cl.tau0) / ds);   // (s - t_min, taken in tau: moving s0 and t_min together moves no anchor)
+    } else {
+        out.s = foot(tr, yc, zb);
+        jd = floor((out.s - p.t_min) / ds);
+    }
     if (!(fabs(jd) < 4.0e18)) return false;
-    const double sf = p.t_min + jd * ds;
-    double as[3], ns[3], P[3];
-    // (s_f - s0 as tau_0 + j_f ds: the chainage's size does not enter)
-    const double kf = clothoid_section(d, f, f.tau0 + jd * ds, as, ns, P);
-    const double of[3] = {P[0] - tr[0], P[1] - tr[1], P[2] - tr[2]};
-    out.anchor_station = (int64_t)jd;
-    out.sensor_chainage = s;
-    out.anchor_chainage = sf;
-    double l1 = 0.0;
+    out.anchor = (int64_t)jd;
+    out.sf = p.t_min + jd * ds;
+    double as[3], ns[3];
+    const double kf = station_section(p, jd, as, ns, out.P);
+    const double *bs = kind == kAxisStraight ? d.v : b;   // (a straight axis: u, v where a curved one has n, b)
+    const double of[3] = {out.P[0] - tr[0], out.P[1] - tr[1], out.P[2] - tr[2]};
+    out.a1 = 0.0;
     for (int c = 0; c < 3; ++c) {   // Rm^T x
         const double oo = Rm[0][c] * of[0] + Rm[1][c] * of[1] + Rm[2][c] * of[2];
         const double aa = Rm[0][c] * as[0] + Rm[1][c] * as[1] + Rm[2][c] * as[2];
         const double nn = Rm[0][c] * ns[0] + Rm[1][c] * ns[1] + Rm[2][c] * ns[2];
-        const double bb = Rm[0][c] * f.b[0] + Rm[1][c] * f.b[1] + Rm[2][c] * f.b[2];
+        const double bb = Rm[0][c] * bs[0] + Rm[1][c] * bs[1] + Rm[2][c] * bs[2];
+        out.o64[c] = oo; out.a64[c] = aa;
         out.o[c] = (float)oo; out.a[c] = (float)aa; out.n[c] = (float)nn; out.b[c] = (float)bb;
-        if (u64) u64[c] = f.un * nn + f.ub * bb;
-        if (v64) v64[c] = f.vn * nn + f.vb * bb;
-        l1 += fabs(aa);
+        out.u64[c] = kind == kAxisStraight ? nn : un * nn + ub * bb;
+        out.v64[c] = kind == kAxisStraight ? bb : vn * nn + vb * bb;
+        out.a1 += fabs(aa);
     }
-    if (a1) *a1 = l1;
     out.kappa = (float)kf;
-    out.rate = (float)f.rate;
-    out.un = (float)f.un; out.ub = (float)f.ub; out.vn = (float)f.vn; out.vb = (float)f.vb;
-    out.R = (float)d.R;
-    out.station_length = (float)ds;
-    out.sector_angle = (float)(kTwoPi / (double)p.n_sectors);
-    out.gate = (float)p.gate;
-    out.reserved[0] = out.reserved[1] = 0u;
+    out.rate = (float)cl.rate;
+    out.un = (float)un; out.ub = (float)ub; out.vn = (float)vn; out.vb = (float)vb;
     return true;
+}
+
+double DesignAxis::reach(const gm_wall_params &p, double B, double a1) const
+{
+    const double ds = p.station_length;
+    // The LDS window affects speed only (a mapped point outside it goes to the map directly).
+    // A clothoid, sized from the largest |kappa| of the map: a mapped point and the sensor both lie within rho = R + gate of
+    // the axis, and rho max |kappa| <= 0.5 (a refusal of the creation), where the foot of the perpendicular moves by at most
+    // 1 / (1 - rho max |kappa|) <= 2 times the distance between two points.  A point of the crop cube |p|_inf <= B is
+    // within sqrt(3) B of the sensor, whose own foot lies less than ds past the anchor section: |t| <= 2 sqrt(3) B + ds
+    // (the one station goes into add_window's slack).  The tangent turns along the reach, so |a'|_1 does not sharpen it.
+    if (kind == kAxisClothoid) return 2.0 * B * 1.7320508075688772 / ds;
+    // An arc: wherever cy >= 0.5, |t| = |atan2(cx, cy)| / kappa <= |cx| / (cy kappa) <= 2 |x|, and |x| <= B |a'|_1 + ds over
+    // the crop cube |p|_inf <= B as on a straight map (the sensor lies within ds of the anchor section: the stations that
+    // costs at the window's ends take the global path).
+    if (kind == kAxisArc) return 2.0 * B * a1 / ds;
+    // A straight axis: t = p.a' + (s - chainage of the anchor station's start) lies in [-B |a'|_1, B |a'|_1 + ds) for the
+    // points of the crop cube |p|_inf <= B, so their stations relative to the anchor in [floor(-reach), floor(reach) + 1].
+    return B * a1 / ds;
+}
+
+void DesignAxis::row(double tc, const double anchor[3], double *row) const
+{
+    const double tau = tc - (kind == kAxisClothoid ? cl.s0 : arc.s0);
+    const double psi = kind == kAxisClothoid ? cl.psi(tau) : arc.kappa * tau;
+    if (kind == kAxisClothoid) {   // (P(tc) - anchor, cos psi, sin psi); an arc: (cos psi, sin psi)
+        double as[3], ns[3], P[3];
+        curved_section(*this, tau, as, ns, P);
+        for (int k = 0; k < 3; ++k) row[k] = P[k] - anchor[k];
+        row += 3;
+    }
+    row[0] = cos(psi);
+    row[1] = sin(psi);
 }
 
 int pose_split(const double pose[12], double Rm[3][3], double tr[3])
@@ -708,6 +770,66 @@ bool defaults_begin(P *p)
     return true;
 }
 
+// The gm_wall_arc_* and gm_wall_clothoid_* entries, each pair one rule: exactly one of arc and cl is the entry's struct (a
+// NULL one is refused), `given`: every other pointer is set and every scalar finite.  All refusals are GM_ERR_INVALID_ARG.
+bool axis_entry(bool given, const gm_wall_params *p, const gm_wall_arc *arc, const gm_wall_clothoid *cl, DesignAxis &ax)
+{
+    return given && (arc || cl) && axis_check(p, arc, cl, ax) == GM_OK;
+}
+
+template <class Info>   // gm_wall_arc_add_info, gm_wall_clothoid_add_info: everything they share
+gm_status axis_add_frame(const gm_wall_params *p, const gm_wall_arc *arc, const gm_wall_clothoid *cl, const double pose[12],
+                         Info *info, AxisAddFrame &f)
+{
+    DesignAxis ax;
+    double Rm[3][3], tr[3];
+    if (!axis_entry(pose && info, p, arc, cl, ax) || pose_split(pose, Rm, tr)) return GM_ERR_INVALID_ARG;
+    memset(info, 0, sizeof(*info));
+    if (!ax.add_frame(*p, Rm, tr, f)) return GM_ERR_INVALID_ARG;
+    info->struct_size = (uint32_t)sizeof(Info);
+    info->status = ax.d.status;
+    info->anchor_station = f.anchor;
+    info->sensor_chainage = f.s;
+    info->anchor_chainage = f.sf;
+    for (int k = 0; k < 3; ++k) { info->o[k] = f.o[k]; info->a[k] = f.a[k]; info->n[k] = f.n[k]; info->b[k] = f.b[k]; }
+    info->kappa = f.kappa;
+    info->un = f.un; info->ub = f.ub; info->vn = f.vn; info->vb = f.vb;
+    info->R = (float)ax.d.R;
+    info->station_length = (float)p->station_length;
+    info->sector_angle = (float)(kTwoPi / (double)p->n_sectors);
+    info->gate = (float)p->gate;
+    return GM_OK;
+}
+
+gm_status axis_frame(const gm_wall_params *p, const gm_wall_arc *arc, const gm_wall_clothoid *cl, double chainage, double o[3],
+                     double a[3], double u[3], double v[3], double *curvature, double n[3])
+{
+    DesignAxis ax;
+    if (!axis_entry(o && a && u && v && (arc || curvature) && isfinite(chainage), p, arc, cl, ax)) return GM_ERR_INVALID_ARG;
+    const double kappa = ax.frame(chainage, o, a, u, v, n);
+    if (curvature) *curvature = kappa;
+    return GM_OK;
+}
+
+gm_status axis_project(const gm_wall_params *p, const gm_wall_arc *arc, const gm_wall_clothoid *cl, const double xyz[3],
+                       double *chainage, double *angle, double *e)
+{
+    DesignAxis ax;
+    const bool given = xyz && chainage && angle && e && isfinite(xyz[0]) && isfinite(xyz[1]) && isfinite(xyz[2]);
+    if (!axis_entry(given, p, arc, cl, ax)) return GM_ERR_INVALID_ARG;
+    ax.project(xyz, *chainage, *angle, *e);
+    return GM_OK;
+}
+
+gm_status axis_point(const gm_wall_params *p, const gm_wall_arc *arc, const gm_wall_clothoid *cl, double chainage, double angle,
+                     double rho, double xyz[3])
+{
+    DesignAxis ax;
+    if (!axis_entry(xyz && isfinite(chainage) && isfinite(angle) && isfinite(rho), p, arc, cl, ax)) return GM_ERR_INVALID_ARG;
+    ax.point(chainage, angle, rho, xyz);
+    return GM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -728,144 +850,66 @@ void gm_wall_default_params(gm_wall_params *p)
 
 gm_status gm_wall_arc_check_params(const gm_wall_params *params, const gm_wall_arc *arc)
 {
-    DesignFrame d;
-    ArcFrame f;
-    return arc_check(params, arc, d, f);
+    DesignAxis ax;
+    return axis_entry(true, params, arc, nullptr, ax) ? GM_OK : GM_ERR_INVALID_ARG;
 }
 
 gm_status gm_wall_arc_add_frame(const gm_wall_params *params, const gm_wall_arc *arc, const double pose[12],
                                 gm_wall_arc_add_info *info)
 {
-    DesignFrame d;
-    ArcFrame f;
-    double Rm[3][3], tr[3];
-    if (!pose || !info || arc_check(params, arc, d, f) != GM_OK || pose_split(pose, Rm, tr)) return GM_ERR_INVALID_ARG;
-    memset(info, 0, sizeof(*info));
-    if (!arc_add_frame(*params, d, f, Rm, tr, *info, nullptr, nullptr, nullptr)) return GM_ERR_INVALID_ARG;
-    info->struct_size = (uint32_t)sizeof(gm_wall_arc_add_info);
-    info->status = d.status;
-    return GM_OK;
+    AxisAddFrame f;
+    return axis_add_frame(params, arc, nullptr, pose, info, f);
 }
 
 gm_status gm_wall_arc_frame(const gm_wall_params *params, const gm_wall_arc *arc, double chainage, double o[3], double a[3],
                             double u[3], double v[3])
 {
-    DesignFrame d;
-    ArcFrame f;
-    if (!o || !a || !u || !v || !isfinite(chainage) || arc_check(params, arc, d, f) != GM_OK) return GM_ERR_INVALID_ARG;
-    double ns[3];
-    arc_section(d, f, chainage, a, ns, o);
-    for (int k = 0; k < 3; ++k) {
-        u[k] = f.un * ns[k] + f.ub * f.b[k];
-        v[k] = f.vn * ns[k] + f.vb * f.b[k];
-    }
-    return GM_OK;
+    return axis_frame(params, arc, nullptr, chainage, o, a, u, v, nullptr, nullptr);
 }
 
 gm_status gm_wall_arc_project(const gm_wall_params *params, const gm_wall_arc *arc, const double xyz[3], double *chainage,
                               double *angle, double *e)
 {
-    DesignFrame d;
-    ArcFrame f;
-    if (!xyz || !chainage || !angle || !e || arc_check(params, arc, d, f) != GM_OK) return GM_ERR_INVALID_ARG;
-    if (!isfinite(xyz[0]) || !isfinite(xyz[1]) || !isfinite(xyz[2])) return GM_ERR_INVALID_ARG;
-    const double r[3] = {xyz[0] - f.C[0], xyz[1] - f.C[1], xyz[2] - f.C[2]};
-    const double xa = dot(r, d.a), xn = dot(r, f.n), zb = dot(r, f.b);
-    *chainage = f.s0 + atan2(xa, -xn) / f.kappa;
-    const double yc = f.inv_kappa - sqrt(xa * xa + xn * xn);
-    *e = sqrt(yc * yc + zb * zb) - d.R;
-    const double th = atan2(yc * f.vn + zb * f.vb, yc * f.un + zb * f.ub);
-    *angle = th < 0.0 ? th + kTwoPi : th;
-    return GM_OK;
+    return axis_project(params, arc, nullptr, xyz, chainage, angle, e);
 }
 
 gm_status gm_wall_arc_point(const gm_wall_params *params, const gm_wall_arc *arc, double chainage, double angle, double rho,
                             double xyz[3])
 {
-    DesignFrame d;
-    ArcFrame f;
-    if (!xyz || !isfinite(chainage) || !isfinite(angle) || !isfinite(rho) || arc_check(params, arc, d, f) != GM_OK)
-        return GM_ERR_INVALID_ARG;
-    const double psi = f.kappa * (chainage - f.s0);
-    const double cp = cos(psi), sp = sin(psi), c = cos(angle), s = sin(angle);
-    const double yc = rho * (c * f.un + s * f.vn), zb = rho * (c * f.ub + s * f.vb);
-    const double r = yc - f.inv_kappa;
-    for (int k = 0; k < 3; ++k) {
-        const double nr = f.n[k] * cp - d.a[k] * sp;
-        xyz[k] = (f.C[k] + r * nr) + zb * f.b[k];
-    }
-    return GM_OK;
+    return axis_point(params, arc, nullptr, chainage, angle, rho, xyz);
 }
 
 gm_status gm_wall_clothoid_check_params(const gm_wall_params *params, const gm_wall_clothoid *clothoid)
 {
-    DesignFrame d;
-    ClothoidFrame f;
-    return clothoid_check(params, clothoid, d, f) == GM_OK ? GM_OK : GM_ERR_INVALID_ARG;
+    DesignAxis ax;
+    return axis_entry(true, params, nullptr, clothoid, ax) ? GM_OK : GM_ERR_INVALID_ARG;
 }
 
 gm_status gm_wall_clothoid_add_frame(const gm_wall_params *params, const gm_wall_clothoid *clothoid, const double pose[12],
                                      gm_wall_clothoid_add_info *info)
 {
-    DesignFrame d;
-    ClothoidFrame f;
-    double Rm[3][3], tr[3];
-    if (!pose || !info || clothoid_check(params, clothoid, d, f) != GM_OK || pose_split(pose, Rm, tr)) return GM_ERR_INVALID_ARG;
-    memset(info, 0, sizeof(*info));
-    if (!clothoid_add_frame(*params, d, f, Rm, tr, *info, nullptr, nullptr, nullptr)) return GM_ERR_INVALID_ARG;
-    info->struct_size = (uint32_t)sizeof(gm_wall_clothoid_add_info);
-    info->status = d.status;
-    return GM_OK;
+    AxisAddFrame f;
+    const gm_status st = axis_add_frame(params, nullptr, clothoid, pose, info, f);
+    if (st == GM_OK) info->rate = f.rate;
+    return st;
 }
 
 gm_status gm_wall_clothoid_frame(const gm_wall_params *params, const gm_wall_clothoid *clothoid, double chainage, double o[3],
                                  double a[3], double u[3], double v[3], double *curvature, double n[3])
 {
-    DesignFrame d;
-    ClothoidFrame f;
-    if (!o || !a || !u || !v || !curvature || !isfinite(chainage) || clothoid_check(params, clothoid, d, f) != GM_OK)
-        return GM_ERR_INVALID_ARG;
-    double ns[3];
-    *curvature = clothoid_section(d, f, chainage - f.s0, a, ns, o);
-    for (int k = 0; k < 3; ++k) {
-        u[k] = f.un * ns[k] + f.ub * f.b[k];
-        v[k] = f.vn * ns[k] + f.vb * f.b[k];
-        if (n) n[k] = ns[k];
-    }
-    return GM_OK;
+    return axis_frame(params, nullptr, clothoid, chainage, o, a, u, v, curvature, n);
 }
 
 gm_status gm_wall_clothoid_project(const gm_wall_params *params, const gm_wall_clothoid *clothoid, const double xyz[3],
                                    double *chainage, double *angle, double *e)
 {
-    DesignFrame d;
-    ClothoidFrame f;
-    if (!xyz || !chainage || !angle || !e || clothoid_check(params, clothoid, d, f) != GM_OK) return GM_ERR_INVALID_ARG;
-    if (!isfinite(xyz[0]) || !isfinite(xyz[1]) || !isfinite(xyz[2])) return GM_ERR_INVALID_ARG;
-    double yc = 0.0;
-    const double tau = clothoid_foot(d, f, xyz, &yc, nullptr);
-    const double r[3] = {xyz[0] - f.pt[0], xyz[1] - f.pt[1], xyz[2] - f.pt[2]};
-    const double zb = dot(r, f.b);
-    *chainage = f.s0 + tau;
-    *e = sqrt(yc * yc + zb * zb) - d.R;
-    const double th = atan2(yc * f.vn + zb * f.vb, yc * f.un + zb * f.ub);
-    *angle = th < 0.0 ? th + kTwoPi : th;
-    return GM_OK;
+    return axis_project(params, nullptr, clothoid, xyz, chainage, angle, e);
 }
 
 gm_status gm_wall_clothoid_point(const gm_wall_params *params, const gm_wall_clothoid *clothoid, double chainage, double angle,
                                  double rho, double xyz[3])
 {
-    DesignFrame d;
-    ClothoidFrame f;
-    if (!xyz || !isfinite(chainage) || !isfinite(angle) || !isfinite(rho) || clothoid_check(params, clothoid, d, f) != GM_OK)
-        return GM_ERR_INVALID_ARG;
-    double as[3], ns[3], P[3];
-    clothoid_section(d, f, chainage - f.s0, as, ns, P);
-    const double c = cos(angle), s = sin(angle);
-    const double yc = rho * (c * f.un + s * f.vn), zb = rho * (c * f.ub + s * f.vb);
-    for (int k = 0; k < 3; ++k) xyz[k] = (P[k] + yc * ns[k]) + zb * f.b[k];
-    return GM_OK;
+    return axis_point(params, nullptr, clothoid, chainage, angle, rho, xyz);
 }
 
 void gm_wall_region_default_params(gm_wall_region_params *p)

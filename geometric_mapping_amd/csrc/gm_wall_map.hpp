@@ -42,52 +42,70 @@ inline double dot(const double *x, const double *y) { return x[0] * y[0] + x[1] 
 struct DesignFrame { double o[3], a[3], u[3], v[3], R; uint32_t status; };
 void design_frame_of(const gm_wall_params &p, DesignFrame &d);
 gm_status check_params(const gm_wall_params *p);
-// The arc design frame of include/gm_hip.h (fp64, not rounded) beside the DesignFrame at params.point.  kappa = 0: a
-// straight map, nothing else is set.
-struct ArcFrame { double kappa, inv_kappa, s0, n[3], b[3], C[3], un, ub, vn, vb; };
-// gm_wall_map_create_arc's refusals; d and f of an accepted pair
-gm_status arc_check(const gm_wall_params *p, const gm_wall_arc *arc, DesignFrame &d, ArcFrame &f);
-// the section at chainage s: a(s), n(s), P(s)
-void arc_section(const DesignFrame &d, const ArcFrame &f, double s, double as[3], double ns[3], double P[3]);
-// the chainage of a map point
-double arc_chainage(const DesignFrame &d, const ArcFrame &f, const double x[3]);
-// The per-add frame of an accepted (Rm, tr): everything but struct_size and status.  u64 / v64 (may be NULL): Rm^T u(s_f)
-// and Rm^T v(s_f) before the rounding; a1 (may be NULL): |a'|_1 before the rounding.  false: the anchor is out of range.
-bool arc_add_frame(const gm_wall_params &p, const DesignFrame &d, const ArcFrame &f, const double Rm[3][3], const double tr[3],
-                   gm_wall_arc_add_info &out, double *u64, double *v64, double *a1);
-// The clothoid design frame of include/gm_hip.h (fp64, not rounded) beside the DesignFrame at params.point.  on false: not
-// a clothoid map, nothing else is set.  tab: (X, Y) at the n_stations + 1 station starts.
+// The arc's own part of a design axis (fp64, not rounded): kappa > 0, the centre C, s0 = point_chainage.
+struct ArcFrame { double kappa, inv_kappa, s0, C[3]; };
+// The clothoid's own part.  tab: (X, Y) at the n_stations + 1 station starts.
 struct ClothoidFrame {
-    bool on = false;
-    double k0 = 0.0, rate = 0.0, s0 = 0.0, tau0 = 0.0, ds = 0.0, pt[3] = {}, n[3] = {}, b[3] = {}, un = 0.0, ub = 0.0, vn = 0.0, vb = 0.0;
+    double k0 = 0.0, rate = 0.0, s0 = 0.0, tau0 = 0.0, ds = 0.0, pt[3] = {};
     uint32_t nst = 0;
     std::vector<double> tab;
     double kappa(double tau) const { return k0 + rate * tau; }
     double psi(double tau) const { return tau * (k0 + (0.5 * rate) * tau); }
 };
-// gm_wall_map_create_clothoid's refusals; d and f (its table included) of an accepted pair
-gm_status clothoid_check(const gm_wall_params *p, const gm_wall_clothoid *cl, DesignFrame &d, ClothoidFrame &f);
-// (X, Y) at tau = s - s0: the table entry at or below it plus the panels from there
-void clothoid_xy(const ClothoidFrame &f, double tau, double &X, double &Y);
-// the section at tau = s - s0: a(s), n(s), P(s); returns kappa(s)
-double clothoid_section(const DesignFrame &d, const ClothoidFrame &f, double tau, double as[3], double ns[3], double P[3]);
-// the foot of the perpendicular of a map point: returns tau; yc, g of the final evaluation (may be NULL)
-double clothoid_foot(const DesignFrame &d, const ClothoidFrame &f, const double x[3], double *yc, double *g);
-// arc_add_frame on a clothoid map
-bool clothoid_add_frame(const gm_wall_params &p, const DesignFrame &d, const ClothoidFrame &f, const double Rm[3][3],
-                        const double tr[3], gm_wall_clothoid_add_info &out, double *u64, double *v64, double *a1);
+// DesignAxis::add_frame's result, the per-add frame of include/gm_hip.h: the anchor station, the sensor's and the anchor's
+// chainage, the anchor section's origin P in map coordinates; in sensor coordinates (o', a', n', b') rounded to fp32 once
+// (u', v' in n, b on a straight axis), the same four and u', v' = Rm^T u(s_f), Rm^T v(s_f) before the rounding, |a'|_1;
+// kappa_f, rate and un .. vb rounded to fp32 once (0 on a straight axis).
+struct AxisAddFrame {
+    int64_t anchor;
+    double s, sf, P[3], o64[3], a64[3], u64[3], v64[3], a1;
+    float o[3], a[3], n[3], b[3], kappa, rate, un, ub, vn, vb;
+};
+// The design axis of a map, straight (gm_device.hpp: kAxisStraight), arc or clothoid: the DesignFrame at params.point, the
+// curved kinds' n, b and un = u.n, ub = u.b, vn = v.n, vb = v.b there, and the kind's own frame.  Every rule of
+// include/gm_hip.h that sees the axis is written here once; where the kinds differ each keeps its own arithmetic,
+// operation for operation.  Chainages are the map's own; offset (a straight element of an alignment: alignment chainage =
+// map chainage + offset) enters project and point alone.
+struct DesignAxis {
+    int kind = kAxisStraight;
+    DesignFrame d;
+    double n[3] = {}, b[3] = {}, un = 0.0, ub = 0.0, vn = 0.0, vb = 0.0, offset = 0.0;
+    ArcFrame arc = {};
+    ClothoidFrame cl;
+    bool is_arc() const { return kind == kAxisArc; }
+    bool is_clothoid() const { return kind == kAxisClothoid; }
+    // the section at chainage s: a(s), n(s) (u on a straight axis), P(s); returns kappa(s)
+    double section(double s, double as[3], double ns[3], double P[3]) const;
+    // ... at the start of station j, as an add evaluates its anchor section (a clothoid in tau_0 + j ds: the chainage's
+    // size does not enter)
+    double station_section(const gm_wall_params &p, double j, double as[3], double ns[3], double P[3]) const;
+    // the design frame at s: o = P(s), a(s), u(s), v(s); n(s) to n_out (may be NULL); returns kappa(s)
+    double frame(double s, double o[3], double a[3], double u[3], double v[3], double *n_out = nullptr) const;
+    // the foot of the perpendicular of a map point: returns its chainage; (yc, zb): the point in the section there, along
+    // n(s) and b (u and v on a straight axis)
+    double foot(const double x[3], double &yc, double &zb) const;
+    void project(const double x[3], double &chainage, double &angle, double &e) const;
+    void point(double chainage, double angle, double rho, double xyz[3]) const;
+    // the per-add frame of an accepted (Rm, tr); false: the anchor is out of range
+    bool add_frame(const gm_wall_params &p, const double Rm[3][3], const double tr[3], AxisAddFrame &out) const;
+    // the reach in stations of an add's LDS window under the crop bound B, a1 = |a'|_1
+    double reach(const gm_wall_params &p, double B, double a1) const;
+    // the position rule's values of a cloud or mesh block row centred at chainage tc, less the anchor: row_width() doubles
+    uint32_t row_width() const { return kind == kAxisClothoid ? 5u : (kind == kAxisArc ? 2u : 0u); }
+    void row(double tc, const double anchor[3], double *row) const;
+};
+// The refusals of gm_wall_map_create (arc and cl NULL), _create_arc and _create_clothoid, each kind's own; the axis of an
+// accepted call (a clothoid's table included: GM_ERR_OOM).
+gm_status axis_check(const gm_wall_params *p, const gm_wall_arc *arc, const gm_wall_clothoid *cl, DesignAxis &ax);
 // ---- gm_wall_alignment_host.hip: a wall alignment (include/gm_hip.h: gm_wall_alignment_create), no device either ----
-// One element: its derived structs (what its map is created from), their frames, its chainage span in the alignment and
-// the offset of a straight element (alignment chainage = map chainage + offset).
+// One element: its derived structs (what its map is created from), its axis (a straight element's offset in it) and its
+// chainage span in the alignment.
 struct AlignElem {
-    uint32_t kind = 0;
     gm_wall_params p;
     gm_wall_arc arc;
     gm_wall_clothoid cl;
-    DesignFrame d;
-    ArcFrame af;
-    ClothoidFrame cf;
-    double s_start = 0.0, s_end = 0.0, offset = 0.0;
+    DesignAxis ax;
+    double s_start = 0.0, s_end = 0.0;
 };
 struct Alignment {
     std::vector<AlignElem> el;
@@ -303,13 +321,9 @@ struct gm_wall_map {
     uint64_t ncell = 0;
     gm::DevArray<uint8_t> base;    // the device table (zeroed at creation)
     gm::WallTable table;
-    gm::wall::DesignFrame frame;   // fp64, not rounded
+    gm::wall::DesignAxis axis;     // fp64, not rounded
     gm_wall_arc arc;               // gm_wall_map_create_arc's (zero on a straight map)
-    gm::wall::ArcFrame af;         // af.kappa > 0: the design axis is an arc
-    bool is_arc() const { return af.kappa > 0.0; }
     gm_wall_clothoid clothoid;     // gm_wall_map_create_clothoid's (zero on other maps)
-    gm::wall::ClothoidFrame cf;    // cf.on: the design axis is a clothoid
-    bool is_clothoid() const { return cf.on; }
     uint64_t frames = 0;
     hipStream_t stream = nullptr;  // the small kernels (read / merge / clear / count) and their copies
     std::vector<uint8_t> pending;  // per slot of ctx: an add was enqueued on its stream since the last sync
@@ -423,12 +437,10 @@ inline void frame_points(const gm_ctx *ctx, const Slot &sl, WallArgs &w)
 // buffers.  The context's crop bound (a cube around the sensor) sizes the LDS window.
 // f64 (a locate's start): the same vectors before the rounding, and o_f in map coordinates.
 struct WallFrame64 { double c[3], d[3], u[3], v[3], of[3]; };
-// ax: what the arc and the clothoid kernels take beside w (an arc map fills ax->arc alone).  An arc or a clothoid map
-// refuses a caller without one (a locate, an align) with GM_ERR_UNSUPPORTED; a straight map leaves it alone.
+// ax: the map's kind and what the arc and the clothoid kernels take beside w (gm_internal.hpp: WallAxis).  An arc or a
+// clothoid map refuses a caller without one (a locate, an align) with GM_ERR_UNSUPPORTED.
 gm_status add_frame_args(gm_wall_map *m, const double pose[12], gm_wall_add_info *info, WallArgs &w, WallFrame64 *f64 = nullptr,
-                         WallClothoid *ax = nullptr);
-// the add and the check of a map, straight, arc or clothoid (ax: add_frame_args')
-void launch_add(gm_wall_map *m, const WallArgs &w, const WallClothoid &ax, uint32_t n_cap, hipStream_t s);
+                         WallAxis *ax = nullptr);
 // An add on `s` (the stream of `slot`) must not be seen by a reader -- a check, a locate, an align -- enqueued before it
 // on another slot: `s` waits for every result outstanding there (nothing to wait for on a map without readers).
 gm_status add_wait_readers(gm_wall_map *m, uint32_t slot, hipStream_t s);

@@ -53,18 +53,16 @@ gm_status check_prepare(gm_wall_map *m, uint32_t slot, uint32_t n_cap, hipStream
 }
 
 // the launch, the copy of its counters and the event behind both
-gm_status check_enqueue(gm_wall_map *m, uint32_t slot, const WallCheckArgs &a, const WallClothoid &ax, uint32_t n_cap, const ScanState &st,
+gm_status check_enqueue(gm_wall_map *m, uint32_t slot, const WallCheckArgs &a, const WallAxis &ax, uint32_t n_cap, const ScanState &st,
                         hipStream_t s)
 {
     gm_ctx *ctx = m->ctx;
     WallCheckSlot &c = m->checks[slot];
-    if (m->is_clothoid()) launch_wall_check_clothoid(a, ax, n_cap, st, s);
-    else if (m->is_arc()) launch_wall_check_arc(a, ax.arc, n_cap, st, s);
-    else launch_wall_check(a, n_cap, st, s);
+    launch_wall_check(a, ax, n_cap, st, s);
     GMW_HIP(ctx, hipGetLastError());
     GMW_HIP(ctx, hipMemcpyAsync(c.h_ctr, c.ctr.p, kWallCheckCounters * 8, hipMemcpyDeviceToHost, s));
     GMW_OK(c.res.record(ctx, s));
-    c.status = m->frame.status;
+    c.status = m->axis.d.status;
     c.T = a.T;
     c.anchor = a.w.anchor;
     c.cloud_seq = ctx->slots[slot].cloud_seq;
@@ -176,7 +174,7 @@ gm_status locate_result(gm_wall_map *m, uint32_t slot, gm_wall_locate_info *info
     }
     if (wk.last_step > GM_FIT_STEP_BOUND) info->status |= GM_LOCATE_NOT_CONVERGED;
     for (int k = 0; k < 2; ++k) { info->lateral[k] = wk.lateral[k]; info->tilt[k] = wk.tilt[k]; }
-    const DesignFrame &d = m->frame;
+    const DesignFrame &d = m->axis.d;
     for (int r = 0; r < 3; ++r) {   // Rm' = a d^T + u u'^T + v v'^T, tr' = o_f - Rm' c
         double rc = 0.0;
         for (int c = 0; c < 3; ++c) {
@@ -271,7 +269,7 @@ gm_status align_result(gm_wall_map *m, uint32_t slot, gm_wall_align_info *info, 
     if (info) {
         double Rm[3][3], tr[3];
         (void)pose_split(l.pose, Rm, tr);   // (accepted at the enqueue)
-        align_select(m->frame, m->prm, l.prm, Rm, tr, table, info);
+        align_select(m->axis.d, m->prm, l.prm, Rm, tr, table, info);
         info->plane = (uint32_t)h[0];
         info->beyond_gate = (uint32_t)h[1];
         info->outside_patch = (uint32_t)h[2];
@@ -426,7 +424,7 @@ gm_status gm_wall_map_check_frame(gm_wall_map *map, gm_ctx *ctx, uint32_t slot, 
     memset(&a, 0, sizeof(a));
     Slot *sl = nullptr;
     GMW_OK(frame_call_head(map, ctx, slot, "gm_wall_map_check_frame", [&] { return check_prm_ok(cp, a.T); }, sl));
-    WallClothoid ax;
+    WallAxis ax;
     GMW_OK(add_frame_args(map, pose, add_info, a.w, nullptr, &ax));
     a.w.gate = (float)cp.gate;
     if (add_info) add_info->gate = a.w.gate;
@@ -468,7 +466,7 @@ gm_status gm_wall_map_check_points(gm_wall_map *map, const float *xyz, uint32_t 
     memset(&a, 0, sizeof(a));
     if (!check_prm_ok(cp, a.T))
         return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_check_points: struct_size mismatch or a parameter outside its limits");
-    WallClothoid ax;
+    WallAxis ax;
     GMW_OK(add_frame_args(map, pose, add_info, a.w, nullptr, &ax));
     a.w.gate = (float)cp.gate;
     if (add_info) add_info->gate = a.w.gate;

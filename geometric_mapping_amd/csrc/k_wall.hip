@@ -245,44 +245,28 @@ uint32_t wall_blocks(uint32_t n_cap, uint32_t points_per_block)
     return (uint32_t)(b < 1 ? 1 : (b > kWallMaxBlocks ? kWallMaxBlocks : b));
 }
 
-void launch_wall_add(const WallArgs &a, uint32_t n_cap, uint32_t points_per_block, hipStream_t s)
+// the add's one front: the instantiation of the axis' kind, masked where a mask is given
+void launch_wall_add(const WallArgs &a, const WallAxis &axis, const unsigned long long *mask, unsigned long long *ctr, uint32_t n_cap,
+                     uint32_t points_per_block, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_wall_add, dim3(wall_blocks(n_cap, points_per_block)), dim3(kWallThreads), 0, s, a);
-}
-void launch_wall_add_masked(const WallArgs &a, const unsigned long long *mask, unsigned long long *ctr, uint32_t n_cap,
-                            uint32_t points_per_block, hipStream_t s)
-{
+    const dim3 grid(wall_blocks(n_cap, points_per_block)), block(kWallThreads);
+    const WallArcArg<true> arc{axis.ax.arc};
+    const WallClothoidArg cl{axis.ax};
     WallMask<true> m;
     m.words = mask;
     m.ctr = ctr;
-    hipLaunchKernelGGL(k_wall_add_masked, dim3(wall_blocks(n_cap, points_per_block)), dim3(kWallThreads), 0, s, a, m);
+    if (axis.kind == kAxisClothoid) {
+        if (mask) hipLaunchKernelGGL(k_wall_add_clothoid_masked, grid, block, 0, s, a, m, cl);
+        else hipLaunchKernelGGL(k_wall_add_clothoid, grid, block, 0, s, a, cl);
+    } else if (axis.kind == kAxisArc) {
+        if (mask) hipLaunchKernelGGL(k_wall_add_arc_masked, grid, block, 0, s, a, m, arc);
+        else hipLaunchKernelGGL(k_wall_add_arc, grid, block, 0, s, a, arc);
+    } else {
+        if (mask) hipLaunchKernelGGL(k_wall_add_masked, grid, block, 0, s, a, m);
+        else hipLaunchKernelGGL(k_wall_add, grid, block, 0, s, a);
+    }
 }
-void launch_wall_add_arc(const WallArgs &a, const WallArc &arc, uint32_t n_cap, uint32_t points_per_block, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_wall_add_arc, dim3(wall_blocks(n_cap, points_per_block)), dim3(kWallThreads), 0, s, a, WallArcArg<true>{arc});
-}
-void launch_wall_add_arc_masked(const WallArgs &a, const WallArc &arc, const unsigned long long *mask, unsigned long long *ctr,
-                                uint32_t n_cap, uint32_t points_per_block, hipStream_t s)
-{
-    WallMask<true> m;
-    m.words = mask;
-    m.ctr = ctr;
-    hipLaunchKernelGGL(k_wall_add_arc_masked, dim3(wall_blocks(n_cap, points_per_block)), dim3(kWallThreads), 0, s, a, m,
-                       WallArcArg<true>{arc});
-}
-void launch_wall_add_clothoid(const WallArgs &a, const WallClothoid &cl, uint32_t n_cap, uint32_t points_per_block, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_wall_add_clothoid, dim3(wall_blocks(n_cap, points_per_block)), dim3(kWallThreads), 0, s, a, WallClothoidArg{cl});
-}
-void launch_wall_add_clothoid_masked(const WallArgs &a, const WallClothoid &cl, const unsigned long long *mask, unsigned long long *ctr,
-                                     uint32_t n_cap, uint32_t points_per_block, hipStream_t s)
-{
-    WallMask<true> m;
-    m.words = mask;
-    m.ctr = ctr;
-    hipLaunchKernelGGL(k_wall_add_clothoid_masked, dim3(wall_blocks(n_cap, points_per_block)), dim3(kWallThreads), 0, s, a, m,
-                       WallClothoidArg{cl});
-}
+
 void launch_wall_read(const WallTable &T, uint64_t first, uint64_t n, gm_surface_cell *out, hipStream_t s)
 {
     hipLaunchKernelGGL(k_wall_read, dim3(small_blocks(n)), dim3(kWallSmallThreads), 0, s, T, first, n, out);

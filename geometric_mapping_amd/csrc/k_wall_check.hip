@@ -86,34 +86,22 @@ struct WallCheckEmit {
     __device__ __forceinline__ void finish(uint32_t) { wall_check_finish<GM_WALL_CHECK_N_CLS>(a.ctr, a.ctr + GM_WALL_CHECK_N_CLS, q_pos, q_neg); }
 };
 
-void launch_wall_check(const WallCheckArgs &a, uint32_t n_cap, const ScanState &st, hipStream_t s)
+template <class Pred>
+static void wall_check_launch(const Pred &pred, const WallCheckArgs &a, uint32_t n_cap, const ScanState &st, hipStream_t s)
 {
-    WallCheckPred pred{a};
     WallCheckEmit emit;
     memset(&emit, 0, sizeof(emit));
     emit.a = a;
-    hipLaunchKernelGGL((k_compact<WallCheckPred, WallCheckEmit>), dim3(compact_grid(n_cap ? n_cap : 1u)), dim3(kCpThreads), 0, s, pred,
-                       emit, a.w.n_ptr, a.w.n_host, st, reinterpret_cast<uint32_t *>(a.ctr + 9), (uint32_t *)nullptr);
+    hipLaunchKernelGGL((k_compact<Pred, WallCheckEmit>), dim3(compact_grid(n_cap ? n_cap : 1u)), dim3(kCpThreads), 0, s, pred, emit,
+                       a.w.n_ptr, a.w.n_host, st, reinterpret_cast<uint32_t *>(a.ctr + 9), (uint32_t *)nullptr);
 }
 
-void launch_wall_check_arc(const WallCheckArgs &a, const WallArc &arc, uint32_t n_cap, const ScanState &st, hipStream_t s)
+// the check's one front: the predicate of the axis' kind
+void launch_wall_check(const WallCheckArgs &a, const WallAxis &axis, uint32_t n_cap, const ScanState &st, hipStream_t s)
 {
-    WallCheckPredArc pred{a, {arc}};
-    WallCheckEmit emit;
-    memset(&emit, 0, sizeof(emit));
-    emit.a = a;
-    hipLaunchKernelGGL((k_compact<WallCheckPredArc, WallCheckEmit>), dim3(compact_grid(n_cap ? n_cap : 1u)), dim3(kCpThreads), 0, s,
-                       pred, emit, a.w.n_ptr, a.w.n_host, st, reinterpret_cast<uint32_t *>(a.ctr + 9), (uint32_t *)nullptr);
-}
-
-void launch_wall_check_clothoid(const WallCheckArgs &a, const WallClothoid &cl, uint32_t n_cap, const ScanState &st, hipStream_t s)
-{
-    WallCheckPredClothoid pred{a, {cl}};
-    WallCheckEmit emit;
-    memset(&emit, 0, sizeof(emit));
-    emit.a = a;
-    hipLaunchKernelGGL((k_compact<WallCheckPredClothoid, WallCheckEmit>), dim3(compact_grid(n_cap ? n_cap : 1u)), dim3(kCpThreads), 0,
-                       s, pred, emit, a.w.n_ptr, a.w.n_host, st, reinterpret_cast<uint32_t *>(a.ctr + 9), (uint32_t *)nullptr);
+    if (axis.kind == kAxisStraight) wall_check_launch(WallCheckPred{a}, a, n_cap, st, s);
+    else if (axis.kind == kAxisArc) wall_check_launch(WallCheckPredArc{a, {axis.ax.arc}}, a, n_cap, st, s);
+    else wall_check_launch(WallCheckPredClothoid{a, {axis.ax}}, a, n_cap, st, s);
 }
 
 }  // namespace gm

@@ -103,31 +103,12 @@ void launch_wall_cloud_merge(const WallCloudArgs &a, hipStream_t s)
     hipLaunchKernelGGL(k_wall_cloud_merge, dim3((uint32_t)b), dim3(kWcThreads), 0, s, a, nseg, (uint32_t)items);
 }
 
-void launch_wall_cloud_compact(const WallCloudArgs &a, const ScanState &st, hipStream_t s)
+// the compaction's one front: the emit step of the axis' kind
+void launch_wall_cloud_compact(const WallCloudArgs &a, const WallCloudAxis &axis, const ScanState &st, hipStream_t s)
 {
-    const uint32_t nb = a.nJ * a.NK;   // >= 1
-    WallCloudPred pred{a};
-    WallCloudEmit emit{a};
-    hipLaunchKernelGGL((k_compact<WallCloudPred, WallCloudEmit>), dim3(compact_grid(nb)), dim3(kCpThreads), 0, s, pred, emit,
-                       (const uint32_t *)nullptr, nb, st, reinterpret_cast<uint32_t *>(a.ctr + 2), (uint32_t *)nullptr);
-}
-
-void launch_wall_cloud_compact_arc(const WallCloudArgs &a, const WallCloudArc &arc, const ScanState &st, hipStream_t s)
-{
-    const uint32_t nb = a.nJ * a.NK;   // >= 1
-    WallCloudPred pred{a};
-    WallCloudEmitArc emit{a, WallCloudOnArc{arc}};
-    hipLaunchKernelGGL((k_compact<WallCloudPred, WallCloudEmitArc>), dim3(compact_grid(nb)), dim3(kCpThreads), 0, s, pred, emit,
-                       (const uint32_t *)nullptr, nb, st, reinterpret_cast<uint32_t *>(a.ctr + 2), (uint32_t *)nullptr);
-}
-
-void launch_wall_cloud_compact_clothoid(const WallCloudArgs &a, const WallCloudClothoid &cl, const ScanState &st, hipStream_t s)
-{
-    const uint32_t nb = a.nJ * a.NK;   // >= 1
-    WallCloudPred pred{a};
-    WallCloudEmitClothoid emit{a, WallCloudOnClothoid{cl}};
-    hipLaunchKernelGGL((k_compact<WallCloudPred, WallCloudEmitClothoid>), dim3(compact_grid(nb)), dim3(kCpThreads), 0, s, pred, emit,
-                       (const uint32_t *)nullptr, nb, st, reinterpret_cast<uint32_t *>(a.ctr + 2), (uint32_t *)nullptr);
+    if (axis.kind == kAxisStraight) wall_cloud_launch(a, WallCloudEmit{a}, st, s);
+    else if (axis.kind == kAxisArc) wall_cloud_launch(a, WallCloudEmitArc{a, WallCloudOnArc{axis.arc}}, st, s);
+    else wall_cloud_launch(a, WallCloudEmitClothoid{a, WallCloudOnClothoid{wall_cloud_clothoid(axis)}}, st, s);
 }
 
 }  // namespace gm

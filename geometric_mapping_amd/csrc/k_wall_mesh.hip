@@ -132,34 +132,18 @@ struct WallMeshEmit {
     }
 };
 
-void launch_wall_mesh_vertices(const WallCloudArgs &a, uint32_t *rank, float *mean, uint32_t rank_base, const ScanState &st,
-                               hipStream_t s)
+// the vertex pass's one front: the cloud's emit step of the axis' kind, wrapped
+void launch_wall_mesh_vertices(const WallCloudArgs &a, const WallCloudAxis &axis, uint32_t *rank, float *mean, uint32_t rank_base,
+                               const ScanState &st, hipStream_t s)
 {
-    const uint32_t nb = a.nJ * a.NK;   // >= 1
-    WallCloudPred pred{a};
-    WallMeshVertexEmit emit{{WallCloudEmit{a}, rank, mean, rank_base}};
-    hipLaunchKernelGGL((k_compact<WallCloudPred, WallMeshVertexEmit>), dim3(compact_grid(nb)), dim3(kCpThreads), 0, s, pred, emit,
-                       (const uint32_t *)nullptr, nb, st, reinterpret_cast<uint32_t *>(a.ctr + 2), (uint32_t *)nullptr);
-}
-
-void launch_wall_mesh_vertices_arc(const WallCloudArgs &a, const WallCloudArc &arc, uint32_t *rank, float *mean, uint32_t rank_base,
-                                   const ScanState &st, hipStream_t s)
-{
-    const uint32_t nb = a.nJ * a.NK;   // >= 1
-    WallCloudPred pred{a};
-    WallMeshVertexEmitArc emit{{WallCloudEmitArc{a, WallCloudOnArc{arc}}, rank, mean, rank_base}};
-    hipLaunchKernelGGL((k_compact<WallCloudPred, WallMeshVertexEmitArc>), dim3(compact_grid(nb)), dim3(kCpThreads), 0, s, pred, emit,
-                       (const uint32_t *)nullptr, nb, st, reinterpret_cast<uint32_t *>(a.ctr + 2), (uint32_t *)nullptr);
-}
-
-void launch_wall_mesh_vertices_clothoid(const WallCloudArgs &a, const WallCloudClothoid &cl, uint32_t *rank, float *mean,
-                                        uint32_t rank_base, const ScanState &st, hipStream_t s)
-{
-    const uint32_t nb = a.nJ * a.NK;   // >= 1
-    WallCloudPred pred{a};
-    WallMeshVertexEmitClothoid emit{{WallCloudEmitClothoid{a, WallCloudOnClothoid{cl}}, rank, mean, rank_base}};
-    hipLaunchKernelGGL((k_compact<WallCloudPred, WallMeshVertexEmitClothoid>), dim3(compact_grid(nb)), dim3(kCpThreads), 0, s, pred,
-                       emit, (const uint32_t *)nullptr, nb, st, reinterpret_cast<uint32_t *>(a.ctr + 2), (uint32_t *)nullptr);
+    if (axis.kind == kAxisStraight) {
+        wall_cloud_launch(a, WallMeshVertexEmit{{WallCloudEmit{a}, rank, mean, rank_base}}, st, s);
+    } else if (axis.kind == kAxisArc) {
+        wall_cloud_launch(a, WallMeshVertexEmitArc{{WallCloudEmitArc{a, WallCloudOnArc{axis.arc}}, rank, mean, rank_base}}, st, s);
+    } else {
+        const WallCloudEmitClothoid cloud{a, WallCloudOnClothoid{wall_cloud_clothoid(axis)}};
+        wall_cloud_launch(a, WallMeshVertexEmitClothoid{{cloud, rank, mean, rank_base}}, st, s);
+    }
 }
 
 void launch_wall_mesh_triangles(const WallMeshArgs &a, const ScanState &st, hipStream_t s)
