@@ -473,6 +473,22 @@ class WallAlignInfo(C.Structure):
                 ("rms_best", C.c_double), ("rms_runner", C.c_double), ("distinction", C.c_double), ("pose", C.c_double * 12)]
 
 
+class WallAlignmentAlignPiece(C.Structure):
+    _fields_ = [("element", C.c_uint32), ("n_stations", C.c_uint32), ("first_row", C.c_int64)]
+
+
+class WallAlignmentAlignPlan(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_pieces", C.c_uint32), ("add", WallAlignmentAddInfo),
+                ("anchor_global", C.c_int64), ("total", C.c_int64), ("row0", C.c_int32 * 4), ("own", C.c_uint32),
+                ("home", C.c_uint32), ("piece", WallAlignmentAlignPiece * 8)]
+
+
+class WallAlignmentAlignInfo(C.Structure):
+    _fields_ = WallAlignInfo._fields_ + [("element", C.c_uint32), ("n_sides", C.c_uint32), ("chainage", C.c_double),
+                                         ("anchor_global", C.c_int64), ("side_class", (C.c_uint32 * 4) * 4),
+                                         ("plan", WallAlignmentAddInfo)]
+
+
 class WallObject(C.Structure):
     _fields_ = [("label", C.c_uint32), ("sign", C.c_int32), ("blocks", C.c_uint32), ("peak_index", C.c_uint32),
                 ("station_min", C.c_uint32), ("station_max", C.c_uint32), ("sector_min", C.c_uint32), ("sector_max", C.c_uint32),
@@ -664,6 +680,13 @@ def load():
         "gm_wall_alignment_locate_frame": (C.c_int, [vp, vp, u32, dp, wlprmp]),
         "gm_wall_alignment_get_locate": (C.c_int, [vp, u32, C.POINTER(WallAlignmentLocateInfo)]),
         "gm_wall_alignment_locate_points": (C.c_int, [vp, fp, u32, u8p, dp, wlprmp, C.POINTER(WallAlignmentLocateInfo), fp, i32p, i32p]),
+        "gm_wall_alignment_align_plan": (C.c_int, [wprmp, welp, u32, dp, C.c_double, waprmp, C.POINTER(WallAlignmentAlignPlan)]),
+        "gm_wall_alignment_align_select": (C.c_int, [wprmp, welp, u32, dp, C.c_double, waprmp, wascp, u32,
+                                                     C.POINTER(WallAlignmentAlignInfo)]),
+        "gm_wall_alignment_align_frame": (C.c_int, [vp, vp, u32, dp, waprmp, C.POINTER(WallAlignmentAlignPlan)]),
+        "gm_wall_alignment_get_align": (C.c_int, [vp, u32, C.POINTER(WallAlignmentAlignInfo), wascp, u32, u32p]),
+        "gm_wall_alignment_align_points": (C.c_int, [vp, fp, u32, u8p, dp, waprmp, C.POINTER(WallAlignmentAlignPlan),
+                                                     C.POINTER(WallAlignmentAlignInfo), wascp, u32, u32p, fp, i32p, i32p]),
         "gm_wall_alignment_check_frame": (C.c_int, [vp, vp, u32, dp, wkprmp, waladdp]),
         "gm_wall_alignment_get_check": (C.c_int, [vp, u32, C.POINTER(WallAlignmentCheckInfo), wkptp, u32, u32p]),
         "gm_wall_alignment_check_points": (C.c_int, [vp, fp, u32, u8p, dp, wkprmp, waladdp, C.POINTER(WallAlignmentCheckInfo), wkptp,

@@ -1811,6 +1811,26 @@ def _alignment_add_info(i):
                 joint_a=np.array([list(r) for r in i.joint_a], dtype=np.float32)[:max(ns - 1, 0)])
 
 
+def _alignment_align_plan(p):
+    """The dict of a gm_wall_alignment_align_plan_info: add (the add's plan dict), anchor_global (G_f), total, row0
+    [n_sides] int32, own, home and pieces [(element, first_row, n_stations)]."""
+    ns, npc = int(p.add.n_sides), int(p.n_pieces)
+    return dict(add=_alignment_add_info(p.add), anchor_global=int(p.anchor_global), total=int(p.total),
+                row0=np.array(p.row0[:ns], dtype=np.int32), own=int(p.own), home=int(p.home), n_pieces=npc,
+                pieces=[(int(q.element), int(q.first_row), int(q.n_stations)) for q in p.piece[:npc]])
+
+
+def _alignment_align_info(i):
+    """The dict of a gm_wall_alignment_align_info: WallMap.align_result()'s keys (bytes: the raw shared head), element,
+    n_sides, chainage, anchor_global, side_class [n_sides, 4] uint32 (plane, beyond_gate, outside_patch, binned) and plan."""
+    d = _align_info(i)
+    d["bytes"] = bytes(i)[:C.sizeof(_lib.WallAlignInfo)]
+    ns = int(i.n_sides)
+    d.update(element=int(i.element), n_sides=ns, chainage=float(i.chainage), anchor_global=int(i.anchor_global),
+             side_class=np.array([list(r) for r in i.side_class], dtype=np.uint32)[:ns], plan=_alignment_add_info(i.plan))
+    return d
+
+
 class WallAlignmentRule:
     """The device-free half of a wall alignment (gm_wall_alignment_check, _element_params, _project, _point, _window,
     _add_plan; include/gm_hip.h states the rule): a template gm_wall_params and the elements.  Needs no context."""
@@ -1896,6 +1916,30 @@ class WallAlignmentRule:
                  side_axis=np.array([list(r) for r in s.side_axis], dtype=np.float32)[:ns],
                  side_kind=[int(x) for x in s.side_kind[:ns]])
         return d
+
+    def align_plan(self, pose, bound, **params):
+        """gm_wall_alignment_align_plan: the plan dict of an align under `pose` (_alignment_align_plan) with the align
+        parameters given as keywords; GmError with GM_ERR_UNSUPPORTED for too many sides or pieces."""
+        m = WallMap._pose(pose)
+        p = _wall_align_params(**params)
+        i = _lib.WallAlignmentAlignPlan()
+        st = self._L.gm_wall_alignment_align_plan(*self._head(), _dptr(m), float(bound), C.byref(p), C.byref(i))
+        if st != _lib.GM_OK:
+            raise _lib.GmError(st, "gm_wall_alignment_align_plan refused the arguments")
+        return _alignment_align_plan(i)
+
+    def align_select(self, pose, bound, table, **params):
+        """gm_wall_alignment_align_select: the info dict of the selection and the pose from a WALL_ALIGN_SCORE table; the
+        device's counts are 0."""
+        t = np.ascontiguousarray(np.asarray(table, dtype=WALL_ALIGN_SCORE).reshape(-1))
+        m = WallMap._pose(pose)
+        p = _wall_align_params(**params)
+        info = _lib.WallAlignmentAlignInfo()
+        st = self._L.gm_wall_alignment_align_select(*self._head(), _dptr(m), float(bound), C.byref(p),
+                                                    t.ctypes.data_as(C.POINTER(_lib.WallAlignScore)), len(t), C.byref(info))
+        if st != _lib.GM_OK:
+            raise _lib.GmError(st, "gm_wall_alignment_align_select refused its arguments")
+        return _alignment_align_info(info)
 
 
 class WallAlignment(WallAlignmentRule):
@@ -2032,6 +2076,59 @@ class WallAlignment(WallAlignmentRule):
         if not outputs:
             return self._locate_info(info), None, None, None
         return self._locate_info(info), res[:n].copy(), cell[:n].copy(), el[:n].copy()
+
+    def align_plan(self, pose, bound=None, **params):
+        return super().align_plan(pose, float(self._ctx.cfg.boxFilterBound) if bound is None else bound, **params)
+
+    def align_select(self, pose, table, bound=None, **params):
+        return super().align_select(pose, float(self._ctx.cfg.boxFilterBound) if bound is None else bound, table, **params)
+
+    def align_frame(self, slot=0, pose=np.eye(4)[:3], **params):
+        """gm_wall_alignment_align_frame: enqueue the chainage and roll alignment of `pose` for the slot's last submitted
+        frame against the alignment (keywords: gm_wall_align_params').  Returns the plan dict at once; align_result()
+        fetches the result."""
+        m = WallMap._pose(pose)
+        p = _wall_align_params(**params)
+        i = _lib.WallAlignmentAlignPlan()
+        self._ctx._check(self._L.gm_wall_alignment_align_frame(self._h(), self._ctx._ctx, slot, _dptr(m), C.byref(p), C.byref(i)))
+        return _alignment_align_plan(i)
+
+    def align_result(self, slot=0):
+        """gm_wall_alignment_get_align: (info dict, WALL_ALIGN_SCORE table shaped (2A + 1, 2B + 1)) of the last align on
+        the slot.  A count query first, then the sized call."""
+        info, got = _lib.WallAlignmentAlignInfo(), C.c_uint32(0)
+        self._ctx._check(self._L.gm_wall_alignment_get_align(self._h(), slot, None, None, 0, C.byref(got)))
+        cap = int(got.value)
+        t = np.zeros(max(cap, 1), dtype=WALL_ALIGN_SCORE)
+        self._ctx._check(self._L.gm_wall_alignment_get_align(self._h(), slot, C.byref(info),
+                                                             t.ctypes.data_as(C.POINTER(_lib.WallAlignScore)), cap, C.byref(got)))
+        d = _alignment_align_info(info)
+        return d, t[:cap].reshape(2 * d["max_station_shift"] + 1, 2 * d["max_sector_shift"] + 1).copy()
+
+    def align_points(self, cloud, pose=np.eye(4)[:3], labels=None, outputs=True, **params):
+        """gm_wall_alignment_align_points on a host cloud [n,3]: (info dict with the align's plan under "align_plan", table,
+        dict(e float32, cell int32: jr * n_sectors + k of a binned point, else -1, element int32) or None without
+        outputs)."""
+        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+        m = WallMap._pose(pose)
+        lab, lp = GeometricMapping._u8(labels)
+        p = _wall_align_params(**params)
+        n = len(xyz)
+        plan, info, got = _lib.WallAlignmentAlignPlan(), _lib.WallAlignmentAlignInfo(), C.c_uint32(0)
+        na, nb = 2 * int(p.max_station_shift) + 1, 2 * int(p.max_sector_shift) + 1
+        t = np.zeros(na * nb, dtype=WALL_ALIGN_SCORE)
+        out = None
+        if outputs:
+            out = dict(e=np.empty(max(n, 1), np.float32), cell=np.empty(max(n, 1), np.int32), element=np.empty(max(n, 1), np.int32))
+        i32p = C.POINTER(C.c_int32)
+        self._ctx._check(self._L.gm_wall_alignment_align_points(
+            self._h(), _f32(xyz), n, lp, _dptr(m), C.byref(p), C.byref(plan), C.byref(info),
+            t.ctypes.data_as(C.POINTER(_lib.WallAlignScore)), len(t), C.byref(got),
+            _f32(out["e"]) if outputs else None, out["cell"].ctypes.data_as(i32p) if outputs else None,
+            out["element"].ctypes.data_as(i32p) if outputs else None))
+        d = _alignment_align_info(info)
+        d["align_plan"] = _alignment_align_plan(plan)
+        return d, t.reshape(na, nb), ({k: v[:n].copy() for k, v in out.items()} if outputs else None)
 
     @staticmethod
     def split_cell(rows):

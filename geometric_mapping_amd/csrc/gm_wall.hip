@@ -148,7 +148,7 @@ gm_status add_wait_readers(gm_wall_map *m, uint32_t slot, hipStream_t s)
     for (uint32_t i = 0; i < m->ctx->n_slots; ++i)
         for (const PendingResult *r : {&m->checks[i].res, &m->locates[i].res, &m->aligns[i].res})
             if (i != slot && r->outstanding) GMW_HIP(m->ctx, hipStreamWaitEvent(s, r->done, 0));
-    for (const std::vector<PendingResult> *al : {m->al_locates, m->al_checks})
+    for (const std::vector<PendingResult> *al : {m->al_locates, m->al_checks, m->al_aligns})
         if (al)
             for (uint32_t i = 0; i < m->ctx->n_slots; ++i)
                 if (i != slot && (*al)[i].outstanding) GMW_HIP(m->ctx, hipStreamWaitEvent(s, (*al)[i].done, 0));

@@ -2,7 +2,7 @@
 // (create, destroy, map, info, sync) and the add.  Host logic only: the element maps, the plan of a call and its refusals, the
 // sides of a plan (their per-add frames: add_frame_args of each element map, unchanged), the deal of the add's LDS table.
 // gm_wall_alignment.hpp declares what the other call families take from here: the locate is gm_wall_alignment_locate.hip,
-// the check and the checked add gm_wall_alignment_check.hip.  The add's kernel is k_wall_joint.hip's; the device-free calls
+// the align gm_wall_alignment_align.hip, the check and the checked add gm_wall_alignment_check.hip.  The add's kernel is k_wall_joint.hip's; the device-free calls
 // are in gm_wall_alignment_host.hip.
 #include "gm_wall_alignment.hpp"
 
@@ -93,9 +93,9 @@ namespace {
 
 void free_alignment(gm_wall_alignment *al, bool maps_too)
 {
-    for (std::vector<PendingResult> *v : {&al->locate_res, &al->check_res, &al->add_res})
+    for (std::vector<PendingResult> *v : {&al->locate_res, &al->check_res, &al->add_res, &al->align_res})
         for (PendingResult &r : *v) r.release();   // nothing may still be writing the alignment's blocks
-    for (gm_wall_map *m : al->maps) { m->al_locates = nullptr; m->al_checks = nullptr; }
+    for (gm_wall_map *m : al->maps) { m->al_locates = nullptr; m->al_checks = nullptr; m->al_aligns = nullptr; }
     if (maps_too)
         for (gm_wall_map *m : al->maps) gm_wall_map_destroy(m);
     delete al;
@@ -140,12 +140,13 @@ gm_status gm_wall_alignment_create(gm_ctx *ctx, const gm_wall_params *params, co
         }
         al->maps.push_back(m);
     }
-    // the per-slot state of the locates and the checks (no device memory: vectors of empty owners); the element maps learn
-    // where the pending results are
+    // the per-slot state of the locates, the checks and the aligns (no device memory: vectors of empty owners); the element
+    // maps learn where the pending results are
     al->locates.resize(ctx->n_slots);
     al->checks.resize(ctx->n_slots);
-    for (std::vector<PendingResult> *v : {&al->locate_res, &al->check_res, &al->add_res}) v->resize(ctx->n_slots);
-    for (gm_wall_map *m : al->maps) { m->al_locates = &al->locate_res; m->al_checks = &al->check_res; }
+    al->aligns.resize(ctx->n_slots);
+    for (std::vector<PendingResult> *v : {&al->locate_res, &al->check_res, &al->add_res, &al->align_res}) v->resize(ctx->n_slots);
+    for (gm_wall_map *m : al->maps) { m->al_locates = &al->locate_res; m->al_checks = &al->check_res; m->al_aligns = &al->align_res; }
     ctx->alignments.push_back(al);
     *alignment = al;
     return GM_OK;
@@ -224,7 +225,7 @@ gm_status gm_wall_alignment_sync(gm_wall_alignment *alignment)
 {
     if (!alignment) return GM_ERR_INVALID_ARG;
     for (gm_wall_map *m : alignment->maps) GMW_OK(gm_wall_map_sync(m));
-    for (std::vector<PendingResult> *v : {&alignment->locate_res, &alignment->check_res, &alignment->add_res})
+    for (std::vector<PendingResult> *v : {&alignment->locate_res, &alignment->check_res, &alignment->add_res, &alignment->align_res})
         for (PendingResult &r : *v) GMW_OK(r.wait(alignment->ctx));
     return GM_OK;
 }

@@ -46,6 +46,21 @@ struct gm_wall_alignment {
     };
     std::vector<CheckSlot> checks;              // per slot of ctx
     std::vector<gm::wall::PendingResult> check_res, add_res;
+    // gm_wall_alignment_align_*: the state of one (alignment, slot).  The device blocks are allocated by the first align that
+    // is not an element map's own; the pending aligns are what the element maps' adds wait for (gm_wall_map::al_aligns)
+    struct AlignSlot {
+        gm::DevArray<uint8_t> zeroed;               // counters | score table | patch sums | patch counts: one zero-fill per align
+        gm::DevArray<int32_t> f, m;                 // the two value images
+        gm::HostArray<uint8_t> h_res;               // pinned copy of counters | score table, valid once the result has been waited for
+        gm_wall_align_params prm;                   // of the last align
+        double pose[12];                            // the caller's pose of that align
+        gm_wall_alignment_align_plan_info plan;     // its plan
+        uint32_t n_shifts = 0;                      // (2A + 1)(2B + 1)
+        gm_wall_map *own = nullptr;                 // the last align was this element map's own (one straight side)
+        bool have = false;
+    };
+    std::vector<AlignSlot> aligns;              // per slot of ctx
+    std::vector<gm::wall::PendingResult> align_res;
     // the checked add's stage call: the uploaded rows and its block
     gm::DevArray<gm_wall_check_point> ac_rows;
     gm::DevArray<unsigned long long> ac_blk;

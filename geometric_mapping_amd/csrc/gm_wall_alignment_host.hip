@@ -3,6 +3,7 @@
 // of an add.  Every element is a DesignAxis (gm_wall_map.hpp): its section, project, point and per-add frame are the
 // element map's own, asked of the axis.  Like gm_wall_host.hip it links against libm and the C++ library alone;
 // host/gm_wall_alignment_host_test.cpp runs it under the host sanitizers.
+#include <stddef.h>
 #include <stdio.h>
 
 #include <vector>
@@ -246,6 +247,103 @@ gm_status alignment_locate_start(const Alignment &A, const double pose[12], doub
     return GM_OK;
 }
 
+// F(x) of include/gm_hip.h's align rule: the design frame at alignment chainage x, on the element the point rule picks
+void alignment_frame(const Alignment &A, double x, double o[3], double a[3], double u[3], double v[3])
+{
+    uint32_t i = 0;
+    while (i + 1u < (uint32_t)A.el.size() && x >= A.el[i].s_end) ++i;
+    const DesignAxis &X = A.el[i].ax;
+    X.frame(x - X.offset, o, a, u, v);   // (the offset is 0 but on a straight element behind the first)
+}
+
+gm_status alignment_align_plan(const Alignment &A, const double pose[12], double bound, const gm_wall_align_params &ap,
+                               gm_wall_alignment_align_plan_info *out)
+{
+    if (!out) return GM_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    out->struct_size = (uint32_t)sizeof(gm_wall_alignment_align_plan_info);
+    if (A.el.empty() || !align_prm_ok(ap, A.el[0].p.n_sectors)) return GM_ERR_INVALID_ARG;
+    GMW_OK(alignment_add_plan(A, pose, bound, &out->add));
+    const gm_wall_alignment_add_info &pl = out->add;
+    const int64_t P = (int64_t)ap.half_patch_stations, Ash = (int64_t)ap.max_station_shift;
+    std::vector<int64_t> base;
+    try {
+        base.resize(A.el.size() + 1u);
+    } catch (...) {
+        return GM_ERR_OOM;
+    }
+    base[0] = 0;
+    for (size_t i = 0; i < A.el.size(); ++i) base[i + 1u] = base[i] + (int64_t)A.el[i].p.n_stations;
+    out->total = base[A.el.size()];
+    out->home = pl.element - pl.side_element[0];
+    const int64_t Gf = base[pl.element] + pl.side_anchor[out->home];   // (|anchor| < 4e18, base < 2^40: no overflow)
+    out->anchor_global = Gf;
+    for (uint32_t k = 0; k < pl.n_sides; ++k) {
+        const int64_t r0 = ((base[pl.side_element[k]] + pl.side_anchor[k]) - Gf) + P;
+        if (r0 < -2147483647ll - 1 || r0 > 2147483647ll) return GM_ERR_INVALID_ARG;
+        out->row0[k] = (int32_t)r0;
+    }
+    // the pieces: the elements the image rows [G_f - P - A, G_f + P + A) meet, ascending
+    const int64_t g0 = (Gf - P) - Ash, g1 = (Gf + P) + Ash;
+    uint32_t np = 0;
+    for (size_t i = 0; i < A.el.size(); ++i) {
+        if (!(base[i] < g1 && base[i + 1u] > g0)) continue;
+        if (np == GM_WALL_ALIGN_MAX_PIECES) {
+            out->n_pieces = 0;
+            memset(out->piece, 0, sizeof(out->piece));
+            return GM_ERR_UNSUPPORTED;
+        }
+        out->piece[np].element = (uint32_t)i;
+        out->piece[np].n_stations = A.el[i].p.n_stations;
+        out->piece[np].first_row = base[i];
+        ++np;
+    }
+    out->n_pieces = np;
+    out->own = (pl.n_sides == 1u && A.el[pl.element].ax.kind == kAxisStraight && (np == 0u || (np == 1u && out->piece[0].element == pl.element)))
+                   ? 1u : 0u;
+    return GM_OK;
+}
+
+// the selection of `table` and the pose of include/gm_hip.h's align rule; everything of info but the device's counts
+gm_status alignment_align_select(const Alignment &A, const double pose[12], const gm_wall_align_params &ap,
+                                 const gm_wall_alignment_align_plan_info &plan, const gm_wall_align_score *table,
+                                 gm_wall_alignment_align_info *info)
+{
+    double Rm[3][3], tr[3];
+    if (!table || !info || pose_split(pose, Rm, tr)) return GM_ERR_INVALID_ARG;
+    static_assert(offsetof(gm_wall_alignment_align_info, element) == sizeof(gm_wall_align_info), "the shared head");
+    memset(info, 0, sizeof(*info));
+    const gm_wall_params &wp = A.el[plan.add.element].p;
+    gm_wall_align_info head;
+    const bool ok = align_select_table(ap, wp.station_length, wp.n_sectors, table, &head);
+    head.anchor_station = plan.add.side_anchor[plan.home];
+    if (ok) {
+        const double s = plan.add.chainage, s2 = s + head.shift_m;
+        double o1[3], a1[3], u1[3], v1[3], o2[3], a2[3], u2[3], v2[3];
+        alignment_frame(A, s, o1, a1, u1, v1);
+        alignment_frame(A, s2, o2, a2, u2, v2);
+        const double cs = cos(head.roll), sn = sin(head.roll);
+        double M[3][3];   // F(s') Q F(s)^T
+        for (int r = 0; r < 3; ++r) {
+            const double qu = cs * u2[r] + sn * v2[r], qv = cs * v2[r] - sn * u2[r];
+            for (int c = 0; c < 3; ++c) M[r][c] = (a2[r] * a1[c] + qu * u1[c]) + qv * v1[c];
+        }
+        const double rel[3] = {tr[0] - o1[0], tr[1] - o1[1], tr[2] - o1[2]};
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) head.pose[4 * r + c] = (M[r][0] * Rm[0][c] + M[r][1] * Rm[1][c]) + M[r][2] * Rm[2][c];
+            head.pose[4 * r + 3] = o2[r] + ((M[r][0] * rel[0] + M[r][1] * rel[1]) + M[r][2] * rel[2]);
+        }
+    }
+    memcpy(info, &head, sizeof(head));
+    info->struct_size = (uint32_t)sizeof(gm_wall_alignment_align_info);
+    info->element = plan.add.element;
+    info->n_sides = plan.add.n_sides;
+    info->chainage = plan.add.chainage;
+    info->anchor_global = plan.anchor_global;
+    info->plan = plan.add;
+    return GM_OK;
+}
+
 gm_status alignment_window(const Alignment &A, double s_from, double s_to, gm_wall_alignment_piece *pieces, uint32_t capacity,
                            uint32_t *n_out)
 {
@@ -338,6 +436,29 @@ gm_status gm_wall_alignment_window(const gm_wall_params *params, const gm_wall_e
     Alignment A;
     GMW_OK(alignment_build(params, elements, n, A));
     return alignment_window(A, s_from, s_to, pieces, capacity, n_out);
+}
+
+gm_status gm_wall_alignment_align_plan(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n,
+                                       const double pose[12], double bound, const gm_wall_align_params *prm,
+                                       gm_wall_alignment_align_plan_info *plan)
+{
+    Alignment A;
+    GMW_OK(alignment_build(params, elements, n, A));
+    return alignment_align_plan(A, pose, bound, params_or(prm, gm_wall_align_default_params), plan);
+}
+
+gm_status gm_wall_alignment_align_select(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n,
+                                         const double pose[12], double bound, const gm_wall_align_params *prm,
+                                         const gm_wall_align_score *table, uint32_t n_scores, gm_wall_alignment_align_info *info)
+{
+    Alignment A;
+    if (!table || !info) return GM_ERR_INVALID_ARG;
+    GMW_OK(alignment_build(params, elements, n, A));
+    const gm_wall_align_params ap = params_or(prm, gm_wall_align_default_params);
+    gm_wall_alignment_align_plan_info plan;
+    GMW_OK(alignment_align_plan(A, pose, bound, ap, &plan));
+    if (n_scores != (2u * ap.max_station_shift + 1u) * (2u * ap.max_sector_shift + 1u)) return GM_ERR_INVALID_ARG;
+    return alignment_align_select(A, pose, ap, plan, table, info);
 }
 
 }  // extern "C"

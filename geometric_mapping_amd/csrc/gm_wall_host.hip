@@ -596,17 +596,12 @@ bool object_prm_ok(const gm_wall_object_params &p)
            p.half_window_stations >= 1u && p.half_window_stations <= (1u << 20);
 }
 
-void align_select(const DesignFrame &d, const gm_wall_params &wp, const gm_wall_align_params &ap, const double Rm[3][3],
-                  const double tr[3], const gm_wall_align_score *t, gm_wall_align_info *info)
+bool align_select_table(const gm_wall_align_params &ap, double ds, uint32_t nsec, const gm_wall_align_score *t, gm_wall_align_info *info)
 {
     const int A = (int)ap.max_station_shift, B = (int)ap.max_sector_shift, nb = 2 * B + 1, ns = (2 * A + 1) * nb;
     const double nan = __builtin_nan(""), inf = __builtin_inf();
-    const double ds = wp.station_length;
     memset(info, 0, sizeof(*info));
     info->struct_size = (uint32_t)sizeof(gm_wall_align_info);
-    const double rel[3] = {tr[0] - d.o[0], tr[1] - d.o[1], tr[2] - d.o[2]};
-    const double jd = floor((dot(rel, d.a) - wp.t_min) / ds);
-    info->anchor_station = fabs(jd) < 4.0e18 ? (int64_t)jd : 0;
     info->half_patch_stations = ap.half_patch_stations;
     info->max_station_shift = ap.max_station_shift;
     info->max_sector_shift = ap.max_sector_shift;
@@ -627,7 +622,7 @@ void align_select(const DesignFrame &d, const gm_wall_params &wp, const gm_wall_
         info->frac_station = info->frac_sector = info->shift_m = info->roll = info->bias_m = nan;
         info->rms_best = info->rms_runner = info->distinction = nan;
         for (int k = 0; k < 12; ++k) info->pose[k] = nan;
-        return;
+        return false;
     }
     const int ia = best / nb, ib = best % nb, sa = ia - A, sb = ib - B;
     const double c0 = cost(best);
@@ -654,7 +649,7 @@ void align_select(const DesignFrame &d, const gm_wall_params &wp, const gm_wall_
     info->frac_station = fa;
     info->frac_sector = fb;
     info->shift_m = ((double)sa + fa) * ds;
-    info->roll = ((double)sb + fb) * (kTwoPi / (double)wp.n_sectors);
+    info->roll = ((double)sb + fb) * (kTwoPi / (double)nsec);
     info->bias_m = ((double)t[best].sum_d * 0x1p-20) / (double)t[best].n;
     info->rms_best = sqrt(c0) * 0x1p-20;
     info->rms_runner = runner ? sqrt(cr) * 0x1p-20 : nan;
@@ -662,6 +657,18 @@ void align_select(const DesignFrame &d, const gm_wall_params &wp, const gm_wall_
     info->status = GM_ALIGN_OK;
     if (info->distinction < ap.min_distinction) info->status |= GM_ALIGN_AMBIGUOUS;
     if ((A > 0 && abs(sa) == A) || (B > 0 && abs(sb) == B)) info->status |= GM_ALIGN_AT_BORDER;
+    return true;
+}
+
+void align_select(const DesignFrame &d, const gm_wall_params &wp, const gm_wall_align_params &ap, const double Rm[3][3],
+                  const double tr[3], const gm_wall_align_score *t, gm_wall_align_info *info)
+{
+    const double ds = wp.station_length;
+    const bool ok = align_select_table(ap, ds, wp.n_sectors, t, info);
+    const double rel[3] = {tr[0] - d.o[0], tr[1] - d.o[1], tr[2] - d.o[2]};
+    const double jd = floor((dot(rel, d.a) - wp.t_min) / ds);
+    info->anchor_station = fabs(jd) < 4.0e18 ? (int64_t)jd : 0;
+    if (!ok) return;
     // Rm' = Q Rm, tr' = o + Q (tr - o) + shift_m a;  Q = cos I + sin [a]x + (1 - cos) a a^T
     const double cs = cos(info->roll), sn = sin(info->roll);
     const double *a = d.a;

@@ -147,6 +147,51 @@ __host__ __device__ inline void wall_locate_blocks(const WallLocateJointArgs &a,
     }
 }
 
+// k_wall_align_joint.hip (gm_wall_alignment_align_*): k_wall_align_bin and k_wall_align_values over an alignment; the score
+// kernel is k_wall_align.hip's, on a WallAlignArgs that carries the images and the table alone.
+// u64 words: the first kWallAlignCounters as k_wall_align_bin's (plane, beyond_gate, outside_patch, binned summed over the
+// sides, n_points, patch_cells_usable), then the four classes per side [GM_WALL_JOINT_MAX_SIDES][4].
+constexpr int kWallAlignJointCounters = kWallAlignCounters + GM_WALL_JOINT_MAX_SIDES * 4;
+struct WallAlignJointArgs {
+    const float4 *pts;
+    const uint8_t *labels;     // nullptr: no point is plane
+    const uint32_t *n_ptr;     // device point count (nullptr: n_host)
+    uint32_t n_host;
+    uint32_t n_sides;          // 1 .. GM_WALL_JOINT_MAX_SIDES
+    uint32_t P;                // half_patch_stations
+    float gate;                // the align's
+    WallJointGrid grid;
+    WallJointPlanes planes;
+    int32_t row0[GM_WALL_JOINT_MAX_SIDES];   // patch row of the side's anchor station: jr = row0 + jl
+    unsigned long long *ctr;   // [kWallAlignJointCounters]  } one block, zeroed by the caller on the same stream
+    unsigned long long *p_sum; // [2P n_sectors] the patch   }
+    uint32_t *p_cnt;           // [2P n_sectors]             }
+    float *res;                // stage call only (nullptr in the frame path)
+    int32_t *cell;
+    int32_t *element;
+    WallJointSide side[GM_WALL_JOINT_MAX_SIDES];   // (table, window fields unused)
+};
+// an element the map image's rows meet
+struct WallAlignPiece {
+    WallTable table;
+    int64_t first_row;         // the global station of the element's station 0
+    uint32_t n_stations;
+    uint32_t pad;
+};
+struct WallAlignJointValuesArgs {
+    uint32_t P, A, n_sectors, min_count, min_frame_count;
+    uint32_t n_pieces;         // 0 .. GM_WALL_ALIGN_MAX_PIECES
+    int64_t g0;                // the image's first global row G_f - P - A
+    unsigned long long *ctr;   // [kWallAlignJointCounters]
+    const unsigned long long *p_sum;
+    const uint32_t *p_cnt;
+    int32_t *f;                // [2P n_sectors]
+    int32_t *m;                // [(2P + 2A) n_sectors]
+    WallAlignPiece piece[GM_WALL_ALIGN_MAX_PIECES];
+};
+void launch_wall_align_bin_joint(const WallAlignJointArgs &a, uint32_t n_cap, hipStream_t s);
+void launch_wall_align_values_joint(const WallAlignJointValuesArgs &a, hipStream_t s);   // behind the wait on the adds
+
 // ---- device side ----
 
 // The joint planes of a block in LDS, Jo' then aJ' per joint: the kernels read them per point from there (a broadcast), 18
@@ -192,23 +237,32 @@ struct JointChainArgs {
     int64_t anchor;
 };
 
-// One trip of the add's and the check's side loop, for the lanes side S owns: S's chain under the call's gate, behind a
-// wave-uniform switch on the side's axis kind in front of the three chain heads of gm_device.hpp (wall_chain, exactly as
-// the kernels of a single map instantiate it).  S is read through uniform addresses: the side's frame stays in scalar
-// registers.  Returns whether the point is mapped; e, jl, kk are wall_chain's, j the map's station of a mapped point, cls
-// the chain's class (kChain*).
-__device__ __forceinline__ bool joint_side_chain(const float4 &q, uint32_t lab, const WallJointSide &S, const WallJointGrid &g, float gate,
-                                                 float &e, float &jl, uint32_t &kk, int64_t &j, uint32_t &cls)
+// One trip of a side loop, for the lanes side S owns: S's chain under the call's gate, behind a wave-uniform switch on the
+// side's axis kind in front of the three chain heads of gm_device.hpp (wall_chain, exactly as the kernels of a single map
+// instantiate it).  S is read through uniform addresses: the side's frame stays in scalar registers.  in_range(w, jl) is
+// the caller's range rule on the side's JointChainArgs w.  Returns whether the point passed gate and range; e, jl, kk are
+// wall_chain's, cls the chain's class (kChain*).
+template <class InRange>
+__device__ __forceinline__ bool joint_side_chain_in(const float4 &q, uint32_t lab, const WallJointSide &S, const WallJointGrid &g,
+                                                    float gate, InRange in_range_of, float &e, float &jl, uint32_t &kk, uint32_t &cls)
 {
     JointChainArgs w;
     for (int k = 0; k < 3; ++k) { w.o[k] = S.o[k]; w.a[k] = S.a[k]; w.u[k] = S.u[k]; w.v[k] = S.v[k]; }
     w.R = g.R; w.station_length = g.station_length; w.gate = gate; w.sector_angle = g.sector_angle; w.two_pi = g.two_pi;
     w.n_sectors = g.n_sectors; w.n_stations = S.n_stations; w.anchor = S.anchor;
-    auto in_range = [&](float x) { return (j = wall_station(w, x)) >= 0; };
+    auto in_range = [&](float x) { return in_range_of(w, x); };
     auto count = [&](uint32_t k) { cls = k; };
     if (S.axis == kAxisClothoid) return wall_chain(q, lab, w, WallClothoidArg{S.ax}, in_range, count, e, jl, kk);
     if (S.axis == kAxisArc) return wall_chain(q, lab, w, WallArcArg<true>{S.ax.arc}, in_range, count, e, jl, kk);
     return wall_chain(q, lab, w, WallArcArg<false>(), in_range, count, e, jl, kk);
+}
+// The add's and the check's trip: the range is the side's map (wall_station).  Returns whether the point is mapped; j the
+// map's station of a mapped point.
+__device__ __forceinline__ bool joint_side_chain(const float4 &q, uint32_t lab, const WallJointSide &S, const WallJointGrid &g, float gate,
+                                                 float &e, float &jl, uint32_t &kk, int64_t &j, uint32_t &cls)
+{
+    return joint_side_chain_in(q, lab, S, g, gate, [&](const JointChainArgs &w, float x) { return (j = wall_station(w, x)) >= 0; }, e, jl,
+                               kk, cls);
 }
 
 }  // namespace gm

@@ -122,6 +122,15 @@ gm_status alignment_window(const Alignment &A, double s_from, double s_to, gm_wa
                            uint32_t *n_out);
 // what a locate on the alignment starts from: the plan, the home section, the state, the attached vectors
 gm_status alignment_locate_start(const Alignment &A, const double pose[12], double bound, gm_wall_alignment_locate_start *out);
+// gm_wall_alignment_align_*: F(x), the design frame at alignment chainage x on the element the point rule picks; the plan
+// of an align (the add's plan, G_f, row0 per side, the pieces; GM_ERR_UNSUPPORTED: too many sides or pieces); the selection
+// and the pose from a table
+void alignment_frame(const Alignment &A, double x, double o[3], double a[3], double u[3], double v[3]);
+gm_status alignment_align_plan(const Alignment &A, const double pose[12], double bound, const gm_wall_align_params &ap,
+                               gm_wall_alignment_align_plan_info *out);
+gm_status alignment_align_select(const Alignment &A, const double pose[12], const gm_wall_align_params &ap,
+                                 const gm_wall_alignment_align_plan_info &plan, const gm_wall_align_score *table,
+                                 gm_wall_alignment_align_info *info);
 // the library's pose check: 0 the pose is accepted (Rm, tr filled), 1 an entry is not finite, 2 Rm is not a rotation
 int pose_split(const double pose[12], double Rm[3][3], double tr[3]);
 // the direction table of include/gm_hip.h: NK pairs (one operation per statement, as stated there)
@@ -144,6 +153,10 @@ bool locate_prm_ok(const gm_wall_locate_params &p);
 bool align_prm_ok(const gm_wall_align_params &p, uint32_t nsec);
 bool object_prm_ok(const gm_wall_object_params &p);
 bool add_checked_prm_ok(const gm_wall_add_checked_params &p, long long &S);   // S of an accepted block
+// The selection half of the align rule of include/gm_hip.h from a table of (2A + 1)(2B + 1) records on a grid of station
+// length ds and nsec sectors: everything of info but the device's counts, anchor_station and the pose (NaN when it returns
+// false: GM_ALIGN_NO_OVERLAP; zero otherwise).
+bool align_select_table(const gm_wall_align_params &ap, double ds, uint32_t nsec, const gm_wall_align_score *t, gm_wall_align_info *info);
 // The selection and the pose of include/gm_hip.h from a table of (2A + 1)(2B + 1) records.  Fills everything but the
 // device's counts.
 void align_select(const DesignFrame &d, const gm_wall_params &wp, const gm_wall_align_params &ap, const double Rm[3][3],
@@ -382,6 +395,8 @@ struct gm_wall_map {
     std::vector<gm::wall::PendingResult> *al_locates = nullptr;
     // gm_wall_alignment_check_*: the same for that alignment's pending checks
     std::vector<gm::wall::PendingResult> *al_checks = nullptr;
+    // gm_wall_alignment_align_*: the same for that alignment's pending aligns
+    std::vector<gm::wall::PendingResult> *al_aligns = nullptr;
     // gm_wall_map_add_frame_checked: per slot of ctx; gm_wall_map_add_points_checked: the stage call's own rows and block
     std::vector<gm::wall::WallAddCheckedSlot> add_checks;
     gm::DevArray<gm_wall_check_point> ac_rows;

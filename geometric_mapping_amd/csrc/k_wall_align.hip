@@ -21,33 +21,13 @@
 // k < n_sectors; every m index is below (2P + 2A) n_sectors; every table index below (2A + 1)(2B + 1).
 #include <string.h>
 
-#include "gm_internal.hpp"
-#include "gm_point_stream.hpp"
+#include "gm_wall_align.hpp"   // the bin kernels' shape and run merge, the halves of the values kernels
 
 namespace gm {
 
-constexpr int kAlignBinThreads = 1024;
-constexpr int kAlignBinUnroll = 2;
-constexpr uint32_t kAlignCells = GM_WALL_ALIGN_MAX_PATCH_CELLS;
-constexpr int kAlignThreads = 256;
 constexpr uint32_t kAlignMaxB = 2 * GM_WALL_ALIGN_MAX_SHIFT + 1;
 
 static_assert(sizeof(gm_wall_align_score) == 24, "the 24-byte score record");
-
-// runs of one patch cell folded into the run's head lane (gm_device.hpp: wave_runs and its ladder)
-__device__ __forceinline__ bool align_merge_runs(int cell, uint32_t &cn, unsigned long long &sm)
-{
-    const WaveRuns r = wave_runs(cell);
-    if (r.any) {
-#pragma unroll
-        for (int o = 1; o < kWave; o <<= 1) {
-            const uint32_t ocn = __shfl_down(cn, o, kWave);
-            const unsigned long long osm = __shfl_down(sm, o, kWave);
-            if (r.lane + o <= r.tail) { cn += ocn; sm += osm; }
-        }
-    }
-    return cell >= 0 && !r.dup;
-}
 
 __global__ __launch_bounds__(kAlignBinThreads) void k_wall_align_bin(WallAlignArgs a)
 {
@@ -110,30 +90,16 @@ __global__ __launch_bounds__(kAlignThreads) void k_wall_align_values(WallAlignAr
     uint32_t usable = 0u;
     for (uint32_t i = blockIdx.x * kAlignThreads + threadIdx.x; i < pcells + mcells; i += gridDim.x * kAlignThreads) {
         if (i < pcells) {
-            const uint32_t cn = a.p_cnt[i];
-            int32_t v = kWallAlignNone;
-            if (cn >= a.min_frame_count) {
-                v = (int32_t)((long long)a.p_sum[i] / (long long)cn);   // |v| <= 2^23
-                ++usable;
-            }
-            a.f[i] = v;
+            usable += align_patch_value(a.p_cnt, a.p_sum, a.min_frame_count, a.f, i);
         } else {
             const uint32_t c = i - pcells;
             const int64_t j = j0 + (int64_t)(c / nsec);
             int32_t v = kWallAlignNone;
-            if (j >= 0 && j < nst) {
-                const uint64_t g = (uint64_t)j * nsec + c % nsec;   // < n_stations * n_sectors
-                const uint32_t cn = w.table.cnt[g];
-                if (cn >= a.min_count) {
-                    const long long q = (long long)w.table.sum[g] / (long long)cn;
-                    v = q > kWallAlignSat ? kWallAlignSat : (q < -kWallAlignSat ? -kWallAlignSat : (int32_t)q);
-                }
-            }
+            if (j >= 0 && j < nst) v = align_map_value(w.table, (uint64_t)j * nsec + c % nsec, a.min_count);   // g < n_stations * n_sectors
             a.m[c] = v;
         }
     }
-    usable = wave_sum(usable);
-    if (lane_id() == 0 && usable) atomicAdd(&a.ctr[5], (unsigned long long)usable);
+    align_patch_usable(usable, &a.ctr[5]);
 }
 
 __global__ __launch_bounds__(kAlignThreads) void k_wall_align_score(WallAlignArgs a)

@@ -413,6 +413,23 @@ gm_wall_alignment_locate_info Processor::locateWallAlignment(const double pose[1
     return info;
 }
 
+gm_wall_alignment_align_info Processor::alignWallAlignment(const double pose[12], const gm_wall_align_params &prm,
+                                                           std::vector<gm_wall_align_score> *scores, gm_wall_alignment_align_plan_info *plan)
+{
+    if (!alignment_) throw Error(GM_ERR_NOT_READY, "alignWallAlignment: createWallAlignment first");
+    if (newest_slot_ < 0) throw Error(GM_ERR_NOT_READY, "alignWallAlignment: no frame yet");
+    const unsigned slot = (unsigned)newest_slot_;
+    check(gm_wall_alignment_align_frame(alignment_, ctx_, slot, pose, &prm, plan), "alignWallAlignment");
+    gm_wall_alignment_align_info info;
+    uint32_t count = 0;
+    check(gm_wall_alignment_get_align(alignment_, slot, &info, 0, 0, &count), "alignWallAlignment");
+    if (scores) {
+        scores->resize(count);
+        if (count) check(gm_wall_alignment_get_align(alignment_, slot, &info, &(*scores)[0], count, &count), "alignWallAlignment");
+    }
+    return info;
+}
+
 std::vector<gm_wall_check_point> Processor::checkWallAlignment(const double pose[12], const gm_wall_check_params &prm,
                                                                gm_wall_alignment_check_info *info, gm_wall_alignment_add_info *plan)
 {

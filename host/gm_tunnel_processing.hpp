@@ -237,6 +237,14 @@ public:
     // info.pose is the corrected pose (NaN when info.status & GM_LOCATE_FAILED_MASK).  The order per frame on an alignment:
     // locateWallAlignment, checkWallAlignment with the located pose, addToWallAlignmentChecked with it.
     gm_wall_alignment_locate_info locateWallAlignment(const double pose[12], const gm_wall_locate_params &prm);
+    // the newest frame's chainage and roll against the alignment (gm_wall_alignment_align_frame + gm_wall_alignment_get_align):
+    // alignWallMap on straight, arc and clothoid elements and across their joints; the element maps are not changed.
+    // info.pose is the aligned pose (NaN when info.status & GM_ALIGN_FAILED_MASK); scores and plan, when given, receive the
+    // score table and the plan of the call's sides and pieces.  The order per frame on an alignment: locateWallAlignment,
+    // alignWallAlignment with the located pose, checkWallAlignment with the aligned pose, addToWallAlignmentChecked with it.
+    gm_wall_alignment_align_info alignWallAlignment(const double pose[12], const gm_wall_align_params &prm,
+                                                    std::vector<gm_wall_align_score> *scores = nullptr,
+                                                    gm_wall_alignment_align_plan_info *plan = nullptr);
     // the changed points of the newest frame against the alignment under pose (gm_wall_alignment_check_frame +
     // gm_wall_alignment_get_check): every point against the map of the element that owns it, ascending by index; a row's
     // cell holds side << 24 | cell (GM_WALL_ROW_SIDE, GM_WALL_ROW_CELL; side indexes plan->side_element).  The element maps

@@ -2025,9 +2025,10 @@ gm_status gm_wall_clothoid_point(const gm_wall_params *params, const gm_wall_clo
  * and every point is classed exactly once.  The LDS table's GM_SURF_MAX_CELLS cells are dealt to the sides in order (a
  * side's window: the stations of its own add's window that lie in the element, cut to what is left); a mapped point outside
  * its side's window goes to the map directly, which affects speed only.
- * Out of scope: align (chainage and roll) and check objects through the alignment (they remain calls on an element map,
- * gm_wall_alignment_map); element maps of different grids; closed loops.  The locate is gm_wall_alignment_locate_*, the
- * check and the checked add gm_wall_alignment_check_* and gm_wall_alignment_add_*_checked below. */
+ * Out of scope: check objects through the alignment (they remain calls on an element map, gm_wall_alignment_map); element
+ * maps of different grids; closed loops.  The locate is gm_wall_alignment_locate_*, the align (chainage and roll)
+ * gm_wall_alignment_align_*, the check and the checked add gm_wall_alignment_check_* and gm_wall_alignment_add_*_checked
+ * below. */
 #define GM_WALL_ALIGNMENT_MAX_ELEMENTS 256
 #define GM_WALL_JOINT_MAX_SIDES 4
 enum { GM_WALL_ELEMENT_STRAIGHT = 0, GM_WALL_ELEMENT_ARC = 1, GM_WALL_ELEMENT_CLOTHOID = 2 };
@@ -2189,8 +2190,8 @@ gm_status gm_wall_alignment_info(gm_wall_alignment *alignment, gm_wall_alignment
  * atomics, no host round trip between the passes, one pending result per (alignment, slot).  Scratch per (alignment,
  * slot) -- the working state, 96 KiB of partial rows, a pinned copy of the result -- and the stage call's three per-point
  * arrays are allocated on first use, kept grow-only and freed with the alignment; an alignment that never locates across
- * a joint or on a curved element allocates nothing.  Out of scope: chainage and roll (they stay the caller's) and align
- * through the alignment. */
+ * a joint or on a curved element allocates nothing.  Out of scope: chainage and roll: they are gm_wall_alignment_align_*'s
+ * below. */
 typedef struct gm_wall_alignment_locate_pass {   /* 376 bytes; the first 112 are gm_wall_locate_pass */
     float    o[3], a[3], u[3], v[3];   /* the pass's state c, d, u', v' in SENSOR coordinates (fp32, as the points saw it) */
     float    gate;                     /* g_k */
@@ -2335,6 +2336,123 @@ gm_status gm_wall_alignment_add_points_checked(gm_wall_alignment *alignment, con
                                                const double pose[12], const gm_wall_add_checked_params *prm,
                                                const gm_wall_check_point *rows, uint32_t n_rows, gm_wall_alignment_add_info *plan,
                                                gm_wall_add_checked_info *info, float *residual, int32_t *cell, int32_t *element);
+
+/* ---- a frame's chainage and roll against a wall alignment (gm_wall_alignment_align_*) -----------------------------------
+ * gm_wall_map_align_* on the alignment: the same parameters (gm_wall_align_params), integer rule, statuses (GM_ALIGN_*) and
+ * score table, on straight, arc and clothoid elements and across their joints.  Every element shares one grid and is a
+ * whole number of stations long, and (u, v) turns rigidly with the section: the alignment is one continuous image of
+ * global station x sector.  Per frame on an alignment: gm_wall_alignment_locate_frame -> gm_wall_alignment_align_frame ->
+ * gm_wall_alignment_check_frame -> gm_wall_alignment_add_frame_checked.  One operation per statement.
+ *   global station  base_i = the sum of n_stations of the elements before i;  G = base_i + j for station j of element i;
+ *                 total = the sum over all elements.
+ *   per align     host, fp64.  The plan is gm_wall_alignment_add_plan's under the caller's pose, unchanged, with the same
+ *                 reach: the sides, each side's own per-add frame, the joint planes; the refusals are the add's (more than
+ *                 GM_WALL_JOINT_MAX_SIDES sides: GM_ERR_UNSUPPORTED, nothing is enqueued).  With e the sensor's side,
+ *                 G_f = base_e + side_anchor[e];  per side  row0_s = base_s + side_anchor[s] - G_f + P  in 64-bit integers,
+ *                 refused (GM_ERR_INVALID_ARG) unless it fits an int32.  The gate is the align's own, rounded to fp32 once.
+ *                 P, A, B, C as gm_wall_map_align_*.
+ *   per point     device, fp32.  The owner by the add's rule on the plan's planes.  The point runs its owner's chain alone
+ *                 (straight, arc or clothoid, as gm_wall_map_align_* instantiates the add's chain on a straight map).
+ *                 Classes in the chain's order: plane; beyond_gate; outside_patch; binned.  jl = floor(t / ds) relative to
+ *                 the OWNER's anchor;  jr = row0_owner + jl in 64-bit integers (|jl| >= 4e18: outside_patch);  binned iff
+ *                 0 <= jr < 2P.  Nothing is clamped to the owner's span: a point that its owner's chain places past the
+ *                 owner's end is binned at the row the chain gives it, and a row outside [0, total) is still binned and
+ *                 never overlaps, as on a map.  The patch cell jr * n_sectors + k, the sums of rint(e 2^20), the
+ *                 min_frame_count rule and f are gm_wall_map_align_*'s.  The class counts are kept per side.
+ *   map image     rows G = G_f - P - A .. G_f + P + A - 1.  Row G reads element i with base_i <= G < base_(i+1) at station
+ *                 j = G - base_i, and is unusable outside [0, total).  m as on a map: min_count, integer division,
+ *                 saturation.  The elements the rows meet are passed as pieces (element table, first global row,
+ *                 n_stations), ascending; more than GM_WALL_ALIGN_MAX_PIECES: GM_ERR_UNSUPPORTED, nothing is enqueued.  The
+ *                 pieces may be more than the sides: P + A stations can reach past the add's reach.
+ *   score table, selection, status   gm_wall_map_align_*'s, unchanged, on (f, m).
+ *   pose          host, fp64.  s = the plan's chainage of the sensor;  s' = s + shift_m.  F(x) = [a(x) u(x) v(x)] and P(x):
+ *                 the design frame at alignment chainage x of the element the `point` rule picks for x (the first element
+ *                 before the start, the last from the end on; gm_wall_arc_frame's, gm_wall_clothoid_frame's, or the
+ *                 straight frame at x - offset).  Q = the rotation by `roll` about the first axis in section coordinates
+ *                 ((1, 0, 0), (0, cos, -sin), (0, sin, cos) by rows).  M = F(s') Q F(s)^T;  Rm' = M Rm;
+ *                 tr' = P(s') + M (tr - P(s)).  On a straight element this is gm_wall_map_align_*'s pose.  The pose passes
+ *                 the library's own pose check.
+ *   one straight side   n_sides == 1, the sensor's element is straight and every image row lies in that element or outside
+ *                 [0, total): the align IS gm_wall_map_align_* of that element map -- the same launches, the table, the
+ *                 shared info fields and the pose byte for byte.  Every other plan, of 1 .. GM_WALL_JOINT_MAX_SIDES sides,
+ *                 runs the rule above.
+ *   ordering      no map is changed.  The align sees every add enqueued before it on any slot to the map of any piece (not
+ *                 only of the sides), through the alignment or through an element map, and none enqueued after: a later
+ *                 add on any slot waits for it through the alignment's pending results, as for a locate and a check.
+ * No floating-point atomics, no ticket, no host round trip inside the align.  Scratch per (alignment, slot) -- the patch,
+ * the two int32 images, the table, a pinned copy of the result -- is allocated by the first align that is not an element
+ * map's own, kept grow-only and freed with the alignment; an alignment that never aligns allocates nothing. */
+#define GM_WALL_ALIGN_MAX_PIECES 8
+typedef struct gm_wall_alignment_align_piece {   /* 16 bytes */
+    uint32_t element;
+    uint32_t n_stations;       /* the element's */
+    int64_t  first_row;        /* base_element: the global station of its station 0 */
+} gm_wall_alignment_align_piece;
+
+typedef struct gm_wall_alignment_align_plan_info {   /* 336 bytes: what an align's kernels receive, host only */
+    uint32_t struct_size;      /* = sizeof(gm_wall_alignment_align_plan_info), filled by the library */
+    uint32_t n_pieces;         /* 1 .. GM_WALL_ALIGN_MAX_PIECES; 0: no image row lies in [0, total) */
+    gm_wall_alignment_add_info add;   /* the plan of the add under the same pose */
+    int64_t  anchor_global;    /* G_f */
+    int64_t  total;            /* the alignment's stations */
+    int32_t  row0[GM_WALL_JOINT_MAX_SIDES];   /* per side; 0 from n_sides on */
+    uint32_t own;              /* 1: the "one straight side" rule holds: the align is the element map's own */
+    uint32_t home;             /* the sensor's element's index among the sides */
+    gm_wall_alignment_align_piece piece[GM_WALL_ALIGN_MAX_PIECES];   /* ascending; zero from n_pieces on */
+} gm_wall_alignment_align_plan_info;
+
+typedef struct gm_wall_alignment_align_info {   /* 472 bytes; the first 224 are gm_wall_align_info's */
+    uint32_t struct_size;     /* = sizeof(gm_wall_alignment_align_info), filled by the library */
+    uint32_t status;          /* GM_ALIGN_* */
+    uint32_t n_points;
+    uint32_t plane, beyond_gate, outside_patch, binned;   /* summed over the sides */
+    uint32_t patch_cells_usable;
+    int64_t  anchor_station;  /* j_f of the sensor's side */
+    uint32_t half_patch_stations, max_station_shift, max_sector_shift;
+    uint32_t overlap;
+    int32_t  best_station, best_sector;
+    double   frac_station, frac_sector;
+    double   shift_m, roll, bias_m, rms_best, rms_runner, distinction;
+    double   pose[12];        /* the aligned pose (the rule above) */
+    uint32_t element;         /* the sensor's element */
+    uint32_t n_sides;
+    double   chainage;        /* s */
+    int64_t  anchor_global;   /* G_f */
+    uint32_t side_class[GM_WALL_JOINT_MAX_SIDES][4];   /* plane, beyond_gate, outside_patch, binned per side; 0 from n_sides on */
+    gm_wall_alignment_add_info plan;
+} gm_wall_alignment_align_info;
+
+/* Host only, no context: the plan of an align under `pose` on a context whose boxFilterBound is `bound`: the add's plan,
+ * G_f, row0 per side and the pieces exactly as the kernels receive them.  prm NULL: the defaults.  GM_ERR_INVALID_ARG: NULL,
+ * the alignment's refusals, parameters gm_wall_align_check_params refuses on the alignment's n_sectors, a refused pose, a
+ * row0 beyond int32; GM_ERR_UNSUPPORTED: too many sides, or more than GM_WALL_ALIGN_MAX_PIECES pieces. */
+gm_status gm_wall_alignment_align_plan(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n,
+                                          const double pose[12], double bound, const gm_wall_align_params *prm,
+                                          gm_wall_alignment_align_plan_info *plan);
+/* Host only, no context: the selection and the pose of the rule above from a score table of (2A + 1)(2B + 1) records, as
+ * gm_wall_align_select on a map: everything of info but the device's counts (n_points, the classes, side_class,
+ * patch_cells_usable stay 0).  Errors as gm_wall_alignment_align_plan; a wrong n_scores: GM_ERR_INVALID_ARG. */
+gm_status gm_wall_alignment_align_select(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n,
+                                         const double pose[12], double bound, const gm_wall_align_params *prm,
+                                         const gm_wall_align_score *table, uint32_t n_scores, gm_wall_alignment_align_info *info);
+/* gm_wall_map_align_frame on the alignment (prm NULL: the defaults).  plan may be NULL.  GM_ERR_INVALID_ARG: NULL, a foreign
+ * context, a bad slot, bad parameters, a refused pose; GM_ERR_NOT_READY: the slot holds no frame; GM_ERR_UNSUPPORTED: too
+ * many sides or pieces. */
+gm_status gm_wall_alignment_align_frame(gm_wall_alignment *alignment, gm_ctx *ctx, uint32_t slot, const double pose[12],
+                                        const gm_wall_align_params *prm, gm_wall_alignment_align_plan_info *plan);
+/* The result of the last align enqueued on (alignment, slot), as gm_wall_map_get_align: waits for that align only; info,
+ * n_out may be NULL; scores NULL with capacity 0 is a count query; GM_ERR_CAPACITY.  GM_ERR_NOT_READY: none was enqueued;
+ * GM_ERR_INVALID_ARG: NULL, a bad slot.  gm_wall_alignment_align_points counts as an align on slot 0. */
+gm_status gm_wall_alignment_get_align(gm_wall_alignment *alignment, uint32_t slot, gm_wall_alignment_align_info *info,
+                                      gm_wall_align_score *scores, uint32_t capacity, uint32_t *n_out);
+/* The same kernels as one blocking stage call on host buffers (slot 0).  The per-point outputs may each be NULL: residual
+ * (e, NaN for plane points), cell (jr * n_sectors + k of a binned point, else -1), element (the owner's element index, set
+ * for every point). */
+gm_status gm_wall_alignment_align_points(gm_wall_alignment *alignment, const float *xyz, uint32_t n, const uint8_t *labels,
+                                         const double pose[12], const gm_wall_align_params *prm,
+                                         gm_wall_alignment_align_plan_info *plan, gm_wall_alignment_align_info *info,
+                                         gm_wall_align_score *scores, uint32_t capacity, uint32_t *n_out, float *residual,
+                                         int32_t *cell, int32_t *element);
 
 /* "Compressed map" record of a completed slot.  The reference defines no such
  * output; this is a build-defined format: header, primitive records,
