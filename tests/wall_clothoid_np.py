@@ -289,6 +289,7 @@ PIO2 = np.array([1.5703125, 4.837512969970703125e-4, 7.54978995489188216e-8], F)
 SIN_C = np.array([-1.9515295891e-4, 8.3321608736e-3, -1.6666654611e-1], F)
 COS_C = np.array([2.443315711809948e-5, -1.388731625493765e-3, 4.166664568298827e-2], F)
 GUARD_DEN = True                     # the den > 0.25 test (the sensitivity test drops it; the cy > 0 test is wall_arc_np.GUARD_CY)
+GUARD_G = True                       # the closing tests: t finite and |g| <= G_BOUND (tests/test_wall_stray_np.py drops them)
 
 
 def sincos_f32(ps):
@@ -376,7 +377,7 @@ def points_f32(xyz, f, labels=None, p=None, gate=None, shifts=None):
             good = (cy > F(0.0)) if wa.GUARD_CY else np.ones(len(x), bool)
             if GUARD_DEN:
                 good = good & np.all(dens > F(MIN_DEN), axis=0)
-            return good & (np.abs(t) < F(np.inf)) & (np.abs(g) <= F(G_BOUND))
+            return good & (np.abs(t) < F(np.inf)) & (np.abs(g) <= F(G_BOUND)) if GUARD_G else good
 
         variants = [(e, ok_of(t, g, dens), t, yc, z)]
         shifts = wa.SHIFTS if shifts is None else shifts
