@@ -524,6 +524,28 @@ class GmError(RuntimeError):
         self.status = status
 
 
+def info_fields(struct):
+    """The field names an info or metrics dict carries: the struct's, less struct_size and reserved."""
+    return tuple(k for k, _t in struct._fields_ if k not in ("struct_size", "reserved"))
+
+
+def params(struct, default_fn, family, kw):
+    """A parameter struct with the library's defaults (`default_fn`, its gm_*_default_params), then the keywords `kw`:
+    a scalar field takes the value, an array field a sequence of floats.  struct_size, reserved and a name the struct
+    does not have are a TypeError that names the `family`."""
+    p = struct()
+    getattr(load(), default_fn)(C.byref(p))
+    fields = info_fields(struct)
+    for k, v in kw.items():
+        if k not in fields:
+            raise TypeError(f"unknown {family} parameter {k!r}")
+        if isinstance(getattr(p, k), C.Array):
+            getattr(p, k)[:] = [float(x) for x in v]
+        else:
+            setattr(p, k, v)
+    return p
+
+
 _lib = None
 
 
@@ -572,34 +594,27 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(make -C geometric_mapping_amd/csrc).  There is no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    vp, u32, u32p, fp, dp, i32p, u8p = (C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float),
-                                         C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8))
-    cfgp, cloudp, resp = C.POINTER(Config), C.POINTER(Cloud), C.POINTER(FrameResult)
-    fitp = C.POINTER(CylinderFit)
-    sprmp, scellp, sinfop = C.POINTER(SurfaceParams), C.POINTER(SurfaceCell), C.POINTER(SurfaceInfo)
-    wprmp, wrawp, waddp, winfop = C.POINTER(WallParams), C.POINTER(WallRawCell), C.POINTER(WallAddInfo), C.POINTER(WallInfo)
-    u64, u64p = C.c_uint64, C.POINTER(C.c_uint64)
-    warcp, warcaddp = C.POINTER(WallArc), C.POINTER(WallArcAddInfo)
-    wclp, wcladdp = C.POINTER(WallClothoid), C.POINTER(WallClothoidAddInfo)
-    welp, wpcp, waladdp, waltotp = (C.POINTER(WallElement), C.POINTER(WallAlignmentPiece), C.POINTER(WallAlignmentAddInfo),
-                                    C.POINTER(WallAlignmentTotals))
-    wregp, wrprmp, wrinfop, wrmetp = (C.POINTER(WallRegion), C.POINTER(WallRegionParams), C.POINTER(WallRegionsInfo),
-                                      C.POINTER(WallRegionMetrics))
-    wcprmp, wcptp, wcinfop = C.POINTER(WallCloudParams), C.POINTER(WallCloudPoint), C.POINTER(WallCloudInfo)
-    wmprmp, wmtrip, wminfop = C.POINTER(WallMeshParams), C.POINTER(WallMeshTriangle), C.POINTER(WallMeshInfo)
-    wgprmp, wgstp, wgcellp, wginfop, wgrunp = (C.POINTER(WallClearanceParams), C.POINTER(WallClearanceStation),
-                                               C.POINTER(WallClearanceCell), C.POINTER(WallClearanceInfo), C.POINTER(WallClearanceRun))
-    wsprmp, wssump, wssecp, wsinfop, wsmetp = (C.POINTER(WallSectionParams), C.POINTER(WallSectionSums), C.POINTER(WallSection),
-                                               C.POINTER(WallSectionsInfo), C.POINTER(WallSectionMetrics))
-    wqprmp, wqrecp, wqinfop, wqcolp, wqmetp, wqrunp = (C.POINTER(WallQuantityParams), C.POINTER(WallQuantity),
-                                                       C.POINTER(WallQuantitiesInfo), C.POINTER(WallQuantityColumnResult),
-                                                       C.POINTER(WallQuantityMetrics), C.POINTER(WallQuantityRun))
-    wkprmp, wkptp, wkinfop = C.POINTER(WallCheckParams), C.POINTER(WallCheckPoint), C.POINTER(WallCheckInfo)
-    wcaprmp, wcainfop = C.POINTER(WallAddCheckedParams), C.POINTER(WallAddCheckedInfo)
-    wlprmp, wlinfop = C.POINTER(WallLocateParams), C.POINTER(WallLocateInfo)
-    waprmp, wascp, wainfop = C.POINTER(WallAlignParams), C.POINTER(WallAlignScore), C.POINTER(WallAlignInfo)
-    woprmp, wobjp, woinfop, wometp = (C.POINTER(WallObjectParams), C.POINTER(WallObject), C.POINTER(WallObjectsInfo),
-                                      C.POINTER(WallObjectMetrics))
+    P = C.POINTER
+    vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
+    u32p, u64p, fp, dp, i32p, u8p = map(P, (C.c_uint32, C.c_uint64, C.c_float, C.c_double, C.c_int32, C.c_uint8))
+    cfgp, cloudp, resp, fitp = map(P, (Config, Cloud, FrameResult, CylinderFit))
+    sprmp, scellp, sinfop = map(P, (SurfaceParams, SurfaceCell, SurfaceInfo))
+    wprmp, wrawp, waddp, winfop = map(P, (WallParams, WallRawCell, WallAddInfo, WallInfo))
+    warcp, warcaddp, wclp, wcladdp = map(P, (WallArc, WallArcAddInfo, WallClothoid, WallClothoidAddInfo))
+    welp, wpcp, waladdp, waltotp = map(P, (WallElement, WallAlignmentPiece, WallAlignmentAddInfo, WallAlignmentTotals))
+    wregp, wrprmp, wrinfop, wrmetp = map(P, (WallRegion, WallRegionParams, WallRegionsInfo, WallRegionMetrics))
+    wcprmp, wcptp, wcinfop = map(P, (WallCloudParams, WallCloudPoint, WallCloudInfo))
+    wmprmp, wmtrip, wminfop = map(P, (WallMeshParams, WallMeshTriangle, WallMeshInfo))
+    wgprmp, wgstp, wgcellp, wginfop, wgrunp = map(P, (WallClearanceParams, WallClearanceStation, WallClearanceCell,
+                                                      WallClearanceInfo, WallClearanceRun))
+    wsprmp, wssump, wssecp, wsinfop, wsmetp = map(P, (WallSectionParams, WallSectionSums, WallSection, WallSectionsInfo,
+                                                      WallSectionMetrics))
+    wqprmp, wqrecp, wqinfop, wqcolp, wqmetp, wqrunp = map(P, (WallQuantityParams, WallQuantity, WallQuantitiesInfo,
+                                                              WallQuantityColumnResult, WallQuantityMetrics, WallQuantityRun))
+    wkprmp, wkptp, wkinfop = map(P, (WallCheckParams, WallCheckPoint, WallCheckInfo))
+    wcaprmp, wcainfop, wlprmp, wlinfop = map(P, (WallAddCheckedParams, WallAddCheckedInfo, WallLocateParams, WallLocateInfo))
+    waprmp, wascp, wainfop = map(P, (WallAlignParams, WallAlignScore, WallAlignInfo))
+    woprmp, wobjp, woinfop, wometp = map(P, (WallObjectParams, WallObject, WallObjectsInfo, WallObjectMetrics))
     proto = {
         "gm_create": (C.c_int, [cfgp, C.POINTER(vp)]),
         "gm_destroy": (None, [vp]),

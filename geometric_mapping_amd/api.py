@@ -29,6 +29,74 @@ def _f32(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _dptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _rptr(a, struct):
+    """The records of a numpy array as a pointer to their struct."""
+    return a.ctypes.data_as(C.POINTER(struct))
+
+
+def _ints(info, fields):
+    return {k: int(getattr(info, k)) for k in fields}
+
+
+def _stage_front(cloud, pose, labels):
+    """The opening arguments of a stage call on a host cloud: (n, (xyz pointer, n, label pointer or None, pose pointer)),
+    the pose pointer left out when `pose` is None.  The arrays live as long as the pointers: ndarray.ctypes.data_as
+    keeps a reference to its array in the pointer it returns (numpy documents that), so nothing else need hold them."""
+    xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+    tail = () if pose is None else (_dptr(WallMap._pose(pose)),)
+    lab, lp = GeometricMapping._u8(labels)
+    return len(xyz), (_f32(xyz), len(xyz), lp) + tail
+
+
+class _PointOutputs:
+    """The per-point outputs of one stage call, from an ordered (name, dtype) list: a buffer of max(n, 1) entries each
+    when `outputs` is set, none otherwise (the ABI takes NULL for an output that is not wanted)."""
+
+    def __init__(self, n, outputs, fields):
+        self.n, self.fields = n, fields
+        self.buf = {k: np.empty(max(n, 1), dtype=t) for k, t in fields} if outputs else None
+
+    def ptrs(self):
+        """One pointer, or None, per output in order."""
+        if self.buf is None:
+            return (None,) * len(self.fields)
+        return tuple(b.ctypes.data_as(_OUT_PTR[b.dtype]) for b in self.buf.values())
+
+    def tuple(self):
+        """The outputs trimmed to n, copied, in order; None each without outputs."""
+        if self.buf is None:
+            return (None,) * len(self.fields)
+        return tuple(b[:self.n].copy() for b in self.buf.values())
+
+    def dict(self):
+        """The same by name; None without outputs."""
+        return {k: b[:self.n].copy() for k, b in self.buf.items()} if self.buf is not None else None
+
+
+_OUT_PTR = {np.dtype(t): C.POINTER(c) for t, c in ((np.float32, C.c_float), (np.int32, C.c_int32), (np.uint8, C.c_uint8))}
+_RES_CELL = (("res", np.float32), ("cell", np.int32))
+_CHECK_OUT = (("e", np.float32), ("cell", np.int32), ("delta", np.int32), ("cls", np.uint8))
+_ALIGN_OUT = (("e", np.float32), ("cell", np.int32))
+_ELEMENT = (("element", np.int32),)
+
+
+def _sized(call, struct, got, fetch):
+    """A count query, then the sized call: call(records, capacity, sized) is the bound and checked ABI call, which leaves
+    the count in `got` -- (None, 0, False) in the query, (the buffer, the count, True) in the sized call, so a caller whose
+    other outputs travel with the sized call only picks them by `sized`; fetch(capacity) is the caller's rule for making
+    the sized call at all.  Returns the records of `struct`, as many as `got` says."""
+    call(None, 0, False)
+    cap = int(got.value)
+    rec = np.zeros(max(cap, 1), dtype=struct)
+    if fetch(cap):
+        call(_rptr(rec, struct), cap, True)
+    return rec[:int(got.value)].copy()
+
+
 class GeometricMapping:
     """One gm_ctx.  Parameter names and defaults are the node's
     (/root/reference launch/mapping.launch:7-10, paramHandler.hpp:26-29)."""
@@ -418,31 +486,20 @@ class GeometricMapping:
         """tunnel_processing.hpp:56-59 (the reference's empty regression stub) as one stage call (gm_fit_cylinder):
         points with labels == want (all when labels is None), starting row init7 (point, direction, radius).
         Returns (fit dict as cylinder_fit, boolean inlier mask [n])."""
-        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+        n, head = _stage_front(cloud, None, labels)
         init = np.ascontiguousarray(np.asarray(init7, dtype=np.float32).reshape(7))
-        lab, lp = self._u8(labels)
-        mask = np.zeros(max(len(xyz), 1), dtype=np.uint8)
+        mask = np.zeros(max(n, 1), dtype=np.uint8)
         f = CylinderFit()
-        self._check(self._L.gm_fit_cylinder(self._ctx, _f32(xyz), len(xyz), lp, int(want), _f32(init), float(tau),
-                                            C.byref(f), mask.ctypes.data_as(C.POINTER(C.c_uint8))))
-        return self._fit(f), mask[:len(xyz)].astype(bool)
+        self._check(self._L.gm_fit_cylinder(self._ctx, *head, int(want), _f32(init), float(tau), C.byref(f),
+                                            mask.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return self._fit(f), mask[:n].astype(bool)
 
     # ---- wall deviation map (GM_CFG_SURFACE_MAP; include/gm_hip.h states the semantics) ----
     @staticmethod
     def surface_params(**kw):
         """gm_surface_params with the library's defaults, then the keywords (n_stations, n_sectors, station_length, t_min,
         gate, up, forward)."""
-        L = _lib.load()
-        p = _lib.SurfaceParams()
-        L.gm_surface_default_params(C.byref(p))
-        for k, v in kw.items():
-            if k in ("up", "forward"):
-                getattr(p, k)[:] = [float(x) for x in v]
-            elif not hasattr(p, k) or k == "struct_size":
-                raise TypeError(f"unknown surface parameter {k!r}")
-            else:
-                setattr(p, k, v)
-        return p
+        return _lib.params(_lib.SurfaceParams, "gm_surface_default_params", "surface", kw)
 
     def set_surface_params(self, **kw):
         """gm_set_surface_params: the map parameters of the frames submitted after the call."""
@@ -493,18 +550,15 @@ class GeometricMapping:
     def surfaceMap(self, cloud, model7, labels=None, **params):
         """The map as one stage call (gm_surface_map) on a host cloud [n,3] against model7 = (c, d, R) (e.g. a frame's
         cylinder_fit()["model"]); labels None: no point is plane.  Returns (info, count, mean, min, max, residual, cell)."""
-        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+        n, head = _stage_front(cloud, None, labels)
         m = np.ascontiguousarray(np.asarray(model7, dtype=np.float32).reshape(7))
-        lab, lp = self._u8(labels)
         p = self.surface_params(**params)
         info = _lib.SurfaceInfo()
         nc = int(p.n_stations) * int(p.n_sectors)
         cells = (_lib.SurfaceCell * max(nc, 1))()
-        res = np.empty(max(len(xyz), 1), dtype=np.float32)
-        cell = np.empty(max(len(xyz), 1), dtype=np.int32)
-        self._check(self._L.gm_surface_map(self._ctx, _f32(xyz), len(xyz), lp, _f32(m), C.byref(p), C.byref(info), cells,
-                                           nc, _f32(res), cell.ctypes.data_as(C.POINTER(C.c_int32))))
-        return (*self._surface(info, cells), res[:len(xyz)].copy(), cell[:len(xyz)].copy())
+        out = _PointOutputs(n, True, _RES_CELL)
+        self._check(self._L.gm_surface_map(self._ctx, *head, _f32(m), C.byref(p), C.byref(info), cells, nc, *out.ptrs()))
+        return (*self._surface(info, cells), *out.tuple())
 
     def wall_map(self, arc=None, clothoid=None, **params):
         """A persistent wall map owned by this context (gm_wall_map_create): WallMap.  Keywords: gm_wall_params fields
@@ -521,44 +575,83 @@ class GeometricMapping:
         return WallAlignment(self, elements, **params)
 
 
-RAW_CELL = np.dtype([("sum", "<i8"), ("count", "<u4"), ("min_key", "<u4"), ("max_key", "<u4"), ("reserved", "<u4")])
-_CELL = np.dtype([("count", "<u4"), ("mean", "<f4"), ("min", "<f4"), ("max", "<f4")])
+# every record dtype is its struct's: _lib.py states each layout once
+RAW_CELL = np.dtype(_lib.WallRawCell)                           # gm_wall_raw_cell, 24 bytes
+_CELL = np.dtype(_lib.SurfaceCell)                              # gm_surface_cell, 16 bytes
+REGION = np.dtype(_lib.WallRegion)                              # gm_wall_region, 64 bytes
+WALL_CLOUD_POINT = np.dtype(_lib.WallCloudPoint)                # gm_wall_cloud_point, 40 bytes
+WALL_MESH_TRIANGLE = np.dtype("<u4")   # gm_wall_mesh_triangle is three of them: meshes are uint32 [nt, 3]
+WALL_CHECK_POINT = np.dtype(_lib.WallCheckPoint)                # gm_wall_check_point, 32 bytes
+WALL_OBJECT = np.dtype(_lib.WallObject)                         # gm_wall_object, 128 bytes
+WALL_ALIGN_SCORE = np.dtype(_lib.WallAlignScore)                # gm_wall_align_score, 24 bytes
+WALL_CLEARANCE_STATION = np.dtype(_lib.WallClearanceStation)    # gm_wall_clearance_station, 32 bytes
+WALL_CLEARANCE_CELL = np.dtype(_lib.WallClearanceCell)          # gm_wall_clearance_cell, 16 bytes
+WALL_CLEARANCE_RUN = np.dtype(_lib.WallClearanceRun)            # gm_wall_clearance_run, 72 bytes
+WALL_QUANTITY = np.dtype(_lib.WallQuantity)                     # gm_wall_quantity, 88 bytes
+WALL_QUANTITY_RUN = np.dtype(_lib.WallQuantityRun)              # gm_wall_quantity_run, 136 bytes
+WALL_SECTION = np.dtype(_lib.WallSection)                       # gm_wall_section, 144 bytes
+WALL_SECTION_SUMS = np.dtype(_lib.WallSectionSums)              # gm_wall_section_sums, 448 bytes
+# the keys of an info dict are its struct's fields less struct_size and reserved, except where written out
+_REGION_METRICS = _lib.info_fields(_lib.WallRegionMetrics)
+_CLOUD_INFO = _lib.info_fields(_lib.WallCloudInfo)
+_CHECK_INFO = _lib.info_fields(_lib.WallCheckInfo)
+_OBJECTS_INFO = _lib.info_fields(_lib.WallObjectsInfo)
+_CLEARANCE_INFO = _lib.info_fields(_lib.WallClearanceInfo)
+_QUANTITIES_INFO = _lib.info_fields(_lib.WallQuantitiesInfo)
+_SECTIONS_INFO = _lib.info_fields(_lib.WallSectionsInfo)
 _WALL_VEC = ("point", "direction", "up", "forward")
-REGION = np.dtype([("label", "<u4"), ("sign", "<i4"), ("cells", "<u4"), ("station_min", "<u4"), ("station_max", "<u4"),
-                   ("sector_min", "<u4"), ("sector_max", "<u4"), ("sector_min_turned", "<u4"), ("sector_max_turned", "<u4"),
-                   ("peak_cell", "<u4"), ("peak", "<i8"), ("sum_d", "<i8"), ("points", "<u8")])   # gm_wall_region, 64 bytes
 _REGION_INFO = ("station0", "n_stations", "n_sectors", "threshold_q", "flagged_pos", "flagged_neg", "unusable", "empty",
                 "components", "regions")
-_REGION_METRICS = tuple(k for k, _ in _lib.WallRegionMetrics._fields_)
-WALL_CLOUD_POINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("mean", "<f4"), ("min", "<f4"), ("max", "<f4"),
-                             ("block", "<u4"), ("cells", "<u4"), ("count", "<u8")])   # gm_wall_cloud_point, 40 bytes
-_CLOUD_INFO = ("station0", "n_stations", "n_sectors", "blocks_stations", "blocks_sectors", "blocks", "points",
-               "below_min_count", "empty")
-WALL_MESH_TRIANGLE = np.dtype("<u4")   # gm_wall_mesh_triangle is three of them: meshes are uint32 [nt, 3]
 _MESH_INFO = ("wrapped", "quads", "quads_two", "quads_one", "quads_none", "cut_by_step", "triangles")
-WALL_CHECK_POINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("delta", "<f4"), ("e", "<f4"), ("cell", "<i4"),
-                             ("index", "<u4"), ("row", "<u4")])   # gm_wall_check_point, 32 bytes
-_CHECK_INFO = ("status", "threshold_q", "n_points", "plane", "beyond_gate", "outside", "unsurveyed", "unchanged",
-               "changed_pos", "changed_neg", "peak_pos", "peak_neg")
 _ADD_CHECKED_INFO = ("status", "min_delta_q", "n_points", "n_rows", "rows_neg", "rows_pos", "rows_kept", "rows_rejected",
                      "skipped", "plane", "beyond_gate", "outside", "mapped", "reserved")
-WALL_OBJECT = np.dtype([("label", "<u4"), ("sign", "<i4"), ("blocks", "<u4"), ("peak_index", "<u4"), ("station_min", "<u4"),
-                        ("station_max", "<u4"), ("sector_min", "<u4"), ("sector_max", "<u4"), ("sector_min_turned", "<u4"),
-                        ("sector_max_turned", "<u4"), ("points", "<u8"), ("peak", "<i8"), ("sum_delta", "<i8"), ("sum_x", "<i8"),
-                        ("sum_y", "<i8"), ("sum_z", "<i8"), ("box_min", "<f4", (3,)), ("box_max", "<f4", (3,)), ("e_min", "<f4"),
-                        ("e_max", "<f4"), ("reserved", "<u8")])   # gm_wall_object, 128 bytes
-_OBJECTS_INFO = ("n_rows", "station0", "n_stations", "blocks_stations", "blocks_sectors", "rejected", "outside_window", "sparse",
-                 "small", "in_object", "flagged_pos", "flagged_neg", "components", "objects")
+_ALIGN_INT = ("status", "n_points", "plane", "beyond_gate", "outside_patch", "binned", "patch_cells_usable", "anchor_station",
+              "half_patch_stations", "max_station_shift", "max_sector_shift", "overlap", "best_station", "best_sector")
+_ALIGN_F64 = ("frac_station", "frac_sector", "shift_m", "roll", "bias_m", "rms_best", "rms_runner", "distinction")
+
+
+def _wall_params(**kw):
+    return _lib.params(_lib.WallParams, "gm_wall_default_params", "wall map", kw)
+
+
+def _wall_region_params(**kw):
+    return _lib.params(_lib.WallRegionParams, "gm_wall_region_default_params", "region", kw)
+
+
+def _wall_cloud_params(**kw):
+    return _lib.params(_lib.WallCloudParams, "gm_wall_cloud_default_params", "cloud", kw)
+
+
+def _wall_clearance_params(**kw):
+    return _lib.params(_lib.WallClearanceParams, "gm_wall_clearance_default_params", "clearance", kw)
+
+
+def _wall_section_params(**kw):
+    return _lib.params(_lib.WallSectionParams, "gm_wall_section_default_params", "section", kw)
+
+
+def _wall_quantity_params(**kw):
+    return _lib.params(_lib.WallQuantityParams, "gm_wall_quantity_default_params", "quantity", kw)
 
 
 def _wall_check_params(**kw):
-    p = _lib.WallCheckParams()
-    _lib.load().gm_wall_check_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k) or k in ("struct_size", "reserved"):
-            raise TypeError(f"unknown check parameter {k!r}")
-        setattr(p, k, v)
-    return p
+    return _lib.params(_lib.WallCheckParams, "gm_wall_check_default_params", "check", kw)
+
+
+def _wall_add_checked_params(**kw):
+    return _lib.params(_lib.WallAddCheckedParams, "gm_wall_add_checked_default_params", "checked-add", kw)
+
+
+def _wall_locate_params(**kw):
+    return _lib.params(_lib.WallLocateParams, "gm_wall_locate_default_params", "locate", kw)
+
+
+def _wall_align_params(**kw):
+    return _lib.params(_lib.WallAlignParams, "gm_wall_align_default_params", "align", kw)
+
+
+def _wall_object_params(**kw):
+    return _lib.params(_lib.WallObjectParams, "gm_wall_object_default_params", "object", kw)
 
 
 def wall_check_classify(raw_cell, e, **params):
@@ -572,32 +665,6 @@ def wall_check_classify(raw_cell, e, **params):
     if st != _lib.GM_OK:
         raise _lib.GmError(st, "gm_wall_check_classify refused the parameters")
     return int(d.value), int(c.value)
-
-
-def _wall_locate_params(**kw):
-    p = _lib.WallLocateParams()
-    _lib.load().gm_wall_locate_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k) or k in ("struct_size", "reserved"):
-            raise TypeError(f"unknown locate parameter {k!r}")
-        setattr(p, k, v)
-    return p
-
-
-WALL_ALIGN_SCORE = np.dtype([("ssd", "<u8"), ("sum_d", "<i8"), ("n", "<u4"), ("reserved", "<u4")])   # gm_wall_align_score, 24 bytes
-_ALIGN_INT = ("status", "n_points", "plane", "beyond_gate", "outside_patch", "binned", "patch_cells_usable", "anchor_station",
-              "half_patch_stations", "max_station_shift", "max_sector_shift", "overlap", "best_station", "best_sector")
-_ALIGN_F64 = ("frac_station", "frac_sector", "shift_m", "roll", "bias_m", "rms_best", "rms_runner", "distinction")
-
-
-def _wall_align_params(**kw):
-    p = _lib.WallAlignParams()
-    _lib.load().gm_wall_align_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k) or k in ("struct_size", "reserved"):
-            raise TypeError(f"unknown align parameter {k!r}")
-        setattr(p, k, v)
-    return p
 
 
 def _align_info(i):
@@ -623,16 +690,6 @@ def align_select(wall_params, pose, table, **params):
     return _align_info(info)
 
 
-def _wall_object_params(**kw):
-    p = _lib.WallObjectParams()
-    _lib.load().gm_wall_object_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k) or k in ("struct_size", "reserved"):
-            raise TypeError(f"unknown object parameter {k!r}")
-        setattr(p, k, v)
-    return p
-
-
 def object_metrics(prm, obj, **params):
     """gm_wall_object_metrics (host only): the fp64 metrics dict (centroid and size as float64 [3]) of one WALL_OBJECT
     record under the gm_wall_params `prm` and the object parameters given as keywords."""
@@ -656,26 +713,6 @@ def wall_region_metrics(prm, region):
     if st != _lib.GM_OK:
         raise _lib.GmError(st, "gm_wall_region_metrics refused the record")
     return {k: float(getattr(out, k)) for k in _REGION_METRICS}
-
-
-WALL_CLEARANCE_STATION = np.dtype([("min_clearance", "<i8"), ("min_sector", "<u4"), ("usable", "<u4"), ("tight", "<u4"),
-                                   ("infringed", "<u4"), ("unsurveyed", "<u4"), ("gauge", "<u4")])   # gm_wall_clearance_station, 32 bytes
-WALL_CLEARANCE_CELL = np.dtype([("cell", "<u4"), ("count", "<u4"), ("clearance", "<i8")])   # gm_wall_clearance_cell, 16 bytes
-WALL_CLEARANCE_RUN = np.dtype([("station_from", "<u4"), ("station_to", "<u4"), ("chainage_from", "<f8"), ("chainage_to", "<f8"),
-                               ("min_clearance", "<i8"), ("min_clearance_m", "<f8"), ("min_station", "<u4"), ("min_sector", "<u4"),
-                               ("angle_deg", "<f8"), ("tight", "<u8"), ("infringed", "<u8")])   # gm_wall_clearance_run, 72 bytes
-_CLEARANCE_INFO = ("station0", "n_stations", "n_sectors", "margin_q", "radius_q", "ungauged", "empty", "unusable", "infringed",
-                   "tight", "clear", "stations_tight", "stations_infringed", "min_clearance", "min_cell")
-
-
-def _wall_clearance_params(**kw):
-    p = _lib.WallClearanceParams()
-    _lib.load().gm_wall_clearance_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k) or k in ("struct_size", "reserved"):
-            raise TypeError(f"unknown clearance parameter {k!r}")
-        setattr(p, k, v)
-    return p
 
 
 def _gauge_tables(gauge_q, n_sectors):
@@ -722,32 +759,9 @@ def wall_clearance_runs(prm, stations, station0=0, max_gap=0):
     return runs[:int(got.value)].copy()
 
 
-WALL_QUANTITY = np.dtype([("station_from", "<u4"), ("stations", "<u4"), ("zone", "<u4"), ("profile", "<u4"), ("under", "<u4"),
-                          ("within", "<u4"), ("over", "<u4"), ("unsurveyed", "<u4"), ("points", "<u8"), ("under_area", "<i8"),
-                          ("over_area", "<i8"), ("excess_area", "<i8"), ("peak_under", "<i8"), ("peak_over", "<i8"),
-                          ("peak_under_sector", "<u4"), ("peak_over_sector", "<u4")])   # gm_wall_quantity, 88 bytes
-WALL_QUANTITY_RUN = np.dtype([("station_from", "<u4"), ("stations", "<u4"), ("zone", "<u4"), ("sections", "<u4"),
-                              ("chainage_from", "<f8"), ("chainage_to", "<f8"), ("under", "<u8"), ("within", "<u8"),
-                              ("over", "<u8"), ("unsurveyed", "<u8"), ("points", "<u8"), ("under_volume_m3", "<f8"),
-                              ("over_volume_m3", "<f8"), ("excess_volume_m3", "<f8"), ("paid_volume_m3", "<f8"),
-                              ("peak_under", "<i8"), ("peak_over", "<i8"), ("peak_under_station", "<u4"),
-                              ("peak_under_sector", "<u4"), ("peak_over_station", "<u4"),
-                              ("peak_over_sector", "<u4")])   # gm_wall_quantity_run, 136 bytes
 WALL_QUANTITY_UNMEASURED = 0xFF
 WALL_QUANTITY_CLASSES = ("unmeasured", "empty", "unusable", "under", "over", "within")   # GM_WALL_QUANTITY_CLASS_* order
 WALL_QUANTITY_RUNS_ALL_ZONES = 1
-_QUANTITIES_INFO = ("station0", "n_stations", "n_sectors", "section_stations", "sections", "n_zones", "n_profiles", "radius_q",
-                    "unmeasured", "empty", "unusable", "under", "over", "within", "sections_under", "sections_over")
-
-
-def _wall_quantity_params(**kw):
-    p = _lib.WallQuantityParams()
-    _lib.load().gm_wall_quantity_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k) or k == "struct_size":
-            raise TypeError(f"unknown quantity parameter {k!r}")
-        setattr(p, k, v)
-    return p
 
 
 def _quantity_tables(lo_q, hi_q, n_sectors):
@@ -828,27 +842,6 @@ def wall_quantity_runs(prm, records, n_zones=1, run_sections=1, all_zones=False)
     return runs[:int(got.value)].copy()
 
 
-WALL_SECTION = np.dtype([("station_from", "<u4"), ("stations", "<u4"), ("status", "<u4"), ("usable", "<u4"), ("fitted", "<u4"),
-                         ("accepted", "<u4"), ("rejected", "<u4"), ("largest_gap", "<u4"), ("points", "<u8"),
-                         ("coef_q", "<i8", (9,)), ("rss", "<u8"), ("peak_out", "<i8"), ("peak_in", "<i8"),
-                         ("peak_out_sector", "<u4"), ("peak_in_sector", "<u4")])   # gm_wall_section, 144 bytes
-WALL_SECTION_SUMS = np.dtype([("N", "<i8", (45,)), ("r", "<i8", (9,)), ("fitted", "<u4"), ("largest_gap", "<u4"),
-                              ("points", "<u8")])   # gm_wall_section_sums, 448 bytes
-_SECTIONS_INFO = ("station0", "n_stations", "n_sectors", "section_stations", "sections", "harmonics", "passes", "reject_q",
-                  "max_gap_sectors", "sections_ok", "sections_failed", "sections_open_arc", "empty", "unusable", "usable",
-                  "accepted", "rejected")
-
-
-def _wall_section_params(**kw):
-    p = _lib.WallSectionParams()
-    _lib.load().gm_wall_section_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k) or k == "struct_size":
-            raise TypeError(f"unknown section parameter {k!r}")
-        setattr(p, k, v)
-    return p
-
-
 def wall_section_basis(n_sectors, harmonics=2):
     """gm_wall_section_basis (host only): the int32 (n_sectors, 1 + 2 harmonics) table gm_wall_map_sections uses."""
     L = _lib.load()
@@ -889,19 +882,6 @@ def wall_section_metrics(prm, section, harmonics=2):
     return d
 
 
-def _wall_cloud_params(**kw):
-    p = _lib.WallCloudParams()
-    _lib.load().gm_wall_cloud_default_params(C.byref(p))
-    for k, v in kw.items():
-        if k == "anchor":
-            p.anchor[:] = [float(x) for x in v]
-        elif not hasattr(p, k) or k in ("struct_size", "reserved"):
-            raise TypeError(f"unknown cloud parameter {k!r}")
-        else:
-            setattr(p, k, v)
-    return p
-
-
 def wall_cloud_directions(prm, **params):
     """gm_wall_cloud_directions (host only): the (NK, 2) float64 table of (cos, sin) that gm_wall_map_cloud uses on a map
     with the gm_wall_params `prm` under the cloud parameters given as keywords (block_sectors decides)."""
@@ -934,10 +914,6 @@ def _arc_call(name, st):
 
 def _d3():
     return np.empty(3, dtype=np.float64)
-
-
-def _dptr(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
 def _axis_add_info(i):
@@ -1055,8 +1031,8 @@ def wall_clothoid_point(prm, clothoid, chainage, angle, rho):
 
 
 def _wall_mesh_info(info):
-    d = {k: int(getattr(info, k)) for k in _MESH_INFO}
-    d["cloud"] = {k: int(getattr(info.cloud, k)) for k in _CLOUD_INFO}
+    d = _ints(info, _MESH_INFO)
+    d["cloud"] = _ints(info.cloud, _CLOUD_INFO)
     return d
 
 
@@ -1095,9 +1071,164 @@ def wall_mesh_write_ply(path, vertices, triangles):
         raise _lib.GmError(st, f"gm_wall_mesh_write_ply could not write {path!r}")
 
 
-class WallMap:
+class _FrameLoop:
+    """The frame loop of a wall map and of a wall alignment, written once: add, check, checked add, locate and align of
+    a slot's frame (*_frame enqueues, *_result fetches) or of a host cloud (*_points).  The ABI entry of a method is
+    `_prefix` + its name; a class states its structs and their converters to dicts:
+      _Plan, _plan_info, _plan_key                  what an add, a check and a checked add return at once -- the map's add
+                                                    info, the alignment's plan -- and its key in a *_points info dict
+      _AlignPlan, _align_plan_info, _align_plan_key the same of an align
+      _CheckInfo, _LocateInfo, _AlignInfo           the results (converters _check_info, _locate_info, _align_dict)
+      _EXTRA                                        per-point outputs beyond the map's: the alignment's owner element"""
+
+    def _abi(self, name, *args):
+        self._ctx._check(getattr(self._L, self._prefix + name)(self._h(), *args))
+
+    def _frame(self, name, slot, pose, *args):
+        self._abi(name, self._ctx._ctx, slot, _dptr(WallMap._pose(pose)), *args)
+
+    def add_frame(self, slot=0, pose=np.eye(4)[:3]):
+        """*_add_frame: enqueue the slot's last submitted frame under `pose` (sensor -> map).  Returns the add info dict
+        of a map, the plan dict of an alignment (computed on the host; the kernel may still be running)."""
+        i = self._Plan()
+        self._frame("add_frame", slot, pose, C.byref(i))
+        return self._plan_info(i)
+
+    def add_points(self, cloud, pose=np.eye(4)[:3], labels=None, outputs=True):
+        """*_add_points on a host cloud [n,3]: (add info or plan, residual [n] float32, cell [n] int32 -- relative to the
+        owner's map on an alignment, which adds element [n] int32); outputs False skips the per-point arrays (None each)."""
+        n, head = _stage_front(cloud, pose, labels)
+        i, out = self._Plan(), _PointOutputs(n, outputs, _RES_CELL + self._EXTRA)
+        self._abi("add_points", *head, C.byref(i), *out.ptrs())
+        return (self._plan_info(i), *out.tuple())
+
+    def sync(self):
+        self._abi("sync")
+
+    def check_frame(self, slot=0, pose=np.eye(4)[:3], **params):
+        """*_check_frame: enqueue the check of the slot's last submitted frame under `pose`, on an alignment every point
+        against its owner's map (keywords: reference, min_count, threshold, gate).  Returns the add info dict (its gate is
+        the check's) or the plan dict; check_result() fetches the result."""
+        p, i = _wall_check_params(**params), self._Plan()
+        self._frame("check_frame", slot, pose, C.byref(p), C.byref(i))
+        return self._plan_info(i)
+
+    def check_result(self, slot=0):
+        """*_get_check: (info dict, WALL_CHECK_POINT records ascending by index) of the last check on the slot; on an
+        alignment split_cell() splits their cell.  A count query first, then the sized call."""
+        info, got = self._CheckInfo(), C.c_uint32(0)
+        pts = _sized(lambda rp, cap, sized: self._abi("get_check", slot, C.byref(info), rp, cap, C.byref(got)), _lib.WallCheckPoint,
+                     got, lambda cap: cap)
+        return self._check_info(info), pts
+
+    def check_points(self, cloud, pose=np.eye(4)[:3], labels=None, outputs=True, **params):
+        """*_check_points on a host cloud [n,3]: (info dict with the add info under "add" or the plan under "plan",
+        records, dict(e float32, cell int32, delta int32, cls uint8 and on an alignment element int32) or None without
+        outputs).  The list buffer holds n rows: one call."""
+        n, head = _stage_front(cloud, pose, labels)
+        p = _wall_check_params(**params)
+        plan, info, got = self._Plan(), self._CheckInfo(), C.c_uint32(0)
+        pts = np.zeros(max(n, 1), dtype=WALL_CHECK_POINT)
+        out = _PointOutputs(n, outputs, _CHECK_OUT + self._EXTRA)
+        self._abi("check_points", *head, C.byref(p), C.byref(plan), C.byref(info), _rptr(pts, _lib.WallCheckPoint), n,
+                  C.byref(got), *out.ptrs())
+        d = self._check_info(info)
+        d[self._plan_key] = self._plan_info(plan)
+        return d, pts[:int(got.value)].copy(), out.dict()
+
+    def add_frame_checked(self, slot=0, pose=np.eye(4)[:3], **params):
+        """*_add_frame_checked: enqueue the add of the slot's last submitted frame under `pose`, less the points the slot's
+        last check_frame on this object selected (keywords: skip, min_delta).  Returns the add info or plan dict;
+        add_checked_result() fetches the counts."""
+        p, i = _wall_add_checked_params(**params), self._Plan()
+        self._frame("add_frame_checked", slot, pose, C.byref(p), C.byref(i))
+        return self._plan_info(i)
+
+    def add_checked_result(self, slot=0):
+        """*_get_add_checked: the info dict of the last checked add on the slot (waits for that call only)."""
+        info = _lib.WallAddCheckedInfo()
+        self._abi("get_add_checked", slot, C.byref(info))
+        return WallMap._add_checked_info(info)
+
+    def add_points_checked(self, cloud, pose, rows, labels=None, outputs=True, **params):
+        """*_add_points_checked on a host cloud [n,3] and WALL_CHECK_POINT rows (any order, duplicates allowed): (info
+        dict with the add info under "add" or the plan under "plan", then add_points' per-point arrays)."""
+        n, head = _stage_front(cloud, pose, labels)
+        p = _wall_add_checked_params(**params)
+        r = np.ascontiguousarray(np.asarray(rows, dtype=WALL_CHECK_POINT).reshape(-1))
+        plan, info, out = self._Plan(), _lib.WallAddCheckedInfo(), _PointOutputs(n, outputs, _RES_CELL + self._EXTRA)
+        self._abi("add_points_checked", *head, C.byref(p), _rptr(r, _lib.WallCheckPoint) if len(r) else None, len(r),
+                  C.byref(plan), C.byref(info), *out.ptrs())
+        d = WallMap._add_checked_info(info)
+        d[self._plan_key] = self._plan_info(plan)
+        return (d, *out.tuple())
+
+    def locate_frame(self, slot=0, pose=np.eye(4)[:3], **params):
+        """*_locate_frame: enqueue the correction of `pose` for the slot's last submitted frame (keywords: reference,
+        min_count, gate).  Returns at once; locate_result() fetches the result."""
+        p = _wall_locate_params(**params)
+        self._frame("locate_frame", slot, pose, C.byref(p))
+
+    def locate_result(self, slot=0):
+        """*_get_locate: the info dict (_locate_info) of the last locate on the slot -- status, passes, n_points,
+        anchor_station, pose (3, 4) float64 (NaN when status & GM_LOCATE_FAILED_MASK), lateral, tilt, pass (a list of three
+        dicts: o, a, u, v, gate, the five class counts, rms, step) and bytes (the raw gm_wall_locate_info)."""
+        info = self._LocateInfo()
+        self._abi("get_locate", slot, C.byref(info))
+        return self._locate_info(info)
+
+    def locate_points(self, cloud, pose=np.eye(4)[:3], labels=None, outputs=True, **params):
+        """*_locate_points on a host cloud [n,3]: (info dict, then add_points' per-point arrays of the last pass that ran,
+        element being the owner under the caller's pose); outputs False skips the per-point arrays."""
+        n, head = _stage_front(cloud, pose, labels)
+        p = _wall_locate_params(**params)
+        info, out = self._LocateInfo(), _PointOutputs(n, outputs, _RES_CELL + self._EXTRA)
+        self._abi("locate_points", *head, C.byref(p), C.byref(info), *out.ptrs())
+        return (self._locate_info(info), *out.tuple())
+
+    def align_frame(self, slot=0, pose=np.eye(4)[:3], **params):
+        """*_align_frame: enqueue the chainage and roll alignment of `pose` for the slot's last submitted frame (keywords:
+        gm_wall_align_params').  Returns the add info dict (its gate is the align's) or the align's plan dict at once;
+        align_result() fetches the result."""
+        p, i = _wall_align_params(**params), self._AlignPlan()
+        self._frame("align_frame", slot, pose, C.byref(p), C.byref(i))
+        return self._align_plan_info(i)
+
+    def align_result(self, slot=0):
+        """*_get_align: (info dict, WALL_ALIGN_SCORE table shaped (2A + 1, 2B + 1)) of the last align on the slot.  The
+        info holds status, the class counts, anchor_station, P, A, B as used, overlap, best_station, best_sector, the
+        fractions, shift_m, roll, bias_m, rms_best, rms_runner, distinction, pose (3, 4) float64 (NaN when
+        status & GM_ALIGN_FAILED_MASK) and bytes (the raw gm_wall_align_info).  A count query first, then the sized call."""
+        info, got = self._AlignInfo(), C.c_uint32(0)
+        t = _sized(lambda rp, cap, sized: self._abi("get_align", slot, C.byref(info) if sized else None, rp, cap,
+                                                    C.byref(got)), _lib.WallAlignScore, got, lambda cap: True)
+        d = self._align_dict(info)
+        return d, t.reshape(2 * d["max_station_shift"] + 1, 2 * d["max_sector_shift"] + 1)
+
+    def _align_points(self, cloud, pose, labels, outputs, params):
+        """*_align_points: (info dict with the align's plan, table, the _PointOutputs)."""
+        n, head = _stage_front(cloud, pose, labels)
+        p = _wall_align_params(**params)
+        plan, info, got = self._AlignPlan(), self._AlignInfo(), C.c_uint32(0)
+        na, nb = 2 * int(p.max_station_shift) + 1, 2 * int(p.max_sector_shift) + 1
+        t = np.zeros(na * nb, dtype=WALL_ALIGN_SCORE)
+        out = _PointOutputs(n, outputs, _ALIGN_OUT + self._EXTRA)
+        self._abi("align_points", *head, C.byref(p), C.byref(plan), C.byref(info), _rptr(t, _lib.WallAlignScore), len(t),
+                  C.byref(got), *out.ptrs())
+        d = self._align_dict(info)
+        d[self._align_plan_key] = self._align_plan_info(plan)
+        return d, t.reshape(na, nb), out
+
+
+class WallMap(_FrameLoop):
     """One gm_wall_map: a device-resident developed wall map against a design cylinder, accumulated over posed frames
-    (include/gm_hip.h states the rule).  Created by GeometricMapping.wall_map(); dies with its context."""
+    (include/gm_hip.h states the rule).  Created by GeometricMapping.wall_map(); dies with its context.  The frame loop
+    (add_*, check_*, add_*_checked, locate_*, align_*) is _FrameLoop's."""
+
+    _prefix, _EXTRA = "gm_wall_map_", ()
+    _Plan = _AlignPlan = _lib.WallAddInfo
+    _plan_key = _align_plan_key = "add"
+    _CheckInfo, _LocateInfo, _AlignInfo = _lib.WallCheckInfo, _lib.WallLocateInfo, _lib.WallAlignInfo
 
     def __init__(self, ctx, arc=None, clothoid=None, **params):
         self._ctx, self._L = ctx, ctx._L
@@ -1123,16 +1254,7 @@ class WallMap:
     @staticmethod
     def params(**kw):
         """gm_wall_params with the library's defaults, then the keywords."""
-        p = _lib.WallParams()
-        _lib.load().gm_wall_default_params(C.byref(p))
-        for k, v in kw.items():
-            if k in _WALL_VEC:
-                getattr(p, k)[:] = [float(x) for x in v]
-            elif not hasattr(p, k) or k == "struct_size":
-                raise TypeError(f"unknown wall map parameter {k!r}")
-            else:
-                setattr(p, k, v)
-        return p
+        return _wall_params(**kw)
 
     @property
     def arc(self):
@@ -1210,32 +1332,8 @@ class WallMap:
             d[k] = np.float32(getattr(i, k))
         return d
 
-    def add_frame(self, slot=0, pose=np.eye(4)[:3]):
-        """gm_wall_map_add_frame: enqueue the slot's last submitted frame under `pose` (sensor -> map).  Returns the add
-        info dict (computed on the host; the kernel may still be running)."""
-        m = self._pose(pose)
-        i = _lib.WallAddInfo()
-        self._ctx._check(self._L.gm_wall_map_add_frame(self._h(), self._ctx._ctx, slot, m.ctypes.data_as(C.POINTER(C.c_double)),
-                                                       C.byref(i)))
-        return self._add_info(i)
-
-    def add_points(self, cloud, pose=np.eye(4)[:3], labels=None, outputs=True):
-        """gm_wall_map_add_points on a host cloud [n,3]: (add info, residual [n] float32, cell [n] int32); outputs False
-        skips the per-point arrays (None, None)."""
-        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
-        m = self._pose(pose)
-        lab, lp = GeometricMapping._u8(labels)
-        i = _lib.WallAddInfo()
-        n = len(xyz)
-        res = np.empty(max(n, 1), dtype=np.float32) if outputs else None
-        cell = np.empty(max(n, 1), dtype=np.int32) if outputs else None
-        self._ctx._check(self._L.gm_wall_map_add_points(
-            self._h(), _f32(xyz), n, lp, m.ctypes.data_as(C.POINTER(C.c_double)), C.byref(i),
-            _f32(res) if outputs else None, cell.ctypes.data_as(C.POINTER(C.c_int32)) if outputs else None))
-        return self._add_info(i), (res[:n].copy() if outputs else None), (cell[:n].copy() if outputs else None)
-
-    def sync(self):
-        self._ctx._check(self._L.gm_wall_map_sync(self._h()))
+    _plan_info = _align_plan_info = _add_info
+    _align_dict = staticmethod(_align_info)
 
     def info(self):
         i = _lib.WallInfo()
@@ -1287,13 +1385,7 @@ class WallMap:
     def region_params(**kw):
         """gm_wall_region_params with the library's defaults, then the keywords (min_count, min_cells, connectivity,
         threshold)."""
-        p = _lib.WallRegionParams()
-        _lib.load().gm_wall_region_default_params(C.byref(p))
-        for k, v in kw.items():
-            if not hasattr(p, k) or k in ("struct_size", "reserved"):
-                raise TypeError(f"unknown region parameter {k!r}")
-            setattr(p, k, v)
-        return p
+        return _wall_region_params(**kw)
 
     def regions(self, station0=0, n=None, baseline=None, labels=False, **params):
         """gm_wall_map_regions: the connected deviation regions of stations [station0, station0 + n) against the design or,
@@ -1302,19 +1394,13 @@ class WallMap:
         s0, n = self._window(station0, n)
         p = self.region_params(**params)
         bh = baseline._h() if baseline is not None else None
-        info = _lib.WallRegionsInfo()
-        got = C.c_uint32(0)
+        info, got = _lib.WallRegionsInfo(), C.c_uint32(0)
         lab = np.empty(max(n * self.n_sectors, 1), dtype=np.int32) if labels else None
         lp = lab.ctypes.data_as(C.POINTER(C.c_int32)) if labels else None
         # a count query, then the list (the labels travel with the second call only)
-        self._ctx._check(self._L.gm_wall_map_regions(self._h(), bh, s0, n, C.byref(p), C.byref(info), None, 0, C.byref(got), None))
-        cap = int(got.value)
-        reg = np.zeros(max(cap, 1), dtype=REGION)
-        if cap or labels:
-            self._ctx._check(self._L.gm_wall_map_regions(self._h(), bh, s0, n, C.byref(p), C.byref(info),
-                                                         reg.ctypes.data_as(C.POINTER(_lib.WallRegion)), cap, C.byref(got), lp))
-        reg = reg[:int(got.value)].copy()
-        d = {k: int(getattr(info, k)) for k in _REGION_INFO}
+        reg = _sized(lambda rp, cap, sized: self._abi("regions", bh, s0, n, C.byref(p), C.byref(info), rp, cap, C.byref(got),
+                                                      lp if sized else None), _lib.WallRegion, got, lambda cap: cap or labels)
+        d = _ints(info, _REGION_INFO)
         d["cell_area"] = float(info.cell_area)
         metrics = [wall_region_metrics(self.prm, reg[i]) for i in range(len(reg))]
         return d, reg, metrics, (lab[:n * self.n_sectors].reshape(n, self.n_sectors).copy() if labels else None)
@@ -1331,15 +1417,10 @@ class WallMap:
         records).  A count query first, then the sized call."""
         s0, n = self._window(station0, n)
         p = self.cloud_params(**params)
-        info = _lib.WallCloudInfo()
-        got = C.c_uint64(0)
-        self._ctx._check(self._L.gm_wall_map_cloud(self._h(), s0, n, C.byref(p), C.byref(info), None, 0, C.byref(got)))
-        cap = int(got.value)
-        pts = np.zeros(max(cap, 1), dtype=WALL_CLOUD_POINT)
-        if cap:
-            self._ctx._check(self._L.gm_wall_map_cloud(self._h(), s0, n, C.byref(p), C.byref(info),
-                                                       pts.ctypes.data_as(C.POINTER(_lib.WallCloudPoint)), cap, C.byref(got)))
-        return {k: int(getattr(info, k)) for k in _CLOUD_INFO}, pts[:int(got.value)].copy()
+        info, got = _lib.WallCloudInfo(), C.c_uint64(0)
+        pts = _sized(lambda rp, cap, sized: self._abi("cloud", s0, n, C.byref(p), C.byref(info), rp, cap, C.byref(got)),
+                     _lib.WallCloudPoint, got, lambda cap: cap)
+        return _ints(info, _CLOUD_INFO), pts
 
     def mesh(self, station0=0, n=None, flags=0, max_step=0.0, **cloud_params):
         """gm_wall_map_mesh: stations [station0, station0 + n) as an indexed triangle mesh.  The vertices are cloud()'s rows
@@ -1383,19 +1464,15 @@ class WallMap:
             if len(sg) != n:
                 raise ValueError("station_gauge must hold one entry per window station")
             sgp = sg.ctypes.data_as(C.POINTER(C.c_uint8)) if n else None
-        info = _lib.WallClearanceInfo()
-        got = C.c_uint64(0)
-        self._ctx._check(self._L.gm_wall_map_clearance(self._h(), s0, n, gp, g.shape[0], sgp, C.byref(p), C.byref(info), None, 0,
-                                                       None, 0, C.byref(got)))
-        cap = int(got.value)
+        info, got = _lib.WallClearanceInfo(), C.c_uint64(0)
         st = np.zeros(max(n, 1), dtype=WALL_CLEARANCE_STATION)
-        cells = np.zeros(max(cap, 1), dtype=WALL_CLEARANCE_CELL)
-        if n:
-            self._ctx._check(self._L.gm_wall_map_clearance(
-                self._h(), s0, n, gp, g.shape[0], sgp, C.byref(p), C.byref(info),
-                st.ctypes.data_as(C.POINTER(_lib.WallClearanceStation)), n,
-                cells.ctypes.data_as(C.POINTER(_lib.WallClearanceCell)), cap, C.byref(got)))
-        return {k: int(getattr(info, k)) for k in _CLEARANCE_INFO}, st[:n].copy(), cells[:int(got.value)].copy()
+        stp = _rptr(st, _lib.WallClearanceStation)
+
+        def call(rp, cap, sized):   # the station records travel with the sized call, which a window with stations makes
+            self._abi("clearance", s0, n, gp, g.shape[0], sgp, C.byref(p), C.byref(info), stp if sized else None,
+                      n if sized else 0, rp, cap, C.byref(got))
+        cells = _sized(call, _lib.WallClearanceCell, got, lambda cap: n)
+        return _ints(info, _CLEARANCE_INFO), st[:n].copy(), cells
 
     @staticmethod
     def section_params(**kw):
@@ -1420,7 +1497,7 @@ class WallMap:
             self._h(), bh, s0, n, C.byref(p), C.byref(info), rec.ctypes.data_as(C.POINTER(_lib.WallSection)), cap, C.byref(got),
             sm.ctypes.data_as(C.POINTER(_lib.WallSectionSums)) if sums else None))
         ns = int(got.value)
-        return {k: int(getattr(info, k)) for k in _SECTIONS_INFO}, rec[:ns].copy(), (sm[:ns].copy() if sums else None)
+        return _ints(info, _SECTIONS_INFO), rec[:ns].copy(), (sm[:ns].copy() if sums else None)
 
     def section_basis(self, harmonics=2):
         """gm_wall_section_basis for this map's n_sectors."""
@@ -1472,7 +1549,7 @@ class WallMap:
             rows.ctypes.data_as(i32) if profile_rows else None))
         nr = int(got.value)
         out_rows = rows[:NS * self.n_sectors].reshape(NS, self.n_sectors).copy() if profile_rows else None
-        return {k: int(getattr(info, k)) for k in _QUANTITIES_INFO}, rec[:nr].reshape(NS, nz).copy(), out_rows
+        return _ints(info, _QUANTITIES_INFO), rec[:nr].reshape(NS, nz).copy(), out_rows
 
     def quantity_metrics(self, record):
         """gm_wall_quantity_metrics of one WALL_QUANTITY record under this map's parameters."""
@@ -1487,109 +1564,18 @@ class WallMap:
         """gm_wall_check_params with the library's defaults, then the keywords (reference, min_count, threshold, gate)."""
         return _wall_check_params(**kw)
 
-    def check_frame(self, slot=0, pose=np.eye(4)[:3], **params):
-        """gm_wall_map_check_frame: enqueue the check of the slot's last submitted frame under `pose` against this map.
-        Returns the add info dict (its gate is the check's); check_result() fetches the result."""
-        m = self._pose(pose)
-        p = self.check_params(**params)
-        i = _lib.WallAddInfo()
-        self._ctx._check(self._L.gm_wall_map_check_frame(self._h(), self._ctx._ctx, slot, m.ctypes.data_as(C.POINTER(C.c_double)),
-                                                         C.byref(p), C.byref(i)))
-        return self._add_info(i)
-
     @staticmethod
     def _check_info(i):
-        return {k: int(getattr(i, k)) for k in _CHECK_INFO}
-
-    def check_result(self, slot=0):
-        """gm_wall_map_get_check: (info dict, WALL_CHECK_POINT records ascending by index) of the last check on the slot.
-        A count query first, then the sized call."""
-        info = _lib.WallCheckInfo()
-        got = C.c_uint32(0)
-        self._ctx._check(self._L.gm_wall_map_get_check(self._h(), slot, C.byref(info), None, 0, C.byref(got)))
-        cap = int(got.value)
-        pts = np.zeros(max(cap, 1), dtype=WALL_CHECK_POINT)
-        if cap:
-            self._ctx._check(self._L.gm_wall_map_get_check(self._h(), slot, C.byref(info),
-                                                           pts.ctypes.data_as(C.POINTER(_lib.WallCheckPoint)), cap, C.byref(got)))
-        return self._check_info(info), pts[:int(got.value)].copy()
-
-    def check_points(self, cloud, pose=np.eye(4)[:3], labels=None, outputs=True, **params):
-        """gm_wall_map_check_points on a host cloud [n,3]: (info dict, records, dict(e float32, cell int32, delta int32,
-        cls uint8) or None without outputs).  The list buffer holds n rows: one call."""
-        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
-        m = self._pose(pose)
-        lab, lp = GeometricMapping._u8(labels)
-        p = self.check_params(**params)
-        n = len(xyz)
-        add, info, got = _lib.WallAddInfo(), _lib.WallCheckInfo(), C.c_uint32(0)
-        pts = np.zeros(max(n, 1), dtype=WALL_CHECK_POINT)
-        out = None
-        if outputs:
-            out = dict(e=np.empty(max(n, 1), np.float32), cell=np.empty(max(n, 1), np.int32), delta=np.empty(max(n, 1), np.int32),
-                       cls=np.empty(max(n, 1), np.uint8))
-        i32p = C.POINTER(C.c_int32)
-        self._ctx._check(self._L.gm_wall_map_check_points(
-            self._h(), _f32(xyz), n, lp, m.ctypes.data_as(C.POINTER(C.c_double)), C.byref(p), C.byref(add), C.byref(info),
-            pts.ctypes.data_as(C.POINTER(_lib.WallCheckPoint)), n, C.byref(got),
-            _f32(out["e"]) if outputs else None, out["cell"].ctypes.data_as(i32p) if outputs else None,
-            out["delta"].ctypes.data_as(i32p) if outputs else None,
-            out["cls"].ctypes.data_as(C.POINTER(C.c_uint8)) if outputs else None))
-        d = self._check_info(info)
-        d["add"] = self._add_info(add)
-        return d, pts[:int(got.value)].copy(), ({k: v[:n].copy() for k, v in out.items()} if outputs else None)
+        return _ints(i, _CHECK_INFO)
 
     @staticmethod
     def add_checked_params(**kw):
         """gm_wall_add_checked_params with the library's defaults, then the keywords (skip, min_delta)."""
-        p = _lib.WallAddCheckedParams()
-        _lib.load().gm_wall_add_checked_default_params(C.byref(p))
-        for k, v in kw.items():
-            if k not in ("skip", "min_delta"):
-                raise TypeError(f"unknown checked-add parameter {k!r}")
-            setattr(p, k, v)
-        return p
+        return _wall_add_checked_params(**kw)
 
     @staticmethod
     def _add_checked_info(i):
-        return {k: int(getattr(i, k)) for k in _ADD_CHECKED_INFO}
-
-    def add_frame_checked(self, slot=0, pose=np.eye(4)[:3], **params):
-        """gm_wall_map_add_frame_checked: enqueue the add of the slot's last submitted frame under `pose`, less the points
-        the slot's last check_frame on this map selected.  Returns the add info dict; add_checked_result() fetches the counts."""
-        m = self._pose(pose)
-        p = self.add_checked_params(**params)
-        i = _lib.WallAddInfo()
-        self._ctx._check(self._L.gm_wall_map_add_frame_checked(self._h(), self._ctx._ctx, slot, m.ctypes.data_as(C.POINTER(C.c_double)),
-                                                               C.byref(p), C.byref(i)))
-        return self._add_info(i)
-
-    def add_checked_result(self, slot=0):
-        """gm_wall_map_get_add_checked: the info dict of the last checked add on the slot (waits for that call only)."""
-        info = _lib.WallAddCheckedInfo()
-        self._ctx._check(self._L.gm_wall_map_get_add_checked(self._h(), slot, C.byref(info)))
-        return self._add_checked_info(info)
-
-    def add_points_checked(self, cloud, pose, rows, labels=None, outputs=True, **params):
-        """gm_wall_map_add_points_checked on a host cloud [n,3] and WALL_CHECK_POINT rows (any order, duplicates allowed):
-        (info dict with the add info under "add", residual [n] float32, cell [n] int32); outputs False skips the per-point
-        arrays (None, None)."""
-        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
-        m = self._pose(pose)
-        lab, lp = GeometricMapping._u8(labels)
-        p = self.add_checked_params(**params)
-        r = np.ascontiguousarray(np.asarray(rows, dtype=WALL_CHECK_POINT).reshape(-1))
-        add, info = _lib.WallAddInfo(), _lib.WallAddCheckedInfo()
-        n = len(xyz)
-        res = np.empty(max(n, 1), dtype=np.float32) if outputs else None
-        cell = np.empty(max(n, 1), dtype=np.int32) if outputs else None
-        self._ctx._check(self._L.gm_wall_map_add_points_checked(
-            self._h(), _f32(xyz), n, lp, m.ctypes.data_as(C.POINTER(C.c_double)), C.byref(p),
-            r.ctypes.data_as(C.POINTER(_lib.WallCheckPoint)) if len(r) else None, len(r), C.byref(add), C.byref(info),
-            _f32(res) if outputs else None, cell.ctypes.data_as(C.POINTER(C.c_int32)) if outputs else None))
-        d = self._add_checked_info(info)
-        d["add"] = self._add_info(add)
-        return d, (res[:n].copy() if outputs else None), (cell[:n].copy() if outputs else None)
+        return _ints(i, _ADD_CHECKED_INFO)
 
     @staticmethod
     def locate_params(**kw):
@@ -1611,89 +1597,18 @@ class WallMap:
             d["pass"].append(q)
         return d
 
-    def locate_frame(self, slot=0, pose=np.eye(4)[:3], **params):
-        """gm_wall_map_locate_frame: enqueue the correction of `pose` for the slot's last submitted frame against this map
-        (keywords: reference, min_count, gate).  Returns at once; locate_result() fetches the result."""
-        m = self._pose(pose)
-        p = self.locate_params(**params)
-        self._ctx._check(self._L.gm_wall_map_locate_frame(self._h(), self._ctx._ctx, slot, m.ctypes.data_as(C.POINTER(C.c_double)),
-                                                          C.byref(p)))
-
-    def locate_result(self, slot=0):
-        """gm_wall_map_get_locate: the info dict of the last locate on the slot -- status, passes, n_points,
-        anchor_station, pose (3, 4) float64 (NaN when status & GM_LOCATE_FAILED_MASK), lateral, tilt, pass (a list of three
-        dicts: o, a, u, v, gate, the five class counts, rms, step) and bytes (the raw gm_wall_locate_info)."""
-        info = _lib.WallLocateInfo()
-        self._ctx._check(self._L.gm_wall_map_get_locate(self._h(), slot, C.byref(info)))
-        return self._locate_info(info)
-
-    def locate_points(self, cloud, pose=np.eye(4)[:3], labels=None, outputs=True, **params):
-        """gm_wall_map_locate_points on a host cloud [n,3]: (info dict, residual [n] float32, cell [n] int32) of the last
-        pass that ran; outputs False skips the per-point arrays (None, None)."""
-        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
-        m = self._pose(pose)
-        lab, lp = GeometricMapping._u8(labels)
-        p = self.locate_params(**params)
-        n = len(xyz)
-        info = _lib.WallLocateInfo()
-        res = np.empty(max(n, 1), dtype=np.float32) if outputs else None
-        cell = np.empty(max(n, 1), dtype=np.int32) if outputs else None
-        self._ctx._check(self._L.gm_wall_map_locate_points(
-            self._h(), _f32(xyz), n, lp, m.ctypes.data_as(C.POINTER(C.c_double)), C.byref(p), C.byref(info),
-            _f32(res) if outputs else None, cell.ctypes.data_as(C.POINTER(C.c_int32)) if outputs else None))
-        return self._locate_info(info), (res[:n].copy() if outputs else None), (cell[:n].copy() if outputs else None)
-
     @staticmethod
     def align_params(**kw):
         """gm_wall_align_params with the library's defaults, then the keywords (half_patch_stations, max_station_shift,
         max_sector_shift, min_count, min_frame_count, min_overlap, gate, clip, min_distinction)."""
         return _wall_align_params(**kw)
 
-    def align_frame(self, slot=0, pose=np.eye(4)[:3], **params):
-        """gm_wall_map_align_frame: enqueue the chainage and roll alignment of `pose` for the slot's last submitted frame
-        against this map.  Returns the add info dict (its gate is the align's) at once; align_result() fetches the result."""
-        m = self._pose(pose)
-        p = self.align_params(**params)
-        i = _lib.WallAddInfo()
-        self._ctx._check(self._L.gm_wall_map_align_frame(self._h(), self._ctx._ctx, slot, m.ctypes.data_as(C.POINTER(C.c_double)),
-                                                         C.byref(p), C.byref(i)))
-        return self._add_info(i)
-
-    def align_result(self, slot=0):
-        """gm_wall_map_get_align: (info dict, WALL_ALIGN_SCORE table shaped (2A + 1, 2B + 1)) of the last align on the slot.
-        The info holds status, the class counts, anchor_station, P, A, B as used, overlap, best_station, best_sector, the
-        fractions, shift_m, roll, bias_m, rms_best, rms_runner, distinction, pose (3, 4) float64 (NaN when
-        status & GM_ALIGN_FAILED_MASK) and bytes (the raw gm_wall_align_info).  A count query first, then the sized call."""
-        info, got = _lib.WallAlignInfo(), C.c_uint32(0)
-        self._ctx._check(self._L.gm_wall_map_get_align(self._h(), slot, None, None, 0, C.byref(got)))
-        cap = int(got.value)
-        t = np.zeros(max(cap, 1), dtype=WALL_ALIGN_SCORE)
-        self._ctx._check(self._L.gm_wall_map_get_align(self._h(), slot, C.byref(info), t.ctypes.data_as(C.POINTER(_lib.WallAlignScore)),
-                                                       cap, C.byref(got)))
-        d = _align_info(info)
-        return d, t[:cap].reshape(2 * d["max_station_shift"] + 1, 2 * d["max_sector_shift"] + 1).copy()
-
     def align_points(self, cloud, pose=np.eye(4)[:3], labels=None, outputs=True, **params):
         """gm_wall_map_align_points on a host cloud [n,3]: (info dict with the add info under "add", table, residual [n]
         float32, cell [n] int32: jr * n_sectors + k of a binned point, else -1); outputs False skips the per-point arrays
         (None, None)."""
-        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
-        m = self._pose(pose)
-        lab, lp = GeometricMapping._u8(labels)
-        p = self.align_params(**params)
-        n = len(xyz)
-        add, info, got = _lib.WallAddInfo(), _lib.WallAlignInfo(), C.c_uint32(0)
-        na, nb = 2 * int(p.max_station_shift) + 1, 2 * int(p.max_sector_shift) + 1
-        t = np.zeros(na * nb, dtype=WALL_ALIGN_SCORE)
-        res = np.empty(max(n, 1), dtype=np.float32) if outputs else None
-        cell = np.empty(max(n, 1), dtype=np.int32) if outputs else None
-        self._ctx._check(self._L.gm_wall_map_align_points(
-            self._h(), _f32(xyz), n, lp, m.ctypes.data_as(C.POINTER(C.c_double)), C.byref(p), C.byref(add), C.byref(info),
-            t.ctypes.data_as(C.POINTER(_lib.WallAlignScore)), len(t), C.byref(got),
-            _f32(res) if outputs else None, cell.ctypes.data_as(C.POINTER(C.c_int32)) if outputs else None))
-        d = _align_info(info)
-        d["add"] = self._add_info(add)
-        return d, t.reshape(na, nb), (res[:n].copy() if outputs else None), (cell[:n].copy() if outputs else None)
+        d, t, out = self._align_points(cloud, pose, labels, outputs, params)
+        return (d, t, *out.tuple())
 
     @staticmethod
     def object_params(**kw):
@@ -1706,17 +1621,12 @@ class WallMap:
         Each of the two runs the whole device pipeline (the library keeps no result between calls), so this binding
         launches every kernel twice per request; a caller that minds sizes the record buffer itself and calls the ABI
         once, as tools/wall_objects_timing.py does."""
-        info = _lib.WallObjectsInfo()
-        got = C.c_uint32(0)
-        self._ctx._check(call(C.byref(info), None, 0, C.byref(got), None))
-        cap = int(got.value)
-        obj = np.zeros(max(cap, 1), dtype=WALL_OBJECT)
+        info, got = _lib.WallObjectsInfo(), C.c_uint32(0)
         of_row = np.full(max(n_rows, 1), -1, dtype=np.int32) if rows else None
-        if cap or rows:
-            self._ctx._check(call(C.byref(info), obj.ctypes.data_as(C.POINTER(_lib.WallObject)), cap, C.byref(got),
-                                  of_row.ctypes.data_as(C.POINTER(C.c_int32)) if rows else None))
-        obj = obj[:int(got.value)].copy()
-        d = {k: int(getattr(info, k)) for k in _OBJECTS_INFO}
+        rowp = of_row.ctypes.data_as(C.POINTER(C.c_int32)) if rows else None
+        obj = _sized(lambda rp, cap, sized: self._ctx._check(call(C.byref(info), rp, cap, C.byref(got), rowp if sized else None)),
+                     _lib.WallObject, got, lambda cap: cap or rows)
+        d = _ints(info, _OBJECTS_INFO)
         metrics = [object_metrics(self.prm, obj[i], **p) for i in range(len(obj))]
         return d, obj, metrics, (of_row[:n_rows].copy() if rows else None)
 
@@ -1942,10 +1852,17 @@ class WallAlignmentRule:
         return _alignment_align_info(info)
 
 
-class WallAlignment(WallAlignmentRule):
+class WallAlignment(WallAlignmentRule, _FrameLoop):
     """One gm_wall_alignment: the element maps of an alignment of straights, arcs and clothoids, chained end to end, and
     the add of a frame to the elements it reaches in one launch.  Created by GeometricMapping.wall_alignment(); dies with
-    its context."""
+    its context.  The frame loop is _FrameLoop's: where a map returns its add info, the alignment returns its plan, and
+    every per-point output gains element [n] int32, the point's owner."""
+
+    _prefix, _EXTRA = "gm_wall_alignment_", _ELEMENT
+    _Plan, _plan_info, _plan_key = _lib.WallAlignmentAddInfo, staticmethod(_alignment_add_info), "plan"
+    _AlignPlan, _align_plan_info, _align_plan_key = _lib.WallAlignmentAlignPlan, staticmethod(_alignment_align_plan), "align_plan"
+    _CheckInfo, _LocateInfo, _AlignInfo = _lib.WallAlignmentCheckInfo, _lib.WallAlignmentLocateInfo, _lib.WallAlignmentAlignInfo
+    _align_dict = staticmethod(_alignment_align_info)
 
     def __init__(self, ctx, elements, **params):
         super().__init__(elements, **params)
@@ -1984,35 +1901,6 @@ class WallAlignment(WallAlignmentRule):
             self._maps[i] = WallMap._borrowed(self._ctx, h, self.element_params(i)[0])
         return self._maps[i]
 
-    def add_frame(self, slot=0, pose=np.eye(4)[:3]):
-        """gm_wall_alignment_add_frame: enqueue the slot's last submitted frame under `pose`.  Returns the plan dict."""
-        m = WallMap._pose(pose)
-        i = _lib.WallAlignmentAddInfo()
-        self._ctx._check(self._L.gm_wall_alignment_add_frame(self._h(), self._ctx._ctx, slot, _dptr(m), C.byref(i)))
-        return _alignment_add_info(i)
-
-    def add_points(self, cloud, pose=np.eye(4)[:3], labels=None, outputs=True):
-        """gm_wall_alignment_add_points on a host cloud [n,3]: (plan, residual [n] float32, cell [n] int32 relative to the
-        owner's map, element [n] int32); outputs False skips the per-point arrays (None each)."""
-        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
-        m = WallMap._pose(pose)
-        lab, lp = GeometricMapping._u8(labels)
-        i = _lib.WallAlignmentAddInfo()
-        n = len(xyz)
-        res = np.empty(max(n, 1), dtype=np.float32) if outputs else None
-        cell = np.empty(max(n, 1), dtype=np.int32) if outputs else None
-        el = np.empty(max(n, 1), dtype=np.int32) if outputs else None
-        i32 = C.POINTER(C.c_int32)
-        self._ctx._check(self._L.gm_wall_alignment_add_points(
-            self._h(), _f32(xyz), n, lp, _dptr(m), C.byref(i), _f32(res) if outputs else None,
-            cell.ctypes.data_as(i32) if outputs else None, el.ctypes.data_as(i32) if outputs else None))
-        if not outputs:
-            return _alignment_add_info(i), None, None, None
-        return _alignment_add_info(i), res[:n].copy(), cell[:n].copy(), el[:n].copy()
-
-    def sync(self):
-        self._ctx._check(self._L.gm_wall_alignment_sync(self._h()))
-
     def info(self):
         """gm_wall_alignment_info: n_elements, n_stations, chainage_min, chainage_max and the summed frames and classes."""
         i = _lib.WallAlignmentTotals()
@@ -2043,92 +1931,18 @@ class WallAlignment(WallAlignmentRule):
             q["joint_a"] = np.array([list(x) for x in r.joint_a], dtype=np.float32)[:max(ns - 1, 0)]
         return d
 
-    def locate_frame(self, slot=0, pose=np.eye(4)[:3], **params):
-        """gm_wall_alignment_locate_frame: enqueue the correction of `pose` for the slot's last submitted frame against the
-        alignment (keywords: reference, min_count, gate).  Returns at once; locate_result() fetches the result."""
-        m = WallMap._pose(pose)
-        p = WallMap.locate_params(**params)
-        self._ctx._check(self._L.gm_wall_alignment_locate_frame(self._h(), self._ctx._ctx, slot, _dptr(m), C.byref(p)))
-
-    def locate_result(self, slot=0):
-        """gm_wall_alignment_get_locate: the info dict (_locate_info) of the last locate on the slot."""
-        info = _lib.WallAlignmentLocateInfo()
-        self._ctx._check(self._L.gm_wall_alignment_get_locate(self._h(), slot, C.byref(info)))
-        return self._locate_info(info)
-
-    def locate_points(self, cloud, pose=np.eye(4)[:3], labels=None, outputs=True, **params):
-        """gm_wall_alignment_locate_points on a host cloud [n,3]: (info dict, residual [n] float32, cell [n] int32 relative
-        to the owner's map) of the last pass that ran and element [n] int32, the owner under the caller's pose; outputs False
-        skips the per-point arrays."""
-        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
-        m = WallMap._pose(pose)
-        lab, lp = GeometricMapping._u8(labels)
-        p = WallMap.locate_params(**params)
-        n = len(xyz)
-        info = _lib.WallAlignmentLocateInfo()
-        res = np.empty(max(n, 1), dtype=np.float32) if outputs else None
-        cell = np.empty(max(n, 1), dtype=np.int32) if outputs else None
-        el = np.empty(max(n, 1), dtype=np.int32) if outputs else None
-        i32 = C.POINTER(C.c_int32)
-        self._ctx._check(self._L.gm_wall_alignment_locate_points(
-            self._h(), _f32(xyz), n, lp, _dptr(m), C.byref(p), C.byref(info), _f32(res) if outputs else None,
-            cell.ctypes.data_as(i32) if outputs else None, el.ctypes.data_as(i32) if outputs else None))
-        if not outputs:
-            return self._locate_info(info), None, None, None
-        return self._locate_info(info), res[:n].copy(), cell[:n].copy(), el[:n].copy()
-
     def align_plan(self, pose, bound=None, **params):
         return super().align_plan(pose, float(self._ctx.cfg.boxFilterBound) if bound is None else bound, **params)
 
     def align_select(self, pose, table, bound=None, **params):
         return super().align_select(pose, float(self._ctx.cfg.boxFilterBound) if bound is None else bound, table, **params)
 
-    def align_frame(self, slot=0, pose=np.eye(4)[:3], **params):
-        """gm_wall_alignment_align_frame: enqueue the chainage and roll alignment of `pose` for the slot's last submitted
-        frame against the alignment (keywords: gm_wall_align_params').  Returns the plan dict at once; align_result()
-        fetches the result."""
-        m = WallMap._pose(pose)
-        p = _wall_align_params(**params)
-        i = _lib.WallAlignmentAlignPlan()
-        self._ctx._check(self._L.gm_wall_alignment_align_frame(self._h(), self._ctx._ctx, slot, _dptr(m), C.byref(p), C.byref(i)))
-        return _alignment_align_plan(i)
-
-    def align_result(self, slot=0):
-        """gm_wall_alignment_get_align: (info dict, WALL_ALIGN_SCORE table shaped (2A + 1, 2B + 1)) of the last align on
-        the slot.  A count query first, then the sized call."""
-        info, got = _lib.WallAlignmentAlignInfo(), C.c_uint32(0)
-        self._ctx._check(self._L.gm_wall_alignment_get_align(self._h(), slot, None, None, 0, C.byref(got)))
-        cap = int(got.value)
-        t = np.zeros(max(cap, 1), dtype=WALL_ALIGN_SCORE)
-        self._ctx._check(self._L.gm_wall_alignment_get_align(self._h(), slot, C.byref(info),
-                                                             t.ctypes.data_as(C.POINTER(_lib.WallAlignScore)), cap, C.byref(got)))
-        d = _alignment_align_info(info)
-        return d, t[:cap].reshape(2 * d["max_station_shift"] + 1, 2 * d["max_sector_shift"] + 1).copy()
-
     def align_points(self, cloud, pose=np.eye(4)[:3], labels=None, outputs=True, **params):
         """gm_wall_alignment_align_points on a host cloud [n,3]: (info dict with the align's plan under "align_plan", table,
         dict(e float32, cell int32: jr * n_sectors + k of a binned point, else -1, element int32) or None without
         outputs)."""
-        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
-        m = WallMap._pose(pose)
-        lab, lp = GeometricMapping._u8(labels)
-        p = _wall_align_params(**params)
-        n = len(xyz)
-        plan, info, got = _lib.WallAlignmentAlignPlan(), _lib.WallAlignmentAlignInfo(), C.c_uint32(0)
-        na, nb = 2 * int(p.max_station_shift) + 1, 2 * int(p.max_sector_shift) + 1
-        t = np.zeros(na * nb, dtype=WALL_ALIGN_SCORE)
-        out = None
-        if outputs:
-            out = dict(e=np.empty(max(n, 1), np.float32), cell=np.empty(max(n, 1), np.int32), element=np.empty(max(n, 1), np.int32))
-        i32p = C.POINTER(C.c_int32)
-        self._ctx._check(self._L.gm_wall_alignment_align_points(
-            self._h(), _f32(xyz), n, lp, _dptr(m), C.byref(p), C.byref(plan), C.byref(info),
-            t.ctypes.data_as(C.POINTER(_lib.WallAlignScore)), len(t), C.byref(got),
-            _f32(out["e"]) if outputs else None, out["cell"].ctypes.data_as(i32p) if outputs else None,
-            out["element"].ctypes.data_as(i32p) if outputs else None))
-        d = _alignment_align_info(info)
-        d["align_plan"] = _alignment_align_plan(plan)
-        return d, t.reshape(na, nb), ({k: v[:n].copy() for k, v in out.items()} if outputs else None)
+        d, t, out = self._align_points(cloud, pose, labels, outputs, params)
+        return d, t, out.dict()
 
     @staticmethod
     def split_cell(rows):
@@ -2145,98 +1959,6 @@ class WallAlignment(WallAlignmentRule):
         ns = int(i.n_sides)
         d.update(n_sides=ns, side_class=np.array([list(r) for r in i.side_class], dtype=np.uint32)[:ns])
         return d
-
-    def check_frame(self, slot=0, pose=np.eye(4)[:3], **params):
-        """gm_wall_alignment_check_frame: enqueue the check of the slot's last submitted frame under `pose`, every point
-        against its owner's map (keywords: reference, min_count, threshold, gate).  Returns the plan dict; check_result()
-        fetches the result."""
-        m = WallMap._pose(pose)
-        p = WallMap.check_params(**params)
-        i = _lib.WallAlignmentAddInfo()
-        self._ctx._check(self._L.gm_wall_alignment_check_frame(self._h(), self._ctx._ctx, slot, _dptr(m), C.byref(p), C.byref(i)))
-        return _alignment_add_info(i)
-
-    def check_result(self, slot=0):
-        """gm_wall_alignment_get_check: (info dict, WALL_CHECK_POINT records ascending by index) of the last check on the
-        slot; split_cell() splits their cell.  A count query first, then the sized call."""
-        info = _lib.WallAlignmentCheckInfo()
-        got = C.c_uint32(0)
-        self._ctx._check(self._L.gm_wall_alignment_get_check(self._h(), slot, C.byref(info), None, 0, C.byref(got)))
-        cap = int(got.value)
-        pts = np.zeros(max(cap, 1), dtype=WALL_CHECK_POINT)
-        if cap:
-            self._ctx._check(self._L.gm_wall_alignment_get_check(self._h(), slot, C.byref(info),
-                                                                 pts.ctypes.data_as(C.POINTER(_lib.WallCheckPoint)), cap, C.byref(got)))
-        return self._check_info(info), pts[:int(got.value)].copy()
-
-    def check_points(self, cloud, pose=np.eye(4)[:3], labels=None, outputs=True, **params):
-        """gm_wall_alignment_check_points on a host cloud [n,3]: (info dict with the plan under "plan", records,
-        dict(e float32, cell int32 relative to the owner's map, delta int32, cls uint8, element int32) or None without
-        outputs)."""
-        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
-        m = WallMap._pose(pose)
-        lab, lp = GeometricMapping._u8(labels)
-        p = WallMap.check_params(**params)
-        n = len(xyz)
-        plan, info, got = _lib.WallAlignmentAddInfo(), _lib.WallAlignmentCheckInfo(), C.c_uint32(0)
-        pts = np.zeros(max(n, 1), dtype=WALL_CHECK_POINT)
-        out = None
-        if outputs:
-            out = dict(e=np.empty(max(n, 1), np.float32), cell=np.empty(max(n, 1), np.int32), delta=np.empty(max(n, 1), np.int32),
-                       cls=np.empty(max(n, 1), np.uint8), element=np.empty(max(n, 1), np.int32))
-        i32p = C.POINTER(C.c_int32)
-        self._ctx._check(self._L.gm_wall_alignment_check_points(
-            self._h(), _f32(xyz), n, lp, _dptr(m), C.byref(p), C.byref(plan), C.byref(info),
-            pts.ctypes.data_as(C.POINTER(_lib.WallCheckPoint)), n, C.byref(got),
-            _f32(out["e"]) if outputs else None, out["cell"].ctypes.data_as(i32p) if outputs else None,
-            out["delta"].ctypes.data_as(i32p) if outputs else None,
-            out["cls"].ctypes.data_as(C.POINTER(C.c_uint8)) if outputs else None,
-            out["element"].ctypes.data_as(i32p) if outputs else None))
-        d = self._check_info(info)
-        d["plan"] = _alignment_add_info(plan)
-        return d, pts[:int(got.value)].copy(), ({k: v[:n].copy() for k, v in out.items()} if outputs else None)
-
-    def add_frame_checked(self, slot=0, pose=np.eye(4)[:3], **params):
-        """gm_wall_alignment_add_frame_checked: enqueue the add of the slot's last submitted frame under `pose`, less the
-        points the slot's last check_frame through this alignment selected (keywords: skip, min_delta).  Returns the plan
-        dict; add_checked_result() fetches the counts."""
-        m = WallMap._pose(pose)
-        p = WallMap.add_checked_params(**params)
-        i = _lib.WallAlignmentAddInfo()
-        self._ctx._check(self._L.gm_wall_alignment_add_frame_checked(self._h(), self._ctx._ctx, slot, _dptr(m), C.byref(p), C.byref(i)))
-        return _alignment_add_info(i)
-
-    def add_checked_result(self, slot=0):
-        """gm_wall_alignment_get_add_checked: the info dict of the last checked add on the slot (waits for that call only)."""
-        info = _lib.WallAddCheckedInfo()
-        self._ctx._check(self._L.gm_wall_alignment_get_add_checked(self._h(), slot, C.byref(info)))
-        return WallMap._add_checked_info(info)
-
-    def add_points_checked(self, cloud, pose, rows, labels=None, outputs=True, **params):
-        """gm_wall_alignment_add_points_checked on a host cloud [n,3] and WALL_CHECK_POINT rows (any order, duplicates
-        allowed): (info dict with the plan under "plan", residual [n] float32, cell [n] int32 relative to the owner's map,
-        element [n] int32); outputs False skips the per-point arrays (None each)."""
-        xyz = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
-        m = WallMap._pose(pose)
-        lab, lp = GeometricMapping._u8(labels)
-        p = WallMap.add_checked_params(**params)
-        r = np.ascontiguousarray(np.asarray(rows, dtype=WALL_CHECK_POINT).reshape(-1))
-        plan, info = _lib.WallAlignmentAddInfo(), _lib.WallAddCheckedInfo()
-        n = len(xyz)
-        res = np.empty(max(n, 1), dtype=np.float32) if outputs else None
-        cell = np.empty(max(n, 1), dtype=np.int32) if outputs else None
-        el = np.empty(max(n, 1), dtype=np.int32) if outputs else None
-        i32 = C.POINTER(C.c_int32)
-        self._ctx._check(self._L.gm_wall_alignment_add_points_checked(
-            self._h(), _f32(xyz), n, lp, _dptr(m), C.byref(p),
-            r.ctypes.data_as(C.POINTER(_lib.WallCheckPoint)) if len(r) else None, len(r), C.byref(plan), C.byref(info),
-            _f32(res) if outputs else None, cell.ctypes.data_as(i32) if outputs else None,
-            el.ctypes.data_as(i32) if outputs else None))
-        d = WallMap._add_checked_info(info)
-        d["plan"] = _alignment_add_info(plan)
-        if not outputs:
-            return d, None, None, None
-        return d, res[:n].copy(), cell[:n].copy(), el[:n].copy()
 
 
 def decode_compressed_map(buf):
