@@ -603,9 +603,12 @@ __host__ __device__ inline void jacobi_eig3(const double a6[6], double w[3], dou
 // returned eigenvectors (arbitrary mathematically, visible on /eigenBasisOutput as the arrow directions) depend on the
 // number of QR sweeps, i.e. on the precision the iteration runs in: T = float reproduces the sign pattern of the
 // reference's MatrixXf solve.  a = {xx,xy,xz,yy,yz,zz}; w ascending, V column-major.
+// One rounding can change the number of sweeps, so every product is rounded (no contraction to FMAs, whatever the build's
+// -ffp-contract): the device pass, the x86-64 host pass and the oracle's restatement then run one and the same sequence.
 template <class T>
 __host__ __device__ inline void eigen_tridiag_qr3(const T a6[6], T w[3], T V[9])
 {
+#pragma clang fp contract(off)
     typedef T double_;   // (the body below is written once for both scalar types)
     double_ scale = 0.0;
     for (int k = 0; k < 6; ++k) { const double_ t = a6[k] < 0 ? -a6[k] : a6[k]; if (t > scale) scale = t; }
