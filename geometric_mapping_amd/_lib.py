@@ -518,6 +518,17 @@ class WallObjectMetrics(C.Structure):
                 ("angle_to_deg", C.c_double)]
 
 
+class WallAlignmentObjectsInfo(C.Structure):
+    _fields_ = WallObjectsInfo._fields_ + [("element", C.c_uint32), ("n_sides", C.c_uint32), ("anchor_global", C.c_int64),
+                                           ("total", C.c_int64), ("side_element", C.c_uint32 * 4),
+                                           ("side_first", C.c_uint32 * 4), ("side_rows", C.c_uint32 * 4)]
+
+
+class WallAlignmentObjectMetrics(C.Structure):
+    _fields_ = WallObjectMetrics._fields_ + [("element_from", C.c_uint32), ("element_to", C.c_uint32),
+                                             ("station_from", C.c_uint32), ("station_to", C.c_uint32)]
+
+
 class GmError(RuntimeError):
     def __init__(self, status, message):
         super().__init__(f"libgm_hip: status {status}: {message}")
@@ -615,6 +626,7 @@ def load():
     wcaprmp, wcainfop, wlprmp, wlinfop = map(P, (WallAddCheckedParams, WallAddCheckedInfo, WallLocateParams, WallLocateInfo))
     waprmp, wascp, wainfop = map(P, (WallAlignParams, WallAlignScore, WallAlignInfo))
     woprmp, wobjp, woinfop, wometp = map(P, (WallObjectParams, WallObject, WallObjectsInfo, WallObjectMetrics))
+    waloinfop, walometp = P(WallAlignmentObjectsInfo), P(WallAlignmentObjectMetrics)
     proto = {
         "gm_create": (C.c_int, [cfgp, C.POINTER(vp)]),
         "gm_destroy": (None, [vp]),
@@ -710,6 +722,10 @@ def load():
         "gm_wall_alignment_get_add_checked": (C.c_int, [vp, u32, wcainfop]),
         "gm_wall_alignment_add_points_checked": (C.c_int, [vp, fp, u32, u8p, dp, wcaprmp, wkptp, u32, waladdp, wcainfop, fp, i32p,
                                                            i32p]),
+        "gm_wall_alignment_check_objects": (C.c_int, [vp, u32, woprmp, waloinfop, wobjp, u32, u32p, i32p, u32]),
+        "gm_wall_alignment_check_objects_rows": (C.c_int, [vp, wkptp, u32, waladdp, woprmp, waloinfop, wobjp, u32, u32p, i32p]),
+        "gm_wall_alignment_object_window": (C.c_int, [wprmp, welp, u32, waladdp, woprmp, waloinfop]),
+        "gm_wall_alignment_object_metrics": (C.c_int, [wprmp, welp, u32, woprmp, wobjp, walometp]),
         "gm_wall_alignment_info": (C.c_int, [vp, waltotp]),
         "gm_wall_map_add_frame": (C.c_int, [vp, vp, u32, dp, waddp]),
         "gm_wall_map_add_points": (C.c_int, [vp, fp, u32, u8p, dp, waddp, fp, i32p]),

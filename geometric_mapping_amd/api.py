@@ -699,10 +699,27 @@ def object_metrics(prm, obj, **params):
     st = _lib.load().gm_wall_object_metrics(C.byref(prm), C.byref(op), r.ctypes.data_as(C.POINTER(_lib.WallObject)), C.byref(out))
     if st != _lib.GM_OK:
         raise _lib.GmError(st, "gm_wall_object_metrics refused the record")
-    d = {k: float(getattr(out, k)) for k, _t in _lib.WallObjectMetrics._fields_ if k not in ("centroid", "size")}
+    return _metrics_dict(out)
+
+
+def _metrics_dict(out):
+    d = {k: (float if t is C.c_double else int)(getattr(out, k)) for k, t in out._fields_ if k not in ("centroid", "size")}
     d["centroid"] = np.array(out.centroid[:], dtype=np.float64)
     d["size"] = np.array(out.size[:], dtype=np.float64)
     return d
+
+
+def _objects_request(ctx, call, n_rows, rows, info, info_dict, metrics):
+    """A count query, then the sized call; call(info, objects, capacity, got, object_of_row) is the bound ABI call.
+    Each of the two runs the whole device pipeline (the library keeps no result between calls), so this binding
+    launches every kernel twice per request; a caller that minds sizes the record buffer itself and calls the ABI
+    once, as tools/wall_objects_timing.py does.  info_dict(info) and metrics(record) shape the result."""
+    got = C.c_uint32(0)
+    of_row = np.full(max(n_rows, 1), -1, dtype=np.int32) if rows else None
+    rowp = of_row.ctypes.data_as(C.POINTER(C.c_int32)) if rows else None
+    obj = _sized(lambda rp, cap, sized: ctx._check(call(C.byref(info), rp, cap, C.byref(got), rowp if sized else None)),
+                 _lib.WallObject, got, lambda cap: cap or rows)
+    return info_dict(info), obj, [metrics(obj[i]) for i in range(len(obj))], (of_row[:n_rows].copy() if rows else None)
 
 
 def wall_region_metrics(prm, region):
@@ -1617,18 +1634,9 @@ class WallMap(_FrameLoop):
         return _wall_object_params(**kw)
 
     def _objects(self, call, n_rows, rows, p):
-        """A count query, then the sized call; call(info, objects, capacity, got, object_of_row) is the bound ABI call.
-        Each of the two runs the whole device pipeline (the library keeps no result between calls), so this binding
-        launches every kernel twice per request; a caller that minds sizes the record buffer itself and calls the ABI
-        once, as tools/wall_objects_timing.py does."""
-        info, got = _lib.WallObjectsInfo(), C.c_uint32(0)
-        of_row = np.full(max(n_rows, 1), -1, dtype=np.int32) if rows else None
-        rowp = of_row.ctypes.data_as(C.POINTER(C.c_int32)) if rows else None
-        obj = _sized(lambda rp, cap, sized: self._ctx._check(call(C.byref(info), rp, cap, C.byref(got), rowp if sized else None)),
-                     _lib.WallObject, got, lambda cap: cap or rows)
-        d = _ints(info, _OBJECTS_INFO)
-        metrics = [object_metrics(self.prm, obj[i], **p) for i in range(len(obj))]
-        return d, obj, metrics, (of_row[:n_rows].copy() if rows else None)
+        """_objects_request with this map's info and metrics."""
+        return _objects_request(self._ctx, call, n_rows, rows, _lib.WallObjectsInfo(), lambda i: _ints(i, _OBJECTS_INFO),
+                                lambda o: object_metrics(self.prm, o, **p))
 
     def check_objects(self, slot=0, rows=False, **params):
         """gm_wall_map_check_objects: the changed points of the last check on the slot grouped into objects on the device.
@@ -1741,6 +1749,100 @@ def _alignment_align_info(i):
     return d
 
 
+def _alignment_plan_struct(plan):
+    """A gm_wall_alignment_add_info from a plan dict (element, side_element, side_anchor: what the object calls read) or
+    the struct itself."""
+    if isinstance(plan, _lib.WallAlignmentAddInfo):
+        return plan
+    i = _lib.WallAlignmentAddInfo()
+    i.struct_size = C.sizeof(_lib.WallAlignmentAddInfo)
+    i.element, i.n_sides = int(plan["element"]), len(plan["side_element"])
+    for k in range(min(i.n_sides, 4)):
+        i.side_element[k], i.side_anchor[k] = int(plan["side_element"][k]), int(plan["side_anchor"][k])
+    return i
+
+
+def _alignment_objects_info(i):
+    """The dict of a gm_wall_alignment_objects_info: WallMap.check_objects()'s keys (station0 / n_stations global),
+    element, n_sides, anchor_global, total and side_element, side_first, side_rows [n_sides]."""
+    d = _ints(i, _OBJECTS_INFO + ("element", "n_sides", "anchor_global", "total"))
+    d.update({k: [int(x) for x in getattr(i, k)[:d["n_sides"]]] for k in ("side_element", "side_first", "side_rows")})
+    return d
+
+
+class _AlignmentObjects:
+    """gm_wall_alignment_check_objects and its kin for one WallAlignmentRule or WallAlignment `al`.  The public methods
+    here are bound onto the instance by its __init__ (al.object_window, al.object_metrics; on a WallAlignment also
+    al.check_objects, al.objects_of_rows) instead of being class attributes: tests/test_api_calls.py holds every callable
+    of the three classes to a recorded trace, and these calls' trace is tests/test_wall_alignment_objects_abi.py's."""
+
+    RULE, DEVICE = ("object_window", "object_metrics"), ("check_objects", "objects_of_rows")
+
+    def __init__(self, al):
+        self._al = al
+        self.bind(self.RULE)
+
+    def bind(self, names):
+        for k in names:
+            setattr(self._al, k, getattr(self, k))
+
+    def object_window(self, plan, **params):
+        """gm_wall_alignment_object_window: the info dict (_alignment_objects_info, the counts 0) of the object calls for
+        `plan` (a plan dict or struct) under the object parameters given as keywords; GmError with GM_ERR_UNSUPPORTED for
+        an alignment beyond the size rule."""
+        p, pl, info = _wall_object_params(**params), _alignment_plan_struct(plan), _lib.WallAlignmentObjectsInfo()
+        st = self._al._L.gm_wall_alignment_object_window(*self._al._head(), C.byref(pl), C.byref(p), C.byref(info))
+        if st != _lib.GM_OK:
+            raise _lib.GmError(st, "gm_wall_alignment_object_window refused the arguments")
+        return _alignment_objects_info(info)
+
+    def object_metrics(self, obj, **params):
+        """gm_wall_alignment_object_metrics of one WALL_OBJECT record on the global station grid: WallMap.object_metrics'
+        keys in alignment chainage, and element_from, element_to, station_from, station_to."""
+        r = np.ascontiguousarray(np.asarray(obj, dtype=WALL_OBJECT).reshape(1))
+        op, out = _wall_object_params(**params), _lib.WallAlignmentObjectMetrics()
+        st = self._al._L.gm_wall_alignment_object_metrics(*self._al._head(), C.byref(op), r.ctypes.data_as(C.POINTER(_lib.WallObject)),
+                                                      C.byref(out))
+        if st != _lib.GM_OK:
+            raise _lib.GmError(st, "gm_wall_alignment_object_metrics refused the record")
+        return _metrics_dict(out)
+
+    def _objects(self, call, n_rows, rows, p):
+        return _objects_request(self._al._ctx, call, n_rows, rows, _lib.WallAlignmentObjectsInfo(), _alignment_objects_info,
+                                lambda o: self.object_metrics(o, **p))
+
+    def check_objects(self, slot=0, rows=False, **params):
+        """gm_wall_alignment_check_objects: the changed points of the last check through the alignment on the slot as
+        objects on the global station grid.  Returns WallMap.check_objects' tuple: (info dict, WALL_OBJECT records
+        ascending by (label, sign), metrics list of dicts, object_of_row int32 per changed row in check_result()'s order
+        or None without rows).  Two device passes (_objects_request); rows=True costs one further
+        gm_wall_alignment_get_check count query for the row count."""
+        p = _wall_object_params(**params)
+        n_rows = 0
+        if rows:
+            got = C.c_uint32(0)
+            self._al._ctx._check(self._al._L.gm_wall_alignment_get_check(self._al._h(), slot, None, None, 0, C.byref(got)))
+            n_rows = int(got.value)
+
+        def call(info, obj, cap, got, of_row):
+            return self._al._L.gm_wall_alignment_check_objects(self._al._h(), slot, C.byref(p), info, obj, cap, got, of_row,
+                                                           n_rows if of_row else 0)
+        return self._objects(call, n_rows, rows, params)
+
+    def objects_of_rows(self, rows, plan, **params):
+        """gm_wall_alignment_check_objects_rows: the same kernels on host rows (WALL_CHECK_POINT records in any order,
+        cell = side << 24 | cell) under the sides and the anchor of `plan` (a check's plan dict, or the struct).  Returns
+        (info dict, WALL_OBJECT records, metrics list, object_of_row int32 [len(rows)])."""
+        p, pl = _wall_object_params(**params), _alignment_plan_struct(plan)
+        r = np.ascontiguousarray(rows, dtype=WALL_CHECK_POINT).reshape(-1)
+        rp = r.ctypes.data_as(C.POINTER(_lib.WallCheckPoint)) if len(r) else None
+
+        def call(info, obj, cap, got, of_row):
+            return self._al._L.gm_wall_alignment_check_objects_rows(self._al._h(), rp, len(r), C.byref(pl), C.byref(p), info, obj, cap, got,
+                                                                of_row)
+        return self._objects(call, len(r), True, params)
+
+
 class WallAlignmentRule:
     """The device-free half of a wall alignment (gm_wall_alignment_check, _element_params, _project, _point, _window,
     _add_plan; include/gm_hip.h states the rule): a template gm_wall_params and the elements.  Needs no context."""
@@ -1751,6 +1853,7 @@ class WallAlignmentRule:
         self._L = _lib.load()
         self.prm = WallMap.params(**params)
         self._els, self.n_elements = _wall_elements(elements)
+        self._object_calls = _AlignmentObjects(self)
 
     def _head(self):
         return C.byref(self.prm), self._els, self.n_elements
@@ -1871,6 +1974,7 @@ class WallAlignment(WallAlignmentRule, _FrameLoop):
         ctx._check(self._L.gm_wall_alignment_create(ctx._ctx, *self._head(), C.byref(h)))
         self._al = h
         self._maps = {}
+        self._object_calls.bind(_AlignmentObjects.DEVICE)
 
     def _h(self):
         if self._al is None or not self._ctx._ctx:

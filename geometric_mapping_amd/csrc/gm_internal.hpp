@@ -674,14 +674,23 @@ __host__ __device__ inline WallQuantityColumn wall_quantity_column(long long Rq,
     return c;
 }
 // k_wall_objects.hip (gm_wall_map_check_objects, gm_wall_check_objects): bin -> tiles -> seams -> flatten | blocks ->
-// reduce -> select | rows
+// reduce -> select | rows; k_wall_objects_joint.hip (gm_wall_alignment_check_objects): bin, reduce and rows behind the
+// alignment's row decode (gm_wall_objects.hpp)
 constexpr uint32_t kWallObjectTileBlocks = 4096;      // the most window blocks of a tile (its LDS tables)
 // (two index spaces that never meet: kCcNone (gm_gridcc.hpp) is a value of parent[], kWallObjectRejected /
 // kWallObjectOutside are values of a row's decoded block index; both are above every real index, 2 NB <= 2^21)
 constexpr uint32_t kWallObjectRejected = 0xFFFFFFFFu, kWallObjectOutside = 0xFFFFFFFEu;   // a row without a window block
 // u64 words 0 .. 8: rejected, outside_window, sparse, small, in_object, flagged_neg, flagged_pos, components, objects;
-// words 9 .. 15 unused: the block is 128 bytes so that its zero-fill and its copy are whole multiples of 16 bytes
+// words 9 .. 12: the rows of each side that are not rejected (the joint kernels only; 0 on a map); words 13 .. 15 unused:
+// the block is 128 bytes so that its zero-fill and its copy are whole multiples of 16 bytes
 constexpr int kWallObjectCounters = 16;
+constexpr int kWallObjectSideRows = 9;
+// gm_wall_alignment_check_objects: a row's cell is side << 24 | cell; side k's stations start at global station first[k]
+// and its map holds cells[k] cells.  n_sides 0: a map's rows (cell is the map's cell), the table is not read.
+struct WallObjectSides {
+    uint32_t n_sides;
+    uint32_t first[4], cells[4];
+};
 struct WallObjectAcc {   // 128 B, zero = empty: minima are kept inverted so that every extent is an integer maximum
     uint32_t label, blocks;
     uint32_t st_min_inv, st_max, k_min_inv, k_max, t_min_inv, t_max;
@@ -706,7 +715,9 @@ struct WallObjectArgs {
     const int32_t *pos;        // [components]: slot -> position in the sorted list, -1 for a small component
     uint32_t ncomp;
     int32_t *object_of_row;    // [n_rows]
+    WallObjectSides sides;     // by value, behind everything the map's kernels read
 };
+static_assert(GM_WALL_JOINT_MAX_SIDES == 4, "WallObjectSides, counter words 9 .. 12");
 void launch_wall_object_label(const WallObjectArgs &a, hipStream_t s);    // four launches, up to the component count
 void launch_wall_object_reduce(const WallObjectArgs &a, hipStream_t s);   // three launches, up to the object list
 void launch_wall_object_rows(const WallObjectArgs &a, hipStream_t s);     // object_of_row

@@ -437,13 +437,7 @@ static gm_status create_map(gm_ctx *ctx, const gm_wall_params *params, const gm_
             m->region_tk = tk;
         }
     }
-    if (const char *e = getenv("GM_WALL_OBJECT_TILE")) {   // <block rows>x<block columns>; anything else: the default
-        unsigned tr = 0, tc = 0;
-        if (sscanf(e, "%ux%u", &tr, &tc) == 2 && tr >= 1u && tc >= 1u && (uint64_t)tr * tc <= kWallObjectTileBlocks) {
-            m->object_tr = tr;
-            m->object_tc = tc;
-        }
-    }
+    m->ob.read_tile_env();
     if (const char *e = getenv("GM_WALL_CLOUD_CHUNK")) {   // blocks; 0 or more than the default: the default (scratch is sized by it)
         const unsigned long long v = strtoull(e, nullptr, 10);
         m->cloud_chunk = v < kStageCells ? (uint32_t)v : 0u;

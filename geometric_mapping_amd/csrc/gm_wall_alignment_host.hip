@@ -4,6 +4,7 @@
 // element map's own, asked of the axis.  Like gm_wall_host.hip it links against libm and the C++ library alone;
 // host/gm_wall_alignment_host_test.cpp runs it under the host sanitizers.
 #include <stddef.h>
+#include <stdint.h>
 #include <stdio.h>
 
 #include <vector>
@@ -369,6 +370,51 @@ gm_status alignment_window(const Alignment &A, double s_from, double s_to, gm_wa
     return got > capacity ? GM_ERR_CAPACITY : GM_OK;
 }
 
+// gm_wall_alignment_check_objects' host half (include/gm_hip.h states the rule): the size rule, the plan's sides on the
+// global station grid, G_f and the window around it
+gm_status alignment_object_window(const Alignment &A, const gm_wall_alignment_add_info &plan, const gm_wall_object_params &op,
+                                  ObjectWindow &w, gm_wall_alignment_objects_info *info)
+{
+    static_assert(sizeof(gm_wall_alignment_objects_info) == 136 && offsetof(gm_wall_alignment_objects_info, element) == sizeof(gm_wall_objects_info),
+                  "the shared head");
+    if (!info) return GM_ERR_INVALID_ARG;
+    memset(info, 0, sizeof(*info));
+    info->struct_size = (uint32_t)sizeof(gm_wall_alignment_objects_info);
+    if (A.el.empty() || !object_prm_ok(op)) return GM_ERR_INVALID_ARG;
+    const uint32_t n = (uint32_t)A.el.size(), nsec = A.el[0].p.n_sectors;
+    uint64_t total = 0;
+    for (const AlignElem &E : A.el) total += E.p.n_stations;   // (<= 256 * 2^32)
+    const uint64_t NK = (nsec + op.block_sectors - 1u) / op.block_sectors;
+    const uint64_t rows_of_blocks = (total + op.block_stations - 1u) / op.block_stations;
+    if (total > 0xFFFFFFFFull || rows_of_blocks * NK > 0xFFFFFFFFull) return GM_ERR_UNSUPPORTED;   // (both factors < 2^32)
+    if (plan.struct_size != sizeof(gm_wall_alignment_add_info) || plan.n_sides < 1u || plan.n_sides > GM_WALL_JOINT_MAX_SIDES)
+        return GM_ERR_INVALID_ARG;
+    for (uint32_t k = 0; k < plan.n_sides; ++k)
+        if (plan.side_element[k] >= n || (k && plan.side_element[k] != plan.side_element[k - 1u] + 1u)) return GM_ERR_INVALID_ARG;
+    if (plan.element < plan.side_element[0] || plan.element > plan.side_element[plan.n_sides - 1u]) return GM_ERR_INVALID_ARG;
+    const uint32_t home = plan.element - plan.side_element[0];
+    uint64_t base = 0;
+    for (uint32_t i = 0; i < plan.side_element[0]; ++i) base += A.el[i].p.n_stations;
+    info->element = plan.element;
+    info->n_sides = plan.n_sides;
+    info->total = (int64_t)total;
+    for (uint32_t k = 0; k < plan.n_sides; ++k) {
+        info->side_element[k] = plan.side_element[k];
+        info->side_first[k] = (uint32_t)base;
+        base += A.el[plan.side_element[k]].p.n_stations;
+    }
+    // G_f in int64: an anchor the add accepts is < 4e18 in size and a base < 2^32; anything else saturates, far outside
+    const int64_t bf = (int64_t)info->side_first[home], an = plan.side_anchor[home];
+    const int64_t Gf = an > INT64_MAX - bf ? INT64_MAX : bf + an;
+    info->anchor_global = Gf;
+    if (!object_window(total, nsec, op, Gf, w)) return GM_ERR_INVALID_ARG;
+    info->station0 = w.station0;
+    info->n_stations = w.n_stations;
+    info->blocks_stations = w.nJ;
+    info->blocks_sectors = w.NK;
+    return GM_OK;
+}
+
 }  // namespace wall
 }  // namespace gm
 
@@ -459,6 +505,50 @@ gm_status gm_wall_alignment_align_select(const gm_wall_params *params, const gm_
     GMW_OK(alignment_align_plan(A, pose, bound, ap, &plan));
     if (n_scores != (2u * ap.max_station_shift + 1u) * (2u * ap.max_sector_shift + 1u)) return GM_ERR_INVALID_ARG;
     return alignment_align_select(A, pose, ap, plan, table, info);
+}
+
+gm_status gm_wall_alignment_object_window(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n,
+                                          const gm_wall_alignment_add_info *plan, const gm_wall_object_params *prm,
+                                          gm_wall_alignment_objects_info *info)
+{
+    Alignment A;
+    if (!plan || !info) return GM_ERR_INVALID_ARG;
+    GMW_OK(alignment_build(params, elements, n, A));
+    ObjectWindow w;
+    return alignment_object_window(A, *plan, params_or(prm, gm_wall_object_default_params), w, info);
+}
+
+gm_status gm_wall_alignment_object_metrics(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n,
+                                           const gm_wall_object_params *op, const gm_wall_object *o,
+                                           struct gm_wall_alignment_object_metrics *out)
+{
+    static_assert(sizeof(struct gm_wall_alignment_object_metrics) == 112 &&
+                      offsetof(struct gm_wall_alignment_object_metrics, element_from) == sizeof(struct gm_wall_object_metrics),
+                  "the shared head");
+    Alignment A;
+    if (!o || !out) return GM_ERR_INVALID_ARG;
+    GMW_OK(alignment_build(params, elements, n, A));
+    struct gm_wall_object_metrics head;
+    GMW_OK(gm_wall_object_metrics(params, op, o, &head));   // (the template's t_min, station_length and n_sectors)
+    uint64_t total = 0;
+    for (const AlignElem &E : A.el) total += E.p.n_stations;
+    if ((uint64_t)o->station_max >= total) return GM_ERR_INVALID_ARG;   // (station_min <= station_max: the head's refusal)
+    memset(out, 0, sizeof(*out));
+    memcpy(out, &head, sizeof(head));
+    uint64_t base = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t next = base + A.el[i].p.n_stations;
+        if (o->station_min >= base && o->station_min < next) {
+            out->element_from = i;
+            out->station_from = (uint32_t)(o->station_min - base);
+        }
+        if (o->station_max >= base && o->station_max < next) {
+            out->element_to = i;
+            out->station_to = (uint32_t)(o->station_max - base);
+        }
+        base = next;
+    }
+    return GM_OK;
 }
 
 }  // extern "C"

@@ -596,6 +596,21 @@ bool object_prm_ok(const gm_wall_object_params &p)
            p.half_window_stations >= 1u && p.half_window_stations <= (1u << 20);
 }
 
+bool object_window(uint64_t n_stations, uint32_t n_sectors, const gm_wall_object_params &op, int64_t jf, ObjectWindow &w)
+{
+    const int64_t H = op.half_window_stations, ns = (int64_t)n_stations;   // (compared before added: j_f is any int64)
+    const int64_t lo = jf > H ? jf - H : 0, hi = jf >= ns - H ? ns : jf + H;
+    w = ObjectWindow();
+    w.NK = (n_sectors + op.block_sectors - 1u) / op.block_sectors;
+    if (lo >= hi) return true;
+    const uint64_t bs = op.block_stations, J0 = (uint64_t)lo / bs, J1 = (uint64_t)(hi - 1) / bs;
+    w.J0 = (uint32_t)J0;
+    w.nJ = (uint32_t)(J1 - J0 + 1u);
+    w.station0 = (uint32_t)(J0 * bs);
+    w.n_stations = (uint32_t)(std::min<uint64_t>((J1 + 1u) * bs, (uint64_t)ns) - J0 * bs);
+    return (uint64_t)w.nJ * w.NK <= GM_WALL_OBJECT_MAX_BLOCKS;
+}
+
 bool align_select_table(const gm_wall_align_params &ap, double ds, uint32_t nsec, const gm_wall_align_score *t, gm_wall_align_info *info)
 {
     const int A = (int)ap.max_station_shift, B = (int)ap.max_sector_shift, nb = 2 * B + 1, ns = (2 * A + 1) * nb;

@@ -152,6 +152,19 @@ bool check_prm_ok(const gm_wall_check_params &c, long long &T);
 bool locate_prm_ok(const gm_wall_locate_params &p);
 bool align_prm_ok(const gm_wall_align_params &p, uint32_t nsec);
 bool object_prm_ok(const gm_wall_object_params &p);
+// The window of the object rule around the anchor station jf on a grid of n_stations x n_sectors -- a map's own, or an
+// alignment's global stations (n_stations = total <= 2^32 - 1).  false: more than GM_WALL_OBJECT_MAX_BLOCKS blocks.
+struct ObjectWindow {
+    uint32_t J0 = 0, nJ = 0, NK = 0;         // block rows [J0, J0 + nJ) (nJ 0: empty), blocks per block row
+    uint32_t station0 = 0, n_stations = 0;   // the block rows' stations, clipped to the grid
+};
+bool object_window(uint64_t n_stations, uint32_t n_sectors, const gm_wall_object_params &op, int64_t jf, ObjectWindow &w);
+// gm_wall_alignment_check_objects: the plan's sides on the global station grid.  Refusals in their order: GM_ERR_UNSUPPORTED
+// (total or the block count beyond 32 bits), GM_ERR_INVALID_ARG (the plan's sides, its element, a window above
+// GM_WALL_OBJECT_MAX_BLOCKS blocks).  info: struct_size, the window fields, element, n_sides, anchor_global, total,
+// side_element, side_first; everything else 0.
+gm_status alignment_object_window(const Alignment &A, const gm_wall_alignment_add_info &plan, const gm_wall_object_params &op,
+                                  ObjectWindow &w, gm_wall_alignment_objects_info *info);
 bool add_checked_prm_ok(const gm_wall_add_checked_params &p, long long &S);   // S of an accepted block
 // The selection half of the align rule of include/gm_hip.h from a table of (2A + 1)(2B + 1) records on a grid of station
 // length ds and nsec sectors: everything of info but the device's counts, anchor_station and the pose (NaN when it returns
@@ -325,6 +338,35 @@ struct PointOutputs {
                         int32_t *h_element) const;
 };
 
+// gm_wall_map_check_objects / gm_wall_check_objects and gm_wall_alignment_check_objects / _rows: the tile in blocks
+// (GM_WALL_OBJECT_TILE: tests, measurements) and the scratch of their owner, a map or an alignment; allocated on first use
+struct ObjectScratch {
+    uint32_t tr = GM_WALL_OBJECT_TILE_ROWS, tc = GM_WALL_OBJECT_TILE_COLS;
+    DevArray<uint32_t> blocks;               // per window block and plane: cnt | parent | slot
+    DevArray<unsigned long long> ctr;        // [kWallObjectCounters]
+    DevArray<uint8_t> recs;                  // per component: WallObjectAcc | gm_wall_object | out_slot u32 | pos i32
+    DevArray<gm_wall_check_point> rows;      // the stage call's rows
+    DevArray<int32_t> of_row;                // object_of_row
+    std::vector<gm_wall_object> host;        // the unsorted list, its slots, the sorting permutation, slot -> position
+    std::vector<uint32_t> host_slot, order;
+    std::vector<int32_t> pos;
+    void read_tile_env();                    // GM_WALL_OBJECT_TILE=<block rows>x<block columns>; anything else: the default
+};
+// The grid a call's rows are decoded on: a map's (sides.n_sides 0) or an alignment's sides on its global stations.
+struct ObjectGrid {
+    uint32_t nsec = 0, cells = 0;
+    WallObjectSides sides = {};
+};
+// The object call on n_rows device rows (32-byte aligned), on stream `s`, blocking.  rejected_if_empty and
+// side_rows_if_empty (may be NULL): the rejected rows and each side's rows that are not, used when nothing is launched
+// (zero rows or an empty window).  info: the fields gm_wall_objects_info and gm_wall_alignment_objects_info share, from
+// n_rows on (struct_size and what lies behind `reserved` are the caller's); side_rows (may be NULL): counter words
+// 9 .. 12.  objects / object_of_row may be NULL; the capacities were checked by the caller but for the record count.
+gm_status objects_run(gm_ctx *ctx, hipStream_t s, ObjectScratch &ob, const ObjectGrid &grid, const gm_wall_check_point *d_rows,
+                      uint32_t n_rows, uint32_t rejected_if_empty, const uint32_t *side_rows_if_empty, const gm_wall_object_params &op,
+                      const ObjectWindow &win, gm_wall_objects_info *info, uint32_t *side_rows, gm_wall_object *objects,
+                      uint32_t capacity, uint32_t *n_out, int32_t *object_of_row, const char *who);
+
 }  // namespace wall
 }  // namespace gm
 
@@ -402,17 +444,8 @@ struct gm_wall_map {
     gm::DevArray<gm_wall_check_point> ac_rows;
     gm::DevArray<unsigned long long> ac_blk;
     uint32_t align_rows = 0;  // the patch rows per score block (GM_WALL_ALIGN_ROWS: tests, measurements; 0: the default rule)
-    // gm_wall_map_check_objects / gm_wall_check_objects: the tile in blocks (GM_WALL_OBJECT_TILE: tests, measurements) and
-    // the scratch
-    uint32_t object_tr = GM_WALL_OBJECT_TILE_ROWS, object_tc = GM_WALL_OBJECT_TILE_COLS;
-    gm::DevArray<uint32_t> ob_blocks;            // per window block and plane: cnt | parent | slot
-    gm::DevArray<unsigned long long> ob_ctr;     // [kWallObjectCounters]
-    gm::DevArray<uint8_t> ob_recs;               // per component: WallObjectAcc | gm_wall_object | out_slot u32 | pos i32
-    gm::DevArray<gm_wall_check_point> ob_rows;   // the stage call's rows
-    gm::DevArray<int32_t> ob_of_row;             // object_of_row
-    std::vector<gm_wall_object> ob_host;     // the unsorted list, its slots, the sorting permutation, slot -> position
-    std::vector<uint32_t> ob_host_slot, ob_order;
-    std::vector<int32_t> ob_pos;
+    // gm_wall_map_check_objects / gm_wall_check_objects
+    gm::wall::ObjectScratch ob;
 };
 
 // ---- gm_wall.hip: what the per-slot calls share with the map's own ----

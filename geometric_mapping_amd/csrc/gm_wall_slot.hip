@@ -2,6 +2,10 @@
 // gm_wall_map_check_objects / gm_wall_check_objects; include/gm_hip.h states the rules).  Each enqueues on a slot's stream
 // and leaves a PendingResult (gm_wall_map.hpp) the host reads later.  Kernels are in k_wall_check.hip, k_wall_locate.hip,
 // k_wall_align.hip and k_wall_objects.hip.
+#include <stddef.h>
+#include <stdio.h>
+#include <stdlib.h>
+
 #include "gm_wall_map.hpp"
 
 using namespace gm;
@@ -284,93 +288,88 @@ gm_status align_result(gm_wall_map *m, uint32_t slot, gm_wall_align_info *info, 
     return GM_OK;
 }
 
-// ---- gm_wall_map_check_objects / gm_wall_check_objects ----
+}  // namespace
 
-struct ObjectWindow {
-    uint32_t J0 = 0, nJ = 0, NK = 0;         // block rows [J0, J0 + nJ) (nJ 0: empty), blocks per block row
-    uint32_t station0 = 0, n_stations = 0;   // the block rows' stations, clipped to the map
-};
-// the window of include/gm_hip.h around the anchor j_f; false: more than GM_WALL_OBJECT_MAX_BLOCKS blocks
-bool object_window(const gm_wall_params &p, const gm_wall_object_params &op, int64_t jf, ObjectWindow &w)
+namespace gm {
+namespace wall {
+
+// ---- gm_wall_map_check_objects / gm_wall_check_objects, gm_wall_alignment_check_objects / _rows ----
+
+void ObjectScratch::read_tile_env()
 {
-    const int64_t H = op.half_window_stations, ns = p.n_stations;   // (compared before added: j_f is any int64)
-    const int64_t lo = jf > H ? jf - H : 0, hi = jf >= ns - H ? ns : jf + H;
-    w = ObjectWindow();
-    w.NK = (p.n_sectors + op.block_sectors - 1u) / op.block_sectors;
-    if (lo >= hi) return true;
-    const uint64_t bs = op.block_stations, J0 = (uint64_t)lo / bs, J1 = (uint64_t)(hi - 1) / bs;
-    w.J0 = (uint32_t)J0;
-    w.nJ = (uint32_t)(J1 - J0 + 1u);
-    w.station0 = (uint32_t)(J0 * bs);
-    w.n_stations = (uint32_t)(std::min<uint64_t>((J1 + 1u) * bs, (uint64_t)ns) - J0 * bs);
-    return (uint64_t)w.nJ * w.NK <= GM_WALL_OBJECT_MAX_BLOCKS;
+    if (const char *e = getenv("GM_WALL_OBJECT_TILE")) {
+        unsigned r = 0, c = 0;
+        if (sscanf(e, "%ux%u", &r, &c) == 2 && r >= 1u && c >= 1u && (uint64_t)r * c <= kWallObjectTileBlocks) {
+            tr = r;
+            tc = c;
+        }
+    }
 }
 
-// The call on n_rows device rows (32-byte aligned), on the map's stream, blocking.  rejected_if_empty: the rejected rows,
-// used when nothing is launched (zero rows or an empty window).  objects / object_of_row may be NULL; the capacities were
-// checked by the caller but for the record count.
-gm_status objects_run(gm_wall_map *m, const gm_wall_check_point *d_rows, uint32_t n_rows, uint32_t rejected_if_empty,
-                      const gm_wall_object_params &op, const ObjectWindow &win, gm_wall_objects_info *info, gm_wall_object *objects,
+gm_status objects_run(gm_ctx *ctx, hipStream_t s, ObjectScratch &ob, const ObjectGrid &grid, const gm_wall_check_point *d_rows,
+                      uint32_t n_rows, uint32_t rejected_if_empty, const uint32_t *side_rows_if_empty, const gm_wall_object_params &op,
+                      const ObjectWindow &win, gm_wall_objects_info *info, uint32_t *side_rows, gm_wall_object *objects,
                       uint32_t capacity, uint32_t *n_out, int32_t *object_of_row, const char *who)
 {
-    gm_ctx *ctx = m->ctx;
-    memset(info, 0, sizeof(*info));
-    info->struct_size = (uint32_t)sizeof(gm_wall_objects_info);
+    memset(&info->n_rows, 0, sizeof(*info) - offsetof(gm_wall_objects_info, n_rows));
     info->n_rows = n_rows;
     info->station0 = win.station0;
     info->n_stations = win.n_stations;
     info->blocks_stations = win.nJ;
     info->blocks_sectors = win.NK;
+    if (side_rows) std::fill(side_rows, side_rows + GM_WALL_JOINT_MAX_SIDES, 0u);
     if (!n_rows || !win.nJ) {   // nothing to launch
         info->rejected = rejected_if_empty;
         info->outside_window = n_rows - rejected_if_empty;
+        if (side_rows && side_rows_if_empty) std::copy(side_rows_if_empty, side_rows_if_empty + GM_WALL_JOINT_MAX_SIDES, side_rows);
         if (object_of_row) std::fill(object_of_row, object_of_row + n_rows, -1);
         return GM_OK;
     }
     const uint64_t NB = (uint64_t)win.nJ * win.NK, pairs = 2u * NB;
-    GMW_HIP(ctx, m->ob_blocks.reserve(3u * pairs));
-    GMW_HIP(ctx, m->ob_ctr.reserve(kWallObjectCounters));
-    if (object_of_row) GMW_HIP(ctx, m->ob_of_row.reserve(n_rows));
+    GMW_HIP(ctx, ob.blocks.reserve(3u * pairs));
+    GMW_HIP(ctx, ob.ctr.reserve(kWallObjectCounters));
+    if (object_of_row) GMW_HIP(ctx, ob.of_row.reserve(n_rows));
     WallObjectArgs a;
     memset(&a, 0, sizeof(a));
     a.rows = d_rows;
     a.n_rows = n_rows;
-    a.nsec = m->prm.n_sectors;
-    a.cells = (uint32_t)m->ncell;   // <= GM_WALL_MAX_CELLS
+    a.nsec = grid.nsec;
+    a.cells = grid.cells;   // <= GM_WALL_MAX_CELLS
+    a.sides = grid.sides;
     a.bs = op.block_stations; a.bk = op.block_sectors; a.NK = win.NK;
     a.J0 = win.J0; a.nJ = win.nJ; a.NB = (uint32_t)NB;
-    a.ts = m->object_tr; a.tk = m->object_tc;
+    a.ts = ob.tr; a.tk = ob.tc;
     a.tiles_s = (a.nJ + a.ts - 1u) / a.ts;
     a.tiles_k = (a.NK + a.tk - 1u) / a.tk;
     a.conn8 = op.connectivity == 8u ? 1u : 0u;
     a.min_block_points = op.min_block_points;
     a.min_points = op.min_points;
-    a.cnt = m->ob_blocks.p;   // cnt | parent | slot, [pairs] each
+    a.cnt = ob.blocks.p;   // cnt | parent | slot, [pairs] each
     a.parent = a.cnt + pairs;
     a.slot = a.parent + pairs;
-    a.ctr = m->ob_ctr.p;
-    a.object_of_row = m->ob_of_row.p;
+    a.ctr = ob.ctr.p;
+    a.object_of_row = ob.of_row.p;
     unsigned long long ctr[kWallObjectCounters];
-    GMW_HIP(ctx, hipMemsetAsync(a.cnt, 0, pairs * 4, m->stream));
-    GMW_HIP(ctx, hipMemsetAsync(a.ctr, 0, kWallObjectCounters * 8, m->stream));
-    launch_wall_object_label(a, m->stream);
+    GMW_HIP(ctx, hipMemsetAsync(a.cnt, 0, pairs * 4, s));
+    GMW_HIP(ctx, hipMemsetAsync(a.ctr, 0, kWallObjectCounters * 8, s));
+    launch_wall_object_label(a, s);
     GMW_HIP(ctx, hipGetLastError());
-    GMW_HIP(ctx, hipMemcpyAsync(ctr, a.ctr, sizeof(ctr), hipMemcpyDeviceToHost, m->stream));
-    GMW_HIP(ctx, hipStreamSynchronize(m->stream));   // the one count the host needs: it sizes the records
+    GMW_HIP(ctx, hipMemcpyAsync(ctr, a.ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
+    GMW_HIP(ctx, hipStreamSynchronize(s));   // the one count the host needs: it sizes the records
     const uint64_t ncomp = ctr[7];
     if (ncomp) {
-        GMW_HIP(ctx, m->ob_recs.reserve(ncomp * (sizeof(WallObjectAcc) + sizeof(gm_wall_object) + 4 + 4)));
-        Carve recs{m->ob_recs.p};
+        GMW_HIP(ctx, ob.recs.reserve(ncomp * (sizeof(WallObjectAcc) + sizeof(gm_wall_object) + 4 + 4)));
+        Carve recs{ob.recs.p};
         a.acc = recs.take<WallObjectAcc>(ncomp);
         a.out = recs.take<gm_wall_object>(ncomp);
         a.out_slot = recs.take<uint32_t>(ncomp);
         a.pos = recs.take<int32_t>(ncomp);
         a.ncomp = (uint32_t)ncomp;
-        GMW_HIP(ctx, hipMemsetAsync(a.acc, 0, ncomp * sizeof(WallObjectAcc), m->stream));
-        launch_wall_object_reduce(a, m->stream);
+        GMW_HIP(ctx, hipMemsetAsync(a.acc, 0, ncomp * sizeof(WallObjectAcc), s));
+        launch_wall_object_reduce(a, s);
         GMW_HIP(ctx, hipGetLastError());
-        GMW_HIP(ctx, hipMemcpyAsync(ctr, a.ctr, sizeof(ctr), hipMemcpyDeviceToHost, m->stream));
-        GMW_HIP(ctx, hipStreamSynchronize(m->stream));
+        GMW_HIP(ctx, hipMemcpyAsync(ctr, a.ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
+        GMW_HIP(ctx, hipStreamSynchronize(s));
     }
     const uint32_t nobj = (uint32_t)ctr[8];
     info->rejected = (uint32_t)ctr[0]; info->outside_window = (uint32_t)ctr[1]; info->sparse = (uint32_t)ctr[2];
@@ -378,32 +377,34 @@ gm_status objects_run(gm_wall_map *m, const gm_wall_check_point *d_rows, uint32_
     info->flagged_neg = (uint32_t)ctr[5]; info->flagged_pos = (uint32_t)ctr[6];
     info->components = (uint32_t)ncomp;
     info->objects = nobj;
+    if (side_rows)
+        for (int k = 0; k < GM_WALL_JOINT_MAX_SIDES; ++k) side_rows[k] = (uint32_t)ctr[kWallObjectSideRows + k];
     if (n_out) *n_out = nobj;
     const bool fits = nobj <= capacity;
     if (nobj && ((objects && fits) || object_of_row)) {   // the list in (label, sign) order
-        m->ob_host.resize(nobj);
-        m->ob_host_slot.resize(nobj);
-        m->ob_order.resize(nobj);
-        GMW_HIP(ctx, hipMemcpyAsync(m->ob_host.data(), a.out, (size_t)nobj * sizeof(gm_wall_object), hipMemcpyDeviceToHost, m->stream));
-        GMW_HIP(ctx, hipMemcpyAsync(m->ob_host_slot.data(), a.out_slot, (size_t)nobj * 4, hipMemcpyDeviceToHost, m->stream));
-        GMW_HIP(ctx, hipStreamSynchronize(m->stream));
-        for (uint32_t i = 0; i < nobj; ++i) m->ob_order[i] = i;
-        const std::vector<gm_wall_object> &h = m->ob_host;
-        std::sort(m->ob_order.begin(), m->ob_order.end(), [&h](uint32_t x, uint32_t y) {
+        ob.host.resize(nobj);
+        ob.host_slot.resize(nobj);
+        ob.order.resize(nobj);
+        GMW_HIP(ctx, hipMemcpyAsync(ob.host.data(), a.out, (size_t)nobj * sizeof(gm_wall_object), hipMemcpyDeviceToHost, s));
+        GMW_HIP(ctx, hipMemcpyAsync(ob.host_slot.data(), a.out_slot, (size_t)nobj * 4, hipMemcpyDeviceToHost, s));
+        GMW_HIP(ctx, hipStreamSynchronize(s));
+        for (uint32_t i = 0; i < nobj; ++i) ob.order[i] = i;
+        const std::vector<gm_wall_object> &h = ob.host;
+        std::sort(ob.order.begin(), ob.order.end(), [&h](uint32_t x, uint32_t y) {
             return h[x].label != h[y].label ? h[x].label < h[y].label : h[x].sign < h[y].sign;
         });
         if (objects && fits)
-            for (uint32_t i = 0; i < nobj; ++i) objects[i] = h[m->ob_order[i]];
+            for (uint32_t i = 0; i < nobj; ++i) objects[i] = h[ob.order[i]];
     }
     if (object_of_row) {
         if (ncomp) {
-            m->ob_pos.assign((size_t)ncomp, -1);
-            for (uint32_t i = 0; i < nobj; ++i) m->ob_pos[m->ob_host_slot[m->ob_order[i]]] = (int32_t)i;
-            GMW_HIP(ctx, hipMemcpyAsync(const_cast<int32_t *>(a.pos), m->ob_pos.data(), (size_t)ncomp * 4, hipMemcpyHostToDevice, m->stream));
-            launch_wall_object_rows(a, m->stream);
+            ob.pos.assign((size_t)ncomp, -1);
+            for (uint32_t i = 0; i < nobj; ++i) ob.pos[ob.host_slot[ob.order[i]]] = (int32_t)i;
+            GMW_HIP(ctx, hipMemcpyAsync(const_cast<int32_t *>(a.pos), ob.pos.data(), (size_t)ncomp * 4, hipMemcpyHostToDevice, s));
+            launch_wall_object_rows(a, s);
             GMW_HIP(ctx, hipGetLastError());
-            GMW_HIP(ctx, hipMemcpyAsync(object_of_row, a.object_of_row, (size_t)n_rows * 4, hipMemcpyDeviceToHost, m->stream));
-            GMW_HIP(ctx, hipStreamSynchronize(m->stream));
+            GMW_HIP(ctx, hipMemcpyAsync(object_of_row, a.object_of_row, (size_t)n_rows * 4, hipMemcpyDeviceToHost, s));
+            GMW_HIP(ctx, hipStreamSynchronize(s));
         } else {
             std::fill(object_of_row, object_of_row + n_rows, -1);
         }
@@ -412,7 +413,8 @@ gm_status objects_run(gm_wall_map *m, const gm_wall_check_point *d_rows, uint32_
     return GM_OK;
 }
 
-}  // namespace
+}  // namespace wall
+}  // namespace gm
 
 extern "C" {
 
@@ -608,15 +610,17 @@ gm_status gm_wall_map_check_objects(gm_wall_map *map, uint32_t slot, const gm_wa
     WallCheckSlot &c = map->checks[slot];
     if (!c.res.have) return gm_fail(ctx, GM_ERR_NOT_READY, "gm_wall_map_check_objects: no check was enqueued on this map and slot");
     ObjectWindow win;
-    if (!object_window(map->prm, op, c.anchor, win))
+    if (!object_window(map->prm.n_stations, map->prm.n_sectors, op, c.anchor, win))
         return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_check_objects: the window holds more than GM_WALL_OBJECT_MAX_BLOCKS blocks");
     GMW_OK(set_device(ctx));
     GMW_OK(c.res.wait(ctx));   // that check only: the slot's stream may be busy with the next frame
     const uint32_t n_rows = (uint32_t)c.h_ctr[9];
     const bool rows_fit = !object_of_row || row_capacity >= n_rows;
     // (a check's own rows are never rejected: with nothing to launch they are all outside the window)
-    const gm_status st = objects_run(map, c.stage.p, n_rows, 0u, op, win, info, objects, capacity, n_out, rows_fit ? object_of_row : nullptr,
-                                     "gm_wall_map_check_objects: object buffer too small");
+    info->struct_size = (uint32_t)sizeof(gm_wall_objects_info);
+    const ObjectGrid grid{map->prm.n_sectors, (uint32_t)map->ncell, {}};
+    const gm_status st = objects_run(ctx, map->stream, map->ob, grid, c.stage.p, n_rows, 0u, nullptr, op, win, info, nullptr, objects, capacity,
+                                     n_out, rows_fit ? object_of_row : nullptr, "gm_wall_map_check_objects: object buffer too small");
     if (st != GM_OK) return st;
     if (!rows_fit) return gm_fail(ctx, GM_ERR_CAPACITY, "gm_wall_map_check_objects: object_of_row buffer too small");
     return GM_OK;
@@ -636,7 +640,7 @@ gm_status gm_wall_check_objects(gm_wall_map *map, const gm_wall_check_point *row
         return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_check_objects: struct_size mismatch or a parameter outside its limits");
     if (!objects && capacity) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_check_objects: NULL objects with a capacity");
     ObjectWindow win;
-    if (!object_window(map->prm, op, anchor_station, win))
+    if (!object_window(map->prm.n_stations, map->prm.n_sectors, op, anchor_station, win))
         return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_check_objects: the window holds more than GM_WALL_OBJECT_MAX_BLOCKS blocks");
     GMW_OK(set_device(ctx));
     uint32_t rejected = 0;
@@ -647,11 +651,13 @@ gm_status gm_wall_check_objects(gm_wall_map *map, const gm_wall_check_point *row
             if (wall_object_rejected(b[0], b[1], b[2], b[4], rows[i].cell, wall_check_fix(rows[i].delta), (uint32_t)map->ncell)) ++rejected;
         }
     } else if (n_rows) {
-        GMW_HIP(ctx, map->ob_rows.reserve(n_rows));
-        GMW_HIP(ctx, hipMemcpyAsync(map->ob_rows.p, rows, (size_t)n_rows * sizeof(gm_wall_check_point), hipMemcpyHostToDevice, map->stream));
+        GMW_HIP(ctx, map->ob.rows.reserve(n_rows));
+        GMW_HIP(ctx, hipMemcpyAsync(map->ob.rows.p, rows, (size_t)n_rows * sizeof(gm_wall_check_point), hipMemcpyHostToDevice, map->stream));
     }
-    return objects_run(map, map->ob_rows.p, n_rows, rejected, op, win, info, objects, capacity, n_out, object_of_row,
-                       "gm_wall_check_objects: object buffer too small");
+    info->struct_size = (uint32_t)sizeof(gm_wall_objects_info);
+    const ObjectGrid grid{map->prm.n_sectors, (uint32_t)map->ncell, {}};
+    return objects_run(ctx, map->stream, map->ob, grid, map->ob.rows.p, n_rows, rejected, nullptr, op, win, info, nullptr, objects, capacity,
+                       n_out, object_of_row, "gm_wall_check_objects: object buffer too small");
 }
 
 }  // extern "C"

@@ -25,11 +25,13 @@
 //   9. k_wall_object_rows     only when the caller asks for object_of_row, after the host has uploaded slot -> position.
 // Every store index is a row index < n_rows, an index < 2 NB or a slot < the component count by construction; nothing is
 // clamped.  No floating-point arithmetic after the two fixed-point conversions of a row.
+// The decode and the bodies of the three kernels that read a row (bin, reduce, rows) are gm_wall_objects.hpp's, shared with
+// k_wall_objects_joint.hip (gm_wall_alignment_check_objects: rows decoded onto the alignment's global stations); the
+// launch fronts below pick that file's instantiations when the arguments carry a side table.
 #include <stddef.h>
 #include <string.h>
 
-#include "gm_internal.hpp"
-#include "gm_gridcc.hpp"
+#include "gm_wall_objects.hpp"
 
 namespace gm {
 
@@ -39,45 +41,9 @@ static_assert(offsetof(gm_wall_object, box_min) == 88 && offsetof(gm_wall_object
                   offsetof(gm_wall_object, e_max) == 116 && sizeof(float) == sizeof(uint32_t),
               "the eight floats of gm_wall_object are contiguous");
 
-// A row's index in the per-block arrays, kWallObjectRejected or kWallObjectOutside; p = x y z delta, q = e cell index row
-__device__ __forceinline__ uint32_t wo_decode(const WallObjectArgs &a, uint64_t i, uint4 &p, uint4 &q, long long &dq, uint32_t &j,
-                                              uint32_t &k)
-{
-    const uint4 *r = reinterpret_cast<const uint4 *>(a.rows + i);
-    p = r[0];
-    q = r[1];
-    dq = wall_check_fix(__uint_as_float(p.w));
-    const int32_t c = (int32_t)q.y;
-    j = 0u; k = 0u;
-    if (wall_object_rejected(p.x, p.y, p.z, q.x, c, dq, a.cells)) return kWallObjectRejected;
-    j = (uint32_t)c / a.nsec;
-    k = (uint32_t)c % a.nsec;
-    const uint32_t J = j / a.bs;
-    if (J < a.J0 || J - a.J0 >= a.nJ) return kWallObjectOutside;
-    return (dq > 0 ? a.NB : 0u) + (J - a.J0) * a.NK + k / a.bk;   // < 2 NB
-}
-
 // ---- 2. bin ----
 
-__global__ __launch_bounds__(kCcThreads) void k_wall_object_bin(WallObjectArgs a)
-{
-    uint32_t rej = 0u, outside = 0u;
-    for (uint64_t i = (uint64_t)blockIdx.x * kCcThreads + threadIdx.x; i < a.n_rows; i += (uint64_t)gridDim.x * kCcThreads) {
-        uint4 p, q;
-        long long dq;
-        uint32_t j, k;
-        const uint32_t b = wo_decode(a, i, p, q, dq, j, k);
-        if (b == kWallObjectRejected) ++rej;
-        else if (b == kWallObjectOutside) ++outside;
-        else atomicAdd(&a.cnt[b], 1u);
-    }
-    rej = wave_sum(rej);
-    outside = wave_sum(outside);
-    if (lane_id() == 0) {
-        if (rej) atomicAdd(&a.ctr[0], (unsigned long long)rej);
-        if (outside) atomicAdd(&a.ctr[1], (unsigned long long)outside);
-    }
-}
+__global__ __launch_bounds__(kCcThreads) void k_wall_object_bin(WallObjectArgs a) { wo_bin<false>(a); }
 
 // ---- 3. tiles ----
 
@@ -159,80 +125,7 @@ __global__ __launch_bounds__(kCcThreads) void k_wall_object_blocks(WallObjectArg
 
 // ---- 7. reduce ----
 
-__global__ __launch_bounds__(kCcThreads) void k_wall_object_reduce(WallObjectArgs a)
-{
-    const uint32_t nsec = a.nsec, half = nsec / 2u;
-    const int lane = lane_id();
-    for (uint64_t i0 = (uint64_t)blockIdx.x * kCcThreads + (threadIdx.x & ~(uint32_t)(kWave - 1)); i0 < a.n_rows;
-         i0 += (uint64_t)gridDim.x * kCcThreads) {
-        const uint64_t i = i0 + lane;
-        int slot = -1;
-        uint32_t pts = 0u, smin = 0u, smax = 0u, kmin = 0u, kmax = 0u, tmin = 0u, tmax = 0u;
-        uint32_t key[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};   // ~ordered(x, y, z), ordered(x, y, z), ~ordered(e), ordered(e)
-        unsigned long long sum = 0ull, sx = 0ull, sy = 0ull, sz = 0ull, peak = 0ull;
-        if (i < a.n_rows) {
-            uint4 p, q;
-            long long dq;
-            uint32_t j, k;
-            const uint32_t b = wo_decode(a, i, p, q, dq, j, k);
-            const uint32_t r = b < kWallObjectOutside ? a.parent[b] : kCcNone;
-            if (r != kCcNone) {
-                slot = (int)a.slot[r];
-                const uint32_t t = k + half < nsec ? k + half : k + half - nsec;
-                const unsigned long long mag = dq < 0 ? 0ull - (unsigned long long)dq : (unsigned long long)dq;
-                pts = 1u;
-                smin = ~j; smax = j; kmin = ~k; kmax = k; tmin = ~t; tmax = t;
-                const uint32_t ox = float_to_ordered(__uint_as_float(p.x)), oy = float_to_ordered(__uint_as_float(p.y)),
-                               oz = float_to_ordered(__uint_as_float(p.z)), oe = float_to_ordered(__uint_as_float(q.x));
-                key[0] = ~ox; key[1] = ~oy; key[2] = ~oz; key[3] = ox; key[4] = oy; key[5] = oz; key[6] = ~oe; key[7] = oe;
-                sum = (unsigned long long)dq;
-                sx = (unsigned long long)wall_object_fix16(__uint_as_float(p.x));
-                sy = (unsigned long long)wall_object_fix16(__uint_as_float(p.y));
-                sz = (unsigned long long)wall_object_fix16(__uint_as_float(p.z));
-                peak = ((mag > 0xFFFFFFFFull ? 0xFFFFFFFFull : mag) << 32) | (uint32_t)~q.z;
-            }
-        }
-        const WaveRuns run = wave_runs(slot);
-        if (run.any) {
-#pragma unroll
-            for (int o = 1; o < kWave; o <<= 1) {
-                const uint32_t oc = __shfl_down(pts, o, kWave), o1 = __shfl_down(smin, o, kWave), o2 = __shfl_down(smax, o, kWave),
-                               o3 = __shfl_down(kmin, o, kWave), o4 = __shfl_down(kmax, o, kWave), o5 = __shfl_down(tmin, o, kWave),
-                               o6 = __shfl_down(tmax, o, kWave);
-                uint32_t ok[8];
-#pragma unroll
-                for (int c = 0; c < 8; ++c) ok[c] = __shfl_down(key[c], o, kWave);
-                const unsigned long long os = __shfl_down(sum, o, kWave), ox = __shfl_down(sx, o, kWave), oy = __shfl_down(sy, o, kWave),
-                                         oz = __shfl_down(sz, o, kWave), op = __shfl_down(peak, o, kWave);
-                if (run.lane + o <= run.tail) {
-                    pts += oc; sum += os; sx += ox; sy += oy; sz += oz;
-                    smin = smin > o1 ? smin : o1; smax = smax > o2 ? smax : o2;
-                    kmin = kmin > o3 ? kmin : o3; kmax = kmax > o4 ? kmax : o4;
-                    tmin = tmin > o5 ? tmin : o5; tmax = tmax > o6 ? tmax : o6;
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) key[c] = key[c] > ok[c] ? key[c] : ok[c];
-                    peak = peak > op ? peak : op;
-                }
-            }
-        }
-        if (slot >= 0 && !run.dup) {
-            WallObjectAcc *r = &a.acc[slot];
-            atomicAdd(&r->points, (unsigned long long)pts);
-            atomicAdd(&r->sum_delta, sum);
-            atomicAdd(&r->sum_x, sx); atomicAdd(&r->sum_y, sy); atomicAdd(&r->sum_z, sz);
-            atomicMax(&r->st_min_inv, smin); atomicMax(&r->st_max, smax);
-            atomicMax(&r->k_min_inv, kmin); atomicMax(&r->k_max, kmax);
-            atomicMax(&r->t_min_inv, tmin); atomicMax(&r->t_max, tmax);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                atomicMax(&r->box_min_inv[c], key[c]);
-                atomicMax(&r->box_max[c], key[3 + c]);
-            }
-            atomicMax(&r->e_min_inv, key[6]); atomicMax(&r->e_max, key[7]);
-            atomicMax(&r->peak_key, peak);
-        }
-    }
-}
+__global__ __launch_bounds__(kCcThreads) void k_wall_object_reduce(WallObjectArgs a) { wo_reduce<false>(a); }
 
 // ---- 8. select ----
 
@@ -291,21 +184,12 @@ __global__ __launch_bounds__(kCcThreads) void k_wall_object_select(WallObjectArg
 
 // ---- 9. rows ----
 
-__global__ __launch_bounds__(kCcThreads) void k_wall_object_rows(WallObjectArgs a)
-{
-    for (uint64_t i = (uint64_t)blockIdx.x * kCcThreads + threadIdx.x; i < a.n_rows; i += (uint64_t)gridDim.x * kCcThreads) {
-        uint4 p, q;
-        long long dq;
-        uint32_t j, k;
-        const uint32_t b = wo_decode(a, i, p, q, dq, j, k);
-        const uint32_t r = b < kWallObjectOutside ? a.parent[b] : kCcNone;
-        a.object_of_row[i] = r != kCcNone ? a.pos[a.slot[r]] : -1;
-    }
-}
+__global__ __launch_bounds__(kCcThreads) void k_wall_object_rows(WallObjectArgs a) { wo_rows<false>(a); }
 
 void launch_wall_object_label(const WallObjectArgs &a, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_wall_object_bin, dim3(cc_blocks(a.n_rows)), dim3(kCcThreads), 0, s, a);
+    if (a.sides.n_sides) launch_wall_object_bin_joint(a, s);
+    else hipLaunchKernelGGL(k_wall_object_bin, dim3(cc_blocks(a.n_rows)), dim3(kCcThreads), 0, s, a);
     hipLaunchKernelGGL(k_wall_object_tiles, dim3(a.tiles_s * a.tiles_k), dim3(kCcThreads), 0, s, a);
     hipLaunchKernelGGL(k_wall_object_seams, dim3(cc_blocks(2u * cc_seam_count(a.nJ, a.NK, a.tiles_s, a.tiles_k))), dim3(kCcThreads),
                        0, s, a);
@@ -314,12 +198,14 @@ void launch_wall_object_label(const WallObjectArgs &a, hipStream_t s)
 void launch_wall_object_reduce(const WallObjectArgs &a, hipStream_t s)
 {
     hipLaunchKernelGGL(k_wall_object_blocks, dim3(cc_blocks(2ull * a.NB)), dim3(kCcThreads), 0, s, a);
-    hipLaunchKernelGGL(k_wall_object_reduce, dim3(cc_blocks(a.n_rows)), dim3(kCcThreads), 0, s, a);
+    if (a.sides.n_sides) launch_wall_object_reduce_joint(a, s);
+    else hipLaunchKernelGGL(k_wall_object_reduce, dim3(cc_blocks(a.n_rows)), dim3(kCcThreads), 0, s, a);
     hipLaunchKernelGGL(k_wall_object_select, dim3(cc_blocks(a.ncomp)), dim3(kCcThreads), 0, s, a);
 }
 void launch_wall_object_rows(const WallObjectArgs &a, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_wall_object_rows, dim3(cc_blocks(a.n_rows)), dim3(kCcThreads), 0, s, a);
+    if (a.sides.n_sides) launch_wall_object_rows_joint(a, s);
+    else hipLaunchKernelGGL(k_wall_object_rows, dim3(cc_blocks(a.n_rows)), dim3(kCcThreads), 0, s, a);
 }
 
 }  // namespace gm

@@ -12,7 +12,7 @@ void Processor::check(gm_status s, const char *what)
 }
 
 Processor::Processor(double b, double leaf, double r, double wf, int device, unsigned flags)
-    : ctx_(0), grp_(0), cur_(0), cur_slot_(0), n_slots_(1), next_slot_(0), pending_(0), wall_(0), alignment_(0), newest_slot_(-1), check_slot_(-1)
+    : ctx_(0), grp_(0), cur_(0), cur_slot_(0), n_slots_(1), next_slot_(0), pending_(0), wall_(0), alignment_(0), newest_slot_(-1), check_slot_(-1), al_check_slot_(-1)
 {
     gm_config cfg;
     gm_default_config(&cfg);
@@ -27,7 +27,7 @@ Processor::Processor(double b, double leaf, double r, double wf, int device, uns
 Processor::Processor(double b, double leaf, double r, double wf, const std::vector<int> &devices, unsigned flags,
                      unsigned slots_per_device)
     : ctx_(0), grp_(0), cur_(0), cur_slot_(0), n_slots_(slots_per_device ? slots_per_device : 1), next_slot_(0), pending_(0), wall_(0), alignment_(0),
-      newest_slot_(-1), check_slot_(-1)
+      newest_slot_(-1), check_slot_(-1), al_check_slot_(-1)
 {
     if (devices.empty()) throw Error(GM_ERR_INVALID_ARG, "Processor: empty device list");
     gm_config cfg;
@@ -391,6 +391,7 @@ void Processor::createWallAlignment(const gm_wall_params &params, const std::vec
           "createWallAlignment");
     if (alignment_) gm_wall_alignment_destroy(alignment_);
     alignment_ = al;
+    al_check_slot_ = -1;
 }
 
 gm_wall_alignment_add_info Processor::addToWallAlignment(const double pose[12])
@@ -437,6 +438,7 @@ std::vector<gm_wall_check_point> Processor::checkWallAlignment(const double pose
     if (newest_slot_ < 0) throw Error(GM_ERR_NOT_READY, "checkWallAlignment: no frame yet");
     const unsigned slot = (unsigned)newest_slot_;
     check(gm_wall_alignment_check_frame(alignment_, ctx_, slot, pose, &prm, plan), "checkWallAlignment");
+    al_check_slot_ = (int)slot;
     gm_wall_alignment_check_info local;
     gm_wall_alignment_check_info *ip = info ? info : &local;
     uint32_t count = 0;
@@ -445,6 +447,22 @@ std::vector<gm_wall_check_point> Processor::checkWallAlignment(const double pose
     if (count) check(gm_wall_alignment_get_check(alignment_, slot, ip, &points[0], count, &count), "checkWallAlignment");
     points.resize(count);
     return points;
+}
+
+std::vector<gm_wall_object> Processor::wallAlignmentCheckObjects(const gm_wall_object_params &prm, gm_wall_alignment_objects_info *info)
+{
+    if (!alignment_) throw Error(GM_ERR_NOT_READY, "wallAlignmentCheckObjects: createWallAlignment first");
+    if (al_check_slot_ < 0) throw Error(GM_ERR_NOT_READY, "wallAlignmentCheckObjects: checkWallAlignment first");
+    gm_wall_alignment_objects_info local;
+    gm_wall_alignment_objects_info *ip = info ? info : &local;
+    uint32_t count = 0;
+    check(gm_wall_alignment_check_objects(alignment_, (unsigned)al_check_slot_, &prm, ip, 0, 0, &count, 0, 0), "wallAlignmentCheckObjects");
+    std::vector<gm_wall_object> objects(count);
+    if (count)
+        check(gm_wall_alignment_check_objects(alignment_, (unsigned)al_check_slot_, &prm, ip, &objects[0], count, &count, 0, 0),
+              "wallAlignmentCheckObjects");
+    objects.resize(count);
+    return objects;
 }
 
 gm_wall_alignment_add_info Processor::addToWallAlignmentChecked(const double pose[12], const gm_wall_add_checked_params &prm,

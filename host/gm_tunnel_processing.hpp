@@ -257,6 +257,12 @@ public:
     // (and the call waits for them).  GM_ERR_NOT_READY without a check of this frame through the alignment.
     gm_wall_alignment_add_info addToWallAlignmentChecked(const double pose[12], const gm_wall_add_checked_params &prm,
                                                          gm_wall_add_checked_info *info = nullptr);
+    // the objects of the last checkWallAlignment's changed points on the alignment's global station grid, ascending by
+    // (label, sign) (gm_wall_alignment_check_objects: a count query, then the sized call; the rows stay on the device): an
+    // object across a joint plane is one object, and station_min / station_max are global stations
+    // (gm_wall_alignment_object_metrics gives the chainage and the elements).  The order per frame on an alignment:
+    // locateWallAlignment, alignWallAlignment, checkWallAlignment, wallAlignmentCheckObjects, addToWallAlignmentChecked.
+    std::vector<gm_wall_object> wallAlignmentCheckObjects(const gm_wall_object_params &prm, gm_wall_alignment_objects_info *info = nullptr);
     gm_wall_alignment *wallAlignment() { return alignment_; }
 
     gm_ctx *ctx() { return ctx_; }
@@ -273,6 +279,7 @@ private:
     gm_wall_alignment *alignment_;             // createWallAlignment (freed with the context)
     int newest_slot_;                          // slot of the frame submitted last (-1: none yet)
     int check_slot_;                           // the slot of the last checkWallMap, -1 before it
+    int al_check_slot_;                        // the slot of the last checkWallAlignment, -1 before it
     struct CloudBuf { gm_ctx *ctx; unsigned slot; float *rows; unsigned cap; };
     std::vector<CloudBuf> cloud_bufs_;         // enableCloudOutput: one per (device, slot)
     void growCloudOutput(unsigned n_points);

@@ -1,8 +1,9 @@
 // gm_wall_alignment_host_test -- the device-free calls of the wall alignment (gm_wall_alignment_check, _element_params,
-// _project, _point, _window, _add_plan) as a stand-alone program: linked with gm_wall_host.hip and
+// _project, _point, _window, _add_plan, _object_window, _object_metrics) as a stand-alone program: linked with gm_wall_host.hip and
 // gm_wall_alignment_host.hip alone and built with AddressSanitizer and UBSan by tests/test_host_wall_alignment.py.
 // Prints "gm_wall_alignment_host_test ok" on success.
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -110,6 +111,39 @@ int main()
     EXPECT(gm_wall_alignment_add_plan(&prm, &el[0], n, pose, 9.0, &info) == GM_ERR_UNSUPPORTED);
     pose[0] = 2.0;
     EXPECT(gm_wall_alignment_add_plan(&prm, &el[0], n, pose, 5.0, &info) == GM_ERR_INVALID_ARG);
+    // the object window and metrics on the global station grid (bases 0, 40, 88, 128, 176; total 216), anchors at the
+    // ends of int64 included
+    pose[0] = 1.0; pose[3] = 9.0;
+    EXPECT(gm_wall_alignment_add_plan(&prm, &el[0], n, pose, 1.0, &info) == GM_OK && info.n_sides == 2);
+    gm_wall_object_params op;
+    gm_wall_object_default_params(&op);
+    op.block_stations = 3;
+    op.half_window_stations = 10;
+    gm_wall_alignment_objects_info oi;
+    EXPECT(gm_wall_alignment_object_window(&prm, &el[0], n, &info, &op, &oi) == GM_OK);
+    EXPECT(oi.struct_size == sizeof(oi) && oi.anchor_global == 36 && oi.total == 216 && oi.side_first[0] == 0 && oi.side_first[1] == 40 &&
+           oi.station0 == 24 && oi.n_stations == 24 && oi.blocks_stations == 8 && oi.n_sides == 2 && oi.in_object == 0);
+    gm_wall_alignment_add_info far = info;
+    far.element = 1;
+    far.side_anchor[1] = INT64_MAX;
+    EXPECT(gm_wall_alignment_object_window(&prm, &el[0], n, &far, &op, &oi) == GM_OK && oi.blocks_stations == 0 && oi.anchor_global == INT64_MAX);
+    far.side_anchor[1] = INT64_MIN;
+    EXPECT(gm_wall_alignment_object_window(&prm, &el[0], n, &far, &op, &oi) == GM_OK && oi.blocks_stations == 0);
+    far.side_anchor[1] = 175;   // G_f = 215, the last station
+    EXPECT(gm_wall_alignment_object_window(&prm, &el[0], n, &far, &op, &oi) == GM_OK && oi.station0 + oi.n_stations == 216);
+    far.side_element[1] = 2;
+    EXPECT(gm_wall_alignment_object_window(&prm, &el[0], n, &far, &op, &oi) == GM_ERR_INVALID_ARG);
+    EXPECT(gm_wall_alignment_object_window(&prm, &el[0], n, 0, &op, &oi) == GM_ERR_INVALID_ARG);
+    gm_wall_object rec;
+    std::memset(&rec, 0, sizeof(rec));
+    rec.points = 3; rec.station_min = 39; rec.station_max = 88; rec.sector_max = 2; rec.sector_max_turned = prm.n_sectors / 2 + 2;
+    rec.sector_min_turned = prm.n_sectors / 2;
+    struct gm_wall_alignment_object_metrics om;
+    EXPECT(gm_wall_alignment_object_metrics(&prm, &el[0], n, &op, &rec, &om) == GM_OK);
+    EXPECT(om.element_from == 0 && om.station_from == 39 && om.element_to == 2 && om.station_to == 0 &&
+           om.chainage_from == prm.t_min + 39.0 * prm.station_length && om.chainage_to == prm.t_min + 89.0 * prm.station_length);
+    rec.station_max = 216;
+    EXPECT(gm_wall_alignment_object_metrics(&prm, &el[0], n, &op, &rec, &om) == GM_ERR_INVALID_ARG);
     // an alignment that turns 143 degrees: a point beyond the arc lies behind the first joint's plane and is element 2's
     std::vector<gm_wall_element> turn;
     turn.push_back(element(GM_WALL_ELEMENT_STRAIGHT, 80, 0.0, 0.0));

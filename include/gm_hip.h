@@ -2025,10 +2025,9 @@ gm_status gm_wall_clothoid_point(const gm_wall_params *params, const gm_wall_clo
  * and every point is classed exactly once.  The LDS table's GM_SURF_MAX_CELLS cells are dealt to the sides in order (a
  * side's window: the stations of its own add's window that lie in the element, cut to what is left); a mapped point outside
  * its side's window goes to the map directly, which affects speed only.
- * Out of scope: check objects through the alignment (they remain calls on an element map, gm_wall_alignment_map); element
- * maps of different grids; closed loops.  The locate is gm_wall_alignment_locate_*, the align (chainage and roll)
- * gm_wall_alignment_align_*, the check and the checked add gm_wall_alignment_check_* and gm_wall_alignment_add_*_checked
- * below. */
+ * Out of scope: element maps of different grids; closed loops.  The locate is gm_wall_alignment_locate_*, the align
+ * (chainage and roll) gm_wall_alignment_align_*, the check and the checked add gm_wall_alignment_check_* and
+ * gm_wall_alignment_add_*_checked, a check's objects gm_wall_alignment_check_objects below. */
 #define GM_WALL_ALIGNMENT_MAX_ELEMENTS 256
 #define GM_WALL_JOINT_MAX_SIDES 4
 enum { GM_WALL_ELEMENT_STRAIGHT = 0, GM_WALL_ELEMENT_ARC = 1, GM_WALL_ELEMENT_CLOTHOID = 2 };
@@ -2453,6 +2452,103 @@ gm_status gm_wall_alignment_align_points(gm_wall_alignment *alignment, const flo
                                          gm_wall_alignment_align_plan_info *plan, gm_wall_alignment_align_info *info,
                                          gm_wall_align_score *scores, uint32_t capacity, uint32_t *n_out, float *residual,
                                          int32_t *cell, int32_t *element);
+
+/* ---- a check's changed points as objects on a wall alignment (gm_wall_alignment_check_objects) ----------------------------
+ * gm_wall_map_check_objects on the alignment: the same parameters (gm_wall_object_params), the same 128-byte record
+ * (gm_wall_object), on the alignment's GLOBAL station grid, so that an object that lies across a joint plane is ONE object
+ * and keeps its label whatever sides the frame's plan happened to have.  Per frame on an alignment:
+ * gm_wall_alignment_locate_frame -> gm_wall_alignment_align_frame -> gm_wall_alignment_check_frame ->
+ * gm_wall_alignment_check_objects -> gm_wall_alignment_add_frame_checked.
+ *   global station  base_i, G = base_i + j and total as in the align section above.
+ *   size          GM_ERR_UNSUPPORTED unless total <= 2^32 - 1 and ceil(total / bs) NK <= 2^32 - 1: G and the label are then
+ *                 32-bit and the kernels need no 64-bit division.
+ *   per row       side = GM_WALL_ROW_SIDE(cell), c = GM_WALL_ROW_CELL(cell).  A row is REJECTED if side >= n_sides of the
+ *                 check's plan, if c >= n_stations_e n_sectors of that side's element e = side_element[side], if dq == 0 or
+ *                 if any of x, y, z, e is not finite.  Otherwise j = c / n_sectors, k = c % n_sectors, G = base_e + j.  The
+ *                 side is checked before it picks anything: no load or store index depends on an unchecked side.
+ *   blocks, window, planes, neighbours, component, classes, order, object_of_row
+ *                 the map rule's (gm_wall_map_check_objects), word for word, on a virtual map of `total` stations with G in
+ *                 place of j.  Blocks are anchored on global station 0: J = G / bs, so a block may hold stations of two
+ *                 elements when base_i % bs != 0; label = J NK + K.  The anchor is G_f = base_e + side_anchor[e] of the
+ *                 sensor's side, in int64; the window is [max(0, G_f - H), min(total, G_f + H)), widened to block rows;
+ *                 above GM_WALL_OBJECT_MAX_BLOCKS blocks GM_ERR_INVALID_ARG.
+ *   record        station_min / station_max are global stations; everything else as on a map.  The sector extents are
+ *                 continuous across joints because (u, v) turns rigidly with the section.
+ * So the result is what gm_wall_check_objects gives on ONE straight map of `total` stations fed the same rows with cell
+ * rewritten to G n_sectors + k, around the anchor G_f -- byte for byte wherever such a map can exist
+ * (total n_sectors <= 2^24); the decode lives in the kernel so that the call also works where none can.  A one-side check
+ * on element 0 gives that element map's gm_wall_map_check_objects records byte for byte; on element i with base_i % bs == 0
+ * the same records with label shifted by (base_i / bs) NK and the station extents by base_i.
+ * On the device: gm_wall_map_check_objects' launches; the three kernels that read a row (bin, reduce, rows) are joint
+ * instantiations of the map's code behind a decode that reads a by-value side table, the others are the map's own. */
+typedef struct gm_wall_alignment_objects_info {   /* 136 bytes; the first 64 are gm_wall_objects_info's */
+    uint32_t struct_size;           /* = sizeof(gm_wall_alignment_objects_info), filled by the library */
+    uint32_t n_rows;                /* = the sum of the five classes below */
+    uint32_t station0, n_stations;  /* the block-aligned window in GLOBAL stations, clipped to [0, total); 0, 0 when empty */
+    uint32_t blocks_stations, blocks_sectors;
+    uint32_t rejected, outside_window, sparse, small, in_object;
+    uint32_t flagged_pos, flagged_neg;
+    uint32_t components;
+    uint32_t objects;
+    uint32_t reserved;              /* 0 */
+    uint32_t element;               /* the sensor's element */
+    uint32_t n_sides;               /* of the check's plan */
+    int64_t  anchor_global;         /* G_f */
+    int64_t  total;                 /* the alignment's stations */
+    uint32_t side_element[GM_WALL_JOINT_MAX_SIDES];   /* 0 from n_sides on */
+    uint32_t side_first[GM_WALL_JOINT_MAX_SIDES];     /* base of each side's element */
+    uint32_t side_rows[GM_WALL_JOINT_MAX_SIDES];      /* the rows of each side that were not rejected; 0 from n_sides on */
+} gm_wall_alignment_objects_info;
+
+/* (a struct tag only, no typedef: the function of the same name below fills it) */
+struct gm_wall_alignment_object_metrics {   /* 112 bytes; the first 96 are gm_wall_object_metrics' */
+    double centroid[3];
+    double mean_m;
+    double peak_m;
+    double size[3];
+    double chainage_from;           /* t_min + station_min * station_length, alignment chainage */
+    double chainage_to;             /* t_min + (station_max + 1) * station_length */
+    double angle_from_deg;
+    double angle_to_deg;
+    uint32_t element_from, element_to;   /* the elements of station_min and of station_max */
+    uint32_t station_from, station_to;   /* those stations inside them: station_min - base_from, station_max - base_to */
+};
+
+/* The objects of the last check enqueued THROUGH THE ALIGNMENT on (alignment, slot), ascending by (label, sign).  It finds
+ * the rows wherever they are staged (the alignment's buffer, or after a one-side check the element map's), by
+ * gm_wall_alignment_add_frame_checked's rules, waits for that check's event only, runs over the staged rows where they lie
+ * -- no row crosses PCIe -- and blocks.  It may be repeated with other parameters and changes neither the maps nor the
+ * rows.  info is required; count queries, GM_ERR_CAPACITY and the NULL rules are gm_wall_map_check_objects'.  Zero rows or
+ * an empty window launch nothing.  Scratch (gm_wall_map_check_objects' amounts) belongs to the alignment: allocated by
+ * the first call, kept grow-only, freed with the alignment; an alignment that never asks allocates nothing.  The tile shape
+ * (GM_WALL_OBJECT_TILE, read at gm_wall_alignment_create) changes nothing in the result.
+ * GM_ERR_NOT_READY: no check was enqueued on (alignment, slot), or a check on the element map itself has since replaced a
+ * one-side check's rows.  GM_ERR_UNSUPPORTED: the size rule.  GM_ERR_INVALID_ARG: as gm_wall_map_check_objects. */
+gm_status gm_wall_alignment_check_objects(gm_wall_alignment *alignment, uint32_t slot, const gm_wall_object_params *prm,
+                                          gm_wall_alignment_objects_info *info, gm_wall_object *objects, uint32_t capacity,
+                                          uint32_t *n_out, int32_t *object_of_row, uint32_t row_capacity);
+/* The same kernels as one blocking stage call on n_rows host rows in any order.  The sides and the anchor are taken from
+ * plan: n_sides, side_element, side_anchor, element.  object_of_row (may be NULL) holds n_rows entries.  Fed the rows and
+ * the plan of gm_wall_alignment_get_check it returns gm_wall_alignment_check_objects' bytes.  GM_ERR_INVALID_ARG as above,
+ * and for rows NULL with n_rows > 0, a NULL plan, a plan whose struct_size is wrong, whose sides are not 1 ..
+ * GM_WALL_JOINT_MAX_SIDES consecutive ascending elements of this alignment, or whose element is not among them. */
+gm_status gm_wall_alignment_check_objects_rows(gm_wall_alignment *alignment, const gm_wall_check_point *rows, uint32_t n_rows,
+                                               const gm_wall_alignment_add_info *plan, const gm_wall_object_params *prm,
+                                               gm_wall_alignment_objects_info *info, gm_wall_object *objects, uint32_t capacity,
+                                               uint32_t *n_out, int32_t *object_of_row);
+/* Host only, no context: an info's window fields, element, n_sides, anchor_global, total, side_element and side_first
+ * exactly as the device calls report them for this plan (the counts stay 0).  prm NULL: the defaults.  Refusals: the
+ * alignment's, the plan's and the parameters' (GM_ERR_INVALID_ARG), the size rule (GM_ERR_UNSUPPORTED). */
+gm_status gm_wall_alignment_object_window(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n,
+                                          const gm_wall_alignment_add_info *plan, const gm_wall_object_params *prm,
+                                          gm_wall_alignment_objects_info *info);
+/* Host only: gm_wall_object_metrics' derivation for a record on the global grid, with the template's t_min and
+ * station_length (every operation rounded once), and the elements and the stations inside them of the record's two station
+ * extents.  op may be NULL.  GM_ERR_INVALID_ARG: NULL, the alignment's refusals, gm_wall_object_metrics' refusals, a
+ * station extent outside [0, total). */
+gm_status gm_wall_alignment_object_metrics(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n,
+                                           const gm_wall_object_params *op, const gm_wall_object *o,
+                                           struct gm_wall_alignment_object_metrics *out);
 
 /* "Compressed map" record of a completed slot.  The reference defines no such
  * output; this is a build-defined format: header, primitive records,
