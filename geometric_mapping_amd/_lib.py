@@ -529,6 +529,19 @@ class WallAlignmentObjectMetrics(C.Structure):
                                              ("station_from", C.c_uint32), ("station_to", C.c_uint32)]
 
 
+class WallAlignmentRegionsInfo(C.Structure):
+    _fields_ = WallRegionsInfo._fields_ + [("total", C.c_int64), ("n_pieces", C.c_uint32), ("element_from", C.c_uint32),
+                                           ("element_to", C.c_uint32), ("station_from", C.c_uint32), ("station_to", C.c_uint32),
+                                           ("reserved", C.c_uint32)]
+
+
+class WallAlignmentRegionMetrics(C.Structure):
+    _fields_ = WallRegionMetrics._fields_ + [("element_from", C.c_uint32), ("element_to", C.c_uint32),
+                                             ("station_from", C.c_uint32), ("station_to", C.c_uint32),
+                                             ("peak_element", C.c_uint32), ("peak_station", C.c_uint32),
+                                             ("peak_sector", C.c_uint32), ("reserved", C.c_uint32), ("peak_point", C.c_double * 3)]
+
+
 class GmError(RuntimeError):
     def __init__(self, status, message):
         super().__init__(f"libgm_hip: status {status}: {message}")
@@ -627,6 +640,7 @@ def load():
     waprmp, wascp, wainfop = map(P, (WallAlignParams, WallAlignScore, WallAlignInfo))
     woprmp, wobjp, woinfop, wometp = map(P, (WallObjectParams, WallObject, WallObjectsInfo, WallObjectMetrics))
     waloinfop, walometp = P(WallAlignmentObjectsInfo), P(WallAlignmentObjectMetrics)
+    walrinfop, walrmetp = P(WallAlignmentRegionsInfo), P(WallAlignmentRegionMetrics)
     proto = {
         "gm_create": (C.c_int, [cfgp, C.POINTER(vp)]),
         "gm_destroy": (None, [vp]),
@@ -726,6 +740,9 @@ def load():
         "gm_wall_alignment_check_objects_rows": (C.c_int, [vp, wkptp, u32, waladdp, woprmp, waloinfop, wobjp, u32, u32p, i32p]),
         "gm_wall_alignment_object_window": (C.c_int, [wprmp, welp, u32, waladdp, woprmp, waloinfop]),
         "gm_wall_alignment_object_metrics": (C.c_int, [wprmp, welp, u32, woprmp, wobjp, walometp]),
+        "gm_wall_alignment_regions": (C.c_int, [vp, vp, u32, u32, wrprmp, walrinfop, wregp, u32, u32p, i32p]),
+        "gm_wall_alignment_region_window": (C.c_int, [wprmp, welp, u32, u32, u32, walrinfop]),
+        "gm_wall_alignment_region_metrics": (C.c_int, [wprmp, welp, u32, wregp, walrmetp]),
         "gm_wall_alignment_info": (C.c_int, [vp, waltotp]),
         "gm_wall_map_add_frame": (C.c_int, [vp, vp, u32, dp, waddp]),
         "gm_wall_map_add_points": (C.c_int, [vp, fp, u32, u8p, dp, waddp, fp, i32p]),

@@ -1843,6 +1843,83 @@ class _AlignmentObjects:
         return self._objects(call, len(r), True, params)
 
 
+_ALIGNMENT_REGION_INFO = _REGION_INFO + ("total", "n_pieces", "element_from", "element_to", "station_from", "station_to")
+
+
+def _alignment_regions_info(i):
+    """The dict of a gm_wall_alignment_regions_info: WallMap.regions()'s keys (station0 / n_stations global) and total,
+    n_pieces, element_from, element_to, station_from, station_to."""
+    d = _ints(i, _ALIGNMENT_REGION_INFO)
+    d["cell_area"] = float(i.cell_area)
+    return d
+
+
+class _AlignmentRegions:
+    """gm_wall_alignment_regions and its kin for one WallAlignmentRule or WallAlignment `al`, bound onto the instance as
+    _AlignmentObjects' methods are and for the same reason (al.region_window, al.region_metrics; on a WallAlignment also
+    al.regions); these calls' trace is tests/test_wall_alignment_regions_abi.py's."""
+
+    RULE, DEVICE = ("region_window", "region_metrics"), ("regions",)
+
+    def __init__(self, al):
+        self._al = al
+        self.bind(self.RULE)
+
+    def bind(self, names):
+        for k in names:
+            setattr(self._al, k, getattr(self, k))
+
+    def total(self):
+        return sum(int(self._al._els[i].n_stations) for i in range(self._al.n_elements))
+
+    def region_window(self, station0, n):
+        """gm_wall_alignment_region_window: the info dict (_alignment_regions_info, threshold_q and the counts 0) of
+        gm_wall_alignment_regions on the global stations [station0, station0 + n); GmError with GM_ERR_UNSUPPORTED for
+        an alignment or a window beyond the size rule."""
+        info = _lib.WallAlignmentRegionsInfo()
+        st = self._al._L.gm_wall_alignment_region_window(*self._al._head(), int(station0), int(n), C.byref(info))
+        if st != _lib.GM_OK:
+            raise _lib.GmError(st, "gm_wall_alignment_region_window refused the arguments")
+        return _alignment_regions_info(info)
+
+    def region_metrics(self, region):
+        """gm_wall_alignment_region_metrics of one REGION record on the global station grid: wall_region_metrics' keys in
+        alignment chainage, element_from, element_to, station_from, station_to, peak_element, peak_station, peak_sector
+        and peak_point float64 [3], the design position of the peak."""
+        r = np.ascontiguousarray(np.asarray(region, dtype=REGION).reshape(1))
+        out = _lib.WallAlignmentRegionMetrics()
+        st = self._al._L.gm_wall_alignment_region_metrics(*self._al._head(), r.ctypes.data_as(C.POINTER(_lib.WallRegion)), C.byref(out))
+        if st != _lib.GM_OK:
+            raise _lib.GmError(st, "gm_wall_alignment_region_metrics refused the record")
+        d = {k: (float if t is C.c_double else int)(getattr(out, k)) for k, t in out._fields_ if k not in ("peak_point", "reserved")}
+        d["peak_point"] = np.array(out.peak_point[:], dtype=np.float64)
+        return d
+
+    def regions(self, station0=0, n=None, baseline=None, labels=False, **params):
+        """gm_wall_alignment_regions: the connected deviation regions of the global stations [station0, station0 + n)
+        (n None: to the alignment's end) against the design or, with `baseline` (another WallAlignment of this context
+        with the same template and elements), against that earlier epoch; a region across a joint is one region.  Returns
+        WallMap.regions' tuple: (info dict, REGION records ascending by label, metrics list of dicts from region_metrics,
+        labels (n, n_sectors) int32 or None)."""
+        al = self._al
+        s0 = int(station0)
+        n = self.total() - s0 if n is None else int(n)
+        if s0 < 0 or n < 0:
+            raise ValueError("the window leaves the alignment")
+        nsec = int(al.prm.n_sectors)
+        p = _wall_region_params(**params)
+        bh = baseline._h() if baseline is not None else None
+        info, got = _lib.WallAlignmentRegionsInfo(), C.c_uint32(0)
+        lab = np.empty(max(n * nsec, 1), dtype=np.int32) if labels else None
+        lp = lab.ctypes.data_as(C.POINTER(C.c_int32)) if labels else None
+        # a count query, then the list (the labels travel with the second call only)
+        reg = _sized(lambda rp, cap, sized: al._ctx._check(al._L.gm_wall_alignment_regions(
+            al._h(), bh, s0, n, C.byref(p), C.byref(info), rp, cap, C.byref(got), lp if sized else None)),
+            _lib.WallRegion, got, lambda cap: cap or labels)
+        metrics = [self.region_metrics(reg[i]) for i in range(len(reg))]
+        return _alignment_regions_info(info), reg, metrics, (lab[:n * nsec].reshape(n, nsec).copy() if labels else None)
+
+
 class WallAlignmentRule:
     """The device-free half of a wall alignment (gm_wall_alignment_check, _element_params, _project, _point, _window,
     _add_plan; include/gm_hip.h states the rule): a template gm_wall_params and the elements.  Needs no context."""
@@ -1854,6 +1931,7 @@ class WallAlignmentRule:
         self.prm = WallMap.params(**params)
         self._els, self.n_elements = _wall_elements(elements)
         self._object_calls = _AlignmentObjects(self)
+        self._region_calls = _AlignmentRegions(self)
 
     def _head(self):
         return C.byref(self.prm), self._els, self.n_elements
@@ -1975,6 +2053,7 @@ class WallAlignment(WallAlignmentRule, _FrameLoop):
         self._al = h
         self._maps = {}
         self._object_calls.bind(_AlignmentObjects.DEVICE)
+        self._region_calls.bind(_AlignmentRegions.DEVICE)
 
     def _h(self):
         if self._al is None or not self._ctx._ctx:

@@ -380,6 +380,12 @@ struct WallRegionAcc {   // 64 B, zero = empty: minima are kept inverted so that
     unsigned long long sum_d, points, peak_key;   // peak_key = min(|d|, 2^32 - 1) << 32 | ~cell
     unsigned long long pad;
 };
+// one element's share of an alignment's window: window rows [row0, row0 + rows) are stations [station0, station0 + rows) of
+// the element map `map` (and of the baseline's map of that element, `base`)
+struct WallRegionPiece {
+    uint32_t row0, station0, rows, pad;
+    WallTable map, base;
+};
 struct WallRegionArgs {
     WallTable map, base;       // base: the baseline's table when has_base
     uint32_t has_base;
@@ -394,10 +400,19 @@ struct WallRegionArgs {
     WallRegionAcc *acc;        // [components]
     gm_wall_region *out;       // [components]: the regions, in the order their slots were taken
     uint32_t ncomp;
+    // gm_wall_alignment_regions (k_wall_regions_joint.hip): the window's pieces in device memory, ascending and gapless over
+    // its rows; n_pieces 0: a map's call (map, base and first are then the map's own).  On an alignment map and base are
+    // not read and first = station0 * nsec is the GLOBAL index of window cell 0.
+    uint32_t n_pieces;
+    const WallRegionPiece *pieces;
 };
 void launch_wall_region_label(const WallRegionArgs &a, hipStream_t s);    // three launches, up to the component count
 void launch_wall_region_reduce(const WallRegionArgs &a, hipStream_t s);   // two launches, up to the region list
 void launch_wall_region_labels(const WallRegionArgs &a, uint64_t first, uint64_t n, int32_t *out, hipStream_t s);
+// k_wall_regions_joint.hip: the two kernels that read a cell, on the pieces (launch_wall_region_label and _reduce launch
+// them in place of the map's when a.n_pieces is not 0)
+void launch_wall_region_tiles_joint(const WallRegionArgs &a, hipStream_t s);
+void launch_wall_region_reduce_joint(const WallRegionArgs &a, hipStream_t s);
 // k_wall_cloud.hip (gm_wall_map_cloud): per chunk of whole block rows merge (unless bs = bk = 1) -> compact + emit
 constexpr int kWallCloudCounters = 4;              // u64: empty, below_min_count, the chunk's points (low word), pad
 constexpr uint32_t kWallCloudAccBytes = 28;        // merged accumulators per block: sum u64 | count u64 | lo, hi, cells u32

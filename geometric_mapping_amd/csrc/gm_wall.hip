@@ -213,6 +213,85 @@ gm_status check_baseline(gm_wall_map *map, gm_wall_map *baseline, const char *wh
     return GM_OK;
 }
 
+}  // namespace
+
+namespace gm {
+namespace wall {
+
+const char *region_prm_refusal(const gm_wall_region_params &p, long long &T)
+{
+    T = 0;
+    if (p.struct_size != sizeof(gm_wall_region_params) || p.min_count < 1u || p.min_cells < 1u || (p.connectivity != 4u && p.connectivity != 8u) ||
+        !(p.threshold > 0.0) || !(p.threshold <= 8.0))
+        return ": struct_size mismatch or a parameter outside its limits";
+    T = (long long)rint(p.threshold * 1048576.0);
+    return T < 1 ? ": the threshold rounds to 0" : nullptr;
+}
+
+gm_status regions_run(gm_ctx *ctx, hipStream_t s, RegionScratch &rg, WallRegionArgs &a, int32_t *stage, uint64_t stage_labels,
+                      gm_wall_regions_info *info, gm_wall_region *regions, uint32_t capacity, uint32_t *n_out, int32_t *cell_labels,
+                      const char *who)
+{
+    const uint64_t total = (uint64_t)a.n * a.nsec;
+    a.ts = rg.ts;
+    a.tk = rg.tk;
+    a.tiles_s = (a.n + a.ts - 1u) / a.ts;
+    a.tiles_k = (a.nsec + a.tk - 1u) / a.tk;
+    GMW_HIP(ctx, rg.cells.reserve(total * (8 + 4 + 4)));
+    GMW_HIP(ctx, rg.ctr.reserve(kWallRegionCounters));
+    Carve cells{rg.cells.p};
+    a.d = cells.take<long long>(total);
+    a.parent = cells.take<uint32_t>(total);
+    a.slot = cells.take<uint32_t>(total);
+    a.ctr = rg.ctr.p;
+    unsigned long long ctr[kWallRegionCounters];
+    GMW_HIP(ctx, hipMemsetAsync(a.ctr, 0, kWallRegionCounters * 8, s));
+    launch_wall_region_label(a, s);
+    GMW_HIP(ctx, hipGetLastError());
+    GMW_HIP(ctx, hipMemcpyAsync(ctr, a.ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
+    GMW_HIP(ctx, hipStreamSynchronize(s));   // the one count the host needs: it sizes the records
+    const uint64_t ncomp = ctr[4];
+    info->flagged_pos = ctr[0]; info->flagged_neg = ctr[1]; info->unusable = ctr[2]; info->empty = ctr[3];
+    info->components = ncomp;
+    uint64_t nreg = 0;
+    if (ncomp) {
+        GMW_HIP(ctx, rg.recs.reserve(ncomp * (sizeof(WallRegionAcc) + sizeof(gm_wall_region))));
+        Carve recs{rg.recs.p};
+        a.acc = recs.take<WallRegionAcc>(ncomp);
+        a.out = recs.take<gm_wall_region>(ncomp);
+        a.ncomp = (uint32_t)ncomp;
+        GMW_HIP(ctx, hipMemsetAsync(a.acc, 0, ncomp * sizeof(WallRegionAcc), s));
+        launch_wall_region_reduce(a, s);
+        GMW_HIP(ctx, hipGetLastError());
+        GMW_HIP(ctx, hipMemcpyAsync(&nreg, a.ctr + 5, 8, hipMemcpyDeviceToHost, s));
+        GMW_HIP(ctx, hipStreamSynchronize(s));
+    }
+    info->regions = nreg;
+    if (n_out) *n_out = (uint32_t)nreg;
+    const bool fits = nreg <= capacity;
+    if (regions && fits && nreg) {
+        GMW_HIP(ctx, hipMemcpyAsync(regions, a.out, nreg * sizeof(gm_wall_region), hipMemcpyDeviceToHost, s));
+        GMW_HIP(ctx, hipStreamSynchronize(s));
+        std::sort(regions, regions + nreg, [](const gm_wall_region &x, const gm_wall_region &y) { return x.label < y.label; });
+    }
+    if (cell_labels) {
+        for (uint64_t done = 0; done < total; done += stage_labels) {
+            const uint64_t c = std::min(stage_labels, total - done);
+            launch_wall_region_labels(a, done, c, stage, s);
+            GMW_HIP(ctx, hipGetLastError());
+            GMW_HIP(ctx, hipMemcpyAsync(cell_labels + done, stage, c * 4, hipMemcpyDeviceToHost, s));
+            GMW_HIP(ctx, hipStreamSynchronize(s));
+        }
+    }
+    if (!fits && (regions || capacity)) return gm_fail(ctx, GM_ERR_CAPACITY, who);
+    return GM_OK;
+}
+
+}  // namespace wall
+}  // namespace gm
+
+namespace {
+
 void free_map(gm_wall_map *m)
 {
     gm_ctx *ctx = m->ctx;
@@ -433,8 +512,8 @@ static gm_status create_map(gm_ctx *ctx, const gm_wall_params *params, const gm_
     if (const char *e = getenv("GM_WALL_REGION_TILE")) {   // <stations>x<sectors>; anything else: the default
         unsigned ts = 0, tk = 0;
         if (sscanf(e, "%ux%u", &ts, &tk) == 2 && ts >= 1u && tk >= 1u && (uint64_t)ts * tk <= kWallRegionTileCells) {
-            m->region_ts = ts;
-            m->region_tk = tk;
+            m->rg.ts = ts;
+            m->rg.tk = tk;
         }
     }
     m->ob.read_tile_env();
@@ -645,11 +724,8 @@ gm_status gm_wall_map_regions(gm_wall_map *map, gm_wall_map *baseline, uint32_t 
     if (n_out) *n_out = 0;
     if (!info) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_regions: NULL info");
     const gm_wall_region_params rp = params_or(prm, gm_wall_region_default_params);
-    if (rp.struct_size != sizeof(gm_wall_region_params) || rp.min_count < 1u || rp.min_cells < 1u ||
-        (rp.connectivity != 4u && rp.connectivity != 8u) || !(rp.threshold > 0.0) || !(rp.threshold <= 8.0))
-        return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_regions: struct_size mismatch or a parameter outside its limits");
-    const long long T = (long long)rint(rp.threshold * 1048576.0);
-    if (T < 1) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_regions: the threshold rounds to 0");
+    long long T = 0;
+    if (const char *why = region_prm_refusal(rp, T)) return gm_fail(ctx, GM_ERR_INVALID_ARG, (std::string("gm_wall_map_regions") + why).c_str());
     if (!regions && capacity) return gm_fail(ctx, GM_ERR_INVALID_ARG, "gm_wall_map_regions: NULL regions with a capacity");
     GMW_OK(check_baseline(map, baseline, "gm_wall_map_regions"));
     GMW_OK(check_window(map, station0, n, ~0ull, nullptr, ""));
@@ -665,7 +741,6 @@ gm_status gm_wall_map_regions(gm_wall_map *map, gm_wall_map *baseline, uint32_t 
     info->cell_area = map->prm.station_length * map->prm.radius * kTwoPi / (double)nsec;
     if (!n) return GM_OK;
 
-    const uint64_t total = (uint64_t)n * nsec;
     WallRegionArgs a;
     memset(&a, 0, sizeof(a));
     a.map = map->table;
@@ -674,64 +749,13 @@ gm_status gm_wall_map_regions(gm_wall_map *map, gm_wall_map *baseline, uint32_t 
     a.n = n;
     a.nsec = nsec;
     a.first = (uint64_t)station0 * nsec;
-    a.ts = map->region_ts;
-    a.tk = map->region_tk;
-    a.tiles_s = (n + a.ts - 1u) / a.ts;
-    a.tiles_k = (nsec + a.tk - 1u) / a.tk;
     a.conn8 = rp.connectivity == 8u ? 1u : 0u;
     a.min_count = rp.min_count;
     a.min_cells = rp.min_cells;
     a.T = T;
-    GMW_HIP(ctx, map->rg_cells.reserve(total * (8 + 4 + 4)));
-    GMW_HIP(ctx, map->rg_ctr.reserve(kWallRegionCounters));
-    Carve cells{map->rg_cells.p};
-    a.d = cells.take<long long>(total);
-    a.parent = cells.take<uint32_t>(total);
-    a.slot = cells.take<uint32_t>(total);
-    a.ctr = map->rg_ctr.p;
-    unsigned long long ctr[kWallRegionCounters];
-    GMW_HIP(ctx, hipMemsetAsync(a.ctr, 0, kWallRegionCounters * 8, map->stream));
-    launch_wall_region_label(a, map->stream);
-    GMW_HIP(ctx, hipGetLastError());
-    GMW_HIP(ctx, hipMemcpyAsync(ctr, a.ctr, sizeof(ctr), hipMemcpyDeviceToHost, map->stream));
-    GMW_HIP(ctx, hipStreamSynchronize(map->stream));   // the one count the host needs: it sizes the records
-    const uint64_t ncomp = ctr[4];
-    info->flagged_pos = ctr[0]; info->flagged_neg = ctr[1]; info->unusable = ctr[2]; info->empty = ctr[3];
-    info->components = ncomp;
-    uint64_t nreg = 0;
-    if (ncomp) {
-        GMW_HIP(ctx, map->rg_recs.reserve(ncomp * (sizeof(WallRegionAcc) + sizeof(gm_wall_region))));
-        Carve recs{map->rg_recs.p};
-        a.acc = recs.take<WallRegionAcc>(ncomp);
-        a.out = recs.take<gm_wall_region>(ncomp);
-        a.ncomp = (uint32_t)ncomp;
-        GMW_HIP(ctx, hipMemsetAsync(a.acc, 0, ncomp * sizeof(WallRegionAcc), map->stream));
-        launch_wall_region_reduce(a, map->stream);
-        GMW_HIP(ctx, hipGetLastError());
-        GMW_HIP(ctx, hipMemcpyAsync(&nreg, a.ctr + 5, 8, hipMemcpyDeviceToHost, map->stream));
-        GMW_HIP(ctx, hipStreamSynchronize(map->stream));
-    }
-    info->regions = nreg;
-    if (n_out) *n_out = (uint32_t)nreg;
-    const bool fits = nreg <= capacity;
-    if (regions && fits && nreg) {
-        GMW_HIP(ctx, hipMemcpyAsync(regions, a.out, nreg * sizeof(gm_wall_region), hipMemcpyDeviceToHost, map->stream));
-        GMW_HIP(ctx, hipStreamSynchronize(map->stream));
-        std::sort(regions, regions + nreg, [](const gm_wall_region &x, const gm_wall_region &y) { return x.label < y.label; });
-    }
-    if (cell_labels) {
-        int32_t *stage = reinterpret_cast<int32_t *>(map->stage.p);   // (kStageCells raw records: room for as many labels)
-        const uint64_t chunk = std::min(kStageCells, map->ncell);
-        for (uint64_t done = 0; done < total; done += chunk) {
-            const uint64_t c = std::min(chunk, total - done);
-            launch_wall_region_labels(a, done, c, stage, map->stream);
-            GMW_HIP(ctx, hipGetLastError());
-            GMW_HIP(ctx, hipMemcpyAsync(cell_labels + done, stage, c * 4, hipMemcpyDeviceToHost, map->stream));
-            GMW_HIP(ctx, hipStreamSynchronize(map->stream));
-        }
-    }
-    if (!fits && (regions || capacity)) return gm_fail(ctx, GM_ERR_CAPACITY, "gm_wall_map_regions: region buffer too small");
-    return GM_OK;
+    // (kStageCells raw records of staging: room for as many labels)
+    return regions_run(ctx, map->stream, map->rg, a, reinterpret_cast<int32_t *>(map->stage.p), std::min(kStageCells, map->ncell), info,
+                       regions, capacity, n_out, cell_labels, "gm_wall_map_regions: region buffer too small");
 }
 
 gm_status gm_wall_map_cloud(gm_wall_map *map, uint32_t station0, uint32_t n, const gm_wall_cloud_params *prm,

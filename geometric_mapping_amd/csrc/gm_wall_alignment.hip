@@ -143,6 +143,8 @@ gm_status gm_wall_alignment_create(gm_ctx *ctx, const gm_wall_params *params, co
     // the per-slot state of the locates, the checks and the aligns (no device memory: vectors of empty owners); the element
     // maps learn where the pending results are
     al->ob.read_tile_env();
+    al->tpl = *params;
+    al->elements.assign(elements, elements + n);
     al->locates.resize(ctx->n_slots);
     al->checks.resize(ctx->n_slots);
     al->aligns.resize(ctx->n_slots);

@@ -1,6 +1,6 @@
 // gm_wall_alignment.hpp -- the wall alignment's object and what its call families share (gm_wall_alignment.hip: create,
 // destroy, map, info, sync and the add; gm_wall_alignment_locate.hip; gm_wall_alignment_check.hip: the check and the checked
-// add; gm_wall_alignment_objects.hip: a check's objects): the plan of a call and its refusals, the sides of a plan as the joint kernels take them, the add's arguments.
+// add; gm_wall_alignment_objects.hip: a check's objects; gm_wall_alignment_regions.hip: the regions of a window): the plan of a call and its refusals, the sides of a plan as the joint kernels take them, the add's arguments.
 #pragma once
 
 #include "gm_wall_joint.hpp"
@@ -63,6 +63,12 @@ struct gm_wall_alignment {
     std::vector<gm::wall::PendingResult> align_res;
     // gm_wall_alignment_check_objects / _rows: the tile and the scratch, allocated by the first call
     gm::wall::ObjectScratch ob;
+    // gm_wall_alignment_regions: the scratch, allocated by the first call (the tile is element map 0's); what a baseline is
+    // compared by: the template and the element list as the create was given them
+    gm::wall::RegionScratch rg;
+    gm::HostArray<gm::WallRegionPiece> rg_pieces_host;   // pinned: the table of the call in progress
+    gm_wall_params tpl;
+    std::vector<gm_wall_element> elements;
     // the checked add's stage call: the uploaded rows and its block
     gm::DevArray<gm_wall_check_point> ac_rows;
     gm::DevArray<unsigned long long> ac_blk;

@@ -1,6 +1,6 @@
 // gm_wall_alignment_host.hip -- the part of the wall alignment's C ABI that needs no device (include/gm_hip.h states the
-// rule): the chaining of the element maps, the joint planes, ownership, project, point, the chainage window and the plan
-// of an add.  Every element is a DesignAxis (gm_wall_map.hpp): its section, project, point and per-add frame are the
+// rule): the chaining of the element maps, the joint planes, ownership, project, point, the chainage window, the plan
+// of an add, and the windows and metrics of the objects and the regions on the global station grid.  Every element is a DesignAxis (gm_wall_map.hpp): its section, project, point and per-add frame are the
 // element map's own, asked of the axis.  Like gm_wall_host.hip it links against libm and the C++ library alone;
 // host/gm_wall_alignment_host_test.cpp runs it under the host sanitizers.
 #include <stddef.h>
@@ -415,6 +415,50 @@ gm_status alignment_object_window(const Alignment &A, const gm_wall_alignment_ad
     return GM_OK;
 }
 
+// gm_wall_alignment_regions' host half (include/gm_hip.h states the rule): the size rule, the window on the global station
+// grid and the elements it meets
+gm_status alignment_region_window(const Alignment &A, uint32_t station0, uint32_t n, gm_wall_alignment_regions_info *info)
+{
+    static_assert(sizeof(gm_wall_alignment_regions_info) == 112 && offsetof(gm_wall_alignment_regions_info, total) == sizeof(gm_wall_regions_info),
+                  "the shared head");
+    if (!info) return GM_ERR_INVALID_ARG;
+    memset(info, 0, sizeof(*info));
+    info->struct_size = (uint32_t)sizeof(gm_wall_alignment_regions_info);
+    if (A.el.empty()) return GM_ERR_INVALID_ARG;
+    const gm_wall_params &t = A.el[0].p;
+    const uint32_t nsec = t.n_sectors;
+    uint64_t total = 0;
+    for (const AlignElem &E : A.el) total += E.p.n_stations;   // (<= 256 * 2^32)
+    if (total * nsec > 0x7FFFFFFFull) return GM_ERR_UNSUPPORTED;   // (nsec <= 4096: no overflow)
+    if ((uint64_t)station0 + n > total) return GM_ERR_INVALID_ARG;
+    if ((uint64_t)n * nsec > GM_WALL_ALIGNMENT_REGION_MAX_CELLS) return GM_ERR_UNSUPPORTED;
+    info->station0 = station0;
+    info->n_stations = n;
+    info->n_sectors = nsec;
+    // (one operation per statement, as gm_wall_region_metrics derives it)
+    const double sr = t.station_length * t.radius;
+    const double ring = sr * kTwoPi;
+    info->cell_area = ring / (double)nsec;
+    info->total = (int64_t)total;
+    if (!n) return GM_OK;
+    const uint64_t last = (uint64_t)station0 + n - 1u;
+    uint64_t base = 0;
+    for (uint32_t i = 0; i < (uint32_t)A.el.size(); ++i) {
+        const uint64_t next = base + A.el[i].p.n_stations;
+        if (station0 >= base && station0 < next) {
+            info->element_from = i;
+            info->station_from = (uint32_t)(station0 - base);
+        }
+        if (last >= base && last < next) {
+            info->element_to = i;
+            info->station_to = (uint32_t)(last - base);
+        }
+        base = next;
+    }
+    info->n_pieces = info->element_to - info->element_from + 1u;
+    return GM_OK;
+}
+
 }  // namespace wall
 }  // namespace gm
 
@@ -548,6 +592,65 @@ gm_status gm_wall_alignment_object_metrics(const gm_wall_params *params, const g
         }
         base = next;
     }
+    return GM_OK;
+}
+
+gm_status gm_wall_alignment_region_window(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n_el,
+                                          uint32_t station0, uint32_t n, gm_wall_alignment_regions_info *info)
+{
+    Alignment A;
+    if (!info) return GM_ERR_INVALID_ARG;
+    GMW_OK(alignment_build(params, elements, n_el, A));
+    return alignment_region_window(A, station0, n, info);
+}
+
+gm_status gm_wall_alignment_region_metrics(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n_el,
+                                           const gm_wall_region *r, struct gm_wall_alignment_region_metrics *out)
+{
+    static_assert(sizeof(struct gm_wall_alignment_region_metrics) == 120 &&
+                      offsetof(struct gm_wall_alignment_region_metrics, element_from) == sizeof(struct gm_wall_region_metrics),
+                  "the shared head");
+    Alignment A;
+    if (!r || !out) return GM_ERR_INVALID_ARG;
+    GMW_OK(alignment_build(params, elements, n_el, A));
+    struct gm_wall_region_metrics head;
+    GMW_OK(gm_wall_region_metrics(params, r, &head));   // (the template's t_min, station_length, radius and n_sectors)
+    const uint32_t nsec = params->n_sectors;
+    uint64_t total = 0;
+    for (const AlignElem &E : A.el) total += E.p.n_stations;
+    const uint64_t Gp = r->peak_cell / nsec;
+    const uint32_t kp = r->peak_cell % nsec;
+    if ((uint64_t)r->station_max >= total || Gp >= total) return GM_ERR_INVALID_ARG;   // (station_min <= station_max: the head's refusal)
+    memset(out, 0, sizeof(*out));
+    memcpy(out, &head, sizeof(head));
+    uint64_t base = 0;
+    for (uint32_t i = 0; i < n_el; ++i) {
+        const uint64_t next = base + A.el[i].p.n_stations;
+        if (r->station_min >= base && r->station_min < next) {
+            out->element_from = i;
+            out->station_from = (uint32_t)(r->station_min - base);
+        }
+        if (r->station_max >= base && r->station_max < next) {
+            out->element_to = i;
+            out->station_to = (uint32_t)(r->station_max - base);
+        }
+        if (Gp >= base && Gp < next) {
+            out->peak_element = i;
+            out->peak_station = (uint32_t)(Gp - base);
+        }
+        base = next;
+    }
+    out->peak_sector = kp;
+    // (one operation per statement: the same roundings as the twin's, whatever the compiler may contract)
+    const double gc = (double)Gp + 0.5;
+    const double along = gc * params->station_length;
+    const double chainage = params->t_min + along;
+    const double kc = (double)kp + 0.5;
+    const double turn = kTwoPi * kc;
+    const double angle = turn / (double)nsec;
+    const double peak_m = (double)r->peak * 0x1p-20;
+    const double rho = params->radius + peak_m;
+    alignment_point(A, chainage, angle, rho, out->peak_point);
     return GM_OK;
 }
 

@@ -165,6 +165,12 @@ bool object_window(uint64_t n_stations, uint32_t n_sectors, const gm_wall_object
 // side_element, side_first; everything else 0.
 gm_status alignment_object_window(const Alignment &A, const gm_wall_alignment_add_info &plan, const gm_wall_object_params &op,
                                   ObjectWindow &w, gm_wall_alignment_objects_info *info);
+// gm_wall_alignment_regions: the window [station0, station0 + n) on the global station grid.  Refusals in their order:
+// GM_ERR_UNSUPPORTED (total n_sectors beyond 2^31 - 1), GM_ERR_INVALID_ARG (a window outside [0, total]), GM_ERR_UNSUPPORTED
+// (more than GM_WALL_ALIGNMENT_REGION_MAX_CELLS cells).  info: struct_size, the window fields, cell_area, total, n_pieces
+// and the element and station fields; everything else 0.  The pieces are the consecutive elements element_from ..
+// element_to, whole but for the first station of the first and the last of the last.
+gm_status alignment_region_window(const Alignment &A, uint32_t station0, uint32_t n, gm_wall_alignment_regions_info *info);
 bool add_checked_prm_ok(const gm_wall_add_checked_params &p, long long &S);   // S of an accepted block
 // The selection half of the align rule of include/gm_hip.h from a table of (2A + 1)(2B + 1) records on a grid of station
 // length ds and nsec sectors: everything of info but the device's counts, anchor_station and the pose (NaN when it returns
@@ -367,6 +373,26 @@ gm_status objects_run(gm_ctx *ctx, hipStream_t s, ObjectScratch &ob, const Objec
                       const ObjectWindow &win, gm_wall_objects_info *info, uint32_t *side_rows, gm_wall_object *objects,
                       uint32_t capacity, uint32_t *n_out, int32_t *object_of_row, const char *who);
 
+// gm_wall_map_regions and gm_wall_alignment_regions: the tile (GM_WALL_REGION_TILE: tests, measurements) and the scratch of
+// their owner, a map or an alignment; allocated on first use
+struct RegionScratch {
+    uint32_t ts = GM_WALL_REGION_TILE_STATIONS, tk = GM_WALL_REGION_TILE_SECTORS;
+    DevArray<uint8_t> cells;                 // per window cell: d i64 | parent u32 | slot u32
+    DevArray<unsigned long long> ctr;        // [kWallRegionCounters]
+    DevArray<uint8_t> recs;                  // per component: WallRegionAcc | gm_wall_region
+    DevArray<WallRegionPiece> pieces;        // an alignment's call: the window's pieces
+};
+// The region call on a window of a.n stations (>= 1), on stream `s`, blocking.  a: the window, the grid, the parameters
+// and what the cells are read from (the map's tables, or an alignment's pieces, already on the device); the tile, the
+// scratch and the counts are filled in here.  stage: device room for stage_labels labels, a chunk of cell_labels.  info:
+// the fields gm_wall_regions_info and gm_wall_alignment_regions_info share; the classes, components and regions are
+// written, the rest is the caller's.  regions / cell_labels may be NULL; `who`: the failure of a list that does not fit.
+gm_status regions_run(gm_ctx *ctx, hipStream_t s, RegionScratch &rg, WallRegionArgs &a, int32_t *stage, uint64_t stage_labels,
+                      gm_wall_regions_info *info, gm_wall_region *regions, uint32_t capacity, uint32_t *n_out, int32_t *cell_labels,
+                      const char *who);
+// gm_wall_map_regions' parameter rule: NULL and T of an accepted block, or why it is refused (to follow the call's name)
+const char *region_prm_refusal(const gm_wall_region_params &p, long long &T);
+
 }  // namespace wall
 }  // namespace gm
 
@@ -386,11 +412,8 @@ struct gm_wall_map {
     gm::DevArray<uint8_t> stage;   // device staging of the window calls, kStageCells records
     gm::wall::PointOutputs pt;     // the stage calls' per-point outputs: gm_wall_map_add_points', gm_wall_map_check_points'
     uint32_t points_per_block = 0; // 0: the kernel's default (GM_WALL_POINTS_PER_BLOCK: measurements)
-    // gm_wall_map_regions: the tile (GM_WALL_REGION_TILE: tests, measurements) and the scratch
-    uint32_t region_ts = GM_WALL_REGION_TILE_STATIONS, region_tk = GM_WALL_REGION_TILE_SECTORS;
-    gm::DevArray<uint8_t> rg_cells;    // per window cell: d i64 | parent u32 | slot u32
-    gm::DevArray<unsigned long long> rg_ctr;   // [kWallRegionCounters]
-    gm::DevArray<uint8_t> rg_recs;     // per component: WallRegionAcc | gm_wall_region
+    // gm_wall_map_regions: the tile (read at the create) and the scratch
+    gm::wall::RegionScratch rg;
     // gm_wall_map_cloud: the chunk (GM_WALL_CLOUD_CHUNK: tests, measurements; 0: kStageCells blocks) and the scratch
     uint32_t cloud_chunk = 0;
     gm::DevArray<uint8_t> cl_acc;      // merged accumulators of a chunk, kWallCloudAccBytes per block (a merging call only)

@@ -465,6 +465,21 @@ std::vector<gm_wall_object> Processor::wallAlignmentCheckObjects(const gm_wall_o
     return objects;
 }
 
+std::vector<gm_wall_region> Processor::wallAlignmentRegions(const gm_wall_region_params &prm, uint32_t station0, uint32_t n,
+                                                            gm_wall_alignment_regions_info *info)
+{
+    if (!alignment_) throw Error(GM_ERR_NOT_READY, "wallAlignmentRegions: createWallAlignment first");
+    gm_wall_alignment_regions_info local;
+    gm_wall_alignment_regions_info *ip = info ? info : &local;
+    uint32_t count = 0;
+    check(gm_wall_alignment_regions(alignment_, 0, station0, n, &prm, ip, 0, 0, &count, 0), "wallAlignmentRegions");
+    std::vector<gm_wall_region> regions(count);
+    if (count)
+        check(gm_wall_alignment_regions(alignment_, 0, station0, n, &prm, ip, &regions[0], count, &count, 0), "wallAlignmentRegions");
+    regions.resize(count);
+    return regions;
+}
+
 gm_wall_alignment_add_info Processor::addToWallAlignmentChecked(const double pose[12], const gm_wall_add_checked_params &prm,
                                                                 gm_wall_add_checked_info *info)
 {

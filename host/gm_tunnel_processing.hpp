@@ -263,6 +263,11 @@ public:
     // (gm_wall_alignment_object_metrics gives the chainage and the elements).  The order per frame on an alignment:
     // locateWallAlignment, alignWallAlignment, checkWallAlignment, wallAlignmentCheckObjects, addToWallAlignmentChecked.
     std::vector<gm_wall_object> wallAlignmentCheckObjects(const gm_wall_object_params &prm, gm_wall_alignment_objects_info *info = nullptr);
+    // the connected deviation regions of the alignment's global stations [station0, station0 + n)
+    // (gm_wall_alignment_regions, without a baseline): wallRegions across joints -- a region that lies across a joint plane
+    // is one record, with global stations and global cell indices; ascending by label.  A count query, then the sized call.
+    std::vector<gm_wall_region> wallAlignmentRegions(const gm_wall_region_params &prm, uint32_t station0, uint32_t n,
+                                                     gm_wall_alignment_regions_info *info = nullptr);
     gm_wall_alignment *wallAlignment() { return alignment_; }
 
     gm_ctx *ctx() { return ctx_; }

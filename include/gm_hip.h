@@ -2550,6 +2550,94 @@ gm_status gm_wall_alignment_object_metrics(const gm_wall_params *params, const g
                                            const gm_wall_object_params *op, const gm_wall_object *o,
                                            struct gm_wall_alignment_object_metrics *out);
 
+/* ---- connected deviation regions of a wall alignment (gm_wall_alignment_regions) ------------------------------------------
+ * gm_wall_map_regions on the alignment: the same parameters (gm_wall_region_params), the same 64-byte record
+ * (gm_wall_region), on a window of the alignment's GLOBAL station grid, so that a patch of overbreak or an intrusion that
+ * lies across a joint plane is ONE region with one label, one min_cells test, its whole volume and its one peak.
+ *   global station  base_i, G = base_i + j and total as in the align and the objects sections above.
+ *   window        the global stations [station0, station0 + n), inside [0, total]; n = 0 gives no regions and launches
+ *                 nothing.
+ *   size          GM_ERR_UNSUPPORTED if total n_sectors > 2^31 - 1 (labels are global cell indices G n_sectors + k, and
+ *                 cell_labels is int32 with -1 for none) or if the window holds more than
+ *                 GM_WALL_ALIGNMENT_REGION_MAX_CELLS cells (1 GiB of scratch at 16 B per cell).
+ *   rule          gm_wall_map_regions', word for word, on a virtual map of `total` stations: d, the classes, the sign, 4-
+ *                 and 8-connectivity, the wrap around the ring, min_cells, the peak and its tie rule, the record and the
+ *                 ascending label order.  Cell (G, k) of the virtual map is cell (G - base_e, k) of the map of the element
+ *                 e that owns station G.
+ *   record        label and peak_cell are global cell indices, station_min and station_max global stations.  The sector
+ *                 extents are continuous across joints because (u, v) turns rigidly with the section.
+ *   baseline      (may be NULL) another alignment of the same context whose template parameters (but for gate and the
+ *                 unused n_stations) and whose element list (kind, n_stations, turn, curvature, rate) equal this
+ *                 alignment's bit for bit; cell (G, k) of the baseline is read beside cell (G, k).
+ * The rule has no floating point and never sees the axis, so the result is what gm_wall_map_regions gives on ONE straight
+ * map of `total` stations fed the element maps' raw cells concatenated in element order -- byte for byte wherever such a map
+ * can exist (total n_sectors <= 2^24); the pieces are read where they lie so that the call also works where none can.  A
+ * window inside element 0 gives that element map's gm_wall_map_regions bytes; a window inside element i the same records
+ * with label and peak_cell shifted by base_i n_sectors and the station extents by base_i.
+ * On the device: gm_wall_map_regions' launches; the two kernels that read a cell (tiles, reduce) are joint instantiations
+ * of the map's code behind a table of the window's pieces in device memory, the others are the map's own. */
+#define GM_WALL_ALIGNMENT_REGION_MAX_CELLS (1u << 26)   /* the most cells of a window */
+
+typedef struct gm_wall_alignment_regions_info {   /* 112 bytes; the first 80 are gm_wall_regions_info's */
+    uint32_t struct_size;     /* = sizeof(gm_wall_alignment_regions_info), filled by the library */
+    uint32_t station0, n_stations, n_sectors;   /* the window in GLOBAL stations and the template's sectors */
+    int64_t  threshold_q;     /* T */
+    uint64_t flagged_pos, flagged_neg, unusable, empty;
+    uint64_t components;
+    uint64_t regions;
+    double   cell_area;       /* station_length * radius * 2 pi / n_sectors of the template, m^2 */
+    int64_t  total;           /* the alignment's stations */
+    uint32_t n_pieces;        /* the elements the window meets: element_from .. element_to, consecutive (0: n = 0) */
+    uint32_t element_from, element_to;
+    uint32_t station_from;    /* the window's first station inside element_from */
+    uint32_t station_to;      /* the window's last station inside element_to, inclusive */
+    uint32_t reserved;        /* 0 */
+} gm_wall_alignment_regions_info;
+
+/* (a struct tag only, no typedef: the function of the same name below fills it) */
+struct gm_wall_alignment_region_metrics {   /* 120 bytes; the first 64 are gm_wall_region_metrics' */
+    double area_m2;
+    double volume_m3;
+    double peak_m;
+    double mean_m;
+    double chainage_from;           /* t_min + station_min * station_length, alignment chainage */
+    double chainage_to;             /* t_min + (station_max + 1) * station_length */
+    double angle_from_deg;
+    double angle_to_deg;
+    uint32_t element_from, element_to;   /* the elements of station_min and of station_max */
+    uint32_t station_from, station_to;   /* those stations inside them: station_min - base_from, station_max - base_to */
+    uint32_t peak_element, peak_station, peak_sector;   /* of peak_cell: G_p = peak_cell / n_sectors = base + peak_station, k_p */
+    uint32_t reserved;              /* 0 */
+    double peak_point[3];           /* gm_wall_alignment_point at chainage t_min + (G_p + 0.5) station_length, angle
+                                       (2 pi (k_p + 0.5)) / n_sectors and rho = radius + peak 2^-20 (every operation rounded
+                                       once): where to send someone */
+};
+
+/* The regions of the window, ascending by label.  Synchronises every element map the window meets and the baseline's (as
+ * gm_wall_map_sync: it sees every add enqueued before it, through the alignment or through an element map), runs on the
+ * device and blocks.  prm NULL: the defaults.  info is required; count queries, GM_ERR_CAPACITY, *n_out, cell_labels
+ * ([n][n_sectors]) and the NULL rules are gm_wall_map_regions'.  No map is changed.  Scratch (gm_wall_map_regions' amounts
+ * and 96 B per piece) belongs to the alignment: allocated by the first call, kept grow-only, freed with the alignment; an
+ * alignment that never asks allocates nothing.  The tile is element map 0's (GM_WALL_REGION_TILE, read at its create) and
+ * changes nothing in the result.
+ * GM_ERR_UNSUPPORTED: the size rule.  GM_ERR_INVALID_ARG: as gm_wall_map_regions, a window outside [0, total], a baseline
+ * that is the alignment itself, of another context, on another template or with another element list. */
+gm_status gm_wall_alignment_regions(gm_wall_alignment *alignment, gm_wall_alignment *baseline, uint32_t station0, uint32_t n,
+                                    const gm_wall_region_params *prm, gm_wall_alignment_regions_info *info, gm_wall_region *regions,
+                                    uint32_t capacity, uint32_t *n_out, int32_t *cell_labels);
+/* Host only, no context: an info's window fields (station0, n_stations, n_sectors, cell_area, total, n_pieces and the four
+ * element and station fields) exactly as the device call reports them (threshold_q and the counts stay 0).  Refusals: the
+ * alignment's and the window's (GM_ERR_INVALID_ARG), the size rule (GM_ERR_UNSUPPORTED; its first arm is tested before the
+ * window, its second behind it). */
+gm_status gm_wall_alignment_region_window(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n_el,
+                                          uint32_t station0, uint32_t n, gm_wall_alignment_regions_info *info);
+/* Host only: gm_wall_region_metrics' derivation for a record on the global grid, with the template's t_min, station_length,
+ * radius and n_sectors, the elements and the stations inside them of the record's two station extents and of its peak cell,
+ * and the design position of the peak.  GM_ERR_INVALID_ARG: NULL, the alignment's refusals, gm_wall_region_metrics'
+ * refusals, a station extent or a peak cell outside [0, total). */
+gm_status gm_wall_alignment_region_metrics(const gm_wall_params *params, const gm_wall_element *elements, uint32_t n_el,
+                                           const gm_wall_region *r, struct gm_wall_alignment_region_metrics *out);
+
 /* "Compressed map" record of a completed slot.  The reference defines no such
  * output; this is a build-defined format: header, primitive records,
  * then n_voxels rows of x,y,z,count (float32).  Returns the bytes needed in
