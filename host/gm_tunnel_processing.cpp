@@ -12,7 +12,8 @@ void Processor::check(gm_status s, const char *what)
 }
 
 Processor::Processor(double b, double leaf, double r, double wf, int device, unsigned flags)
-    : ctx_(0), grp_(0), cur_(0), cur_slot_(0), n_slots_(1), next_slot_(0), pending_(0), wall_(0), alignment_(0), newest_slot_(-1), check_slot_(-1), al_check_slot_(-1)
+    : ctx_(0), grp_(0), cur_(0), cur_slot_(0), n_slots_(1), next_slot_(0), pending_(0), wall_(0), alignment_(0), newest_slot_(-1), check_slot_(-1), al_check_slot_(-1),
+      submitted_(0), waited_(0)
 {
     gm_config cfg;
     gm_default_config(&cfg);
@@ -27,7 +28,7 @@ Processor::Processor(double b, double leaf, double r, double wf, int device, uns
 Processor::Processor(double b, double leaf, double r, double wf, const std::vector<int> &devices, unsigned flags,
                      unsigned slots_per_device)
     : ctx_(0), grp_(0), cur_(0), cur_slot_(0), n_slots_(slots_per_device ? slots_per_device : 1), next_slot_(0), pending_(0), wall_(0), alignment_(0),
-      newest_slot_(-1), check_slot_(-1), al_check_slot_(-1)
+      newest_slot_(-1), check_slot_(-1), al_check_slot_(-1), submitted_(0), waited_(0)
 {
     if (devices.empty()) throw Error(GM_ERR_INVALID_ARG, "Processor: empty device list");
     gm_config cfg;
@@ -35,7 +36,12 @@ Processor::Processor(double b, double leaf, double r, double wf, const std::vect
     cfg.boxFilterBound = b; cfg.voxelGridLeafSize = leaf; cfg.neighborRadius = r; cfg.weightingFactor = wf;
     cfg.flags = flags; cfg.n_slots = n_slots_;
     std::vector<int32_t> dev(devices.begin(), devices.end());
-    gm_status s = gm_group_create(&cfg, &dev[0], (uint32_t)dev.size(), 0u, &grp_);
+    // a device listed twice ("0,0": two ranks that stream on one GPU) needs the group's loopback flag; streaming has no
+    // collective, so nothing else changes
+    bool repeats = false;
+    for (size_t a = 0; a < dev.size(); ++a)
+        for (size_t c = a + 1; c < dev.size(); ++c) repeats = repeats || dev[a] == dev[c];
+    gm_status s = gm_group_create(&cfg, &dev[0], (uint32_t)dev.size(), repeats ? GM_GROUP_LOOPBACK : 0u, &grp_);
     if (s != GM_OK) throw Error(s, std::string("gm_group_create: ") + gm_group_last_error(0));
     ctx_ = gm_group_ctx(grp_, 0);
     cur_ = ctx_;
@@ -45,8 +51,10 @@ Processor::Processor(double b, double leaf, double r, double wf, const std::vect
 Processor::~Processor()
 {
     for (size_t i = 0; i < cloud_bufs_.size(); ++i) {   // (gm_set_cloud_output waits for a frame that still writes the rows)
-        gm_set_cloud_output(cloud_bufs_[i].ctx, cloud_bufs_[i].slot, 0, 0);
-        gm_host_free(cloud_bufs_[i].ctx, cloud_bufs_[i].rows);
+        CloudBuf &b = cloud_bufs_[i];
+        gm_set_cloud_output(b.ctx, b.slot, 0, 0);
+        if (b.rows) gm_host_free(b.ctx, b.rows);
+        for (size_t k = 0; k < b.retired.size(); ++k) gm_host_free(b.ctx, b.retired[k].rows);
     }
     if (grp_) gm_group_destroy(grp_);   // (owns the contexts)
     else gm_destroy(ctx_);
@@ -58,15 +66,33 @@ void Processor::enableCloudOutput(unsigned max_points)
         const unsigned ranks = grp_ ? gm_group_size(grp_) : 1u;
         for (unsigned r = 0; r < ranks; ++r)
             for (unsigned s = 0; s < n_slots_; ++s) {
-                CloudBuf b = {grp_ ? gm_group_ctx(grp_, r) : ctx_, s, 0, 0u};
+                CloudBuf b;
+                b.ctx = grp_ ? gm_group_ctx(grp_, r) : ctx_; b.slot = s; b.rows = 0; b.cap = 0u; b.since = 0;
                 cloud_bufs_.push_back(b);
             }
     }
     growCloudOutput(max_points ? max_points : 1u);
 }
 
+// Retired rows received the slot's frames below the `since` of the rows that replaced them.  Frames leave in submission
+// order and the accessors read frame waited_ - 1, so once that frame is one of the replacement's, none of the retired
+// rows' frames is in flight or can still be read.
+void Processor::freeRetiredCloudRows()
+{
+    for (size_t i = 0; i < cloud_bufs_.size(); ++i) {
+        CloudBuf &b = cloud_bufs_[i];
+        while (!b.retired.empty()) {
+            const unsigned long long replaced_at = b.retired.size() > 1 ? b.retired[1].since : b.since;
+            if (waited_ <= replaced_at) break;
+            gm_host_free(b.ctx, b.retired[0].rows);
+            b.retired.erase(b.retired.begin());
+        }
+    }
+}
+
 void Processor::growCloudOutput(unsigned n_points)
 {
+    freeRetiredCloudRows();
     for (size_t i = 0; i < cloud_bufs_.size(); ++i) {
         CloudBuf &b = cloud_bufs_[i];
         if (b.cap >= n_points) continue;
@@ -76,8 +102,13 @@ void Processor::growCloudOutput(unsigned n_points)
         if (s != GM_OK) throw Error(s, std::string("enableCloudOutput: ") + gm_last_error(b.ctx));
         s = gm_set_cloud_output(b.ctx, b.slot, (float *)rows, cap);   // (waits for the slot's frame in flight, if any)
         if (s != GM_OK) { gm_host_free(b.ctx, rows); throw Error(s, std::string("enableCloudOutput: ") + gm_last_error(b.ctx)); }
-        if (b.rows) gm_host_free(b.ctx, b.rows);
-        b.rows = (float *)rows; b.cap = cap;
+        // A frame in flight, or the finished frame the accessors refer to, may have written its cloud into the old rows:
+        // they are retired, not freed, unless no frame was submitted since they were set.
+        if (b.rows) {
+            if (b.since == submitted_) gm_host_free(b.ctx, b.rows);
+            else { const CloudRows old = {b.rows, b.since}; b.retired.push_back(old); }
+        }
+        b.rows = (float *)rows; b.cap = cap; b.since = submitted_;
     }
 }
 
@@ -91,6 +122,7 @@ void Processor::submitFrame(const void *rows, unsigned n, unsigned step, unsigne
     if (grp_) {
         gm_status s = gm_group_submit_frame(grp_, &c);
         if (s != GM_OK) throw Error(s, std::string("submitFrame: ") + gm_group_last_error(grp_));
+        ++submitted_;
         return;
     }
     if (pending_ >= n_slots_) throw Error(GM_ERR_NOT_READY, "submitFrame: every slot holds a frame (waitFrame first)");
@@ -98,6 +130,7 @@ void Processor::submitFrame(const void *rows, unsigned n, unsigned step, unsigne
     newest_slot_ = (int)next_slot_;
     next_slot_ = (next_slot_ + 1) % n_slots_;
     ++pending_;
+    ++submitted_;
 }
 
 gm_frame_result Processor::waitFrame()
@@ -105,6 +138,8 @@ gm_frame_result Processor::waitFrame()
     gm_frame_result r;
     if (grp_) {
         uint32_t rank = 0, slot = 0;
+        if (!gm_group_in_flight(grp_)) throw Error(GM_ERR_NOT_READY, "waitFrame: no frame in flight");
+        ++waited_;   // (the frame leaves the queue whatever the wait returns)
         gm_status s = gm_group_wait_frame(grp_, &r, &rank, &slot);
         if (s != GM_OK) throw Error(s, std::string("waitFrame: ") + gm_group_last_error(grp_));
         cur_ = gm_group_ctx(grp_, rank);
@@ -115,6 +150,7 @@ gm_frame_result Processor::waitFrame()
     if (!pending_) throw Error(GM_ERR_NOT_READY, "waitFrame: no frame in flight");
     const unsigned slot = (next_slot_ + n_slots_ - pending_) % n_slots_;   // the oldest
     --pending_;   // (the frame leaves the queue whatever the wait returns: a failed frame must not be waited for again)
+    ++waited_;
     check(gm_wait_frame(ctx_, slot, &r), "waitFrame");
     cur_ = ctx_; cur_slot_ = slot;
     last_ = r;
@@ -205,6 +241,7 @@ gm_frame_result Processor::processFrame(const void *rows, unsigned n, unsigned s
     gm_cloud c = {rows, n, step, ox, oy, oz, bigendian ? GM_CLOUD_BIGENDIAN : 0u};
     if (!cloud_bufs_.empty()) growCloudOutput(n);
     gm_frame_result r;
+    ++submitted_; ++waited_;   // (submitted and waited for in one call)
     check(gm_process_frame(ctx_, &c, &r), "processFrame");
     cur_ = ctx_; cur_slot_ = 0;
     newest_slot_ = 0;
@@ -216,9 +253,14 @@ PointCloud Processor::choppedCloud()
 {
     for (size_t i = 0; i < cloud_bufs_.size(); ++i) {   // the rows are already on the host (enableCloudOutput)
         const CloudBuf &b = cloud_bufs_[i];
-        if (b.ctx != cur_ || b.slot != cur_slot_ || !b.rows) continue;
+        if (b.ctx != cur_ || b.slot != cur_slot_ || !b.rows || !waited_) continue;
+        // the rows the frame wrote into: those set last before it was submitted (replaced since, if a larger frame came)
+        const unsigned long long frame = waited_ - 1;
+        const float *rows = b.rows;
+        if (frame < b.since)
+            for (size_t k = b.retired.size(); k-- > 0;) { rows = b.retired[k].rows; if (b.retired[k].since <= frame) break; }
         PointCloud out(last_.n_valid);
-        if (last_.n_valid) std::memcpy(&out[0].x, b.rows, (size_t)last_.n_valid * sizeof(PointXYZ));
+        if (last_.n_valid) std::memcpy(&out[0].x, rows, (size_t)last_.n_valid * sizeof(PointXYZ));
         return out;
     }
     uint32_t n = 0;

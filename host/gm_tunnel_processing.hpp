@@ -78,7 +78,8 @@ public:
     bool tryWaitFrame(gm_frame_result &result);
     // /choppedCloud straight into page-locked host rows (gm_set_cloud_output): one buffer per slot of every device, each
     // with room for max_points rows (grown when a larger frame is submitted).  The copy overlaps the tail of the frame;
-    // choppedCloud() then reads those rows instead of fetching the cloud from the device.
+    // choppedCloud() then reads those rows instead of fetching the cloud from the device.  Rows replaced by a growth stay
+    // allocated while a frame that wrote into them is in flight or is the frame the accessors refer to.
     void enableCloudOutput(unsigned max_points);
 
     // ---- tunnel_processing.hpp:38-54 ----
@@ -285,9 +286,15 @@ private:
     int newest_slot_;                          // slot of the frame submitted last (-1: none yet)
     int check_slot_;                           // the slot of the last checkWallMap, -1 before it
     int al_check_slot_;                        // the slot of the last checkWallAlignment, -1 before it
-    struct CloudBuf { gm_ctx *ctx; unsigned slot; float *rows; unsigned cap; };
-    std::vector<CloudBuf> cloud_bufs_;         // enableCloudOutput: one per (device, slot)
+    // enableCloudOutput: one per (device, slot).  `rows` receive the slot's frames from number `since` on (frames are
+    // numbered in submission order, which is the order they are waited for in).  Rows that were replaced while a frame that
+    // wrote into them could still be read are kept in `retired`, oldest first, and freed by a later growCloudOutput.
+    struct CloudRows { float *rows; unsigned long long since; };
+    struct CloudBuf { gm_ctx *ctx; unsigned slot; float *rows; unsigned cap; unsigned long long since; std::vector<CloudRows> retired; };
+    std::vector<CloudBuf> cloud_bufs_;
+    unsigned long long submitted_, waited_;    // frames handed to the library / taken back from it (the accessors' frame: waited_ - 1)
     void growCloudOutput(unsigned n_points);
+    void freeRetiredCloudRows();
     Processor(const Processor &);
     Processor &operator=(const Processor &);
 };

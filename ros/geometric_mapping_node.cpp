@@ -18,9 +18,11 @@
 // and replaces the PCL/Eigen arithmetic of cloud_cb (:48-125) with ONE call into
 // the C ABI (gm_process_frame reads the PointCloud2 rows directly: no pcl::fromROSMsg).
 //
-// ROS is absent from the build image: here the node is only TYPE-CHECKED against minimal
-// stand-in headers (tests/stubs/, tests/test_ros_node_compiles.py).  Build it for real in a catkin workspace with
-// ros/CMakeLists.txt.
+// ROS is absent from the build image.  Here the node is type-checked against minimal stand-in
+// headers (tests/stubs/, tests/test_ros_node_compiles.py) and RUN against a recording stand-in (tests/ros_recorder/: the
+// parameters from a file, a script of messages and timer firings in place of ros::spin(), every published message logged;
+// host/Makefile builds gm_ros_node_recorded, tests/test_gpu_ros_node.py pins what it publishes).  Build it for real in a
+// catkin workspace with ros/CMakeLists.txt.
 // Deliberate differences from the reference, all on non-default paths:
 //   * usePCLViz is accepted and ignored with a warning (the reference stores the
 //     address of a block-local PCLVisualizer: dangling, src/geometric_mapping.cpp:140-143);
@@ -48,6 +50,7 @@
 #include <visualization_msgs/MarkerArray.h>
 
 #include <algorithm>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
@@ -164,6 +167,10 @@ void publish_frame(const gm_frame_result &r, const std_msgs::Header &header)
         }
         out.data.resize((size_t)out.row_step);
         if (!cloud.empty()) std::memcpy(&out.data[0], &cloud[0], out.data.size());
+        // bytes 12..15 of a point: pcl::PointXYZ's padding word is 1.0f and pcl::toROSMsg copies whole points (:103), so
+        // the reference publishes 1.0f there; the library's rows carry the input row index in that word (gm_hip.h)
+        const float one = 1.0f;
+        for (size_t i = 0; i < cloud.size(); ++i) std::memcpy(&out.data[16 * i + 12], &one, 4);
         cloudPub.publish(out);
     }
     if (params->rvizNormals)  // :109-112: centroids + nearest normals were produced inside the frame (GM_CFG_NEAREST)
@@ -209,6 +216,16 @@ void cloud_cb(const sensor_msgs::PointCloud2ConstPtr &input)
     unsigned ox = 0, oy = 4, oz = 8;
     if (!find_xyz(*input, ox, oy, oz)) { ROS_ERROR("input cloud has no float32 x/y/z fields"); return; }
     const unsigned n = input->width * input->height;
+    {   // the data vector must hold what width, height, point_step and row_step say: below, the rows are read as they stand
+        // (sensor_msgs/PointCloud2: data holds height rows of row_step bytes; a cloud of one row is read as width points)
+        const uint64_t row = (uint64_t)input->width * input->point_step;
+        const uint64_t need = input->height > 1 ? (uint64_t)input->height * input->row_step : row;
+        if (n && ((input->height > 1 && input->row_step < row) || input->data.size() < need)) {
+            ROS_ERROR("input cloud is malformed: %lu data bytes for %u x %u points of %u bytes (row_step %u)",
+                      (unsigned long)input->data.size(), input->height, input->width, input->point_step, input->row_step);
+            return;
+        }
+    }
     // fromROSMsg + chopCloud + getNormals + VoxelGrid + getLocalFrame: one device pass (:55-92)
     const unsigned char *rows = n ? &input->data[0] : nullptr;
     std::vector<unsigned char> packed;
@@ -224,13 +241,17 @@ void cloud_cb(const sensor_msgs::PointCloud2ConstPtr &input)
     if (params->devices.size() > 1) {
         // streaming: publish what has finished, make room if every slot is taken, hand the frame to the next device
         publish_finished(false);
-        try {
-            if (proc->inFlight() >= proc->capacity() && !headers.empty()) {
-                const std_msgs::Header h = headers.front();
-                headers.pop_front();                       // (waitFrame takes the frame off the queue, also when it throws)
+        if (proc->inFlight() >= proc->capacity() && !headers.empty()) {
+            const std_msgs::Header h = headers.front();
+            headers.pop_front();                       // (waitFrame takes the frame off the queue, also when it throws)
+            try {
                 const gm_frame_result r = proc->waitFrame();
                 publish_frame(r, h);
+            } catch (const gm_host::Error &e) {        // the old frame is dropped with its header; the new one is still submitted
+                ROS_ERROR("libgm_hip: %s", e.what());
             }
+        }
+        try {
             proc->submitFrame(rows, n, input->point_step, ox, oy, oz, input->is_bigendian);
             headers.push_back(input->header);
         } catch (const gm_host::Error &e) {
